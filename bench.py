@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- decode throughput of the MI355X-native Llama-2-7B hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the outputs of the last
+timed step if --dump-outputs is given, the result line.  --full adds every side measurement (the keys listed below,
+the other formats / sizes under `extra`, the device peaks, the CPU baseline, the solo-replica reference of N > 1).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32 for
+values, float64 for ids and counters): token_ids, logits, topk_ids, topk_vals, seq_len, finished, next_hidden (the next
+step's input embedding) and k_cache_new / v_cache_new (the K / V rows that step appended, every layer).  An array larger
+than 2^21 elements is written as a fixed seeded sample of its flattened elements.  Weights, KV cache and token ids are
+seeded, so the same arguments give the same inputs on every run.  Rank 0 writes the files.
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on; fits one GPU):
 Llama-2-7B, 32 layers, fp16 weights/activations/KV, batch 1, context 2048 (the K timed steps
@@ -17,7 +27,7 @@ path; torch.distributed/gloo only for the start/stop barrier and the MAX over ra
 itself: the parent never imports torch or touches a GPU, it starts N fresh child processes pinned one
 per device with HIP_VISIBLE_DEVICES=i (RANK/WORLD_SIZE/MASTER_* set), waits, and relays rank 0's line.
 
-Prints ONE JSON line (rank 0).  Extra keys beside the driver contract:
+Prints ONE JSON line (rank 0).  Extra keys beside the driver contract (--full only):
   roofline      dominant kernel (gate/up GEMV + SwiGLU): algorithmic bytes per launch / mean launch
                 duration measured with hipEvents on the launch stream (engine profiling pass, eager
                 launches of the same step right after the timed region).
@@ -214,6 +224,23 @@ def cpu_baseline(cfg, ctx, budget_s=25.0):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 21   # per array: 8 MB of float32, 16 MB of float64; nine arrays stay under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """writes each host array as out_dir/<name>.npy: float32 for floating-point values, float64 for integers; an array of
+    more than DUMP_MAX_ELEMS elements becomes a fixed seeded sample of its flattened elements (same shape -> same sample)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32) if np.issubdtype(a.dtype, np.floating) else a.astype(np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def replica_aggregate(elapsed_s, tokens_this_rank, world):
     """Independent data-parallel replicas (no collective on the data path): the job's time is the MAX over
     ranks, its work the SUM of the per-rank tokens.  torch.distributed (gloo, CPU tensors) is control plane only.
@@ -289,6 +316,11 @@ def main():
                                                "decode:<f16|int8|int4|fp8>:<batch>:<ctx>[:kvfp8] or prefill:<f16|int8|int4|fp8>:<batch>:<seq>")
     ap.add_argument("--dry-run", action="store_true",
                     help="replica plumbing only (no GPU, no kernels): simulated per-rank times through the real launcher/aggregation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement: per-op profile and roofline, other formats / sizes, device peaks, "
+                         "CPU baseline, solo-replica reference (N > 1)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -340,10 +372,11 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
-    def run_decode(wfmt, layers, B, S, K, W, profile_steps, sync_ranks, kv_fp8=False):
-        """K timed decode steps ending at context S (hipGraph replay); returns (elapsed_s, profile dict or None)"""
+    def run_decode(wfmt, layers, B, S, K, W, profile_steps, sync_ranks, kv_fp8=False, solo=False, dump_dir=""):
+        """K timed decode steps ending at context S (hipGraph replay); returns (elapsed_s, profile dict or None, solo_s or None)"""
         dec, kc, vc = make_decoder(torch, llmie, cfg, weights, layers, wfmt, B, S, kv_fp8)
-        ids = torch.randint(0, V, (B,), dtype=torch.int32, device=dev)
+        # from the seeded generator: torch's default device generator starts from a different seed in every process
+        ids = torch.randint(0, V, (B,), generator=weights["gen"], dtype=torch.int32, device=dev)
         hidden = torch.empty((B, H), dtype=torch.float16, device=dev)
         logits = torch.empty((B, V), dtype=torch.float16, device=dev)
         tmp_ids = torch.empty((B, BPR, TOPK), dtype=torch.int32, device=dev)
@@ -405,15 +438,23 @@ def main():
         t1 = time.perf_counter()
         if sync_ranks:
             barrier()
-        solo = None
-        if sync_ranks and world > 1:
+        if dump_dir:
+            # what the last timed step handed its caller; it ran at context host_step - 1 and appended K / V at slot host_step - 2
+            slot = host_step[0] - 2
+            dump_outputs(dump_dir, dict(
+                token_ids=host_tok.numpy(), logits=logits.float().cpu().numpy(), topk_ids=top_ids.cpu().numpy(),
+                topk_vals=top_vals.float().cpu().numpy(), seq_len=seq_len.cpu().numpy(), finished=finished.cpu().numpy(),
+                next_hidden=hidden.float().cpu().numpy(), k_cache_new=kc[:, :, :, slot].float().cpu().numpy(),
+                v_cache_new=vc[:, :, :, slot].float().cpu().numpy()))
+        solo_s = None
+        if solo and sync_ranks and world > 1:
             # the same K steps on rank 0 ALONE (the other replicas idle at the barrier): the one-replica reference the
             # scaling efficiency of this job is quoted against
             if rank == 0:
                 ts0 = time.perf_counter()
                 run(K)
                 torch.cuda.synchronize()
-                solo = time.perf_counter() - ts0
+                solo_s = time.perf_counter() - ts0
             barrier()
         prof = None
         if profile_steps:
@@ -430,7 +471,7 @@ def main():
         dec.close()
         del graph, kc, vc
         torch.cuda.empty_cache()
-        return t1 - t0, prof, solo
+        return t1 - t0, prof, solo_s
 
     P = 4
 
@@ -533,20 +574,12 @@ def main():
                               "ops_us_per_launch": {op: round(ms / n * 1e3, 2) for op, (ms, n) in pr.items() if n}}), flush=True)
         return
 
-    own_elapsed, prof, solo_elapsed = run_decode("f16", weights["layers"], B, S, K, W, P, True)
+    own_elapsed, prof, solo_elapsed = run_decode("f16", weights["layers"], B, S, K, W, P if args.full else 0, True,
+                                                 solo=args.full, dump_dir=args.dump_outputs if rank == 0 else "")
     value, elapsed = replica_aggregate(own_elapsed, B * K, world)
     per_replica = replica_gather(B * K / own_elapsed, world)
     ms_per_step = elapsed / K * 1e3
 
-    breakdown = {op: dict(us_per_launch=round(ms / n * 1e3, 2), launches_per_step=n // P,
-                          us_per_step=round(ms / P * 1e3, 1))
-                 for op, (ms, n) in prof.items() if n}
-    I = cfg["inter_size"]
-    gu_bytes = 2 * I * H * 2  # fused gate_up matrix streamed once per launch (180.4 MB)
-    gu_ms, gu_n = prof["gate_up_swiglu"]
-    gu_us = gu_ms / gu_n * 1e3
-    roofline = roofline_block("gemv_ksplit_kernel<M=%d,RPW=4,XC=2,fp16> (RMSNorm + gate/up projection + SwiGLU)" % B, "hbm", gu_bytes,
-                              gu_us, gu_n, HBM_PEAK_GBS, "GB/s", "decode_f16_b1_ctx2048" if (B == 1 and S == 2048) else "")
     step_bytes = decode_bytes_per_step(cfg, B, S)
     whole = dict(algorithmic_bytes_per_step=step_bytes,
                  achieved_GBs=round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
@@ -561,15 +594,27 @@ def main():
                    "global_batch": world * B, "seq_len": S, "parallelism": "replicas x%d (no collective)" % world,
                    "graph": not args.no_graph, "layers": cfg["num_layers"]},
         "metric_full": "decode tokens/s + prefill tokens/s, Llama-2-7B fp16 & int8, 1 MI355X",
-        "roofline": roofline, "whole_step": whole, "breakdown": breakdown,
+        "whole_step": whole,
         "per_replica_tokens_per_s": [round(v, 2) for v in per_replica],
     }
+    if prof:
+        breakdown = {op: dict(us_per_launch=round(ms / n * 1e3, 2), launches_per_step=n // P,
+                              us_per_step=round(ms / P * 1e3, 1))
+                     for op, (ms, n) in prof.items() if n}
+        I = cfg["inter_size"]
+        gu_bytes = 2 * I * H * 2  # fused gate_up matrix streamed once per launch (180.4 MB)
+        gu_ms, gu_n = prof["gate_up_swiglu"]
+        gu_us = gu_ms / gu_n * 1e3
+        out["roofline"] = roofline_block("gemv_ksplit_kernel<M=%d,RPW=4,XC=2,fp16> (RMSNorm + gate/up projection + SwiGLU)" % B, "hbm",
+                                         gu_bytes, gu_us, gu_n, HBM_PEAK_GBS, "GB/s",
+                                         "decode_f16_b1_ctx2048" if (B == 1 and S == 2048) else "")
+        out["breakdown"] = breakdown
     if world > 1 and solo_elapsed:
         # whole job / (N x one replica running alone on this node), both measured inside this run
         out["solo_replica_tokens_per_s"] = round(B * K / solo_elapsed, 2)
         out["scaling_efficiency"] = round(value / (world * (B * K / solo_elapsed)), 4)
     # ---- other configurations of the metric (rank 0, single GPU only; not the headline value) ----
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         extra = {}
 
         def record(name, wfmt, layers, b, s, wbytes, kv_fp8=False, profile=False):
@@ -729,7 +774,7 @@ def main():
         out["peaks"] = peaks
     if args.layers:
         out["config"]["INVALID_debug_layers"] = args.layers
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, S)
     else:
         out["cpu_baseline"] = None

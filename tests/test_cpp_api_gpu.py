@@ -36,12 +36,12 @@ def test_examples_cpp_call_sequences_replayed():
 
 
 def test_reference_user_entry_runs_unchanged():
-    """the reference's chat driver, compiled unchanged where the reference tree is present (cpp_tests/Makefile, _ref/user_entry;
+    """the reference's chat driver, compiled unchanged where the reference tree is present (oracle/Makefile, oracle/_ref/user_entry;
     a force-included shim swaps its checkpoint path for the reference's own dummy weights on a small geometry): one question,
     then the stop command"""
-    path = os.path.join(BIN, "_ref", "user_entry")
+    path = os.path.join(ROOT, "oracle", "_ref", "user_entry")
     if not os.path.exists(path):
-        pytest.skip("built only where the reference tree is present (make -C llm-inference-engine_amd/cpp_tests)")
+        pytest.skip("built only where the reference tree is present (make -C oracle)")
     r = subprocess.run([path], input="Hey, are you conscious? Can you talk to me?\ns\n", capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert r.stdout.count("please input the question") == 2   # one answered round, then the stop command

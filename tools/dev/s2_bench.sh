@@ -1,3 +1,4 @@
 cd $GRAFT_REPO_ROOT
-timeout -k 10 1100 python3 bench.py > gpurun_out/s2_bench.json 2> gpurun_out/s2_bench.err; echo "rc=$?"
-tail -c 1500 gpurun_out/s2_bench.json
+OUT=${1:?usage: s2_bench.sh OUTPUT_DIR}
+timeout -k 10 1100 python3 bench.py --full > $OUT/s2_bench.json 2> $OUT/s2_bench.err; echo "rc=$?"
+tail -c 1500 $OUT/s2_bench.json
