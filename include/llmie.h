@@ -40,7 +40,8 @@ extern "C" {
  *   2  llmie_linear, llmie_linear_swiglu, llmie_linear_w8a16, llmie_linear_w4a16 gained (workspace, workspace_bytes) in front
  *      of the stream argument and llmie_linear_fp8_workspace_bytes gained N; w8a16 with M > 64 / w4a16 with M > 8 need a
  *      workspace (NULL -> LLMIE_ERR_UNSUPPORTED).  A version-1 consumer would pass its stream where the slab pointer goes.
- *   3  round 3: additions only are listed at the entries they concern (int8 / int4 weight-only prefill, decoder config flags). */
+ *   3  round 3: additions only are listed at the entries they concern (int8 / int4 weight-only prefill, decoder config flags,
+ *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -225,6 +226,46 @@ int llmie_sampling(const int32_t *topk_id, const void *topk_val, int32_t *seq_le
                    uint8_t *finished, int32_t *out_id, int batch, int K, int step,
                    const int32_t *step_dev, int end_id, int vocab,
                    llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3.  Per-request sampling controls (no reference launcher: the reference samples from the top-K at temperature 1).
+ * One entry per row of the batch, read on the device from params_dev[batch] (a captured graph picks up new values on replay).
+ * Per row, from logits[b, 0..V) read as fp32:
+ *   1 penalties, once per distinct id t of history[b, 0..history_len[b]) (ids outside [0, V) ignored, c_t = its count):
+ *     l_t <- (l_t > 0 ? l_t / rep : l_t * rep) - presence - c_t * frequency, in fp32 in that order;
+ *   2 temperature == 0: greedy (largest penalised logit, ties -> lower id, no draw); else l <- l / T clamped to +-FLT_MAX;
+ *   3 top_k (0 = off) keeps exactly min(top_k, valid) tokens in (value desc, id asc) order -- llmie_topk's order;
+ *   4 softmax exp(l - max) over them;  5 top_p (>= 1 = off): the smallest prefix of that order whose mass is >= top_p x the
+ *     total, widened to every token whose value equals the prefix's last;  6 min_p (0 = off): probability >= min_p x the max;
+ *   7 u = Philox4x32-10(seed = step, stream = params.seed) (llmie_sampling's generator); the pick is the first kept token, in
+ *     that order, at which the running mass exceeds u x the kept mass (u == 1: the last kept token).
+ * NaN logits are excluded everywhere; a row without a valid token emits end_id.  out_id / seq_len / finished follow
+ * llmie_sampling.  out_logprob (may be NULL) = log_softmax(raw logits)[chosen], before penalties, temperature and truncation.
+ * history_append != 0: the pick is written at history[b, history_len[b]] and history_len[b] += 1 while history_len[b] <
+ * history_stride.  history / history_len may be NULL when history_stride == 0; history_stride <= LLMIE_SAMPLE_MAX_HISTORY.
+ * Clamped on the device: temperature < 0 / NaN -> 0; top_k < 0 -> 0, > V -> V; top_p <= 0 keeps one token, > 1 -> 1; min_p to
+ * [0, 1]; repetition_penalty <= 0 / NaN -> 1.
+ * Determinism: masses are fixed point, floor(exp(l - max) * 2^32) summed as uint64 (exact, in any order), so the same inputs
+ * give the same bits and a row's result does not depend on the other rows or the batch size.  The cost: a token whose
+ * exp(l - max) is below 2^-32 has mass 0 and is never drawn, and masses carry a 2^-32 absolute rounding (the float sums of
+ * llmie_sampling can pick the neighbour when u sits on a boundary).
+ * One launch per call (one 1024-thread workgroup per row).  workspace: llmie_sample_logits_workspace_bytes(batch, vocab)
+ * bytes, 16-byte aligned (a fp32 / key copy of each row). */
+typedef struct {
+    float temperature;
+    int top_k;
+    float top_p;
+    float min_p;
+    float repetition_penalty;
+    float presence_penalty;
+    float frequency_penalty;
+    uint32_t seed;
+} llmie_sampling_params;
+#define LLMIE_SAMPLE_MAX_HISTORY 8192
+size_t llmie_sample_logits_workspace_bytes(int batch, int vocab);
+int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
+                        int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                        int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                        size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
 
 /* ------------------------------------------------------------------------- */
 /* 2. weight-only quantised / fp8 linears (reference: planned only,           */
@@ -439,6 +480,17 @@ int llmie_lm_head_sample_next(llmie_decoder *dec, void *hidden, const void *fina
                               void *topk_vals, int K, int blocks_per_row, int32_t *seq_len, uint8_t *finished, int32_t *out_ids,
                               int batch, int step, int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden,
                               int advance_step, llmie_stream stream);
+
+/* ABI 3.  The LM head of llmie_lm_head_sample (final norm, or the fused-norm GEMV where that route applies) followed by
+ * llmie_sample_logits on the decoder's vocab_size and dtype, with llmie_lm_head_sample_next's options: next_hidden[b] =
+ * embed_table[out_ids[b]] if next_hidden != NULL, and *step_dev += 1 once every row has read it if advance_step != 0.  The
+ * sampler is one launch (LM head + 1, or + 2 with a separate final norm). */
+int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                                llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev, int32_t *history,
+                                int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                                int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev, int end_id,
+                                const void *embed_table, void *next_hidden, int advance_step, void *workspace, size_t workspace_bytes,
+                                llmie_stream stream);
 
 /* Per-kernel timing of the engine (eager launches only, never inside graph capture): between
  * profile_begin and profile_end every kernel the engine launches is bracketed by hipEvents

@@ -93,6 +93,10 @@ _SIGS = {
     "llmie_lm_head_sample_next": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp,
                                   _i, _vp],
     "llmie_advance_step": [_vp, _vp],
+    "llmie_sample_logits_workspace_bytes": [_i, _i],
+    "llmie_sample_logits": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _vp],
+    "llmie_lm_head_sample_params": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp,
+                                    _vp, _i, _vp, _sz, _vp],
     "llmie_decoder_forward_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "llmie_decoder_prefill_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
     "llmie_kv_pages_copy": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -117,6 +121,7 @@ _RESTYPES = {
     "llmie_linear_packed_workspace_bytes": _sz,
     "llmie_decoder_workspace_bytes": _sz,
     "llmie_decoder_prefill_workspace_bytes": _sz,
+    "llmie_sample_logits_workspace_bytes": _sz,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -358,6 +363,64 @@ def advance_step(step_dev):
     _check(lib().llmie_advance_step(_p(step_dev), _st()), "advance_step")
 
 
+# ------------------------------------------------------------------ per-request sampling
+SAMPLE_MAX_HISTORY = 8192  # LLMIE_SAMPLE_MAX_HISTORY
+SAMPLING_DEFAULTS = dict(temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0,
+                         frequency_penalty=0.0, seed=0)
+
+
+class SamplingParams(C.Structure):
+    """llmie_sampling_params (include/llmie.h)"""
+    _fields_ = [("temperature", _f), ("top_k", _i), ("top_p", _f), ("min_p", _f), ("repetition_penalty", _f),
+                ("presence_penalty", _f), ("frequency_penalty", _f), ("seed", C.c_uint32)]
+
+
+def sampling_params(rows, out=None, device="cuda"):
+    """Pack a list of per-row dicts (missing keys: SAMPLING_DEFAULTS, i.e. plain sampling at temperature 1) into the device
+    array llmie_sample_logits reads: a uint8 tensor of len(rows) * sizeof(llmie_sampling_params) bytes.  out: an existing
+    array to overwrite in place (a captured graph then sees the new values on replay)."""
+    import torch
+    arr = (SamplingParams * len(rows))()
+    for i, r in enumerate(rows):
+        unknown = set(r) - set(SAMPLING_DEFAULTS)
+        if unknown:
+            raise LlmieError("unknown sampling parameters: %s" % ", ".join(sorted(unknown)))
+        v = dict(SAMPLING_DEFAULTS, **r)
+        arr[i] = SamplingParams(v["temperature"], int(v["top_k"]), v["top_p"], v["min_p"], v["repetition_penalty"],
+                                v["presence_penalty"], v["frequency_penalty"], int(v["seed"]) & 0xffffffff)
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    if out is None:
+        return host.to(device)
+    if out.numel() != host.numel():
+        raise LlmieError("sampling_params: out holds %d bytes, %d rows need %d" % (out.numel(), len(rows), host.numel()))
+    out.copy_(host)
+    return out
+
+
+def sample_logits_workspace_bytes(batch, vocab):
+    return lib().llmie_sample_logits_workspace_bytes(batch, vocab)
+
+
+def _sample_ws(workspace, batch, vocab, device):
+    import torch
+    need = sample_logits_workspace_bytes(batch, vocab)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def sample_logits(logits, params, seq_len, finished, out_id, step, end_id, history=None, history_len=None, append=False,
+                  out_logprob=None, step_dev=None, workspace=None):
+    """llmie_sample_logits on logits [batch, vocab] (fp16 / fp32, read-only).  params: sampling_params(...) of batch rows.
+    history: int32 [batch, stride] with history_len int32 [batch] (device), or None.  workspace: None allocates one."""
+    bs, V = logits.shape
+    ws, ws_bytes = _sample_ws(workspace, bs, V, logits.device)
+    stride = 0 if history is None else history.shape[1]
+    _check(lib().llmie_sample_logits(_p(logits), bs, V, _p(params), _p(history), stride, _p(history_len), 1 if append else 0,
+                                     _p(seq_len), _p(finished), _p(out_id), _p(out_logprob), step, _p(step_dev), end_id,
+                                     _p(ws), ws_bytes, _dt(logits), _st()), "sample_logits")
+
+
 # ------------------------------------------------------------------ fused decoder engine
 class Matrix(C.Structure):
     _fields_ = [("data", _vp), ("scale", _vp), ("bias", _vp)]
@@ -473,6 +536,22 @@ class Decoder:
                                           _p(tmp_ids), _p(tmp_vals), _p(topk_ids), _p(topk_vals),
                                           topk_ids.shape[-1], blocks_per_row, _p(seq_len), _p(finished), _p(out_ids),
                                           hidden.shape[0], step, _p(step_dev), end_id, _st()), "lm_head_sample")
+
+    def lm_head_sample_params(self, hidden, final_gamma, lm_head, lm_fmt, logits, params, seq_len, finished, out_ids, step,
+                              end_id, history=None, history_len=None, append=False, out_logprob=None, step_dev=None, embed=None,
+                              next_hidden=None, advance=False, workspace=None):
+        """llmie_lm_head_sample_params: the LM head of lm_head_sample, then sample_logits (+ next_hidden[b] = embed[out_ids[b]])
+        (+ step_dev += 1).  workspace: sample_logits_workspace_bytes(batch, vocab) bytes, or None to allocate one (not
+        inside a graph capture)."""
+        m = _mat(lm_head)
+        bs = hidden.shape[0]
+        ws, ws_bytes = _sample_ws(workspace, bs, self.cfg.vocab_size, hidden.device)
+        stride = 0 if history is None else history.shape[1]
+        _check(lib().llmie_lm_head_sample_params(self.handle, _p(hidden), _p(final_gamma), C.byref(m), lm_fmt, _p(logits),
+                                                 _p(params), _p(history), stride, _p(history_len), 1 if append else 0,
+                                                 _p(seq_len), _p(finished), _p(out_ids), _p(out_logprob), bs, step,
+                                                 _p(step_dev), end_id, _p(embed), _p(next_hidden), 1 if advance else 0,
+                                                 _p(ws), ws_bytes, _st()), "lm_head_sample_params")
 
     OPS = ("attn_norm", "qkv_gemm", "rope", "mha", "o_gemm", "ffn_norm", "gate_up_swiglu", "down_gemm",
            "final_norm", "lm_head", "topk", "sampling", "chain")

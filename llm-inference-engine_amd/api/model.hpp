@@ -4,6 +4,7 @@
 // it is used as the specification of names and control flow: prefill once through the context decoder,
 // then <= output_token_limit decode steps, LM head on the last token, top-k, sampling, callback.
 #pragma once
+#include <algorithm>
 #include <functional>
 
 #include "layers.hpp"
@@ -75,6 +76,32 @@ private:
     DevBuf<T> d_ctx_in, d_ctx_out, d_dec_in, d_dec_out, d_kcache, d_vcache, d_probs, d_topk_val, d_final_val, d_unused;
     DevBuf<int> d_ids, d_in_len, d_hist_len, d_ctx_len, d_seq_len, d_token, d_topk_id, d_final_id;
     DevBuf<bool> d_finished;
+    DevBuf<llmie_sampling_params> d_sparams;
+    DevBuf<int> d_penalty_ids, d_penalty_len;
+    DevBuf<unsigned char> d_sample_ws;
+    std::vector<int> penalty_ids;   // prompt + generated ids: the penalty history of the SamplingConfig path
+
+    // SamplingConfig path: llmie_sample_logits over the whole vocabulary, seeded by (h_step, sampling.seed)
+    int sampleWithConfig(TensorWrapper<T> &probs, TensorWrapper<int> &seq, TensorWrapper<bool> &fin, TensorWrapper<int> &tok) {
+        const llmie_sampling_params p{sampling.temperature, sampling.top_k, sampling.top_p, sampling.min_p,
+                                      sampling.repetition_penalty, sampling.presence_penalty, sampling.frequency_penalty,
+                                      sampling.seed};
+        const int n = static_cast<int>(std::min<size_t>(penalty_ids.size(), LLMIE_SAMPLE_MAX_HISTORY));
+        const int *recent = penalty_ids.data() + (penalty_ids.size() - n);   // the most recent ids when the context is longer
+        int *hist = d_penalty_ids.ensure(std::max(n, 1));
+        int *hlen = d_penalty_len.ensure(1);
+        CHECK(hipMemcpyAsync(d_sparams.ensure(1), &p, sizeof(p), hipMemcpyHostToDevice, llmie_api::st()));
+        if (n) CHECK(hipMemcpyAsync(hist, recent, sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(hlen, &n, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+        const size_t ws = llmie_sample_logits_workspace_bytes(batch_size, vocab_size);
+        LLMIE_CALL(llmie_sample_logits(probs.data, batch_size, vocab_size, d_sparams.p, hist, std::max(n, 1), hlen, 0, seq.data,
+                                       reinterpret_cast<uint8_t *>(fin.data), tok.data, nullptr, h_step, nullptr, eos_token_id,
+                                       d_sample_ws.ensure(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st()));
+        int h_tok = 0;
+        CHECK(hipMemcpyAsync(&h_tok, tok.data, sizeof(int), hipMemcpyDeviceToHost, llmie_api::st()));
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps p / n alive until the copies are done)
+        return h_tok;
+    }
 
     int lmHeadAndSample(T *hidden_row /*[1,H] device*/) {
         const DataType ty = getTensorType<T>(), ti = getTensorType<int>();
@@ -83,6 +110,12 @@ private:
         launchRMSNorm(&x, &unused, &llama_weights->out_rmsnorm_weight, rmsnorm_eps, true);      // llama.cpp:247
         TensorWrapper<T> probs(Device::GPU, ty, {batch_size, vocab_size}, d_probs.ensure(vocab_size));
         launchLinearGemm(&x, &llama_weights->post_decoder_embedding_weight, &probs, cublas_wrapper, false, true);  // :282
+        if (!sampling.isDefault()) {
+            TensorWrapper<int> seq(Device::GPU, ti, {batch_size}, d_seq_len.ensure(1));
+            TensorWrapper<bool> fin(Device::GPU, getTensorType<bool>(), {batch_size}, d_finished.ensure(1));
+            TensorWrapper<int> tok(Device::GPU, ti, {batch_size}, d_token.ensure(1));
+            return sampleWithConfig(probs, seq, fin, tok);
+        }
         TensorWrapper<int> topk_id(Device::GPU, ti, {batch_size, beamwidth, blocks_per_beam, K}, d_topk_id.ensure(blocks_per_beam * K));
         TensorWrapper<T> topk_val(Device::GPU, ty, {batch_size, beamwidth, blocks_per_beam, K}, d_topk_val.ensure(blocks_per_beam * K));
         TensorWrapper<int> final_id(Device::GPU, ti, {batch_size * beamwidth, K}, d_final_id.ensure(K));
@@ -101,6 +134,26 @@ private:
 
 public:
     int output_token_limit = 20;  // llama.h:26
+
+    // Per-request sampling controls (llmie_sampling_params; include/llmie.h has the semantics).  The default keeps the
+    // reference's tail bit for bit (top-4 at temperature 1: launchTopKForBeamSearch + launchSampling); any other value
+    // samples with llmie_sample_logits over the whole vocabulary, with the prompt and the generated ids as the penalty
+    // history and Philox(step, seed) as the draw.
+    struct SamplingConfig {
+        float temperature = 1.0f;   // 0: greedy
+        int top_k = 0;              // 0: off
+        float top_p = 1.0f;         // >= 1: off
+        float min_p = 0.0f;         // 0: off
+        float repetition_penalty = 1.0f;
+        float presence_penalty = 0.0f;
+        float frequency_penalty = 0.0f;
+        uint32_t seed = 0;
+        bool isDefault() const {
+            return temperature == 1.0f && top_k == 0 && top_p == 1.0f && min_p == 0.0f && repetition_penalty == 1.0f &&
+                   presence_penalty == 0.0f && frequency_penalty == 0.0f && seed == 0;
+        }
+    };
+    SamplingConfig sampling;
 
     LlamaModel(int head_num, int kv_head_num, int head_size, int inter_size, int num_layers, int vocab_size,
                const LlamaAttentionStaticParams &attention_static_params, int max_seq_len, hipStream_t stream,
@@ -176,6 +229,8 @@ public:
         dyn.num_layers = num_layers;
         context_decoder->forward(&decoder_inputs, &layer_ptrs, &decoder_outputs, &dyn);
         h_step = ctx;
+        if (history_len == 0) penalty_ids.clear();
+        penalty_ids.insert(penalty_ids.end(), ids.begin(), ids.end());
         return lmHeadAndSample(ctx_out.data + static_cast<size_t>(n - 1) * hidden_units);  // last token only (:262-279)
     }
 
@@ -198,6 +253,7 @@ public:
         dyn.batch_size = 1;
         dyn.num_layers = num_layers;
         self_decoder->forward(&decoder_inputs, &layer_ptrs, &decoder_outputs, &dyn);
+        penalty_ids.push_back(id);
         return lmHeadAndSample(dec_out.data);
     }
 

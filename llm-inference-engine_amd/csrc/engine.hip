@@ -1242,12 +1242,23 @@ extern "C" int llmie_decoder_prefill_paged(llmie_decoder *dec, const void *hidde
     return rc;
 }
 
+// the sampler operands of llmie_lm_head_sample_params (checked by sample_logits_check)
+struct SampleParamsArgs {
+    const llmie_sampling_params *params;
+    int32_t *history;
+    int history_stride;
+    int32_t *history_len;
+    int history_append;
+    float *out_logprob;
+    void *workspace;
+};
+
 static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
                                llmie_weight_format lm_fmt, void *logits, int32_t *tmp_ids, void *tmp_vals, int32_t *topk_ids,
                                void *topk_vals, int K, int blocks_per_row, int32_t *seq_len, uint8_t *finished, int32_t *out_ids,
                                int batch, int step, int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden,
-                               int advance_step, bool fused_tail, llmie_stream stream) {
-    LLMIE_REQUIRE(dec && hidden && final_norm_gamma && lm_head && lm_head->data && logits && topk_ids && topk_vals &&
+                               int advance_step, bool fused_tail, llmie_stream stream, const SampleParamsArgs *sp = nullptr) {
+    LLMIE_REQUIRE(dec && hidden && final_norm_gamma && lm_head && lm_head->data && logits && (sp || (topk_ids && topk_vals)) &&
                       seq_len && finished && out_ids, "lm_head_sample: NULL pointer");
     const llmie_decoder_config &c = dec->cfg;
     LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "lm_head_sample: batch %d outside [1,%d]", batch, c.max_batch);
@@ -1277,6 +1288,14 @@ static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *fin
                                              c.dtype, as_stream(stream)));
         return LLMIE_OK;
     }
+    if (sp) {
+        // per-request controls: ONE launch (sampling_params.hip), with the next step's embedding and counter in it
+        TIMED(LLMIE_OP_SAMPLING, sample_logits_launch(logits, batch, c.vocab_size, sp->params, sp->history, sp->history_stride,
+                                                      sp->history_len, sp->history_append, seq_len, finished, out_ids, sp->out_logprob,
+                                                      step, step_dev, end_id, sp->workspace, c.dtype, embed_table, next_hidden, dec->H,
+                                                      advance_step, dec->tail_ticket, as_stream(stream)));
+        return LLMIE_OK;
+    }
     // llama.cpp:293,304
     TIMED(LLMIE_OP_TOPK, llmie_topk(logits, tmp_ids, tmp_vals, topk_ids, topk_vals, batch, c.vocab_size, K, blocks_per_row,
                                     c.dtype, stream));
@@ -1304,4 +1323,23 @@ extern "C" int llmie_lm_head_sample_next(llmie_decoder *dec, void *hidden, const
     LLMIE_REQUIRE(tmp_ids && tmp_vals, "lm_head_sample_next: tmp buffers required");
     return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, tmp_ids, tmp_vals, topk_ids, topk_vals, K, blocks_per_row,
                                seq_len, finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, true, stream);
+}
+
+extern "C" int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                                           llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev,
+                                           int32_t *history, int history_stride, int32_t *history_len, int history_append,
+                                           int32_t *seq_len, uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step,
+                                           int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden, int advance_step,
+                                           void *workspace, size_t workspace_bytes, llmie_stream stream) {
+    LLMIE_REQUIRE(dec, "lm_head_sample_params: NULL decoder");
+    LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_params: next_hidden without an embedding table");
+    LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_params: advance_step needs the device-resident step");
+    LLMIE_REQUIRE(batch >= 1 && batch <= dec->cfg.max_batch, "lm_head_sample_params: batch %d outside [1,%d]", batch, dec->cfg.max_batch);
+    LLMIE_REQUIRE(dec->cfg.vocab_size > 0, "lm_head_sample_params: vocab_size not set in the decoder config");
+    const int rc = sample_logits_check(logits, batch, dec->cfg.vocab_size, params_dev, history, history_stride, history_len, seq_len,
+                                       finished, out_ids, workspace, workspace_bytes, dec->cfg.dtype);
+    if (rc != LLMIE_OK) return rc;
+    const SampleParamsArgs sp{params_dev, history, history_stride, history_len, history_append, out_logprob, workspace};
+    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, nullptr, nullptr, nullptr, nullptr, 0, 1, seq_len,
+                               finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, false, stream, &sp);
 }

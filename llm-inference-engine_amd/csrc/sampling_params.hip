@@ -1,0 +1,451 @@
+// llmie_sample_logits / llmie_lm_head_sample_params: per-request sampling controls over the whole vocabulary (no reference
+// launcher: the reference samples from the top-K only).
+//
+// ONE launch per step: one 1024-thread workgroup per row; everything below runs inside it.
+//   pass 1   raw logits (fp16 / fp32) -> fp32 copy of the row in the workspace + the raw log-sum-exp (for out_logprob)
+//   penalty  the history (<= kSpMaxHistory ids) is bitonic-sorted in LDS; every distinct id patches its entry of the copy
+//   pass 2   temperature + clamp -> order-preserving 32-bit keys in place (0 = NaN, excluded) + the (key, id) maximum and
+//            the number of valid tokens.  Greedy rows (T == 0) stop here.
+//   then up to three runs of ONE operation, radix_select: in (value desc, id asc) order, the first token at which a running
+//   integer weight exceeds a threshold -- 4 digit passes of a 256-bin histogram in LDS over the keys (narrowing the prefix
+//   after each digit), then, for exact-value ties, id_select: the j-th id of the tie group by a block-wide scan.
+//     top-k: weight 1, threshold top_k - 1;  top-p: mass, ceil(top_p * kept mass) - 1;  draw: mass, floor(u * kept mass).
+//   The kept set is always a prefix of that order (top-k, top-p and min-p each cut it), so the three runs compose.
+//
+// Masses are fixed point: mass(t) = floor(exp(v_t - v_max) * 2^32) as uint64 (a token below 2^-32 of the maximum weighs 0 and is
+// never drawn).  Every sum is an integer sum, so LDS atomics in any order give the same bits; the float reductions (max,
+// log-sum-exp) use a fixed thread mapping and a fixed tree.  A row's result does not depend on the batch it runs in.
+#include "device_utils.cuh"
+#include "llmie_internal.h"
+#include "philox.cuh"
+
+#include <cfloat>
+#include <climits>
+
+namespace llmie {
+
+constexpr int kSpThreads = 1024;
+constexpr int kSpMaxHistory = LLMIE_SAMPLE_MAX_HISTORY;
+constexpr int kSpWaves = kSpThreads / 64;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ uint32_t sp_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sp_val(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+struct SpShared {
+    u64 hist[256];
+    u64 red64[kSpWaves];
+    float redm[kSpWaves], reds[kSpWaves];
+    int redi[kSpWaves];
+    u64 b_above;
+    uint32_t b_prefix;
+    int b_id;
+    int sorted[kSpMaxHistory];
+};
+
+// block-wide reductions (fixed mapping and order: deterministic)
+__device__ __forceinline__ u64 sp_sum64(u64 v, SpShared &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if (lane == 0) s.red64[w] = v;
+    __syncthreads();
+    u64 t = 0;
+#pragma unroll
+    for (int i = 0; i < kSpWaves; ++i) t += s.red64[i];
+    return t;
+}
+__device__ __forceinline__ u64 sp_max64(u64 v, SpShared &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 y = __shfl_xor(v, o);
+        v = y > v ? y : v;
+    }
+    __syncthreads();
+    if (lane == 0) s.red64[w] = v;
+    __syncthreads();
+    u64 t = 0;
+#pragma unroll
+    for (int i = 0; i < kSpWaves; ++i) t = s.red64[i] > t ? s.red64[i] : t;
+    return t;
+}
+// exclusive prefix of an int over the block (thread order)
+__device__ __forceinline__ int sp_excl_scan(int v, SpShared &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(inc, o);
+        if (lane >= o) inc += y;
+    }
+    __syncthreads();
+    if (lane == 63) s.redi[w] = inc;
+    __syncthreads();
+    int before = 0;
+    for (int i = 0; i < w; ++i) before += s.redi[i];
+    return before + inc - v;
+}
+// f(t, key) over this thread's tokens (stride kSpThreads), kSpUnroll loads in flight: one CU streams the whole row, so the
+// passes are bound by load latency unless the loads of several tokens overlap.  Keys past V read as 0 (excluded).
+constexpr int kSpUnroll = 8;
+template <class F> __device__ __forceinline__ void sp_for_keys(const uint32_t *keys, int V, F f) {
+    for (int t0 = threadIdx.x; t0 < V; t0 += kSpUnroll * kSpThreads) {
+        uint32_t k[kSpUnroll];
+#pragma unroll
+        for (int u = 0; u < kSpUnroll; ++u) {
+            const int t = t0 + u * kSpThreads;
+            k[u] = t < V ? keys[t] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < kSpUnroll; ++u) f(t0 + u * kSpThreads, k[u]);
+    }
+}
+// (max, sum of exp(x - max)) pairs
+__device__ __forceinline__ void sp_lse_combine(float &m, float &sum, float m2, float s2) {
+    const float mn = fmaxf(m, m2);
+    if (mn == -INFINITY) return;
+    sum = (m == -INFINITY ? 0.f : sum * expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * expf(m2 - mn));
+    m = mn;
+}
+
+// In (value desc, id asc) order over the tokens t with in(t, key) (key != 0), the first token at which the running weight
+// w(key) exceeds thr.  The caller guarantees that the total weight exceeds thr.  Returns its key; *above = the weight of the
+// set strictly above that key.  4 passes over the keys, one 8-bit digit each, highest first.
+template <class In, class W>
+__device__ uint32_t radix_select(const uint32_t *keys, int V, In in, W w, u64 thr, u64 *above_out, SpShared &s) {
+    const int tid = threadIdx.x;
+    uint32_t prefix = 0;
+    u64 above = 0;
+    for (int d = 3; d >= 0; --d) {
+        const int shift = 8 * d;
+        const uint32_t hmask = d == 3 ? 0u : (0xffffffffu << (shift + 8));
+        if (tid < 256) s.hist[tid] = 0;
+        __syncthreads();
+        sp_for_keys(keys, V, [&](int t, uint32_t k) {
+            if (k == 0 || (k & hmask) != prefix || !in(t, k)) return;
+            const u64 wt = w(k);
+            if (wt) atomicAdd(&s.hist[(k >> shift) & 255u], wt);
+        });
+        __syncthreads();
+        if (tid < 64) {
+            // lane l holds bins 255-4l .. 252-4l (descending value)
+            const int base = 255 - 4 * tid;
+            const u64 h0 = s.hist[base], h1 = s.hist[base - 1], h2 = s.hist[base - 2], h3 = s.hist[base - 3];
+            const u64 sum = h0 + h1 + h2 + h3;
+            u64 inc = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const u64 y = __shfl_up(inc, o);
+                if (tid >= o) inc += y;
+            }
+            const u64 hit = __ballot(above + inc > thr);
+            const int first = hit ? __ffsll(static_cast<long long>(hit)) - 1 : 63;
+            if (tid == first) {
+                u64 c = above + inc - sum;
+                int bin = base - 3;
+                if (c + h0 > thr) bin = base;
+                else if ((c += h0) + h1 > thr) bin = base - 1;
+                else if ((c += h1) + h2 > thr) bin = base - 2;
+                else c += h2;
+                s.b_above = c;
+                s.b_prefix = prefix | (static_cast<uint32_t>(bin) << shift);
+            }
+        }
+        __syncthreads();
+        prefix = s.b_prefix;
+        above = s.b_above;
+    }
+    *above_out = above;
+    return prefix;
+}
+
+// the j-th (0-based) id, ascending, among the tokens with keys[t] == key and in(t, key); -1 if there are not that many
+template <class In>
+__device__ int id_select(const uint32_t *keys, int V, uint32_t key, In in, u64 j, SpShared &s) {
+    const int chunk = (V + kSpThreads - 1) / kSpThreads;
+    const int t0 = min(V, threadIdx.x * chunk), t1 = min(V, t0 + chunk);
+    int c = 0;
+    for (int t = t0; t < t1; ++t) c += (keys[t] == key && in(t, key)) ? 1 : 0;
+    if (threadIdx.x == 0) s.b_id = -1;
+    const int ex = sp_excl_scan(c, s);   // (its barriers order the store above)
+    if (j >= static_cast<u64>(ex) && j < static_cast<u64>(ex + c)) {
+        int r = static_cast<int>(j - ex);
+        for (int t = t0; t < t1; ++t)
+            if (keys[t] == key && in(t, key) && r-- == 0) {
+                s.b_id = t;
+                break;
+            }
+    }
+    __syncthreads();
+    return s.b_id;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
+    const T *__restrict__ logits, int V, const llmie_sampling_params *__restrict__ params, int32_t *history, int hstride,
+    int32_t *history_len, int happend, int32_t *__restrict__ seq_len, uint8_t *__restrict__ finished, int32_t *__restrict__ out_id,
+    float *__restrict__ out_logprob, int step_arg, const int32_t *step_dev, int end_id, uint32_t *ws, size_t ws_row,
+    const T *__restrict__ embed, T *__restrict__ next_hidden, int hidden, int advance, unsigned *ticket, int rows) {
+    __shared__ SpShared s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int step = step_dev ? *step_dev : step_arg;
+    const T *lg = logits + static_cast<size_t>(b) * V;
+    uint32_t *keys = ws + static_cast<size_t>(b) * ws_row;
+    float *rowf = reinterpret_cast<float *>(keys);
+
+    // parameters, clamped (they live in device memory: the host cannot check them)
+    const llmie_sampling_params p = params[b];
+    float temp = p.temperature;
+    if (!(temp >= 0.f)) temp = 0.f;
+    int top_k = p.top_k < 0 ? 0 : (p.top_k > V ? V : p.top_k);
+    float top_p = p.top_p;
+    if (!(top_p > 0.f)) {   // <= 0 (or NaN): one token
+        top_k = 1;
+        top_p = 1.f;
+    }
+    top_p = fminf(top_p, 1.f);
+    float min_p = p.min_p;
+    min_p = (min_p >= 0.f) ? fminf(min_p, 1.f) : 0.f;
+    float rep = p.repetition_penalty;
+    if (!(rep > 0.f)) rep = 1.f;
+    const float presence = p.presence_penalty, frequency = p.frequency_penalty;
+
+    // pass 1: fp32 copy + raw log-sum-exp (per-thread online pairs, then a fixed tree)
+    float m = -INFINITY, sum = 0.f;
+    for (int t = tid; t < V; t += kSpThreads) {
+        const float x = to_f32(lg[t]);
+        rowf[t] = x;
+        if (x == x) sp_lse_combine(m, sum, x, 1.f);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sp_lse_combine(m, sum, __shfl_xor(m, o), __shfl_xor(sum, o));
+    if (lane == 0) {
+        s.redm[wave] = m;
+        s.reds[wave] = sum;
+    }
+
+    // penalties over the distinct ids of the history
+    const int hlen = hstride > 0 ? min(max(history_len[b], 0), hstride) : 0;
+    const bool penal = hlen > 0 && (rep != 1.f || presence != 0.f || frequency != 0.f);
+    if (penal) {
+        int n = 1;
+        while (n < hlen) n <<= 1;
+        const int32_t *h = history + static_cast<size_t>(b) * hstride;
+        for (int i = tid; i < n; i += kSpThreads) {
+            const int t = i < hlen ? h[i] : -1;
+            s.sorted[i] = (t >= 0 && t < V) ? t : INT_MAX;
+        }
+        __syncthreads();
+        for (int k = 2; k <= n; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = tid; i < n; i += kSpThreads) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const int a = s.sorted[i], c = s.sorted[l];
+                        if ((a > c) == ((i & k) == 0)) {
+                            s.sorted[i] = c;
+                            s.sorted[l] = a;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        __syncthreads();   // pass 1's copy of the row is complete
+        for (int i = tid; i < n; i += kSpThreads) {
+            const int t = s.sorted[i];
+            if (t == INT_MAX || (i > 0 && s.sorted[i - 1] == t)) continue;
+            int lo = i + 1, hi = n;   // first index past the run
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s.sorted[mid] == t) lo = mid + 1;
+                else hi = mid;
+            }
+            const float c = static_cast<float>(lo - i);
+            float x = rowf[t];
+            x = x > 0.f ? x / rep : x * rep;
+            x = x - presence;
+            x = x - c * frequency;
+            rowf[t] = x;
+        }
+    }
+    __syncthreads();
+    float lse_m = s.redm[0], lse_s = s.reds[0];
+    for (int i = 1; i < kSpWaves; ++i) sp_lse_combine(lse_m, lse_s, s.redm[i], s.reds[i]);
+
+    // pass 2: keys (value desc, id asc -> the larger (key, ~id)), the maximum and the valid count
+    const bool greedy = temp == 0.f;
+    const float inv_t = greedy ? 1.f : temp;
+    u64 best = 0;
+    int nvalid = 0;
+    for (int t0 = tid; t0 < V; t0 += kSpUnroll * kSpThreads) {
+        float xs[kSpUnroll];
+#pragma unroll
+        for (int u = 0; u < kSpUnroll; ++u) {
+            const int t = t0 + u * kSpThreads;
+            xs[u] = t < V ? rowf[t] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < kSpUnroll; ++u) {
+            const int t = t0 + u * kSpThreads;
+            if (t >= V) break;
+            float x = xs[u];
+            uint32_t k = 0;
+            if (x == x) {
+                if (!greedy) x = fminf(fmaxf(x / inv_t, -FLT_MAX), FLT_MAX);
+                k = sp_key(x);
+                ++nvalid;
+                const u64 c = (static_cast<u64>(k) << 32) | (0xffffffffu - static_cast<uint32_t>(t));
+                best = c > best ? c : best;
+            }
+            keys[t] = k;
+        }
+    }
+    best = sp_max64(best, s);
+    const int valid = static_cast<int>(sp_sum64(static_cast<u64>(nvalid), s));
+    int chosen = end_id;
+    if (valid > 0) chosen = static_cast<int>(0xffffffffu - static_cast<uint32_t>(best & 0xffffffffu));
+
+    if (!greedy && valid > 1) {
+        const float vmax = sp_val(static_cast<uint32_t>(best >> 32));
+        auto mass = [vmax](uint32_t k) -> u64 {
+            const float d = sp_val(k) - vmax;
+            if (!(d > -23.f)) return 0ull;
+            return static_cast<u64>(expf(d) * 4294967296.0f);
+        };
+        // top-k: the top_k-th token (kk, kid); the set {key > kk} + {key == kk, id <= kid}
+        uint32_t kk = 0;
+        int kid = INT_MAX;
+        if (top_k > 0 && top_k < valid) {
+            u64 above;
+            auto all = [](int, uint32_t) { return true; };
+            kk = radix_select(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_k - 1), &above, s);
+            kid = id_select(keys, V, kk, all, static_cast<u64>(top_k - 1) - above, s);
+        }
+        auto in_k = [kk, kid](int t, uint32_t k) { return k > kk || (k == kk && t <= kid); };
+        // top-p: keep every value >= that of the first token at which the mass reaches top_p * the top-k mass
+        uint32_t pk = 0;
+        if (top_p < 1.f) {
+            u64 ms = 0;
+            sp_for_keys(keys, V, [&](int t, uint32_t k) {
+                if (k && in_k(t, k)) ms += mass(k);
+            });
+            ms = sp_sum64(ms, s);
+            u64 thr = static_cast<u64>(ceil(static_cast<double>(top_p) * static_cast<double>(ms)));
+            thr = thr == 0 ? 0 : thr - 1;
+            if (thr >= ms) thr = ms - 1;
+            u64 above;
+            pk = radix_select(keys, V, in_k, mass, thr, &above, s);
+        }
+        auto kept = [=](int t, uint32_t k) {
+            return in_k(t, k) && k >= pk && (min_p == 0.f || expf(sp_val(k) - vmax) >= min_p);
+        };
+        u64 mk = 0;
+        sp_for_keys(keys, V, [&](int t, uint32_t k) {
+            if (k && kept(t, k)) mk += mass(k);
+        });
+        mk = sp_sum64(mk, s);
+        // draw: the first kept token at which the running mass exceeds u * kept mass (u == 1: the last kept token)
+        const float u = uniform_philox(static_cast<uint32_t>(step), p.seed);
+        u64 thr = static_cast<u64>(floor(static_cast<double>(u) * static_cast<double>(mk)));
+        if (thr >= mk) thr = mk - 1;
+        u64 above;
+        const uint32_t dk = radix_select(keys, V, kept, mass, thr, &above, s);
+        const int id = id_select(keys, V, dk, kept, (thr - above) / mass(dk), s);
+        if (id >= 0) chosen = id;
+    }
+
+    if (tid == 0) {
+        out_id[b] = chosen;
+        if (!finished[b]) ++seq_len[b];
+        finished[b] = static_cast<uint8_t>(chosen == end_id);
+        if (out_logprob)
+            out_logprob[b] = (chosen >= 0 && chosen < V && valid > 0) ? to_f32(lg[chosen]) - (lse_m + logf(lse_s)) : -INFINITY;
+        if (happend && hstride > 0) {
+            const int len = history_len[b];
+            if (len >= 0 && len < hstride) {
+                history[static_cast<size_t>(b) * hstride + len] = chosen;
+                history_len[b] = len + 1;
+            }
+        }
+    }
+    if (next_hidden && chosen >= 0 && chosen < V) {
+        // llmie_input_embedding's rule: ids outside the table are skipped
+        const T *src = embed + static_cast<size_t>(chosen) * hidden;
+        T *dst = next_hidden + static_cast<size_t>(b) * hidden;
+        for (int i = tid; i < hidden; i += kSpThreads) dst[i] = src[i];
+    }
+    if (advance && step_dev && tid == 0) {
+        // every thread of the row has read the step (the barriers above): the last row moves the counter, re-zeroes the ticket
+        if (atomicAdd(ticket, 1u) == static_cast<unsigned>(rows) - 1u) {
+            *const_cast<int32_t *>(step_dev) = step + 1;
+            atomicExch(ticket, 0u);
+        }
+    }
+}
+
+size_t sample_logits_ws_row(int vocab) { return (static_cast<size_t>(vocab) + 63) & ~static_cast<size_t>(63); }
+
+int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
+                         int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                         int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                         llmie_dtype dtype, const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket,
+                         hipStream_t st) {
+    const size_t row = sample_logits_ws_row(vocab);
+    uint32_t *ws = static_cast<uint32_t *>(workspace);
+    if (dtype == LLMIE_F16)
+        sample_params_kernel<half_t><<<batch, kSpThreads, 0, st>>>(
+            static_cast<const half_t *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
+            out_id, out_logprob, step, step_dev, end_id, ws, row, static_cast<const half_t *>(embed), static_cast<half_t *>(next_hidden),
+            hidden, advance, ticket, batch);
+    else
+        sample_params_kernel<float><<<batch, kSpThreads, 0, st>>>(
+            static_cast<const float *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
+            out_id, out_logprob, step, step_dev, end_id, ws, row, static_cast<const float *>(embed), static_cast<float *>(next_hidden),
+            hidden, advance, ticket, batch);
+    return launch_status("sample_logits");
+}
+
+int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
+                        int history_stride, const int32_t *history_len, const int32_t *seq_len, const uint8_t *finished,
+                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype) {
+    LLMIE_REQUIRE(logits && params && seq_len && finished && out_id, "sample_logits: NULL pointer");
+    LLMIE_REQUIRE(batch > 0 && vocab > 0, "sample_logits: batch %d / vocab %d must be positive", batch, vocab);
+    LLMIE_REQUIRE(history_stride >= 0, "sample_logits: history_stride %d < 0", history_stride);
+    LLMIE_REQUIRE(history_stride == 0 || (history && history_len), "sample_logits: history_stride %d > 0 without history / history_len",
+                  history_stride);
+    if (history_stride > kSpMaxHistory)
+        LLMIE_UNSUPPORTED("sample_logits: history_stride %d above %d", history_stride, kSpMaxHistory);
+    if (dtype != LLMIE_F16 && dtype != LLMIE_F32) LLMIE_UNSUPPORTED("sample_logits: dtype %d", (int)dtype);
+    const size_t need = llmie_sample_logits_workspace_bytes(batch, vocab);
+    if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
+        set_error("sample_logits: workspace %zu bytes (need %zu, 16-byte aligned)", workspace ? workspace_bytes : (size_t)0, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    return LLMIE_OK;
+}
+
+}  // namespace llmie
+
+using namespace llmie;
+
+extern "C" size_t llmie_sample_logits_workspace_bytes(int batch, int vocab) {
+    if (batch <= 0 || vocab <= 0) return 0;
+    return static_cast<size_t>(batch) * sample_logits_ws_row(vocab) * sizeof(uint32_t);
+}
+
+extern "C" int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
+                                   int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                                   int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                                   size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
+    const int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_id,
+                                       workspace, workspace_bytes, dtype);
+    if (rc != LLMIE_OK) return rc;
+    return sample_logits_launch(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
+                                out_id, out_logprob, step, step_dev, end_id, workspace, dtype, nullptr, nullptr, 0, 0, nullptr,
+                                as_stream(stream));
+}

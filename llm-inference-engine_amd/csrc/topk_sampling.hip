@@ -9,6 +9,7 @@
 //
 // sampling: one lane per sequence; Philox4x32-10 keyed by (step, "LLMI"), counter = batch index.
 #include "device_utils.cuh"
+#include "philox.cuh"
 
 #include <climits>
 
@@ -157,20 +158,7 @@ static int topk_impl(const T *probs, int32_t *tmp_ids, T *tmp_vals, int32_t *ids
 }
 
 // ---------------- sampling ----------------
-__device__ __forceinline__ float uniform_philox(uint32_t seed, uint32_t stream) {
-    uint32_t c0 = stream, c1 = 0, c2 = 0, c3 = 0;
-    uint32_t k0 = seed, k1 = 0x4c4c4d49u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return static_cast<float>((c0 >> 8) + 1u) * (1.0f / 16777216.0f);
-}
+// uniform_philox: philox.cuh (shared with sampling_params.hip)
 
 template <typename T>
 __global__ __launch_bounds__(64) void sampling_kernel(const int32_t *__restrict__ topk_id, const T *__restrict__ topk_val,
