@@ -274,7 +274,8 @@ int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sa
 
 /* y[M,N] = x[M,K] . (scale[n]*Wq[n,k])^T ; x,y,scale,bias fp16; Wq int8 row-major [N,K].
  * workspace: llmie_linear_workspace_bytes(LLMIE_W_INT8 / LLMIE_W_INT4, M, K, N) bytes of caller-owned split-K slabs (see
- * llmie_linear); without it int8 serves M <= 64 and int4 the GEMV sizes only. */
+ * llmie_linear); without it int8 serves M <= 64 and int4 the GEMV sizes only.  int8 shapes none of the int8 kernels take
+ * (8 < M < 192 with K % 256 != 0 beyond 64 rows, or K % 16 != 0) run on an fp16 image of W that the workspace holds as well. */
 int llmie_linear_w8a16(const void *x, const int8_t *wq, const void *scale, void *y,
                        int M, int K, int N, const void *bias, const void *residual,
                        void *workspace, size_t workspace_bytes, llmie_stream stream);

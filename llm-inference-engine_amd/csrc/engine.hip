@@ -990,6 +990,14 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
                               slabs, st);
         return linear_f16_nk(x, (const half_t *)w.data, y, T, K, N, EPI_NONE_, nullptr, residual, slabs, st);
     };
+    // has the gate/up projection a fused SwiGLU form at this T?  (else: projection + llmie_silu_and_mul; e.g. fp16 H < 512 at 65-192
+    // rows, int8 H % 256 != 0 at 9-191 rows, weights at offsets the vector kernels do not take)
+    auto f16_swiglu = [&](const half_t *x, const llmie_matrix &w) {
+        return linear_f16_swiglu_eligible(T, H, 2 * I, x, w.data, act, slabs);
+    };
+    auto wq_swiglu = [&](const half_t *x, const llmie_matrix &w) {
+        return linear_wq_swiglu_eligible(wqbits, T, H, 2 * I, c.int4_group, x, w.data, w.scale, act, slabs, deq, deq_bytes);
+    };
     // context_decoder.cpp:70: exclusive prefix of the lengths (padding offsets are a by-product nobody needs here);
     // the prefix kernel takes [batch, max_q_len] with max_q_len = ceil(T / batch) rows worth of scratch -> use 1 row of T
     if ((rc = llmie_cal_padding_offset(pad, cum, input_lengths, batch, (T + batch - 1) / batch, stream))) return rc;
@@ -1101,7 +1109,19 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
     static const bool short_off = getenv("LLMIE_NO_FUSED_SHORT_PREFILL") != nullptr;
     const int sbits = wqbits ? wqbits : 16;   // split-K kernels' weight-format code
     const bool short_fmt_ok = !fp8 && (wqbits != 4 || (c.int4_group == 128 && T <= 64));   // int4 split-K form: 64 rows, group 128
-    if (!short_off && short_fmt_ok && T <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H)) {
+    // the split-K kernels read the weights, the out-of-place norms hidden_out and the gammas in 16-byte vectors: weights handed over
+    // as views at other offsets (llmie_decoder_create takes any address) run the general sequences below
+    auto a16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    bool w_a16 = true, g_a16 = a16(h);
+    for (int l = 0; l < c.num_layers; ++l) {
+        const llmie_layer_weights &w = dec->layers[l];
+        w_a16 = w_a16 && a16(w.qkv.data) && a16(w.o.data) && a16(w.gate_up.data) && a16(w.down.data);
+        if (wqbits == 4)
+            w_a16 = w_a16 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
+                              reinterpret_cast<uintptr_t>(w.gate_up.scale) | reinterpret_cast<uintptr_t>(w.down.scale)) % 4 == 0;
+        g_a16 = g_a16 && a16(w.attn_norm_gamma) && a16(w.ffn_norm_gamma);
+    }
+    if (!short_off && short_fmt_ok && w_a16 && T <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H)) {
         // int8: row scales applied by the slab consumers; int4: group scales applied inside the split-K kernel
         auto sc_of = [&](const llmie_matrix &m) { return SlabScale{wqbits == 8 ? static_cast<const half_t *>(m.scale) : nullptr, nullptr, nullptr}; };
         auto gs_of = [&](const llmie_matrix &m) { return wqbits == 4 ? static_cast<const half_t *>(m.scale) : nullptr; };
@@ -1151,7 +1171,7 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
     // moves 2 x |S| bytes instead of 3-4 x (context_decoder.cpp:70-199 order).
     // (interleaved A/B on one box, fp16: 1 x 2048 78.15k -> 78.55k tok/s, 8 x 512 89.56k -> 89.87k: the norms drop 13.5 + 15.0 ->
     // 9.7 + 9.7 us per layer, the O projection's residual epilogue costs 6.3 us of that back)
-    bool lean = !fp8 && rmsnorm_oop_eligible(H);
+    bool lean = !fp8 && g_a16 && rmsnorm_oop_eligible(H);
     for (int l = 0; l < c.num_layers && lean; ++l) lean = dec->layers[l].o.bias == nullptr;
     if (lean) {
         half_t *S = h, *Nn = resid;
@@ -1163,10 +1183,10 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
             TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, S, H, H, S));
             TIMED(LLMIE_OP_FFN_NORM, rmsnorm_oop_f16(S, Nn, (const half_t *)w.ffn_norm_gamma, c.rms_eps, T, H, st));
-            if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I))) {
+            if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && wq_swiglu(Nn, w.gate_up)) {
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, Nn, w.gate_up.data, (const half_t *)w.gate_up.scale, act, T, H, 2 * I, c.int4_group,
                                                          EPI_SWIGLU_, nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
-            } else if (!wqbits && (T <= 192 || gemm256_swiglu_fills(T, 2 * I))) {
+            } else if (!wqbits && (T <= 192 || gemm256_swiglu_fills(T, 2 * I)) && f16_swiglu(Nn, w.gate_up)) {
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(Nn, (const half_t *)w.gate_up.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
             } else {
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(Nn, w.gate_up, gu, H, 2 * I, nullptr));
@@ -1207,10 +1227,10 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
         TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, T, H,
                                                                        LLMIE_F16, stream));
         // ffn.cpp:105-122: act = silu(h.Wg^T) * (h.Wu^T); SwiGLU fused into the projection's epilogue where a fused form exists
-        if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I))) {
+        if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && wq_swiglu(h, w.gate_up)) {
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, h, w.gate_up.data, (const half_t *)w.gate_up.scale, act, T, H, 2 * I, c.int4_group,
                                                      EPI_SWIGLU_, nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
-        } else if (!wqbits && !fp8 && (T <= 192 || gemm256_swiglu_fills(T, 2 * I))) {
+        } else if (!wqbits && !fp8 && (T <= 192 || gemm256_swiglu_fills(T, 2 * I)) && f16_swiglu(h, w.gate_up)) {
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(h, (const half_t *)w.gate_up.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
         } else if (fp8 && gemm256_swiglu_fills(T, 2 * I) && H % 128 == 0 && reinterpret_cast<uintptr_t>(w.gate_up.data) % 16 == 0) {
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_linear_fp8_swiglu(h, (const uint8_t *)w.gate_up.data, (const float *)w.gate_up.scale,

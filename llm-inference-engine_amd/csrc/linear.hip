@@ -929,6 +929,15 @@ bool g8p_w8_swiglu_eligible(int M, int K, int two_inter, const void *x, const vo
            (reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(y)) % 8 == 0;
 }
 
+// does linear_f16_nk have a fused SwiGLU form for this call?  (the GEMV, split-K, skinny and 256-row SwiGLU conditions below)
+bool linear_f16_swiglu_eligible(int M, int K, int N, const void *x, const void *W, const void *y, SlabWs ws) {
+    const bool aligned = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16 == 0);
+    if (gemv_f16_eligible(M, K, x, W)) return true;
+    if (ws.p && aligned && M <= 192 && K % 128 == 0 && K >= 512) return true;
+    if (aligned && M <= 64 && K % 32 == 0 && (N / 2) % 16 == 0) return true;
+    return aligned && K % 64 == 0 && gemm256_swiglu_fills(M, N) && reinterpret_cast<uintptr_t>(y) % 8 == 0;
+}
+
 int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
                   const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st) {
     const bool aligned = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16 == 0);

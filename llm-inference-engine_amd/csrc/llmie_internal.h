@@ -18,6 +18,8 @@ struct SlabWs {
 size_t linear_splitk_ws_floats(int wbits, int M, int K, int N);   // 0 = the shape has no split-K form
 int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
                   const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st);
+// true when linear_f16_nk(x, W, y, M, K, N, EPI_SWIGLU_, no bias / residual, ws) has a fused form (else it refuses the call)
+bool linear_f16_swiglu_eligible(int M, int K, int N, const void *x, const void *W, const void *y, SlabWs ws);
 
 // same with rmsnorm(x + pre_bias) * gamma fused in front (GEMV path only; LLMIE_ERR_UNSUPPORTED otherwise)
 bool gemv_f16_eligible(int M, int K, const void *x, const void *W);
@@ -91,6 +93,9 @@ int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half
 int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,
               int epi, const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
               SlabWs ws, hipStream_t st, void *deq = nullptr, size_t deq_bytes = 0);
+// true when linear_wq(..., EPI_SWIGLU_, no bias / residual / norm, ws, deq) has a fused form (else it refuses the call)
+bool linear_wq_swiglu_eligible(int wbits, int M, int K, int N, int group, const void *x, const void *wq, const void *scale, const void *y,
+                               SlabWs ws, const void *deq, size_t deq_bytes);
 
 // ---- packed-weight batch-decode projections (pk_gemm.cuh / pk_linear.hip): 1 <= M <= 32 rows on tile-packed weight images ----
 enum : int { PKF_F16 = 16, PKF_I8 = 8, PKF_I4 = 4, PKF_FP8 = 108 };                 // = PK_F16 ... of pk_gemm.cuh

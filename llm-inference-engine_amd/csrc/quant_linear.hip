@@ -178,8 +178,30 @@ int dequantize_weights_f16(int wbits, const void *wq, const half_t *scale, half_
 }
 
 size_t linear_wq_dequant_bytes(int wbits, int M, int K, int N) {
-    if (M < kWqPrefillRows || (wbits != 8 && wbits != 4) || K % 8 != 0) return 0;
+    if ((wbits != 8 && wbits != 4) || K % 8 != 0) return 0;
+    // below the prefill rows: only int8 shapes that no int8 kernel takes (K not a whole number of the GEMV's 16-byte chunks, of the
+    // split-K sub-blocks or of the 64-row kernel's) read the fp16 image -- the last form of linear_wq
+    const bool int8_form = K % 16 == 0 && (ksplit_eligible(M, K, 8) || (K % 256 == 0 && K >= 512) || (M <= 64 && K % 64 == 0));
+    if (M < kWqPrefillRows && (wbits != 8 || int8_form)) return 0;
     return static_cast<size_t>(N) * K * sizeof(half_t);
+}
+
+// does linear_wq have a fused SwiGLU form for this call (no bias, residual or norm)?  (the conditions of linear_wq below, in order)
+bool linear_wq_swiglu_eligible(int wbits, int M, int K, int N, int group, const void *x, const void *wq, const void *scale, const void *y,
+                               SlabWs ws, const void *deq, size_t deq_bytes) {
+    const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) % 16 == 0) &&
+                         (static_cast<size_t>(K) * wbits / 8) % 16 == 0;
+    if (M >= kWqPrefillRows) {
+        if (wbits == 8 && g8p_w8_swiglu_eligible(M, K, N, x, wq, scale, y)) return true;
+        const size_t need = linear_wq_dequant_bytes(wbits, M, K, N);
+        if (deq && need && deq_bytes >= need && reinterpret_cast<uintptr_t>(deq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 8 == 0 &&
+            (wbits == 8 || (group % 8 == 0 && K % group == 0)) && gemm256_swiglu_fills(M, N))
+            return linear_f16_swiglu_eligible(M, K, N, x, deq, y, SlabWs{nullptr, 0});
+    }
+    if (aligned && ksplit_eligible(M, K, wbits)) return true;
+    if (aligned && wbits == 4 && group == 128 && K % 256 == 0 && K >= 512 && M > 8 && ws.p) return true;
+    if (aligned && wbits == 4 && ksplit_eligible(1, K, 4)) return true;   // (row chunks)
+    return wbits == 8 && aligned && K % 256 == 0 && K >= 512 && ws.p;
 }
 
 int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,

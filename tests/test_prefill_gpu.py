@@ -173,6 +173,101 @@ def test_quantised_prefill_matches_oracle_on_dequantised_weights(llmie, fmt, nam
     dec.close()
 
 
+def _engine_fmt(llmie, layers, fmt, nh, kvh, hs, I, max_seq, max_batch, offset=None):
+    """engine in `fmt` on `layers` + the oracle's layers (de-quantised weights for int8 / int4); offset: None, "weights" or
+    "gammas_weights" -- those operands handed over as views 8 bytes past a 16-byte boundary (e.g. views into one flat buffer)"""
+    def d(a, off=False):
+        if a is None:
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+        t = t.to(F16) if t.is_floating_point() else t
+        if not off:
+            return t
+        n = 8 // t.element_size()
+        buf = torch.empty(t.numel() + n, dtype=t.dtype, device=DEV)
+        v = buf[n:].view(t.shape)
+        v.copy_(t)
+        return v
+    eng, olayers = [], []
+    for w in layers:
+        e = dict(attn_norm=d(w["attn_norm"], offset == "gammas_weights"), ffn_norm=d(w["ffn_norm"], offset == "gammas_weights"))
+        o = dict(w)
+        for m in ("qkv", "o", "gate_up", "down"):
+            if fmt == "f16":
+                e[m] = dict(data=d(w[m], offset is not None))
+            else:
+                q, s, deq = _quantise(w[m], fmt)
+                e[m] = dict(data=d(q, offset is not None), scale=d(s))
+                o[m] = deq
+        e["o"]["bias"] = d(w["o_bias"])
+        eng.append(e)
+        olayers.append(o)
+    cfg = dict(head_num=nh, kv_head_num=kvh, head_size=hs, inter_size=I, num_layers=len(layers), vocab_size=100, max_seq_len=max_seq,
+               max_batch=max_batch, rotary_dim=hs, rotary_base=10000.0, rms_eps=1e-5, dtype=llmie.F16,
+               wfmt=dict(f16=llmie.W_F16, int8=llmie.W_INT8, int4=llmie.W_INT4)[fmt], int4_group=128)
+    return llmie.Decoder(cfg, eng), olayers
+
+
+def _prefill_vs_oracle(dec, olayers, rng, nh, kvh, hs, I, max_seq, lens, hist, label):
+    L, H, bs, T = len(olayers), nh * hs, len(lens), int(sum(lens))
+    x = _h(rng.standard_normal((T, H)).astype(np.float32))
+    kc = _h(rng.standard_normal((L, bs, kvh, max_seq, hs)).astype(np.float32) * 0.5)
+    vc = _h(rng.standard_normal((L, bs, kvh, max_seq, hs)).astype(np.float32) * 0.5)
+    kd, vd = torch.from_numpy(kc).to(DEV).to(F16), torch.from_numpy(vc).to(DEV).to(F16)
+    xd = torch.from_numpy(x).to(DEV).to(F16)
+    out = torch.empty_like(xd)
+    dec.prefill(xd, out, kd, vd, torch.tensor(lens, dtype=torch.int32, device=DEV), torch.tensor(hist, dtype=torch.int32, device=DEV), max(lens))
+    exp = oracle_prefill(olayers, x, kc, vc, np.array(lens, np.int32), np.array(hist, np.int32), nh, kvh, hs, I, max_seq)
+    got = out.float().cpu().numpy()
+    err = np.abs(got - exp)
+    assert (err <= 3e-2 + 3e-2 * np.abs(exp)).all(), "%s: max err %g (|exp| max %g)" % (label, err.max(), np.abs(exp).max())
+    fro, proj = systematic_error(got, exp)
+    assert fro <= FRO_F16 and proj <= PROJ_F16, "%s: relative Frobenius error %.3g, projection on the signal %.3g" % (label, fro, proj)
+    assert np.abs(kd.float().cpu().numpy() - kc).max() <= 2e-2, label
+    assert np.abs(vd.float().cpu().numpy() - vc).max() <= 2e-2, label
+
+
+# token counts across the projection routes of a small model: GEMV (5), skinny / split-K (40), the 65..192 forms (100, 150), the
+# prefill-sized forms (300); single sequences without history and ragged batches with history
+ODD_LENS = [([5], [0]), ([40], [0]), ([100], [0]), ([150], [0]), ([300], [0]), ([70, 30], [0, 9]), ([150, 4, 146], [3, 0, 21])]
+# H = 384 / 1152 (head_num 3 / 9: not multiples of 256, H < 512 for 3), I not a multiple of 16 / 128, with and without an output
+# bias (the lean in-place sequence and the classic one)
+ODD = [("h384_kv1_i1000", 3, 1, 1000, False), ("h384_kv3_i1024_bias", 3, 3, 1024, True),
+       ("h1152_kv3_i1000_bias", 9, 3, 1000, True), ("h1152_kv9_i1024", 9, 9, 1024, False)]
+
+
+@pytest.mark.parametrize("fmt", ["f16", "int8", "int4"])
+@pytest.mark.parametrize("name,nh,kvh,I,o_bias", ODD, ids=[c[0] for c in ODD])
+def test_odd_shape_prefill_matches_oracle(llmie, fmt, name, nh, kvh, I, o_bias):
+    """shapes config_ok accepts but no other prefill case uses: used to refuse (LLMIE_ERR_UNSUPPORTED) where the gate/up projection
+    was sent to a fused SwiGLU form the shape does not have -- fp16 H < 512 at 65..192 tokens (and I % 16 != 0 below), int8
+    H % 256 != 0 at 9..191 tokens"""
+    rng = np.random.default_rng(53 + nh + I)
+    hs, L, max_seq = 128, 2, 384
+    if fmt == "int4":
+        I = I // 128 * 128   # group-128 scales along K of the down projection
+    layers = _model(rng, nh, kvh, hs, I, L, o_bias=o_bias)
+    dec, olayers = _engine_fmt(llmie, layers, fmt, nh, kvh, hs, I, max_seq, 3)
+    for lens, hist in ODD_LENS:
+        _prefill_vs_oracle(dec, olayers, rng, nh, kvh, hs, I, max_seq, lens, hist, "%s %s lens %s hist %s" % (fmt, name, lens, hist))
+    dec.close()
+
+
+@pytest.mark.parametrize("fmt", ["f16", "int8", "int4"])
+@pytest.mark.parametrize("offset", ["weights", "gammas_weights"])
+def test_prefill_with_weights_at_8_byte_offsets(llmie, fmt, offset):
+    """weight matrices (and norm gammas) handed over as views 8 bytes past a 16-byte boundary: the split-K short path, the fused
+    SwiGLU forms and the out-of-place norms of the lean sequence take 16-byte vectors only -- such prefills must run the general
+    kernels instead of refusing.  (max_batch 1: engines with a packed copy for batch decode need 16-byte aligned weights at create.)"""
+    rng = np.random.default_rng(59)
+    nh, hs, I, L, max_seq = 8, 128, 1024, 2, 384
+    layers = _model(rng, nh, nh, hs, I, L)
+    dec, olayers = _engine_fmt(llmie, layers, fmt, nh, nh, hs, I, max_seq, 1, offset=offset)
+    for T in (5, 40, 100, 300):
+        _prefill_vs_oracle(dec, olayers, rng, nh, nh, hs, I, max_seq, [T], [0], "%s %s T %d" % (fmt, offset, T))
+    dec.close()
+
+
 def test_prefill_then_decode_consistency(llmie):
     rng = np.random.default_rng(42)
     nh, hs, I, L, max_seq, n = 8, 128, 1376, 2, 256, 150
