@@ -128,6 +128,16 @@ int llmie_linear(const void *x, const void *w, void *y, int M, int K, int N, int
 int llmie_linear_swiglu(const void *x, const void *w, void *y, int M, int K, int two_inter,
                         llmie_dtype dtype, void *workspace, size_t workspace_bytes, llmie_stream stream);
 
+/* Which kernel route llmie_linear (fmt LLMIE_W_F16, fp16, trans_b) / llmie_linear_swiglu (swiglu != 0) / llmie_linear_w8a16 /
+ * llmie_linear_w4a16 would run this call on: the planned route's name ("splitk", "tiles256", "g8p", ...; the fp16 image routes
+ * of int8 / int4 weights as "image_prefill+<route of the fp16 GEMM>"), from the same planner the entry points launch from.
+ * Pure host function: the pointers are never dereferenced (only their alignment counts), the workspace is split exactly as the
+ * entry points split it.  scale / group as in _w8a16 / _w4a16 (ignored for fp16).  A call the entry point would refuse returns
+ * NULL and leaves the reason in llmie_last_error().  The string is valid until the thread's next call. */
+const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const void *w, const void *scale, const void *y, int M,
+                               int K, int N, int swiglu, int group, const void *bias, const void *residual,
+                               const void *workspace, size_t workspace_bytes);
+
 /* replaces launchLinearStridedBatchGemm src/kernels/linear.cu:89-158 (+ cublas_utils.cpp:95-154)
  * per batch i: C_i[m,n] = A_i[m,k] . B_i  (B_i is [n,k] if trans_b else [k,n]); dense strides */
 int llmie_batched_gemm(const void *a, const void *b, void *c, int batch, int m, int n, int k,

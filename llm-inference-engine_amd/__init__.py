@@ -50,6 +50,7 @@ _SIGS = {
     "llmie_linear_workspace_bytes": [_i, _i, _i, _i],
     "llmie_linear": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp],
     "llmie_linear_swiglu": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp],
+    "llmie_linear_route": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz],
     "llmie_batched_gemm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "llmie_qkv_bias_transpose_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     "llmie_rope_decode": [_vp, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _vp],
@@ -125,6 +126,7 @@ _RESTYPES = {
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
+    "llmie_linear_route": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
 }
 
@@ -215,6 +217,13 @@ def add_residual(resid, out):
 def linear_workspace_bytes(fmt, M, K, N):
     """bytes of caller-owned split-K slab scratch llmie_linear / _swiglu / _w8a16 / _w4a16 use for this shape (0: none)"""
     return lib().llmie_linear_workspace_bytes(fmt, M, K, N)
+
+
+def linear_route(fmt, x, w, scale, y, M, K, N, swiglu=False, group=0, bias=None, residual=None, workspace=None, workspace_bytes=0):
+    """name of the kernel route the projection entry points plan for this call, None where they refuse it (llmie_last_error() says
+    why).  The operands are ADDRESSES (ints, never dereferenced: only their alignment counts) -- no device needed."""
+    r = lib().llmie_linear_route(fmt, x, w, scale, y, M, K, N, int(swiglu), group, bias, residual, workspace, workspace_bytes)
+    return r.decode() if r is not None else None
 
 
 _scratch = {}

@@ -884,17 +884,15 @@ extern "C" int llmie_decoder_forward_paged(llmie_decoder *dec, const void *hidde
     return rc;
 }
 
-// slabs of a prefill pass: the engine format's plans up to 192 rows, and -- for projections whose 256-row grid does not fill the chip
-// at T rows, which fp16 engines and the fp16 weight images of int4 / packed-only engines may run as 128-row split-K passes
-// (linear_f16_nk's time model) -- the fp16 plans at 128 rows
+// slabs of a prefill pass: the engine format's plans up to 192 rows, and -- beyond, where fp16 engines and the fp16 weight images of
+// int4 / packed-only engines may run a projection as 128-row split-K passes -- what the fp16 projections reserve at T rows
 static size_t prefill_slab_floats(const llmie_decoder_config *c, int T) {
     size_t m = engine_slab_floats(c, T < 192 ? T : 192);
     if (T > 192 && c->wfmt != LLMIE_W_FP8) {
         const int H = c->head_num * c->head_size, QKV = (c->head_num + 2 * c->kv_head_num) * c->head_size, I = c->inter_size;
         const int shapes[4][2] = {{H, QKV}, {H, H}, {H, 2 * I}, {I, H}};
         for (const auto &sh : shapes) {
-            if (gemm256_fills(T, sh[1])) continue;
-            const size_t f = linear_splitk_ws_floats(16, 128, sh[0], sh[1]);
+            const size_t f = linear_f16_reserve_slab_floats(T, sh[0], sh[1]);
             m = f > m ? f : m;
         }
     }
@@ -914,14 +912,12 @@ static size_t prefill_carve(const llmie_decoder_config *c, int T, int B, size_t 
     // fp8 engines: per-token e4m3 image + scales of the activation matrix entering each projection
     o[7] = k.take(c->wfmt == LLMIE_W_FP8 ? llmie_linear_fp8_workspace_bytes(T, static_cast<int>(I > H ? I : H), 0) : 256);
     o[8] = k.take(prefill_slab_floats(c, T) * sizeof(float) + 256);   // split-K slabs (short prefills; fp8 passes; mid-size fp16 passes)
-    // int8 / int4 engines at prefill-sized T: room for the fp16 image of the largest matrix (projections without an in-kernel
-    // de-quantising form: int4, and int8 shapes whose 256-row grid does not fill the chip)
+    // int8 / int4 / packed-only engines: room for the fp16 image of the largest matrix, at every T -- at least the image_bytes of any
+    // plan (plan_linear_wq's image routes; packed-only engines unpack every matrix), and more where the plan needs none: kept
     size_t dq = 0;
     if (c->wfmt == LLMIE_W_INT8 || c->wfmt == LLMIE_W_INT4 || (c->flags & LLMIE_DEC_PACKED_ONLY)) {
-        const int bits = c->wfmt == LLMIE_W_INT8 ? 8 : 4;
         const size_t shapes[4][2] = {{H, QKV}, {H, H}, {H, 2 * I}, {I, H}};
-        (void)bits;
-        for (const auto &sh : shapes) {   // (any T: shapes outside the quantised kernels' K sub-blocks take the image at every size)
+        for (const auto &sh : shapes) {
             const size_t b = sh[0] * sh[1] * sizeof(half_t);
             dq = b > dq ? b : dq;
         }
@@ -990,13 +986,23 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
                               slabs, st);
         return linear_f16_nk(x, (const half_t *)w.data, y, T, K, N, EPI_NONE_, nullptr, residual, slabs, st);
     };
-    // has the gate/up projection a fused SwiGLU form at this T?  (else: projection + llmie_silu_and_mul; e.g. fp16 H < 512 at 65-192
-    // rows, int8 H % 256 != 0 at 9-191 rows, weights at offsets the vector kernels do not take)
-    auto f16_swiglu = [&](const half_t *x, const llmie_matrix &w) {
-        return linear_f16_swiglu_eligible(T, H, 2 * I, x, w.data, act, slabs);
-    };
-    auto wq_swiglu = [&](const half_t *x, const llmie_matrix &w) {
-        return linear_wq_swiglu_eligible(wqbits, T, H, 2 * I, c.int4_group, x, w.data, w.scale, act, slabs, deq, deq_bytes);
+    // act = swiglu(x . Wgu^T) of fp16 / int8 / int4 engines (ffn.cpp:105-122): fused into the projection's epilogue where the plan has
+    // a form, else projection + llmie_silu_and_mul (e.g. fp16 H < 512 at 65-192 rows, int8 H % 256 != 0 at 9-191 rows, weights at
+    // offsets the vector kernels do not take).  Quantised weights at prefill-sized T fuse only where the 256-row SwiGLU grid fills
+    // the chip: the split-K and row-chunk forms the plan has left there cost more than the two launches.
+    auto gate_up = [&](const half_t *x, const llmie_matrix &w) -> int {
+        const LinearCall gc = linear_call(wqbits ? wqbits : 16, T, H, 2 * I, EPI_SWIGLU_, c.int4_group, x, w.data, w.scale, act, nullptr, nullptr,
+                                          nullptr, nullptr, slabs, wqbits ? deq : nullptr, deq_bytes);
+        if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && plan_linear_wq(gc).route != LR_REFUSED) {
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, x, w.data, (const half_t *)w.scale, act, T, H, 2 * I, c.int4_group, EPI_SWIGLU_,
+                                                     nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
+        } else if (!wqbits && plan_linear_f16(gc).route != LR_REFUSED) {
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(x, (const half_t *)w.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
+        } else {
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(x, w, gu, H, 2 * I, nullptr));
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+        }
+        return LLMIE_OK;
     };
     // context_decoder.cpp:70: exclusive prefix of the lengths (padding offsets are a by-product nobody needs here);
     // the prefix kernel takes [batch, max_q_len] with max_q_len = ceil(T / batch) rows worth of scratch -> use 1 row of T
@@ -1040,13 +1046,16 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
                 *fused = 1;
                 return qkv_rope(l, w, 0, x, nullptr, w.data, nullptr);
             }
-            if (wqbits == 8 && g8p_w8_eligible(T, H, QKV, x, w.data, w.scale, qkv) && gemm256_qkv_rope_eligible(8, T, QKV, H, x, w.data, w.scale, qkv)) {
+            // int8 / int4: the route proj() would take -- the eight-phase int8 form, or (int4, and int8 shapes without the in-kernel
+            // form) the fp16 image of the matrix -- with the epilogue on the same kernels
+            const int route = !wqbits ? LR_REFUSED
+                                      : plan_linear_wq(linear_call(wqbits, T, H, QKV, EPI_NONE_, c.int4_group, x, w.data, w.scale, qkv, nullptr, nullptr,
+                                                                   nullptr, nullptr, slabs, deq, deq_bytes)).route;
+            if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(8, T, QKV, H, x, w.data, w.scale, qkv)) {
                 *fused = 1;
                 return qkv_rope(l, w, 8, x, nullptr, w.data, w.scale);
             }
-            // int4 (and int8 shapes without the in-kernel form): the fp16 image of the matrix, as linear_wq takes it
-            if (wqbits && deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) && H % 8 == 0 && reinterpret_cast<uintptr_t>(w.data) % 8 == 0 &&
-                (wqbits == 8 || (c.int4_group % 8 == 0 && H % c.int4_group == 0)) && gemm256_qkv_rope_eligible(0, T, QKV, H, x, deq, nullptr, qkv)) {
+            if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(0, T, QKV, H, x, deq, nullptr, qkv)) {
                 int rc2 = dequantize_weights_f16(wqbits, w.data, static_cast<const half_t *>(w.scale), static_cast<half_t *>(deq), QKV, H, c.int4_group, st);
                 if (rc2) return rc2;
                 *fused = 1;
@@ -1096,7 +1105,9 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
             TIMED(LLMIE_OP_O_GEMM, pproj(pw.o, w.o.scale, 0, attn, h, H, H, EPI_NONE_, nullptr));
             TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
-            if (T <= 192 || gemm256_swiglu_fills(T, 2 * I)) {
+            // (the gate_up helper's choice for fp16 weights, on the unpacked image)
+            if (plan_linear_f16(linear_call(16, T, H, 2 * I, EPI_SWIGLU_, 0, h, deq, nullptr, act, nullptr, nullptr, nullptr, nullptr, slabs, nullptr, 0))
+                    .route != LR_REFUSED) {
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, act, H, 2 * I, EPI_SWIGLU_, nullptr));
             } else {
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, gu, H, 2 * I, EPI_NONE_, nullptr));
@@ -1183,15 +1194,7 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
             TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, S, H, H, S));
             TIMED(LLMIE_OP_FFN_NORM, rmsnorm_oop_f16(S, Nn, (const half_t *)w.ffn_norm_gamma, c.rms_eps, T, H, st));
-            if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && wq_swiglu(Nn, w.gate_up)) {
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, Nn, w.gate_up.data, (const half_t *)w.gate_up.scale, act, T, H, 2 * I, c.int4_group,
-                                                         EPI_SWIGLU_, nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
-            } else if (!wqbits && (T <= 192 || gemm256_swiglu_fills(T, 2 * I)) && f16_swiglu(Nn, w.gate_up)) {
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(Nn, (const half_t *)w.gate_up.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
-            } else {
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(Nn, w.gate_up, gu, H, 2 * I, nullptr));
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
-            }
+            if ((rc = gate_up(Nn, w.gate_up))) return rc;
             TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, S, I, H, S));
         }
         return LLMIE_OK;
@@ -1227,12 +1230,9 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
         TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, T, H,
                                                                        LLMIE_F16, stream));
         // ffn.cpp:105-122: act = silu(h.Wg^T) * (h.Wu^T); SwiGLU fused into the projection's epilogue where a fused form exists
-        if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && wq_swiglu(h, w.gate_up)) {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, h, w.gate_up.data, (const half_t *)w.gate_up.scale, act, T, H, 2 * I, c.int4_group,
-                                                     EPI_SWIGLU_, nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
-        } else if (!wqbits && !fp8 && (T <= 192 || gemm256_swiglu_fills(T, 2 * I)) && f16_swiglu(h, w.gate_up)) {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(h, (const half_t *)w.gate_up.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
-        } else if (fp8 && gemm256_swiglu_fills(T, 2 * I) && H % 128 == 0 && reinterpret_cast<uintptr_t>(w.gate_up.data) % 16 == 0) {
+        if (!fp8) {
+            if ((rc = gate_up(h, w.gate_up))) return rc;
+        } else if (gu_fused8) {
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_linear_fp8_swiglu(h, (const uint8_t *)w.gate_up.data, (const float *)w.gate_up.scale,
                                                                    act, T, H, 2 * I, f8ws, f8ws_bytes, stream));
         } else {

@@ -10,7 +10,7 @@
 namespace llmie {
 
 // ---- decode GEMV dispatch ----
-// K-split kernel: XC = 16-byte chunks per thread = ceil(K*WBITS/128/256) rounded up to {1,2,3,4,6,8}; RPW rows per
+// K-split kernel: XC = 16-byte chunks per thread = ceil(K*WBITS/128/256) rounded up to a form of the table below; RPW rows per
 // iteration so that RPW*XC ~ 16 loads are in flight per lane; register budget M*XC*XE <= 16 half8 of activations.
 template <int M, int RPW, int XC, int WBITS, bool DB = false, bool FP8 = false, int RI = 1> static void launch_ksplit(const GemvArgs &a, hipStream_t st) {
     const bool swiglu = a.epi == EPI_SWIGLU;
@@ -26,69 +26,77 @@ template <int M, int RPW, int XC, int WBITS, bool DB = false, bool FP8 = false, 
 
 static int ksplit_xc(int K, int wbits) { return (K * wbits / 128 + 255) / 256; }
 
-template <int M, int WBITS, bool FP8 = false> static bool dispatch_ksplit(const GemvArgs &a, hipStream_t st) {
-    constexpr int XE = WFmt<WBITS>::XE;
-    const int xc = ksplit_xc(a.K, WBITS);
-    if constexpr (M * 1 * XE <= 16) {
-        if (xc <= 1) {  // quantised rows are short: 8 rows per group, double buffered (16 loads in flight per lane)
-            if constexpr (WBITS == 4) {
-                // rows of at most 2 KiB (K <= 4096): two consecutive rows per workgroup instruction, or half the threads idle
-                if (a.K * WBITS / 128 <= 128 && (a.epi != EPI_SWIGLU || (a.N / 2) % 2 == 0)) {
-                    launch_ksplit<M, 8, 1, WBITS, true, FP8, 2>(a, st);
-                    return true;
-                }
-            }
-            if constexpr (WBITS == 16) launch_ksplit<M, 8, 1, 16>(a, st);
-            else launch_ksplit<M, (WBITS == 8 && !FP8) ? 4 : 8, 1, WBITS, true, FP8>(a, st);   // int8: 4 rows per iteration (+2.8 % in A/B); fp8, int4: 8
-            return true;
-        }
-    }
-    if constexpr (M * 2 * XE <= 16) {
-        if (xc <= 2) {
-            if constexpr (WBITS == 16) launch_ksplit<M, 4, 2, 16>(a, st);   // 4 rows x 2 chunks per iteration: A/B against 8 x 2 (+1.6 % batch 1, +4.4 % batch 3) and 2 x 2, 16 x 2
-            else launch_ksplit<M, 4, 2, WBITS, true, FP8>(a, st);
-            return true;
-        }
-    }
-    if constexpr (M * 3 * XE <= 16 && WBITS != 16) {
-        if (xc <= 3) { launch_ksplit<M, 2, 3, WBITS, true, FP8>(a, st); return true; }
-    }
-    if constexpr (M * 4 * XE <= 16 && WBITS == 16) {
-        if (xc <= 4) { launch_ksplit<M, 4, 4, WBITS>(a, st); return true; }
-    }
-    if constexpr (M * 6 * XE <= 16 && WBITS == 16) {
-        if (xc <= 6) { launch_ksplit<M, 4, 6, WBITS>(a, st); return true; }
-    }
-    if constexpr (M * 8 * XE <= 16 && WBITS == 16) {
-        if (xc <= 8) { launch_ksplit<M, 2, 8, WBITS>(a, st); return true; }
-    }
-    return false;
+// The forms of the K-split kernel, by 16-byte chunks per thread: a row of ksplit_xc chunks runs on the first form that covers it, if
+// M rows of it fit the register budget.  One table for the eligibility test and for the launcher.
+struct KsplitForm {
+    int xc, rpw;   // chunks per thread, rows per iteration (xc = 0: no such form)
+};
+constexpr int kKsplitForms = 5;
+constexpr KsplitForm ksplit_form_at(int wbits, bool fp8, int i) {
+    // fp16, two chunks: 4 rows per iteration in A/B against 8 x 2 (+1.6 % batch 1, +4.4 % batch 3) and 2 x 2, 16 x 2
+    constexpr KsplitForm f16[kKsplitForms] = {{1, 8}, {2, 4}, {4, 4}, {6, 4}, {8, 2}};
+    // quantised rows are short: double buffered (16 loads in flight per lane)
+    constexpr KsplitForm q[kKsplitForms] = {{1, 8}, {2, 4}, {3, 2}, {0, 0}, {0, 0}};
+    if (wbits == 16) return f16[i];
+    if (i == 0 && wbits == 8 && !fp8) return KsplitForm{1, 4};   // int8: 4 rows per iteration (+2.8 % in A/B); fp8, int4: 8
+    return q[i];
 }
-
-bool ksplit_eligible(int M, int K, int wbits) {
+// index of the form that takes (M, K), -1: none
+static int ksplit_form(int M, int K, int wbits) {
+    if (M < 1 || M > 8 || K % (128 / wbits) != 0) return -1;   // whole 16-byte chunks
     const int xe = wbits == 16 ? 1 : (wbits == 8 ? 2 : 4);
     const int xc = ksplit_xc(K, wbits);
-    if (K % (128 / wbits) != 0) return false;  // whole 16-byte chunks
-    int xcr;  // the XC the dispatcher would round to
-    if (xc <= 1) xcr = 1;
-    else if (xc <= 2) xcr = 2;
-    else if (wbits != 16) xcr = xc <= 3 ? 3 : 99;
-    else xcr = xc <= 4 ? 4 : (xc <= 6 ? 6 : (xc <= 8 ? 8 : 99));
-    return M >= 1 && M <= 8 && M * xcr * xe <= 16;
+    for (int i = 0; i < kKsplitForms; ++i) {
+        const KsplitForm f = ksplit_form_at(wbits, false, i);
+        if (f.xc && xc <= f.xc) return M * f.xc * xe <= 16 ? i : -1;
+    }
+    return -1;
+}
+bool ksplit_eligible(int M, int K, int wbits) { return ksplit_form(M, K, wbits) >= 0; }
+
+template <int M, int WBITS, bool FP8, int I> static void launch_ksplit_form(const GemvArgs &a, hipStream_t st) {
+    constexpr KsplitForm f = ksplit_form_at(WBITS, FP8, I);
+    if constexpr (f.xc != 0 && M * f.xc * WFmt<WBITS>::XE <= 16) {   // (register budget: ksplit_form picks no other)
+        if constexpr (WBITS == 4 && I == 0) {
+            // rows of at most 2 KiB (K <= 4096): two consecutive rows per workgroup instruction, or half the threads idle
+            if (a.K * WBITS / 128 <= 128 && (a.epi != EPI_SWIGLU || (a.N / 2) % 2 == 0)) {
+                launch_ksplit<M, 8, 1, WBITS, true, FP8, 2>(a, st);
+                return;
+            }
+        }
+        launch_ksplit<M, f.rpw, f.xc, WBITS, WBITS != 16, FP8>(a, st);
+    }
+}
+template <int M, int WBITS, bool FP8 = false> static void dispatch_ksplit(int form, const GemvArgs &a, hipStream_t st) {
+    switch (form) {
+        case 0: launch_ksplit_form<M, WBITS, FP8, 0>(a, st); break;
+        case 1: launch_ksplit_form<M, WBITS, FP8, 1>(a, st); break;
+        case 2: launch_ksplit_form<M, WBITS, FP8, 2>(a, st); break;
+        case 3: launch_ksplit_form<M, WBITS, FP8, 3>(a, st); break;
+        case 4: launch_ksplit_form<M, WBITS, FP8, 4>(a, st); break;
+        default: break;
+    }
 }
 
-template <int M> static bool dispatch_gemv_m(const GemvArgs &a, hipStream_t st) {
-    if (dispatch_ksplit<M, 16>(a, st)) return true;
-    if (static_cast<size_t>(M) * a.K * 2 > 64 * 1024) return false;
+// the GEMV family's route for M rows of K (16-byte aligned operands): K-split register budget, else the LDS fallback's 64 KB
+static int gemv_f16_route(int M, int K) {
+    if (K % 8 || M < 1 || M > 8) return LR_REFUSED;
+    if (ksplit_form(M, K, 16) >= 0) return LR_GEMV_KSPLIT;
+    return static_cast<size_t>(M) * K * 2 <= 64 * 1024 ? LR_GEMV_LDS : LR_REFUSED;
+}
+
+template <int M> static void dispatch_gemv_m(const GemvArgs &a, hipStream_t st) {
+    const int form = ksplit_form(M, a.K, 16);
+    if (form >= 0) return dispatch_ksplit<M, 16>(form, a, st);
     const bool swiglu = a.epi == EPI_SWIGLU;
     const int npairs = swiglu ? a.N / 2 : (a.N + 1) / 2;
     int wgs = (npairs + 3) / 4;
     if (wgs > 2048) wgs = 2048;
     gemv_lds_kernel<M><<<wgs, 256, static_cast<size_t>(M) * a.K * sizeof(half_t), st>>>(a);
-    return true;
 }
 
-static bool dispatch_gemv(int M, const GemvArgs &a, hipStream_t st) {
+// fp16 GEMV; needs gemv_f16_route(M, a.K) != LR_REFUSED
+static void dispatch_gemv(int M, const GemvArgs &a, hipStream_t st) {
     switch (M) {
         case 1: return dispatch_gemv_m<1>(a, st);
         case 2: return dispatch_gemv_m<2>(a, st);
@@ -98,64 +106,55 @@ static bool dispatch_gemv(int M, const GemvArgs &a, hipStream_t st) {
         case 6: return dispatch_gemv_m<6>(a, st);
         case 7: return dispatch_gemv_m<7>(a, st);
         case 8: return dispatch_gemv_m<8>(a, st);
-        default: return false;
+        default: return;
     }
 }
 
-// quantised-weight GEMV (M <= 8): true when launched
-template <int WBITS> static bool dispatch_gemv_q(int M, const GemvArgs &a, hipStream_t st) {
+// quantised-weight GEMV (M <= 8): true when launched (a form of the table takes the shape)
+template <int WBITS, bool FP8 = false> static bool dispatch_gemv_q(int M, const GemvArgs &a, hipStream_t st) {
+    const int form = ksplit_form(M, a.K, WBITS);
+    if (form < 0) return false;
     switch (M) {
-        case 1: return dispatch_ksplit<1, WBITS>(a, st);
-        case 2: return dispatch_ksplit<2, WBITS>(a, st);
-        case 3: return dispatch_ksplit<3, WBITS>(a, st);
-        case 4: return dispatch_ksplit<4, WBITS>(a, st);
-        case 5: return dispatch_ksplit<5, WBITS>(a, st);
-        case 6: return dispatch_ksplit<6, WBITS>(a, st);
-        case 7: return dispatch_ksplit<7, WBITS>(a, st);
-        case 8: return dispatch_ksplit<8, WBITS>(a, st);
-        default: return false;
+        case 1: dispatch_ksplit<1, WBITS, FP8>(form, a, st); break;
+        case 2: dispatch_ksplit<2, WBITS, FP8>(form, a, st); break;
+        case 3: dispatch_ksplit<3, WBITS, FP8>(form, a, st); break;
+        case 4: dispatch_ksplit<4, WBITS, FP8>(form, a, st); break;
+        case 5: dispatch_ksplit<5, WBITS, FP8>(form, a, st); break;
+        case 6: dispatch_ksplit<6, WBITS, FP8>(form, a, st); break;
+        case 7: dispatch_ksplit<7, WBITS, FP8>(form, a, st); break;
+        default: dispatch_ksplit<8, WBITS, FP8>(form, a, st); break;
     }
+    return true;
 }
-bool gemv_q_launch(int wbits, int M, const GemvArgs &a, hipStream_t st) {
-    return wbits == 8 ? dispatch_gemv_q<8>(M, a, st) : dispatch_gemv_q<4>(M, a, st);
+void gemv_q_launch(int wbits, int M, const GemvArgs &a, hipStream_t st) {
+    if (wbits == 8) dispatch_gemv_q<8>(M, a, st);
+    else dispatch_gemv_q<4>(M, a, st);
 }
 // fp8 (e4m3 weights, fp32 row scales in a.scale, activations quantised per token in the prologue)
-bool gemv_fp8_launch(int M, const GemvArgs &a, hipStream_t st) {
-    switch (M) {
-        case 1: return dispatch_ksplit<1, 8, true>(a, st);
-        case 2: return dispatch_ksplit<2, 8, true>(a, st);
-        case 3: return dispatch_ksplit<3, 8, true>(a, st);
-        case 4: return dispatch_ksplit<4, 8, true>(a, st);
-        case 5: return dispatch_ksplit<5, 8, true>(a, st);
-        case 6: return dispatch_ksplit<6, 8, true>(a, st);
-        case 7: return dispatch_ksplit<7, 8, true>(a, st);
-        case 8: return dispatch_ksplit<8, 8, true>(a, st);
-        default: return false;
-    }
-}
+bool gemv_fp8_launch(int M, const GemvArgs &a, hipStream_t st) { return dispatch_gemv_q<8, true>(M, a, st); }
 
 template <int EPI>
-static bool dispatch_skinny(int M, const half_t *x, const half_t *W, half_t *y, int K, int N,
+static void dispatch_skinny(int M, const half_t *x, const half_t *W, half_t *y, int K, int N,
                             const half_t *bias, const half_t *residual, hipStream_t st) {
     constexpr int NW = 8;
     const int mt = (M + 15) / 16;
     if constexpr (EPI == EPI_SWIGLU) {
         const int wgs = (N / 2 + 15) / 16;
         switch (mt) {
-            case 1: skinny_mfma_f16_kernel<1, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 2: skinny_mfma_f16_kernel<2, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 3: skinny_mfma_f16_kernel<3, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 4: skinny_mfma_f16_kernel<4, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            default: return false;
+            case 1: skinny_mfma_f16_kernel<1, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 2: skinny_mfma_f16_kernel<2, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 3: skinny_mfma_f16_kernel<3, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 4: skinny_mfma_f16_kernel<4, 2, NW, EPI><<<wgs, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            default: break;
         }
     } else {
         const int tiles = (N + 15) / 16;
         switch (mt) {
-            case 1: skinny_mfma_f16_kernel<1, 1, NW, EPI><<<tiles, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 2: skinny_mfma_f16_kernel<2, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 3: skinny_mfma_f16_kernel<3, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            case 4: skinny_mfma_f16_kernel<4, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); return true;
-            default: return false;
+            case 1: skinny_mfma_f16_kernel<1, 1, NW, EPI><<<tiles, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 2: skinny_mfma_f16_kernel<2, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 3: skinny_mfma_f16_kernel<3, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            case 4: skinny_mfma_f16_kernel<4, 2, NW, EPI><<<(tiles + 1) / 2, NW * 64, 0, st>>>(x, W, y, M, K, N, bias, residual); break;
+            default: break;
         }
     }
 }
@@ -583,10 +582,9 @@ int splitk_rownorm(const SplitKSlabs &sk, const SlabScale &wscale, const half_t 
     return launch_status("splitk_rownorm");
 }
 
-// does the GEMV family take (M, K)?  (K-split register budget, else the LDS fallback's 64 KB)
+// does the GEMV family take (M, K)?
 bool gemv_f16_eligible(int M, int K, const void *x, const void *W) {
-    if (K % 8 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16) || M < 1 || M > 8) return false;
-    return ksplit_eligible(M, K, 16) || static_cast<size_t>(M) * K * 2 <= 64 * 1024;
+    return (mis16(x) | mis16(W)) == 0 && gemv_f16_route(M, K) != LR_REFUSED;
 }
 
 int linear_f16_nk_norm(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi, const half_t *bias,
@@ -916,36 +914,39 @@ void gemm256_qkv_rope_launch(int kind, const void *x, const void *W, half_t *qkv
     }
 }
 
-// int8 [N, K] weights through the eight-phase kernels (gemm8p.cuh, WQ = 8): prefill-sized M whose 256-row grid fills the chip
-bool g8p_w8_eligible(int M, int K, int N, const void *x, const void *wq, const void *scale, const void *y) {
-    return K % 64 == 0 && N % 4 == 0 && gemm256_fills(M, N) && (static_cast<size_t>(N) + 512) * K * 2 < (size_t{1} << 32) &&
-           (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) % 16 == 0 &&
-           (reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(y)) % 8 == 0;
+// ---- route planning: which kernel a projection runs on.  Pure host code: no HIP call, no error text, no launch. ----
+LinearCall linear_call(int bits, int M, int K, int N, int epi, int group, const void *x, const void *w, const void *scale, const void *y,
+                       const void *bias, const void *residual, const void *gamma, const void *pre_bias, SlabWs ws, const void *image,
+                       size_t image_bytes) {
+    return LinearCall{bits, M, K, N, epi, group, bias != nullptr, residual != nullptr, gamma != nullptr, pre_bias != nullptr,
+                      mis16(x), mis16(w), mis16(y), mis16(bias), mis16(residual), mis16(gamma), mis16(pre_bias), mis16(scale), mis16(image),
+                      ws.p != nullptr, ws.p ? ws.floats : 0, image != nullptr, image ? image_bytes : 0};
 }
-bool g8p_w8_swiglu_eligible(int M, int K, int two_inter, const void *x, const void *wq, const void *scale, const void *y) {
-    return K % 64 == 0 && two_inter % 8 == 0 && gemm256_swiglu_fills(M, two_inter) &&
-           (static_cast<size_t>(two_inter) + 512) * K * 2 < (size_t{1} << 32) &&
-           (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) % 16 == 0 &&
-           (reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(y)) % 8 == 0;
-}
-
-// does linear_f16_nk have a fused SwiGLU form for this call?  (the GEMV, split-K, skinny and 256-row SwiGLU conditions below)
-bool linear_f16_swiglu_eligible(int M, int K, int N, const void *x, const void *W, const void *y, SlabWs ws) {
-    const bool aligned = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16 == 0);
-    if (gemv_f16_eligible(M, K, x, W)) return true;
-    if (ws.p && aligned && M <= 192 && K % 128 == 0 && K >= 512) return true;
-    if (aligned && M <= 64 && K % 32 == 0 && (N / 2) % 16 == 0) return true;
-    return aligned && K % 64 == 0 && gemm256_swiglu_fills(M, N) && reinterpret_cast<uintptr_t>(y) % 8 == 0;
+LinearCall linear_call_sizing(int bits, int M, int K, int N, int epi, int group) {
+    LinearCall c{};
+    c.bits = bits, c.M = M, c.K = K, c.N = N, c.epi = epi, c.group = group;
+    c.slabs = c.image = true;
+    c.slab_floats = c.image_bytes = ~static_cast<size_t>(0);
+    return c;
 }
 
-int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
-                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st) {
-    const bool aligned = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16 == 0);
-    bool done = false;
-    if (gemv_f16_eligible(M, K, x, W)) {
-        const GemvArgs a{x, W, y, K, N, bias, residual, nullptr, nullptr, 0.f, epi, 0, nullptr, 0};
-        done = dispatch_gemv(M, a, st);
-    }
+static LinearPlan planned(int route) { return LinearPlan{route, LREF_NONE, 0, 0, 0, LR_REFUSED}; }
+static LinearPlan refused(int why) { return LinearPlan{LR_REFUSED, why, 0, 0, 0, LR_REFUSED}; }
+// a split-K route in passes of `pass` rows over the caller's slabs (sized for the first pass, the largest)
+static LinearPlan planned_splitk(const LinearCall &c, int route, int pass) {
+    LinearPlan p = planned(route);
+    p.pass_rows = pass;
+    p.slab_floats = linear_splitk_ws_floats(c.bits, c.M < pass ? c.M : pass, c.K, c.N);
+    if (c.slab_floats < p.slab_floats) p.route = LR_REFUSED, p.refusal = LREF_SLABS;
+    return p;
+}
+
+LinearPlan plan_linear_f16(const LinearCall &c) {
+    const int M = c.M, K = c.K, N = c.N;
+    const bool swiglu = c.epi == EPI_SWIGLU;
+    const bool aligned = K % 8 == 0 && (c.mis_x | c.mis_w) == 0;
+    const bool epi8 = (c.mis_bias | c.mis_residual) % 8 == 0;
+    if (aligned && gemv_f16_route(M, K) != LR_REFUSED) return planned(gemv_f16_route(M, K));
     // decode / short-prefill batches: split-K over the caller's slabs (without a workspace: the non-split kernels below).
     // Round 3, 192 < M where the eight-phase kernels' 256-row grid does not fill the chip (N = 4096 at 256-1023 tokens): such
     // shapes used to fall to the 128 x 128 kernel -- 82 us for the O and 190 us for the down projection of a 7B layer WHATEVER the
@@ -953,69 +954,221 @@ int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int
     //   split-K passes of 128 rows:  passes x (weight bytes / 4.2 TB/s + 10 us)          O: 19.5 us per pass, down: 30 us
     //   256 x 128 eight-phase tiles: rounds of 256 tiles x K / 64 k-tiles x 0.9 us        O: 58 us, down: 140 us per round
     bool mid_rows = false, mid_tiles = false;
-    if (M > 192 && epi != EPI_SWIGLU && aligned && K % 64 == 0 && !gemm256_fills(M, N)) {
+    if (M > 192 && !swiglu && aligned && K % 64 == 0 && !gemm256_fills(M, N)) {
         const int passes = (M + kSplitKPassRows - 1) / kSplitKPassRows;
         const float t_split = passes * (static_cast<float>(N) * K * 2.f / 4.2e6f + 10.f);
         const int tiles2 = ((M + 255) / 256) * ((N + 127) / 128);
         const float t_tiles = static_cast<float>((tiles2 + 255) / 256) * (K / 64) * 0.9f;
-        const bool split_ok = ws.p && K % 128 == 0 && K >= 512 && ws.floats >= linear_splitk_ws_floats(16, kSplitKPassRows, K, N);
-        const bool tiles_ok = g8p_fits(N, K, false) && reinterpret_cast<uintptr_t>(y) % 8 == 0 &&
-                              (reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) % 8 == 0;
+        const bool split_ok = c.slabs && K % 128 == 0 && K >= 512 && c.slab_floats >= linear_splitk_ws_floats(16, kSplitKPassRows, K, N);
+        const bool tiles_ok = g8p_fits(N, K, false) && c.mis_y % 8 == 0 && epi8;
         mid_rows = split_ok && (!tiles_ok || t_split < t_tiles);
         mid_tiles = tiles_ok && !mid_rows;
     }
-    if (!done && ws.p && aligned && (M <= 192 || mid_rows) && K % 128 == 0 && K >= 512)
-        return linear_splitk(16, x, W, nullptr, y, M, K, N, epi, bias, residual, ws, st);
-    if (!done && aligned && M <= 64 && K % 32 == 0 && (epi != EPI_SWIGLU || (N / 2) % 16 == 0)) {
-        done = (epi == EPI_SWIGLU) ? dispatch_skinny<EPI_SWIGLU>(M, x, W, y, K, N, bias, residual, st)
-                                   : dispatch_skinny<EPI_NONE>(M, x, W, y, K, N, bias, residual, st);
-    }
-    if (!done && epi == EPI_SWIGLU && aligned && K % 64 == 0 && gemm256_swiglu_fills(M, N) && reinterpret_cast<uintptr_t>(y) % 8 == 0) {
-        gemm256_swiglu_launch(false, x, W, y, M, N, K, nullptr, nullptr, st);
-        return launch_status("linear(gemm256 SwiGLU)");
-    }
-    if (!done && epi == EPI_SWIGLU) {
-        set_error("linear: fused SwiGLU epilogue without a split-K workspace needs M<=64, K%%32==0, (N/2)%%16==0 (M=%d K=%d N=%d)", M, K, N);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!done && aligned && K % 64 == 0 && reinterpret_cast<uintptr_t>(y) % 8 == 0) {
+    if (c.slabs && aligned && (M <= 192 || mid_rows) && K % 128 == 0 && K >= 512)
+        return planned_splitk(c, mid_rows ? LR_SPLITK_PASSES : LR_SPLITK, kSplitKPassRows);
+    if (aligned && M <= 64 && K % 32 == 0 && (!swiglu || (N / 2) % 16 == 0)) return planned(LR_SKINNY);
+    if (swiglu)
+        return aligned && K % 64 == 0 && gemm256_swiglu_fills(M, N) && c.mis_y % 8 == 0 ? planned(LR_SWIGLU256) : refused(LREF_F16_SWIGLU);
+    if (aligned && K % 64 == 0 && c.mis_y % 8 == 0) {
         // 256 x 256 LDS-DMA kernel when its grid fills the chip (one 512-thread workgroup per CU); else 128 x 128 tiles
-        if ((gemm256_fills(M, N) || mid_tiles) && (reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) % 8 == 0) {
+        if ((gemm256_fills(M, N) || mid_tiles) && epi8) return planned(gemm256_fills(M, N) ? LR_TILES256 : LR_TILES256_PART);
+        return planned(LR_TILES128);
+    }
+    return planned(LR_GENERIC);
+}
+
+// Slab floats to reserve for an fp16 projection of M rows: the plan's, and those of the shape's split-K form where the plan needs
+// none because M <= 8 runs the GEMV, or because a partly filled tile grid beats the passes in the time model.  (More than the plan
+// needs: callers share one workspace across row counts, and the reservation has always been this.)
+size_t linear_f16_reserve_slab_floats(int M, int K, int N) {
+    const LinearPlan p = plan_linear_f16(linear_call_sizing(16, M, K, N, EPI_NONE));
+    if (p.route == LR_GEMV_KSPLIT || p.route == LR_GEMV_LDS || p.route == LR_TILES256_PART) return linear_splitk_ws_floats(16, M, K, N);
+    return p.slab_floats;
+}
+
+// the fp16 GEMM on the image of quantised weights: the same call with W = the image and no slabs
+static LinearPlan planned_image(const LinearCall &c, int route) {
+    LinearCall f = c;
+    f.bits = 16, f.mis_w = c.mis_image, f.slabs = false, f.slab_floats = 0;
+    const LinearPlan in = plan_linear_f16(f);
+    if (in.route == LR_REFUSED) return in;
+    LinearPlan p = planned(route);
+    p.image_bytes = static_cast<size_t>(c.N) * c.K * sizeof(half_t);
+    p.inner = in.route;
+    return p;
+}
+
+LinearPlan plan_linear_wq(const LinearCall &c) {
+    const int bits = c.bits, M = c.M, K = c.K, N = c.N;
+    const bool swiglu = c.epi == EPI_SWIGLU, plain = c.epi == EPI_NONE;
+    const bool aligned = (c.mis_x | c.mis_w | c.mis_gamma | c.mis_pre_bias) == 0 && (static_cast<size_t>(K) * bits / 8) % 16 == 0;
+    // int8 [N, K] weights through the eight-phase kernels (gemm8p.cuh, WQ = 8): prefill-sized M whose 256-row grid fills the chip
+    // (per-lane DMA offsets are 32-bit)
+    const bool g8p_operands = bits == 8 && K % 64 == 0 && (static_cast<size_t>(N) + 512) * K * 2 < (size_t{1} << 32) &&
+                              (c.mis_x | c.mis_w) == 0 && (c.mis_scale | c.mis_y) % 8 == 0;
+    const bool g8p = g8p_operands && N % 4 == 0 && gemm256_fills(M, N);
+    const bool g8p_swiglu = g8p_operands && N % 8 == 0 && gemm256_swiglu_fills(M, N);
+    const bool splitk_shape = aligned && K % 256 == 0 && K >= 512 && c.slabs;
+    const bool image_ok = c.image && K % 8 == 0 && c.image_bytes >= static_cast<size_t>(N) * K * sizeof(half_t) && c.mis_image == 0 &&
+                          c.mis_w % 8 == 0 && (bits == 8 || (c.group % 8 == 0 && K % c.group == 0));
+    // ---- prefill-sized row counts: MFMA-bound, the weights are read M / 256 times from L2 instead of streamed once ----
+    // (round 3) int8, M from 192, shapes whose 256-row grid does not fill the chip (N = 4096 of a 7B layer at 193 .. 1023 tokens):
+    // split-K passes of 128 rows on the int8 rows against the fp16 image + a partly filled tile grid, by a time model fitted to the
+    // sweep (us; O / down of a 7B layer: 22 / 33 per pass against 56 / 123 for the image route whatever the row count):
+    //   passes x (N K bytes / 2.8 TB/s + 16)   <   N K x 3 bytes / 4 TB/s  +  K / 64 x 0.55
+    bool int8_mid_passes = false;
+    if (bits == 8 && M >= kWqPrefillRows && !c.gamma && plain && splitk_shape && !g8p &&
+        c.slab_floats >= linear_splitk_ws_floats(8, kSplitKPassRows, K, N)) {
+        const float nk = static_cast<float>(N) * K;
+        const float t_passes = ((M + 127) / 128) * (nk / 2.8e6f + 16.f), t_image = nk * 3.f / 4.0e6f + (K / 64) * 0.55f;
+        int8_mid_passes = t_passes * 1.05f < t_image;   // (ties go to the image route)
+    }
+    if (M >= kWqPrefillRows && !c.gamma && !int8_mid_passes) {
+        // int8: the eight-phase GEMM takes the int8 rows as they are (raw bytes HBM -> LDS by DMA, de-quantised at fragment read,
+        // scale in the epilogue)
+        if (swiglu && !c.bias && !c.residual && g8p_swiglu) return planned(LR_W8_G8P_SWIGLU);
+        if (plain && g8p && (c.mis_bias | c.mis_residual) % 8 == 0) return planned(LR_W8_G8P);
+        // other shapes, and int4 (group scales along K): one pass writes the fp16 image of the matrix into the caller's scratch,
+        // the fp16 GEMM reads it back (mostly from the 256 MiB Infinity Cache): + (bits / 8 + 2) bytes of traffic per weight
+        // (the fp16 GEMM has no fused SwiGLU where its 256-row grid does not fill: the forms below)
+        if (image_ok && (!swiglu || gemm256_swiglu_fills(M, N))) return planned_image(c, LR_WQ_IMAGE_PREFILL);
+    }
+    if (aligned && ksplit_eligible(M, K, bits)) return planned(LR_WQ_GEMV);
+    if (bits == 4 && c.group == 128 && splitk_shape && M > 8 && !c.gamma) {   // MFMA path, group scales in the kernel
+        if (c.mis_scale % 4) return refused(LREF_W4_SPLITK);
+        return planned_splitk(c, LR_W4_SPLITK, 64);
+    }
+    if (aligned && bits == 4) {
+        // other int4 shapes: batches beyond the GEMV's register budget run as row chunks of the largest eligible
+        // size (the weights are streamed once per chunk -- correct for any batch, bandwidth-efficient only for small ones)
+        int mc = 8;
+        while (mc > 0 && !ksplit_eligible(mc, K, 4)) --mc;
+        if (mc > 0) {
+            LinearPlan p = planned(LR_W4_CHUNKS);
+            p.pass_rows = mc;
+            return p;
+        }
+    }
+    if (c.gamma) return refused(LREF_WQ_NORM);
+    if (bits == 8 && splitk_shape) return planned_splitk(c, int8_mid_passes ? LR_W8_SPLITK_PASSES : LR_W8_SPLITK, kSplitKPassRows);
+    if (!plain) return refused(LREF_WQ_SWIGLU);
+    if (bits == 8 && aligned && K % 64 == 0 && M <= 64) return planned(LR_W8_SKINNY);
+    // shapes none of the quantised kernels take (K not a multiple of their sub-blocks): the fp16 image, where the caller gave room
+    if (image_ok) return planned_image(c, LR_WQ_IMAGE_LAST);
+    return refused(LREF_WQ_SHAPE);
+}
+
+// fp16 scratch to reserve beside the slabs for an int8 / int4 projection of M rows.  From kWqPrefillRows rows on: room for the whole
+// image, also where the plan needs none (the int8 eight-phase and split-K routes) -- more than the plan needs, kept: callers share
+// one workspace across shapes.  Below: int8 reserves what the plan needs (the last-resort image of shapes no int8 kernel takes);
+// int4 has never reserved any there.
+size_t linear_wq_dequant_bytes(int wbits, int M, int K, int N) {
+    if ((wbits != 8 && wbits != 4) || K % 8 != 0) return 0;
+    if (M >= kWqPrefillRows) return static_cast<size_t>(N) * K * sizeof(half_t);
+    return wbits == 8 ? plan_linear_wq(linear_call_sizing(8, M, K, N, EPI_NONE)).image_bytes : 0;
+}
+WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t workspace_bytes) {
+    const size_t dq = (linear_wq_dequant_bytes(wbits, M, K, N) + 255) & ~static_cast<size_t>(255);
+    if (workspace && dq && workspace_bytes >= dq) {
+        char *b = static_cast<char *>(workspace);
+        return WqWorkspace{b, dq, SlabWs{reinterpret_cast<float *>(b + dq), (workspace_bytes - dq) / sizeof(float)}};
+    }
+    return WqWorkspace{nullptr, 0, SlabWs{static_cast<float *>(workspace), workspace_bytes / sizeof(float)}};
+}
+
+const char *linear_route_name(int route) {
+    static const char *const names[] = {"refused", "gemv_ksplit", "gemv_lds", "splitk", "splitk_passes", "skinny", "swiglu256", "tiles256",
+                                        "tiles256_part", "tiles128", "generic", "g8p", "g8p_swiglu", "int8_splitk_passes", "image_prefill",
+                                        "image_last", "gemv_ksplit", "int4_splitk", "int4_chunks", "int8_splitk", "int8_skinny"};
+    return names[route];
+}
+
+int linear_refuse(const LinearCall &c, const LinearPlan &p) {
+    const int M = c.M, K = c.K, N = c.N;
+    switch (p.refusal) {
+        case LREF_F16_SWIGLU:
+            set_error("linear: fused SwiGLU epilogue without a split-K workspace needs M<=64, K%%32==0, (N/2)%%16==0 (M=%d K=%d N=%d)", M, K, N);
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_SLABS:
+            set_error("linear(split-K): slab workspace too small or misaligned (%zu < %zu bytes); size it with "
+                      "llmie_linear_workspace_bytes()", c.slab_floats * sizeof(float), p.slab_floats * sizeof(float));
+            return LLMIE_ERR_WORKSPACE;
+        case LREF_W4_SPLITK:
+            set_error("linear(split-K int4): needs M <= 64 per pass, K %% 256 == 0, group-128 scales");
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_WQ_NORM:
+            set_error("linear_wq: fused norm only on the GEMV path (M=%d K=%d bits=%d)", M, K, c.bits);
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_WQ_SWIGLU:
+            set_error("linear_wq: fused SwiGLU needs the GEMV or split-K path (M=%d K=%d bits=%d)", M, K, c.bits);
+            return LLMIE_ERR_UNSUPPORTED;
+        default:
+            set_error("linear_wq: unsupported shape M=%d K=%d N=%d bits=%d without a split-K workspace (int8: M<=64, K%%64==0; int4: "
+                      "M<=8 on the GEMV path); size one with llmie_linear_workspace_bytes()", M, K, N, c.bits);
+            return LLMIE_ERR_UNSUPPORTED;
+    }
+}
+
+int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
+                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st) {
+    const LinearCall c = linear_call(16, M, K, N, epi, 0, x, W, nullptr, y, bias, residual, nullptr, nullptr, ws, nullptr, 0);
+    const LinearPlan p = plan_linear_f16(c);
+    switch (p.route) {
+        case LR_GEMV_KSPLIT:
+        case LR_GEMV_LDS:
+            dispatch_gemv(M, GemvArgs{x, W, y, K, N, bias, residual, nullptr, nullptr, 0.f, epi, 0, nullptr, 0}, st);
+            return launch_status("linear");
+        case LR_SPLITK:
+        case LR_SPLITK_PASSES:
+            return linear_splitk(16, x, W, nullptr, y, M, K, N, epi, bias, residual, ws, st);
+        case LR_SKINNY:
+            if (epi == EPI_SWIGLU) dispatch_skinny<EPI_SWIGLU>(M, x, W, y, K, N, bias, residual, st);
+            else dispatch_skinny<EPI_NONE>(M, x, W, y, K, N, bias, residual, st);
+            return launch_status("linear");
+        case LR_SWIGLU256:
+            gemm256_swiglu_launch(false, x, W, y, M, N, K, nullptr, nullptr, st);
+            return launch_status("linear(gemm256 SwiGLU)");
+        case LR_TILES256:
+        case LR_TILES256_PART:
             gemm256_launch(false, x, W, y, M, N, K, bias, residual, nullptr, nullptr, st);
             return launch_status("linear(gemm256)");
+        case LR_TILES128: {
+            dim3 grid((N + 127) / 128, (M + 127) / 128, 1);
+            if (bias || residual)
+                tiled_mfma_f16_kernel<true><<<grid, 256, 0, st>>>(x, W, y, M, N, K, 0, 0, 0, bias, residual);
+            else
+                tiled_mfma_f16_kernel<false><<<grid, 256, 0, st>>>(x, W, y, M, N, K, 0, 0, 0, nullptr, nullptr);
+            return launch_status("linear");
         }
-        dim3 grid((N + 127) / 128, (M + 127) / 128, 1);
-        if (bias || residual)
-            tiled_mfma_f16_kernel<true><<<grid, 256, 0, st>>>(x, W, y, M, N, K, 0, 0, 0, bias, residual);
-        else
-            tiled_mfma_f16_kernel<false><<<grid, 256, 0, st>>>(x, W, y, M, N, K, 0, 0, 0, nullptr, nullptr);
-        done = true;
+        case LR_GENERIC:
+            launch_generic<half_t>(x, W, y, 1, M, N, K, true, bias, residual, st);
+            return launch_status("linear");
+        default:
+            return linear_refuse(c, p);
     }
-    if (!done) launch_generic<half_t>(x, W, y, 1, M, N, K, true, bias, residual, st);
-    return launch_status("linear");
 }
 
 }  // namespace llmie
 
 using namespace llmie;
 
-// fp32 slab scratch of the split-K forms for this shape (the counterpart of the workspace the reference's cublasWrapper owns)
+// scratch of the projection entry points for this shape: [fp16 image of int8 / int4 weights | fp32 split-K slabs] (the counterpart of
+// the workspace the reference's cublasWrapper owns)
 extern "C" size_t llmie_linear_workspace_bytes(llmie_weight_format fmt, int M, int K, int N) {
     if (M <= 0 || K <= 0 || N <= 0) return 0;
-    int wbits;
     switch (fmt) {
-        case LLMIE_W_F16: wbits = 16; break;
-        case LLMIE_W_INT8: wbits = 8; break;
-        case LLMIE_W_INT4: wbits = 4; break;
-        case LLMIE_W_FP8: wbits = WF_FP8; break;
+        case LLMIE_W_F16: return linear_f16_reserve_slab_floats(M, K, N) * sizeof(float);
+        case LLMIE_W_FP8: return linear_splitk_ws_floats(WF_FP8, M, K, N) * sizeof(float);
+        case LLMIE_W_INT8:
+        case LLMIE_W_INT4: {
+            // the slabs of the shape's split-K form at every M, whatever route M takes (more than the eight-phase, image and GEMV
+            // routes need, kept: callers share one workspace across row counts), behind the image (linear_wq_dequant_bytes)
+            const int wbits = fmt == LLMIE_W_INT8 ? 8 : 4;
+            const size_t dq = (linear_wq_dequant_bytes(wbits, M, K, N) + 255) & ~static_cast<size_t>(255);
+            return dq + linear_splitk_ws_floats(wbits, M, K, N) * sizeof(float);
+        }
         default: return 0;
     }
-    // prefill-sized fp16: tiled kernels, no slabs -- except where the 256-row grid does not fill the chip: split-K passes of 128
-    // rows may be the cheaper form there (linear_f16_nk's time model)
-    if (fmt == LLMIE_W_F16 && M > 192 && gemm256_fills(M, N)) return 0;
-    // int8 / int4 at prefill-sized M: room for the fp16 image of W in front of the slabs (llmie_linear_w8a16 / _w4a16)
-    const size_t dq = (fmt == LLMIE_W_INT8 || fmt == LLMIE_W_INT4) ? ((linear_wq_dequant_bytes(wbits, M, K, N) + 255) & ~static_cast<size_t>(255)) : 0;
-    return dq + linear_splitk_ws_floats(wbits, M, K, N) * sizeof(float);
 }
 
 static bool slab_ws_of(void *workspace, size_t bytes, SlabWs *out) {
@@ -1056,6 +1209,40 @@ extern "C" int llmie_linear_swiglu(const void *x, const void *w, void *y, int M,
     LLMIE_REQUIRE(slab_ws_of(workspace, workspace_bytes, &ws), "linear_swiglu: workspace must be 16-byte aligned");
     return linear_f16_nk((const half_t *)x, (const half_t *)w, (half_t *)y, M, K, two_inter, EPI_SWIGLU, nullptr,
                          nullptr, ws, as_stream(stream));
+}
+
+extern "C" const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const void *w, const void *scale, const void *y, int M,
+                                          int K, int N, int swiglu, int group, const void *bias, const void *residual,
+                                          const void *workspace, size_t workspace_bytes) {
+    const int bits = fmt == LLMIE_W_F16 ? 16 : (fmt == LLMIE_W_INT8 ? 8 : (fmt == LLMIE_W_INT4 ? 4 : 0));
+    const int epi = swiglu ? EPI_SWIGLU : EPI_NONE;
+    static thread_local char name[48];
+    auto fail = [](const char *what) -> const char * {
+        set_error("linear_route: %s", what);
+        return nullptr;
+    };
+    if (!bits) return fail("fp16, int8 and int4 weights only");
+    if (!x || !w || !y || (bits != 16 && !scale)) return fail("NULL pointer");
+    if (M <= 0 || K <= 0 || N <= 0 || (swiglu && (N % 2 || bias || residual))) return fail("bad shape or epilogue");
+    if (bits == 4 && !(group > 0 && group % 32 == 0 && K % group == 0)) return fail("group must be a multiple of 32 dividing K");
+    if (mis16(workspace)) return fail("workspace must be 16-byte aligned");
+    void *wsp = const_cast<void *>(workspace);
+    LinearCall c;
+    if (bits == 16) {
+        c = linear_call(16, M, K, N, epi, 0, x, w, nullptr, y, bias, residual, nullptr, nullptr,
+                        SlabWs{static_cast<float *>(wsp), workspace_bytes / sizeof(float)}, nullptr, 0);
+    } else {
+        const WqWorkspace ws = wq_workspace(bits, M, K, N, wsp, workspace_bytes);
+        c = linear_call(bits, M, K, N, epi, bits == 4 ? group : 0, x, w, scale, y, bias, residual, nullptr, nullptr, ws.slabs, ws.deq, ws.deq_bytes);
+    }
+    const LinearPlan p = bits == 16 ? plan_linear_f16(c) : plan_linear_wq(c);
+    if (p.route == LR_REFUSED) {
+        linear_refuse(c, p);
+        return nullptr;
+    }
+    if (p.inner != LR_REFUSED) snprintf(name, sizeof(name), "%s+%s", linear_route_name(p.route), linear_route_name(p.inner));
+    else snprintf(name, sizeof(name), "%s", linear_route_name(p.route));
+    return name;
 }
 
 extern "C" int llmie_batched_gemm(const void *a, const void *b, void *c, int batch, int m, int n, int k,

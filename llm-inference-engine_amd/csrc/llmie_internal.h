@@ -16,10 +16,50 @@ struct SlabWs {
     size_t floats;
 };
 size_t linear_splitk_ws_floats(int wbits, int M, int K, int N);   // 0 = the shape has no split-K form
+
+// ---- which kernel a projection runs on: decided once, by a pure host function per weight family (linear.hip) ----
+enum LinearRoute : int {
+    LR_REFUSED = 0,
+    // fp16 weights
+    LR_GEMV_KSPLIT, LR_GEMV_LDS, LR_SPLITK, LR_SPLITK_PASSES, LR_SKINNY, LR_SWIGLU256, LR_TILES256, LR_TILES256_PART, LR_TILES128, LR_GENERIC,
+    // int8 / int4 weights
+    LR_W8_G8P, LR_W8_G8P_SWIGLU, LR_W8_SPLITK_PASSES, LR_WQ_IMAGE_PREFILL, LR_WQ_IMAGE_LAST, LR_WQ_GEMV, LR_W4_SPLITK, LR_W4_CHUNKS,
+    LR_W8_SPLITK, LR_W8_SKINNY,
+};
+enum LinearRefusal : int { LREF_NONE = 0, LREF_F16_SWIGLU, LREF_SLABS, LREF_W4_SPLITK, LREF_WQ_NORM, LREF_WQ_SWIGLU, LREF_WQ_SHAPE };
+// One projection call as the planners see it: shape, epilogue, which operands are there and how far each pointer is from 16-byte
+// alignment (address % 16; 0 for a null pointer), and the caller's scratch.  bits = 16: fp16 weights (group / scale / image unused).
+struct LinearCall {
+    int bits, M, K, N, epi, group;
+    bool bias, residual, gamma, pre_bias;
+    unsigned mis_x, mis_w, mis_y, mis_bias, mis_residual, mis_gamma, mis_pre_bias, mis_scale, mis_image;
+    bool slabs;            // split-K slab workspace present
+    size_t slab_floats;
+    bool image;            // scratch for the fp16 image of quantised weights present
+    size_t image_bytes;
+};
+struct LinearPlan {
+    int route;             // LinearRoute
+    int refusal;           // LinearRefusal of LR_REFUSED
+    size_t slab_floats;    // what the route needs of the caller's scratch (0: nothing)
+    size_t image_bytes;
+    int pass_rows;         // activation rows per pass of the split-K and row-chunk routes
+    int inner;             // fp16 image routes: the route of the fp16 GEMM on the image
+};
+inline unsigned mis16(const void *p) { return static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) % 16); }
+// the call with every pointer aligned, no bias / residual / norm and all the scratch a route may ask for: what the size queries plan
+LinearCall linear_call_sizing(int bits, int M, int K, int N, int epi, int group = 128);
+LinearCall linear_call(int bits, int M, int K, int N, int epi, int group, const void *x, const void *w, const void *scale, const void *y,
+                       const void *bias, const void *residual, const void *gamma, const void *pre_bias, SlabWs ws, const void *image,
+                       size_t image_bytes);
+LinearPlan plan_linear_f16(const LinearCall &c);
+LinearPlan plan_linear_wq(const LinearCall &c);
+const char *linear_route_name(int route);
+int linear_refuse(const LinearCall &c, const LinearPlan &p);   // sets the refusal's error text, returns its error code
+// slab floats to reserve for an fp16 projection of M rows (>= the plan's: see linear.hip)
+size_t linear_f16_reserve_slab_floats(int M, int K, int N);
 int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
                   const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st);
-// true when linear_f16_nk(x, W, y, M, K, N, EPI_SWIGLU_, no bias / residual, ws) has a fused form (else it refuses the call)
-bool linear_f16_swiglu_eligible(int M, int K, int N, const void *x, const void *W, const void *y, SlabWs ws);
 
 // same with rmsnorm(x + pre_bias) * gamma fused in front (GEMV path only; LLMIE_ERR_UNSUPPORTED otherwise)
 bool gemv_f16_eligible(int M, int K, const void *x, const void *W);
@@ -60,25 +100,31 @@ void gemm256_launch(bool fp8, const void *x, const void *W, half_t *y, int M, in
 bool gemm256_swiglu_fills(int M, int two_inter);
 void gemm256_swiglu_launch(bool fp8, const void *x, const void *W, half_t *y, int M, int two_inter, int K, const float *xscale,
                            const float *wscale, hipStream_t st, int wq = 0);
-bool g8p_w8_eligible(int M, int K, int N, const void *x, const void *wq, const void *scale, const void *y);
 // QKV projection with RoPE + KV-cache append as its epilogue (gemm8p.cuh ROPE forms): kind 0 = fp16, 1 = e4m3 operands, 8 = int8
 // weights (wscale = fp16 row scales); q columns -> qkv (rotated), k / v columns -> the caches only; linear.hip
 bool gemm256_qkv_rope_eligible(int kind, int M, int N, int K, const void *x, const void *W, const void *wscale, const void *qkv);
 // rap: the epilogue's layer-invariant operands in DEVICE memory (prefill_token_table writes them); bias: the layer's QKV bias or null
 void gemm256_qkv_rope_launch(int kind, const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale,
                              const float *wscale, const half_t *bias, const QkvRopeArgs *rap, int layer, hipStream_t st);
-bool g8p_w8_swiglu_eligible(int M, int K, int two_inter, const void *x, const void *wq, const void *scale, const void *y);
 // fp16 image of int8 / int4 weights (row scales / group scales applied, one rounding): the operand of the prefill-sized
 // projections that have no in-kernel de-quantising form; quant_linear.hip
 int dequantize_weights_f16(int wbits, const void *wq, const half_t *scale, half_t *w16, int N, int K, int group, hipStream_t st);
 // rows from which a weight-only projection runs as an MFMA-bound tiled GEMM (prefill) instead of split-K passes
 constexpr int kWqPrefillRows = 192;
-// bytes of fp16 scratch linear_wq needs at M rows beside the split-K slabs (0: none)
+// bytes of fp16 scratch to reserve for linear_wq at M rows beside the split-K slabs (0: none); linear.hip
 size_t linear_wq_dequant_bytes(int wbits, int M, int K, int N);
+// [fp16 image | slabs] split of a caller workspace, as llmie_linear_workspace_bytes sizes it (a workspace too small for the image is
+// all slabs); linear.hip
+struct WqWorkspace {
+    void *deq;
+    size_t deq_bytes;
+    SlabWs slabs;
+};
+WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t workspace_bytes);
 // quantised-weight (int8 / int4) decode GEMV on the K-split kernel; defined in linear.hip
 struct GemvArgs;
 bool ksplit_eligible(int M, int K, int wbits);
-bool gemv_q_launch(int wbits, int M, const GemvArgs &a, hipStream_t st);
+void gemv_q_launch(int wbits, int M, const GemvArgs &a, hipStream_t st);   // needs ksplit_eligible(M, K, wbits)
 bool gemv_fp8_launch(int M, const GemvArgs &a, hipStream_t st);
 // fp8 linear on the GEMV path (M <= 8, ksplit_eligible(M, K, 8)); optional fused norm prologue / SwiGLU epilogue; fp8_linear.hip
 int linear_fp8_gemv(const half_t *x, const uint8_t *wq, const float *wscale, half_t *y, int M, int K, int N, int epi,
@@ -87,15 +133,12 @@ int linear_fp8_gemv(const half_t *x, const uint8_t *wq, const float *wscale, hal
 // llmie_linear_fp8 with the activation scratch and the split-K slabs as separate areas; fp8_linear.hip
 int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half_t *y, int M, int K, int N, const half_t *bias,
                const half_t *residual, void *act_ws, size_t act_ws_bytes, SlabWs slabs, hipStream_t st);
-// weight-only int8/int4 linear with optional fused norm prologue / SwiGLU epilogue (quant_linear.hip)
-// M >= kWqPrefillRows (prefill): int8 through the eight-phase kernels' int8 form where eligible, else (and int4) a de-quantised
-// fp16 image in `deq` (linear_wq_dequant_bytes) + the fp16 GEMM; without `deq` those shapes keep the split-K passes
+// weight-only int8/int4 linear with optional fused norm prologue / SwiGLU epilogue (quant_linear.hip): launches what
+// plan_linear_wq plans -- at M >= kWqPrefillRows int8 through the eight-phase kernels' int8 form where eligible, else (and int4) a
+// de-quantised fp16 image in `deq` + the fp16 GEMM; without `deq` those shapes keep the split-K passes
 int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,
               int epi, const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
               SlabWs ws, hipStream_t st, void *deq = nullptr, size_t deq_bytes = 0);
-// true when linear_wq(..., EPI_SWIGLU_, no bias / residual / norm, ws, deq) has a fused form (else it refuses the call)
-bool linear_wq_swiglu_eligible(int wbits, int M, int K, int N, int group, const void *x, const void *wq, const void *scale, const void *y,
-                               SlabWs ws, const void *deq, size_t deq_bytes);
 
 // ---- packed-weight batch-decode projections (pk_gemm.cuh / pk_linear.hip): 1 <= M <= 32 rows on tile-packed weight images ----
 enum : int { PKF_F16 = 16, PKF_I8 = 8, PKF_I4 = 4, PKF_FP8 = 108 };                 // = PK_F16 ... of pk_gemm.cuh

@@ -177,154 +177,61 @@ int dequantize_weights_f16(int wbits, const void *wq, const half_t *scale, half_
     return launch_status("dequantize_weights");
 }
 
-size_t linear_wq_dequant_bytes(int wbits, int M, int K, int N) {
-    if ((wbits != 8 && wbits != 4) || K % 8 != 0) return 0;
-    // below the prefill rows: only int8 shapes that no int8 kernel takes (K not a whole number of the GEMV's 16-byte chunks, of the
-    // split-K sub-blocks or of the 64-row kernel's) read the fp16 image -- the last form of linear_wq
-    const bool int8_form = K % 16 == 0 && (ksplit_eligible(M, K, 8) || (K % 256 == 0 && K >= 512) || (M <= 64 && K % 64 == 0));
-    if (M < kWqPrefillRows && (wbits != 8 || int8_form)) return 0;
-    return static_cast<size_t>(N) * K * sizeof(half_t);
-}
-
-// does linear_wq have a fused SwiGLU form for this call (no bias, residual or norm)?  (the conditions of linear_wq below, in order)
-bool linear_wq_swiglu_eligible(int wbits, int M, int K, int N, int group, const void *x, const void *wq, const void *scale, const void *y,
-                               SlabWs ws, const void *deq, size_t deq_bytes) {
-    const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) % 16 == 0) &&
-                         (static_cast<size_t>(K) * wbits / 8) % 16 == 0;
-    if (M >= kWqPrefillRows) {
-        if (wbits == 8 && g8p_w8_swiglu_eligible(M, K, N, x, wq, scale, y)) return true;
-        const size_t need = linear_wq_dequant_bytes(wbits, M, K, N);
-        if (deq && need && deq_bytes >= need && reinterpret_cast<uintptr_t>(deq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 8 == 0 &&
-            (wbits == 8 || (group % 8 == 0 && K % group == 0)) && gemm256_swiglu_fills(M, N))
-            return linear_f16_swiglu_eligible(M, K, N, x, deq, y, SlabWs{nullptr, 0});
-    }
-    if (aligned && ksplit_eligible(M, K, wbits)) return true;
-    if (aligned && wbits == 4 && group == 128 && K % 256 == 0 && K >= 512 && M > 8 && ws.p) return true;
-    if (aligned && wbits == 4 && ksplit_eligible(1, K, 4)) return true;   // (row chunks)
-    return wbits == 8 && aligned && K % 256 == 0 && K >= 512 && ws.p;
-}
-
 int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,
               int epi, const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
               SlabWs ws, hipStream_t st, void *deq, size_t deq_bytes) {
-    const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq) |
-                           reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(pre_bias)) % 16 == 0) &&
-                         (static_cast<size_t>(K) * wbits / 8) % 16 == 0;
-    // ---- prefill-sized row counts: MFMA-bound, the weights are read M / 256 times from L2 instead of streamed once ----
-    // (round 3) int8, M from 192, shapes whose 256-row grid does not fill the chip (N = 4096 of a 7B layer at 193 .. 1023 tokens):
-    // split-K passes of 128 rows on the int8 rows against the fp16 image + a partly filled tile grid, by a time model fitted to the
-    // sweep (us; O / down of a 7B layer: 22 / 33 per pass against 56 / 123 for the image route whatever the row count):
-    //   passes x (N K bytes / 2.8 TB/s + 16)   <   N K x 3 bytes / 4 TB/s  +  K / 64 x 0.55
-    bool int8_mid_passes = false;
-    if (wbits == 8 && M >= kWqPrefillRows && !gamma && epi == EPI_NONE && ws.p && aligned && K % 256 == 0 && K >= 512 &&
-        !g8p_w8_eligible(M, K, N, x, wq, scale, y) && ws.floats >= linear_splitk_ws_floats(8, 128, K, N)) {
-        const float nk = static_cast<float>(N) * K;
-        const float t_passes = ((M + 127) / 128) * (nk / 2.8e6f + 16.f), t_image = nk * 3.f / 4.0e6f + (K / 64) * 0.55f;
-        int8_mid_passes = t_passes * 1.05f < t_image;   // (ties go to the image route)
-    }
-    if (M >= kWqPrefillRows && !gamma && !int8_mid_passes) {
-        // int8: the eight-phase GEMM takes the int8 rows as they are (raw bytes HBM -> LDS by DMA, de-quantised at fragment read,
-        // scale in the epilogue)
-        if (wbits == 8 && epi == EPI_SWIGLU && !bias && !residual && g8p_w8_swiglu_eligible(M, K, N, x, wq, scale, y)) {
+    const LinearCall c = linear_call(wbits, M, K, N, epi, group, x, wq, scale, y, bias, residual, gamma, pre_bias, ws, deq, deq_bytes);
+    const LinearPlan p = plan_linear_wq(c);
+    switch (p.route) {
+        case LR_W8_G8P_SWIGLU:
             gemm256_swiglu_launch(false, x, wq, y, M, N, K, nullptr, reinterpret_cast<const float *>(scale), st, 8);
             return launch_status("linear_w8a16(gemm8p SwiGLU)");
-        }
-        if (wbits == 8 && epi == EPI_NONE && g8p_w8_eligible(M, K, N, x, wq, scale, y) &&
-            (reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) % 8 == 0) {
+        case LR_W8_G8P:
             gemm256_launch(false, x, wq, y, M, N, K, bias, residual, nullptr, reinterpret_cast<const float *>(scale), st, 8);
             return launch_status("linear_w8a16(gemm8p)");
-        }
-        // other shapes, and int4 (group scales along K): one pass writes the fp16 image of the matrix into the caller's scratch,
-        // the fp16 GEMM reads it back (mostly from the 256 MiB Infinity Cache): + (wbits / 8 + 2) bytes of traffic per weight
-        const size_t need = linear_wq_dequant_bytes(wbits, M, K, N);
-        if (deq && need && deq_bytes >= need && reinterpret_cast<uintptr_t>(deq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 8 == 0 &&
-            (wbits == 8 || (group % 8 == 0 && K % group == 0))) {
-            if (epi == EPI_SWIGLU && !gemm256_swiglu_fills(M, N)) goto no_prefill_form;   // (the fp16 GEMM has no fused SwiGLU there)
+        case LR_WQ_IMAGE_PREFILL:
+        case LR_WQ_IMAGE_LAST: {
             int rc = dequantize_weights_f16(wbits, wq, scale, static_cast<half_t *>(deq), N, K, group, st);
             if (rc) return rc;
             return linear_f16_nk(x, static_cast<const half_t *>(deq), y, M, K, N, epi, bias, residual, SlabWs{nullptr, 0}, st);
         }
-    }
-no_prefill_form:
-    if (aligned && ksplit_eligible(M, K, wbits)) {
-        const GemvArgs a{x, wq, y, K, N, bias, residual, gamma, pre_bias, eps, epi, gamma ? 1 : 0, scale, group};
-        if (gemv_q_launch(wbits, M, a, st)) return launch_status("linear_wq");
-    }
-    if (aligned && wbits == 4 && group == 128 && K % 256 == 0 && K >= 512 && M > 8 && !gamma && ws.p)
-        return linear_splitk(4, x, wq, scale, y, M, K, N, epi, bias, residual, ws, st);  // MFMA path, group scales in the kernel
-    if (aligned && wbits == 4) {
-        // other int4 shapes: batches beyond the GEMV's register budget run as row chunks of the largest eligible
-        // size (the weights are streamed once per chunk -- correct for any batch, bandwidth-efficient only for small ones)
-        int mc = 8;
-        while (mc > 0 && !ksplit_eligible(mc, K, 4)) --mc;
-        if (mc > 0) {
-            const int out_n = epi == EPI_SWIGLU ? N / 2 : N;
+        case LR_WQ_GEMV:
+            gemv_q_launch(wbits, M, GemvArgs{x, wq, y, K, N, bias, residual, gamma, pre_bias, eps, epi, gamma ? 1 : 0, scale, group}, st);
+            return launch_status("linear_wq");
+        case LR_W4_SPLITK:
+        case LR_W8_SPLITK:
+        case LR_W8_SPLITK_PASSES:   // int8: row scales in the finalize; int4: group scales in the kernel
+            return linear_splitk(wbits, x, wq, scale, y, M, K, N, epi, bias, residual, ws, st);
+        case LR_W4_CHUNKS: {
+            const int mc = p.pass_rows, out_n = epi == EPI_SWIGLU ? N / 2 : N;
             for (int m0 = 0; m0 < M; m0 += mc) {
                 const int m = M - m0 < mc ? M - m0 : mc;
-                const GemvArgs a{x + static_cast<size_t>(m0) * K, wq, y + static_cast<size_t>(m0) * out_n, K, N, bias,
-                                 residual ? residual + static_cast<size_t>(m0) * N : nullptr, gamma, pre_bias, eps, epi, gamma ? 1 : 0,
-                                 scale, group};
-                if (!gemv_q_launch(4, m, a, st)) {
-                    set_error("linear_wq: no int4 GEMV instantiation for M=%d K=%d", m, K);
-                    return LLMIE_ERR_UNSUPPORTED;
-                }
+                gemv_q_launch(4, m, GemvArgs{x + static_cast<size_t>(m0) * K, wq, y + static_cast<size_t>(m0) * out_n, K, N, bias,
+                                             residual ? residual + static_cast<size_t>(m0) * N : nullptr, gamma, pre_bias, eps, epi,
+                                             gamma ? 1 : 0, scale, group}, st);
             }
             return launch_status("linear_wq(int4, row chunks)");
         }
-    }
-    if (gamma) {
-        set_error("linear_wq: fused norm only on the GEMV path (M=%d K=%d bits=%d)", M, K, wbits);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (wbits == 8 && aligned && K % 256 == 0 && K >= 512 && ws.p)
-        return linear_splitk(8, x, wq, scale, y, M, K, N, epi, bias, residual, ws, st);
-    if (epi != EPI_NONE) {
-        set_error("linear_wq: fused SwiGLU needs the GEMV or split-K path (M=%d K=%d bits=%d)", M, K, wbits);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (wbits == 8 && aligned && K % 64 == 0 && M <= 64) {
-        const int tiles = (N + 15) / 16;
-        const int mt = (M + 15) / 16;
-        const int8_t *w8 = static_cast<const int8_t *>(wq);
-        switch (mt) {
-            case 1: skinny_mfma_w8_kernel<1, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
-            case 2: skinny_mfma_w8_kernel<2, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
-            case 3: skinny_mfma_w8_kernel<3, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
-            default: skinny_mfma_w8_kernel<4, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
+        case LR_W8_SKINNY: {
+            const int tiles = (N + 15) / 16;
+            const int mt = (M + 15) / 16;
+            const int8_t *w8 = static_cast<const int8_t *>(wq);
+            switch (mt) {
+                case 1: skinny_mfma_w8_kernel<1, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
+                case 2: skinny_mfma_w8_kernel<2, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
+                case 3: skinny_mfma_w8_kernel<3, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
+                default: skinny_mfma_w8_kernel<4, 8><<<tiles, 512, 0, st>>>(x, w8, scale, y, M, K, N, bias, residual); break;
+            }
+            return launch_status("linear_w8a16");
         }
-        return launch_status("linear_w8a16");
+        default:
+            return linear_refuse(c, p);
     }
-    // shapes none of the quantised kernels take (K not a multiple of their sub-blocks): the fp16 image, where the caller gave room
-    if (deq && K % 8 == 0 && deq_bytes >= static_cast<size_t>(N) * K * sizeof(half_t) && reinterpret_cast<uintptr_t>(deq) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(wq) % 8 == 0 && (wbits == 8 || (group % 8 == 0 && K % group == 0)) &&
-        (epi != EPI_SWIGLU || M <= 64 || gemm256_swiglu_fills(M, N))) {
-        int rc = dequantize_weights_f16(wbits, wq, scale, static_cast<half_t *>(deq), N, K, group, st);
-        if (rc) return rc;
-        return linear_f16_nk(x, static_cast<const half_t *>(deq), y, M, K, N, epi, bias, residual, SlabWs{nullptr, 0}, st);
-    }
-    set_error("linear_wq: unsupported shape M=%d K=%d N=%d bits=%d without a split-K workspace (int8: M<=64, K%%64==0; int4: "
-              "M<=8 on the GEMV path); size one with llmie_linear_workspace_bytes()", M, K, N, wbits);
-    return LLMIE_ERR_UNSUPPORTED;
 }
 
 }  // namespace llmie
 
 using namespace llmie;
-
-// [fp16 image | slabs] split of a caller workspace (a workspace too small for the image keeps the round-2 meaning: all slabs)
-struct WqWorkspace {
-    void *deq;
-    size_t deq_bytes;
-    SlabWs slabs;
-};
-static WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t workspace_bytes) {
-    const size_t dq = (linear_wq_dequant_bytes(wbits, M, K, N) + 255) & ~static_cast<size_t>(255);
-    if (workspace && dq && workspace_bytes >= dq) {
-        char *b = static_cast<char *>(workspace);
-        return WqWorkspace{b, dq, SlabWs{reinterpret_cast<float *>(b + dq), (workspace_bytes - dq) / sizeof(float)}};
-    }
-    return WqWorkspace{nullptr, 0, SlabWs{static_cast<float *>(workspace), workspace_bytes / sizeof(float)}};
-}
 
 extern "C" int llmie_linear_w8a16(const void *x, const int8_t *wq, const void *scale, void *y, int M, int K, int N,
                                   const void *bias, const void *residual, void *workspace, size_t workspace_bytes,

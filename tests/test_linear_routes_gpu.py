@@ -6,29 +6,8 @@ workspace and operand offsets select (linear_f16_nk / linear_wq predicates and t
 separate residual and once in place, compares both with a float64 reference on the (de-quantised) weights and requires the two
 outputs to be bit-identical.  Every route has a case with ragged M and N edges.
 
-Kernels per case, from one `rocprofv3 --kernel-trace` run of this module on the MI355X (a change of the dispatch predicates or of
-the time models shows up here as a stale row):
-
-  f16  gemv_m5              gemv_ksplit_kernel<5, ...>
-       skinny_m40_nows      skinny_mfma_f16_kernel<3, ...>
-       splitk0_m20          skinny_splitk_kernel + splitk_finalize4_kernel
-       splitk2_m50          mid_splitk_kernel<.., 64, 0> + splitk_finalize4_kernel
-       splitk1_m100         mid_splitk_kernel<.., 128, 0> + splitk_finalize4_kernel
-       splitk1_m150         mid_splitk_kernel<.., 128, 0> + skinny_splitk_kernel (22-row pass), a finalize each
-       passes_*             2 / 3 / 3 x (mid_splitk_kernel + splitk_finalize4_kernel); a 44-row last pass takes the 64-row form
-       midtiles_*           gemm8p_n128_kernel (one partly filled round)
-       tiled_*_nows         tiled_mfma_f16_kernel<true>
-       generic_*            generic_gemm_kernel<half, true>
-  int8 i8_gemv_m7           gemv_ksplit_kernel<7, .., 8, ...>
-       i8_skinny_m40_nows   skinny_mfma_w8_kernel<3, 8>
-       i8_splitk_m100       mid_splitk_kernel<.., 128, 8> + splitk_finalize4_kernel (m150: + skinny_splitk_kernel pass)
-       i8_midpasses_*       2 x (mid_splitk_kernel<.., 128, 8> + splitk_finalize4_kernel)
-       i8_image_m300 / m700 dequant_f16_kernel<8> + gemm8p_n128_kernel
-       i8_image_k1152_m100  dequant_f16_kernel<8> + tiled_mfma_f16_kernel<true>
-  int4 i4_gemv_m3           gemv_ksplit_kernel<3, .., 4, ...>
-       i4_splitk_*          passes of <= 64 rows: skinny_splitk_kernel<4 / 2, 4> + splitk_finalize4_kernel
-       i4_chunks_*          gemv_ksplit_kernel<4, .., 4, ...>, one launch per 4-row chunk
-       i4_image_*           dequant_f16_kernel<4> + gemm8p_n128_kernel
+Which route each case takes is asserted on the host, without a GPU, by tests/test_linear_routes_cpu.py (llmie_linear_route on these
+very case lists: the id's leading part names the route).
 """
 import numpy as np
 import pytest
