@@ -387,11 +387,12 @@ typedef struct {
     int flags;
 } llmie_decoder_config;
 
-/* Weight residency (ABI 3).  An engine whose max_batch lies above the GEMV range (fp16 5, int8 / fp8 2, int4 2 rows) builds
+/* Weight residency (ABI 3).  An engine whose max_batch lies above the GEMV range (gemv_max_batch in csrc/engine.hip is the one table:
+ * fp16 5, int8 / fp8 / int4 2 rows when this was written; ask llmie_decoder_plan_name) builds
  * tile-packed images of its four matrices per layer inside its workspace at create time -- a SNAPSHOT: weights updated in place
  * afterwards are seen by the batch <= GEMV-range and prefill paths, not by the packed one; create synchronises the device before
  * it packs, so uploads on any stream have landed.  By default that image is a second copy next to the caller's row-major matrices.
- *   LLMIE_DEC_NO_PACKED_COPY  no image is built: batches 4..32 take the split-K batch path on the row-major weights (slower there,
+ *   LLMIE_DEC_NO_PACKED_COPY  no image is built: batches above the GEMV range up to 32 take the split-K batch path on the row-major weights (slower there,
  *                             nothing doubled).
  *   LLMIE_DEC_PACKED_ONLY     the images are the ONLY weights the engine reads after create: the `data` arrays of the four
  *                             matrices of every layer may be freed or reused once llmie_decoder_create has returned (scales,
@@ -406,6 +407,27 @@ typedef struct {
 #define LLMIE_DEC_NO_PACKED_COPY 1
 #define LLMIE_DEC_PACKED_ONLY 2
 size_t llmie_decoder_resident_weight_bytes(const llmie_decoder_config *cfg);
+
+/* Which launch sequence an engine of this config runs (an addition within ABI 3; host only, no device access): the plan of
+ * llmie_decoder_forward at `rows` sequences (prefill = 0: "gemv", "packed", "splitk" or "unfused"; LLMIE_CHAIN upgrades "packed" to
+ * the chain launches where its probe of the built engine passes) or of llmie_decoder_prefill at `rows` tokens (prefill = 1:
+ * "packed_only", "short_splitk", "lean" or "general").  call_flags describe the call, switch_mask stands in for the LLMIE_*
+ * environment switches the entry points read.  NULL, with the reason in llmie_last_error(), where the call -- or creating the engine
+ * -- is refused.  tests/golden/decoder_paths.txt pins the answers. */
+#define LLMIE_PLAN_PAGED 1u              /* the *_paged entry points */
+#define LLMIE_PLAN_RAGGED 2u             /* the *_ragged entry points */
+#define LLMIE_PLAN_HIDDEN_MISALIGNED 4u  /* hidden_out not 16-byte aligned */
+#define LLMIE_PLAN_WEIGHTS_MISALIGNED 8u /* a layer matrix not 16-byte aligned (decode: layer 0's QKV matrix) */
+#define LLMIE_PLAN_GAMMAS_MISALIGNED 16u /* a norm gamma not 16-byte aligned */
+#define LLMIE_PLAN_O_BIAS 32u            /* some layer has an output-projection bias */
+#define LLMIE_PLAN_SCALES_MISALIGNED 64u /* an int4 group-scale array not 4-byte aligned */
+#define LLMIE_SW_NO_FUSED_DECODE 1u
+#define LLMIE_SW_NO_FUSED_BATCH 2u
+#define LLMIE_SW_NO_PACKED_BATCH 4u
+#define LLMIE_SW_CHAIN 8u
+#define LLMIE_SW_NO_FUSED_SHORT_PREFILL 16u
+#define LLMIE_SW_NO_QKV_ROPE_FUSION 32u
+const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, int prefill, int rows, unsigned call_flags, unsigned switch_mask);
 
 typedef struct llmie_decoder llmie_decoder; /* opaque */
 

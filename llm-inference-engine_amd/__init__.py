@@ -106,6 +106,7 @@ _SIGS = {
     "llmie_decoder_status": [_vp, _vp],
     "llmie_decoder_resident_weight_bytes": [_vp],
     "llmie_decoder_repack": [_vp, _vp, _vp],
+    "llmie_decoder_plan_name": [_vp, _i, _i, C.c_uint, C.c_uint],
     "llmie_decoder_debug_stamps": [_vp, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
@@ -127,6 +128,7 @@ _RESTYPES = {
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
     "llmie_linear_route": C.c_char_p,
+    "llmie_decoder_plan_name": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
 }
 
@@ -223,6 +225,14 @@ def linear_route(fmt, x, w, scale, y, M, K, N, swiglu=False, group=0, bias=None,
     """name of the kernel route the projection entry points plan for this call, None where they refuse it (llmie_last_error() says
     why).  The operands are ADDRESSES (ints, never dereferenced: only their alignment counts) -- no device needed."""
     r = lib().llmie_linear_route(fmt, x, w, scale, y, M, K, N, int(swiglu), group, bias, residual, workspace, workspace_bytes)
+    return r.decode() if r is not None else None
+
+
+def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):
+    """name of the launch sequence an engine of `cfg` (dict or DecoderConfig) plans for a decode step at `rows` sequences or
+    (prefill=True) a prefill of `rows` tokens; None where the call is refused (llmie_last_error() says why).  No device needed."""
+    c = cfg if isinstance(cfg, DecoderConfig) else DecoderConfig(**cfg)
+    r = lib().llmie_decoder_plan_name(C.byref(c), int(bool(prefill)), rows, call_flags, switch_mask)
     return r.decode() if r is not None else None
 
 

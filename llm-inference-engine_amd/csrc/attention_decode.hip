@@ -850,12 +850,14 @@ static int decoder_mha_fp8kv(const half_t *qkv, const half_t *bias, uint8_t *k_c
 }
 
 // engine entry: same as llmie_decoder_mha with RoPE (table [max_pos][hs/2] of (cos,sin)) fused in front
-int decoder_mha_rope(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer, int batch,
-                     int head_num, int kv_head_num, int head_size, int max_seq_len, int step, const int32_t *step_dev,
+int decoder_mha_rope(const void *qkv, const void *qkv_bias, const KvView &kv, void *out, int layer, int batch,
+                     int head_num, int kv_head_num, int head_size, int max_seq_len, const DecodePos &pos,
                      void *workspace, size_t workspace_bytes, const float2 *rope, int rot_dim, int32_t *tickets,
-                     llmie_dtype dtype, hipStream_t st, const SplitKSlabs *qkv_slabs, const SlabScale *qkv_scale, int kv_fp8,
-                     float k_scale, float v_scale, const int32_t *block_table, int max_pages, int num_pages, int ragged,
-                     int out_x32) {
+                     llmie_dtype dtype, hipStream_t st, const SplitKSlabs *qkv_slabs, const SlabScale *qkv_scale, int out_x32) {
+    void *k_cache = kv.k, *v_cache = kv.v;
+    const int32_t *block_table = kv.block_table, *step_dev = pos.step_dev;
+    const int max_pages = kv.max_pages, num_pages = kv.num_pages, kv_fp8 = kv.fp8, step = pos.step, ragged = pos.ragged;
+    const float k_scale = kv.k_scale, v_scale = kv.v_scale;
     const PagedKv pg{block_table, max_pages, ragged ? 1 : 0, out_x32 ? 1 : 0};
     if (ragged && !step_dev) {
         set_error("decoder_mha: a ragged batch needs the device array of context lengths");
@@ -947,8 +949,8 @@ extern "C" int llmie_decoder_mha_rope(const void *qkv, const void *qkv_bias, voi
     if ((rope_table || tickets) && !(hs_ok && rep_ok))
         LLMIE_UNSUPPORTED("decoder_mha_rope: fused RoPE / in-launch merge need head_size in {32,64,128,256} and "
                           "head_num/kv_head_num in {1,2,4,8}");
-    return decoder_mha_rope(qkv, qkv_bias, k_cache, v_cache, out, layer, batch, head_num, kv_head_num, head_size,
-                            max_seq_len, step, step_dev, workspace, workspace_bytes,
+    return decoder_mha_rope(qkv, qkv_bias, kv_dense(k_cache, v_cache), out, layer, batch, head_num, kv_head_num, head_size,
+                            max_seq_len, DecodePos{step, step_dev, 0}, workspace, workspace_bytes,
                             static_cast<const float2 *>(rope_table), rotary_dim, tickets, dtype, as_stream(stream));
 }
 
@@ -965,7 +967,7 @@ extern "C" int llmie_decoder_mha_ragged(const void *qkv, const void *qkv_bias, v
     LLMIE_REQUIRE(head_num % kv_head_num == 0, "decoder_mha_ragged: kv_head_num must divide head_num");
     LLMIE_REQUIRE(!rope_table || (rotary_dim > 0 && rotary_dim % 2 == 0), "decoder_mha_ragged: bad rotary_dim");
     if (dtype != LLMIE_F32 && dtype != LLMIE_F16) LLMIE_UNSUPPORTED("decoder_mha_ragged: dtype %d", (int)dtype);
-    return decoder_mha_rope(qkv, qkv_bias, k_cache, v_cache, out, layer, batch, head_num, kv_head_num, head_size, max_seq_len, -1,
-                            ctx_len_dev, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim, nullptr,
-                            dtype, as_stream(stream), nullptr, nullptr, 0, 1.f, 1.f, block_table, max_pages, num_pages, 1, 0);
+    return decoder_mha_rope(qkv, qkv_bias, KvView{k_cache, v_cache, block_table, max_pages, num_pages, 0, 1.f, 1.f}, out, layer, batch,
+                            head_num, kv_head_num, head_size, max_seq_len, DecodePos{-1, ctx_len_dev, 1}, workspace, workspace_bytes,
+                            static_cast<const float2 *>(rope_table), rotary_dim, nullptr, dtype, as_stream(stream));
 }

@@ -25,7 +25,7 @@ struct llmie_decoder {
     int H, QKV, I;
     size_t esz;
     // workspace carve-up
-    char *resid, *qkv, *mha, *normed, *act, *gu;
+    char *resid, *qkv, *mha, *act, *gu;
     void *attn_ws;
     size_t attn_ws_bytes;
     float2 *rope_table;  // [max_seq_len][head_size/2] (cos, sin), host-computed at create
@@ -33,7 +33,6 @@ struct llmie_decoder {
     size_t fp8_ws_bytes;
     SlabWs slab_ws;      // fp32 slabs of the split-K projections (batch path, row-major engines)
     unsigned *tail_ticket = nullptr;   // one zeroed word: arrival ticket of the fused decode tail (llmie_lm_head_sample_next)
-    int ragged = 0;      // set for the duration of a *_ragged forward: step_dev is the per-sequence context-length array
     // packed-weight batch path (gemv_max < batch <= 32): tile-packed images of the four matrices of every layer (built once at
     // create time into the caller's workspace: the MI355X's 288 GB buy a second, stream-friendly copy of the weights), the
     // activations between the packed kernels in the x32 layout, and the split-K slabs of the down projection
@@ -52,9 +51,6 @@ struct llmie_decoder {
     unsigned char *pk_base = nullptr;   // first byte of the packed images (the workspace area carved for them)
     unsigned *pk_sync = nullptr, *pk_err = nullptr;
     unsigned long long *pk_stamps = nullptr;   // diagnostic: phase-edge timestamps of the LAST chain launch of a step
-    // paged KV cache of the current llmie_decoder_forward_paged call (null: dense caches)
-    const int32_t *page_table = nullptr;
-    int max_pages = 0, num_pages = 0;
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -133,22 +129,30 @@ static int gemv_max_batch(llmie_weight_format wfmt) {
     }
 }
 
+// The batches an engine with tile-packed images decodes on the packed kernels: above the GEMV crossover (a LLMIE_DEC_PACKED_ONLY
+// engine: every batch), up to 32 rows, fp8 16.  fp8: the per-launch activation quantisation (amax + conversions of the whole register
+// slice) costs ~5 us at 32 rows; measured (7B, ctx 512, tokens/s packed vs split-K batch path): b8 2705 / 2506, b16 5011 / 4450,
+// b24 5656 / 5833, b32 7103 / 7120
+static int packed_rows_max(const llmie_decoder_config &c) { return c.wfmt == LLMIE_W_FP8 ? 16 : 32; }
+static bool packed_batch(const llmie_decoder_config &c, int batch) {
+    return (batch > gemv_max_batch(c.wfmt) || (c.flags & LLMIE_DEC_PACKED_ONLY)) && batch <= packed_rows_max(c);
+}
+
 // weight format / shapes the packed batch path covers; max rows it will be asked for
 static int packed_wf(const llmie_decoder_config *c) {
     if (c->dtype != LLMIE_F16) return 0;
     const int wf = c->wfmt == LLMIE_W_F16 ? PKF_F16
                    : (c->wfmt == LLMIE_W_INT8 ? PKF_I8 : (c->wfmt == LLMIE_W_FP8 ? PKF_FP8 : (c->wfmt == LLMIE_W_INT4 && c->int4_group == 128 ? PKF_I4 : 0)));
-    // batches up to the GEMV crossover never take the packed path: no second copy of the weights for such engines
-    const int gemv_max = gemv_max_batch(c->wfmt);
     const bool only = (c->flags & LLMIE_DEC_PACKED_ONLY) != 0;   // the images are all there is: built whatever the batch
-    if (!wf || (c->flags & LLMIE_DEC_NO_PACKED_COPY) || (!only && c->max_batch <= gemv_max)) return 0;
-    if (only && c->max_batch > (wf == PKF_FP8 ? 16 : 32)) return 0;
+    if (!wf || (c->flags & LLMIE_DEC_NO_PACKED_COPY)) return 0;
+    // no second copy of the weights where no batch up to max_batch takes the packed path; a packed-only engine needs it to take all
+    const int rows_max = packed_rows_max(*c);
+    if (!packed_batch(*c, only || c->max_batch < rows_max ? c->max_batch : rows_max)) return 0;
     const int H = c->head_num * c->head_size, QKV = (c->head_num + 2 * c->kv_head_num) * c->head_size, I = c->inter_size;
     const int m = c->max_batch < 32 ? c->max_batch : 32;
-    const int mm = m;
     if (H % 32 || I % 32) return 0;
-    if (!pk_eligible(wf, mm, H, QKV, PKE_PLAIN) || !pk_eligible(wf, mm, H, H, PKE_PLAIN) || !pk_eligible(wf, mm, H, 2 * I, PKE_SWIGLU) ||
-        !pk_eligible(wf, mm, I, H, PKE_PLAIN))
+    if (!pk_eligible(wf, m, H, QKV, PKE_PLAIN) || !pk_eligible(wf, m, H, H, PKE_PLAIN) || !pk_eligible(wf, m, H, 2 * I, PKE_SWIGLU) ||
+        !pk_eligible(wf, m, I, H, PKE_PLAIN))
         return 0;
     return wf;
 }
@@ -179,7 +183,6 @@ static PackedCarve packed_carve(const llmie_decoder_config *c, int wf) {
     p.total = p.layer_bytes * c->num_layers + p.hx + p.actx + p.mhax + p.slab + p.sync;
     return p;
 }
-
 // fp32 floats of split-K slab scratch the engine's projections can need at up to `rows` activation rows (0: none)
 static size_t engine_slab_floats(const llmie_decoder_config *c, int rows) {
     int wbits;
@@ -210,33 +213,38 @@ static size_t engine_slab_floats(const llmie_decoder_config *c, int rows) {
     return m;
 }
 
-static size_t carve(const llmie_decoder_config *c, size_t *offs /*[12]*/) {
+// the engine's workspace: offsets of its areas, in carve order
+struct EngineCarve {
+    size_t resid, qkv, mha, attn_out, act, gu, attn_ws, rope_table, tail_ticket, fp8_ws, packed, slabs, total;
+};
+static EngineCarve carve(const llmie_decoder_config *c) {
     const size_t e = c->dtype == LLMIE_F16 ? 2 : 4;
     const size_t B = c->max_batch, H = static_cast<size_t>(c->head_num) * c->head_size;
     const size_t QKV = static_cast<size_t>(c->head_num + 2 * c->kv_head_num) * c->head_size;
     const size_t I = c->inter_size;
     Carve k;
-    offs[0] = k.take(B * H * e);        // resid
-    offs[1] = k.take(B * QKV * e);      // qkv
-    offs[2] = k.take(B * H * e);        // mha
-    offs[3] = k.take(B * H * e);        // normed / attn_out
-    offs[4] = k.take(B * I * e);        // act
-    offs[5] = k.take(B * 2 * I * e);    // gate_up (unfused paths)
-    offs[6] = k.take(llmie_decoder_mha_workspace_bytes(c->max_batch, c->head_num, c->head_size, c->max_seq_len));
-    offs[7] = k.take(static_cast<size_t>(c->max_seq_len) * (c->head_size / 2) * sizeof(float2));  // RoPE table
-    offs[8] = k.take(256);   // (spare)
+    EngineCarve o;
+    o.resid = k.take(B * H * e);
+    o.qkv = k.take(B * QKV * e);
+    o.mha = k.take(B * H * e);
+    o.attn_out = k.take(B * H * e);   // (no sequence uses it any more; kept: the workspace size is part of what callers allocate)
+    o.act = k.take(B * I * e);
+    o.gu = k.take(B * 2 * I * e);     // gate_up (unfused paths)
+    o.attn_ws = k.take(llmie_decoder_mha_workspace_bytes(c->max_batch, c->head_num, c->head_size, c->max_seq_len));
+    o.rope_table = k.take(static_cast<size_t>(c->max_seq_len) * (c->head_size / 2) * sizeof(float2));
+    o.tail_ticket = k.take(256);      // arrival ticket word of the fused decode tail
     const int kmax = c->inter_size > static_cast<int>(H) ? c->inter_size : static_cast<int>(H);
-    // fp8: three activation-quantisation units (normed input, attention output, SwiGLU output), see decoder_forward
-    offs[9] = k.take(c->wfmt == LLMIE_W_FP8 ? 3 * llmie_linear_fp8_workspace_bytes(c->max_batch, kmax, 0) : 256);
-    offs[10] = k.take(packed_carve(c, packed_wf(c)).total + 256);   // packed weight images + x32 activations + slabs
-    offs[11] = k.take(engine_slab_floats(c, c->max_batch) * sizeof(float) + 256);   // split-K slabs of the row-major paths
-    return k.off;
+    // fp8: three activation-quantisation units (normed input, attention output, SwiGLU output), see DecodeStep::splitk
+    o.fp8_ws = k.take(c->wfmt == LLMIE_W_FP8 ? 3 * llmie_linear_fp8_workspace_bytes(c->max_batch, kmax, 0) : 256);
+    o.packed = k.take(packed_carve(c, packed_wf(c)).total + 256);   // packed weight images + x32 activations + slabs
+    o.slabs = k.take(engine_slab_floats(c, c->max_batch) * sizeof(float) + 256);   // split-K slabs of the row-major paths
+    o.total = k.off;
+    return o;
 }
 
 extern "C" size_t llmie_decoder_workspace_bytes(const llmie_decoder_config *cfg) {
     if (!config_ok(cfg)) return 0;
-    size_t offs[12];
-    return carve(cfg, offs);
+    return carve(cfg).total;
 }
 
 // (re)build the tile-packed images of every layer from row-major matrices (create; llmie_decoder_repack)
@@ -311,8 +319,8 @@ extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, 
         set_error("decoder_create: NULL layers/workspace");
         return nullptr;
     }
-    size_t offs[12];
-    const size_t need = carve(cfg, offs);
+    const EngineCarve offs = carve(cfg);
+    const size_t need = offs.total;
     if (workspace_bytes < need) {
         set_error("decoder_create: workspace too small (%zu < %zu)", workspace_bytes, need);
         return nullptr;
@@ -342,27 +350,26 @@ extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, 
     d->I = cfg->inter_size;
     d->esz = cfg->dtype == LLMIE_F16 ? 2 : 4;
     char *base = static_cast<char *>(workspace);
-    d->resid = base + offs[0];
-    d->qkv = base + offs[1];
-    d->mha = base + offs[2];
-    d->normed = base + offs[3];
-    d->act = base + offs[4];
-    d->gu = base + offs[5];
-    d->attn_ws = base + offs[6];
+    d->resid = base + offs.resid;
+    d->qkv = base + offs.qkv;
+    d->mha = base + offs.mha;
+    d->act = base + offs.act;
+    d->gu = base + offs.gu;
+    d->attn_ws = base + offs.attn_ws;
     d->attn_ws_bytes = llmie_decoder_mha_workspace_bytes(cfg->max_batch, cfg->head_num, cfg->head_size, cfg->max_seq_len);
-    d->rope_table = reinterpret_cast<float2 *>(base + offs[7]);
-    d->tail_ticket = reinterpret_cast<unsigned *>(base + offs[8]);
+    d->rope_table = reinterpret_cast<float2 *>(base + offs.rope_table);
+    d->tail_ticket = reinterpret_cast<unsigned *>(base + offs.tail_ticket);
     if (hipMemset(d->tail_ticket, 0, 256) != hipSuccess) {
         set_error("decoder_create: clearing the workspace words failed");
         delete d;
         return nullptr;
     }
-    d->fp8_ws = base + offs[9];
+    d->fp8_ws = base + offs.fp8_ws;
     {
         const int kmax = cfg->inter_size > d->H ? cfg->inter_size : d->H;
         d->fp8_ws_bytes = cfg->wfmt == LLMIE_W_FP8 ? llmie_linear_fp8_workspace_bytes(cfg->max_batch, kmax, 0) : 0;
     }
-    d->slab_ws = SlabWs{reinterpret_cast<float *>(base + offs[11]), engine_slab_floats(cfg, cfg->max_batch)};
+    d->slab_ws = SlabWs{reinterpret_cast<float *>(base + offs.slabs), engine_slab_floats(cfg, cfg->max_batch)};
     if (!d->slab_ws.floats) d->slab_ws.p = nullptr;
     d->pk_wf = packed_wf(cfg);
     if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !d->pk_wf) {
@@ -380,7 +387,7 @@ extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, 
         // one-time re-tiling of every matrix into the stream-friendly image (null stream, synchronous: create is not on the
         // compute path); the row-major originals stay in use for batch <= gemv_max (GEMV) and for prefill
         const PackedCarve pc = packed_carve(cfg, d->pk_wf);
-        unsigned char *pb = reinterpret_cast<unsigned char *>(base + offs[10]);
+        unsigned char *pb = reinterpret_cast<unsigned char *>(base + offs.packed);
         d->pk_base = pb;
         const int prc = pack_layers(d, layers, nullptr);
         unsigned char *tail = pb + pc.layer_bytes * cfg->num_layers;
@@ -541,26 +548,197 @@ static int engine_linear(const llmie_decoder *d, llmie_weight_format fmt, const 
     }
 }
 
-extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache,
-                                     void *v_cache, int batch, int step, const int32_t *step_dev,
-                                     llmie_stream stream) {
-    LLMIE_REQUIRE(dec && hidden_in && hidden_out && k_cache && v_cache, "decoder_forward: NULL pointer");
-    const llmie_decoder_config &c = dec->cfg;
-    LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "decoder_forward: batch %d outside [1,%d]", batch, c.max_batch);
-    LLMIE_REQUIRE(step_dev || (step >= 1 && step <= c.max_seq_len), "decoder_forward: step %d outside [1,%d]", step,
-                  c.max_seq_len);
-    const int H = dec->H, QKV = dec->QKV, I = dec->I;
-    const llmie_dtype dt = c.dtype;
-    int rc;
-    if (hidden_out != hidden_in) {
-        hipError_t e = hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(batch) * H * dec->esz,
-                                      hipMemcpyDeviceToDevice, as_stream(stream));
-        if (e != hipSuccess) {
-            set_error("decoder_forward: copy failed: %s", hipGetErrorString(e));
-            return LLMIE_ERR_LAUNCH;
-        }
+// ---- which launch sequence a call runs: decided once, by a pure host function per entry point (no device access, no getenv) ----
+// The environment switches of the engine, read once per process.  (LLMIE_NO_NORM_QUANT belongs to norm.hip.)
+struct EngineSwitches {
+    bool no_fused_decode, no_fused_batch, no_packed_batch, chain, no_fused_short_prefill, no_qkv_rope_fusion;
+};
+static const EngineSwitches &engine_switches() {
+    static const EngineSwitches s{getenv("LLMIE_NO_FUSED_DECODE") != nullptr,        getenv("LLMIE_NO_FUSED_BATCH") != nullptr,
+                                  getenv("LLMIE_NO_PACKED_BATCH") != nullptr,        getenv("LLMIE_CHAIN") != nullptr,
+                                  getenv("LLMIE_NO_FUSED_SHORT_PREFILL") != nullptr, getenv("LLMIE_NO_QKV_ROPE_FUSION") != nullptr};
+    return s;
+}
+static EngineSwitches switches_of_mask(unsigned m) {
+    return EngineSwitches{(m & LLMIE_SW_NO_FUSED_DECODE) != 0,        (m & LLMIE_SW_NO_FUSED_BATCH) != 0, (m & LLMIE_SW_NO_PACKED_BATCH) != 0,
+                          (m & LLMIE_SW_CHAIN) != 0,                  (m & LLMIE_SW_NO_FUSED_SHORT_PREFILL) != 0,
+                          (m & LLMIE_SW_NO_QKV_ROPE_FUSION) != 0};
+}
+// head sizes / head ratios of the attention kernels with RoPE, bias and the KV append fused in front
+static bool fused_attention_geometry(const llmie_decoder_config &c) {
+    const int rep = c.head_num / c.kv_head_num;
+    return (c.head_size == 32 || c.head_size == 64 || c.head_size == 128 || c.head_size == 256) && (rep == 1 || rep == 2 || rep == 4 || rep == 8);
+}
+
+enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED };
+enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED };
+// One decode call as the planner sees it.  mis_hidden / mis_wqkv0: address % 16 of the hidden state and of layer 0's QKV matrix.
+struct DecodeCall {
+    llmie_decoder_config cfg;
+    int batch;
+    bool paged, ragged;
+    unsigned mis_hidden, mis_wqkv0;
+    EngineSwitches sw;
+};
+// The LLMIE_CHAIN probe (can every projection of a layer join a chain at this batch?) reads the engine's images and LDS plans, so it
+// stays with the packed sequence: the plan answers DP_PACKED with chain_wanted, and the dispatch upgrades to DP_PACKED_CHAIN where
+// the probe passes.
+struct DecodePlan {
+    int path, refusal;
+    bool chain_wanted;
+};
+static DecodePlan plan_decode(const DecodeCall &d) {
+    const llmie_decoder_config &c = d.cfg;
+    const int batch = d.batch, H = c.head_num * c.head_size, I = c.inter_size;
+    const bool attn_ok = fused_attention_geometry(c);
+    const int wbits = c.wfmt == LLMIE_W_F16 ? 16 : (c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0));
+    const bool fp8 = c.wfmt == LLMIE_W_FP8, packed_only = (c.flags & LLMIE_DEC_PACKED_ONLY) != 0;
+    // GEMV form up to gemv_max rows (its dot products are VALU work that grows with the batch), MFMA split-K above
+    // measured crossover on MI355X (7B, ctx 512, tokens/s GEMV vs split-K): fp16 b4 1157/1143, b6 1496/1592; int8 b4 1416/1404,
+    // b6 1672/1962; fp8 b3 947/944, b4 1127/1213; int4 b2 796/745, b3 896/1074
+    const int gemv_max = gemv_max_batch(c.wfmt);
+    const bool int4_ok = wbits == 4 && c.int4_group == 128 && batch <= 64;  // int4 MFMA form: group-128 scales, 64 rows per pass
+    const bool batch_path_ok = !d.sw.no_fused_batch && c.dtype == LLMIE_F16 && (wbits == 16 || wbits == 8 || int4_ok || fp8) && attn_ok &&
+                               batch <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H);
+    // (gemv_f16_eligible looks at the two addresses' alignment only)
+    const bool gemv_ok = !packed_only && (batch <= gemv_max || !batch_path_ok) &&
+                         (wbits == 16 ? gemv_f16_eligible(batch, H, reinterpret_cast<const void *>(static_cast<uintptr_t>(d.mis_hidden)),
+                                                          reinterpret_cast<const void *>(static_cast<uintptr_t>(d.mis_wqkv0)))
+                                      : ((wbits != 0 || fp8) && ksplit_eligible(batch, H, fp8 ? 8 : wbits)));
+    // (fp8: gemv_ok holds ksplit_eligible(batch, H, 8), so every projection with a fused norm or SwiGLU -- K = H -- has its GEMV form)
+    if (!d.sw.no_fused_decode && c.dtype == LLMIE_F16 && (wbits != 0 || fp8) && attn_ok && H % 8 == 0 && gemv_ok) return {DP_GEMV, DREF_NONE, false};
+    const bool packed_on = !d.sw.no_packed_batch && !d.sw.no_fused_decode && attn_ok;
+    if (packed_only && !(packed_on && packed_batch(c, batch))) return {DP_REFUSED, DREF_PACKED_ONLY, false};
+    if (packed_on && packed_wf(&c) && packed_batch(c, batch)) return {DP_PACKED, DREF_NONE, d.sw.chain};
+    if (batch_path_ok) return {DP_SPLITK, DREF_NONE, false};
+    if (d.paged) return {DP_REFUSED, DREF_PAGED, false};
+    if (c.kv_fmt == LLMIE_KV_FP8) return {DP_REFUSED, DREF_KV_FP8, false};
+    if (d.ragged && !attn_ok) return {DP_REFUSED, DREF_RAGGED, false};
+    return {DP_UNFUSED, DREF_NONE, false};
+}
+static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
+    switch (p.refusal) {
+        case DREF_PACKED_ONLY:
+            set_error("decoder_forward: a LLMIE_DEC_PACKED_ONLY engine decodes on the packed kernels only (batch <= %d, no path switch)",
+                      packed_rows_max(d.cfg));
+            break;
+        case DREF_PAGED: set_error("decoder_forward_paged: the paged KV cache needs the fused decode paths (fp16 engines, batch <= 128)"); break;
+        case DREF_KV_FP8:
+            set_error("decoder_forward: the fp8 KV cache needs the fused decode paths (batch <= 128, fp16/int8/int4/fp8 weights with "
+                      "H and I multiples of 256 at batch > 8)");
+            break;
+        default: set_error("decoder_forward_ragged: needs head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}"); break;
     }
-    void *h = hidden_out;  // running hidden state, updated in place like decoder_output in the reference
+    return LLMIE_ERR_UNSUPPORTED;
+}
+static const char *decode_path_name(int path) {
+    static const char *const names[] = {"refused", "gemv", "packed", "packed_chain", "splitk", "unfused"};
+    return names[path];
+}
+
+enum PrefillPath : int { PP_REFUSED = 0, PP_PACKED_ONLY, PP_SHORT_SPLITK, PP_LEAN, PP_GENERAL };
+enum PrefillRefusal : int { PREF_NONE = 0, PREF_FORMAT, PREF_PACKED_ONLY_FP8 };
+// One prefill call as the planner sees it.  The split-K kernels read the weights, the out-of-place norms hidden_out and the gammas
+// in 16-byte vectors: weights handed over as views at other offsets (llmie_decoder_create takes any address) run the general sequences.
+struct PrefillCall {
+    llmie_decoder_config cfg;
+    int T;
+    bool weights_a16;         // every layer matrix 16-byte aligned
+    bool int4_scales_a4;      // every int4 group-scale array 4-byte aligned
+    bool hidden_gammas_a16;   // hidden_out and every gamma 16-byte aligned
+    bool o_bias;              // some layer has an output-projection bias
+    EngineSwitches sw;
+};
+struct PrefillPlan {
+    int path, refusal;
+};
+static PrefillPlan plan_prefill(const PrefillCall &p) {
+    const llmie_decoder_config &c = p.cfg;
+    const int T = p.T, H = c.head_num * c.head_size, I = c.inter_size;
+    const bool fp8 = c.wfmt == LLMIE_W_FP8;
+    const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
+    if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits) || c.head_size != 128) return {PP_REFUSED, PREF_FORMAT};
+    if (c.flags & LLMIE_DEC_PACKED_ONLY) return fp8 ? PrefillPlan{PP_REFUSED, PREF_PACKED_ONLY_FP8} : PrefillPlan{PP_PACKED_ONLY, PREF_NONE};
+    const bool short_fmt_ok = !fp8 && (wqbits != 4 || (c.int4_group == 128 && T <= 64));   // int4 split-K form: 64 rows, group 128
+    if (!p.sw.no_fused_short_prefill && short_fmt_ok && p.weights_a16 && (wqbits != 4 || p.int4_scales_a4) && T <= 128 && H % 256 == 0 &&
+        I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H))
+        return {PP_SHORT_SPLITK, PREF_NONE};
+    if (!fp8 && p.hidden_gammas_a16 && rmsnorm_oop_eligible(H) && !p.o_bias) return {PP_LEAN, PREF_NONE};
+    return {PP_GENERAL, PREF_NONE};
+}
+static int prefill_refuse(const PrefillPlan &p) {
+    if (p.refusal == PREF_FORMAT)
+        LLMIE_UNSUPPORTED("decoder_prefill: fp16 activations + fp16 / int8 / int4 / fp8 weights + head_size 128 only (use the per-kernel path)");
+    LLMIE_UNSUPPORTED("decoder_prefill: LLMIE_DEC_PACKED_ONLY engines prefill fp16 / int8 / int4 weights only");
+}
+static const char *prefill_path_name(int path) {
+    static const char *const names[] = {"refused", "packed_only", "short_splitk", "lean", "general"};
+    return names[path];
+}
+
+// Host-only: the launch sequence llmie_decoder_forward (prefill = 0, rows = batch) or llmie_decoder_prefill (prefill = 1, rows =
+// tokens) plans for an engine of this config; NULL with llmie_last_error() set where the call -- or creating the engine -- is refused.
+extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, int prefill, int rows, unsigned call_flags,
+                                               unsigned switch_mask) {
+    if (!config_ok(cfg)) {
+        set_error("decoder_plan_name: invalid config");
+        return nullptr;
+    }
+    if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !packed_wf(cfg)) {
+        set_error("decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take");
+        return nullptr;
+    }
+    const EngineSwitches sw = switches_of_mask(switch_mask);
+    if (prefill) {
+        if (rows < 1) {
+            set_error("decoder_plan_name: %d tokens", rows);
+            return nullptr;
+        }
+        const PrefillCall pc{*cfg, rows, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
+                             !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw};
+        const PrefillPlan p = plan_prefill(pc);
+        if (p.path == PP_REFUSED) return (void)prefill_refuse(p), nullptr;
+        return prefill_path_name(p.path);
+    }
+    if (rows < 1 || rows > cfg->max_batch) {
+        set_error("decoder_forward: batch %d outside [1,%d]", rows, cfg->max_batch);
+        return nullptr;
+    }
+    const DecodeCall dc{*cfg, rows, (call_flags & LLMIE_PLAN_PAGED) != 0, (call_flags & LLMIE_PLAN_RAGGED) != 0,
+                        (call_flags & LLMIE_PLAN_HIDDEN_MISALIGNED) ? 8u : 0u, (call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED) ? 8u : 0u, sw};
+    const DecodePlan p = plan_decode(dc);
+    if (p.path == DP_REFUSED) return (void)decode_refuse(dc, p), nullptr;
+    return decode_path_name(p.path);
+}
+
+// the KV cache of an engine call (block_table null: dense caches)
+static KvView kv_view(const llmie_decoder_config &c, void *k, void *v, const int32_t *block_table, int max_pages, int num_pages) {
+    const bool fp8 = c.kv_fmt == LLMIE_KV_FP8;
+    return KvView{k, v, block_table, max_pages, num_pages, fp8 ? 1 : 0, (fp8 && c.k_scale > 0.f) ? c.k_scale : 1.f,
+                  (fp8 && c.v_scale > 0.f) ? c.v_scale : 1.f};
+}
+
+// One decode step: the call as every launch sequence reads it.  The sequences are members, so their bodies name the call's parts
+// like locals.
+struct DecodeStep {
+    llmie_decoder *dec;
+    const llmie_decoder_config &c;
+    void *h;  // running hidden state, updated in place like decoder_output in the reference
+    int batch;
+    KvView kv;
+    DecodePos pos;
+    llmie_stream stream;
+    hipStream_t st;
+    int H, QKV, I, wbits;
+    bool fp8;
+    llmie_dtype dt;
+
+    // attention with RoPE, bias and the KV append fused in front; out_x32: `out` is the x32 image of the packed sequences
+    int attention(const void *qkv, const void *qkv_bias, void *out, int layer, const SplitKSlabs *qkv_slabs = nullptr,
+                  const SlabScale *qkv_scale = nullptr, int out_x32 = 0) const {
+        return decoder_mha_rope(qkv, qkv_bias, kv, out, layer, batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, pos, dec->attn_ws,
+                                dec->attn_ws_bytes, dec->rope_table, c.rotary_dim, nullptr, dt, st, qkv_slabs, qkv_scale, out_x32);
+    }
 
     // ---- fused fp16 decode path (batch <= 8): 5 launches per layer ----
     //   qkv  = rmsnorm(h)*g1 . Wqkv^T                      (norm fused into the GEMV prologue)
@@ -569,27 +747,8 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
     //   act  = swiglu(rmsnorm(h + o.bias)*g2 . Wgu^T)      (norm prologue + SwiGLU epilogue)
     //   h   += act . Wd^T
     // Same math as self_decoder.cpp:69-119 (residual updated before the o.bias add, as the reference).
-    static const int fused_off = getenv("LLMIE_NO_FUSED_DECODE") ? 1 : 0;
-    const int rep = c.head_num / c.kv_head_num;
-    const bool hs_ok = c.head_size == 32 || c.head_size == 64 || c.head_size == 128 || c.head_size == 256;
-    const bool rep_ok = rep == 1 || rep == 2 || rep == 4 || rep == 8;
-    const int wbits = c.wfmt == LLMIE_W_F16 ? 16 : (c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0));
-    const bool fp8 = c.wfmt == LLMIE_W_FP8;
-    const int kv8 = c.kv_fmt == LLMIE_KV_FP8;
-    const float k_scale = c.k_scale > 0.f ? c.k_scale : 1.f, v_scale = c.v_scale > 0.f ? c.v_scale : 1.f;
-    // GEMV form up to gemv_max rows (its dot products are VALU work that grows with the batch), MFMA split-K above
-    // measured crossover on MI355X (7B, ctx 512, tokens/s GEMV vs split-K): fp16 b4 1157/1143, b6 1496/1592; int8 b4 1416/1404,
-    // b6 1672/1962; fp8 b3 947/944, b4 1127/1213; int4 b2 796/745, b3 896/1074
-    const int gemv_max = gemv_max_batch(c.wfmt);
-    static const int batch_fused_off = getenv("LLMIE_NO_FUSED_BATCH") ? 1 : 0;
-    const bool int4_ok = wbits == 4 && c.int4_group == 128 && batch <= 64;  // int4 MFMA form: group-128 scales, 64 rows per pass
-    const bool batch_path_ok = !batch_fused_off && c.dtype == LLMIE_F16 && (wbits == 16 || wbits == 8 || int4_ok || fp8) && hs_ok &&
-                               rep_ok && batch <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H);
-    const bool gemv_ok = !dec->packed_only && (batch <= gemv_max || !batch_path_ok) &&
-                         (wbits == 16 ? gemv_f16_eligible(batch, H, h, dec->layers[0].qkv.data)
-                                      : ((wbits != 0 || fp8) && ksplit_eligible(batch, H, fp8 ? 8 : wbits)));
-    if (!fused_off && c.dtype == LLMIE_F16 && (wbits != 0 || fp8) && hs_ok && rep_ok && H % 8 == 0 && gemv_ok) {
-        hipStream_t st = as_stream(stream);
+    int gemv() const {
+        int rc;
         // (the in-launch merge of the attention partials -- the tickets argument of llmie_decoder_mha_rope -- measured SLOWER than the
         // separate 4.8 us merge kernel on MI355X, 2.97 vs 2.81 ms per token: every workgroup pays the release fence; the engine
         // always uses the merge kernel)
@@ -603,10 +762,7 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
                     return linear_fp8_gemv((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, batch,
                                            K, N, epi, nullptr, (const half_t *)residual, (const half_t *)gamma,
                                            (const half_t *)pre_bias, c.rms_eps, st);
-                if (epi != EPI_NONE_ || gamma) {
-                    set_error("engine: fp8 projection K=%d at batch %d has no fused form", K, batch);
-                    return LLMIE_ERR_UNSUPPORTED;
-                }
+                // (plan_decode: a projection with a fused norm or SwiGLU has K = H, which the plan found GEMV-eligible)
                 return linear_fp8((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, batch, K, N, nullptr,
                                   (const half_t *)residual, dec->fp8_ws, dec->fp8_ws_bytes, dec->slab_ws, st);
             }
@@ -625,12 +781,7 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
             TIMED(LLMIE_OP_QKV_GEMM, lin(h, w.qkv, dec->qkv, H, QKV, EPI_NONE_, nullptr, w.attn_norm_gamma, nullptr));
-            TIMED(LLMIE_OP_MHA, decoder_mha_rope(dec->qkv, w.qkv.bias, k_cache, v_cache, dec->mha, l, batch, c.head_num,
-                                                 c.kv_head_num, c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws,
-                                                 dec->attn_ws_bytes, dec->rope_table, c.rotary_dim,
-                                                 nullptr, dt, st, nullptr,
-                                                 nullptr, kv8, k_scale, v_scale, dec->page_table, dec->max_pages, dec->num_pages,
-                                                 dec->ragged));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
             TIMED(LLMIE_OP_O_GEMM, lin(dec->mha, w.o, h, H, H, EPI_NONE_, h, nullptr, nullptr));
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, lin(h, w.gate_up, dec->act, H, 2 * I, EPI_SWIGLU_, nullptr, w.ffn_norm_gamma, w.o.bias));
             TIMED(LLMIE_OP_DOWN_GEMM, lin(dec->act, w.down, h, I, H, EPI_NONE_, h, nullptr, nullptr));
@@ -646,76 +797,11 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
     //   actx = swiglu(rmsnorm(hx + o.bias) * g2 . Wgu^T)
     //   hx  += actx . Wd^T                          K split over workgroups (K = inter_size) + one reduce launch
     // Same math as self_decoder.cpp:69-119.  Weights come from the tile-packed images built at create time.
-    static const int packed_off = getenv("LLMIE_NO_PACKED_BATCH") ? 1 : 0;
-    // fp8: the per-launch activation quantisation (amax + conversions of the whole register slice) costs ~5 us at 32 rows;
-    // measured (7B, ctx 512, tokens/s packed vs split-K batch path): b8 2705 / 2506, b16 5011 / 4450, b24 5656 / 5833, b32 7103 / 7120
-    const int pk_rows_max = fp8 ? 16 : 32;
-    if (dec->packed_only && (packed_off || fused_off || batch > pk_rows_max || !hs_ok || !rep_ok)) {
-        set_error("decoder_forward: a LLMIE_DEC_PACKED_ONLY engine decodes on the packed kernels only (batch <= %d, no path switch)", pk_rows_max);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!packed_off && !fused_off && dec->pk_wf && (batch > gemv_max || dec->packed_only) && batch <= pk_rows_max && hs_ok && rep_ok) {
-        hipStream_t st = as_stream(stream);
+    int packed() const {
+        int rc;
         const int wf = dec->pk_wf;
         half_t *hh = static_cast<half_t *>(h);
         half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
-        // Round 3, OPT-IN (LLMIE_CHAIN=1): ONE persistent launch per layer for the chain O -> gate/up -> down (-> slab reduce) -> next
-        // layer's QKV (pk_gemm.cuh, pk_chain_kernel: grid barriers between the phases, the next phase's weight ring prefetched across
-        // each): 2 launches per layer (attention + chain) instead of 6, the launches' own code per phase (bit-identical outputs).
-        // Measured SLOWER than the launch sequence (int8, batch 32, MI355X: 94 us per chain against 78 us for the five launches it
-        // replaces; phase-edge timestamps, DESIGN.md section 9: a phase inside the chain takes what its launch takes -- the ~8 us of
-        // fixed cost per projection is the kernel's own prologue (activation slice, norm) and epilogue, not the launch -- and a grid
-        // barrier costs 5.5-7 us against ~2.5 us for a launch boundary), so the launch sequence stays the default.
-        static const int chain_off = getenv("LLMIE_CHAIN") ? 0 : 1;
-        bool chain = !chain_off && dec->pk_sync != nullptr;
-        if (chain) {
-            // probe: can every projection of a layer join a chain at this batch?  (pk_chain_add validates shapes / plans / LDS)
-            const llmie_layer_weights &w = dec->layers[0];
-            const llmie_decoder::PackedLayer &pw = dec->packed[0];
-            PkChain ch;
-            pk_chain_begin(&ch, wf, batch);
-            chain = ch.ok &&
-                    !pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | PKX_RES, dec->hx, nullptr, nullptr, 0.f, nullptr, 0) &&
-                    !pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
-                                  static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0) &&
-                    !pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, dec->hx, I, H, PKE_PLAIN, PKX_X | PKX_RES | PKX_Y, dec->hx, nullptr, nullptr,
-                                  0.f, dec->pk_slab, dec->pk_slab_floats) &&
-                    (c.num_layers == 1 ||
-                     !pk_chain_add(&ch, 4, dec->hx, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
-                                   static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0));
-        }
-        if (chain) {
-            for (int l = 0; l < c.num_layers; ++l) {
-                const llmie_layer_weights &w = dec->layers[l];
-                const llmie_decoder::PackedLayer &pw = dec->packed[l];
-                const bool first = l == 0, last = l + 1 == c.num_layers;
-                if (first)
-                    TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, hh, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, batch, H, QKV, PKE_PLAIN, 0, nullptr,
-                                                       static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0, st));
-                TIMED(LLMIE_OP_MHA, decoder_mha_rope(dec->qkv, w.qkv.bias, k_cache, v_cache, dec->mhax, l, batch, c.head_num, c.kv_head_num,
-                                                     c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws, dec->attn_ws_bytes,
-                                                     dec->rope_table, c.rotary_dim, nullptr, dt, st, nullptr, nullptr, kv8, k_scale, v_scale,
-                                                     dec->page_table, dec->max_pages, dec->num_pages, dec->ragged, 1));
-                PkChain ch;
-                pk_chain_begin(&ch, wf, batch);
-                rc = pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES),
-                                  first ? hh : dec->hx, nullptr, nullptr, 0.f, nullptr, 0);
-                if (!rc) rc = pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
-                                           static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0);
-                if (!rc) rc = pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, last ? hh : dec->hx, I, H, PKE_PLAIN,
-                                           PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr, 0.f, dec->pk_slab, dec->pk_slab_floats);
-                if (!rc && !last) {
-                    const llmie_layer_weights &wn = dec->layers[l + 1];
-                    const llmie_decoder::PackedLayer &pn = dec->packed[l + 1];
-                    rc = pk_chain_add(&ch, 4, dec->hx, pn.qkv, pn.sc[0] ? pn.sc[0] : wn.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
-                                      static_cast<const half_t *>(wn.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0);
-                }
-                if (rc) return rc;
-                ch.stamps = dec->pk_stamps;   // (diagnostic; null unless llmie_decoder_debug_stamps armed it)
-                TIMED(LLMIE_OP_CHAIN, pk_chain_launch(&ch, dec->pk_sync + static_cast<size_t>(l) * (pk_chain_sync_bytes() / sizeof(unsigned)), dec->pk_err, st));
-            }
-            return LLMIE_OK;
-        }
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
             const llmie_decoder::PackedLayer &pw = dec->packed[l];
@@ -723,10 +809,7 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
             // layer 0 reads the caller's row-major hidden state; from its output projection on the residual stream lives in hx
             TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, first ? hh : dec->hx, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, batch, H, QKV, PKE_PLAIN, first ? 0 : PKX_X,
                                                nullptr, static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0, st));
-            TIMED(LLMIE_OP_MHA, decoder_mha_rope(dec->qkv, w.qkv.bias, k_cache, v_cache, dec->mhax, l, batch, c.head_num, c.kv_head_num,
-                                                 c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws, dec->attn_ws_bytes,
-                                                 dec->rope_table, c.rotary_dim, nullptr, dt, st, nullptr, nullptr, kv8, k_scale, v_scale,
-                                                 dec->page_table, dec->max_pages, dec->num_pages, dec->ragged, 1));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
             TIMED(LLMIE_OP_O_GEMM, pk_linear(wf, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, batch, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES),
                                              first ? hh : dec->hx, nullptr, nullptr, 0.f, nullptr, 0, st));
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, pk_linear(wf, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, batch, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y,
@@ -735,6 +818,65 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
             TIMED(LLMIE_OP_DOWN_GEMM, pk_linear(wf, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, last ? hh : dec->hx, batch, I, H, PKE_PLAIN,
                                                 PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr, 0.f, dec->pk_slab,
                                                 dec->pk_slab_floats, st));
+        }
+        return LLMIE_OK;
+    }
+    // Round 3, OPT-IN (LLMIE_CHAIN=1): ONE persistent launch per layer for the chain O -> gate/up -> down (-> slab reduce) -> next
+    // layer's QKV (pk_gemm.cuh, pk_chain_kernel: grid barriers between the phases, the next phase's weight ring prefetched across
+    // each): 2 launches per layer (attention + chain) instead of 6, the launches' own code per phase (bit-identical outputs).
+    // Measured SLOWER than the launch sequence (int8, batch 32, MI355X: 94 us per chain against 78 us for the five launches it
+    // replaces; phase-edge timestamps, DESIGN.md section 9: a phase inside the chain takes what its launch takes -- the ~8 us of
+    // fixed cost per projection is the kernel's own prologue (activation slice, norm) and epilogue, not the launch -- and a grid
+    // barrier costs 5.5-7 us against ~2.5 us for a launch boundary), so the launch sequence stays the default.
+    // probe: can every projection of a layer join a chain at this batch?  (pk_chain_add validates shapes / plans / LDS)
+    bool chain_joins() const {
+        if (!dec->pk_sync) return false;
+        const int wf = dec->pk_wf;
+        half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
+        const llmie_layer_weights &w = dec->layers[0];
+        const llmie_decoder::PackedLayer &pw = dec->packed[0];
+        PkChain ch;
+        pk_chain_begin(&ch, wf, batch);
+        return ch.ok &&
+                !pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | PKX_RES, dec->hx, nullptr, nullptr, 0.f, nullptr, 0) &&
+                !pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
+                              static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0) &&
+                !pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, dec->hx, I, H, PKE_PLAIN, PKX_X | PKX_RES | PKX_Y, dec->hx, nullptr, nullptr,
+                              0.f, dec->pk_slab, dec->pk_slab_floats) &&
+                (c.num_layers == 1 ||
+                 !pk_chain_add(&ch, 4, dec->hx, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
+                               static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0));
+    }
+    int packed_chain() const {
+        int rc;
+        const int wf = dec->pk_wf;
+        half_t *hh = static_cast<half_t *>(h);
+        half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
+        for (int l = 0; l < c.num_layers; ++l) {
+            const llmie_layer_weights &w = dec->layers[l];
+            const llmie_decoder::PackedLayer &pw = dec->packed[l];
+            const bool first = l == 0, last = l + 1 == c.num_layers;
+            if (first)
+                TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, hh, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, batch, H, QKV, PKE_PLAIN, 0, nullptr,
+                                                   static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0, st));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
+            PkChain ch;
+            pk_chain_begin(&ch, wf, batch);
+            rc = pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES),
+                              first ? hh : dec->hx, nullptr, nullptr, 0.f, nullptr, 0);
+            if (!rc) rc = pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
+                                       static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0);
+            if (!rc) rc = pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, last ? hh : dec->hx, I, H, PKE_PLAIN,
+                                       PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr, 0.f, dec->pk_slab, dec->pk_slab_floats);
+            if (!rc && !last) {
+                const llmie_layer_weights &wn = dec->layers[l + 1];
+                const llmie_decoder::PackedLayer &pn = dec->packed[l + 1];
+                rc = pk_chain_add(&ch, 4, dec->hx, pn.qkv, pn.sc[0] ? pn.sc[0] : wn.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
+                                  static_cast<const half_t *>(wn.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0);
+            }
+            if (rc) return rc;
+            ch.stamps = dec->pk_stamps;   // (diagnostic; null unless llmie_decoder_debug_stamps armed it)
+            TIMED(LLMIE_OP_CHAIN, pk_chain_launch(&ch, dec->pk_sync + static_cast<size_t>(l) * (pk_chain_sync_bytes() / sizeof(unsigned)), dec->pk_err, st));
         }
         return LLMIE_OK;
     }
@@ -748,8 +890,8 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
     // (each small dependent launch costs ~4.5 us on MI355X, a third of a batch-32 int8 layer before this fusion)
     // fp8: activations enter every projection as per-token e4m3; the row kernel emits them directly for the qkv and
     // gate_up inputs, the attention and SwiGLU outputs take a quantize_rows launch each (10 launches per layer).
-    if (batch_path_ok) {
-        hipStream_t st = as_stream(stream);
+    int splitk() const {
+        int rc;
         half_t *hh = static_cast<half_t *>(h), *resid = reinterpret_cast<half_t *>(dec->resid);
         half_t *mha = reinterpret_cast<half_t *>(dec->mha), *act = reinterpret_cast<half_t *>(dec->act);
         const int fmt = fp8 ? WF_FP8 : wbits;
@@ -776,10 +918,7 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
             SplitKSlabs sk;
             TIMED(LLMIE_OP_QKV_GEMM, linear_splitk_partial(fmt, xin, w.qkv.data, batch, H, QKV, st, &sk, dec->slab_ws, gs_of(w.qkv)));
             const SlabScale qsc = scale_of(w.qkv, xsA);
-            TIMED(LLMIE_OP_MHA, decoder_mha_rope(nullptr, w.qkv.bias, k_cache, v_cache, dec->mha, l, batch, c.head_num,
-                                                 c.kv_head_num, c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws,
-                                                 dec->attn_ws_bytes, dec->rope_table, c.rotary_dim, nullptr, dt, st, &sk, &qsc, kv8,
-                                                 k_scale, v_scale, dec->page_table, dec->max_pages, dec->num_pages, dec->ragged));
+            TIMED(LLMIE_OP_MHA, attention(nullptr, w.qkv.bias, dec->mha, l, &sk, &qsc));
             if (fp8) TIMED(LLMIE_OP_O_GEMM, quantize_rows_fp8(mha, xqB, xsB, batch, H, st));
             TIMED(LLMIE_OP_O_GEMM, linear_splitk_partial(fmt, fp8 ? static_cast<const void *>(xqB) : mha, w.o.data, batch, H, H, st, &sk, dec->slab_ws, gs_of(w.o)));
             // self_decoder.cpp:92  h += resid; resid = h; h += o.bias; h = rmsnorm(h, ffn_gamma)
@@ -798,39 +937,30 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
         }
         return LLMIE_OK;
     }
+    int unfused() const;
+};
 
-    if (dec->page_table) {
-        set_error("decoder_forward_paged: the paged KV cache needs the fused decode paths (fp16 engines, batch <= 128)");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (kv8) {
-        set_error("decoder_forward: the fp8 KV cache needs the fused decode paths (batch <= 128, fp16/int8/int4/fp8 weights with "
-                  "H and I multiples of 256 at batch > 8)");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
+// ---- the reference's launch sequence (self_decoder.cpp:69-119), one kernel per step; RoPE inside the attention launch where its
+// geometry allows ----
+int DecodeStep::unfused() const {
+    int rc;
+    const bool fused_rope = fused_attention_geometry(c);
     for (int l = 0; l < c.num_layers; ++l) {
         const llmie_layer_weights &w = dec->layers[l];
         // self_decoder.cpp:77  resid = h ; h = rmsnorm(h)
         TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, dec->resid, w.attn_norm_gamma, c.rms_eps, batch, H, dt, stream));
         // self_attention.cpp:79  qkv = h . Wqkv^T   (bias is applied inside the MHA kernel, as the reference)
         TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, h, w.qkv, dec->qkv, batch, H, QKV, false, nullptr, false, stream));
-        if (hs_ok && rep_ok) {
+        if (fused_rope) {
             // :100-:108 RoPE at position step-1 + fused masked MHA with KV append, one launch (+ merge)
-            TIMED(LLMIE_OP_MHA, decoder_mha_rope(dec->qkv, w.qkv.bias, k_cache, v_cache, dec->mha, l, batch, c.head_num,
-                                                 c.kv_head_num, c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws,
-                                                 dec->attn_ws_bytes, dec->rope_table, c.rotary_dim, nullptr, dt,
-                                                 as_stream(stream), nullptr, nullptr, 0, 1.f, 1.f, nullptr, 0, 0, dec->ragged));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
         } else {
-            if (dec->ragged) {
-                set_error("decoder_forward_ragged: needs head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}");
-                return LLMIE_ERR_UNSUPPORTED;
-            }
             // :100 RoPE at position step-1
-            TIMED(LLMIE_OP_ROPE, llmie_rope_decode(dec->qkv, batch, c.head_num, c.kv_head_num, c.head_size, step, step_dev,
+            TIMED(LLMIE_OP_ROPE, llmie_rope_decode(dec->qkv, batch, c.head_num, c.kv_head_num, c.head_size, pos.step, pos.step_dev,
                                                    c.rotary_dim, c.rotary_base, dt, stream));
             // :108 fused masked MHA with KV append
-            TIMED(LLMIE_OP_MHA, llmie_decoder_mha(dec->qkv, w.qkv.bias, k_cache, v_cache, dec->mha, l, batch, c.head_num,
-                                                  c.kv_head_num, c.head_size, c.max_seq_len, step, step_dev, dec->attn_ws,
+            TIMED(LLMIE_OP_MHA, llmie_decoder_mha(dec->qkv, w.qkv.bias, kv.k, kv.v, dec->mha, l, batch, c.head_num,
+                                                  c.kv_head_num, c.head_size, c.max_seq_len, pos.step, pos.step_dev, dec->attn_ws,
                                                   dec->attn_ws_bytes, dt, stream));
         }
         // :131 output projection (no bias here: the fused norm below adds o.bias, self_decoder.cpp:92-98)
@@ -846,42 +976,73 @@ extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, 
     return LLMIE_OK;
 }
 
+// every decode entry point: validate, copy hidden_in, plan, refuse or dispatch
+static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache, void *v_cache,
+                           const int32_t *block_table, int max_pages, int num_pages, int batch, const DecodePos &pos, llmie_stream stream) {
+    LLMIE_REQUIRE(dec && hidden_in && hidden_out && k_cache && v_cache, "decoder_forward: NULL pointer");
+    const llmie_decoder_config &c = dec->cfg;
+    LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "decoder_forward: batch %d outside [1,%d]", batch, c.max_batch);
+    LLMIE_REQUIRE(pos.step_dev || (pos.step >= 1 && pos.step <= c.max_seq_len), "decoder_forward: step %d outside [1,%d]", pos.step,
+                  c.max_seq_len);
+    if (hidden_out != hidden_in) {
+        hipError_t e = hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(batch) * dec->H * dec->esz,
+                                      hipMemcpyDeviceToDevice, as_stream(stream));
+        if (e != hipSuccess) {
+            set_error("decoder_forward: copy failed: %s", hipGetErrorString(e));
+            return LLMIE_ERR_LAUNCH;
+        }
+    }
+    const DecodeCall call{c, batch, block_table != nullptr, pos.ragged != 0, mis16(hidden_out), mis16(dec->layers[0].qkv.data), engine_switches()};
+    const DecodePlan plan = plan_decode(call);
+    const DecodeStep s{dec, c, hidden_out, batch, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), pos, stream, as_stream(stream),
+                       dec->H, dec->QKV, dec->I, c.wfmt == LLMIE_W_F16 ? 16 : (c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0)),
+                       c.wfmt == LLMIE_W_FP8, c.dtype};
+    switch (plan.path) {
+        case DP_GEMV: return s.gemv();
+        case DP_PACKED: return plan.chain_wanted && s.chain_joins() ? s.packed_chain() : s.packed();
+        case DP_SPLITK: return s.splitk();
+        case DP_UNFUSED: return s.unfused();
+        default: return decode_refuse(call, plan);
+    }
+}
+
+extern "C" int llmie_decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache,
+                                     void *v_cache, int batch, int step, const int32_t *step_dev,
+                                     llmie_stream stream) {
+    return decoder_forward(dec, hidden_in, hidden_out, k_cache, v_cache, nullptr, 0, 0, batch, DecodePos{step, step_dev, 0}, stream);
+}
+
 // Ragged batch (continuous batching): ctx_len_dev[b] = context length of sequence b including this step's token.  Every
 // projection is row-wise, so only the attention launch sees the difference (RoPE position, append slot, span per sequence).
 extern "C" int llmie_decoder_forward_ragged(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache,
                                             void *v_cache, int batch, const int32_t *ctx_len_dev, llmie_stream stream) {
     LLMIE_REQUIRE(dec && ctx_len_dev, "decoder_forward_ragged: NULL pointer");
-    dec->ragged = 1;
-    const int rc = llmie_decoder_forward(dec, hidden_in, hidden_out, k_cache, v_cache, batch, -1, ctx_len_dev, stream);
-    dec->ragged = 0;
-    return rc;
+    return decoder_forward(dec, hidden_in, hidden_out, k_cache, v_cache, nullptr, 0, 0, batch, DecodePos{-1, ctx_len_dev, 1}, stream);
+}
+
+static int paged_args_ok(const llmie_decoder *dec, const int32_t *block_table, int max_pages, int num_pages, const char *who) {
+    LLMIE_REQUIRE(dec && block_table, "%s: NULL pointer", who);
+    LLMIE_REQUIRE(max_pages > 0 && num_pages > 0 &&
+                      static_cast<long long>(max_pages) * LLMIE_KV_PAGE_TOKENS >= dec->cfg.max_seq_len,
+                  "%s: max_pages * %d must cover max_seq_len %d", who, LLMIE_KV_PAGE_TOKENS, dec->cfg.max_seq_len);
+    return LLMIE_OK;
 }
 
 extern "C" int llmie_decoder_forward_paged_ragged(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_pool,
                                                   void *v_pool, const int32_t *block_table, int max_pages, int num_pages, int batch,
                                                   const int32_t *ctx_len_dev, llmie_stream stream) {
     LLMIE_REQUIRE(dec && ctx_len_dev, "decoder_forward_paged_ragged: NULL pointer");
-    dec->ragged = 1;
-    const int rc = llmie_decoder_forward_paged(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, batch,
-                                               -1, ctx_len_dev, stream);
-    dec->ragged = 0;
-    return rc;
+    if (int rc = paged_args_ok(dec, block_table, max_pages, num_pages, "decoder_forward_paged")) return rc;
+    return decoder_forward(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, batch, DecodePos{-1, ctx_len_dev, 1},
+                           stream);
 }
 
 extern "C" int llmie_decoder_forward_paged(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_pool, void *v_pool,
                                            const int32_t *block_table, int max_pages, int num_pages, int batch, int step,
                                            const int32_t *step_dev, llmie_stream stream) {
-    LLMIE_REQUIRE(dec && block_table, "decoder_forward_paged: NULL pointer");
-    LLMIE_REQUIRE(max_pages > 0 && num_pages > 0 &&
-                      static_cast<long long>(max_pages) * LLMIE_KV_PAGE_TOKENS >= dec->cfg.max_seq_len,
-                  "decoder_forward_paged: max_pages * %d must cover max_seq_len %d", LLMIE_KV_PAGE_TOKENS, dec->cfg.max_seq_len);
-    dec->page_table = block_table;
-    dec->max_pages = max_pages;
-    dec->num_pages = num_pages;
-    const int rc = llmie_decoder_forward(dec, hidden_in, hidden_out, k_pool, v_pool, batch, step, step_dev, stream);
-    dec->page_table = nullptr;
-    dec->max_pages = dec->num_pages = 0;
-    return rc;
+    if (int rc = paged_args_ok(dec, block_table, max_pages, num_pages, "decoder_forward_paged")) return rc;
+    return decoder_forward(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, batch, DecodePos{step, step_dev, 0},
+                           stream);
 }
 
 // slabs of a prefill pass: the engine format's plans up to 192 rows, and -- beyond, where fp16 engines and the fp16 weight images of
@@ -898,20 +1059,25 @@ static size_t prefill_slab_floats(const llmie_decoder_config *c, int T) {
     }
     return m;
 }
-static size_t prefill_carve(const llmie_decoder_config *c, int T, int B, size_t *o /*[11]*/) {
+// the prefill workspace: offsets of its areas, in carve order
+struct PrefillCarve {
+    size_t resid, qkv, attn, gu, act, pad, cum, fp8_ws, slabs, deq, tokens, total;
+};
+static PrefillCarve prefill_carve(const llmie_decoder_config *c, int T, int B) {
     const size_t e = 2, H = static_cast<size_t>(c->head_num) * c->head_size;
     const size_t QKV = static_cast<size_t>(c->head_num + 2 * c->kv_head_num) * c->head_size, I = c->inter_size;
     Carve k;
-    o[0] = k.take(static_cast<size_t>(T) * H * e);        // residual
-    o[1] = k.take(static_cast<size_t>(T) * QKV * e);      // packed qkv
-    o[2] = k.take(static_cast<size_t>(T) * H * e);        // attention output
-    o[3] = k.take(static_cast<size_t>(T) * 2 * I * e);    // gate_up
-    o[4] = k.take(static_cast<size_t>(T) * I * e);        // act
-    o[5] = k.take(static_cast<size_t>(T) * sizeof(int32_t));        // padding offsets (by-product of the prefix kernel)
-    o[6] = k.take(static_cast<size_t>(B + 1) * sizeof(int32_t));    // cum_seqlens
+    PrefillCarve o;
+    o.resid = k.take(static_cast<size_t>(T) * H * e);
+    o.qkv = k.take(static_cast<size_t>(T) * QKV * e);      // packed qkv
+    o.attn = k.take(static_cast<size_t>(T) * H * e);       // attention output
+    o.gu = k.take(static_cast<size_t>(T) * 2 * I * e);
+    o.act = k.take(static_cast<size_t>(T) * I * e);
+    o.pad = k.take(static_cast<size_t>(T) * sizeof(int32_t));        // padding offsets (by-product of the prefix kernel)
+    o.cum = k.take(static_cast<size_t>(B + 1) * sizeof(int32_t));    // cum_seqlens
     // fp8 engines: per-token e4m3 image + scales of the activation matrix entering each projection
-    o[7] = k.take(c->wfmt == LLMIE_W_FP8 ? llmie_linear_fp8_workspace_bytes(T, static_cast<int>(I > H ? I : H), 0) : 256);
-    o[8] = k.take(prefill_slab_floats(c, T) * sizeof(float) + 256);   // split-K slabs (short prefills; fp8 passes; mid-size fp16 passes)
+    o.fp8_ws = k.take(c->wfmt == LLMIE_W_FP8 ? llmie_linear_fp8_workspace_bytes(T, static_cast<int>(I > H ? I : H), 0) : 256);
+    o.slabs = k.take(prefill_slab_floats(c, T) * sizeof(float) + 256);   // split-K slabs (short prefills; fp8 passes; mid-size fp16 passes)
     // int8 / int4 / packed-only engines: room for the fp16 image of the largest matrix, at every T -- at least the image_bytes of any
     // plan (plan_linear_wq's image routes; packed-only engines unpack every matrix), and more where the plan needs none: kept
     size_t dq = 0;
@@ -922,62 +1088,41 @@ static size_t prefill_carve(const llmie_decoder_config *c, int T, int B, size_t 
             dq = b > dq ? b : dq;
         }
     }
-    o[9] = k.take(dq + 256);
-    o[10] = k.take(static_cast<size_t>(T) * 2 * sizeof(int32_t) + 256);   // (sequence, cache position) of every packed token + QkvRopeArgs
-    return k.off;
+    o.deq = k.take(dq + 256);
+    o.tokens = k.take(static_cast<size_t>(T) * 2 * sizeof(int32_t) + 256);   // QkvRopeArgs, then (sequence, cache position) of every packed token
+    o.total = k.off;
+    return o;
 }
 
 extern "C" size_t llmie_decoder_prefill_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int max_batch) {
     if (!config_ok(cfg) || max_tokens <= 0 || max_batch <= 0) return 0;
-    size_t o[11];
-    return prefill_carve(cfg, max_tokens, max_batch, o);
+    return prefill_carve(cfg, max_tokens, max_batch).total;
 }
 
-extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache,
-                                     void *v_cache, const int32_t *input_lengths, const int32_t *history_lengths,
-                                     int batch, int num_tokens, int max_q_len, void *workspace, size_t workspace_bytes,
-                                     llmie_stream stream) {
-    LLMIE_REQUIRE(dec && hidden_in && hidden_out && k_cache && v_cache && input_lengths && history_lengths && workspace,
-                  "decoder_prefill: NULL pointer");
-    const llmie_decoder_config &c = dec->cfg;
-    LLMIE_REQUIRE(batch >= 1 && num_tokens >= 1 && max_q_len >= 1 && max_q_len <= num_tokens && max_q_len <= c.max_seq_len,
-                  "decoder_prefill: bad shape batch=%d tokens=%d max_q_len=%d", batch, num_tokens, max_q_len);
-    LLMIE_REQUIRE(num_tokens <= static_cast<long long>(batch) * max_q_len, "decoder_prefill: num_tokens > batch*max_q_len");
-    const bool fp8 = c.wfmt == LLMIE_W_FP8;
-    // weight-only int8 / int4 (round 3): the same layer sequence on the quantised matrices -- the projections de-quantise inside
-    // the GEMM (int8: gemm8p.cuh WQ form) or through an fp16 image of one matrix at a time (int4; quant_linear.hip)
-    const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
-    if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits) || c.head_size != 128)
-        LLMIE_UNSUPPORTED("decoder_prefill: fp16 activations + fp16 / int8 / int4 / fp8 weights + head_size 128 only (use the per-kernel path)");
-    size_t o[11];
-    const size_t need = prefill_carve(&c, num_tokens, batch, o);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
-        set_error("decoder_prefill: workspace too small or unaligned (%zu < %zu)", workspace_bytes, need);
-        return LLMIE_ERR_WORKSPACE;
-    }
-    char *base = static_cast<char *>(workspace);
-    half_t *resid = (half_t *)(base + o[0]), *qkv = (half_t *)(base + o[1]), *attn = (half_t *)(base + o[2]);
-    half_t *gu = (half_t *)(base + o[3]), *act = (half_t *)(base + o[4]);
-    int32_t *pad = (int32_t *)(base + o[5]), *cum = (int32_t *)(base + o[6]);
-    const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
-    hipStream_t st = as_stream(stream);
-    int rc;
-    if (hidden_out != hidden_in) {
-        if (hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(T) * H * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            set_error("decoder_prefill: copy failed");
-            return LLMIE_ERR_LAUNCH;
-        }
-    }
-    half_t *h = (half_t *)hidden_out;
-    void *f8ws = base + o[7];
-    const size_t f8ws_bytes = fp8 ? llmie_linear_fp8_workspace_bytes(T, I > H ? I : H, 0) : 0;
-    const SlabWs slabs{reinterpret_cast<float *>(base + o[8]), prefill_slab_floats(&c, T)};
-    void *deq = base + o[9];
-    const size_t deq_bytes = o[10] - o[9];
-    QkvRopeArgs *rope_args = (QkvRopeArgs *)(base + o[10]);   // (device copy of the fused QKV epilogue's operands)
-    int32_t *tok_b = (int32_t *)(base + o[10] + 256), *tok_tpos = tok_b + T;
+// One prefill pass: the call, its workspace areas and the projections every launch sequence shares.  The sequences are members, so
+// their bodies name the call's parts like locals.
+struct PrefillPass {
+    llmie_decoder *dec;
+    const llmie_decoder_config &c;
+    llmie_stream stream;
+    hipStream_t st;
+    KvView kv;
+    const int32_t *cum, *history_lengths;
+    int batch, T, max_q_len, H, QKV, I;
+    bool fp8;
+    int wqbits;   // weight-only int8 / int4: the same layer sequence on the quantised matrices -- the projections de-quantise inside
+                  // the GEMM (int8: gemm8p.cuh WQ form) or through an fp16 image of one matrix at a time (int4; quant_linear.hip)
+    half_t *h, *resid, *qkv, *attn, *gu, *act;
+    void *f8ws;
+    size_t f8ws_bytes;
+    SlabWs slabs;
+    void *deq;
+    size_t deq_bytes;
+    QkvRopeArgs *rope_args;   // (device copy of the fused QKV epilogue's operands)
+    bool rope_fuse_off, rope_fusable;
+
     // y = x . W^T (+ residual) in the engine's weight format (fp8: per-token e4m3 activations, fp8 MFMA)
-    auto proj = [&](const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual) -> int {
+    int proj(const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual) const {
         if (wqbits)
             return linear_wq(wqbits, x, w.data, (const half_t *)w.scale, y, T, K, N, c.int4_group, EPI_NONE_, nullptr, residual, nullptr,
                              nullptr, 0.f, slabs, st, deq, deq_bytes);
@@ -985,12 +1130,13 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             return linear_fp8(x, (const uint8_t *)w.data, (const float *)w.scale, y, T, K, N, nullptr, residual, f8ws, f8ws_bytes,
                               slabs, st);
         return linear_f16_nk(x, (const half_t *)w.data, y, T, K, N, EPI_NONE_, nullptr, residual, slabs, st);
-    };
+    }
     // act = swiglu(x . Wgu^T) of fp16 / int8 / int4 engines (ffn.cpp:105-122): fused into the projection's epilogue where the plan has
     // a form, else projection + llmie_silu_and_mul (e.g. fp16 H < 512 at 65-192 rows, int8 H % 256 != 0 at 9-191 rows, weights at
     // offsets the vector kernels do not take).  Quantised weights at prefill-sized T fuse only where the 256-row SwiGLU grid fills
     // the chip: the split-K and row-chunk forms the plan has left there cost more than the two launches.
-    auto gate_up = [&](const half_t *x, const llmie_matrix &w) -> int {
+    int gate_up(const half_t *x, const llmie_matrix &w) const {
+        int rc;
         const LinearCall gc = linear_call(wqbits ? wqbits : 16, T, H, 2 * I, EPI_SWIGLU_, c.int4_group, x, w.data, w.scale, act, nullptr, nullptr,
                                           nullptr, nullptr, slabs, wqbits ? deq : nullptr, deq_bytes);
         if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && plan_linear_wq(gc).route != LR_REFUSED) {
@@ -1003,43 +1149,14 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
         }
         return LLMIE_OK;
-    };
-    // context_decoder.cpp:70: exclusive prefix of the lengths (padding offsets are a by-product nobody needs here);
-    // the prefix kernel takes [batch, max_q_len] with max_q_len = ceil(T / batch) rows worth of scratch -> use 1 row of T
-    if ((rc = llmie_cal_padding_offset(pad, cum, input_lengths, batch, (T + batch - 1) / batch, stream))) return rc;
-    // Round 3: RoPE + KV-cache append as the EPILOGUE of the QKV projection (context_attention.cpp:158-205 in one launch sequence;
-    // gemm8p.cuh ROPE forms): q is rotated on its way into the packed QKV buffer, k / v go straight to their cache slots and never
-    // travel through the buffer; bit-identical to projection + prefill_rope_append_kernel (same arithmetic on the fp16-rounded
-    // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.
-    static const bool rope_fuse_off = getenv("LLMIE_NO_QKV_ROPE_FUSION") != nullptr;
-    const bool kv8 = c.kv_fmt == LLMIE_KV_FP8;
-    const float ksc = (kv8 && c.k_scale > 0.f) ? c.k_scale : 1.f, vsc = (kv8 && c.v_scale > 0.f) ? c.v_scale : 1.f;
-    bool rope_fusable = !rope_fuse_off && T >= kWqPrefillRows && gemm256_fills(T, QKV);
-    if (rope_fusable) {
-        QkvRopeArgs ra{};
-        ra.k_cache = k_cache;
-        ra.v_cache = v_cache;
-        ra.rope = dec->rope_table;
-        ra.table = dec->page_table;
-        ra.layer_stride = dec->page_table ? static_cast<size_t>(dec->num_pages) * c.kv_head_num * 128 * c.head_size
-                                          : static_cast<size_t>(batch) * c.kv_head_num * c.max_seq_len * c.head_size;
-        ra.head_num = c.head_num;
-        ra.kv_head_num = c.kv_head_num;
-        ra.max_seq_len = c.max_seq_len;
-        ra.rotary_dim = c.rotary_dim;
-        ra.max_pages = dec->max_pages;
-        ra.kv8 = kv8 ? 1 : 0;
-        ra.k_inv_scale = 1.0f / ksc;
-        ra.v_inv_scale = 1.0f / vsc;
-        if ((rc = prefill_token_table(cum, history_lengths, batch, T, tok_b, tok_tpos, ra, rope_args, st))) return rc;
     }
     // kind: 0 = fp16 operands, 1 = e4m3 operands (xs = token scales), 8 = int8 weights
-    auto qkv_rope = [&](int l, const llmie_matrix &w, int kind, const void *x, const float *xs, const void *Wd, const void *wsc) -> int {
+    int qkv_rope(int l, const llmie_matrix &w, int kind, const void *x, const float *xs, const void *Wd, const void *wsc) const {
         gemm256_qkv_rope_launch(kind, x, Wd, qkv, T, QKV, H, xs, static_cast<const float *>(wsc), static_cast<const half_t *>(w.bias), rope_args, l, st);
         return launch_status("decoder_prefill(qkv + rope + append)");
-    };
+    }
     // the QKV projection of fp16 / int8 / int4 engines; *fused = 1 when its epilogue did RoPE + the cache append
-    auto qkv_proj = [&](int l, const llmie_matrix &w, const half_t *x, int *fused) -> int {
+    int qkv_proj(int l, const llmie_matrix &w, const half_t *x, int *fused) const {
         *fused = 0;
         if (rope_fusable && !fp8 && reinterpret_cast<uintptr_t>(w.bias) % 8 == 0) {
             if (!wqbits && gemm256_qkv_rope_eligible(0, T, QKV, H, x, w.data, nullptr, qkv)) {
@@ -1063,21 +1180,15 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             }
         }
         return proj(x, w, qkv, H, QKV, nullptr);
-    };
-    auto attention = [&](int l, const llmie_matrix &wqkv, int fused) -> int {
-        return prefill_attention_f16(qkv, (const half_t *)wqkv.bias, k_cache, v_cache, attn, cum, history_lengths, dec->rope_table, l, batch, T,
-                                     max_q_len, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, c.rotary_dim, st, kv8, ksc, vsc,
-                                     dec->page_table, dec->max_pages, dec->num_pages, fused);
-    };
-    // Short prefills (<= 128 tokens, fp16 weights) are weight-stream bound like a decode batch: same launch fusion as the batch
-    // decode path -- every projection leaves split-K slabs, the O and down slabs are consumed by the row kernel (reduction +
-    // residual stream + the next RMSNorm), the gate/up slabs by the SwiGLU finalize: 9 launches per layer instead of 13.
-    if (dec->packed_only) {
+    }
+    int attention(int l, const llmie_matrix &wqkv, int fused) const {
+        return prefill_attention_f16(qkv, (const half_t *)wqkv.bias, kv, attn, cum, history_lengths, dec->rope_table, l, batch, T,
+                                     max_q_len, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, c.rotary_dim, st, fused);
+    }
+    int packed_only() const {
+        int rc;
         // LLMIE_DEC_PACKED_ONLY: the row-major matrices are gone -- every projection unpacks its tile-packed image (scales applied,
         // one fp16 rounding per weight: the numerics of the int4 prefill) into the workspace and runs the fp16 GEMM on it
-        if (fp8) LLMIE_UNSUPPORTED("decoder_prefill: LLMIE_DEC_PACKED_ONLY engines prefill fp16 / int8 / int4 weights only");
-        const size_t img_need = static_cast<size_t>(H > QKV ? H : QKV) * (I > H ? I : H);   // (an upper bound is carved: 2 I x H)
-        (void)img_need;
         auto pproj = [&](const void *img, const void *scale, int swiglu_img, const half_t *x, half_t *y, int K, int N, int epi,
                          const half_t *residual) -> int {
             if (deq_bytes < static_cast<size_t>(N) * K * sizeof(half_t)) {
@@ -1117,22 +1228,12 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
         }
         return LLMIE_OK;
     }
-    static const bool short_off = getenv("LLMIE_NO_FUSED_SHORT_PREFILL") != nullptr;
-    const int sbits = wqbits ? wqbits : 16;   // split-K kernels' weight-format code
-    const bool short_fmt_ok = !fp8 && (wqbits != 4 || (c.int4_group == 128 && T <= 64));   // int4 split-K form: 64 rows, group 128
-    // the split-K kernels read the weights, the out-of-place norms hidden_out and the gammas in 16-byte vectors: weights handed over
-    // as views at other offsets (llmie_decoder_create takes any address) run the general sequences below
-    auto a16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    bool w_a16 = true, g_a16 = a16(h);
-    for (int l = 0; l < c.num_layers; ++l) {
-        const llmie_layer_weights &w = dec->layers[l];
-        w_a16 = w_a16 && a16(w.qkv.data) && a16(w.o.data) && a16(w.gate_up.data) && a16(w.down.data);
-        if (wqbits == 4)
-            w_a16 = w_a16 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
-                              reinterpret_cast<uintptr_t>(w.gate_up.scale) | reinterpret_cast<uintptr_t>(w.down.scale)) % 4 == 0;
-        g_a16 = g_a16 && a16(w.attn_norm_gamma) && a16(w.ffn_norm_gamma);
-    }
-    if (!short_off && short_fmt_ok && w_a16 && T <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H)) {
+    // Short prefills (<= 128 tokens, fp16 weights) are weight-stream bound like a decode batch: same launch fusion as the batch
+    // decode path -- every projection leaves split-K slabs, the O and down slabs are consumed by the row kernel (reduction +
+    // residual stream + the next RMSNorm), the gate/up slabs by the SwiGLU finalize: 9 launches per layer instead of 13.
+    int short_splitk() const {
+        int rc;
+        const int sbits = wqbits ? wqbits : 16;   // split-K kernels' weight-format code
         // int8: row scales applied by the slab consumers; int4: group scales applied inside the split-K kernel
         auto sc_of = [&](const llmie_matrix &m) { return SlabScale{wqbits == 8 ? static_cast<const half_t *>(m.scale) : nullptr, nullptr, nullptr}; };
         auto gs_of = [&](const llmie_matrix &m) { return wqbits == 4 ? static_cast<const half_t *>(m.scale) : nullptr; };
@@ -1145,9 +1246,8 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
             // (the slab consumer of the QKV projection does RoPE + the cache append as well: one launch less per layer)
             const bool qfuse = !rope_fuse_off && splitk_finalize_qkv_rope_eligible(sk, c.head_size, qkv, w.qkv.bias);
             if (qfuse) {
-                TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize_qkv_rope(sk, sc_of(w.qkv), qkv, (const half_t *)w.qkv.bias, k_cache, v_cache, cum, history_lengths,
-                                                                  dec->rope_table, l, batch, c.head_num, c.kv_head_num, c.max_seq_len, c.rotary_dim, st,
-                                                                  kv8, ksc, vsc, dec->page_table, dec->max_pages, dec->num_pages));
+                TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize_qkv_rope(sk, sc_of(w.qkv), qkv, (const half_t *)w.qkv.bias, kv, cum, history_lengths,
+                                                                  dec->rope_table, l, batch, c.head_num, c.kv_head_num, c.max_seq_len, c.rotary_dim, st));
             } else {
                 TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize(sk, sc_of(w.qkv), qkv, EPI_NONE_, nullptr, nullptr, st));
             }
@@ -1166,14 +1266,6 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
         }
         return LLMIE_OK;
     }
-    // fp8, prefill-sized: the two RMSNorms emit the e4m3 activations of the projection behind them (norm.hip
-    // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are
-    const bool nq = fp8 && T > 8 && H % 128 == 0 && rmsnorm_quant_eligible(H);
-    uint8_t *xqn = static_cast<uint8_t *>(f8ws);
-    float *xsn = reinterpret_cast<float *>(xqn + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255)));
-    auto tiled_fp8 = [&](const llmie_matrix &w, int N) {
-        return nq && gemm256_fills(T, N) && N % 4 == 0 && (reinterpret_cast<uintptr_t>(w.data) | reinterpret_cast<uintptr_t>(w.scale)) % 16 == 0;
-    };
     // Round 3, fp16 / int8 / int4 weights without an output-projection bias (Llama): the residual stream S lives un-normalised in
     // `h` for the whole pass -- the O and down projections add into it in their epilogues (y = S, residual = S: every element is read
     // and written by the same lane) and the two norms are out-of-place reads of S into `resid` (used as the projections' input N):
@@ -1182,9 +1274,8 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
     // moves 2 x |S| bytes instead of 3-4 x (context_decoder.cpp:70-199 order).
     // (interleaved A/B on one box, fp16: 1 x 2048 78.15k -> 78.55k tok/s, 8 x 512 89.56k -> 89.87k: the norms drop 13.5 + 15.0 ->
     // 9.7 + 9.7 us per layer, the O projection's residual epilogue costs 6.3 us of that back)
-    bool lean = !fp8 && g_a16 && rmsnorm_oop_eligible(H);
-    for (int l = 0; l < c.num_layers && lean; ++l) lean = dec->layers[l].o.bias == nullptr;
-    if (lean) {
+    int lean() const {
+        int rc;
         half_t *S = h, *Nn = resid;
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
@@ -1199,6 +1290,20 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
         }
         return LLMIE_OK;
     }
+    int general() const;
+};
+
+// ---- the general sequence (context_decoder.cpp:70-199): every format, any alignment, an output-projection bias ----
+int PrefillPass::general() const {
+    int rc;
+    // fp8, prefill-sized: the two RMSNorms emit the e4m3 activations of the projection behind them (norm.hip
+    // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are
+    const bool nq = fp8 && T > 8 && H % 128 == 0 && rmsnorm_quant_eligible(H);
+    uint8_t *xqn = static_cast<uint8_t *>(f8ws);
+    float *xsn = reinterpret_cast<float *>(xqn + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255)));
+    auto tiled_fp8 = [&](const llmie_matrix &w, int N) {
+        return nq && gemm256_fills(T, N) && N % 4 == 0 && (reinterpret_cast<uintptr_t>(w.data) | reinterpret_cast<uintptr_t>(w.scale)) % 16 == 0;
+    };
     for (int l = 0; l < c.num_layers; ++l) {
         const llmie_layer_weights &w = dec->layers[l];
         int fused = 0;
@@ -1244,22 +1349,101 @@ extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, 
     return LLMIE_OK;
 }
 
+// both prefill entry points: validate, plan, refuse or: carve the workspace, copy hidden_in, set up what the sequences share, dispatch
+static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache, void *v_cache,
+                           const int32_t *block_table, int max_pages, int num_pages, const int32_t *input_lengths,
+                           const int32_t *history_lengths, int batch, int num_tokens, int max_q_len, void *workspace,
+                           size_t workspace_bytes, llmie_stream stream) {
+    LLMIE_REQUIRE(dec && hidden_in && hidden_out && k_cache && v_cache && input_lengths && history_lengths && workspace,
+                  "decoder_prefill: NULL pointer");
+    const llmie_decoder_config &c = dec->cfg;
+    LLMIE_REQUIRE(batch >= 1 && num_tokens >= 1 && max_q_len >= 1 && max_q_len <= num_tokens && max_q_len <= c.max_seq_len,
+                  "decoder_prefill: bad shape batch=%d tokens=%d max_q_len=%d", batch, num_tokens, max_q_len);
+    LLMIE_REQUIRE(num_tokens <= static_cast<long long>(batch) * max_q_len, "decoder_prefill: num_tokens > batch*max_q_len");
+    const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
+    const EngineSwitches &sw = engine_switches();
+    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw};
+    for (const llmie_layer_weights &w : dec->layers) {
+        call.weights_a16 = call.weights_a16 && (mis16(w.qkv.data) | mis16(w.o.data) | mis16(w.gate_up.data) | mis16(w.down.data)) == 0;
+        call.int4_scales_a4 = call.int4_scales_a4 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
+                                                      reinterpret_cast<uintptr_t>(w.gate_up.scale) | reinterpret_cast<uintptr_t>(w.down.scale)) % 4 == 0;
+        call.hidden_gammas_a16 = call.hidden_gammas_a16 && (mis16(w.attn_norm_gamma) | mis16(w.ffn_norm_gamma)) == 0;
+        call.o_bias = call.o_bias || w.o.bias != nullptr;
+    }
+    const PrefillPlan plan = plan_prefill(call);
+    if (plan.path == PP_REFUSED) return prefill_refuse(plan);
+    const PrefillCarve o = prefill_carve(&c, T, batch);
+    if (workspace_bytes < o.total || reinterpret_cast<uintptr_t>(workspace) % 256) {
+        set_error("decoder_prefill: workspace too small or unaligned (%zu < %zu)", workspace_bytes, o.total);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    if (hidden_out != hidden_in) {
+        if (hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(T) * H * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            set_error("decoder_prefill: copy failed");
+            return LLMIE_ERR_LAUNCH;
+        }
+    }
+    char *base = static_cast<char *>(workspace);
+    const bool fp8 = c.wfmt == LLMIE_W_FP8;
+    int32_t *pad = (int32_t *)(base + o.pad), *cum = (int32_t *)(base + o.cum);
+    int32_t *tok_b = (int32_t *)(base + o.tokens + 256), *tok_tpos = tok_b + T;
+    PrefillPass p{dec, c, stream, st, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), cum, history_lengths, batch, T, max_q_len,
+                  H, QKV, I, fp8, c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0),
+                  (half_t *)hidden_out, (half_t *)(base + o.resid), (half_t *)(base + o.qkv), (half_t *)(base + o.attn), (half_t *)(base + o.gu),
+                  (half_t *)(base + o.act), base + o.fp8_ws, fp8 ? llmie_linear_fp8_workspace_bytes(T, I > H ? I : H, 0) : 0,
+                  SlabWs{reinterpret_cast<float *>(base + o.slabs), prefill_slab_floats(&c, T)}, base + o.deq, o.tokens - o.deq,
+                  (QkvRopeArgs *)(base + o.tokens), sw.no_qkv_rope_fusion, false};
+    int rc;
+    // context_decoder.cpp:70: exclusive prefix of the lengths (padding offsets are a by-product nobody needs here);
+    // the prefix kernel takes [batch, max_q_len] with max_q_len = ceil(T / batch) rows worth of scratch -> use 1 row of T
+    if ((rc = llmie_cal_padding_offset(pad, cum, input_lengths, batch, (T + batch - 1) / batch, stream))) return rc;
+    // Round 3: RoPE + KV-cache append as the EPILOGUE of the QKV projection (context_attention.cpp:158-205 in one launch sequence;
+    // gemm8p.cuh ROPE forms): q is rotated on its way into the packed QKV buffer, k / v go straight to their cache slots and never
+    // travel through the buffer; bit-identical to projection + prefill_rope_append_kernel (same arithmetic on the fp16-rounded
+    // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.
+    p.rope_fusable = !p.rope_fuse_off && T >= kWqPrefillRows && gemm256_fills(T, QKV);
+    if (p.rope_fusable) {
+        QkvRopeArgs ra{};
+        ra.k_cache = p.kv.k;
+        ra.v_cache = p.kv.v;
+        ra.rope = dec->rope_table;
+        ra.table = p.kv.block_table;
+        ra.layer_stride = p.kv.block_table ? static_cast<size_t>(p.kv.num_pages) * c.kv_head_num * 128 * c.head_size
+                                           : static_cast<size_t>(batch) * c.kv_head_num * c.max_seq_len * c.head_size;
+        ra.head_num = c.head_num;
+        ra.kv_head_num = c.kv_head_num;
+        ra.max_seq_len = c.max_seq_len;
+        ra.rotary_dim = c.rotary_dim;
+        ra.max_pages = p.kv.max_pages;
+        ra.kv8 = p.kv.fp8;
+        ra.k_inv_scale = 1.0f / p.kv.k_scale;
+        ra.v_inv_scale = 1.0f / p.kv.v_scale;
+        if ((rc = prefill_token_table(cum, history_lengths, batch, T, tok_b, tok_tpos, ra, p.rope_args, st))) return rc;
+    }
+    switch (plan.path) {
+        case PP_PACKED_ONLY: return p.packed_only();
+        case PP_SHORT_SPLITK: return p.short_splitk();
+        case PP_LEAN: return p.lean();
+        default: return p.general();
+    }
+}
+
+extern "C" int llmie_decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache,
+                                     void *v_cache, const int32_t *input_lengths, const int32_t *history_lengths,
+                                     int batch, int num_tokens, int max_q_len, void *workspace, size_t workspace_bytes,
+                                     llmie_stream stream) {
+    return decoder_prefill(dec, hidden_in, hidden_out, k_cache, v_cache, nullptr, 0, 0, input_lengths, history_lengths, batch, num_tokens,
+                           max_q_len, workspace, workspace_bytes, stream);
+}
+
 extern "C" int llmie_decoder_prefill_paged(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_pool, void *v_pool,
                                            const int32_t *block_table, int max_pages, int num_pages, const int32_t *input_lengths,
                                            const int32_t *history_lengths, int batch, int num_tokens, int max_q_len,
                                            void *workspace, size_t workspace_bytes, llmie_stream stream) {
-    LLMIE_REQUIRE(dec && block_table, "decoder_prefill_paged: NULL pointer");
-    LLMIE_REQUIRE(max_pages > 0 && num_pages > 0 &&
-                      static_cast<long long>(max_pages) * LLMIE_KV_PAGE_TOKENS >= dec->cfg.max_seq_len,
-                  "decoder_prefill_paged: max_pages * %d must cover max_seq_len %d", LLMIE_KV_PAGE_TOKENS, dec->cfg.max_seq_len);
-    dec->page_table = block_table;
-    dec->max_pages = max_pages;
-    dec->num_pages = num_pages;
-    const int rc = llmie_decoder_prefill(dec, hidden_in, hidden_out, k_pool, v_pool, input_lengths, history_lengths, batch, num_tokens,
-                                         max_q_len, workspace, workspace_bytes, stream);
-    dec->page_table = nullptr;
-    dec->max_pages = dec->num_pages = 0;
-    return rc;
+    if (int rc = paged_args_ok(dec, block_table, max_pages, num_pages, "decoder_prefill_paged")) return rc;
+    return decoder_prefill(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, input_lengths, history_lengths, batch,
+                           num_tokens, max_q_len, workspace, workspace_bytes, stream);
 }
 
 // the sampler operands of llmie_lm_head_sample_params (checked by sample_logits_check)
@@ -1285,7 +1469,7 @@ static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *fin
     LLMIE_REQUIRE(c.vocab_size > 0, "lm_head_sample: vocab_size not set in the decoder config");
     int rc;
     if (lm_fmt == LLMIE_W_F16 && c.dtype == LLMIE_F16 && gemv_f16_eligible(batch, dec->H, hidden, lm_head->data) &&
-        !getenv("LLMIE_NO_FUSED_DECODE")) {
+        !engine_switches().no_fused_decode) {
         // final RMSNorm fused into the LM-head GEMV prologue (hidden itself is left un-normalised)
         TIMED(LLMIE_OP_LM_HEAD, linear_f16_nk_norm((const half_t *)hidden, (const half_t *)lm_head->data, (half_t *)logits, batch,
                                                    dec->H, c.vocab_size, EPI_NONE_, (const half_t *)lm_head->bias, nullptr,

@@ -171,19 +171,32 @@ int pk_chain_add(PkChain *ch, int slot /* 0 = O, 1 = gate/up, 2 = down, 4 = next
 int pk_chain_launch(PkChain *ch, unsigned *sync, unsigned *err, hipStream_t st);
 size_t pk_chain_sync_bytes();
 
+// The KV cache of one call, as every attention / append launch sees it.  Dense: k / v are [L, batch, kvh, max_seq_len, hs] and
+// block_table is null.  Paged: block_table is [batch, max_pages] pool pages of 128 tokens and k / v are the pools
+// [L, num_pages, kvh, 128, hs].  fp8: the caches are e4m3 bytes, stored = e4m3(x / scale) (the scales are 1 otherwise).
+struct KvView {
+    void *k, *v;
+    const int32_t *block_table;
+    int max_pages, num_pages;
+    int fp8;
+    float k_scale, v_scale;
+};
+inline KvView kv_dense(void *k, void *v) { return KvView{k, v, nullptr, 0, 0, 0, 1.f, 1.f}; }
+// The position of a decode step: `step` on the host or *step_dev; ragged: step_dev is an array, step_dev[b] = context length of
+// sequence b including this token
+struct DecodePos {
+    int step;
+    const int32_t *step_dev;
+    int ragged;
+};
 // decode attention with optional RoPE (rope may be null) fused in front (rope = [max_pos][head_size/2] (cos,sin) table); attention_decode.hip
-int decoder_mha_rope(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer, int batch,
-                     int head_num, int kv_head_num, int head_size, int max_seq_len, int step, const int32_t *step_dev,
+int decoder_mha_rope(const void *qkv, const void *qkv_bias, const KvView &kv, void *out, int layer, int batch,
+                     int head_num, int kv_head_num, int head_size, int max_seq_len, const DecodePos &pos,
                      void *workspace, size_t workspace_bytes, const float2 *rope, int rot_dim,
                      int32_t *tickets /* [batch,kvh] zeroed arrival counters: in-launch merge; null = merge kernel */,
                      llmie_dtype dtype, hipStream_t st,
                      const SplitKSlabs *qkv_slabs = nullptr /* q/k/v read from the QKV projection's split-K slabs (qkv unused) */,
                      const SlabScale *qkv_scale = nullptr,
-                     int kv_fp8 = 0 /* caches are e4m3 bytes, stored = e4m3(x / scale) */, float k_scale = 1.f, float v_scale = 1.f,
-                     const int32_t *block_table = nullptr /* paged cache: [batch, max_pages] pool pages of 128 tokens; the cache
-                                                             pointers are then pools [L, num_pages, kvh, 128, hs] */,
-                     int max_pages = 0, int num_pages = 0,
-                     int ragged = 0 /* step_dev is an array: step_dev[b] = context length of sequence b incl. this token */,
                      int out_x32 = 0 /* out is the x32 activation image (batch <= 32) instead of row-major [batch, H] */);
 
 // fused tail of a decode step (topk_sampling.hip): round 1 of the top-k alone, and round 2 + sampling (+ the next step's input
@@ -194,19 +207,16 @@ int decode_tail(const int32_t *tmp_ids, const void *tmp_vals, int32_t *ids, void
                 int advance, unsigned *ticket, llmie_dtype dtype, hipStream_t st);
 
 // prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip
-int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, void *k_cache, void *v_cache, half_t *out,
+int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, const KvView &kv, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch,
                           int num_tokens, int max_q_len, int head_num, int kv_head_num, int head_size, int max_seq_len,
-                          int rotary_dim, hipStream_t st, int kv_fp8 = 0 /* caches are e4m3 bytes */, float k_scale = 1.f,
-                          float v_scale = 1.f, const int32_t *block_table = nullptr /* paged cache, see decoder_mha_rope */,
-                          int max_pages = 0, int num_pages = 0,
+                          int rotary_dim, hipStream_t st,
                           int rope_done = 0 /* RoPE + append already done by the QKV projection's epilogue (gemm256_qkv_rope_launch) */);
 // short prefills: slab consumer of the QKV projection with RoPE + KV-cache append folded in (q -> qkv, k / v -> the caches only)
 bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, const void *qkv, const void *bias);
-int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, void *k_cache, void *v_cache,
+int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,
                              const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch, int head_num,
-                             int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, int kv_fp8, float k_scale, float v_scale,
-                             const int32_t *block_table, int max_pages, int num_pages);
+                             int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st);
 // tok_b[t] / tok_tpos[t] = sequence / cache position (history + position) of packed token t: operands of that epilogue
 // (also copies `args` -- whose tok_b / tok_tpos it fills in -- to args_dev)
 int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, int batch, int num_tokens, int32_t *tok_b, int32_t *tok_tpos,

@@ -206,10 +206,13 @@ bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, con
     return head_size == 128 && sk.N % 128 == 0 && reinterpret_cast<uintptr_t>(sk.slab) % 16 == 0 &&
            (reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(bias)) % 8 == 0;
 }
-int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, void *k_cache, void *v_cache,
+int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,
                              const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch, int head_num,
-                             int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, int kv_fp8, float k_scale, float v_scale,
-                             const int32_t *block_table, int max_pages, int num_pages) {
+                             int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st) {
+    void *k_cache = kv.k, *v_cache = kv.v;
+    const int32_t *block_table = kv.block_table;
+    const int max_pages = kv.max_pages, num_pages = kv.num_pages, kv_fp8 = kv.fp8;
+    const float k_scale = kv.k_scale, v_scale = kv.v_scale;
     const size_t layer_off = block_table ? static_cast<size_t>(layer) * num_pages * kv_head_num * 128 * 128
                                          : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * 128;
     const dim3 grid(sk.M, (sk.N / 128 + 15) / 16);
@@ -555,11 +558,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
 }
 
-int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, void *k_cache, void *v_cache, half_t *out,
+int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, const KvView &kv, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch,
                           int num_tokens, int max_q_len, int head_num, int kv_head_num, int head_size, int max_seq_len,
-                          int rotary_dim, hipStream_t st, int kv_fp8, float k_scale, float v_scale, const int32_t *block_table,
-                          int max_pages, int num_pages, int rope_done) {
+                          int rotary_dim, hipStream_t st, int rope_done) {
+    void *k_cache = kv.k, *v_cache = kv.v;
+    const int32_t *block_table = kv.block_table;
+    const int max_pages = kv.max_pages, num_pages = kv.num_pages, kv_fp8 = kv.fp8;
+    const float k_scale = kv.k_scale, v_scale = kv.v_scale;
     if (head_size != 128) {
         set_error("prefill attention: head_size %d not supported by the flash kernel (128 only)", head_size);
         return LLMIE_ERR_UNSUPPORTED;

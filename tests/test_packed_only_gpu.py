@@ -39,11 +39,12 @@ def test_packed_only_engine_runs_without_the_row_major_weights(llmie, wfmt):
     rng = np.random.default_rng(57)
     layers = _layers(llmie, rng, wfmt)
     fmt = dict(f16=llmie.W_F16, int8=llmie.W_INT8, int4=llmie.W_INT4)[wfmt]
-    gemv_max = dict(f16=5, int8=2, int4=2)[wfmt]
     max_seq, maxb = 384, 32
     cfg = dict(head_num=NH, kv_head_num=NH, head_size=HS, inter_size=I, num_layers=L, vocab_size=100, max_seq_len=max_seq, max_batch=maxb,
                rotary_dim=HS, rotary_base=10000.0, rms_eps=1e-5, dtype=llmie.F16, wfmt=fmt, int4_group=128)
     ref = llmie.Decoder(cfg, layers)
+    default_plans_packed = lambda bs: llmie.decoder_plan_name(cfg, False, bs) == "packed"   # (above the GEMV crossover of the format)
+    assert not default_plans_packed(1) and default_plans_packed(17) and default_plans_packed(32)
     # the packed-only engine gets COPIES of the matrices, which are trashed as soon as create has returned
     copies = [{k: (dict(v, data=v["data"].clone()) if isinstance(v, dict) else v) for k, v in lw.items()} for lw in layers]
     po = llmie.Decoder(dict(cfg, flags=llmie.DEC_PACKED_ONLY), copies)
@@ -61,7 +62,7 @@ def test_packed_only_engine_runs_without_the_row_major_weights(llmie, wfmt):
         a = ref.forward(x, torch.empty_like(x), k1, v1, 200)
         b = po.forward(x, torch.empty_like(x), k2, v2, 200)
         assert torch.isfinite(b.float()).all()
-        if bs > gemv_max:
+        if default_plans_packed(bs):
             assert torch.equal(a, b) and torch.equal(k1, k2), "batch %d: packed-only differs from the default engine's packed path" % bs
         else:   # default engine: GEMV kernels; packed-only: MFMA kernels on the image
             d = (a.float() - b.float()).abs()

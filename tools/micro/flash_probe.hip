@@ -41,7 +41,7 @@ int main() {
     for (int rep = 0; rep < 5; ++rep) {
         hipEventRecord(e0);
         // rope_done = 1: the flash kernel alone (the caches are filled above)
-        prefill_attention_f16(qkv, nullptr, kc, vc, out, cum, hist, rope, 0, 1, T, T, nh, nh, hs, max_seq, hs, nullptr, 0, 1.f, 1.f, nullptr, 0, 0, 1);
+        prefill_attention_f16(qkv, nullptr, kv_dense(kc, vc), out, cum, hist, rope, 0, 1, T, T, nh, nh, hs, max_seq, hs, nullptr, 1);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         float ms;
