@@ -138,6 +138,17 @@ const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const voi
                                int K, int N, int swiglu, int group, const void *bias, const void *residual,
                                const void *workspace, size_t workspace_bytes);
 
+/* How the 256-row tiled GEMM family cuts a prefill-sized projection into column tiles, and which kernels run the cuts: the plan the
+ * "tiles256" / "swiglu256" / "g8p" routes, llmie_linear_fp8 / _fp8_swiglu and the prefill's QKV projection launch from.
+ *   form:     0 plain (y[M,N], bias / residual), 1 SwiGLU (N = two_inter, the columns are those of the [M, N/2] output, N % 8 == 0),
+ *             2 QKV projection with RoPE + KV-cache append as its epilogue (N % 128 == 0)
+ *   operands: 0 fp16, 1 e4m3 weights and activations, 2 int8 weights under fp16 activations
+ * Answer: the kernel family ("8p" eight-phase, "2s" two-stage where the eight-phase kernels' 32-bit offsets do not fit; named again
+ * in front of a range that changes it), then one WIDTHxTILES@FIRSTCOL per launch: "8p 256x32@0 128x2@8192".  Any positive shape is
+ * answered, also those whose grid does not fill the chip.  Pure host function; NULL + llmie_last_error() for other arguments.  The
+ * string is valid until the thread's next call. */
+const char *llmie_gemm256_tiles(int form, int operands, int M, int N, int K);
+
 /* replaces launchLinearStridedBatchGemm src/kernels/linear.cu:89-158 (+ cublas_utils.cpp:95-154)
  * per batch i: C_i[m,n] = A_i[m,k] . B_i  (B_i is [n,k] if trans_b else [k,n]); dense strides */
 int llmie_batched_gemm(const void *a, const void *b, void *c, int batch, int m, int n, int k,

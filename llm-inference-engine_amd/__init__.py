@@ -51,6 +51,7 @@ _SIGS = {
     "llmie_linear": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp],
     "llmie_linear_swiglu": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp],
     "llmie_linear_route": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz],
+    "llmie_gemm256_tiles": [_i, _i, _i, _i, _i],
     "llmie_batched_gemm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "llmie_qkv_bias_transpose_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     "llmie_rope_decode": [_vp, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _vp],
@@ -128,6 +129,7 @@ _RESTYPES = {
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
     "llmie_linear_route": C.c_char_p,
+    "llmie_gemm256_tiles": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
 }
@@ -225,6 +227,17 @@ def linear_route(fmt, x, w, scale, y, M, K, N, swiglu=False, group=0, bias=None,
     """name of the kernel route the projection entry points plan for this call, None where they refuse it (llmie_last_error() says
     why).  The operands are ADDRESSES (ints, never dereferenced: only their alignment counts) -- no device needed."""
     r = lib().llmie_linear_route(fmt, x, w, scale, y, M, K, N, int(swiglu), group, bias, residual, workspace, workspace_bytes)
+    return r.decode() if r is not None else None
+
+
+G256_FORMS = {"plain": 0, "swiglu": 1, "qkv_rope": 2}
+G256_OPERANDS = {"f16": 0, "e4m3": 1, "int8": 2}
+
+
+def gemm256_tiles(form, operands, M, N, K):
+    """tile plan of the 256-row GEMM family for a projection of the form ("plain", "swiglu": N = two_inter, "qkv_rope") and operand
+    format ("f16", "e4m3", "int8"): e.g. "8p 256x32@0 128x2@8192" (include/llmie.h); None for other arguments.  No device needed."""
+    r = lib().llmie_gemm256_tiles(G256_FORMS[form], G256_OPERANDS[operands], M, N, K)
     return r.decode() if r is not None else None
 
 

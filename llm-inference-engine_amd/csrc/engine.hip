@@ -1150,33 +1150,33 @@ struct PrefillPass {
         }
         return LLMIE_OK;
     }
-    // kind: 0 = fp16 operands, 1 = e4m3 operands (xs = token scales), 8 = int8 weights
-    int qkv_rope(int l, const llmie_matrix &w, int kind, const void *x, const float *xs, const void *Wd, const void *wsc) const {
-        gemm256_qkv_rope_launch(kind, x, Wd, qkv, T, QKV, H, xs, static_cast<const float *>(wsc), static_cast<const half_t *>(w.bias), rope_args, l, st);
+    // xs: token scales of e4m3 operands
+    int qkv_rope(int l, const llmie_matrix &w, G256Operands ops, const void *x, const float *xs, const void *Wd, const void *wsc) const {
+        gemm256_qkv_rope_launch(ops, x, Wd, qkv, T, QKV, H, xs, static_cast<const float *>(wsc), static_cast<const half_t *>(w.bias), rope_args, l, st);
         return launch_status("decoder_prefill(qkv + rope + append)");
     }
     // the QKV projection of fp16 / int8 / int4 engines; *fused = 1 when its epilogue did RoPE + the cache append
     int qkv_proj(int l, const llmie_matrix &w, const half_t *x, int *fused) const {
         *fused = 0;
         if (rope_fusable && !fp8 && reinterpret_cast<uintptr_t>(w.bias) % 8 == 0) {
-            if (!wqbits && gemm256_qkv_rope_eligible(0, T, QKV, H, x, w.data, nullptr, qkv)) {
+            if (!wqbits && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, w.data, nullptr, qkv)) {
                 *fused = 1;
-                return qkv_rope(l, w, 0, x, nullptr, w.data, nullptr);
+                return qkv_rope(l, w, G256_F16, x, nullptr, w.data, nullptr);
             }
             // int8 / int4: the route proj() would take -- the eight-phase int8 form, or (int4, and int8 shapes without the in-kernel
             // form) the fp16 image of the matrix -- with the epilogue on the same kernels
             const int route = !wqbits ? LR_REFUSED
                                       : plan_linear_wq(linear_call(wqbits, T, H, QKV, EPI_NONE_, c.int4_group, x, w.data, w.scale, qkv, nullptr, nullptr,
                                                                    nullptr, nullptr, slabs, deq, deq_bytes)).route;
-            if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(8, T, QKV, H, x, w.data, w.scale, qkv)) {
+            if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(G256_W8, T, QKV, H, x, w.data, w.scale, qkv)) {
                 *fused = 1;
-                return qkv_rope(l, w, 8, x, nullptr, w.data, w.scale);
+                return qkv_rope(l, w, G256_W8, x, nullptr, w.data, w.scale);
             }
-            if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(0, T, QKV, H, x, deq, nullptr, qkv)) {
+            if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, deq, nullptr, qkv)) {
                 int rc2 = dequantize_weights_f16(wqbits, w.data, static_cast<const half_t *>(w.scale), static_cast<half_t *>(deq), QKV, H, c.int4_group, st);
                 if (rc2) return rc2;
                 *fused = 1;
-                return qkv_rope(l, w, 0, x, nullptr, deq, nullptr);
+                return qkv_rope(l, w, G256_F16, x, nullptr, deq, nullptr);
             }
         }
         return proj(x, w, qkv, H, QKV, nullptr);
@@ -1205,11 +1205,11 @@ struct PrefillPass {
             TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, resid, w.attn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
             int fused = 0;
             if (rope_fusable && reinterpret_cast<uintptr_t>(w.qkv.bias) % 8 == 0 && deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) &&
-                gemm256_qkv_rope_eligible(0, T, QKV, H, h, deq, nullptr, qkv)) {
+                gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, h, deq, nullptr, qkv)) {
                 // (the unpacked fp16 image as the operand of the QKV projection with the RoPE + append epilogue)
                 fused = 1;
                 TIMED(LLMIE_OP_QKV_GEMM, pk_unpack_f16(dec->pk_wf, pw.qkv, static_cast<const half_t *>(w.qkv.scale), static_cast<half_t *>(deq), QKV, H, 0, st));
-                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, 0, h, nullptr, deq, nullptr));
+                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, G256_F16, h, nullptr, deq, nullptr));
             } else {
                 TIMED(LLMIE_OP_QKV_GEMM, pproj(pw.qkv, w.qkv.scale, 0, h, qkv, H, QKV, EPI_NONE_, nullptr));
             }
@@ -1310,11 +1310,11 @@ int PrefillPass::general() const {
         if (tiled_fp8(w.qkv, QKV)) {
             TIMED(LLMIE_OP_ATTN_NORM, rmsnorm_quant_f16(h, resid, nullptr, (const half_t *)w.attn_norm_gamma, c.rms_eps, T, H, false, xqn, xsn, st));
             if (rope_fusable && reinterpret_cast<uintptr_t>(w.qkv.bias) % 8 == 0 &&
-                gemm256_qkv_rope_eligible(1, T, QKV, H, xqn, w.qkv.data, w.qkv.scale, qkv)) {
+                gemm256_qkv_rope_eligible(G256_E4M3, T, QKV, H, xqn, w.qkv.data, w.qkv.scale, qkv)) {
                 fused = 1;
-                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, 1, xqn, xsn, w.qkv.data, w.qkv.scale));
+                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, G256_E4M3, xqn, xsn, w.qkv.data, w.qkv.scale));
             } else {
-                TIMED(LLMIE_OP_QKV_GEMM, (gemm256_launch(true, xqn, w.qkv.data, qkv, T, QKV, H, nullptr, nullptr, xsn, (const float *)w.qkv.scale, st),
+                TIMED(LLMIE_OP_QKV_GEMM, (gemm256_launch(G256_E4M3, xqn, w.qkv.data, qkv, T, QKV, H, nullptr, nullptr, xsn, (const float *)w.qkv.scale, st),
                                           launch_status("decoder_prefill(qkv fp8)")));
             }
         } else {
@@ -1327,7 +1327,7 @@ int PrefillPass::general() const {
         if (nq && gu_fused8 && w.ffn_norm_gamma && reinterpret_cast<uintptr_t>(w.gate_up.scale) % 16 == 0) {
             TIMED(LLMIE_OP_FFN_NORM, rmsnorm_quant_f16(h, resid, (const half_t *)w.o.bias, (const half_t *)w.ffn_norm_gamma, c.rms_eps, T, H, true,
                                                        xqn, xsn, st));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, (gemm256_swiglu_launch(true, xqn, w.gate_up.data, act, T, 2 * I, H, xsn, (const float *)w.gate_up.scale, st),
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, (gemm256_swiglu_launch(G256_E4M3, xqn, w.gate_up.data, act, T, 2 * I, H, xsn, (const float *)w.gate_up.scale, st),
                                             launch_status("decoder_prefill(gate_up fp8)")));
             TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
             continue;

@@ -127,9 +127,8 @@ static bool fp8_tiled(const void *w_scale, const void *bias, const void *residua
     // (round 3) a grid that does not fill the chip against split-K passes of 128 rows, by the time model fitted to the sweep
     // (tools/dev/s2_run27.sh; us): O / down of a 7B layer 41 / 90 tiled at any row count, 18.9 / 22.3 per pass -- at 768 tokens
     // the six passes took 113 / 134 us
-    if (M <= 128 || static_cast<size_t>(N + 512) * K >= (size_t{1} << 32)) return false;
-    const int tiles2 = ((M + 255) / 256) * ((N + 127) / 128);
-    const float t_tiles = static_cast<float>((tiles2 + 255) / 256) * (K / 128) * 1.15f;
+    if (M <= 128 || !gemm8p_fits(N, K, 1)) return false;
+    const float t_tiles = static_cast<float>(gemm256_narrow_rounds(M, N)) * (K / 128) * 1.15f;
     const float t_passes = ((M + 127) / 128) * (static_cast<float>(N) * K / 8.3e6f + 17.f);
     return t_tiles < t_passes;
 }
@@ -155,7 +154,7 @@ int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half
     if (rc) return rc;
     if (tiled) {
         // prefill-sized: MFMA-bound tiled GEMM on v_mfma_scale_f32_16x16x128_f8f6f4
-        gemm256_launch(true, xq, w_fp8, y, M, N, K, bias, residual, xscale, w_scale, st);
+        gemm256_launch(G256_E4M3, xq, w_fp8, y, M, N, K, bias, residual, xscale, w_scale, st);
         return launch_status("linear_fp8(gemm256)");
     }
     for (int m0 = 0; m0 < M; m0 += 128) {
@@ -203,7 +202,7 @@ extern "C" int llmie_linear_fp8_swiglu(const void *x, const uint8_t *w_fp8, cons
     float *xscale = reinterpret_cast<float *>(xq + fp8_align(static_cast<size_t>(M) * K));
     const int rc = quantize_rows_fp8((const half_t *)x, xq, xscale, M, K, st);
     if (rc) return rc;
-    gemm256_swiglu_launch(true, xq, w_fp8, (half_t *)y, M, two_inter, K, xscale, w_scale, st);
+    gemm256_swiglu_launch(G256_E4M3, xq, w_fp8, (half_t *)y, M, two_inter, K, xscale, w_scale, st);
     return launch_status("linear_fp8_swiglu");
 }
 

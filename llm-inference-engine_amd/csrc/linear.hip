@@ -5,6 +5,7 @@
 #include "gemm_mid.cuh"
 #include "llmie_internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace llmie {
@@ -599,319 +600,217 @@ int linear_f16_nk_norm(const half_t *x, const half_t *W, half_t *y, int M, int K
     return launch_status("linear(norm-fused)");
 }
 
-// 256 x 256 (or 256 x 128) LDS-DMA GEMM (gemm256.cuh): fp16 operands, or e4m3 operands with per-token / per-row scales.
-// Tile choice by grid fill: 256-wide column tiles when they give >= min_tiles workgroups (one per CU), else 128-wide.
-static int g256_group_m() {
-    constexpr int v = 4;
-    return v;
-}
-static int gemm256_wn(int M, int N) {
-    constexpr int min_tiles = 192, min_tiles_narrow = 128;
-    const int tm = (M + 255) / 256;
-    if (tm * ((N + 255) / 256) >= min_tiles) return 4;
-    // 256 x 128 tiles already from HALF the chip (round 3): at 1024 tokens the O / down projections (N = 4096: 128 tiles) used to
-    // fall to the 128 x 128 kernel -- 80 / 181 us against 58 / 140 us on the eight-phase kernel; 1 x 1024 prefill 57.7k -> 65.5k tok/s
-    if (tm * ((N + 127) / 128) >= min_tiles_narrow) return 2;
-    return 0;
-}
-bool gemm256_fills(int M, int N) { return gemm256_wn(M, N) != 0; }
+// ---- the 256-row tiled GEMM family: gemm8p.cuh (eight-phase; 32-bit DMA offsets) and gemm256.cuh (two-stage, any size); fp16
+// operands, e4m3 operands with per-token / per-row scales, or int8 weights under fp16 activations.  One tile planner (pure host code:
+// no HIP call, no error text), one launcher; llmie_gemm256_tiles reports the plan, tests/test_gemm256_tiles_cpu.py pins it.
+//
+// Tile plan by rounds of the CUs (one 512-thread workgroup per CU): a narrow tile costs ~0.6 of a wide one (measured: 0.96 vs 1.12
+// PFLOP/s on full rounds of 256 x 128 against 256 x 256 tiles).  A half-empty last round of wide tiles (qkv at 2048 tokens: 384
+// tiles = 1.5 rounds) is avoided by running the whole rounds wide and the left-over columns narrow in a second launch, when that is
+// cheaper (SwiGLU at 4096 tokens: 1376 tiles = 5.4 rounds; not at 2048 tokens: 2.7 rounds would become 2 + 2 x 0.6).
+constexpr int kG256Cus = 256;             // workgroups of one round
+constexpr float kG256NarrowCost = 0.6f;   // a narrow tile, in wide tiles
+constexpr int kG256FillWide = 192;        // wide tiles from which a grid fills the chip
+// Narrow tiles that fill it = wide tiles from which the rounds decide: HALF the chip (round 3: at 1024 tokens the O / down projections,
+// N = 4096: 128 tiles, used to fall to the 128 x 128 kernel -- 80 / 181 us against 58 / 140 us; 1 x 1024 prefill 57.7k -> 65.5k tok/s)
+constexpr int kG256FillNarrow = 128;
+static int g256_row_tiles(int M) { return (M + 255) / 256; }
+static int g256_rounds(int tiles) { return (tiles + kG256Cus - 1) / kG256Cus; }
+static int g256_ceil(int n, int w) { return (n + w - 1) / w; }
 
-// eight-phase form of the 256 x 256 tile (gemm8p.cuh): per-lane DMA offsets are 32-bit
-static bool g8p_fits(int N, int K, bool fp8) {
-    return (static_cast<size_t>(N) + 512) * K * (fp8 ? 1 : 2) < (size_t{1} << 32);
-}
-
-template <bool FP8, bool EPI, int WN, int WQ = 0>
-static void gemm256_launch_t(const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias, const half_t *residual,
-                             const float *xscale, const float *wscale, hipStream_t st, int ldc = 0) {
-    constexpr int lds_bytes = 2 * (2 + WN / 2) * 128 * 128;
-    if constexpr (WQ != 0) {   // int8 weights: the eight-phase kernels only (callers check g8p_w8_eligible)
-        const int tmq = (M + 255) / 256, tnq = (N + 64 * WN - 1) / (64 * WN);
-        if constexpr (WN == 4) {
-            static const bool a8 = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<false, EPI, false, WQ>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                return true;
-            }();
-            (void)a8;
-            gemm8p_kernel<false, EPI, false, WQ><<<tmq * tnq, 512, lds_bytes, st>>>(x, W, y, M, N, K, bias, residual, tnq, xscale, wscale, ldc, g256_group_m());
-        } else {
-            constexpr int ring_bytes = 9 * 128 * 128;
-            static const bool a8 = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<false, EPI, false, WQ>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-                return true;
-            }();
-            (void)a8;
-            gemm8p_n128_kernel<false, EPI, false, WQ><<<tmq * tnq, 512, ring_bytes, st>>>(x, W, y, M, N, K, bias, residual, tnq, xscale, wscale, ldc, g256_group_m());
-        }
-        return;
-    }
-    static const bool attr_set = [] {   // once per process, thread-safe (function-local static initialisation)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm256_kernel<FP8, EPI, WN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        return true;
-    }();
-    (void)attr_set;
-    const int tm = (M + 255) / 256, tn = (N + 64 * WN - 1) / (64 * WN);
-    if constexpr (WN == 4) {
-        if (g8p_fits(N, K, FP8)) {
-            static const bool attr8 = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<FP8, EPI, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                return true;
-            }();
-            (void)attr8;
-            gemm8p_kernel<FP8, EPI, false><<<tm * tn, 512, lds_bytes, st>>>(x, W, y, M, N, K, bias, residual, tn, xscale, wscale, ldc, g256_group_m());
-            return;
-        }
-    }
-    if constexpr (WN == 2) {
-        if (g8p_fits(N, K, FP8)) {
-            constexpr int ring_bytes = 9 * 128 * 128;
-            static const bool attr8 = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<FP8, EPI>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-                return true;
-            }();
-            (void)attr8;
-            gemm8p_n128_kernel<FP8, EPI><<<tm * tn, 512, ring_bytes, st>>>(x, W, y, M, N, K, bias, residual, tn, xscale, wscale, ldc, g256_group_m());
-            return;
-        }
-    }
-    gemm256_kernel<FP8, EPI, WN><<<tm * tn, 512, lds_bytes, st>>>(x, W, y, M, N, K, bias, residual, tn, xscale, wscale, ldc, g256_group_m());
+struct G256Rules {
+    int wide, narrow;    // widths of the form's column tiles, in output columns
+    bool whole_tiles;    // the output is a whole number of narrow tiles and no tile straddles its end (else: the last tile is ragged)
+    int align;           // output columns % align == 0 lets the rounds decide and permits a split
+    int gate;            // wide tiles below which the rounds do not decide (the fill gate)
+    bool narrow_alone;   // the form runs all-narrow grids
+    bool tie_narrow;     // all-wide and all-narrow cost the same: narrow (else wide)
+};
+static const G256Rules &g256_rules(G256Form form) {
+    static const G256Rules rules[] = {
+        // plain: 256 / 128 wide; ragged last tile; the epilogue stores 4 columns at a time (768 x 12288 is ONE round of 144 wide tiles
+        // or TWO of 288 narrow ones -- 97 against 119 us: from half the chip on, the rounds decide)
+        {256, 128, false, 4, kG256FillNarrow, true, false},
+        // SwiGLU: 128 / 64 columns of the [M, I] output (256 / 128 weight rows); the 64-wide kernel only takes left-over columns; no gate
+        // (callers come with gemm256_swiglu_fills)
+        {128, 64, false, 4, 0, false, false},
+        // QKV + RoPE: the ROPE forms fetch their weight rows unclamped, in permuted order, so every range is whole tiles: N % 128 == 0
+        // always, all-wide only where N % 256 == 0; starts from all-narrow, so ties stay narrow
+        {256, 128, true, 128, kG256FillNarrow, true, true},
+    };
+    return rules[form];
 }
 
+bool gemm256_fills(int M, int N) {
+    const int tm = g256_row_tiles(M);
+    return tm * g256_ceil(N, 256) >= kG256FillWide || tm * g256_ceil(N, 128) >= kG256FillNarrow;
+}
 // SwiGLU form: W = fused gate_up [2I, K], y = silu(x.Wg^T) * (x.Wu^T) [M, I]
 bool gemm256_swiglu_fills(int M, int two_inter) {
-    constexpr int min_tiles = 192;
-    constexpr bool off = false;
-    return !off && two_inter % 8 == 0 && ((M + 255) / 256) * ((two_inter / 2 + 127) / 128) >= min_tiles;
+    return two_inter % 8 == 0 && g256_row_tiles(M) * g256_ceil(two_inter / 2, 128) >= kG256FillWide;
 }
-void gemm256_swiglu_launch(bool fp8, const void *x, const void *W, half_t *y, int M, int two_inter, int K, const float *xscale,
-                           const float *wscale, hipStream_t st, int wq) {
-    constexpr int lds_bytes = 2 * 4 * 128 * 128;
-    static const bool attr_set = [] {   // once per process, thread-safe (function-local static initialisation)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm256_kernel<false, false, 4, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm256_kernel<true, false, 4, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+int gemm256_narrow_rounds(int M, int N) { return g256_rounds(g256_row_tiles(M) * g256_ceil(N, 128)); }
+bool gemm8p_fits(int N, int K, int elem_bytes) { return (static_cast<size_t>(N) + 512) * K * elem_bytes < (size_t{1} << 32); }
+
+G256Plan plan_gemm256(G256Form form, G256Operands ops, int M, int N, int K) {
+    const G256Rules &r = g256_rules(form);
+    const int cols = form == G256_SWIGLU ? N / 2 : N, tm = g256_row_tiles(M);
+    auto tiles_of = [&](int n, int w) { return r.whole_tiles ? n / w : g256_ceil(n, w); };
+    const int tn_wide = tiles_of(cols, r.wide), tn_narrow = tiles_of(cols, r.narrow);
+    // bytes per element of the fit: int8 weights count 2 like the fp16 activations beside them
+    const int fit_bytes = ops == G256_E4M3 ? 1 : 2;
+    G256Plan p{1, {{true, r.wide, 0, tn_wide}, {}}};
+    // SwiGLU decides the family on the whole matrix, before the ranges: the two-stage kernel has no 64-wide form.  (int8 weights have
+    // no two-stage form at all: plan_linear_wq routes them here only where the offsets fit)
+    if (form == G256_SWIGLU && !gemm8p_fits(N, K, fit_bytes)) {
+        p.range[0].eight_phase = false;
+        return p;
+    }
+    if (cols % r.align != 0 || tm * tn_wide < r.gate) {
+        if (r.narrow_alone && tm * tn_wide < kG256FillWide) p.range[0] = {true, r.narrow, 0, tn_narrow};
+    } else {
+        constexpr float never = 1e30f;
+        const bool wide_ok = !r.whole_tiles || cols % r.wide == 0;
+        const float c_wide = wide_ok ? static_cast<float>(g256_rounds(tm * tn_wide)) : never;
+        const float c_narrow = r.narrow_alone ? g256_rounds(tm * tn_narrow) * kG256NarrowCost : never;
+        const bool narrow = r.tie_narrow ? !(c_wide < c_narrow) : c_narrow < c_wide;
+        if (narrow) p.range[0] = {true, r.narrow, 0, tn_narrow};
+        const int a = (tm * tn_wide / kG256Cus) * kG256Cus / tm;   // wide column tiles that make whole rounds
+        if (a > 0 && a * r.wide < cols) {
+            const int b = tiles_of(cols - a * r.wide, r.narrow);
+            const float c = static_cast<float>(g256_rounds(tm * a)) + g256_rounds(tm * b) * kG256NarrowCost;
+            if (c < (narrow ? c_narrow : c_wide)) p = G256Plan{2, {{true, r.wide, 0, a}, {true, r.narrow, a * r.wide, b}}};
+        }
+    }
+    // plain: each range by its own size (its W pointer is advanced to the range); int8 weights never leave the eight-phase kernels
+    // (plan_linear_wq checks the whole matrix).  QKV + RoPE: gemm256_qkv_rope_eligible checks the whole matrix.
+    if (form == G256_PLAIN && ops != G256_W8)
+        for (int i = 0; i < p.ranges; ++i) {
+            G256Range &g = p.range[i];
+            g.eight_phase = gemm8p_fits(std::min(g.tiles * g.width, N - g.col0), K, fit_bytes);
+        }
+    return p;
+}
+
+// "8p 256x32@0 128x2@8192": family (8p eight-phase, 2s two-stage; again before a range that changes it), then WIDTHxTILES@FIRSTCOL
+static void g256_plan_text(const G256Plan &p, char *buf, size_t size) {
+    size_t len = 0;
+    for (int i = 0; i < p.ranges && len < size; ++i) {
+        const G256Range &g = p.range[i];
+        if (i == 0 || g.eight_phase != p.range[i - 1].eight_phase)
+            len += snprintf(buf + len, size - len, "%s%s", i ? " " : "", g.eight_phase ? "8p" : "2s");
+        if (len < size) len += snprintf(buf + len, size - len, " %dx%d@%d", g.width, g.tiles, g.col0);
+    }
+}
+
+// One launch: the dynamic-LDS attribute is set once per instantiation and process (function-local static initialisation: thread-safe)
+struct G256Args {
+    const void *x, *W;
+    half_t *y;
+    int M, N, K;
+    const half_t *bias, *residual;
+    int tiles_n;
+    const float *xscale, *wscale;
+    int ldc, col0;
+    const QkvRopeArgs *rap;
+    int layer;
+};
+template <auto Kernel, int LDS_BYTES, bool EIGHT_PHASE> static void g256_run(const G256Args &a, int grid, hipStream_t st) {
+    static const bool attr_set = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         return true;
     }();
     (void)attr_set;
-    const int tm = (M + 255) / 256, tn = (two_inter / 2 + 127) / 128;
-    if (g8p_fits(two_inter, K, fp8)) {
-        static const bool attr8 = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<true, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            return true;
-        }();
-        (void)attr8;
-        // Rounds of the 256 CUs, as gemm256_launch plans them: a partly filled last round of 128-column tiles (4096 tokens: 1376 tiles =
-        // 5.4 rounds) runs instead as 64-column tiles (gemm8p_n128_kernel's SwiGLU form, ~0.6 of a wide tile each) over the
-        // left-over columns, in a second launch -- when that is cheaper (not at 2048 tokens: 2.7 rounds become 2 + 2 x 0.6)
-        constexpr int cus = 256, ring_bytes = 9 * 128 * 128;
-        auto rounds = [&](int t) { return (t + cus - 1) / cus; };
-        const int inter = two_inter / 2, tiles = tm * tn, full = tiles / cus;
-        int a_tn = tn, b_tn = 0;
-        if (full >= 1 && tiles % cus != 0 && inter % 4 == 0) {
-            const int a = full * cus / tm;   // 128-column tiles that make whole rounds
-            if (a > 0 && a < tn) {
-                const int tnb = (inter - a * 128 + 63) / 64;
-                if (rounds(a * tm) + rounds(tm * tnb) * 0.6f < static_cast<float>(rounds(tiles))) {
-                    a_tn = a;
-                    b_tn = tnb;
-                }
-            }
-        }
-        if (wq) {   // int8 weights (wscale = their fp16 row scales)
-            static const bool attrq = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<false, false, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<false, false, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-                return true;
-            }();
-            (void)attrq;
-            gemm8p_kernel<false, false, true, 8><<<tm * a_tn, 512, lds_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, a_tn, nullptr, wscale, 0, g256_group_m(), 0);
-            if (b_tn)
-                gemm8p_n128_kernel<false, false, true, 8><<<tm * b_tn, 512, ring_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, b_tn, nullptr, wscale, 0, g256_group_m(), a_tn * 128);
-            return;
-        }
-        if (fp8)
-            gemm8p_kernel<true, false, true><<<tm * a_tn, 512, lds_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, a_tn, xscale, wscale, 0, g256_group_m(), 0);
-        else
-            gemm8p_kernel<false, false, true><<<tm * a_tn, 512, lds_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, a_tn, nullptr, nullptr, 0, g256_group_m(), 0);
-        if (b_tn) {
-            static const bool attrn = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-                return true;
-            }();
-            (void)attrn;
-            if (fp8)
-                gemm8p_n128_kernel<true, false, true><<<tm * b_tn, 512, ring_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, b_tn, xscale, wscale, 0, g256_group_m(), a_tn * 128);
-            else
-                gemm8p_n128_kernel<false, false, true><<<tm * b_tn, 512, ring_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, b_tn, nullptr, nullptr, 0, g256_group_m(), a_tn * 128);
-        }
-        return;
-    }
-    if (fp8)
-        gemm256_kernel<true, false, 4, true><<<tm * tn, 512, lds_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, tn, xscale, wscale, 0, g256_group_m());
+    constexpr int group_m = 4;   // XCD-aware tile order: row tiles per group
+    if constexpr (EIGHT_PHASE)
+        Kernel<<<grid, 512, LDS_BYTES, st>>>(a.x, a.W, a.y, a.M, a.N, a.K, a.bias, a.residual, a.tiles_n, a.xscale, a.wscale, a.ldc, group_m,
+                                             a.col0, a.rap, a.layer);
     else
-        gemm256_kernel<false, false, 4, true><<<tm * tn, 512, lds_bytes, st>>>(x, W, y, M, two_inter, K, nullptr, nullptr, tn, nullptr, nullptr, 0, g256_group_m());
+        Kernel<<<grid, 512, LDS_BYTES, st>>>(a.x, a.W, a.y, a.M, a.N, a.K, a.bias, a.residual, a.tiles_n, a.xscale, a.wscale, a.ldc, group_m);
 }
-
-// One launch over the column range [nb, nb + n) of the [M, N] output with 64*wn-column tiles.
-static void gemm256_range(bool fp8, int wn, const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias,
-                          const half_t *residual, const float *xscale, const float *wscale, hipStream_t st, int nb, int n, int wq = 0) {
-    const bool epi = bias || residual;
-    const void *Wr = static_cast<const unsigned char *>(W) + static_cast<size_t>(nb) * K * ((fp8 || wq) ? 1 : 2);
-    half_t *yr = y + nb;
-    const half_t *br = bias ? bias + nb : nullptr, *rr = residual ? residual + nb : nullptr;
-    // (int8: the scales are fp16, carried through the float pointer of the shared signature)
-    const float *wsr = !wscale ? nullptr : (wq ? reinterpret_cast<const float *>(reinterpret_cast<const half_t *>(wscale) + nb) : wscale + nb);
-    if (wq) {
-        if (wn == 4) {
-            if (epi) gemm256_launch_t<false, true, 4, 8>(x, Wr, yr, M, n, K, br, rr, nullptr, wsr, st, N);
-            else gemm256_launch_t<false, false, 4, 8>(x, Wr, yr, M, n, K, br, rr, nullptr, wsr, st, N);
+// (family, width) -> instantiation, for one form, operand format and epilogue
+template <G256Form FORM, bool FP8, int WQ, bool EPI> static void g256_run_range(const G256Range &g, const G256Args &a, int grid, hipStream_t st) {
+    constexpr bool SWIGLU = FORM == G256_SWIGLU, ROPE = FORM == G256_QKV_ROPE;
+    constexpr int stage_bytes = 2 * 4 * 128 * 128, stage_bytes_narrow = 2 * 3 * 128 * 128, ring_bytes = 9 * 128 * 128;
+    const bool wide = g.width == (SWIGLU ? 128 : 256);
+    if (g.eight_phase) {
+        if (wide) g256_run<gemm8p_kernel<FP8, EPI, SWIGLU, WQ, ROPE>, stage_bytes, true>(a, grid, st);
+        else g256_run<gemm8p_n128_kernel<FP8, EPI, SWIGLU, WQ, ROPE>, ring_bytes, true>(a, grid, st);
+    } else if constexpr (!ROPE) {   // (the two-stage kernel reads W as the activations' format: never planned for int8 weights)
+        if (wide) g256_run<gemm256_kernel<FP8, EPI, 4, SWIGLU>, stage_bytes, false>(a, grid, st);
+        else if constexpr (!SWIGLU) g256_run<gemm256_kernel<FP8, EPI, 2>, stage_bytes_narrow, false>(a, grid, st);
+    }
+}
+// plan, then one launch per column range
+static void g256_launch(G256Form form, G256Operands ops, G256Args a, int N, hipStream_t st) {
+    const G256Plan p = plan_gemm256(form, ops, a.M, N, a.K);
+    const bool epi = a.bias || a.residual;
+    const size_t w_elem = ops == G256_F16 ? 2 : 1;
+    const G256Args whole = a;
+    for (int i = 0; i < p.ranges; ++i) {
+        const G256Range &g = p.range[i];
+        a = whole;
+        a.tiles_n = g.tiles;
+        if (form == G256_SWIGLU) {   // operands whole, N = 2I: the kernel finds its gate / up rows and output columns from col0
+            a.col0 = g.col0;
         } else {
-            if (epi) gemm256_launch_t<false, true, 2, 8>(x, Wr, yr, M, n, K, br, rr, nullptr, wsr, st, N);
-            else gemm256_launch_t<false, false, 2, 8>(x, Wr, yr, M, n, K, br, rr, nullptr, wsr, st, N);
+            a.W = static_cast<const unsigned char *>(whole.W) + static_cast<size_t>(g.col0) * a.K * w_elem;
+            a.N = std::min(g.tiles * g.width, N - g.col0);
+            a.ldc = N;
         }
-        return;
+        if (form == G256_QKV_ROPE) {   // C, the scales and the bias stay whole: the epilogue indexes them by col0 + tile column
+            a.col0 = g.col0;
+        } else if (form == G256_PLAIN) {
+            a.y += g.col0;
+            if (a.bias) a.bias += g.col0;
+            if (a.residual) a.residual += g.col0;
+            // int8 weights: the row scales are fp16, carried through the float pointer of the kernels' shared signature
+            if (a.wscale)
+                a.wscale = ops == G256_W8 ? reinterpret_cast<const float *>(reinterpret_cast<const half_t *>(whole.wscale) + g.col0)
+                                          : whole.wscale + g.col0;
+        }
+        const int grid = g256_row_tiles(a.M) * g.tiles;
+        switch (form) {
+            case G256_PLAIN:
+                if (ops == G256_W8) epi ? g256_run_range<G256_PLAIN, false, 8, true>(g, a, grid, st) : g256_run_range<G256_PLAIN, false, 8, false>(g, a, grid, st);
+                else if (ops == G256_E4M3) epi ? g256_run_range<G256_PLAIN, true, 0, true>(g, a, grid, st) : g256_run_range<G256_PLAIN, true, 0, false>(g, a, grid, st);
+                else epi ? g256_run_range<G256_PLAIN, false, 0, true>(g, a, grid, st) : g256_run_range<G256_PLAIN, false, 0, false>(g, a, grid, st);
+                break;
+            case G256_SWIGLU:
+                if (ops == G256_W8) g256_run_range<G256_SWIGLU, false, 8, false>(g, a, grid, st);
+                else if (ops == G256_E4M3) g256_run_range<G256_SWIGLU, true, 0, false>(g, a, grid, st);
+                else g256_run_range<G256_SWIGLU, false, 0, false>(g, a, grid, st);
+                break;
+            case G256_QKV_ROPE:
+                if (ops == G256_W8) g256_run_range<G256_QKV_ROPE, false, 8, false>(g, a, grid, st);
+                else if (ops == G256_E4M3) g256_run_range<G256_QKV_ROPE, true, 0, false>(g, a, grid, st);
+                else g256_run_range<G256_QKV_ROPE, false, 0, false>(g, a, grid, st);
+                break;
+        }
     }
-#define LLMIE_G256(F8_, EPI_)                                                                                          \
-    (wn == 4 ? gemm256_launch_t<F8_, EPI_, 4>(x, Wr, yr, M, n, K, br, rr, xscale, wsr, st, N)                          \
-             : gemm256_launch_t<F8_, EPI_, 2>(x, Wr, yr, M, n, K, br, rr, xscale, wsr, st, N))
-    if (fp8) {
-        if (epi) LLMIE_G256(true, true);
-        else LLMIE_G256(true, false);
-    } else {
-        if (epi) LLMIE_G256(false, true);
-        else LLMIE_G256(false, false);
-    }
-#undef LLMIE_G256
 }
 
-// Tile plan by rounds of the 256 CUs (one 512-thread workgroup per CU): a 256 x 128 tile costs ~0.6 of a 256 x 256 tile
-// (measured: 0.96 vs 1.12 PFLOP/s on full rounds).  A half-empty last round of 256-wide tiles (qkv at 2048 tokens: 384
-// tiles = 1.5 rounds) is avoided by running the full rounds 256-wide and the remaining columns 128-wide in a second launch.
-void gemm256_launch(bool fp8, const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias,
-                    const half_t *residual, const float *xscale, const float *wscale, hipStream_t st, int wq) {
-    constexpr int cus = 256;
-    constexpr bool no_split = false;
-    const int tm = (M + 255) / 256, tn4 = (N + 255) / 256, tn2 = (N + 127) / 128;
-    const int tiles4 = tm * tn4, tiles2 = tm * tn2;
-    auto rounds = [&](int t) { return (t + cus - 1) / cus; };
-    const float narrow = 0.6f;
-    float best = static_cast<float>(rounds(tiles4));
-    int plan = 4;
-    if (gemm256_wn(M, N) != 4 && (N % 4 != 0 || tiles4 < cus / 2)) {  // the 256-wide grid fills less than half the chip
-        plan = 2;
-    } else if (!no_split && N % 4 == 0) {   // (from half the chip on, the rounds decide: 768 x 12288 is ONE round of 144 wide tiles or
-                                            //  TWO of 288 narrow ones -- 97 against 119 us)
-        if (rounds(tiles2) * narrow < best) {
-            best = rounds(tiles2) * narrow;
-            plan = 2;
-        }
-        const int a_tn = (tiles4 / cus) * cus / tm;  // 256-wide column tiles that make whole rounds
-        if (a_tn > 0 && a_tn < tn4) {
-            const int nB = N - a_tn * 256, tilesB = tm * ((nB + 127) / 128);
-            const float c = static_cast<float>(rounds(tm * a_tn)) + rounds(tilesB) * narrow;
-            if (c < best) {
-                best = c;
-                plan = 42;
-            }
-        }
-    }
-    if (plan == 42) {
-        const int a_tn = (tiles4 / cus) * cus / tm;
-        gemm256_range(fp8, 4, x, W, y, M, N, K, bias, residual, xscale, wscale, st, 0, a_tn * 256, wq);
-        gemm256_range(fp8, 2, x, W, y, M, N, K, bias, residual, xscale, wscale, st, a_tn * 256, N - a_tn * 256, wq);
-    } else {
-        gemm256_range(fp8, plan, x, W, y, M, N, K, bias, residual, xscale, wscale, st, 0, N, wq);
-    }
+void gemm256_launch(G256Operands ops, const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias,
+                    const half_t *residual, const float *xscale, const float *wscale, hipStream_t st) {
+    g256_launch(G256_PLAIN, ops, G256Args{x, W, y, M, N, K, bias, residual, 0, xscale, wscale, 0, 0, nullptr, 0}, N, st);
+}
+void gemm256_swiglu_launch(G256Operands ops, const void *x, const void *W, half_t *y, int M, int two_inter, int K, const float *xscale,
+                           const float *wscale, hipStream_t st) {
+    g256_launch(G256_SWIGLU, ops, G256Args{x, W, y, M, two_inter, K, nullptr, nullptr, 0, xscale, wscale, 0, 0, nullptr, 0}, two_inter, st);
 }
 
 // ---- QKV projection of a prefill with RoPE + KV-cache append as its epilogue (gemm8p.cuh ROPE forms; context_attention.cpp:158-205
-// as one launch sequence).  kind: 0 = fp16 operands, 1 = e4m3 operands (xscale / wscale), 8 = int8 weights (wscale = fp16 row scales).
-// N = (head_num + 2 kv_head_num) * 128; the tile plan is gemm256_launch's, with every column range a whole number of tiles (a tile
-// never straddles the end of the matrix: the ROPE forms fetch their weight rows unclamped, in permuted order).
-bool gemm256_qkv_rope_eligible(int kind, int M, int N, int K, const void *x, const void *W, const void *wscale, const void *qkv) {
-    const bool fp8 = kind == 1;
-    return N % 128 == 0 && K % (fp8 ? 128 : 64) == 0 && gemm256_fills(M, N) &&
-           (static_cast<size_t>(N) + 512) * K * (fp8 ? 1 : 2) < (size_t{1} << 32) &&
+// as one launch sequence).  N = (head_num + 2 kv_head_num) * 128.
+bool gemm256_qkv_rope_eligible(G256Operands ops, int M, int N, int K, const void *x, const void *W, const void *wscale, const void *qkv) {
+    const bool fp8 = ops == G256_E4M3;
+    return N % 128 == 0 && K % (fp8 ? 128 : 64) == 0 && gemm256_fills(M, N) && gemm8p_fits(N, K, fp8 ? 1 : 2) &&
            (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) % 16 == 0 &&
            (reinterpret_cast<uintptr_t>(wscale) % (fp8 ? 16 : 8)) == 0 && reinterpret_cast<uintptr_t>(qkv) % 8 == 0;
 }
-template <bool FP8, int WQ, int WN>
-static void qkv_rope_range(const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale, const float *wscale,
-                           const half_t *bias, const QkvRopeArgs *rap, int layer, hipStream_t st, int nb, int n) {
-    // W is offset to the range like every range launch; C, the scales and the bias stay whole: the epilogue indexes them by the
-    // absolute output column col0 + tile column.  rap: DEVICE pointer (prefill_token_table); bias: this layer's QKV bias or null
-    const void *Wr = static_cast<const unsigned char *>(W) + static_cast<size_t>(nb) * K * ((FP8 || WQ) ? 1 : 2);
-    const int tm = (M + 255) / 256, tn = n / (64 * WN);
-    if constexpr (WN == 4) {
-        constexpr int lds_bytes = 2 * 4 * 128 * 128;
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_kernel<FP8, false, false, WQ, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            return true;
-        }();
-        (void)attr;
-        gemm8p_kernel<FP8, false, false, WQ, true><<<tm * tn, 512, lds_bytes, st>>>(x, Wr, qkv, M, n, K, bias, nullptr, tn, xscale, wscale, N,
-                                                                                   g256_group_m(), nb, rap, layer);
-    } else {
-        constexpr int ring_bytes = 9 * 128 * 128;
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm8p_n128_kernel<FP8, false, false, WQ, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes);
-            return true;
-        }();
-        (void)attr;
-        gemm8p_n128_kernel<FP8, false, false, WQ, true><<<tm * tn, 512, ring_bytes, st>>>(x, Wr, qkv, M, n, K, bias, nullptr, tn, xscale, wscale, N,
-                                                                                         g256_group_m(), nb, rap, layer);
-    }
-}
-void gemm256_qkv_rope_launch(int kind, const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale,
+// rap: DEVICE pointer (prefill_token_table); bias: this layer's QKV bias or null
+void gemm256_qkv_rope_launch(G256Operands ops, const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale,
                              const float *wscale, const half_t *bias, const QkvRopeArgs *rap, int layer, hipStream_t st) {
-    constexpr int cus = 256;
-    const int tm = (M + 255) / 256, tn4 = N / 256, tn2 = N / 128;
-    auto rounds = [&](int t) { return (t + cus - 1) / cus; };
-    const float narrow = 0.6f;
-    // candidates: all 128-wide; all 256-wide (N a multiple of 256); whole rounds 256-wide + the rest 128-wide
-    int plan = 2, a_tn = 0;
-    float best = rounds(tm * tn2) * narrow;
-    if (gemm256_wn(M, N) == 4 || tm * tn4 >= cus / 2) {   // (from half the chip on, the rounds decide: gemm256_launch's rule)
-        if (N % 256 == 0 && static_cast<float>(rounds(tm * tn4)) < best) {
-            best = static_cast<float>(rounds(tm * tn4));
-            plan = 4;
-        }
-        const int a = (tm * tn4 / cus) * cus / tm;   // 256-wide column tiles that make whole rounds
-        if (a > 0 && a * 256 < N) {
-            const float c = static_cast<float>(rounds(tm * a)) + rounds(tm * ((N - a * 256) / 128)) * narrow;
-            if (c < best) {
-                best = c;
-                plan = 42;
-                a_tn = a;
-            }
-        }
-    }
-    auto range = [&](int wn, int nb, int n) {
-#define LLMIE_QR(F8_, WQ_) (wn == 4 ? qkv_rope_range<F8_, WQ_, 4>(x, W, qkv, M, N, K, xscale, wscale, bias, rap, layer, st, nb, n) \
-                                    : qkv_rope_range<F8_, WQ_, 2>(x, W, qkv, M, N, K, xscale, wscale, bias, rap, layer, st, nb, n))
-        if (kind == 1) LLMIE_QR(true, 0);
-        else if (kind == 8) LLMIE_QR(false, 8);
-        else LLMIE_QR(false, 0);
-#undef LLMIE_QR
-    };
-    if (plan == 42) {
-        range(4, 0, a_tn * 256);
-        range(2, a_tn * 256, N - a_tn * 256);
-    } else {
-        range(plan, 0, N);
-    }
+    g256_launch(G256_QKV_ROPE, ops, G256Args{x, W, qkv, M, N, K, bias, nullptr, 0, xscale, wscale, 0, 0, rap, layer}, N, st);
 }
 
 // ---- route planning: which kernel a projection runs on.  Pure host code: no HIP call, no error text, no launch. ----
@@ -957,10 +856,9 @@ LinearPlan plan_linear_f16(const LinearCall &c) {
     if (M > 192 && !swiglu && aligned && K % 64 == 0 && !gemm256_fills(M, N)) {
         const int passes = (M + kSplitKPassRows - 1) / kSplitKPassRows;
         const float t_split = passes * (static_cast<float>(N) * K * 2.f / 4.2e6f + 10.f);
-        const int tiles2 = ((M + 255) / 256) * ((N + 127) / 128);
-        const float t_tiles = static_cast<float>((tiles2 + 255) / 256) * (K / 64) * 0.9f;
+        const float t_tiles = static_cast<float>(gemm256_narrow_rounds(M, N)) * (K / 64) * 0.9f;
         const bool split_ok = c.slabs && K % 128 == 0 && K >= 512 && c.slab_floats >= linear_splitk_ws_floats(16, kSplitKPassRows, K, N);
-        const bool tiles_ok = g8p_fits(N, K, false) && c.mis_y % 8 == 0 && epi8;
+        const bool tiles_ok = gemm8p_fits(N, K, 2) && c.mis_y % 8 == 0 && epi8;
         mid_rows = split_ok && (!tiles_ok || t_split < t_tiles);
         mid_tiles = tiles_ok && !mid_rows;
     }
@@ -1003,8 +901,8 @@ LinearPlan plan_linear_wq(const LinearCall &c) {
     const bool swiglu = c.epi == EPI_SWIGLU, plain = c.epi == EPI_NONE;
     const bool aligned = (c.mis_x | c.mis_w | c.mis_gamma | c.mis_pre_bias) == 0 && (static_cast<size_t>(K) * bits / 8) % 16 == 0;
     // int8 [N, K] weights through the eight-phase kernels (gemm8p.cuh, WQ = 8): prefill-sized M whose 256-row grid fills the chip
-    // (per-lane DMA offsets are 32-bit)
-    const bool g8p_operands = bits == 8 && K % 64 == 0 && (static_cast<size_t>(N) + 512) * K * 2 < (size_t{1} << 32) &&
+    // (the fit counts 2 bytes per element although int8 weights are 1: kept, it is where these routes have always ended)
+    const bool g8p_operands = bits == 8 && K % 64 == 0 && gemm8p_fits(N, K, 2) &&
                               (c.mis_x | c.mis_w) == 0 && (c.mis_scale | c.mis_y) % 8 == 0;
     const bool g8p = g8p_operands && N % 4 == 0 && gemm256_fills(M, N);
     const bool g8p_swiglu = g8p_operands && N % 8 == 0 && gemm256_swiglu_fills(M, N);
@@ -1126,11 +1024,11 @@ int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int
             else dispatch_skinny<EPI_NONE>(M, x, W, y, K, N, bias, residual, st);
             return launch_status("linear");
         case LR_SWIGLU256:
-            gemm256_swiglu_launch(false, x, W, y, M, N, K, nullptr, nullptr, st);
+            gemm256_swiglu_launch(G256_F16, x, W, y, M, N, K, nullptr, nullptr, st);
             return launch_status("linear(gemm256 SwiGLU)");
         case LR_TILES256:
         case LR_TILES256_PART:
-            gemm256_launch(false, x, W, y, M, N, K, bias, residual, nullptr, nullptr, st);
+            gemm256_launch(G256_F16, x, W, y, M, N, K, bias, residual, nullptr, nullptr, st);
             return launch_status("linear(gemm256)");
         case LR_TILES128: {
             dim3 grid((N + 127) / 128, (M + 127) / 128, 1);
@@ -1243,6 +1141,20 @@ extern "C" const char *llmie_linear_route(llmie_weight_format fmt, const void *x
     if (p.inner != LR_REFUSED) snprintf(name, sizeof(name), "%s+%s", linear_route_name(p.route), linear_route_name(p.inner));
     else snprintf(name, sizeof(name), "%s", linear_route_name(p.route));
     return name;
+}
+
+extern "C" const char *llmie_gemm256_tiles(int form, int operands, int M, int N, int K) {
+    static thread_local char text[64];
+    auto fail = [](const char *what) -> const char * {
+        set_error("gemm256_tiles: %s", what);
+        return nullptr;
+    };
+    if (form < G256_PLAIN || form > G256_QKV_ROPE || operands < G256_F16 || operands > G256_W8) return fail("unknown form or operand format");
+    if (M <= 0 || N <= 0 || K <= 0) return fail("bad shape");
+    if (form == G256_SWIGLU && N % 8 != 0) return fail("SwiGLU form: two_inter % 8 == 0");
+    if (form == G256_QKV_ROPE && N % 128 != 0) return fail("QKV + RoPE form: N % 128 == 0");
+    g256_plan_text(plan_gemm256(static_cast<G256Form>(form), static_cast<G256Operands>(operands), M, N, K), text, sizeof(text));
+    return text;
 }
 
 extern "C" int llmie_batched_gemm(const void *a, const void *b, void *c, int batch, int m, int n, int k,

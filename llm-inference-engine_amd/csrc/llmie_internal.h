@@ -92,19 +92,36 @@ int rmsnorm_oop_f16(const half_t *x, half_t *y, const half_t *gamma, float eps, 
 int quantize_rows_fp8(const half_t *x, uint8_t *xq, float *xscale, int M, int K, hipStream_t st);
 int linear_splitk(int wbits, const half_t *x, const void *W, const half_t *scale, half_t *y, int M, int K, int N, int epi,
                   const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st);
-// 256 x 256 LDS-DMA tiled GEMM (gemm256.cuh; K % 64 == 0 fp16, K % 128 == 0 fp8; 16-byte aligned operands); linear.hip
+// The 256-row tiled GEMM family (gemm8p.cuh eight-phase, gemm256.cuh two-stage; K % 64 == 0 fp16, K % 128 == 0 fp8; 16-byte aligned
+// operands); linear.hip.  Operand formats: fp16; e4m3 weights and activations (xscale per token, wscale per weight row, fp32); int8
+// weights [N, K] under fp16 activations (`wscale` carries their fp16 per-row scales).  The values are llmie_gemm256_tiles' codes.
+enum G256Operands : int { G256_F16 = 0, G256_E4M3 = 1, G256_W8 = 2 };
+enum G256Form : int { G256_PLAIN = 0, G256_SWIGLU = 1, G256_QKV_ROPE = 2 };
+// The tile plan of one projection: one or two launches, each over the column tiles [col0, col0 + tiles * width) of the output
+struct G256Range {
+    bool eight_phase;   // gemm8p.cuh; false: gemm256_kernel, where the eight-phase kernels' 32-bit DMA offsets do not fit
+    int width, col0, tiles;
+};
+struct G256Plan {
+    int ranges;
+    G256Range range[2];
+};
+// N: weight rows (SwiGLU form: two_inter; its ranges are columns of the [M, I] output).  Pure host code.
+G256Plan plan_gemm256(G256Form form, G256Operands ops, int M, int N, int K);
 bool gemm256_fills(int M, int N);
-// wq = 8: W is int8 [N, K] under fp16 activations and `wscale` carries its fp16 per-row scales (gemm8p.cuh, WQ = 8)
-void gemm256_launch(bool fp8, const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias,
-                    const half_t *residual, const float *xscale, const float *wscale, hipStream_t st, int wq = 0);
 bool gemm256_swiglu_fills(int M, int two_inter);
-void gemm256_swiglu_launch(bool fp8, const void *x, const void *W, half_t *y, int M, int two_inter, int K, const float *xscale,
-                           const float *wscale, hipStream_t st, int wq = 0);
-// QKV projection with RoPE + KV-cache append as its epilogue (gemm8p.cuh ROPE forms): kind 0 = fp16, 1 = e4m3 operands, 8 = int8
-// weights (wscale = fp16 row scales); q columns -> qkv (rotated), k / v columns -> the caches only; linear.hip
-bool gemm256_qkv_rope_eligible(int kind, int M, int N, int K, const void *x, const void *W, const void *wscale, const void *qkv);
+int gemm256_narrow_rounds(int M, int N);   // rounds of the chip that the all-narrow (256 x 128) grid of the plain form takes
+// do the eight-phase kernels' 32-bit DMA offsets reach every element of N rows of K elements?
+bool gemm8p_fits(int N, int K, int elem_bytes);
+void gemm256_launch(G256Operands ops, const void *x, const void *W, half_t *y, int M, int N, int K, const half_t *bias,
+                    const half_t *residual, const float *xscale, const float *wscale, hipStream_t st);
+void gemm256_swiglu_launch(G256Operands ops, const void *x, const void *W, half_t *y, int M, int two_inter, int K, const float *xscale,
+                           const float *wscale, hipStream_t st);
+// QKV projection with RoPE + KV-cache append as its epilogue (gemm8p.cuh ROPE forms): q columns -> qkv (rotated), k / v columns ->
+// the caches only
+bool gemm256_qkv_rope_eligible(G256Operands ops, int M, int N, int K, const void *x, const void *W, const void *wscale, const void *qkv);
 // rap: the epilogue's layer-invariant operands in DEVICE memory (prefill_token_table writes them); bias: the layer's QKV bias or null
-void gemm256_qkv_rope_launch(int kind, const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale,
+void gemm256_qkv_rope_launch(G256Operands ops, const void *x, const void *W, half_t *qkv, int M, int N, int K, const float *xscale,
                              const float *wscale, const half_t *bias, const QkvRopeArgs *rap, int layer, hipStream_t st);
 // fp16 image of int8 / int4 weights (row scales / group scales applied, one rounding): the operand of the prefill-sized
 // projections that have no in-kernel de-quantising form; quant_linear.hip

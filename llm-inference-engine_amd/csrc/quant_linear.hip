@@ -184,10 +184,10 @@ int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, h
     const LinearPlan p = plan_linear_wq(c);
     switch (p.route) {
         case LR_W8_G8P_SWIGLU:
-            gemm256_swiglu_launch(false, x, wq, y, M, N, K, nullptr, reinterpret_cast<const float *>(scale), st, 8);
+            gemm256_swiglu_launch(G256_W8, x, wq, y, M, N, K, nullptr, reinterpret_cast<const float *>(scale), st);
             return launch_status("linear_w8a16(gemm8p SwiGLU)");
         case LR_W8_G8P:
-            gemm256_launch(false, x, wq, y, M, N, K, bias, residual, nullptr, reinterpret_cast<const float *>(scale), st, 8);
+            gemm256_launch(G256_W8, x, wq, y, M, N, K, bias, residual, nullptr, reinterpret_cast<const float *>(scale), st);
             return launch_status("linear_w8a16(gemm8p)");
         case LR_WQ_IMAGE_PREFILL:
         case LR_WQ_IMAGE_LAST: {

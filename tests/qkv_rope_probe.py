@@ -20,6 +20,8 @@ res = {}
 # name, weight format, heads, kv heads, inter, lengths, histories, max_seq, e4m3 cache, paged, qkv bias, rotary_dim
 CASES = [
     ("f16_b1_7b_heads", "f16", 32, 32, 1024, [2048], [0], 2048, False, False, False, 128),          # 256-wide + 128-wide launches (the bench's plan)
+    ("int8_b1_7b_heads", "int8", 32, 32, 1024, [2048], [0], 2048, False, False, False, 128),        # the same two-launch plan on the int8 forms
+    ("fp8_b1_7b_heads", "fp8", 32, 32, 1024, [2048], [0], 2048, False, False, False, 128),          # ... and on the e4m3 forms
     ("f16_ragged_gqa_bias", "f16", 32, 8, 1024, [700, 257, 129], [0, 0, 0], 768, False, False, True, 128),
     ("f16_history_paged", "f16", 16, 16, 768, [1200, 848], [150, 200], 1408, False, True, False, 128),   # all 256-wide tiles
     ("f16_kv8_np2", "f16", 16, 16, 768, [1000, 131], [0, 17], 1024, True, False, True, 64),          # e4m3 cache, partial rotary
