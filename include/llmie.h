@@ -41,7 +41,8 @@ extern "C" {
  *      of the stream argument and llmie_linear_fp8_workspace_bytes gained N; w8a16 with M > 64 / w4a16 with M > 8 need a
  *      workspace (NULL -> LLMIE_ERR_UNSUPPORTED).  A version-1 consumer would pass its stream where the slab pointer goes.
  *   3  round 3: additions only are listed at the entries they concern (int8 / int4 weight-only prefill, decoder config flags,
- *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params). */
+ *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params; token scoring:
+ *      llmie_score_tokens(_workspace_bytes)). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -287,6 +288,30 @@ int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sa
                         int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
                         int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
                         size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition).  Score given tokens: RMSNorm + LM head + log-softmax over `rows` hidden states at once, for prompt
+ * log-probabilities ("echo + logprobs"), perplexity and ranking by likelihood.  No reference launcher: the reference computes
+ * logits for the last prompt token only.  The [rows, vocab] logits are never written and never rounded to fp16.  Per row t:
+ *   1 x[t] = RMSNorm(hidden[t], norm_gamma, rms_eps) rounded to fp16 -- the bits llmie_rmsnorm leaves in place (it runs on a
+ *     copy in the workspace; `hidden` is NOT modified).  norm_gamma == NULL: x = hidden.
+ *   2 z[t, v] = sum_k x[t, k] * lm_head[v, k] (+ lm_bias[v]), accumulated and kept in fp32.
+ *   3 lse[t] = log sum_v exp(z[t, v]) with a running maximum (logits of magnitude 200 do not overflow).
+ *   4 out_logprob[t] = z[t, targets[t]] - lse[t].  A target outside [0, vocab) means "no target" (the last token of a sequence):
+ *     out_logprob[t] = 0, lse and argmax are still produced.
+ *   5 out_argmax[t] = id of the largest z[t, :], ties -> lower id (llmie_topk's rule); out_argmax_logprob[t] = max - lse[t].
+ * out_lse / out_argmax / out_argmax_logprob may be NULL.  Rows past `rows` of the outputs are not written.
+ * Determinism: the vocabulary is cut into spans of column tiles by `vocab` alone and the spans' partial (max, sum, best) are
+ * merged in span order without atomics, so the same inputs give the same bits and a row's result depends neither on `rows`
+ * nor on the row's position.
+ * LLMIE_F16 only (LLMIE_F32: LLMIE_ERR_UNSUPPORTED); hidden_size % 64 == 0 and 16-byte aligned hidden / lm_head, else
+ * LLMIE_ERR_UNSUPPORTED; rows >= 1, any vocab >= 1.  workspace: llmie_score_tokens_workspace_bytes(rows, hidden_size, vocab)
+ * bytes, 16-byte aligned: the normalised rows (rows * hidden_size halves) and 32 bytes per (row, span), at most 32 spans --
+ * never rows * vocab.  NULL / short: LLMIE_ERR_WORKSPACE.  No allocation, no synchronisation; legal inside a graph capture. */
+size_t llmie_score_tokens_workspace_bytes(int rows, int hidden_size, int vocab);
+int llmie_score_tokens(const void *hidden, const void *norm_gamma, float rms_eps, const void *lm_head, const void *lm_bias,
+                       const int32_t *targets, float *out_logprob, float *out_lse, int32_t *out_argmax,
+                       float *out_argmax_logprob, int rows, int hidden_size, int vocab, void *workspace,
+                       size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
 
 /* ------------------------------------------------------------------------- */
 /* 2. weight-only quantised / fp8 linears (reference: planned only,           */

@@ -97,6 +97,8 @@ _SIGS = {
     "llmie_advance_step": [_vp, _vp],
     "llmie_sample_logits_workspace_bytes": [_i, _i],
     "llmie_sample_logits": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _vp],
+    "llmie_score_tokens_workspace_bytes": [_i, _i, _i],
+    "llmie_score_tokens": [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp],
     "llmie_lm_head_sample_params": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp,
                                     _vp, _i, _vp, _sz, _vp],
     "llmie_decoder_forward_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
@@ -125,6 +127,7 @@ _RESTYPES = {
     "llmie_decoder_workspace_bytes": _sz,
     "llmie_decoder_prefill_workspace_bytes": _sz,
     "llmie_sample_logits_workspace_bytes": _sz,
+    "llmie_score_tokens_workspace_bytes": _sz,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -451,6 +454,41 @@ def sample_logits(logits, params, seq_len, finished, out_id, step, end_id, histo
     _check(lib().llmie_sample_logits(_p(logits), bs, V, _p(params), _p(history), stride, _p(history_len), 1 if append else 0,
                                      _p(seq_len), _p(finished), _p(out_id), _p(out_logprob), step, _p(step_dev), end_id,
                                      _p(ws), ws_bytes, _dt(logits), _st()), "sample_logits")
+
+
+# ------------------------------------------------------------------ token scoring
+def score_tokens_workspace_bytes(rows, hidden, vocab):
+    return lib().llmie_score_tokens_workspace_bytes(rows, hidden, vocab)
+
+
+_score_scratch = {}
+
+
+def score_tokens(hidden, lm_head, targets, gamma=None, eps=0.0, bias=None, want_lse=False, want_argmax=False, workspace="auto"):
+    """llmie_score_tokens: log-probability of targets[t] (int32, device; outside [0, V): no target -> 0) under
+    softmax(rmsnorm(hidden[t]) . lm_head^T + bias), the logits kept in fp32 and never written.  hidden [rows, H] fp16 is left as
+    it is; gamma None: no RMSNorm.  Returns the fp32 logprob tensor, or a tuple (logprob[, lse][, argmax int32, argmax_logprob]).
+    workspace: a device tensor of score_tokens_workspace_bytes(rows, H, V) bytes, or the string auto (one grow-only buffer per
+    device owned by this module; inside a graph capture pass a tensor, or make a first call outside)."""
+    import torch
+    rows, H = hidden.shape
+    V = lm_head.shape[0]
+    if isinstance(workspace, str):
+        need = score_tokens_workspace_bytes(rows, H, V)
+        workspace = _score_scratch.get(hidden.device)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=hidden.device)
+            _score_scratch[hidden.device] = workspace
+    out = torch.empty(rows, dtype=torch.float32, device=hidden.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=hidden.device) if want_lse else None
+    amax = torch.empty(rows, dtype=torch.int32, device=hidden.device) if want_argmax else None
+    amax_lp = torch.empty(rows, dtype=torch.float32, device=hidden.device) if want_argmax else None
+    _check(lib().llmie_score_tokens(_p(hidden), _p(gamma), eps, _p(lm_head), _p(bias), _p(targets), _p(out), _p(lse), _p(amax),
+                                    _p(amax_lp), rows, H, V, _p(workspace),
+                                    0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(hidden), _st()),
+           "score_tokens")
+    res = (out,) + ((lse,) if want_lse else ()) + ((amax, amax_lp) if want_argmax else ())
+    return res[0] if len(res) == 1 else res
 
 
 # ------------------------------------------------------------------ fused decoder engine

@@ -78,7 +78,9 @@ private:
     DevBuf<bool> d_finished;
     DevBuf<llmie_sampling_params> d_sparams;
     DevBuf<int> d_penalty_ids, d_penalty_len;
-    DevBuf<unsigned char> d_sample_ws;
+    DevBuf<unsigned char> d_sample_ws, d_score_ws;
+    DevBuf<int> d_targets;
+    DevBuf<float> d_logprob;
     std::vector<int> penalty_ids;   // prompt + generated ids: the penalty history of the SamplingConfig path
 
     // SamplingConfig path: llmie_sample_logits over the whole vocabulary, seeded by (h_step, sampling.seed)
@@ -198,6 +200,43 @@ public:
 
     // llama.cpp:165-217: prefill of `ids` on top of `history_len` cached tokens; returns the first new token
     int generateFirstToken(const std::vector<int> &ids, int history_len) {
+        T *ctx_out = runContext(ids, history_len);
+        return lmHeadAndSample(ctx_out + (ids.size() - 1) * hidden_units);  // last token only (:262-279)
+    }
+
+    // Log-probability of every prompt token after the first under the model: the prefill of generateFirstToken (no history), then
+    // llmie_score_tokens on all n rows of the context decoder's output, row i scoring ids[i + 1] (the last row has no target).
+    // Returns the n - 1 values log P(ids[i] | ids[0..i)), i = 1 .. n - 1.  fp16 models only (T = float throws: unsupported).  The
+    // model is left as after a prefill of `ids`: continueWith can follow.
+    std::vector<float> scoreTokens(const std::vector<int> &ids) {
+        const int n = static_cast<int>(ids.size());
+        const T *ctx_out = runContext(ids, 0);
+        std::vector<int> targets(ids.begin() + 1, ids.end());
+        targets.push_back(-1);
+        CHECK(hipMemcpyAsync(d_targets.ensure(n), targets.data(), sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
+        const size_t ws = llmie_score_tokens_workspace_bytes(n, hidden_units, vocab_size);
+        LLMIE_CALL(llmie_score_tokens(ctx_out, llama_weights->out_rmsnorm_weight.gamma, rmsnorm_eps,
+                                      llama_weights->post_decoder_embedding_weight.data, nullptr, d_targets.p, d_logprob.ensure(n),
+                                      nullptr, nullptr, nullptr, n, hidden_units, vocab_size, d_score_ws.ensure(std::max<size_t>(ws, 16)),
+                                      ws, llmie_api::dtype_of<T>(), llmie_api::st()));
+        std::vector<float> logprob(n);
+        CHECK(hipMemcpyAsync(logprob.data(), d_logprob.p, sizeof(float) * n, hipMemcpyDeviceToHost, llmie_api::st()));
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps `targets` alive until its copy is done)
+        logprob.pop_back();
+        return logprob;
+    }
+    // the context decoder's output [n, hidden_units] of the last prefill (generateFirstToken normalises its last row in place)
+    const T *contextOutput() const { return d_ctx_out.p; }
+    // the decode step response() runs after a prefill: token `id` joins the context, then generateNextToken
+    int continueWith(int id) {
+        LLM_CHECK_WITH_INFO(h_step + 1 < max_seq_len, "context does not fit max_seq_len");
+        ++h_step;
+        return generateNextToken(id);
+    }
+
+private:
+    // embedding + context decoder over `ids` on top of `history_len` cached tokens -> its output [n, hidden_units] (device)
+    T *runContext(const std::vector<int> &ids, int history_len) {
         const int n = static_cast<int>(ids.size());
         LLM_CHECK_WITH_INFO(n > 0 && history_len + n < max_seq_len, "prompt does not fit max_seq_len");
         const DataType ty = getTensorType<T>(), ti = getTensorType<int>();
@@ -231,8 +270,10 @@ public:
         h_step = ctx;
         if (history_len == 0) penalty_ids.clear();
         penalty_ids.insert(penalty_ids.end(), ids.begin(), ids.end());
-        return lmHeadAndSample(ctx_out.data + static_cast<size_t>(n - 1) * hidden_units);  // last token only (:262-279)
+        return ctx_out.data;
     }
+
+public:
 
     // llama.cpp:219-257: one decode step for token `id`; h_step = context length including it
     int generateNextToken(int id) {
