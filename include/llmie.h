@@ -42,7 +42,7 @@ extern "C" {
  *      workspace (NULL -> LLMIE_ERR_UNSUPPORTED).  A version-1 consumer would pass its stream where the slab pointer goes.
  *   3  round 3: additions only are listed at the entries they concern (int8 / int4 weight-only prefill, decoder config flags,
  *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params; token scoring:
- *      llmie_score_tokens(_workspace_bytes)). */
+ *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -205,6 +205,29 @@ int llmie_decoder_mha_ragged(const void *qkv, const void *qkv_bias, void *k_cach
                              const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
                              int rotary_dim, const int32_t *block_table, int max_pages, int num_pages,
                              llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition; host only, no device access).  The launch the three entries above -- and the engine's calls, which add the
+ * e4m3 cache, the split-K slabs and the x32 output -- plan for a call, as one line of text:
+ *   "split f16 hs128 rep4 kv=e4m3 cpw2 chunk512 grid 4x8x16 merge 32x16/128"   the split kernel's instantiation, chunks per workgroup,
+ *        tokens per workgroup, grid (splits x kv heads x batch) and the merge launch (grid / block; "in-launch": by tickets; "none":
+ *        one split)
+ *   "generic f32 grid 32x2 lds 1028"   the kernel for any head size / ratio: grid (heads x batch), dynamic LDS bytes
+ * NULL for a call they refuse: llmie_last_error() says why and *status (nullable) receives the code they return.
+ * step: the host position (ignored with LLMIE_ATTN_STEP_DEV).  residues: address % 16 of each operand after the layer offset, 4 bits
+ * each from bit 0: qkv, qkv_bias, k_cache, v_cache, slabs, the slab scales' wf and wh vectors, and (slab rows x columns) % 4.
+ * workspace_bytes < 0: no workspace. */
+#define LLMIE_ATTN_STEP_DEV 1u    /* the position is device resident (*step_dev, or ctx_len_dev) */
+#define LLMIE_ATTN_RAGGED 2u      /* one context length per sequence */
+#define LLMIE_ATTN_BIAS 4u
+#define LLMIE_ATTN_ROPE 8u        /* rope_table given */
+#define LLMIE_ATTN_TICKETS 16u
+#define LLMIE_ATTN_SLABS 32u      /* q/k/v from the QKV projection's split-K slabs (engine) */
+#define LLMIE_ATTN_PAGED 64u      /* block_table given, with max_pages / num_pages */
+#define LLMIE_ATTN_X32 128u       /* the output is the x32 activation image (engine) */
+#define LLMIE_ATTN_BAD_SCALES 256u /* e4m3 cache: a scale that is not positive */
+const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                   int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                   unsigned long long residues, long long workspace_bytes, int *status);
 
 /* replaces launchConcatKVCache         src/kernels/concat_past_kv.cu:44-89  (one call = K or V) */
 int llmie_concat_kv(const void *src, void *cache, const int32_t *cur_len,

@@ -87,6 +87,7 @@ _SIGS = {
     "llmie_decoder_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "llmie_decoder_forward_ragged": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "llmie_decoder_forward_paged_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "llmie_decoder_mha_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _vp],
     "llmie_decoder_mha_ragged": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp],
     "llmie_decoder_prefill_workspace_bytes": [_vp, _i, _i],
     "llmie_decoder_prefill": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
@@ -133,6 +134,7 @@ _RESTYPES = {
     "llmie_last_error": C.c_char_p,
     "llmie_linear_route": C.c_char_p,
     "llmie_gemm256_tiles": C.c_char_p,
+    "llmie_decoder_mha_plan": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
 }
@@ -242,6 +244,26 @@ def gemm256_tiles(form, operands, M, N, K):
     format ("f16", "e4m3", "int8"): e.g. "8p 256x32@0 128x2@8192" (include/llmie.h); None for other arguments.  No device needed."""
     r = lib().llmie_gemm256_tiles(G256_FORMS[form], G256_OPERANDS[operands], M, N, K)
     return r.decode() if r is not None else None
+
+
+ATTN_FORMS = {"step_dev": 1, "ragged": 2, "bias": 4, "rope": 8, "tickets": 16, "slabs": 32, "paged": 64, "x32": 128, "bad_scales": 256}
+ATTN_OPERANDS = ("qkv", "bias", "k", "v", "slab", "wf", "wh", "slab_stride")
+
+
+def decoder_mha_plan(dtype, batch, head_num, kv_head_num, head_size, max_seq_len, step=-1, kv_e4m3=False, forms=(), max_pages=0,
+                     num_pages=0, residues=None, workspace_bytes="exact"):
+    """(plan text or None, status) of the decode attention launch for a call (include/llmie.h): e.g. "split f16 hs128 rep4 kv=f16 cpw1
+    chunk128 grid 3x2x4 merge 8x4/128" or "generic f32 grid 6x2 lds 1028"; None where the entries refuse the call (status = their
+    error code, llmie_last_error() says why).  forms: names of ATTN_FORMS; residues: {operand of ATTN_OPERANDS: address % 16};
+    workspace_bytes: a size, None (no workspace) or "exact".  No device needed."""
+    f = sum(ATTN_FORMS[n] for n in forms)
+    r = sum((v & 15) << (4 * ATTN_OPERANDS.index(k)) for k, v in (residues or {}).items())
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_decoder_mha_plan(dtype, int(kv_e4m3), batch, head_num, kv_head_num, head_size, max_seq_len, step, f, max_pages,
+                                     num_pages, r, -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):

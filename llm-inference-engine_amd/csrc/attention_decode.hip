@@ -707,196 +707,244 @@ struct KvScale {
     float k, v;
 };
 
-template <typename T, int HS, int REP, typename KT = T>
-static void launch_split(const T *qkv, const T *bias, KT *kc, KT *vc, float *part, T *out, int batch,
-                         int head_num, int kv_head_num, int max_seq_len, int step, const int32_t *step_dev,
-                         int max_splits_ws, const float2 *rope, int rot_dim, int32_t *tickets, const QkvSlabs &qs,
-                         KvScale ks, PagedKv pg, hipStream_t st) {
-    const int bound = step_dev ? max_seq_len : step;
+// ---- the launch plan: pure host code (no pointer read, no environment, no HIP call, no error text) ----
+// tokens per chunk of the split kernel's geometry (4 waves, 8 K + 8 V loads in flight per lane; 8 waves x 8 and 4 x 4 measured
+// slower, round 1) for a supported head size
+template <typename KT> static int attn_chunk(int hs) {
+    switch (hs) {
+        case 32: return AttnGeom<KT, 32>::CHUNK;
+        case 64: return AttnGeom<KT, 64>::CHUNK;
+        case 128: return AttnGeom<KT, 128>::CHUNK;
+        default: return AttnGeom<KT, 256>::CHUNK;
+    }
+}
+static bool attn_fused_geometry(const DecodeAttnCall &c) {
+    const int rep = c.head_num / c.kv_head_num;
+    return (c.head_size == 32 || c.head_size == 64 || c.head_size == 128 || c.head_size == 256) && (rep == 1 || rep == 2 || rep == 4 || rep == 8);
+}
+static DecodeAttnPlan attn_refusal(int refusal, size_t need = 0) {
+    DecodeAttnPlan p{};
+    p.kind = DA_REFUSED, p.refusal = refusal, p.workspace_bytes = need;
+    return p;
+}
+static DecodeAttnPlan plan_attn_split(const DecodeAttnCall &c, size_t need) {
+    DecodeAttnPlan p{};
+    const int bound = c.step_dev ? c.max_seq_len : c.step;
+    p.kind = DA_SPLIT, p.hs = c.head_size, p.rep = c.head_num / c.kv_head_num, p.e4m3 = c.kv_e4m3;
     // chunks per workgroup: a function of the batch geometry ONLY (not of the step: the host-step and the device-step form of
     // one call must chunk alike), 1 while the grid needs every chunk as its own workgroup, up to 8 for large batches (batch 32 x 32
-    // heads at ctx 2048: one workgroup per (sequence, head), no partials and no merge launch at all)
-    int cpw = 1;
-    if constexpr (!std::is_same<KT, T>::value) {   // (e4m3 cache only, see the kernel)
-        while (cpw < 8 && batch * kv_head_num >= 128 * cpw) cpw *= 2;   // >= 256 workgroups per chunk row are kept
-    }
-    int CHUNK, splits;
-#define LLMIE_ATTN_LAUNCH(NWV_, GL_)                                                                                   \
-    do {                                                                                                                \
-        CHUNK = cpw * AttnGeom<KT, HS, NWV_, GL_>::CHUNK;                                                               \
-        splits = (bound + CHUNK - 1) / CHUNK;                                                                           \
-        dim3 grid(splits, kv_head_num, batch);                                                                          \
-        decode_attn_split_kernel<T, HS, REP, NWV_, GL_, KT><<<grid, NWV_ * 64, 0, st>>>(                                \
-            qkv, bias, kc, vc, part, out, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, \
-            tickets, qs, ks.k, ks.v, pg, cpw);                                                                          \
-    } while (0)
-    LLMIE_ATTN_LAUNCH(4, 8);   // 4 waves, 8 K + 8 V loads in flight per lane (8 waves x 8 and 4 x 4 measured slower, round 1)
-#undef LLMIE_ATTN_LAUNCH
-    if (splits > 1 && !tickets) {
-        dim3 cgrid(head_num, batch);
-        decode_attn_combine_kernel<T><<<cgrid, HS < 64 ? 64 : (HS > 256 ? 256 : HS), 0, st>>>(part, out, head_num, HS, CHUNK,
-                                                                                              step, step_dev, max_splits_ws, pg.step_stride,
-                                                                                              max_seq_len, pg.out_x32);
-    }
+    // heads at ctx 2048: one workgroup per (sequence, head), no partials and no merge launch at all); e4m3 cache only, see the kernel
+    p.cpw = 1;
+    if (c.kv_e4m3)
+        while (p.cpw < 8 && c.batch * c.kv_head_num >= 128 * p.cpw) p.cpw *= 2;   // >= 256 workgroups per chunk row are kept
+    const int base = c.kv_e4m3 ? attn_chunk<fp8kv_t>(p.hs) : (c.dtype == LLMIE_F32 ? attn_chunk<float>(p.hs) : attn_chunk<half_t>(p.hs));
+    p.chunk = p.cpw * base;
+    p.grid[0] = (bound + p.chunk - 1) / p.chunk, p.grid[1] = c.kv_head_num, p.grid[2] = c.batch;
+    p.max_splits_ws = (c.max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
+    p.merge = p.grid[0] > 1 && !c.tickets;
+    p.merge_grid[0] = c.head_num, p.merge_grid[1] = c.batch;
+    p.merge_block = p.hs < 64 ? 64 : p.hs;
+    p.workspace_bytes = need;
+    return p;
 }
 
-template <typename T, int HS, typename KT = T>
-static bool dispatch_rep(int rep, const T *qkv, const T *bias, KT *kc, KT *vc, float *part, T *out, int batch,
-                         int head_num, int kv_head_num, int max_seq_len, int step, const int32_t *step_dev,
-                         int max_splits_ws, const float2 *rope, int rot_dim, int32_t *tickets, const QkvSlabs &qs,
-                         KvScale ks, PagedKv pg, hipStream_t st) {
-    switch (rep) {
-        case 1: launch_split<T, HS, 1, KT>(qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, ks, pg, st); return true;
-        case 2: launch_split<T, HS, 2, KT>(qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, ks, pg, st); return true;
-        case 4: launch_split<T, HS, 4, KT>(qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, ks, pg, st); return true;
-        case 8:
-            if constexpr (!std::is_same<KT, T>::value) return false;  // fp8 cache: 16 dims per lane x 8 heads does not fit registers
-            else launch_split<T, HS, 8, KT>(qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, ks, pg, st); return true;
-        default: return false;
+DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
+    if (c.ragged && !c.step_dev) return attn_refusal(DAREF_RAGGED_LENGTHS);
+    if (c.out_x32 && (c.batch > 32 || c.dtype != LLMIE_F16)) return attn_refusal(DAREF_X32);
+    if (c.paged && (c.max_pages <= 0 || c.num_pages <= 0 || static_cast<long long>(c.max_pages) * KV_PAGE < c.max_seq_len))
+        return attn_refusal(DAREF_PAGES);
+    if (c.slabs && (c.mis_wh8 || c.mis_wf || c.mis_slab || c.slab_stride_mod4)) return attn_refusal(DAREF_SLAB_ALIGNMENT);
+    const int rep = c.head_num / c.kv_head_num;
+    const bool aligned = !(c.mis_qkv | c.mis_k | c.mis_v | c.mis_bias);
+    const size_t need = llmie_decoder_mha_workspace_bytes(c.batch, c.head_num, c.head_size, c.max_seq_len);
+    const bool ws_ok = c.workspace && c.workspace_bytes >= need;
+    if (c.kv_e4m3) {
+        // fp16 activations over e4m3 cache bytes: 16 cache elements per 16-byte load (8 lanes per token row at head size 128,
+        // 256-token chunks); head ratio 8 does not fit registers (16 dims per lane x 8 heads); no generic form, and one refusal
+        // for everything -- a short workspace included, which the native cache answers with LLMIE_ERR_WORKSPACE
+        if (c.dtype != LLMIE_F16 || c.tickets) return attn_refusal(DAREF_E4M3_FORM);
+        if (!aligned || !ws_ok || c.batch > 65535 || !c.scales_positive || (rep != 1 && rep != 2 && rep != 4) ||
+            (c.head_size != 128 && c.head_size != 64))
+            return attn_refusal(DAREF_E4M3, need);
+        return plan_attn_split(c, need);
     }
+    // an unaligned call or one past the grid's y / z range has no split form: it runs on the generic kernel unless it asked for
+    // something only the split kernel does
+    const bool geometry = attn_fused_geometry(c);
+    if (aligned && c.batch <= 65535 && c.kv_head_num <= 65535 && geometry)
+        return ws_ok ? plan_attn_split(c, need) : attn_refusal(DAREF_WORKSPACE, need);
+    if (c.paged) return attn_refusal(DAREF_PAGED_GEOMETRY);
+    if (c.slabs) return attn_refusal(DAREF_SLABS_GEOMETRY);
+    // (tickets on a supported geometry that fell through -- unaligned -- are ignored: the generic kernel has no partials)
+    if (c.rope || (c.tickets && !geometry)) return attn_refusal(DAREF_ROPE_GEOMETRY);
+    if (c.ragged || c.out_x32) return attn_refusal(DAREF_RAGGED_GEOMETRY);
+    DecodeAttnPlan p{};
+    p.lds_bytes = sizeof(float) * static_cast<size_t>(c.step_dev ? c.max_seq_len : c.step);   // the logits of one (sequence, head)
+    if (p.lds_bytes > 60 * 1024) return attn_refusal(DAREF_GENERIC_SPAN);
+    p.kind = DA_GENERIC, p.grid[0] = c.head_num, p.grid[1] = c.batch, p.grid[2] = 1;
+    return p;
 }
 
-template <typename T>
-static int decoder_mha_impl(const T *qkv, const T *bias, T *k_cache, T *v_cache, T *out, int layer, int batch,
-                            int head_num, int kv_head_num, int head_size, int max_seq_len, int step,
-                            const int32_t *step_dev, void *workspace, size_t workspace_bytes, const float2 *rope,
-                            int rot_dim, int32_t *tickets, const QkvSlabs &qs, hipStream_t st, PagedKv pg = PagedKv{nullptr, 0, 0, 0},
-                            int num_pages = 0) {
-    const size_t layer_off = pg.table ? static_cast<size_t>(layer) * num_pages * kv_head_num * KV_PAGE * head_size
-                                      : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * head_size;
-    T *kc = k_cache + layer_off, *vc = v_cache + layer_off;
-    const int rep = head_num / kv_head_num;
-    const int max_splits_ws = (max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
-    const bool aligned = ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kc) |
-                           reinterpret_cast<uintptr_t>(vc)) % 16 == 0) && (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
-    bool done = false;
-    if (aligned && batch <= 65535 && kv_head_num <= 65535) {
-        const size_t need = llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len);
-        float *part = static_cast<float *>(workspace);
-        auto ws_ok = [&]() { return workspace && workspace_bytes >= need; };
-        if (head_size == 128 && ws_ok())
-            done = dispatch_rep<T, 128>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, KvScale{1.f, 1.f}, pg, st);
-        else if (head_size == 64 && ws_ok())
-            done = dispatch_rep<T, 64>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, KvScale{1.f, 1.f}, pg, st);
-        else if (head_size == 32 && ws_ok())
-            done = dispatch_rep<T, 32>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, KvScale{1.f, 1.f}, pg, st);
-        else if (head_size == 256 && ws_ok())
-            done = dispatch_rep<T, 256>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step, step_dev, max_splits_ws, rope, rot_dim, tickets, qs, KvScale{1.f, 1.f}, pg, st);
-        if (!done && (head_size == 128 || head_size == 64 || head_size == 32 || head_size == 256) && !ws_ok() &&
-            (rep == 1 || rep == 2 || rep == 4 || rep == 8)) {
-            set_error("decoder_mha: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+int decode_attn_refuse(const DecodeAttnCall &c, const DecodeAttnPlan &p) {
+    const char *fused = "head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}";
+    switch (p.refusal) {
+        case DAREF_RAGGED_LENGTHS: set_error("decoder_mha: a ragged batch needs the device array of context lengths"); return LLMIE_ERR_INVALID_ARG;
+        case DAREF_X32: set_error("decoder_mha: the x32 output image holds at most 32 fp16 rows"); break;
+        case DAREF_PAGES: set_error("decoder_mha: paged KV cache needs max_pages * %d >= max_seq_len and num_pages > 0", KV_PAGE); break;
+        case DAREF_SLAB_ALIGNMENT: set_error("decoder_mha: q/k/v from split-K slabs needs 16-byte aligned slabs and aligned scale vectors"); break;
+        case DAREF_E4M3_FORM: set_error("decoder_mha(fp8 KV): fp16 activations, separate merge kernel only"); break;
+        case DAREF_E4M3:
+            set_error("decoder_mha(fp8 KV): needs head_size 64/128, head ratio 1/2/4, 16-byte aligned buffers, positive scales and "
+                      "the llmie_decoder_mha workspace");
+            break;
+        case DAREF_WORKSPACE:
+            set_error("decoder_mha: workspace too small (%zu < %zu bytes)", c.workspace_bytes, p.workspace_bytes);
             return LLMIE_ERR_WORKSPACE;
-        }
+        case DAREF_PAGED_GEOMETRY: set_error("decoder_mha: the paged KV cache needs %s", fused); break;
+        case DAREF_SLABS_GEOMETRY: set_error("decoder_mha: q/k/v from split-K slabs needs %s", fused); break;
+        case DAREF_ROPE_GEOMETRY: set_error("decoder_mha: fused RoPE / in-launch merge need %s", fused); break;
+        case DAREF_RAGGED_GEOMETRY: set_error("decoder_mha: ragged batches / x32 output need %s", fused); break;
+        case DAREF_GENERIC_SPAN:
+            set_error("decoder_mha: generic path supports at most 15360 tokens (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
+            break;
+        default: set_error("decoder_mha: refused"); break;
     }
-    if (!done && pg.table) {
-        set_error("decoder_mha: the paged KV cache needs head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!done && qs.slab) {
-        set_error("decoder_mha: q/k/v from split-K slabs needs head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!done && rope) {
-        set_error("decoder_mha: fused RoPE needs head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!done && (pg.step_stride || pg.out_x32)) {
-        set_error("decoder_mha: ragged batches / x32 output need head_size in {32,64,128,256} and head_num/kv_head_num in {1,2,4,8}");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (!done) {
-        const int bound = step_dev ? max_seq_len : step;
-        const size_t lds = sizeof(float) * static_cast<size_t>(bound);
-        if (lds > 60 * 1024) {
-            set_error("decoder_mha: generic path supports at most 15360 tokens (head_size=%d, rep=%d)", head_size, rep);
-            return LLMIE_ERR_UNSUPPORTED;
-        }
-        dim3 grid(head_num, batch);
-        decode_attn_generic_kernel<T><<<grid, 256, lds, st>>>(qkv, bias, kc, vc, out, head_num, kv_head_num,
-                                                             head_size, max_seq_len, step, step_dev);
-    }
-    return launch_status("decoder_mha");
+    return LLMIE_ERR_UNSUPPORTED;
 }
 
-// fp16 activations over an e4m3 KV cache [L, batch, kvh, max_seq, hs] bytes (stored = e4m3(x / scale)): same kernel with 16
-// cache elements per 16-byte load (8 lanes per token row, 256-token chunks); head_size 128 or 64, head ratio 1/2/4
-static int decoder_mha_fp8kv(const half_t *qkv, const half_t *bias, uint8_t *k_cache, uint8_t *v_cache, half_t *out, int layer, int batch,
-                             int head_num, int kv_head_num, int head_size, int max_seq_len, int step, const int32_t *step_dev,
-                             void *workspace, size_t workspace_bytes, const float2 *rope, int rot_dim, const QkvSlabs &qs,
-                             KvScale ks, hipStream_t st, PagedKv pg, int num_pages) {
-    const size_t layer_off = pg.table ? static_cast<size_t>(layer) * num_pages * kv_head_num * KV_PAGE * head_size
-                                      : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * head_size;
-    fp8kv_t *kc = reinterpret_cast<fp8kv_t *>(k_cache) + layer_off, *vc = reinterpret_cast<fp8kv_t *>(v_cache) + layer_off;
-    const int rep = head_num / kv_head_num;
-    const int max_splits_ws = (max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
-    const size_t need = llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len);
-    if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kc) | reinterpret_cast<uintptr_t>(vc) |
-         reinterpret_cast<uintptr_t>(bias)) % 16 || !workspace || workspace_bytes < need || batch > 65535 || !(ks.k > 0.f) ||
-        !(ks.v > 0.f) || (rep != 1 && rep != 2 && rep != 4) || (head_size != 128 && head_size != 64)) {
-        set_error("decoder_mha(fp8 KV): needs head_size 64/128, head ratio 1/2/4, 16-byte aligned buffers, positive scales and "
-                  "the llmie_decoder_mha workspace");
-        return LLMIE_ERR_UNSUPPORTED;
+// ---- the launcher: what the kernels read, built once per call ----
+struct DecodeAttnArgs {
+    const void *qkv, *bias;
+    void *kc, *vc, *out;   // kc / vc: this layer's cache (or page pool)
+    float *part;
+    int head_num, kv_head_num, head_size, max_seq_len, step;
+    const int32_t *step_dev;
+    const float2 *rope;
+    int rot_dim;
+    int32_t *tickets;
+    QkvSlabs qs;
+    KvScale ks;
+    PagedKv pg;
+};
+
+template <typename T, int HS, int REP, typename KT> static void launch_split(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    decode_attn_split_kernel<T, HS, REP, 4, 8, KT><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+        static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
+        static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim, a.tickets,
+        a.qs, a.ks.k, a.ks.v, a.pg, p.cpw);
+    if (p.merge)
+        decode_attn_combine_kernel<T><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
+            a.part, static_cast<T *>(a.out), a.head_num, HS, p.chunk, a.step, a.step_dev, p.max_splits_ws, a.pg.step_stride, a.max_seq_len,
+            a.pg.out_x32);
+}
+template <typename T> static void launch_generic(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    decode_attn_generic_kernel<T><<<dim3(p.grid[0], p.grid[1]), 256, p.lds_bytes, st>>>(
+        static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<T *>(a.kc), static_cast<T *>(a.vc), static_cast<T *>(a.out),
+        a.head_num, a.kv_head_num, a.head_size, a.max_seq_len, a.step, a.step_dev);
+}
+// every instantiation of the split kernel: head sizes 32 / 64 / 128 / 256 x head ratios 1 / 2 / 4 / 8 over the native cache, head
+// sizes 64 / 128 x ratios 1 / 2 / 4 over e4m3 bytes (the planner plans nothing else)
+template <typename T, int HS, typename KT> static void launch_split_rep(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    switch (p.rep) {
+        case 1: return launch_split<T, HS, 1, KT>(p, a, st);
+        case 2: return launch_split<T, HS, 2, KT>(p, a, st);
+        case 4: return launch_split<T, HS, 4, KT>(p, a, st);
+        case 8:
+            if constexpr (std::is_same<KT, T>::value) return launch_split<T, HS, 8, KT>(p, a, st);
     }
-    float *part = static_cast<float *>(workspace);
-    bool done;
-    if (head_size == 128)
-        done = dispatch_rep<half_t, 128, fp8kv_t>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step,
-                                                  step_dev, max_splits_ws, rope, rot_dim, nullptr, qs, ks, pg, st);
-    else
-        done = dispatch_rep<half_t, 64, fp8kv_t>(rep, qkv, bias, kc, vc, part, out, batch, head_num, kv_head_num, max_seq_len, step,
-                                                 step_dev, max_splits_ws, rope, rot_dim, nullptr, qs, ks, pg, st);
-    (void)done;
-    return launch_status("decoder_mha(fp8 KV)");
+}
+template <typename T, typename KT> static void launch_split_hs(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    switch (p.hs) {
+        case 128: return launch_split_rep<T, 128, KT>(p, a, st);
+        case 64: return launch_split_rep<T, 64, KT>(p, a, st);
+        case 32:
+            if constexpr (std::is_same<KT, T>::value) return launch_split_rep<T, 32, KT>(p, a, st);
+            break;
+        case 256:
+            if constexpr (std::is_same<KT, T>::value) return launch_split_rep<T, 256, KT>(p, a, st);
+            break;
+    }
+}
+static int launch_decode_attn(const DecodeAttnCall &c, const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    const bool split = p.kind == DA_SPLIT;
+    if (p.e4m3) launch_split_hs<half_t, fp8kv_t>(p, a, st);
+    else if (c.dtype == LLMIE_F32) split ? launch_split_hs<float, float>(p, a, st) : launch_generic<float>(p, a, st);
+    else split ? launch_split_hs<half_t, half_t>(p, a, st) : launch_generic<half_t>(p, a, st);
+    return launch_status(p.e4m3 ? "decoder_mha(fp8 KV)" : "decoder_mha");
 }
 
-// engine entry: same as llmie_decoder_mha with RoPE (table [max_pos][hs/2] of (cos,sin)) fused in front
-int decoder_mha_rope(const void *qkv, const void *qkv_bias, const KvView &kv, void *out, int layer, int batch,
-                     int head_num, int kv_head_num, int head_size, int max_seq_len, const DecodePos &pos,
-                     void *workspace, size_t workspace_bytes, const float2 *rope, int rot_dim, int32_t *tickets,
-                     llmie_dtype dtype, hipStream_t st, const SplitKSlabs *qkv_slabs, const SlabScale *qkv_scale, int out_x32) {
-    void *k_cache = kv.k, *v_cache = kv.v;
-    const int32_t *block_table = kv.block_table, *step_dev = pos.step_dev;
-    const int max_pages = kv.max_pages, num_pages = kv.num_pages, kv_fp8 = kv.fp8, step = pos.step, ragged = pos.ragged;
-    const float k_scale = kv.k_scale, v_scale = kv.v_scale;
-    const PagedKv pg{block_table, max_pages, ragged ? 1 : 0, out_x32 ? 1 : 0};
-    if (ragged && !step_dev) {
-        set_error("decoder_mha: a ragged batch needs the device array of context lengths");
-        return LLMIE_ERR_INVALID_ARG;
-    }
-    if (out_x32 && (batch > 32 || dtype != LLMIE_F16)) {
-        set_error("decoder_mha: the x32 output image holds at most 32 fp16 rows");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (block_table && (max_pages <= 0 || num_pages <= 0 || static_cast<long long>(max_pages) * KV_PAGE < max_seq_len)) {
-        set_error("decoder_mha: paged KV cache needs max_pages * %d >= max_seq_len and num_pages > 0", KV_PAGE);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
+// elements in front of `layer` in a dense cache or a page pool
+static size_t kv_layer_offset(const DecodeAttnShape &g, const KvView &kv, int layer) {
+    return kv.block_table ? static_cast<size_t>(layer) * kv.num_pages * g.kv_head_num * KV_PAGE * g.head_size
+                          : static_cast<size_t>(layer) * g.batch * g.kv_head_num * g.max_seq_len * g.head_size;
+}
+static DecodeAttnArgs decode_attn_args(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer) {
+    const size_t elem = kv.fp8 ? 1 : (g.dtype == LLMIE_F32 ? sizeof(float) : sizeof(half_t));
+    const size_t layer_bytes = kv_layer_offset(g, kv, layer) * elem;
     QkvSlabs qs{nullptr, 0, 0, SlabScale{nullptr, nullptr, nullptr}};
-    const SlabScale no_scale{nullptr, nullptr, nullptr};
-    const SlabScale &qsc = qkv_scale ? *qkv_scale : no_scale;
-    if (qkv_slabs && (reinterpret_cast<uintptr_t>(qsc.wh) % 8 || reinterpret_cast<uintptr_t>(qsc.wf) % 16 ||
-                      reinterpret_cast<uintptr_t>(qkv_slabs->slab) % 16 ||
-                      (static_cast<size_t>(qkv_slabs->M) * qkv_slabs->N) % 4)) {
-        set_error("decoder_mha: q/k/v from split-K slabs needs 16-byte aligned slabs and aligned scale vectors");
-        return LLMIE_ERR_UNSUPPORTED;
+    if (io.qkv_slabs)
+        qs = QkvSlabs{io.qkv_slabs->slab, io.qkv_slabs->KS, static_cast<size_t>(io.qkv_slabs->M) * io.qkv_slabs->N,
+                      io.qkv_scale ? *io.qkv_scale : SlabScale{nullptr, nullptr, nullptr}};
+    return DecodeAttnArgs{io.qkv, io.qkv_bias, static_cast<char *>(kv.k) + layer_bytes, static_cast<char *>(kv.v) + layer_bytes, io.out,
+                          static_cast<float *>(io.workspace), g.head_num, g.kv_head_num, g.head_size, g.max_seq_len, pos.step, pos.step_dev,
+                          io.rope, io.rot_dim, io.tickets, qs, KvScale{kv.k_scale, kv.v_scale},
+                          PagedKv{kv.block_table, kv.max_pages, pos.ragged ? 1 : 0, io.out_x32 ? 1 : 0}};
+}
+static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos,
+                                       const DecodeAttnArgs &a) {
+    DecodeAttnCall c{};
+    c.dtype = g.dtype, c.kv_e4m3 = kv.fp8 != 0, c.scales_positive = kv.k_scale > 0.f && kv.v_scale > 0.f;
+    c.head_size = g.head_size, c.head_num = g.head_num, c.kv_head_num = g.kv_head_num, c.batch = g.batch, c.max_seq_len = g.max_seq_len;
+    c.step = pos.step, c.step_dev = pos.step_dev != nullptr, c.ragged = pos.ragged != 0;
+    c.bias = io.qkv_bias != nullptr, c.rope = io.rope != nullptr, c.tickets = io.tickets != nullptr, c.slabs = io.qkv_slabs != nullptr;
+    c.paged = kv.block_table != nullptr, c.out_x32 = io.out_x32 != 0, c.max_pages = kv.max_pages, c.num_pages = kv.num_pages;
+    c.mis_qkv = mis16(a.qkv), c.mis_bias = mis16(a.bias), c.mis_k = mis16(a.kc), c.mis_v = mis16(a.vc);
+    if (c.slabs) {
+        c.mis_slab = mis16(a.qs.slab), c.mis_wf = mis16(a.qs.sc.wf), c.mis_wh8 = mis16(a.qs.sc.wh) % 8;
+        c.slab_stride_mod4 = static_cast<unsigned>(a.qs.stride % 4);
     }
-    if (qkv_slabs) qs = QkvSlabs{qkv_slabs->slab, qkv_slabs->KS, static_cast<size_t>(qkv_slabs->M) * qkv_slabs->N, qsc};
-    if (kv_fp8) {
-        if (dtype != LLMIE_F16 || tickets) {
-            set_error("decoder_mha(fp8 KV): fp16 activations, separate merge kernel only");
-            return LLMIE_ERR_UNSUPPORTED;
-        }
-        return decoder_mha_fp8kv((const half_t *)qkv, (const half_t *)qkv_bias, (uint8_t *)k_cache, (uint8_t *)v_cache, (half_t *)out,
-                                 layer, batch, head_num, kv_head_num, head_size, max_seq_len, step, step_dev, workspace,
-                                 workspace_bytes, rope, rot_dim, qs, KvScale{k_scale, v_scale}, st, pg, num_pages);
+    c.workspace = io.workspace != nullptr, c.workspace_bytes = io.workspace_bytes;
+    return c;
+}
+
+int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st) {
+    const DecodeAttnArgs a = decode_attn_args(g, io, kv, pos, layer);
+    const DecodeAttnCall c = decode_attn_call(g, io, kv, pos, a);
+    const DecodeAttnPlan p = plan_decode_attn(c);
+    if (p.kind == DA_REFUSED) return decode_attn_refuse(c, p);
+    return launch_decode_attn(c, p, a, st);
+}
+
+// the argument checks of every entry, in front of the plan
+static int decode_attn_validate(const char *who, const DecodeAttnShape &g, const DecodePos &pos, bool pointers, int layer, bool rope, int rot_dim) {
+    LLMIE_REQUIRE(pointers && (!pos.ragged || pos.step_dev), "%s: NULL pointer", who);
+    LLMIE_REQUIRE(layer >= 0 && g.batch > 0 && g.head_num > 0 && g.kv_head_num > 0 && g.head_size > 0 && g.max_seq_len > 0, "%s: bad shape", who);
+    LLMIE_REQUIRE(g.head_num % g.kv_head_num == 0, "%s: kv_head_num must divide head_num", who);
+    LLMIE_REQUIRE(pos.step_dev || (pos.step >= 1 && pos.step <= g.max_seq_len), "%s: step %d outside [1, max_seq_len=%d]", who, pos.step,
+                  g.max_seq_len);
+    LLMIE_REQUIRE(!rope || (rot_dim > 0 && rot_dim % 2 == 0), "%s: bad rotary_dim", who);
+    if (g.dtype != LLMIE_F32 && g.dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: dtype %d", who, (int)g.dtype);
+    return LLMIE_OK;
+}
+// a public entry: validate, then as the engine's calls
+static int decode_attn_entry(const char *who, const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer,
+                             llmie_stream stream) {
+    const int rc = decode_attn_validate(who, g, pos, io.qkv && kv.k && kv.v && io.out, layer, io.rope != nullptr, io.rot_dim);
+    return rc != LLMIE_OK ? rc : decoder_mha_rope(g, io, kv, pos, layer, as_stream(stream));
+}
+
+// "split f16 hs128 rep4 kv=e4m3 cpw2 chunk512 grid 4x8x16 merge 32x16/128" (merge: grid / block, "in-launch" by tickets, "none"
+// for one split) or "generic f16 grid 32x2 lds 1028"
+static void decode_attn_plan_text(const DecodeAttnCall &c, const DecodeAttnPlan &p, char *text, size_t n) {
+    const char *dt = c.dtype == LLMIE_F32 ? "f32" : "f16";
+    if (p.kind == DA_GENERIC) {
+        snprintf(text, n, "generic %s grid %dx%d lds %zu", dt, p.grid[0], p.grid[1], p.lds_bytes);
+        return;
     }
-    if (dtype == LLMIE_F32)
-        return decoder_mha_impl<float>((const float *)qkv, (const float *)qkv_bias, (float *)k_cache, (float *)v_cache,
-                                       (float *)out, layer, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                       step_dev, workspace, workspace_bytes, rope, rot_dim, tickets, qs, st, pg, num_pages);
-    return decoder_mha_impl<half_t>((const half_t *)qkv, (const half_t *)qkv_bias, (half_t *)k_cache, (half_t *)v_cache,
-                                    (half_t *)out, layer, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                    step_dev, workspace, workspace_bytes, rope, rot_dim, tickets, qs, st, pg, num_pages);
+    const int k = snprintf(text, n, "split %s hs%d rep%d kv=%s cpw%d chunk%d grid %dx%dx%d merge ", dt, p.hs, p.rep, p.e4m3 ? "e4m3" : dt, p.cpw,
+                           p.chunk, p.grid[0], p.grid[1], p.grid[2]);
+    if (p.merge) snprintf(text + k, n - k, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
+    else snprintf(text + k, n - k, "%s", p.grid[0] > 1 ? "in-launch" : "none");
 }
 
 }  // namespace llmie
@@ -913,21 +961,9 @@ extern "C" int llmie_decoder_mha(const void *qkv, const void *qkv_bias, void *k_
                                  int layer, int batch, int head_num, int kv_head_num, int head_size,
                                  int max_seq_len, int step, const int32_t *step_dev, void *workspace,
                                  size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
-    LLMIE_REQUIRE(qkv && k_cache && v_cache && out, "decoder_mha: NULL pointer");
-    LLMIE_REQUIRE(layer >= 0 && batch > 0 && head_num > 0 && kv_head_num > 0 && head_size > 0 && max_seq_len > 0,
-                  "decoder_mha: bad shape");
-    LLMIE_REQUIRE(head_num % kv_head_num == 0, "decoder_mha: kv_head_num must divide head_num");
-    LLMIE_REQUIRE(step_dev || (step >= 1 && step <= max_seq_len), "decoder_mha: step %d outside [1, max_seq_len=%d]",
-                  step, max_seq_len);
-    if (dtype == LLMIE_F32)
-        return decoder_mha_impl<float>((const float *)qkv, (const float *)qkv_bias, (float *)k_cache, (float *)v_cache,
-                                       (float *)out, layer, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                       step_dev, workspace, workspace_bytes, nullptr, 0, nullptr, QkvSlabs{nullptr, 0, 0, SlabScale{nullptr, nullptr, nullptr}}, as_stream(stream));
-    if (dtype == LLMIE_F16)
-        return decoder_mha_impl<half_t>((const half_t *)qkv, (const half_t *)qkv_bias, (half_t *)k_cache,
-                                        (half_t *)v_cache, (half_t *)out, layer, batch, head_num, kv_head_num, head_size,
-                                        max_seq_len, step, step_dev, workspace, workspace_bytes, nullptr, 0, nullptr, QkvSlabs{nullptr, 0, 0, SlabScale{nullptr, nullptr, nullptr}}, as_stream(stream));
-    LLMIE_UNSUPPORTED("decoder_mha: dtype %d", (int)dtype);
+    return decode_attn_entry("decoder_mha", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, nullptr, 0, nullptr, nullptr, nullptr, 0},
+                             kv_dense(k_cache, v_cache), DecodePos{step, step_dev, 0}, layer, stream);
 }
 
 extern "C" int llmie_decoder_mha_rope(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out,
@@ -935,23 +971,10 @@ extern "C" int llmie_decoder_mha_rope(const void *qkv, const void *qkv_bias, voi
                                       int max_seq_len, int step, const int32_t *step_dev, void *workspace,
                                       size_t workspace_bytes, const void *rope_table, int rotary_dim, int32_t *tickets,
                                       llmie_dtype dtype, llmie_stream stream) {
-    LLMIE_REQUIRE(qkv && k_cache && v_cache && out, "decoder_mha_rope: NULL pointer");
-    LLMIE_REQUIRE(layer >= 0 && batch > 0 && head_num > 0 && kv_head_num > 0 && head_size > 0 && max_seq_len > 0,
-                  "decoder_mha_rope: bad shape");
-    LLMIE_REQUIRE(head_num % kv_head_num == 0, "decoder_mha_rope: kv_head_num must divide head_num");
-    LLMIE_REQUIRE(step_dev || (step >= 1 && step <= max_seq_len), "decoder_mha_rope: step %d outside [1, max_seq_len=%d]",
-                  step, max_seq_len);
-    LLMIE_REQUIRE(!rope_table || (rotary_dim > 0 && rotary_dim % 2 == 0), "decoder_mha_rope: bad rotary_dim");
-    if (dtype != LLMIE_F32 && dtype != LLMIE_F16) LLMIE_UNSUPPORTED("decoder_mha_rope: dtype %d", (int)dtype);
-    const int rep = head_num / kv_head_num;
-    const bool hs_ok = head_size == 32 || head_size == 64 || head_size == 128 || head_size == 256;
-    const bool rep_ok = rep == 1 || rep == 2 || rep == 4 || rep == 8;
-    if ((rope_table || tickets) && !(hs_ok && rep_ok))
-        LLMIE_UNSUPPORTED("decoder_mha_rope: fused RoPE / in-launch merge need head_size in {32,64,128,256} and "
-                          "head_num/kv_head_num in {1,2,4,8}");
-    return decoder_mha_rope(qkv, qkv_bias, kv_dense(k_cache, v_cache), out, layer, batch, head_num, kv_head_num, head_size,
-                            max_seq_len, DecodePos{step, step_dev, 0}, workspace, workspace_bytes,
-                            static_cast<const float2 *>(rope_table), rotary_dim, tickets, dtype, as_stream(stream));
+    return decode_attn_entry("decoder_mha_rope", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim,
+                                          tickets, nullptr, nullptr, 0},
+                             kv_dense(k_cache, v_cache), DecodePos{step, step_dev, 0}, layer, stream);
 }
 
 // Ragged batch: RoPE position, append slot and attention span per sequence (ctx_len_dev[b] includes this step's token);
@@ -961,13 +984,37 @@ extern "C" int llmie_decoder_mha_ragged(const void *qkv, const void *qkv_bias, v
                                         const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
                                         int rotary_dim, const int32_t *block_table, int max_pages, int num_pages,
                                         llmie_dtype dtype, llmie_stream stream) {
-    LLMIE_REQUIRE(qkv && k_cache && v_cache && out && ctx_len_dev, "decoder_mha_ragged: NULL pointer");
-    LLMIE_REQUIRE(layer >= 0 && batch > 0 && head_num > 0 && kv_head_num > 0 && head_size > 0 && max_seq_len > 0,
-                  "decoder_mha_ragged: bad shape");
-    LLMIE_REQUIRE(head_num % kv_head_num == 0, "decoder_mha_ragged: kv_head_num must divide head_num");
-    LLMIE_REQUIRE(!rope_table || (rotary_dim > 0 && rotary_dim % 2 == 0), "decoder_mha_ragged: bad rotary_dim");
-    if (dtype != LLMIE_F32 && dtype != LLMIE_F16) LLMIE_UNSUPPORTED("decoder_mha_ragged: dtype %d", (int)dtype);
-    return decoder_mha_rope(qkv, qkv_bias, KvView{k_cache, v_cache, block_table, max_pages, num_pages, 0, 1.f, 1.f}, out, layer, batch,
-                            head_num, kv_head_num, head_size, max_seq_len, DecodePos{-1, ctx_len_dev, 1}, workspace, workspace_bytes,
-                            static_cast<const float2 *>(rope_table), rotary_dim, nullptr, dtype, as_stream(stream));
+    return decode_attn_entry("decoder_mha_ragged", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim,
+                                          nullptr, nullptr, nullptr, 0},
+                             KvView{k_cache, v_cache, block_table, max_pages, num_pages, 0, 1.f, 1.f}, DecodePos{-1, ctx_len_dev, 1}, layer,
+                             stream);
+}
+
+extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                              int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                              unsigned long long residues, long long workspace_bytes, int *status) {
+    static thread_local char text[96];
+    static const int32_t some_position = 0;   // stands for the device position: never read
+    auto res = [&](int i) { return static_cast<unsigned>((residues >> (4 * i)) & 15u); };
+    const DecodeAttnShape g{batch, head_num, kv_head_num, head_size, max_seq_len, dtype};
+    const DecodePos pos{step, (forms & LLMIE_ATTN_STEP_DEV) ? &some_position : nullptr, (forms & LLMIE_ATTN_RAGGED) != 0};
+    int rc = decode_attn_validate("decoder_mha_plan", g, pos, true, 0, (forms & LLMIE_ATTN_ROPE) != 0, 2);
+    if (rc == LLMIE_OK) {
+        DecodeAttnCall c{};
+        c.dtype = dtype, c.kv_e4m3 = kv_e4m3 != 0, c.scales_positive = !(forms & LLMIE_ATTN_BAD_SCALES);
+        c.head_size = head_size, c.head_num = head_num, c.kv_head_num = kv_head_num, c.batch = batch, c.max_seq_len = max_seq_len;
+        c.step = step, c.step_dev = pos.step_dev != nullptr, c.ragged = pos.ragged != 0;
+        c.bias = (forms & LLMIE_ATTN_BIAS) != 0, c.rope = (forms & LLMIE_ATTN_ROPE) != 0, c.tickets = (forms & LLMIE_ATTN_TICKETS) != 0;
+        c.slabs = (forms & LLMIE_ATTN_SLABS) != 0, c.paged = (forms & LLMIE_ATTN_PAGED) != 0, c.out_x32 = (forms & LLMIE_ATTN_X32) != 0;
+        c.max_pages = max_pages, c.num_pages = num_pages;
+        c.mis_qkv = res(0), c.mis_bias = c.bias ? res(1) : 0, c.mis_k = res(2), c.mis_v = res(3);
+        if (c.slabs) c.mis_slab = res(4), c.mis_wf = res(5), c.mis_wh8 = res(6) % 8, c.slab_stride_mod4 = res(7) % 4;
+        c.workspace = workspace_bytes >= 0, c.workspace_bytes = c.workspace ? static_cast<size_t>(workspace_bytes) : 0;
+        const DecodeAttnPlan p = plan_decode_attn(c);
+        if (p.kind == DA_REFUSED) rc = decode_attn_refuse(c, p);
+        else decode_attn_plan_text(c, p, text, sizeof(text));
+    }
+    if (status) *status = rc;
+    return rc == LLMIE_OK ? text : nullptr;
 }

@@ -733,11 +733,14 @@ struct DecodeStep {
     bool fp8;
     llmie_dtype dt;
 
-    // attention with RoPE, bias and the KV append fused in front; out_x32: `out` is the x32 image of the packed sequences
+    // attention with bias, the KV append and RoPE (rope = false: already applied) fused in front; out_x32: `out` is the x32 image of
+    // the packed sequences
     int attention(const void *qkv, const void *qkv_bias, void *out, int layer, const SplitKSlabs *qkv_slabs = nullptr,
-                  const SlabScale *qkv_scale = nullptr, int out_x32 = 0) const {
-        return decoder_mha_rope(qkv, qkv_bias, kv, out, layer, batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, pos, dec->attn_ws,
-                                dec->attn_ws_bytes, dec->rope_table, c.rotary_dim, nullptr, dt, st, qkv_slabs, qkv_scale, out_x32);
+                  const SlabScale *qkv_scale = nullptr, int out_x32 = 0, bool rope = true) const {
+        return decoder_mha_rope(DecodeAttnShape{batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, dt},
+                                DecodeAttnIo{qkv, qkv_bias, out, dec->attn_ws, dec->attn_ws_bytes, rope ? dec->rope_table : nullptr,
+                                             rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32},
+                                kv, pos, layer, st);
     }
 
     // ---- fused fp16 decode path (batch <= 8): 5 launches per layer ----
@@ -959,9 +962,7 @@ int DecodeStep::unfused() const {
             TIMED(LLMIE_OP_ROPE, llmie_rope_decode(dec->qkv, batch, c.head_num, c.kv_head_num, c.head_size, pos.step, pos.step_dev,
                                                    c.rotary_dim, c.rotary_base, dt, stream));
             // :108 fused masked MHA with KV append
-            TIMED(LLMIE_OP_MHA, llmie_decoder_mha(dec->qkv, w.qkv.bias, kv.k, kv.v, dec->mha, l, batch, c.head_num,
-                                                  c.kv_head_num, c.head_size, c.max_seq_len, pos.step, pos.step_dev, dec->attn_ws,
-                                                  dec->attn_ws_bytes, dt, stream));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l, nullptr, nullptr, 0, false));
         }
         // :131 output projection (no bias here: the fused norm below adds o.bias, self_decoder.cpp:92-98)
         TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, dec->mha, w.o, h, batch, H, H, false, nullptr, false, stream));

@@ -206,15 +206,63 @@ struct DecodePos {
     const int32_t *step_dev;
     int ragged;
 };
-// decode attention with optional RoPE (rope may be null) fused in front (rope = [max_pos][head_size/2] (cos,sin) table); attention_decode.hip
-int decoder_mha_rope(const void *qkv, const void *qkv_bias, const KvView &kv, void *out, int layer, int batch,
-                     int head_num, int kv_head_num, int head_size, int max_seq_len, const DecodePos &pos,
-                     void *workspace, size_t workspace_bytes, const float2 *rope, int rot_dim,
-                     int32_t *tickets /* [batch,kvh] zeroed arrival counters: in-launch merge; null = merge kernel */,
-                     llmie_dtype dtype, hipStream_t st,
-                     const SplitKSlabs *qkv_slabs = nullptr /* q/k/v read from the QKV projection's split-K slabs (qkv unused) */,
-                     const SlabScale *qkv_scale = nullptr,
-                     int out_x32 = 0 /* out is the x32 activation image (batch <= 32) instead of row-major [batch, H] */);
+// ---- decode attention (attention_decode.hip): one pure host planner decides the launch, one launcher runs the plan ----
+enum DecodeAttnKind : int { DA_REFUSED = 0, DA_SPLIT, DA_GENERIC };
+enum DecodeAttnRefusal : int {
+    DAREF_NONE = 0, DAREF_RAGGED_LENGTHS, DAREF_X32, DAREF_PAGES, DAREF_SLAB_ALIGNMENT, DAREF_E4M3_FORM, DAREF_E4M3, DAREF_WORKSPACE,
+    DAREF_PAGED_GEOMETRY, DAREF_SLABS_GEOMETRY, DAREF_ROPE_GEOMETRY, DAREF_RAGGED_GEOMETRY, DAREF_GENERIC_SPAN,
+};
+// One decode attention call as the planner sees it: geometry, position form, which optional operands are there, how far each
+// pointer is from 16-byte alignment (address % 16 AFTER the layer offset; 0 for a null pointer), and the caller's scratch.
+struct DecodeAttnCall {
+    llmie_dtype dtype;                 // activations (and the native cache)
+    bool kv_e4m3, scales_positive;     // e4m3 cache bytes; both of its scales > 0
+    int head_size, head_num, kv_head_num, batch, max_seq_len;
+    int step;                          // host position (used when !step_dev)
+    bool step_dev, ragged;             // *step_dev / one context length per sequence
+    bool bias, rope, tickets, slabs, paged, out_x32;
+    int max_pages, num_pages;          // paged
+    unsigned mis_qkv, mis_bias, mis_k, mis_v;
+    unsigned mis_slab, mis_wf, mis_wh8, slab_stride_mod4;   // slabs: slab % 16, wf % 16, wh % 8, (M * N) % 4
+    bool workspace;
+    size_t workspace_bytes;
+};
+struct DecodeAttnPlan {
+    int kind, refusal;                 // DecodeAttnKind, DecodeAttnRefusal of DA_REFUSED
+    // DA_SPLIT: the instantiation decode_attn_split_kernel<T, hs, rep, 4, 8, e4m3 ? fp8kv_t : T>, chunks per workgroup, tokens per
+    // workgroup (cpw chunks), grid (splits, kv heads, batch), partial slots per (sequence, head), the merge launch (none: one
+    // split, or the in-launch merge by tickets)
+    int hs, rep;
+    bool e4m3;
+    int cpw, chunk, grid[3], max_splits_ws;
+    bool merge;
+    int merge_grid[2], merge_block;
+    // DA_GENERIC: grid (heads, batch), dynamic LDS
+    size_t lds_bytes;
+    size_t workspace_bytes;            // what the kind needs of the caller's scratch
+};
+DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c);
+int decode_attn_refuse(const DecodeAttnCall &c, const DecodeAttnPlan &p);   // sets the refusal's error text, returns its error code
+struct DecodeAttnShape {
+    int batch, head_num, kv_head_num, head_size, max_seq_len;
+    llmie_dtype dtype;
+};
+// operands of a call beside the cache and the position.  rope: [max_pos][head_size/2] (cos,sin) table fused in front, or null;
+// tickets: [batch, kvh] zeroed arrival counters = in-launch merge, null = merge kernel; qkv_slabs: q/k/v are read from the QKV
+// projection's split-K slabs (qkv unused) with qkv_scale; out_x32: out is the x32 activation image (batch <= 32), not [batch, H]
+struct DecodeAttnIo {
+    const void *qkv, *qkv_bias;
+    void *out, *workspace;
+    size_t workspace_bytes;
+    const float2 *rope;
+    int rot_dim;
+    int32_t *tickets;
+    const SplitKSlabs *qkv_slabs;
+    const SlabScale *qkv_scale;
+    int out_x32;
+};
+// decode attention of one layer with bias, RoPE and the KV append fused in front: plan, refuse or launch
+int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st);
 
 // fused tail of a decode step (topk_sampling.hip): round 1 of the top-k alone, and round 2 + sampling (+ the next step's input
 // embedding into next_hidden, + *step_dev += 1 by the last row to finish; `ticket` = one zeroed word) in one launch
