@@ -42,7 +42,9 @@ extern "C" {
  *      workspace (NULL -> LLMIE_ERR_UNSUPPORTED).  A version-1 consumer would pass its stream where the slab pointer goes.
  *   3  round 3: additions only are listed at the entries they concern (int8 / int4 weight-only prefill, decoder config flags,
  *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params; token scoring:
- *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan). */
+ *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan; masks, logit bias,
+ *      stop sets and top-N log-probabilities in the sampler: llmie_sampling_ext, llmie_sample_logits_ext,
+ *      llmie_lm_head_sample_ext). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -311,6 +313,63 @@ int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sa
                         int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
                         int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
                         size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition).  llmie_sample_logits with four more per-request controls, each read from device memory inside the same
+ * launch (a captured graph picks up new contents on replay): an allowed-token bit mask (constrained decoding), a logit bias
+ * list, a set of stop tokens with a minimum step, and the top-N alternatives of the row.  ext == NULL, or a struct with every
+ * pointer NULL and top_n == 0, IS llmie_sample_logits: the same launch and the same bits.  Otherwise the numbered steps of
+ * llmie_sample_logits are extended as follows (V = vocab, `step` = the value the Philox seed uses: *step_dev or the argument):
+ *   0a bias: for every id of bias_ids[b, 0..bias_len[b]) (bias_len clamped to [0, bias_stride]) l_t <- l_t + bias, one plain
+ *      fp32 add, applied ONCE per distinct id, before the penalties of step 1.  Ids outside [0, V) and entries whose value is
+ *      NaN or +INFINITY are ignored as if they were absent; of the remaining entries that name one id the LAST of the list
+ *      wins (whatever the thread order).  A value of -INFINITY bans the token: it is excluded (0b).
+ *   0b mask: a token is EXCLUDED if the row is constrained and the token's bit is clear, if it is banned, or if
+ *      step < min_step[b] and it is end_id or one of stop_ids[b, 0..stop_len[b]).  An excluded token is treated everywhere as a
+ *      NaN logit is: it cannot be the greedy pick, does not count as valid (top_k clamps to the valid count), has no mass and
+ *      cannot be drawn.  A row with no token left emits end_id and sets finished (the rule for a row without a valid token).
+ *      Row b is constrained by mask row m = (mask_index ? mask_index[b] : b) if allowed_mask != NULL and 0 <= m < mask_rows;
+ *      token v is allowed iff bit (v % 32) of word allowed_mask[m * mask_stride + v / 32] is set; bits at and past V are ignored.
+ *   8  stops: finished[b] = (pick == end_id) || pick is one of stop_ids[b, 0..stop_len[b]) (stop_len clamped to
+ *      [0, stop_stride]); seq_len and the history append are those of llmie_sample_logits.
+ * Reporting is of the model, not of the controls.  out_logprob stays log_softmax(raw logits)[pick].  out_top_ids[b, 0..top_n)
+ * are the top_n largest RAW logits of the row in llmie_topk's order (value descending, ties -> lower id, -0 == +0, NaN
+ * excluded), whatever the mask, bias, penalties, temperature and truncation are; out_top_logprobs[b, i] is their raw
+ * log-softmax (value - log-sum-exp of the raw row).  Entries past the row's count of non-NaN logits hold id -1 and -INFINITY.
+ * Comparing out_logprob with out_top_logprobs[b, 0] shows what a constraint cost.
+ * Determinism and batch invariance are those of llmie_sample_logits: same inputs, same bits; a row's outputs (top-N
+ * included) depend neither on its slot nor on the other rows.
+ * Refused on the host before any launch.  LLMIE_ERR_INVALID_ARG: a negative stride or top_n; one of bias_ids / bias_vals /
+ * bias_len without the other two; stop_ids without stop_len or the reverse; allowed_mask with mask_stride < ceil(V / 32) or
+ * mask_rows < 1, or with mask_index == NULL and mask_rows < batch; mask_index without allowed_mask; top_n > 0 without both
+ * outputs.  LLMIE_ERR_UNSUPPORTED: bias_stride, stop_stride or top_n above its LLMIE_SAMPLE_MAX_*.  (min_step alone is
+ * legal: it then holds back end_id.)
+ * Workspace, launch count (one), no allocation, no synchronisation, capture: as llmie_sample_logits (the same workspace query).
+ * A mask row is loaded 16 bytes at a time where allowed_mask and mask_stride keep its rows 16-byte aligned. */
+#define LLMIE_SAMPLE_MAX_BIAS   1024
+#define LLMIE_SAMPLE_MAX_STOPS  16
+#define LLMIE_SAMPLE_MAX_TOP_N  32      /* llmie_topk's bound on K */
+typedef struct {                 /* host struct; every pointer is a DEVICE pointer and may be NULL (= that control is off) */
+    const uint32_t *allowed_mask;   /* [mask_rows, mask_stride] words; token v is allowed iff bit (v % 32) of word v / 32 is set */
+    int mask_stride;                /* words per mask row, >= ceil(vocab / 32); bits at and past `vocab` are ignored */
+    int mask_rows;
+    const int32_t *mask_index;      /* [batch]: which mask row sequence b uses; < 0 or >= mask_rows: unconstrained.
+                                       NULL: row b uses mask row b (mask_rows >= batch) */
+    const int32_t *bias_ids;        /* [batch, bias_stride] */
+    const float   *bias_vals;       /* [batch, bias_stride] */
+    const int32_t *bias_len;        /* [batch], clamped on the device to [0, bias_stride] */
+    int bias_stride;                /* <= LLMIE_SAMPLE_MAX_BIAS */
+    const int32_t *stop_ids;        /* [batch, stop_stride] */
+    const int32_t *stop_len;        /* [batch], clamped to [0, stop_stride] */
+    int stop_stride;                /* <= LLMIE_SAMPLE_MAX_STOPS */
+    const int32_t *min_step;        /* [batch]: while step < min_step[b], end_id and the row's stop ids cannot be picked */
+    int top_n;                      /* 0 .. LLMIE_SAMPLE_MAX_TOP_N */
+    int32_t *out_top_ids;           /* [batch, top_n] */
+    float   *out_top_logprobs;      /* [batch, top_n] */
+} llmie_sampling_ext;
+int llmie_sample_logits_ext(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
+                            int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                            int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                            size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream, const llmie_sampling_ext *ext);
 
 /* ABI 3 (an addition).  Score given tokens: RMSNorm + LM head + log-softmax over `rows` hidden states at once, for prompt
  * log-probabilities ("echo + logprobs"), perplexity and ranking by likelihood.  No reference launcher: the reference computes
@@ -583,6 +642,15 @@ int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *fi
                                 int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev, int end_id,
                                 const void *embed_table, void *next_hidden, int advance_step, void *workspace, size_t workspace_bytes,
                                 llmie_stream stream);
+
+/* ABI 3 (an addition).  llmie_lm_head_sample_params with the controls of llmie_sample_logits_ext in its sampler launch (still
+ * one launch behind the LM head).  ext == NULL or an empty struct: llmie_lm_head_sample_params itself. */
+int llmie_lm_head_sample_ext(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                             llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev, int32_t *history,
+                             int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                             int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev, int end_id,
+                             const void *embed_table, void *next_hidden, int advance_step, void *workspace, size_t workspace_bytes,
+                             llmie_stream stream, const llmie_sampling_ext *ext);
 
 /* Per-kernel timing of the engine (eager launches only, never inside graph capture): between
  * profile_begin and profile_end every kernel the engine launches is bracketed by hipEvents

@@ -98,10 +98,13 @@ _SIGS = {
     "llmie_advance_step": [_vp, _vp],
     "llmie_sample_logits_workspace_bytes": [_i, _i],
     "llmie_sample_logits": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _vp],
+    "llmie_sample_logits_ext": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _vp, _vp],
     "llmie_score_tokens_workspace_bytes": [_i, _i, _i],
     "llmie_score_tokens": [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp],
     "llmie_lm_head_sample_params": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp,
                                     _vp, _i, _vp, _sz, _vp],
+    "llmie_lm_head_sample_ext": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp,
+                                 _vp, _i, _vp, _sz, _vp, _vp],
     "llmie_decoder_forward_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "llmie_decoder_prefill_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
     "llmie_kv_pages_copy": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -466,16 +469,132 @@ def _sample_ws(workspace, batch, vocab, device):
     return workspace, workspace.numel() * workspace.element_size()
 
 
+SAMPLE_MAX_BIAS, SAMPLE_MAX_STOPS, SAMPLE_MAX_TOP_N = 1024, 16, 32  # LLMIE_SAMPLE_MAX_*
+
+
+class SamplingExt(C.Structure):
+    """llmie_sampling_ext (include/llmie.h): a host struct of device pointers"""
+    _fields_ = [("allowed_mask", _vp), ("mask_stride", _i), ("mask_rows", _i), ("mask_index", _vp), ("bias_ids", _vp),
+                ("bias_vals", _vp), ("bias_len", _vp), ("bias_stride", _i), ("stop_ids", _vp), ("stop_len", _vp),
+                ("stop_stride", _i), ("min_step", _vp), ("top_n", _i), ("out_top_ids", _vp), ("out_top_logprobs", _vp)]
+
+
+class SamplingExtArrays:
+    """What sampling_ext() returns: the device arrays of one llmie_sampling_ext (kept alive here; None where a control is off)
+    and the struct that points at them.  mask (int32 words [rows, stride]), mask_index, bias_ids / bias_vals / bias_len,
+    stop_ids / stop_len and min_step can be rewritten in place -- a captured graph reads them on replay.  top_ids /
+    top_logprobs [batch, top_n] receive the alternatives (None when top_n == 0)."""
+
+    def __init__(self):
+        self.mask = self.mask_index = self.bias_ids = self.bias_vals = self.bias_len = None
+        self.stop_ids = self.stop_len = self.min_step = self.top_ids = self.top_logprobs = None
+        self.struct = SamplingExt()
+
+
+def pack_token_mask(allowed, stride=None):
+    """bool array-like [rows, vocab] -> numpy uint32 words [rows, stride]: bit v % 32 of word v / 32 is token v"""
+    import numpy as np
+    a = np.asarray(allowed, dtype=bool)
+    rows, V = a.shape
+    words = (V + 31) // 32
+    stride = words if stride is None else stride
+    if stride < words:
+        raise LlmieError("pack_token_mask: stride %d below the %d words of %d tokens" % (stride, words, V))
+    bits = np.zeros((rows, stride * 32), dtype=bool)
+    bits[:, :V] = a
+    return np.packbits(bits.reshape(rows, stride, 32), axis=-1, bitorder="little").view("<u4").reshape(rows, stride)
+
+
+def _i32(x, device):
+    import numpy as np
+    import torch
+    if isinstance(x, torch.Tensor):
+        return x.to(device=device, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64).astype(np.int32))).to(device)
+
+
+def sampling_ext(batch, vocab, masks=None, mask_index=None, bias=None, stops=None, min_step=None, top_n=0, device="cuda"):
+    """Build the device arrays of a llmie_sampling_ext for `batch` rows over `vocab` tokens (-> SamplingExtArrays).
+    masks: bool [rows, vocab] (packed here), or words [rows, stride >= ceil(vocab / 32)] as a numpy uint32 / int32 array or an
+    int32 tensor.  mask_index: [batch] ints, None = row b uses mask row b.  bias: per row a list of (id, value) pairs (or a
+    dict).  stops: per row a list of ids.  min_step: [batch] ints.  top_n: alternatives to return per row."""
+    import numpy as np
+    import torch
+    x = SamplingExtArrays()
+    e = x.struct
+    if masks is not None:
+        if isinstance(masks, torch.Tensor):
+            if masks.dtype == torch.bool:
+                masks = masks.cpu().numpy()
+            else:
+                x.mask = masks.to(device=device, dtype=torch.int32).contiguous()
+        if x.mask is None:
+            m = np.asarray(masks)
+            m = pack_token_mask(m) if m.dtype == bool else np.ascontiguousarray(m).astype(np.uint32, copy=False)
+            x.mask = torch.from_numpy(m.view(np.int32).copy()).to(device)
+        if x.mask.dim() != 2:
+            raise LlmieError("sampling_ext: masks must be [rows, vocab] bools or [rows, stride] words")
+        e.allowed_mask, e.mask_rows, e.mask_stride = x.mask.data_ptr(), x.mask.shape[0], x.mask.shape[1]
+    if mask_index is not None:
+        x.mask_index = _i32(mask_index, device)
+        e.mask_index = x.mask_index.data_ptr()
+    if bias is not None:
+        rows = [list(r.items()) if isinstance(r, dict) else list(r) for r in bias]
+        if len(rows) != batch:
+            raise LlmieError("sampling_ext: bias has %d rows, batch is %d" % (len(rows), batch))
+        stride = max(1, max(len(r) for r in rows))
+        ids = np.zeros((batch, stride), np.int32)
+        vals = np.zeros((batch, stride), np.float32)
+        for b, r in enumerate(rows):
+            for j, (t, v) in enumerate(r):
+                ids[b, j], vals[b, j] = t, v
+        x.bias_ids, x.bias_vals = torch.from_numpy(ids).to(device), torch.from_numpy(vals).to(device)
+        x.bias_len = _i32([len(r) for r in rows], device)
+        e.bias_ids, e.bias_vals, e.bias_len, e.bias_stride = x.bias_ids.data_ptr(), x.bias_vals.data_ptr(), x.bias_len.data_ptr(), stride
+    if stops is not None:
+        rows = [list(r) for r in stops]
+        if len(rows) != batch:
+            raise LlmieError("sampling_ext: stops has %d rows, batch is %d" % (len(rows), batch))
+        stride = max(1, max(len(r) for r in rows))
+        ids = np.full((batch, stride), -1, np.int32)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = r
+        x.stop_ids = torch.from_numpy(ids).to(device)
+        x.stop_len = _i32([len(r) for r in rows], device)
+        e.stop_ids, e.stop_len, e.stop_stride = x.stop_ids.data_ptr(), x.stop_len.data_ptr(), stride
+    if min_step is not None:
+        x.min_step = _i32(min_step, device)
+        e.min_step = x.min_step.data_ptr()
+    for name in ("mask_index", "min_step"):
+        t = getattr(x, name)
+        if t is not None and t.numel() != batch:
+            raise LlmieError("sampling_ext: %s has %d entries, batch is %d" % (name, t.numel(), batch))
+    if top_n:
+        x.top_ids = torch.full((batch, top_n), -2, dtype=torch.int32, device=device)
+        x.top_logprobs = torch.zeros((batch, top_n), dtype=torch.float32, device=device)
+        e.top_n, e.out_top_ids, e.out_top_logprobs = top_n, x.top_ids.data_ptr(), x.top_logprobs.data_ptr()
+    return x
+
+
+def _ext_ref(ext):
+    """ext= of sample_logits / Decoder.lm_head_sample_params: a SamplingExtArrays or a SamplingExt -> what ctypes passes"""
+    return C.byref(ext.struct if isinstance(ext, SamplingExtArrays) else ext)
+
+
 def sample_logits(logits, params, seq_len, finished, out_id, step, end_id, history=None, history_len=None, append=False,
-                  out_logprob=None, step_dev=None, workspace=None):
+                  out_logprob=None, step_dev=None, workspace=None, ext=None):
     """llmie_sample_logits on logits [batch, vocab] (fp16 / fp32, read-only).  params: sampling_params(...) of batch rows.
-    history: int32 [batch, stride] with history_len int32 [batch] (device), or None.  workspace: None allocates one."""
+    history: int32 [batch, stride] with history_len int32 [batch] (device), or None.  workspace: None allocates one.
+    ext: sampling_ext(...) (or a SamplingExt) -> llmie_sample_logits_ext; None calls llmie_sample_logits."""
     bs, V = logits.shape
     ws, ws_bytes = _sample_ws(workspace, bs, V, logits.device)
     stride = 0 if history is None else history.shape[1]
-    _check(lib().llmie_sample_logits(_p(logits), bs, V, _p(params), _p(history), stride, _p(history_len), 1 if append else 0,
-                                     _p(seq_len), _p(finished), _p(out_id), _p(out_logprob), step, _p(step_dev), end_id,
-                                     _p(ws), ws_bytes, _dt(logits), _st()), "sample_logits")
+    args = (_p(logits), bs, V, _p(params), _p(history), stride, _p(history_len), 1 if append else 0, _p(seq_len), _p(finished),
+            _p(out_id), _p(out_logprob), step, _p(step_dev), end_id, _p(ws), ws_bytes, _dt(logits), _st())
+    if ext is None:
+        _check(lib().llmie_sample_logits(*args), "sample_logits")
+    else:
+        _check(lib().llmie_sample_logits_ext(*args, _ext_ref(ext)), "sample_logits_ext")
 
 
 # ------------------------------------------------------------------ token scoring
@@ -631,19 +750,21 @@ class Decoder:
 
     def lm_head_sample_params(self, hidden, final_gamma, lm_head, lm_fmt, logits, params, seq_len, finished, out_ids, step,
                               end_id, history=None, history_len=None, append=False, out_logprob=None, step_dev=None, embed=None,
-                              next_hidden=None, advance=False, workspace=None):
+                              next_hidden=None, advance=False, workspace=None, ext=None):
         """llmie_lm_head_sample_params: the LM head of lm_head_sample, then sample_logits (+ next_hidden[b] = embed[out_ids[b]])
         (+ step_dev += 1).  workspace: sample_logits_workspace_bytes(batch, vocab) bytes, or None to allocate one (not
-        inside a graph capture)."""
+        inside a graph capture).  ext: sampling_ext(...) (or a SamplingExt) -> llmie_lm_head_sample_ext."""
         m = _mat(lm_head)
         bs = hidden.shape[0]
         ws, ws_bytes = _sample_ws(workspace, bs, self.cfg.vocab_size, hidden.device)
         stride = 0 if history is None else history.shape[1]
-        _check(lib().llmie_lm_head_sample_params(self.handle, _p(hidden), _p(final_gamma), C.byref(m), lm_fmt, _p(logits),
-                                                 _p(params), _p(history), stride, _p(history_len), 1 if append else 0,
-                                                 _p(seq_len), _p(finished), _p(out_ids), _p(out_logprob), bs, step,
-                                                 _p(step_dev), end_id, _p(embed), _p(next_hidden), 1 if advance else 0,
-                                                 _p(ws), ws_bytes, _st()), "lm_head_sample_params")
+        args = (self.handle, _p(hidden), _p(final_gamma), C.byref(m), lm_fmt, _p(logits), _p(params), _p(history), stride,
+                _p(history_len), 1 if append else 0, _p(seq_len), _p(finished), _p(out_ids), _p(out_logprob), bs, step,
+                _p(step_dev), end_id, _p(embed), _p(next_hidden), 1 if advance else 0, _p(ws), ws_bytes, _st())
+        if ext is None:
+            _check(lib().llmie_lm_head_sample_params(*args), "lm_head_sample_params")
+        else:
+            _check(lib().llmie_lm_head_sample_ext(*args, _ext_ref(ext)), "lm_head_sample_ext")
 
     OPS = ("attn_norm", "qkv_gemm", "rope", "mha", "o_gemm", "ffn_norm", "gate_up_swiglu", "down_gemm",
            "final_norm", "lm_head", "topk", "sampling", "chain")

@@ -6,6 +6,8 @@
 #pragma once
 #include <algorithm>
 #include <functional>
+#include <utility>
+#include <vector>
 
 #include "layers.hpp"
 #include "tokenizer.hpp"
@@ -82,8 +84,16 @@ private:
     DevBuf<int> d_targets;
     DevBuf<float> d_logprob;
     std::vector<int> penalty_ids;   // prompt + generated ids: the penalty history of the SamplingConfig path
+    // llmie_sampling_ext of the SamplingConfig path: mask, bias list, stop list, min_step, and the top-N of the last step
+    DevBuf<uint32_t> d_mask;
+    DevBuf<int> d_bias_ids, d_bias_len, d_stop_ids, d_stop_len, d_min_step, d_top_ids;
+    DevBuf<float> d_bias_vals, d_top_logprobs, d_pick_logprob;
+    std::vector<int> last_top_ids;
+    std::vector<float> last_top_logprobs;
+    float last_logprob = 0.f;
+    int first_step = 0;   // h_step at the first generated token: min_tokens counts from it
 
-    // SamplingConfig path: llmie_sample_logits over the whole vocabulary, seeded by (h_step, sampling.seed)
+    // SamplingConfig path: llmie_sample_logits(_ext) over the whole vocabulary, seeded by (h_step, sampling.seed)
     int sampleWithConfig(TensorWrapper<T> &probs, TensorWrapper<int> &seq, TensorWrapper<bool> &fin, TensorWrapper<int> &tok) {
         const llmie_sampling_params p{sampling.temperature, sampling.top_k, sampling.top_p, sampling.min_p,
                                       sampling.repetition_penalty, sampling.presence_penalty, sampling.frequency_penalty,
@@ -95,13 +105,65 @@ private:
         CHECK(hipMemcpyAsync(d_sparams.ensure(1), &p, sizeof(p), hipMemcpyHostToDevice, llmie_api::st()));
         if (n) CHECK(hipMemcpyAsync(hist, recent, sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
         CHECK(hipMemcpyAsync(hlen, &n, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+        // the controls of llmie_sampling_ext that are set (an empty struct is llmie_sample_logits itself)
+        llmie_sampling_ext ext{};
+        std::vector<int> bias_ids;
+        std::vector<float> bias_vals;
+        const int n_bias = static_cast<int>(sampling.logit_bias.size()), n_stop = static_cast<int>(sampling.stop_token_ids.size());
+        const int min_step = first_step + sampling.min_tokens, top_n = sampling.top_logprobs;
+        if (!sampling.allowed_tokens.empty()) {
+            const size_t words = sampling.allowed_tokens.size();
+            LLM_CHECK_WITH_INFO(words >= static_cast<size_t>(vocab_size + 31) / 32, "allowed_tokens holds fewer than vocab_size bits");
+            CHECK(hipMemcpyAsync(d_mask.ensure(words), sampling.allowed_tokens.data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice,
+                                 llmie_api::st()));
+            ext.allowed_mask = d_mask.p;
+            ext.mask_stride = static_cast<int>(words);
+            ext.mask_rows = 1;
+        }
+        if (n_bias) {
+            for (const auto &e : sampling.logit_bias) {
+                bias_ids.push_back(e.first);
+                bias_vals.push_back(e.second);
+            }
+            CHECK(hipMemcpyAsync(d_bias_ids.ensure(n_bias), bias_ids.data(), sizeof(int) * n_bias, hipMemcpyHostToDevice, llmie_api::st()));
+            CHECK(hipMemcpyAsync(d_bias_vals.ensure(n_bias), bias_vals.data(), sizeof(float) * n_bias, hipMemcpyHostToDevice, llmie_api::st()));
+            CHECK(hipMemcpyAsync(d_bias_len.ensure(1), &n_bias, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+            ext.bias_ids = d_bias_ids.p;
+            ext.bias_vals = d_bias_vals.p;
+            ext.bias_len = d_bias_len.p;
+            ext.bias_stride = n_bias;   // above LLMIE_SAMPLE_MAX_BIAS: the call refuses it
+        }
+        if (n_stop) {
+            CHECK(hipMemcpyAsync(d_stop_ids.ensure(n_stop), sampling.stop_token_ids.data(), sizeof(int) * n_stop, hipMemcpyHostToDevice,
+                                 llmie_api::st()));
+            CHECK(hipMemcpyAsync(d_stop_len.ensure(1), &n_stop, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+            ext.stop_ids = d_stop_ids.p;
+            ext.stop_len = d_stop_len.p;
+            ext.stop_stride = n_stop;
+        }
+        if (sampling.min_tokens > 0) {
+            CHECK(hipMemcpyAsync(d_min_step.ensure(1), &min_step, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+            ext.min_step = d_min_step.p;
+        }
+        if (top_n > 0) {
+            ext.top_n = top_n;
+            ext.out_top_ids = d_top_ids.ensure(top_n);
+            ext.out_top_logprobs = d_top_logprobs.ensure(top_n);
+        }
         const size_t ws = llmie_sample_logits_workspace_bytes(batch_size, vocab_size);
-        LLMIE_CALL(llmie_sample_logits(probs.data, batch_size, vocab_size, d_sparams.p, hist, std::max(n, 1), hlen, 0, seq.data,
-                                       reinterpret_cast<uint8_t *>(fin.data), tok.data, nullptr, h_step, nullptr, eos_token_id,
-                                       d_sample_ws.ensure(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st()));
+        LLMIE_CALL(llmie_sample_logits_ext(probs.data, batch_size, vocab_size, d_sparams.p, hist, std::max(n, 1), hlen, 0, seq.data,
+                                           reinterpret_cast<uint8_t *>(fin.data), tok.data, d_pick_logprob.ensure(1), h_step, nullptr,
+                                           eos_token_id, d_sample_ws.ensure(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st(), &ext));
         int h_tok = 0;
+        last_top_ids.assign(std::max(top_n, 0), -1);
+        last_top_logprobs.assign(std::max(top_n, 0), 0.f);
         CHECK(hipMemcpyAsync(&h_tok, tok.data, sizeof(int), hipMemcpyDeviceToHost, llmie_api::st()));
-        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps p / n alive until the copies are done)
+        CHECK(hipMemcpyAsync(&last_logprob, d_pick_logprob.p, sizeof(float), hipMemcpyDeviceToHost, llmie_api::st()));
+        if (top_n > 0) {
+            CHECK(hipMemcpyAsync(last_top_ids.data(), d_top_ids.p, sizeof(int) * top_n, hipMemcpyDeviceToHost, llmie_api::st()));
+            CHECK(hipMemcpyAsync(last_top_logprobs.data(), d_top_logprobs.p, sizeof(float) * top_n, hipMemcpyDeviceToHost, llmie_api::st()));
+        }
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps p / n / the lists alive until the copies are done)
         return h_tok;
     }
 
@@ -140,7 +202,11 @@ public:
     // Per-request sampling controls (llmie_sampling_params; include/llmie.h has the semantics).  The default keeps the
     // reference's tail bit for bit (top-4 at temperature 1: launchTopKForBeamSearch + launchSampling); any other value
     // samples with llmie_sample_logits over the whole vocabulary, with the prompt and the generated ids as the penalty
-    // history and Philox(step, seed) as the draw.
+    // history and Philox(step, seed) as the draw.  logit_bias / stop_token_ids / min_tokens / top_logprobs / allowed_tokens are
+    // the controls of llmie_sampling_ext (same header): the bias list (a value of -INFINITY bans a token), stop tokens that end
+    // the reply like EOS, no EOS or stop token among the first min_tokens generated tokens (min_step = the step of the first
+    // generated token + min_tokens), the top_logprobs most likely tokens of every step (lastTopIds / lastTopLogprobs), and a
+    // host bit mask of the allowed tokens (bit v % 32 of word v / 32; uploaded at every step; empty: unconstrained).
     struct SamplingConfig {
         float temperature = 1.0f;   // 0: greedy
         int top_k = 0;              // 0: off
@@ -150,12 +216,29 @@ public:
         float presence_penalty = 0.0f;
         float frequency_penalty = 0.0f;
         uint32_t seed = 0;
+        std::vector<std::pair<int, float>> logit_bias;
+        std::vector<int> stop_token_ids;
+        int min_tokens = 0;
+        int top_logprobs = 0;                   // <= LLMIE_SAMPLE_MAX_TOP_N
+        std::vector<uint32_t> allowed_tokens;   // >= ceil(vocab_size / 32) words
         bool isDefault() const {
             return temperature == 1.0f && top_k == 0 && top_p == 1.0f && min_p == 0.0f && repetition_penalty == 1.0f &&
-                   presence_penalty == 0.0f && frequency_penalty == 0.0f && seed == 0;
+                   presence_penalty == 0.0f && frequency_penalty == 0.0f && seed == 0 && logit_bias.empty() &&
+                   stop_token_ids.empty() && min_tokens == 0 && top_logprobs == 0 && allowed_tokens.empty();
         }
     };
     SamplingConfig sampling;
+    // the last step of the SamplingConfig path: the top_logprobs most likely tokens of the raw row (id -1 / -INFINITY past the
+    // row's valid tokens) and the picked token's raw log-probability
+    const std::vector<int> &lastTopIds() const { return last_top_ids; }
+    const std::vector<float> &lastTopLogprobs() const { return last_top_logprobs; }
+    float lastLogprob() const { return last_logprob; }
+    // the [1, vocab_size] logits of the last step (device), as the sampler read them
+    const T *lastLogits() const { return d_probs.p; }
+    bool isStopToken(int id) const {
+        return id == eos_token_id ||
+               std::find(sampling.stop_token_ids.begin(), sampling.stop_token_ids.end(), id) != sampling.stop_token_ids.end();
+    }
 
     LlamaModel(int head_num, int kv_head_num, int head_size, int inter_size, int num_layers, int vocab_size,
                const LlamaAttentionStaticParams &attention_static_params, int max_seq_len, hipStream_t stream,
@@ -201,6 +284,7 @@ public:
     // llama.cpp:165-217: prefill of `ids` on top of `history_len` cached tokens; returns the first new token
     int generateFirstToken(const std::vector<int> &ids, int history_len) {
         T *ctx_out = runContext(ids, history_len);
+        first_step = h_step;
         return lmHeadAndSample(ctx_out + (ids.size() - 1) * hidden_units);  // last token only (:262-279)
     }
 
@@ -315,7 +399,7 @@ public:
                 if (h_step + 1 >= max_seq_len) break;
                 ++h_step;  // the token generated last round becomes part of the context
                 ret = generateNextToken(ret);
-                if (ret == eos_token_id) break;
+                if (isStopToken(ret)) break;
             }
             last_token_ids.push_back(ret);
             const std::string piece = tokenizer.Decode({ret});

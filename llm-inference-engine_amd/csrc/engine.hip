@@ -1456,6 +1456,7 @@ struct SampleParamsArgs {
     int history_append;
     float *out_logprob;
     void *workspace;
+    const llmie_sampling_ext *ext;   // llmie_lm_head_sample_ext: the sampler's extension (nullptr: the kernel without it)
 };
 
 static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
@@ -1498,7 +1499,7 @@ static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *fin
         TIMED(LLMIE_OP_SAMPLING, sample_logits_launch(logits, batch, c.vocab_size, sp->params, sp->history, sp->history_stride,
                                                       sp->history_len, sp->history_append, seq_len, finished, out_ids, sp->out_logprob,
                                                       step, step_dev, end_id, sp->workspace, c.dtype, embed_table, next_hidden, dec->H,
-                                                      advance_step, dec->tail_ticket, as_stream(stream)));
+                                                      advance_step, dec->tail_ticket, as_stream(stream), sp->ext));
         return LLMIE_OK;
     }
     // llama.cpp:293,304
@@ -1530,21 +1531,46 @@ extern "C" int llmie_lm_head_sample_next(llmie_decoder *dec, void *hidden, const
                                seq_len, finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, true, stream);
 }
 
+static int lm_head_sample_params_impl(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                                      llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev, int32_t *history,
+                                      int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                                      int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev, int end_id,
+                                      const void *embed_table, void *next_hidden, int advance_step, void *workspace,
+                                      size_t workspace_bytes, llmie_stream stream, const llmie_sampling_ext *ext) {
+    LLMIE_REQUIRE(dec, "lm_head_sample_params: NULL decoder");
+    LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_params: next_hidden without an embedding table");
+    LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_params: advance_step needs the device-resident step");
+    LLMIE_REQUIRE(batch >= 1 && batch <= dec->cfg.max_batch, "lm_head_sample_params: batch %d outside [1,%d]", batch, dec->cfg.max_batch);
+    LLMIE_REQUIRE(dec->cfg.vocab_size > 0, "lm_head_sample_params: vocab_size not set in the decoder config");
+    int rc = sample_logits_check(logits, batch, dec->cfg.vocab_size, params_dev, history, history_stride, history_len, seq_len, finished,
+                                 out_ids, workspace, workspace_bytes, dec->cfg.dtype);
+    if (rc != LLMIE_OK) return rc;
+    bool active;
+    if ((rc = sample_ext_check(batch, dec->cfg.vocab_size, ext, &active)) != LLMIE_OK) return rc;
+    const SampleParamsArgs sp{params_dev, history, history_stride, history_len, history_append, out_logprob, workspace,
+                              active ? ext : nullptr};
+    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, nullptr, nullptr, nullptr, nullptr, 0, 1, seq_len,
+                               finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, false, stream, &sp);
+}
+
 extern "C" int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
                                            llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev,
                                            int32_t *history, int history_stride, int32_t *history_len, int history_append,
                                            int32_t *seq_len, uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step,
                                            int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden, int advance_step,
                                            void *workspace, size_t workspace_bytes, llmie_stream stream) {
-    LLMIE_REQUIRE(dec, "lm_head_sample_params: NULL decoder");
-    LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_params: next_hidden without an embedding table");
-    LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_params: advance_step needs the device-resident step");
-    LLMIE_REQUIRE(batch >= 1 && batch <= dec->cfg.max_batch, "lm_head_sample_params: batch %d outside [1,%d]", batch, dec->cfg.max_batch);
-    LLMIE_REQUIRE(dec->cfg.vocab_size > 0, "lm_head_sample_params: vocab_size not set in the decoder config");
-    const int rc = sample_logits_check(logits, batch, dec->cfg.vocab_size, params_dev, history, history_stride, history_len, seq_len,
-                                       finished, out_ids, workspace, workspace_bytes, dec->cfg.dtype);
-    if (rc != LLMIE_OK) return rc;
-    const SampleParamsArgs sp{params_dev, history, history_stride, history_len, history_append, out_logprob, workspace};
-    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, nullptr, nullptr, nullptr, nullptr, 0, 1, seq_len,
-                               finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, false, stream, &sp);
+    return lm_head_sample_params_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, params_dev, history, history_stride,
+                                      history_len, history_append, seq_len, finished, out_ids, out_logprob, batch, step, step_dev, end_id,
+                                      embed_table, next_hidden, advance_step, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int llmie_lm_head_sample_ext(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                                        llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev,
+                                        int32_t *history, int history_stride, int32_t *history_len, int history_append, int32_t *seq_len,
+                                        uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev,
+                                        int end_id, const void *embed_table, void *next_hidden, int advance_step, void *workspace,
+                                        size_t workspace_bytes, llmie_stream stream, const llmie_sampling_ext *ext) {
+    return lm_head_sample_params_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, params_dev, history, history_stride,
+                                      history_len, history_append, seq_len, finished, out_ids, out_logprob, batch, step, step_dev, end_id,
+                                      embed_table, next_hidden, advance_step, workspace, workspace_bytes, stream, ext);
 }

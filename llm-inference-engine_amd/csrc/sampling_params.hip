@@ -15,6 +15,17 @@
 // Masses are fixed point: mass(t) = floor(exp(v_t - v_max) * 2^32) as uint64 (a token below 2^-32 of the maximum weighs 0 and is
 // never drawn).  Every sum is an integer sum, so LDS atomics in any order give the same bits; the float reductions (max,
 // log-sum-exp) use a fixed thread mapping and a fixed tree.  A row's result does not depend on the batch it runs in.
+//
+// llmie_sample_logits_ext / llmie_lm_head_sample_ext launch the EXT instantiation of the same body (sample_params_ext_kernel);
+// the entries without the extension keep sample_params_kernel, whose code the extension does not touch.  EXT adds, in order:
+//   top-N    behind pass 1, on the raw fp32 copy: radix_select (weight 1) + id_select find the top_n-th raw token, one more sweep
+//            collects the <= 32 tokens at or above it into LDS, and each ranks itself among them
+//   bias     one thread per list entry (<= 1024 = the block): an entry patches the copy unless a later entry names its id
+//   min_step the stop ids and end_id become NaN in the copy while step < min_step
+//   penalty  (as before)
+//   mask     the row's bit mask is staged in LDS (16-byte loads) behind the penalties, which are done with `sorted` by then;
+//            pass 2 turns a token whose bit is clear into key 0, what a NaN gets -- everything downstream ignores key 0
+//   stops    finished also if the pick is in the row's stop list
 #include "device_utils.cuh"
 #include "llmie_internal.h"
 #include "philox.cuh"
@@ -93,13 +104,22 @@ __device__ __forceinline__ int sp_excl_scan(int v, SpShared &s) {
 // f(t, key) over this thread's tokens (stride kSpThreads), kSpUnroll loads in flight: one CU streams the whole row, so the
 // passes are bound by load latency unless the loads of several tokens overlap.  Keys past V read as 0 (excluded).
 constexpr int kSpUnroll = 8;
-template <class F> __device__ __forceinline__ void sp_for_keys(const uint32_t *keys, int V, F f) {
+// RAW: `keys` still holds pass 1's fp32 copy of the raw row; its keys are formed on the fly (NaN -> 0, -0 -> +0: llmie_topk's ties)
+template <bool RAW> __device__ __forceinline__ uint32_t sp_load_key(const uint32_t *keys, int t) {
+    if constexpr (RAW) {
+        const float x = __uint_as_float(keys[t]);
+        return x == x ? sp_key(x + 0.f) : 0u;
+    } else {
+        return keys[t];
+    }
+}
+template <bool RAW = false, class F> __device__ __forceinline__ void sp_for_keys(const uint32_t *keys, int V, F f) {
     for (int t0 = threadIdx.x; t0 < V; t0 += kSpUnroll * kSpThreads) {
         uint32_t k[kSpUnroll];
 #pragma unroll
         for (int u = 0; u < kSpUnroll; ++u) {
             const int t = t0 + u * kSpThreads;
-            k[u] = t < V ? keys[t] : 0u;
+            k[u] = t < V ? sp_load_key<RAW>(keys, t) : 0u;
         }
 #pragma unroll
         for (int u = 0; u < kSpUnroll; ++u) f(t0 + u * kSpThreads, k[u]);
@@ -116,7 +136,7 @@ __device__ __forceinline__ void sp_lse_combine(float &m, float &sum, float m2, f
 // In (value desc, id asc) order over the tokens t with in(t, key) (key != 0), the first token at which the running weight
 // w(key) exceeds thr.  The caller guarantees that the total weight exceeds thr.  Returns its key; *above = the weight of the
 // set strictly above that key.  4 passes over the keys, one 8-bit digit each, highest first.
-template <class In, class W>
+template <bool RAW = false, class In, class W>
 __device__ uint32_t radix_select(const uint32_t *keys, int V, In in, W w, u64 thr, u64 *above_out, SpShared &s) {
     const int tid = threadIdx.x;
     uint32_t prefix = 0;
@@ -126,7 +146,7 @@ __device__ uint32_t radix_select(const uint32_t *keys, int V, In in, W w, u64 th
         const uint32_t hmask = d == 3 ? 0u : (0xffffffffu << (shift + 8));
         if (tid < 256) s.hist[tid] = 0;
         __syncthreads();
-        sp_for_keys(keys, V, [&](int t, uint32_t k) {
+        sp_for_keys<RAW>(keys, V, [&](int t, uint32_t k) {
             if (k == 0 || (k & hmask) != prefix || !in(t, k)) return;
             const u64 wt = w(k);
             if (wt) atomicAdd(&s.hist[(k >> shift) & 255u], wt);
@@ -165,18 +185,18 @@ __device__ uint32_t radix_select(const uint32_t *keys, int V, In in, W w, u64 th
 }
 
 // the j-th (0-based) id, ascending, among the tokens with keys[t] == key and in(t, key); -1 if there are not that many
-template <class In>
+template <bool RAW = false, class In>
 __device__ int id_select(const uint32_t *keys, int V, uint32_t key, In in, u64 j, SpShared &s) {
     const int chunk = (V + kSpThreads - 1) / kSpThreads;
     const int t0 = min(V, threadIdx.x * chunk), t1 = min(V, t0 + chunk);
     int c = 0;
-    for (int t = t0; t < t1; ++t) c += (keys[t] == key && in(t, key)) ? 1 : 0;
+    for (int t = t0; t < t1; ++t) c += (sp_load_key<RAW>(keys, t) == key && in(t, key)) ? 1 : 0;
     if (threadIdx.x == 0) s.b_id = -1;
     const int ex = sp_excl_scan(c, s);   // (its barriers order the store above)
     if (j >= static_cast<u64>(ex) && j < static_cast<u64>(ex + c)) {
         int r = static_cast<int>(j - ex);
         for (int t = t0; t < t1; ++t)
-            if (keys[t] == key && in(t, key) && r-- == 0) {
+            if (sp_load_key<RAW>(keys, t) == key && in(t, key) && r-- == 0) {
                 s.b_id = t;
                 break;
             }
@@ -185,13 +205,56 @@ __device__ int id_select(const uint32_t *keys, int V, uint32_t key, In in, u64 j
     return s.b_id;
 }
 
-template <typename T>
+static_assert(LLMIE_SAMPLE_MAX_BIAS <= kSpThreads, "one thread per bias entry");
+static_assert(LLMIE_SAMPLE_MAX_TOP_N <= 256, "the top-N candidates live in SpShared::hist");
+static_assert(offsetof(SpShared, sorted) % 16 == 0, "the mask row is staged in `sorted` with 16-byte stores");
+
+// EXT: the top_n largest raw logits of the row (value desc, id asc) and their raw log-softmax.  `keys` holds pass 1's fp32 copy,
+// untouched so far; valid = its count of non-NaN values; lse = the raw log-sum-exp.
+__device__ __forceinline__ void sp_top_n(const uint32_t *keys, int V, int valid, float lse, int top_n, int32_t *out_ids, float *out_lp, SpShared &s) {
+    const int tid = threadIdx.x;
+    const int n = min(top_n, valid);
+    uint32_t kk = 0;   // the n-th token (kk, kid); kk == 0: every valid token is in
+    int kid = INT_MAX;
+    if (valid > top_n) {
+        auto all = [](int, uint32_t) { return true; };
+        u64 above;
+        kk = radix_select<true>(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_n - 1), &above, s);
+        kid = id_select<true>(keys, V, kk, all, static_cast<u64>(top_n - 1) - above, s);
+    }
+    __syncthreads();   // every thread has read id_select's b_id
+    if (tid == 0) s.b_id = 0;
+    __syncthreads();
+    sp_for_keys<true>(keys, V, [&](int t, uint32_t k) {
+        if (k == 0 || !(k > kk || (k == kk && t <= kid))) return;
+        const int slot = atomicAdd(&s.b_id, 1);   // (any order: the candidates rank themselves below)
+        if (slot < LLMIE_SAMPLE_MAX_TOP_N) s.hist[slot] = (static_cast<u64>(k) << 32) | (0xffffffffu - static_cast<uint32_t>(t));
+    });
+    __syncthreads();
+    if (tid < n) {
+        const u64 mine = s.hist[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += s.hist[j] > mine ? 1 : 0;   // ids differ, so do the candidates
+        out_ids[rank] = static_cast<int32_t>(0xffffffffu - static_cast<uint32_t>(mine & 0xffffffffu));
+        out_lp[rank] = sp_val(static_cast<uint32_t>(mine >> 32)) - lse;
+    } else if (tid < top_n) {
+        out_ids[tid] = -1;
+        out_lp[tid] = -INFINITY;
+    }
+    __syncthreads();   // hist / b_id are free again, and the copy may be patched
+}
+
+// Ext is empty (the kernel of the entries without the extension: their parameter list and their code are what they were before the
+// extension existed) or one llmie_sampling_ext by value (EXT)
+__device__ __forceinline__ const llmie_sampling_ext &sp_ext(const llmie_sampling_ext &e) { return e; }
+template <typename T, typename... Ext>
 __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
     const T *__restrict__ logits, int V, const llmie_sampling_params *__restrict__ params, int32_t *history, int hstride,
     int32_t *history_len, int happend, int32_t *__restrict__ seq_len, uint8_t *__restrict__ finished, int32_t *__restrict__ out_id,
     float *__restrict__ out_logprob, int step_arg, const int32_t *step_dev, int end_id, uint32_t *ws, size_t ws_row,
-    const T *__restrict__ embed, T *__restrict__ next_hidden, int hidden, int advance, unsigned *ticket, int rows) {
-    __shared__ SpShared s;
+    const T *__restrict__ embed, T *__restrict__ next_hidden, int hidden, int advance, unsigned *ticket, int rows, Ext... ext) {
+    constexpr bool EXT = sizeof...(Ext) == 1;
+    __shared__ alignas(EXT ? 16 : alignof(SpShared)) SpShared s;   // (EXT stages the mask row with 16-byte stores)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int step = step_dev ? *step_dev : step_arg;
     const T *lg = logits + static_cast<size_t>(b) * V;
@@ -217,16 +280,66 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
 
     // pass 1: fp32 copy + raw log-sum-exp (per-thread online pairs, then a fixed tree)
     float m = -INFINITY, sum = 0.f;
+    int nraw = 0;   // (EXT) non-NaN raw logits of this thread
     for (int t = tid; t < V; t += kSpThreads) {
         const float x = to_f32(lg[t]);
         rowf[t] = x;
         if (x == x) sp_lse_combine(m, sum, x, 1.f);
+        if constexpr (EXT) nraw += x == x ? 1 : 0;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sp_lse_combine(m, sum, __shfl_xor(m, o), __shfl_xor(sum, o));
     if (lane == 0) {
         s.redm[wave] = m;
         s.reds[wave] = sum;
+    }
+
+    // (EXT) the stop list; the top-N of the raw row; then bias and min_step patch the copy in front of the penalties
+    int slen = 0;
+    const int32_t *stops = nullptr;
+    if constexpr (EXT) {
+        const llmie_sampling_ext &e = sp_ext(ext...);
+        if (e.stop_ids) {
+            slen = min(max(e.stop_len[b], 0), e.stop_stride);
+            stops = e.stop_ids + static_cast<size_t>(b) * e.stop_stride;
+        }
+        if (e.top_n > 0) {
+            const int rawvalid = static_cast<int>(sp_sum64(static_cast<u64>(nraw), s));   // (its barriers complete pass 1)
+            float rm = s.redm[0], rs = s.reds[0];
+            for (int i = 1; i < kSpWaves; ++i) sp_lse_combine(rm, rs, s.redm[i], s.reds[i]);
+            sp_top_n(keys, V, rawvalid, rm + logf(rs), e.top_n, e.out_top_ids + static_cast<size_t>(b) * e.top_n,
+                     e.out_top_logprobs + static_cast<size_t>(b) * e.top_n, s);
+        } else {
+            __syncthreads();   // pass 1's copy of the row is complete
+        }
+        const int blen = e.bias_ids ? min(max(e.bias_len[b], 0), e.bias_stride) : 0;
+        if (blen > 0) {
+            // entry tid of the list; -1: ignored.  It patches the row unless a later entry names the same id (last wins).
+            int id = -1;
+            float val = 0.f;
+            if (tid < blen) {
+                id = e.bias_ids[static_cast<size_t>(b) * e.bias_stride + tid];
+                val = e.bias_vals[static_cast<size_t>(b) * e.bias_stride + tid];
+                if (id < 0 || id >= V || val != val || val == INFINITY) id = -1;
+            }
+            s.sorted[tid] = id;
+            __syncthreads();
+            if (id >= 0) {
+                bool last = true;
+#pragma unroll 8
+                for (int j = tid + 1; j < blen; ++j) last = last && s.sorted[j] != id;
+                if (last) rowf[id] = val == -INFINITY ? __uint_as_float(0x7fc00000u) : rowf[id] + val;
+            }
+            __syncthreads();   // `sorted` is free for the history; the bias is in the row
+        }
+        if (e.min_step && step < e.min_step[b]) {
+            // (the same NaN from several threads where ids repeat)
+            if (tid < slen) {
+                const int t = stops[tid];
+                if (t >= 0 && t < V) rowf[t] = __uint_as_float(0x7fc00000u);
+            }
+            if (tid == LLMIE_SAMPLE_MAX_STOPS && end_id >= 0 && end_id < V) rowf[end_id] = __uint_as_float(0x7fc00000u);
+        }
     }
 
     // penalties over the distinct ids of the history
@@ -277,6 +390,26 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
     float lse_m = s.redm[0], lse_s = s.reds[0];
     for (int i = 1; i < kSpWaves; ++i) sp_lse_combine(lse_m, lse_s, s.redm[i], s.reds[i]);
 
+    // (EXT) the row's allowed-token mask: its first kSpMaxHistory words (262144 tokens) go to `sorted`, which the penalties no
+    // longer need; a longer row reads the rest from memory
+    const uint32_t *mrow = nullptr;
+    const uint32_t *mlds = reinterpret_cast<const uint32_t *>(s.sorted);
+    if constexpr (EXT) {
+        const llmie_sampling_ext &e = sp_ext(ext...);
+        if (e.allowed_mask) {
+            const int mi = e.mask_index ? e.mask_index[b] : b;
+            if (mi >= 0 && mi < e.mask_rows) mrow = e.allowed_mask + static_cast<size_t>(mi) * e.mask_stride;
+        }
+        if (mrow) {
+            const int lw = min((V + 31) >> 5, kSpMaxHistory);
+            uint32_t *dst = reinterpret_cast<uint32_t *>(s.sorted);
+            const int n4 = (reinterpret_cast<uintptr_t>(mrow) % 16 == 0) ? lw >> 2 : 0;
+            for (int i = tid; i < n4; i += kSpThreads) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(mrow)[i];
+            for (int i = 4 * n4 + tid; i < lw; i += kSpThreads) dst[i] = mrow[i];
+            __syncthreads();
+        }
+    }
+
     // pass 2: keys (value desc, id asc -> the larger (key, ~id)), the maximum and the valid count
     const bool greedy = temp == 0.f;
     const float inv_t = greedy ? 1.f : temp;
@@ -295,7 +428,15 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
             if (t >= V) break;
             float x = xs[u];
             uint32_t k = 0;
-            if (x == x) {
+            bool in = true;
+            if constexpr (EXT) {
+                if (mrow) {
+                    const int w = t >> 5;
+                    const uint32_t word = w < kSpMaxHistory ? mlds[w] : mrow[w];
+                    in = (word >> (t & 31)) & 1u;
+                }
+            }
+            if (x == x && in) {
                 if (!greedy) x = fminf(fmaxf(x / inv_t, -FLT_MAX), FLT_MAX);
                 k = sp_key(x);
                 ++nvalid;
@@ -362,7 +503,10 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
     if (tid == 0) {
         out_id[b] = chosen;
         if (!finished[b]) ++seq_len[b];
-        finished[b] = static_cast<uint8_t>(chosen == end_id);
+        bool fin = chosen == end_id;
+        if constexpr (EXT)
+            for (int i = 0; i < slen; ++i) fin = fin || stops[i] == chosen;
+        finished[b] = static_cast<uint8_t>(fin);
         if (out_logprob)
             out_logprob[b] = (chosen >= 0 && chosen < V && valid > 0) ? to_f32(lg[chosen]) - (lse_m + logf(lse_s)) : -INFINITY;
         if (happend && hstride > 0) {
@@ -390,24 +534,69 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
 
 size_t sample_logits_ws_row(int vocab) { return (static_cast<size_t>(vocab) + 63) & ~static_cast<size_t>(63); }
 
+template <typename T>
+static void sample_launch_t(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
+                            int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                            int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                            const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket, hipStream_t st,
+                            const llmie_sampling_ext *ext) {
+    const size_t row = sample_logits_ws_row(vocab);
+    uint32_t *ws = static_cast<uint32_t *>(workspace);
+    if (ext)
+        sample_params_kernel<T, llmie_sampling_ext><<<batch, kSpThreads, 0, st>>>(
+            static_cast<const T *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished, out_id,
+            out_logprob, step, step_dev, end_id, ws, row, static_cast<const T *>(embed), static_cast<T *>(next_hidden), hidden, advance,
+            ticket, batch, *ext);
+    else
+        sample_params_kernel<T><<<batch, kSpThreads, 0, st>>>(
+            static_cast<const T *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished, out_id,
+            out_logprob, step, step_dev, end_id, ws, row, static_cast<const T *>(embed), static_cast<T *>(next_hidden), hidden, advance,
+            ticket, batch);
+}
+
 int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
                          int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
                          int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
                          llmie_dtype dtype, const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket,
-                         hipStream_t st) {
-    const size_t row = sample_logits_ws_row(vocab);
-    uint32_t *ws = static_cast<uint32_t *>(workspace);
+                         hipStream_t st, const llmie_sampling_ext *ext) {
     if (dtype == LLMIE_F16)
-        sample_params_kernel<half_t><<<batch, kSpThreads, 0, st>>>(
-            static_cast<const half_t *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
-            out_id, out_logprob, step, step_dev, end_id, ws, row, static_cast<const half_t *>(embed), static_cast<half_t *>(next_hidden),
-            hidden, advance, ticket, batch);
+        sample_launch_t<half_t>(logits, batch, vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
+                                out_id, out_logprob, step, step_dev, end_id, workspace, embed, next_hidden, hidden, advance, ticket, st, ext);
     else
-        sample_params_kernel<float><<<batch, kSpThreads, 0, st>>>(
-            static_cast<const float *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
-            out_id, out_logprob, step, step_dev, end_id, ws, row, static_cast<const float *>(embed), static_cast<float *>(next_hidden),
-            hidden, advance, ticket, batch);
+        sample_launch_t<float>(logits, batch, vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
+                               out_id, out_logprob, step, step_dev, end_id, workspace, embed, next_hidden, hidden, advance, ticket, st, ext);
     return launch_status("sample_logits");
+}
+
+// llmie_sampling_ext as the host can judge it (the arrays live in device memory).  *active: some control is on -- the EXT kernel
+// is needed; otherwise the call is the entry without the extension.
+int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *e, bool *active) {
+    *active = false;
+    if (!e) return LLMIE_OK;
+    LLMIE_REQUIRE(e->mask_stride >= 0 && e->mask_rows >= 0 && e->bias_stride >= 0 && e->stop_stride >= 0 && e->top_n >= 0,
+                  "sample_logits_ext: negative mask_stride %d / mask_rows %d / bias_stride %d / stop_stride %d / top_n %d", e->mask_stride,
+                  e->mask_rows, e->bias_stride, e->stop_stride, e->top_n);
+    const bool bias_any = e->bias_ids || e->bias_vals || e->bias_len;
+    LLMIE_REQUIRE(!bias_any || (e->bias_ids && e->bias_vals && e->bias_len),
+                  "sample_logits_ext: bias needs bias_ids, bias_vals and bias_len together");
+    LLMIE_REQUIRE(!e->stop_ids == !e->stop_len, "sample_logits_ext: stop_ids and stop_len go together");
+    LLMIE_REQUIRE(e->allowed_mask || !e->mask_index, "sample_logits_ext: mask_index without allowed_mask");
+    if (e->allowed_mask) {
+        LLMIE_REQUIRE(e->mask_stride >= (vocab + 31) / 32, "sample_logits_ext: mask_stride %d words below ceil(vocab %d / 32)",
+                      e->mask_stride, vocab);
+        LLMIE_REQUIRE(e->mask_rows >= 1, "sample_logits_ext: mask_rows %d < 1", e->mask_rows);
+        LLMIE_REQUIRE(e->mask_index || e->mask_rows >= batch, "sample_logits_ext: mask_rows %d below batch %d without a mask_index",
+                      e->mask_rows, batch);
+    }
+    LLMIE_REQUIRE(e->top_n == 0 || (e->out_top_ids && e->out_top_logprobs), "sample_logits_ext: top_n %d without out_top_ids / out_top_logprobs",
+                  e->top_n);
+    if (e->bias_stride > LLMIE_SAMPLE_MAX_BIAS)
+        LLMIE_UNSUPPORTED("sample_logits_ext: bias_stride %d above %d", e->bias_stride, LLMIE_SAMPLE_MAX_BIAS);
+    if (e->stop_stride > LLMIE_SAMPLE_MAX_STOPS)
+        LLMIE_UNSUPPORTED("sample_logits_ext: stop_stride %d above %d", e->stop_stride, LLMIE_SAMPLE_MAX_STOPS);
+    if (e->top_n > LLMIE_SAMPLE_MAX_TOP_N) LLMIE_UNSUPPORTED("sample_logits_ext: top_n %d above %d", e->top_n, LLMIE_SAMPLE_MAX_TOP_N);
+    *active = e->allowed_mask || bias_any || e->stop_ids || e->min_step || e->top_n > 0;
+    return LLMIE_OK;
 }
 
 int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
@@ -448,4 +637,19 @@ extern "C" int llmie_sample_logits(const void *logits, int batch, int vocab, con
     return sample_logits_launch(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
                                 out_id, out_logprob, step, step_dev, end_id, workspace, dtype, nullptr, nullptr, 0, 0, nullptr,
                                 as_stream(stream));
+}
+
+extern "C" int llmie_sample_logits_ext(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
+                                       int history_stride, int32_t *history_len, int history_append, int32_t *seq_len,
+                                       uint8_t *finished, int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev,
+                                       int end_id, void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream,
+                                       const llmie_sampling_ext *ext) {
+    int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_id,
+                                 workspace, workspace_bytes, dtype);
+    if (rc != LLMIE_OK) return rc;
+    bool active;
+    if ((rc = sample_ext_check(batch, vocab, ext, &active)) != LLMIE_OK) return rc;
+    return sample_logits_launch(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
+                                out_id, out_logprob, step, step_dev, end_id, workspace, dtype, nullptr, nullptr, 0, 0, nullptr,
+                                as_stream(stream), active ? ext : nullptr);
 }

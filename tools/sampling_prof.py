@@ -1,10 +1,12 @@
 """Device time of the per-request sampler (llmie_sample_logits), one configuration per process so that a
 `rocprofv3 --kernel-trace --stats` run attributes every sample_params_kernel launch to it (tools/sampling_prof.sh runs them).
 
-    python tools/sampling_prof.py <all|greedy|top_p|tail> <batch> [iters]
+    python tools/sampling_prof.py <all|greedy|top_p|tail|ext_mask|ext_all|ext_top> <batch> [iters]
 
 all: temperature 0.8, top_k 50, top_p 0.9, min_p 0.02, the three penalties over a 64-id history;  greedy: temperature 0;
 top_p: top_p 0.9 alone;  tail: the existing top-4 tail (llmie_topk round 1 + round 2, llmie_sampling) on the same rows.
+ext_*: llmie_sample_logits_ext on the parameters of "all" -- ext_mask: an allowed-token mask per row (half the tokens) alone;
+ext_all: the mask, 300 bias entries per row and top_n = 20;  ext_top: top_n = 20 alone.
 V = 32000, fp16 logits."""
 import os
 import sys
@@ -44,15 +46,23 @@ def main():
             llmie.topk(logits, tid, tv, ids, vals)
             llmie.sampling(ids, vals, seq, fin, out, i, 2, V)
     else:
+        ext = None
+        if kind.startswith("ext_"):
+            masks = rng.random((bs, V)) < 0.5 if kind in ("ext_mask", "ext_all") else None
+            bias = [[(int(t), float(v)) for t, v in zip(rng.integers(0, V, 300), rng.standard_normal(300))]
+                    for _ in range(bs)] if kind == "ext_all" else None
+            ext = llmie.sampling_ext(bs, V, masks=masks, bias=bias, top_n=0 if kind == "ext_mask" else 20)
+            kind = "all"
         params = llmie.sampling_params([dict(CONFIGS[kind], seed=b) for b in range(bs)])
         hist = torch.from_numpy(rng.integers(0, V, (bs, 64)).astype(np.int32)).cuda()
         hlen = torch.full((bs,), 64, dtype=torch.int32, device="cuda")
         lp = torch.empty(bs, dtype=torch.float32, device="cuda")
         ws = torch.empty(llmie.sample_logits_workspace_bytes(bs, V), dtype=torch.uint8, device="cuda")
         for i in range(iters):
-            llmie.sample_logits(logits, params, seq, fin, out, i, 2, history=hist, history_len=hlen, out_logprob=lp, workspace=ws)
+            llmie.sample_logits(logits, params, seq, fin, out, i, 2, history=hist, history_len=hlen, out_logprob=lp, workspace=ws,
+                                ext=ext)
     torch.cuda.synchronize()
-    print(kind, bs, "ok", out[:4].tolist())
+    print(sys.argv[1], bs, "ok", out[:4].tolist())
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ set -u
 OUT=${1:-profiles/sampling}
 mkdir -p "$OUT"
 for bs in 1 128; do
-    for kind in all greedy top_p tail; do
+    for kind in all greedy top_p tail ext_mask ext_all ext_top; do
         timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw" -o "${kind}_b${bs}" -- \
             python tools/sampling_prof.py "$kind" "$bs" 200 || exit $?
         f=$(find "$OUT/raw" -name "${kind}_b${bs}_kernel_stats.csv" | head -1)
