@@ -44,7 +44,8 @@ extern "C" {
  *      per-request sampling: llmie_sampling_params, llmie_sample_logits(_workspace_bytes), llmie_lm_head_sample_params; token scoring:
  *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan; masks, logit bias,
  *      stop sets and top-N log-probabilities in the sampler: llmie_sampling_ext, llmie_sample_logits_ext,
- *      llmie_lm_head_sample_ext). */
+ *      llmie_lm_head_sample_ext; several hypotheses per request: llmie_beam_step(_workspace_bytes),
+ *      llmie_kv_pages_fork(_workspace_bytes)). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -592,6 +593,61 @@ int llmie_decoder_prefill_paged(llmie_decoder *dec, const void *hidden_in, void 
 int llmie_kv_pages_copy(void *dense, void *pool, const int32_t *block_table, const int32_t *ctx_len, int to_pages,
                         int layers, int batch, int kv_head_num, int max_seq_len, int head_size, int max_pages,
                         int num_pages, int elem_bytes, llmie_stream stream);
+
+/* ABI 3 (an addition).  Several hypotheses per request: beam search, or n samples that share one prefilled prompt.  No reference
+ * launcher (the reference carries a beamwidth dimension and `launchTopKForBeamSearch` by name only).
+ *
+ * llmie_beam_step: from the logits [groups * width, vocab] of a step, the next `width` hypotheses of every request.  Beam w of
+ * group g is row r = g * width + w, in one of three states:
+ *   dead      cum_logprob is -INFINITY or NaN: contributes nothing;
+ *   finished  (and not dead): contributes the one candidate (w, end_id, score = cum[w], len = gen_len[w]) -- it stays frozen
+ *             and keeps competing; its logits are not read;
+ *   live      lse = log-sum-exp of the row's non-NaN logits (fp32, running maximum); the row contributes its min(width, valid)
+ *             best tokens in llmie_topk's order on the raw logits (value descending, ties to the lower id, -0 == +0, NaN
+ *             excluded), each as (w, v, score = cum[w] + (logit[v] - lse), len = gen_len[w] + 1): one fp32 subtract, then one
+ *             fp32 add.  A score that comes out NaN (a +INFINITY logit, a row of -INFINITY) is no candidate.
+ * Candidates of a group are ordered by key descending, ties to the lower w, then to the earlier rank inside the row;
+ * key = score when length_penalty == 0 (bit exact, no powf), else score / powf((float)len, length_penalty) (a NaN key, 0 / 0 at
+ * len 0, ranks as -INFINITY).  The first `width` candidates fill slots 0..width-1 in that order: out_parent[g, j] = g * width + w
+ * (the ABSOLUTE row), out_token = v, cum_logprob = score, gen_len = len, finished = parent was finished || v == end_id.  Slots
+ * past the candidate count become dead: out_parent = the slot's own row (llmie_kv_pages_fork leaves it alone), out_token =
+ * end_id, cum = -INFINITY, gen_len = 0, finished = 1.  The state is updated in place; all of a group's reads happen before any
+ * of its writes.  A request starts with cum = [0, -INFINITY, ...] so that its identical first-step rows yield no duplicates.
+ * Same inputs, same bits; a group's outputs depend neither on its slot nor on the other groups; no float atomics.
+ * LLMIE_ERR_INVALID_ARG: NULL pointers, non-positive sizes, NaN length_penalty.  LLMIE_ERR_UNSUPPORTED: width >
+ * LLMIE_BEAM_MAX_WIDTH.  LLMIE_ERR_WORKSPACE: NULL, short or not 4-byte aligned.  LLMIE_ERR_UNSUPPORTED: an unknown dtype.
+ * Two launches, no allocation, no synchronisation, legal inside a graph capture: every operand is read on the device. */
+#define LLMIE_BEAM_MAX_WIDTH 16
+size_t llmie_beam_step_workspace_bytes(int groups, int width, int vocab);
+int llmie_beam_step(const void *logits /* [groups*width, vocab], dtype */, int groups, int width, int vocab,
+                    float *cum_logprob /* [groups, width] in/out */, int32_t *gen_len /* [groups, width] in/out */,
+                    uint8_t *finished /* [groups, width] in/out */, int32_t *out_parent /* [groups, width] */,
+                    int32_t *out_token /* [groups, width] */, int end_id, float length_penalty, void *workspace,
+                    size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition).  llmie_kv_pages_fork: row j of a paged cache continues the sequence of row parent[j] (copy on fork).
+ * Pools [L, num_pages, kvh, 128, hs] and block_table [rows, max_pages] as llmie_decoder_forward_paged takes them; own_table
+ * [rows, max_pages] names the pages row j may write; cached_len [rows] is the number of tokens in the cache of each row.  "Old"
+ * is a value as it was before the call.  With q = parent[j], n = old cached_len[q], pc = n / 128, r = n % 128, row j is left
+ * entirely untouched if q == j, q lies outside [0, rows), n lies outside [0, 128 * max_pages], or -- r > 0 -- the page it would
+ * read (old block_table[q][pc]) or write (own_table[j][pc]) lies outside [0, num_pages).  Otherwise cached_len[j] = n;
+ * block_table[j][p] = old block_table[q][p] for p < pc (completed pages are shared, nothing is copied) and own_table[j][p] for
+ * p >= pc; and if r > 0 the first r token rows of page old block_table[q][pc] are copied bit-exactly into page own_table[j][pc],
+ * for every layer and KV head, in both pools -- exactly those rows are written and nothing else in either pool.  Every read is of
+ * the old state whatever `parent` is (a swap, a rotation: source tails are destination tails of other rows): one launch gathers
+ * tails, table rows and lengths into the workspace, a second scatters them.  16 bytes per lane where the addresses allow it, plain
+ * bytes otherwise; any elem_bytes (fp16 and e4m3 caches are both just bytes).
+ * Caller contract: own_table names a distinct page per (row, page index); a row's pages at indices >= cached_len / 128 are its
+ * own; the context lengths in a family of forks never shrink -- a row's own page at index p is shared only once it is complete,
+ * such a page is never handed out again, and a caller that forks to a shorter context supplies fresh pages.
+ * LLMIE_ERR_INVALID_ARG: NULL pointers, non-positive sizes.  LLMIE_ERR_UNSUPPORTED: kv_head_num or layers above 65535, rows above
+ * 32767.  LLMIE_ERR_WORKSPACE: NULL, short or not 16-byte aligned.  No allocation, no synchronisation, legal inside a capture. */
+size_t llmie_kv_pages_fork_workspace_bytes(int rows, int layers, int kv_head_num, int head_size, int elem_bytes, int max_pages);
+int llmie_kv_pages_fork(void *k_pool, void *v_pool, int32_t *block_table /* [rows, max_pages] in/out */,
+                        const int32_t *own_table /* [rows, max_pages] */, const int32_t *parent /* [rows]: absolute row */,
+                        int32_t *cached_len /* [rows] in/out */, int rows, int layers, int kv_head_num, int head_size,
+                        int max_pages, int num_pages, int elem_bytes, void *workspace, size_t workspace_bytes,
+                        llmie_stream stream);
 
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,
  * context_attention.cpp:143-312) on PACKED tokens: hidden_in/out [num_tokens, H] hold the sequences back to back

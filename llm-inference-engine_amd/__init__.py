@@ -108,6 +108,10 @@ _SIGS = {
     "llmie_decoder_forward_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "llmie_decoder_prefill_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
     "llmie_kv_pages_copy": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "llmie_beam_step_workspace_bytes": [_i, _i, _i],
+    "llmie_beam_step": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _sz, _i, _vp],
+    "llmie_kv_pages_fork_workspace_bytes": [_i, _i, _i, _i, _i, _i],
+    "llmie_kv_pages_fork": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -132,6 +136,8 @@ _RESTYPES = {
     "llmie_decoder_prefill_workspace_bytes": _sz,
     "llmie_sample_logits_workspace_bytes": _sz,
     "llmie_score_tokens_workspace_bytes": _sz,
+    "llmie_beam_step_workspace_bytes": _sz,
+    "llmie_kv_pages_fork_workspace_bytes": _sz,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -843,6 +849,83 @@ def kv_pages_copy(dense, pool, block_table, ctx_len, to_pages):
     _check(lib().llmie_kv_pages_copy(_p(dense), _p(pool), _p(block_table), _p(ctx_len), 1 if to_pages else 0, L, batch, kvh,
                                      max_seq, hs, block_table.shape[1], pool.shape[1], dense.element_size(), _st()),
            "kv_pages_copy")
+
+
+# ------------------------------------------------------------------ several hypotheses per request
+BEAM_MAX_WIDTH = 16  # LLMIE_BEAM_MAX_WIDTH
+_beam_scratch = {}
+_fork_scratch = {}
+
+
+def _grow(cache, device, need):
+    """workspace="auto": one grow-only torch buffer per device and entry, owned by this module"""
+    import torch
+    buf = cache.get(device)
+    if buf is None or buf.numel() < need:
+        buf = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+        cache[device] = buf
+    return buf
+
+
+class BeamState:
+    """cum [groups, width] fp32, gen_len [groups, width] int32, finished [groups, width] uint8: what llmie_beam_step updates in
+    place.  The tensors can be overwritten in place -- a captured graph reads them on replay."""
+
+    def __init__(self, cum, gen_len, finished):
+        self.cum, self.gen_len, self.finished = cum, gen_len, finished
+
+
+def beam_state(groups, width, device="cuda"):
+    """state of `groups` requests in front of their first step: beam 0 live at log-probability 0, the others dead (-inf), so that
+    the identical rows of a first step yield no duplicates"""
+    import torch
+    cum = torch.full((groups, width), float("-inf"), dtype=torch.float32, device=device)
+    cum[:, 0] = 0.0
+    return BeamState(cum, torch.zeros((groups, width), dtype=torch.int32, device=device),
+                     torch.zeros((groups, width), dtype=torch.uint8, device=device))
+
+
+def beam_step_workspace_bytes(groups, width, vocab):
+    return lib().llmie_beam_step_workspace_bytes(groups, width, vocab)
+
+
+def beam_step(logits, state, end_id, length_penalty=0.0, workspace="auto", out=None):
+    """llmie_beam_step on logits [groups * width, vocab] (fp16 / fp32, read-only): updates `state` (a BeamState) in place and
+    returns (parent, token), int32 [groups, width]; parent holds ABSOLUTE rows, ready for kv_pages_fork.  out: a (parent, token)
+    pair to write into.  workspace: a device tensor of beam_step_workspace_bytes(groups, width, vocab) bytes, or the string auto
+    (inside a graph capture pass a tensor, or make a first call outside)."""
+    import torch
+    groups, width = state.cum.shape
+    rows, vocab = logits.shape
+    if rows != groups * width:
+        raise LlmieError("beam_step: %d rows of logits for %d groups of %d beams" % (rows, groups, width))
+    if isinstance(workspace, str):
+        workspace = _grow(_beam_scratch, logits.device, beam_step_workspace_bytes(groups, width, vocab))
+    parent, token = out if out is not None else (torch.empty((groups, width), dtype=torch.int32, device=logits.device),
+                                                 torch.empty((groups, width), dtype=torch.int32, device=logits.device))
+    _check(lib().llmie_beam_step(_p(logits), groups, width, vocab, _p(state.cum), _p(state.gen_len), _p(state.finished), _p(parent),
+                                 _p(token), end_id, length_penalty, _p(workspace),
+                                 0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(logits), _st()),
+           "beam_step")
+    return parent, token
+
+
+def kv_pages_fork_workspace_bytes(rows, layers, kv_head_num, head_size, elem_bytes, max_pages):
+    return lib().llmie_kv_pages_fork_workspace_bytes(rows, layers, kv_head_num, head_size, elem_bytes, max_pages)
+
+
+def kv_pages_fork(k_pool, v_pool, block_table, own_table, parent, cached_len, workspace="auto"):
+    """llmie_kv_pages_fork: row j continues the sequence of row parent[j] (absolute rows, e.g. beam_step's parent).  Pools
+    [L, num_pages, kvh, 128, hs]; block_table / own_table int32 [rows, max_pages]; cached_len int32 [rows].  Completed pages are
+    shared through the table, only the partial tail page is copied, into own_table's page.  workspace: a device tensor of
+    kv_pages_fork_workspace_bytes(...) bytes, or the string auto."""
+    L, num_pages, kvh, _, hs = k_pool.shape
+    rows, max_pages = block_table.shape
+    if isinstance(workspace, str):
+        workspace = _grow(_fork_scratch, k_pool.device, kv_pages_fork_workspace_bytes(rows, L, kvh, hs, k_pool.element_size(), max_pages))
+    _check(lib().llmie_kv_pages_fork(_p(k_pool), _p(v_pool), _p(block_table), _p(own_table), _p(parent), _p(cached_len), rows, L, kvh,
+                                     hs, max_pages, num_pages, k_pool.element_size(), _p(workspace),
+                                     0 if workspace is None else workspace.numel() * workspace.element_size(), _st()), "kv_pages_fork")
 
 
 def linear_fp8_workspace_bytes(M, K, N=0):

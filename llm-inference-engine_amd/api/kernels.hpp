@@ -270,3 +270,34 @@ void launchSampling(TensorWrapper<int> *topk_id, TensorWrapper<T> *topk_val, Ten
                               topk_id->shape[1], params->at("step"), nullptr, params->at("end_id"),
                               params->at("vocab_size"), llmie_api::dtype_of<T>(), llmie_api::st()));
 }
+
+// No reference launcher (the reference names a beamwidth and never fills it): one beam-search step on the logits
+// [groups * width, vocab] of a decode step.  cum_logprob / gen_len / finished [groups, width] are updated in place; parent (ABSOLUTE
+// rows, ready for launchForkKVPages) and token [groups, width] are written.
+template <typename T>
+void launchBeamSearchStep(TensorWrapper<T> *logits, TensorWrapper<float> *cum_logprob, TensorWrapper<int> *gen_len,
+                          TensorWrapper<bool> *finished, TensorWrapper<int> *parent, TensorWrapper<int> *token, int end_id,
+                          float length_penalty = 0.f) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int groups = cum_logprob->shape[0], width = cum_logprob->shape[1], vocab = logits->shape[1];
+    LLM_CHECK_WITH_INFO(logits->shape[0] == groups * width, "logits rows should equal groups * width of the beam state");
+    const size_t ws = llmie_beam_step_workspace_bytes(groups, width, vocab);
+    LLMIE_CALL(llmie_beam_step(logits->data, groups, width, vocab, cum_logprob->data, gen_len->data,
+                               reinterpret_cast<uint8_t *>(finished->data), parent->data, token->data, end_id, length_penalty,
+                               llmie_api::scratch(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st()));
+}
+
+// No reference launcher: row j of the paged caches [layers, num_pages, kv_heads, 128, head_size] continues the sequence of row
+// parent[j]; completed pages are shared through block_table [rows, max_pages], the partial tail page is copied into own_table's.
+template <typename T>
+void launchForkKVPages(TensorWrapper<T> *k_pool, TensorWrapper<T> *v_pool, TensorWrapper<int> *block_table,
+                       TensorWrapper<int> *own_table, TensorWrapper<int> *parent, TensorWrapper<int> *cached_len) {
+    const int layers = k_pool->shape[0], num_pages = k_pool->shape[1], kv_head_num = k_pool->shape[2], head_size = k_pool->shape[4];
+    const int rows = block_table->shape[0], max_pages = block_table->shape[1];
+    LLM_CHECK_WITH_INFO(k_pool->shape[3] == LLMIE_KV_PAGE_TOKENS, "pages hold 128 tokens");
+    LLM_CHECK_WITH_INFO(own_table->shape[0] == rows && own_table->shape[1] == max_pages, "own_table should have block_table's shape");
+    const size_t ws = llmie_kv_pages_fork_workspace_bytes(rows, layers, kv_head_num, head_size, static_cast<int>(sizeof(T)), max_pages);
+    LLMIE_CALL(llmie_kv_pages_fork(k_pool->data, v_pool->data, block_table->data, own_table->data, parent->data, cached_len->data, rows,
+                                   layers, kv_head_num, head_size, max_pages, num_pages, static_cast<int>(sizeof(T)),
+                                   llmie_api::scratch(ws), ws, llmie_api::st()));
+}
