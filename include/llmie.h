@@ -548,6 +548,25 @@ size_t llmie_decoder_resident_weight_bytes(const llmie_decoder_config *cfg);
 #define LLMIE_SW_NO_QKV_ROPE_FUSION 32u
 const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, int prefill, int rows, unsigned call_flags, unsigned switch_mask);
 
+/* What ONE LAYER of llmie_decoder_prefill launches (an addition within ABI 3; host only, no device access), as one line of text:
+ *   "lean token_table=1 attn_norm=oop qkv=rope_f16 pre=none rope_done=1 attn=q128w8t1 kv=f16 grid=16x16x1 rope_append=0 ffn_norm=oop
+ *    gate_up=fused launches attn_norm=1 qkv_gemm=1 mha=1 o_gemm=1 ffn_norm=1 gate_up_swiglu=1 down_gemm=1"
+ * the pass's sequence (llmie_decoder_plan_name) and whether it writes the token table of the fused QKV epilogue; the two norm forms
+ * (none / inplace / oop / quant: emits e4m3 rows / rownorm: the split-K row kernel); the QKV form (plain, rope_f16 / rope_w8 /
+ * rope_image / rope_unpacked / rope_e4m3: RoPE + the cache append in the projection's epilogue, plain_e4m3, unpack_plain, splitk,
+ * splitk_rope) with the launch in front of it (dequant / unpack of the matrix's fp16 image) and the rope_done flag the attention
+ * launch receives; the flash kernel's instantiation (query rows per workgroup, waves, row tiles per wave, cache format), its grid and
+ * whether the RoPE + append launch runs in front; the gate/up form (fused, e4m3_swiglu, fp8_swiglu, two_launch, unpack_fused,
+ * unpack_two_launch, splitk); and the launches per profiled op kind of one pass through the layer.  call_flags describe the pass
+ * (LLMIE_PLAN_* above) and this layer's operands (below); switch_mask as above.  NULL where llmie_decoder_prefill -- or creating the
+ * engine -- refuses: llmie_last_error() says why and *status (nullable) receives the code.  tests/golden/prefill_layer_plans.txt pins
+ * the answers. */
+#define LLMIE_PLAN_QKV_BIAS_MISALIGNED 128u       /* the layer's QKV bias not 8-byte aligned */
+#define LLMIE_PLAN_GATE_UP_SCALES_MISALIGNED 256u /* the layer's gate/up scales not 16-byte aligned */
+#define LLMIE_PLAN_NO_FFN_GAMMA 512u              /* the layer has no FFN norm gamma */
+const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_config *cfg, int tokens, int batch, int max_q_len, unsigned call_flags,
+                                             unsigned switch_mask, int *status);
+
 typedef struct llmie_decoder llmie_decoder; /* opaque */
 
 /* Workspace is caller-owned device memory (no allocation inside). */

@@ -118,6 +118,7 @@ _SIGS = {
     "llmie_decoder_resident_weight_bytes": [_vp],
     "llmie_decoder_repack": [_vp, _vp, _vp],
     "llmie_decoder_plan_name": [_vp, _i, _i, C.c_uint, C.c_uint],
+    "llmie_decoder_prefill_layer_plan": [_vp, _i, _i, _i, C.c_uint, C.c_uint, _vp],
     "llmie_decoder_debug_stamps": [_vp, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
@@ -145,6 +146,7 @@ _RESTYPES = {
     "llmie_gemm256_tiles": C.c_char_p,
     "llmie_decoder_mha_plan": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
+    "llmie_decoder_prefill_layer_plan": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
 }
 
@@ -281,6 +283,25 @@ def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):
     c = cfg if isinstance(cfg, DecoderConfig) else DecoderConfig(**cfg)
     r = lib().llmie_decoder_plan_name(C.byref(c), int(bool(prefill)), rows, call_flags, switch_mask)
     return r.decode() if r is not None else None
+
+
+def decoder_prefill_layer_plan(cfg, tokens, batch=1, max_q_len=None, call_flags=0, switch_mask=0):
+    """(plan text or None, status) of what one layer of a prefill of `tokens` tokens in `batch` sequences of at most `max_q_len`
+    (default: tokens) launches on an engine of `cfg` (include/llmie.h): sequence, norm / QKV / attention / gate-up forms, launches per
+    op; as a dict through plan_fields().  None where the pass is refused (llmie_last_error() says why).  No device needed."""
+    c = cfg if isinstance(cfg, DecoderConfig) else DecoderConfig(**cfg)
+    status = C.c_int(0)
+    t = lib().llmie_decoder_prefill_layer_plan(C.byref(c), tokens, batch, tokens if max_q_len is None else max_q_len, call_flags, switch_mask,
+                                               C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def plan_fields(text):
+    """{"path": ..., "qkv": ..., ..., "launches": {op: n}} of a llmie_decoder_prefill_layer_plan text"""
+    forms, launches = text.split(" launches")
+    words = forms.split(" ")
+    return dict([("path", words[0])] + [w.split("=") for w in words[1:]],
+                launches={k: int(v) for k, v in (w.split("=") for w in launches.split())})
 
 
 _scratch = {}

@@ -676,6 +676,111 @@ static const char *prefill_path_name(int path) {
     return names[path];
 }
 
+// ---- what one LAYER of a prefill pass launches: decided per layer, by a pure host function as well ----
+enum PrefillNorm : int { PN_NONE = 0, PN_INPLACE, PN_OOP, PN_QUANT, PN_ROWNORM };
+enum PrefillQkv : int {
+    PQ_PLAIN = 0, PQ_ROPE_F16, PQ_ROPE_W8, PQ_ROPE_IMAGE, PQ_PLAIN_E4M3, PQ_ROPE_E4M3, PQ_UNPACK_PLAIN, PQ_ROPE_UNPACKED, PQ_SPLITK, PQ_SPLITK_ROPE
+};
+enum PrefillGateUp : int { PG_FUSED = 0, PG_TWO_LAUNCH, PG_E4M3_SWIGLU, PG_FP8_SWIGLU, PG_UNPACK_FUSED, PG_UNPACK_TWO_LAUNCH, PG_SPLITK };
+// What the form choices read of one layer's operands: address % 16 of the QKV matrix, scales and bias, of the gate/up matrix and scales
+// and of the hidden state; whether the FFN gamma is there; the split-K slab and de-quantisation areas of the pass's workspace.
+struct PrefillLayerCall {
+    unsigned mis_qkv_w, mis_qkv_scale, mis_qkv_bias, mis_gu_w, mis_gu_scale, mis_hidden;
+    bool ffn_gamma;
+    size_t slab_floats, deq_bytes;
+};
+// attn_norm / ffn_norm: PrefillNorm (PN_INPLACE: llmie_rmsnorm / llmie_fused_add_bias_residual_rmsnorm; PN_QUANT: rmsnorm_quant_f16, the
+// FFN one with the O bias; PN_NONE / PN_ROWNORM: the split-K sequence, whose row kernels normalise for the next projection).  qkv:
+// PrefillQkv (ROPE forms: RoPE + the cache append in the projection's epilogue, hence rope_done; IMAGE: dequantize_weights_f16 first;
+// UNPACK: pk_unpack_f16 first).  launches: per LLMIE_OP_* kind, one per TIMED launch -- derived from the forms.
+struct PrefillLayerPlan {
+    int attn_norm, qkv, ffn_norm, gate_up;
+    bool rope_done;
+    PrefillAttnPlan attn;
+    int launches[LLMIE_OP_COUNT];
+};
+// Round 3: RoPE + KV-cache append as the EPILOGUE of the QKV projection (context_attention.cpp:158-205 in one launch sequence;
+// gemm8p.cuh ROPE forms): q is rotated on its way into the packed QKV buffer, k / v go straight to their cache slots and never
+// travel through the buffer; bit-identical to projection + prefill_rope_append_kernel (same arithmetic on the fp16-rounded
+// accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
+// this holds writes the epilogue's token table once, whatever its layers end up choosing.)
+static bool prefill_rope_fusable(const PrefillCall &p) {
+    return !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+}
+static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
+    const llmie_decoder_config &c = p.cfg;
+    const int T = p.T, H = c.head_num * c.head_size, QKV = (c.head_num + 2 * c.kv_head_num) * c.head_size, I = c.inter_size;
+    const bool fp8 = c.wfmt == LLMIE_W_FP8, lean = path == PP_LEAN;
+    const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
+    // stand-in addresses with the residues the eligibility functions look at (never dereferenced); ws: any workspace area -- they are
+    // carved at 256-byte multiples
+    auto at = [](unsigned mis) { return reinterpret_cast<void *>(static_cast<uintptr_t>(256 + mis)); };
+    void *const ws = at(0);
+    const SlabWs slabs{static_cast<float *>(ws), lc.slab_floats};
+    // the projections' input: the lean sequence's norms write it into the workspace, the others normalise the hidden state in place
+    const void *x = lean ? ws : at(lc.mis_hidden);
+    const void *qw = at(lc.mis_qkv_w), *qsc = at(lc.mis_qkv_scale), *gw = at(lc.mis_gu_w), *gsc = at(lc.mis_gu_scale);
+    const bool rope_ok = prefill_rope_fusable(p) && lc.mis_qkv_bias % 8 == 0;
+    PrefillLayerPlan o{};
+    if (path == PP_SHORT_SPLITK) {
+        // (the slab consumer of the QKV projection does RoPE + the cache append as well: one launch less per layer)
+        const SplitKSlabs sk{slabs.p, 1, T, QKV};
+        o.qkv = !p.sw.no_qkv_rope_fusion && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
+        o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
+    } else if (path == PP_PACKED_ONLY) {
+        // every projection runs the fp16 GEMM on the unpacked image of its matrix: the fp16 forms, on the de-quantisation area
+        o.qkv = rope_ok && lc.deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, ws, nullptr, ws)
+                    ? PQ_ROPE_UNPACKED : PQ_UNPACK_PLAIN;
+        const LinearCall gc = linear_call(16, T, H, 2 * I, EPI_SWIGLU_, 0, x, ws, nullptr, ws, nullptr, nullptr, nullptr, nullptr, slabs, nullptr, 0);
+        o.gate_up = plan_linear_f16(gc).route != LR_REFUSED ? PG_UNPACK_FUSED : PG_UNPACK_TWO_LAUNCH;
+        o.attn_norm = o.ffn_norm = PN_INPLACE;
+    } else {
+        // fp8, prefill-sized: the two RMSNorms emit the e4m3 activations of the projection behind them (norm.hip
+        // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are
+        const bool nq = fp8 && T > 8 && H % 128 == 0 && rmsnorm_quant_eligible(H);
+        o.attn_norm = o.ffn_norm = lean ? PN_OOP : PN_INPLACE;
+        o.qkv = PQ_PLAIN;
+        if (nq && gemm256_fills(T, QKV) && QKV % 4 == 0 && (lc.mis_qkv_w | lc.mis_qkv_scale) == 0) {
+            o.attn_norm = PN_QUANT;
+            o.qkv = rope_ok && gemm256_qkv_rope_eligible(G256_E4M3, T, QKV, H, ws, qw, qsc, ws) ? PQ_ROPE_E4M3 : PQ_PLAIN_E4M3;
+        } else if (rope_ok && !fp8 && !wqbits) {
+            if (gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, qw, nullptr, ws)) o.qkv = PQ_ROPE_F16;
+        } else if (rope_ok && !fp8) {
+            // int8 / int4: the route the plain projection would take -- the eight-phase int8 form, or (int4, and int8 shapes without the
+            // in-kernel form) the fp16 image of the matrix -- with the epilogue on the same kernels
+            const int route = plan_linear_wq(linear_call(wqbits, T, H, QKV, EPI_NONE_, c.int4_group, x, qw, qsc, ws, nullptr, nullptr, nullptr,
+                                                         nullptr, slabs, ws, lc.deq_bytes)).route;
+            if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(G256_W8, T, QKV, H, x, qw, qsc, ws)) o.qkv = PQ_ROPE_W8;
+            if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, ws, nullptr, ws)) o.qkv = PQ_ROPE_IMAGE;
+        }
+        // act = swiglu(x . Wgu^T) (ffn.cpp:105-122): fused into the projection's epilogue where the route plan has a form, else
+        // projection + llmie_silu_and_mul (e.g. fp16 H < 512 at 65-192 rows, int8 H % 256 != 0 at 9-191 rows, weights at offsets the
+        // vector kernels do not take).  Quantised weights at prefill-sized T fuse only where the 256-row SwiGLU grid fills the chip:
+        // the split-K and row-chunk forms the plan has left there cost more than the two launches.
+        const bool gu_fused8 = fp8 && gemm256_swiglu_fills(T, 2 * I) && H % 128 == 0 && lc.mis_gu_w == 0;
+        const LinearCall gc = linear_call(wqbits ? wqbits : 16, T, H, 2 * I, EPI_SWIGLU_, c.int4_group, x, gw, gsc, ws, nullptr, nullptr, nullptr, nullptr,
+                                          slabs, wqbits ? ws : nullptr, lc.deq_bytes);
+        if (nq && gu_fused8 && lc.ffn_gamma && lc.mis_gu_scale == 0) o.ffn_norm = PN_QUANT, o.gate_up = PG_E4M3_SWIGLU;
+        else if (fp8) o.gate_up = gu_fused8 ? PG_FP8_SWIGLU : PG_TWO_LAUNCH;
+        else if (wqbits) o.gate_up = (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && plan_linear_wq(gc).route != LR_REFUSED ? PG_FUSED : PG_TWO_LAUNCH;
+        else o.gate_up = plan_linear_f16(gc).route != LR_REFUSED ? PG_FUSED : PG_TWO_LAUNCH;
+    }
+    o.rope_done = o.qkv == PQ_ROPE_F16 || o.qkv == PQ_ROPE_W8 || o.qkv == PQ_ROPE_IMAGE || o.qkv == PQ_ROPE_E4M3 || o.qkv == PQ_ROPE_UNPACKED ||
+                  o.qkv == PQ_SPLITK_ROPE;
+    o.attn = plan_prefill_attn(batch, max_q_len, c.head_num, c.kv_fmt == LLMIE_KV_FP8, o.rope_done);
+    // (the split-K sequence's ATTN_NORM launch is the row kernel behind the down projection)
+    for (int op : {LLMIE_OP_ATTN_NORM, LLMIE_OP_QKV_GEMM, LLMIE_OP_MHA, LLMIE_OP_O_GEMM, LLMIE_OP_FFN_NORM, LLMIE_OP_GATE_UP_SWIGLU, LLMIE_OP_DOWN_GEMM})
+        o.launches[op] = 1;
+    if (o.qkv == PQ_ROPE_UNPACKED || o.qkv == PQ_SPLITK || o.qkv == PQ_SPLITK_ROPE) o.launches[LLMIE_OP_QKV_GEMM] = 2;
+    if (o.gate_up == PG_TWO_LAUNCH || o.gate_up == PG_UNPACK_TWO_LAUNCH || o.gate_up == PG_SPLITK) o.launches[LLMIE_OP_GATE_UP_SWIGLU] = 2;
+    return o;
+}
+// the PrefillCall llmie_decoder_plan_name / llmie_decoder_prefill_layer_plan describe with their call flags
+static PrefillCall prefill_call_of_flags(const llmie_decoder_config &cfg, int tokens, unsigned call_flags, const EngineSwitches &sw) {
+    return PrefillCall{cfg, tokens, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
+                       !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw};
+}
+
 // Host-only: the launch sequence llmie_decoder_forward (prefill = 0, rows = batch) or llmie_decoder_prefill (prefill = 1, rows =
 // tokens) plans for an engine of this config; NULL with llmie_last_error() set where the call -- or creating the engine -- is refused.
 extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, int prefill, int rows, unsigned call_flags,
@@ -694,9 +799,7 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
             set_error("decoder_plan_name: %d tokens", rows);
             return nullptr;
         }
-        const PrefillCall pc{*cfg, rows, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
-                             !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw};
-        const PrefillPlan p = plan_prefill(pc);
+        const PrefillPlan p = plan_prefill(prefill_call_of_flags(*cfg, rows, call_flags, sw));
         if (p.path == PP_REFUSED) return (void)prefill_refuse(p), nullptr;
         return prefill_path_name(p.path);
     }
@@ -1101,10 +1204,13 @@ extern "C" size_t llmie_decoder_prefill_workspace_bytes(const llmie_decoder_conf
 }
 
 // One prefill pass: the call, its workspace areas and the projections every launch sequence shares.  The sequences are members, so
-// their bodies name the call's parts like locals.
+// their bodies name the call's parts like locals.  Which form each launch of a layer takes is plan_prefill_layer's answer for that
+// layer's operands; the sequences run it.
 struct PrefillPass {
     llmie_decoder *dec;
     const llmie_decoder_config &c;
+    const PrefillCall &call;
+    int path;
     llmie_stream stream;
     hipStream_t st;
     KvView kv;
@@ -1120,8 +1226,20 @@ struct PrefillPass {
     void *deq;
     size_t deq_bytes;
     QkvRopeArgs *rope_args;   // (device copy of the fused QKV epilogue's operands)
-    bool rope_fuse_off, rope_fusable;
 
+    PrefillLayerPlan layer_plan(const llmie_layer_weights &w) const {
+        return plan_prefill_layer(call, path, batch, max_q_len,
+                                  PrefillLayerCall{mis16(w.qkv.data), mis16(w.qkv.scale), mis16(w.qkv.bias), mis16(w.gate_up.data),
+                                                   mis16(w.gate_up.scale), mis16(h), w.ffn_norm_gamma != nullptr, slabs.floats, deq_bytes});
+    }
+    // a form this sequence has no launch for: the planner and the sequence disagree
+    int bad_form(const char *what, int form) const {
+        set_error("decoder_prefill: the %s sequence cannot run %s form %d", prefill_path_name(path), what, form);
+        return LLMIE_ERR_UNSUPPORTED;
+    }
+    // e4m3 rows + token scales the quantising norms leave for the projection behind them
+    uint8_t *xqn() const { return static_cast<uint8_t *>(f8ws); }
+    float *xsn() const { return reinterpret_cast<float *>(xqn() + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255))); }
     // y = x . W^T (+ residual) in the engine's weight format (fp8: per-token e4m3 activations, fp8 MFMA)
     int proj(const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual) const {
         if (wqbits)
@@ -1132,59 +1250,74 @@ struct PrefillPass {
                               slabs, st);
         return linear_f16_nk(x, (const half_t *)w.data, y, T, K, N, EPI_NONE_, nullptr, residual, slabs, st);
     }
-    // act = swiglu(x . Wgu^T) of fp16 / int8 / int4 engines (ffn.cpp:105-122): fused into the projection's epilogue where the plan has
-    // a form, else projection + llmie_silu_and_mul (e.g. fp16 H < 512 at 65-192 rows, int8 H % 256 != 0 at 9-191 rows, weights at
-    // offsets the vector kernels do not take).  Quantised weights at prefill-sized T fuse only where the 256-row SwiGLU grid fills
-    // the chip: the split-K and row-chunk forms the plan has left there cost more than the two launches.
-    int gate_up(const half_t *x, const llmie_matrix &w) const {
-        int rc;
-        const LinearCall gc = linear_call(wqbits ? wqbits : 16, T, H, 2 * I, EPI_SWIGLU_, c.int4_group, x, w.data, w.scale, act, nullptr, nullptr,
-                                          nullptr, nullptr, slabs, wqbits ? deq : nullptr, deq_bytes);
-        if (wqbits && (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && plan_linear_wq(gc).route != LR_REFUSED) {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_wq(wqbits, x, w.data, (const half_t *)w.scale, act, T, H, 2 * I, c.int4_group, EPI_SWIGLU_,
-                                                     nullptr, nullptr, nullptr, nullptr, 0.f, slabs, st, deq, deq_bytes));
-        } else if (!wqbits && plan_linear_f16(gc).route != LR_REFUSED) {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, linear_f16_nk(x, (const half_t *)w.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
-        } else {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(x, w, gu, H, 2 * I, nullptr));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+    // the two norms of the lean (out of place: h stays the residual stream) and general sequences
+    int norm_form(int form) const { return (path == PP_LEAN) == (form == PN_OOP) ? form : -1; }
+    int attn_norm(int form, const llmie_layer_weights &w) const {
+        const half_t *g = (const half_t *)w.attn_norm_gamma;
+        switch (norm_form(form)) {
+            case PN_INPLACE: return llmie_rmsnorm(h, resid, g, c.rms_eps, T, H, LLMIE_F16, stream);
+            case PN_OOP: return rmsnorm_oop_f16(h, resid, g, c.rms_eps, T, H, st);
+            case PN_QUANT: return rmsnorm_quant_f16(h, resid, nullptr, g, c.rms_eps, T, H, false, xqn(), xsn(), st);
+            default: return bad_form("attention norm", form);
         }
-        return LLMIE_OK;
+    }
+    int ffn_norm(int form, const llmie_layer_weights &w) const {
+        const half_t *g = (const half_t *)w.ffn_norm_gamma;
+        switch (norm_form(form)) {
+            case PN_INPLACE: return llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, g, c.rms_eps, T, H, LLMIE_F16, stream);
+            case PN_OOP: return rmsnorm_oop_f16(h, resid, g, c.rms_eps, T, H, st);
+            case PN_QUANT: return rmsnorm_quant_f16(h, resid, (const half_t *)w.o.bias, g, c.rms_eps, T, H, true, xqn(), xsn(), st);
+            default: return bad_form("FFN norm", form);
+        }
     }
     // xs: token scales of e4m3 operands
     int qkv_rope(int l, const llmie_matrix &w, G256Operands ops, const void *x, const float *xs, const void *Wd, const void *wsc) const {
         gemm256_qkv_rope_launch(ops, x, Wd, qkv, T, QKV, H, xs, static_cast<const float *>(wsc), static_cast<const half_t *>(w.bias), rope_args, l, st);
         return launch_status("decoder_prefill(qkv + rope + append)");
     }
-    // the QKV projection of fp16 / int8 / int4 engines; *fused = 1 when its epilogue did RoPE + the cache append
-    int qkv_proj(int l, const llmie_matrix &w, const half_t *x, int *fused) const {
-        *fused = 0;
-        if (rope_fusable && !fp8 && reinterpret_cast<uintptr_t>(w.bias) % 8 == 0) {
-            if (!wqbits && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, w.data, nullptr, qkv)) {
-                *fused = 1;
-                return qkv_rope(l, w, G256_F16, x, nullptr, w.data, nullptr);
-            }
-            // int8 / int4: the route proj() would take -- the eight-phase int8 form, or (int4, and int8 shapes without the in-kernel
-            // form) the fp16 image of the matrix -- with the epilogue on the same kernels
-            const int route = !wqbits ? LR_REFUSED
-                                      : plan_linear_wq(linear_call(wqbits, T, H, QKV, EPI_NONE_, c.int4_group, x, w.data, w.scale, qkv, nullptr, nullptr,
-                                                                   nullptr, nullptr, slabs, deq, deq_bytes)).route;
-            if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(G256_W8, T, QKV, H, x, w.data, w.scale, qkv)) {
-                *fused = 1;
-                return qkv_rope(l, w, G256_W8, x, nullptr, w.data, w.scale);
-            }
-            if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, deq, nullptr, qkv)) {
-                int rc2 = dequantize_weights_f16(wqbits, w.data, static_cast<const half_t *>(w.scale), static_cast<half_t *>(deq), QKV, H, c.int4_group, st);
-                if (rc2) return rc2;
-                *fused = 1;
+    // the QKV projection of the lean and general sequences, on the normalised rows x (the e4m3 forms: on the quantising norm's)
+    int qkv_proj(int l, const llmie_matrix &w, const half_t *x, int form) const {
+        switch (form) {
+            case PQ_PLAIN: return proj(x, w, qkv, H, QKV, nullptr);
+            case PQ_ROPE_F16: return qkv_rope(l, w, G256_F16, x, nullptr, w.data, nullptr);
+            case PQ_ROPE_W8: return qkv_rope(l, w, G256_W8, x, nullptr, w.data, w.scale);
+            case PQ_ROPE_IMAGE:
+                if (int rc = dequantize_weights_f16(wqbits, w.data, static_cast<const half_t *>(w.scale), static_cast<half_t *>(deq), QKV, H, c.int4_group, st)) return rc;
                 return qkv_rope(l, w, G256_F16, x, nullptr, deq, nullptr);
-            }
+            case PQ_ROPE_E4M3: return qkv_rope(l, w, G256_E4M3, xqn(), xsn(), w.data, w.scale);
+            case PQ_PLAIN_E4M3:
+                gemm256_launch(G256_E4M3, xqn(), w.data, qkv, T, QKV, H, nullptr, nullptr, xsn(), (const float *)w.scale, st);
+                return launch_status("decoder_prefill(qkv fp8)");
+            default: return bad_form("QKV", form);
         }
-        return proj(x, w, qkv, H, QKV, nullptr);
     }
-    int attention(int l, const llmie_matrix &wqkv, int fused) const {
-        return prefill_attention_f16(qkv, (const half_t *)wqkv.bias, kv, attn, cum, history_lengths, dec->rope_table, l, batch, T,
-                                     max_q_len, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, c.rotary_dim, st, fused);
+    int attention(int l, const llmie_matrix &wqkv, const PrefillLayerPlan &lp) const {
+        return prefill_attention_f16(lp.attn, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
+                                     c.max_seq_len, c.rotary_dim, st);
+    }
+    // act = swiglu(x . Wgu^T) of the lean and general sequences (ffn.cpp:105-122)
+    int gate_up(const half_t *x, const llmie_matrix &w, int form) const {
+        int rc;
+        switch (form) {
+            case PG_FUSED:
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU,
+                      wqbits ? linear_wq(wqbits, x, w.data, (const half_t *)w.scale, act, T, H, 2 * I, c.int4_group, EPI_SWIGLU_, nullptr, nullptr, nullptr,
+                                         nullptr, 0.f, slabs, st, deq, deq_bytes)
+                             : linear_f16_nk(x, (const half_t *)w.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
+                return LLMIE_OK;
+            case PG_E4M3_SWIGLU:
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, (gemm256_swiglu_launch(G256_E4M3, xqn(), w.data, act, T, 2 * I, H, xsn(), (const float *)w.scale, st),
+                                                launch_status("decoder_prefill(gate_up fp8)")));
+                return LLMIE_OK;
+            case PG_FP8_SWIGLU:
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_linear_fp8_swiglu(x, (const uint8_t *)w.data, (const float *)w.scale, act, T, H, 2 * I, f8ws, f8ws_bytes, stream));
+                return LLMIE_OK;
+            case PG_TWO_LAUNCH:
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(x, w, gu, H, 2 * I, nullptr));
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+                return LLMIE_OK;
+            default: return bad_form("gate/up", form);
+        }
     }
     int packed_only() const {
         int rc;
@@ -1203,27 +1336,26 @@ struct PrefillPass {
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
             const llmie_decoder::PackedLayer &pw = dec->packed[l];
+            const PrefillLayerPlan lp = layer_plan(w);
             TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, resid, w.attn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
-            int fused = 0;
-            if (rope_fusable && reinterpret_cast<uintptr_t>(w.qkv.bias) % 8 == 0 && deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) &&
-                gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, h, deq, nullptr, qkv)) {
-                // (the unpacked fp16 image as the operand of the QKV projection with the RoPE + append epilogue)
-                fused = 1;
-                TIMED(LLMIE_OP_QKV_GEMM, pk_unpack_f16(dec->pk_wf, pw.qkv, static_cast<const half_t *>(w.qkv.scale), static_cast<half_t *>(deq), QKV, H, 0, st));
-                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, G256_F16, h, nullptr, deq, nullptr));
-            } else {
-                TIMED(LLMIE_OP_QKV_GEMM, pproj(pw.qkv, w.qkv.scale, 0, h, qkv, H, QKV, EPI_NONE_, nullptr));
+            switch (lp.qkv) {
+                case PQ_ROPE_UNPACKED:   // (the unpacked fp16 image as the operand of the QKV projection with the RoPE + append epilogue)
+                    TIMED(LLMIE_OP_QKV_GEMM, pk_unpack_f16(dec->pk_wf, pw.qkv, static_cast<const half_t *>(w.qkv.scale), static_cast<half_t *>(deq), QKV, H, 0, st));
+                    TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, G256_F16, h, nullptr, deq, nullptr));
+                    break;
+                case PQ_UNPACK_PLAIN: TIMED(LLMIE_OP_QKV_GEMM, pproj(pw.qkv, w.qkv.scale, 0, h, qkv, H, QKV, EPI_NONE_, nullptr)); break;
+                default: return bad_form("QKV", lp.qkv);
             }
-            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
             TIMED(LLMIE_OP_O_GEMM, pproj(pw.o, w.o.scale, 0, attn, h, H, H, EPI_NONE_, nullptr));
             TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
-            // (the gate_up helper's choice for fp16 weights, on the unpacked image)
-            if (plan_linear_f16(linear_call(16, T, H, 2 * I, EPI_SWIGLU_, 0, h, deq, nullptr, act, nullptr, nullptr, nullptr, nullptr, slabs, nullptr, 0))
-                    .route != LR_REFUSED) {
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, act, H, 2 * I, EPI_SWIGLU_, nullptr));
-            } else {
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, gu, H, 2 * I, EPI_NONE_, nullptr));
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+            switch (lp.gate_up) {
+                case PG_UNPACK_FUSED: TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, act, H, 2 * I, EPI_SWIGLU_, nullptr)); break;
+                case PG_UNPACK_TWO_LAUNCH:
+                    TIMED(LLMIE_OP_GATE_UP_SWIGLU, pproj(pw.gate_up, w.gate_up.scale, 1, h, gu, H, 2 * I, EPI_NONE_, nullptr));
+                    TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+                    break;
+                default: return bad_form("gate/up", lp.gate_up);
             }
             TIMED(LLMIE_OP_DOWN_GEMM, pproj(pw.down, w.down.scale, 0, act, h, I, H, EPI_NONE_, resid));
         }
@@ -1241,18 +1373,19 @@ struct PrefillPass {
         TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, resid, dec->layers[0].attn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
+            const PrefillLayerPlan lp = layer_plan(w);
             const bool last = l + 1 == c.num_layers;
             SplitKSlabs sk;
             TIMED(LLMIE_OP_QKV_GEMM, linear_splitk_partial(sbits, h, w.qkv.data, T, H, QKV, st, &sk, slabs, gs_of(w.qkv)));
-            // (the slab consumer of the QKV projection does RoPE + the cache append as well: one launch less per layer)
-            const bool qfuse = !rope_fuse_off && splitk_finalize_qkv_rope_eligible(sk, c.head_size, qkv, w.qkv.bias);
-            if (qfuse) {
-                TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize_qkv_rope(sk, sc_of(w.qkv), qkv, (const half_t *)w.qkv.bias, kv, cum, history_lengths,
-                                                                  dec->rope_table, l, batch, c.head_num, c.kv_head_num, c.max_seq_len, c.rotary_dim, st));
-            } else {
-                TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize(sk, sc_of(w.qkv), qkv, EPI_NONE_, nullptr, nullptr, st));
+            switch (lp.qkv) {
+                case PQ_SPLITK_ROPE:
+                    TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize_qkv_rope(sk, sc_of(w.qkv), qkv, (const half_t *)w.qkv.bias, kv, cum, history_lengths,
+                                                                      dec->rope_table, l, batch, c.head_num, c.kv_head_num, c.max_seq_len, c.rotary_dim, st));
+                    break;
+                case PQ_SPLITK: TIMED(LLMIE_OP_QKV_GEMM, splitk_finalize(sk, sc_of(w.qkv), qkv, EPI_NONE_, nullptr, nullptr, st)); break;
+                default: return bad_form("QKV", lp.qkv);
             }
-            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, qfuse ? 1 : 0));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
             TIMED(LLMIE_OP_O_GEMM, linear_splitk_partial(sbits, attn, w.o.data, T, H, H, st, &sk, slabs, gs_of(w.o)));
             // context_decoder.cpp: h += resid; resid = h; h += o.bias; h = rmsnorm(h, ffn_gamma)
             TIMED(LLMIE_OP_FFN_NORM, splitk_rownorm(sk, sc_of(w.o), static_cast<const half_t *>(w.o.bias), resid,
@@ -1271,7 +1404,7 @@ struct PrefillPass {
     // `h` for the whole pass -- the O and down projections add into it in their epilogues (y = S, residual = S: every element is read
     // and written by the same lane) and the two norms are out-of-place reads of S into `resid` (used as the projections' input N):
     //   N = norm(S) g1 -> qkv -> attention -> S += attn . Wo^T -> N = norm(S) g2 -> act = swiglu(N . Wgu^T) -> S += act . Wd^T
-    // Same values as the sequence below up to where fp16 roundings fall (o + resid is rounded once instead of twice); each norm
+    // Same values as the general sequence up to where fp16 roundings fall (o + resid is rounded once instead of twice); each norm
     // moves 2 x |S| bytes instead of 3-4 x (context_decoder.cpp:70-199 order).
     // (interleaved A/B on one box, fp16: 1 x 2048 78.15k -> 78.55k tok/s, 8 x 512 89.56k -> 89.87k: the norms drop 13.5 + 15.0 ->
     // 9.7 + 9.7 us per layer, the O projection's residual epilogue costs 6.3 us of that back)
@@ -1280,76 +1413,41 @@ struct PrefillPass {
         half_t *S = h, *Nn = resid;
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
-            TIMED(LLMIE_OP_ATTN_NORM, rmsnorm_oop_f16(S, Nn, (const half_t *)w.attn_norm_gamma, c.rms_eps, T, H, st));
-            int fused;
-            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, Nn, &fused));
-            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
+            const PrefillLayerPlan lp = layer_plan(w);
+            TIMED(LLMIE_OP_ATTN_NORM, attn_norm(lp.attn_norm, w));
+            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, Nn, lp.qkv));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
             TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, S, H, H, S));
-            TIMED(LLMIE_OP_FFN_NORM, rmsnorm_oop_f16(S, Nn, (const half_t *)w.ffn_norm_gamma, c.rms_eps, T, H, st));
-            if ((rc = gate_up(Nn, w.gate_up))) return rc;
+            TIMED(LLMIE_OP_FFN_NORM, ffn_norm(lp.ffn_norm, w));
+            if ((rc = gate_up(Nn, w.gate_up, lp.gate_up))) return rc;
             TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, S, I, H, S));
         }
         return LLMIE_OK;
     }
-    int general() const;
+    // the general sequence (context_decoder.cpp:70-199): every format, any alignment, an output-projection bias
+    int general() const {
+        int rc;
+        for (int l = 0; l < c.num_layers; ++l) {
+            const llmie_layer_weights &w = dec->layers[l];
+            const PrefillLayerPlan lp = layer_plan(w);
+            TIMED(LLMIE_OP_ATTN_NORM, attn_norm(lp.attn_norm, w));
+            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, h, lp.qkv));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
+            TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, h, H, H, nullptr));
+            TIMED(LLMIE_OP_FFN_NORM, ffn_norm(lp.ffn_norm, w));
+            if ((rc = gate_up(h, w.gate_up, lp.gate_up))) return rc;
+            TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
+        }
+        return LLMIE_OK;
+    }
 };
 
-// ---- the general sequence (context_decoder.cpp:70-199): every format, any alignment, an output-projection bias ----
-int PrefillPass::general() const {
-    int rc;
-    // fp8, prefill-sized: the two RMSNorms emit the e4m3 activations of the projection behind them (norm.hip
-    // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are
-    const bool nq = fp8 && T > 8 && H % 128 == 0 && rmsnorm_quant_eligible(H);
-    uint8_t *xqn = static_cast<uint8_t *>(f8ws);
-    float *xsn = reinterpret_cast<float *>(xqn + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255)));
-    auto tiled_fp8 = [&](const llmie_matrix &w, int N) {
-        return nq && gemm256_fills(T, N) && N % 4 == 0 && (reinterpret_cast<uintptr_t>(w.data) | reinterpret_cast<uintptr_t>(w.scale)) % 16 == 0;
-    };
-    for (int l = 0; l < c.num_layers; ++l) {
-        const llmie_layer_weights &w = dec->layers[l];
-        int fused = 0;
-        if (tiled_fp8(w.qkv, QKV)) {
-            TIMED(LLMIE_OP_ATTN_NORM, rmsnorm_quant_f16(h, resid, nullptr, (const half_t *)w.attn_norm_gamma, c.rms_eps, T, H, false, xqn, xsn, st));
-            if (rope_fusable && reinterpret_cast<uintptr_t>(w.qkv.bias) % 8 == 0 &&
-                gemm256_qkv_rope_eligible(G256_E4M3, T, QKV, H, xqn, w.qkv.data, w.qkv.scale, qkv)) {
-                fused = 1;
-                TIMED(LLMIE_OP_QKV_GEMM, qkv_rope(l, w.qkv, G256_E4M3, xqn, xsn, w.qkv.data, w.qkv.scale));
-            } else {
-                TIMED(LLMIE_OP_QKV_GEMM, (gemm256_launch(G256_E4M3, xqn, w.qkv.data, qkv, T, QKV, H, nullptr, nullptr, xsn, (const float *)w.qkv.scale, st),
-                                          launch_status("decoder_prefill(qkv fp8)")));
-            }
-        } else {
-            TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, resid, w.attn_norm_gamma, c.rms_eps, T, H, LLMIE_F16, stream));
-            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, h, &fused));
-        }
-        TIMED(LLMIE_OP_MHA, attention(l, w.qkv, fused));
-        TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, h, H, H, nullptr));
-        const bool gu_fused8 = fp8 && gemm256_swiglu_fills(T, 2 * I) && H % 128 == 0 && reinterpret_cast<uintptr_t>(w.gate_up.data) % 16 == 0;
-        if (nq && gu_fused8 && w.ffn_norm_gamma && reinterpret_cast<uintptr_t>(w.gate_up.scale) % 16 == 0) {
-            TIMED(LLMIE_OP_FFN_NORM, rmsnorm_quant_f16(h, resid, (const half_t *)w.o.bias, (const half_t *)w.ffn_norm_gamma, c.rms_eps, T, H, true,
-                                                       xqn, xsn, st));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, (gemm256_swiglu_launch(G256_E4M3, xqn, w.gate_up.data, act, T, 2 * I, H, xsn, (const float *)w.gate_up.scale, st),
-                                            launch_status("decoder_prefill(gate_up fp8)")));
-            TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
-            continue;
-        }
-        TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, T, H,
-                                                                       LLMIE_F16, stream));
-        // ffn.cpp:105-122: act = silu(h.Wg^T) * (h.Wu^T); SwiGLU fused into the projection's epilogue where a fused form exists
-        if (!fp8) {
-            if ((rc = gate_up(h, w.gate_up))) return rc;
-        } else if (gu_fused8) {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_linear_fp8_swiglu(h, (const uint8_t *)w.gate_up.data, (const float *)w.gate_up.scale,
-                                                                   act, T, H, 2 * I, f8ws, f8ws_bytes, stream));
-        } else {
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(h, w.gate_up, gu, H, 2 * I, nullptr));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
-        }
-        TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
-    }
+static int prefill_shape_ok(const llmie_decoder_config &c, int batch, int num_tokens, int max_q_len) {
+    LLMIE_REQUIRE(batch >= 1 && num_tokens >= 1 && max_q_len >= 1 && max_q_len <= num_tokens && max_q_len <= c.max_seq_len,
+                  "decoder_prefill: bad shape batch=%d tokens=%d max_q_len=%d", batch, num_tokens, max_q_len);
+    LLMIE_REQUIRE(num_tokens <= static_cast<long long>(batch) * max_q_len, "decoder_prefill: num_tokens > batch*max_q_len");
     return LLMIE_OK;
 }
-
 // both prefill entry points: validate, plan, refuse or: carve the workspace, copy hidden_in, set up what the sequences share, dispatch
 static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache, void *v_cache,
                            const int32_t *block_table, int max_pages, int num_pages, const int32_t *input_lengths,
@@ -1358,9 +1456,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     LLMIE_REQUIRE(dec && hidden_in && hidden_out && k_cache && v_cache && input_lengths && history_lengths && workspace,
                   "decoder_prefill: NULL pointer");
     const llmie_decoder_config &c = dec->cfg;
-    LLMIE_REQUIRE(batch >= 1 && num_tokens >= 1 && max_q_len >= 1 && max_q_len <= num_tokens && max_q_len <= c.max_seq_len,
-                  "decoder_prefill: bad shape batch=%d tokens=%d max_q_len=%d", batch, num_tokens, max_q_len);
-    LLMIE_REQUIRE(num_tokens <= static_cast<long long>(batch) * max_q_len, "decoder_prefill: num_tokens > batch*max_q_len");
+    if (int rc = prefill_shape_ok(c, batch, num_tokens, max_q_len)) return rc;
     const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
     const EngineSwitches &sw = engine_switches();
     PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw};
@@ -1389,22 +1485,17 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     const bool fp8 = c.wfmt == LLMIE_W_FP8;
     int32_t *pad = (int32_t *)(base + o.pad), *cum = (int32_t *)(base + o.cum);
     int32_t *tok_b = (int32_t *)(base + o.tokens + 256), *tok_tpos = tok_b + T;
-    PrefillPass p{dec, c, stream, st, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), cum, history_lengths, batch, T, max_q_len,
+    PrefillPass p{dec, c, call, plan.path, stream, st, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), cum, history_lengths, batch, T, max_q_len,
                   H, QKV, I, fp8, c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0),
                   (half_t *)hidden_out, (half_t *)(base + o.resid), (half_t *)(base + o.qkv), (half_t *)(base + o.attn), (half_t *)(base + o.gu),
                   (half_t *)(base + o.act), base + o.fp8_ws, fp8 ? llmie_linear_fp8_workspace_bytes(T, I > H ? I : H, 0) : 0,
                   SlabWs{reinterpret_cast<float *>(base + o.slabs), prefill_slab_floats(&c, T)}, base + o.deq, o.tokens - o.deq,
-                  (QkvRopeArgs *)(base + o.tokens), sw.no_qkv_rope_fusion, false};
+                  (QkvRopeArgs *)(base + o.tokens)};
     int rc;
     // context_decoder.cpp:70: exclusive prefix of the lengths (padding offsets are a by-product nobody needs here);
     // the prefix kernel takes [batch, max_q_len] with max_q_len = ceil(T / batch) rows worth of scratch -> use 1 row of T
     if ((rc = llmie_cal_padding_offset(pad, cum, input_lengths, batch, (T + batch - 1) / batch, stream))) return rc;
-    // Round 3: RoPE + KV-cache append as the EPILOGUE of the QKV projection (context_attention.cpp:158-205 in one launch sequence;
-    // gemm8p.cuh ROPE forms): q is rotated on its way into the packed QKV buffer, k / v go straight to their cache slots and never
-    // travel through the buffer; bit-identical to projection + prefill_rope_append_kernel (same arithmetic on the fp16-rounded
-    // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.
-    p.rope_fusable = !p.rope_fuse_off && T >= kWqPrefillRows && gemm256_fills(T, QKV);
-    if (p.rope_fusable) {
+    if (prefill_rope_fusable(call)) {   // the token table of the QKV projection's RoPE + append epilogue
         QkvRopeArgs ra{};
         ra.k_cache = p.kv.k;
         ra.v_cache = p.kv.v;
@@ -1445,6 +1536,46 @@ extern "C" int llmie_decoder_prefill_paged(llmie_decoder *dec, const void *hidde
     if (int rc = paged_args_ok(dec, block_table, max_pages, num_pages, "decoder_prefill_paged")) return rc;
     return decoder_prefill(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, input_lengths, history_lengths, batch,
                            num_tokens, max_q_len, workspace, workspace_bytes, stream);
+}
+
+// Host-only: what one layer of llmie_decoder_prefill launches (include/llmie.h) -- the pass's plan_prefill, plan_prefill_layer for a
+// layer whose operands follow the call flags, and its plan_prefill_attn, as text
+extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_config *cfg, int tokens, int batch, int max_q_len, unsigned call_flags,
+                                                        unsigned switch_mask, int *status) {
+    static thread_local char text[384];
+    const int rc = [&]() -> int {
+        LLMIE_REQUIRE(config_ok(cfg), "decoder_prefill_layer_plan: invalid config");
+        if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !packed_wf(cfg))
+            LLMIE_UNSUPPORTED("decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take");
+        if (int bad = prefill_shape_ok(*cfg, batch, tokens, max_q_len)) return bad;
+        const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
+        const PrefillPlan plan = plan_prefill(call);
+        if (plan.path == PP_REFUSED) return prefill_refuse(plan);
+        const PrefillCarve o = prefill_carve(cfg, tokens, batch);
+        const bool scales = cfg->wfmt != LLMIE_W_F16;   // (fp16 engines have none: a null pointer)
+        const unsigned mis_w = (call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED) ? 8u : 0u, mis_s = scales && (call_flags & LLMIE_PLAN_SCALES_MISALIGNED) ? 2u : 0u;
+        const PrefillLayerPlan lp = plan_prefill_layer(
+            call, plan.path, batch, max_q_len,
+            PrefillLayerCall{mis_w, mis_s, (call_flags & LLMIE_PLAN_QKV_BIAS_MISALIGNED) ? 4u : 0u, mis_w,
+                             mis_s + (scales && (call_flags & LLMIE_PLAN_GATE_UP_SCALES_MISALIGNED) ? 8u : 0u),
+                             (call_flags & LLMIE_PLAN_HIDDEN_MISALIGNED) ? 8u : 0u, !(call_flags & LLMIE_PLAN_NO_FFN_GAMMA), prefill_slab_floats(cfg, tokens),
+                             o.tokens - o.deq});
+        static const char *const norms[] = {"none", "inplace", "oop", "quant", "rownorm"};
+        static const char *const qkvs[] = {"plain", "rope_f16", "rope_w8", "rope_image", "plain_e4m3", "rope_e4m3", "unpack_plain", "rope_unpacked", "splitk", "splitk_rope"};
+        static const char *const gus[] = {"fused", "two_launch", "e4m3_swiglu", "fp8_swiglu", "unpack_fused", "unpack_two_launch", "splitk"};
+        static const char *const ops[] = {"attn_norm", "qkv_gemm", "rope", "mha", "o_gemm", "ffn_norm", "gate_up_swiglu", "down_gemm"};
+        const char *pre = lp.qkv == PQ_ROPE_IMAGE ? "dequant" : (lp.qkv == PQ_UNPACK_PLAIN || lp.qkv == PQ_ROPE_UNPACKED ? "unpack" : "none");
+        const PrefillAttnPlan &a = lp.attn;
+        int n = snprintf(text, sizeof(text), "%s token_table=%d attn_norm=%s qkv=%s pre=%s rope_done=%d attn=q%dw%dt%d kv=%s grid=%dx%dx%d rope_append=%d "
+                         "ffn_norm=%s gate_up=%s launches", prefill_path_name(plan.path), prefill_rope_fusable(call) ? 1 : 0, norms[lp.attn_norm], qkvs[lp.qkv],
+                         pre, lp.rope_done ? 1 : 0, a.q_rows, a.waves, a.row_tiles, a.kv_e4m3 ? "e4m3" : "f16", a.grid[0], a.grid[1], a.grid[2],
+                         a.rope_append ? 1 : 0, norms[lp.ffn_norm], gus[lp.gate_up]);
+        for (int op = 0; op <= LLMIE_OP_DOWN_GEMM; ++op)
+            if (lp.launches[op]) n += snprintf(text + n, sizeof(text) - n, " %s=%d", ops[op], lp.launches[op]);
+        return LLMIE_OK;
+    }();
+    if (status) *status = rc;
+    return rc == LLMIE_OK ? text : nullptr;
 }
 
 // the sampler operands of llmie_lm_head_sample_params (checked by sample_logits_check)

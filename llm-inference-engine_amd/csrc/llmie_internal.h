@@ -271,12 +271,18 @@ int decode_tail(const int32_t *tmp_ids, const void *tmp_vals, int32_t *ids, void
                 int32_t *out_id, int rows, int step, int32_t *step_dev, int end_id, int vocab, const void *embed, void *next_hidden, int hidden,
                 int advance, unsigned *ticket, llmie_dtype dtype, hipStream_t st);
 
-// prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip
-int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, const KvView &kv, half_t *out,
-                          const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch,
-                          int num_tokens, int max_q_len, int head_num, int kv_head_num, int head_size, int max_seq_len,
-                          int rotary_dim, hipStream_t st,
-                          int rope_done = 0 /* RoPE + append already done by the QKV projection's epilogue (gemm256_qkv_rope_launch) */);
+// prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip: one pure host planner decides the
+// launch, one launcher runs the plan
+struct PrefillAttnPlan {
+    int q_rows, waves, row_tiles;   // prefill_flash_kernel<128, kv_e4m3, waves, row_tiles>: q_rows query rows per workgroup
+    bool kv_e4m3;
+    int grid[3];                    // (query tiles of the longest sequence, head_num, batch)
+    bool rope_append;               // prefill_rope_append_kernel runs first (else the QKV projection's epilogue did RoPE + the append)
+};
+PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done);
+int prefill_attention_f16(const PrefillAttnPlan &plan, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
+                          const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st);
 // short prefills: slab consumer of the QKV projection with RoPE + KV-cache append folded in (q -> qkv, k / v -> the caches only)
 bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, const void *qkv, const void *bias);
 int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,

@@ -558,20 +558,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
 }
 
-int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, const KvView &kv, half_t *out,
-                          const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int batch,
-                          int num_tokens, int max_q_len, int head_num, int kv_head_num, int head_size, int max_seq_len,
-                          int rotary_dim, hipStream_t st, int rope_done) {
-    void *k_cache = kv.k, *v_cache = kv.v;
-    const int32_t *block_table = kv.block_table;
-    const int max_pages = kv.max_pages, num_pages = kv.num_pages, kv_fp8 = kv.fp8;
-    const float k_scale = kv.k_scale, v_scale = kv.v_scale;
-    if (head_size != 128) {
-        set_error("prefill attention: head_size %d not supported by the flash kernel (128 only)", head_size);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    const size_t layer_off = block_table ? static_cast<size_t>(layer) * num_pages * kv_head_num * 128 * head_size
-                                         : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * head_size;
+// Which flash instantiation a prefill attention launch runs, its grid, and whether the RoPE + append launch goes in front.  Pure host code.
+PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done) {
     // 128 query rows per workgroup either way: 8 waves x 16 rows (one workgroup per CU at a time, dynamic rounds, longest first), or
     // 4 waves x 2 x 16 rows (every fragment read from LDS feeds two MFMAs; two workgroups per CU, out of phase with each other).
     // Measured (bench, same box, us per layer): 8 x 512 tokens 54.5 -> 47.5 and 16 x 256 tokens 38 with the 4-wave form; 1 x 2048
@@ -584,27 +572,34 @@ int prefill_attention_f16(half_t *qkv, const half_t *qkv_bias, const KvView &kv,
     // (interleaved A/B, 7B, one sequence: 128 tokens 27.8k -> 28.1k tok/s, 256 32.6k -> 32.9k, 512 46.0k -> 46.6k, 768 equal)
     const bool bq64 = ((max_q_len + 127) / 128) * head_num * batch < 256;
     const int bq = bq64 ? 64 : 128;
-    dim3 grid((max_q_len + bq - 1) / bq, head_num, batch);
-    const float ks = kv_fp8 ? k_scale : 1.f, vs = kv_fp8 ? v_scale : 1.f;
-    if (rope_done) {   // the QKV projection's epilogue rotated q in `qkv` and wrote k / v into the caches
-    } else if (kv_fp8)
-        prefill_rope_append_kernel<128, true><<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, k_cache, v_cache, cum_seqlens, history_len,
-                                                                          rope, batch, head_num, kv_head_num, max_seq_len,
-                                                                          rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, block_table, max_pages);
-    else
-        prefill_rope_append_kernel<128, false><<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, k_cache, v_cache, cum_seqlens, history_len,
-                                                                           rope, batch, head_num, kv_head_num, max_seq_len,
-                                                                           rotary_dim, layer_off, 1.f, 1.f, block_table, max_pages);
-#define LLMIE_FLASH(KV8_, NW_, RT_)                                                                                                      \
-    prefill_flash_kernel<128, KV8_, NW_, RT_><<<grid, NW_ * 64, 0, st>>>(qkv, k_cache, v_cache, out, cum_seqlens, history_len, head_num, \
-                                                                         kv_head_num, max_seq_len, layer_off, ks, vs, block_table, max_pages)
-    if (kv_fp8 && bq64) LLMIE_FLASH(true, 4, 1);
-    else if (bq64) LLMIE_FLASH(false, 4, 1);
-    else if (kv_fp8 && rt2) LLMIE_FLASH(true, 4, 2);
-    else if (kv_fp8) LLMIE_FLASH(true, 8, 1);
-    else if (rt2) LLMIE_FLASH(false, 4, 2);
-    else LLMIE_FLASH(false, 8, 1);
-#undef LLMIE_FLASH
+    return PrefillAttnPlan{bq, bq64 || rt2 ? 4 : 8, !bq64 && rt2 ? 2 : 1, kv_e4m3, {(max_q_len + bq - 1) / bq, head_num, batch}, !rope_done};
+}
+
+// g.grid[1] / g.grid[2] are head_num / batch
+int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
+                          const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st) {
+    const int head_num = g.grid[1], batch = g.grid[2];
+    const size_t layer_off = kv.block_table ? static_cast<size_t>(layer) * kv.num_pages * kv_head_num * 128 * 128
+                                            : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * 128;
+    const float ks = g.kv_e4m3 ? kv.k_scale : 1.f, vs = g.kv_e4m3 ? kv.v_scale : 1.f;
+    if (g.rope_append) {   // (else the QKV projection's epilogue rotated q in `qkv` and wrote k / v into the caches)
+        auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true> : prefill_rope_append_kernel<128, false>;
+        append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
+                                           rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages);
+    }
+    decltype(&prefill_flash_kernel<128, false, 4, 1>) flash = nullptr;
+    switch ((g.kv_e4m3 ? 100 : 0) + g.waves * 10 + g.row_tiles) {
+        case 41: flash = prefill_flash_kernel<128, false, 4, 1>; break;
+        case 42: flash = prefill_flash_kernel<128, false, 4, 2>; break;
+        case 81: flash = prefill_flash_kernel<128, false, 8, 1>; break;
+        case 141: flash = prefill_flash_kernel<128, true, 4, 1>; break;
+        case 142: flash = prefill_flash_kernel<128, true, 4, 2>; break;
+        case 181: flash = prefill_flash_kernel<128, true, 8, 1>; break;
+        default: set_error("prefill attention: no flash kernel of %d waves x %d row tiles", g.waves, g.row_tiles); return LLMIE_ERR_UNSUPPORTED;
+    }
+    flash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), g.waves * 64, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num,
+                                                                       max_seq_len, layer_off, ks, vs, kv.block_table, kv.max_pages);
     return launch_status("prefill_attention");
 }
 

@@ -41,7 +41,7 @@ int main() {
     for (int rep = 0; rep < 5; ++rep) {
         hipEventRecord(e0);
         // rope_done = 1: the flash kernel alone (the caches are filled above)
-        prefill_attention_f16(qkv, nullptr, kv_dense(kc, vc), out, cum, hist, rope, 0, 1, T, T, nh, nh, hs, max_seq, hs, nullptr, 1);
+        prefill_attention_f16(plan_prefill_attn(1, T, nh, false, true), kv_dense(kc, vc), qkv, nullptr, out, cum, hist, rope, 0, T, nh, max_seq, hs, nullptr);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         float ms;
