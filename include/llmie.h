@@ -45,7 +45,7 @@ extern "C" {
  *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan; masks, logit bias,
  *      stop sets and top-N log-probabilities in the sampler: llmie_sampling_ext, llmie_sample_logits_ext,
  *      llmie_lm_head_sample_ext; several hypotheses per request: llmie_beam_step(_workspace_bytes),
- *      llmie_kv_pages_fork(_workspace_bytes)). */
+ *      llmie_kv_pages_fork(_workspace_bytes); speculative decoding: llmie_spec_verify(_workspace_bytes), llmie_ngram_draft). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -667,6 +667,70 @@ int llmie_kv_pages_fork(void *k_pool, void *v_pool, int32_t *block_table /* [row
                         int32_t *cached_len /* [rows] in/out */, int rows, int layers, int kv_head_num, int head_size,
                         int max_pages, int num_pages, int elem_bytes, void *workspace, size_t workspace_bytes,
                         llmie_stream stream);
+
+/* ABI 3 (an addition).  Speculative decoding behind the logits.  No reference launcher.  The forward over a chunk of k + 1
+ * inputs per sequence is llmie_decoder_prefill(_paged) on top of the cached history; these two entries are what follows the
+ * logits, and a drafter that needs no second model.  Rejection sampling against a full draft distribution is out of scope.
+ *
+ * llmie_spec_verify: EXACT-MATCH verification.  logits [batch * (k + 1), vocab]: row r = b * (k + 1) + i holds the logits that
+ * follow input i of sequence b; input 0 is the last emitted token, input i >= 1 is draft_ids[b, i - 1].  s_b, the Philox step of
+ * sequence b, is step_rows[b] if step_rows != NULL, else *step_dev if step_dev != NULL, else `step`.  For a sequence with
+ * finished[b] == 0 on entry, pick_i is the token llmie_sample_logits_ext returns for row (b, i) alone at step s_b + i, with
+ * the parameters of b, the ext arrays of b, and the history of b as i preceding calls would have left it: history_append != 0:
+ * the old history followed by pick_0 .. pick_{i-1} as far as history_stride lets them be appended; history_append == 0: the
+ * history unchanged.  (The sampler is deterministic -- Philox keyed by (step, seed), fixed-point masses -- so pick_i is THE
+ * token plain decoding would have emitted.)  Emission walks i = 0, 1, ...: emit pick_i; stop behind it if i == draft_len[b]
+ * (draft_len == NULL: k; clamped to [0, k]), if pick_i != draft_ids[b, i], or if pick_i finishes the sequence (end_id or one of
+ * the row's stop ids: step 8 of llmie_sample_logits_ext); otherwise go on.  count, in [1, k + 1], is the number of emitted tokens:
+ * bit for bit what `count` successive llmie_sample_logits_ext calls emit from these rows, for greedy and for every control.
+ *   out_tokens[b, 0..count) the emitted tokens, later slots -1;  out_count[b] = count;
+ *   out_logprob[b, i] (may be NULL) the raw log-softmax of emitted token i as the sampler's out_logprob, later slots -INFINITY;
+ *   seq_len, finished, history, history_len: exactly as behind those `count` sequential calls;
+ *   last_token[b] (may be NULL) = out_tokens[b, count - 1];  cached_len[b] (may be NULL) += count: input 0 and the accepted
+ *   drafts are now valid cache rows;  step_rows[b] (may be NULL) += count.
+ * A sequence with finished[b] != 0 on entry is left alone -- out_count = 0, out_tokens all -1, out_logprob all -INFINITY, no state
+ * changes -- the one deliberate departure from the plain sampler, which samples finished rows again.
+ * ext (may be NULL): per-request arrays are indexed by b (bias, stops, min_step -- compared with s_b + i -- and the mask row
+ * when mask_index == NULL); mask_index, if given, is [batch * (k + 1)], indexed by r (a grammar has one mask per position);
+ * out_top_ids / out_top_logprobs are [batch * (k + 1), top_n], indexed by r, and written for EVERY row, rejected positions and
+ * finished sequences included: they are a property of the raw logits.
+ * Refused on the host before any launch: first whatever llmie_sample_logits_ext refuses (out_tokens in the place of out_id),
+ * then LLMIE_ERR_INVALID_ARG: k < 1, NULL draft_ids / out_tokens / out_count; LLMIE_ERR_UNSUPPORTED: k > LLMIE_SPEC_MAX_DRAFT;
+ * LLMIE_ERR_WORKSPACE: NULL, short (llmie_spec_verify_workspace_bytes; 0 for non-positive or unsupported sizes) or not 16-byte
+ * aligned.
+ * Two launches (one 1024-thread workgroup per row runs the sampler's body on a history view that splices draft_ids[b, 0..i)
+ * behind the stored history -- whenever position i matters the earlier picks equal the earlier drafts, so the positions of a
+ * sequence run side by side; then one pass per sequence walks the picks).  No allocation, no synchronisation, legal inside a
+ * graph capture: every operand is read on the device.  No float atomics; same inputs, same bits; a sequence's outputs depend
+ * neither on its slot nor on the other sequences. */
+#define LLMIE_SPEC_MAX_DRAFT 15
+size_t llmie_spec_verify_workspace_bytes(int batch, int k, int vocab);
+int llmie_spec_verify(const void *logits /* [batch*(k+1), vocab], row r = b*(k+1)+i */, int batch, int k, int vocab,
+                      const int32_t *draft_ids /* [batch, k] */, const int32_t *draft_len /* [batch], NULL = k; clamped to [0,k] */,
+                      const llmie_sampling_params *params_dev /* [batch] */, int32_t *history, int history_stride,
+                      int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                      int32_t *out_tokens /* [batch, k+1] */, int32_t *out_count /* [batch] */, float *out_logprob /* [batch,k+1], nullable */,
+                      int32_t *last_token /* [batch], nullable */, int32_t *cached_len /* [batch], nullable, in/out */,
+                      int32_t *step_rows /* [batch], nullable, in/out */, int step, const int32_t *step_dev, int end_id,
+                      void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream,
+                      const llmie_sampling_ext *ext /* nullable */);
+
+/* ABI 3 (an addition).  llmie_ngram_draft: prompt-lookup drafting.  tokens [batch, stride] holds each sequence's tokens so far
+ * (prompt included), len [batch] their count; they may be the sampler's history / history_len when the caller put the prompt
+ * there.  Per sequence, L = len[b] clamped to [0, stride].  out_ids[b, 0] = tokens[b, L - 1] (pad_id when L == 0): the last
+ * emitted token, input 0 of the verify chunk.  No drafts (out_draft_len[b] = 0) when finished != NULL and finished[b] != 0, or
+ * L < min_n + 1.  Otherwise, for n = min(max_n, L - 1) down to min_n, with S = tokens[L - n .. L): a match is a start
+ * p <= L - n - 1 with tokens[p .. p + n) == S; of the matches take the largest p with p + n + k <= L (a full continuation), if
+ * there is none the largest p at all; the first n with a match wins.  m = min(k, L - p - n) and the drafts are
+ * tokens[p + n .. p + n + m): out_draft_ids[b, 0..m), out_ids[b, 1..m], out_draft_len[b] = m.  Slots past m hold pad_id.
+ * 1 <= min_n <= max_n <= 8 and 1 <= k <= LLMIE_SPEC_MAX_DRAFT (LLMIE_ERR_INVALID_ARG below, LLMIE_ERR_UNSUPPORTED above the
+ * bounds); stride is any positive value.  One launch, one workgroup per sequence, one sweep over the row for every n at once
+ * (16-byte loads where the row is 16-byte aligned); "the largest p" is an integer maximum: same inputs, same bits.  No
+ * allocation, no synchronisation, legal inside a graph capture. */
+int llmie_ngram_draft(const int32_t *tokens /* [batch, stride] */, int stride, const int32_t *len /* [batch] */,
+                      const uint8_t *finished /* nullable */, int batch, int k, int max_n, int min_n, int pad_id,
+                      int32_t *out_ids /* [batch, k+1]: the verify chunk's input ids */, int32_t *out_draft_ids /* [batch, k] */,
+                      int32_t *out_draft_len /* [batch] */, llmie_stream stream);
 
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,
  * context_attention.cpp:143-312) on PACKED tokens: hidden_in/out [num_tokens, H] hold the sequences back to back

@@ -112,6 +112,10 @@ _SIGS = {
     "llmie_beam_step": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _sz, _i, _vp],
     "llmie_kv_pages_fork_workspace_bytes": [_i, _i, _i, _i, _i, _i],
     "llmie_kv_pages_fork": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp],
+    "llmie_spec_verify_workspace_bytes": [_i, _i, _i],
+    "llmie_spec_verify": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz,
+                          _i, _vp, _vp],
+    "llmie_ngram_draft": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -139,6 +143,7 @@ _RESTYPES = {
     "llmie_score_tokens_workspace_bytes": _sz,
     "llmie_beam_step_workspace_bytes": _sz,
     "llmie_kv_pages_fork_workspace_bytes": _sz,
+    "llmie_spec_verify_workspace_bytes": _sz,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -540,13 +545,15 @@ def _i32(x, device):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64).astype(np.int32))).to(device)
 
 
-def sampling_ext(batch, vocab, masks=None, mask_index=None, bias=None, stops=None, min_step=None, top_n=0, device="cuda"):
+def sampling_ext(batch, vocab, masks=None, mask_index=None, bias=None, stops=None, min_step=None, top_n=0, device="cuda", rows=None):
     """Build the device arrays of a llmie_sampling_ext for `batch` rows over `vocab` tokens (-> SamplingExtArrays).
     masks: bool [rows, vocab] (packed here), or words [rows, stride >= ceil(vocab / 32)] as a numpy uint32 / int32 array or an
     int32 tensor.  mask_index: [batch] ints, None = row b uses mask row b.  bias: per row a list of (id, value) pairs (or a
-    dict).  stops: per row a list of ids.  min_step: [batch] ints.  top_n: alternatives to return per row."""
+    dict).  stops: per row a list of ids.  min_step: [batch] ints.  top_n: alternatives to return per row.  rows: the entries of
+    mask_index and the rows of the top-N outputs where they differ from batch (spec_verify: batch * (k + 1), one per position)."""
     import numpy as np
     import torch
+    rows_n = batch if rows is None else rows
     x = SamplingExtArrays()
     e = x.struct
     if masks is not None:
@@ -592,13 +599,13 @@ def sampling_ext(batch, vocab, masks=None, mask_index=None, bias=None, stops=Non
     if min_step is not None:
         x.min_step = _i32(min_step, device)
         e.min_step = x.min_step.data_ptr()
-    for name in ("mask_index", "min_step"):
+    for name, want in (("mask_index", rows_n), ("min_step", batch)):
         t = getattr(x, name)
-        if t is not None and t.numel() != batch:
-            raise LlmieError("sampling_ext: %s has %d entries, batch is %d" % (name, t.numel(), batch))
+        if t is not None and t.numel() != want:
+            raise LlmieError("sampling_ext: %s has %d entries, %d expected" % (name, t.numel(), want))
     if top_n:
-        x.top_ids = torch.full((batch, top_n), -2, dtype=torch.int32, device=device)
-        x.top_logprobs = torch.zeros((batch, top_n), dtype=torch.float32, device=device)
+        x.top_ids = torch.full((rows_n, top_n), -2, dtype=torch.int32, device=device)
+        x.top_logprobs = torch.zeros((rows_n, top_n), dtype=torch.float32, device=device)
         e.top_n, e.out_top_ids, e.out_top_logprobs = top_n, x.top_ids.data_ptr(), x.top_logprobs.data_ptr()
     return x
 
@@ -947,6 +954,78 @@ def kv_pages_fork(k_pool, v_pool, block_table, own_table, parent, cached_len, wo
     _check(lib().llmie_kv_pages_fork(_p(k_pool), _p(v_pool), _p(block_table), _p(own_table), _p(parent), _p(cached_len), rows, L, kvh,
                                      hs, max_pages, num_pages, k_pool.element_size(), _p(workspace),
                                      0 if workspace is None else workspace.numel() * workspace.element_size(), _st()), "kv_pages_fork")
+
+
+# ------------------------------------------------------------------ speculative decoding
+SPEC_MAX_DRAFT = 15  # LLMIE_SPEC_MAX_DRAFT
+NGRAM_MAX_N = 8
+_spec_scratch = {}
+
+
+class SpecState:
+    """last_token, cached_len, step_rows: int32 [batch] each, what llmie_spec_verify moves in place.  The loop's invariant:
+    cached_len[b] tokens of sequence b have K / V in the cache, last_token[b] is emitted but not yet cached, step_rows[b] is the
+    Philox step of the next pick.  The tensors can be overwritten in place -- a captured graph reads them on replay."""
+
+    def __init__(self, last_token, cached_len, step_rows):
+        self.last_token, self.cached_len, self.step_rows = last_token, cached_len, step_rows
+
+
+def spec_state(last_token, cached_len, step_rows=None, device="cuda"):
+    """state behind a prefill: last_token = the first emitted token of each sequence, cached_len = its prompt length,
+    step_rows = the step of its next pick (default 0).  Lists or tensors; built on the host, moved to `device`."""
+    import torch
+    n = len(last_token)
+    if len(cached_len) != n or (step_rows is not None and len(step_rows) != n):
+        raise LlmieError("spec_state: last_token, cached_len and step_rows must have one entry per sequence")
+    mk = lambda v: torch.as_tensor(v, dtype=torch.int32).clone().to(device)
+    return SpecState(mk(last_token), mk(cached_len), mk([0] * n if step_rows is None else step_rows))
+
+
+def spec_verify_workspace_bytes(batch, k, vocab):
+    return lib().llmie_spec_verify_workspace_bytes(batch, k, vocab)
+
+
+def spec_verify(logits, draft_ids, params, seq_len, finished, end_id, state=None, draft_len=None, history=None, history_len=None,
+                append=False, out_logprob=None, step=0, step_dev=None, workspace="auto", ext=None, out=None):
+    """llmie_spec_verify on logits [batch * (k + 1), vocab] (fp16 / fp32, read-only; row b * (k + 1) + i follows input i of
+    sequence b) and draft_ids int32 [batch, k]: returns (tokens int32 [batch, k + 1], count int32 [batch]) and moves seq_len,
+    finished, the history and `state` (a SpecState, or None: the Philox step is *step_dev or `step` for every sequence) as
+    `count` sequential sample_logits calls would.  draft_len: int32 [batch] or None (= k).  ext: sampling_ext(...) whose
+    mask_index / top-N arrays have batch * (k + 1) rows.  out: a (tokens, count) pair to write into.  workspace: a device tensor
+    of spec_verify_workspace_bytes(batch, k, vocab) bytes, or the string auto (inside a graph capture pass a tensor, or make a
+    first call outside)."""
+    import torch
+    batch, k = draft_ids.shape
+    rows, vocab = logits.shape
+    if rows != batch * (k + 1):
+        raise LlmieError("spec_verify: %d rows of logits for %d sequences of %d + 1 positions" % (rows, batch, k))
+    if isinstance(workspace, str):
+        workspace = _grow(_spec_scratch, logits.device, spec_verify_workspace_bytes(batch, k, vocab))
+    tokens, count = out if out is not None else (torch.empty((batch, k + 1), dtype=torch.int32, device=logits.device),
+                                                 torch.empty(batch, dtype=torch.int32, device=logits.device))
+    stride = 0 if history is None else history.shape[1]
+    st = state if state is not None else SpecState(None, None, None)
+    _check(lib().llmie_spec_verify(_p(logits), batch, k, vocab, _p(draft_ids), _p(draft_len), _p(params), _p(history), stride,
+                                   _p(history_len), 1 if append else 0, _p(seq_len), _p(finished), _p(tokens), _p(count), _p(out_logprob),
+                                   _p(st.last_token), _p(st.cached_len), _p(st.step_rows), step, _p(step_dev), end_id, _p(workspace),
+                                   0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(logits), _st(),
+                                   None if ext is None else _ext_ref(ext)), "spec_verify")
+    return tokens, count
+
+
+def ngram_draft(tokens, length, k, max_n=3, min_n=1, pad_id=0, finished=None, out=None):
+    """llmie_ngram_draft on tokens int32 [batch, stride] with length int32 [batch] (the sampler's history / history_len when the
+    prompt was put there): returns (ids int32 [batch, k + 1] -- the verify chunk's inputs, the last token first --, draft_ids
+    int32 [batch, k], draft_len int32 [batch]).  out: such a triple to write into."""
+    import torch
+    batch, stride = tokens.shape
+    ids, draft_ids, draft_len = out if out is not None else (torch.empty((batch, k + 1), dtype=torch.int32, device=tokens.device),
+                                                             torch.empty((batch, k), dtype=torch.int32, device=tokens.device),
+                                                             torch.empty(batch, dtype=torch.int32, device=tokens.device))
+    _check(lib().llmie_ngram_draft(_p(tokens), stride, _p(length), _p(finished), batch, k, max_n, min_n, pad_id, _p(ids), _p(draft_ids),
+                                   _p(draft_len), _st()), "ngram_draft")
+    return ids, draft_ids, draft_len
 
 
 def linear_fp8_workspace_bytes(M, K, N=0):

@@ -301,3 +301,41 @@ void launchForkKVPages(TensorWrapper<T> *k_pool, TensorWrapper<T> *v_pool, Tenso
                                    layers, kv_head_num, head_size, max_pages, num_pages, static_cast<int>(sizeof(T)),
                                    llmie_api::scratch(ws), ws, llmie_api::st()));
 }
+
+// No reference launcher: exact-match verification of k draft tokens per sequence on the logits [batch * (k + 1), vocab] of a
+// chunk (row b * (k + 1) + i follows input i of sequence b; include/llmie.h has the semantics).  draft_ids [batch, k];
+// out_tokens [batch, k + 1] and out_count [batch] are written; seq_len / finished and -- where given -- the history
+// [batch, stride] + history_len, last_token, cached_len and step_rows [batch] move as `count` sampler calls would move them.
+// draft_len, history (with history_len), last_token, cached_len, step_rows, out_logprob and ext may be null; without step_rows
+// every sequence draws at `step`.
+template <typename T>
+void launchSpecVerify(TensorWrapper<T> *logits, TensorWrapper<int> *draft_ids, TensorWrapper<int> *draft_len,
+                      const llmie_sampling_params *params_dev, TensorWrapper<int> *history, TensorWrapper<int> *history_len,
+                      bool history_append, TensorWrapper<int> *seq_len, TensorWrapper<bool> *finished, TensorWrapper<int> *out_tokens,
+                      TensorWrapper<int> *out_count, TensorWrapper<float> *out_logprob, TensorWrapper<int> *last_token,
+                      TensorWrapper<int> *cached_len, TensorWrapper<int> *step_rows, int step, int end_id,
+                      const llmie_sampling_ext *ext = nullptr) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int batch = draft_ids->shape[0], k = draft_ids->shape[1], vocab = logits->shape[1];
+    LLM_CHECK_WITH_INFO(logits->shape[0] == batch * (k + 1), "logits rows should equal batch * (k + 1)");
+    const size_t ws = llmie_spec_verify_workspace_bytes(batch, k, vocab);
+    LLMIE_CALL(llmie_spec_verify(logits->data, batch, k, vocab, draft_ids->data, draft_len ? draft_len->data : nullptr, params_dev,
+                                 history ? history->data : nullptr, history ? history->shape[1] : 0,
+                                 history_len ? history_len->data : nullptr, history_append ? 1 : 0, seq_len->data,
+                                 reinterpret_cast<uint8_t *>(finished->data), out_tokens->data, out_count->data,
+                                 out_logprob ? out_logprob->data : nullptr, last_token ? last_token->data : nullptr,
+                                 cached_len ? cached_len->data : nullptr, step_rows ? step_rows->data : nullptr, step, nullptr, end_id,
+                                 llmie_api::scratch(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st(), ext));
+}
+
+// No reference launcher: prompt-lookup drafts from each sequence's own tokens [batch, stride] (len [batch] of them): the last
+// max_n .. min_n tokens are looked up earlier in the row and what followed them there becomes the draft.  out_ids [batch, k + 1]
+// (the verify chunk's inputs: the last token, then the drafts), out_draft_ids [batch, k], out_draft_len [batch].
+inline void launchNgramDraft(TensorWrapper<int> *tokens, TensorWrapper<int> *len, TensorWrapper<bool> *finished, int max_n, int min_n,
+                             int pad_id, TensorWrapper<int> *out_ids, TensorWrapper<int> *out_draft_ids, TensorWrapper<int> *out_draft_len) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int batch = tokens->shape[0], stride = tokens->shape[1], k = out_draft_ids->shape[1];
+    LLM_CHECK_WITH_INFO(out_ids->shape[0] == batch && out_ids->shape[1] == k + 1, "out_ids should be [batch, k + 1]");
+    LLMIE_CALL(llmie_ngram_draft(tokens->data, stride, len->data, finished ? reinterpret_cast<uint8_t *>(finished->data) : nullptr, batch, k,
+                                 max_n, min_n, pad_id, out_ids->data, out_draft_ids->data, out_draft_len->data, llmie_api::st()));
+}

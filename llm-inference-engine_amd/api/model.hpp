@@ -81,7 +81,7 @@ private:
     DevBuf<llmie_sampling_params> d_sparams;
     DevBuf<int> d_penalty_ids, d_penalty_len;
     DevBuf<unsigned char> d_sample_ws, d_score_ws;
-    DevBuf<int> d_targets;
+    DevBuf<int> d_targets, d_spec;
     DevBuf<float> d_logprob;
     std::vector<int> penalty_ids;   // prompt + generated ids: the penalty history of the SamplingConfig path
     // llmie_sampling_ext of the SamplingConfig path: mask, bias list, stop list, min_step, and the top-N of the last step
@@ -308,6 +308,54 @@ public:
         CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps `targets` alive until its copy is done)
         logprob.pop_back();
         return logprob;
+    }
+    // One speculative step.  `last` -- emitted, not yet in the cache -- and `drafts` (<= LLMIE_SPEC_MAX_DRAFT guesses of what follows it:
+    // an n-gram lookup, a small model) run as ONE chunk of the context decoder on top of the cached tokens; llmie_spec_verify then
+    // emits what plain decoding would have emitted from those logits: 1 .. drafts.size() + 1 tokens, the accepted drafts and one
+    // more.  The rejected drafts' cache rows are scratch: the next call overwrites them.  The pick behind cache position c draws at
+    // Philox step c + 1, as continueWith does.  Samples with the seven llmie_sampling_params of `sampling` over the whole vocabulary
+    // (temperature 0: greedy; the reference's top-4 tail and the llmie_sampling_ext controls have no form here), the prompt and the
+    // generated ids as the penalty history.  Stops behind EOS.  lastLogits() holds the chunk's [drafts.size() + 1, vocab_size] rows.
+    std::vector<int> speculativeStep(int last, const std::vector<int> &drafts) {
+        const int k = static_cast<int>(drafts.size()), cached = h_step;
+        LLM_CHECK_WITH_INFO(k >= 1 && k <= LLMIE_SPEC_MAX_DRAFT, "1 .. LLMIE_SPEC_MAX_DRAFT drafts");
+        std::vector<int> chunk{last};
+        chunk.insert(chunk.end(), drafts.begin(), drafts.end());
+        const size_t fed = penalty_ids.size();
+        T *ctx_out = runContext(chunk, cached);   // (checks the fit; resets finished / seq_len; h_step = cached + k + 1)
+        penalty_ids.resize(fed);
+        penalty_ids.push_back(last);
+        const DataType ty = getTensorType<T>();
+        TensorWrapper<T> x(Device::GPU, ty, {k + 1, hidden_units}, ctx_out);
+        TensorWrapper<T> unused(Device::GPU, ty, {k + 1, hidden_units}, d_unused.ensure(static_cast<size_t>(k + 1) * hidden_units));
+        launchRMSNorm(&x, &unused, &llama_weights->out_rmsnorm_weight, rmsnorm_eps, true);
+        TensorWrapper<T> probs(Device::GPU, ty, {k + 1, vocab_size}, d_probs.ensure(static_cast<size_t>(k + 1) * vocab_size));
+        launchLinearGemm(&x, &llama_weights->post_decoder_embedding_weight, &probs, cublas_wrapper, false, true);
+        const llmie_sampling_params p{sampling.temperature, sampling.top_k, sampling.top_p, sampling.min_p,
+                                      sampling.repetition_penalty, sampling.presence_penalty, sampling.frequency_penalty,
+                                      sampling.seed};
+        // the penalty history: the most recent ids, with room for the k + 1 picks behind them
+        const int room = LLMIE_SAMPLE_MAX_HISTORY - (k + 1);
+        const int n = static_cast<int>(std::min<size_t>(penalty_ids.size(), room)), stride = n + k + 1;
+        int *hist = d_penalty_ids.ensure(stride), *hlen = d_penalty_len.ensure(1);
+        int *spec = d_spec.ensure(2 * (k + 1) + 1);   // drafts [k] | tokens [k + 1] | count
+        CHECK(hipMemcpyAsync(d_sparams.ensure(1), &p, sizeof(p), hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(hist, penalty_ids.data() + (penalty_ids.size() - n), sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(hlen, &n, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(spec, drafts.data(), sizeof(int) * k, hipMemcpyHostToDevice, llmie_api::st()));
+        const size_t ws = llmie_spec_verify_workspace_bytes(1, k, vocab_size);
+        LLMIE_CALL(llmie_spec_verify(probs.data, 1, k, vocab_size, spec, nullptr, d_sparams.p, hist, stride, hlen, 1, d_seq_len.p,
+                                     reinterpret_cast<uint8_t *>(d_finished.p), spec + k, spec + 2 * k + 1, nullptr, nullptr, nullptr,
+                                     nullptr, cached + 1, nullptr, eos_token_id, d_sample_ws.ensure(ws), ws, llmie_api::dtype_of<T>(),
+                                     llmie_api::st(), nullptr));
+        std::vector<int> got(k + 2);
+        CHECK(hipMemcpyAsync(got.data(), spec + k, sizeof(int) * (k + 2), hipMemcpyDeviceToHost, llmie_api::st()));
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps p / n / drafts alive until the copies are done)
+        const int count = got[k + 1];
+        got.resize(count);
+        penalty_ids.insert(penalty_ids.end(), got.begin(), got.end() - 1);   // the last pick joins when it is fed
+        h_step = cached + count;   // `last` and the accepted drafts are cached; the last pick is not
+        return got;
     }
     // the context decoder's output [n, hidden_units] of the last prefill (generateFirstToken normalises its last row in place)
     const T *contextOutput() const { return d_ctx_out.p; }

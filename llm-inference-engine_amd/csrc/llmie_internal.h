@@ -296,14 +296,17 @@ int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, 
 // per-request sampling (sampling_params.hip): the host-side checks of llmie_sample_logits, and its launch with the optional
 // tail of llmie_lm_head_sample_params (next_hidden[b] = embed[out_id[b]], *step_dev += 1 once every row has read it).
 // ext != nullptr launches the kernel with the extension (llmie_sampling_ext); sample_ext_check says whether a struct needs it.
+// entry: the name the messages carry; own_workspace == false leaves the workspace to a caller that sizes its own (spec_decode.hip).
 int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
                         int history_stride, const int32_t *history_len, const int32_t *seq_len, const uint8_t *finished,
-                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype);
+                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype,
+                        const char *entry = "sample_logits", bool own_workspace = true);
 int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
                          int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
                          int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
                          llmie_dtype dtype, const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket,
                          hipStream_t st, const llmie_sampling_ext *ext = nullptr);
-int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *ext, bool *active);
+int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *ext, bool *active, const char *entry = "sample_logits_ext");
+size_t sample_logits_ws_row(int vocab);   // uint32 words of workspace per row
 
 }  // namespace llmie

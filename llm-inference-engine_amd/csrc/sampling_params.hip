@@ -26,223 +26,12 @@
 //   mask     the row's bit mask is staged in LDS (16-byte loads) behind the penalties, which are done with `sorted` by then;
 //            pass 2 turns a token whose bit is clear into key 0, what a NaN gets -- everything downstream ignores key 0
 //   stops    finished also if the pick is in the row's stop list
-#include "device_utils.cuh"
-#include "llmie_internal.h"
-#include "philox.cuh"
-
-#include <cfloat>
-#include <climits>
+//
+// The device code of all this -- sp_sample_row and what it calls -- lives in sampling_body.cuh, which spec_decode.hip shares; this
+// file keeps the kernels' shell (operands, the epilogue that writes the state), the launches and the host checks.
+#include "sampling_body.cuh"
 
 namespace llmie {
-
-constexpr int kSpThreads = 1024;
-constexpr int kSpMaxHistory = LLMIE_SAMPLE_MAX_HISTORY;
-constexpr int kSpWaves = kSpThreads / 64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ uint32_t sp_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sp_val(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-struct SpShared {
-    u64 hist[256];
-    u64 red64[kSpWaves];
-    float redm[kSpWaves], reds[kSpWaves];
-    int redi[kSpWaves];
-    u64 b_above;
-    uint32_t b_prefix;
-    int b_id;
-    int sorted[kSpMaxHistory];
-};
-
-// block-wide reductions (fixed mapping and order: deterministic)
-__device__ __forceinline__ u64 sp_sum64(u64 v, SpShared &s) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if (lane == 0) s.red64[w] = v;
-    __syncthreads();
-    u64 t = 0;
-#pragma unroll
-    for (int i = 0; i < kSpWaves; ++i) t += s.red64[i];
-    return t;
-}
-__device__ __forceinline__ u64 sp_max64(u64 v, SpShared &s) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 y = __shfl_xor(v, o);
-        v = y > v ? y : v;
-    }
-    __syncthreads();
-    if (lane == 0) s.red64[w] = v;
-    __syncthreads();
-    u64 t = 0;
-#pragma unroll
-    for (int i = 0; i < kSpWaves; ++i) t = s.red64[i] > t ? s.red64[i] : t;
-    return t;
-}
-// exclusive prefix of an int over the block (thread order)
-__device__ __forceinline__ int sp_excl_scan(int v, SpShared &s) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(inc, o);
-        if (lane >= o) inc += y;
-    }
-    __syncthreads();
-    if (lane == 63) s.redi[w] = inc;
-    __syncthreads();
-    int before = 0;
-    for (int i = 0; i < w; ++i) before += s.redi[i];
-    return before + inc - v;
-}
-// f(t, key) over this thread's tokens (stride kSpThreads), kSpUnroll loads in flight: one CU streams the whole row, so the
-// passes are bound by load latency unless the loads of several tokens overlap.  Keys past V read as 0 (excluded).
-constexpr int kSpUnroll = 8;
-// RAW: `keys` still holds pass 1's fp32 copy of the raw row; its keys are formed on the fly (NaN -> 0, -0 -> +0: llmie_topk's ties)
-template <bool RAW> __device__ __forceinline__ uint32_t sp_load_key(const uint32_t *keys, int t) {
-    if constexpr (RAW) {
-        const float x = __uint_as_float(keys[t]);
-        return x == x ? sp_key(x + 0.f) : 0u;
-    } else {
-        return keys[t];
-    }
-}
-template <bool RAW = false, class F> __device__ __forceinline__ void sp_for_keys(const uint32_t *keys, int V, F f) {
-    for (int t0 = threadIdx.x; t0 < V; t0 += kSpUnroll * kSpThreads) {
-        uint32_t k[kSpUnroll];
-#pragma unroll
-        for (int u = 0; u < kSpUnroll; ++u) {
-            const int t = t0 + u * kSpThreads;
-            k[u] = t < V ? sp_load_key<RAW>(keys, t) : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < kSpUnroll; ++u) f(t0 + u * kSpThreads, k[u]);
-    }
-}
-// (max, sum of exp(x - max)) pairs
-__device__ __forceinline__ void sp_lse_combine(float &m, float &sum, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    if (mn == -INFINITY) return;
-    sum = (m == -INFINITY ? 0.f : sum * expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * expf(m2 - mn));
-    m = mn;
-}
-
-// In (value desc, id asc) order over the tokens t with in(t, key) (key != 0), the first token at which the running weight
-// w(key) exceeds thr.  The caller guarantees that the total weight exceeds thr.  Returns its key; *above = the weight of the
-// set strictly above that key.  4 passes over the keys, one 8-bit digit each, highest first.
-template <bool RAW = false, class In, class W>
-__device__ uint32_t radix_select(const uint32_t *keys, int V, In in, W w, u64 thr, u64 *above_out, SpShared &s) {
-    const int tid = threadIdx.x;
-    uint32_t prefix = 0;
-    u64 above = 0;
-    for (int d = 3; d >= 0; --d) {
-        const int shift = 8 * d;
-        const uint32_t hmask = d == 3 ? 0u : (0xffffffffu << (shift + 8));
-        if (tid < 256) s.hist[tid] = 0;
-        __syncthreads();
-        sp_for_keys<RAW>(keys, V, [&](int t, uint32_t k) {
-            if (k == 0 || (k & hmask) != prefix || !in(t, k)) return;
-            const u64 wt = w(k);
-            if (wt) atomicAdd(&s.hist[(k >> shift) & 255u], wt);
-        });
-        __syncthreads();
-        if (tid < 64) {
-            // lane l holds bins 255-4l .. 252-4l (descending value)
-            const int base = 255 - 4 * tid;
-            const u64 h0 = s.hist[base], h1 = s.hist[base - 1], h2 = s.hist[base - 2], h3 = s.hist[base - 3];
-            const u64 sum = h0 + h1 + h2 + h3;
-            u64 inc = sum;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u64 y = __shfl_up(inc, o);
-                if (tid >= o) inc += y;
-            }
-            const u64 hit = __ballot(above + inc > thr);
-            const int first = hit ? __ffsll(static_cast<long long>(hit)) - 1 : 63;
-            if (tid == first) {
-                u64 c = above + inc - sum;
-                int bin = base - 3;
-                if (c + h0 > thr) bin = base;
-                else if ((c += h0) + h1 > thr) bin = base - 1;
-                else if ((c += h1) + h2 > thr) bin = base - 2;
-                else c += h2;
-                s.b_above = c;
-                s.b_prefix = prefix | (static_cast<uint32_t>(bin) << shift);
-            }
-        }
-        __syncthreads();
-        prefix = s.b_prefix;
-        above = s.b_above;
-    }
-    *above_out = above;
-    return prefix;
-}
-
-// the j-th (0-based) id, ascending, among the tokens with keys[t] == key and in(t, key); -1 if there are not that many
-template <bool RAW = false, class In>
-__device__ int id_select(const uint32_t *keys, int V, uint32_t key, In in, u64 j, SpShared &s) {
-    const int chunk = (V + kSpThreads - 1) / kSpThreads;
-    const int t0 = min(V, threadIdx.x * chunk), t1 = min(V, t0 + chunk);
-    int c = 0;
-    for (int t = t0; t < t1; ++t) c += (sp_load_key<RAW>(keys, t) == key && in(t, key)) ? 1 : 0;
-    if (threadIdx.x == 0) s.b_id = -1;
-    const int ex = sp_excl_scan(c, s);   // (its barriers order the store above)
-    if (j >= static_cast<u64>(ex) && j < static_cast<u64>(ex + c)) {
-        int r = static_cast<int>(j - ex);
-        for (int t = t0; t < t1; ++t)
-            if (sp_load_key<RAW>(keys, t) == key && in(t, key) && r-- == 0) {
-                s.b_id = t;
-                break;
-            }
-    }
-    __syncthreads();
-    return s.b_id;
-}
-
-static_assert(LLMIE_SAMPLE_MAX_BIAS <= kSpThreads, "one thread per bias entry");
-static_assert(LLMIE_SAMPLE_MAX_TOP_N <= 256, "the top-N candidates live in SpShared::hist");
-static_assert(offsetof(SpShared, sorted) % 16 == 0, "the mask row is staged in `sorted` with 16-byte stores");
-
-// EXT: the top_n largest raw logits of the row (value desc, id asc) and their raw log-softmax.  `keys` holds pass 1's fp32 copy,
-// untouched so far; valid = its count of non-NaN values; lse = the raw log-sum-exp.
-__device__ __forceinline__ void sp_top_n(const uint32_t *keys, int V, int valid, float lse, int top_n, int32_t *out_ids, float *out_lp, SpShared &s) {
-    const int tid = threadIdx.x;
-    const int n = min(top_n, valid);
-    uint32_t kk = 0;   // the n-th token (kk, kid); kk == 0: every valid token is in
-    int kid = INT_MAX;
-    if (valid > top_n) {
-        auto all = [](int, uint32_t) { return true; };
-        u64 above;
-        kk = radix_select<true>(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_n - 1), &above, s);
-        kid = id_select<true>(keys, V, kk, all, static_cast<u64>(top_n - 1) - above, s);
-    }
-    __syncthreads();   // every thread has read id_select's b_id
-    if (tid == 0) s.b_id = 0;
-    __syncthreads();
-    sp_for_keys<true>(keys, V, [&](int t, uint32_t k) {
-        if (k == 0 || !(k > kk || (k == kk && t <= kid))) return;
-        const int slot = atomicAdd(&s.b_id, 1);   // (any order: the candidates rank themselves below)
-        if (slot < LLMIE_SAMPLE_MAX_TOP_N) s.hist[slot] = (static_cast<u64>(k) << 32) | (0xffffffffu - static_cast<uint32_t>(t));
-    });
-    __syncthreads();
-    if (tid < n) {
-        const u64 mine = s.hist[tid];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += s.hist[j] > mine ? 1 : 0;   // ids differ, so do the candidates
-        out_ids[rank] = static_cast<int32_t>(0xffffffffu - static_cast<uint32_t>(mine & 0xffffffffu));
-        out_lp[rank] = sp_val(static_cast<uint32_t>(mine >> 32)) - lse;
-    } else if (tid < top_n) {
-        out_ids[tid] = -1;
-        out_lp[tid] = -INFINITY;
-    }
-    __syncthreads();   // hist / b_id are free again, and the copy may be patched
-}
 
 // Ext is empty (the kernel of the entries without the extension: their parameter list and their code are what they were before the
 // extension existed) or one llmie_sampling_ext by value (EXT)
@@ -255,250 +44,16 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
     const T *__restrict__ embed, T *__restrict__ next_hidden, int hidden, int advance, unsigned *ticket, int rows, Ext... ext) {
     constexpr bool EXT = sizeof...(Ext) == 1;
     __shared__ alignas(EXT ? 16 : alignof(SpShared)) SpShared s;   // (EXT stages the mask row with 16-byte stores)
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int step = step_dev ? *step_dev : step_arg;
+    const llmie_sampling_ext *ep = nullptr;
+    if constexpr (EXT) ep = &sp_ext(ext...);
+    const SpPick pick = sp_sample_row<T, EXT>(logits + static_cast<size_t>(b) * V, V, params[b], SpStoredHistory{history, history_len, b, hstride},
+                                              step, end_id, ws + static_cast<size_t>(b) * ws_row, ep, b, b, s);
     const T *lg = logits + static_cast<size_t>(b) * V;
-    uint32_t *keys = ws + static_cast<size_t>(b) * ws_row;
-    float *rowf = reinterpret_cast<float *>(keys);
-
-    // parameters, clamped (they live in device memory: the host cannot check them)
-    const llmie_sampling_params p = params[b];
-    float temp = p.temperature;
-    if (!(temp >= 0.f)) temp = 0.f;
-    int top_k = p.top_k < 0 ? 0 : (p.top_k > V ? V : p.top_k);
-    float top_p = p.top_p;
-    if (!(top_p > 0.f)) {   // <= 0 (or NaN): one token
-        top_k = 1;
-        top_p = 1.f;
-    }
-    top_p = fminf(top_p, 1.f);
-    float min_p = p.min_p;
-    min_p = (min_p >= 0.f) ? fminf(min_p, 1.f) : 0.f;
-    float rep = p.repetition_penalty;
-    if (!(rep > 0.f)) rep = 1.f;
-    const float presence = p.presence_penalty, frequency = p.frequency_penalty;
-
-    // pass 1: fp32 copy + raw log-sum-exp (per-thread online pairs, then a fixed tree)
-    float m = -INFINITY, sum = 0.f;
-    int nraw = 0;   // (EXT) non-NaN raw logits of this thread
-    for (int t = tid; t < V; t += kSpThreads) {
-        const float x = to_f32(lg[t]);
-        rowf[t] = x;
-        if (x == x) sp_lse_combine(m, sum, x, 1.f);
-        if constexpr (EXT) nraw += x == x ? 1 : 0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sp_lse_combine(m, sum, __shfl_xor(m, o), __shfl_xor(sum, o));
-    if (lane == 0) {
-        s.redm[wave] = m;
-        s.reds[wave] = sum;
-    }
-
-    // (EXT) the stop list; the top-N of the raw row; then bias and min_step patch the copy in front of the penalties
-    int slen = 0;
-    const int32_t *stops = nullptr;
-    if constexpr (EXT) {
-        const llmie_sampling_ext &e = sp_ext(ext...);
-        if (e.stop_ids) {
-            slen = min(max(e.stop_len[b], 0), e.stop_stride);
-            stops = e.stop_ids + static_cast<size_t>(b) * e.stop_stride;
-        }
-        if (e.top_n > 0) {
-            const int rawvalid = static_cast<int>(sp_sum64(static_cast<u64>(nraw), s));   // (its barriers complete pass 1)
-            float rm = s.redm[0], rs = s.reds[0];
-            for (int i = 1; i < kSpWaves; ++i) sp_lse_combine(rm, rs, s.redm[i], s.reds[i]);
-            sp_top_n(keys, V, rawvalid, rm + logf(rs), e.top_n, e.out_top_ids + static_cast<size_t>(b) * e.top_n,
-                     e.out_top_logprobs + static_cast<size_t>(b) * e.top_n, s);
-        } else {
-            __syncthreads();   // pass 1's copy of the row is complete
-        }
-        const int blen = e.bias_ids ? min(max(e.bias_len[b], 0), e.bias_stride) : 0;
-        if (blen > 0) {
-            // entry tid of the list; -1: ignored.  It patches the row unless a later entry names the same id (last wins).
-            int id = -1;
-            float val = 0.f;
-            if (tid < blen) {
-                id = e.bias_ids[static_cast<size_t>(b) * e.bias_stride + tid];
-                val = e.bias_vals[static_cast<size_t>(b) * e.bias_stride + tid];
-                if (id < 0 || id >= V || val != val || val == INFINITY) id = -1;
-            }
-            s.sorted[tid] = id;
-            __syncthreads();
-            if (id >= 0) {
-                bool last = true;
-#pragma unroll 8
-                for (int j = tid + 1; j < blen; ++j) last = last && s.sorted[j] != id;
-                if (last) rowf[id] = val == -INFINITY ? __uint_as_float(0x7fc00000u) : rowf[id] + val;
-            }
-            __syncthreads();   // `sorted` is free for the history; the bias is in the row
-        }
-        if (e.min_step && step < e.min_step[b]) {
-            // (the same NaN from several threads where ids repeat)
-            if (tid < slen) {
-                const int t = stops[tid];
-                if (t >= 0 && t < V) rowf[t] = __uint_as_float(0x7fc00000u);
-            }
-            if (tid == LLMIE_SAMPLE_MAX_STOPS && end_id >= 0 && end_id < V) rowf[end_id] = __uint_as_float(0x7fc00000u);
-        }
-    }
-
-    // penalties over the distinct ids of the history
-    const int hlen = hstride > 0 ? min(max(history_len[b], 0), hstride) : 0;
-    const bool penal = hlen > 0 && (rep != 1.f || presence != 0.f || frequency != 0.f);
-    if (penal) {
-        int n = 1;
-        while (n < hlen) n <<= 1;
-        const int32_t *h = history + static_cast<size_t>(b) * hstride;
-        for (int i = tid; i < n; i += kSpThreads) {
-            const int t = i < hlen ? h[i] : -1;
-            s.sorted[i] = (t >= 0 && t < V) ? t : INT_MAX;
-        }
-        __syncthreads();
-        for (int k = 2; k <= n; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < n; i += kSpThreads) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const int a = s.sorted[i], c = s.sorted[l];
-                        if ((a > c) == ((i & k) == 0)) {
-                            s.sorted[i] = c;
-                            s.sorted[l] = a;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        __syncthreads();   // pass 1's copy of the row is complete
-        for (int i = tid; i < n; i += kSpThreads) {
-            const int t = s.sorted[i];
-            if (t == INT_MAX || (i > 0 && s.sorted[i - 1] == t)) continue;
-            int lo = i + 1, hi = n;   // first index past the run
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s.sorted[mid] == t) lo = mid + 1;
-                else hi = mid;
-            }
-            const float c = static_cast<float>(lo - i);
-            float x = rowf[t];
-            x = x > 0.f ? x / rep : x * rep;
-            x = x - presence;
-            x = x - c * frequency;
-            rowf[t] = x;
-        }
-    }
-    __syncthreads();
-    float lse_m = s.redm[0], lse_s = s.reds[0];
-    for (int i = 1; i < kSpWaves; ++i) sp_lse_combine(lse_m, lse_s, s.redm[i], s.reds[i]);
-
-    // (EXT) the row's allowed-token mask: its first kSpMaxHistory words (262144 tokens) go to `sorted`, which the penalties no
-    // longer need; a longer row reads the rest from memory
-    const uint32_t *mrow = nullptr;
-    const uint32_t *mlds = reinterpret_cast<const uint32_t *>(s.sorted);
-    if constexpr (EXT) {
-        const llmie_sampling_ext &e = sp_ext(ext...);
-        if (e.allowed_mask) {
-            const int mi = e.mask_index ? e.mask_index[b] : b;
-            if (mi >= 0 && mi < e.mask_rows) mrow = e.allowed_mask + static_cast<size_t>(mi) * e.mask_stride;
-        }
-        if (mrow) {
-            const int lw = min((V + 31) >> 5, kSpMaxHistory);
-            uint32_t *dst = reinterpret_cast<uint32_t *>(s.sorted);
-            const int n4 = (reinterpret_cast<uintptr_t>(mrow) % 16 == 0) ? lw >> 2 : 0;
-            for (int i = tid; i < n4; i += kSpThreads) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(mrow)[i];
-            for (int i = 4 * n4 + tid; i < lw; i += kSpThreads) dst[i] = mrow[i];
-            __syncthreads();
-        }
-    }
-
-    // pass 2: keys (value desc, id asc -> the larger (key, ~id)), the maximum and the valid count
-    const bool greedy = temp == 0.f;
-    const float inv_t = greedy ? 1.f : temp;
-    u64 best = 0;
-    int nvalid = 0;
-    for (int t0 = tid; t0 < V; t0 += kSpUnroll * kSpThreads) {
-        float xs[kSpUnroll];
-#pragma unroll
-        for (int u = 0; u < kSpUnroll; ++u) {
-            const int t = t0 + u * kSpThreads;
-            xs[u] = t < V ? rowf[t] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < kSpUnroll; ++u) {
-            const int t = t0 + u * kSpThreads;
-            if (t >= V) break;
-            float x = xs[u];
-            uint32_t k = 0;
-            bool in = true;
-            if constexpr (EXT) {
-                if (mrow) {
-                    const int w = t >> 5;
-                    const uint32_t word = w < kSpMaxHistory ? mlds[w] : mrow[w];
-                    in = (word >> (t & 31)) & 1u;
-                }
-            }
-            if (x == x && in) {
-                if (!greedy) x = fminf(fmaxf(x / inv_t, -FLT_MAX), FLT_MAX);
-                k = sp_key(x);
-                ++nvalid;
-                const u64 c = (static_cast<u64>(k) << 32) | (0xffffffffu - static_cast<uint32_t>(t));
-                best = c > best ? c : best;
-            }
-            keys[t] = k;
-        }
-    }
-    best = sp_max64(best, s);
-    const int valid = static_cast<int>(sp_sum64(static_cast<u64>(nvalid), s));
-    int chosen = end_id;
-    if (valid > 0) chosen = static_cast<int>(0xffffffffu - static_cast<uint32_t>(best & 0xffffffffu));
-
-    if (!greedy && valid > 1) {
-        const float vmax = sp_val(static_cast<uint32_t>(best >> 32));
-        auto mass = [vmax](uint32_t k) -> u64 {
-            const float d = sp_val(k) - vmax;
-            if (!(d > -23.f)) return 0ull;
-            return static_cast<u64>(expf(d) * 4294967296.0f);
-        };
-        // top-k: the top_k-th token (kk, kid); the set {key > kk} + {key == kk, id <= kid}
-        uint32_t kk = 0;
-        int kid = INT_MAX;
-        if (top_k > 0 && top_k < valid) {
-            u64 above;
-            auto all = [](int, uint32_t) { return true; };
-            kk = radix_select(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_k - 1), &above, s);
-            kid = id_select(keys, V, kk, all, static_cast<u64>(top_k - 1) - above, s);
-        }
-        auto in_k = [kk, kid](int t, uint32_t k) { return k > kk || (k == kk && t <= kid); };
-        // top-p: keep every value >= that of the first token at which the mass reaches top_p * the top-k mass
-        uint32_t pk = 0;
-        if (top_p < 1.f) {
-            u64 ms = 0;
-            sp_for_keys(keys, V, [&](int t, uint32_t k) {
-                if (k && in_k(t, k)) ms += mass(k);
-            });
-            ms = sp_sum64(ms, s);
-            u64 thr = static_cast<u64>(ceil(static_cast<double>(top_p) * static_cast<double>(ms)));
-            thr = thr == 0 ? 0 : thr - 1;
-            if (thr >= ms) thr = ms - 1;
-            u64 above;
-            pk = radix_select(keys, V, in_k, mass, thr, &above, s);
-        }
-        auto kept = [=](int t, uint32_t k) {
-            return in_k(t, k) && k >= pk && (min_p == 0.f || expf(sp_val(k) - vmax) >= min_p);
-        };
-        u64 mk = 0;
-        sp_for_keys(keys, V, [&](int t, uint32_t k) {
-            if (k && kept(t, k)) mk += mass(k);
-        });
-        mk = sp_sum64(mk, s);
-        // draw: the first kept token at which the running mass exceeds u * kept mass (u == 1: the last kept token)
-        const float u = uniform_philox(static_cast<uint32_t>(step), p.seed);
-        u64 thr = static_cast<u64>(floor(static_cast<double>(u) * static_cast<double>(mk)));
-        if (thr >= mk) thr = mk - 1;
-        u64 above;
-        const uint32_t dk = radix_select(keys, V, kept, mass, thr, &above, s);
-        const int id = id_select(keys, V, dk, kept, (thr - above) / mass(dk), s);
-        if (id >= 0) chosen = id;
-    }
+    const int chosen = pick.chosen, valid = pick.valid, slen = pick.slen;
+    const int32_t *stops = pick.stops;
+    const float lse_m = pick.lse_m, lse_s = pick.lse_s;
 
     if (tid == 0) {
         out_id[b] = chosen;
@@ -570,49 +125,51 @@ int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_s
 
 // llmie_sampling_ext as the host can judge it (the arrays live in device memory).  *active: some control is on -- the EXT kernel
 // is needed; otherwise the call is the entry without the extension.
-int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *e, bool *active) {
+int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *e, bool *active, const char *entry) {
     *active = false;
     if (!e) return LLMIE_OK;
     LLMIE_REQUIRE(e->mask_stride >= 0 && e->mask_rows >= 0 && e->bias_stride >= 0 && e->stop_stride >= 0 && e->top_n >= 0,
-                  "sample_logits_ext: negative mask_stride %d / mask_rows %d / bias_stride %d / stop_stride %d / top_n %d", e->mask_stride,
+                  "%s: negative mask_stride %d / mask_rows %d / bias_stride %d / stop_stride %d / top_n %d", entry, e->mask_stride,
                   e->mask_rows, e->bias_stride, e->stop_stride, e->top_n);
     const bool bias_any = e->bias_ids || e->bias_vals || e->bias_len;
     LLMIE_REQUIRE(!bias_any || (e->bias_ids && e->bias_vals && e->bias_len),
-                  "sample_logits_ext: bias needs bias_ids, bias_vals and bias_len together");
-    LLMIE_REQUIRE(!e->stop_ids == !e->stop_len, "sample_logits_ext: stop_ids and stop_len go together");
-    LLMIE_REQUIRE(e->allowed_mask || !e->mask_index, "sample_logits_ext: mask_index without allowed_mask");
+                  "%s: bias needs bias_ids, bias_vals and bias_len together", entry);
+    LLMIE_REQUIRE(!e->stop_ids == !e->stop_len, "%s: stop_ids and stop_len go together", entry);
+    LLMIE_REQUIRE(e->allowed_mask || !e->mask_index, "%s: mask_index without allowed_mask", entry);
     if (e->allowed_mask) {
-        LLMIE_REQUIRE(e->mask_stride >= (vocab + 31) / 32, "sample_logits_ext: mask_stride %d words below ceil(vocab %d / 32)",
+        LLMIE_REQUIRE(e->mask_stride >= (vocab + 31) / 32, "%s: mask_stride %d words below ceil(vocab %d / 32)", entry,
                       e->mask_stride, vocab);
-        LLMIE_REQUIRE(e->mask_rows >= 1, "sample_logits_ext: mask_rows %d < 1", e->mask_rows);
-        LLMIE_REQUIRE(e->mask_index || e->mask_rows >= batch, "sample_logits_ext: mask_rows %d below batch %d without a mask_index",
+        LLMIE_REQUIRE(e->mask_rows >= 1, "%s: mask_rows %d < 1", entry, e->mask_rows);
+        LLMIE_REQUIRE(e->mask_index || e->mask_rows >= batch, "%s: mask_rows %d below batch %d without a mask_index", entry,
                       e->mask_rows, batch);
     }
-    LLMIE_REQUIRE(e->top_n == 0 || (e->out_top_ids && e->out_top_logprobs), "sample_logits_ext: top_n %d without out_top_ids / out_top_logprobs",
+    LLMIE_REQUIRE(e->top_n == 0 || (e->out_top_ids && e->out_top_logprobs), "%s: top_n %d without out_top_ids / out_top_logprobs", entry,
                   e->top_n);
     if (e->bias_stride > LLMIE_SAMPLE_MAX_BIAS)
-        LLMIE_UNSUPPORTED("sample_logits_ext: bias_stride %d above %d", e->bias_stride, LLMIE_SAMPLE_MAX_BIAS);
+        LLMIE_UNSUPPORTED("%s: bias_stride %d above %d", entry, e->bias_stride, LLMIE_SAMPLE_MAX_BIAS);
     if (e->stop_stride > LLMIE_SAMPLE_MAX_STOPS)
-        LLMIE_UNSUPPORTED("sample_logits_ext: stop_stride %d above %d", e->stop_stride, LLMIE_SAMPLE_MAX_STOPS);
-    if (e->top_n > LLMIE_SAMPLE_MAX_TOP_N) LLMIE_UNSUPPORTED("sample_logits_ext: top_n %d above %d", e->top_n, LLMIE_SAMPLE_MAX_TOP_N);
+        LLMIE_UNSUPPORTED("%s: stop_stride %d above %d", entry, e->stop_stride, LLMIE_SAMPLE_MAX_STOPS);
+    if (e->top_n > LLMIE_SAMPLE_MAX_TOP_N) LLMIE_UNSUPPORTED("%s: top_n %d above %d", entry, e->top_n, LLMIE_SAMPLE_MAX_TOP_N);
     *active = e->allowed_mask || bias_any || e->stop_ids || e->min_step || e->top_n > 0;
     return LLMIE_OK;
 }
 
 int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
                         int history_stride, const int32_t *history_len, const int32_t *seq_len, const uint8_t *finished,
-                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype) {
-    LLMIE_REQUIRE(logits && params && seq_len && finished && out_id, "sample_logits: NULL pointer");
-    LLMIE_REQUIRE(batch > 0 && vocab > 0, "sample_logits: batch %d / vocab %d must be positive", batch, vocab);
-    LLMIE_REQUIRE(history_stride >= 0, "sample_logits: history_stride %d < 0", history_stride);
-    LLMIE_REQUIRE(history_stride == 0 || (history && history_len), "sample_logits: history_stride %d > 0 without history / history_len",
+                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype, const char *entry,
+                        bool own_workspace) {
+    LLMIE_REQUIRE(logits && params && seq_len && finished && out_id, "%s: NULL pointer", entry);
+    LLMIE_REQUIRE(batch > 0 && vocab > 0, "%s: batch %d / vocab %d must be positive", entry, batch, vocab);
+    LLMIE_REQUIRE(history_stride >= 0, "%s: history_stride %d < 0", entry, history_stride);
+    LLMIE_REQUIRE(history_stride == 0 || (history && history_len), "%s: history_stride %d > 0 without history / history_len", entry,
                   history_stride);
     if (history_stride > kSpMaxHistory)
-        LLMIE_UNSUPPORTED("sample_logits: history_stride %d above %d", history_stride, kSpMaxHistory);
-    if (dtype != LLMIE_F16 && dtype != LLMIE_F32) LLMIE_UNSUPPORTED("sample_logits: dtype %d", (int)dtype);
+        LLMIE_UNSUPPORTED("%s: history_stride %d above %d", entry, history_stride, kSpMaxHistory);
+    if (dtype != LLMIE_F16 && dtype != LLMIE_F32) LLMIE_UNSUPPORTED("%s: dtype %d", entry, (int)dtype);
+    if (!own_workspace) return LLMIE_OK;   // (the caller sizes and checks a workspace of its own)
     const size_t need = llmie_sample_logits_workspace_bytes(batch, vocab);
     if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
-        set_error("sample_logits: workspace %zu bytes (need %zu, 16-byte aligned)", workspace ? workspace_bytes : (size_t)0, need);
+        set_error("%s: workspace %zu bytes (need %zu, 16-byte aligned)", entry, workspace ? workspace_bytes : (size_t)0, need);
         return LLMIE_ERR_WORKSPACE;
     }
     return LLMIE_OK;

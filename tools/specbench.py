@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Speculative decoding: what a verify step costs against a plain decode step, at the Llama-2-7B geometry, fp16, paged cache:
+
+    python tools/specbench.py [--batch 1 8] [--k 2 4 7] [--ctx 2048] [--rounds 7] [--reps 20] [--out FILE]
+
+plain step   forward_paged_ragged (one token per sequence on top of ctx cached tokens) + lm_head_sample_params
+verify step  input_embedding + prefill_paged (k + 1 inputs per sequence on top of ctx cached tokens) + rmsnorm + linear over the
+             batch * (k + 1) rows + spec_verify; the n-gram drafter's launch is timed on its own (ngram_ms)
+
+Same build, same process, same weights; the arms alternate inside every round (plain, k = 2, 4, 7, plain, ...) and the median
+round of each arm is reported with its min and max.  A verify step emits 1 .. k + 1 tokens for its time, a plain step one: the
+break-even is verify_ms / plain_ms emitted tokens per verify step, i.e. that minus one accepted drafts.  Prints one JSON line
+(and writes it to --out)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402  (the flagship benchmark's weights and engine construction)
+
+EPS, V_PAGE = 1e-5, 128
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps   # ms
+
+
+def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
+    H, V, L, KVH, HS = cfg["head_num"] * cfg["head_size"], cfg["vocab_size"], cfg["num_layers"], cfg["kv_head_num"], cfg["head_size"]
+    kmax = max(ks)
+    max_pages = (ctx + kmax + 1 + V_PAGE - 1) // V_PAGE
+    num_pages = B * max_pages
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device="cuda")
+    ecfg = dict(cfg, max_seq_len=max_pages * V_PAGE, max_batch=B, rotary_dim=HS, rotary_base=10000.0, rms_eps=EPS, dtype=llmie.F16,
+                wfmt=llmie.W_F16, int4_group=128, kv_fmt=llmie.KV_NATIVE, k_scale=1.0, v_scale=1.0)
+    dec = llmie.Decoder(ecfg, weights["layers"])
+    kp = torch.empty((L, num_pages, KVH, V_PAGE, HS), dtype=torch.float16, device="cuda").normal_(0, 0.5)
+    vp = torch.empty((L, num_pages, KVH, V_PAGE, HS), dtype=torch.float16, device="cuda").normal_(0, 0.5)
+    table = torch.randperm(num_pages, device="cuda").to(torch.int32).reshape(B, max_pages).contiguous()
+    g = torch.Generator(device="cuda").manual_seed(B)
+    params = llmie.sampling_params([dict(temperature=0.8, top_k=50, top_p=0.9, seed=b) for b in range(B)])
+    seq, fin = i32([0] * B), torch.zeros(B, dtype=torch.uint8, device="cuda")
+
+    # plain step
+    x1 = torch.randn((B, H), generator=g, device="cuda").half()
+    y1, logits1, out1 = torch.empty_like(x1), torch.empty((B, V), dtype=torch.float16, device="cuda"), i32([0] * B)
+    ctx1 = i32([ctx + 1] * B)
+    ws1 = torch.empty(llmie.sample_logits_workspace_bytes(B, V), dtype=torch.uint8, device="cuda")
+
+    def plain():
+        dec.forward_paged_ragged(x1, y1, kp, vp, table, ctx1)
+        dec.lm_head_sample_params(y1, weights["final_norm"], weights["lm_head"], llmie.W_F16, logits1, params, seq, fin, out1, 7, -1, workspace=ws1)
+
+    # verify steps
+    arms = {}
+    cached = i32([ctx] * B)
+    for k in ks:
+        T = B * (k + 1)
+        ids = torch.randint(0, V, (T,), generator=g, device="cuda").to(torch.int32)
+        drafts = ids.reshape(B, k + 1)[:, 1:].contiguous()
+        xk, logits = torch.empty((T, H), dtype=torch.float16, device="cuda"), torch.empty((T, V), dtype=torch.float16, device="cuda")
+        yk = torch.empty_like(xk)
+        in_len = i32([k + 1] * B)
+        ws = torch.empty(llmie.spec_verify_workspace_bytes(B, k, V), dtype=torch.uint8, device="cuda")
+        outs = (torch.empty((B, k + 1), dtype=torch.int32, device="cuda"), i32([0] * B))
+
+        def verify(k=k, ids=ids, drafts=drafts, xk=xk, yk=yk, logits=logits, in_len=in_len, ws=ws, outs=outs):
+            llmie.input_embedding(ids, weights["embed"], xk)
+            dec.prefill_paged(xk, yk, kp, vp, table, in_len, cached, k + 1)
+            llmie.rmsnorm(yk, None, weights["final_norm"], EPS)
+            llmie.linear(yk, weights["lm_head"], logits)
+            llmie.spec_verify(logits, drafts, params, seq, fin, -1, draft_len=None, step=7, workspace=ws, out=outs)
+
+        arms[k] = verify
+    # the drafter alone, on rows of ctx tokens from an alphabet of 4 (matches of every n all over the row: the costly case)
+    toks = torch.randint(0, 4, (B, ctx + 64), generator=g, device="cuda").to(torch.int32)
+    tlen = i32([ctx] * B)
+    dout = (torch.empty((B, kmax + 1), dtype=torch.int32, device="cuda"), torch.empty((B, kmax), dtype=torch.int32, device="cuda"), i32([0] * B))
+
+    def draft():
+        llmie.ngram_draft(toks, tlen, kmax, max_n=3, min_n=1, out=dout)
+
+    for _ in range(3):   # every shape of the timed window, warm
+        plain()
+        draft()
+        for k in ks:
+            arms[k]()
+    torch.cuda.synchronize()
+    tp, tv, td = [], {k: [] for k in ks}, []
+    for _ in range(rounds):
+        tp.append(timed(plain, reps))
+        for k in ks:
+            tv[k].append(timed(arms[k], reps))
+        td.append(timed(draft, reps))
+    mp = statistics.median(tp)
+    res = dict(batch=B, ctx=ctx, plain_ms=mp, plain_ms_min_max=[min(tp), max(tp)], ngram_ms=statistics.median(td), verify=[])
+    for k in ks:
+        mv = statistics.median(tv[k])
+        # per-round ratios: the spread of the break-even itself (the arms of a round run back to back)
+        ratios = [a / b for a, b in zip(tv[k], tp)]
+        res["verify"].append(dict(k=k, rows=B * (k + 1), verify_ms=mv, verify_ms_min_max=[min(tv[k]), max(tv[k])], verify_over_plain=mv / mp,
+                                  verify_over_plain_min_max=[min(ratios), max(ratios)], break_even_tokens_per_step=mv / mp,
+                                  break_even_accepted_drafts=mv / mp - 1, speedup_if_all_accepted=(k + 1) * mp / mv))
+    dec.close()
+    del kp, vp
+    torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, nargs="*", default=[1, 8])
+    ap.add_argument("--k", type=int, nargs="*", default=[2, 4, 7])
+    ap.add_argument("--ctx", type=int, default=2048)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--layers", type=int, default=0, help="fewer layers than the model's 32 (a rehearsal; not a measurement)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("specbench: needs a GPU (a time measured anywhere else says nothing)")
+    llmie = bench.load_llmie()
+    cfg = dict(bench.LLAMA2_7B)
+    if a.layers:
+        cfg["num_layers"] = a.layers
+    weights = bench.build_weights(torch, cfg, 0)
+    res = dict(bench="spec_decode", device=torch.cuda.get_device_name(0), rounds=a.rounds, reps=a.reps, layers=cfg["num_layers"],
+               results=[run_batch(llmie, cfg, weights, B, a.k, a.ctx, a.rounds, a.reps) for B in a.batch])
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
