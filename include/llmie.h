@@ -732,6 +732,93 @@ int llmie_ngram_draft(const int32_t *tokens /* [batch, stride] */, int stride, c
                       int32_t *out_ids /* [batch, k+1]: the verify chunk's input ids */, int32_t *out_draft_ids /* [batch, k] */,
                       int32_t *out_draft_len /* [batch] */, llmie_stream stream);
 
+/* ABI 3 (an addition).  Multi-LoRA: per-row adapters on top of a projection.  No reference launcher.
+ *
+ * For a projection y = x . W^T (W is [N, K]; x [rows, K], y [rows, N], fp16, row-major), row m carrying adapter slot s = slot[m] gets
+ *   y[m, n] = fp16( float(y[m, n]) + scale_s * sum_r B_s[n, r] * t[m, j(n) * rank_s + r] ),   t[m, :] = x[m, :] . A_s^T
+ * A_s is [blocks * rank_s, K] and B_s is [N, rank_s], both fp16, row-major, 16-byte aligned.  The output columns are cut into
+ * `blocks` (1..3) column blocks of host-given widths (QKV: q / k / v; gate_up: gate / up; o and down: one) and j(n) is the block of
+ * column n; block j uses rows [j * rank, (j + 1) * rank) of A -- PEFT's separate q_proj / k_proj / v_proj (gate_proj / up_proj)
+ * adapters stacked onto the fused matrices.  A module whose A / B pointer pair is NULL contributes nothing.  Every sum is fp32; t
+ * is summed over K in fp32 (the K slices in a fixed order) and rounded to fp16 ONCE, as the operand of the second product; scale is
+ * applied to the fp32 sum before the update.  rank_s in {8, 16, 32, 64}; slots of different rank may meet in one call.
+ * A row is left bit for bit as it was when its slot is -1, lies outside [0, slots), or names a slot of rank 0 (an empty slot).
+ * fp16 activations only (LLMIE_F32: LLMIE_ERR_UNSUPPORTED).  No atomics on results; the K split is a host function of K alone; a
+ * row belongs to exactly one tile of <= 16 rows of one slot and every row of a tile is computed on its own: same inputs, same
+ * bits, and a row's bits depend neither on its position nor on which other rows or slots share the call.
+ *
+ * Everything that may change between steps lives in DEVICE memory read at launch: the slot table (per slot its rank and scale, per
+ * layer and module the A / B pointers) and the per-row or per-sequence slot array.  A captured step serves a new adapter mix, or a
+ * slot reloaded with another adapter, on replay.
+ *   llmie_lora_table_bytes(slots, layers) = slots * (16 + 64 * layers): [slots] x {int32 rank, float scale, 8 bytes of padding},
+ *     then [slots][layers][4 modules][2] device pointers (A, B).  A table of zero bytes is a table of empty slots.  0 for
+ *     non-positive sizes or slots > LLMIE_LORA_MAX_SLOTS.
+ *   llmie_lora_slot_load writes one slot from a HOST description (NULL: empties the slot).  Enqueued on `stream` as kernel launches
+ *     whose arguments carry the values (no host buffer has to outlive the call); not meant for a captured region.
+ *   llmie_lora_workspace_bytes(max_rows, slots, max_rank_total), with tiles = max_rows / 16 + min(slots, max_rows) and every term
+ *     rounded up to 256 bytes: 256 (the plan's header) + 4 * max_rows (the slot of every row) + 4 * tiles (the slot of every tile) +
+ *     64 * tiles (16 row indices per tile, -1 = padding) + LLMIE_LORA_MAX_KSPLIT * tiles * 16 * max_rank_total * 4 (the fp32
+ *     partials of t).  max_rank_total: the largest blocks * 64 of any llmie_lora_apply call on the workspace (192 covers QKV).
+ *   llmie_lora_plan, ONE launch per forward call: groups the rows of each slot, in row order, into tiles of <= 16 rows and leaves
+ *     the plan in the workspace.  lengths == NULL: slot is [rows]; else slot is [batch] and row t takes the slot of the sequence it
+ *     belongs to when the sequences lie back to back with lengths[b] rows each (rows behind their sum: -1).  Nothing is read back:
+ *     every later grid is sized to the bound `tiles` and surplus tiles exit at once.
+ *   llmie_lora_apply, TWO launches: shrink (grid tiles x K slices: fp32 partials of t by v_mfma_f32_16x16x32_f16, both operand
+ *     fragments 16-byte loads from global memory, an A matrix read once per tile) and expand (grid tiles x groups of 256 columns:
+ *     sums the K slices, the transposed product B . t^T so that a lane owns 4 consecutive columns of one row, scale, 8-byte
+ *     read-modify-write of y).  Reads the plan the last llmie_lora_plan left in `workspace` for the same rows and slots (a
+ *     workspace whose plan is of another shape: the launches do nothing).
+ * Refused on the host before any launch.  LLMIE_ERR_INVALID_ARG: NULL pointers; non-positive sizes; a slot, layer or module outside
+ * its range; a rank outside {8, 16, 32, 64}; an A without its B; fewer than 1 or more than 3 blocks; block widths not summing to N.
+ * LLMIE_ERR_UNSUPPORTED: LLMIE_F32; K % 32 != 0; a block width that is not a multiple of 16; x, y, A or B not 16-byte aligned;
+ * slots > LLMIE_LORA_MAX_SLOTS.  LLMIE_ERR_WORKSPACE: NULL, short or not 256-byte aligned.  No launch allocates or synchronises. */
+#define LLMIE_LORA_MAX_SLOTS 1024
+#define LLMIE_LORA_MAX_KSPLIT 8
+#define LLMIE_LORA_QKV 0
+#define LLMIE_LORA_O 1
+#define LLMIE_LORA_GATE_UP 2
+#define LLMIE_LORA_DOWN 3
+typedef struct {
+    const void *a[4]; /* per module (LLMIE_LORA_*): A [blocks * rank, K], device, fp16; NULL = the adapter lacks the module */
+    const void *b[4]; /* per module: B [N, rank], device, fp16 */
+} llmie_lora_layer;
+typedef struct { /* host struct */
+    int rank;    /* 8, 16, 32 or 64 */
+    float scale; /* lora_alpha / rank */
+    int layers;  /* entries of `layer`: the table's layer count */
+    const llmie_lora_layer *layer;
+} llmie_lora_adapter;
+size_t llmie_lora_table_bytes(int slots, int layers);
+int llmie_lora_slot_load(void *table_dev, int slots, int layers, int slot, const llmie_lora_adapter *host_desc, llmie_stream stream);
+size_t llmie_lora_workspace_bytes(int max_rows, int slots, int max_rank_total);
+int llmie_lora_plan(const int32_t *slot_dev, const int32_t *lengths_dev /* nullable */, int batch, int rows, const void *table_dev,
+                    int slots, void *workspace, size_t workspace_bytes, llmie_stream stream);
+int llmie_lora_apply(const void *x /* [rows, K] */, void *y /* [rows, N] in/out */, int rows, int K, int N, int blocks,
+                     const int *block_widths /* host, [blocks] */, const void *table_dev, int slots, int layers, int layer, int module,
+                     void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition).  Per-request adapters in the engine.  While a table is attached, llmie_decoder_forward, _forward_paged,
+ * _forward_ragged, _forward_paged_ragged, llmie_decoder_prefill and _prefill_paged run the "lora" launch sequence: the unfused
+ * decode sequence (the general prefill sequence: in-place norms, the plain QKV form with the RoPE + append launch in front of the
+ * flash kernel, gate/up as projection + llmie_silu_and_mul) with llmie_lora_apply behind the QKV projection (input: the normalised
+ * rows; before RoPE), the O projection (input: the attention output), the gate/up projection (input: the FFN-normalised rows; added
+ * to the un-activated buffer) and the down projection (input: the SwiGLU output), and ONE llmie_lora_plan per call.  The base
+ * projections run as before, on whatever route their planner picks: fp16, int8 or int4 weights.  seq_slot_dev[b] is the slot of
+ * batch row b in the decode entries and of sequence b in the prefill entries; it and the table are read on the device at every
+ * launch.  workspace: llmie_decoder_lora_workspace_bytes(cfg, max_tokens, slots) = llmie_lora_workspace_bytes(max(max_tokens,
+ * cfg->max_batch), slots, 192) bytes, the attach call's own (llmie_decoder_workspace_bytes and
+ * llmie_decoder_prefill_workspace_bytes keep their values); a call with more rows than it covers is LLMIE_ERR_WORKSPACE.  The table
+ * must have cfg->num_layers layers.  llmie_decoder_plan_name and llmie_decoder_prefill_layer_plan describe the sequence under
+ * LLMIE_PLAN_LORA.  llmie_decoder_lora_detach restores the previous sequences exactly.
+ * LLMIE_ERR_UNSUPPORTED: an LLMIE_F32 engine; an LLMIE_W_FP8 engine (its sequences never materialise fp16 normalised rows); an
+ * LLMIE_DEC_PACKED_ONLY engine (it has no row-major route for the base projections); hidden or inter sizes that are not multiples
+ * of 32, or q / kv widths that are not multiples of 16. */
+#define LLMIE_PLAN_LORA 1024u /* an adapter table is attached (llmie_decoder_lora_attach) */
+size_t llmie_decoder_lora_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int slots);
+int llmie_decoder_lora_attach(llmie_decoder *dec, const void *table_dev, int slots, const int32_t *seq_slot_dev, void *workspace,
+                              size_t workspace_bytes);
+int llmie_decoder_lora_detach(llmie_decoder *dec);
+
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,
  * context_attention.cpp:143-312) on PACKED tokens: hidden_in/out [num_tokens, H] hold the sequences back to back
  * (input_lengths[b] tokens each, device int32), history_lengths[b] tokens of each sequence are already in the caches;

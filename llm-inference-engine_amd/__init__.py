@@ -116,6 +116,14 @@ _SIGS = {
     "llmie_spec_verify": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz,
                           _i, _vp, _vp],
     "llmie_ngram_draft": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "llmie_lora_table_bytes": [_i, _i],
+    "llmie_lora_slot_load": [_vp, _i, _i, _i, _vp, _vp],
+    "llmie_lora_workspace_bytes": [_i, _i, _i],
+    "llmie_lora_plan": [_vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp],
+    "llmie_lora_apply": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _i, _vp],
+    "llmie_decoder_lora_workspace_bytes": [_vp, _i, _i],
+    "llmie_decoder_lora_attach": [_vp, _vp, _i, _vp, _vp, _sz],
+    "llmie_decoder_lora_detach": [_vp],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -144,6 +152,9 @@ _RESTYPES = {
     "llmie_beam_step_workspace_bytes": _sz,
     "llmie_kv_pages_fork_workspace_bytes": _sz,
     "llmie_spec_verify_workspace_bytes": _sz,
+    "llmie_lora_table_bytes": _sz,
+    "llmie_lora_workspace_bytes": _sz,
+    "llmie_decoder_lora_workspace_bytes": _sz,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -803,6 +814,28 @@ class Decoder:
     OPS = ("attn_norm", "qkv_gemm", "rope", "mha", "o_gemm", "ffn_norm", "gate_up_swiglu", "down_gemm",
            "final_norm", "lm_head", "topk", "sampling", "chain")
 
+    def lora_workspace_bytes(self, max_tokens, slots):
+        return lib().llmie_decoder_lora_workspace_bytes(C.byref(self.cfg), max_tokens, slots)
+
+    def lora_attach(self, table, seq_slot, max_tokens=None, workspace=None):
+        """While attached, every forward / prefill entry runs the lora sequence: seq_slot (device int32) holds the slot of batch
+        row b (decode) or of sequence b (prefill), -1 = no adapter; it and the table are read on the device at every launch.
+        max_tokens: the most rows a call will bring (default: max_batch); workspace: a uint8 tensor of lora_workspace_bytes, or None
+        to allocate it."""
+        import torch
+        assert table.layers == self.cfg.num_layers, "the table must have the engine's layer count"
+        need = self.lora_workspace_bytes(max_tokens or self.cfg.max_batch, table.slots)
+        if workspace is None:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.data.device)
+        _check(lib().llmie_decoder_lora_attach(self.handle, _p(table.data), table.slots, _p(seq_slot), _p(workspace), workspace.numel()),
+               "decoder_lora_attach")
+        self._lora_keep = (table, seq_slot, workspace)
+        return workspace
+
+    def lora_detach(self):
+        _check(lib().llmie_decoder_lora_detach(self.handle), "decoder_lora_detach")
+        self._lora_keep = None
+
     def profile_begin(self, max_events):
         _check(lib().llmie_decoder_profile_begin(self.handle, max_events), "decoder_profile_begin")
 
@@ -839,6 +872,111 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------ multi-LoRA: per-request adapters
+LORA_MODULES = ("qkv", "o", "gate_up", "down")   # LLMIE_LORA_QKV ... LLMIE_LORA_DOWN
+LORA_RANKS = (8, 16, 32, 64)
+LORA_MAX_SLOTS = 1024   # LLMIE_LORA_MAX_SLOTS
+LORA_MAX_KSPLIT = 8     # LLMIE_LORA_MAX_KSPLIT
+PLAN_LORA = 1024        # LLMIE_PLAN_LORA
+
+
+class LoraLayer(C.Structure):
+    _fields_ = [("a", _vp * 4), ("b", _vp * 4)]
+
+
+class LoraAdapter(C.Structure):
+    _fields_ = [("rank", _i), ("scale", _f), ("layers", _i), ("layer", C.POINTER(LoraLayer))]
+
+
+class LoraTable:
+    """The device slot table of llmie_lora_*: `data` (uint8, zeroed = every slot empty) plus the tensors its slots point to."""
+
+    def __init__(self, data, slots, layers):
+        self.data, self.slots, self.layers = data, slots, layers
+        self.keep = [None] * slots
+
+
+def lora_table(slots, layers, device="cuda"):
+    import torch
+    n = lib().llmie_lora_table_bytes(slots, layers)
+    if n == 0:
+        raise LlmieError("lora_table: bad shape slots=%d layers=%d" % (slots, layers))
+    return LoraTable(torch.zeros(n, dtype=torch.uint8, device=device), slots, layers)
+
+
+def _lora_stack(m, parts):
+    """one module's (A, B): the fused pair, or the separate projections' pairs stacked (A rows block after block, B rows too)"""
+    import torch
+    if m is None:
+        m = parts
+    if m is None or (isinstance(m, (tuple, list)) and all(x is None for x in m)):
+        return None
+    if any(x is None for x in m):   # separate projections with one missing, or a pair without its A or B
+        raise LlmieError("lora_slot_load: a fused module needs the adapter of every block (pass zero matrices for a missing one), "
+                         "and every A its B")
+    if isinstance(m[0], (tuple, list)):   # ((A_q, B_q), (A_k, B_k), (A_v, B_v))
+        return torch.cat([x[0] for x in m], 0).contiguous(), torch.cat([x[1] for x in m], 0).contiguous()
+    return m[0].contiguous(), m[1].contiguous()
+
+
+def lora_slot_load(table, slot, adapter, scale=1.0):
+    """adapter: None (empties the slot) or a list with one dict per layer.  Keys: qkv / o / gate_up / down -> (A, B) with A
+    [blocks * rank, K] and B [N, rank], fp16 device tensors; or q, k, v (all three) and gate, up (both) -> (A [rank, K], B [n, rank])
+    pairs of the separate projections, stacked here onto the fused matrices.  A missing key: the adapter lacks the module.  A zero
+    block (no k_proj adapter, say) is a pair of zero matrices.  Enqueued on the current stream."""
+    if adapter is None:
+        _check(lib().llmie_lora_slot_load(_p(table.data), table.slots, table.layers, slot, None, _st()), "lora_slot_load")
+        if 0 <= slot < table.slots:
+            # (the tensors of the adapter that was loaded stay referenced until the next load: launches already enqueued may read them)
+            table.keep[slot] = (table.keep[slot][1] or table.keep[slot][0] if table.keep[slot] else None, None)
+        return
+    arr = (LoraLayer * len(adapter))()
+    keep, rank = [], 0
+    for i, lw in enumerate(adapter):
+        sep = {"qkv": ("q", "k", "v"), "gate_up": ("gate", "up")}
+        for mo, name in enumerate(LORA_MODULES):
+            parts = [lw.get(k) for k in sep[name]] if name in sep else None
+            ab = _lora_stack(lw.get(name), parts)
+            if ab is None:
+                continue
+            keep.append(ab)
+            rank = rank or ab[1].shape[1]
+            if ab[1].shape[1] != rank or ab[0].shape[0] % rank:
+                raise LlmieError("lora_slot_load: layer %d module %s has rank %d (A rows %d), the adapter's first module has %d"
+                                 % (i, name, ab[1].shape[1], ab[0].shape[0], rank))
+            arr[i].a[mo], arr[i].b[mo] = _p(ab[0]), _p(ab[1])
+    desc = LoraAdapter(rank, scale, len(adapter), arr)
+    _check(lib().llmie_lora_slot_load(_p(table.data), table.slots, table.layers, slot, C.byref(desc), _st()), "lora_slot_load")
+    table.keep[slot] = (table.keep[slot][1] or table.keep[slot][0] if table.keep[slot] else None, keep)
+
+
+def lora_workspace_bytes(max_rows, slots, max_rank_total=192):
+    return lib().llmie_lora_workspace_bytes(max_rows, slots, max_rank_total)
+
+
+def lora_plan(slot, table, workspace, lengths=None, rows=None):
+    """one launch per forward call: groups the rows of each slot into tiles of <= 16.  lengths (device int32 [batch]): slot holds one
+    entry per sequence and is expanded over the lengths; rows: the packed token count then (default slot.numel())."""
+    batch = slot.numel()
+    rows = rows if rows is not None else batch
+    _check(lib().llmie_lora_plan(_p(slot), _p(lengths), batch, rows, _p(table.data), table.slots, _p(workspace), workspace.numel(), _st()),
+           "lora_plan")
+
+
+def lora_apply(x, y, table, layer, module, workspace, block_widths=None):
+    """y[m] += scale_s * B_s . (A_s . x[m]) for every row with a loaded slot (include/llmie.h), on the plan lora_plan left in
+    `workspace`.  module: index or name in LORA_MODULES; block_widths: the column blocks of y (default: one block)."""
+    if isinstance(module, str):
+        module = LORA_MODULES.index(module)
+    rows, K = x.shape
+    N = y.shape[1]
+    widths = list(block_widths) if block_widths is not None else [N]
+    arr = (C.c_int * len(widths))(*widths)
+    _check(lib().llmie_lora_apply(_p(x), _p(y), rows, K, N, len(widths), arr, _p(table.data), table.slots, table.layers, layer, module,
+                                  _p(workspace), workspace.numel(), _dt(x), _st()), "lora_apply")
+    return y
 
 
 # ------------------------------------------------------------------ weight-only quantised linears

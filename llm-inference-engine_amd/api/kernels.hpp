@@ -339,3 +339,19 @@ inline void launchNgramDraft(TensorWrapper<int> *tokens, TensorWrapper<int> *len
     LLMIE_CALL(llmie_ngram_draft(tokens->data, stride, len->data, finished ? reinterpret_cast<uint8_t *>(finished->data) : nullptr, batch, k,
                                  max_n, min_n, pad_id, out_ids->data, out_draft_ids->data, out_draft_len->data, llmie_api::st()));
 }
+
+// No reference launcher: per-row LoRA adapters on top of a projection (include/llmie.h has the semantics).  x [rows, K], y [rows, N]
+// (updated in place), slot [rows] (-1: no adapter); table: the device slot table (llmie_lora_table_bytes / llmie_lora_slot_load) of
+// `slots` slots and `layers` layers; block_widths: the column blocks of y (q / k / v, gate / up; one block otherwise).  Plans the
+// rows (one launch), then shrink + expand.
+template <typename T>
+void launchLoraApply(TensorWrapper<T> *x, TensorWrapper<T> *y, TensorWrapper<int> *slot, const void *table, int slots, int layers, int layer,
+                     int module, const std::vector<int> &block_widths) {
+    const int rows = x->shape[0], K = x->shape[1], N = y->shape[1], blocks = static_cast<int>(block_widths.size());
+    LLM_CHECK_WITH_INFO(y->shape[0] == rows && slot->shape[0] == rows, "x, y and slot should have the same rows");
+    const size_t ws = llmie_lora_workspace_bytes(rows, slots, 64 * (blocks < 1 ? 1 : (blocks > 3 ? 3 : blocks)));
+    void *scratch = llmie_api::scratch(ws);
+    LLMIE_CALL(llmie_lora_plan(slot->data, nullptr, rows, rows, table, slots, scratch, ws, llmie_api::st()));
+    LLMIE_CALL(llmie_lora_apply(x->data, y->data, rows, K, N, blocks, block_widths.data(), table, slots, layers, layer, module, scratch, ws,
+                                llmie_api::dtype_of<T>(), llmie_api::st()));
+}

@@ -63,6 +63,43 @@ template <typename T> class EngineHolder {
     int batch_cap = 0, max_seq = 0;
     void *pf_ws = nullptr;
     size_t pf_cap = 0;
+    llmie_decoder_config made{};   // the config of `engine`
+
+public:
+    // Per-request adapters (include/llmie.h llmie_decoder_lora_attach): the binding is attached to every engine this holder creates,
+    // with scratch for max_tokens rows; a binding without a table detaches.
+    struct LoraBinding {
+        const void *table = nullptr;
+        int slots = 0;
+        const int32_t *seq_slot = nullptr;
+        int max_tokens = 0;
+    };
+    void set_lora(const LoraBinding &b) {
+        lora = b;
+        lora_dirty = true;
+    }
+
+private:
+    LoraBinding lora;
+    bool lora_dirty = false;
+    void *lora_ws = nullptr;
+    size_t lora_cap = 0;
+    void sync_lora() {
+        if (!engine || !lora_dirty) return;
+        if (lora.table) {
+            const size_t bytes = llmie_decoder_lora_workspace_bytes(&made, lora.max_tokens, lora.slots);
+            LLM_CHECK_WITH_INFO(bytes > 0, "invalid adapter binding");
+            if (bytes > lora_cap) {
+                if (lora_ws) CHECK(hipFree(lora_ws));
+                CHECK(hipMalloc(&lora_ws, bytes));
+                lora_cap = bytes;
+            }
+            LLMIE_CALL(llmie_decoder_lora_attach(engine, lora.table, lora.slots, lora.seq_slot, lora_ws, lora_cap));
+        } else {
+            LLMIE_CALL(llmie_decoder_lora_detach(engine));
+        }
+        lora_dirty = false;
+    }
 
 public:
     ~EngineHolder() { destroy(); }
@@ -80,13 +117,17 @@ public:
         if (engine) llmie_decoder_destroy(engine);
         if (ws) (void)hipFree(ws);
         if (pf_ws) (void)hipFree(pf_ws);
+        if (lora_ws) (void)hipFree(lora_ws);
         engine = nullptr;
-        ws = pf_ws = nullptr;
-        pf_cap = 0;
+        ws = pf_ws = lora_ws = nullptr;
+        pf_cap = lora_cap = 0;
     }
     llmie_decoder *get(std::vector<LlamaLayerWeight<T> *> *lw, int num_layer, int head_num, int kv_head_num, int head_size,
                        int inter_size, const LlamaAttentionStaticParams &sp, float eps, int batch, int max_seq_len) {
-        if (engine && key == lw->data() && batch <= batch_cap && max_seq_len == max_seq) return engine;
+        if (engine && key == lw->data() && batch <= batch_cap && max_seq_len == max_seq) {
+            sync_lora();
+            return engine;
+        }
         destroy();
         llmie_decoder_config cfg{};
         cfg.head_num = head_num;
@@ -121,6 +162,9 @@ public:
         key = lw->data();
         batch_cap = batch;
         max_seq = max_seq_len;
+        made = cfg;
+        lora_dirty = lora.table != nullptr;
+        sync_lora();
         return engine;
     }
     void *prefill_workspace(const llmie_decoder_config *cfg, int tokens, int batch, size_t *bytes) {
@@ -294,6 +338,8 @@ public:
     }
     // set false to force the per-kernel loop even for HF-layout weights (used by the parity tests)
     bool use_fused_engine = true;
+    // per-request adapters on the fused engine (the per-kernel loop knows none)
+    void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
 
     // self_decoder.cpp:24-122
     void forward(TensorMap *input_tensors, std::vector<LlamaLayerWeight<T> *> *layer_weights, TensorMap *output_tensors,
@@ -463,6 +509,8 @@ public:
     // set false to force the reference's kernel sequence (padded q/k/v, batched GEMMs, softmax) even when the
     // flash-attention engine path (fp16, head_size 128, HF-layout weights) is eligible
     bool use_fused_engine = true;
+    // per-request adapters on the fused engine (the reference's kernel sequence knows none)
+    void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
 
     LlamaContextDecoder(const int &head_num, const int &kv_head_num, const int &head_size, const int &intermediate_size,
                         const int &num_layer, LlamaAttentionStaticParams *const &attention_static_params,

@@ -83,6 +83,8 @@ private:
     DevBuf<unsigned char> d_sample_ws, d_score_ws;
     DevBuf<int> d_targets, d_spec;
     DevBuf<float> d_logprob;
+    DevBuf<unsigned char> d_lora_table;   // the adapter slot table (loadAdapter)
+    DevBuf<int> d_lora_slot;              // the slot of the one sequence this model runs
     std::vector<int> penalty_ids;   // prompt + generated ids: the penalty history of the SamplingConfig path
     // llmie_sampling_ext of the SamplingConfig path: mask, bias list, stop list, min_step, and the top-N of the last step
     DevBuf<uint32_t> d_mask;
@@ -228,6 +230,35 @@ public:
         }
     };
     SamplingConfig sampling;
+
+    // Per-request LoRA adapters (include/llmie.h llmie_lora_* / llmie_decoder_lora_attach).  loadAdapter puts a host description
+    // (rank, scale, per layer and module the DEVICE A / B matrices, which the caller keeps alive) into one of kAdapterSlots slots
+    // of the model's device table (nullptr empties the slot); selectAdapter names the slot the NEXT request runs with (-1: the base
+    // model).  Both decoders read the table and the slot on the device, so neither call rebuilds anything.  fp16 models only.
+    static constexpr int kAdapterSlots = 8;
+    void loadAdapter(int slot, const llmie_lora_adapter *desc) {
+        // the adapter updates live in the fused engine's lora sequence; the per-kernel loops know none, and a model that runs them
+        // must not take an adapter and then ignore it
+        LLM_CHECK_WITH_INFO((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs),
+                            "loadAdapter: adapters need the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        if (!d_lora_table.p) {
+            const size_t bytes = llmie_lora_table_bytes(kAdapterSlots, num_layers);
+            CHECK(hipMemsetAsync(d_lora_table.ensure(bytes), 0, bytes, llmie_api::st()));
+            const int none = -1;
+            CHECK(hipMemcpyAsync(d_lora_slot.ensure(1), &none, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+            CHECK(hipStreamSynchronize(llmie_api::st()));
+            typename EngineHolder<T>::LoraBinding b;
+            b.table = d_lora_table.p, b.slots = kAdapterSlots, b.seq_slot = d_lora_slot.p, b.max_tokens = max_seq_len;
+            context_decoder->setLora(b);
+            self_decoder->setLora(b);
+        }
+        LLMIE_CALL(llmie_lora_slot_load(d_lora_table.p, kAdapterSlots, num_layers, slot, desc, llmie_api::st()));
+    }
+    void selectAdapter(int slot) {
+        LLM_CHECK_WITH_INFO(d_lora_table.p != nullptr, "selectAdapter: no adapter was loaded");
+        CHECK(hipMemcpyAsync(d_lora_slot.p, &slot, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (`slot` lives on this frame)
+    }
     // the last step of the SamplingConfig path: the top_logprobs most likely tokens of the raw row (id -1 / -INFINITY past the
     // row's valid tokens) and the picked token's raw log-probability
     const std::vector<int> &lastTopIds() const { return last_top_ids; }
@@ -359,6 +390,8 @@ public:
     }
     // the context decoder's output [n, hidden_units] of the last prefill (generateFirstToken normalises its last row in place)
     const T *contextOutput() const { return d_ctx_out.p; }
+    // the self decoder's output [1, hidden_units] of the last decode step, before the final norm
+    const T *decodeOutput() const { return d_dec_out.p; }
     // the decode step response() runs after a prefill: token `id` joins the context, then generateNextToken
     int continueWith(int id) {
         LLM_CHECK_WITH_INFO(h_step + 1 < max_seq_len, "context does not fit max_seq_len");

@@ -51,6 +51,15 @@ struct llmie_decoder {
     unsigned char *pk_base = nullptr;   // first byte of the packed images (the workspace area carved for them)
     unsigned *pk_sync = nullptr, *pk_err = nullptr;
     unsigned long long *pk_stamps = nullptr;   // diagnostic: phase-edge timestamps of the LAST chain launch of a step
+    // per-request adapters (llmie_decoder_lora_attach): the device slot table, the slot of every batch row / sequence, the attach
+    // call's scratch.  table != nullptr: every forward / prefill entry runs the lora sequence
+    struct Lora {
+        const void *table = nullptr;
+        int slots = 0;
+        const int32_t *seq_slot = nullptr;
+        void *ws = nullptr;
+        size_t ws_bytes = 0;
+    } lora;
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -570,8 +579,8 @@ static bool fused_attention_geometry(const llmie_decoder_config &c) {
     return (c.head_size == 32 || c.head_size == 64 || c.head_size == 128 || c.head_size == 256) && (rep == 1 || rep == 2 || rep == 4 || rep == 8);
 }
 
-enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED };
-enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED };
+enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED, DP_LORA };
+enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED, DREF_LORA };
 // One decode call as the planner sees it.  mis_hidden / mis_wqkv0: address % 16 of the hidden state and of layer 0's QKV matrix.
 struct DecodeCall {
     llmie_decoder_config cfg;
@@ -579,7 +588,19 @@ struct DecodeCall {
     bool paged, ragged;
     unsigned mis_hidden, mis_wqkv0;
     EngineSwitches sw;
+    bool lora;   // an adapter table is attached
 };
+// what the adapter updates need of an engine: fp16 rows in front of every projection and a row-major route for the base (not fp8
+// weights, not a packed-only engine), K % 32 == 0 and column blocks (q / k / v, gate / up) that are multiples of 16
+static bool lora_engine_ok(const llmie_decoder_config &c) {
+    const int H = c.head_num * c.head_size;
+    return c.dtype == LLMIE_F16 && c.wfmt != LLMIE_W_FP8 && c.wfmt != LLMIE_W_F32 && !(c.flags & LLMIE_DEC_PACKED_ONLY) && H % 32 == 0 &&
+           c.inter_size % 32 == 0 && (c.kv_head_num * c.head_size) % 16 == 0;
+}
+static const char *const kLoraRefusal =
+    "adapters need an fp16 engine with fp16 / int8 / int4 weights (an fp8-weight engine never materialises fp16 normalised rows, a "
+    "LLMIE_DEC_PACKED_ONLY engine has no row-major route), hidden and inter sizes that are multiples of 32 and q / kv widths that are "
+    "multiples of 16";
 // The LLMIE_CHAIN probe (can every projection of a layer join a chain at this batch?) reads the engine's images and LDS plans, so it
 // stays with the packed sequence: the plan answers DP_PACKED with chain_wanted, and the dispatch upgrades to DP_PACKED_CHAIN where
 // the probe passes.
@@ -597,6 +618,15 @@ static DecodePlan plan_decode(const DecodeCall &d) {
     // measured crossover on MI355X (7B, ctx 512, tokens/s GEMV vs split-K): fp16 b4 1157/1143, b6 1496/1592; int8 b4 1416/1404,
     // b6 1672/1962; fp8 b3 947/944, b4 1127/1213; int4 b2 796/745, b3 896/1074
     const int gemv_max = gemv_max_batch(c.wfmt);
+    if (d.lora) {
+        // the unfused sequence with the four adapter updates behind its projections; its attention launch carries what the fused
+        // paths need of it (paged / e4m3 caches, ragged lengths) where the geometry has the fused kernel
+        if (!lora_engine_ok(c)) return {DP_REFUSED, DREF_LORA, false};
+        if (!attn_ok && d.paged) return {DP_REFUSED, DREF_PAGED, false};
+        if (!attn_ok && c.kv_fmt == LLMIE_KV_FP8) return {DP_REFUSED, DREF_KV_FP8, false};
+        if (!attn_ok && d.ragged) return {DP_REFUSED, DREF_RAGGED, false};
+        return {DP_LORA, DREF_NONE, false};
+    }
     const bool int4_ok = wbits == 4 && c.int4_group == 128 && batch <= 64;  // int4 MFMA form: group-128 scales, 64 rows per pass
     const bool batch_path_ok = !d.sw.no_fused_batch && c.dtype == LLMIE_F16 && (wbits == 16 || wbits == 8 || int4_ok || fp8) && attn_ok &&
                                batch <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H);
@@ -622,6 +652,7 @@ static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
             set_error("decoder_forward: a LLMIE_DEC_PACKED_ONLY engine decodes on the packed kernels only (batch <= %d, no path switch)",
                       packed_rows_max(d.cfg));
             break;
+        case DREF_LORA: set_error("decoder_forward: %s", kLoraRefusal); break;
         case DREF_PAGED: set_error("decoder_forward_paged: the paged KV cache needs the fused decode paths (fp16 engines, batch <= 128)"); break;
         case DREF_KV_FP8:
             set_error("decoder_forward: the fp8 KV cache needs the fused decode paths (batch <= 128, fp16/int8/int4/fp8 weights with "
@@ -632,12 +663,12 @@ static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
     return LLMIE_ERR_UNSUPPORTED;
 }
 static const char *decode_path_name(int path) {
-    static const char *const names[] = {"refused", "gemv", "packed", "packed_chain", "splitk", "unfused"};
+    static const char *const names[] = {"refused", "gemv", "packed", "packed_chain", "splitk", "unfused", "lora"};
     return names[path];
 }
 
-enum PrefillPath : int { PP_REFUSED = 0, PP_PACKED_ONLY, PP_SHORT_SPLITK, PP_LEAN, PP_GENERAL };
-enum PrefillRefusal : int { PREF_NONE = 0, PREF_FORMAT, PREF_PACKED_ONLY_FP8 };
+enum PrefillPath : int { PP_REFUSED = 0, PP_PACKED_ONLY, PP_SHORT_SPLITK, PP_LEAN, PP_GENERAL, PP_LORA };
+enum PrefillRefusal : int { PREF_NONE = 0, PREF_FORMAT, PREF_PACKED_ONLY_FP8, PREF_LORA };
 // One prefill call as the planner sees it.  The split-K kernels read the weights, the out-of-place norms hidden_out and the gammas
 // in 16-byte vectors: weights handed over as views at other offsets (llmie_decoder_create takes any address) run the general sequences.
 struct PrefillCall {
@@ -648,6 +679,7 @@ struct PrefillCall {
     bool hidden_gammas_a16;   // hidden_out and every gamma 16-byte aligned
     bool o_bias;              // some layer has an output-projection bias
     EngineSwitches sw;
+    bool lora;                // an adapter table is attached
 };
 struct PrefillPlan {
     int path, refusal;
@@ -658,6 +690,7 @@ static PrefillPlan plan_prefill(const PrefillCall &p) {
     const bool fp8 = c.wfmt == LLMIE_W_FP8;
     const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
     if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits) || c.head_size != 128) return {PP_REFUSED, PREF_FORMAT};
+    if (p.lora) return lora_engine_ok(c) ? PrefillPlan{PP_LORA, PREF_NONE} : PrefillPlan{PP_REFUSED, PREF_LORA};
     if (c.flags & LLMIE_DEC_PACKED_ONLY) return fp8 ? PrefillPlan{PP_REFUSED, PREF_PACKED_ONLY_FP8} : PrefillPlan{PP_PACKED_ONLY, PREF_NONE};
     const bool short_fmt_ok = !fp8 && (wqbits != 4 || (c.int4_group == 128 && T <= 64));   // int4 split-K form: 64 rows, group 128
     if (!p.sw.no_fused_short_prefill && short_fmt_ok && p.weights_a16 && (wqbits != 4 || p.int4_scales_a4) && T <= 128 && H % 256 == 0 &&
@@ -669,10 +702,11 @@ static PrefillPlan plan_prefill(const PrefillCall &p) {
 static int prefill_refuse(const PrefillPlan &p) {
     if (p.refusal == PREF_FORMAT)
         LLMIE_UNSUPPORTED("decoder_prefill: fp16 activations + fp16 / int8 / int4 / fp8 weights + head_size 128 only (use the per-kernel path)");
+    if (p.refusal == PREF_LORA) LLMIE_UNSUPPORTED("decoder_prefill: %s", kLoraRefusal);
     LLMIE_UNSUPPORTED("decoder_prefill: LLMIE_DEC_PACKED_ONLY engines prefill fp16 / int8 / int4 weights only");
 }
 static const char *prefill_path_name(int path) {
-    static const char *const names[] = {"refused", "packed_only", "short_splitk", "lean", "general"};
+    static const char *const names[] = {"refused", "packed_only", "short_splitk", "lean", "general", "lora"};
     return names[path];
 }
 
@@ -705,7 +739,7 @@ struct PrefillLayerPlan {
 // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
 // this holds writes the epilogue's token table once, whatever its layers end up choosing.)
 static bool prefill_rope_fusable(const PrefillCall &p) {
-    return !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+    return !p.lora && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
 }
 static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
     const llmie_decoder_config &c = p.cfg;
@@ -727,6 +761,10 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         const SplitKSlabs sk{slabs.p, 1, T, QKV};
         o.qkv = !p.sw.no_qkv_rope_fusion && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
         o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
+    } else if (path == PP_LORA) {
+        // the general sequence with the forms the adapter updates need: normalised rows in place, the QKV buffer un-rotated (the update
+        // lands before RoPE: the RoPE + append launch runs in front of the flash kernel), gate/up un-activated
+        o.attn_norm = o.ffn_norm = PN_INPLACE, o.qkv = PQ_PLAIN, o.gate_up = PG_TWO_LAUNCH;
     } else if (path == PP_PACKED_ONLY) {
         // every projection runs the fp16 GEMM on the unpacked image of its matrix: the fp16 forms, on the de-quantisation area
         o.qkv = rope_ok && lc.deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, ws, nullptr, ws)
@@ -773,12 +811,15 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         o.launches[op] = 1;
     if (o.qkv == PQ_ROPE_UNPACKED || o.qkv == PQ_SPLITK || o.qkv == PQ_SPLITK_ROPE) o.launches[LLMIE_OP_QKV_GEMM] = 2;
     if (o.gate_up == PG_TWO_LAUNCH || o.gate_up == PG_UNPACK_TWO_LAUNCH || o.gate_up == PG_SPLITK) o.launches[LLMIE_OP_GATE_UP_SWIGLU] = 2;
+    if (path == PP_LORA)   // shrink + expand behind each of the four projections
+        for (int op : {LLMIE_OP_QKV_GEMM, LLMIE_OP_O_GEMM, LLMIE_OP_GATE_UP_SWIGLU, LLMIE_OP_DOWN_GEMM}) o.launches[op] += 2;
     return o;
 }
 // the PrefillCall llmie_decoder_plan_name / llmie_decoder_prefill_layer_plan describe with their call flags
 static PrefillCall prefill_call_of_flags(const llmie_decoder_config &cfg, int tokens, unsigned call_flags, const EngineSwitches &sw) {
     return PrefillCall{cfg, tokens, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
-                       !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw};
+                       !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw,
+                       (call_flags & LLMIE_PLAN_LORA) != 0};
 }
 
 // Host-only: the launch sequence llmie_decoder_forward (prefill = 0, rows = batch) or llmie_decoder_prefill (prefill = 1, rows =
@@ -808,7 +849,8 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
         return nullptr;
     }
     const DecodeCall dc{*cfg, rows, (call_flags & LLMIE_PLAN_PAGED) != 0, (call_flags & LLMIE_PLAN_RAGGED) != 0,
-                        (call_flags & LLMIE_PLAN_HIDDEN_MISALIGNED) ? 8u : 0u, (call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED) ? 8u : 0u, sw};
+                        (call_flags & LLMIE_PLAN_HIDDEN_MISALIGNED) ? 8u : 0u, (call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED) ? 8u : 0u, sw,
+                        (call_flags & LLMIE_PLAN_LORA) != 0};
     const DecodePlan p = plan_decode(dc);
     if (p.path == DP_REFUSED) return (void)decode_refuse(dc, p), nullptr;
     return decode_path_name(p.path);
@@ -1044,6 +1086,7 @@ struct DecodeStep {
         return LLMIE_OK;
     }
     int unfused() const;
+    int lora() const;
 };
 
 // ---- the reference's launch sequence (self_decoder.cpp:69-119), one kernel per step; RoPE inside the attention launch where its
@@ -1080,6 +1123,54 @@ int DecodeStep::unfused() const {
     return LLMIE_OK;
 }
 
+// the attach call's scratch must cover this call's rows: checked before anything is enqueued
+static int lora_rows_fit(const llmie_decoder *d, int rows, const char *who) {
+    const size_t need = llmie_lora_workspace_bytes(rows, d->lora.slots, 192);
+    if (d->lora.ws_bytes < need) {
+        set_error("%s: the adapter workspace given to llmie_decoder_lora_attach does not cover %d rows (%zu < %zu)", who, rows, d->lora.ws_bytes, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    return LLMIE_OK;
+}
+
+// one adapter update of the lora sequences: y += scale . B . (A . x) per row, shrink + expand on the plan this call's plan launch left
+static int engine_lora(const llmie_decoder *d, const void *x, void *y, int rows, int K, int N, int blocks, const int *widths, int layer,
+                       int module, llmie_stream stream) {
+    return llmie_lora_apply(x, y, rows, K, N, blocks, widths, d->lora.table, d->lora.slots, d->cfg.num_layers, layer, module, d->lora.ws,
+                            d->lora.ws_bytes, LLMIE_F16, stream);
+}
+
+// ---- per-request adapters: the unfused sequence, every projection followed by its adapter update where the update's input is
+// materialised (the QKV one before RoPE: the attention launch rotates); gate/up as projection + update + llmie_silu_and_mul ----
+int DecodeStep::lora() const {
+    int rc;
+    const int qkv_w[3] = {c.head_num * c.head_size, c.kv_head_num * c.head_size, c.kv_head_num * c.head_size}, gu_w[2] = {I, I};
+    if ((rc = llmie_lora_plan(dec->lora.seq_slot, nullptr, batch, batch, dec->lora.table, dec->lora.slots, dec->lora.ws, dec->lora.ws_bytes, stream)))
+        return rc;
+    for (int l = 0; l < c.num_layers; ++l) {
+        const llmie_layer_weights &w = dec->layers[l];
+        TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, dec->resid, w.attn_norm_gamma, c.rms_eps, batch, H, dt, stream));
+        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, h, w.qkv, dec->qkv, batch, H, QKV, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_QKV_GEMM, engine_lora(dec, h, dec->qkv, batch, H, QKV, 3, qkv_w, l, LLMIE_LORA_QKV, stream));
+        if (fused_attention_geometry(c)) {
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
+        } else {
+            TIMED(LLMIE_OP_ROPE, llmie_rope_decode(dec->qkv, batch, c.head_num, c.kv_head_num, c.head_size, pos.step, pos.step_dev,
+                                                   c.rotary_dim, c.rotary_base, dt, stream));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l, nullptr, nullptr, 0, false));
+        }
+        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, dec->mha, w.o, h, batch, H, H, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_O_GEMM, engine_lora(dec, dec->mha, h, batch, H, H, 1, &H, l, LLMIE_LORA_O, stream));
+        TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(dec->resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, batch, H, dt, stream));
+        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, h, w.gate_up, dec->gu, batch, H, 2 * I, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_lora(dec, h, dec->gu, batch, H, 2 * I, 2, gu_w, l, LLMIE_LORA_GATE_UP, stream));
+        TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(dec->gu, dec->act, batch, I, dt, stream));
+        TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, dec->act, w.down, h, batch, I, H, false, dec->resid, false, stream));
+        TIMED(LLMIE_OP_DOWN_GEMM, engine_lora(dec, dec->act, h, batch, I, H, 1, &H, l, LLMIE_LORA_DOWN, stream));
+    }
+    return LLMIE_OK;
+}
+
 // every decode entry point: validate, copy hidden_in, plan, refuse or dispatch
 static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache, void *v_cache,
                            const int32_t *block_table, int max_pages, int num_pages, int batch, const DecodePos &pos, llmie_stream stream) {
@@ -1088,6 +1179,8 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
     LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "decoder_forward: batch %d outside [1,%d]", batch, c.max_batch);
     LLMIE_REQUIRE(pos.step_dev || (pos.step >= 1 && pos.step <= c.max_seq_len), "decoder_forward: step %d outside [1,%d]", pos.step,
                   c.max_seq_len);
+    if (dec->lora.table)
+        if (int rc = lora_rows_fit(dec, batch, "decoder_forward")) return rc;
     if (hidden_out != hidden_in) {
         hipError_t e = hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(batch) * dec->H * dec->esz,
                                       hipMemcpyDeviceToDevice, as_stream(stream));
@@ -1096,7 +1189,8 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
             return LLMIE_ERR_LAUNCH;
         }
     }
-    const DecodeCall call{c, batch, block_table != nullptr, pos.ragged != 0, mis16(hidden_out), mis16(dec->layers[0].qkv.data), engine_switches()};
+    const DecodeCall call{c, batch, block_table != nullptr, pos.ragged != 0, mis16(hidden_out), mis16(dec->layers[0].qkv.data), engine_switches(),
+                          dec->lora.table != nullptr};
     const DecodePlan plan = plan_decode(call);
     const DecodeStep s{dec, c, hidden_out, batch, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), pos, stream, as_stream(stream),
                        dec->H, dec->QKV, dec->I, c.wfmt == LLMIE_W_F16 ? 16 : (c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0)),
@@ -1106,6 +1200,7 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
         case DP_PACKED: return plan.chain_wanted && s.chain_joins() ? s.packed_chain() : s.packed();
         case DP_SPLITK: return s.splitk();
         case DP_UNFUSED: return s.unfused();
+        case DP_LORA: return s.lora();
         default: return decode_refuse(call, plan);
     }
 }
@@ -1424,6 +1519,29 @@ struct PrefillPass {
         }
         return LLMIE_OK;
     }
+    // per-request adapters: the general sequence in the forms plan_prefill_layer forces, every projection followed by its adapter update
+    int lora() const {
+        int rc;
+        const int qkv_w[3] = {c.head_num * c.head_size, c.kv_head_num * c.head_size, c.kv_head_num * c.head_size}, gu_w[2] = {I, I};
+        for (int l = 0; l < c.num_layers; ++l) {
+            const llmie_layer_weights &w = dec->layers[l];
+            const PrefillLayerPlan lp = layer_plan(w);
+            TIMED(LLMIE_OP_ATTN_NORM, attn_norm(lp.attn_norm, w));
+            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, h, lp.qkv));
+            TIMED(LLMIE_OP_QKV_GEMM, engine_lora(dec, h, qkv, T, H, QKV, 3, qkv_w, l, LLMIE_LORA_QKV, stream));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
+            TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, h, H, H, nullptr));
+            TIMED(LLMIE_OP_O_GEMM, engine_lora(dec, attn, h, T, H, H, 1, &H, l, LLMIE_LORA_O, stream));
+            TIMED(LLMIE_OP_FFN_NORM, ffn_norm(lp.ffn_norm, w));
+            if (lp.gate_up != PG_TWO_LAUNCH) return bad_form("gate/up", lp.gate_up);
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(h, w.gate_up, gu, H, 2 * I, nullptr));
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_lora(dec, h, gu, T, H, 2 * I, 2, gu_w, l, LLMIE_LORA_GATE_UP, stream));
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(gu, act, T, I, LLMIE_F16, stream));
+            TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
+            TIMED(LLMIE_OP_DOWN_GEMM, engine_lora(dec, act, h, T, I, H, 1, &H, l, LLMIE_LORA_DOWN, stream));
+        }
+        return LLMIE_OK;
+    }
     // the general sequence (context_decoder.cpp:70-199): every format, any alignment, an output-projection bias
     int general() const {
         int rc;
@@ -1459,7 +1577,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (int rc = prefill_shape_ok(c, batch, num_tokens, max_q_len)) return rc;
     const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
     const EngineSwitches &sw = engine_switches();
-    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw};
+    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr};
     for (const llmie_layer_weights &w : dec->layers) {
         call.weights_a16 = call.weights_a16 && (mis16(w.qkv.data) | mis16(w.o.data) | mis16(w.gate_up.data) | mis16(w.down.data)) == 0;
         call.int4_scales_a4 = call.int4_scales_a4 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
@@ -1469,6 +1587,8 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     }
     const PrefillPlan plan = plan_prefill(call);
     if (plan.path == PP_REFUSED) return prefill_refuse(plan);
+    if (plan.path == PP_LORA)
+        if (int rc = lora_rows_fit(dec, T, "decoder_prefill")) return rc;
     const PrefillCarve o = prefill_carve(&c, T, batch);
     if (workspace_bytes < o.total || reinterpret_cast<uintptr_t>(workspace) % 256) {
         set_error("decoder_prefill: workspace too small or unaligned (%zu < %zu)", workspace_bytes, o.total);
@@ -1513,7 +1633,11 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
         ra.v_inv_scale = 1.0f / p.kv.v_scale;
         if ((rc = prefill_token_table(cum, history_lengths, batch, T, tok_b, tok_tpos, ra, p.rope_args, st))) return rc;
     }
+    if (plan.path == PP_LORA &&   // the slot of every token: its sequence's, expanded over the lengths on the device
+        (rc = llmie_lora_plan(dec->lora.seq_slot, input_lengths, batch, T, dec->lora.table, dec->lora.slots, dec->lora.ws, dec->lora.ws_bytes, stream)))
+        return rc;
     switch (plan.path) {
+        case PP_LORA: return p.lora();
         case PP_PACKED_ONLY: return p.packed_only();
         case PP_SHORT_SPLITK: return p.short_splitk();
         case PP_LEAN: return p.lean();
@@ -1536,6 +1660,32 @@ extern "C" int llmie_decoder_prefill_paged(llmie_decoder *dec, const void *hidde
     if (int rc = paged_args_ok(dec, block_table, max_pages, num_pages, "decoder_prefill_paged")) return rc;
     return decoder_prefill(dec, hidden_in, hidden_out, k_pool, v_pool, block_table, max_pages, num_pages, input_lengths, history_lengths, batch,
                            num_tokens, max_q_len, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t llmie_decoder_lora_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int slots) {
+    if (!config_ok(cfg) || max_tokens <= 0) return 0;
+    return llmie_lora_workspace_bytes(max_tokens > cfg->max_batch ? max_tokens : cfg->max_batch, slots, 192);
+}
+
+extern "C" int llmie_decoder_lora_attach(llmie_decoder *dec, const void *table_dev, int slots, const int32_t *seq_slot_dev, void *workspace,
+                                         size_t workspace_bytes) {
+    LLMIE_REQUIRE(dec && table_dev && seq_slot_dev && workspace, "decoder_lora_attach: NULL pointer");
+    LLMIE_REQUIRE(slots > 0, "decoder_lora_attach: %d slots", slots);
+    if (slots > LLMIE_LORA_MAX_SLOTS) LLMIE_UNSUPPORTED("decoder_lora_attach: %d slots above LLMIE_LORA_MAX_SLOTS (%d)", slots, LLMIE_LORA_MAX_SLOTS);
+    if (!lora_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_lora_attach: %s", kLoraRefusal);
+    const size_t need = llmie_lora_workspace_bytes(dec->cfg.max_batch, slots, 192);
+    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
+        set_error("decoder_lora_attach: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    dec->lora.table = table_dev, dec->lora.slots = slots, dec->lora.seq_slot = seq_slot_dev, dec->lora.ws = workspace, dec->lora.ws_bytes = workspace_bytes;
+    return LLMIE_OK;
+}
+
+extern "C" int llmie_decoder_lora_detach(llmie_decoder *dec) {
+    LLMIE_REQUIRE(dec, "decoder_lora_detach: NULL decoder");
+    dec->lora = llmie_decoder::Lora{};
+    return LLMIE_OK;
 }
 
 // Host-only: what one layer of llmie_decoder_prefill launches (include/llmie.h) -- the pass's plan_prefill, plan_prefill_layer for a
