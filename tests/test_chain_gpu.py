@@ -23,6 +23,8 @@ from tests.conftest import load_llmie
 llmie = load_llmie()
 DEV, F16 = "cuda", torch.float16
 out_path, wfmt = sys.argv[1], sys.argv[2]
+# (rms_eps, rotary_base, rotary_dim): the defaults every engine test builds with, or a point off them
+eps, base, rot = (0.5, 500000.0, 64) if sys.argv[3:] == ["P1"] else (1e-5, 10000.0, 128)
 rng = np.random.default_rng(23)
 nh, hs, I, L, max_seq = 32, 128, 11008, 3, 160
 H, QKV = nh * hs, 3 * nh * hs
@@ -47,7 +49,7 @@ fmt = {"f16": llmie.W_F16, "int8": llmie.W_INT8, "int4": llmie.W_INT4, "fp8": ll
 res = {}
 for bs in ((9, 16) if wfmt == "fp8" else ((5, 16) if wfmt == "int4" else (5, 17, 32))):
     cfg = dict(head_num=nh, kv_head_num=nh, head_size=hs, inter_size=I, num_layers=L, vocab_size=100, max_seq_len=max_seq, max_batch=bs,
-               rotary_dim=hs, rotary_base=10000.0, rms_eps=1e-5, dtype=llmie.F16, wfmt=fmt, int4_group=128)
+               rotary_dim=rot, rotary_base=base, rms_eps=eps, dtype=llmie.F16, wfmt=fmt, int4_group=128)
     dec = llmie.Decoder(cfg, layers)
     g = torch.Generator(device="cpu").manual_seed(bs)
     kc = (torch.randn((L, bs, nh, max_seq, hs), generator=g) * 0.5).to(DEV).to(F16)
@@ -80,9 +82,9 @@ np.savez(out_path, **res)
 """ % dict(root=ROOT)
 
 
-def _run(tmp_path, name, wfmt, env_extra):
+def _run(tmp_path, name, wfmt, env_extra, point=()):
     out = os.path.join(str(tmp_path), name + ".npz")
-    r = subprocess.run([sys.executable, "-c", PROBE, out, wfmt], capture_output=True, text=True, timeout=900, cwd=ROOT,
+    r = subprocess.run([sys.executable, "-c", PROBE, out, wfmt, *point], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, **env_extra))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return dict(np.load(out))
@@ -97,3 +99,18 @@ def test_chain_launch_is_bit_identical_to_the_launch_sequence(tmp_path, wfmt):
         assert np.isfinite(chain[k]).all()
         assert np.array_equal(chain[k], seq[k]), "%s %s: chain launch differs from the launch sequence (max diff %g)" % (
             wfmt, k, np.abs(chain[k] - seq[k]).max())
+
+
+def test_chain_launch_takes_the_engine_eps_and_rope_parameters(tmp_path):
+    """the same comparison off the default point (eps 0.5, base 500000, rot 64): bit identity at eps 1e-5 cannot tell whether the chain
+    launch takes eps at all -- there a dropped eps moves a row by 1.5e-5 relative, below an fp16 ulp.  The launch sequence at this point
+    is held to the oracle by tests/test_model_params_gpu.py; a chain that ignored the parameters would differ from it in every row."""
+    chain = _run(tmp_path, "chain_p1", "f16", {"LLMIE_CHAIN": "1"}, ("P1",))
+    seq = _run(tmp_path, "seq_p1", "f16", {}, ("P1",))
+    default = _run(tmp_path, "seq_p0", "f16", {})
+    assert set(chain) == set(seq) and chain
+    for k in chain:
+        assert np.isfinite(chain[k]).all()
+        assert np.array_equal(chain[k], seq[k]), "%s: chain launch differs from the launch sequence at P1 (max diff %g)" % (
+            k, np.abs(chain[k] - seq[k]).max())
+        assert not np.array_equal(seq[k], default[k]), "%s: the point changed nothing" % k
