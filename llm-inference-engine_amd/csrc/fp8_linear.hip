@@ -108,9 +108,11 @@ static size_t fp8_act_bytes(int M, int K) {   // quantised activations + per-tok
 }
 extern "C" size_t llmie_linear_fp8_workspace_bytes(int M, int K, int N) {
     if (M <= 0 || K <= 0 || N < 0) return 0;
-    // quantised activations + per-token scales, then the fp32 slabs of the split-K form (8 < M, below the tiled GEMM's sizes);
+    // quantised activations + per-token scales, then the fp32 slabs of the split-K form (below the tiled GEMM's sizes: 8 < M, and
+    // M <= 8 where K is past the GEMV's register budget -- 3 .. 8 rows of K = 11008 run split-K too);
     // N = 0: the activation part only (llmie_linear_fp8_swiglu)
-    return fp8_act_bytes(M, K) + (N > 0 && M > 8 ? fp8_align(linear_splitk_ws_floats(WF_FP8, M, K, N) * sizeof(float)) : 0);
+    const bool splitk = M > 8 || !ksplit_eligible(M, K, 8);
+    return fp8_act_bytes(M, K) + (N > 0 && splitk ? fp8_align(linear_splitk_ws_floats(WF_FP8, M, K, N) * sizeof(float)) : 0);
 }
 
 extern "C" int llmie_quantize_fp8(const void *w, uint8_t *wq, float *scale, int N, int K, llmie_stream stream) {
