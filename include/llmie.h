@@ -65,7 +65,8 @@ typedef enum {
     LLMIE_W_INT8 = 1,    /* int8 [N,K] + fp16 per-row scale                      */
     LLMIE_W_INT4 = 2,    /* packed int4 [N,K/2] + fp16 scale per (row, group)    */
     LLMIE_W_FP8 = 3,     /* e4m3 [N,K] + fp32 per-row scale                      */
-    LLMIE_W_F32 = 4      /* fp32 weights (dtype LLMIE_F32 engines only)          */
+    LLMIE_W_F32 = 4,     /* fp32 weights (dtype LLMIE_F32 engines only)          */
+    LLMIE_W_MXFP4 = 5    /* OCP MXFP4: packed e2m1 [N,K/2] + e8m0 scale byte per (row, 32 k) */
 } llmie_weight_format;
 
 int llmie_abi_version(void);
@@ -433,6 +434,49 @@ int llmie_quantize_w8(const void *w, int8_t *wq, void *scale, int N, int K, llmi
 int llmie_quantize_w4(const void *w, uint8_t *wq, void *scale, int N, int K, int group,
                       llmie_stream stream);
 int llmie_quantize_fp8(const void *w, uint8_t *wq, float *scale, int N, int K, llmie_stream stream);
+
+/* MXFP4 weights (OCP microscaling, an addition within ABI 3; no reference counterpart).  LLMIE_W_MXFP4 = 5.  A matrix W[N, K] with
+ * K % 32 == 0 is stored as two arrays:
+ *   wq     uint8 [N, K/2], two e2m1 codes per byte, low nibble = even k (the int4 entries' packing).  Bit 3 of a code is the sign,
+ *          bits 2..0 index the magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}; code 0x8 is -0.
+ *   scale  uint8 [N, K/32], row-major, e8m0: block (n, k/32) has exponent e = byte - 127 and w[n, k] = magnitude * 2^e with the
+ *          code's sign.  Byte 0xFF is NaN.  (This array is what llmie_matrix.scale would carry.)
+ * Pinned range: for e in [-23, 13] every weight is exactly an fp16 number (subnormals included, 6 * 2^13 = 49152), and inside that
+ * range every route of llmie_linear_mxfp4 agrees on the weight to the bit.  Outside it, or with a 0xFF block, llmie_linear_mxfp4
+ * returns unspecified values for the affected columns; it stays in bounds and terminates.
+ *
+ * llmie_quantize_mxfp4: w fp16 [N, K] -> codes + scales.  Per block of 32 with amax = max |w|: a non-finite element gives scale
+ * byte 0xFF (the block's codes are then unspecified); amax == 0 gives byte 127 and all-zero magnitudes; otherwise
+ * e = clamp(floor(log2(amax)) - 2, -23, 13) (the OCP rule with emax(e2m1) = 2; the lower clamp departs from OCP on purpose: fp16
+ * inputs reach e = -26, where codes would stop being fp16 numbers, and with the clamp such a block lands losslessly on the fp16
+ * subnormal grid).  Each element is w / 2^e rounded to the nearest magnitude, ties to the even code (0.25 -> 0, 0.75 -> 1,
+ * 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at 6.  The sign bit is the sign bit of w, also for a zero result.
+ * K % 32 != 0 or w not 16-byte aligned: LLMIE_ERR_UNSUPPORTED.
+ * llmie_dequantize_mxfp4: w16[n, k] = the round-to-nearest-even fp16 of the exact value (exact in the pinned range; outside it
+ * overflow to +-inf and underflow through the subnormals; a 0xFF block gives fp16 NaN 0x7E00; -0 stays -0).  K % 32 != 0 or w16 not
+ * 16-byte / wq not 4-byte aligned: LLMIE_ERR_UNSUPPORTED.
+ * llmie_linear_mxfp4: weight-only, y[m, n] = fp16(sum_k float(x[m, k]) * w[n, k] (+ bias[n]) (+ residual[m, n])); x, y, bias,
+ * residual fp16, residual may alias y; fp32 accumulation, a block's 2^e applied to the block's fp32 partial sum; no float atomics:
+ * same inputs, same bits.  Routes (llmie_linear_route(LLMIE_W_MXFP4, ...) names them): M <= 8 "mxfp4_gemv" (one pass over the
+ * weights for all rows); 8 < M <= 64 "mxfp4_mfma" (codes expanded to unscaled fp16 fragments, one v_mfma_f32_16x16x32_f16 per block
+ * into a zeroed tile, the tile scaled per lane and added to the accumulator; K split over the waves of a workgroup and reduced in a
+ * fixed order); 64 < M < 192 "mxfp4_chunks" (passes of <= 64 rows through that kernel); M >= 192 "image_prefill+<fp16 route>"
+ * (llmie_dequantize_mxfp4 into the workspace, then the fp16 GEMM), or "mxfp4_chunks" without a workspace that holds the image.
+ * workspace: llmie_linear_workspace_bytes(LLMIE_W_MXFP4, M, K, N) bytes, 16-byte aligned (the fp16 image from 192 rows; 0 below).
+ * No route NEEDS one, so the entry never returns LLMIE_ERR_WORKSPACE: from 192 rows a NULL or short workspace is not an error, the
+ * call runs as "mxfp4_chunks" -- the slower route there, without a signal to the caller; llmie_linear_route tells which one runs.
+ * K % 32 != 0, or x / wq not 16-byte aligned: LLMIE_ERR_UNSUPPORTED.  Scale rows carry no alignment beyond one byte.
+ * Engine format: llmie_decoder_config.wfmt = LLMIE_W_MXFP4 (fp16 activations; int4_group ignored; llmie_matrix.scale = the e8m0
+ * array; hidden size and inter_size multiples of 32).  Every decode batch runs the "unfused" sequence on the routes above (SwiGLU as
+ * projection + llmie_silu_and_mul), dense, paged, ragged or e4m3 caches where the attention geometry has the fused kernel; a
+ * hidden_out that is not 16-byte aligned is LLMIE_ERR_UNSUPPORTED.  Prefill runs the "general" sequence at every row count (in-place
+ * norms, the plain QKV projection with the RoPE + append launch, gate/up as two launches).  Refused with LLMIE_ERR_UNSUPPORTED:
+ * LLMIE_DEC_PACKED_ONLY (no packed image is built), llmie_decoder_lora_attach, and an MXFP4 LM head (lm_fmt) in the
+ * llmie_lm_head_sample* entries. */
+int llmie_quantize_mxfp4(const void *w, uint8_t *wq, uint8_t *scale, int N, int K, llmie_stream stream);
+int llmie_dequantize_mxfp4(const uint8_t *wq, const uint8_t *scale, void *w16, int N, int K, llmie_stream stream);
+int llmie_linear_mxfp4(const void *x, const uint8_t *wq, const uint8_t *scale, void *y, int M, int K, int N, const void *bias,
+                       const void *residual, void *workspace, size_t workspace_bytes, llmie_stream stream);
 
 /* Tile-packed weight images for decode batches (no reference counterpart: the reference streams row-major weights through
  * cuBLAS, src/kernels/linear.cu:10-87).  An MFMA operand wants 16 different weight rows across the lanes of one load, a

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libllmie.so")
 
 F32, F16 = 0, 1
 W_F16, W_INT8, W_INT4, W_FP8, W_F32 = 0, 1, 2, 3, 4
+W_MXFP4 = 5   # e2m1 codes [N, K/2] + e8m0 scale bytes [N, K/32]: linear_mxfp4 and an engine format (Decoder, wfmt=W_MXFP4)
 KV_NATIVE, KV_FP8 = 0, 1
 DEC_NO_PACKED_COPY, DEC_PACKED_ONLY = 1, 2
 ABI_VERSION = 3  # LLMIE_ABI_VERSION of include/llmie.h this binding mirrors
@@ -81,6 +82,9 @@ _SIGS = {
     "llmie_quantize_w8": [_vp, _vp, _vp, _i, _i, _vp],
     "llmie_quantize_w4": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "llmie_quantize_fp8": [_vp, _vp, _vp, _i, _i, _vp],
+    "llmie_quantize_mxfp4": [_vp, _vp, _vp, _i, _i, _vp],
+    "llmie_dequantize_mxfp4": [_vp, _vp, _vp, _i, _i, _vp],
+    "llmie_linear_mxfp4": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "llmie_decoder_workspace_bytes": [_vp],
     "llmie_decoder_create": [_vp, _vp, _vp, _sz],
     "llmie_decoder_destroy": [_vp],
@@ -299,6 +303,12 @@ def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):
     c = cfg if isinstance(cfg, DecoderConfig) else DecoderConfig(**cfg)
     r = lib().llmie_decoder_plan_name(C.byref(c), int(bool(prefill)), rows, call_flags, switch_mask)
     return r.decode() if r is not None else None
+
+
+def decoder_resident_weight_bytes(cfg):
+    """bytes of layer-matrix storage (row-major matrices, scales and packed images) an engine of `cfg` keeps resident"""
+    c = cfg if isinstance(cfg, DecoderConfig) else DecoderConfig(**cfg)
+    return lib().llmie_decoder_resident_weight_bytes(C.byref(c))
 
 
 def decoder_prefill_layer_plan(cfg, tokens, batch=1, max_q_len=None, call_flags=0, switch_mask=0):
@@ -880,6 +890,7 @@ LORA_RANKS = (8, 16, 32, 64)
 LORA_MAX_SLOTS = 1024   # LLMIE_LORA_MAX_SLOTS
 LORA_MAX_KSPLIT = 8     # LLMIE_LORA_MAX_KSPLIT
 PLAN_LORA = 1024        # LLMIE_PLAN_LORA
+PLAN_PAGED, PLAN_RAGGED, PLAN_HIDDEN_MISALIGNED = 1, 2, 4   # LLMIE_PLAN_* call flags of decoder_plan_name
 
 
 class LoraLayer(C.Structure):
@@ -999,6 +1010,26 @@ def linear_w4a16(x, wq, scale, y, group, bias=None, residual=None, workspace="au
     wp, wb = _ws_args(workspace, W_INT4, x.shape[0], x.shape[1], wq.shape[0], x.device)
     _check(lib().llmie_linear_w4a16(_p(x), _p(wq), _p(scale), _p(y), x.shape[0], x.shape[1], wq.shape[0], group,
                                     _p(bias), _p(residual), wp, wb, _st()), "linear_w4a16")
+    return y
+
+
+def quantize_mxfp4(w, wq, scale):
+    """w fp16 [N, K], K % 32 == 0 -> wq uint8 [N, K/2] (e2m1, low nibble = even k) + scale uint8 [N, K/32] (e8m0)"""
+    _check(lib().llmie_quantize_mxfp4(_p(w), _p(wq), _p(scale), w.shape[0], w.shape[1], _st()), "quantize_mxfp4")
+
+
+def dequantize_mxfp4(wq, scale, w16):
+    """the fp16 image of MXFP4 weights: exact for block exponents in [-23, 13]"""
+    _check(lib().llmie_dequantize_mxfp4(_p(wq), _p(scale), _p(w16), w16.shape[0], w16.shape[1], _st()), "dequantize_mxfp4")
+    return w16
+
+
+def linear_mxfp4(x, wq, scale, y, bias=None, residual=None, workspace="auto"):
+    """workspace: a device tensor of linear_workspace_bytes(W_MXFP4, M, K, N) bytes (the fp16 image of the matrix from 192 rows on),
+    None (such row counts then run as passes of 64 rows), or the string auto"""
+    wp, wb = _ws_args(workspace, W_MXFP4, x.shape[0], x.shape[1], wq.shape[0], x.device)
+    _check(lib().llmie_linear_mxfp4(_p(x), _p(wq), _p(scale), _p(y), x.shape[0], x.shape[1], wq.shape[0], _p(bias),
+                                    _p(residual), wp, wb, _st()), "linear_mxfp4")
     return y
 
 

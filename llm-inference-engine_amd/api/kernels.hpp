@@ -355,3 +355,21 @@ void launchLoraApply(TensorWrapper<T> *x, TensorWrapper<T> *y, TensorWrapper<int
     LLMIE_CALL(llmie_lora_apply(x->data, y->data, rows, K, N, blocks, block_widths.data(), table, slots, layers, layer, module, scratch, ws,
                                 llmie_api::dtype_of<T>(), llmie_api::st()));
 }
+
+// No reference launchers: MXFP4 weights (include/llmie.h has the format).  w [N, K] fp16 <-> wq: device bytes [N, K/2] (e2m1 codes, low
+// nibble = even k) + scale: device bytes [N, K/32] (e8m0); the linear is weight-only under fp16 activations, y [M, N] = x [M, K] . W^T
+// (+ bias [N]) (+ residual [M, N], may be y).  From 192 rows the fp16 image of the matrix goes through the adaptors' scratch.
+inline void launchQuantizeMxfp4(TensorWrapper<half> *w, uint8_t *wq, uint8_t *scale) {
+    LLMIE_CALL(llmie_quantize_mxfp4(w->data, wq, scale, w->shape[0], w->shape[1], llmie_api::st()));
+}
+inline void launchDequantizeMxfp4(const uint8_t *wq, const uint8_t *scale, TensorWrapper<half> *w16) {
+    LLMIE_CALL(llmie_dequantize_mxfp4(wq, scale, w16->data, w16->shape[0], w16->shape[1], llmie_api::st()));
+}
+inline void launchLinearMxfp4(TensorWrapper<half> *x, const uint8_t *wq, const uint8_t *scale, TensorWrapper<half> *y,
+                              TensorWrapper<half> *bias = nullptr, TensorWrapper<half> *residual = nullptr) {
+    const int M = x->shape[0], K = x->shape[1], N = y->shape[1];
+    LLM_CHECK_WITH_INFO(y->shape[0] == M, "x and y should have the same rows");
+    const size_t ws = llmie_linear_workspace_bytes(LLMIE_W_MXFP4, M, K, N);
+    LLMIE_CALL(llmie_linear_mxfp4(x->data, wq, scale, y->data, M, K, N, bias ? bias->data : nullptr, residual ? residual->data : nullptr,
+                                  ws ? llmie_api::scratch(ws) : nullptr, ws, llmie_api::st()));
+}

@@ -103,6 +103,8 @@ static bool config_ok(const llmie_decoder_config *c) {
     if (c->dtype != LLMIE_F32 && c->dtype != LLMIE_F16) return false;
     if (c->dtype == LLMIE_F32 && c->wfmt != LLMIE_W_F32) return false;
     if (c->dtype == LLMIE_F16 && c->wfmt == LLMIE_W_F32) return false;
+    // MXFP4: blocks of 32 along K of every projection (K = hidden size or inter_size)
+    if (c->wfmt == LLMIE_W_MXFP4 && ((c->head_num * c->head_size) % 32 || c->inter_size % 32)) return false;
     if (c->kv_fmt != LLMIE_KV_NATIVE && c->kv_fmt != LLMIE_KV_FP8) return false;
     if (c->flags & ~(LLMIE_DEC_NO_PACKED_COPY | LLMIE_DEC_PACKED_ONLY)) return false;
     if ((c->flags & LLMIE_DEC_NO_PACKED_COPY) && (c->flags & LLMIE_DEC_PACKED_ONLY)) return false;
@@ -165,6 +167,11 @@ static int packed_wf(const llmie_decoder_config *c) {
         return 0;
     return wf;
 }
+// why a LLMIE_DEC_PACKED_ONLY config without a packed format is refused (create and the two plan queries)
+static const char *packed_only_refusal(const llmie_decoder_config *c) {
+    return c->wfmt == LLMIE_W_MXFP4 ? "decoder_create: LLMIE_DEC_PACKED_ONLY is not available for MXFP4 weights (no packed image is built)"
+                                    : "decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take";
+}
 struct PackedCarve {
     size_t per_layer[4], layer_bytes, hx, actx, mhax, slab, sync, total;
 };
@@ -200,6 +207,7 @@ static size_t engine_slab_floats(const llmie_decoder_config *c, int rows) {
         case LLMIE_W_INT8: wbits = 8; break;
         case LLMIE_W_INT4: wbits = 4; break;
         case LLMIE_W_FP8: wbits = WF_FP8; break;
+        case LLMIE_W_MXFP4: wbits = 0; break;   // no MXFP4 route takes slabs; the LM head (another format) below may
         default: return 0;
     }
     if (c->dtype != LLMIE_F16) return 0;
@@ -210,7 +218,7 @@ static size_t engine_slab_floats(const llmie_decoder_config *c, int rows) {
     // format than the layers (fp16 beside int8 / fp8 layers): all formats for that shape
     const int lm_bits[4] = {16, 8, 4, WF_FP8};
     for (int r = 1; r <= rows; ++r) {
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4 && wbits; ++i) {
             const size_t f = linear_splitk_ws_floats(wbits, r, shapes[i][0], shapes[i][1]);
             m = f > m ? f : m;
         }
@@ -310,6 +318,7 @@ extern "C" size_t llmie_decoder_resident_weight_bytes(const llmie_decoder_config
         case LLMIE_W_INT8: row_major = elems; scales = rows * 2; break;
         case LLMIE_W_FP8: row_major = elems; scales = rows * 4; break;
         case LLMIE_W_INT4: row_major = elems / 2; scales = (elems / (cfg->int4_group > 0 ? cfg->int4_group : 128)) * 2; break;
+        case LLMIE_W_MXFP4: row_major = elems / 2; scales = elems / 32; break;   // N K / 2 codes + N K / 32 e8m0 bytes per matrix
         default: return 0;
     }
     const int wf = packed_wf(cfg);
@@ -382,7 +391,7 @@ extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, 
     if (!d->slab_ws.floats) d->slab_ws.p = nullptr;
     d->pk_wf = packed_wf(cfg);
     if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !d->pk_wf) {
-        set_error("decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take");
+        set_error("%s", packed_only_refusal(cfg));
         delete d;
         return nullptr;
     }
@@ -551,6 +560,18 @@ static int engine_linear(const llmie_decoder *d, llmie_weight_format fmt, const 
             return linear_fp8((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, M, K, N,
                               (const half_t *)bias, (const half_t *)residual, d->fp8_ws, d->fp8_ws_bytes, d->slab_ws, as_stream(stream));
         }
+        case LLMIE_W_MXFP4: {
+            // plain epilogue only: SwiGLU as projection + llmie_silu_and_mul; no image area in the decode workspace (from
+            // kWqPrefillRows rows: passes of 64 rows)
+            if (swiglu) {
+                int rc = linear_mxfp4((const half_t *)x, (const uint8_t *)w.data, (const uint8_t *)w.scale, (half_t *)d->gu, M, K, N,
+                                      (const half_t *)bias, nullptr, nullptr, 0, as_stream(stream));
+                if (rc) return rc;
+                return llmie_silu_and_mul(d->gu, y, M, N / 2, LLMIE_F16, stream);
+            }
+            return linear_mxfp4((const half_t *)x, (const uint8_t *)w.data, (const uint8_t *)w.scale, (half_t *)y, M, K, N,
+                                (const half_t *)bias, (const half_t *)residual, nullptr, 0, as_stream(stream));
+        }
         default:
             set_error("engine: weight format %d not supported by this build", (int)fmt);
             return LLMIE_ERR_UNSUPPORTED;
@@ -580,7 +601,7 @@ static bool fused_attention_geometry(const llmie_decoder_config &c) {
 }
 
 enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED, DP_LORA };
-enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED, DREF_LORA };
+enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED, DREF_LORA, DREF_MX4_HIDDEN };
 // One decode call as the planner sees it.  mis_hidden / mis_wqkv0: address % 16 of the hidden state and of layer 0's QKV matrix.
 struct DecodeCall {
     llmie_decoder_config cfg;
@@ -594,7 +615,8 @@ struct DecodeCall {
 // weights, not a packed-only engine), K % 32 == 0 and column blocks (q / k / v, gate / up) that are multiples of 16
 static bool lora_engine_ok(const llmie_decoder_config &c) {
     const int H = c.head_num * c.head_size;
-    return c.dtype == LLMIE_F16 && c.wfmt != LLMIE_W_FP8 && c.wfmt != LLMIE_W_F32 && !(c.flags & LLMIE_DEC_PACKED_ONLY) && H % 32 == 0 &&
+    return c.dtype == LLMIE_F16 && c.wfmt != LLMIE_W_FP8 && c.wfmt != LLMIE_W_F32 && c.wfmt != LLMIE_W_MXFP4 &&
+           !(c.flags & LLMIE_DEC_PACKED_ONLY) && H % 32 == 0 &&
            c.inter_size % 32 == 0 && (c.kv_head_num * c.head_size) % 16 == 0;
 }
 static const char *const kLoraRefusal =
@@ -627,6 +649,16 @@ static DecodePlan plan_decode(const DecodeCall &d) {
         if (!attn_ok && d.ragged) return {DP_REFUSED, DREF_RAGGED, false};
         return {DP_LORA, DREF_NONE, false};
     }
+    if (c.wfmt == LLMIE_W_MXFP4) {
+        // every batch runs the unfused sequence (the fused-norm and SwiGLU forms of the GEMV are not built for the format); its
+        // attention launch carries paged / e4m3 caches and ragged lengths where the geometry has the fused kernel, as the lora one's
+        if (packed_only) return {DP_REFUSED, DREF_PACKED_ONLY, false};
+        if (d.mis_hidden) return {DP_REFUSED, DREF_MX4_HIDDEN, false};
+        if (!attn_ok && d.paged) return {DP_REFUSED, DREF_PAGED, false};
+        if (!attn_ok && c.kv_fmt == LLMIE_KV_FP8) return {DP_REFUSED, DREF_KV_FP8, false};
+        if (!attn_ok && d.ragged) return {DP_REFUSED, DREF_RAGGED, false};
+        return {DP_UNFUSED, DREF_NONE, false};
+    }
     const bool int4_ok = wbits == 4 && c.int4_group == 128 && batch <= 64;  // int4 MFMA form: group-128 scales, 64 rows per pass
     const bool batch_path_ok = !d.sw.no_fused_batch && c.dtype == LLMIE_F16 && (wbits == 16 || wbits == 8 || int4_ok || fp8) && attn_ok &&
                                batch <= 128 && H % 256 == 0 && I % 256 == 0 && H >= 512 && I >= 512 && splitk_rownorm_eligible(H);
@@ -653,6 +685,7 @@ static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
                       packed_rows_max(d.cfg));
             break;
         case DREF_LORA: set_error("decoder_forward: %s", kLoraRefusal); break;
+        case DREF_MX4_HIDDEN: set_error("decoder_forward: MXFP4 weights need a 16-byte aligned hidden_out"); break;
         case DREF_PAGED: set_error("decoder_forward_paged: the paged KV cache needs the fused decode paths (fp16 engines, batch <= 128)"); break;
         case DREF_KV_FP8:
             set_error("decoder_forward: the fp8 KV cache needs the fused decode paths (batch <= 128, fp16/int8/int4/fp8 weights with "
@@ -689,8 +722,12 @@ static PrefillPlan plan_prefill(const PrefillCall &p) {
     const int T = p.T, H = c.head_num * c.head_size, I = c.inter_size;
     const bool fp8 = c.wfmt == LLMIE_W_FP8;
     const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
-    if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits) || c.head_size != 128) return {PP_REFUSED, PREF_FORMAT};
+    const bool mx4 = c.wfmt == LLMIE_W_MXFP4;
+    if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits && !mx4) || c.head_size != 128) return {PP_REFUSED, PREF_FORMAT};
     if (p.lora) return lora_engine_ok(c) ? PrefillPlan{PP_LORA, PREF_NONE} : PrefillPlan{PP_REFUSED, PREF_LORA};
+    // MXFP4: the general sequence at every row count (llmie_linear_mxfp4 picks the projection's route by the rows; no packed image)
+    // (a LLMIE_DEC_PACKED_ONLY config never gets here: creating the engine refuses it)
+    if (mx4) return {PP_GENERAL, PREF_NONE};
     if (c.flags & LLMIE_DEC_PACKED_ONLY) return fp8 ? PrefillPlan{PP_REFUSED, PREF_PACKED_ONLY_FP8} : PrefillPlan{PP_PACKED_ONLY, PREF_NONE};
     const bool short_fmt_ok = !fp8 && (wqbits != 4 || (c.int4_group == 128 && T <= 64));   // int4 split-K form: 64 rows, group 128
     if (!p.sw.no_fused_short_prefill && short_fmt_ok && p.weights_a16 && (wqbits != 4 || p.int4_scales_a4) && T <= 128 && H % 256 == 0 &&
@@ -739,7 +776,7 @@ struct PrefillLayerPlan {
 // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
 // this holds writes the epilogue's token table once, whatever its layers end up choosing.)
 static bool prefill_rope_fusable(const PrefillCall &p) {
-    return !p.lora && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+    return !p.lora && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
 }
 static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
     const llmie_decoder_config &c = p.cfg;
@@ -761,9 +798,10 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         const SplitKSlabs sk{slabs.p, 1, T, QKV};
         o.qkv = !p.sw.no_qkv_rope_fusion && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
         o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
-    } else if (path == PP_LORA) {
+    } else if (path == PP_LORA || c.wfmt == LLMIE_W_MXFP4) {
         // the general sequence with the forms the adapter updates need: normalised rows in place, the QKV buffer un-rotated (the update
-        // lands before RoPE: the RoPE + append launch runs in front of the flash kernel), gate/up un-activated
+        // lands before RoPE: the RoPE + append launch runs in front of the flash kernel), gate/up un-activated.  MXFP4 weights run the
+        // same forms: their projections have the plain epilogue only
         o.attn_norm = o.ffn_norm = PN_INPLACE, o.qkv = PQ_PLAIN, o.gate_up = PG_TWO_LAUNCH;
     } else if (path == PP_PACKED_ONLY) {
         // every projection runs the fp16 GEMM on the unpacked image of its matrix: the fp16 forms, on the de-quantisation area
@@ -831,7 +869,7 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
         return nullptr;
     }
     if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !packed_wf(cfg)) {
-        set_error("decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take");
+        set_error("%s", packed_only_refusal(cfg));
         return nullptr;
     }
     const EngineSwitches sw = switches_of_mask(switch_mask);
@@ -1280,7 +1318,7 @@ static PrefillCarve prefill_carve(const llmie_decoder_config *c, int T, int B) {
     // int8 / int4 / packed-only engines: room for the fp16 image of the largest matrix, at every T -- at least the image_bytes of any
     // plan (plan_linear_wq's image routes; packed-only engines unpack every matrix), and more where the plan needs none: kept
     size_t dq = 0;
-    if (c->wfmt == LLMIE_W_INT8 || c->wfmt == LLMIE_W_INT4 || (c->flags & LLMIE_DEC_PACKED_ONLY)) {
+    if (c->wfmt == LLMIE_W_INT8 || c->wfmt == LLMIE_W_INT4 || c->wfmt == LLMIE_W_MXFP4 || (c->flags & LLMIE_DEC_PACKED_ONLY)) {
         const size_t shapes[4][2] = {{H, QKV}, {H, H}, {H, 2 * I}, {I, H}};
         for (const auto &sh : shapes) {
             const size_t b = sh[0] * sh[1] * sizeof(half_t);
@@ -1337,6 +1375,8 @@ struct PrefillPass {
     float *xsn() const { return reinterpret_cast<float *>(xqn() + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255))); }
     // y = x . W^T (+ residual) in the engine's weight format (fp8: per-token e4m3 activations, fp8 MFMA)
     int proj(const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual) const {
+        if (c.wfmt == LLMIE_W_MXFP4)   // (from kWqPrefillRows rows: the fp16 image of the matrix in `deq` + the fp16 GEMM)
+            return linear_mxfp4(x, (const uint8_t *)w.data, (const uint8_t *)w.scale, y, T, K, N, nullptr, residual, deq, deq_bytes, st);
         if (wqbits)
             return linear_wq(wqbits, x, w.data, (const half_t *)w.scale, y, T, K, N, c.int4_group, EPI_NONE_, nullptr, residual, nullptr,
                              nullptr, 0.f, slabs, st, deq, deq_bytes);
@@ -1696,7 +1736,7 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
     const int rc = [&]() -> int {
         LLMIE_REQUIRE(config_ok(cfg), "decoder_prefill_layer_plan: invalid config");
         if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !packed_wf(cfg))
-            LLMIE_UNSUPPORTED("decoder_create: LLMIE_DEC_PACKED_ONLY needs max_batch <= 32 (fp8: 16) and shapes / a format the packed kernels take");
+            LLMIE_UNSUPPORTED("%s", packed_only_refusal(cfg));
         if (int bad = prefill_shape_ok(*cfg, batch, tokens, max_q_len)) return bad;
         const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
         const PrefillPlan plan = plan_prefill(call);
@@ -1750,6 +1790,7 @@ static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *fin
     const llmie_decoder_config &c = dec->cfg;
     LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "lm_head_sample: batch %d outside [1,%d]", batch, c.max_batch);
     LLMIE_REQUIRE(c.vocab_size > 0, "lm_head_sample: vocab_size not set in the decoder config");
+    if (lm_fmt == LLMIE_W_MXFP4) LLMIE_UNSUPPORTED("lm_head_sample: an MXFP4 LM head is not supported (fp16 / int8 / int4 / fp8 heads; a follow-up)");
     int rc;
     if (lm_fmt == LLMIE_W_F16 && c.dtype == LLMIE_F16 && gemv_f16_eligible(batch, dec->H, hidden, lm_head->data) &&
         !engine_switches().no_fused_decode) {

@@ -896,7 +896,25 @@ static LinearPlan planned_image(const LinearCall &c, int route) {
     return p;
 }
 
+// MXFP4 weights (mxfp4_linear.hip): e2m1 codes [N, K/2] + one e8m0 byte per 32 k.  Plain epilogue only; no route needs slabs (the
+// MFMA kernel splits K over the waves of a workgroup), the image route needs room for the whole fp16 matrix.
+static LinearPlan plan_linear_mxfp4(const LinearCall &c) {
+    const int M = c.M;
+    if (c.K % 32 != 0 || (c.mis_x | c.mis_w) != 0) return refused(LREF_MX4_SHAPE);
+    if (c.epi != EPI_NONE || c.gamma || c.pre_bias) return refused(LREF_MX4_EPI);
+    if (M <= kMx4GemvRows) return planned(LR_MX4_GEMV);
+    if (M <= kMx4MfmaRows) return planned(LR_MX4_MFMA);
+    if (M >= kWqPrefillRows && c.image && c.mis_image == 0 && c.image_bytes >= static_cast<size_t>(c.N) * c.K * sizeof(half_t)) {
+        const LinearPlan p = planned_image(c, LR_WQ_IMAGE_PREFILL);
+        if (p.route != LR_REFUSED) return p;
+    }
+    LinearPlan p = planned(LR_MX4_CHUNKS);
+    p.pass_rows = kMx4MfmaRows;
+    return p;
+}
+
 LinearPlan plan_linear_wq(const LinearCall &c) {
+    if (c.bits == WF_MXFP4) return plan_linear_mxfp4(c);
     const int bits = c.bits, M = c.M, K = c.K, N = c.N;
     const bool swiglu = c.epi == EPI_SWIGLU, plain = c.epi == EPI_NONE;
     const bool aligned = (c.mis_x | c.mis_w | c.mis_gamma | c.mis_pre_bias) == 0 && (static_cast<size_t>(K) * bits / 8) % 16 == 0;
@@ -961,6 +979,7 @@ LinearPlan plan_linear_wq(const LinearCall &c) {
 // one workspace across shapes.  Below: int8 reserves what the plan needs (the last-resort image of shapes no int8 kernel takes);
 // int4 has never reserved any there.
 size_t linear_wq_dequant_bytes(int wbits, int M, int K, int N) {
+    if (wbits == WF_MXFP4) return K % 32 == 0 && M >= kWqPrefillRows ? static_cast<size_t>(N) * K * sizeof(half_t) : 0;
     if ((wbits != 8 && wbits != 4) || K % 8 != 0) return 0;
     if (M >= kWqPrefillRows) return static_cast<size_t>(N) * K * sizeof(half_t);
     return wbits == 8 ? plan_linear_wq(linear_call_sizing(8, M, K, N, EPI_NONE)).image_bytes : 0;
@@ -977,7 +996,8 @@ WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t
 const char *linear_route_name(int route) {
     static const char *const names[] = {"refused", "gemv_ksplit", "gemv_lds", "splitk", "splitk_passes", "skinny", "swiglu256", "tiles256",
                                         "tiles256_part", "tiles128", "generic", "g8p", "g8p_swiglu", "int8_splitk_passes", "image_prefill",
-                                        "image_last", "gemv_ksplit", "int4_splitk", "int4_chunks", "int8_splitk", "int8_skinny"};
+                                        "image_last", "gemv_ksplit", "int4_splitk", "int4_chunks", "int8_splitk", "int8_skinny", "mxfp4_gemv",
+                                        "mxfp4_mfma", "mxfp4_chunks"};
     return names[route];
 }
 
@@ -999,6 +1019,12 @@ int linear_refuse(const LinearCall &c, const LinearPlan &p) {
             return LLMIE_ERR_UNSUPPORTED;
         case LREF_WQ_SWIGLU:
             set_error("linear_wq: fused SwiGLU needs the GEMV or split-K path (M=%d K=%d bits=%d)", M, K, c.bits);
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_MX4_SHAPE:
+            set_error("linear_mxfp4: needs K %% 32 == 0 and 16-byte aligned x and wq (M=%d K=%d N=%d)", M, K, N);
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_MX4_EPI:
+            set_error("linear_mxfp4: plain epilogue (bias, residual) only: no fused norm or SwiGLU form (M=%d K=%d N=%d)", M, K, N);
             return LLMIE_ERR_UNSUPPORTED;
         default:
             set_error("linear_wq: unsupported shape M=%d K=%d N=%d bits=%d without a split-K workspace (int8: M<=64, K%%64==0; int4: "
@@ -1065,6 +1091,8 @@ extern "C" size_t llmie_linear_workspace_bytes(llmie_weight_format fmt, int M, i
             const size_t dq = (linear_wq_dequant_bytes(wbits, M, K, N) + 255) & ~static_cast<size_t>(255);
             return dq + linear_splitk_ws_floats(wbits, M, K, N) * sizeof(float);
         }
+        // MXFP4: the fp16 image from kWqPrefillRows rows on; no route takes slabs
+        case LLMIE_W_MXFP4: return (linear_wq_dequant_bytes(WF_MXFP4, M, K, N) + 255) & ~static_cast<size_t>(255);
         default: return 0;
     }
 }
@@ -1112,14 +1140,14 @@ extern "C" int llmie_linear_swiglu(const void *x, const void *w, void *y, int M,
 extern "C" const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const void *w, const void *scale, const void *y, int M,
                                           int K, int N, int swiglu, int group, const void *bias, const void *residual,
                                           const void *workspace, size_t workspace_bytes) {
-    const int bits = fmt == LLMIE_W_F16 ? 16 : (fmt == LLMIE_W_INT8 ? 8 : (fmt == LLMIE_W_INT4 ? 4 : 0));
+    const int bits = fmt == LLMIE_W_F16 ? 16 : (fmt == LLMIE_W_INT8 ? 8 : (fmt == LLMIE_W_INT4 ? 4 : (fmt == LLMIE_W_MXFP4 ? WF_MXFP4 : 0)));
     const int epi = swiglu ? EPI_SWIGLU : EPI_NONE;
     static thread_local char name[48];
     auto fail = [](const char *what) -> const char * {
         set_error("linear_route: %s", what);
         return nullptr;
     };
-    if (!bits) return fail("fp16, int8 and int4 weights only");
+    if (!bits) return fail("fp16, int8, int4 and MXFP4 weights only");
     if (!x || !w || !y || (bits != 16 && !scale)) return fail("NULL pointer");
     if (M <= 0 || K <= 0 || N <= 0 || (swiglu && (N % 2 || bias || residual))) return fail("bad shape or epilogue");
     if (bits == 4 && !(group > 0 && group % 32 == 0 && K % group == 0)) return fail("group must be a multiple of 32 dividing K");

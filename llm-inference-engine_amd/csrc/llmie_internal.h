@@ -25,8 +25,10 @@ enum LinearRoute : int {
     // int8 / int4 weights
     LR_W8_G8P, LR_W8_G8P_SWIGLU, LR_W8_SPLITK_PASSES, LR_WQ_IMAGE_PREFILL, LR_WQ_IMAGE_LAST, LR_WQ_GEMV, LR_W4_SPLITK, LR_W4_CHUNKS,
     LR_W8_SPLITK, LR_W8_SKINNY,
+    // MXFP4 weights (mxfp4_linear.hip)
+    LR_MX4_GEMV, LR_MX4_MFMA, LR_MX4_CHUNKS,
 };
-enum LinearRefusal : int { LREF_NONE = 0, LREF_F16_SWIGLU, LREF_SLABS, LREF_W4_SPLITK, LREF_WQ_NORM, LREF_WQ_SWIGLU, LREF_WQ_SHAPE };
+enum LinearRefusal : int { LREF_NONE = 0, LREF_F16_SWIGLU, LREF_SLABS, LREF_W4_SPLITK, LREF_WQ_NORM, LREF_WQ_SWIGLU, LREF_WQ_SHAPE, LREF_MX4_SHAPE, LREF_MX4_EPI };
 // One projection call as the planners see it: shape, epilogue, which operands are there and how far each pointer is from 16-byte
 // alignment (address % 16; 0 for a null pointer), and the caller's scratch.  bits = 16: fp16 weights (group / scale / image unused).
 struct LinearCall {
@@ -73,6 +75,7 @@ struct SplitKSlabs {
     int KS, M, N;
 };
 enum : int { WF_FP8 = 108 };  // wbits code of e4m3 weights + e4m3 activations (16 / 8 = fp16 / int8 weights, fp16 activations)
+enum : int { WF_MXFP4 = 204 }; // LinearCall::bits of MXFP4 weights (e2m1 codes + e8m0 block scales) under fp16 activations
 int linear_splitk_partial(int wbits, const void *x, const void *W, int M, int K, int N, hipStream_t st, SplitKSlabs *out,
                           SlabWs ws, const half_t *gscale = nullptr /* wbits 4: group-128 scales [N, K/128], applied in the kernel */);
 int splitk_finalize(const SplitKSlabs &sk, const SlabScale &sc, half_t *y, int epi, const half_t *bias, const half_t *residual,
@@ -138,6 +141,12 @@ struct WqWorkspace {
     SlabWs slabs;
 };
 WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t workspace_bytes);
+// MXFP4 weight-only linear (mxfp4_linear.hip): launches what plan_linear_wq plans for bits = WF_MXFP4.  image: room for the fp16
+// image of the matrix (the route from kWqPrefillRows rows), or null
+constexpr int kMx4GemvRows = 8, kMx4MfmaRows = 64;
+int dequantize_mxfp4_f16(const uint8_t *wq, const uint8_t *scale, half_t *w16, int N, int K, hipStream_t st);
+int linear_mxfp4(const half_t *x, const uint8_t *wq, const uint8_t *scale, half_t *y, int M, int K, int N, const half_t *bias,
+                 const half_t *residual, void *image, size_t image_bytes, hipStream_t st);
 // quantised-weight (int8 / int4) decode GEMV on the K-split kernel; defined in linear.hip
 struct GemvArgs;
 bool ksplit_eligible(int M, int K, int wbits);
