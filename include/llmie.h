@@ -45,7 +45,8 @@ extern "C" {
  *      llmie_score_tokens(_workspace_bytes); the decode attention's launch plan: llmie_decoder_mha_plan; masks, logit bias,
  *      stop sets and top-N log-probabilities in the sampler: llmie_sampling_ext, llmie_sample_logits_ext,
  *      llmie_lm_head_sample_ext; several hypotheses per request: llmie_beam_step(_workspace_bytes),
- *      llmie_kv_pages_fork(_workspace_bytes); speculative decoding: llmie_spec_verify(_workspace_bytes), llmie_ngram_draft). */
+ *      llmie_kv_pages_fork(_workspace_bytes); speculative decoding: llmie_spec_verify(_workspace_bytes), llmie_ngram_draft,
+ *      llmie_spec_verify_sampled(_workspace_bytes)). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -714,7 +715,8 @@ int llmie_kv_pages_fork(void *k_pool, void *v_pool, int32_t *block_table /* [row
 
 /* ABI 3 (an addition).  Speculative decoding behind the logits.  No reference launcher.  The forward over a chunk of k + 1
  * inputs per sequence is llmie_decoder_prefill(_paged) on top of the cached history; these two entries are what follows the
- * logits, and a drafter that needs no second model.  Rejection sampling against a full draft distribution is out of scope.
+ * logits, and a drafter that needs no second model.  (Rejection sampling against a sampled draft model: llmie_spec_verify_sampled,
+ * below.)
  *
  * llmie_spec_verify: EXACT-MATCH verification.  logits [batch * (k + 1), vocab]: row r = b * (k + 1) + i holds the logits that
  * follow input i of sequence b; input 0 is the last emitted token, input i >= 1 is draft_ids[b, i - 1].  s_b, the Philox step of
@@ -758,6 +760,64 @@ int llmie_spec_verify(const void *logits /* [batch*(k+1), vocab], row r = b*(k+1
                       int32_t *step_rows /* [batch], nullable, in/out */, int step, const int32_t *step_dev, int end_id,
                       void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream,
                       const llmie_sampling_ext *ext /* nullable */);
+
+/* ABI 3 (an addition).  llmie_spec_verify_sampled: REJECTION-SAMPLING verification against a drafter that SAMPLED its drafts (a
+ * small model at temperature > 0).  Exact match accepts such a draft with probability p(d); the rule below accepts with
+ * probability min(1, p(d) / q(d)) and, behind a rejection, draws from the residual max(0, p - q): the emitted tokens are
+ * distributed as plain sampling from the target, whatever the drafter's distribution.
+ * Operands are those of llmie_spec_verify, plus draft_logits [batch, k, vocab] (same dtype as logits; row (b, i) holds the draft
+ * model's logits from which draft i of sequence b was sampled), draft_params_dev [batch] (the controls the drafter sampled with)
+ * and out_accepted [batch] (may be NULL: the number of drafts among the emitted tokens).
+ * CALLER CONTRACT: the drafter sampled draft_ids[b, i] with llmie_sample_logits from draft_logits[b, i], draft_params_dev[b] and
+ * the history view of position i below (no extension).  Its seed should differ from params_dev[b].seed, or the drafter's draw and
+ * this entry's draws of lane 0 coincide.
+ * Position i of sequence b is row r = b * (k + 1) + i; its Philox step is s_b + i (s_b as in llmie_spec_verify) and its history is
+ * the spliced view of llmie_spec_verify: the stored history followed by draft_ids[b, 0..i) as far as i appends reach.
+ *   Target masses.  P_v is the sampler's fixed-point mass of token v in row r for params_dev[b] and ext: floor(expf(l_v - max) *
+ *   2^32) as a 64-bit integer over the tokens llmie_sample_logits_ext keeps (behind bias, mask, stops and min_step, penalties,
+ *   temperature, top-k, top-p, min-p), 0 for every other token; S_P = sum_v P_v.  A greedy row, or one with at most one valid token,
+ *   is the point mass P = S_P = 1 on the sampler's pick; a row without a valid token has P = 0 everywhere and S_P = 0.
+ *   Draft masses.  Q_v, S_Q: the same construction on draft_logits[b, i] with draft_params_dev[b], the same history view and no
+ *   extension -- the distribution llmie_sample_logits draws from.  A greedy draft is a point mass.
+ *   Draws.  U(lane) = (c0 >> 8) + 1 in [1, 2^24], c0 the first word of Philox4x32-10 with key (s_b + i, 0x4c4c4d49) on the counter
+ *   (params_dev[b].seed, lane, 0, 0).  Lane 0 is the sampler's own draw (u = U / 2^24), lane 1 the accept draw, lane 2 the residual
+ *   draw.
+ *   Accept.  With d = draft_ids[b, i], draft i is accepted iff 0 <= d < vocab and (U(1) - 1) * Q_d * S_P < 2^24 * P_d * S_Q, an
+ *   exact comparison of 128-bit integers (no division, no rounding): P_d / S_P >= Q_d / S_Q always accepts, P_d == 0 never does,
+ *   Q_d == 0 < P_d does.
+ *   Residual.  R_v = max(0, P_v * S_Q - Q_v * S_P), SR = sum_v R_v, thr = ((U(2) - 1) * SR) >> 24, all in 128-bit integers; the
+ *   residual token is the first id, ascending, at which the running sum of R exceeds thr.  If SR == 0 -- a point-mass or degenerate
+ *   input only, S_Q == 0 included; SR > 0 wherever a non-degenerate rejection is possible -- it is the sampler's own pick of the row.
+ * Emission walks i = 0, 1, ... with m = draft_len[b] clamped to [0, k] (NULL: k).  For i < m: if draft i is accepted emit it and
+ * go on, unless it finishes the sequence (end_id or one of the row's stop ids); otherwise emit the residual token and stop.  At
+ * i == m emit the sampler's own pick of row m (the lane-0 draw: the bonus token) and stop.  A position without a valid token is
+ * always rejected and emits end_id (finished), as the sampler does.  out_tokens, out_count, out_logprob (the raw log-softmax of the
+ * emitted token on the TARGET row), seq_len, finished, the history append, last_token, cached_len and step_rows follow count exactly
+ * as in llmie_spec_verify; a sequence finished on entry is left alone, and ext's top-N outputs are written for every row, as there.
+ * Guarantees: same inputs, same bits (integer sums, a scan in a fixed order, no float atomics); a sequence's outputs depend neither
+ * on its slot nor on the other sequences; with a greedy target the emitted tokens are those of plain greedy decoding whatever the
+ * drafter did; with draft_logits and draft_params_dev bit-equal to the target's rows and parameters and no ext, every draft is
+ * accepted (P == Q turns the comparison into U(1) - 1 < 2^24).
+ * Refused on the host before any launch: whatever llmie_spec_verify refuses, in its order, under this entry's name;
+ * LLMIE_ERR_INVALID_ARG: NULL draft_logits / draft_params_dev; LLMIE_ERR_UNSUPPORTED: vocab > 2^19 (S_P, S_Q < 2^51 keep both sides
+ * of the comparison below 2^107 and (U - 1) * SR inside 128 bits); LLMIE_ERR_WORKSPACE: NULL, short
+ * (llmie_spec_verify_sampled_workspace_bytes: two key rows per position; 0 for non-positive or unsupported sizes) or not 16-byte
+ * aligned.  Two launches (one 1024-thread workgroup per row prepares the target and the draft row, decides and leaves a fixed-size
+ * record; one pass per sequence walks the records).  No allocation, no synchronisation, legal inside a graph capture: every
+ * operand is read on the device. */
+size_t llmie_spec_verify_sampled_workspace_bytes(int batch, int k, int vocab);
+int llmie_spec_verify_sampled(const void *logits /* [batch*(k+1), vocab], row r = b*(k+1)+i */,
+                              const void *draft_logits /* [batch, k, vocab], dtype */, int batch, int k, int vocab,
+                              const int32_t *draft_ids /* [batch, k] */, const int32_t *draft_len /* [batch], NULL = k; clamped to [0,k] */,
+                              const llmie_sampling_params *params_dev /* [batch] */,
+                              const llmie_sampling_params *draft_params_dev /* [batch] */, int32_t *history, int history_stride,
+                              int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                              int32_t *out_tokens /* [batch, k+1] */, int32_t *out_count /* [batch] */,
+                              int32_t *out_accepted /* [batch], nullable */, float *out_logprob /* [batch,k+1], nullable */,
+                              int32_t *last_token /* [batch], nullable */, int32_t *cached_len /* [batch], nullable, in/out */,
+                              int32_t *step_rows /* [batch], nullable, in/out */, int step, const int32_t *step_dev, int end_id,
+                              void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream,
+                              const llmie_sampling_ext *ext /* nullable */);
 
 /* ABI 3 (an addition).  llmie_ngram_draft: prompt-lookup drafting.  tokens [batch, stride] holds each sequence's tokens so far
  * (prompt included), len [batch] their count; they may be the sampler's history / history_len when the caller put the prompt

@@ -120,6 +120,9 @@ _SIGS = {
     "llmie_spec_verify": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz,
                           _i, _vp, _vp],
     "llmie_ngram_draft": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "llmie_spec_verify_sampled_workspace_bytes": [_i, _i, _i],
+    "llmie_spec_verify_sampled": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                  _vp, _i, _vp, _sz, _i, _vp, _vp],
     "llmie_lora_table_bytes": [_i, _i],
     "llmie_lora_slot_load": [_vp, _i, _i, _i, _vp, _vp],
     "llmie_lora_workspace_bytes": [_i, _i, _i],
@@ -156,6 +159,7 @@ _RESTYPES = {
     "llmie_beam_step_workspace_bytes": _sz,
     "llmie_kv_pages_fork_workspace_bytes": _sz,
     "llmie_spec_verify_workspace_bytes": _sz,
+    "llmie_spec_verify_sampled_workspace_bytes": _sz,
     "llmie_lora_table_bytes": _sz,
     "llmie_lora_workspace_bytes": _sz,
     "llmie_decoder_lora_workspace_bytes": _sz,
@@ -1180,6 +1184,42 @@ def spec_verify(logits, draft_ids, params, seq_len, finished, end_id, state=None
                                    _p(st.last_token), _p(st.cached_len), _p(st.step_rows), step, _p(step_dev), end_id, _p(workspace),
                                    0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(logits), _st(),
                                    None if ext is None else _ext_ref(ext)), "spec_verify")
+    return tokens, count
+
+
+def spec_verify_sampled_workspace_bytes(batch, k, vocab):
+    return lib().llmie_spec_verify_sampled_workspace_bytes(batch, k, vocab)
+
+
+def spec_verify_sampled(logits, draft_logits, draft_ids, params, draft_params, seq_len, finished, end_id, state=None, draft_len=None,
+                        history=None, history_len=None, append=False, out_logprob=None, out_accepted=None, step=0, step_dev=None,
+                        workspace="auto", ext=None, out=None):
+    """llmie_spec_verify_sampled: spec_verify's operands plus draft_logits [batch, k, vocab] (the logits the drafter sampled
+    draft_ids from; dtype of logits) and draft_params (sampling_params(...) of the drafter, one per sequence).  Rejection
+    sampling: draft i is accepted with probability min(1, p / q), a rejection emits a draw from the residual max(0, p - q).
+    Returns (tokens int32 [batch, k + 1], count int32 [batch]) and moves seq_len, finished, the history and `state` by count as
+    spec_verify does; out_accepted: int32 [batch] or None, the number of drafts among the emitted tokens.  ext, out, workspace
+    (spec_verify_sampled_workspace_bytes(batch, k, vocab) bytes, or the string auto; inside a graph capture pass a tensor, or
+    make a first call outside): as in spec_verify."""
+    import torch
+    batch, k = draft_ids.shape
+    rows, vocab = logits.shape
+    if rows != batch * (k + 1):
+        raise LlmieError("spec_verify_sampled: %d rows of logits for %d sequences of %d + 1 positions" % (rows, batch, k))
+    if draft_logits.numel() != batch * k * vocab or draft_logits.dtype != logits.dtype or not draft_logits.is_contiguous():
+        raise LlmieError("spec_verify_sampled: draft_logits must be contiguous [%d, %d, %d] of the logits' dtype" % (batch, k, vocab))
+    if isinstance(workspace, str):
+        workspace = _grow(_spec_scratch, logits.device, spec_verify_sampled_workspace_bytes(batch, k, vocab))
+    tokens, count = out if out is not None else (torch.empty((batch, k + 1), dtype=torch.int32, device=logits.device),
+                                                 torch.empty(batch, dtype=torch.int32, device=logits.device))
+    stride = 0 if history is None else history.shape[1]
+    st = state if state is not None else SpecState(None, None, None)
+    _check(lib().llmie_spec_verify_sampled(_p(logits), _p(draft_logits), batch, k, vocab, _p(draft_ids), _p(draft_len), _p(params),
+                                           _p(draft_params), _p(history), stride, _p(history_len), 1 if append else 0, _p(seq_len),
+                                           _p(finished), _p(tokens), _p(count), _p(out_accepted), _p(out_logprob), _p(st.last_token),
+                                           _p(st.cached_len), _p(st.step_rows), step, _p(step_dev), end_id, _p(workspace),
+                                           0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(logits), _st(),
+                                           None if ext is None else _ext_ref(ext)), "spec_verify_sampled")
     return tokens, count
 
 

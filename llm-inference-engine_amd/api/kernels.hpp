@@ -328,6 +328,34 @@ void launchSpecVerify(TensorWrapper<T> *logits, TensorWrapper<int> *draft_ids, T
                                  llmie_api::scratch(ws), ws, llmie_api::dtype_of<T>(), llmie_api::st(), ext));
 }
 
+// No reference launcher: rejection-sampling verification against a drafter that sampled its drafts (include/llmie.h has the rule).
+// launchSpecVerify's operands, plus draft_logits [batch, k, vocab] -- the logits draft i of sequence b was sampled from --, the
+// drafter's controls draft_params_dev [batch] and out_accepted [batch] (may be null: the drafts among the emitted tokens).
+template <typename T>
+void launchSpecVerifySampled(TensorWrapper<T> *logits, TensorWrapper<T> *draft_logits, TensorWrapper<int> *draft_ids,
+                             TensorWrapper<int> *draft_len, const llmie_sampling_params *params_dev,
+                             const llmie_sampling_params *draft_params_dev, TensorWrapper<int> *history, TensorWrapper<int> *history_len,
+                             bool history_append, TensorWrapper<int> *seq_len, TensorWrapper<bool> *finished, TensorWrapper<int> *out_tokens,
+                             TensorWrapper<int> *out_count, TensorWrapper<int> *out_accepted, TensorWrapper<float> *out_logprob,
+                             TensorWrapper<int> *last_token, TensorWrapper<int> *cached_len, TensorWrapper<int> *step_rows, int step, int end_id,
+                             const llmie_sampling_ext *ext = nullptr) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int batch = draft_ids->shape[0], k = draft_ids->shape[1], vocab = logits->shape[1];
+    LLM_CHECK_WITH_INFO(logits->shape[0] == batch * (k + 1), "logits rows should equal batch * (k + 1)");
+    LLM_CHECK_WITH_INFO(draft_logits->shape.size() == 3 && draft_logits->shape[0] == batch && draft_logits->shape[1] == k &&
+                            draft_logits->shape[2] == vocab,
+                        "draft_logits should be [batch, k, vocab]");
+    const size_t ws = llmie_spec_verify_sampled_workspace_bytes(batch, k, vocab);
+    LLMIE_CALL(llmie_spec_verify_sampled(logits->data, draft_logits->data, batch, k, vocab, draft_ids->data, draft_len ? draft_len->data : nullptr,
+                                         params_dev, draft_params_dev, history ? history->data : nullptr, history ? history->shape[1] : 0,
+                                         history_len ? history_len->data : nullptr, history_append ? 1 : 0, seq_len->data,
+                                         reinterpret_cast<uint8_t *>(finished->data), out_tokens->data, out_count->data,
+                                         out_accepted ? out_accepted->data : nullptr, out_logprob ? out_logprob->data : nullptr,
+                                         last_token ? last_token->data : nullptr, cached_len ? cached_len->data : nullptr,
+                                         step_rows ? step_rows->data : nullptr, step, nullptr, end_id, llmie_api::scratch(ws), ws,
+                                         llmie_api::dtype_of<T>(), llmie_api::st(), ext));
+}
+
 // No reference launcher: prompt-lookup drafts from each sequence's own tokens [batch, stride] (len [batch] of them): the last
 // max_n .. min_n tokens are looked up earlier in the row and what followed them there becomes the draft.  out_ids [batch, k + 1]
 // (the verify chunk's inputs: the last token, then the drafts), out_draft_ids [batch, k], out_draft_len [batch].

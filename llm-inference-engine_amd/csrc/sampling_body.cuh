@@ -237,11 +237,38 @@ struct SpPick {
     const int32_t *stops;
 };
 
-// The sampler's body for ONE row, run by the whole 1024-thread workgroup: steps 0a .. 7 of include/llmie.h on the logits `lg`,
-// with `keys` the row's workspace.  b indexes the per-request operands (bias, stops, min_step, the mask row without a
-// mask_index); r indexes mask_index and the top-N outputs (the sampler's entries: r == b).  ep: the extension (EXT) or null.
+// The distribution a row is drawn from, over the row's keys: which tokens are kept and their fixed-point mass.  point: a greedy
+// row or one with at most one valid token -- the point mass on the row's pick, no cuts, total unused.
+struct SpKept {
+    bool point;
+    uint32_t kk, pk;   // the top-k cut is the token (kk, kid); the top-p cut keeps every key >= pk
+    int kid;
+    float min_p, vmax;
+    u64 total;         // the mass of the kept set
+    __device__ __forceinline__ u64 mass(uint32_t k) const {
+        const float d = sp_val(k) - vmax;
+        if (!(d > -23.f)) return 0ull;
+        return static_cast<u64>(expf(d) * 4294967296.0f);
+    }
+    __device__ __forceinline__ bool in_k(int t, uint32_t k) const { return k > kk || (k == kk && t <= kid); }
+    __device__ __forceinline__ bool kept(int t, uint32_t k) const {
+        return in_k(t, k) && k >= pk && (min_p == 0.f || expf(sp_val(k) - vmax) >= min_p);
+    }
+};
+
+// What sp_prepare_row leaves: SpPick with `chosen` the (key, id) maximum of the row (end_id without a valid token) -- the pick of
+// a point-mass row -- and the kept set.
+struct SpRow {
+    SpPick pick;
+    SpKept kept;
+};
+
+// The first half of the sampler's body for ONE row, run by the whole 1024-thread workgroup: steps 0a .. 6 of include/llmie.h on
+// the logits `lg` -- everything up to the kept set and its mass -- with `keys` the row's workspace, which holds the row's keys
+// afterwards.  b indexes the per-request operands (bias, stops, min_step, the mask row without a mask_index); r indexes
+// mask_index and the top-N outputs (the sampler's entries: r == b).  ep: the extension (EXT) or null.
 template <typename T, bool EXT, class History>
-__device__ __forceinline__ SpPick sp_sample_row(const T *__restrict__ lg, int V, const llmie_sampling_params p, const History hist, int step,
+__device__ __forceinline__ SpRow sp_prepare_row(const T *__restrict__ lg, int V, const llmie_sampling_params p, const History hist, int step,
                                                 int end_id, uint32_t *keys, const llmie_sampling_ext *ep, int b, int r, SpShared &s) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *rowf = reinterpret_cast<float *>(keys);
@@ -434,25 +461,21 @@ __device__ __forceinline__ SpPick sp_sample_row(const T *__restrict__ lg, int V,
     int chosen = end_id;
     if (valid > 0) chosen = static_cast<int>(0xffffffffu - static_cast<uint32_t>(best & 0xffffffffu));
 
+    SpKept kp{true, 0u, 0u, INT_MAX, min_p, 0.f, 0ull};
     if (!greedy && valid > 1) {
-        const float vmax = sp_val(static_cast<uint32_t>(best >> 32));
-        auto mass = [vmax](uint32_t k) -> u64 {
-            const float d = sp_val(k) - vmax;
-            if (!(d > -23.f)) return 0ull;
-            return static_cast<u64>(expf(d) * 4294967296.0f);
-        };
+        kp.point = false;
+        kp.vmax = sp_val(static_cast<uint32_t>(best >> 32));
         // top-k: the top_k-th token (kk, kid); the set {key > kk} + {key == kk, id <= kid}
-        uint32_t kk = 0;
-        int kid = INT_MAX;
         if (top_k > 0 && top_k < valid) {
             u64 above;
             auto all = [](int, uint32_t) { return true; };
-            kk = radix_select(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_k - 1), &above, s);
-            kid = id_select(keys, V, kk, all, static_cast<u64>(top_k - 1) - above, s);
+            kp.kk = radix_select(keys, V, all, [](uint32_t) { return 1ull; }, static_cast<u64>(top_k - 1), &above, s);
+            kp.kid = id_select(keys, V, kp.kk, all, static_cast<u64>(top_k - 1) - above, s);
         }
-        auto in_k = [kk, kid](int t, uint32_t k) { return k > kk || (k == kk && t <= kid); };
+        const SpKept topk = kp;   // (pk == 0: the top-k set alone)
+        auto in_k = [topk](int t, uint32_t k) { return topk.in_k(t, k); };
+        auto mass = [topk](uint32_t k) { return topk.mass(k); };
         // top-p: keep every value >= that of the first token at which the mass reaches top_p * the top-k mass
-        uint32_t pk = 0;
         if (top_p < 1.f) {
             u64 ms = 0;
             sp_for_keys(keys, V, [&](int t, uint32_t k) {
@@ -463,26 +486,42 @@ __device__ __forceinline__ SpPick sp_sample_row(const T *__restrict__ lg, int V,
             thr = thr == 0 ? 0 : thr - 1;
             if (thr >= ms) thr = ms - 1;
             u64 above;
-            pk = radix_select(keys, V, in_k, mass, thr, &above, s);
+            kp.pk = radix_select(keys, V, in_k, mass, thr, &above, s);
         }
-        auto kept = [=](int t, uint32_t k) {
-            return in_k(t, k) && k >= pk && (min_p == 0.f || expf(sp_val(k) - vmax) >= min_p);
-        };
+        const SpKept cut = kp;
         u64 mk = 0;
         sp_for_keys(keys, V, [&](int t, uint32_t k) {
-            if (k && kept(t, k)) mk += mass(k);
+            if (k && cut.kept(t, k)) mk += cut.mass(k);
         });
-        mk = sp_sum64(mk, s);
-        // draw: the first kept token at which the running mass exceeds u * kept mass (u == 1: the last kept token)
-        const float u = uniform_philox(static_cast<uint32_t>(step), p.seed);
-        u64 thr = static_cast<u64>(floor(static_cast<double>(u) * static_cast<double>(mk)));
-        if (thr >= mk) thr = mk - 1;
-        u64 above;
-        const uint32_t dk = radix_select(keys, V, kept, mass, thr, &above, s);
-        const int id = id_select(keys, V, dk, kept, (thr - above) / mass(dk), s);
-        if (id >= 0) chosen = id;
+        kp.total = sp_sum64(mk, s);
     }
-    return SpPick{chosen, valid, lse_m, lse_s, slen, stops};
+    return SpRow{SpPick{chosen, valid, lse_m, lse_s, slen, stops}, kp};
+}
+
+// The second half, for a row that is no point mass: the first kept token, in (value desc, id asc) order, at which the running
+// mass exceeds u * kept mass (u == 1: the last kept token); -1 if there is none.
+__device__ __forceinline__ int sp_draw_row(const uint32_t *keys, int V, const SpKept kp, float u, SpShared &s) {
+    auto kept = [kp](int t, uint32_t k) { return kp.kept(t, k); };
+    auto mass = [kp](uint32_t k) { return kp.mass(k); };
+    const u64 mk = kp.total;
+    u64 thr = static_cast<u64>(floor(static_cast<double>(u) * static_cast<double>(mk)));
+    if (thr >= mk) thr = mk - 1;
+    u64 above;
+    const uint32_t dk = radix_select(keys, V, kept, mass, thr, &above, s);
+    return id_select(keys, V, dk, kept, (thr - above) / mass(dk), s);
+}
+
+// The sampler's body for ONE row: the two halves in sequence (steps 0a .. 7 of include/llmie.h).
+template <typename T, bool EXT, class History>
+__device__ __forceinline__ SpPick sp_sample_row(const T *__restrict__ lg, int V, const llmie_sampling_params p, const History hist, int step,
+                                                int end_id, uint32_t *keys, const llmie_sampling_ext *ep, int b, int r, SpShared &s) {
+    const SpRow row = sp_prepare_row<T, EXT>(lg, V, p, hist, step, end_id, keys, ep, b, r, s);
+    SpPick pick = row.pick;
+    if (!row.kept.point) {
+        const int id = sp_draw_row(keys, V, row.kept, uniform_philox(static_cast<uint32_t>(step), p.seed), s);
+        if (id >= 0) pick.chosen = id;
+    }
+    return pick;
 }
 
 }  // namespace llmie

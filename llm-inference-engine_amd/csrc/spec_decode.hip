@@ -13,6 +13,12 @@
 // have made from these logits, and draft i is accepted iff it equals it: the emitted tokens are bit for bit those of `count`
 // llmie_sample_logits_ext calls.
 //
+// llmie_spec_verify_sampled, two launches of the same shape, for a drafter that SAMPLED its drafts: the rows kernel prepares the
+// target row and the draft row (sp_prepare_row: the kept set and its fixed-point masses instead of a pick) in two key rows of the
+// workspace and decides by the rejection rule min(1, p / q) -- cross-multiplied, one exact comparison of 128-bit integers -- and,
+// behind a rejection, draws from the residual max(0, P_v S_Q - Q_v S_P) by a scan in ascending id order; the accept kernel walks
+// the records.  include/llmie.h has the rule.
+//
 // llmie_ngram_draft, one launch, one 256-thread workgroup per sequence: ONE sweep over the row finds, for every n at once, the
 // last place the sequence's final n tokens occurred before.  A thread that sees the final token at q extends the comparison
 // backwards (<= 7 more loads, rare); the sweep itself reads 16 bytes per thread where the row is aligned.  "The last place" is an
@@ -111,6 +117,206 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(const SpecPick *__restr
     }
     out_count[b] = count;
 }
+
+// ---------------------------------------------------------------------------------------------- llmie_spec_verify_sampled
+typedef unsigned __int128 u128;
+
+struct SpecSampledRec {   // workspace record of a row
+    int32_t token;        // the sampler's own pick of the row (lane 0), its raw log-probability and finish flag
+    float logprob;
+    int32_t fin;
+    int32_t accept;       // bit 0: the draft is accepted; bit 1: the draft finishes the sequence
+    float draft_logprob;
+    int32_t res_token;    // what a rejection emits: the residual draw (the pick when SR == 0)
+    float res_logprob;
+    int32_t res_fin;
+};
+
+__device__ __forceinline__ u128 sp_shfl_up128(u128 v, int o) {
+    const u64 lo = __shfl_up(static_cast<u64>(v), o), hi = __shfl_up(static_cast<u64>(v >> 64), o);
+    return (static_cast<u128>(hi) << 64) | lo;
+}
+// exclusive prefix of a 128-bit integer over the block (thread order) and the block's total; the wave totals go through
+// SpShared::hist
+__device__ __forceinline__ u128 sp_excl_scan128(u128 v, u128 *total, SpShared &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    u128 inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u128 y = sp_shfl_up128(inc, o);
+        if (lane >= o) inc += y;
+    }
+    __syncthreads();
+    if (lane == 63) {
+        s.hist[2 * w] = static_cast<u64>(inc);
+        s.hist[2 * w + 1] = static_cast<u64>(inc >> 64);
+    }
+    __syncthreads();
+    u128 before = 0, all = 0;
+    for (int i = 0; i < kSpWaves; ++i) {
+        const u128 t = (static_cast<u128>(s.hist[2 * i + 1]) << 64) | s.hist[2 * i];
+        if (i < w) before += t;
+        all += t;
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+// the mass of token t under a prepared row (its keys, its kept set): 0 for a token not kept; the point mass is 1 on the pick
+__device__ __forceinline__ u64 sp_mass_at(const uint32_t *keys, const SpRow &row, int t) {
+    if (row.kept.point) return (row.pick.valid > 0 && t == row.pick.chosen) ? 1ull : 0ull;
+    const uint32_t key = keys[t];
+    return (key && row.kept.kept(t, key)) ? row.kept.mass(key) : 0ull;
+}
+
+// One 1024-thread workgroup per (sequence b, position i), r = b * (k + 1) + i.  The target row is prepared in key row 2r of the
+// workspace (the sampler's first half: kept set P and its mass S_P) and its plain pick drawn (lane 0); for i < draft_len the
+// draft row is prepared in key row 2r + 1 on the same history view (Q, S_Q), and the joint passes follow: the accept comparison
+// on (P_d, Q_d, S_P, S_Q) and, behind a rejection, the residual R_v = max(0, P_v S_Q - Q_v S_P) -- every thread sums a contiguous
+// chunk of ids, a block scan orders the chunks, and the one thread whose chunk holds thr walks it: the first id, ascending, at
+// which the running sum exceeds thr.  All sums are 128-bit integers: exact in any order.  No state is written.
+template <typename T, bool EXT>
+__global__ __launch_bounds__(kSpThreads) void spec_sampled_rows_kernel(
+    const T *__restrict__ logits, const T *__restrict__ draft_logits, int V, int k, const llmie_sampling_params *__restrict__ params,
+    const llmie_sampling_params *__restrict__ draft_params, const int32_t *__restrict__ history, int hstride,
+    const int32_t *__restrict__ history_len, int happend, const int32_t *__restrict__ draft_ids, const int32_t *__restrict__ draft_len,
+    const int32_t *__restrict__ step_rows, int step_arg, const int32_t *step_dev, int end_id, uint32_t *ws, size_t ws_row,
+    SpecSampledRec *__restrict__ recs, const llmie_sampling_ext ext) {
+    __shared__ alignas(16) SpShared s;
+    const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
+    const int step = (step_rows ? step_rows[b] : (step_dev ? *step_dev : step_arg)) + i;
+    SpSplicedHistory hist{nullptr, draft_ids + static_cast<size_t>(b) * k, 0, 0};
+    if (hstride > 0) {
+        const int len0 = history_len[b];
+        hist.row = history + static_cast<size_t>(b) * hstride;
+        hist.stored = min(max(len0, 0), hstride);
+        hist.len = (happend && len0 >= 0) ? min(hist.stored + i, hstride) : hist.stored;
+    }
+    const T *lg = logits + static_cast<size_t>(r) * V;
+    uint32_t *keys_p = ws + static_cast<size_t>(2 * r) * ws_row, *keys_q = keys_p + ws_row;
+    const llmie_sampling_params p = params[b];
+    const SpRow P = sp_prepare_row<T, EXT>(lg, V, p, hist, step, end_id, keys_p, EXT ? &ext : nullptr, b, r, s);
+    int plain = P.pick.chosen;
+    if (!P.kept.point) {
+        const int id = sp_draw_row(keys_p, V, P.kept, uniform_philox(static_cast<uint32_t>(step), p.seed), s);
+        if (id >= 0) plain = id;
+    }
+    const float lse = P.pick.lse_m + logf(P.pick.lse_s);
+    auto logprob = [&](int t) { return (t >= 0 && t < V && P.pick.valid > 0) ? to_f32(lg[t]) - lse : -INFINITY; };
+    auto finishes = [&](int t) {
+        bool fin = t == end_id;
+        if constexpr (EXT)
+            for (int j = 0; j < P.pick.slen; ++j) fin = fin || P.pick.stops[j] == t;
+        return fin ? 1 : 0;
+    };
+
+    const int m = draft_len ? min(max(draft_len[b], 0), k) : k;
+    bool accept = false;
+    int d = -1, res = plain;
+    if (i < m) {   // (uniform over the workgroup)
+        __syncthreads();   // the draw is done with SpShared
+        const T *dlg = draft_logits + (static_cast<size_t>(b) * k + i) * V;
+        const SpRow Q = sp_prepare_row<T, false>(dlg, V, draft_params[b], hist, step, end_id, keys_q, nullptr, b, r, s);
+        __syncthreads();   // both key rows are complete
+        const u64 sp = P.kept.point ? (P.pick.valid > 0 ? 1ull : 0ull) : P.kept.total;
+        const u64 sq = Q.kept.point ? (Q.pick.valid > 0 ? 1ull : 0ull) : Q.kept.total;
+        d = draft_ids[static_cast<size_t>(b) * k + i];
+        if (d >= 0 && d < V) {
+            const u64 pd = sp_mass_at(keys_p, P, d), qd = sp_mass_at(keys_q, Q, d);
+            const u64 u1 = philox_u24(static_cast<uint32_t>(step), p.seed, 1u) - 1u;
+            // (U1 - 1) Q_d S_P < 2^24 P_d S_Q: below 2^24 * 2^32 * 2^51 on either side (vocab <= 2^19)
+            accept = static_cast<u128>(u1 * qd) * sp < ((static_cast<u128>(pd) * sq) << 24);
+        }
+        if (!accept && sp != 0 && sq != 0) {
+            const int chunk = (V + kSpThreads - 1) / kSpThreads;
+            const int t0 = min(V, static_cast<int>(threadIdx.x) * chunk), t1 = min(V, t0 + chunk);
+            auto residual = [&](int t) -> u128 {
+                const u64 pv = sp_mass_at(keys_p, P, t);
+                if (pv == 0) return 0;
+                const u128 a = static_cast<u128>(pv) * sq, c = static_cast<u128>(sp_mass_at(keys_q, Q, t)) * sp;
+                return a > c ? a - c : static_cast<u128>(0);
+            };
+            u128 mine = 0, sr;
+            for (int t = t0; t < t1; ++t) mine += residual(t);
+            if (threadIdx.x == 0) s.b_id = -1;
+            const u128 ex = sp_excl_scan128(mine, &sr, s);   // (its barriers order the store above)
+            if (sr != 0) {
+                const u128 thr = (static_cast<u128>(philox_u24(static_cast<uint32_t>(step), p.seed, 2u) - 1u) * sr) >> 24;
+                if (thr >= ex && thr < ex + mine) {
+                    u128 run = ex;
+                    for (int t = t0; t < t1; ++t) {
+                        run += residual(t);
+                        if (run > thr) {
+                            s.b_id = t;
+                            break;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (s.b_id >= 0) res = s.b_id;
+        }
+    }
+    if (threadIdx.x == 0) {
+        SpecSampledRec out;
+        out.token = plain;
+        out.logprob = logprob(plain);
+        out.fin = finishes(plain);
+        out.accept = accept ? (1 | (finishes(d) << 1)) : 0;
+        out.draft_logprob = accept ? logprob(d) : -INFINITY;
+        out.res_token = res;
+        out.res_logprob = logprob(res);
+        out.res_fin = finishes(res);
+        recs[r] = out;
+    }
+}
+
+// one workgroup (one working thread) per sequence
+__global__ __launch_bounds__(64) void spec_sampled_accept_kernel(const SpecSampledRec *__restrict__ recs, int k, const int32_t *__restrict__ draft_ids,
+                                                                 const int32_t *__restrict__ draft_len, int32_t *history, int hstride,
+                                                                 int32_t *history_len, int happend, int32_t *seq_len, uint8_t *finished,
+                                                                 int32_t *__restrict__ out_tokens, int32_t *__restrict__ out_count,
+                                                                 float *__restrict__ out_logprob, int32_t *__restrict__ out_accepted,
+                                                                 int32_t *last_token, int32_t *cached_len, int32_t *step_rows) {
+    if (threadIdx.x != 0) return;
+    const int b = blockIdx.x, n = k + 1;
+    int32_t *tok = out_tokens + static_cast<size_t>(b) * n;
+    float *lp = out_logprob ? out_logprob + static_cast<size_t>(b) * n : nullptr;
+    int count = 0, accepted = 0;
+    if (!finished[b]) {
+        const int dl = draft_len ? min(max(draft_len[b], 0), k) : k;
+        const SpecSampledRec *p = recs + static_cast<size_t>(b) * n;
+        const int32_t *draft = draft_ids + static_cast<size_t>(b) * k;
+        int hl = (happend && hstride > 0) ? history_len[b] : -1;
+        int fin = 0;
+        for (int i = 0; i < n; ++i) {
+            const SpecSampledRec c = p[i];
+            const bool acc = i < dl && (c.accept & 1);
+            const int32_t t = acc ? draft[i] : (i < dl ? c.res_token : c.token);
+            tok[i] = t;
+            if (lp) lp[i] = acc ? c.draft_logprob : (i < dl ? c.res_logprob : c.logprob);
+            fin = acc ? (c.accept >> 1) : (i < dl ? c.res_fin : c.fin);
+            ++count;
+            accepted += acc ? 1 : 0;
+            if (hl >= 0 && hl < hstride) history[static_cast<size_t>(b) * hstride + hl++] = t;
+            if (!acc || fin) break;
+        }
+        seq_len[b] += count;
+        finished[b] = static_cast<uint8_t>(fin);
+        if (happend && hstride > 0 && hl >= 0) history_len[b] = hl;
+        if (last_token) last_token[b] = tok[count - 1];
+        if (cached_len) cached_len[b] += count;
+        if (step_rows) step_rows[b] += count;
+    }
+    for (int i = count; i < n; ++i) {
+        tok[i] = -1;
+        if (lp) lp[i] = -INFINITY;
+    }
+    out_count[b] = count;
+    if (out_accepted) out_accepted[b] = accepted;
+}
+
+constexpr int kSpecSampledMaxVocab = 1 << 19;   // S_P, S_Q < 2^51: the rule's products stay inside 128 bits
 
 constexpr int kNgThreads = 256;
 constexpr int kNgMaxN = 8;
@@ -245,6 +451,75 @@ extern "C" int llmie_spec_verify(const void *logits, int batch, int k, int vocab
     spec_accept_kernel<<<batch, 64, 0, st>>>(picks, k, draft_ids, draft_len, history, history_stride, history_len, history_append, seq_len,
                                              finished, out_tokens, out_count, out_logprob, last_token, cached_len, step_rows);
     return launch_status("spec_verify(accept)");
+}
+
+// two key rows per position, then the records
+static size_t spec_sampled_recs_offset(int rows, int vocab) { return 2 * static_cast<size_t>(rows) * sample_logits_ws_row(vocab) * sizeof(uint32_t); }
+
+extern "C" size_t llmie_spec_verify_sampled_workspace_bytes(int batch, int k, int vocab) {
+    if (batch <= 0 || k <= 0 || vocab <= 0 || k > LLMIE_SPEC_MAX_DRAFT || vocab > kSpecSampledMaxVocab) return 0;
+    const int rows = batch * (k + 1);
+    return spec_sampled_recs_offset(rows, vocab) + static_cast<size_t>(rows) * sizeof(SpecSampledRec);
+}
+
+template <typename T>
+static void spec_sampled_rows_launch(bool ext_active, const void *logits, const void *draft_logits, int rows, int vocab, int k,
+                                     const llmie_sampling_params *params, const llmie_sampling_params *draft_params, const int32_t *history,
+                                     int hstride, const int32_t *history_len, int happend, const int32_t *draft_ids, const int32_t *draft_len,
+                                     const int32_t *step_rows, int step, const int32_t *step_dev, int end_id, uint32_t *ws,
+                                     SpecSampledRec *recs, const llmie_sampling_ext &ext, hipStream_t st) {
+    const size_t ws_row = sample_logits_ws_row(vocab);
+    const T *lg = static_cast<const T *>(logits), *dlg = static_cast<const T *>(draft_logits);
+    if (ext_active)
+        spec_sampled_rows_kernel<T, true><<<rows, kSpThreads, 0, st>>>(lg, dlg, vocab, k, params, draft_params, history, hstride, history_len, happend,
+                                                                       draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, ws_row, recs, ext);
+    else
+        spec_sampled_rows_kernel<T, false><<<rows, kSpThreads, 0, st>>>(lg, dlg, vocab, k, params, draft_params, history, hstride, history_len, happend,
+                                                                        draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, ws_row, recs, ext);
+}
+
+extern "C" int llmie_spec_verify_sampled(const void *logits, const void *draft_logits, int batch, int k, int vocab, const int32_t *draft_ids,
+                                         const int32_t *draft_len, const llmie_sampling_params *params_dev,
+                                         const llmie_sampling_params *draft_params_dev, int32_t *history, int history_stride,
+                                         int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished, int32_t *out_tokens,
+                                         int32_t *out_count, int32_t *out_accepted, float *out_logprob, int32_t *last_token, int32_t *cached_len,
+                                         int32_t *step_rows, int step, const int32_t *step_dev, int end_id, void *workspace,
+                                         size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream, const llmie_sampling_ext *ext) {
+    const char *name = "spec_verify_sampled";
+    int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_tokens, nullptr, 0,
+                                 dtype, name, false);
+    if (rc != LLMIE_OK) return rc;
+    bool active;
+    if ((rc = sample_ext_check(batch, vocab, ext, &active, name)) != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(k >= 1, "%s: k %d < 1", name, k);
+    LLMIE_REQUIRE(draft_ids && out_tokens && out_count, "%s: NULL draft_ids / out_tokens / out_count", name);
+    LLMIE_REQUIRE(draft_logits && draft_params_dev, "%s: NULL draft_logits / draft_params_dev", name);
+    if (k > LLMIE_SPEC_MAX_DRAFT) LLMIE_UNSUPPORTED("%s: k %d above LLMIE_SPEC_MAX_DRAFT (%d)", name, k, LLMIE_SPEC_MAX_DRAFT);
+    if (vocab > kSpecSampledMaxVocab) LLMIE_UNSUPPORTED("%s: vocab %d above %d", name, vocab, kSpecSampledMaxVocab);
+    LLMIE_REQUIRE(static_cast<long long>(batch) * (k + 1) <= INT_MAX / 2, "%s: batch * (k + 1) = %lld rows", name,
+                  static_cast<long long>(batch) * (k + 1));
+    const size_t need = llmie_spec_verify_sampled_workspace_bytes(batch, k, vocab);
+    if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
+        set_error("%s: workspace %zu bytes (need %zu, 16-byte aligned: llmie_spec_verify_sampled_workspace_bytes)", name,
+                  workspace ? workspace_bytes : (size_t)0, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    const int rows = batch * (k + 1);
+    uint32_t *ws = static_cast<uint32_t *>(workspace);
+    SpecSampledRec *recs = reinterpret_cast<SpecSampledRec *>(static_cast<unsigned char *>(workspace) + spec_sampled_recs_offset(rows, vocab));
+    const llmie_sampling_ext none = {};
+    const llmie_sampling_ext &e = active ? *ext : none;
+    hipStream_t st = as_stream(stream);
+    if (dtype == LLMIE_F16)
+        spec_sampled_rows_launch<half_t>(active, logits, draft_logits, rows, vocab, k, params_dev, draft_params_dev, history, history_stride,
+                                         history_len, history_append, draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, recs, e, st);
+    else
+        spec_sampled_rows_launch<float>(active, logits, draft_logits, rows, vocab, k, params_dev, draft_params_dev, history, history_stride,
+                                        history_len, history_append, draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, recs, e, st);
+    if ((rc = launch_status("spec_verify_sampled(rows)")) != LLMIE_OK) return rc;
+    spec_sampled_accept_kernel<<<batch, 64, 0, st>>>(recs, k, draft_ids, draft_len, history, history_stride, history_len, history_append, seq_len,
+                                                     finished, out_tokens, out_count, out_logprob, out_accepted, last_token, cached_len, step_rows);
+    return launch_status("spec_verify_sampled(accept)");
 }
 
 extern "C" int llmie_ngram_draft(const int32_t *tokens, int stride, const int32_t *len, const uint8_t *finished, int batch, int k, int max_n,

@@ -7,6 +7,13 @@ plain step   forward_paged_ragged (one token per sequence on top of ctx cached t
 verify step  input_embedding + prefill_paged (k + 1 inputs per sequence on top of ctx cached tokens) + rmsnorm + linear over the
              batch * (k + 1) rows + spec_verify; the n-gram drafter's launch is timed on its own (ngram_ms)
 
+    python tools/specbench.py --sampled [--batch 1 8] [--k 2 4 7] [--rounds 7] [--reps 50]
+
+the sampled-draft arm: the device time of llmie_spec_verify_sampled beside llmie_spec_verify on the same [batch * (k + 1), 32000]
+fp16 logits (no model: the entries alone, between device events), the drafts drawn by llmie_sample_logits from draft logits that
+are the target's plus noise -- so that acceptances and rejections (the residual pass) both occur; the two arms alternate inside
+every round.
+
 Same build, same process, same weights; the arms alternate inside every round (plain, k = 2, 4, 7, plain, ...) and the median
 round of each arm is reported with its min and max.  A verify step emits 1 .. k + 1 tokens for its time, a plain step one: the
 break-even is verify_ms / plain_ms emitted tokens per verify step, i.e. that minus one accepted drafts.  Prints one JSON line
@@ -118,6 +125,50 @@ def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
     return res
 
 
+def run_sampled(llmie, B, ks, rounds, reps, V=32000):
+    """the sampled-draft arm: spec_verify and spec_verify_sampled alone, alternating, device events around `reps` calls"""
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(100 + B)
+    params = llmie.sampling_params([dict(temperature=0.8, top_k=50, top_p=0.9, seed=b) for b in range(B)])
+    dparams = llmie.sampling_params([dict(temperature=1.0, top_k=50, seed=1000 + b) for b in range(B)])
+    out = dict(batch=B, vocab=V, arms=[])
+    for k in ks:
+        T = B * (k + 1)
+        logits = (torch.randn((T, V), generator=g, device="cuda") * 3).half()
+        dlogits = (logits.reshape(B, k + 1, V)[:, :k].float() + torch.randn((B, k, V), generator=g, device="cuda")).half().contiguous()
+        # the drafter's side of the contract: every draft is llmie_sample_logits' pick from its draft row (no history here)
+        drafts = i32([0] * (B * k))
+        dp_rows = llmie.sampling_params([dict(temperature=1.0, top_k=50, seed=1000 + b) for b in range(B) for _ in range(k)])
+        llmie.sample_logits(dlogits.reshape(B * k, V), dp_rows, i32([0] * (B * k)), torch.zeros(B * k, dtype=torch.uint8, device="cuda"), drafts, 7, -1)
+        # (one step for all rows is not the per-position step of the contract: this is a timing, the verdicts only need to vary)
+        drafts = drafts.reshape(B, k).contiguous()
+        seq, fin = i32([0] * B), torch.zeros(B, dtype=torch.uint8, device="cuda")
+        outs = (torch.empty((B, k + 1), dtype=torch.int32, device="cuda"), i32([0] * B))
+        acc = i32([0] * B)
+        ws = torch.empty(llmie.spec_verify_sampled_workspace_bytes(B, k, V), dtype=torch.uint8, device="cuda")
+
+        def exact():
+            llmie.spec_verify(logits, drafts, params, seq, fin, -1, step=7, workspace=ws, out=outs)
+
+        def sampled():
+            llmie.spec_verify_sampled(logits, dlogits, drafts, params, dparams, seq, fin, -1, step=7, workspace=ws, out=outs, out_accepted=acc)
+
+        for _ in range(3):
+            exact()
+            sampled()
+        torch.cuda.synchronize()
+        accepted = float(acc.float().mean().item())
+        te, ts = [], []
+        for _ in range(rounds):
+            te.append(timed(exact, reps) * 1e3)
+            ts.append(timed(sampled, reps) * 1e3)
+        me, ms = statistics.median(te), statistics.median(ts)
+        out["arms"].append(dict(k=k, rows=T, spec_verify_us=me, spec_verify_us_min_max=[min(te), max(te)], spec_verify_sampled_us=ms,
+                                spec_verify_sampled_us_min_max=[min(ts), max(ts)], sampled_over_exact=ms / me,
+                                accepted_drafts_per_sequence=accepted))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="*", default=[1, 8])
@@ -126,11 +177,22 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--layers", type=int, default=0, help="fewer layers than the model's 32 (a rehearsal; not a measurement)")
+    ap.add_argument("--sampled", action="store_true", help="the sampled-draft arm: spec_verify_sampled beside spec_verify, the entries alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("specbench: needs a GPU (a time measured anywhere else says nothing)")
     llmie = bench.load_llmie()
+    if a.sampled:
+        res = dict(bench="spec_verify_sampled", device=torch.cuda.get_device_name(0), rounds=a.rounds, reps=a.reps,
+                   results=[run_sampled(llmie, B, a.k, a.rounds, a.reps) for B in a.batch])
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     cfg = dict(bench.LLAMA2_7B)
     if a.layers:
         cfg["num_layers"] = a.layers
