@@ -234,6 +234,45 @@ const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, in
                                    int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
                                    unsigned long long residues, long long workspace_bytes, int *status);
 
+/* ABI 3 (an addition; no reference counterpart).  Sliding-window attention with sink tokens.
+ * Positions are absolute and 0-based.  With window W >= 1 and S >= 0 sink tokens the query at position i sees key j iff
+ *        j <= i  and  ( i - j < W  or  j < S )
+ * W = 0 is full attention and S is then ignored.  RoPE is unchanged: keys are cached rotated at their absolute position, queries are
+ * rotated at theirs, nothing is re-based.  The appended token always sees itself.  The softmax keeps the (sum + 1e-6) denominator.
+ * In a decode step at context length `step` (the new token included) the live keys are [0, min(S, step)) and [max(0, step - W),
+ * step); the ranges may overlap or touch, a key of both counts once.
+ *
+ * llmie_decoder_mha_window: llmie_decoder_mha_ragged's operands and behaviour (ctx_len_dev[b] = context length of sequence b with
+ * this step's token; block_table nullable) under that mask, plus `tickets` (nullable; llmie_decoder_mha_rope) and, with kv_e4m3 != 0,
+ * caches of e4m3 bytes, stored = e4m3(x / scale) (fp16 activations; separate merge only).  The split kernel walks only the chunks
+ * that hold a live key -- the grid's x extent is at most ceil(S / chunk) + ceil(W / chunk) + 1 whatever max_seq_len is -- and never
+ * follows the block-table entry of a page without a live key, so such entries may be unmapped (-1).  Supported with a window: fp16
+ * activations, head_size 64 / 128, head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4}); everything else with window > 0 is
+ * LLMIE_ERR_UNSUPPORTED.  window = 0 makes the call llmie_decoder_mha_ragged makes; a window >= the context gives its output bit
+ * for bit.  llmie_decoder_mha_window_plan: llmie_decoder_mha_plan for such a call; with a window the line gains
+ * " window W sinks S live N" (N live chunks of the host step) or "... live <=N" (device position: the grid's bound). */
+int llmie_decoder_mha_window(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer,
+                             int batch, int head_num, int kv_head_num, int head_size, int max_seq_len,
+                             const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
+                             int rotary_dim, const int32_t *block_table, int max_pages, int num_pages, int window, int sinks,
+                             int32_t *tickets, int kv_e4m3, float k_scale, float v_scale, llmie_dtype dtype, llmie_stream stream);
+const char *llmie_decoder_mha_window_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                          int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                          unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                          int *status);
+
+/* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
+ * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
+ * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the
+ * lowest mapped logical page that lies wholly at or above the sink pages and wholly below cached_len[b] + 1 - window (dead for this
+ * and every later query), maps it at the new index and unmaps the old one; status[b] = 0.  Without enough dead pages status[b] = 1
+ * and the row is left as it was: the caller must supply a page.  status[b] = 2: the positions do not fit max_pages.  A sequence
+ * then lives in ceil(S / 128) + ceil((W + n) / 128) + 1 pool pages at any context length.  window: the LARGEST window of any layer
+ * (>= 1).  Not applicable when some layer attends to everything, or when table rows share pages (llmie_kv_pages_fork). */
+int llmie_kv_window_advance(int32_t *block_table /* [batch, max_pages] in/out */, int max_pages, const int32_t *cached_len /* [batch] */,
+                            const int32_t *new_tokens /* [batch] or NULL = 1 each */, int batch, int window, int sinks,
+                            int32_t *status /* [batch] */, llmie_stream stream);
+
 /* replaces launchConcatKVCache         src/kernels/concat_past_kv.cu:44-89  (one call = K or V) */
 int llmie_concat_kv(const void *src, void *cache, const int32_t *cur_len,
                     const int32_t *history_len, int layer, int batch, int kv_head_num,
@@ -922,6 +961,23 @@ size_t llmie_decoder_lora_workspace_bytes(const llmie_decoder_config *cfg, int m
 int llmie_decoder_lora_attach(llmie_decoder *dec, const void *table_dev, int slots, const int32_t *seq_slot_dev, void *workspace,
                               size_t workspace_bytes);
 int llmie_decoder_lora_detach(llmie_decoder *dec);
+
+/* ABI 3 (an addition; llmie_decoder_config is not touched).  Sliding-window attention with sink tokens on an engine, per layer: the
+ * mask stated at llmie_decoder_mha_window (query i sees key j iff j <= i and (i - j < W or j < S); absolute positions, RoPE unchanged).
+ * layer_window: host array [num_layers], the window W of every layer, 0 = full attention on that layer (alternating local / global
+ * stacks); NULL clears every window (sinks must be 0).  sinks: the S of every windowed layer.  The state lives on the engine and is
+ * read when a call is planned (the llmie_decoder_lora_attach pattern): from then on every decode entry (forward, _ragged, _paged,
+ * _paged_ragged, with any weight format, adapters, the speculative and scoring entries) runs the windowed instantiation of the
+ * split-KV kernel on the windowed layers -- grid and time bounded by the window, not by the context -- and every prefill entry the
+ * windowed instantiation of its flash kernel, which walks only the key tiles some query of the workgroup sees.  Only the attention
+ * launches change; with no window set nothing does, and llmie_decoder_set_window(dec, NULL, 0) restores today's bits.
+ * LLMIE_ERR_INVALID_ARG: a negative window or sinks; sinks without a window on any layer.  LLMIE_ERR_UNSUPPORTED: an engine whose
+ * decode attention has no windowed form (fp32; head sizes other than 64 / 128; head ratios other than 1 / 2 / 4 / 8; with an e4m3 cache also ratio 8).
+ * A call whose operands send its attention to the generic kernel (unaligned buffers) fails with LLMIE_ERR_UNSUPPORTED while a window
+ * is set: it would attend to everything.  llmie_decoder_plan_name and llmie_decoder_prefill_layer_plan answer for a windowed call
+ * under LLMIE_PLAN_WINDOW (same sequences; NULL for an engine set_window refuses; the layer plan ends in " attn_window=1"). */
+#define LLMIE_PLAN_WINDOW 2048u /* a sliding window is set on some layer (llmie_decoder_set_window) */
+int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer_window /* host, [num_layers], 0 = full; NULL clears */, int sinks);
 
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,
  * context_attention.cpp:143-312) on PACKED tokens: hidden_in/out [num_tokens, H] hold the sequences back to back

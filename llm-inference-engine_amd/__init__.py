@@ -93,6 +93,10 @@ _SIGS = {
     "llmie_decoder_forward_paged_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "llmie_decoder_mha_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _vp],
     "llmie_decoder_mha_ragged": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp],
+    "llmie_decoder_mha_window": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _vp,
+                                 _i, _f, _f, _i, _vp],
+    "llmie_decoder_mha_window_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _i, _i, _vp],
+    "llmie_kv_window_advance": [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp],
     "llmie_decoder_prefill_workspace_bytes": [_vp, _i, _i],
     "llmie_decoder_prefill": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
     "llmie_lm_head_sample": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp,
@@ -131,6 +135,7 @@ _SIGS = {
     "llmie_decoder_lora_workspace_bytes": [_vp, _i, _i],
     "llmie_decoder_lora_attach": [_vp, _vp, _i, _vp, _vp, _sz],
     "llmie_decoder_lora_detach": [_vp],
+    "llmie_decoder_set_window": [_vp, _vp, _i],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -169,6 +174,7 @@ _RESTYPES = {
     "llmie_linear_route": C.c_char_p,
     "llmie_gemm256_tiles": C.c_char_p,
     "llmie_decoder_mha_plan": C.c_char_p,
+    "llmie_decoder_mha_window_plan": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
     "llmie_decoder_prefill_layer_plan": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
@@ -301,6 +307,22 @@ def decoder_mha_plan(dtype, batch, head_num, kv_head_num, head_size, max_seq_len
     return (t.decode() if t is not None else None), status.value
 
 
+def decoder_mha_window_plan(dtype, batch, head_num, kv_head_num, head_size, max_seq_len, window, sinks=0, step=-1, kv_e4m3=False,
+                            forms=(), max_pages=0, num_pages=0, residues=None, workspace_bytes="exact"):
+    """decoder_mha_plan for a sliding-window call (llmie_decoder_mha_window_plan): with window > 0 the line ends in " window W sinks
+    S live N" (host step: N live chunks = grid x) or "... live <=N" (device position: the bound the grid is launched with); window =
+    0 gives decoder_mha_plan's text.  No device needed."""
+    f = sum(ATTN_FORMS[n] for n in forms)
+    r = sum((v & 15) << (4 * ATTN_OPERANDS.index(k)) for k, v in (residues or {}).items())
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_decoder_mha_window_plan(dtype, int(kv_e4m3), batch, head_num, kv_head_num, head_size, max_seq_len, step, f,
+                                            max_pages, num_pages, r, -1 if workspace_bytes is None else workspace_bytes, window, sinks,
+                                            C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):
     """name of the launch sequence an engine of `cfg` (dict or DecoderConfig) plans for a decode step at `rows` sequences or
     (prefill=True) a prefill of `rows` tokens; None where the call is refused (llmie_last_error() says why).  No device needed."""
@@ -420,6 +442,35 @@ def decoder_mha_ragged(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv
                                           k_cache.shape[1] if block_table is not None else 0, _dt(qkv), _st()),
            "decoder_mha_ragged")
     return out
+
+
+def decoder_mha_window(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv_head_num, ctx_len, workspace, rope_table,
+                       rotary_dim, max_seq_len, window, sinks=0, block_table=None, tickets=None, kv_scales=None):
+    """decoder_mha_ragged under a sliding window of `window` tokens plus `sinks` sink tokens (window = 0: full attention).  tickets:
+    zeroed int32 [batch, kv_head_num] = in-launch merge.  kv_scales = (k_scale, v_scale): the caches are uint8 e4m3 bytes (fp16
+    activations).  Block-table entries of pages without a live key are never followed and may be -1."""
+    batch, hs = qkv.shape[0], qkv.shape[-1]
+    ks, vs = kv_scales if kv_scales is not None else (1.0, 1.0)
+    _check(lib().llmie_decoder_mha_window(_p(qkv), _p(qkv_bias), _p(k_cache), _p(v_cache), _p(out), layer, batch, head_num,
+                                          kv_head_num, hs, max_seq_len, _p(ctx_len), _p(workspace),
+                                          0 if workspace is None else workspace.numel() * workspace.element_size(), _p(rope_table),
+                                          rotary_dim, _p(block_table), block_table.shape[1] if block_table is not None else 0,
+                                          k_cache.shape[1] if block_table is not None else 0, window, sinks, _p(tickets),
+                                          int(kv_scales is not None), ks, vs, _dt(qkv), _st()), "decoder_mha_window")
+    return out
+
+
+def kv_window_advance(block_table, cached_len, window, sinks=0, new_tokens=None, status=None):
+    """llmie_kv_window_advance: the page ring of windowed sequences.  block_table int32 [batch, max_pages] (in/out, -1 = unmapped),
+    cached_len int32 [batch], new_tokens int32 [batch] or None (1 each); returns status int32 [batch] (0 ok, 1 no dead page:
+    the row is untouched, 2 positions past the table).  One launch, no host read: capturable."""
+    import torch
+    batch, max_pages = block_table.shape
+    if status is None:
+        status = torch.empty(batch, dtype=torch.int32, device=block_table.device)
+    _check(lib().llmie_kv_window_advance(_p(block_table), max_pages, _p(cached_len), _p(new_tokens), batch, window, sinks, _p(status),
+                                         _st()), "kv_window_advance")
+    return status
 
 
 def decoder_mha_rope(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv_head_num, step, workspace, rope_table,
@@ -846,6 +897,19 @@ class Decoder:
         self._lora_keep = (table, seq_slot, workspace)
         return workspace
 
+    def set_window(self, layer_window, sinks=0):
+        """sliding-window attention (llmie_decoder_set_window): layer_window = one window per layer (0 = full attention on that layer),
+        or one int for every layer, or None to clear; sinks = sink tokens of the windowed layers"""
+        if layer_window is None:
+            _check(lib().llmie_decoder_set_window(self.handle, None, sinks), "decoder_set_window")
+            return
+        L = self.cfg.num_layers
+        w = [int(layer_window)] * L if isinstance(layer_window, int) else [int(x) for x in layer_window]
+        if len(w) != L:
+            raise LlmieError("set_window: %d windows for %d layers" % (len(w), L))
+        arr = (C.c_int32 * L)(*w)
+        _check(lib().llmie_decoder_set_window(self.handle, C.addressof(arr), sinks), "decoder_set_window")
+
     def lora_detach(self):
         _check(lib().llmie_decoder_lora_detach(self.handle), "decoder_lora_detach")
         self._lora_keep = None
@@ -894,6 +958,7 @@ LORA_RANKS = (8, 16, 32, 64)
 LORA_MAX_SLOTS = 1024   # LLMIE_LORA_MAX_SLOTS
 LORA_MAX_KSPLIT = 8     # LLMIE_LORA_MAX_KSPLIT
 PLAN_LORA = 1024        # LLMIE_PLAN_LORA
+PLAN_WINDOW = 2048      # LLMIE_PLAN_WINDOW
 PLAN_PAGED, PLAN_RAGGED, PLAN_HIDDEN_MISALIGNED = 1, 2, 4   # LLMIE_PLAN_* call flags of decoder_plan_name
 
 

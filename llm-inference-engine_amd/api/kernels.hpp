@@ -368,6 +368,38 @@ inline void launchNgramDraft(TensorWrapper<int> *tokens, TensorWrapper<int> *len
                                  max_n, min_n, pad_id, out_ids->data, out_draft_ids->data, out_draft_len->data, llmie_api::st()));
 }
 
+// No reference launcher: decode attention of a ragged batch under a sliding window with sink tokens (include/llmie.h has the mask):
+// qkv_buf [batch, head_num + 2 kv_head_num, head_size] (bias: the QKV bias or null), ctx_len [batch] = context length of every
+// sequence with this step's token, caches [L, batch, kvh, max_seq_len, hs] -- or, with block_table [batch, max_pages], page pools
+// [L, num_pages, kvh, 128, hs] and max_seq_len given --, rope_table: [max_pos][hs / 2] (cos, sin) pairs or null (q, k rotated
+// already).  window = 0: full attention.  Appends k / v at ctx_len - 1 and attends; entries of dead pages are never followed.
+template <typename T>
+void launchDecoderWindowAttention(TensorWrapper<T> *qkv_buf, const T *qkv_bias, int layer, TensorWrapper<T> *k_cache, TensorWrapper<T> *v_cache,
+                                  TensorWrapper<int> *ctx_len, const void *rope_table, int rotary_dim, TensorWrapper<int> *block_table,
+                                  int max_seq_len, int window, int sinks, TensorWrapper<T> *mha_output) {
+    const int batch = qkv_buf->shape[0], qkv_head_num = qkv_buf->shape[1], head_size = qkv_buf->shape[2];
+    const int kv_head_num = k_cache->shape[2];
+    const int head_num = qkv_head_num - 2 * kv_head_num;
+    if (!block_table) max_seq_len = k_cache->shape[3];
+    const size_t ws = llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len);
+    LLMIE_CALL(llmie_decoder_mha_window(qkv_buf->data, qkv_bias, k_cache->data, v_cache->data, mha_output->data, layer, batch, head_num,
+                                        kv_head_num, head_size, max_seq_len, ctx_len->data, llmie_api::scratch(ws), ws, rope_table, rotary_dim,
+                                        block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                        block_table ? k_cache->shape[1] : 0, window, sinks, nullptr, 0, 1.f, 1.f, llmie_api::dtype_of<T>(),
+                                        llmie_api::st()));
+}
+
+// No reference launcher: the page ring of windowed sequences (include/llmie.h llmie_kv_window_advance).  block_table [batch,
+// max_pages] (in / out, -1 = unmapped), cached_len [batch], new_tokens [batch] or null (one each), status [batch] (0 mapped, 1 no
+// dead page: the row is untouched, 2 past the table).  One launch, nothing read by the host.
+inline void launchKvWindowAdvance(TensorWrapper<int> *block_table, TensorWrapper<int> *cached_len, TensorWrapper<int> *new_tokens, int window,
+                                  int sinks, TensorWrapper<int> *status) {
+    const int batch = block_table->shape[0];
+    LLM_CHECK_WITH_INFO(cached_len->shape[0] == batch && status->shape[0] == batch, "cached_len and status should be [batch]");
+    LLMIE_CALL(llmie_kv_window_advance(block_table->data, block_table->shape[1], cached_len->data, new_tokens ? new_tokens->data : nullptr, batch,
+                                       window, sinks, status->data, llmie_api::st()));
+}
+
 // No reference launcher: per-row LoRA adapters on top of a projection (include/llmie.h has the semantics).  x [rows, K], y [rows, N]
 // (updated in place), slot [rows] (-1: no adapter); table: the device slot table (llmie_lora_table_bytes / llmie_lora_slot_load) of
 // `slots` slots and `layers` layers; block_widths: the column blocks of y (q / k / v, gate / up; one block otherwise).  Plans the

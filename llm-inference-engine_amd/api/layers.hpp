@@ -79,7 +79,23 @@ public:
         lora_dirty = true;
     }
 
+    // Sliding-window attention (include/llmie.h llmie_decoder_set_window): one window per layer (0 = full attention; empty: none) and
+    // the sink tokens, set on every engine this holder creates
+    void set_window(const std::vector<int> &layer_window, int sinks) {
+        window = layer_window, window_sinks = sinks;
+        window_dirty = true;
+    }
+
 private:
+    std::vector<int> window;
+    int window_sinks = 0;
+    bool window_dirty = false;
+    void sync_window() {
+        if (!engine || !window_dirty) return;
+        LLM_CHECK_WITH_INFO(window.empty() || static_cast<int>(window.size()) == made.num_layers, "one window per layer");
+        LLMIE_CALL(llmie_decoder_set_window(engine, window.empty() ? nullptr : window.data(), window.empty() ? 0 : window_sinks));
+        window_dirty = false;
+    }
     LoraBinding lora;
     bool lora_dirty = false;
     void *lora_ws = nullptr;
@@ -126,6 +142,7 @@ public:
                        int inter_size, const LlamaAttentionStaticParams &sp, float eps, int batch, int max_seq_len) {
         if (engine && key == lw->data() && batch <= batch_cap && max_seq_len == max_seq) {
             sync_lora();
+            sync_window();
             return engine;
         }
         destroy();
@@ -165,6 +182,8 @@ public:
         made = cfg;
         lora_dirty = lora.table != nullptr;
         sync_lora();
+        window_dirty = !window.empty();
+        sync_window();
         return engine;
     }
     void *prefill_workspace(const llmie_decoder_config *cfg, int tokens, int batch, size_t *bytes) {
@@ -340,6 +359,8 @@ public:
     bool use_fused_engine = true;
     // per-request adapters on the fused engine (the per-kernel loop knows none)
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
+    // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
+    void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
 
     // self_decoder.cpp:24-122
     void forward(TensorMap *input_tensors, std::vector<LlamaLayerWeight<T> *> *layer_weights, TensorMap *output_tensors,
@@ -511,6 +532,8 @@ public:
     bool use_fused_engine = true;
     // per-request adapters on the fused engine (the reference's kernel sequence knows none)
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
+    // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
+    void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
 
     LlamaContextDecoder(const int &head_num, const int &kv_head_num, const int &head_size, const int &intermediate_size,
                         const int &num_layer, LlamaAttentionStaticParams *const &attention_static_params,

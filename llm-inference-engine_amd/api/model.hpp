@@ -259,6 +259,19 @@ public:
         CHECK(hipMemcpyAsync(d_lora_slot.p, &slot, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
         CHECK(hipStreamSynchronize(llmie_api::st()));   // (`slot` lives on this frame)
     }
+    // Sliding-window attention with sink tokens (include/llmie.h llmie_decoder_set_window): layer_window[l] tokens on layer l (0 keeps
+    // that layer global), `sinks` sink tokens on the windowed layers; an empty vector goes back to full attention.  Takes effect from
+    // the next prefill / decode call of both decoders.  The windowed kernels live in the fused engine, and a model that runs the
+    // per-kernel loops must not take a window and then attend to everything.
+    void setAttentionWindow(const std::vector<int> &layer_window, int sinks = 0) {
+        LLM_CHECK_WITH_INFO(layer_window.empty() || static_cast<int>(layer_window.size()) == num_layers, "setAttentionWindow: one window per layer");
+        LLM_CHECK_WITH_INFO(layer_window.empty() || ((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs)),
+                            "setAttentionWindow: a window needs the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        for (int w : layer_window) LLM_CHECK_WITH_INFO(w >= 0, "setAttentionWindow: negative window");
+        LLM_CHECK_WITH_INFO(sinks >= 0, "setAttentionWindow: negative sinks");
+        context_decoder->setWindow(layer_window, layer_window.empty() ? 0 : sinks);
+        self_decoder->setWindow(layer_window, layer_window.empty() ? 0 : sinks);
+    }
     // the last step of the SamplingConfig path: the top_logprobs most likely tokens of the raw row (id -1 / -INFINITY past the
     // row's valid tokens) and the picked token's raw log-probability
     const std::vector<int> &lastTopIds() const { return last_top_ids; }

@@ -15,6 +15,7 @@
 // HBM-bound: algorithmic bytes = 2 * step * kvh * hs * sizeof(T) per sequence.
 #include "llmie_internal.h"
 
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
@@ -84,6 +85,37 @@ template <typename KT, int HS, int NWV = 4, int GL = 8> struct AttnGeom {
 };
 
 __host__ __device__ inline int attn_min_chunk() { return 32; }
+
+// Sliding window with sink tokens (include/llmie.h): the query at step - 1 sees key j iff j < step and (j >= step - window or
+// j < sinks); window <= 0 is full attention.  Chunks of `chunk` tokens stay aligned to token 0; the LIVE chunks of a sequence --
+// those that hold a visible key -- are the sink chunks [0, ceil(min(sinks, step) / chunk)), then the chunks from
+// floor(max(0, step - window) / chunk) to the last; a chunk of both lists counts once.  The split kernel's grid x, its partial
+// slots, the merge (kernel or ticket) and the host planner all index the live chunks compactly through this one mapping, so the
+// slot count, `nsplits` and the ticket count agree by construction.  A window that covers the context gives the unwindowed walk.
+struct AttnLive {
+    int sink_chunks;   // live chunks in front of `first` (0 when the two lists meet or overlap)
+    int first;         // first chunk of the window's list
+    int total;         // live chunks
+};
+__host__ __device__ inline AttnLive attn_live_chunks(int step, int window, int sinks, int chunk) {
+    const int n = (step + chunk - 1) / chunk;
+    if (window <= 0 || window >= step) return AttnLive{0, 0, n};
+    const int first = (step - window) / chunk;
+    const int s = sinks < step ? (sinks > 0 ? sinks : 0) : step;
+    const int ns = (s + chunk - 1) / chunk;
+    if (ns >= first) return AttnLive{0, 0, n};   // the lists meet or overlap: one run from chunk 0
+    return AttnLive{ns, first, ns + n - first};
+}
+// chunk of live index i (< total); its first token is this times the chunk length
+__host__ __device__ inline int attn_live_chunk(const AttnLive &lv, int i) { return i < lv.sink_chunks ? i : lv.first + (i - lv.sink_chunks); }
+// grid x of a call whose position the host does not know: no context has more live chunks than this
+__host__ __device__ inline int attn_live_bound(int max_seq_len, int window, int sinks, int chunk) {
+    const int n = (max_seq_len + chunk - 1) / chunk;
+    if (window <= 0) return n;
+    const long long s = sinks > 0 ? sinks : 0, w = window;
+    const long long b = (s + chunk - 1) / chunk + (w + chunk - 1) / chunk + 1;
+    return b < n ? static_cast<int>(b) : n;
+}
 
 // q/k/v source when the QKV projection's split-K finalize is fused into the attention: fp32 slabs [KS][batch][qkv_dim]
 struct QkvSlabs {
@@ -160,7 +192,11 @@ __device__ __forceinline__ float merge_splits(const float *__restrict__ p, int n
     return o / (L + 1e-6f);
 }
 
-template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T>
+// WIN (compile time) selects the sliding-window form: the workgroup's chunk comes from the live-chunk mapping, a row is masked from
+// below as well as from above, and no load goes through the block-table entry of a page without a live row.  Its two launch
+// arguments (window, sinks) are the pack WinArgs = (int, int); WIN = false has an empty pack: the arguments and the code the kernel
+// had before there was a window.
+template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T, bool WIN = false, typename... WinArgs>
 __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const T *__restrict__ qkv, const T *__restrict__ qkv_bias, KT *k_cache, KT *v_cache,
     float *__restrict__ part, T *__restrict__ out, int head_num, int kv_head_num, int max_seq_len,
@@ -171,7 +207,9 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const float k_scale, const float v_scale /* fp8 cache: stored = e4m3(x / scale); 1 otherwise */,
     const PagedKv pg /* pg.table != null: k_cache / v_cache are this layer's page pools */,
     const int cpw /* chunks of CHUNK tokens one workgroup walks through (online softmax across them): large batches amortise
-                     the per-workgroup prologue / merge (~550 of ~1000 VALU instructions per wave at one chunk) */) {
+                     the per-workgroup prologue / merge (~550 of ~1000 VALU instructions per wave at one chunk) */,
+    const WinArgs... win /* WIN: window, sinks -- the query sees key j iff j >= step - window or j < sinks (and j < step) */) {
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
     using G = AttnGeom<KT, HS, kAttnWaves, kAttnG>;
     using V = typename CacheVec<KT>::type;  // one 16-byte vector of cache elements
     constexpr int N = G::N, LPT = G::LPT, TPW = G::TPW, CHUNK = G::CHUNK;
@@ -182,11 +220,29 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const int split = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
     const int step = seq_step(step_dev, step_arg, pg.step_stride, b, max_seq_len);
     const int span = cpw * CHUNK;   // tokens of one workgroup
-    const int t0 = split * span;
+    // WIN: blockIdx.x counts the sequence's LIVE spans; t_lo = first token of the window, s_eff = its sink tokens
+    int t0w = split * span, nsw = 0, t_lo = 0, s_eff = 0;
+    if constexpr (WIN) {
+        const int wa[2] = {win...};
+        const int window = wa[0], sinks = wa[1];
+        const AttnLive lv = attn_live_chunks(step, window, sinks, span);
+        if (split >= lv.total) return;   // (also: invalid position, total = 0)
+        t0w = attn_live_chunk(lv, split) * span;
+        nsw = lv.total;
+        t_lo = (window > 0 && window < step) ? step - window : 0;
+        s_eff = max(0, min(sinks, step));
+    }
+    const int t0 = t0w;
     if (t0 >= step) return;  // whole workgroup exits together (also: invalid position)
     int tc0 = t0;                             // first token of the chunk being processed
+    if constexpr (WIN) {
+        if (t0 >= s_eff) tc0 = max(t0, t_lo / CHUNK * CHUNK);   // cpw > 1: the span's first live chunk
+    }
     int t_end = min(step, tc0 + CHUNK);       // end of that chunk
-    const int nsplits = (step + span - 1) / span;
+    const int nsplits = WIN ? nsw : (step + span - 1) / span;
+    // WIN: is row t of the current chunk visible / does the chunk at tc (< step) hold a visible row
+    auto row_live = [&](int t) { return t < t_end && (!WIN || t >= t_lo || t < s_eff); };
+    auto chunk_live = [&](int tc) { return tc < s_eff || tc + CHUNK > t_lo; };
     const int batch = gridDim.z;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -205,8 +261,22 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     KT *kbase[NPG], *vbase[NPG];
     auto set_pages = [&]() {   // of the chunk at tc0
         pg0 = tc0 / KV_PAGE;
+        // WIN, chunks of several pages: a page without a visible row (before the window and past the sinks, or past the context)
+        // may be unmapped, so its slot takes the base of the chunk's first page that has one and no load goes through its entry
+        auto page_live = [&](int j) {
+            const int a = (pg0 + j) * KV_PAGE;
+            return a < t_end && (a < s_eff || min(a + KV_PAGE, t_end) > t_lo);
+        };
+        int jl = 0;
+        if constexpr (WIN && NPG > 1) {
 #pragma unroll
-        for (int j = 0; j < NPG; ++j) {
+            for (int j = NPG - 1; j >= 0; --j)
+                if (page_live(j)) jl = j;
+        }
+#pragma unroll
+        for (int j0 = 0; j0 < NPG; ++j0) {
+            int j = j0;
+            if constexpr (WIN && NPG > 1) j = page_live(j0) ? j0 : jl;
             size_t off;
             if (pg.table) {
                 const int page = pg.table[static_cast<size_t>(b) * pg.max_pages + min(pg0 + j, pg.max_pages - 1)];
@@ -214,8 +284,8 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
             } else {
                 off = (static_cast<size_t>(b) * kv_head_num + g) * max_seq_len * HS + static_cast<size_t>(pg0 + j) * KV_PAGE * HS;
             }
-            kbase[j] = k_cache + off;
-            vbase[j] = v_cache + off;
+            kbase[j0] = k_cache + off;
+            vbase[j0] = v_cache + off;
         }
     };
     set_pages();
@@ -285,17 +355,24 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     V kv[kAttnG], vv[kAttnG];
     int tok[kAttnG];
     auto issue_loads = [&]() {   // of the chunk at tc0 (pages set)
+        // WIN: a masked row -- past the chunk end, or between the sinks and the window -- re-reads one visible row of the chunk (the
+        // window's first row there, else the chunk's first row, a sink), so the clamp holds from below as from above
+        const int t_fb = (tc0 + CHUNK > t_lo) ? max(tc0, t_lo) : tc0;
 #pragma unroll
         for (int i = 0; i < kAttnG; ++i) {
             const int t = tc0 + (wave * kAttnG + i) * TPW + sub;
             tok[i] = t;
-            // rows past the chunk end re-read its last row (masked below); the slot of this step's token is read as it is
-            // (stale, replaced below): every load is unconditional so all 2*G of them are in flight together
-            kv[i] = load_nt(reinterpret_cast<const V *>(krow(min(t, t_end - 1))) + dl);
+            // unwindowed: rows past the chunk end re-read its last row (masked below); WIN: every masked row, those past the chunk
+            // end included, re-reads t_fb.  The slot of this step's token is read as it is (stale, replaced below): every load is
+            // unconditional so all 2*G of them are in flight together
+            if constexpr (WIN) kv[i] = load_nt(reinterpret_cast<const V *>(krow(row_live(t) ? t : t_fb)) + dl);
+            else kv[i] = load_nt(reinterpret_cast<const V *>(krow(min(t, t_end - 1))) + dl);
         }
 #pragma unroll
-        for (int i = 0; i < kAttnG; ++i)
-            vv[i] = load_nt(reinterpret_cast<const V *>(vrow(min(tok[i], t_end - 1))) + dl);
+        for (int i = 0; i < kAttnG; ++i) {
+            if constexpr (WIN) vv[i] = load_nt(reinterpret_cast<const V *>(vrow(row_live(tok[i]) ? tok[i] : t_fb)) + dl);
+            else vv[i] = load_nt(reinterpret_cast<const V *>(vrow(min(tok[i], t_end - 1))) + dl);
+        }
     };
     issue_loads();
     if (qs.slab) {
@@ -448,7 +525,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     for (int r = 0; r < REP; ++r) cm[r] = -INFINITY;
 #pragma unroll
     for (int i = 0; i < kAttnG; ++i) {
-        const bool valid = tok[i] < t_end;
+        const bool valid = row_live(tok[i]);
         float kf[FP8KV ? 1 : N];
         half2_t kh[FP8KV ? N / 2 : 1];
         if constexpr (FP8KV) {
@@ -496,7 +573,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     // ---- softmax numerators and P.V ----
 #pragma unroll
     for (int i = 0; i < kAttnG; ++i) {
-        const bool valid = tok[i] < t_end;
+        const bool valid = row_live(tok[i]);
         if (valid) {
             float vf[N];
             kv_to_f32<KT, N>(vv[i], vf);
@@ -519,6 +596,10 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
         for (int c = 1; c < cpw; ++c) {
             tc0 += CHUNK;
             if (tc0 >= step) break;   // workgroup-uniform
+            if constexpr (WIN) {      // (the span's first live chunk may lie past its start; a chunk between sinks and window is skipped)
+                if (tc0 >= t0 + span) break;
+                if (!chunk_live(tc0)) continue;
+            }
             t_end = min(step, tc0 + CHUNK);
             set_pages();
             issue_loads();
@@ -613,12 +694,15 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
 // merge the per-split partials: grid (head_num, batch), one thread per output dim.  Every thread reads the
 // (m, l) pairs itself (broadcast loads) and its own o values, 16 splits per round with all loads issued before
 // the first use, so the kernel is about one L2 round trip per 16 splits -- no LDS, no barrier.
-template <typename T>
+// WIN: the partial slots are the live chunks of the window (attn_live_chunks), as the split kernel filled them.
+template <typename T, bool WIN = false, typename... WinArgs>
 __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float *__restrict__ part,
                                                                   T *__restrict__ out, int head_num,
                                                                   int head_size, int chunk, int step_arg,
                                                                   const int32_t *__restrict__ step_dev,
-                                                                  int max_splits, int step_stride, int max_seq_len, int out_x32) {
+                                                                  int max_splits, int step_stride, int max_seq_len, int out_x32,
+                                                                  const WinArgs... win /* WIN: window, sinks */) {
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
     const int h = blockIdx.x, b = blockIdx.y;
     const size_t stride = static_cast<size_t>(head_size) + 2;
     const float *p = part + (static_cast<size_t>(b) * head_num + h) * max_splits * stride;
@@ -629,7 +713,11 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float *_
     float ms[16], ls[16], os[16];
     merge_load(p, 0, max_splits - 1, stride, min(d, head_size - 1), ms, ls, os);
     const int step = seq_step(step_dev, step_arg, step_stride, b, max_seq_len);
-    const int nsplits = (step + chunk - 1) / chunk;
+    int nsplits = (step + chunk - 1) / chunk;
+    if constexpr (WIN) {
+        const int wa[2] = {win...};
+        nsplits = attn_live_chunks(step, wa[0], wa[1], chunk).total;
+    }
     if (nsplits <= 1) return;  // the split kernel already wrote the final output (or: invalid position)
     if (d < head_size) {
         float M = -INFINITY, L = 0.f, o = 0.f;
@@ -740,6 +828,10 @@ static DecodeAttnPlan plan_attn_split(const DecodeAttnCall &c, size_t need) {
     const int base = c.kv_e4m3 ? attn_chunk<fp8kv_t>(p.hs) : (c.dtype == LLMIE_F32 ? attn_chunk<float>(p.hs) : attn_chunk<half_t>(p.hs));
     p.chunk = p.cpw * base;
     p.grid[0] = (bound + p.chunk - 1) / p.chunk, p.grid[1] = c.kv_head_num, p.grid[2] = c.batch;
+    if (c.window > 0) {   // grid x = live spans: known from a host step, bounded by the window (not by max_seq_len) otherwise
+        p.window = c.window, p.sinks = c.sinks;
+        p.grid[0] = c.step_dev ? attn_live_bound(c.max_seq_len, c.window, c.sinks, p.chunk) : attn_live_chunks(c.step, c.window, c.sinks, p.chunk).total;
+    }
     p.max_splits_ws = (c.max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
     p.merge = p.grid[0] > 1 && !c.tickets;
     p.merge_grid[0] = c.head_num, p.merge_grid[1] = c.batch;
@@ -758,6 +850,8 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
     const bool aligned = !(c.mis_qkv | c.mis_k | c.mis_v | c.mis_bias);
     const size_t need = llmie_decoder_mha_workspace_bytes(c.batch, c.head_num, c.head_size, c.max_seq_len);
     const bool ws_ok = c.workspace && c.workspace_bytes >= need;
+    // a window runs on the split kernel's windowed instantiations only: fp16 activations, head size 64 / 128 (ratios as below)
+    if (c.window > 0 && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128))) return attn_refusal(DAREF_WINDOW);
     if (c.kv_e4m3) {
         // fp16 activations over e4m3 cache bytes: 16 cache elements per 16-byte load (8 lanes per token row at head size 128,
         // 256-token chunks); head ratio 8 does not fit registers (16 dims per lane x 8 heads); no generic form, and one refusal
@@ -773,6 +867,7 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
     const bool geometry = attn_fused_geometry(c);
     if (aligned && c.batch <= 65535 && c.kv_head_num <= 65535 && geometry)
         return ws_ok ? plan_attn_split(c, need) : attn_refusal(DAREF_WORKSPACE, need);
+    if (c.window > 0) return attn_refusal(DAREF_WINDOW);   // the generic kernel attends to everything
     if (c.paged) return attn_refusal(DAREF_PAGED_GEOMETRY);
     if (c.slabs) return attn_refusal(DAREF_SLABS_GEOMETRY);
     // (tickets on a supported geometry that fell through -- unaligned -- are ignored: the generic kernel has no partials)
@@ -804,6 +899,10 @@ int decode_attn_refuse(const DecodeAttnCall &c, const DecodeAttnPlan &p) {
         case DAREF_SLABS_GEOMETRY: set_error("decoder_mha: q/k/v from split-K slabs needs %s", fused); break;
         case DAREF_ROPE_GEOMETRY: set_error("decoder_mha: fused RoPE / in-launch merge need %s", fused); break;
         case DAREF_RAGGED_GEOMETRY: set_error("decoder_mha: ragged batches / x32 output need %s", fused); break;
+        case DAREF_WINDOW:
+            set_error("decoder_mha: a sliding window needs fp16 activations, head_size 64/128, head_num/kv_head_num in {1,2,4,8} (e4m3 cache: "
+                      "{1,2,4}) and 16-byte aligned buffers (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
+            break;
         case DAREF_GENERIC_SPAN:
             set_error("decoder_mha: generic path supports at most 15360 tokens (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
             break;
@@ -828,6 +927,20 @@ struct DecodeAttnArgs {
 };
 
 template <typename T, int HS, int REP, typename KT> static void launch_split(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
+    // the windowed instantiations: fp16 activations, head size 64 / 128 (what plan_decode_attn plans with a window)
+    if constexpr (std::is_same<T, half_t>::value && (HS == 64 || HS == 128)) {
+        if (p.window > 0) {
+            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, true, int, int><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+                static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
+                static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
+                a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, p.window, p.sinks);
+            if (p.merge)
+                decode_attn_combine_kernel<T, true, int, int><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
+                    a.part, static_cast<T *>(a.out), a.head_num, HS, p.chunk, a.step, a.step_dev, p.max_splits_ws, a.pg.step_stride,
+                    a.max_seq_len, a.pg.out_x32, p.window, p.sinks);
+            return;
+        }
+    }
     decode_attn_split_kernel<T, HS, REP, 4, 8, KT><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
         static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
         static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim, a.tickets,
@@ -904,6 +1017,7 @@ static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAtt
         c.slab_stride_mod4 = static_cast<unsigned>(a.qs.stride % 4);
     }
     c.workspace = io.workspace != nullptr, c.workspace_bytes = io.workspace_bytes;
+    c.window = io.window > 0 ? io.window : 0, c.sinks = io.window > 0 ? io.sinks : 0;
     return c;
 }
 
@@ -926,6 +1040,11 @@ static int decode_attn_validate(const char *who, const DecodeAttnShape &g, const
     if (g.dtype != LLMIE_F32 && g.dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: dtype %d", who, (int)g.dtype);
     return LLMIE_OK;
 }
+// the window of a call: window >= 0 (0 = full attention: the sinks are then ignored), sinks >= 0
+static int decode_attn_validate_window(const char *who, int window, int sinks) {
+    LLMIE_REQUIRE(window >= 0 && sinks >= 0, "%s: window %d / sinks %d must not be negative", who, window, sinks);
+    return LLMIE_OK;
+}
 // a public entry: validate, then as the engine's calls
 static int decode_attn_entry(const char *who, const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer,
                              llmie_stream stream) {
@@ -934,7 +1053,7 @@ static int decode_attn_entry(const char *who, const DecodeAttnShape &g, const De
 }
 
 // "split f16 hs128 rep4 kv=e4m3 cpw2 chunk512 grid 4x8x16 merge 32x16/128" (merge: grid / block, "in-launch" by tickets, "none"
-// for one split) or "generic f16 grid 32x2 lds 1028"
+// for one split) or "generic f16 grid 32x2 lds 1028"; a window adds " window 4096 sinks 4 live <=34"
 static void decode_attn_plan_text(const DecodeAttnCall &c, const DecodeAttnPlan &p, char *text, size_t n) {
     const char *dt = c.dtype == LLMIE_F32 ? "f32" : "f16";
     if (p.kind == DA_GENERIC) {
@@ -943,8 +1062,52 @@ static void decode_attn_plan_text(const DecodeAttnCall &c, const DecodeAttnPlan 
     }
     const int k = snprintf(text, n, "split %s hs%d rep%d kv=%s cpw%d chunk%d grid %dx%dx%d merge ", dt, p.hs, p.rep, p.e4m3 ? "e4m3" : dt, p.cpw,
                            p.chunk, p.grid[0], p.grid[1], p.grid[2]);
-    if (p.merge) snprintf(text + k, n - k, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
-    else snprintf(text + k, n - k, "%s", p.grid[0] > 1 ? "in-launch" : "none");
+    int m;
+    if (p.merge) m = snprintf(text + k, n - k, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
+    else m = snprintf(text + k, n - k, "%s", p.grid[0] > 1 ? "in-launch" : "none");
+    // a windowed call (no window: the line above, unchanged): the mask and what grid x counts -- the live spans of the host step, or
+    // their bound for any position
+    if (p.window > 0) snprintf(text + k + m, n - k - m, " window %d sinks %d live %s%d", p.window, p.sinks, c.step_dev ? "<=" : "", p.grid[0]);
+}
+
+// The page ring of a windowed sequence (llmie_kv_window_advance): one thread per sequence.  The logical pages the positions
+// [cached, cached + n) need and that are unmapped (-1) take the pool pages of the lowest mapped logical pages that lie wholly at or
+// above the sink pages and wholly below cached + 1 - window (dead for this and every later query); all of them or none.
+__global__ __launch_bounds__(64) void kv_window_advance_kernel(int32_t *__restrict__ table, int max_pages, const int32_t *__restrict__ cached_len,
+                                                               const int32_t *__restrict__ new_tokens, int batch, int window, int sinks,
+                                                               int32_t *__restrict__ status) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    int32_t *row = table + static_cast<size_t>(b) * max_pages;
+    const int cached = cached_len[b], n = new_tokens ? new_tokens[b] : 1;
+    if (n <= 0) {
+        status[b] = 0;
+        return;
+    }
+    if (cached < 0 || static_cast<long long>(cached) + n > static_cast<long long>(max_pages) * KV_PAGE) {
+        status[b] = 2;   // the positions do not fit the table row
+        return;
+    }
+    const int p0 = cached / KV_PAGE, p1 = (cached + n - 1) / KV_PAGE;
+    const int lo = min((sinks + KV_PAGE - 1) / KV_PAGE, max_pages);                  // first page without a sink token
+    const long long dead_end = static_cast<long long>(cached) + 1 - window;         // tokens below are dead
+    const int hi = dead_end > 0 ? static_cast<int>(min(static_cast<long long>(p0), dead_end / KV_PAGE)) : 0;   // pages [lo, hi) are dead
+    int need = 0, have = 0;
+    for (int p = p0; p <= p1; ++p) need += row[p] < 0;
+    for (int p = lo; p < hi; ++p) have += row[p] >= 0;
+    if (have < need) {
+        status[b] = 1;   // the caller must supply a page; the row is as it was
+        return;
+    }
+    int d = lo;
+    for (int p = p0; p <= p1; ++p) {
+        if (row[p] >= 0) continue;
+        while (row[d] < 0) ++d;   // (have >= need: stops below hi)
+        row[p] = row[d];
+        row[d] = -1;
+        ++d;
+    }
+    status[b] = 0;
 }
 
 }  // namespace llmie
@@ -991,15 +1154,16 @@ extern "C" int llmie_decoder_mha_ragged(const void *qkv, const void *qkv_bias, v
                              stream);
 }
 
-extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
-                                              int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
-                                              unsigned long long residues, long long workspace_bytes, int *status) {
-    static thread_local char text[96];
+static const char *decode_attn_plan_query(const char *who, llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                          int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                          unsigned long long residues, long long workspace_bytes, int window, int sinks, int *status) {
+    static thread_local char text[160];
     static const int32_t some_position = 0;   // stands for the device position: never read
     auto res = [&](int i) { return static_cast<unsigned>((residues >> (4 * i)) & 15u); };
     const DecodeAttnShape g{batch, head_num, kv_head_num, head_size, max_seq_len, dtype};
     const DecodePos pos{step, (forms & LLMIE_ATTN_STEP_DEV) ? &some_position : nullptr, (forms & LLMIE_ATTN_RAGGED) != 0};
-    int rc = decode_attn_validate("decoder_mha_plan", g, pos, true, 0, (forms & LLMIE_ATTN_ROPE) != 0, 2);
+    int rc = decode_attn_validate(who, g, pos, true, 0, (forms & LLMIE_ATTN_ROPE) != 0, 2);
+    if (rc == LLMIE_OK) rc = decode_attn_validate_window(who, window, sinks);
     if (rc == LLMIE_OK) {
         DecodeAttnCall c{};
         c.dtype = dtype, c.kv_e4m3 = kv_e4m3 != 0, c.scales_positive = !(forms & LLMIE_ATTN_BAD_SCALES);
@@ -1011,10 +1175,55 @@ extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, in
         c.mis_qkv = res(0), c.mis_bias = c.bias ? res(1) : 0, c.mis_k = res(2), c.mis_v = res(3);
         if (c.slabs) c.mis_slab = res(4), c.mis_wf = res(5), c.mis_wh8 = res(6) % 8, c.slab_stride_mod4 = res(7) % 4;
         c.workspace = workspace_bytes >= 0, c.workspace_bytes = c.workspace ? static_cast<size_t>(workspace_bytes) : 0;
+        c.window = window, c.sinks = window > 0 ? sinks : 0;
         const DecodeAttnPlan p = plan_decode_attn(c);
         if (p.kind == DA_REFUSED) rc = decode_attn_refuse(c, p);
         else decode_attn_plan_text(c, p, text, sizeof(text));
     }
     if (status) *status = rc;
     return rc == LLMIE_OK ? text : nullptr;
+}
+
+extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                              int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                              unsigned long long residues, long long workspace_bytes, int *status) {
+    return decode_attn_plan_query("decoder_mha_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step, forms,
+                                  max_pages, num_pages, residues, workspace_bytes, 0, 0, status);
+}
+
+extern "C" const char *llmie_decoder_mha_window_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                                     int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                                     unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                                     int *status) {
+    return decode_attn_plan_query("decoder_mha_window_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
+                                  forms, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
+}
+
+// Sliding-window decode attention on the operands of llmie_decoder_mha_ragged (+ tickets and the e4m3 cache, which the engine's calls
+// use): the windowed split kernel without an engine around it.  window = 0: full attention, the call llmie_decoder_mha_ragged makes.
+extern "C" int llmie_decoder_mha_window(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer,
+                                        int batch, int head_num, int kv_head_num, int head_size, int max_seq_len,
+                                        const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
+                                        int rotary_dim, const int32_t *block_table, int max_pages, int num_pages, int window, int sinks,
+                                        int32_t *tickets, int kv_e4m3, float k_scale, float v_scale, llmie_dtype dtype,
+                                        llmie_stream stream) {
+    const int rc = decode_attn_validate_window("decoder_mha_window", window, sinks);
+    if (rc != LLMIE_OK) return rc;
+    return decode_attn_entry("decoder_mha_window", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim,
+                                          tickets, nullptr, nullptr, 0, window, sinks},
+                             KvView{k_cache, v_cache, block_table, max_pages, num_pages, kv_e4m3 ? 1 : 0, kv_e4m3 ? k_scale : 1.f,
+                                    kv_e4m3 ? v_scale : 1.f},
+                             DecodePos{-1, ctx_len_dev, 1}, layer, stream);
+}
+
+extern "C" int llmie_kv_window_advance(int32_t *block_table, int max_pages, const int32_t *cached_len, const int32_t *new_tokens, int batch,
+                                       int window, int sinks, int32_t *status, llmie_stream stream) {
+    LLMIE_REQUIRE(block_table && cached_len && status, "kv_window_advance: NULL pointer");
+    LLMIE_REQUIRE(batch > 0 && max_pages > 0, "kv_window_advance: bad shape");
+    LLMIE_REQUIRE(static_cast<long long>(max_pages) * KV_PAGE <= INT_MAX, "kv_window_advance: max_pages %d too large", max_pages);
+    LLMIE_REQUIRE(window >= 1 && sinks >= 0, "kv_window_advance: needs window >= 1 and sinks >= 0 (window %d, sinks %d)", window, sinks);
+    kv_window_advance_kernel<<<(batch + 63) / 64, 64, 0, as_stream(stream)>>>(block_table, max_pages, cached_len, new_tokens, batch, window,
+                                                                              sinks, status);
+    return launch_status("kv_window_advance");
 }

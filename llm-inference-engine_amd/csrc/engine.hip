@@ -60,6 +60,11 @@ struct llmie_decoder {
         void *ws = nullptr;
         size_t ws_bytes = 0;
     } lora;
+    // sliding-window attention (llmie_decoder_set_window): the window of every layer (0 = full attention; empty: none set) and the
+    // sink tokens; read where a call's attention launches are planned
+    std::vector<int> layer_window;
+    int sinks = 0;
+    int window_of(int layer) const { return layer_window.empty() ? 0 : layer_window[layer]; }
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -619,6 +624,15 @@ static bool lora_engine_ok(const llmie_decoder_config &c) {
            !(c.flags & LLMIE_DEC_PACKED_ONLY) && H % 32 == 0 &&
            c.inter_size % 32 == 0 && (c.kv_head_num * c.head_size) % 16 == 0;
 }
+// what a sliding window needs of an engine: the windowed instantiations of the decode split kernel (attention_decode.hip; the flash
+// prefill kernel has them for every engine it runs on)
+static bool window_engine_ok(const llmie_decoder_config &c) {
+    const int rep = c.head_num / c.kv_head_num;
+    return c.dtype == LLMIE_F16 && (c.head_size == 64 || c.head_size == 128) &&
+           (rep == 1 || rep == 2 || rep == 4 || (rep == 8 && c.kv_fmt != LLMIE_KV_FP8));
+}
+static const char *const kWindowRefusal =
+    "a sliding window needs an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
 static const char *const kLoraRefusal =
     "adapters need an fp16 engine with fp16 / int8 / int4 weights (an fp8-weight engine never materialises fp16 normalised rows, a "
     "LLMIE_DEC_PACKED_ONLY engine has no row-major route), hidden and inter sizes that are multiples of 32 and q / kv widths that are "
@@ -873,6 +887,10 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
         return nullptr;
     }
     const EngineSwitches sw = switches_of_mask(switch_mask);
+    if ((call_flags & LLMIE_PLAN_WINDOW) && !window_engine_ok(*cfg)) {
+        set_error("decoder_plan_name: %s", kWindowRefusal);
+        return nullptr;
+    }
     if (prefill) {
         if (rows < 1) {
             set_error("decoder_plan_name: %d tokens", rows);
@@ -922,7 +940,7 @@ struct DecodeStep {
                   const SlabScale *qkv_scale = nullptr, int out_x32 = 0, bool rope = true) const {
         return decoder_mha_rope(DecodeAttnShape{batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, dt},
                                 DecodeAttnIo{qkv, qkv_bias, out, dec->attn_ws, dec->attn_ws_bytes, rope ? dec->rope_table : nullptr,
-                                             rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32},
+                                             rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32, dec->window_of(layer), dec->sinks},
                                 kv, pos, layer, st);
     }
 
@@ -1427,7 +1445,9 @@ struct PrefillPass {
         }
     }
     int attention(int l, const llmie_matrix &wqkv, const PrefillLayerPlan &lp) const {
-        return prefill_attention_f16(lp.attn, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
+        PrefillAttnPlan ap = lp.attn;   // (the layer plan is per pass; the window is per layer)
+        ap.window = dec->window_of(l), ap.sinks = ap.window > 0 ? dec->sinks : 0;
+        return prefill_attention_f16(ap, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
                                      c.max_seq_len, c.rotary_dim, st);
     }
     // act = swiglu(x . Wgu^T) of the lean and general sequences (ffn.cpp:105-122)
@@ -1722,6 +1742,27 @@ extern "C" int llmie_decoder_lora_attach(llmie_decoder *dec, const void *table_d
     return LLMIE_OK;
 }
 
+// Sliding-window attention: state on the engine, read where a call's attention launches are planned (the lora_attach pattern)
+extern "C" int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer_window, int sinks) {
+    LLMIE_REQUIRE(dec, "decoder_set_window: NULL decoder");
+    if (!layer_window) {   // back to full attention on every layer
+        LLMIE_REQUIRE(sinks == 0, "decoder_set_window: %d sink tokens without a window", sinks);
+        dec->layer_window.clear(), dec->sinks = 0;
+        return LLMIE_OK;
+    }
+    LLMIE_REQUIRE(sinks >= 0, "decoder_set_window: sinks %d must not be negative", sinks);
+    bool any = false;
+    for (int l = 0; l < dec->cfg.num_layers; ++l) {
+        LLMIE_REQUIRE(layer_window[l] >= 0, "decoder_set_window: window %d of layer %d must not be negative", layer_window[l], l);
+        any |= layer_window[l] > 0;
+    }
+    LLMIE_REQUIRE(any || sinks == 0, "decoder_set_window: %d sink tokens without a window on any layer", sinks);
+    if (any && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_window: %s", kWindowRefusal);
+    if (any) dec->layer_window.assign(layer_window, layer_window + dec->cfg.num_layers), dec->sinks = sinks;
+    else dec->layer_window.clear(), dec->sinks = 0;
+    return LLMIE_OK;
+}
+
 extern "C" int llmie_decoder_lora_detach(llmie_decoder *dec) {
     LLMIE_REQUIRE(dec, "decoder_lora_detach: NULL decoder");
     dec->lora = llmie_decoder::Lora{};
@@ -1738,6 +1779,7 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         if ((cfg->flags & LLMIE_DEC_PACKED_ONLY) && !packed_wf(cfg))
             LLMIE_UNSUPPORTED("%s", packed_only_refusal(cfg));
         if (int bad = prefill_shape_ok(*cfg, batch, tokens, max_q_len)) return bad;
+        if ((call_flags & LLMIE_PLAN_WINDOW) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kWindowRefusal);
         const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
         const PrefillPlan plan = plan_prefill(call);
         if (plan.path == PP_REFUSED) return prefill_refuse(plan);
@@ -1762,6 +1804,8 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
                          a.rope_append ? 1 : 0, norms[lp.ffn_norm], gus[lp.gate_up]);
         for (int op = 0; op <= LLMIE_OP_DOWN_GEMM; ++op)
             if (lp.launches[op]) n += snprintf(text + n, sizeof(text) - n, " %s=%d", ops[op], lp.launches[op]);
+        // (a windowed layer runs the windowed instantiation of the same flash form on the same grid)
+        if (call_flags & LLMIE_PLAN_WINDOW) snprintf(text + n, sizeof(text) - n, " attn_window=1");
         return LLMIE_OK;
     }();
     if (status) *status = rc;

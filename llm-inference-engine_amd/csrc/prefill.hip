@@ -252,14 +252,22 @@ int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, 
 // tile (global -> LDS, two barriers: 80 of the 175 us of the 4-wave form at 2048 tokens) serves 128 query rows.
 // RT = 16-row query tiles per wave (round 3): with RT = 2 every K / V^T fragment a wave reads from LDS feeds two MFMAs, and a
 // 4-wave workgroup covers the same 128 query rows -- two such workgroups share a CU and run out of phase with each other.
-template <int HS, bool KV8, int NW, int RT = 1>
+// WIN (compile time): sliding-window attention with sink tokens (include/llmie.h) -- query position i sees key j iff j <= i and
+// (i - j < W or j < S).  Its two launch arguments (W >= 1, S >= 0) are the pack WinArgs = (int, int); WIN = false has an empty pack:
+// the arguments and the code the kernel had before there was a window.  The key-tile loop then walks the sink tiles [0, ceil(S / 64))
+// and the tiles from floor(max(0, history + q0 - W + 1) / 64) on (a tile of both once); a wave skips a tile wholly in front of every
+// window of its rows like one wholly in their future; rows of a walked tile that no query of the workgroup sees re-read a visible
+// row of the same tile (0 x NaN would poison P.V), so neither a dead row nor the table entry of a dead page is ever read.
+template <int HS, bool KV8, int NW, int RT = 1, bool WIN = false, typename... WinArgs>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void prefill_flash_kernel(const half_t *__restrict__ qkv, const void *__restrict__ k_cache,
                                                             const void *__restrict__ v_cache, half_t *__restrict__ out,
                                                             const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
                                                             int head_num, int kv_head_num, int max_seq_len, size_t layer_off,
                                                             float k_scale, float v_scale,
-                                                            const int32_t *__restrict__ table /* paged cache or null */, int max_pages) {
+                                                            const int32_t *__restrict__ table /* paged cache or null */, int max_pages,
+                                                            const WinArgs... win /* WIN: window, sinks */) {
     static_assert(HS == 128, "tuned for head_size 128");
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
     // V rows are 288 bytes (256 + 32): the PV operand is fetched with ds_read_b64_tr_b16 (gfx950 transposed LDS read: a 16-lane
     // group reads a block of 4 keys x 16 head dims and every lane receives one column of it = 4 consecutive keys of its head
     // dim), whose 16 lanes address 4 rows x 4 eight-byte pieces -- rows 32 bytes apart modulo 256 keep a 32-lane half
@@ -329,6 +337,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
 
     const int t_hi = min(ctx, history + min(q0 + BQ, len));  // keys needed by any row of this q tile
+    // WIN: the tiles this workgroup walks, it -> tile: it < tl_sink ? it : tl_first + (it - tl_sink); w_lo = the lowest window start of
+    // its rows (row q0's)
+    int win_w = 0, win_s = 0, w_lo = 0, tl_sink = 0, tl_first = 0, n_tiles = 0;
+    if constexpr (WIN) {
+        const int wa[2] = {win...};
+        win_w = wa[0], win_s = wa[1];
+        w_lo = max(0, history + q0 - win_w + 1);
+        const int all = (t_hi + BT - 1) / BT, first = w_lo / BT, ns = (min(win_s, t_hi) + BT - 1) / BT;
+        if (ns < first) tl_sink = ns, tl_first = first;
+        n_tiles = all - (tl_first - tl_sink);
+    }
+    auto tile_t0 = [&](int it) { return (it < tl_sink ? it : tl_first + (it - tl_sink)) * BT; };
     constexpr int NCH = 1024 / NTHR;  // 16-byte chunks of each tile per thread
     half8_t kreg[NCH], vreg[NCH];
     uint2 kreg8[NCH], vreg8[NCH];
@@ -342,7 +362,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int id = tid + NTHR * i, row = id >> 4, ch = id & 15;
-            const int t = min(t0 + row, ctx - 1);
+            int t = min(t0 + row, ctx - 1);
+            if constexpr (WIN) {   // a row behind the sinks and in front of every window: the window's first row if the tile holds it, else a sink
+                if (t >= win_s && t < w_lo) t = t0 + BT > w_lo ? w_lo : t0;
+            }
             const size_t off = tile_base + static_cast<size_t>(table ? t % 128 : t) * HS;
             if constexpr (KV8) {
                 kreg8[i] = *reinterpret_cast<const uint2 *>(kc8 + off + ch * 8);
@@ -382,19 +405,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #ifdef FLASH_STAMPS
     unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    fetch_tile(0);
+    fetch_tile(WIN ? tile_t0(0) : 0);
     publish_tile(0);
-    if (BT < t_hi) fetch_tile(BT);
-    for (int t0 = 0, it = 0; t0 < t_hi; t0 += BT, ++it) {
+    if (WIN ? 1 < n_tiles : BT < t_hi) fetch_tile(WIN ? tile_t0(1) : BT);
+    for (int t0 = WIN ? tile_t0(0) : 0, it = 0; WIN ? it < n_tiles : t0 < t_hi; t0 = WIN ? tile_t0(it + 1) : t0 + BT, ++it) {
         const half_t *Ks = Ksb[it & 1], *Vs = Vsb[it & 1];
         FLASH_T(ta);
         __syncthreads();  // tile `it` published by every thread; every wave done with tile it-1 (the other buffer)
         FLASH_T(tb);
         FLASH_ACC(0, ta, tb);
 #ifndef FLASH_SKIP_STAGE   // (timing experiment only, wrong results: no staging inside the loop)
-        if (t0 + BT < t_hi) {
+        if (WIN ? it + 1 < n_tiles : t0 + BT < t_hi) {
             publish_tile((it + 1) & 1);                        // tile it+1: registers (fetched last iteration) -> other buffer
-            if (t0 + 2 * BT < t_hi) fetch_tile(t0 + 2 * BT);   // tile it+2: in flight under this iteration's MFMAs
+            if (WIN ? it + 2 < n_tiles : t0 + 2 * BT < t_hi) fetch_tile(WIN ? tile_t0(it + 2) : t0 + 2 * BT);   // tile it+2: in flight under this iteration's MFMAs
         }
 #endif
         __builtin_amdgcn_sched_barrier(0);  // keep the loads above the compute below
@@ -403,6 +426,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         // key tiles entirely in the future of this wave's query rows are skipped by the whole wave (it still takes part in
         // the staging and the barriers above)
         if (t0 > history + q0 + wave * WROWS + WROWS - 1) continue;
+        if constexpr (WIN) {   // ... and so are tiles without a sink that end in front of the window of the wave's first row
+            if (t0 >= win_s && t0 + BT - 1 <= history + q0 + wave * WROWS - win_w) continue;
+        }
         // ---- S^T = K . Q^T : 4 key tiles of 16, 4 k-steps over the head dim, RT row tiles per fragment ----
         // all 16 K fragments of the tile are read before the first MFMA (the compiler's own order was read -> wait -> MFMA,
         // one LDS round trip per MFMA)
@@ -445,7 +471,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         // the causal / length mask is only evaluated on tiles that reach past the wave's first query position or the context end
         // (wave-uniform test), and 2^(-inf) = 0 needs no select.
         const float scale2 = scale * 1.44269504088896341f;
-        const bool need_mask = t0 + BT - 1 > history + q0 + wave * WROWS || t0 + BT > ctx;
+        // (WIN: or that begin at or in front of the window start of the wave's last row)
+        const bool need_mask = t0 + BT - 1 > history + q0 + wave * WROWS || t0 + BT > ctx ||
+                               (WIN && t0 <= history + q0 + wave * WROWS + WROWS - 1 - win_w);
         half8_t pf[RT][2];  // P^T fragments of row tile u = MFMA B operand of the two 32-key steps
         typedef float float2v_t __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -457,7 +485,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int t = t0 + tt * 16 + 4 * q + e;
-                        const float v = (t <= qpos[u] && t < ctx) ? sacc[u][tt][e] : -INFINITY;
+                        const float v = (t <= qpos[u] && t < ctx && (!WIN || t > qpos[u] - win_w || t < win_s)) ? sacc[u][tt][e] : -INFINITY;
                         sacc[u][tt][e] = v;
                         mloc = fmaxf(mloc, v);
                     }
@@ -559,7 +587,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 }
 
 // Which flash instantiation a prefill attention launch runs, its grid, and whether the RoPE + append launch goes in front.  Pure host code.
-PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done) {
+PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window, int sinks) {
     // 128 query rows per workgroup either way: 8 waves x 16 rows (one workgroup per CU at a time, dynamic rounds, longest first), or
     // 4 waves x 2 x 16 rows (every fragment read from LDS feeds two MFMAs; two workgroups per CU, out of phase with each other).
     // Measured (bench, same box, us per layer): 8 x 512 tokens 54.5 -> 47.5 and 16 x 256 tokens 38 with the 4-wave form; 1 x 2048
@@ -572,7 +600,9 @@ PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool k
     // (interleaved A/B, 7B, one sequence: 128 tokens 27.8k -> 28.1k tok/s, 256 32.6k -> 32.9k, 512 46.0k -> 46.6k, 768 equal)
     const bool bq64 = ((max_q_len + 127) / 128) * head_num * batch < 256;
     const int bq = bq64 ? 64 : 128;
-    return PrefillAttnPlan{bq, bq64 || rt2 ? 4 : 8, !bq64 && rt2 ? 2 : 1, kv_e4m3, {(max_q_len + bq - 1) / bq, head_num, batch}, !rope_done};
+    // (a window changes the key tiles a workgroup walks, not the grid: the forms are chosen as for full attention)
+    return PrefillAttnPlan{bq, bq64 || rt2 ? 4 : 8, !bq64 && rt2 ? 2 : 1, kv_e4m3, {(max_q_len + bq - 1) / bq, head_num, batch}, !rope_done,
+                           window > 0 ? window : 0, window > 0 ? sinks : 0};
 }
 
 // g.grid[1] / g.grid[2] are head_num / batch
@@ -597,6 +627,21 @@ int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qk
         case 142: flash = prefill_flash_kernel<128, true, 4, 2>; break;
         case 181: flash = prefill_flash_kernel<128, true, 8, 1>; break;
         default: set_error("prefill attention: no flash kernel of %d waves x %d row tiles", g.waves, g.row_tiles); return LLMIE_ERR_UNSUPPORTED;
+    }
+    if (g.window > 0) {   // the windowed instantiations of the same forms
+        decltype(&prefill_flash_kernel<128, false, 4, 1, true, int, int>) wflash = nullptr;
+        switch ((g.kv_e4m3 ? 100 : 0) + g.waves * 10 + g.row_tiles) {
+            case 41: wflash = prefill_flash_kernel<128, false, 4, 1, true, int, int>; break;
+            case 42: wflash = prefill_flash_kernel<128, false, 4, 2, true, int, int>; break;
+            case 81: wflash = prefill_flash_kernel<128, false, 8, 1, true, int, int>; break;
+            case 141: wflash = prefill_flash_kernel<128, true, 4, 1, true, int, int>; break;
+            case 142: wflash = prefill_flash_kernel<128, true, 4, 2, true, int, int>; break;
+            case 181: wflash = prefill_flash_kernel<128, true, 8, 1, true, int, int>; break;
+        }
+        wflash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), g.waves * 64, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num,
+                                                                            kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
+                                                                            kv.max_pages, g.window, g.sinks);
+        return launch_status("prefill_attention(window)");
     }
     flash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), g.waves * 64, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num,
                                                                        max_seq_len, layer_off, ks, vs, kv.block_table, kv.max_pages);
