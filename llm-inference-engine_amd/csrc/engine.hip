@@ -1812,68 +1812,60 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
     return rc == LLMIE_OK ? text : nullptr;
 }
 
-// the sampler operands of llmie_lm_head_sample_params (checked by sample_logits_check)
-struct SampleParamsArgs {
-    const llmie_sampling_params *params;
-    int32_t *history;
-    int history_stride;
-    int32_t *history_len;
-    int history_append;
-    float *out_logprob;
-    void *workspace;
-    const llmie_sampling_ext *ext;   // llmie_lm_head_sample_ext: the sampler's extension (nullptr: the kernel without it)
+// One LM-head call: what every entry brings.  Final RMSNorm and the LM-head projection into `logits` are common (lm_head_logits);
+// behind them each entry runs its own tail on the logits, with the operands only that tail uses: top-k + sampling (the reference's
+// two launches), top-k round 1 + the fused decode tail, or the per-request sampler (+ its extension).
+struct LmHeadCall {
+    llmie_decoder *dec;
+    void *hidden;
+    const void *gamma;
+    const llmie_matrix *head;
+    llmie_weight_format fmt;
+    void *logits;
+    int batch;
+    SamplePos pos;
+    int end_id;
+    llmie_stream stream;
+    SampleState state;   // (the top-k tails move seq_len and finished alone)
+    SampleOut out;
+    const void *embed;   // the optional tail: next_hidden[b] = embed[out_id[b]], *step_dev += 1
+    void *next_hidden;
+    int advance;
 };
 
-static int lm_head_sample_impl(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
-                               llmie_weight_format lm_fmt, void *logits, int32_t *tmp_ids, void *tmp_vals, int32_t *topk_ids,
-                               void *topk_vals, int K, int blocks_per_row, int32_t *seq_len, uint8_t *finished, int32_t *out_ids,
-                               int batch, int step, int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden,
-                               int advance_step, bool fused_tail, llmie_stream stream, const SampleParamsArgs *sp = nullptr) {
-    LLMIE_REQUIRE(dec && hidden && final_norm_gamma && lm_head && lm_head->data && logits && (sp || (topk_ids && topk_vals)) &&
-                      seq_len && finished && out_ids, "lm_head_sample: NULL pointer");
+// the checks every entry shares, then the logits.  tail_operands: the entry's own tail has what it needs
+static int lm_head_logits(const LmHeadCall &call, bool tail_operands) {
+    llmie_decoder *dec = call.dec;
+    llmie_stream stream = call.stream;
+    LLMIE_REQUIRE(dec && call.hidden && call.gamma && call.head && call.head->data && call.logits && tail_operands && call.state.seq_len &&
+                      call.state.finished && call.out.out_id, "lm_head_sample: NULL pointer");
     const llmie_decoder_config &c = dec->cfg;
+    const int batch = call.batch;
     LLMIE_REQUIRE(batch >= 1 && batch <= c.max_batch, "lm_head_sample: batch %d outside [1,%d]", batch, c.max_batch);
     LLMIE_REQUIRE(c.vocab_size > 0, "lm_head_sample: vocab_size not set in the decoder config");
-    if (lm_fmt == LLMIE_W_MXFP4) LLMIE_UNSUPPORTED("lm_head_sample: an MXFP4 LM head is not supported (fp16 / int8 / int4 / fp8 heads; a follow-up)");
+    if (call.fmt == LLMIE_W_MXFP4) LLMIE_UNSUPPORTED("lm_head_sample: an MXFP4 LM head is not supported (fp16 / int8 / int4 / fp8 heads; a follow-up)");
     int rc;
-    if (lm_fmt == LLMIE_W_F16 && c.dtype == LLMIE_F16 && gemv_f16_eligible(batch, dec->H, hidden, lm_head->data) &&
+    if (call.fmt == LLMIE_W_F16 && c.dtype == LLMIE_F16 && gemv_f16_eligible(batch, dec->H, call.hidden, call.head->data) &&
         !engine_switches().no_fused_decode) {
         // final RMSNorm fused into the LM-head GEMV prologue (hidden itself is left un-normalised)
-        TIMED(LLMIE_OP_LM_HEAD, linear_f16_nk_norm((const half_t *)hidden, (const half_t *)lm_head->data, (half_t *)logits, batch,
-                                                   dec->H, c.vocab_size, EPI_NONE_, (const half_t *)lm_head->bias, nullptr,
-                                                   (const half_t *)final_norm_gamma, nullptr, c.rms_eps, as_stream(stream)));
+        TIMED(LLMIE_OP_LM_HEAD, linear_f16_nk_norm((const half_t *)call.hidden, (const half_t *)call.head->data, (half_t *)call.logits, batch,
+                                                   dec->H, c.vocab_size, EPI_NONE_, (const half_t *)call.head->bias, nullptr,
+                                                   (const half_t *)call.gamma, nullptr, c.rms_eps, as_stream(stream)));
     } else {
-    // llama.cpp:247  final RMSNorm (the residual copy is unused there: pass NULL)
-    TIMED(LLMIE_OP_FINAL_NORM, llmie_rmsnorm(hidden, nullptr, final_norm_gamma, c.rms_eps, batch, dec->H, c.dtype, stream));
-    // llama.cpp:282  logits = hidden . lm_head^T
-    TIMED(LLMIE_OP_LM_HEAD, engine_linear(dec, lm_fmt, hidden, *lm_head, logits, batch, dec->H, c.vocab_size, false, nullptr,
-                                          false, stream));
+        // llama.cpp:247  final RMSNorm (the residual copy is unused there: pass NULL)
+        TIMED(LLMIE_OP_FINAL_NORM, llmie_rmsnorm(call.hidden, nullptr, call.gamma, c.rms_eps, batch, dec->H, c.dtype, stream));
+        // llama.cpp:282  logits = hidden . lm_head^T
+        TIMED(LLMIE_OP_LM_HEAD, engine_linear(dec, call.fmt, call.hidden, *call.head, call.logits, batch, dec->H, c.vocab_size, false, nullptr,
+                                              false, stream));
     }
-    if (fused_tail) {
-        // llama.cpp:293-318 (+ :219 of the next token): round 1 of the top-k, then ONE launch for round 2, the sampling, the next
-        // step's input embedding and the step counter
-        LLMIE_REQUIRE(K >= 1 && K <= 32 && K <= c.vocab_size && blocks_per_row >= 1 && blocks_per_row <= 64 && tmp_ids && tmp_vals,
-                      "lm_head_sample_next: K=%d / blocks_per_row=%d outside [1, 32] / [1, 64], or tmp buffers missing", K, blocks_per_row);
-        TIMED(LLMIE_OP_TOPK, topk_round1_only(logits, tmp_ids, tmp_vals, batch, c.vocab_size, K, blocks_per_row, c.dtype, as_stream(stream)));
-        TIMED(LLMIE_OP_SAMPLING, decode_tail(tmp_ids, tmp_vals, topk_ids, topk_vals, K, blocks_per_row, seq_len, finished, out_ids, batch, step,
-                                             step_dev, end_id, c.vocab_size, embed_table, next_hidden, dec->H, advance_step, dec->tail_ticket,
-                                             c.dtype, as_stream(stream)));
-        return LLMIE_OK;
-    }
-    if (sp) {
-        // per-request controls: ONE launch (sampling_params.hip), with the next step's embedding and counter in it
-        TIMED(LLMIE_OP_SAMPLING, sample_logits_launch(logits, batch, c.vocab_size, sp->params, sp->history, sp->history_stride,
-                                                      sp->history_len, sp->history_append, seq_len, finished, out_ids, sp->out_logprob,
-                                                      step, step_dev, end_id, sp->workspace, c.dtype, embed_table, next_hidden, dec->H,
-                                                      advance_step, dec->tail_ticket, as_stream(stream), sp->ext));
-        return LLMIE_OK;
-    }
-    // llama.cpp:293,304
-    TIMED(LLMIE_OP_TOPK, llmie_topk(logits, tmp_ids, tmp_vals, topk_ids, topk_vals, batch, c.vocab_size, K, blocks_per_row,
-                                    c.dtype, stream));
-    TIMED(LLMIE_OP_SAMPLING, llmie_sampling(topk_ids, topk_vals, seq_len, finished, out_ids, batch, K, step, step_dev, end_id,
-                                            c.vocab_size, c.dtype, stream));
     return LLMIE_OK;
+}
+// the sampler family's view of the call behind lm_head_logits (the decoder is there)
+static SampleRows lm_head_rows(const LmHeadCall &call, const llmie_sampling_params *params) {
+    return SampleRows{call.logits, call.batch, call.dec->cfg.vocab_size, call.dec->cfg.dtype, params, call.end_id};
+}
+static SampleTail lm_head_tail(const LmHeadCall &call) {
+    return SampleTail{call.embed, call.next_hidden, call.dec->H, call.advance, call.dec->tail_ticket};
 }
 
 extern "C" int llmie_lm_head_sample(llmie_decoder *dec, void *hidden, const void *final_norm_gamma,
@@ -1881,8 +1873,16 @@ extern "C" int llmie_lm_head_sample(llmie_decoder *dec, void *hidden, const void
                                     int32_t *tmp_ids, void *tmp_vals, int32_t *topk_ids, void *topk_vals, int K,
                                     int blocks_per_row, int32_t *seq_len, uint8_t *finished, int32_t *out_ids,
                                     int batch, int step, const int32_t *step_dev, int end_id, llmie_stream stream) {
-    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, tmp_ids, tmp_vals, topk_ids, topk_vals, K, blocks_per_row,
-                               seq_len, finished, out_ids, batch, step, const_cast<int32_t *>(step_dev), end_id, nullptr, nullptr, 0, false, stream);
+    LmHeadCall call{dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, batch, SamplePos{step, step_dev}, end_id, stream};
+    call.state.seq_len = seq_len, call.state.finished = finished, call.out.out_id = out_ids;
+    int rc = lm_head_logits(call, topk_ids && topk_vals);
+    if (rc != LLMIE_OK) return rc;
+    const int V = dec->cfg.vocab_size;
+    // llama.cpp:293,304
+    TIMED(LLMIE_OP_TOPK, llmie_topk(logits, tmp_ids, tmp_vals, topk_ids, topk_vals, batch, V, K, blocks_per_row, dec->cfg.dtype, stream));
+    TIMED(LLMIE_OP_SAMPLING, llmie_sampling(topk_ids, topk_vals, seq_len, finished, out_ids, batch, K, step, step_dev, end_id, V, dec->cfg.dtype,
+                                            stream));
+    return LLMIE_OK;
 }
 
 extern "C" int llmie_lm_head_sample_next(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
@@ -1893,41 +1893,19 @@ extern "C" int llmie_lm_head_sample_next(llmie_decoder *dec, void *hidden, const
     LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_next: next_hidden without an embedding table");
     LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_next: advance_step needs the device-resident step");
     LLMIE_REQUIRE(tmp_ids && tmp_vals, "lm_head_sample_next: tmp buffers required");
-    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, tmp_ids, tmp_vals, topk_ids, topk_vals, K, blocks_per_row,
-                               seq_len, finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, true, stream);
-}
-
-static int lm_head_sample_params_impl(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
-                                      llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev, int32_t *history,
-                                      int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
-                                      int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev, int end_id,
-                                      const void *embed_table, void *next_hidden, int advance_step, void *workspace,
-                                      size_t workspace_bytes, llmie_stream stream, const llmie_sampling_ext *ext) {
-    LLMIE_REQUIRE(dec, "lm_head_sample_params: NULL decoder");
-    LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_params: next_hidden without an embedding table");
-    LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_params: advance_step needs the device-resident step");
-    LLMIE_REQUIRE(batch >= 1 && batch <= dec->cfg.max_batch, "lm_head_sample_params: batch %d outside [1,%d]", batch, dec->cfg.max_batch);
-    LLMIE_REQUIRE(dec->cfg.vocab_size > 0, "lm_head_sample_params: vocab_size not set in the decoder config");
-    int rc = sample_logits_check(logits, batch, dec->cfg.vocab_size, params_dev, history, history_stride, history_len, seq_len, finished,
-                                 out_ids, workspace, workspace_bytes, dec->cfg.dtype);
+    LmHeadCall call{dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, batch, SamplePos{step, step_dev}, end_id, stream};
+    call.state.seq_len = seq_len, call.state.finished = finished, call.out.out_id = out_ids;
+    call.embed = embed_table, call.next_hidden = next_hidden, call.advance = advance_step;
+    int rc = lm_head_logits(call, topk_ids && topk_vals);
     if (rc != LLMIE_OK) return rc;
-    bool active;
-    if ((rc = sample_ext_check(batch, dec->cfg.vocab_size, ext, &active)) != LLMIE_OK) return rc;
-    const SampleParamsArgs sp{params_dev, history, history_stride, history_len, history_append, out_logprob, workspace,
-                              active ? ext : nullptr};
-    return lm_head_sample_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, nullptr, nullptr, nullptr, nullptr, 0, 1, seq_len,
-                               finished, out_ids, batch, step, step_dev, end_id, embed_table, next_hidden, advance_step, false, stream, &sp);
-}
-
-extern "C" int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
-                                           llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev,
-                                           int32_t *history, int history_stride, int32_t *history_len, int history_append,
-                                           int32_t *seq_len, uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step,
-                                           int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden, int advance_step,
-                                           void *workspace, size_t workspace_bytes, llmie_stream stream) {
-    return lm_head_sample_params_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, params_dev, history, history_stride,
-                                      history_len, history_append, seq_len, finished, out_ids, out_logprob, batch, step, step_dev, end_id,
-                                      embed_table, next_hidden, advance_step, workspace, workspace_bytes, stream, nullptr);
+    // llama.cpp:293-318 (+ :219 of the next token): round 1 of the top-k, then ONE launch for round 2, the sampling, the next
+    // step's input embedding and the step counter
+    LLMIE_REQUIRE(K >= 1 && K <= 32 && K <= dec->cfg.vocab_size && blocks_per_row >= 1 && blocks_per_row <= 64,
+                  "lm_head_sample_next: K=%d / blocks_per_row=%d outside [1, 32] / [1, 64], or tmp buffers missing", K, blocks_per_row);
+    const TopkOperands tk{tmp_ids, tmp_vals, topk_ids, topk_vals, K, blocks_per_row};
+    TIMED(LLMIE_OP_TOPK, topk_round1_only(logits, tk, batch, dec->cfg.vocab_size, dec->cfg.dtype, as_stream(stream)));
+    TIMED(LLMIE_OP_SAMPLING, decode_tail(tk, lm_head_rows(call, nullptr), call.state, call.pos, out_ids, lm_head_tail(call), as_stream(stream)));
+    return LLMIE_OK;
 }
 
 extern "C" int llmie_lm_head_sample_ext(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
@@ -1936,7 +1914,37 @@ extern "C" int llmie_lm_head_sample_ext(llmie_decoder *dec, void *hidden, const 
                                         uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step, int32_t *step_dev,
                                         int end_id, const void *embed_table, void *next_hidden, int advance_step, void *workspace,
                                         size_t workspace_bytes, llmie_stream stream, const llmie_sampling_ext *ext) {
-    return lm_head_sample_params_impl(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, params_dev, history, history_stride,
-                                      history_len, history_append, seq_len, finished, out_ids, out_logprob, batch, step, step_dev, end_id,
-                                      embed_table, next_hidden, advance_step, workspace, workspace_bytes, stream, ext);
+    LLMIE_REQUIRE(dec, "lm_head_sample_params: NULL decoder");
+    LLMIE_REQUIRE(!next_hidden || embed_table, "lm_head_sample_params: next_hidden without an embedding table");
+    LLMIE_REQUIRE(!advance_step || step_dev, "lm_head_sample_params: advance_step needs the device-resident step");
+    LLMIE_REQUIRE(batch >= 1 && batch <= dec->cfg.max_batch, "lm_head_sample_params: batch %d outside [1,%d]", batch, dec->cfg.max_batch);
+    LLMIE_REQUIRE(dec->cfg.vocab_size > 0, "lm_head_sample_params: vocab_size not set in the decoder config");
+    LmHeadCall call{dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, batch, SamplePos{step, step_dev}, end_id, stream};
+    call.state = SampleState{history, history_stride, history_len, history_append, seq_len, finished};
+    call.out = SampleOut{out_ids, out_logprob};
+    call.embed = embed_table, call.next_hidden = next_hidden, call.advance = advance_step;
+    const SampleRows rows = lm_head_rows(call, params_dev);
+    const SampleWs ws{workspace, workspace_bytes};
+    int rc = sample_logits_check("sample_logits", rows, call.state, out_ids);
+    if (rc != LLMIE_OK) return rc;
+    if ((rc = sample_workspace_check("sample_logits", ws, llmie_sample_logits_workspace_bytes(batch, rows.vocab), nullptr)) != LLMIE_OK) return rc;
+    bool active;
+    if ((rc = sample_ext_check(batch, rows.vocab, ext, &active)) != LLMIE_OK) return rc;
+    if ((rc = lm_head_logits(call, true)) != LLMIE_OK) return rc;
+    // per-request controls: ONE launch (sampling_params.hip), with the next step's embedding and counter in it
+    TIMED(LLMIE_OP_SAMPLING, sample_logits_launch(rows, call.state, call.pos, call.out, lm_head_tail(call), ws, active ? ext : nullptr,
+                                                  as_stream(stream)));
+    return LLMIE_OK;
+}
+
+// (no extension: nothing for sample_ext_check to refuse, and the kernel without it)
+extern "C" int llmie_lm_head_sample_params(llmie_decoder *dec, void *hidden, const void *final_norm_gamma, const llmie_matrix *lm_head,
+                                           llmie_weight_format lm_fmt, void *logits, const llmie_sampling_params *params_dev,
+                                           int32_t *history, int history_stride, int32_t *history_len, int history_append,
+                                           int32_t *seq_len, uint8_t *finished, int32_t *out_ids, float *out_logprob, int batch, int step,
+                                           int32_t *step_dev, int end_id, const void *embed_table, void *next_hidden, int advance_step,
+                                           void *workspace, size_t workspace_bytes, llmie_stream stream) {
+    return llmie_lm_head_sample_ext(dec, hidden, final_norm_gamma, lm_head, lm_fmt, logits, params_dev, history, history_stride, history_len,
+                                    history_append, seq_len, finished, out_ids, out_logprob, batch, step, step_dev, end_id, embed_table,
+                                    next_hidden, advance_step, workspace, workspace_bytes, stream, nullptr);
 }

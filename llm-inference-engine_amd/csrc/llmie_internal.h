@@ -2,6 +2,8 @@
 #pragma once
 #include "device_utils.cuh"
 
+#include <type_traits>
+
 namespace llmie {
 
 enum : int { EPI_NONE_ = 0, EPI_SWIGLU_ = 1 };
@@ -277,13 +279,6 @@ struct DecodeAttnIo {
 // decode attention of one layer with bias, RoPE and the KV append fused in front: plan, refuse or launch
 int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st);
 
-// fused tail of a decode step (topk_sampling.hip): round 1 of the top-k alone, and round 2 + sampling (+ the next step's input
-// embedding into next_hidden, + *step_dev += 1 by the last row to finish; `ticket` = one zeroed word) in one launch
-int topk_round1_only(const void *probs, int32_t *tmp_ids, void *tmp_vals, int rows, int vocab, int K, int bpr, llmie_dtype dtype, hipStream_t st);
-int decode_tail(const int32_t *tmp_ids, const void *tmp_vals, int32_t *ids, void *vals, int K, int bpr, int32_t *seq_len, uint8_t *finished,
-                int32_t *out_id, int rows, int step, int32_t *step_dev, int end_id, int vocab, const void *embed, void *next_hidden, int hidden,
-                int advance, unsigned *ticket, llmie_dtype dtype, hipStream_t st);
-
 // prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip: one pure host planner decides the
 // launch, one launcher runs the plan
 struct PrefillAttnPlan {
@@ -307,20 +302,68 @@ int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t 
 int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, int batch, int num_tokens, int32_t *tok_b, int32_t *tok_tpos,
                         QkvRopeArgs args, QkvRopeArgs *args_dev, hipStream_t st);
 
-// per-request sampling (sampling_params.hip): the host-side checks of llmie_sample_logits, and its launch with the optional
-// tail of llmie_lm_head_sample_params (next_hidden[b] = embed[out_id[b]], *step_dev += 1 once every row has read it).
-// ext != nullptr launches the kernel with the extension (llmie_sampling_ext); sample_ext_check says whether a struct needs it.
-// entry: the name the messages carry; own_workspace == false leaves the workspace to a caller that sizes its own (spec_decode.hip).
-int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
-                        int history_stride, const int32_t *history_len, const int32_t *seq_len, const uint8_t *finished,
-                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype,
-                        const char *entry = "sample_logits", bool own_workspace = true);
-int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
-                         int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
-                         int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
-                         llmie_dtype dtype, const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket,
-                         hipStream_t st, const llmie_sampling_ext *ext = nullptr);
+// ---- the sampler family (sampling_params.hip, spec_decode.hip, topk_sampling.hip and the LM-head entries of engine.hip) ----
+// A call is a few structs that say what its operands are, from the C entry to the kernel launch: a new operand is added to ONE struct,
+// at the entries that fill it and at the launch that reads it.  The rows: logits [batch, vocab], one llmie_sampling_params per row
+struct SampleRows {
+    const void *logits;
+    int batch, vocab;
+    llmie_dtype dtype;
+    const llmie_sampling_params *params;
+    int end_id;
+};
+struct SampleState {   // the per-sequence state a call moves
+    int32_t *history;
+    int history_stride;
+    int32_t *history_len;
+    int history_append;
+    int32_t *seq_len;
+    uint8_t *finished;
+};
+struct SamplePos { int step; const int32_t *step_dev; };   // the Philox step: on the host, or *step_dev (which the tail may advance)
+struct SampleOut { int32_t *out_id; float *out_logprob /* or null */; };
+// The optional tail of a decode step: next_hidden[b] = embed[out_id[b]] (rows of `hidden` elements), and *step_dev += 1 by the last
+// row to finish (`ticket` = one zeroed word).  All zero: none.
+struct SampleTail {
+    const void *embed;
+    void *next_hidden;
+    int hidden, advance;
+    unsigned *ticket;
+};
+struct SampleWs { void *p; size_t bytes; };
+// The host-side checks of llmie_sample_logits under the name `entry`; `out` is where the call writes its tokens.  The workspace is
+// the caller's to size: sample_workspace_check is the one rule -- present, `need` bytes, 16-byte aligned -- and `query` the size
+// query its message names (null: none).  sample_ext_check says whether an extension struct needs the EXT kernels: the launch gets
+// ext != nullptr exactly then.
+int sample_logits_check(const char *entry, const SampleRows &rows, const SampleState &state, const void *out);
+int sample_workspace_check(const char *entry, SampleWs ws, size_t need, const char *query);
 int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *ext, bool *active, const char *entry = "sample_logits_ext");
 size_t sample_logits_ws_row(int vocab);   // uint32 words of workspace per row
+int sample_logits_launch(const SampleRows &rows, const SampleState &state, const SamplePos &pos, const SampleOut &out, const SampleTail &tail,
+                         SampleWs ws, const llmie_sampling_ext *ext, hipStream_t st);
+// fp16 / fp32 -> f(TypeTag<T>{}); (dtype, extension active) -> the <T, EXT> instantiation of a sampler kernel:
+// f(TypeTag<T>{}, std::bool_constant<EXT>{}).  A kernel launch is written once, inside the callable.
+template <class T> struct TypeTag { using type = T; };
+template <class F> void dtype_dispatch(llmie_dtype dtype, F f) {
+    if (dtype == LLMIE_F16) f(TypeTag<half_t>{});
+    else f(TypeTag<float>{});
+}
+template <class F> void sample_dispatch(llmie_dtype dtype, bool ext, F f) {
+    dtype_dispatch(dtype, [&](auto type) {
+        if (ext) f(type, std::true_type{});
+        else f(type, std::false_type{});
+    });
+}
+// fused tail of a decode step (topk_sampling.hip): round 1 of the top-k alone, and round 2 + sampling + SampleTail in one launch
+struct TopkOperands {   // llmie_topk's: round 1 -> (tmp_ids, tmp_vals) [rows, bpr * K] -> round 2 -> (ids, vals) [rows, K]
+    int32_t *tmp_ids;
+    void *tmp_vals;
+    int32_t *ids;
+    void *vals;
+    int K, bpr;
+};
+int topk_round1_only(const void *probs, const TopkOperands &tk, int rows, int vocab, llmie_dtype dtype, hipStream_t st);
+int decode_tail(const TopkOperands &tk, const SampleRows &rows, const SampleState &state, const SamplePos &pos, int32_t *out_id,
+                const SampleTail &tail, hipStream_t st);
 
 }  // namespace llmie

@@ -237,6 +237,18 @@ struct SpPick {
     const int32_t *stops;
 };
 
+// A row's epilogue, shared by every kernel that emits a token of it.  Does `token` finish the sequence: end_id, or (EXT) a stop
+template <bool EXT> __device__ __forceinline__ bool sp_finishes(const SpPick &pick, int token, int end_id) {
+    bool fin = token == end_id;
+    if constexpr (EXT)
+        for (int i = 0; i < pick.slen; ++i) fin = fin || pick.stops[i] == token;
+    return fin;
+}
+// and its raw log-probability.  lse = pick.lse_m + logf(pick.lse_s), computed by the caller: ONCE where it asks for several tokens
+template <typename T> __device__ __forceinline__ float sp_logprob(const T *__restrict__ lg, int V, const SpPick &pick, float lse, int token) {
+    return (token >= 0 && token < V && pick.valid > 0) ? to_f32(lg[token]) - lse : -INFINITY;
+}
+
 // The distribution a row is drawn from, over the row's keys: which tokens are kept and their fixed-point mass.  point: a greedy
 // row or one with at most one valid token -- the point mass on the row's pick, no cuts, total unused.
 struct SpKept {

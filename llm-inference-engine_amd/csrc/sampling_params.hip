@@ -27,8 +27,8 @@
 //            pass 2 turns a token whose bit is clear into key 0, what a NaN gets -- everything downstream ignores key 0
 //   stops    finished also if the pick is in the row's stop list
 //
-// The device code of all this -- sp_sample_row and what it calls -- lives in sampling_body.cuh, which spec_decode.hip shares; this
-// file keeps the kernels' shell (operands, the epilogue that writes the state), the launches and the host checks.
+// The device code of all this lives in sampling_body.cuh, which spec_decode.hip shares; this file keeps the kernel's shell, its one
+// launch and the host checks.  On the host a call is the structs of llmie_internal.h (rows, state, position, ...) from entry to launch.
 #include "sampling_body.cuh"
 
 namespace llmie {
@@ -50,20 +50,13 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
     if constexpr (EXT) ep = &sp_ext(ext...);
     const SpPick pick = sp_sample_row<T, EXT>(logits + static_cast<size_t>(b) * V, V, params[b], SpStoredHistory{history, history_len, b, hstride},
                                               step, end_id, ws + static_cast<size_t>(b) * ws_row, ep, b, b, s);
-    const T *lg = logits + static_cast<size_t>(b) * V;
-    const int chosen = pick.chosen, valid = pick.valid, slen = pick.slen;
-    const int32_t *stops = pick.stops;
-    const float lse_m = pick.lse_m, lse_s = pick.lse_s;
+    const int chosen = pick.chosen;
 
     if (tid == 0) {
         out_id[b] = chosen;
         if (!finished[b]) ++seq_len[b];
-        bool fin = chosen == end_id;
-        if constexpr (EXT)
-            for (int i = 0; i < slen; ++i) fin = fin || stops[i] == chosen;
-        finished[b] = static_cast<uint8_t>(fin);
-        if (out_logprob)
-            out_logprob[b] = (chosen >= 0 && chosen < V && valid > 0) ? to_f32(lg[chosen]) - (lse_m + logf(lse_s)) : -INFINITY;
+        finished[b] = static_cast<uint8_t>(sp_finishes<EXT>(pick, chosen, end_id));
+        if (out_logprob) out_logprob[b] = sp_logprob(logits + static_cast<size_t>(b) * V, V, pick, pick.lse_m + logf(pick.lse_s), chosen);
         if (happend && hstride > 0) {
             const int len = history_len[b];
             if (len >= 0 && len < hstride) {
@@ -89,37 +82,20 @@ __global__ __launch_bounds__(kSpThreads) void sample_params_kernel(
 
 size_t sample_logits_ws_row(int vocab) { return (static_cast<size_t>(vocab) + 63) & ~static_cast<size_t>(63); }
 
-template <typename T>
-static void sample_launch_t(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
-                            int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
-                            int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
-                            const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket, hipStream_t st,
-                            const llmie_sampling_ext *ext) {
-    const size_t row = sample_logits_ws_row(vocab);
-    uint32_t *ws = static_cast<uint32_t *>(workspace);
-    if (ext)
-        sample_params_kernel<T, llmie_sampling_ext><<<batch, kSpThreads, 0, st>>>(
-            static_cast<const T *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished, out_id,
-            out_logprob, step, step_dev, end_id, ws, row, static_cast<const T *>(embed), static_cast<T *>(next_hidden), hidden, advance,
-            ticket, batch, *ext);
-    else
-        sample_params_kernel<T><<<batch, kSpThreads, 0, st>>>(
-            static_cast<const T *>(logits), vocab, params, history, history_stride, history_len, history_append, seq_len, finished, out_id,
-            out_logprob, step, step_dev, end_id, ws, row, static_cast<const T *>(embed), static_cast<T *>(next_hidden), hidden, advance,
-            ticket, batch);
-}
-
-int sample_logits_launch(const void *logits, int batch, int vocab, const llmie_sampling_params *params, int32_t *history,
-                         int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
-                         int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
-                         llmie_dtype dtype, const void *embed, void *next_hidden, int hidden, int advance, unsigned *ticket,
-                         hipStream_t st, const llmie_sampling_ext *ext) {
-    if (dtype == LLMIE_F16)
-        sample_launch_t<half_t>(logits, batch, vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
-                                out_id, out_logprob, step, step_dev, end_id, workspace, embed, next_hidden, hidden, advance, ticket, st, ext);
-    else
-        sample_launch_t<float>(logits, batch, vocab, params, history, history_stride, history_len, history_append, seq_len, finished,
-                               out_id, out_logprob, step, step_dev, end_id, workspace, embed, next_hidden, hidden, advance, ticket, st, ext);
+int sample_logits_launch(const SampleRows &rows, const SampleState &state, const SamplePos &pos, const SampleOut &out, const SampleTail &tail,
+                         SampleWs ws, const llmie_sampling_ext *ext, hipStream_t st) {
+    sample_dispatch(rows.dtype, ext != nullptr, [&](auto type, auto with_ext) {
+        using T = typename decltype(type)::type;
+        auto launch = [&](auto... e) {   // e: nothing, or one llmie_sampling_ext -- which is what chooses the kernel
+            sample_params_kernel<T, decltype(e)...><<<rows.batch, kSpThreads, 0, st>>>(
+                static_cast<const T *>(rows.logits), rows.vocab, rows.params, state.history, state.history_stride, state.history_len,
+                state.history_append, state.seq_len, state.finished, out.out_id, out.out_logprob, pos.step, pos.step_dev, rows.end_id,
+                static_cast<uint32_t *>(ws.p), sample_logits_ws_row(rows.vocab), static_cast<const T *>(tail.embed),
+                static_cast<T *>(tail.next_hidden), tail.hidden, tail.advance, tail.ticket, rows.batch, e...);
+        };
+        if constexpr (decltype(with_ext)::value) launch(*ext);
+        else launch();
+    });
     return launch_status("sample_logits");
 }
 
@@ -154,25 +130,22 @@ int sample_ext_check(int batch, int vocab, const llmie_sampling_ext *e, bool *ac
     return LLMIE_OK;
 }
 
-int sample_logits_check(const void *logits, int batch, int vocab, const llmie_sampling_params *params, const int32_t *history,
-                        int history_stride, const int32_t *history_len, const int32_t *seq_len, const uint8_t *finished,
-                        const int32_t *out_id, const void *workspace, size_t workspace_bytes, llmie_dtype dtype, const char *entry,
-                        bool own_workspace) {
-    LLMIE_REQUIRE(logits && params && seq_len && finished && out_id, "%s: NULL pointer", entry);
-    LLMIE_REQUIRE(batch > 0 && vocab > 0, "%s: batch %d / vocab %d must be positive", entry, batch, vocab);
-    LLMIE_REQUIRE(history_stride >= 0, "%s: history_stride %d < 0", entry, history_stride);
-    LLMIE_REQUIRE(history_stride == 0 || (history && history_len), "%s: history_stride %d > 0 without history / history_len", entry,
-                  history_stride);
-    if (history_stride > kSpMaxHistory)
-        LLMIE_UNSUPPORTED("%s: history_stride %d above %d", entry, history_stride, kSpMaxHistory);
-    if (dtype != LLMIE_F16 && dtype != LLMIE_F32) LLMIE_UNSUPPORTED("%s: dtype %d", entry, (int)dtype);
-    if (!own_workspace) return LLMIE_OK;   // (the caller sizes and checks a workspace of its own)
-    const size_t need = llmie_sample_logits_workspace_bytes(batch, vocab);
-    if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
-        set_error("%s: workspace %zu bytes (need %zu, 16-byte aligned)", entry, workspace ? workspace_bytes : (size_t)0, need);
-        return LLMIE_ERR_WORKSPACE;
-    }
+int sample_logits_check(const char *entry, const SampleRows &r, const SampleState &s, const void *out) {
+    LLMIE_REQUIRE(r.logits && r.params && s.seq_len && s.finished && out, "%s: NULL pointer", entry);
+    LLMIE_REQUIRE(r.batch > 0 && r.vocab > 0, "%s: batch %d / vocab %d must be positive", entry, r.batch, r.vocab);
+    LLMIE_REQUIRE(s.history_stride >= 0, "%s: history_stride %d < 0", entry, s.history_stride);
+    LLMIE_REQUIRE(s.history_stride == 0 || (s.history && s.history_len), "%s: history_stride %d > 0 without history / history_len", entry,
+                  s.history_stride);
+    if (s.history_stride > kSpMaxHistory) LLMIE_UNSUPPORTED("%s: history_stride %d above %d", entry, s.history_stride, kSpMaxHistory);
+    if (r.dtype != LLMIE_F16 && r.dtype != LLMIE_F32) LLMIE_UNSUPPORTED("%s: dtype %d", entry, (int)r.dtype);
     return LLMIE_OK;
+}
+
+int sample_workspace_check(const char *entry, SampleWs ws, size_t need, const char *query) {
+    if (ws.p && ws.bytes >= need && reinterpret_cast<uintptr_t>(ws.p) % 16 == 0) return LLMIE_OK;
+    set_error("%s: workspace %zu bytes (need %zu, 16-byte aligned%s%s)", entry, ws.p ? ws.bytes : (size_t)0, need, query ? ": " : "",
+              query ? query : "");
+    return LLMIE_ERR_WORKSPACE;
 }
 
 }  // namespace llmie
@@ -184,29 +157,28 @@ extern "C" size_t llmie_sample_logits_workspace_bytes(int batch, int vocab) {
     return static_cast<size_t>(batch) * sample_logits_ws_row(vocab) * sizeof(uint32_t);
 }
 
-extern "C" int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
-                                   int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
-                                   int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
-                                   size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
-    const int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_id,
-                                       workspace, workspace_bytes, dtype);
-    if (rc != LLMIE_OK) return rc;
-    return sample_logits_launch(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
-                                out_id, out_logprob, step, step_dev, end_id, workspace, dtype, nullptr, nullptr, 0, 0, nullptr,
-                                as_stream(stream));
-}
-
 extern "C" int llmie_sample_logits_ext(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
                                        int history_stride, int32_t *history_len, int history_append, int32_t *seq_len,
                                        uint8_t *finished, int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev,
                                        int end_id, void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream,
                                        const llmie_sampling_ext *ext) {
-    int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_id,
-                                 workspace, workspace_bytes, dtype);
+    const SampleRows rows{logits, batch, vocab, dtype, params_dev, end_id};
+    const SampleState state{history, history_stride, history_len, history_append, seq_len, finished};
+    const SampleWs ws{workspace, workspace_bytes};
+    int rc = sample_logits_check("sample_logits", rows, state, out_id);
     if (rc != LLMIE_OK) return rc;
+    if ((rc = sample_workspace_check("sample_logits", ws, llmie_sample_logits_workspace_bytes(batch, vocab), nullptr)) != LLMIE_OK) return rc;
     bool active;
     if ((rc = sample_ext_check(batch, vocab, ext, &active)) != LLMIE_OK) return rc;
-    return sample_logits_launch(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
-                                out_id, out_logprob, step, step_dev, end_id, workspace, dtype, nullptr, nullptr, 0, 0, nullptr,
-                                as_stream(stream), active ? ext : nullptr);
+    return sample_logits_launch(rows, state, SamplePos{step, step_dev}, SampleOut{out_id, out_logprob}, SampleTail{}, ws,
+                                active ? ext : nullptr, as_stream(stream));
+}
+
+// (no extension: nothing for sample_ext_check to refuse, and the kernel without it)
+extern "C" int llmie_sample_logits(const void *logits, int batch, int vocab, const llmie_sampling_params *params_dev, int32_t *history,
+                                   int history_stride, int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                                   int32_t *out_id, float *out_logprob, int step, const int32_t *step_dev, int end_id, void *workspace,
+                                   size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
+    return llmie_sample_logits_ext(logits, batch, vocab, params_dev, history, history_stride, history_len, history_append, seq_len, finished,
+                                   out_id, out_logprob, step, step_dev, end_id, workspace, workspace_bytes, dtype, stream, nullptr);
 }

@@ -23,6 +23,10 @@
 // last place the sequence's final n tokens occurred before.  A thread that sees the final token at q extends the comparison
 // backwards (<= 7 more loads, rare); the sweep itself reads 16 bytes per thread where the row is aligned.  "The last place" is an
 // integer maximum in LDS: deterministic.
+//
+// The two verify entries are shells over ONE host function, spec_verify_impl (checks, workspace carve, rows launch, accept launch;
+// SpecDraft::sampled picks the kernels); the two rows kernels share spec_row_view and the sampler's epilogue helpers.  The accept
+// kernels keep their own walk + state commit: one function around a per-position callable cost spec_accept_kernel a register.
 #include "sampling_body.cuh"
 
 namespace llmie {
@@ -37,6 +41,27 @@ struct SpSplicedHistory {
     __device__ __forceinline__ int at(int j) const { return j < stored ? row[j] : draft[j - stored]; }
 };
 
+// A rows kernel's view of workgroup r = b * (k + 1) + i: the sequence, the position, its Philox step and its penalty history
+struct SpecRowView {
+    int b, i, step;
+    SpSplicedHistory hist;
+};
+__device__ __forceinline__ SpecRowView spec_row_view(int r, int k, const int32_t *__restrict__ history, int hstride,
+                                                     const int32_t *__restrict__ history_len, int happend, const int32_t *__restrict__ draft_ids,
+                                                     const int32_t *__restrict__ step_rows, int step_arg, const int32_t *step_dev) {
+    const int b = r / (k + 1), i = r - b * (k + 1);
+    const int step = (step_rows ? step_rows[b] : (step_dev ? *step_dev : step_arg)) + i;
+    SpSplicedHistory hist{nullptr, draft_ids + static_cast<size_t>(b) * k, 0, 0};
+    if (hstride > 0) {
+        const int len0 = history_len[b];
+        hist.row = history + static_cast<size_t>(b) * hstride;
+        hist.stored = min(max(len0, 0), hstride);
+        // (a negative length is never appended to: llmie_sample_logits appends while 0 <= history_len < history_stride)
+        hist.len = (happend && len0 >= 0) ? min(hist.stored + i, hstride) : hist.stored;
+    }
+    return SpecRowView{b, i, step, hist};
+}
+
 struct SpecPick {   // workspace record of a row
     int32_t token;
     float logprob;
@@ -50,28 +75,16 @@ __global__ __launch_bounds__(kSpThreads) void spec_verify_rows_kernel(
     const int32_t *__restrict__ step_rows, int step_arg, const int32_t *__restrict__ step_dev, int end_id, uint32_t *ws, size_t ws_row,
     SpecPick *__restrict__ picks, const llmie_sampling_ext ext) {
     __shared__ alignas(16) SpShared s;
-    const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
-    const int step = (step_rows ? step_rows[b] : (step_dev ? *step_dev : step_arg)) + i;
-    SpSplicedHistory hist{nullptr, draft_ids + static_cast<size_t>(b) * k, 0, 0};
-    if (hstride > 0) {
-        const int len0 = history_len[b];
-        hist.row = history + static_cast<size_t>(b) * hstride;
-        hist.stored = min(max(len0, 0), hstride);
-        // (a negative length is never appended to: llmie_sample_logits appends while 0 <= history_len < history_stride)
-        hist.len = (happend && len0 >= 0) ? min(hist.stored + i, hstride) : hist.stored;
-    }
+    const int r = blockIdx.x;
+    const SpecRowView v = spec_row_view(r, k, history, hstride, history_len, happend, draft_ids, step_rows, step_arg, step_dev);
     const T *lg = logits + static_cast<size_t>(r) * V;
-    const SpPick pick = sp_sample_row<T, EXT>(lg, V, params[b], hist, step, end_id, ws + static_cast<size_t>(r) * ws_row, EXT ? &ext : nullptr, b,
-                                              r, s);
+    const SpPick pick = sp_sample_row<T, EXT>(lg, V, params[v.b], v.hist, v.step, end_id, ws + static_cast<size_t>(r) * ws_row, EXT ? &ext : nullptr,
+                                              v.b, r, s);
     if (threadIdx.x == 0) {
-        const int chosen = pick.chosen;
-        bool fin = chosen == end_id;
-        if constexpr (EXT)
-            for (int j = 0; j < pick.slen; ++j) fin = fin || pick.stops[j] == chosen;
         SpecPick out;
-        out.token = chosen;
-        out.logprob = (chosen >= 0 && chosen < V && pick.valid > 0) ? to_f32(lg[chosen]) - (pick.lse_m + logf(pick.lse_s)) : -INFINITY;
-        out.fin = fin ? 1 : 0;
+        out.token = pick.chosen;
+        out.logprob = sp_logprob(lg, V, pick, pick.lse_m + logf(pick.lse_s), pick.chosen);
+        out.fin = sp_finishes<EXT>(pick, pick.chosen, end_id) ? 1 : 0;
         out.pad = 0;
         picks[r] = out;
     }
@@ -183,15 +196,8 @@ __global__ __launch_bounds__(kSpThreads) void spec_sampled_rows_kernel(
     const int32_t *__restrict__ step_rows, int step_arg, const int32_t *step_dev, int end_id, uint32_t *ws, size_t ws_row,
     SpecSampledRec *__restrict__ recs, const llmie_sampling_ext ext) {
     __shared__ alignas(16) SpShared s;
-    const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
-    const int step = (step_rows ? step_rows[b] : (step_dev ? *step_dev : step_arg)) + i;
-    SpSplicedHistory hist{nullptr, draft_ids + static_cast<size_t>(b) * k, 0, 0};
-    if (hstride > 0) {
-        const int len0 = history_len[b];
-        hist.row = history + static_cast<size_t>(b) * hstride;
-        hist.stored = min(max(len0, 0), hstride);
-        hist.len = (happend && len0 >= 0) ? min(hist.stored + i, hstride) : hist.stored;
-    }
+    const int r = blockIdx.x;
+    const auto [b, i, step, hist] = spec_row_view(r, k, history, hstride, history_len, happend, draft_ids, step_rows, step_arg, step_dev);
     const T *lg = logits + static_cast<size_t>(r) * V;
     uint32_t *keys_p = ws + static_cast<size_t>(2 * r) * ws_row, *keys_q = keys_p + ws_row;
     const llmie_sampling_params p = params[b];
@@ -202,13 +208,8 @@ __global__ __launch_bounds__(kSpThreads) void spec_sampled_rows_kernel(
         if (id >= 0) plain = id;
     }
     const float lse = P.pick.lse_m + logf(P.pick.lse_s);
-    auto logprob = [&](int t) { return (t >= 0 && t < V && P.pick.valid > 0) ? to_f32(lg[t]) - lse : -INFINITY; };
-    auto finishes = [&](int t) {
-        bool fin = t == end_id;
-        if constexpr (EXT)
-            for (int j = 0; j < P.pick.slen; ++j) fin = fin || P.pick.stops[j] == t;
-        return fin ? 1 : 0;
-    };
+    auto logprob = [&](int t) { return sp_logprob(lg, V, P.pick, lse, t); };
+    auto finishes = [&](int t) { return sp_finishes<EXT>(P.pick, t, end_id) ? 1 : 0; };
 
     const int m = draft_len ? min(max(draft_len[b], 0), k) : k;
     bool accept = false;
@@ -386,19 +387,79 @@ __global__ __launch_bounds__(kNgThreads) void ngram_draft_kernel(const int32_t *
 
 static_assert(LLMIE_SPEC_MAX_DRAFT + 1 <= kNgThreads, "one thread per slot of the chunk");
 
-size_t spec_picks_offset(int rows, int vocab) { return static_cast<size_t>(rows) * sample_logits_ws_row(vocab) * sizeof(uint32_t); }
+// the draft of a verify call: draft_ids [batch, k], draft_len [batch] or null (= k); sampled: the drafter SAMPLED them from
+// draft_logits [batch, k, vocab] under draft_params (llmie_spec_verify_sampled), else both are unused
+struct SpecDraft {
+    bool sampled;
+    const int32_t *draft_ids, *draft_len;
+    int k;
+    const void *draft_logits;
+    const llmie_sampling_params *draft_params;
+};
+struct SpecOut {
+    int32_t *out_tokens, *out_count, *out_accepted;
+    float *out_logprob;
+    int32_t *last_token, *cached_len;
+};
 
-template <typename T>
-void spec_rows_launch(bool ext_active, const void *logits, int rows, int vocab, int k, const llmie_sampling_params *params, const int32_t *history,
-                      int hstride, const int32_t *history_len, int happend, const int32_t *draft_ids, const int32_t *step_rows, int step,
-                      const int32_t *step_dev, int end_id, uint32_t *ws, SpecPick *picks, const llmie_sampling_ext &ext, hipStream_t st) {
-    const size_t ws_row = sample_logits_ws_row(vocab);
-    if (ext_active)
-        spec_verify_rows_kernel<T, true><<<rows, kSpThreads, 0, st>>>(static_cast<const T *>(logits), vocab, k, params, history, hstride, history_len,
-                                                                      happend, draft_ids, step_rows, step, step_dev, end_id, ws, ws_row, picks, ext);
+// the workspace: 1 (2: sampled) key rows per position, then one record per position
+size_t spec_records_offset(bool sampled, int rows, int vocab) { return (sampled ? 2 : 1) * static_cast<size_t>(rows) * sample_logits_ws_row(vocab) * sizeof(uint32_t); }
+size_t spec_workspace_bytes(bool sampled, int batch, int k, int vocab) {
+    if (batch <= 0 || k <= 0 || vocab <= 0 || k > LLMIE_SPEC_MAX_DRAFT || (sampled && vocab > kSpecSampledMaxVocab)) return 0;
+    const int rows = batch * (k + 1);
+    return spec_records_offset(sampled, rows, vocab) + static_cast<size_t>(rows) * (sampled ? sizeof(SpecSampledRec) : sizeof(SpecPick));
+}
+
+// step_rows: the per-sequence steps (wins over pos) or null
+int spec_verify_impl(const SampleRows &r, const SpecDraft &d, const SampleState &s, const SamplePos &pos, int32_t *step_rows, const SpecOut &o,
+                     SampleWs ws, const llmie_sampling_ext *ext, hipStream_t st) {
+    const char *name = d.sampled ? "spec_verify_sampled" : "spec_verify";
+    const int k = d.k;
+    // the sampler's own checks, under this entry's name
+    int rc = sample_logits_check(name, r, s, o.out_tokens);
+    if (rc != LLMIE_OK) return rc;
+    bool active;
+    if ((rc = sample_ext_check(r.batch, r.vocab, ext, &active, name)) != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(k >= 1, "%s: k %d < 1", name, k);
+    LLMIE_REQUIRE(d.draft_ids && o.out_tokens && o.out_count, "%s: NULL draft_ids / out_tokens / out_count", name);
+    if (d.sampled) LLMIE_REQUIRE(d.draft_logits && d.draft_params, "%s: NULL draft_logits / draft_params_dev", name);
+    if (k > LLMIE_SPEC_MAX_DRAFT) LLMIE_UNSUPPORTED("%s: k %d above LLMIE_SPEC_MAX_DRAFT (%d)", name, k, LLMIE_SPEC_MAX_DRAFT);
+    if (d.sampled && r.vocab > kSpecSampledMaxVocab) LLMIE_UNSUPPORTED("%s: vocab %d above %d", name, r.vocab, kSpecSampledMaxVocab);
+    const long long positions = static_cast<long long>(r.batch) * (k + 1);   // (sampled: two key rows each)
+    LLMIE_REQUIRE(positions <= INT_MAX / (d.sampled ? 2 : 1), "%s: batch * (k + 1) = %lld rows", name, positions);
+    rc = sample_workspace_check(name, ws, spec_workspace_bytes(d.sampled, r.batch, k, r.vocab),
+                                d.sampled ? "llmie_spec_verify_sampled_workspace_bytes" : "llmie_spec_verify_workspace_bytes");
+    if (rc != LLMIE_OK) return rc;
+    const int rows = static_cast<int>(positions);
+    uint32_t *keys = static_cast<uint32_t *>(ws.p);
+    void *records = static_cast<unsigned char *>(ws.p) + spec_records_offset(d.sampled, rows, r.vocab);
+    const size_t ws_row = sample_logits_ws_row(r.vocab);
+    const llmie_sampling_ext none = {};
+    const llmie_sampling_ext &e = active ? *ext : none;
+    sample_dispatch(r.dtype, active, [&](auto type, auto with_ext) {
+        using T = typename decltype(type)::type;
+        constexpr bool EXT = decltype(with_ext)::value;
+        const T *lg = static_cast<const T *>(r.logits);
+        if (d.sampled)
+            spec_sampled_rows_kernel<T, EXT><<<rows, kSpThreads, 0, st>>>(
+                lg, static_cast<const T *>(d.draft_logits), r.vocab, k, r.params, d.draft_params, s.history, s.history_stride, s.history_len,
+                s.history_append, d.draft_ids, d.draft_len, step_rows, pos.step, pos.step_dev, r.end_id, keys, ws_row,
+                static_cast<SpecSampledRec *>(records), e);
+        else
+            spec_verify_rows_kernel<T, EXT><<<rows, kSpThreads, 0, st>>>(lg, r.vocab, k, r.params, s.history, s.history_stride, s.history_len,
+                                                                        s.history_append, d.draft_ids, step_rows, pos.step, pos.step_dev, r.end_id,
+                                                                        keys, ws_row, static_cast<SpecPick *>(records), e);
+    });
+    if ((rc = launch_status(d.sampled ? "spec_verify_sampled(rows)" : "spec_verify(rows)")) != LLMIE_OK) return rc;
+    if (d.sampled)
+        spec_sampled_accept_kernel<<<r.batch, 64, 0, st>>>(static_cast<const SpecSampledRec *>(records), k, d.draft_ids, d.draft_len, s.history,
+                                                           s.history_stride, s.history_len, s.history_append, s.seq_len, s.finished, o.out_tokens,
+                                                           o.out_count, o.out_logprob, o.out_accepted, o.last_token, o.cached_len, step_rows);
     else
-        spec_verify_rows_kernel<T, false><<<rows, kSpThreads, 0, st>>>(static_cast<const T *>(logits), vocab, k, params, history, hstride, history_len,
-                                                                       happend, draft_ids, step_rows, step, step_dev, end_id, ws, ws_row, picks, ext);
+        spec_accept_kernel<<<r.batch, 64, 0, st>>>(static_cast<const SpecPick *>(records), k, d.draft_ids, d.draft_len, s.history, s.history_stride,
+                                                   s.history_len, s.history_append, s.seq_len, s.finished, o.out_tokens, o.out_count, o.out_logprob,
+                                                   o.last_token, o.cached_len, step_rows);
+    return launch_status(d.sampled ? "spec_verify_sampled(accept)" : "spec_verify(accept)");
 }
 
 }  // namespace
@@ -406,11 +467,8 @@ void spec_rows_launch(bool ext_active, const void *logits, int rows, int vocab, 
 
 using namespace llmie;
 
-extern "C" size_t llmie_spec_verify_workspace_bytes(int batch, int k, int vocab) {
-    if (batch <= 0 || k <= 0 || vocab <= 0 || k > LLMIE_SPEC_MAX_DRAFT) return 0;
-    const int rows = batch * (k + 1);
-    return spec_picks_offset(rows, vocab) + static_cast<size_t>(rows) * sizeof(SpecPick);
-}
+extern "C" size_t llmie_spec_verify_workspace_bytes(int batch, int k, int vocab) { return spec_workspace_bytes(false, batch, k, vocab); }
+extern "C" size_t llmie_spec_verify_sampled_workspace_bytes(int batch, int k, int vocab) { return spec_workspace_bytes(true, batch, k, vocab); }
 
 extern "C" int llmie_spec_verify(const void *logits, int batch, int k, int vocab, const int32_t *draft_ids, const int32_t *draft_len,
                                  const llmie_sampling_params *params_dev, int32_t *history, int history_stride, int32_t *history_len,
@@ -418,64 +476,10 @@ extern "C" int llmie_spec_verify(const void *logits, int batch, int k, int vocab
                                  float *out_logprob, int32_t *last_token, int32_t *cached_len, int32_t *step_rows, int step,
                                  const int32_t *step_dev, int end_id, void *workspace, size_t workspace_bytes, llmie_dtype dtype,
                                  llmie_stream stream, const llmie_sampling_ext *ext) {
-    // the sampler's own checks, under this entry's name (the workspace is this entry's: checked below)
-    int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_tokens, nullptr, 0,
-                                 dtype, "spec_verify", false);
-    if (rc != LLMIE_OK) return rc;
-    bool active;
-    if ((rc = sample_ext_check(batch, vocab, ext, &active, "spec_verify")) != LLMIE_OK) return rc;
-    LLMIE_REQUIRE(k >= 1, "spec_verify: k %d < 1", k);
-    LLMIE_REQUIRE(draft_ids && out_tokens && out_count, "spec_verify: NULL draft_ids / out_tokens / out_count");
-    if (k > LLMIE_SPEC_MAX_DRAFT) LLMIE_UNSUPPORTED("spec_verify: k %d above LLMIE_SPEC_MAX_DRAFT (%d)", k, LLMIE_SPEC_MAX_DRAFT);
-    LLMIE_REQUIRE(static_cast<long long>(batch) * (k + 1) <= INT_MAX, "spec_verify: batch * (k + 1) = %lld rows",
-                  static_cast<long long>(batch) * (k + 1));
-    const size_t need = llmie_spec_verify_workspace_bytes(batch, k, vocab);
-    if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
-        set_error("spec_verify: workspace %zu bytes (need %zu, 16-byte aligned: llmie_spec_verify_workspace_bytes)",
-                  workspace ? workspace_bytes : (size_t)0, need);
-        return LLMIE_ERR_WORKSPACE;
-    }
-    const int rows = batch * (k + 1);
-    uint32_t *ws = static_cast<uint32_t *>(workspace);
-    SpecPick *picks = reinterpret_cast<SpecPick *>(static_cast<unsigned char *>(workspace) + spec_picks_offset(rows, vocab));
-    const llmie_sampling_ext none = {};
-    const llmie_sampling_ext &e = active ? *ext : none;
-    hipStream_t st = as_stream(stream);
-    if (dtype == LLMIE_F16)
-        spec_rows_launch<half_t>(active, logits, rows, vocab, k, params_dev, history, history_stride, history_len, history_append, draft_ids,
-                                 step_rows, step, step_dev, end_id, ws, picks, e, st);
-    else
-        spec_rows_launch<float>(active, logits, rows, vocab, k, params_dev, history, history_stride, history_len, history_append, draft_ids,
-                                step_rows, step, step_dev, end_id, ws, picks, e, st);
-    if ((rc = launch_status("spec_verify(rows)")) != LLMIE_OK) return rc;
-    spec_accept_kernel<<<batch, 64, 0, st>>>(picks, k, draft_ids, draft_len, history, history_stride, history_len, history_append, seq_len,
-                                             finished, out_tokens, out_count, out_logprob, last_token, cached_len, step_rows);
-    return launch_status("spec_verify(accept)");
-}
-
-// two key rows per position, then the records
-static size_t spec_sampled_recs_offset(int rows, int vocab) { return 2 * static_cast<size_t>(rows) * sample_logits_ws_row(vocab) * sizeof(uint32_t); }
-
-extern "C" size_t llmie_spec_verify_sampled_workspace_bytes(int batch, int k, int vocab) {
-    if (batch <= 0 || k <= 0 || vocab <= 0 || k > LLMIE_SPEC_MAX_DRAFT || vocab > kSpecSampledMaxVocab) return 0;
-    const int rows = batch * (k + 1);
-    return spec_sampled_recs_offset(rows, vocab) + static_cast<size_t>(rows) * sizeof(SpecSampledRec);
-}
-
-template <typename T>
-static void spec_sampled_rows_launch(bool ext_active, const void *logits, const void *draft_logits, int rows, int vocab, int k,
-                                     const llmie_sampling_params *params, const llmie_sampling_params *draft_params, const int32_t *history,
-                                     int hstride, const int32_t *history_len, int happend, const int32_t *draft_ids, const int32_t *draft_len,
-                                     const int32_t *step_rows, int step, const int32_t *step_dev, int end_id, uint32_t *ws,
-                                     SpecSampledRec *recs, const llmie_sampling_ext &ext, hipStream_t st) {
-    const size_t ws_row = sample_logits_ws_row(vocab);
-    const T *lg = static_cast<const T *>(logits), *dlg = static_cast<const T *>(draft_logits);
-    if (ext_active)
-        spec_sampled_rows_kernel<T, true><<<rows, kSpThreads, 0, st>>>(lg, dlg, vocab, k, params, draft_params, history, hstride, history_len, happend,
-                                                                       draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, ws_row, recs, ext);
-    else
-        spec_sampled_rows_kernel<T, false><<<rows, kSpThreads, 0, st>>>(lg, dlg, vocab, k, params, draft_params, history, hstride, history_len, happend,
-                                                                        draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, ws_row, recs, ext);
+    return spec_verify_impl(SampleRows{logits, batch, vocab, dtype, params_dev, end_id}, SpecDraft{false, draft_ids, draft_len, k, nullptr, nullptr},
+                            SampleState{history, history_stride, history_len, history_append, seq_len, finished}, SamplePos{step, step_dev},
+                            step_rows, SpecOut{out_tokens, out_count, nullptr, out_logprob, last_token, cached_len},
+                            SampleWs{workspace, workspace_bytes}, ext, as_stream(stream));
 }
 
 extern "C" int llmie_spec_verify_sampled(const void *logits, const void *draft_logits, int batch, int k, int vocab, const int32_t *draft_ids,
@@ -485,41 +489,11 @@ extern "C" int llmie_spec_verify_sampled(const void *logits, const void *draft_l
                                          int32_t *out_count, int32_t *out_accepted, float *out_logprob, int32_t *last_token, int32_t *cached_len,
                                          int32_t *step_rows, int step, const int32_t *step_dev, int end_id, void *workspace,
                                          size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream, const llmie_sampling_ext *ext) {
-    const char *name = "spec_verify_sampled";
-    int rc = sample_logits_check(logits, batch, vocab, params_dev, history, history_stride, history_len, seq_len, finished, out_tokens, nullptr, 0,
-                                 dtype, name, false);
-    if (rc != LLMIE_OK) return rc;
-    bool active;
-    if ((rc = sample_ext_check(batch, vocab, ext, &active, name)) != LLMIE_OK) return rc;
-    LLMIE_REQUIRE(k >= 1, "%s: k %d < 1", name, k);
-    LLMIE_REQUIRE(draft_ids && out_tokens && out_count, "%s: NULL draft_ids / out_tokens / out_count", name);
-    LLMIE_REQUIRE(draft_logits && draft_params_dev, "%s: NULL draft_logits / draft_params_dev", name);
-    if (k > LLMIE_SPEC_MAX_DRAFT) LLMIE_UNSUPPORTED("%s: k %d above LLMIE_SPEC_MAX_DRAFT (%d)", name, k, LLMIE_SPEC_MAX_DRAFT);
-    if (vocab > kSpecSampledMaxVocab) LLMIE_UNSUPPORTED("%s: vocab %d above %d", name, vocab, kSpecSampledMaxVocab);
-    LLMIE_REQUIRE(static_cast<long long>(batch) * (k + 1) <= INT_MAX / 2, "%s: batch * (k + 1) = %lld rows", name,
-                  static_cast<long long>(batch) * (k + 1));
-    const size_t need = llmie_spec_verify_sampled_workspace_bytes(batch, k, vocab);
-    if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
-        set_error("%s: workspace %zu bytes (need %zu, 16-byte aligned: llmie_spec_verify_sampled_workspace_bytes)", name,
-                  workspace ? workspace_bytes : (size_t)0, need);
-        return LLMIE_ERR_WORKSPACE;
-    }
-    const int rows = batch * (k + 1);
-    uint32_t *ws = static_cast<uint32_t *>(workspace);
-    SpecSampledRec *recs = reinterpret_cast<SpecSampledRec *>(static_cast<unsigned char *>(workspace) + spec_sampled_recs_offset(rows, vocab));
-    const llmie_sampling_ext none = {};
-    const llmie_sampling_ext &e = active ? *ext : none;
-    hipStream_t st = as_stream(stream);
-    if (dtype == LLMIE_F16)
-        spec_sampled_rows_launch<half_t>(active, logits, draft_logits, rows, vocab, k, params_dev, draft_params_dev, history, history_stride,
-                                         history_len, history_append, draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, recs, e, st);
-    else
-        spec_sampled_rows_launch<float>(active, logits, draft_logits, rows, vocab, k, params_dev, draft_params_dev, history, history_stride,
-                                        history_len, history_append, draft_ids, draft_len, step_rows, step, step_dev, end_id, ws, recs, e, st);
-    if ((rc = launch_status("spec_verify_sampled(rows)")) != LLMIE_OK) return rc;
-    spec_sampled_accept_kernel<<<batch, 64, 0, st>>>(recs, k, draft_ids, draft_len, history, history_stride, history_len, history_append, seq_len,
-                                                     finished, out_tokens, out_count, out_logprob, out_accepted, last_token, cached_len, step_rows);
-    return launch_status("spec_verify_sampled(accept)");
+    return spec_verify_impl(SampleRows{logits, batch, vocab, dtype, params_dev, end_id},
+                            SpecDraft{true, draft_ids, draft_len, k, draft_logits, draft_params_dev},
+                            SampleState{history, history_stride, history_len, history_append, seq_len, finished}, SamplePos{step, step_dev},
+                            step_rows, SpecOut{out_tokens, out_count, out_accepted, out_logprob, last_token, cached_len},
+                            SampleWs{workspace, workspace_bytes}, ext, as_stream(stream));
 }
 
 extern "C" int llmie_ngram_draft(const int32_t *tokens, int stride, const int32_t *len, const uint8_t *finished, int batch, int k, int max_n,

@@ -9,6 +9,7 @@
 //
 // sampling: one lane per sequence; Philox4x32-10 keyed by (step, "LLMI"), counter = batch index.
 #include "device_utils.cuh"
+#include "llmie_internal.h"
 #include "philox.cuh"
 
 #include <climits>
@@ -138,23 +139,22 @@ __global__ __launch_bounds__(64) void topk_round2_kernel(const int32_t *__restri
     block_select<T, KMAX, 1>(tl, K, ids + static_cast<size_t>(row) * K, vals + static_cast<size_t>(row) * K, nullptr, nullptr);
 }
 
-template <typename T>
-static int topk_impl(const T *probs, int32_t *tmp_ids, T *tmp_vals, int32_t *ids, T *vals, int rows, int vocab,
-                     int K, int bpr, hipStream_t st) {
-    const bool vec_ok = vocab % Vec16<T>::n == 0 && reinterpret_cast<uintptr_t>(probs) % 16 == 0;
-    int32_t *r1_ids = (bpr == 1) ? ids : tmp_ids;
-    T *r1_vals = (bpr == 1) ? vals : tmp_vals;
-    if (K <= 8)
-        topk_round1_kernel<T, 8><<<rows * bpr, 256, 0, st>>>(probs, r1_ids, r1_vals, vocab, K, bpr, vec_ok);
-    else
-        topk_round1_kernel<T, 32><<<rows * bpr, 256, 0, st>>>(probs, r1_ids, r1_vals, vocab, K, bpr, vec_ok);
-    if (bpr > 1) {
-        if (K <= 8)
-            topk_round2_kernel<T, 8><<<rows, 64, 0, st>>>(tmp_ids, tmp_vals, ids, vals, K, bpr);
-        else
-            topk_round2_kernel<T, 32><<<rows, 64, 0, st>>>(tmp_ids, tmp_vals, ids, vals, K, bpr);
-    }
-    return launch_status("topk");
+// (dtype, K) -> the <T, KMAX> instantiation of a top-k kernel: f(TypeTag<T>{}, std::integral_constant<int, KMAX>{})
+template <class F> static void topk_dispatch(llmie_dtype dtype, int K, F f) {
+    dtype_dispatch(dtype, [&](auto type) {
+        if (K <= 8) f(type, std::integral_constant<int, 8>{});
+        else f(type, std::integral_constant<int, 32>{});
+    });
+}
+
+// round 1 into (ids, vals): K candidates of each of the bpr blocks of a row
+static void topk_round1(const void *probs, int32_t *ids, void *vals, int rows, int vocab, int K, int bpr, llmie_dtype dtype, hipStream_t st) {
+    topk_dispatch(dtype, K, [&](auto type, auto kmax) {
+        using T = typename decltype(type)::type;
+        const T *p = static_cast<const T *>(probs);
+        const bool vec_ok = vocab % Vec16<T>::n == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
+        topk_round1_kernel<T, decltype(kmax)::value><<<rows * bpr, 256, 0, st>>>(p, ids, static_cast<T *>(vals), vocab, K, bpr, vec_ok);
+    });
 }
 
 // ---------------- sampling ----------------
@@ -307,39 +307,23 @@ __global__ __launch_bounds__(64) void decode_tail_kernel(const int32_t *__restri
     }
 }
 
-int topk_round1_only(const void *probs, int32_t *tmp_ids, void *tmp_vals, int rows, int vocab, int K, int bpr, llmie_dtype dtype, hipStream_t st) {
-    if (dtype == LLMIE_F16) {
-        const half_t *p = static_cast<const half_t *>(probs);
-        const bool vec_ok = vocab % Vec16<half_t>::n == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
-        if (K <= 8) topk_round1_kernel<half_t, 8><<<rows * bpr, 256, 0, st>>>(p, tmp_ids, static_cast<half_t *>(tmp_vals), vocab, K, bpr, vec_ok);
-        else topk_round1_kernel<half_t, 32><<<rows * bpr, 256, 0, st>>>(p, tmp_ids, static_cast<half_t *>(tmp_vals), vocab, K, bpr, vec_ok);
-    } else {
-        const float *p = static_cast<const float *>(probs);
-        const bool vec_ok = vocab % Vec16<float>::n == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
-        if (K <= 8) topk_round1_kernel<float, 8><<<rows * bpr, 256, 0, st>>>(p, tmp_ids, static_cast<float *>(tmp_vals), vocab, K, bpr, vec_ok);
-        else topk_round1_kernel<float, 32><<<rows * bpr, 256, 0, st>>>(p, tmp_ids, static_cast<float *>(tmp_vals), vocab, K, bpr, vec_ok);
-    }
+int topk_round1_only(const void *probs, const TopkOperands &tk, int rows, int vocab, llmie_dtype dtype, hipStream_t st) {
+    topk_round1(probs, tk.tmp_ids, tk.tmp_vals, rows, vocab, tk.K, tk.bpr, dtype, st);
     return launch_status("topk(round 1)");
 }
 
-int decode_tail(const int32_t *tmp_ids, const void *tmp_vals, int32_t *ids, void *vals, int K, int bpr, int32_t *seq_len, uint8_t *finished,
-                int32_t *out_id, int rows, int step, int32_t *step_dev, int end_id, int vocab, const void *embed, void *next_hidden, int hidden,
-                int advance, unsigned *ticket, llmie_dtype dtype, hipStream_t st) {
-#define LLMIE_TAIL(T_, KM_)                                                                                                         \
-    decode_tail_kernel<T_, KM_><<<rows, 64, 0, st>>>(tmp_ids, static_cast<const T_ *>(tmp_vals), ids, static_cast<T_ *>(vals), K, bpr, seq_len, \
-                                                     finished, out_id, rows, step, step_dev, end_id, vocab, static_cast<const T_ *>(embed),   \
-                                                     static_cast<T_ *>(next_hidden), hidden, advance, ticket)
-    if (dtype == LLMIE_F16) {
-        if (K <= 8) LLMIE_TAIL(half_t, 8);
-        else LLMIE_TAIL(half_t, 32);
-    } else {
-        if (K <= 8) LLMIE_TAIL(float, 8);
-        else LLMIE_TAIL(float, 32);
-    }
-#undef LLMIE_TAIL
+int decode_tail(const TopkOperands &tk, const SampleRows &rows, const SampleState &state, const SamplePos &pos, int32_t *out_id,
+                const SampleTail &tail, hipStream_t st) {
+    topk_dispatch(rows.dtype, tk.K, [&](auto type, auto kmax) {
+        using T = typename decltype(type)::type;
+        // (the kernel advances *step_dev: the entry that sets tail.advance takes it writable)
+        decode_tail_kernel<T, decltype(kmax)::value><<<rows.batch, 64, 0, st>>>(
+            tk.tmp_ids, static_cast<const T *>(tk.tmp_vals), tk.ids, static_cast<T *>(tk.vals), tk.K, tk.bpr, state.seq_len, state.finished, out_id,
+            rows.batch, pos.step, const_cast<int32_t *>(pos.step_dev), rows.end_id, rows.vocab, static_cast<const T *>(tail.embed),
+            static_cast<T *>(tail.next_hidden), tail.hidden, tail.advance, tail.ticket);
+    });
     return launch_status("decode_tail");
 }
-
 
 }  // namespace llmie
 
@@ -352,13 +336,17 @@ extern "C" int llmie_topk(const void *probs, int32_t *tmp_ids, void *tmp_vals, i
     LLMIE_REQUIRE(K >= 1 && K <= 32 && K <= vocab, "topk: K=%d outside [1, min(32, vocab)]", K);
     LLMIE_REQUIRE(blocks_per_row >= 1 && blocks_per_row <= 64, "topk: blocks_per_row=%d outside [1,64]", blocks_per_row);
     LLMIE_REQUIRE(blocks_per_row == 1 || (tmp_ids && tmp_vals), "topk: tmp buffers required when blocks_per_row > 1");
-    if (dtype == LLMIE_F32)
-        return topk_impl<float>((const float *)probs, tmp_ids, (float *)tmp_vals, ids, (float *)vals, rows, vocab, K,
-                                blocks_per_row, as_stream(stream));
-    if (dtype == LLMIE_F16)
-        return topk_impl<half_t>((const half_t *)probs, tmp_ids, (half_t *)tmp_vals, ids, (half_t *)vals, rows, vocab, K,
-                                 blocks_per_row, as_stream(stream));
-    LLMIE_UNSUPPORTED("topk: dtype %d", (int)dtype);
+    if (dtype != LLMIE_F32 && dtype != LLMIE_F16) LLMIE_UNSUPPORTED("topk: dtype %d", (int)dtype);
+    hipStream_t st = as_stream(stream);
+    const bool one = blocks_per_row == 1;   // round 1 is the result
+    topk_round1(probs, one ? ids : tmp_ids, one ? vals : tmp_vals, rows, vocab, K, blocks_per_row, dtype, st);
+    if (!one)
+        topk_dispatch(dtype, K, [&](auto type, auto kmax) {
+            using T = typename decltype(type)::type;
+            topk_round2_kernel<T, decltype(kmax)::value><<<rows, 64, 0, st>>>(tmp_ids, static_cast<const T *>(tmp_vals), ids, static_cast<T *>(vals),
+                                                                             K, blocks_per_row);
+        });
+    return launch_status("topk");
 }
 
 extern "C" int llmie_sampling(const int32_t *topk_id, const void *topk_val, int32_t *seq_len, uint8_t *finished,
@@ -366,15 +354,12 @@ extern "C" int llmie_sampling(const int32_t *topk_id, const void *topk_val, int3
                               int vocab, llmie_dtype dtype, llmie_stream stream) {
     LLMIE_REQUIRE(topk_id && topk_val && seq_len && finished && out_id, "sampling: NULL pointer");
     LLMIE_REQUIRE(batch > 0 && K > 0 && vocab > 0, "sampling: bad shape");
-    const int grid = (batch + 63) / 64;
-    if (dtype == LLMIE_F32)
-        sampling_kernel<float><<<grid, 64, 0, as_stream(stream)>>>(topk_id, (const float *)topk_val, seq_len, finished,
-                                                                  out_id, batch, K, step, step_dev, end_id, vocab);
-    else if (dtype == LLMIE_F16)
-        sampling_kernel<half_t><<<grid, 64, 0, as_stream(stream)>>>(topk_id, (const half_t *)topk_val, seq_len, finished,
-                                                                   out_id, batch, K, step, step_dev, end_id, vocab);
-    else
-        LLMIE_UNSUPPORTED("sampling: dtype %d", (int)dtype);
+    if (dtype != LLMIE_F32 && dtype != LLMIE_F16) LLMIE_UNSUPPORTED("sampling: dtype %d", (int)dtype);
+    dtype_dispatch(dtype, [&](auto type) {
+        using T = typename decltype(type)::type;
+        sampling_kernel<T><<<(batch + 63) / 64, 64, 0, as_stream(stream)>>>(topk_id, static_cast<const T *>(topk_val), seq_len, finished, out_id,
+                                                                            batch, K, step, step_dev, end_id, vocab);
+    });
     return launch_status("sampling");
 }
 
