@@ -139,7 +139,11 @@ int llmie_linear_swiglu(const void *x, const void *w, void *y, int M, int K, int
  * of int8 / int4 weights as "image_prefill+<route of the fp16 GEMM>"), from the same planner the entry points launch from.
  * Pure host function: the pointers are never dereferenced (only their alignment counts), the workspace is split exactly as the
  * entry points split it.  scale / group as in _w8a16 / _w4a16 (ignored for fp16).  A call the entry point would refuse returns
- * NULL and leaves the reason in llmie_last_error().  The string is valid until the thread's next call. */
+ * NULL and leaves the reason in llmie_last_error().  The string is valid until the thread's next call.
+ * LLMIE_W_FP8: the route of llmie_linear_fp8 -- "fp8_gemv" (M <= 8, K within the GEMV's register budget), "fp8_gemm256" (the
+ * 256-row tiled GEMM on the quantised activations) or "fp8_splitk" (passes of 128 rows over the slabs); scale = the fp32 row
+ * scales, workspace as llmie_linear_fp8_workspace_bytes(M, K, N) sizes it (the activation part first, which has to be there, the
+ * slabs behind it).  LLMIE_W_MXFP4: section "MXFP4 weights" below. */
 const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const void *w, const void *scale, const void *y, int M,
                                int K, int N, int swiglu, int group, const void *bias, const void *residual,
                                const void *workspace, size_t workspace_bytes);

@@ -271,7 +271,9 @@ def linear_workspace_bytes(fmt, M, K, N):
 
 def linear_route(fmt, x, w, scale, y, M, K, N, swiglu=False, group=0, bias=None, residual=None, workspace=None, workspace_bytes=0):
     """name of the kernel route the projection entry points plan for this call, None where they refuse it (llmie_last_error() says
-    why).  The operands are ADDRESSES (ints, never dereferenced: only their alignment counts) -- no device needed."""
+    why).  The operands are ADDRESSES (ints, never dereferenced: only their alignment counts) -- no device needed.  fmt W_FP8: the
+    route of linear_fp8 ("fp8_gemv", "fp8_gemm256", "fp8_splitk"), with scale = the fp32 row scales and a workspace of
+    linear_fp8_workspace_bytes(M, K, N) bytes (the activation part, which has to be there, then the slabs)."""
     r = lib().llmie_linear_route(fmt, x, w, scale, y, M, K, N, int(swiglu), group, bias, residual, workspace, workspace_bytes)
     return r.decode() if r is not None else None
 

@@ -529,58 +529,46 @@ extern "C" int llmie_decoder_debug_stamps(llmie_decoder *dec, void *stamps_dev) 
     return LLMIE_OK;
 }
 
-// y = x . W^T (+bias)(+residual) | swiglu, dispatching on the engine's weight format
-static int engine_linear(const llmie_decoder *d, llmie_weight_format fmt, const void *x, const llmie_matrix &w,
-                         void *y, int M, int K, int N, bool swiglu, const void *residual, bool use_bias,
-                         llmie_stream stream) {
-    const void *bias = use_bias ? w.bias : nullptr;
+// ---- the engine's projections: ONE switch over the weight format.  A call on a layer matrix is a LinearOperands (proj_operands) and
+// the scratch of the sequence that makes it (decode: decode_scratch; prefill: PrefillPass::scratch); engine_proj runs it. ----
+static int wfmt_bits(llmie_weight_format fmt) {
     switch (fmt) {
-        case LLMIE_W_F16:
-            return linear_f16_nk((const half_t *)x, (const half_t *)w.data, (half_t *)y, M, K, N,
-                                 swiglu ? EPI_SWIGLU_ : EPI_NONE_, (const half_t *)bias, (const half_t *)residual, d->slab_ws,
-                                 as_stream(stream));
-        case LLMIE_W_F32:
-            if (swiglu) {
-                int rc = llmie_linear(x, w.data, d->gu, M, K, N, 1, bias, nullptr, LLMIE_F32, nullptr, 0, stream);
-                if (rc) return rc;
-                return llmie_silu_and_mul(d->gu, y, M, N / 2, LLMIE_F32, stream);
-            }
-            return llmie_linear(x, w.data, y, M, K, N, 1, bias, residual, LLMIE_F32, nullptr, 0, stream);
-        case LLMIE_W_INT8:
-        case LLMIE_W_INT4: {
-            const int bits = fmt == LLMIE_W_INT8 ? 8 : 4;
-            // GEMV (M <= 8) and split-K MFMA (int8) paths take the SwiGLU epilogue directly
-            int rc = linear_wq(bits, (const half_t *)x, w.data, (const half_t *)w.scale, (half_t *)y, M, K, N, d->cfg.int4_group,
-                               swiglu ? EPI_SWIGLU_ : EPI_NONE_, (const half_t *)bias, (const half_t *)residual, nullptr, nullptr,
-                               0.f, d->slab_ws, as_stream(stream));
-            return rc;
-        }
-        case LLMIE_W_FP8: {
-            if (swiglu) {
-                int rc = linear_fp8((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)d->gu, M, K, N,
-                                    (const half_t *)bias, nullptr, d->fp8_ws, d->fp8_ws_bytes, d->slab_ws, as_stream(stream));
-                if (rc) return rc;
-                return llmie_silu_and_mul(d->gu, y, M, N / 2, LLMIE_F16, stream);
-            }
-            return linear_fp8((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, M, K, N,
-                              (const half_t *)bias, (const half_t *)residual, d->fp8_ws, d->fp8_ws_bytes, d->slab_ws, as_stream(stream));
-        }
-        case LLMIE_W_MXFP4: {
-            // plain epilogue only: SwiGLU as projection + llmie_silu_and_mul; no image area in the decode workspace (from
-            // kWqPrefillRows rows: passes of 64 rows)
-            if (swiglu) {
-                int rc = linear_mxfp4((const half_t *)x, (const uint8_t *)w.data, (const uint8_t *)w.scale, (half_t *)d->gu, M, K, N,
-                                      (const half_t *)bias, nullptr, nullptr, 0, as_stream(stream));
-                if (rc) return rc;
-                return llmie_silu_and_mul(d->gu, y, M, N / 2, LLMIE_F16, stream);
-            }
-            return linear_mxfp4((const half_t *)x, (const uint8_t *)w.data, (const uint8_t *)w.scale, (half_t *)y, M, K, N,
-                                (const half_t *)bias, (const half_t *)residual, nullptr, 0, as_stream(stream));
-        }
-        default:
-            set_error("engine: weight format %d not supported by this build", (int)fmt);
-            return LLMIE_ERR_UNSUPPORTED;
+        case LLMIE_W_F16: return 16;
+        case LLMIE_W_INT8: return 8;
+        case LLMIE_W_INT4: return 4;
+        case LLMIE_W_FP8: return WF_FP8;
+        case LLMIE_W_MXFP4: return WF_MXFP4;
+        default: return 0;
     }
+}
+// y = [swiglu]( rmsnorm(x + pre_bias) * gamma . w^T ) (+ residual) on a matrix of the engine (the projections take no bias: the norm
+// behind the O projection adds its bias, the attention launch the QKV one)
+static LinearOperands proj_operands(const llmie_decoder_config &c, const void *x, const llmie_matrix &w, void *y, int M, int K, int N, int epi,
+                                    const void *residual, const void *gamma = nullptr, const void *pre_bias = nullptr) {
+    return LinearOperands{x, w.data, w.scale, y, M, K, N, epi, c.int4_group, nullptr, residual, gamma, pre_bias, c.rms_eps};
+}
+// decode: one slab area and the fp8 activation area; no room for an fp16 image (such row counts run their split-K or row-chunk routes)
+static LinearScratch decode_scratch(const llmie_decoder *d) { return LinearScratch{d->slab_ws, nullptr, 0, d->fp8_ws, d->fp8_ws_bytes}; }
+// gu: [M, N] scratch.  Formats without a fused SwiGLU form in linear_run (fp32, fp8 and MXFP4 weights) run it as projection +
+// llmie_silu_and_mul
+static int engine_proj(llmie_weight_format fmt, const LinearOperands &o, const LinearScratch &s, void *gu, llmie_stream stream) {
+    const bool f32 = fmt == LLMIE_W_F32;
+    if (o.epi == EPI_SWIGLU_ && (f32 || fmt == LLMIE_W_FP8 || fmt == LLMIE_W_MXFP4)) {
+        LinearOperands p = o;
+        p.y = gu, p.epi = EPI_NONE_, p.residual = nullptr;
+        if (int rc = engine_proj(fmt, p, s, gu, stream)) return rc;
+        return llmie_silu_and_mul(gu, o.y, o.M, o.N / 2, f32 ? LLMIE_F32 : LLMIE_F16, stream);
+    }
+    if (f32) return llmie_linear(o.x, o.w, o.y, o.M, o.K, o.N, 1, o.bias, o.residual, LLMIE_F32, nullptr, 0, stream);
+    if (!wfmt_bits(fmt)) {
+        set_error("engine: weight format %d not supported by this build", (int)fmt);
+        return LLMIE_ERR_UNSUPPORTED;
+    }
+    return linear_run(wfmt_bits(fmt), o, s, as_stream(stream));
+}
+// a decode-side projection (the unfused and lora sequences, the LM head)
+static int engine_linear(const llmie_decoder *d, llmie_weight_format fmt, const LinearOperands &o, llmie_stream stream) {
+    return engine_proj(fmt, o, decode_scratch(d), d->gu, stream);
 }
 
 // ---- which launch sequence a call runs: decided once, by a pure host function per entry point (no device access, no getenv) ----
@@ -821,12 +809,14 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         // every projection runs the fp16 GEMM on the unpacked image of its matrix: the fp16 forms, on the de-quantisation area
         o.qkv = rope_ok && lc.deq_bytes >= static_cast<size_t>(QKV) * H * sizeof(half_t) && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, ws, nullptr, ws)
                     ? PQ_ROPE_UNPACKED : PQ_UNPACK_PLAIN;
-        const LinearCall gc = linear_call(16, T, H, 2 * I, EPI_SWIGLU_, 0, x, ws, nullptr, ws, nullptr, nullptr, nullptr, nullptr, slabs, nullptr, 0);
+        const LinearCall gc = linear_call(16, LinearOperands{x, ws, nullptr, ws, T, H, 2 * I, EPI_SWIGLU_}, LinearScratch{slabs});
         o.gate_up = plan_linear_f16(gc).route != LR_REFUSED ? PG_UNPACK_FUSED : PG_UNPACK_TWO_LAUNCH;
         o.attn_norm = o.ffn_norm = PN_INPLACE;
     } else {
         // fp8, prefill-sized: the two RMSNorms emit the e4m3 activations of the projection behind them (norm.hip
-        // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are
+        // rmsnorm_quant_kernel; bit-identical to norm + quantize_rows) and the tiled fp8 GEMM takes them as they are.
+        // (The conditions here are the sequence's own, not plan_linear_fp8's route: a quantising norm needs a 256-row grid that FILLS
+        // -- the time model's partly filled grids quantise inside linear_fp8 -- and the fused gate/up is llmie_linear_fp8_swiglu's rule.)
         const bool nq = fp8 && T > 8 && H % 128 == 0 && rmsnorm_quant_eligible(H);
         o.attn_norm = o.ffn_norm = lean ? PN_OOP : PN_INPLACE;
         o.qkv = PQ_PLAIN;
@@ -838,8 +828,8 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         } else if (rope_ok && !fp8) {
             // int8 / int4: the route the plain projection would take -- the eight-phase int8 form, or (int4, and int8 shapes without the
             // in-kernel form) the fp16 image of the matrix -- with the epilogue on the same kernels
-            const int route = plan_linear_wq(linear_call(wqbits, T, H, QKV, EPI_NONE_, c.int4_group, x, qw, qsc, ws, nullptr, nullptr, nullptr,
-                                                         nullptr, slabs, ws, lc.deq_bytes)).route;
+            const int route = plan_linear_wq(linear_call(wqbits, LinearOperands{x, qw, qsc, ws, T, H, QKV, EPI_NONE_, c.int4_group},
+                                                         LinearScratch{slabs, ws, lc.deq_bytes})).route;
             if (route == LR_W8_G8P && gemm256_qkv_rope_eligible(G256_W8, T, QKV, H, x, qw, qsc, ws)) o.qkv = PQ_ROPE_W8;
             if (route == LR_WQ_IMAGE_PREFILL && gemm256_qkv_rope_eligible(G256_F16, T, QKV, H, x, ws, nullptr, ws)) o.qkv = PQ_ROPE_IMAGE;
         }
@@ -848,8 +838,8 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         // vector kernels do not take).  Quantised weights at prefill-sized T fuse only where the 256-row SwiGLU grid fills the chip:
         // the split-K and row-chunk forms the plan has left there cost more than the two launches.
         const bool gu_fused8 = fp8 && gemm256_swiglu_fills(T, 2 * I) && H % 128 == 0 && lc.mis_gu_w == 0;
-        const LinearCall gc = linear_call(wqbits ? wqbits : 16, T, H, 2 * I, EPI_SWIGLU_, c.int4_group, x, gw, gsc, ws, nullptr, nullptr, nullptr, nullptr,
-                                          slabs, wqbits ? ws : nullptr, lc.deq_bytes);
+        const LinearCall gc = linear_call(wqbits ? wqbits : 16, LinearOperands{x, gw, gsc, ws, T, H, 2 * I, EPI_SWIGLU_, c.int4_group},
+                                          LinearScratch{slabs, wqbits ? ws : nullptr, lc.deq_bytes});
         if (nq && gu_fused8 && lc.ffn_gamma && lc.mis_gu_scale == 0) o.ffn_norm = PN_QUANT, o.gate_up = PG_E4M3_SWIGLU;
         else if (fp8) o.gate_up = gu_fused8 ? PG_FP8_SWIGLU : PG_TWO_LAUNCH;
         else if (wqbits) o.gate_up = (T < kWqPrefillRows || gemm256_swiglu_fills(T, 2 * I)) && plan_linear_wq(gc).route != LR_REFUSED ? PG_FUSED : PG_TWO_LAUNCH;
@@ -957,30 +947,16 @@ struct DecodeStep {
         // separate 4.8 us merge kernel on MI355X, 2.97 vs 2.81 ms per token: every workgroup pays the release fence; the engine
         // always uses the merge kernel)
         // y = [swiglu]( rmsnorm(x + pre_bias)*gamma . W^T ) + residual on the streaming GEMV of the weight format
+        const LinearScratch scratch = decode_scratch(dec);
         auto lin = [&](const void *x, const llmie_matrix &w, void *y, int K, int N, int epi, const void *residual,
                        const void *gamma, const void *pre_bias) -> int {
-            if (fp8) {
-                // e4m3 weights x per-token e4m3 activations; the GEMV handles K rows that fit its register budget,
-                // longer ones (down projection at batch > 2) take the MFMA launch sequence of llmie_linear_fp8
-                if (ksplit_eligible(batch, K, 8))
-                    return linear_fp8_gemv((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, batch,
-                                           K, N, epi, nullptr, (const half_t *)residual, (const half_t *)gamma,
-                                           (const half_t *)pre_bias, c.rms_eps, st);
-                // (plan_decode: a projection with a fused norm or SwiGLU has K = H, which the plan found GEMV-eligible)
-                return linear_fp8((const half_t *)x, (const uint8_t *)w.data, (const float *)w.scale, (half_t *)y, batch, K, N, nullptr,
-                                  (const half_t *)residual, dec->fp8_ws, dec->fp8_ws_bytes, dec->slab_ws, st);
-            }
-            if (wbits == 16) {
-                if (gamma)
-                    return linear_f16_nk_norm((const half_t *)x, (const half_t *)w.data, (half_t *)y, batch, K, N, epi, nullptr,
-                                              (const half_t *)residual, (const half_t *)gamma, (const half_t *)pre_bias,
-                                              c.rms_eps, st);
-                return linear_f16_nk((const half_t *)x, (const half_t *)w.data, (half_t *)y, batch, K, N, epi, nullptr,
-                                     (const half_t *)residual, dec->slab_ws, st);
-            }
-            return linear_wq(wbits, (const half_t *)x, w.data, (const half_t *)w.scale, (half_t *)y, batch, K, N, c.int4_group,
-                             epi, nullptr, (const half_t *)residual, (const half_t *)gamma, (const half_t *)pre_bias,
-                             c.rms_eps, dec->slab_ws, st);
+            const LinearOperands o = proj_operands(c, x, w, y, batch, K, N, epi, residual, gamma, pre_bias);
+            // fp8 (e4m3 weights x per-token e4m3 activations): this sequence takes the GEMV wherever K fits its register budget, AHEAD of
+            // plan_linear_fp8's shape rules (which ask K % 256 == 0 of every call: an inter_size of 1376 decodes on the GEMV); longer
+            // rows (down projection at batch > 2) take what linear_fp8 plans.  (plan_decode: a projection with a fused norm or
+            // SwiGLU has K = H, which the plan found GEMV-eligible)
+            if (fp8 && ksplit_eligible(batch, K, 8)) return linear_fp8_gemv(o, st);
+            return engine_proj(c.wfmt, o, scratch, dec->gu, stream);
         };
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
@@ -1001,27 +977,38 @@ struct DecodeStep {
     //   actx = swiglu(rmsnorm(hx + o.bias) * g2 . Wgu^T)
     //   hx  += actx . Wd^T                          K split over workgroups (K = inter_size) + one reduce launch
     // Same math as self_decoder.cpp:69-119.  Weights come from the tile-packed images built at create time.
+    // The four projections of layer l on its packed images.  first: the layer reads the caller's row-major hidden state (from its O
+    // projection on, the residual stream lives in the x32 image hx); last: its down projection writes the hidden state back row-major
+    struct PackedLayerOps {
+        PkOperands qkv, o, gate_up, down;
+    };
+    PackedLayerOps pk_layer(int l, bool first, bool last) const {
+        const llmie_layer_weights &w = dec->layers[l];
+        const llmie_decoder::PackedLayer &pw = dec->packed[l];
+        half_t *hh = static_cast<half_t *>(h), *qkvb = reinterpret_cast<half_t *>(dec->qkv);
+        // (int4: the packed group-scale image; else the caller's row scales)
+        auto sc = [&](int i, const llmie_matrix &m) -> const void * { return pw.sc[i] ? pw.sc[i] : m.scale; };
+        auto f16 = [](const void *p) { return static_cast<const half_t *>(p); };
+        return PackedLayerOps{
+            {first ? hh : dec->hx, pw.qkv, sc(0, w.qkv), qkvb, H, QKV, PKE_PLAIN, first ? 0 : PKX_X, nullptr, f16(w.attn_norm_gamma), nullptr, c.rms_eps,
+             nullptr, 0},
+            {dec->mhax, pw.o, sc(1, w.o), dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES), first ? hh : dec->hx, nullptr, nullptr, 0.f,
+             nullptr, 0},
+            {dec->hx, pw.gate_up, sc(2, w.gate_up), dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr, f16(w.ffn_norm_gamma), f16(w.o.bias),
+             c.rms_eps, nullptr, 0},
+            {dec->actx, pw.down, sc(3, w.down), last ? hh : dec->hx, I, H, PKE_PLAIN, PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr,
+             0.f, dec->pk_slab, dec->pk_slab_floats}};
+    }
     int packed() const {
         int rc;
         const int wf = dec->pk_wf;
-        half_t *hh = static_cast<half_t *>(h);
-        half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
         for (int l = 0; l < c.num_layers; ++l) {
-            const llmie_layer_weights &w = dec->layers[l];
-            const llmie_decoder::PackedLayer &pw = dec->packed[l];
-            const bool first = l == 0, last = l + 1 == c.num_layers;
-            // layer 0 reads the caller's row-major hidden state; from its output projection on the residual stream lives in hx
-            TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, first ? hh : dec->hx, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, batch, H, QKV, PKE_PLAIN, first ? 0 : PKX_X,
-                                               nullptr, static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0, st));
-            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
-            TIMED(LLMIE_OP_O_GEMM, pk_linear(wf, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, batch, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES),
-                                             first ? hh : dec->hx, nullptr, nullptr, 0.f, nullptr, 0, st));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, pk_linear(wf, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, batch, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y,
-                                                     nullptr, static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias),
-                                                     c.rms_eps, nullptr, 0, st));
-            TIMED(LLMIE_OP_DOWN_GEMM, pk_linear(wf, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, last ? hh : dec->hx, batch, I, H, PKE_PLAIN,
-                                                PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr, 0.f, dec->pk_slab,
-                                                dec->pk_slab_floats, st));
+            const PackedLayerOps p = pk_layer(l, l == 0, l + 1 == c.num_layers);
+            TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, batch, p.qkv, st));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, dec->layers[l].qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
+            TIMED(LLMIE_OP_O_GEMM, pk_linear(wf, batch, p.o, st));
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, pk_linear(wf, batch, p.gate_up, st));
+            TIMED(LLMIE_OP_DOWN_GEMM, pk_linear(wf, batch, p.down, st));
         }
         return LLMIE_OK;
     }
@@ -1035,49 +1022,26 @@ struct DecodeStep {
     // probe: can every projection of a layer join a chain at this batch?  (pk_chain_add validates shapes / plans / LDS)
     bool chain_joins() const {
         if (!dec->pk_sync) return false;
-        const int wf = dec->pk_wf;
-        half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
-        const llmie_layer_weights &w = dec->layers[0];
-        const llmie_decoder::PackedLayer &pw = dec->packed[0];
+        const PackedLayerOps p = pk_layer(0, false, false);   // a middle layer's operands
         PkChain ch;
-        pk_chain_begin(&ch, wf, batch);
-        return ch.ok &&
-                !pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | PKX_RES, dec->hx, nullptr, nullptr, 0.f, nullptr, 0) &&
-                !pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
-                              static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0) &&
-                !pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, dec->hx, I, H, PKE_PLAIN, PKX_X | PKX_RES | PKX_Y, dec->hx, nullptr, nullptr,
-                              0.f, dec->pk_slab, dec->pk_slab_floats) &&
-                (c.num_layers == 1 ||
-                 !pk_chain_add(&ch, 4, dec->hx, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
-                               static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0));
+        pk_chain_begin(&ch, dec->pk_wf, batch);
+        return ch.ok && !pk_chain_add(&ch, 0, p.o) && !pk_chain_add(&ch, 1, p.gate_up) && !pk_chain_add(&ch, 2, p.down) &&
+               (c.num_layers == 1 || !pk_chain_add(&ch, 4, p.qkv));
     }
     int packed_chain() const {
         int rc;
         const int wf = dec->pk_wf;
-        half_t *hh = static_cast<half_t *>(h);
-        half_t *qkvb = reinterpret_cast<half_t *>(dec->qkv);
         for (int l = 0; l < c.num_layers; ++l) {
-            const llmie_layer_weights &w = dec->layers[l];
-            const llmie_decoder::PackedLayer &pw = dec->packed[l];
             const bool first = l == 0, last = l + 1 == c.num_layers;
-            if (first)
-                TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, hh, pw.qkv, pw.sc[0] ? pw.sc[0] : w.qkv.scale, qkvb, batch, H, QKV, PKE_PLAIN, 0, nullptr,
-                                                   static_cast<const half_t *>(w.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0, st));
-            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
+            const PackedLayerOps p = pk_layer(l, first, last);
+            if (first) TIMED(LLMIE_OP_QKV_GEMM, pk_linear(wf, batch, p.qkv, st));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, dec->layers[l].qkv.bias, dec->mhax, l, nullptr, nullptr, 1));
             PkChain ch;
             pk_chain_begin(&ch, wf, batch);
-            rc = pk_chain_add(&ch, 0, dec->mhax, pw.o, pw.sc[1] ? pw.sc[1] : w.o.scale, dec->hx, H, H, PKE_PLAIN, PKX_X | PKX_Y | (first ? 0 : PKX_RES),
-                              first ? hh : dec->hx, nullptr, nullptr, 0.f, nullptr, 0);
-            if (!rc) rc = pk_chain_add(&ch, 1, dec->hx, pw.gate_up, pw.sc[2] ? pw.sc[2] : w.gate_up.scale, dec->actx, H, 2 * I, PKE_SWIGLU, PKX_X | PKX_Y, nullptr,
-                                       static_cast<const half_t *>(w.ffn_norm_gamma), static_cast<const half_t *>(w.o.bias), c.rms_eps, nullptr, 0);
-            if (!rc) rc = pk_chain_add(&ch, 2, dec->actx, pw.down, pw.sc[3] ? pw.sc[3] : w.down.scale, last ? hh : dec->hx, I, H, PKE_PLAIN,
-                                       PKX_X | PKX_RES | (last ? 0 : PKX_Y), dec->hx, nullptr, nullptr, 0.f, dec->pk_slab, dec->pk_slab_floats);
-            if (!rc && !last) {
-                const llmie_layer_weights &wn = dec->layers[l + 1];
-                const llmie_decoder::PackedLayer &pn = dec->packed[l + 1];
-                rc = pk_chain_add(&ch, 4, dec->hx, pn.qkv, pn.sc[0] ? pn.sc[0] : wn.qkv.scale, qkvb, H, QKV, PKE_PLAIN, PKX_X, nullptr,
-                                  static_cast<const half_t *>(wn.attn_norm_gamma), nullptr, c.rms_eps, nullptr, 0);
-            }
+            rc = pk_chain_add(&ch, 0, p.o);
+            if (!rc) rc = pk_chain_add(&ch, 1, p.gate_up);
+            if (!rc) rc = pk_chain_add(&ch, 2, p.down);
+            if (!rc && !last) rc = pk_chain_add(&ch, 4, pk_layer(l + 1, false, false).qkv);
             if (rc) return rc;
             ch.stamps = dec->pk_stamps;   // (diagnostic; null unless llmie_decoder_debug_stamps armed it)
             TIMED(LLMIE_OP_CHAIN, pk_chain_launch(&ch, dec->pk_sync + static_cast<size_t>(l) * (pk_chain_sync_bytes() / sizeof(unsigned)), dec->pk_err, st));
@@ -1155,7 +1119,7 @@ int DecodeStep::unfused() const {
         // self_decoder.cpp:77  resid = h ; h = rmsnorm(h)
         TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, dec->resid, w.attn_norm_gamma, c.rms_eps, batch, H, dt, stream));
         // self_attention.cpp:79  qkv = h . Wqkv^T   (bias is applied inside the MHA kernel, as the reference)
-        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, h, w.qkv, dec->qkv, batch, H, QKV, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, h, w.qkv, dec->qkv, batch, H, QKV, EPI_NONE_, nullptr), stream));
         if (fused_rope) {
             // :100-:108 RoPE at position step-1 + fused masked MHA with KV append, one launch (+ merge)
             TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
@@ -1167,14 +1131,14 @@ int DecodeStep::unfused() const {
             TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l, nullptr, nullptr, 0, false));
         }
         // :131 output projection (no bias here: the fused norm below adds o.bias, self_decoder.cpp:92-98)
-        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, dec->mha, w.o, h, batch, H, H, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->mha, w.o, h, batch, H, H, EPI_NONE_, nullptr), stream));
         // self_decoder.cpp:92  h += resid; resid = h; h += o.bias; h = rmsnorm(h, ffn_gamma)
         TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(dec->resid, h, w.o.bias, w.ffn_norm_gamma,
                                                                        c.rms_eps, batch, H, dt, stream));
         // ffn.cpp:105-122  act = silu(h.Wg^T) * (h.Wu^T)
-        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, h, w.gate_up, dec->act, batch, H, 2 * I, true, nullptr, false, stream));
+        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, proj_operands(c, h, w.gate_up, dec->act, batch, H, 2 * I, EPI_SWIGLU_, nullptr), stream));
         // ffn.cpp:132 + self_decoder.cpp:111  h = act . Wd^T + resid
-        TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, dec->act, w.down, h, batch, I, H, false, dec->resid, false, stream));
+        TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->act, w.down, h, batch, I, H, EPI_NONE_, dec->resid), stream));
     }
     return LLMIE_OK;
 }
@@ -1206,7 +1170,7 @@ int DecodeStep::lora() const {
     for (int l = 0; l < c.num_layers; ++l) {
         const llmie_layer_weights &w = dec->layers[l];
         TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, dec->resid, w.attn_norm_gamma, c.rms_eps, batch, H, dt, stream));
-        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, h, w.qkv, dec->qkv, batch, H, QKV, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, h, w.qkv, dec->qkv, batch, H, QKV, EPI_NONE_, nullptr), stream));
         TIMED(LLMIE_OP_QKV_GEMM, engine_lora(dec, h, dec->qkv, batch, H, QKV, 3, qkv_w, l, LLMIE_LORA_QKV, stream));
         if (fused_attention_geometry(c)) {
             TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
@@ -1215,13 +1179,13 @@ int DecodeStep::lora() const {
                                                    c.rotary_dim, c.rotary_base, dt, stream));
             TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l, nullptr, nullptr, 0, false));
         }
-        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, dec->mha, w.o, h, batch, H, H, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->mha, w.o, h, batch, H, H, EPI_NONE_, nullptr), stream));
         TIMED(LLMIE_OP_O_GEMM, engine_lora(dec, dec->mha, h, batch, H, H, 1, &H, l, LLMIE_LORA_O, stream));
         TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(dec->resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, batch, H, dt, stream));
-        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, h, w.gate_up, dec->gu, batch, H, 2 * I, false, nullptr, false, stream));
+        TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, proj_operands(c, h, w.gate_up, dec->gu, batch, H, 2 * I, EPI_NONE_, nullptr), stream));
         TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_lora(dec, h, dec->gu, batch, H, 2 * I, 2, gu_w, l, LLMIE_LORA_GATE_UP, stream));
         TIMED(LLMIE_OP_GATE_UP_SWIGLU, llmie_silu_and_mul(dec->gu, dec->act, batch, I, dt, stream));
-        TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, dec->act, w.down, h, batch, I, H, false, dec->resid, false, stream));
+        TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->act, w.down, h, batch, I, H, EPI_NONE_, dec->resid), stream));
         TIMED(LLMIE_OP_DOWN_GEMM, engine_lora(dec, dec->act, h, batch, I, H, 1, &H, l, LLMIE_LORA_DOWN, stream));
     }
     return LLMIE_OK;
@@ -1391,17 +1355,11 @@ struct PrefillPass {
     // e4m3 rows + token scales the quantising norms leave for the projection behind them
     uint8_t *xqn() const { return static_cast<uint8_t *>(f8ws); }
     float *xsn() const { return reinterpret_cast<float *>(xqn() + ((static_cast<size_t>(T) * H + 255) & ~static_cast<size_t>(255))); }
-    // y = x . W^T (+ residual) in the engine's weight format (fp8: per-token e4m3 activations, fp8 MFMA)
-    int proj(const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual) const {
-        if (c.wfmt == LLMIE_W_MXFP4)   // (from kWqPrefillRows rows: the fp16 image of the matrix in `deq` + the fp16 GEMM)
-            return linear_mxfp4(x, (const uint8_t *)w.data, (const uint8_t *)w.scale, y, T, K, N, nullptr, residual, deq, deq_bytes, st);
-        if (wqbits)
-            return linear_wq(wqbits, x, w.data, (const half_t *)w.scale, y, T, K, N, c.int4_group, EPI_NONE_, nullptr, residual, nullptr,
-                             nullptr, 0.f, slabs, st, deq, deq_bytes);
-        if (fp8)
-            return linear_fp8(x, (const uint8_t *)w.data, (const float *)w.scale, y, T, K, N, nullptr, residual, f8ws, f8ws_bytes,
-                              slabs, st);
-        return linear_f16_nk(x, (const half_t *)w.data, y, T, K, N, EPI_NONE_, nullptr, residual, slabs, st);
+    // the pass's scratch: the split-K slabs, the area of the fp16 image of quantised (int8 / int4 / MXFP4) weights, the fp8 activations
+    LinearScratch scratch() const { return LinearScratch{slabs, deq, deq_bytes, f8ws, f8ws_bytes}; }
+    // y = [swiglu]( x . W^T ) (+ residual) in the engine's weight format (fp8: per-token e4m3 activations, fp8 MFMA)
+    int proj(const half_t *x, const llmie_matrix &w, half_t *y, int K, int N, const half_t *residual, int epi = EPI_NONE_) const {
+        return engine_proj(c.wfmt, proj_operands(c, x, w, y, T, K, N, epi, residual), scratch(), gu, stream);
     }
     // the two norms of the lean (out of place: h stays the residual stream) and general sequences
     int norm_form(int form) const { return (path == PP_LEAN) == (form == PN_OOP) ? form : -1; }
@@ -1455,10 +1413,7 @@ struct PrefillPass {
         int rc;
         switch (form) {
             case PG_FUSED:
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU,
-                      wqbits ? linear_wq(wqbits, x, w.data, (const half_t *)w.scale, act, T, H, 2 * I, c.int4_group, EPI_SWIGLU_, nullptr, nullptr, nullptr,
-                                         nullptr, 0.f, slabs, st, deq, deq_bytes)
-                             : linear_f16_nk(x, (const half_t *)w.data, act, T, H, 2 * I, EPI_SWIGLU_, nullptr, nullptr, slabs, st));
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, proj(x, w, act, H, 2 * I, nullptr, EPI_SWIGLU_));
                 return LLMIE_OK;
             case PG_E4M3_SWIGLU:
                 TIMED(LLMIE_OP_GATE_UP_SWIGLU, (gemm256_swiglu_launch(G256_E4M3, xqn(), w.data, act, T, 2 * I, H, xsn(), (const float *)w.scale, st),
@@ -1486,7 +1441,7 @@ struct PrefillPass {
             }
             int rc2 = pk_unpack_f16(dec->pk_wf, img, static_cast<const half_t *>(scale), static_cast<half_t *>(deq), N, K, swiglu_img, st);
             if (rc2) return rc2;
-            return linear_f16_nk(x, static_cast<const half_t *>(deq), y, T, K, N, epi, nullptr, residual, slabs, st);
+            return linear_f16_nk(LinearOperands{x, deq, nullptr, y, T, K, N, epi, 0, nullptr, residual}, LinearScratch{slabs}, st);
         };
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
@@ -1848,15 +1803,15 @@ static int lm_head_logits(const LmHeadCall &call, bool tail_operands) {
     if (call.fmt == LLMIE_W_F16 && c.dtype == LLMIE_F16 && gemv_f16_eligible(batch, dec->H, call.hidden, call.head->data) &&
         !engine_switches().no_fused_decode) {
         // final RMSNorm fused into the LM-head GEMV prologue (hidden itself is left un-normalised)
-        TIMED(LLMIE_OP_LM_HEAD, linear_f16_nk_norm((const half_t *)call.hidden, (const half_t *)call.head->data, (half_t *)call.logits, batch,
-                                                   dec->H, c.vocab_size, EPI_NONE_, (const half_t *)call.head->bias, nullptr,
-                                                   (const half_t *)call.gamma, nullptr, c.rms_eps, as_stream(stream)));
+        LinearOperands o = proj_operands(c, call.hidden, *call.head, call.logits, batch, dec->H, c.vocab_size, EPI_NONE_, nullptr, call.gamma);
+        o.bias = call.head->bias;
+        TIMED(LLMIE_OP_LM_HEAD, linear_f16_nk(o, LinearScratch{}, as_stream(stream)));
     } else {
         // llama.cpp:247  final RMSNorm (the residual copy is unused there: pass NULL)
         TIMED(LLMIE_OP_FINAL_NORM, llmie_rmsnorm(call.hidden, nullptr, call.gamma, c.rms_eps, batch, dec->H, c.dtype, stream));
         // llama.cpp:282  logits = hidden . lm_head^T
-        TIMED(LLMIE_OP_LM_HEAD, engine_linear(dec, call.fmt, call.hidden, *call.head, call.logits, batch, dec->H, c.vocab_size, false, nullptr,
-                                              false, stream));
+        TIMED(LLMIE_OP_LM_HEAD, engine_linear(dec, call.fmt, proj_operands(c, call.hidden, *call.head, call.logits, batch, dec->H, c.vocab_size,
+                                                                           EPI_NONE_, nullptr), stream));
     }
     return LLMIE_OK;
 }

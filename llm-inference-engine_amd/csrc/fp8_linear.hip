@@ -81,15 +81,15 @@ int quantize_rows_fp8(const half_t *x, uint8_t *xq, float *xscale, int M, int K,
     return launch_status("quantize_rows_fp8");
 }
 
-int linear_fp8_gemv(const half_t *x, const uint8_t *wq, const float *wscale, half_t *y, int M, int K, int N, int epi,
-                    const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
-                    hipStream_t st) {
-    if (!ksplit_eligible(M, K, 8) || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) % 16 ||
-        (gamma && (reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(pre_bias)) % 16)) {
+int linear_fp8_gemv(const LinearOperands &o, hipStream_t st) {
+    const int M = o.M, K = o.K;
+    if (!ksplit_eligible(M, K, 8) || (mis16(o.x) | mis16(o.w)) != 0 || (o.gamma && (mis16(o.gamma) | mis16(o.pre_bias)) != 0)) {
         set_error("linear_fp8: shape M=%d K=%d not on the GEMV path", M, K);
         return LLMIE_ERR_UNSUPPORTED;
     }
-    const GemvArgs a{x, wq, y, K, N, bias, residual, gamma, pre_bias, eps, epi, gamma ? 1 : 0, wscale, 0};
+    const GemvArgs a{static_cast<const half_t *>(o.x), o.w, static_cast<half_t *>(o.y), K, o.N, static_cast<const half_t *>(o.bias),
+                     static_cast<const half_t *>(o.residual), static_cast<const half_t *>(o.gamma), static_cast<const half_t *>(o.pre_bias),
+                     o.eps, o.epi, o.gamma ? 1 : 0, o.scale, 0};
     if (!gemv_fp8_launch(M, a, st)) {
         set_error("linear_fp8: no GEMV instantiation for M=%d K=%d", M, K);
         return LLMIE_ERR_UNSUPPORTED;
@@ -97,72 +97,27 @@ int linear_fp8_gemv(const half_t *x, const uint8_t *wq, const float *wscale, hal
     return launch_status("linear_fp8(gemv)");
 }
 
-}  // namespace llmie
-
-using namespace llmie;
-
-static size_t fp8_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
-
-static size_t fp8_act_bytes(int M, int K) {   // quantised activations + per-token scales
-    return fp8_align(static_cast<size_t>(M) * K) + fp8_align(static_cast<size_t>(M) * sizeof(float));
-}
-extern "C" size_t llmie_linear_fp8_workspace_bytes(int M, int K, int N) {
-    if (M <= 0 || K <= 0 || N < 0) return 0;
-    // quantised activations + per-token scales, then the fp32 slabs of the split-K form (below the tiled GEMM's sizes: 8 < M, and
-    // M <= 8 where K is past the GEMV's register budget -- 3 .. 8 rows of K = 11008 run split-K too);
-    // N = 0: the activation part only (llmie_linear_fp8_swiglu)
-    const bool splitk = M > 8 || !ksplit_eligible(M, K, 8);
-    return fp8_act_bytes(M, K) + (N > 0 && splitk ? fp8_align(linear_splitk_ws_floats(WF_FP8, M, K, N) * sizeof(float)) : 0);
-}
-
-extern "C" int llmie_quantize_fp8(const void *w, uint8_t *wq, float *scale, int N, int K, llmie_stream stream) {
-    LLMIE_REQUIRE(w && wq && scale && N > 0 && K > 0 && K % 4 == 0, "quantize_fp8: bad arguments (K %% 4 == 0)");
-    return quantize_rows_fp8((const half_t *)w, wq, scale, N, K, as_stream(stream));
-}
-
-namespace llmie {
-static bool fp8_tiled(const void *w_scale, const void *bias, const void *residual, int M, int K, int N) {
-    if (!(M > 8 && K % 128 == 0 && N % 4 == 0 && reinterpret_cast<uintptr_t>(w_scale) % 16 == 0 &&
-          (reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) % 8 == 0))
-        return false;
-    if (gemm256_fills(M, N)) return true;
-    // (round 3) a grid that does not fill the chip against split-K passes of 128 rows, by the time model fitted to the sweep
-    // (tools/dev/s2_run27.sh; us): O / down of a 7B layer 41 / 90 tiled at any row count, 18.9 / 22.3 per pass -- at 768 tokens
-    // the six passes took 113 / 134 us
-    if (M <= 128 || !gemm8p_fits(N, K, 1)) return false;
-    const float t_tiles = static_cast<float>(gemm256_narrow_rounds(M, N)) * (K / 128) * 1.15f;
-    const float t_passes = ((M + 127) / 128) * (static_cast<float>(N) * K / 8.3e6f + 17.f);
-    return t_tiles < t_passes;
-}
-// llmie_linear_fp8 with its two scratch areas apart: `act_ws` (>= llmie_linear_fp8_workspace_bytes(M, K, 0), 256-byte aligned)
-// receives the quantised activations, `slabs` the split-K partial sums (engine: one slab area serves every projection)
-int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half_t *y, int M, int K, int N, const half_t *bias,
-               const half_t *residual, void *act_ws, size_t act_ws_bytes, SlabWs slabs, hipStream_t st) {
-    const bool tiled = fp8_tiled(w_scale, bias, residual, M, K, N);
-    if ((!tiled && (K % 256 != 0 || K < 512)) || reinterpret_cast<uintptr_t>(w_fp8) % 16 || reinterpret_cast<uintptr_t>(act_ws) % 256) {
-        set_error("linear_fp8: needs K %% 256 == 0, K >= 512 (K %% 128 == 0 for prefill-sized M x N), 16-byte aligned weights, "
-                  "256-byte aligned workspace");
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    if (act_ws_bytes < fp8_act_bytes(M, K)) {
-        set_error("linear_fp8: workspace too small (%zu < %zu bytes)", act_ws_bytes, fp8_act_bytes(M, K));
-        return LLMIE_ERR_WORKSPACE;
-    }
-    if (M <= 8 && ksplit_eligible(M, K, 8) && reinterpret_cast<uintptr_t>(x) % 16 == 0)
-        return linear_fp8_gemv(x, w_fp8, w_scale, y, M, K, N, EPI_NONE, bias, residual, nullptr, nullptr, 0.f, st);
-    uint8_t *xq = static_cast<uint8_t *>(act_ws);
+int linear_fp8(const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
+    const LinearCall c = linear_call(WF_FP8, o, s);
+    const LinearPlan p = plan_linear_fp8(c);
+    if (p.route == LR_REFUSED) return linear_refuse(c, p);
+    if (p.route == LR_FP8_GEMV) return linear_fp8_gemv(o, st);
+    const int M = o.M, K = o.K, N = o.N;
+    const half_t *bias = static_cast<const half_t *>(o.bias), *residual = static_cast<const half_t *>(o.residual);
+    const float *w_scale = static_cast<const float *>(o.scale);
+    half_t *y = static_cast<half_t *>(o.y);
+    uint8_t *xq = static_cast<uint8_t *>(s.act);
     float *xscale = reinterpret_cast<float *>(xq + fp8_align(static_cast<size_t>(M) * K));
-    int rc = quantize_rows_fp8(x, xq, xscale, M, K, st);
+    int rc = quantize_rows_fp8(static_cast<const half_t *>(o.x), xq, xscale, M, K, st);
     if (rc) return rc;
-    if (tiled) {
-        // prefill-sized: MFMA-bound tiled GEMM on v_mfma_scale_f32_16x16x128_f8f6f4
-        gemm256_launch(G256_E4M3, xq, w_fp8, y, M, N, K, bias, residual, xscale, w_scale, st);
+    if (p.route == LR_FP8_GEMM256) {
+        gemm256_launch(G256_E4M3, xq, o.w, y, M, N, K, bias, residual, xscale, w_scale, st);
         return launch_status("linear_fp8(gemm256)");
     }
-    for (int m0 = 0; m0 < M; m0 += 128) {
-        const int mc = M - m0 < 128 ? M - m0 : 128;
+    for (int m0 = 0; m0 < M; m0 += p.pass_rows) {   // LR_FP8_SPLITK
+        const int mc = M - m0 < p.pass_rows ? M - m0 : p.pass_rows;
         SplitKSlabs sk;
-        rc = linear_splitk_partial(WF_FP8, xq + static_cast<size_t>(m0) * K, w_fp8, mc, K, N, st, &sk, slabs);
+        rc = linear_splitk_partial(WF_FP8, xq + static_cast<size_t>(m0) * K, o.w, mc, K, N, st, &sk, s.slabs);
         if (rc) return rc;
         rc = splitk_finalize(sk, SlabScale{nullptr, w_scale, xscale + m0}, y + static_cast<size_t>(m0) * N, EPI_NONE, bias,
                              residual ? residual + static_cast<size_t>(m0) * N : nullptr, st);
@@ -170,7 +125,24 @@ int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half
     }
     return launch_status("linear_fp8");
 }
+
 }  // namespace llmie
+
+using namespace llmie;
+
+extern "C" size_t llmie_linear_fp8_workspace_bytes(int M, int K, int N) {
+    if (M <= 0 || K <= 0 || N < 0) return 0;
+    // quantised activations + per-token scales, then the fp32 slabs of the split-K form wherever the shape's plan is not the GEMV (also
+    // under the tiled GEMM's sizes -- more than that route needs, kept: callers share one workspace across row counts);
+    // N = 0: the activation part only (llmie_linear_fp8_swiglu)
+    const bool splitk = N > 0 && plan_linear_fp8(linear_call_sizing(WF_FP8, M, K, N, EPI_NONE)).route != LR_FP8_GEMV;
+    return fp8_act_bytes(M, K) + (splitk ? fp8_align(linear_splitk_ws_floats(WF_FP8, M, K, N) * sizeof(float)) : 0);
+}
+
+extern "C" int llmie_quantize_fp8(const void *w, uint8_t *wq, float *scale, int N, int K, llmie_stream stream) {
+    LLMIE_REQUIRE(w && wq && scale && N > 0 && K > 0 && K % 4 == 0, "quantize_fp8: bad arguments (K %% 4 == 0)");
+    return quantize_rows_fp8((const half_t *)w, wq, scale, N, K, as_stream(stream));
+}
 
 extern "C" int llmie_linear_fp8(const void *x, const uint8_t *w_fp8, const float *w_scale, void *y, int M, int K, int N,
                                 const void *bias, const void *residual, void *workspace, size_t workspace_bytes,
@@ -183,8 +155,8 @@ extern "C" int llmie_linear_fp8(const void *x, const uint8_t *w_fp8, const float
         return LLMIE_ERR_WORKSPACE;
     }
     const SlabWs slabs{reinterpret_cast<float *>(static_cast<char *>(workspace) + act), (workspace_bytes - act) / sizeof(float)};
-    return linear_fp8((const half_t *)x, w_fp8, w_scale, (half_t *)y, M, K, N, (const half_t *)bias, (const half_t *)residual,
-                      workspace, act, slabs, as_stream(stream));
+    return linear_fp8(LinearOperands{x, w_fp8, w_scale, y, M, K, N, EPI_NONE, 0, bias, residual}, LinearScratch{slabs, nullptr, 0, workspace, act},
+                      as_stream(stream));
 }
 
 extern "C" int llmie_linear_fp8_swiglu(const void *x, const uint8_t *w_fp8, const float *w_scale, void *y, int M, int K,

@@ -458,9 +458,14 @@ int linear_splitk_partial(int wbits, const void *x, const void *W, int M, int K,
 }
 
 // split-K skinny MFMA path: 8 < M (any M, 128 rows of x per pass); wbits 16 or 8
-int linear_splitk(int wbits, const half_t *x, const void *W, const half_t *scale, half_t *y, int M, int K, int N, int epi,
-                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st) {
+int linear_splitk(int wbits, const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
     // wbits 8: `scale` = per-row fp16 scales applied by the finalize; wbits 4: `scale` = group-128 scales applied in the kernel
+    const half_t *x = static_cast<const half_t *>(o.x), *scale = static_cast<const half_t *>(o.scale);
+    const half_t *bias = static_cast<const half_t *>(o.bias), *residual = static_cast<const half_t *>(o.residual);
+    half_t *y = static_cast<half_t *>(o.y);
+    const void *W = o.w;
+    const int M = o.M, K = o.K, N = o.N, epi = o.epi;
+    const SlabWs ws = s.slabs;
     const int mpass = wbits == 4 ? 64 : kSplitKPassRows;
     const int out_n = epi == EPI_SWIGLU ? N / 2 : N;
     for (int m0 = 0; m0 < M; m0 += mpass) {
@@ -586,18 +591,6 @@ int splitk_rownorm(const SplitKSlabs &sk, const SlabScale &wscale, const half_t 
 // does the GEMV family take (M, K)?
 bool gemv_f16_eligible(int M, int K, const void *x, const void *W) {
     return (mis16(x) | mis16(W)) == 0 && gemv_f16_route(M, K) != LR_REFUSED;
-}
-
-int linear_f16_nk_norm(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi, const half_t *bias,
-                       const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, hipStream_t st) {
-    if (!gemv_f16_eligible(M, K, x, W) || !gamma || reinterpret_cast<uintptr_t>(gamma) % 16 ||
-        reinterpret_cast<uintptr_t>(pre_bias) % 16) {
-        set_error("linear(norm-fused): shape M=%d K=%d not on the GEMV path", M, K);
-        return LLMIE_ERR_UNSUPPORTED;
-    }
-    const GemvArgs a{x, W, y, K, N, bias, residual, gamma, pre_bias, eps, epi, 1, nullptr, 0};
-    dispatch_gemv(M, a, st);
-    return launch_status("linear(norm-fused)");
 }
 
 // ---- the 256-row tiled GEMM family: gemm8p.cuh (eight-phase; 32-bit DMA offsets) and gemm256.cuh (two-stage, any size); fp16
@@ -814,18 +807,17 @@ void gemm256_qkv_rope_launch(G256Operands ops, const void *x, const void *W, hal
 }
 
 // ---- route planning: which kernel a projection runs on.  Pure host code: no HIP call, no error text, no launch. ----
-LinearCall linear_call(int bits, int M, int K, int N, int epi, int group, const void *x, const void *w, const void *scale, const void *y,
-                       const void *bias, const void *residual, const void *gamma, const void *pre_bias, SlabWs ws, const void *image,
-                       size_t image_bytes) {
-    return LinearCall{bits, M, K, N, epi, group, bias != nullptr, residual != nullptr, gamma != nullptr, pre_bias != nullptr,
-                      mis16(x), mis16(w), mis16(y), mis16(bias), mis16(residual), mis16(gamma), mis16(pre_bias), mis16(scale), mis16(image),
-                      ws.p != nullptr, ws.p ? ws.floats : 0, image != nullptr, image ? image_bytes : 0};
+LinearCall linear_call(int bits, const LinearOperands &o, const LinearScratch &s) {
+    return LinearCall{bits, o.M, o.K, o.N, o.epi, o.group, o.bias != nullptr, o.residual != nullptr, o.gamma != nullptr, o.pre_bias != nullptr,
+                      mis16(o.x), mis16(o.w), mis16(o.y), mis16(o.bias), mis16(o.residual), mis16(o.gamma), mis16(o.pre_bias), mis16(o.scale),
+                      mis16(s.image), s.slabs.p != nullptr, s.slabs.p ? s.slabs.floats : 0, s.image != nullptr, s.image ? s.image_bytes : 0,
+                      s.act != nullptr, s.act ? s.act_bytes : 0, static_cast<unsigned>(reinterpret_cast<uintptr_t>(s.act) % 256)};
 }
 LinearCall linear_call_sizing(int bits, int M, int K, int N, int epi, int group) {
     LinearCall c{};
     c.bits = bits, c.M = M, c.K = K, c.N = N, c.epi = epi, c.group = group;
-    c.slabs = c.image = true;
-    c.slab_floats = c.image_bytes = ~static_cast<size_t>(0);
+    c.slabs = c.image = c.act = true;
+    c.slab_floats = c.image_bytes = c.act_bytes = ~static_cast<size_t>(0);
     return c;
 }
 
@@ -845,6 +837,10 @@ LinearPlan plan_linear_f16(const LinearCall &c) {
     const bool swiglu = c.epi == EPI_SWIGLU;
     const bool aligned = K % 8 == 0 && (c.mis_x | c.mis_w) == 0;
     const bool epi8 = (c.mis_bias | c.mis_residual) % 8 == 0;
+    // a fused norm rides on the GEMV routes only
+    if (c.gamma || c.pre_bias)
+        return aligned && c.gamma && (c.mis_gamma | c.mis_pre_bias) == 0 && gemv_f16_route(M, K) != LR_REFUSED ? planned(gemv_f16_route(M, K))
+                                                                                                                 : refused(LREF_F16_NORM);
     if (aligned && gemv_f16_route(M, K) != LR_REFUSED) return planned(gemv_f16_route(M, K));
     // decode / short-prefill batches: split-K over the caller's slabs (without a workspace: the non-split kernels below).
     // Round 3, 192 < M where the eight-phase kernels' 256-row grid does not fill the chip (N = 4096 at 256-1023 tokens): such
@@ -974,6 +970,33 @@ LinearPlan plan_linear_wq(const LinearCall &c) {
     return refused(LREF_WQ_SHAPE);
 }
 
+// e4m3 weights x per-token e4m3 activations (fp8_linear.hip): the GEMV (M <= 8, K within its register budget; the only route with a
+// fused norm or SwiGLU), the 256-row tiled GEMM on the quantised activations, or split-K passes of 128 rows over the caller's slabs.
+LinearPlan plan_linear_fp8(const LinearCall &c) {
+    const int M = c.M, K = c.K, N = c.N;
+    const bool gemv = M <= 8 && ksplit_eligible(M, K, 8) && c.mis_x == 0;
+    if (c.gamma || c.pre_bias || c.epi != EPI_NONE)
+        return gemv && c.mis_w == 0 && (!c.gamma || (c.mis_gamma | c.mis_pre_bias) == 0) ? planned(LR_FP8_GEMV) : refused(LREF_FP8_GEMV);
+    bool tiled = M > 8 && K % 128 == 0 && N % 4 == 0 && c.mis_scale == 0 && (c.mis_bias | c.mis_residual) % 8 == 0;
+    if (tiled && !gemm256_fills(M, N)) {
+        // (round 3) a grid that does not fill the chip against split-K passes of 128 rows, by the time model fitted to the sweep
+        // (tools/dev/s2_run27.sh; us): O / down of a 7B layer 41 / 90 tiled at any row count, 18.9 / 22.3 per pass -- at 768 tokens
+        // the six passes took 113 / 134 us
+        tiled = M > 128 && gemm8p_fits(N, K, 1);
+        if (tiled) {
+            const float t_tiles = static_cast<float>(gemm256_narrow_rounds(M, N)) * (K / 128) * 1.15f;
+            const float t_passes = ((M + 127) / 128) * (static_cast<float>(N) * K / 8.3e6f + 17.f);
+            tiled = t_tiles < t_passes;
+        }
+    }
+    if ((!tiled && (K % 256 != 0 || K < 512)) || c.mis_w != 0 || c.mis_act != 0) return refused(LREF_FP8_SHAPE);
+    if (c.act_bytes < fp8_act_bytes(M, K)) return refused(LREF_FP8_ACT);
+    if (gemv) return planned(LR_FP8_GEMV);
+    // prefill-sized: MFMA-bound tiled GEMM on v_mfma_scale_f32_16x16x128_f8f6f4
+    if (tiled) return planned(LR_FP8_GEMM256);
+    return planned_splitk(c, LR_FP8_SPLITK, kSplitKPassRows);
+}
+
 // fp16 scratch to reserve beside the slabs for an int8 / int4 projection of M rows.  From kWqPrefillRows rows on: room for the whole
 // image, also where the plan needs none (the int8 eight-phase and split-K routes) -- more than the plan needs, kept: callers share
 // one workspace across shapes.  Below: int8 reserves what the plan needs (the last-resort image of shapes no int8 kernel takes);
@@ -997,7 +1020,7 @@ const char *linear_route_name(int route) {
     static const char *const names[] = {"refused", "gemv_ksplit", "gemv_lds", "splitk", "splitk_passes", "skinny", "swiglu256", "tiles256",
                                         "tiles256_part", "tiles128", "generic", "g8p", "g8p_swiglu", "int8_splitk_passes", "image_prefill",
                                         "image_last", "gemv_ksplit", "int4_splitk", "int4_chunks", "int8_splitk", "int8_skinny", "mxfp4_gemv",
-                                        "mxfp4_mfma", "mxfp4_chunks"};
+                                        "mxfp4_mfma", "mxfp4_chunks", "fp8_gemv", "fp8_gemm256", "fp8_splitk"};
     return names[route];
 }
 
@@ -1026,6 +1049,19 @@ int linear_refuse(const LinearCall &c, const LinearPlan &p) {
         case LREF_MX4_EPI:
             set_error("linear_mxfp4: plain epilogue (bias, residual) only: no fused norm or SwiGLU form (M=%d K=%d N=%d)", M, K, N);
             return LLMIE_ERR_UNSUPPORTED;
+        case LREF_F16_NORM:
+            set_error("linear(norm-fused): shape M=%d K=%d not on the GEMV path", M, K);
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_FP8_SHAPE:
+            set_error("linear_fp8: needs K %% 256 == 0, K >= 512 (K %% 128 == 0 for prefill-sized M x N), 16-byte aligned weights, "
+                      "256-byte aligned workspace");
+            return LLMIE_ERR_UNSUPPORTED;
+        case LREF_FP8_ACT:
+            set_error("linear_fp8: workspace too small (%zu < %zu bytes)", c.act_bytes, fp8_act_bytes(M, K));
+            return LLMIE_ERR_WORKSPACE;
+        case LREF_FP8_GEMV:
+            set_error("linear_fp8: shape M=%d K=%d not on the GEMV path", M, K);
+            return LLMIE_ERR_UNSUPPORTED;
         default:
             set_error("linear_wq: unsupported shape M=%d K=%d N=%d bits=%d without a split-K workspace (int8: M<=64, K%%64==0; int4: "
                       "M<=8 on the GEMV path); size one with llmie_linear_workspace_bytes()", M, K, N, c.bits);
@@ -1033,18 +1069,26 @@ int linear_refuse(const LinearCall &c, const LinearPlan &p) {
     }
 }
 
-int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
-                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st) {
-    const LinearCall c = linear_call(16, M, K, N, epi, 0, x, W, nullptr, y, bias, residual, nullptr, nullptr, ws, nullptr, 0);
+int linear_f16_nk(const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
+    const LinearCall c = linear_call(16, o, s);
     const LinearPlan p = plan_linear_f16(c);
+    const half_t *x = static_cast<const half_t *>(o.x), *W = static_cast<const half_t *>(o.w);
+    const half_t *bias = static_cast<const half_t *>(o.bias), *residual = static_cast<const half_t *>(o.residual);
+    half_t *y = static_cast<half_t *>(o.y);
+    const int M = o.M, K = o.K, N = o.N, epi = o.epi;
     switch (p.route) {
         case LR_GEMV_KSPLIT:
         case LR_GEMV_LDS:
+            if (o.gamma) {
+                dispatch_gemv(M, GemvArgs{x, W, y, K, N, bias, residual, static_cast<const half_t *>(o.gamma), static_cast<const half_t *>(o.pre_bias),
+                                          o.eps, epi, 1, nullptr, 0}, st);
+                return launch_status("linear(norm-fused)");
+            }
             dispatch_gemv(M, GemvArgs{x, W, y, K, N, bias, residual, nullptr, nullptr, 0.f, epi, 0, nullptr, 0}, st);
             return launch_status("linear");
         case LR_SPLITK:
         case LR_SPLITK_PASSES:
-            return linear_splitk(16, x, W, nullptr, y, M, K, N, epi, bias, residual, ws, st);
+            return linear_splitk(16, o, s, st);
         case LR_SKINNY:
             if (epi == EPI_SWIGLU) dispatch_skinny<EPI_SWIGLU>(M, x, W, y, K, N, bias, residual, st);
             else dispatch_skinny<EPI_NONE>(M, x, W, y, K, N, bias, residual, st);
@@ -1069,6 +1113,17 @@ int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int
             return launch_status("linear");
         default:
             return linear_refuse(c, p);
+    }
+}
+
+int linear_run(int bits, const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
+    switch (bits) {
+        case 16: return linear_f16_nk(o, s, st);
+        case 8:
+        case 4: return linear_wq(bits, o, s, st);
+        case WF_FP8: return linear_fp8(o, s, st);
+        case WF_MXFP4: return linear_mxfp4(o, s, st);
+        default: set_error("linear: weight format code %d not supported by this build", bits); return LLMIE_ERR_UNSUPPORTED;
     }
 }
 
@@ -1111,9 +1166,7 @@ extern "C" int llmie_linear(const void *x, const void *w, void *y, int M, int K,
     LLMIE_REQUIRE(slab_ws_of(workspace, workspace_bytes, &ws), "linear: workspace must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (dtype == LLMIE_F16) {
-        if (trans_b)
-            return linear_f16_nk((const half_t *)x, (const half_t *)w, (half_t *)y, M, K, N, EPI_NONE,
-                                 (const half_t *)bias, (const half_t *)residual, ws, st);
+        if (trans_b) return linear_f16_nk(LinearOperands{x, w, nullptr, y, M, K, N, EPI_NONE, 0, bias, residual}, LinearScratch{ws}, st);
         launch_generic<half_t>((const half_t *)x, (const half_t *)w, (half_t *)y, 1, M, N, K, false,
                                (const half_t *)bias, (const half_t *)residual, st);
         return launch_status("linear");
@@ -1133,35 +1186,41 @@ extern "C" int llmie_linear_swiglu(const void *x, const void *w, void *y, int M,
     if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("linear_swiglu: fp16 only (dtype %d)", (int)dtype);
     SlabWs ws;
     LLMIE_REQUIRE(slab_ws_of(workspace, workspace_bytes, &ws), "linear_swiglu: workspace must be 16-byte aligned");
-    return linear_f16_nk((const half_t *)x, (const half_t *)w, (half_t *)y, M, K, two_inter, EPI_SWIGLU, nullptr,
-                         nullptr, ws, as_stream(stream));
+    return linear_f16_nk(LinearOperands{x, w, nullptr, y, M, K, two_inter, EPI_SWIGLU}, LinearScratch{ws}, as_stream(stream));
 }
 
 extern "C" const char *llmie_linear_route(llmie_weight_format fmt, const void *x, const void *w, const void *scale, const void *y, int M,
                                           int K, int N, int swiglu, int group, const void *bias, const void *residual,
                                           const void *workspace, size_t workspace_bytes) {
-    const int bits = fmt == LLMIE_W_F16 ? 16 : (fmt == LLMIE_W_INT8 ? 8 : (fmt == LLMIE_W_INT4 ? 4 : (fmt == LLMIE_W_MXFP4 ? WF_MXFP4 : 0)));
+    const int bits = fmt == LLMIE_W_F16 ? 16 : (fmt == LLMIE_W_INT8 ? 8 : (fmt == LLMIE_W_INT4 ? 4 : (fmt == LLMIE_W_MXFP4 ? WF_MXFP4 : (fmt == LLMIE_W_FP8 ? WF_FP8 : 0))));
     const int epi = swiglu ? EPI_SWIGLU : EPI_NONE;
     static thread_local char name[48];
     auto fail = [](const char *what) -> const char * {
         set_error("linear_route: %s", what);
         return nullptr;
     };
-    if (!bits) return fail("fp16, int8, int4 and MXFP4 weights only");
+    if (!bits) return fail("fp16, int8, int4, fp8 and MXFP4 weights only");
     if (!x || !w || !y || (bits != 16 && !scale)) return fail("NULL pointer");
     if (M <= 0 || K <= 0 || N <= 0 || (swiglu && (N % 2 || bias || residual))) return fail("bad shape or epilogue");
     if (bits == 4 && !(group > 0 && group % 32 == 0 && K % group == 0)) return fail("group must be a multiple of 32 dividing K");
     if (mis16(workspace)) return fail("workspace must be 16-byte aligned");
     void *wsp = const_cast<void *>(workspace);
-    LinearCall c;
+    const LinearOperands o{x, w, bits == 16 ? nullptr : scale, const_cast<void *>(y), M, K, N, epi, bits == 4 ? group : 0, bias, residual};
+    LinearScratch s{};
     if (bits == 16) {
-        c = linear_call(16, M, K, N, epi, 0, x, w, nullptr, y, bias, residual, nullptr, nullptr,
-                        SlabWs{static_cast<float *>(wsp), workspace_bytes / sizeof(float)}, nullptr, 0);
+        s.slabs = SlabWs{static_cast<float *>(wsp), workspace_bytes / sizeof(float)};
+    } else if (bits == WF_FP8) {
+        // as llmie_linear_fp8 splits its workspace: the activation part, which has to be there, then the slabs
+        const size_t act = fp8_act_bytes(M, K);
+        if (!wsp) return fail("fp8 weights need a workspace (llmie_linear_fp8_workspace_bytes)");
+        if (workspace_bytes < act) return fail("fp8 workspace too small for the quantised activations (llmie_linear_fp8_workspace_bytes)");
+        s = LinearScratch{SlabWs{reinterpret_cast<float *>(static_cast<char *>(wsp) + act), (workspace_bytes - act) / sizeof(float)}, nullptr, 0, wsp, act};
     } else {
         const WqWorkspace ws = wq_workspace(bits, M, K, N, wsp, workspace_bytes);
-        c = linear_call(bits, M, K, N, epi, bits == 4 ? group : 0, x, w, scale, y, bias, residual, nullptr, nullptr, ws.slabs, ws.deq, ws.deq_bytes);
+        s = LinearScratch{ws.slabs, ws.deq, ws.deq_bytes};
     }
-    const LinearPlan p = bits == 16 ? plan_linear_f16(c) : plan_linear_wq(c);
+    const LinearCall c = linear_call(bits, o, s);
+    const LinearPlan p = bits == 16 ? plan_linear_f16(c) : (bits == WF_FP8 ? plan_linear_fp8(c) : plan_linear_wq(c));
     if (p.route == LR_REFUSED) {
         linear_refuse(c, p);
         return nullptr;

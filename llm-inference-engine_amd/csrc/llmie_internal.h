@@ -29,10 +29,34 @@ enum LinearRoute : int {
     LR_W8_SPLITK, LR_W8_SKINNY,
     // MXFP4 weights (mxfp4_linear.hip)
     LR_MX4_GEMV, LR_MX4_MFMA, LR_MX4_CHUNKS,
+    // e4m3 weights x per-token e4m3 activations (fp8_linear.hip)
+    LR_FP8_GEMV, LR_FP8_GEMM256, LR_FP8_SPLITK,
 };
-enum LinearRefusal : int { LREF_NONE = 0, LREF_F16_SWIGLU, LREF_SLABS, LREF_W4_SPLITK, LREF_WQ_NORM, LREF_WQ_SWIGLU, LREF_WQ_SHAPE, LREF_MX4_SHAPE, LREF_MX4_EPI };
-// One projection call as the planners see it: shape, epilogue, which operands are there and how far each pointer is from 16-byte
-// alignment (address % 16; 0 for a null pointer), and the caller's scratch.  bits = 16: fp16 weights (group / scale / image unused).
+enum LinearRefusal : int {
+    LREF_NONE = 0, LREF_F16_SWIGLU, LREF_SLABS, LREF_W4_SPLITK, LREF_WQ_NORM, LREF_WQ_SWIGLU, LREF_WQ_SHAPE, LREF_MX4_SHAPE, LREF_MX4_EPI,
+    LREF_F16_NORM, LREF_FP8_SHAPE, LREF_FP8_ACT, LREF_FP8_GEMV,
+};
+// ---- a projection call, from the C entry (or the engine) to the launch: two structs.  A new operand is added to LinearOperands, at the
+// entries that fill it, in linear_call() where a planner has to see it, and at the launch that reads it.  The weight format (`bits`:
+// 16 / 8 / 4, WF_FP8, WF_MXFP4) decides the element types behind the void pointers: x, y, bias, residual, gamma, pre_bias are fp16 in
+// every format; scale is fp16 per row (int8) or per group (int4), fp32 per row (fp8), e8m0 bytes per 32 k (MXFP4), unused (fp16).
+struct LinearOperands {   // y = [swiglu]( rmsnorm(x + pre_bias) * gamma . w^T ) (+ bias) (+ residual); gamma null: no norm
+    const void *x, *w, *scale;
+    void *y;
+    int M, K, N, epi, group;   // epi: EPI_NONE_ / EPI_SWIGLU_ (N = two_inter, y is [M, N / 2]); group: int4 scale group
+    const void *bias, *residual, *gamma, *pre_bias;
+    float eps;
+};
+struct LinearScratch {    // caller-owned, each area optional (null): a route that needs a missing one is not planned, or refused
+    SlabWs slabs;                     // fp32 split-K slabs
+    void *image;                      // fp16 image of quantised weights
+    size_t image_bytes;
+    void *act;                        // fp8: e4m3 activations + per-token scales (fp8_act_bytes, 256-byte aligned)
+    size_t act_bytes;
+};
+// The call as the planners see it: shape, epilogue, which operands are there and how far each pointer is from 16-byte alignment
+// (address % 16; 0 for a null pointer; the fp8 activation area: % 256), and the caller's scratch.  bits = 16: fp16 weights (group /
+// scale / image unused).
 struct LinearCall {
     int bits, M, K, N, epi, group;
     bool bias, residual, gamma, pre_bias;
@@ -41,6 +65,9 @@ struct LinearCall {
     size_t slab_floats;
     bool image;            // scratch for the fp16 image of quantised weights present
     size_t image_bytes;
+    bool act;              // fp8 activation scratch present
+    size_t act_bytes;
+    unsigned mis_act;      // its address % 256
 };
 struct LinearPlan {
     int route;             // LinearRoute
@@ -53,22 +80,21 @@ struct LinearPlan {
 inline unsigned mis16(const void *p) { return static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) % 16); }
 // the call with every pointer aligned, no bias / residual / norm and all the scratch a route may ask for: what the size queries plan
 LinearCall linear_call_sizing(int bits, int M, int K, int N, int epi, int group = 128);
-LinearCall linear_call(int bits, int M, int K, int N, int epi, int group, const void *x, const void *w, const void *scale, const void *y,
-                       const void *bias, const void *residual, const void *gamma, const void *pre_bias, SlabWs ws, const void *image,
-                       size_t image_bytes);
+LinearCall linear_call(int bits, const LinearOperands &o, const LinearScratch &s);
 LinearPlan plan_linear_f16(const LinearCall &c);
 LinearPlan plan_linear_wq(const LinearCall &c);
+LinearPlan plan_linear_fp8(const LinearCall &c);
 const char *linear_route_name(int route);
 int linear_refuse(const LinearCall &c, const LinearPlan &p);   // sets the refusal's error text, returns its error code
 // slab floats to reserve for an fp16 projection of M rows (>= the plan's: see linear.hip)
 size_t linear_f16_reserve_slab_floats(int M, int K, int N);
-int linear_f16_nk(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi,
-                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st);
-
-// same with rmsnorm(x + pre_bias) * gamma fused in front (GEMV path only; LLMIE_ERR_UNSUPPORTED otherwise)
+// The projection in the weight format `bits`: plans the call with the format's planner and launches the plan, or refuses.  Every call
+// site of the engine comes through here; the per-format launchers below are what it switches over.
+int linear_run(int bits, const LinearOperands &o, const LinearScratch &s, hipStream_t st);
+// fp16 weights W[N, K] (linear.hip).  gamma: rmsnorm(x + pre_bias) * gamma fused in front -- the GEMV routes only
+// (LLMIE_ERR_UNSUPPORTED otherwise, so that the caller can run the norm as its own kernel)
+int linear_f16_nk(const LinearOperands &o, const LinearScratch &s, hipStream_t st);
 bool gemv_f16_eligible(int M, int K, const void *x, const void *W);
-int linear_f16_nk_norm(const half_t *x, const half_t *W, half_t *y, int M, int K, int N, int epi, const half_t *bias,
-                       const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, hipStream_t st);
 
 // split-K skinny MFMA GEMM (fp16 or int8 weights), any M processed 64 tokens per pass; epi may be SwiGLU; linear.hip
 // partial products of a split-K projection: fp32 slabs [KS][M][N] in the caller's SlabWs
@@ -95,8 +121,7 @@ bool rmsnorm_oop_eligible(int hidden);
 int rmsnorm_oop_f16(const half_t *x, half_t *y, const half_t *gamma, float eps, int tokens, int hidden, hipStream_t st);
 // per-token e4m3 quantisation of fp16 rows (scale amax/448); fp8_linear.hip
 int quantize_rows_fp8(const half_t *x, uint8_t *xq, float *xscale, int M, int K, hipStream_t st);
-int linear_splitk(int wbits, const half_t *x, const void *W, const half_t *scale, half_t *y, int M, int K, int N, int epi,
-                  const half_t *bias, const half_t *residual, SlabWs ws, hipStream_t st);
+int linear_splitk(int wbits, const LinearOperands &o, const LinearScratch &s, hipStream_t st);
 // The 256-row tiled GEMM family (gemm8p.cuh eight-phase, gemm256.cuh two-stage; K % 64 == 0 fp16, K % 128 == 0 fp8; 16-byte aligned
 // operands); linear.hip.  Operand formats: fp16; e4m3 weights and activations (xscale per token, wscale per weight row, fp32); int8
 // weights [N, K] under fp16 activations (`wscale` carries their fp16 per-row scales).  The values are llmie_gemm256_tiles' codes.
@@ -147,26 +172,25 @@ WqWorkspace wq_workspace(int wbits, int M, int K, int N, void *workspace, size_t
 // image of the matrix (the route from kWqPrefillRows rows), or null
 constexpr int kMx4GemvRows = 8, kMx4MfmaRows = 64;
 int dequantize_mxfp4_f16(const uint8_t *wq, const uint8_t *scale, half_t *w16, int N, int K, hipStream_t st);
-int linear_mxfp4(const half_t *x, const uint8_t *wq, const uint8_t *scale, half_t *y, int M, int K, int N, const half_t *bias,
-                 const half_t *residual, void *image, size_t image_bytes, hipStream_t st);
+int linear_mxfp4(const LinearOperands &o, const LinearScratch &s, hipStream_t st);
 // quantised-weight (int8 / int4) decode GEMV on the K-split kernel; defined in linear.hip
 struct GemvArgs;
 bool ksplit_eligible(int M, int K, int wbits);
 void gemv_q_launch(int wbits, int M, const GemvArgs &a, hipStream_t st);   // needs ksplit_eligible(M, K, wbits)
 bool gemv_fp8_launch(int M, const GemvArgs &a, hipStream_t st);
 // fp8 linear on the GEMV path (M <= 8, ksplit_eligible(M, K, 8)); optional fused norm prologue / SwiGLU epilogue; fp8_linear.hip
-int linear_fp8_gemv(const half_t *x, const uint8_t *wq, const float *wscale, half_t *y, int M, int K, int N, int epi,
-                    const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
-                    hipStream_t st);
-// llmie_linear_fp8 with the activation scratch and the split-K slabs as separate areas; fp8_linear.hip
-int linear_fp8(const half_t *x, const uint8_t *w_fp8, const float *w_scale, half_t *y, int M, int K, int N, const half_t *bias,
-               const half_t *residual, void *act_ws, size_t act_ws_bytes, SlabWs slabs, hipStream_t st);
+int linear_fp8_gemv(const LinearOperands &o, hipStream_t st);
+// e4m3 weights: launches what plan_linear_fp8 plans.  The activation scratch (>= fp8_act_bytes(M, K), 256-byte aligned) receives the
+// quantised activations, the slabs the split-K partial sums (engine: one slab area serves every projection); fp8_linear.hip
+inline size_t fp8_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+inline size_t fp8_act_bytes(int M, int K) {   // quantised activations + per-token scales
+    return fp8_align(static_cast<size_t>(M) * K) + fp8_align(static_cast<size_t>(M) * sizeof(float));
+}
+int linear_fp8(const LinearOperands &o, const LinearScratch &s, hipStream_t st);
 // weight-only int8/int4 linear with optional fused norm prologue / SwiGLU epilogue (quant_linear.hip): launches what
 // plan_linear_wq plans -- at M >= kWqPrefillRows int8 through the eight-phase kernels' int8 form where eligible, else (and int4) a
-// de-quantised fp16 image in `deq` + the fp16 GEMM; without `deq` those shapes keep the split-K passes
-int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,
-              int epi, const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
-              SlabWs ws, hipStream_t st, void *deq = nullptr, size_t deq_bytes = 0);
+// de-quantised fp16 image in the scratch's image area + the fp16 GEMM; without one those shapes keep the split-K passes
+int linear_wq(int wbits, const LinearOperands &o, const LinearScratch &s, hipStream_t st);
 
 // ---- packed-weight batch-decode projections (pk_gemm.cuh / pk_linear.hip): 1 <= M <= 32 rows on tile-packed weight images ----
 enum : int { PKF_F16 = 16, PKF_I8 = 8, PKF_I4 = 4, PKF_FP8 = 108 };                 // = PK_F16 ... of pk_gemm.cuh
@@ -179,9 +203,19 @@ int pk_pack(int wf, const void *src, const void *src_scale, void *dst, void *dst
 int pk_unpack_f16(int wf, const void *packed, const half_t *scale, half_t *w16, int N, int K, int swiglu, hipStream_t st);
 bool pk_eligible(int wf, int M, int K, int N, int epi);
 size_t pk_slab_floats(int wf, int M, int K, int N);
-int pk_linear(int wf, const half_t *x, const void *Wp, const void *scale, half_t *y, int M, int K, int N, int epi, int x32_flags,
-              const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, float *slab_ws, size_t slab_ws_floats,
-              hipStream_t st);
+// one projection on a packed image: y = [swiglu]( rmsnorm(x + pre_bias) * gamma . W^T ) (+ residual); x32_flags: PKX_*; the slabs
+// serve a K split over workgroups (null: none).  What pk_linear launches and pk_chain_add makes a phase of.
+struct PkOperands {
+    const half_t *x;
+    const void *Wp, *scale;
+    half_t *y;
+    int K, N, epi, x32_flags;
+    const half_t *residual, *gamma, *pre_bias;
+    float eps;
+    float *slab_ws;
+    size_t slab_ws_floats;
+};
+int pk_linear(int wf, int M, const PkOperands &o, hipStream_t st);
 int x32_convert(const half_t *src, half_t *dst, int M, int K, int to_x32, hipStream_t st);
 // Persistent chain (pk_chain_kernel): up to 5 dependent phases -- each a pk_linear of the same format and row count whose x is an
 // x32 image -- in ONE launch with grid barriers in between and the next phase's weight ring prefetched across each barrier.
@@ -194,8 +228,7 @@ struct PkChain {
     alignas(16) unsigned char args[1024];
 };
 void pk_chain_begin(PkChain *ch, int wf, int M);
-int pk_chain_add(PkChain *ch, int slot /* 0 = O, 1 = gate/up, 2 = down, 4 = next QKV */, const half_t *x, const void *Wp, const void *scale, half_t *y, int K, int N, int epi, int x32_flags,
-                 const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, float *slab_ws, size_t slab_ws_floats);
+int pk_chain_add(PkChain *ch, int slot /* 0 = O, 1 = gate/up, 2 = down, 4 = next QKV */, const PkOperands &o);
 int pk_chain_launch(PkChain *ch, unsigned *sync, unsigned *err, hipStream_t st);
 size_t pk_chain_sync_bytes();
 

@@ -308,11 +308,13 @@ int dequantize_mxfp4_f16(const uint8_t *wq, const uint8_t *scale, half_t *w16, i
     return launch_status("dequantize_mxfp4");
 }
 
-int linear_mxfp4(const half_t *x, const uint8_t *wq, const uint8_t *scale, half_t *y, int M, int K, int N, const half_t *bias,
-                 const half_t *residual, void *image, size_t image_bytes, hipStream_t st) {
-    const LinearCall c = linear_call(WF_MXFP4, M, K, N, EPI_NONE_, 0, x, wq, scale, y, bias, residual, nullptr, nullptr, SlabWs{nullptr, 0},
-                                     image, image_bytes);
+int linear_mxfp4(const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
+    const LinearCall c = linear_call(WF_MXFP4, o, s);
     const LinearPlan p = plan_linear_wq(c);
+    const half_t *x = static_cast<const half_t *>(o.x), *bias = static_cast<const half_t *>(o.bias), *residual = static_cast<const half_t *>(o.residual);
+    const uint8_t *wq = static_cast<const uint8_t *>(o.w), *scale = static_cast<const uint8_t *>(o.scale);
+    half_t *y = static_cast<half_t *>(o.y);
+    const int M = o.M, K = o.K, N = o.N;
     switch (p.route) {
         case LR_MX4_GEMV:
             mxfp4_gemv_launch(x, wq, scale, y, M, K, N, bias, residual, st);
@@ -328,9 +330,11 @@ int linear_mxfp4(const half_t *x, const uint8_t *wq, const uint8_t *scale, half_
             }
             return launch_status("linear_mxfp4(row chunks)");
         case LR_WQ_IMAGE_PREFILL: {
-            const int rc = dequantize_mxfp4_f16(wq, scale, static_cast<half_t *>(image), N, K, st);
+            const int rc = dequantize_mxfp4_f16(wq, scale, static_cast<half_t *>(s.image), N, K, st);
             if (rc) return rc;
-            return linear_f16_nk(x, static_cast<const half_t *>(image), y, M, K, N, EPI_NONE_, bias, residual, SlabWs{nullptr, 0}, st);
+            LinearOperands f = o;   // the fp16 GEMM on the image, without slabs
+            f.w = s.image, f.scale = nullptr;
+            return linear_f16_nk(f, LinearScratch{}, st);
         }
         default:
             return linear_refuse(c, p);
@@ -366,6 +370,6 @@ extern "C" int llmie_linear_mxfp4(const void *x, const uint8_t *wq, const uint8_
     LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "linear_mxfp4: workspace must be 16-byte aligned");
     // workspace = the fp16 image of W from kWqPrefillRows rows on, as llmie_linear_workspace_bytes sizes it; too small for it: row chunks
     const WqWorkspace w = wq_workspace(WF_MXFP4, M, K, N, workspace, workspace_bytes);
-    return linear_mxfp4(static_cast<const half_t *>(x), wq, scale, static_cast<half_t *>(y), M, K, N, static_cast<const half_t *>(bias),
-                        static_cast<const half_t *>(residual), w.deq, w.deq_bytes, as_stream(stream));
+    return linear_mxfp4(LinearOperands{x, wq, scale, y, M, K, N, EPI_NONE_, 0, bias, residual}, LinearScratch{SlabWs{nullptr, 0}, w.deq, w.deq_bytes},
+                        as_stream(stream));
 }

@@ -168,9 +168,14 @@ template <int WF> static void pk_launch_f(int mt, int epi, const PkArgs &a, cons
 // y = [swiglu]( rmsnorm(x + pre_bias) * gamma . W^T ) (+ residual) on a packed image.
 // epi: PK_EPI_PLAIN or PK_EPI_SWIGLU.  K longer than the 8 waves' register budget is split over workgroups: fp32 slabs in
 // `slab_ws` (>= pk_slab_floats floats, caller-owned) and a reduce launch (no fused norm on that route).
-int pk_linear(int wf, const half_t *x, const void *Wp, const void *scale, half_t *y, int M, int K, int N, int epi, int x32_flags,
-              const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, float *slab_ws, size_t slab_ws_floats,
-              hipStream_t st) {
+int pk_linear(int wf, int M, const PkOperands &o, hipStream_t st) {
+    const half_t *x = o.x, *residual = o.residual, *gamma = o.gamma, *pre_bias = o.pre_bias;
+    const void *Wp = o.Wp, *scale = o.scale;
+    half_t *y = o.y;
+    const int K = o.K, N = o.N, epi = o.epi, x32_flags = o.x32_flags;
+    const float eps = o.eps;
+    float *slab_ws = o.slab_ws;
+    const size_t slab_ws_floats = o.slab_ws_floats;
     if (!pk_eligible(wf, M, K, N, epi) || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(Wp) | reinterpret_cast<uintptr_t>(gamma) |
                                             reinterpret_cast<uintptr_t>(pre_bias)) % 16 ||
         reinterpret_cast<uintptr_t>(y) % 8 || reinterpret_cast<uintptr_t>(residual) % 8 ||
@@ -250,9 +255,15 @@ void pk_chain_begin(PkChain *ch, int wf, int M) {
     }
 }
 // slot: 0 = O projection (PLAIN), 1 = gate/up (SWIGLU), 2 = down (PLAIN; a K split adds the reduce slot 3), 4 = next QKV (PLAIN)
-int pk_chain_add(PkChain *ch, int slot, const half_t *x, const void *Wp, const void *scale, half_t *y, int K, int N, int epi, int x32_flags,
-                 const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps, float *slab_ws, size_t slab_ws_floats) {
+int pk_chain_add(PkChain *ch, int slot, const PkOperands &o) {
     const int wf = ch->wf, M = ch->M;
+    const half_t *x = o.x, *residual = o.residual, *gamma = o.gamma, *pre_bias = o.pre_bias;
+    const void *Wp = o.Wp, *scale = o.scale;
+    half_t *y = o.y;
+    const int K = o.K, N = o.N, epi = o.epi, x32_flags = o.x32_flags;
+    const float eps = o.eps;
+    float *slab_ws = o.slab_ws;
+    const size_t slab_ws_floats = o.slab_ws_floats;
     PkChainArgs &c = *reinterpret_cast<PkChainArgs *>(ch->args);
     static_assert(sizeof(PkChainArgs) <= sizeof(ch->args), "PkChain::args too small");
     auto fail = [&](const char *why) {
@@ -374,9 +385,9 @@ extern "C" int llmie_linear_packed(llmie_weight_format fmt, const void *x, const
     LLMIE_REQUIRE(!swiglu || !residual, "linear_packed: the SwiGLU form takes no residual");
     const int wf = pk_code(fmt);
     if (!wf) LLMIE_UNSUPPORTED("linear_packed: format %d", (int)fmt);
-    return pk_linear(wf, (const half_t *)x, packed, scale, (half_t *)y, M, K, N, swiglu ? PK_EPI_SWIGLU : PK_EPI_PLAIN, x32_flags,
-                     (const half_t *)residual, (const half_t *)gamma, (const half_t *)pre_bias, eps, static_cast<float *>(workspace),
-                     workspace_bytes / sizeof(float), as_stream(stream));
+    return pk_linear(wf, M, PkOperands{(const half_t *)x, packed, scale, (half_t *)y, K, N, swiglu ? PK_EPI_SWIGLU : PK_EPI_PLAIN, x32_flags,
+                                       (const half_t *)residual, (const half_t *)gamma, (const half_t *)pre_bias, eps,
+                                       static_cast<float *>(workspace), workspace_bytes / sizeof(float)}, as_stream(stream));
 }
 
 extern "C" size_t llmie_x32_bytes(int K) { return K > 0 && K % 32 == 0 ? static_cast<size_t>(K) * 64 : 0; }

@@ -177,11 +177,16 @@ int dequantize_weights_f16(int wbits, const void *wq, const half_t *scale, half_
     return launch_status("dequantize_weights");
 }
 
-int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, half_t *y, int M, int K, int N, int group,
-              int epi, const half_t *bias, const half_t *residual, const half_t *gamma, const half_t *pre_bias, float eps,
-              SlabWs ws, hipStream_t st, void *deq, size_t deq_bytes) {
-    const LinearCall c = linear_call(wbits, M, K, N, epi, group, x, wq, scale, y, bias, residual, gamma, pre_bias, ws, deq, deq_bytes);
+int linear_wq(int wbits, const LinearOperands &o, const LinearScratch &s, hipStream_t st) {
+    const LinearCall c = linear_call(wbits, o, s);
     const LinearPlan p = plan_linear_wq(c);
+    const half_t *x = static_cast<const half_t *>(o.x), *scale = static_cast<const half_t *>(o.scale);
+    const half_t *bias = static_cast<const half_t *>(o.bias), *residual = static_cast<const half_t *>(o.residual);
+    const half_t *gamma = static_cast<const half_t *>(o.gamma), *pre_bias = static_cast<const half_t *>(o.pre_bias);
+    const void *wq = o.w;
+    half_t *y = static_cast<half_t *>(o.y);
+    const int M = o.M, K = o.K, N = o.N, group = o.group, epi = o.epi;
+    const float eps = o.eps;
     switch (p.route) {
         case LR_W8_G8P_SWIGLU:
             gemm256_swiglu_launch(G256_W8, x, wq, y, M, N, K, nullptr, reinterpret_cast<const float *>(scale), st);
@@ -191,9 +196,11 @@ int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, h
             return launch_status("linear_w8a16(gemm8p)");
         case LR_WQ_IMAGE_PREFILL:
         case LR_WQ_IMAGE_LAST: {
-            int rc = dequantize_weights_f16(wbits, wq, scale, static_cast<half_t *>(deq), N, K, group, st);
+            int rc = dequantize_weights_f16(wbits, wq, scale, static_cast<half_t *>(s.image), N, K, group, st);
             if (rc) return rc;
-            return linear_f16_nk(x, static_cast<const half_t *>(deq), y, M, K, N, epi, bias, residual, SlabWs{nullptr, 0}, st);
+            LinearOperands f = o;   // the fp16 GEMM on the image, without slabs
+            f.w = s.image, f.scale = nullptr;
+            return linear_f16_nk(f, LinearScratch{}, st);
         }
         case LR_WQ_GEMV:
             gemv_q_launch(wbits, M, GemvArgs{x, wq, y, K, N, bias, residual, gamma, pre_bias, eps, epi, gamma ? 1 : 0, scale, group}, st);
@@ -201,7 +208,7 @@ int linear_wq(int wbits, const half_t *x, const void *wq, const half_t *scale, h
         case LR_W4_SPLITK:
         case LR_W8_SPLITK:
         case LR_W8_SPLITK_PASSES:   // int8: row scales in the finalize; int4: group scales in the kernel
-            return linear_splitk(wbits, x, wq, scale, y, M, K, N, epi, bias, residual, ws, st);
+            return linear_splitk(wbits, o, s, st);
         case LR_W4_CHUNKS: {
             const int mc = p.pass_rows, out_n = epi == EPI_SWIGLU ? N / 2 : N;
             for (int m0 = 0; m0 < M; m0 += mc) {
@@ -241,8 +248,8 @@ extern "C" int llmie_linear_w8a16(const void *x, const int8_t *wq, const void *s
     LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "linear_w8a16: workspace must be 16-byte aligned");
     // workspace = [fp16 image of W (prefill-sized M without an in-kernel form) | split-K slabs], as llmie_linear_workspace_bytes sizes it
     const WqWorkspace w = wq_workspace(8, M, K, N, workspace, workspace_bytes);
-    return linear_wq(8, (const half_t *)x, wq, (const half_t *)scale, (half_t *)y, M, K, N, 0, EPI_NONE,
-                     (const half_t *)bias, (const half_t *)residual, nullptr, nullptr, 0.f, w.slabs, as_stream(stream), w.deq, w.deq_bytes);
+    return linear_wq(8, LinearOperands{x, wq, scale, y, M, K, N, EPI_NONE, 0, bias, residual}, LinearScratch{w.slabs, w.deq, w.deq_bytes},
+                     as_stream(stream));
 }
 
 extern "C" int llmie_linear_w4a16(const void *x, const uint8_t *wq, const void *scale, void *y, int M, int K, int N,
@@ -253,8 +260,8 @@ extern "C" int llmie_linear_w4a16(const void *x, const uint8_t *wq, const void *
     LLMIE_REQUIRE(group > 0 && group % 32 == 0 && K % group == 0, "linear_w4a16: group must be a multiple of 32 dividing K");
     LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "linear_w4a16: workspace must be 16-byte aligned");
     const WqWorkspace w = wq_workspace(4, M, K, N, workspace, workspace_bytes);
-    return linear_wq(4, (const half_t *)x, wq, (const half_t *)scale, (half_t *)y, M, K, N, group, EPI_NONE,
-                     (const half_t *)bias, (const half_t *)residual, nullptr, nullptr, 0.f, w.slabs, as_stream(stream), w.deq, w.deq_bytes);
+    return linear_wq(4, LinearOperands{x, wq, scale, y, M, K, N, EPI_NONE, group, bias, residual}, LinearScratch{w.slabs, w.deq, w.deq_bytes},
+                     as_stream(stream));
 }
 
 extern "C" int llmie_quantize_w8(const void *w, int8_t *wq, void *scale, int N, int K, llmie_stream stream) {

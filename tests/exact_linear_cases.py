@@ -360,7 +360,7 @@ WQ = [
     _c("i4_image_m300", "int4", "image_prefill+tiles256_part", 300, 4096, 1000, group=128),
     _c("i4_image_g64", "int4", "image_prefill+tiles256_part", 200, 4096, 1000, group=64),
 ]
-# ---- llmie_linear_fp8: the form follows from the shape (fp8_linear.hip): M <= 8 and ksplit_eligible(M, K, 8) -> GEMV; fp8_tiled(): M > 8,
+# ---- llmie_linear_fp8: the form follows from the shape (linear.hip, plan_linear_fp8): M <= 8 and ksplit_eligible(M, K, 8) -> GEMV; tiled: M > 8,
 # K % 128 == 0, N % 4 == 0 and (gemm256_fills(M, N) or, from 129 rows, the time model rounds * K / 128 * 1.15 < passes * (N K / 8.3e6 + 17))
 # -> gemm256 e4m3; else split-K skinny in passes of 128 rows (K % 256 == 0).  rule: what the CPU test recomputes for the shape.
 FP8 = [

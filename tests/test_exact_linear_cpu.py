@@ -1,9 +1,10 @@
 """The exact projection cases of tests/exact_linear_cases.py, checked without a GPU.
 
   * every case meets the conditions that make its arithmetic exact (exact_linear_cases.conditions);
-  * every case id takes the route it names (llmie_linear_route for fp16 / int8 / int4; the shape rule of fp8_linear.hip, restated in
-    fp8_form() below, for llmie_linear_fp8; the K split of the packed entry from its workspace query), and the cases name every route
-    of the planner's vocabulary that is reachable without SwiGLU;
+  * every case id takes the route it names (llmie_linear_route; for llmie_linear_fp8 also by fp8_form() below, an independent
+    restatement of plan_linear_fp8's rule that has to agree with the route query over the grid of test_linear_routes_cpu.py; the K
+    split of the packed entry from its workspace query), and the cases name every route of the planner's vocabulary that is reachable
+    without SwiGLU;
   * seeded defects, applied to a numpy restatement of the projection (project()), change at least one output bit in every case where
     they can be expressed (DEFECTS: which operands each needs).
 
@@ -36,7 +37,10 @@ def built(llmie):
 # ---------------------------------------------------------------- routes
 def _route(lib, case, epi):
     fmt = W_CODE[case["fmt"]]
-    nbytes = lib.llmie_linear_workspace_bytes(fmt, case["M"], case["K"], case["N"]) if case["ws"] == "auto" else 0
+    if case["fmt"] == "fp8":   # (its own size query: the activation part, then the slabs)
+        nbytes = lib.llmie_linear_fp8_workspace_bytes(case["M"], case["K"], case["N"])
+    else:
+        nbytes = lib.llmie_linear_workspace_bytes(fmt, case["M"], case["K"], case["N"]) if case["ws"] == "auto" else 0
     br = epi == "epi"
     r = lib.llmie_linear_route(fmt, X + 2 * case["xoff"], W, SCALE, Y, case["M"], case["K"], case["N"], 0, case["group"],
                                BIAS if br else None, RESIDUAL if br else None, WORKSPACE if nbytes else None, nbytes)
@@ -44,8 +48,8 @@ def _route(lib, case, epi):
 
 
 def fp8_form(M, K, N):
-    """the form llmie_linear_fp8 runs for 16-byte aligned operands (fp8_linear.hip: linear_fp8, fp8_tiled; linear.hip: ksplit_form,
-    gemm256_fills, gemm256_narrow_rounds, gemm8p_fits)"""
+    """the form llmie_linear_fp8 runs for 16-byte aligned operands and a workspace of the queried size (linear.hip: plan_linear_fp8,
+    ksplit_form, gemm256_fills, gemm256_narrow_rounds, gemm8p_fits), restated"""
     ceil = lambda a, b: -(-a // b)
     tm = ceil(M, 256)
     fills = tm * ceil(N, 256) >= 192 or tm * ceil(N, 128) >= 128
@@ -71,11 +75,26 @@ def test_case_takes_the_route_it_names(built, case):
         assert (slabs > 0) == (case["K"] == 11008)
     elif case["fmt"] == "fp8":
         assert fp8_form(case["M"], case["K"], case["N"]) == case["route"]
+        for epi in E.epilogues(case):
+            assert _route(lib, case, epi) == case["route"]
     else:
         for epi in E.epilogues(case):
             assert _route(lib, case, epi) == case["route"]
     if "plan" in case:
         assert built.gemm256_tiles("plain", {"f16": "f16", "int8": "int8", "fp8": "e4m3"}[case["fmt"]], case["M"], case["N"], case["K"]) == case["plan"]
+
+
+def test_fp8_form_agrees_with_the_route_query(built):
+    """over the aligned, workspace-given part of the grid of test_linear_routes_cpu.py; all four answers occur"""
+    from collections import Counter
+    import test_linear_routes_cpu as R
+    lib, seen = built.lib(), Counter()
+    for K, N in R.SHAPES:
+        for M in R.MS:
+            form = fp8_form(M, K, N)
+            seen[form] += 1
+            assert R._route_fp8(lib, M, K, N, "plain", "auto", 0) == form, (M, K, N)
+    assert seen == {"fp8_gemm256": 174, "refused": 90, "fp8_splitk": 56, "fp8_gemv": 32}, seen
 
 
 def test_fp8_workspace_query_sizes_the_slabs_of_every_split_k_case(built):

@@ -18,7 +18,9 @@ from test_linear_routes_gpu import F16_CASES, WQ_CASES
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linear_routes.txt")
 
-W_F16, W_INT8, W_INT4 = 0, 1, 2
+FIXTURE_FP8 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linear_routes_fp8.txt")
+
+W_F16, W_INT8, W_INT4, W_FP8 = 0, 1, 2, 3
 FORMATS = [("f16", W_F16, 0), ("int8", W_INT8, 0), ("int4g128", W_INT4, 128), ("int4g64", W_INT4, 64)]
 MS = [1, 2, 4, 5, 8, 9, 16, 32, 33, 64, 65, 100, 128, 129, 150, 191, 192, 193, 200, 250, 256, 257, 300, 384, 400, 512, 700, 768, 769,
       1024, 2048, 4096]
@@ -72,9 +74,34 @@ def recording(llmie, route=_route):
     return rec
 
 
-def _fixture():
+def _route_fp8(lib, M, K, N, epi, ws, xoff):
+    """ws: None or "auto" (as sized by llmie_linear_fp8_workspace_bytes(M, K, N): the activation part, then the slabs)"""
+    nbytes = lib.llmie_linear_fp8_workspace_bytes(M, K, N) if ws == "auto" else 0
+    br = epi == "bias+residual"
+    r = lib.llmie_linear_route(W_FP8, X + xoff, W, SCALE, Y, M, K, N, 0, 0, BIAS if br else None, RESIDUAL if br else None,
+                               WORKSPACE if nbytes else None, nbytes)
+    return r.decode() if r is not None else "refused"
+
+
+def recording_fp8(llmie, route=_route_fp8):
+    """the fp8 lines (golden/linear_routes_fp8.txt): llmie_linear_fp8's routes and the three size queries that follow them"""
+    lib = llmie.lib()
     rec = {}
-    for line in open(FIXTURE):
+    for K, N in SHAPES:
+        for epi in EPILOGUES[:2]:
+            for ws in (None, "auto"):
+                for xoff in (0, 2):
+                    key = "route fp8 K=%d N=%d %s ws=%s x+%d" % (K, N, epi, ws or "none", xoff)
+                    rec[key] = _rle(route(lib, M, K, N, epi, ws, xoff) for M in MS)
+        rec["linear_fp8_workspace_bytes K=%d N=%d" % (K, N)] = _rle(lib.llmie_linear_fp8_workspace_bytes(M, K, N) for M in MS)
+        rec["linear_workspace_bytes fp8 K=%d N=%d" % (K, N)] = _rle(lib.llmie_linear_workspace_bytes(W_FP8, M, K, N) for M in MS)
+    rec["prefill_workspace_bytes fp8 7B"] = _rle(_prefill_bytes(llmie, W_FP8, 0, T) for T in MS)
+    return rec
+
+
+def _fixture(path=FIXTURE):
+    rec = {}
+    for line in open(path):
         if line.strip() and not line.startswith("#"):
             key, val = line.rstrip("\n").split(" : ")
             rec[key] = val
@@ -92,6 +119,18 @@ def test_routes_and_sizes_reproduce_the_recording(built):
     assert list(got) == list(exp), "the grid of the fixture is not the grid of this test"
     wrong = ["%s\n    recorded %s\n    planned  %s" % (k, exp[k], got[k]) for k in exp if got[k] != exp[k]]
     assert not wrong, "%d of %d lines differ:\n%s" % (len(wrong), len(exp), "\n".join(wrong[:20]))
+
+
+def test_fp8_routes_and_sizes_reproduce_the_recording(built):
+    """linear_routes_fp8.txt: recorded like the first file, from linear_fp8 as it chose its kernels inline (a dry-run build in which
+    each of its launch sites -- the GEMV, the tiled GEMM, the split-K passes -- returned its name, through llmie_linear_fp8 and so
+    behind that entry's own checks), before plan_linear_fp8 existed.  A second file, so that the first keeps its grid."""
+    got, exp = recording_fp8(built), _fixture(FIXTURE_FP8)
+    assert list(got) == list(exp), "the grid of the fixture is not the grid of this test"
+    wrong = ["%s\n    recorded %s\n    planned  %s" % (k, exp[k], got[k]) for k in exp if got[k] != exp[k]]
+    assert not wrong, "%d of %d lines differ:\n%s" % (len(wrong), len(exp), "\n".join(wrong[:20]))
+    routes = {r.split("*")[0] for k, v in exp.items() if k.startswith("route ") for r in v.split(" ")}
+    assert routes == {"fp8_gemv", "fp8_gemm256", "fp8_splitk", "refused"}, routes
 
 
 # the route each case id of tests/test_linear_routes_gpu.py names (longest prefix first)
