@@ -983,6 +983,90 @@ int llmie_decoder_lora_detach(llmie_decoder *dec);
 #define LLMIE_PLAN_WINDOW 2048u /* a sliding window is set on some layer (llmie_decoder_set_window) */
 int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer_window /* host, [num_layers], 0 = full; NULL clears */, int sinks);
 
+/* ABI 3 (an addition).  Mixture-of-experts FFN, Mixtral / Qwen-MoE semantics: every row is routed to top_k of `experts` expert FFNs.
+ * fp16 activations and fp16 experts only.  Operands (device, 16-byte aligned): x [rows, hidden]; router Wr [experts, hidden];
+ * gate_up [experts, 2 * inter, hidden] with rows [0, inter) of an expert its gate and [inter, 2 inter) its up matrix, as the dense
+ * gate_up; down [experts, hidden, inter]; resid [rows, hidden] or NULL; y [rows, hidden].  `inter` is the EXPERT inter size.
+ * 1 <= experts <= LLMIE_MOE_MAX_EXPERTS, 1 <= top_k <= min(experts, LLMIE_MOE_MAX_TOP_K), hidden % 64 == 0, inter % 64 == 0.
+ *
+ * The arithmetic, for one row x (E = experts, k = top_k, Ie = inter):
+ *   router     r[e] = sum_i x[i] * Wr[e][i]: fp16 inputs, fp32 accumulation, summation order unspecified.
+ *   selection  the k largest logits ranked by (logit descending, expert id ascending): e_0 .. e_{k-1}, logits r_0 >= .. >= r_{k-1}.
+ *              A NaN logit ranks as -inf.  Every emitted id lies in [0, E) whatever the input.
+ *   weights    fp32.  Default (Mixtral): w_j = exp(r_j - r_0) / sum_{j < k} exp(r_j - r_0) over the selected logits (= softmax over
+ *              all experts, renormalised over the selected).  LLMIE_MOE_SOFTMAX_ALL (Qwen norm_topk_prob = false): w_j =
+ *              exp(r_j - r_0) / sum_{e < E} exp(r[e] - r_0), no renormalisation.
+ *   expert     for rank j: a_j = fp16(silu(g) * u) with g, u the fp32 accumulations of x against expert e_j's gate and up rows, SiLU
+ *              and the product in fp32, ONE rounding; d_j = the fp32 accumulation of a_j against expert e_j's down rows.
+ *   combine    y = fp16((w_0 d_0 + w_1 d_1 + ... in rank order, fp32) + resid): ONE rounding.  No atomics on results.
+ *   A row whose largest logit is not finite -- every logit a NaN or -inf, or a +inf logit -- has NaN weights (exp(r_j - r_0) of
+ *   inf - inf) and therefore a NaN output row: a non-finite router input shows in y, as it would after a dense FFN.  Its ids are valid.
+ * Bit-reproducible: the bits of an output row depend on that row's input, the weights and the route (below) only -- not on the
+ * row's position and not on the other rows of the call.
+ *
+ * Two routes, chosen by a pure host function of (rows, hidden, inter, experts, top_k, flags):
+ *   gemv     rows <= 4 (and hidden, inter <= 16384): route, gate/up + SwiGLU (grid: blocks of 16 inter columns x pairs; a workgroup
+ *            reads its (row, rank) pair's expert id on the device and streams that expert's rows), down + combine (grid: blocks of
+ *            16 hidden columns x rows; walks the row's k experts in rank order).  3 launches; at one row exactly the k selected
+ *            experts are read.
+ *   grouped  otherwise: route, plan (one workgroup: each expert's pairs in (row, rank) order cut into tiles of <= 16 * RT pairs; RT =
+ *            4 once rows * top_k / experts >= 32, else 1), gate/up + SwiGLU and down on v_mfma_f32_16x16x32_f16 over
+ *            tiles = rows * top_k / (16 RT) + min(experts, rows * top_k) workgroup rows (surplus ones exit on the device tile count:
+ *            nothing is read back, a captured call replays with other routings), combine.  5 launches.
+ *   LLMIE_MOE_FORCE_GEMV (rows <= 16) and LLMIE_MOE_FORCE_GROUPED override the choice; LLMIE_MOE_FORCE_RT1 / _RT4 the tile height of
+ *   the grouped route (a row's bits do not depend on it).
+ * llmie_moe_workspace_bytes(max_rows, ...) covers llmie_moe_ffn at every rows <= max_rows under any flags (256-byte aligned
+ * sections: header, expert ids, weights, a, the tile list, d); 0 for a shape the entries refuse.  llmie_moe_ffn_plan answers one
+ * line, "route=gemv|grouped rt=.. tiles=.. route_grid=.. plan_grid=.. gate_up_grid=AxB down_grid=AxB combine_grid=AxB ws=BYTES"
+ * (ws: what that call needs of its workspace), or NULL + llmie_last_error() where llmie_moe_ffn would refuse the shape or flags.
+ * llmie_moe_route runs the route launch alone: expert_out [rows, top_k] int32, weight_out [rows, top_k] fp32.
+ * Refused on the host before any launch.  LLMIE_ERR_INVALID_ARG: NULL pointers (resid excepted), non-positive sizes, unknown or
+ * contradictory flags.  LLMIE_ERR_UNSUPPORTED: LLMIE_F32; experts or top_k outside the ranges above; hidden or inter not a
+ * multiple of 64; an operand not 16-byte aligned; LLMIE_MOE_FORCE_GEMV above 16 rows.  LLMIE_ERR_WORKSPACE: NULL, short or not
+ * 256-byte aligned.  No entry allocates or synchronises; all are legal inside a graph capture.  y may be the buffer of x (the engine
+ * runs it in place): x is last read before y is first written. */
+#define LLMIE_MOE_MAX_EXPERTS 128
+#define LLMIE_MOE_MAX_TOP_K 8
+#define LLMIE_MOE_SOFTMAX_ALL 1u
+#define LLMIE_MOE_FORCE_GEMV 2u
+#define LLMIE_MOE_FORCE_GROUPED 4u
+/* measurement only (tools/moebench.py compares the tile heights): not a serving control, a row's bits do not depend on them */
+#define LLMIE_MOE_FORCE_RT1 8u  /* grouped route: tiles of 16 pairs whatever the row count */
+#define LLMIE_MOE_FORCE_RT4 16u /* grouped route: tiles of 64 pairs whatever the row count */
+size_t llmie_moe_workspace_bytes(int max_rows, int hidden, int inter, int experts, int top_k);
+const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags);
+int llmie_moe_route(const void *x, const void *router, int rows, int hidden, int experts, int top_k, unsigned flags,
+                    int32_t *expert_out /* [rows, top_k] */, float *weight_out /* [rows, top_k] */, llmie_dtype dtype, llmie_stream stream);
+int llmie_moe_ffn(const void *x, const void *router, const void *gate_up, const void *down, const void *resid /* nullable */, void *y,
+                  int rows, int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
+                  llmie_dtype dtype, llmie_stream stream);
+
+/* ABI 3 (an addition; llmie_decoder_config is not touched).  Experts on an engine, the llmie_decoder_lora_attach pattern.  layers:
+ * HOST array [num_layers], copied; a layer whose router is NULL keeps its dense FFN (interleaved dense / sparse stacks), every other
+ * layer runs llmie_moe_ffn (router [experts, hidden], gate_up [experts, 2 * inter, hidden], down [experts, hidden, inter], fp16,
+ * device, 16-byte aligned) in place of its gate/up and down launches; `inter` is the expert inter size and need not equal
+ * cfg->inter_size.  The dense gate_up / down of a sparse layer are still what llmie_decoder_create was given (valid matrices of
+ * cfg->inter_size: the create call may pack them) and are not read by a call.  While attached, llmie_decoder_forward, _forward_paged,
+ * _forward_ragged, _forward_paged_ragged run the "moe" sequence -- the unfused decode sequence, with the fused attention launch
+ * carrying paged / e4m3 caches and ragged lengths where the geometry has it, as the lora sequence -- and llmie_decoder_prefill /
+ * _prefill_paged the general prefill sequence in its in-place-norm forms; in both, the FFN of a sparse layer is route + expert
+ * launches on the FFN-normalised rows with the layer's residual through `resid`, accounted under LLMIE_OP_FFN_NORM (route),
+ * LLMIE_OP_GATE_UP_SWIGLU (plan, gate/up) and LLMIE_OP_DOWN_GEMM (down, combine).  The
+ * attention projections keep the engine's weight format; a sliding window combines freely.  flags: LLMIE_MOE_*.
+ * workspace: llmie_decoder_moe_workspace_bytes(cfg, max_tokens, inter, experts, top_k) = llmie_moe_workspace_bytes(max(max_tokens,
+ * cfg->max_batch), hidden, ...) bytes, the attach call's own, 256-byte aligned; a call with more rows than it covers is
+ * LLMIE_ERR_WORKSPACE before anything is enqueued.  llmie_decoder_plan_name and llmie_decoder_prefill_layer_plan answer for an
+ * engine without experts.  llmie_decoder_moe_detach restores the previous sequences exactly.
+ * LLMIE_ERR_UNSUPPORTED: an engine that is not fp16 with fp16 / int8 / int4 weights, LLMIE_DEC_PACKED_ONLY, hidden % 64 != 0, an
+ * adapter table attached at the same time (either order), and what llmie_moe_ffn refuses of the expert geometry. */
+typedef struct {
+    const void *router, *gate_up, *down; /* router == NULL: the layer keeps its dense FFN */
+} llmie_moe_layer;
+size_t llmie_decoder_moe_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int inter, int experts, int top_k);
+int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_layer *layers /* host, [num_layers], copied */, int inter, int experts,
+                             int top_k, unsigned flags, void *workspace, size_t workspace_bytes);
+int llmie_decoder_moe_detach(llmie_decoder *dec);
+
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,
  * context_attention.cpp:143-312) on PACKED tokens: hidden_in/out [num_tokens, H] hold the sequences back to back
  * (input_lengths[b] tokens each, device int32), history_lengths[b] tokens of each sequence are already in the caches;

@@ -136,6 +136,13 @@ _SIGS = {
     "llmie_decoder_lora_attach": [_vp, _vp, _i, _vp, _vp, _sz],
     "llmie_decoder_lora_detach": [_vp],
     "llmie_decoder_set_window": [_vp, _vp, _i],
+    "llmie_moe_workspace_bytes": [_i, _i, _i, _i, _i],
+    "llmie_moe_ffn_plan": [_i, _i, _i, _i, _i, C.c_uint],
+    "llmie_moe_route": [_vp, _vp, _i, _i, _i, _i, C.c_uint, _vp, _vp, _i, _vp],
+    "llmie_moe_ffn": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint, _vp, _sz, _i, _vp],
+    "llmie_decoder_moe_workspace_bytes": [_vp, _i, _i, _i, _i],
+    "llmie_decoder_moe_attach": [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _sz],
+    "llmie_decoder_moe_detach": [_vp],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -168,6 +175,9 @@ _RESTYPES = {
     "llmie_lora_table_bytes": _sz,
     "llmie_lora_workspace_bytes": _sz,
     "llmie_decoder_lora_workspace_bytes": _sz,
+    "llmie_moe_workspace_bytes": _sz,
+    "llmie_decoder_moe_workspace_bytes": _sz,
+    "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -745,6 +755,10 @@ def score_tokens(hidden, lm_head, targets, gamma=None, eps=0.0, bias=None, want_
 
 
 # ------------------------------------------------------------------ fused decoder engine
+class MoeLayer(C.Structure):   # llmie_moe_layer
+    _fields_ = [("router", _vp), ("gate_up", _vp), ("down", _vp)]
+
+
 class Matrix(C.Structure):
     _fields_ = [("data", _vp), ("scale", _vp), ("bias", _vp)]
 
@@ -912,6 +926,39 @@ class Decoder:
         arr = (C.c_int32 * L)(*w)
         _check(lib().llmie_decoder_set_window(self.handle, C.addressof(arr), sinks), "decoder_set_window")
 
+    def moe_workspace_bytes(self, max_tokens, inter, experts, top_k):
+        return lib().llmie_decoder_moe_workspace_bytes(C.byref(self.cfg), max_tokens, inter, experts, top_k)
+
+    def moe_attach(self, layers, top_k, flags=0, max_tokens=None, workspace=None):
+        """While attached, every forward / prefill entry runs the moe sequence.  layers: one entry per layer, None (the layer keeps
+        its dense FFN) or a dict / tuple (router [E, H], gate_up [E, 2 Ie, H], down [E, H, Ie]) of fp16 device tensors.  max_tokens:
+        the most rows a call will bring (default: max_batch); workspace: a uint8 tensor of moe_workspace_bytes, or None (one is made)."""
+        import torch
+        arr = (MoeLayer * len(layers))()
+        keep, shape = [], None
+        for i, lw in enumerate(layers):
+            if lw is None:
+                continue
+            r, gu, dn = (lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw
+            shape = shape or (gu.shape[1] // 2, gu.shape[0])
+            if (gu.shape[1] // 2, gu.shape[0]) != shape or r.shape[0] != shape[1] or tuple(dn.shape[:1]) != (shape[1],) or dn.shape[2] != shape[0]:
+                raise LlmieError("moe_attach: layer %d: expert shapes differ from the first sparse layer's" % i)
+            arr[i].router, arr[i].gate_up, arr[i].down = _p(r), _p(gu), _p(dn)
+            keep.append((r, gu, dn))
+        if shape is None:
+            raise LlmieError("moe_attach: no layer has experts")
+        inter, experts = shape
+        if workspace is None:
+            need = self.moe_workspace_bytes(max_tokens or self.cfg.max_batch, inter, experts, top_k)
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+        _check(lib().llmie_decoder_moe_attach(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), "decoder_moe_attach")
+        self._moe_keep = (keep, workspace)
+        return workspace
+
+    def moe_detach(self):
+        _check(lib().llmie_decoder_moe_detach(self.handle), "decoder_moe_detach")
+        self._moe_keep = None
+
     def lora_detach(self):
         _check(lib().llmie_decoder_lora_detach(self.handle), "decoder_lora_detach")
         self._lora_keep = None
@@ -1058,6 +1105,56 @@ def lora_apply(x, y, table, layer, module, workspace, block_widths=None):
     arr = (C.c_int * len(widths))(*widths)
     _check(lib().llmie_lora_apply(_p(x), _p(y), rows, K, N, len(widths), arr, _p(table.data), table.slots, table.layers, layer, module,
                                   _p(workspace), workspace.numel(), _dt(x), _st()), "lora_apply")
+    return y
+
+
+# ------------------------------------------------------------------ mixture-of-experts FFN
+MOE_MAX_EXPERTS, MOE_MAX_TOP_K = 128, 8                           # LLMIE_MOE_MAX_EXPERTS, LLMIE_MOE_MAX_TOP_K
+MOE_SOFTMAX_ALL, MOE_FORCE_GEMV, MOE_FORCE_GROUPED = 1, 2, 4      # LLMIE_MOE_* flags
+MOE_FORCE_RT1, MOE_FORCE_RT4 = 8, 16
+
+
+def moe_workspace(max_rows, hidden, inter, experts, top_k, device="cuda"):
+    """a uint8 workspace that covers moe_ffn at every row count up to max_rows"""
+    import torch
+    n = lib().llmie_moe_workspace_bytes(max_rows, hidden, inter, experts, top_k)
+    if n == 0:
+        raise LlmieError("moe_workspace: bad shape: %s" % lib().llmie_last_error().decode())
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def moe_ffn_plan(rows, hidden, inter, experts, top_k, flags=0):
+    """the one-line plan of a moe_ffn call, space-separated key=value words; raises where the call would be refused"""
+    s = lib().llmie_moe_ffn_plan(rows, hidden, inter, experts, top_k, flags)
+    if s is None:
+        raise LlmieError("moe_ffn_plan: %s" % lib().llmie_last_error().decode())
+    return s.decode()
+
+
+def moe_route(x, router, top_k, flags=0, expert=None, weight=None):
+    """(expert ids int32 [rows, top_k], weights fp32 [rows, top_k]) of every row of x under the router matrix [experts, hidden]"""
+    import torch
+    rows, H = x.shape
+    E = router.shape[0]
+    if expert is None:
+        expert = torch.empty((rows, top_k), dtype=torch.int32, device=x.device)
+    if weight is None:
+        weight = torch.empty((rows, top_k), dtype=torch.float32, device=x.device)
+    _check(lib().llmie_moe_route(_p(x), _p(router), rows, H, E, top_k, flags, _p(expert), _p(weight), _dt(x), _st()), "moe_route")
+    return expert, weight
+
+
+def moe_ffn(x, router, gate_up, down, y, top_k, resid=None, flags=0, workspace=None, rows=None, workspace_bytes=None):
+    """y = MoE FFN of x (+ resid): router [E, H], gate_up [E, 2 Ie, H], down [E, H, Ie] (include/llmie.h states the arithmetic).
+    workspace: a uint8 tensor from moe_workspace (None: one is made for this call)."""
+    rows = x.shape[0] if rows is None else rows
+    H = x.shape[1]
+    E, Ie = gate_up.shape[0], gate_up.shape[1] // 2
+    if workspace is None:
+        workspace = moe_workspace(rows, H, Ie, E, top_k, device=x.device)
+    nbytes = workspace.numel() if workspace_bytes is None else workspace_bytes
+    _check(lib().llmie_moe_ffn(_p(x), _p(router), _p(gate_up), _p(down), _p(resid), _p(y), rows, H, Ie, E, top_k, flags, _p(workspace), nbytes,
+                               _dt(x), _st()), "moe_ffn")
     return y
 
 

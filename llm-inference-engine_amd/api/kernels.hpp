@@ -416,6 +416,27 @@ void launchLoraApply(TensorWrapper<T> *x, TensorWrapper<T> *y, TensorWrapper<int
                                 llmie_api::dtype_of<T>(), llmie_api::st()));
 }
 
+// No reference launchers: the mixture-of-experts FFN (include/llmie.h states the arithmetic).  x [rows, H], router [E, H], gate_up
+// [E, 2 Ie, H], down [E, H, Ie], resid [rows, H] or null, y [rows, H], all fp16; expert [rows, k] / weight [rows, k] receive the routing.
+inline void launchMoeRoute(TensorWrapper<half> *x, TensorWrapper<half> *router, TensorWrapper<int> *expert, TensorWrapper<float> *weight,
+                           unsigned flags = 0) {
+    const int rows = x->shape[0], H = x->shape[1], E = router->shape[0], k = expert->shape[1];
+    LLM_CHECK_WITH_INFO(router->shape[1] == H && expert->shape[0] == rows && weight->shape[0] == rows && weight->shape[1] == k,
+                        "router should be [E, H], expert and weight [rows, k]");
+    LLMIE_CALL(llmie_moe_route(x->data, router->data, rows, H, E, k, flags, expert->data, weight->data, LLMIE_F16, llmie_api::st()));
+}
+inline void launchMoeFfn(TensorWrapper<half> *x, TensorWrapper<half> *router, TensorWrapper<half> *gate_up, TensorWrapper<half> *down,
+                         TensorWrapper<half> *resid, TensorWrapper<half> *y, int top_k, unsigned flags = 0) {
+    const int rows = x->shape[0], H = x->shape[1], E = router->shape[0], Ie = down->shape[2];
+    LLM_CHECK_WITH_INFO(router->shape[1] == H && gate_up->shape[0] == E && gate_up->shape[1] == 2 * Ie && gate_up->shape[2] == H &&
+                            down->shape[0] == E && down->shape[1] == H && y->shape[0] == rows && y->shape[1] == H,
+                        "router [E, H], gate_up [E, 2 Ie, H], down [E, H, Ie], y [rows, H]");
+    const size_t ws = llmie_moe_workspace_bytes(rows, H, Ie, E, top_k);
+    LLM_CHECK_WITH_INFO(ws > 0, std::string(llmie_last_error()));
+    LLMIE_CALL(llmie_moe_ffn(x->data, router->data, gate_up->data, down->data, resid ? resid->data : nullptr, y->data, rows, H, Ie, E, top_k,
+                             flags, llmie_api::scratch(ws), ws, LLMIE_F16, llmie_api::st()));
+}
+
 // No reference launchers: MXFP4 weights (include/llmie.h has the format).  w [N, K] fp16 <-> wq: device bytes [N, K/2] (e2m1 codes, low
 // nibble = even k) + scale: device bytes [N, K/32] (e8m0); the linear is weight-only under fp16 activations, y [M, N] = x [M, K] . W^T
 // (+ bias [N]) (+ residual [M, N], may be y).  From 192 rows the fp16 image of the matrix goes through the adaptors' scratch.

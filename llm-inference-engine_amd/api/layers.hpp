@@ -79,6 +79,18 @@ public:
         lora_dirty = true;
     }
 
+    // Experts (include/llmie.h llmie_decoder_moe_attach): attached to every engine this holder creates, with scratch for max_tokens
+    // rows; an empty layer list detaches
+    struct MoeBinding {
+        std::vector<llmie_moe_layer> layers;
+        int inter = 0, experts = 0, top_k = 0, max_tokens = 0;
+        unsigned flags = 0;
+    };
+    void set_moe(const MoeBinding &b) {
+        moe = b;
+        moe_dirty = true;
+    }
+
     // Sliding-window attention (include/llmie.h llmie_decoder_set_window): one window per layer (0 = full attention; empty: none) and
     // the sink tokens, set on every engine this holder creates
     void set_window(const std::vector<int> &layer_window, int sinks) {
@@ -95,6 +107,27 @@ private:
         LLM_CHECK_WITH_INFO(window.empty() || static_cast<int>(window.size()) == made.num_layers, "one window per layer");
         LLMIE_CALL(llmie_decoder_set_window(engine, window.empty() ? nullptr : window.data(), window.empty() ? 0 : window_sinks));
         window_dirty = false;
+    }
+    MoeBinding moe;
+    bool moe_dirty = false;
+    void *moe_ws = nullptr;
+    size_t moe_cap = 0;
+    void sync_moe() {
+        if (!engine || !moe_dirty) return;
+        if (!moe.layers.empty()) {
+            LLM_CHECK_WITH_INFO(static_cast<int>(moe.layers.size()) == made.num_layers, "one expert entry per layer");
+            const size_t bytes = llmie_decoder_moe_workspace_bytes(&made, moe.max_tokens, moe.inter, moe.experts, moe.top_k);
+            LLM_CHECK_WITH_INFO(bytes > 0, std::string(llmie_last_error()));
+            if (bytes > moe_cap) {
+                if (moe_ws) CHECK(hipFree(moe_ws));
+                CHECK(hipMalloc(&moe_ws, bytes));
+                moe_cap = bytes;
+            }
+            LLMIE_CALL(llmie_decoder_moe_attach(engine, moe.layers.data(), moe.inter, moe.experts, moe.top_k, moe.flags, moe_ws, moe_cap));
+        } else {
+            LLMIE_CALL(llmie_decoder_moe_detach(engine));
+        }
+        moe_dirty = false;
     }
     LoraBinding lora;
     bool lora_dirty = false;
@@ -134,6 +167,8 @@ public:
         if (ws) (void)hipFree(ws);
         if (pf_ws) (void)hipFree(pf_ws);
         if (lora_ws) (void)hipFree(lora_ws);
+        if (moe_ws) (void)hipFree(moe_ws);
+        moe_ws = nullptr, moe_cap = 0;
         engine = nullptr;
         ws = pf_ws = lora_ws = nullptr;
         pf_cap = lora_cap = 0;
@@ -142,6 +177,7 @@ public:
                        int inter_size, const LlamaAttentionStaticParams &sp, float eps, int batch, int max_seq_len) {
         if (engine && key == lw->data() && batch <= batch_cap && max_seq_len == max_seq) {
             sync_lora();
+            sync_moe();
             sync_window();
             return engine;
         }
@@ -182,6 +218,8 @@ public:
         made = cfg;
         lora_dirty = lora.table != nullptr;
         sync_lora();
+        moe_dirty = !moe.layers.empty();
+        sync_moe();
         window_dirty = !window.empty();
         sync_window();
         return engine;
@@ -361,6 +399,7 @@ public:
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
+    void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 
     // self_decoder.cpp:24-122
     void forward(TensorMap *input_tensors, std::vector<LlamaLayerWeight<T> *> *layer_weights, TensorMap *output_tensors,
@@ -534,6 +573,7 @@ public:
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
+    void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 
     LlamaContextDecoder(const int &head_num, const int &kv_head_num, const int &head_size, const int &intermediate_size,
                         const int &num_layer, LlamaAttentionStaticParams *const &attention_static_params,

@@ -259,6 +259,25 @@ public:
         CHECK(hipMemcpyAsync(d_lora_slot.p, &slot, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
         CHECK(hipStreamSynchronize(llmie_api::st()));   // (`slot` lives on this frame)
     }
+    // Mixture-of-experts layers (include/llmie.h llmie_decoder_moe_attach).  layers: one entry per layer with the DEVICE router
+    // [experts, H], gate_up [experts, 2 inter, H] and down [experts, H, inter] (fp16, kept alive by the caller); router == nullptr keeps
+    // the layer's dense FFN.  Takes effect from the next prefill / decode call of both decoders; detachExperts goes back.  The expert
+    // kernels live in the fused engine, and a model that runs the per-kernel loops must not take experts and then ignore them.
+    void attachExperts(const std::vector<llmie_moe_layer> &layers, int inter, int experts, int top_k, unsigned flags = 0) {
+        LLM_CHECK_WITH_INFO(static_cast<int>(layers.size()) == num_layers, "attachExperts: one entry per layer");
+        LLM_CHECK_WITH_INFO((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs),
+                            "attachExperts: experts need the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        LLM_CHECK_WITH_INFO(d_lora_table.p == nullptr, "attachExperts: adapters and experts cannot be used on one model");
+        typename EngineHolder<T>::MoeBinding b;
+        b.layers = layers, b.inter = inter, b.experts = experts, b.top_k = top_k, b.flags = flags, b.max_tokens = max_seq_len;
+        context_decoder->setExperts(b);
+        self_decoder->setExperts(b);
+    }
+    void detachExperts() {
+        typename EngineHolder<T>::MoeBinding none;
+        context_decoder->setExperts(none);
+        self_decoder->setExperts(none);
+    }
     // Sliding-window attention with sink tokens (include/llmie.h llmie_decoder_set_window): layer_window[l] tokens on layer l (0 keeps
     // that layer global), `sinks` sink tokens on the windowed layers; an empty vector goes back to full attention.  Takes effect from
     // the next prefill / decode call of both decoders.  The windowed kernels live in the fused engine, and a model that runs the

@@ -60,6 +60,16 @@ struct llmie_decoder {
         void *ws = nullptr;
         size_t ws_bytes = 0;
     } lora;
+    // mixture-of-experts FFN (llmie_decoder_moe_attach): per layer the router / expert matrices (router == nullptr: the layer keeps its
+    // dense FFN), the expert geometry and the attach call's scratch.  layers non-empty: every forward / prefill entry runs the moe sequence
+    struct Moe {
+        std::vector<llmie_moe_layer> layers;
+        int inter = 0, experts = 0, top_k = 0;
+        unsigned flags = 0;
+        void *ws = nullptr;
+        size_t ws_bytes = 0;
+        bool on() const { return !layers.empty(); }
+    } moe;
     // sliding-window attention (llmie_decoder_set_window): the window of every layer (0 = full attention; empty: none set) and the
     // sink tokens; read where a call's attention launches are planned
     std::vector<int> layer_window;
@@ -593,8 +603,8 @@ static bool fused_attention_geometry(const llmie_decoder_config &c) {
     return (c.head_size == 32 || c.head_size == 64 || c.head_size == 128 || c.head_size == 256) && (rep == 1 || rep == 2 || rep == 4 || rep == 8);
 }
 
-enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED, DP_LORA };
-enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED, DREF_LORA, DREF_MX4_HIDDEN };
+enum DecodePath : int { DP_REFUSED = 0, DP_GEMV, DP_PACKED, DP_PACKED_CHAIN, DP_SPLITK, DP_UNFUSED, DP_LORA, DP_MOE };
+enum DecodeRefusal : int { DREF_NONE = 0, DREF_PACKED_ONLY, DREF_PAGED, DREF_KV_FP8, DREF_RAGGED, DREF_LORA, DREF_MX4_HIDDEN, DREF_MOE, DREF_MOE_LORA };
 // One decode call as the planner sees it.  mis_hidden / mis_wqkv0: address % 16 of the hidden state and of layer 0's QKV matrix.
 struct DecodeCall {
     llmie_decoder_config cfg;
@@ -603,6 +613,7 @@ struct DecodeCall {
     unsigned mis_hidden, mis_wqkv0;
     EngineSwitches sw;
     bool lora;   // an adapter table is attached
+    bool moe;    // experts are attached (llmie_decoder_moe_attach)
 };
 // what the adapter updates need of an engine: fp16 rows in front of every projection and a row-major route for the base (not fp8
 // weights, not a packed-only engine), K % 32 == 0 and column blocks (q / k / v, gate / up) that are multiples of 16
@@ -619,6 +630,14 @@ static bool window_engine_ok(const llmie_decoder_config &c) {
     return c.dtype == LLMIE_F16 && (c.head_size == 64 || c.head_size == 128) &&
            (rep == 1 || rep == 2 || rep == 4 || (rep == 8 && c.kv_fmt != LLMIE_KV_FP8));
 }
+// what the expert FFN needs of an engine: fp16 normalised rows in front of the FFN and a row-major route for the other projections
+static bool moe_engine_ok(const llmie_decoder_config &c) {
+    return c.dtype == LLMIE_F16 && (c.wfmt == LLMIE_W_F16 || c.wfmt == LLMIE_W_INT8 || c.wfmt == LLMIE_W_INT4) &&
+           !(c.flags & LLMIE_DEC_PACKED_ONLY) && (c.head_num * c.head_size) % 64 == 0;
+}
+static const char *const kMoeRefusal =
+    "experts need an fp16 engine with fp16 / int8 / int4 weights (not LLMIE_DEC_PACKED_ONLY) and a hidden size that is a multiple of 64";
+static const char *const kMoeLoraRefusal = "an adapter table and experts cannot be attached to one engine at the same time";
 static const char *const kWindowRefusal =
     "a sliding window needs an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
 static const char *const kLoraRefusal =
@@ -642,6 +661,16 @@ static DecodePlan plan_decode(const DecodeCall &d) {
     // measured crossover on MI355X (7B, ctx 512, tokens/s GEMV vs split-K): fp16 b4 1157/1143, b6 1496/1592; int8 b4 1416/1404,
     // b6 1672/1962; fp8 b3 947/944, b4 1127/1213; int4 b2 796/745, b3 896/1074
     const int gemv_max = gemv_max_batch(c.wfmt);
+    if (d.moe) {
+        // the unfused sequence with route + expert FFN in place of the gate/up and down launches of every layer that has a router; the
+        // same attention conditions as the lora sequence
+        if (d.lora) return {DP_REFUSED, DREF_MOE_LORA, false};
+        if (!moe_engine_ok(c)) return {DP_REFUSED, DREF_MOE, false};
+        if (!attn_ok && d.paged) return {DP_REFUSED, DREF_PAGED, false};
+        if (!attn_ok && c.kv_fmt == LLMIE_KV_FP8) return {DP_REFUSED, DREF_KV_FP8, false};
+        if (!attn_ok && d.ragged) return {DP_REFUSED, DREF_RAGGED, false};
+        return {DP_MOE, DREF_NONE, false};
+    }
     if (d.lora) {
         // the unfused sequence with the four adapter updates behind its projections; its attention launch carries what the fused
         // paths need of it (paged / e4m3 caches, ragged lengths) where the geometry has the fused kernel
@@ -687,6 +716,8 @@ static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
                       packed_rows_max(d.cfg));
             break;
         case DREF_LORA: set_error("decoder_forward: %s", kLoraRefusal); break;
+        case DREF_MOE: set_error("decoder_forward: %s", kMoeRefusal); break;
+        case DREF_MOE_LORA: set_error("decoder_forward: %s", kMoeLoraRefusal); break;
         case DREF_MX4_HIDDEN: set_error("decoder_forward: MXFP4 weights need a 16-byte aligned hidden_out"); break;
         case DREF_PAGED: set_error("decoder_forward_paged: the paged KV cache needs the fused decode paths (fp16 engines, batch <= 128)"); break;
         case DREF_KV_FP8:
@@ -698,12 +729,12 @@ static int decode_refuse(const DecodeCall &d, const DecodePlan &p) {
     return LLMIE_ERR_UNSUPPORTED;
 }
 static const char *decode_path_name(int path) {
-    static const char *const names[] = {"refused", "gemv", "packed", "packed_chain", "splitk", "unfused", "lora"};
+    static const char *const names[] = {"refused", "gemv", "packed", "packed_chain", "splitk", "unfused", "lora", "moe"};
     return names[path];
 }
 
-enum PrefillPath : int { PP_REFUSED = 0, PP_PACKED_ONLY, PP_SHORT_SPLITK, PP_LEAN, PP_GENERAL, PP_LORA };
-enum PrefillRefusal : int { PREF_NONE = 0, PREF_FORMAT, PREF_PACKED_ONLY_FP8, PREF_LORA };
+enum PrefillPath : int { PP_REFUSED = 0, PP_PACKED_ONLY, PP_SHORT_SPLITK, PP_LEAN, PP_GENERAL, PP_LORA, PP_MOE };
+enum PrefillRefusal : int { PREF_NONE = 0, PREF_FORMAT, PREF_PACKED_ONLY_FP8, PREF_LORA, PREF_MOE, PREF_MOE_LORA };
 // One prefill call as the planner sees it.  The split-K kernels read the weights, the out-of-place norms hidden_out and the gammas
 // in 16-byte vectors: weights handed over as views at other offsets (llmie_decoder_create takes any address) run the general sequences.
 struct PrefillCall {
@@ -715,6 +746,7 @@ struct PrefillCall {
     bool o_bias;              // some layer has an output-projection bias
     EngineSwitches sw;
     bool lora;                // an adapter table is attached
+    bool moe;                 // experts are attached
 };
 struct PrefillPlan {
     int path, refusal;
@@ -726,6 +758,10 @@ static PrefillPlan plan_prefill(const PrefillCall &p) {
     const int wqbits = c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0);
     const bool mx4 = c.wfmt == LLMIE_W_MXFP4;
     if (c.dtype != LLMIE_F16 || (c.wfmt != LLMIE_W_F16 && !fp8 && !wqbits && !mx4) || c.head_size != 128) return {PP_REFUSED, PREF_FORMAT};
+    if (p.moe) {
+        if (p.lora) return {PP_REFUSED, PREF_MOE_LORA};
+        return moe_engine_ok(c) ? PrefillPlan{PP_MOE, PREF_NONE} : PrefillPlan{PP_REFUSED, PREF_MOE};
+    }
     if (p.lora) return lora_engine_ok(c) ? PrefillPlan{PP_LORA, PREF_NONE} : PrefillPlan{PP_REFUSED, PREF_LORA};
     // MXFP4: the general sequence at every row count (llmie_linear_mxfp4 picks the projection's route by the rows; no packed image)
     // (a LLMIE_DEC_PACKED_ONLY config never gets here: creating the engine refuses it)
@@ -742,10 +778,12 @@ static int prefill_refuse(const PrefillPlan &p) {
     if (p.refusal == PREF_FORMAT)
         LLMIE_UNSUPPORTED("decoder_prefill: fp16 activations + fp16 / int8 / int4 / fp8 weights + head_size 128 only (use the per-kernel path)");
     if (p.refusal == PREF_LORA) LLMIE_UNSUPPORTED("decoder_prefill: %s", kLoraRefusal);
+    if (p.refusal == PREF_MOE) LLMIE_UNSUPPORTED("decoder_prefill: %s", kMoeRefusal);
+    if (p.refusal == PREF_MOE_LORA) LLMIE_UNSUPPORTED("decoder_prefill: %s", kMoeLoraRefusal);
     LLMIE_UNSUPPORTED("decoder_prefill: LLMIE_DEC_PACKED_ONLY engines prefill fp16 / int8 / int4 weights only");
 }
 static const char *prefill_path_name(int path) {
-    static const char *const names[] = {"refused", "packed_only", "short_splitk", "lean", "general", "lora"};
+    static const char *const names[] = {"refused", "packed_only", "short_splitk", "lean", "general", "lora", "moe"};
     return names[path];
 }
 
@@ -778,7 +816,7 @@ struct PrefillLayerPlan {
 // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
 // this holds writes the epilogue's token table once, whatever its layers end up choosing.)
 static bool prefill_rope_fusable(const PrefillCall &p) {
-    return !p.lora && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+    return !p.lora && !p.moe && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
 }
 static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
     const llmie_decoder_config &c = p.cfg;
@@ -800,7 +838,7 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
         const SplitKSlabs sk{slabs.p, 1, T, QKV};
         o.qkv = !p.sw.no_qkv_rope_fusion && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
         o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
-    } else if (path == PP_LORA || c.wfmt == LLMIE_W_MXFP4) {
+    } else if (path == PP_LORA || path == PP_MOE || c.wfmt == LLMIE_W_MXFP4) {
         // the general sequence with the forms the adapter updates need: normalised rows in place, the QKV buffer un-rotated (the update
         // lands before RoPE: the RoPE + append launch runs in front of the flash kernel), gate/up un-activated.  MXFP4 weights run the
         // same forms: their projections have the plain epilogue only
@@ -1107,6 +1145,7 @@ struct DecodeStep {
     }
     int unfused() const;
     int lora() const;
+    int moe() const;
 };
 
 // ---- the reference's launch sequence (self_decoder.cpp:69-119), one kernel per step; RoPE inside the attention launch where its
@@ -1191,6 +1230,52 @@ int DecodeStep::lora() const {
     return LLMIE_OK;
 }
 
+// the attach call's scratch must cover this call's rows: checked before anything is enqueued
+static int moe_rows_fit(const llmie_decoder *d, int rows, const char *who) {
+    const size_t need = llmie_moe_workspace_bytes(rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k);
+    if (d->moe.ws_bytes < need) {
+        set_error("%s: the workspace given to llmie_decoder_moe_attach does not cover %d rows (%zu < %zu)", who, rows, d->moe.ws_bytes, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    // and the attach flags must hold at this row count (LLMIE_MOE_FORCE_GEMV has a row limit)
+    return moe_call_check(who, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags);
+}
+// one stage of the FFN of a layer with a router, y = moe_ffn(x) + resid (x and y may be one buffer): route, gate/up, down
+static int engine_moe(const llmie_decoder *d, int layer, const void *x, const void *resid, void *y, int rows, unsigned stage, llmie_stream stream) {
+    const llmie_moe_layer &m = d->moe.layers[layer];
+    return moe_ffn_stages(x, m.router, m.gate_up, m.down, resid, y, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.ws,
+                          d->moe.ws_bytes, LLMIE_F16, stage, stream);
+}
+
+// ---- experts attached: the unfused sequence; a layer with a router runs route + expert FFN (the down projection's residual through
+// `resid`) where a dense layer runs its gate/up and down launches ----
+int DecodeStep::moe() const {
+    int rc;
+    for (int l = 0; l < c.num_layers; ++l) {
+        const llmie_layer_weights &w = dec->layers[l];
+        TIMED(LLMIE_OP_ATTN_NORM, llmie_rmsnorm(h, dec->resid, w.attn_norm_gamma, c.rms_eps, batch, H, dt, stream));
+        TIMED(LLMIE_OP_QKV_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, h, w.qkv, dec->qkv, batch, H, QKV, EPI_NONE_, nullptr), stream));
+        if (fused_attention_geometry(c)) {
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l));
+        } else {
+            TIMED(LLMIE_OP_ROPE, llmie_rope_decode(dec->qkv, batch, c.head_num, c.kv_head_num, c.head_size, pos.step, pos.step_dev,
+                                                   c.rotary_dim, c.rotary_base, dt, stream));
+            TIMED(LLMIE_OP_MHA, attention(dec->qkv, w.qkv.bias, dec->mha, l, nullptr, nullptr, 0, false));
+        }
+        TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->mha, w.o, h, batch, H, H, EPI_NONE_, nullptr), stream));
+        TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(dec->resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, batch, H, dt, stream));
+        if (dec->moe.layers[l].router) {
+            TIMED(LLMIE_OP_FFN_NORM, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_ROUTE, stream));
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_GATE_UP, stream));
+            TIMED(LLMIE_OP_DOWN_GEMM, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_DOWN, stream));
+        } else {
+            TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, proj_operands(c, h, w.gate_up, dec->act, batch, H, 2 * I, EPI_SWIGLU_, nullptr), stream));
+            TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->act, w.down, h, batch, I, H, EPI_NONE_, dec->resid), stream));
+        }
+    }
+    return LLMIE_OK;
+}
+
 // every decode entry point: validate, copy hidden_in, plan, refuse or dispatch
 static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidden_out, void *k_cache, void *v_cache,
                            const int32_t *block_table, int max_pages, int num_pages, int batch, const DecodePos &pos, llmie_stream stream) {
@@ -1201,6 +1286,8 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
                   c.max_seq_len);
     if (dec->lora.table)
         if (int rc = lora_rows_fit(dec, batch, "decoder_forward")) return rc;
+    if (dec->moe.on() && !dec->lora.table)
+        if (int rc = moe_rows_fit(dec, batch, "decoder_forward")) return rc;
     if (hidden_out != hidden_in) {
         hipError_t e = hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(batch) * dec->H * dec->esz,
                                       hipMemcpyDeviceToDevice, as_stream(stream));
@@ -1210,7 +1297,7 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
         }
     }
     const DecodeCall call{c, batch, block_table != nullptr, pos.ragged != 0, mis16(hidden_out), mis16(dec->layers[0].qkv.data), engine_switches(),
-                          dec->lora.table != nullptr};
+                          dec->lora.table != nullptr, dec->moe.on()};
     const DecodePlan plan = plan_decode(call);
     const DecodeStep s{dec, c, hidden_out, batch, kv_view(c, k_cache, v_cache, block_table, max_pages, num_pages), pos, stream, as_stream(stream),
                        dec->H, dec->QKV, dec->I, c.wfmt == LLMIE_W_F16 ? 16 : (c.wfmt == LLMIE_W_INT8 ? 8 : (c.wfmt == LLMIE_W_INT4 ? 4 : 0)),
@@ -1221,6 +1308,7 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
         case DP_SPLITK: return s.splitk();
         case DP_UNFUSED: return s.unfused();
         case DP_LORA: return s.lora();
+        case DP_MOE: return s.moe();
         default: return decode_refuse(call, plan);
     }
 }
@@ -1557,6 +1645,29 @@ struct PrefillPass {
         }
         return LLMIE_OK;
     }
+    // experts attached: the general sequence in the forms plan_prefill_layer forces (normalised fp16 rows in place); a layer with a
+    // router runs route + expert FFN where a dense layer runs its gate/up and down launches
+    int moe() const {
+        int rc;
+        for (int l = 0; l < c.num_layers; ++l) {
+            const llmie_layer_weights &w = dec->layers[l];
+            const PrefillLayerPlan lp = layer_plan(w);
+            TIMED(LLMIE_OP_ATTN_NORM, attn_norm(lp.attn_norm, w));
+            TIMED(LLMIE_OP_QKV_GEMM, qkv_proj(l, w.qkv, h, lp.qkv));
+            TIMED(LLMIE_OP_MHA, attention(l, w.qkv, lp));
+            TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, h, H, H, nullptr));
+            TIMED(LLMIE_OP_FFN_NORM, ffn_norm(lp.ffn_norm, w));
+            if (dec->moe.layers[l].router) {
+                TIMED(LLMIE_OP_FFN_NORM, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_ROUTE, stream));
+                TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_GATE_UP, stream));
+                TIMED(LLMIE_OP_DOWN_GEMM, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_DOWN, stream));
+            } else {
+                if ((rc = gate_up(h, w.gate_up, lp.gate_up))) return rc;
+                TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
+            }
+        }
+        return LLMIE_OK;
+    }
     // the general sequence (context_decoder.cpp:70-199): every format, any alignment, an output-projection bias
     int general() const {
         int rc;
@@ -1592,7 +1703,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (int rc = prefill_shape_ok(c, batch, num_tokens, max_q_len)) return rc;
     const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
     const EngineSwitches &sw = engine_switches();
-    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr};
+    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr, dec->moe.on()};
     for (const llmie_layer_weights &w : dec->layers) {
         call.weights_a16 = call.weights_a16 && (mis16(w.qkv.data) | mis16(w.o.data) | mis16(w.gate_up.data) | mis16(w.down.data)) == 0;
         call.int4_scales_a4 = call.int4_scales_a4 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
@@ -1604,6 +1715,8 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (plan.path == PP_REFUSED) return prefill_refuse(plan);
     if (plan.path == PP_LORA)
         if (int rc = lora_rows_fit(dec, T, "decoder_prefill")) return rc;
+    if (plan.path == PP_MOE)
+        if (int rc = moe_rows_fit(dec, T, "decoder_prefill")) return rc;
     const PrefillCarve o = prefill_carve(&c, T, batch);
     if (workspace_bytes < o.total || reinterpret_cast<uintptr_t>(workspace) % 256) {
         set_error("decoder_prefill: workspace too small or unaligned (%zu < %zu)", workspace_bytes, o.total);
@@ -1653,6 +1766,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
         return rc;
     switch (plan.path) {
         case PP_LORA: return p.lora();
+        case PP_MOE: return p.moe();
         case PP_PACKED_ONLY: return p.packed_only();
         case PP_SHORT_SPLITK: return p.short_splitk();
         case PP_LEAN: return p.lean();
@@ -1688,12 +1802,51 @@ extern "C" int llmie_decoder_lora_attach(llmie_decoder *dec, const void *table_d
     LLMIE_REQUIRE(slots > 0, "decoder_lora_attach: %d slots", slots);
     if (slots > LLMIE_LORA_MAX_SLOTS) LLMIE_UNSUPPORTED("decoder_lora_attach: %d slots above LLMIE_LORA_MAX_SLOTS (%d)", slots, LLMIE_LORA_MAX_SLOTS);
     if (!lora_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_lora_attach: %s", kLoraRefusal);
+    if (dec->moe.on()) LLMIE_UNSUPPORTED("decoder_lora_attach: %s", kMoeLoraRefusal);
     const size_t need = llmie_lora_workspace_bytes(dec->cfg.max_batch, slots, 192);
     if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
         set_error("decoder_lora_attach: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, need);
         return LLMIE_ERR_WORKSPACE;
     }
     dec->lora.table = table_dev, dec->lora.slots = slots, dec->lora.seq_slot = seq_slot_dev, dec->lora.ws = workspace, dec->lora.ws_bytes = workspace_bytes;
+    return LLMIE_OK;
+}
+
+extern "C" size_t llmie_decoder_moe_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int inter, int experts, int top_k) {
+    if (!config_ok(cfg) || max_tokens <= 0) return 0;
+    return llmie_moe_workspace_bytes(max_tokens > cfg->max_batch ? max_tokens : cfg->max_batch, cfg->head_num * cfg->head_size, inter, experts, top_k);
+}
+
+extern "C" int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_layer *layers, int inter, int experts, int top_k, unsigned flags,
+                                        void *workspace, size_t workspace_bytes) {
+    LLMIE_REQUIRE(dec && layers && workspace, "decoder_moe_attach: NULL pointer");
+    LLMIE_REQUIRE(inter > 0 && experts > 0 && top_k > 0, "decoder_moe_attach: non-positive size inter=%d experts=%d top_k=%d", inter, experts, top_k);
+    if (!moe_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_moe_attach: %s", kMoeRefusal);
+    if (dec->lora.table) LLMIE_UNSUPPORTED("decoder_moe_attach: %s", kMoeLoraRefusal);
+    // the operator's own checks of the expert geometry and flags, at one row (a flag with a row limit is checked per call)
+    if (int rc = moe_call_check("decoder_moe_attach", 1, dec->H, inter, experts, top_k, flags)) return rc;
+    bool any = false;
+    for (int l = 0; l < dec->cfg.num_layers; ++l) {
+        const llmie_moe_layer &m = layers[l];
+        LLMIE_REQUIRE(!m.router || (m.gate_up && m.down), "decoder_moe_attach: layer %d has a router without its expert matrices", l);
+        if (mis16(m.router) || mis16(m.gate_up) || mis16(m.down)) LLMIE_UNSUPPORTED("decoder_moe_attach: layer %d: router / gate_up / down not 16-byte aligned", l);
+        any |= m.router != nullptr;
+    }
+    LLMIE_REQUIRE(any, "decoder_moe_attach: no layer has a router");
+    const size_t need = llmie_moe_workspace_bytes(dec->cfg.max_batch, dec->H, inter, experts, top_k);
+    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
+        set_error("decoder_moe_attach: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    dec->moe.layers.assign(layers, layers + dec->cfg.num_layers);
+    dec->moe.inter = inter, dec->moe.experts = experts, dec->moe.top_k = top_k, dec->moe.flags = flags;
+    dec->moe.ws = workspace, dec->moe.ws_bytes = workspace_bytes;
+    return LLMIE_OK;
+}
+
+extern "C" int llmie_decoder_moe_detach(llmie_decoder *dec) {
+    LLMIE_REQUIRE(dec, "decoder_moe_detach: NULL decoder");
+    dec->moe = llmie_decoder::Moe{};
     return LLMIE_OK;
 }
 

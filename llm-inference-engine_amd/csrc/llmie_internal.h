@@ -335,6 +335,13 @@ int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t 
 int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, int batch, int num_tokens, int32_t *tok_b, int32_t *tok_tpos,
                         QkvRopeArgs args, QkvRopeArgs *args_dev, hipStream_t st);
 
+// ---- mixture-of-experts FFN (moe.hip): llmie_moe_ffn by stages, for the engine's per-op accounting, and its host checks alone ----
+enum : unsigned { MOE_STAGE_ROUTE = 1, MOE_STAGE_GATE_UP = 2 /* grouped route: with the plan launch */, MOE_STAGE_DOWN = 4 /* with combine */ };
+int moe_ffn_stages(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows, int hidden,
+                   int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
+                   llmie_stream stream);
+int moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags);
+
 // ---- the sampler family (sampling_params.hip, spec_decode.hip, topk_sampling.hip and the LM-head entries of engine.hip) ----
 // A call is a few structs that say what its operands are, from the C entry to the kernel launch: a new operand is added to ONE struct,
 // at the entries that fill it and at the launch that reads it.  The rows: logits [batch, vocab], one llmie_sampling_params per row

@@ -1,0 +1,579 @@
+// Mixture-of-experts FFN (llmie_moe_*; include/llmie.h states the arithmetic).  No reference launcher.
+//
+// Kernels, gfx950:
+//   route     one wave per row: the E router logits (16-byte loads of x and Wr, fp32 dot2 accumulation, DPP reduction), the k maxima
+//             by (logit descending, expert id ascending) through wave maxima + ballots, the weights in fp32.
+//   plan      one workgroup (the shape of lora_plan_kernel): pairs per expert, each expert's pairs in (row, rank) order cut into
+//             tiles of <= 16 * RT, the tile list and the tile count.  The grids are sized to the host bound
+//             pairs / (16 RT) + min(E, pairs); surplus workgroups exit on the device count.
+//   GEMV      gate/up + SwiGLU: grid (blocks of 16 Ie columns, pair); the workgroup reads its pair's expert id and streams that
+//             expert's gate and up rows in the manner of gemv_ksplit_kernel (activation row in registers, 16-byte non-temporal
+//             loads, the next rows requested before the reduction, DPP + one LDS exchange).  down + combine: grid (blocks of 16 H
+//             columns, row); the workgroup walks its row's k experts in rank order and sums w_j d_j in fp32 -- no partials.
+//   grouped   v_mfma_f32_16x16x32_f16, expert rows as the A operand and the gathered rows of the tile's pairs as B, both fetched as
+//             16-byte row-contiguous loads (no LDS), two k-steps per loop body.  Gate/up: a wave holds 16 gate columns and the
+//             matching 16 up columns of RT row tiles: SwiGLU in registers, every weight fragment shared by the RT tiles.  Down: the
+//             same arrangement, d[pair][H] in fp32 to the workspace; a combine launch applies the weights in rank order.
+// Every output element is computed by one lane chain that depends on its row, the weights and the route only: no atomics, same bits
+// wherever the row stands.
+#include "llmie_internal.h"
+
+#include <cstring>
+
+namespace llmie {
+namespace {
+
+constexpr int kMoeMaxExperts = LLMIE_MOE_MAX_EXPERTS;
+constexpr int kMoeMaxTopK = LLMIE_MOE_MAX_TOP_K;
+constexpr int kMoeGemvRows = 4;         // plan_moe: the GEMV route up to this many rows
+constexpr int kMoeGemvForceRows = 16;   // LLMIE_MOE_FORCE_GEMV up to this many rows
+constexpr int kMoeRt4PairsPerExpert = 32;   // plan_moe: RT = 4 once pairs / E reaches this
+constexpr int kMoeGemvCols = 16;        // output columns per GEMV workgroup
+constexpr int kMoeGemvMaxK = 8 * 256 * 8;   // the GEMV kernels hold at most 8 chunks of the activation row per thread
+constexpr int kMoeGroupCols = 64;       // output columns per grouped workgroup: 4 waves x 16
+constexpr int kMoeCombineThreads = 256;
+constexpr unsigned kMoeFlags = LLMIE_MOE_SOFTMAX_ALL | LLMIE_MOE_FORCE_GEMV | LLMIE_MOE_FORCE_GROUPED | LLMIE_MOE_FORCE_RT1 | LLMIE_MOE_FORCE_RT4;
+
+__host__ __device__ inline size_t moe_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+
+// ---- plan_moe: a pure host function of (rows, H, Ie, E, k, flags) ----
+enum MoeRoute : int { MOE_GEMV = 0, MOE_GROUPED = 1 };
+struct MoePlan {
+    int route, rt, tiles, pairs;
+    int route_grid, gate_up_grid[2], down_grid[2], combine_grid[2];
+    // the workspace carve: byte offsets; tile_* and d are 0-sized on the GEMV route
+    size_t expert, weight, act, tile_expert, tile_pairs, d, bytes;
+};
+
+int moe_shape_check(const char *who, int rows, int H, int Ie, int E, int k) {
+    LLMIE_REQUIRE(rows > 0 && H > 0 && Ie > 0 && E > 0 && k > 0, "%s: non-positive size rows=%d hidden=%d inter=%d experts=%d top_k=%d", who, rows, H,
+                  Ie, E, k);
+    if (E > kMoeMaxExperts) LLMIE_UNSUPPORTED("%s: %d experts above LLMIE_MOE_MAX_EXPERTS (%d)", who, E, kMoeMaxExperts);
+    if (k > E) LLMIE_UNSUPPORTED("%s: top_k=%d above the %d experts", who, k, E);
+    if (k > kMoeMaxTopK) LLMIE_UNSUPPORTED("%s: top_k=%d above LLMIE_MOE_MAX_TOP_K (%d)", who, k, kMoeMaxTopK);
+    if (H % 64) LLMIE_UNSUPPORTED("%s: hidden=%d is not a multiple of 64", who, H);
+    if (Ie % 64) LLMIE_UNSUPPORTED("%s: inter=%d is not a multiple of 64", who, Ie);
+    if (static_cast<long long>(rows) * k > (1ll << 24)) LLMIE_UNSUPPORTED("%s: rows * top_k = %lld above 2^24", who, static_cast<long long>(rows) * k);
+    return LLMIE_OK;
+}
+
+inline int moe_tiles(int pairs, int E, int rt) { return pairs / (16 * rt) + (E < pairs ? E : pairs); }
+
+void moe_carve(MoePlan *p, int H, int Ie, int tiles_max, size_t tile_pair_slots) {
+    size_t off = 256;   // the plan's header: {tiles in use}
+    p->expert = off, off += moe_align(4 * static_cast<size_t>(p->pairs));
+    p->weight = off, off += moe_align(4 * static_cast<size_t>(p->pairs));
+    p->act = off, off += moe_align(2 * static_cast<size_t>(p->pairs) * Ie);
+    p->tile_expert = off, off += moe_align(4 * static_cast<size_t>(tiles_max));
+    p->tile_pairs = off, off += moe_align(4 * tile_pair_slots);
+    p->d = off, off += p->route == MOE_GROUPED ? moe_align(4 * static_cast<size_t>(p->pairs) * H) : 0;
+    p->bytes = off;
+}
+
+// the shape has been checked (moe_shape_check)
+int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned flags, MoePlan *p) {
+    const bool fg = flags & LLMIE_MOE_FORCE_GEMV, fm = flags & LLMIE_MOE_FORCE_GROUPED;
+    LLMIE_REQUIRE(!(fg && fm), "%s: LLMIE_MOE_FORCE_GEMV and LLMIE_MOE_FORCE_GROUPED together", who);
+    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "%s: unknown flags 0x%x", who, flags);
+    LLMIE_REQUIRE(!((flags & LLMIE_MOE_FORCE_RT1) && (flags & LLMIE_MOE_FORCE_RT4)), "%s: LLMIE_MOE_FORCE_RT1 and LLMIE_MOE_FORCE_RT4 together", who);
+    const bool gemv_fits = H <= kMoeGemvMaxK && Ie <= kMoeGemvMaxK;
+    if (fg && rows > kMoeGemvForceRows) LLMIE_UNSUPPORTED("%s: LLMIE_MOE_FORCE_GEMV with %d rows, above %d", who, rows, kMoeGemvForceRows);
+    if (fg && !gemv_fits) LLMIE_UNSUPPORTED("%s: LLMIE_MOE_FORCE_GEMV with hidden=%d / inter=%d above %d", who, H, Ie, kMoeGemvMaxK);
+    std::memset(p, 0, sizeof(*p));
+    p->pairs = rows * k;
+    p->route = fg ? MOE_GEMV : (fm ? MOE_GROUPED : (rows <= kMoeGemvRows && gemv_fits ? MOE_GEMV : MOE_GROUPED));
+    p->route_grid = (rows + 3) / 4;
+    if (p->route == MOE_GEMV) {
+        p->gate_up_grid[0] = Ie / kMoeGemvCols, p->gate_up_grid[1] = p->pairs;
+        p->down_grid[0] = H / kMoeGemvCols, p->down_grid[1] = rows;
+        moe_carve(p, H, Ie, 0, 0);
+    } else {
+        p->rt = (flags & LLMIE_MOE_FORCE_RT1) ? 1 : ((flags & LLMIE_MOE_FORCE_RT4) || p->pairs / E >= kMoeRt4PairsPerExpert ? 4 : 1);
+        p->tiles = moe_tiles(p->pairs, E, p->rt);
+        p->gate_up_grid[0] = p->tiles, p->gate_up_grid[1] = Ie / kMoeGroupCols;
+        p->down_grid[0] = p->tiles, p->down_grid[1] = H / kMoeGroupCols;
+        p->combine_grid[0] = rows, p->combine_grid[1] = (H / 4 + kMoeCombineThreads - 1) / kMoeCombineThreads;   // rows on x: no 65535 limit
+        moe_carve(p, H, Ie, p->tiles, static_cast<size_t>(p->tiles) * 16 * p->rt);
+    }
+    return LLMIE_OK;
+}
+
+// ---- route ----
+struct MoeRouteArgs {
+    const half_t *x, *router;
+    int rows, H, E, k, softmax_all;
+    int32_t *expert;
+    float *weight;
+};
+
+__global__ __launch_bounds__(256) void moe_route_kernel(const MoeRouteArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= a.rows) return;   // the whole wave
+    const int nch = a.H >> 3;
+    const half8_t *xr = reinterpret_cast<const half8_t *>(a.x + static_cast<size_t>(row) * a.H);
+    const half8_t *wr = reinterpret_cast<const half8_t *>(a.router);
+    // lane l keeps the logits of experts l and 64 + l; -inf behind E and for a NaN
+    float v0 = -INFINITY, v1 = -INFINITY;
+    for (int e0 = 0; e0 < a.E; e0 += 4) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = lane; c < nch; c += 64) {
+            const half8_t xv = xr[c];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = min(e0 + i, a.E - 1);   // (a clamped expert's logit is not kept)
+                acc[i] = dot8(xv, wr[static_cast<size_t>(e) * nch + c], acc[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float r = wave_sum(acc[i]);
+            if (r != r) r = -INFINITY;
+            const int e = e0 + i;
+            if (e < a.E && (e & 63) == lane) {
+                if (e < 64) v0 = r;
+                else v1 = r;
+            }
+        }
+    }
+    // the k maxima: (logit descending, expert id ascending); an entry leaves the contest once taken
+    bool open0 = lane < a.E, open1 = lane + 64 < a.E;
+    float sel[kMoeMaxTopK];
+    int sel_id[kMoeMaxTopK];
+#pragma unroll
+    for (int j = 0; j < kMoeMaxTopK; ++j) {
+        sel[j] = -INFINITY, sel_id[j] = 0;
+        if (j < a.k) {
+            const float mine = fmaxf(open0 ? v0 : -INFINITY, open1 ? v1 : -INFINITY);
+            const float m = wave_max(mine);
+            const unsigned long long b0 = __ballot(open0 && v0 == m), b1 = __ballot(open1 && v1 == m);
+            // k <= E: an open entry exists, and -inf == -inf finds it when nothing finite is left
+            int id = b0 ? __builtin_ctzll(b0) : (b1 ? 64 + __builtin_ctzll(b1) : 0);
+            id = min(id, a.E - 1);
+            if (id == lane) open0 = false;
+            if (id == lane + 64) open1 = false;
+            sel[j] = m, sel_id[j] = id;
+        }
+    }
+    float den = 0.f;
+    if (a.softmax_all) {
+        float t = (lane < a.E ? expf(v0 - sel[0]) : 0.f) + (lane + 64 < a.E ? expf(v1 - sel[0]) : 0.f);
+        den = wave_sum(t);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kMoeMaxTopK; ++j)
+            if (j < a.k) den += expf(sel[j] - sel[0]);
+    }
+#pragma unroll
+    for (int j = 0; j < kMoeMaxTopK; ++j)
+        if (j < a.k && lane == j) {
+            a.expert[static_cast<size_t>(row) * a.k + j] = sel_id[j];
+            a.weight[static_cast<size_t>(row) * a.k + j] = expf(sel[j] - sel[0]) / den;
+        }
+}
+
+// ---- plan: hdr[0] = tiles in use; tile_expert[tiles]; tile_pairs[tiles][16 * RT] (-1 = padding) ----
+__global__ __launch_bounds__(256) void moe_plan_kernel(const int32_t *__restrict__ expert, int pairs, int E, int rt, int32_t *hdr,
+                                                       int32_t *tile_expert, int32_t *tile_pairs, int tiles) {
+    __shared__ int32_t s_base[kMoeMaxExperts + 1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slots = 16 * rt;
+    // wave w owns the experts w, w + 4, ...: lane i counts expert w + 4 i (E <= 128: i < 32)
+    const int mine = wave + 4 * lane;
+    const int owned = wave < E ? (E - wave + 3) / 4 : 0;
+    int n = 0;
+    for (int p0 = 0; p0 < pairs; p0 += 64) {
+        const int p = p0 + lane;
+        const int e = p < pairs ? expert[p] : -1;
+        for (int i = 0; i < owned; ++i) {
+            const int c = __popcll(__ballot(e == wave + 4 * i));
+            if (lane == i) n += c;
+        }
+    }
+    if (lane < owned) s_base[mine + 1] = (n + slots - 1) / slots;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        s_base[0] = 0;
+        for (int e = 0; e < E; ++e) acc += s_base[e + 1], s_base[e + 1] = acc;
+    }
+    __syncthreads();
+    const int used = min(s_base[E], tiles);
+    // the pairs of an expert in pair order: a pair's place is the matches in front of it (earlier chunks, lower lanes of its own)
+    int run = 0;   // lane i: pairs of expert wave + 4 i placed so far
+    for (int p0 = 0; p0 < pairs; p0 += 64) {
+        const int p = p0 + lane;
+        const int e = p < pairs ? expert[p] : -1;
+        for (int i = 0; i < owned; ++i) {
+            const int ex = wave + 4 * i;
+            const bool hit = e == ex;
+            const unsigned long long m = __ballot(hit);
+            if (!m) continue;
+            const int before = __builtin_amdgcn_readlane(run, i);
+            const int base = s_base[ex], end = s_base[ex + 1];
+            const int at = before + __popcll(m & ((1ull << lane) - 1));
+            if (hit && end <= tiles && at < (end - base) * slots) tile_pairs[static_cast<size_t>(base) * slots + at] = p;
+            if (lane == i) run += __popcll(m);
+        }
+    }
+    for (int i = 0; i < owned; ++i) {
+        const int ex = wave + 4 * i;
+        const int base = s_base[ex], end = s_base[ex + 1];
+        if (base == end || end > tiles) continue;
+        const int placed = __builtin_amdgcn_readlane(run, i);
+        for (int q = placed + lane; q < (end - base) * slots; q += 64) tile_pairs[static_cast<size_t>(base) * slots + q] = -1;
+        for (int ti = base + lane; ti < end; ti += 64) tile_expert[ti] = ex;
+    }
+    for (int ti = used + threadIdx.x; ti < tiles; ti += 256) tile_expert[ti] = -1;
+    if (threadIdx.x == 0) hdr[0] = used;
+}
+
+// ---- GEMV route ----
+struct MoeFfnArgs {
+    const half_t *x, *gate_up, *down, *resid;
+    half_t *y, *act;
+    const int32_t *expert;
+    const float *weight;
+    int rows, H, Ie, E, k, pairs;
+    // grouped
+    const int32_t *hdr, *tile_expert, *tile_pairs;
+    float *d;
+};
+
+__device__ __forceinline__ int moe_expert_of(const MoeFfnArgs &a, int pair) { return min(max(a.expert[pair], 0), a.E - 1); }
+__device__ __forceinline__ float moe_silu_mul(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+
+// XC: 16-byte chunks of the activation row per thread (H <= XC * 2048)
+template <int XC>
+__global__ __launch_bounds__(256) void moe_gemv_gate_up_kernel(const MoeFfnArgs a) {
+    constexpr int RP = 2;                      // (gate, up) row pairs per iteration: 4 rows x XC loads in flight per lane
+    constexpr int ITERS = kMoeGemvCols / RP;
+    __shared__ float red[2][4][2 * RP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pair = blockIdx.y, row = pair / a.k;
+    const int H = a.H, Ie = a.Ie, nch = H >> 3;
+    const int e = moe_expert_of(a, pair);
+    const half_t *W = a.gate_up + static_cast<size_t>(e) * 2 * Ie * H;
+    const int n_base = blockIdx.x * kMoeGemvCols;
+    uint4_t wb[2 * RP][XC];
+    auto load_rows = [&](int it) {
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) {
+            const int n = n_base + it * RP + (r >> 1) + (r & 1) * Ie;
+            const uint4_t *w = reinterpret_cast<const uint4_t *>(W + static_cast<size_t>(n) * H);
+#pragma unroll
+            for (int j = 0; j < XC; ++j) wb[r][j] = load_nt(w + min(j * 256 + tid, nch - 1));   // past the row end: meets a zero activation chunk
+        }
+    };
+    half8_t xr[XC];
+    const half8_t *xg = reinterpret_cast<const half8_t *>(a.x + static_cast<size_t>(row) * H);
+#pragma unroll
+    for (int j = 0; j < XC; ++j) xr[j] = j * 256 + tid < nch ? xg[j * 256 + tid] : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    load_rows(0);
+#pragma unroll 1
+    for (int it = 0; it < ITERS; ++it) {
+        float acc[2 * RP];
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) {
+            acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < XC; ++j) acc[r] = dot8(__builtin_bit_cast(half8_t, wb[r][j]), xr[j], acc[r]);
+        }
+        if (it + 1 < ITERS) load_rows(it + 1);   // in flight across the reduction
+        float (*slot)[2 * RP] = red[it & 1];
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) {
+            const float s = wave_sum(acc[r]);
+            if (lane == 0) slot[wave][r] = s;
+        }
+        __syncthreads();
+        if (tid < RP) {
+            const float g = ((slot[0][2 * tid] + slot[1][2 * tid]) + slot[2][2 * tid]) + slot[3][2 * tid];
+            const float u = ((slot[0][2 * tid + 1] + slot[1][2 * tid + 1]) + slot[2][2 * tid + 1]) + slot[3][2 * tid + 1];
+            a.act[static_cast<size_t>(pair) * Ie + n_base + it * RP + tid] = from_f32<half_t>(moe_silu_mul(g, u));
+        }
+    }
+}
+
+// XC: 16-byte chunks of the SwiGLU row per thread (Ie <= XC * 2048)
+template <int XC>
+__global__ __launch_bounds__(256) void moe_gemv_down_kernel(const MoeFfnArgs a) {
+    constexpr int RPW = 4;
+    constexpr int ITERS = kMoeGemvCols / RPW;
+    __shared__ float red[2][4][RPW];
+    __shared__ float ysum[kMoeGemvCols];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.y;
+    const int H = a.H, Ie = a.Ie, nch = Ie >> 3;
+    const int n_base = blockIdx.x * kMoeGemvCols;
+    const int steps = a.k * ITERS;   // step s: expert rank s / ITERS, columns n_base + (s % ITERS) * RPW ..
+    uint4_t wb[RPW][XC];
+    half8_t ar[XC], ar_next[XC];
+    auto load_rows = [&](int s) {
+        const int pair = row * a.k + s / ITERS, it = s % ITERS;
+        const half_t *W = a.down + static_cast<size_t>(moe_expert_of(a, pair)) * H * Ie;
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const uint4_t *w = reinterpret_cast<const uint4_t *>(W + static_cast<size_t>(n_base + it * RPW + r) * Ie);
+#pragma unroll
+            for (int j = 0; j < XC; ++j) wb[r][j] = load_nt(w + min(j * 256 + tid, nch - 1));
+        }
+        if (it == 0) {
+            const half8_t *ag = reinterpret_cast<const half8_t *>(a.act + static_cast<size_t>(pair) * Ie);
+#pragma unroll
+            for (int j = 0; j < XC; ++j) ar_next[j] = j * 256 + tid < nch ? ag[j * 256 + tid] : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+    if (tid < kMoeGemvCols) ysum[tid] = 0.f;
+    load_rows(0);
+#pragma unroll 1
+    for (int s = 0; s < steps; ++s) {
+        const int it = s % ITERS;
+        if (it == 0) {
+#pragma unroll
+            for (int j = 0; j < XC; ++j) ar[j] = ar_next[j];
+        }
+        float acc[RPW];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < XC; ++j) acc[r] = dot8(__builtin_bit_cast(half8_t, wb[r][j]), ar[j], acc[r]);
+        }
+        if (s + 1 < steps) load_rows(s + 1);
+        float (*slot)[RPW] = red[s & 1];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const float v = wave_sum(acc[r]);
+            if (lane == 0) slot[wave][r] = v;
+        }
+        __syncthreads();
+        if (tid < RPW) {   // thread t owns ysum[it * RPW + t] through the whole walk: rank order, no race
+            const float dj = ((slot[0][tid] + slot[1][tid]) + slot[2][tid]) + slot[3][tid];
+            const float wj = a.weight[row * a.k + s / ITERS];
+            ysum[it * RPW + tid] = ysum[it * RPW + tid] + wj * dj;
+        }
+    }
+    __syncthreads();
+    if (tid < kMoeGemvCols) {
+        const size_t at = static_cast<size_t>(row) * H + n_base + tid;
+        const float r = a.resid ? to_f32(a.resid[at]) : 0.f;
+        a.y[at] = from_f32<half_t>(ysum[tid] + r);
+    }
+}
+
+// ---- grouped MFMA route ----
+// SWIGLU: A = the expert's gate rows n and up rows Ie + n (K = H), B = x rows of the tile's pairs; writes act[pair][Ie] fp16.
+// else:   A = the expert's down rows n (K = Ie), B = act rows of the tile's pairs; writes d[pair][H] fp32.
+template <int RT, bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_grouped_kernel(const MoeFfnArgs a) {
+    constexpr int NA = SWIGLU ? 2 : 1;
+    const int ti = blockIdx.x;
+    if (ti >= a.hdr[0]) return;   // surplus tile (the whole workgroup)
+    const int e = a.tile_expert[ti];
+    if (e < 0 || e >= a.E) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+    const int H = a.H, Ie = a.Ie;
+    const int K = SWIGLU ? H : Ie;
+    const int n0 = blockIdx.y * kMoeGroupCols + wave * 16;
+    const half_t *W = SWIGLU ? a.gate_up + static_cast<size_t>(e) * 2 * Ie * H : a.down + static_cast<size_t>(e) * H * Ie;
+    const half_t *wrow[NA];
+    wrow[0] = W + static_cast<size_t>(n0 + c) * K + 8 * g;
+    if constexpr (SWIGLU) wrow[1] = W + static_cast<size_t>(Ie + n0 + c) * K + 8 * g;
+    const int32_t *tp = a.tile_pairs + static_cast<size_t>(ti) * 16 * RT;
+    const int first = tp[0];
+    if (first < 0 || first >= a.pairs) return;   // (a tile in use has a first pair)
+    int pr[RT];
+    bool live[RT];
+    const half_t *brow[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        pr[t] = tp[t * 16 + c];
+        live[t] = pr[t] >= 0 && pr[t] < a.pairs;
+        if (!live[t]) pr[t] = first;   // padding: any pair of the tile, the result is not stored
+        brow[t] = (SWIGLU ? a.x + static_cast<size_t>(pr[t] / a.k) * H : a.act + static_cast<size_t>(pr[t]) * Ie) + 8 * g;
+    }
+    floatx4 acc[RT][NA];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int i = 0; i < NA; ++i) acc[t][i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    // K % 64 == 0: two k-steps of loads per body, all requested before the first MFMA; the compiler's unroll puts four in flight
+#pragma unroll 2
+    for (int k = 0; k < K; k += 64) {
+        half8_t w0[NA], w1[NA], b0[RT], b1[RT];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) w0[i] = *reinterpret_cast<const half8_t *>(wrow[i] + k), w1[i] = *reinterpret_cast<const half8_t *>(wrow[i] + k + 32);
+#pragma unroll
+        for (int t = 0; t < RT; ++t) b0[t] = *reinterpret_cast<const half8_t *>(brow[t] + k), b1[t] = *reinterpret_cast<const half8_t *>(brow[t] + k + 32);
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[i], b0[t], acc[t][i], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[i], b1[t], acc[t][i], 0, 0, 0);
+    }
+    // D: row (output column) = n0 + 4 g + i, column (pair of the tile) = lane & 15
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        if (!live[t]) continue;
+        if constexpr (SWIGLU) {
+            half4_t v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = from_f32<half_t>(moe_silu_mul(acc[t][0][i], acc[t][1][i]));
+            *reinterpret_cast<half4_t *>(a.act + static_cast<size_t>(pr[t]) * Ie + n0 + 4 * g) = v;
+        } else {
+            *reinterpret_cast<float4_t *>(a.d + static_cast<size_t>(pr[t]) * H + n0 + 4 * g) =
+                float4_t{acc[t][0][0], acc[t][0][1], acc[t][0][2], acc[t][0][3]};
+        }
+    }
+}
+
+// y[row] = fp16(sum_j w_j d_j (rank order, fp32) + resid[row]); a thread owns 4 columns
+__global__ __launch_bounds__(kMoeCombineThreads) void moe_combine_kernel(const MoeFfnArgs a) {
+    const int row = blockIdx.x, q = blockIdx.y * kMoeCombineThreads + threadIdx.x;
+    if (4 * q >= a.H) return;
+    float4_t s = float4_t{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < a.k; ++j) {
+        const size_t pair = static_cast<size_t>(row) * a.k + j;
+        const float w = a.weight[pair];
+        const float4_t v = *reinterpret_cast<const float4_t *>(a.d + pair * a.H + 4 * q);
+        s.x = s.x + w * v.x, s.y = s.y + w * v.y, s.z = s.z + w * v.z, s.w = s.w + w * v.w;
+    }
+    const size_t at = static_cast<size_t>(row) * a.H + 4 * q;
+    if (a.resid) {
+        const half4_t r = *reinterpret_cast<const half4_t *>(a.resid + at);
+        s.x += to_f32(r[0]), s.y += to_f32(r[1]), s.z += to_f32(r[2]), s.w += to_f32(r[3]);
+    }
+    *reinterpret_cast<half4_t *>(a.y + at) = half4_t{from_f32<half_t>(s.x), from_f32<half_t>(s.y), from_f32<half_t>(s.z), from_f32<half_t>(s.w)};
+}
+
+int moe_xc(int K) {
+    const int need = (K / 8 + 255) / 256;
+    return need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 8));
+}
+
+void moe_route_launch(const MoeRouteArgs &r, hipStream_t st) { moe_route_kernel<<<(r.rows + 3) / 4, 256, 0, st>>>(r); }
+
+thread_local char g_moe_plan_text[256];
+
+}  // namespace
+}  // namespace llmie
+
+using namespace llmie;
+
+extern "C" size_t llmie_moe_workspace_bytes(int max_rows, int hidden, int inter, int experts, int top_k) {
+    if (moe_shape_check("moe_workspace_bytes", max_rows, hidden, inter, experts, top_k)) return 0;
+    // every section at the larger of its sizes over the routes and RT: covers the plan of every row count up to max_rows
+    MoePlan p{};
+    p.pairs = max_rows * top_k;
+    p.route = MOE_GROUPED;
+    const int t1 = moe_tiles(p.pairs, experts, 1), t4 = moe_tiles(p.pairs, experts, 4);
+    const size_t s1 = static_cast<size_t>(t1) * 16, s4 = static_cast<size_t>(t4) * 64;
+    moe_carve(&p, hidden, inter, t1 > t4 ? t1 : t4, s1 > s4 ? s1 : s4);
+    return p.bytes;
+}
+
+extern "C" const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+    MoePlan p;
+    if (moe_shape_check("moe_ffn_plan", rows, hidden, inter, experts, top_k)) return nullptr;
+    if (plan_moe("moe_ffn_plan", rows, hidden, inter, experts, top_k, flags, &p)) return nullptr;
+    snprintf(g_moe_plan_text, sizeof(g_moe_plan_text), "route=%s rt=%d tiles=%d route_grid=%d plan_grid=%d gate_up_grid=%dx%d down_grid=%dx%d combine_grid=%dx%d ws=%zu",
+             p.route == MOE_GEMV ? "gemv" : "grouped", p.rt, p.tiles, p.route_grid, p.route == MOE_GROUPED ? 1 : 0, p.gate_up_grid[0], p.gate_up_grid[1],
+             p.down_grid[0], p.down_grid[1], p.combine_grid[0], p.combine_grid[1], p.bytes);
+    return g_moe_plan_text;
+}
+
+extern "C" int llmie_moe_route(const void *x, const void *router, int rows, int hidden, int experts, int top_k, unsigned flags, int32_t *expert_out,
+                               float *weight_out, llmie_dtype dtype, llmie_stream stream) {
+    LLMIE_REQUIRE(x && router && expert_out && weight_out, "moe_route: NULL pointer");
+    if (int rc = moe_shape_check("moe_route", rows, hidden, 64, experts, top_k)) return rc;
+    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_route: fp16 activations only");
+    if (mis16(x) || mis16(router)) LLMIE_UNSUPPORTED("moe_route: x / router not 16-byte aligned");
+    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "moe_route: unknown flags 0x%x", flags);
+    MoeRouteArgs r{static_cast<const half_t *>(x), static_cast<const half_t *>(router), rows, hidden, experts, top_k,
+                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out};
+    moe_route_launch(r, as_stream(stream));
+    return launch_status("moe_route");
+}
+
+// would llmie_moe_ffn take this shape and these flags?  The code and the message under `who`; nothing is launched
+int llmie::moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
+    MoePlan p;
+    return plan_moe(who, rows, hidden, inter, experts, top_k, flags, &p);
+}
+
+extern "C" int llmie_moe_ffn(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows,
+                             int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
+                             llmie_dtype dtype, llmie_stream stream) {
+    return moe_ffn_stages(x, router, gate_up, down, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
+                          MOE_STAGE_ROUTE | MOE_STAGE_GATE_UP | MOE_STAGE_DOWN, stream);
+}
+
+// llmie_moe_ffn, or some of its stages (the engine accounts them under three op kinds): every check is made for every stage
+int llmie::moe_ffn_stages(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows,
+                          int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
+                          llmie_dtype dtype, unsigned stages, llmie_stream stream) {
+    LLMIE_REQUIRE(x && router && gate_up && down && y, "moe_ffn: NULL pointer");
+    if (int rc = moe_shape_check("moe_ffn", rows, hidden, inter, experts, top_k)) return rc;
+    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_ffn: fp16 activations only");
+    if (mis16(x) || mis16(router) || mis16(gate_up) || mis16(down) || mis16(resid) || mis16(y))
+        LLMIE_UNSUPPORTED("moe_ffn: x / router / gate_up / down / resid / y not 16-byte aligned");
+    MoePlan p;
+    if (int rc = plan_moe("moe_ffn", rows, hidden, inter, experts, top_k, flags, &p)) return rc;
+    if (!workspace || workspace_bytes < p.bytes || reinterpret_cast<uintptr_t>(workspace) % 256) {
+        set_error("moe_ffn: workspace missing, too small or not 256-byte aligned (%zu < %zu)", workspace ? workspace_bytes : size_t(0), p.bytes);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    char *base = static_cast<char *>(workspace);
+    hipStream_t st = as_stream(stream);
+    MoeFfnArgs a{};
+    a.x = static_cast<const half_t *>(x), a.gate_up = static_cast<const half_t *>(gate_up), a.down = static_cast<const half_t *>(down);
+    a.resid = static_cast<const half_t *>(resid), a.y = static_cast<half_t *>(y), a.act = reinterpret_cast<half_t *>(base + p.act);
+    a.expert = reinterpret_cast<const int32_t *>(base + p.expert), a.weight = reinterpret_cast<const float *>(base + p.weight);
+    a.rows = rows, a.H = hidden, a.Ie = inter, a.E = experts, a.k = top_k, a.pairs = p.pairs;
+    a.hdr = reinterpret_cast<const int32_t *>(base), a.tile_expert = reinterpret_cast<const int32_t *>(base + p.tile_expert);
+    a.tile_pairs = reinterpret_cast<const int32_t *>(base + p.tile_pairs), a.d = reinterpret_cast<float *>(base + p.d);
+    MoeRouteArgs r{a.x, static_cast<const half_t *>(router), rows, hidden, experts, top_k, (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0,
+                   reinterpret_cast<int32_t *>(base + p.expert), reinterpret_cast<float *>(base + p.weight)};
+    if (stages & MOE_STAGE_ROUTE) {
+        moe_route_launch(r, st);
+        if (int rc = launch_status("moe_ffn(route)")) return rc;
+    }
+    const dim3 g1(p.gate_up_grid[0], p.gate_up_grid[1]), g2(p.down_grid[0], p.down_grid[1]), g3(p.combine_grid[0], p.combine_grid[1]);
+    if (p.route == MOE_GEMV) {
+        if (stages & MOE_STAGE_GATE_UP) switch (moe_xc(hidden)) {
+            case 1: moe_gemv_gate_up_kernel<1><<<g1, 256, 0, st>>>(a); break;
+            case 2: moe_gemv_gate_up_kernel<2><<<g1, 256, 0, st>>>(a); break;
+            case 4: moe_gemv_gate_up_kernel<4><<<g1, 256, 0, st>>>(a); break;
+            default: moe_gemv_gate_up_kernel<8><<<g1, 256, 0, st>>>(a); break;
+        }
+        if (int rc = launch_status("moe_ffn(gate_up gemv)")) return rc;
+        if (stages & MOE_STAGE_DOWN) switch (moe_xc(inter)) {
+            case 1: moe_gemv_down_kernel<1><<<g2, 256, 0, st>>>(a); break;
+            case 2: moe_gemv_down_kernel<2><<<g2, 256, 0, st>>>(a); break;
+            case 4: moe_gemv_down_kernel<4><<<g2, 256, 0, st>>>(a); break;
+            default: moe_gemv_down_kernel<8><<<g2, 256, 0, st>>>(a); break;
+        }
+        return launch_status("moe_ffn(down gemv)");
+    }
+    if (stages & MOE_STAGE_GATE_UP) {
+        moe_plan_kernel<<<1, 256, 0, st>>>(a.expert, p.pairs, experts, p.rt, reinterpret_cast<int32_t *>(base), reinterpret_cast<int32_t *>(base + p.tile_expert),
+                                           reinterpret_cast<int32_t *>(base + p.tile_pairs), p.tiles);
+        if (int rc = launch_status("moe_ffn(plan)")) return rc;
+        if (p.rt == 4) moe_grouped_kernel<4, true><<<g1, 256, 0, st>>>(a);
+        else moe_grouped_kernel<1, true><<<g1, 256, 0, st>>>(a);
+        if (int rc = launch_status("moe_ffn(gate_up grouped)")) return rc;
+    }
+    if (stages & MOE_STAGE_DOWN) {
+        if (p.rt == 4) moe_grouped_kernel<4, false><<<g2, 256, 0, st>>>(a);
+        else moe_grouped_kernel<1, false><<<g2, 256, 0, st>>>(a);
+        if (int rc = launch_status("moe_ffn(down grouped)")) return rc;
+        moe_combine_kernel<<<g3, kMoeCombineThreads, 0, st>>>(a);
+        return launch_status("moe_ffn(combine)");
+    }
+    return LLMIE_OK;
+}
