@@ -1041,6 +1041,50 @@ int llmie_moe_ffn(const void *x, const void *router, const void *gate_up, const 
                   int rows, int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
                   llmie_dtype dtype, llmie_stream stream);
 
+/* ABI 3 (an addition).  The _ex entries: MXFP4 experts, router and expert biases and gpt-oss's clamped SwiGLU.  Each takes the operands
+ * of its counterpart above with one expert descriptor -- a HOST struct, copied by the call -- in place of the router / gate_up / down
+ * pointers.  Everything said above (shapes, selection, weights, routes, flags, workspace, bit-reproducibility, no atomics) holds; the
+ * additions to the arithmetic:
+ *   router     r[e] = (the fp32 sum) + float(router_bias[e]): one fp32 add.
+ *   gate/up    g, u = the fp32 accumulation of x against the expert's gate and up rows, + float(gate_up_bias[e][n]) and
+ *              + float(gate_up_bias[e][inter + n]).  LLMIE_W_MXFP4: the rows are the exact values of the codes, (-1)^s * {0, .5, 1,
+ *              1.5, 2, 3, 4, 6} * 2^e(block of 32); both routes multiply the unscaled codes (exact fp16 numbers) and apply the block's
+ *              2^e to the block's fp32 partial sum -- gemv: per lane and block; grouped: to the MFMA's 16 x 16 tile of that block.
+ *   act        LLMIE_MOE_ACT_SWIGLU: a = fp16(silu(g) * u).  LLMIE_MOE_ACT_SWIGLU_CLAMPED: g' = min(g, limit), u' = clamp(u, -limit,
+ *              limit), a = fp16((u' + 1) * g' / (1 + expf(-alpha * g'))): ONE rounding (gpt-oss: alpha 1.702, limit 7).
+ *   down       d_j = (the fp32 accumulation) + float(down_bias[e_j][c]);  combine  y = fp16(sum_j w_j d_j (rank order) + resid).
+ * MXFP4 experts are laid out exactly as llmie_quantize_mxfp4 writes the flattened [experts * 2 inter, hidden] and [experts * hidden,
+ * inter] matrices: codes uint8, two per byte, and one e8m0 byte per 32 k, block exponents in the pinned range [-23, 13]; outside
+ * it, or for a 0xFF block, results are unspecified but the call stays in bounds and terminates.  A loader of gpt-oss checkpoints
+ * de-interleaves the even / odd gate / up columns into [gate; up] first.
+ * With format LLMIE_W_F16, no bias and LLMIE_MOE_ACT_SWIGLU, llmie_moe_ffn_ex launches what llmie_moe_ffn launches and returns its bits.
+ * llmie_moe_workspace_bytes covers the _ex entries in both formats (the MXFP4 routes use the same sections).  llmie_moe_ffn_plan_ex:
+ * the line of llmie_moe_ffn_plan for that format followed by " format=f16|mxfp4 act=swiglu|swiglu_clamped".  MXFP4 experts take the
+ * gemv route up to 16 rows (fp16: 4), where it is measured ahead of the grouped one; RT as above.
+ * llmie_moe_route_ex reads the descriptor's router and router_bias only.
+ * Refused on the host before any launch, beyond what the counterparts refuse.  LLMIE_ERR_UNSUPPORTED: a format other than
+ * LLMIE_W_F16 / LLMIE_W_MXFP4; router, gate_up (codes) or down (codes) not 16-byte aligned; a bias not 2-byte aligned (scale bytes
+ * need no alignment).  LLMIE_ERR_INVALID_ARG: a NULL descriptor, router, gate_up or down; a NULL scale with LLMIE_W_MXFP4; a
+ * non-NULL scale with LLMIE_W_F16; an unknown act; with the clamped act a limit that is not finite and > 0 or an alpha that is
+ * not finite. */
+typedef enum { LLMIE_MOE_ACT_SWIGLU = 0, LLMIE_MOE_ACT_SWIGLU_CLAMPED = 1 } llmie_moe_act;
+typedef struct {
+    llmie_weight_format format;          /* LLMIE_W_F16 or LLMIE_W_MXFP4; anything else LLMIE_ERR_UNSUPPORTED */
+    const void *router;                  /* [E, H] fp16; NULL in an engine layer list = the layer keeps its dense FFN */
+    const void *router_bias;             /* nullable, [E] fp16 */
+    const void *gate_up, *gate_up_scale; /* F16: [E, 2Ie, H], scale NULL.  MXFP4: codes uint8 [E, 2Ie, H/2], e8m0 uint8 [E, 2Ie, H/32] */
+    const void *gate_up_bias;            /* nullable, [E, 2Ie] fp16: [0, Ie) gate, [Ie, 2Ie) up */
+    const void *down, *down_scale;       /* F16: [E, H, Ie].  MXFP4: [E, H, Ie/2] + [E, H, Ie/32] */
+    const void *down_bias;               /* nullable, [E, H] fp16 */
+    llmie_moe_act act; float alpha, limit; /* CLAMPED only (gpt-oss: 1.702, 7.0); limit > 0 and finite, alpha finite */
+} llmie_moe_experts;
+const char *llmie_moe_ffn_plan_ex(int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format,
+                                  llmie_moe_act act);
+int llmie_moe_route_ex(const void *x, const llmie_moe_experts *ex, int rows, int hidden, int experts, int top_k, unsigned flags,
+                       int32_t *expert_out /* [rows, top_k] */, float *weight_out /* [rows, top_k] */, llmie_dtype dtype, llmie_stream stream);
+int llmie_moe_ffn_ex(const void *x, const llmie_moe_experts *ex, const void *resid /* nullable */, void *y, int rows, int hidden, int inter,
+                     int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream);
+
 /* ABI 3 (an addition; llmie_decoder_config is not touched).  Experts on an engine, the llmie_decoder_lora_attach pattern.  layers:
  * HOST array [num_layers], copied; a layer whose router is NULL keeps its dense FFN (interleaved dense / sparse stacks), every other
  * layer runs llmie_moe_ffn (router [experts, hidden], gate_up [experts, 2 * inter, hidden], down [experts, hidden, inter], fp16,
@@ -1065,6 +1109,13 @@ typedef struct {
 size_t llmie_decoder_moe_workspace_bytes(const llmie_decoder_config *cfg, int max_tokens, int inter, int experts, int top_k);
 int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_layer *layers /* host, [num_layers], copied */, int inter, int experts,
                              int top_k, unsigned flags, void *workspace, size_t workspace_bytes);
+/* The same with expert descriptors (llmie_moe_ffn_ex): layers is a HOST array [num_layers], copied; a layer whose router is NULL keeps
+ * its dense FFN, every other layer runs llmie_moe_ffn_ex on its descriptor -- the same "moe" sequences, accounting, workspace and
+ * refusals as llmie_decoder_moe_attach.  The engine's own weight format stays fp16 / int8 / int4 whatever the experts' format
+ * (gpt-oss keeps its attention unquantised).  Refused in addition: what llmie_moe_ffn_ex refuses of a sparse layer's descriptor;
+ * LLMIE_ERR_UNSUPPORTED for sparse layers that disagree in format or act.  llmie_decoder_moe_detach detaches either kind. */
+int llmie_decoder_moe_attach_ex(llmie_decoder *dec, const llmie_moe_experts *layers /* host, [num_layers], copied */, int inter, int experts,
+                                int top_k, unsigned flags, void *workspace, size_t workspace_bytes);
 int llmie_decoder_moe_detach(llmie_decoder *dec);
 
 /* Prefill through all layers = LlamaContextDecoder<T>::forward (src/layers/context_decoder.cpp:58-199,

@@ -143,6 +143,10 @@ _SIGS = {
     "llmie_decoder_moe_workspace_bytes": [_vp, _i, _i, _i, _i],
     "llmie_decoder_moe_attach": [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _sz],
     "llmie_decoder_moe_detach": [_vp],
+    "llmie_moe_ffn_plan_ex": [_i, _i, _i, _i, _i, C.c_uint, _i, _i],
+    "llmie_moe_route_ex": [_vp, _vp, _i, _i, _i, _i, C.c_uint, _vp, _vp, _i, _vp],
+    "llmie_moe_ffn_ex": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint, _vp, _sz, _i, _vp],
+    "llmie_decoder_moe_attach_ex": [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _sz],
     "llmie_decoder_profile_begin": [_vp, _i],
     "llmie_decoder_profile_end": [_vp, _vp, _vp, _vp],
     "llmie_decoder_status": [_vp, _vp],
@@ -178,6 +182,7 @@ _RESTYPES = {
     "llmie_moe_workspace_bytes": _sz,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
+    "llmie_moe_ffn_plan_ex": C.c_char_p,
     "llmie_decoder_create": _vp,
     "llmie_decoder_destroy": None,
     "llmie_last_error": C.c_char_p,
@@ -759,6 +764,11 @@ class MoeLayer(C.Structure):   # llmie_moe_layer
     _fields_ = [("router", _vp), ("gate_up", _vp), ("down", _vp)]
 
 
+class MoeExpertsDesc(C.Structure):   # llmie_moe_experts
+    _fields_ = [("format", _i), ("router", _vp), ("router_bias", _vp), ("gate_up", _vp), ("gate_up_scale", _vp), ("gate_up_bias", _vp),
+                ("down", _vp), ("down_scale", _vp), ("down_bias", _vp), ("act", _i), ("alpha", _f), ("limit", _f)]
+
+
 class Matrix(C.Structure):
     _fields_ = [("data", _vp), ("scale", _vp), ("bias", _vp)]
 
@@ -934,6 +944,8 @@ class Decoder:
         its dense FFN) or a dict / tuple (router [E, H], gate_up [E, 2 Ie, H], down [E, H, Ie]) of fp16 device tensors.  max_tokens:
         the most rows a call will bring (default: max_batch); workspace: a uint8 tensor of moe_workspace_bytes, or None (one is made)."""
         import torch
+        if any(isinstance(lw, MoeExperts) for lw in layers):
+            return self._moe_attach_ex(layers, top_k, flags, max_tokens, workspace)
         arr = (MoeLayer * len(layers))()
         keep, shape = [], None
         for i, lw in enumerate(layers):
@@ -952,6 +964,32 @@ class Decoder:
             need = self.moe_workspace_bytes(max_tokens or self.cfg.max_batch, inter, experts, top_k)
             workspace = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
         _check(lib().llmie_decoder_moe_attach(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), "decoder_moe_attach")
+        self._moe_keep = (keep, workspace)
+        return workspace
+
+    def _moe_attach_ex(self, layers, top_k, flags, max_tokens, workspace):
+        """moe_attach with MoeExperts descriptors (llmie_decoder_moe_attach_ex); tuples / dicts among them count as fp16 experts"""
+        import torch
+        arr = (MoeExpertsDesc * len(layers))()
+        keep, shape = [], None
+        for i, lw in enumerate(layers):
+            if lw is None:
+                continue
+            if not isinstance(lw, MoeExperts):
+                r, gu, dn = (lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw
+                lw = MoeExperts(r, gu, dn)
+            shape = shape or (lw.inter, lw.experts)
+            if (lw.inter, lw.experts) != shape:
+                raise LlmieError("moe_attach: layer %d: expert shapes differ from the first sparse layer's" % i)
+            arr[i] = lw.desc()
+            keep.append(lw)
+        if shape is None:
+            raise LlmieError("moe_attach: no layer has experts")
+        inter, experts = shape
+        if workspace is None:
+            need = self.moe_workspace_bytes(max_tokens or self.cfg.max_batch, inter, experts, top_k)
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+        _check(lib().llmie_decoder_moe_attach_ex(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), "decoder_moe_attach_ex")
         self._moe_keep = (keep, workspace)
         return workspace
 
@@ -1155,6 +1193,83 @@ def moe_ffn(x, router, gate_up, down, y, top_k, resid=None, flags=0, workspace=N
     nbytes = workspace.numel() if workspace_bytes is None else workspace_bytes
     _check(lib().llmie_moe_ffn(_p(x), _p(router), _p(gate_up), _p(down), _p(resid), _p(y), rows, H, Ie, E, top_k, flags, _p(workspace), nbytes,
                                _dt(x), _st()), "moe_ffn")
+    return y
+
+
+MOE_ACT_SWIGLU, MOE_ACT_SWIGLU_CLAMPED = 0, 1                      # llmie_moe_act
+
+
+class MoeExperts:
+    """The expert descriptor of the _ex entries (llmie_moe_experts): device tensors, kept alive by this object.
+    fp16 experts: gate_up [E, 2 Ie, H], down [E, H, Ie] fp16, no scales.  MXFP4 experts: gate_up uint8 codes [E, 2 Ie, H / 2] with
+    gate_up_scale uint8 [E, 2 Ie, H / 32], down uint8 [E, H, Ie / 2] with down_scale [E, H, Ie / 32] (MoeExperts.quantize makes them).
+    Optional fp16 biases: router_bias [E], gate_up_bias [E, 2 Ie], down_bias [E, H].  act: MOE_ACT_SWIGLU, or MOE_ACT_SWIGLU_CLAMPED
+    with alpha and limit (gpt-oss: 1.702, 7.0)."""
+
+    def __init__(self, router, gate_up, down, gate_up_scale=None, down_scale=None, router_bias=None, gate_up_bias=None, down_bias=None,
+                 act=MOE_ACT_SWIGLU, alpha=0.0, limit=0.0, format=None):
+        self.router, self.gate_up, self.down = router, gate_up, down
+        self.gate_up_scale, self.down_scale = gate_up_scale, down_scale
+        self.router_bias, self.gate_up_bias, self.down_bias = router_bias, gate_up_bias, down_bias
+        self.act, self.alpha, self.limit = act, alpha, limit
+        self.format = (W_MXFP4 if gate_up_scale is not None or down_scale is not None else W_F16) if format is None else format
+        self.experts, self.inter = gate_up.shape[0], gate_up.shape[1] // 2
+        self.hidden = down.shape[1]
+
+    @classmethod
+    def quantize(cls, router, gate_up, down, **kw):
+        """MXFP4 experts from fp16 gate_up [E, 2 Ie, H] and down [E, H, Ie]: llmie_quantize_mxfp4 on the flattened matrices"""
+        import torch
+        E, two_ie, H = gate_up.shape
+        Ie = down.shape[2]
+        gq = torch.empty((E, two_ie, H // 2), dtype=torch.uint8, device=gate_up.device)
+        gs = torch.empty((E, two_ie, H // 32), dtype=torch.uint8, device=gate_up.device)
+        dq = torch.empty((E, H, Ie // 2), dtype=torch.uint8, device=down.device)
+        ds = torch.empty((E, H, Ie // 32), dtype=torch.uint8, device=down.device)
+        quantize_mxfp4(gate_up.reshape(E * two_ie, H), gq.view(E * two_ie, H // 2), gs.view(E * two_ie, H // 32))
+        quantize_mxfp4(down.reshape(E * H, Ie), dq.view(E * H, Ie // 2), ds.view(E * H, Ie // 32))
+        return cls(router, gq, dq, gate_up_scale=gs, down_scale=ds, **kw)
+
+    def desc(self):
+        d = MoeExpertsDesc()
+        d.format = self.format
+        for n in ("router", "router_bias", "gate_up", "gate_up_scale", "gate_up_bias", "down", "down_scale", "down_bias"):
+            setattr(d, n, _p(getattr(self, n)))
+        d.act, d.alpha, d.limit = self.act, self.alpha, self.limit
+        return d
+
+
+def moe_ffn_plan_ex(rows, hidden, inter, experts, top_k, flags=0, format=0, act=MOE_ACT_SWIGLU):
+    """moe_ffn_plan for experts of a format (W_F16 / W_MXFP4) under an act: the same line + " format=.. act=.."."""
+    s = lib().llmie_moe_ffn_plan_ex(rows, hidden, inter, experts, top_k, flags, format, act)
+    if s is None:
+        raise LlmieError("moe_ffn_plan_ex: %s" % lib().llmie_last_error().decode())
+    return s.decode()
+
+
+def moe_route_ex(x, ex, top_k, flags=0, expert=None, weight=None):
+    """moe_route under the descriptor's router and router bias"""
+    import torch
+    rows, H = x.shape
+    if expert is None:
+        expert = torch.empty((rows, top_k), dtype=torch.int32, device=x.device)
+    if weight is None:
+        weight = torch.empty((rows, top_k), dtype=torch.float32, device=x.device)
+    d = ex.desc()
+    _check(lib().llmie_moe_route_ex(_p(x), C.byref(d), rows, H, ex.router.shape[0], top_k, flags, _p(expert), _p(weight), _dt(x), _st()), "moe_route_ex")
+    return expert, weight
+
+
+def moe_ffn_ex(x, ex, y, top_k, resid=None, flags=0, workspace=None, rows=None, workspace_bytes=None):
+    """y = MoE FFN of x (+ resid) under a MoeExperts descriptor: MXFP4 or fp16 experts, biases, clamped SwiGLU (include/llmie.h)."""
+    rows = x.shape[0] if rows is None else rows
+    H = x.shape[1]
+    if workspace is None:
+        workspace = moe_workspace(rows, H, ex.inter, ex.experts, top_k, device=x.device)
+    nbytes = workspace.numel() if workspace_bytes is None else workspace_bytes
+    d = ex.desc()
+    _check(lib().llmie_moe_ffn_ex(_p(x), C.byref(d), _p(resid), _p(y), rows, H, ex.inter, ex.experts, top_k, flags, _p(workspace), nbytes, _dt(x),
+                                  _st()), "moe_ffn_ex")
     return y
 
 

@@ -436,6 +436,18 @@ inline void launchMoeFfn(TensorWrapper<half> *x, TensorWrapper<half> *router, Te
     LLMIE_CALL(llmie_moe_ffn(x->data, router->data, gate_up->data, down->data, resid ? resid->data : nullptr, y->data, rows, H, Ie, E, top_k,
                              flags, llmie_api::scratch(ws), ws, LLMIE_F16, llmie_api::st()));
 }
+// The same under an expert descriptor (include/llmie.h llmie_moe_experts: fp16 or MXFP4 experts, router / gate-up / down biases, the
+// clamped SwiGLU); the descriptor's DEVICE pointers are the caller's, inter and experts say their shapes
+inline void launchMoeFfnEx(TensorWrapper<half> *x, const llmie_moe_experts &ex, TensorWrapper<half> *resid, TensorWrapper<half> *y, int inter,
+                           int experts, int top_k, unsigned flags = 0) {
+    const int rows = x->shape[0], H = x->shape[1];
+    LLM_CHECK_WITH_INFO(y->shape[0] == rows && y->shape[1] == H && (!resid || (resid->shape[0] == rows && resid->shape[1] == H)),
+                        "y and resid should be [rows, H]");
+    const size_t ws = llmie_moe_workspace_bytes(rows, H, inter, experts, top_k);
+    LLM_CHECK_WITH_INFO(ws > 0, std::string(llmie_last_error()));
+    LLMIE_CALL(llmie_moe_ffn_ex(x->data, &ex, resid ? resid->data : nullptr, y->data, rows, H, inter, experts, top_k, flags, llmie_api::scratch(ws), ws,
+                                LLMIE_F16, llmie_api::st()));
+}
 
 // No reference launchers: MXFP4 weights (include/llmie.h has the format).  w [N, K] fp16 <-> wq: device bytes [N, K/2] (e2m1 codes, low
 // nibble = even k) + scale: device bytes [N, K/32] (e8m0); the linear is weight-only under fp16 activations, y [M, N] = x [M, K] . W^T

@@ -83,6 +83,7 @@ public:
     // rows; an empty layer list detaches
     struct MoeBinding {
         std::vector<llmie_moe_layer> layers;
+        std::vector<llmie_moe_experts> descriptors;   // set instead of `layers`: llmie_decoder_moe_attach_ex (MXFP4 experts, biases, act)
         int inter = 0, experts = 0, top_k = 0, max_tokens = 0;
         unsigned flags = 0;
     };
@@ -114,8 +115,8 @@ private:
     size_t moe_cap = 0;
     void sync_moe() {
         if (!engine || !moe_dirty) return;
-        if (!moe.layers.empty()) {
-            LLM_CHECK_WITH_INFO(static_cast<int>(moe.layers.size()) == made.num_layers, "one expert entry per layer");
+        if (!moe.layers.empty() || !moe.descriptors.empty()) {
+            LLM_CHECK_WITH_INFO(static_cast<int>(moe.layers.size() + moe.descriptors.size()) == made.num_layers, "one expert entry per layer");
             const size_t bytes = llmie_decoder_moe_workspace_bytes(&made, moe.max_tokens, moe.inter, moe.experts, moe.top_k);
             LLM_CHECK_WITH_INFO(bytes > 0, std::string(llmie_last_error()));
             if (bytes > moe_cap) {
@@ -123,7 +124,10 @@ private:
                 CHECK(hipMalloc(&moe_ws, bytes));
                 moe_cap = bytes;
             }
-            LLMIE_CALL(llmie_decoder_moe_attach(engine, moe.layers.data(), moe.inter, moe.experts, moe.top_k, moe.flags, moe_ws, moe_cap));
+            if (!moe.descriptors.empty())
+                LLMIE_CALL(llmie_decoder_moe_attach_ex(engine, moe.descriptors.data(), moe.inter, moe.experts, moe.top_k, moe.flags, moe_ws, moe_cap));
+            else
+                LLMIE_CALL(llmie_decoder_moe_attach(engine, moe.layers.data(), moe.inter, moe.experts, moe.top_k, moe.flags, moe_ws, moe_cap));
         } else {
             LLMIE_CALL(llmie_decoder_moe_detach(engine));
         }
@@ -218,7 +222,7 @@ public:
         made = cfg;
         lora_dirty = lora.table != nullptr;
         sync_lora();
-        moe_dirty = !moe.layers.empty();
+        moe_dirty = !moe.layers.empty() || !moe.descriptors.empty();
         sync_moe();
         window_dirty = !window.empty();
         sync_window();

@@ -273,6 +273,17 @@ public:
         context_decoder->setExperts(b);
         self_decoder->setExperts(b);
     }
+    // The same with expert descriptors (include/llmie.h llmie_decoder_moe_attach_ex): MXFP4 or fp16 experts, biases, the clamped SwiGLU
+    void attachExperts(const std::vector<llmie_moe_experts> &layers, int inter, int experts, int top_k, unsigned flags = 0) {
+        LLM_CHECK_WITH_INFO(static_cast<int>(layers.size()) == num_layers, "attachExperts: one entry per layer");
+        LLM_CHECK_WITH_INFO((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs),
+                            "attachExperts: experts need the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        LLM_CHECK_WITH_INFO(d_lora_table.p == nullptr, "attachExperts: adapters and experts cannot be used on one model");
+        typename EngineHolder<T>::MoeBinding b;
+        b.descriptors = layers, b.inter = inter, b.experts = experts, b.top_k = top_k, b.flags = flags, b.max_tokens = max_seq_len;
+        context_decoder->setExperts(b);
+        self_decoder->setExperts(b);
+    }
     void detachExperts() {
         typename EngineHolder<T>::MoeBinding none;
         context_decoder->setExperts(none);

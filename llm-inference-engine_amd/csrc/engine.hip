@@ -63,9 +63,10 @@ struct llmie_decoder {
     // mixture-of-experts FFN (llmie_decoder_moe_attach): per layer the router / expert matrices (router == nullptr: the layer keeps its
     // dense FFN), the expert geometry and the attach call's scratch.  layers non-empty: every forward / prefill entry runs the moe sequence
     struct Moe {
-        std::vector<llmie_moe_layer> layers;
+        std::vector<llmie_moe_experts> layers;   // (llmie_decoder_moe_attach: fp16 descriptors without biases, plain SwiGLU)
         int inter = 0, experts = 0, top_k = 0;
         unsigned flags = 0;
+        llmie_weight_format format = LLMIE_W_F16;   // of the experts (the engine's own weight format is cfg.wfmt)
         void *ws = nullptr;
         size_t ws_bytes = 0;
         bool on() const { return !layers.empty(); }
@@ -1238,12 +1239,11 @@ static int moe_rows_fit(const llmie_decoder *d, int rows, const char *who) {
         return LLMIE_ERR_WORKSPACE;
     }
     // and the attach flags must hold at this row count (LLMIE_MOE_FORCE_GEMV has a row limit)
-    return moe_call_check(who, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags);
+    return moe_call_check(who, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.format);
 }
 // one stage of the FFN of a layer with a router, y = moe_ffn(x) + resid (x and y may be one buffer): route, gate/up, down
 static int engine_moe(const llmie_decoder *d, int layer, const void *x, const void *resid, void *y, int rows, unsigned stage, llmie_stream stream) {
-    const llmie_moe_layer &m = d->moe.layers[layer];
-    return moe_ffn_stages(x, m.router, m.gate_up, m.down, resid, y, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.ws,
+    return moe_ffn_stages("moe_ffn", x, &d->moe.layers[layer], resid, y, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.ws,
                           d->moe.ws_bytes, LLMIE_F16, stage, stream);
 }
 
@@ -1817,6 +1817,20 @@ extern "C" size_t llmie_decoder_moe_workspace_bytes(const llmie_decoder_config *
     return llmie_moe_workspace_bytes(max_tokens > cfg->max_batch ? max_tokens : cfg->max_batch, cfg->head_num * cfg->head_size, inter, experts, top_k);
 }
 
+// both attach entries: the descriptors of every layer are already checked pointer by pointer
+static int moe_attach_common(llmie_decoder *dec, const char *who, std::vector<llmie_moe_experts> &&layers, llmie_weight_format format, int inter,
+                             int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes) {
+    const size_t need = llmie_moe_workspace_bytes(dec->cfg.max_batch, dec->H, inter, experts, top_k);
+    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
+        set_error("%s: workspace too small or not 256-byte aligned (%zu < %zu)", who, workspace_bytes, need);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    dec->moe.layers = std::move(layers);
+    dec->moe.inter = inter, dec->moe.experts = experts, dec->moe.top_k = top_k, dec->moe.flags = flags, dec->moe.format = format;
+    dec->moe.ws = workspace, dec->moe.ws_bytes = workspace_bytes;
+    return LLMIE_OK;
+}
+
 extern "C" int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_layer *layers, int inter, int experts, int top_k, unsigned flags,
                                         void *workspace, size_t workspace_bytes) {
     LLMIE_REQUIRE(dec && layers && workspace, "decoder_moe_attach: NULL pointer");
@@ -1826,22 +1840,37 @@ extern "C" int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_laye
     // the operator's own checks of the expert geometry and flags, at one row (a flag with a row limit is checked per call)
     if (int rc = moe_call_check("decoder_moe_attach", 1, dec->H, inter, experts, top_k, flags)) return rc;
     bool any = false;
+    std::vector<llmie_moe_experts> ex(dec->cfg.num_layers, llmie_moe_experts{});
     for (int l = 0; l < dec->cfg.num_layers; ++l) {
         const llmie_moe_layer &m = layers[l];
         LLMIE_REQUIRE(!m.router || (m.gate_up && m.down), "decoder_moe_attach: layer %d has a router without its expert matrices", l);
         if (mis16(m.router) || mis16(m.gate_up) || mis16(m.down)) LLMIE_UNSUPPORTED("decoder_moe_attach: layer %d: router / gate_up / down not 16-byte aligned", l);
         any |= m.router != nullptr;
+        ex[l].format = LLMIE_W_F16, ex[l].router = m.router, ex[l].gate_up = m.gate_up, ex[l].down = m.down, ex[l].act = LLMIE_MOE_ACT_SWIGLU;
     }
     LLMIE_REQUIRE(any, "decoder_moe_attach: no layer has a router");
-    const size_t need = llmie_moe_workspace_bytes(dec->cfg.max_batch, dec->H, inter, experts, top_k);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
-        set_error("decoder_moe_attach: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, need);
-        return LLMIE_ERR_WORKSPACE;
+    return moe_attach_common(dec, "decoder_moe_attach", std::move(ex), LLMIE_W_F16, inter, experts, top_k, flags, workspace, workspace_bytes);
+}
+
+extern "C" int llmie_decoder_moe_attach_ex(llmie_decoder *dec, const llmie_moe_experts *layers, int inter, int experts, int top_k, unsigned flags,
+                                           void *workspace, size_t workspace_bytes) {
+    LLMIE_REQUIRE(dec && layers && workspace, "decoder_moe_attach_ex: NULL pointer");
+    LLMIE_REQUIRE(inter > 0 && experts > 0 && top_k > 0, "decoder_moe_attach_ex: non-positive size inter=%d experts=%d top_k=%d", inter, experts, top_k);
+    if (!moe_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_moe_attach_ex: %s", kMoeRefusal);
+    if (dec->lora.table) LLMIE_UNSUPPORTED("decoder_moe_attach_ex: %s", kMoeLoraRefusal);
+    const llmie_moe_experts *first = nullptr;
+    for (int l = 0; l < dec->cfg.num_layers; ++l) {
+        const llmie_moe_experts &m = layers[l];
+        if (!m.router) continue;   // the layer keeps its dense FFN
+        if (int rc = moe_experts_ok("decoder_moe_attach_ex", &m)) return rc;
+        if (!first) first = &m;
+        if (m.format != first->format || m.act != first->act)
+            LLMIE_UNSUPPORTED("decoder_moe_attach_ex: layer %d differs from the first sparse layer in expert format or act", l);
     }
-    dec->moe.layers.assign(layers, layers + dec->cfg.num_layers);
-    dec->moe.inter = inter, dec->moe.experts = experts, dec->moe.top_k = top_k, dec->moe.flags = flags;
-    dec->moe.ws = workspace, dec->moe.ws_bytes = workspace_bytes;
-    return LLMIE_OK;
+    LLMIE_REQUIRE(first, "decoder_moe_attach_ex: no layer has a router");
+    if (int rc = moe_call_check("decoder_moe_attach_ex", 1, dec->H, inter, experts, top_k, flags, first->format)) return rc;
+    return moe_attach_common(dec, "decoder_moe_attach_ex", std::vector<llmie_moe_experts>(layers, layers + dec->cfg.num_layers), first->format, inter,
+                             experts, top_k, flags, workspace, workspace_bytes);
 }
 
 extern "C" int llmie_decoder_moe_detach(llmie_decoder *dec) {

@@ -337,10 +337,13 @@ int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, 
 
 // ---- mixture-of-experts FFN (moe.hip): llmie_moe_ffn by stages, for the engine's per-op accounting, and its host checks alone ----
 enum : unsigned { MOE_STAGE_ROUTE = 1, MOE_STAGE_GATE_UP = 2 /* grouped route: with the plan launch */, MOE_STAGE_DOWN = 4 /* with combine */ };
-int moe_ffn_stages(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows, int hidden,
-                   int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
+// (who: the entry's name in messages; ex: the expert descriptor of llmie_moe_ffn_ex -- llmie_moe_ffn fills one with fp16 experts)
+int moe_ffn_stages(const char *who, const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter,
+                   int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
                    llmie_stream stream);
-int moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags);
+int moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags,
+                   llmie_weight_format format = LLMIE_W_F16);
+int moe_experts_ok(const char *who, const llmie_moe_experts *ex);   // a descriptor's own checks: format, pointers, scales, act, alignment
 
 // ---- the sampler family (sampling_params.hip, spec_decode.hip, topk_sampling.hip and the LM-head entries of engine.hip) ----
 // A call is a few structs that say what its operands are, from the C entry to the kernel launch: a new operand is added to ONE struct,

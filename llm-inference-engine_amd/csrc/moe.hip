@@ -14,6 +14,10 @@
 //             16-byte row-contiguous loads (no LDS), two k-steps per loop body.  Gate/up: a wave holds 16 gate columns and the
 //             matching 16 up columns of RT row tiles: SwiGLU in registers, every weight fragment shared by the RT tiles.  Down: the
 //             same arrangement, d[pair][H] in fp32 to the workspace; a combine launch applies the weights in rank order.
+//   _ex       llmie_moe_ffn_ex / _route_ex: an expert descriptor with a router bias, gate/up and down biases and the clamped SwiGLU as
+//             epilogues of the kernels above (a template flag on the fp16 expert kernels, uniform branches elsewhere), and MXFP4
+//             experts on kernels of their own beside the fp16 ones: moe_mx4_gemv_* (waves own weight rows, a lane's 16-byte load is
+//             one block of 32 codes) and moe_mx4_grouped_kernel (operands swapped: a lane owns one weight row and one scale).
 // Every output element is computed by one lane chain that depends on its row, the weights and the route only: no atomics, same bits
 // wherever the row stands.
 #include "llmie_internal.h"
@@ -25,7 +29,8 @@ namespace {
 
 constexpr int kMoeMaxExperts = LLMIE_MOE_MAX_EXPERTS;
 constexpr int kMoeMaxTopK = LLMIE_MOE_MAX_TOP_K;
-constexpr int kMoeGemvRows = 4;         // plan_moe: the GEMV route up to this many rows
+constexpr int kMoeGemvRows = 4;         // plan_moe: the GEMV route up to this many rows (fp16 experts)
+constexpr int kMoeGemvRowsMx4 = 16;     // MXFP4 experts: the GEMV route is ahead of the grouped one at 5, 8 and 16 rows
 constexpr int kMoeGemvForceRows = 16;   // LLMIE_MOE_FORCE_GEMV up to this many rows
 constexpr int kMoeRt4PairsPerExpert = 32;   // plan_moe: RT = 4 once pairs / E reaches this
 constexpr int kMoeGemvCols = 16;        // output columns per GEMV workgroup
@@ -36,7 +41,7 @@ constexpr unsigned kMoeFlags = LLMIE_MOE_SOFTMAX_ALL | LLMIE_MOE_FORCE_GEMV | LL
 
 __host__ __device__ inline size_t moe_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
-// ---- plan_moe: a pure host function of (rows, H, Ie, E, k, flags) ----
+// ---- plan_moe: a pure host function of (rows, H, Ie, E, k, flags, expert format) ----
 enum MoeRoute : int { MOE_GEMV = 0, MOE_GROUPED = 1 };
 struct MoePlan {
     int route, rt, tiles, pairs;
@@ -71,7 +76,10 @@ void moe_carve(MoePlan *p, int H, int Ie, int tiles_max, size_t tile_pair_slots)
 }
 
 // the shape has been checked (moe_shape_check)
-int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned flags, MoePlan *p) {
+// format: LLMIE_W_F16 or LLMIE_W_MXFP4 experts.  The GEMV row threshold is a per-format constant (tools/moebench.py --mxfp4 shows the
+// MXFP4 crossover at the 16 rows the GEMV kernels stop at); RT = 4 from 32 pairs per expert in both (rt4 is ahead from 128 tokens in both)
+int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned flags, llmie_weight_format format, MoePlan *p) {
+    const int gemv_rows = format == LLMIE_W_MXFP4 ? kMoeGemvRowsMx4 : kMoeGemvRows;
     const bool fg = flags & LLMIE_MOE_FORCE_GEMV, fm = flags & LLMIE_MOE_FORCE_GROUPED;
     LLMIE_REQUIRE(!(fg && fm), "%s: LLMIE_MOE_FORCE_GEMV and LLMIE_MOE_FORCE_GROUPED together", who);
     LLMIE_REQUIRE(!(flags & ~kMoeFlags), "%s: unknown flags 0x%x", who, flags);
@@ -81,7 +89,7 @@ int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned fl
     if (fg && !gemv_fits) LLMIE_UNSUPPORTED("%s: LLMIE_MOE_FORCE_GEMV with hidden=%d / inter=%d above %d", who, H, Ie, kMoeGemvMaxK);
     std::memset(p, 0, sizeof(*p));
     p->pairs = rows * k;
-    p->route = fg ? MOE_GEMV : (fm ? MOE_GROUPED : (rows <= kMoeGemvRows && gemv_fits ? MOE_GEMV : MOE_GROUPED));
+    p->route = fg ? MOE_GEMV : (fm ? MOE_GROUPED : (rows <= gemv_rows && gemv_fits ? MOE_GEMV : MOE_GROUPED));
     p->route_grid = (rows + 3) / 4;
     if (p->route == MOE_GEMV) {
         p->gate_up_grid[0] = Ie / kMoeGemvCols, p->gate_up_grid[1] = p->pairs;
@@ -104,6 +112,7 @@ struct MoeRouteArgs {
     int rows, H, E, k, softmax_all;
     int32_t *expert;
     float *weight;
+    const half_t *bias;   // [E] or null (llmie_moe_route_ex): one fp32 add to the summed logit
 };
 
 __global__ __launch_bounds__(256) void moe_route_kernel(const MoeRouteArgs a) {
@@ -128,6 +137,7 @@ __global__ __launch_bounds__(256) void moe_route_kernel(const MoeRouteArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float r = wave_sum(acc[i]);
+            if (a.bias) r += to_f32(a.bias[min(e0 + i, a.E - 1)]);
             if (r != r) r = -INFINITY;
             const int e = e0 + i;
             if (e < a.E && (e & 63) == lane) {
@@ -238,13 +248,30 @@ struct MoeFfnArgs {
     // grouped
     const int32_t *hdr, *tile_expert, *tile_pairs;
     float *d;
+    // llmie_moe_ffn_ex.  MXFP4 experts: gate_up / down point at the codes, these at the e8m0 bytes.  Biases: null = none.  act_kind: llmie_moe_act
+    const uint8_t *gate_up_scale, *down_scale;
+    const half_t *gate_up_bias, *down_bias;
+    int act_kind;
+    float alpha, limit;
 };
 
 __device__ __forceinline__ int moe_expert_of(const MoeFfnArgs &a, int pair) { return min(max(a.expert[pair], 0), a.E - 1); }
 __device__ __forceinline__ float moe_silu_mul(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+// the _ex epilogue of a (gate, up) pair of expert e at inter column n: the biases (a uniform branch), then the act
+__device__ __forceinline__ float moe_act_ex(const MoeFfnArgs &a, int e, int n, float g, float u) {
+    if (a.gate_up_bias) {
+        const half_t *b = a.gate_up_bias + static_cast<size_t>(e) * 2 * a.Ie;
+        g += to_f32(b[n]), u += to_f32(b[a.Ie + n]);
+    }
+    if (a.act_kind == LLMIE_MOE_ACT_SWIGLU_CLAMPED) {
+        g = fminf(g, a.limit), u = fminf(fmaxf(u, -a.limit), a.limit);
+        return (u + 1.0f) * g / (1.0f + expf(-a.alpha * g));
+    }
+    return moe_silu_mul(g, u);
+}
 
-// XC: 16-byte chunks of the activation row per thread (H <= XC * 2048)
-template <int XC>
+// XC: 16-byte chunks of the activation row per thread (H <= XC * 2048).  EX: with the _ex epilogue (biases, act); false = llmie_moe_ffn
+template <int XC, bool EX>
 __global__ __launch_bounds__(256) void moe_gemv_gate_up_kernel(const MoeFfnArgs a) {
     constexpr int RP = 2;                      // (gate, up) row pairs per iteration: 4 rows x XC loads in flight per lane
     constexpr int ITERS = kMoeGemvCols / RP;
@@ -290,13 +317,15 @@ __global__ __launch_bounds__(256) void moe_gemv_gate_up_kernel(const MoeFfnArgs 
         if (tid < RP) {
             const float g = ((slot[0][2 * tid] + slot[1][2 * tid]) + slot[2][2 * tid]) + slot[3][2 * tid];
             const float u = ((slot[0][2 * tid + 1] + slot[1][2 * tid + 1]) + slot[2][2 * tid + 1]) + slot[3][2 * tid + 1];
-            a.act[static_cast<size_t>(pair) * Ie + n_base + it * RP + tid] = from_f32<half_t>(moe_silu_mul(g, u));
+            const int n = n_base + it * RP + tid;
+            if constexpr (EX) a.act[static_cast<size_t>(pair) * Ie + n] = from_f32<half_t>(moe_act_ex(a, e, n, g, u));
+            else a.act[static_cast<size_t>(pair) * Ie + n] = from_f32<half_t>(moe_silu_mul(g, u));
         }
     }
 }
 
-// XC: 16-byte chunks of the SwiGLU row per thread (Ie <= XC * 2048)
-template <int XC>
+// XC: 16-byte chunks of the SwiGLU row per thread (Ie <= XC * 2048).  EX: with the down bias
+template <int XC, bool EX>
 __global__ __launch_bounds__(256) void moe_gemv_down_kernel(const MoeFfnArgs a) {
     constexpr int RPW = 4;
     constexpr int ITERS = kMoeGemvCols / RPW;
@@ -349,7 +378,10 @@ __global__ __launch_bounds__(256) void moe_gemv_down_kernel(const MoeFfnArgs a) 
         }
         __syncthreads();
         if (tid < RPW) {   // thread t owns ysum[it * RPW + t] through the whole walk: rank order, no race
-            const float dj = ((slot[0][tid] + slot[1][tid]) + slot[2][tid]) + slot[3][tid];
+            float dj = ((slot[0][tid] + slot[1][tid]) + slot[2][tid]) + slot[3][tid];
+            if constexpr (EX) {
+                if (a.down_bias) dj += to_f32(a.down_bias[static_cast<size_t>(moe_expert_of(a, row * a.k + s / ITERS)) * H + n_base + it * RPW + tid]);
+            }
             const float wj = a.weight[row * a.k + s / ITERS];
             ysum[it * RPW + tid] = ysum[it * RPW + tid] + wj * dj;
         }
@@ -365,7 +397,8 @@ __global__ __launch_bounds__(256) void moe_gemv_down_kernel(const MoeFfnArgs a) 
 // ---- grouped MFMA route ----
 // SWIGLU: A = the expert's gate rows n and up rows Ie + n (K = H), B = x rows of the tile's pairs; writes act[pair][Ie] fp16.
 // else:   A = the expert's down rows n (K = Ie), B = act rows of the tile's pairs; writes d[pair][H] fp32.
-template <int RT, bool SWIGLU>
+// EX (SWIGLU only): with the _ex epilogue; the down bias of the grouped route is added by the combine launch
+template <int RT, bool SWIGLU, bool EX>
 __global__ __launch_bounds__(256) void moe_grouped_kernel(const MoeFfnArgs a) {
     constexpr int NA = SWIGLU ? 2 : 1;
     const int ti = blockIdx.x;
@@ -422,7 +455,10 @@ __global__ __launch_bounds__(256) void moe_grouped_kernel(const MoeFfnArgs a) {
         if constexpr (SWIGLU) {
             half4_t v;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = from_f32<half_t>(moe_silu_mul(acc[t][0][i], acc[t][1][i]));
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (EX) v[i] = from_f32<half_t>(moe_act_ex(a, e, n0 + 4 * g + i, acc[t][0][i], acc[t][1][i]));
+                else v[i] = from_f32<half_t>(moe_silu_mul(acc[t][0][i], acc[t][1][i]));
+            }
             *reinterpret_cast<half4_t *>(a.act + static_cast<size_t>(pr[t]) * Ie + n0 + 4 * g) = v;
         } else {
             *reinterpret_cast<float4_t *>(a.d + static_cast<size_t>(pr[t]) * H + n0 + 4 * g) =
@@ -431,7 +467,8 @@ __global__ __launch_bounds__(256) void moe_grouped_kernel(const MoeFfnArgs a) {
     }
 }
 
-// y[row] = fp16(sum_j w_j d_j (rank order, fp32) + resid[row]); a thread owns 4 columns
+// y[row] = fp16(sum_j w_j d_j (rank order, fp32) + resid[row]); a thread owns 4 columns.  d_j gains the down bias of its expert here
+// (a uniform branch; null: today's sum)
 __global__ __launch_bounds__(kMoeCombineThreads) void moe_combine_kernel(const MoeFfnArgs a) {
     const int row = blockIdx.x, q = blockIdx.y * kMoeCombineThreads + threadIdx.x;
     if (4 * q >= a.H) return;
@@ -439,7 +476,11 @@ __global__ __launch_bounds__(kMoeCombineThreads) void moe_combine_kernel(const M
     for (int j = 0; j < a.k; ++j) {
         const size_t pair = static_cast<size_t>(row) * a.k + j;
         const float w = a.weight[pair];
-        const float4_t v = *reinterpret_cast<const float4_t *>(a.d + pair * a.H + 4 * q);
+        float4_t v = *reinterpret_cast<const float4_t *>(a.d + pair * a.H + 4 * q);
+        if (a.down_bias) {
+            const half_t *b = a.down_bias + static_cast<size_t>(moe_expert_of(a, static_cast<int>(pair))) * a.H + 4 * q;   // (2-byte aligned only)
+            v.x += to_f32(b[0]), v.y += to_f32(b[1]), v.z += to_f32(b[2]), v.w += to_f32(b[3]);
+        }
         s.x = s.x + w * v.x, s.y = s.y + w * v.y, s.z = s.z + w * v.z, s.w = s.w + w * v.w;
     }
     const size_t at = static_cast<size_t>(row) * a.H + 4 * q;
@@ -450,9 +491,291 @@ __global__ __launch_bounds__(kMoeCombineThreads) void moe_combine_kernel(const M
     *reinterpret_cast<half4_t *>(a.y + at) = half4_t{from_f32<half_t>(s.x), from_f32<half_t>(s.y), from_f32<half_t>(s.z), from_f32<half_t>(s.w)};
 }
 
+// ---- MXFP4 experts (llmie_moe_ffn_ex, LLMIE_W_MXFP4): the layout of llmie_quantize_mxfp4 on the flattened [E * 2 Ie, H] / [E * H, Ie] ----
+// GEMV route, the arrangement of mxfp4_gemv_kernel: a lane's 16-byte load is one block of 32 codes and KW waves share a weight row (lane
+// l of part p takes blocks 64 p + l, 64 (p + KW) + l, ..: XB of them), so the 4 / KW wave groups of a workgroup walk their own
+// columns of its 16.  The pair's activation blocks stay in registers; a block's 2^e scales the block's fp32 partial sum; the next
+// rows are requested before the reduction.  K <= 64 KW XB blocks of 32: (XB, KW) = (1, 1), (2, 1), (2, 2), (2, 4) cover K <= 16384.
+template <int XB, int KW>
+__global__ __launch_bounds__(256) void moe_mx4_gemv_gate_up_kernel(const MoeFfnArgs a) {
+    constexpr int GROUPS = 4 / KW, CPG = kMoeGemvCols / GROUPS;   // columns per wave group
+    constexpr int RP = 4, ITERS = CPG / RP;                        // (gate, up) row pairs per iteration: 8 rows x XB loads in flight per lane
+    __shared__ float red[2][4][2 * RP];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, group = wave / KW, part = wave % KW;
+    const int pair = blockIdx.y, row = pair / a.k;
+    const int H = a.H, Ie = a.Ie, nb = H >> 5;
+    const int e = moe_expert_of(a, pair);
+    const uint8_t *W = reinterpret_cast<const uint8_t *>(a.gate_up) + static_cast<size_t>(e) * 2 * Ie * (H >> 1);
+    const uint8_t *S = a.gate_up_scale + static_cast<size_t>(e) * 2 * Ie * nb;
+    const int n_base = blockIdx.x * kMoeGemvCols + group * CPG;
+    int blk[XB];
+    half8_t xr[XB][4];
+    const half_t *xg = a.x + static_cast<size_t>(row) * H;
+#pragma unroll
+    for (int j = 0; j < XB; ++j) {
+        const int b = part * 64 + lane + 64 * KW * j;
+        blk[j] = min(b, nb - 1);   // past the row end: a clamped load meets zero activations
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            xr[j][i] = b < nb ? *reinterpret_cast<const half8_t *>(xg + 32 * static_cast<size_t>(b) + 8 * i) : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    uint4_t wb[2 * RP][XB];
+    unsigned sb[2 * RP][XB];
+    auto load_rows = [&](int it) {
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) {   // r = 2 c + {0: gate, 1: up} of column n_base + it * RP + c
+            const size_t n = static_cast<size_t>(n_base + it * RP + (r >> 1) + (r & 1) * Ie);
+#pragma unroll
+            for (int j = 0; j < XB; ++j) {
+                wb[r][j] = load_nt(reinterpret_cast<const uint4_t *>(W + n * (H >> 1) + 16 * static_cast<size_t>(blk[j])));
+                sb[r][j] = S[n * nb + blk[j]];
+            }
+        }
+    };
+    load_rows(0);
+#pragma unroll 1
+    for (int it = 0; it < ITERS; ++it) {
+        float acc[2 * RP];
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) {
+            acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < XB; ++j) {
+                float p = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p = dot8(mx4_expand(wb[r][j][i]), xr[j][i], p);
+                acc[r] += p * mx4_scale(sb[r][j]);
+            }
+        }
+        if (it + 1 < ITERS) load_rows(it + 1);   // in flight across the reduction
+        float v[2 * RP];
+#pragma unroll
+        for (int r = 0; r < 2 * RP; ++r) v[r] = wave_sum(acc[r]);
+        if constexpr (KW > 1) {   // the parts' sums meet in LDS and are added in part order
+            float (*slot)[2 * RP] = red[it & 1];
+            if (lane == 0) {
+#pragma unroll
+                for (int r = 0; r < 2 * RP; ++r) slot[wave][r] = v[r];
+            }
+            __syncthreads();
+            if (part == 0) {
+#pragma unroll
+                for (int r = 0; r < 2 * RP; ++r) {
+                    v[r] = slot[wave][r];
+#pragma unroll
+                    for (int p = 1; p < KW; ++p) v[r] += slot[wave + p][r];
+                }
+            }
+        }
+        if (part == 0 && lane == 0) {
+#pragma unroll
+            for (int c = 0; c < RP; ++c) {
+                const int n = n_base + it * RP + c;
+                a.act[static_cast<size_t>(pair) * Ie + n] = from_f32<half_t>(moe_act_ex(a, e, n, v[2 * c], v[2 * c + 1]));
+            }
+        }
+    }
+}
+
+// down + combine: grid (blocks of 16 H columns, row); a wave group walks the row's k experts in rank order over its own columns, four
+// per step; the lane that reduces a column owns its sum through the whole walk (rank order, no race)
+template <int XB, int KW>
+__global__ __launch_bounds__(256) void moe_mx4_gemv_down_kernel(const MoeFfnArgs a) {
+    constexpr int GROUPS = 4 / KW, CPG = kMoeGemvCols / GROUPS, RPW = 4, ITERS = CPG / RPW;
+    __shared__ float red[2][4][RPW];
+    __shared__ float ysum[kMoeGemvCols];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, group = wave / KW, part = wave % KW;
+    const int row = blockIdx.y;
+    const int H = a.H, Ie = a.Ie, nb = Ie >> 5;
+    const int n_base = blockIdx.x * kMoeGemvCols + group * CPG;
+    const int steps = a.k * ITERS;   // step s: expert rank s / ITERS, columns n_base + (s % ITERS) * RPW ..
+    const uint8_t *Wd = reinterpret_cast<const uint8_t *>(a.down);
+    int blk[XB];
+    bool live[XB];
+#pragma unroll
+    for (int j = 0; j < XB; ++j) {
+        const int b = part * 64 + lane + 64 * KW * j;
+        blk[j] = min(b, nb - 1), live[j] = b < nb;
+    }
+    uint4_t wb[RPW][XB];
+    unsigned sb[RPW][XB];
+    half8_t ar[XB][4], ar_next[XB][4];
+    auto load_rows = [&](int s) {
+        const int pair = row * a.k + s / ITERS, it = s % ITERS;
+        const size_t wrow = static_cast<size_t>(moe_expert_of(a, pair)) * H + n_base + it * RPW;
+#pragma unroll
+        for (int r = 0; r < RPW; ++r)
+#pragma unroll
+            for (int j = 0; j < XB; ++j) {
+                wb[r][j] = load_nt(reinterpret_cast<const uint4_t *>(Wd + (wrow + r) * (Ie >> 1) + 16 * static_cast<size_t>(blk[j])));
+                sb[r][j] = a.down_scale[(wrow + r) * nb + blk[j]];
+            }
+        if (it == 0) {
+            const half_t *ag = a.act + static_cast<size_t>(pair) * Ie;
+#pragma unroll
+            for (int j = 0; j < XB; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    ar_next[j][i] = live[j] ? *reinterpret_cast<const half8_t *>(ag + 32 * static_cast<size_t>(blk[j]) + 8 * i) : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+    const bool owner = part == 0 && lane == 0;
+    if (owner) {
+#pragma unroll
+        for (int c = 0; c < CPG; ++c) ysum[group * CPG + c] = 0.f;
+    }
+    load_rows(0);
+#pragma unroll 1
+    for (int s = 0; s < steps; ++s) {
+        const int it = s % ITERS;
+        if (it == 0) {
+#pragma unroll
+            for (int j = 0; j < XB; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ar[j][i] = ar_next[j][i];
+        }
+        float acc[RPW];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < XB; ++j) {
+                float p = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p = dot8(mx4_expand(wb[r][j][i]), ar[j][i], p);
+                acc[r] += p * mx4_scale(sb[r][j]);
+            }
+        }
+        if (s + 1 < steps) load_rows(s + 1);
+        float v[RPW];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) v[r] = wave_sum(acc[r]);
+        if constexpr (KW > 1) {
+            float (*slot)[RPW] = red[s & 1];
+            if (lane == 0) {
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) slot[wave][r] = v[r];
+            }
+            __syncthreads();
+            if (part == 0) {
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) {
+                    v[r] = slot[wave][r];
+#pragma unroll
+                    for (int p = 1; p < KW; ++p) v[r] += slot[wave + p][r];
+                }
+            }
+        }
+        if (owner) {
+            const int pair = row * a.k + s / ITERS;
+            const float wj = a.weight[pair];
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const int c = group * CPG + it * RPW + r;
+                float dj = v[r];
+                if (a.down_bias) dj += to_f32(a.down_bias[static_cast<size_t>(moe_expert_of(a, pair)) * H + blockIdx.x * kMoeGemvCols + c]);
+                ysum[c] = ysum[c] + wj * dj;
+            }
+        }
+    }
+    if (owner) {
+#pragma unroll
+        for (int c = 0; c < CPG; ++c) {
+            const size_t at = static_cast<size_t>(row) * H + n_base + c;
+            const float r = a.resid ? to_f32(a.resid[at]) : 0.f;
+            a.y[at] = from_f32<half_t>(ysum[group * CPG + c] + r);
+        }
+    }
+}
+
+// grouped route, the operand order of mxfp4_mfma_kernel: A = the gathered rows of the tile's pairs (lane (c, g): pair slot c, k = 8 g ..
+// 8 g + 7 of the block), B = the expanded codes (weight row n0 + c, the same k), so lane (c, g) of the C/D tile holds D[pair slot
+// 4 g + j][column n0 + c]: one weight row and one scale per lane.  One MFMA per block of 32 into a zeroed tile; the tile times the
+// block's 2^e (exact) is added to the accumulator.  No fp16 weight below the normal range reaches the MFMA.
+template <int RT, bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_mx4_grouped_kernel(const MoeFfnArgs a) {
+    constexpr int NA = SWIGLU ? 2 : 1;
+    const int ti = blockIdx.x;
+    if (ti >= a.hdr[0]) return;   // surplus tile (the whole workgroup)
+    const int e = a.tile_expert[ti];
+    if (e < 0 || e >= a.E) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+    const int H = a.H, Ie = a.Ie;
+    const int K = SWIGLU ? H : Ie, nb = K >> 5;
+    const int n0 = blockIdx.y * kMoeGroupCols + wave * 16;
+    const size_t row0 = SWIGLU ? static_cast<size_t>(e) * 2 * Ie : static_cast<size_t>(e) * H;   // the expert's first weight row
+    const uint8_t *Wc = reinterpret_cast<const uint8_t *>(SWIGLU ? a.gate_up : a.down);
+    const uint8_t *Sc = SWIGLU ? a.gate_up_scale : a.down_scale;
+    const uint8_t *wp[NA], *sp[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const size_t n = row0 + static_cast<size_t>(i) * Ie + n0 + c;
+        wp[i] = Wc + n * (K >> 1) + 4 * g, sp[i] = Sc + n * nb;
+    }
+    const int32_t *tp = a.tile_pairs + static_cast<size_t>(ti) * 16 * RT;
+    const int first = tp[0];
+    if (first < 0 || first >= a.pairs) return;   // (a tile in use has a first pair)
+    const half_t *arow[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        int pa = tp[t * 16 + c];
+        if (pa < 0 || pa >= a.pairs) pa = first;   // padding: any pair of the tile, the result is not stored
+        arow[t] = (SWIGLU ? a.x + static_cast<size_t>(pa / a.k) * H : a.act + static_cast<size_t>(pa) * Ie) + 8 * g;
+    }
+    floatx4 acc[RT][NA];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int i = 0; i < NA; ++i) acc[t][i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    // K % 64 == 0: two blocks per body, all loads requested before the first MFMA
+#pragma unroll 2
+    for (int b = 0; b < nb; b += 2) {
+        unsigned c0[NA], c1[NA], s0[NA], s1[NA];
+        half8_t a0[RT], a1[RT];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            c0[i] = load_nt(reinterpret_cast<const unsigned *>(wp[i] + 16 * static_cast<size_t>(b)));
+            c1[i] = load_nt(reinterpret_cast<const unsigned *>(wp[i] + 16 * static_cast<size_t>(b + 1)));
+            s0[i] = sp[i][b], s1[i] = sp[i][b + 1];
+        }
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+            a0[t] = *reinterpret_cast<const half8_t *>(arow[t] + 32 * static_cast<size_t>(b)), a1[t] = *reinterpret_cast<const half8_t *>(arow[t] + 32 * static_cast<size_t>(b + 1));
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const half8_t bw = mx4_expand(c0[i]);
+            const float s = mx4_scale(s0[i]);
+#pragma unroll
+            for (int t = 0; t < RT; ++t) acc[t][i] += __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[t], bw, floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0) * s;
+        }
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const half8_t bw = mx4_expand(c1[i]);
+            const float s = mx4_scale(s1[i]);
+#pragma unroll
+            for (int t = 0; t < RT; ++t) acc[t][i] += __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t], bw, floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0) * s;
+        }
+    }
+    // D: row (pair slot of the tile) = 4 g + j, column (output column) = n0 + c
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int pq = tp[t * 16 + 4 * g + j];
+            if (pq < 0 || pq >= a.pairs) continue;
+            if constexpr (SWIGLU) a.act[static_cast<size_t>(pq) * Ie + n0 + c] = from_f32<half_t>(moe_act_ex(a, e, n0 + c, acc[t][0][j], acc[t][1][j]));
+            else a.d[static_cast<size_t>(pq) * H + n0 + c] = acc[t][0][j];
+        }
+}
+
 int moe_xc(int K) {
     const int need = (K / 8 + 255) / 256;
     return need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 8));
+}
+// the (XB, KW) of the MXFP4 GEMV kernels: 0 .. 3 = (1, 1), (2, 1), (2, 2), (2, 4)
+int moe_mx4_cfg(int K) {
+    const int nb = K / 32;
+    return nb <= 64 ? 0 : (nb <= 128 ? 1 : (nb <= 256 ? 2 : 3));
 }
 
 void moe_route_launch(const MoeRouteArgs &r, hipStream_t st) { moe_route_kernel<<<(r.rows + 3) / 4, 256, 0, st>>>(r); }
@@ -476,14 +799,57 @@ extern "C" size_t llmie_moe_workspace_bytes(int max_rows, int hidden, int inter,
     return p.bytes;
 }
 
-extern "C" const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+static int moe_plan_line(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format) {
     MoePlan p;
-    if (moe_shape_check("moe_ffn_plan", rows, hidden, inter, experts, top_k)) return nullptr;
-    if (plan_moe("moe_ffn_plan", rows, hidden, inter, experts, top_k, flags, &p)) return nullptr;
+    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
+    if (int rc = plan_moe(who, rows, hidden, inter, experts, top_k, flags, format, &p)) return rc;
     snprintf(g_moe_plan_text, sizeof(g_moe_plan_text), "route=%s rt=%d tiles=%d route_grid=%d plan_grid=%d gate_up_grid=%dx%d down_grid=%dx%d combine_grid=%dx%d ws=%zu",
              p.route == MOE_GEMV ? "gemv" : "grouped", p.rt, p.tiles, p.route_grid, p.route == MOE_GROUPED ? 1 : 0, p.gate_up_grid[0], p.gate_up_grid[1],
              p.down_grid[0], p.down_grid[1], p.combine_grid[0], p.combine_grid[1], p.bytes);
+    return LLMIE_OK;
+}
+
+extern "C" const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+    return moe_plan_line("moe_ffn_plan", rows, hidden, inter, experts, top_k, flags, LLMIE_W_F16) ? nullptr : g_moe_plan_text;
+}
+
+extern "C" const char *llmie_moe_ffn_plan_ex(int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format,
+                                             llmie_moe_act act) {
+    if (format != LLMIE_W_F16 && format != LLMIE_W_MXFP4) {
+        set_error("moe_ffn_plan_ex: expert format %d is neither LLMIE_W_F16 nor LLMIE_W_MXFP4", static_cast<int>(format));
+        return nullptr;
+    }
+    if (act != LLMIE_MOE_ACT_SWIGLU && act != LLMIE_MOE_ACT_SWIGLU_CLAMPED) {
+        set_error("moe_ffn_plan_ex: unknown act %d", static_cast<int>(act));
+        return nullptr;
+    }
+    if (moe_plan_line("moe_ffn_plan_ex", rows, hidden, inter, experts, top_k, flags, format)) return nullptr;
+    const size_t n = strlen(g_moe_plan_text);
+    snprintf(g_moe_plan_text + n, sizeof(g_moe_plan_text) - n, " format=%s act=%s", format == LLMIE_W_MXFP4 ? "mxfp4" : "f16",
+             act == LLMIE_MOE_ACT_SWIGLU_CLAMPED ? "swiglu_clamped" : "swiglu");
     return g_moe_plan_text;
+}
+
+// an expert descriptor on its own: format, the pointers every call needs, scales against the format, the act's constants
+static int moe_experts_check(const char *who, const llmie_moe_experts *ex) {
+    LLMIE_REQUIRE(ex, "%s: NULL expert descriptor", who);
+    if (ex->format != LLMIE_W_F16 && ex->format != LLMIE_W_MXFP4)
+        LLMIE_UNSUPPORTED("%s: expert format %d is neither LLMIE_W_F16 nor LLMIE_W_MXFP4", who, static_cast<int>(ex->format));
+    LLMIE_REQUIRE(ex->router && ex->gate_up && ex->down, "%s: NULL pointer", who);
+    const bool mx = ex->format == LLMIE_W_MXFP4;
+    LLMIE_REQUIRE(!mx || (ex->gate_up_scale && ex->down_scale), "%s: MXFP4 experts with a NULL scale", who);
+    LLMIE_REQUIRE(mx || (!ex->gate_up_scale && !ex->down_scale), "%s: fp16 experts with a scale", who);
+    LLMIE_REQUIRE(ex->act == LLMIE_MOE_ACT_SWIGLU || ex->act == LLMIE_MOE_ACT_SWIGLU_CLAMPED, "%s: unknown act %d", who, static_cast<int>(ex->act));
+    if (ex->act == LLMIE_MOE_ACT_SWIGLU_CLAMPED)
+        LLMIE_REQUIRE(ex->limit > 0.f && ex->limit <= 3.4028235e38f && ex->alpha >= -3.4028235e38f && ex->alpha <= 3.4028235e38f,
+                      "%s: clamped SwiGLU needs a finite limit > 0 and a finite alpha (limit=%g alpha=%g)", who, ex->limit, ex->alpha);
+    return LLMIE_OK;
+}
+static int moe_experts_aligned(const char *who, const llmie_moe_experts *ex) {
+    if (mis16(ex->router) || mis16(ex->gate_up) || mis16(ex->down)) LLMIE_UNSUPPORTED("%s: x / router / gate_up / down / resid / y not 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(ex->router_bias) % 2 || reinterpret_cast<uintptr_t>(ex->gate_up_bias) % 2 || reinterpret_cast<uintptr_t>(ex->down_bias) % 2)
+        LLMIE_UNSUPPORTED("%s: a bias is not 2-byte aligned", who);
+    return LLMIE_OK;
 }
 
 extern "C" int llmie_moe_route(const void *x, const void *router, int rows, int hidden, int experts, int top_k, unsigned flags, int32_t *expert_out,
@@ -494,83 +860,145 @@ extern "C" int llmie_moe_route(const void *x, const void *router, int rows, int 
     if (mis16(x) || mis16(router)) LLMIE_UNSUPPORTED("moe_route: x / router not 16-byte aligned");
     LLMIE_REQUIRE(!(flags & ~kMoeFlags), "moe_route: unknown flags 0x%x", flags);
     MoeRouteArgs r{static_cast<const half_t *>(x), static_cast<const half_t *>(router), rows, hidden, experts, top_k,
-                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out};
+                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out, nullptr};
     moe_route_launch(r, as_stream(stream));
     return launch_status("moe_route");
 }
 
-// would llmie_moe_ffn take this shape and these flags?  The code and the message under `who`; nothing is launched
-int llmie::moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+// llmie_moe_route with the descriptor's router and router bias; the expert matrices are not looked at
+extern "C" int llmie_moe_route_ex(const void *x, const llmie_moe_experts *ex, int rows, int hidden, int experts, int top_k, unsigned flags,
+                                  int32_t *expert_out, float *weight_out, llmie_dtype dtype, llmie_stream stream) {
+    LLMIE_REQUIRE(x && ex && ex->router && expert_out && weight_out, "moe_route_ex: NULL pointer");
+    if (int rc = moe_shape_check("moe_route_ex", rows, hidden, 64, experts, top_k)) return rc;
+    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_route_ex: fp16 activations only");
+    if (mis16(x) || mis16(ex->router)) LLMIE_UNSUPPORTED("moe_route_ex: x / router not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(ex->router_bias) % 2) LLMIE_UNSUPPORTED("moe_route_ex: router_bias not 2-byte aligned");
+    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "moe_route_ex: unknown flags 0x%x", flags);
+    MoeRouteArgs r{static_cast<const half_t *>(x), static_cast<const half_t *>(ex->router), rows, hidden, experts, top_k,
+                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out, static_cast<const half_t *>(ex->router_bias)};
+    moe_route_launch(r, as_stream(stream));
+    return launch_status("moe_route_ex");
+}
+
+// would llmie_moe_ffn / _ex take this shape and these flags?  The code and the message under `who`; nothing is launched
+int llmie::moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format) {
     if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
     MoePlan p;
-    return plan_moe(who, rows, hidden, inter, experts, top_k, flags, &p);
+    return plan_moe(who, rows, hidden, inter, experts, top_k, flags, format, &p);
+}
+// would the entries take this descriptor (llmie_decoder_moe_attach_ex checks every sparse layer's)?
+int llmie::moe_experts_ok(const char *who, const llmie_moe_experts *ex) {
+    if (int rc = moe_experts_check(who, ex)) return rc;
+    return moe_experts_aligned(who, ex);
 }
 
 extern "C" int llmie_moe_ffn(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows,
                              int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
                              llmie_dtype dtype, llmie_stream stream) {
-    return moe_ffn_stages(x, router, gate_up, down, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
+    llmie_moe_experts ex{};   // fp16, no biases, plain SwiGLU
+    ex.format = LLMIE_W_F16, ex.router = router, ex.gate_up = gate_up, ex.down = down, ex.act = LLMIE_MOE_ACT_SWIGLU;
+    return moe_ffn_stages("moe_ffn", x, &ex, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
                           MOE_STAGE_ROUTE | MOE_STAGE_GATE_UP | MOE_STAGE_DOWN, stream);
 }
 
-// llmie_moe_ffn, or some of its stages (the engine accounts them under three op kinds): every check is made for every stage
-int llmie::moe_ffn_stages(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows,
-                          int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
-                          llmie_dtype dtype, unsigned stages, llmie_stream stream) {
-    LLMIE_REQUIRE(x && router && gate_up && down && y, "moe_ffn: NULL pointer");
-    if (int rc = moe_shape_check("moe_ffn", rows, hidden, inter, experts, top_k)) return rc;
-    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_ffn: fp16 activations only");
-    if (mis16(x) || mis16(router) || mis16(gate_up) || mis16(down) || mis16(resid) || mis16(y))
-        LLMIE_UNSUPPORTED("moe_ffn: x / router / gate_up / down / resid / y not 16-byte aligned");
+extern "C" int llmie_moe_ffn_ex(const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter, int experts,
+                                int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
+    return moe_ffn_stages("moe_ffn_ex", x, ex, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
+                          MOE_STAGE_ROUTE | MOE_STAGE_GATE_UP | MOE_STAGE_DOWN, stream);
+}
+
+// llmie_moe_ffn / _ex, or some of its stages (the engine accounts them under three op kinds): every check is made for every stage.
+// fp16 experts without a bias under plain SwiGLU launch the instantiations llmie_moe_ffn always launched
+int llmie::moe_ffn_stages(const char *who, const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter,
+                          int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
+                          llmie_stream stream) {
+    LLMIE_REQUIRE(x && y, "%s: NULL pointer", who);
+    if (int rc = moe_experts_check(who, ex)) return rc;
+    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
+    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: fp16 activations only", who);
+    if (mis16(x) || mis16(resid) || mis16(y)) LLMIE_UNSUPPORTED("%s: x / router / gate_up / down / resid / y not 16-byte aligned", who);
+    if (int rc = moe_experts_aligned(who, ex)) return rc;
+    const void *router = ex->router;
+    const bool mx4 = ex->format == LLMIE_W_MXFP4;
+    const bool plain = !mx4 && !ex->gate_up_bias && !ex->down_bias && ex->act == LLMIE_MOE_ACT_SWIGLU;
     MoePlan p;
-    if (int rc = plan_moe("moe_ffn", rows, hidden, inter, experts, top_k, flags, &p)) return rc;
+    if (int rc = plan_moe(who, rows, hidden, inter, experts, top_k, flags, ex->format, &p)) return rc;
     if (!workspace || workspace_bytes < p.bytes || reinterpret_cast<uintptr_t>(workspace) % 256) {
-        set_error("moe_ffn: workspace missing, too small or not 256-byte aligned (%zu < %zu)", workspace ? workspace_bytes : size_t(0), p.bytes);
+        set_error("%s: workspace missing, too small or not 256-byte aligned (%zu < %zu)", who, workspace ? workspace_bytes : size_t(0), p.bytes);
         return LLMIE_ERR_WORKSPACE;
     }
     char *base = static_cast<char *>(workspace);
     hipStream_t st = as_stream(stream);
     MoeFfnArgs a{};
-    a.x = static_cast<const half_t *>(x), a.gate_up = static_cast<const half_t *>(gate_up), a.down = static_cast<const half_t *>(down);
+    a.x = static_cast<const half_t *>(x), a.gate_up = static_cast<const half_t *>(ex->gate_up), a.down = static_cast<const half_t *>(ex->down);
     a.resid = static_cast<const half_t *>(resid), a.y = static_cast<half_t *>(y), a.act = reinterpret_cast<half_t *>(base + p.act);
     a.expert = reinterpret_cast<const int32_t *>(base + p.expert), a.weight = reinterpret_cast<const float *>(base + p.weight);
     a.rows = rows, a.H = hidden, a.Ie = inter, a.E = experts, a.k = top_k, a.pairs = p.pairs;
     a.hdr = reinterpret_cast<const int32_t *>(base), a.tile_expert = reinterpret_cast<const int32_t *>(base + p.tile_expert);
     a.tile_pairs = reinterpret_cast<const int32_t *>(base + p.tile_pairs), a.d = reinterpret_cast<float *>(base + p.d);
+    a.gate_up_scale = static_cast<const uint8_t *>(ex->gate_up_scale), a.down_scale = static_cast<const uint8_t *>(ex->down_scale);
+    a.gate_up_bias = static_cast<const half_t *>(ex->gate_up_bias), a.down_bias = static_cast<const half_t *>(ex->down_bias);
+    a.act_kind = static_cast<int>(ex->act), a.alpha = ex->alpha, a.limit = ex->limit;
     MoeRouteArgs r{a.x, static_cast<const half_t *>(router), rows, hidden, experts, top_k, (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0,
-                   reinterpret_cast<int32_t *>(base + p.expert), reinterpret_cast<float *>(base + p.weight)};
+                   reinterpret_cast<int32_t *>(base + p.expert), reinterpret_cast<float *>(base + p.weight), static_cast<const half_t *>(ex->router_bias)};
     if (stages & MOE_STAGE_ROUTE) {
         moe_route_launch(r, st);
         if (int rc = launch_status("moe_ffn(route)")) return rc;
     }
     const dim3 g1(p.gate_up_grid[0], p.gate_up_grid[1]), g2(p.down_grid[0], p.down_grid[1]), g3(p.combine_grid[0], p.combine_grid[1]);
+// one launch of KERNEL<N, EX> for the XC the K needs; EX = !plain
+#define LLMIE_MOE_GEMV(KERNEL, K, GRID)                                                      \
+    switch (moe_xc(K)) {                                                                     \
+        case 1: if (plain) KERNEL<1, false><<<GRID, 256, 0, st>>>(a); else KERNEL<1, true><<<GRID, 256, 0, st>>>(a); break; \
+        case 2: if (plain) KERNEL<2, false><<<GRID, 256, 0, st>>>(a); else KERNEL<2, true><<<GRID, 256, 0, st>>>(a); break; \
+        case 4: if (plain) KERNEL<4, false><<<GRID, 256, 0, st>>>(a); else KERNEL<4, true><<<GRID, 256, 0, st>>>(a); break; \
+        default: if (plain) KERNEL<8, false><<<GRID, 256, 0, st>>>(a); else KERNEL<8, true><<<GRID, 256, 0, st>>>(a); break; \
+    }
+#define LLMIE_MOE_MX4_GEMV(KERNEL, K, GRID)                        \
+    switch (moe_mx4_cfg(K)) {                                      \
+        case 0: KERNEL<1, 1><<<GRID, 256, 0, st>>>(a); break;      \
+        case 1: KERNEL<2, 1><<<GRID, 256, 0, st>>>(a); break;      \
+        case 2: KERNEL<2, 2><<<GRID, 256, 0, st>>>(a); break;      \
+        default: KERNEL<2, 4><<<GRID, 256, 0, st>>>(a); break;     \
+    }
     if (p.route == MOE_GEMV) {
-        if (stages & MOE_STAGE_GATE_UP) switch (moe_xc(hidden)) {
-            case 1: moe_gemv_gate_up_kernel<1><<<g1, 256, 0, st>>>(a); break;
-            case 2: moe_gemv_gate_up_kernel<2><<<g1, 256, 0, st>>>(a); break;
-            case 4: moe_gemv_gate_up_kernel<4><<<g1, 256, 0, st>>>(a); break;
-            default: moe_gemv_gate_up_kernel<8><<<g1, 256, 0, st>>>(a); break;
+        if (stages & MOE_STAGE_GATE_UP) {
+            if (mx4) LLMIE_MOE_MX4_GEMV(moe_mx4_gemv_gate_up_kernel, hidden, g1)
+            else LLMIE_MOE_GEMV(moe_gemv_gate_up_kernel, hidden, g1)
         }
         if (int rc = launch_status("moe_ffn(gate_up gemv)")) return rc;
-        if (stages & MOE_STAGE_DOWN) switch (moe_xc(inter)) {
-            case 1: moe_gemv_down_kernel<1><<<g2, 256, 0, st>>>(a); break;
-            case 2: moe_gemv_down_kernel<2><<<g2, 256, 0, st>>>(a); break;
-            case 4: moe_gemv_down_kernel<4><<<g2, 256, 0, st>>>(a); break;
-            default: moe_gemv_down_kernel<8><<<g2, 256, 0, st>>>(a); break;
+        if (stages & MOE_STAGE_DOWN) {
+            if (mx4) LLMIE_MOE_MX4_GEMV(moe_mx4_gemv_down_kernel, inter, g2)
+            else LLMIE_MOE_GEMV(moe_gemv_down_kernel, inter, g2)
         }
         return launch_status("moe_ffn(down gemv)");
     }
+#undef LLMIE_MOE_GEMV
+#undef LLMIE_MOE_MX4_GEMV
     if (stages & MOE_STAGE_GATE_UP) {
         moe_plan_kernel<<<1, 256, 0, st>>>(a.expert, p.pairs, experts, p.rt, reinterpret_cast<int32_t *>(base), reinterpret_cast<int32_t *>(base + p.tile_expert),
                                            reinterpret_cast<int32_t *>(base + p.tile_pairs), p.tiles);
         if (int rc = launch_status("moe_ffn(plan)")) return rc;
-        if (p.rt == 4) moe_grouped_kernel<4, true><<<g1, 256, 0, st>>>(a);
-        else moe_grouped_kernel<1, true><<<g1, 256, 0, st>>>(a);
+        if (mx4) {
+            if (p.rt == 4) moe_mx4_grouped_kernel<4, true><<<g1, 256, 0, st>>>(a);
+            else moe_mx4_grouped_kernel<1, true><<<g1, 256, 0, st>>>(a);
+        } else if (plain) {
+            if (p.rt == 4) moe_grouped_kernel<4, true, false><<<g1, 256, 0, st>>>(a);
+            else moe_grouped_kernel<1, true, false><<<g1, 256, 0, st>>>(a);
+        } else {
+            if (p.rt == 4) moe_grouped_kernel<4, true, true><<<g1, 256, 0, st>>>(a);
+            else moe_grouped_kernel<1, true, true><<<g1, 256, 0, st>>>(a);
+        }
         if (int rc = launch_status("moe_ffn(gate_up grouped)")) return rc;
     }
     if (stages & MOE_STAGE_DOWN) {
-        if (p.rt == 4) moe_grouped_kernel<4, false><<<g2, 256, 0, st>>>(a);
-        else moe_grouped_kernel<1, false><<<g2, 256, 0, st>>>(a);
+        if (mx4) {
+            if (p.rt == 4) moe_mx4_grouped_kernel<4, false><<<g2, 256, 0, st>>>(a);
+            else moe_mx4_grouped_kernel<1, false><<<g2, 256, 0, st>>>(a);
+        } else {
+            if (p.rt == 4) moe_grouped_kernel<4, false, false><<<g2, 256, 0, st>>>(a);
+            else moe_grouped_kernel<1, false, false><<<g2, 256, 0, st>>>(a);
+        }
         if (int rc = launch_status("moe_ffn(down grouped)")) return rc;
         moe_combine_kernel<<<g3, kMoeCombineThreads, 0, st>>>(a);
         return launch_status("moe_ffn(combine)");

@@ -14,21 +14,7 @@
 
 namespace llmie {
 
-// 8 codes (one word, nibble j = element j) -> 8 unscaled fp16 weights, signs included (-0 stays -0)
-__device__ __forceinline__ half8_t mx4_expand(unsigned w) {
-    const half2_t up = {static_cast<half_t>(16384.f), static_cast<half_t>(16384.f)};
-    half8_t o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const unsigned b = w >> (8 * j);
-        const unsigned v = (b & 0xfu) | ((b & 0xf0u) << 12);   // the byte's two codes in bits 0..3 and 16..19
-        const half2_t h = __builtin_bit_cast(half2_t, ((v & 0x00070007u) << 9) | ((v & 0x00080008u) << 12)) * up;
-        o[2 * j] = h[0], o[2 * j + 1] = h[1];
-    }
-    return o;
-}
-// 2^(byte - 127) as fp32 (byte 0: the subnormal 2^-127; byte 0xFF, NaN in e8m0, comes out as +inf: unspecified results)
-__device__ __forceinline__ float mx4_scale(unsigned byte) { return __builtin_bit_cast(float, byte ? byte << 23 : 0x00400000u); }
+// mx4_expand / mx4_scale (device_utils.cuh): 8 codes of one word -> 8 unscaled fp16 weights; a scale byte -> 2^e as fp32
 
 // ---- quantiser: one thread per block of 32 ----
 __global__ __launch_bounds__(256) void mxfp4_quantize_kernel(const half_t *__restrict__ w, uint8_t *__restrict__ wq,

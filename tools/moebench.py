@@ -2,7 +2,7 @@
 """Mixture-of-experts FFN: llmie_moe_ffn against the dense FFN launches of the same weight bytes, at the Mixtral-8x7B layer shape
 (H = 4096, Ie = 14336, E = 8, k = 2):
 
-    python tools/moebench.py [--decode 1 2 3 4 5 6 8 12 16] [--prefill 128 512 2048] [--rounds 7] [--reps 20] [--out FILE]
+    python tools/moebench.py [--decode 1 2 3 4 5 6 8 12 16] [--prefill 128 512 2048] [--rounds 7] [--reps 20] [--mxfp4] [--out FILE]
 
 Arms, same process, same weights, alternating inside every round; the median round of each arm is reported with its min and max.
   decode rows R (1 .. 16):  gemv     llmie_moe_ffn under LLMIE_MOE_FORCE_GEMV
@@ -12,6 +12,9 @@ Arms, same process, same weights, alternating inside every round; the median rou
   prefill T tokens:         rt1 / rt4  llmie_moe_ffn grouped under LLMIE_MOE_FORCE_RT1 / _RT4
                             dense      ONE dense FFN of inter size Ie on the T tokens (each token runs k experts: the MoE layer does
                                        k times these FLOPs)
+--mxfp4 adds the same arms on the MXFP4 image of the same experts (llmie_moe_ffn_ex; mx_gemv, mx_grouped, mx_rt1, mx_rt4), interleaved
+with the fp16 arms in every round, and reports each one's ratio to its fp16 arm and the weight bytes per second of the faster route
+(fp16: 2 bytes per weight, MXFP4: 17 / 32).  Decode rows above 16 have no GEMV arm (LLMIE_MOE_FORCE_GEMV stops at 16 rows).
 The rows of a call are independent normal vectors and the router is random, so the pairs spread over the experts as a trained
 router's roughly would.  Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -60,6 +63,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--mxfp4", action="store_true", help="add the MXFP4-expert arms beside the fp16 ones")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -70,6 +74,7 @@ def main():
     router = (torch.randn((E, H), generator=g, device="cuda") / H ** 0.5).half()
     gate_up = (torch.randn((E, 2 * Ie, H), generator=g, device="cuda") / H ** 0.5).half()
     down = (torch.randn((E, H, Ie), generator=g, device="cuda") / Ie ** 0.5).half()
+    exq = llmie.MoeExperts.quantize(router, gate_up, down) if a.mxfp4 else None
     top = max(a.decode + a.prefill)
     ws = llmie.moe_workspace(top, H, Ie, E, k)
     results = []
@@ -84,6 +89,9 @@ def main():
             def moe(flags):
                 return lambda: llmie.moe_ffn(x, router, gate_up, down, y, k, resid=resid, flags=flags, workspace=ws)
 
+            def moe_mx(flags):
+                return lambda: llmie.moe_ffn_ex(x, exq, y, k, resid=resid, flags=flags, workspace=ws)
+
             def dense(experts):
                 def run():
                     for e in experts:
@@ -92,26 +100,53 @@ def main():
                 return run
 
             if kind == "decode":
-                arms = dict(gemv=moe(llmie.MOE_FORCE_GEMV), grouped=moe(llmie.MOE_FORCE_GROUPED), dense=dense(chosen))
+                arms = dict(grouped=moe(llmie.MOE_FORCE_GROUPED), dense=dense(chosen))
+                if R <= 16:
+                    arms["gemv"] = moe(llmie.MOE_FORCE_GEMV)
+                if a.mxfp4:
+                    arms["mx_grouped"] = moe_mx(llmie.MOE_FORCE_GROUPED)
+                    if R <= 16:
+                        arms["mx_gemv"] = moe_mx(llmie.MOE_FORCE_GEMV)
                 reps = a.reps
             else:
                 arms = dict(rt1=moe(llmie.MOE_FORCE_GROUPED | llmie.MOE_FORCE_RT1), rt4=moe(llmie.MOE_FORCE_GROUPED | llmie.MOE_FORCE_RT4),
                             dense=dense(chosen[:1]))
+                if a.mxfp4:
+                    arms.update(mx_rt1=moe_mx(llmie.MOE_FORCE_GROUPED | llmie.MOE_FORCE_RT1), mx_rt4=moe_mx(llmie.MOE_FORCE_GROUPED | llmie.MOE_FORCE_RT4))
                 reps = max(a.reps // 4, 2)
+            try:   # the dense launches refuse some shapes (a fused SwiGLU projection above 64 rows with inter % 256 != 0): no dense arm then
+                arms["dense"]()
+            except llmie.LlmieError:
+                del arms["dense"]
             r = measure(arms, a.rounds, reps)
             res = dict(kind=kind, rows=R, plan=llmie.moe_ffn_plan(R, H, Ie, E, k), **{n + "_ms": v["ms"] for n, v in r.items()},
                        **{n + "_min_max": [v["min"], v["max"]] for n, v in r.items()})
-            if kind == "decode":
-                res["gemv_over_dense"] = r["gemv"]["ms"] / r["dense"]["ms"]
+            if a.mxfp4:
+                # the weights a call streams: every expert some pair selects, once (counted from the routing of this call's rows)
+                touched = len(set(ids.flatten().tolist()))
+                weights = touched * 3 * Ie * H
+                f16 = min(v["ms"] for n, v in r.items() if n in ("gemv", "grouped", "rt1", "rt4"))
+                mx4 = min(v["ms"] for n, v in r.items() if n.startswith("mx_"))
+                res.update(experts_touched=touched, f16_best_ms=f16, mx_best_ms=mx4, mx_over_f16=mx4 / f16,
+                           f16_weight_tb_s=weights * 2 / f16 / 1e9, mx_weight_tb_s=weights * 17 / 32 / mx4 / 1e9)
+                for n in ("gemv", "grouped", "rt1", "rt4"):
+                    if n in r and "mx_" + n in r:
+                        res["mx_%s_over_%s" % (n, n)] = r["mx_" + n]["ms"] / r[n]["ms"]
+                if "mx_gemv" in r:
+                    res["mx_grouped_over_mx_gemv"] = r["mx_grouped"]["ms"] / r["mx_gemv"]["ms"]
+            if kind == "decode" and "gemv" in r:
+                if "dense" in r:
+                    res["gemv_over_dense"] = r["gemv"]["ms"] / r["dense"]["ms"]
                 res["grouped_over_gemv"] = r["grouped"]["ms"] / r["gemv"]["ms"]
-            else:
+            elif kind == "prefill":
                 best = min(r["rt1"]["ms"], r["rt4"]["ms"])
                 res["tokens_per_s"] = R / best * 1e3
                 res["rt4_over_rt1"] = r["rt4"]["ms"] / r["rt1"]["ms"]
-                res["dense_ffn_over_moe"] = r["dense"]["ms"] / best
+                if "dense" in r:
+                    res["dense_ffn_over_moe"] = r["dense"]["ms"] / best
             results.append(res)
             print(json.dumps(res), file=sys.stderr)
-    line = json.dumps(dict(bench="moe", device=torch.cuda.get_device_name(0), hidden=H, inter=Ie, experts=E, top_k=k, rounds=a.rounds, reps=a.reps,
+    line = json.dumps(dict(bench="moe", mxfp4=bool(a.mxfp4), device=torch.cuda.get_device_name(0), hidden=H, inter=Ie, experts=E, top_k=k, rounds=a.rounds, reps=a.reps,
                            results=results))
     print(line)
     if a.out:
