@@ -265,6 +265,65 @@ const char *llmie_decoder_mha_window_plan(llmie_dtype dtype, int kv_e4m3, int ba
                                           unsigned long long residues, long long workspace_bytes, int window, int sinks,
                                           int *status);
 
+/* ABI 3 (an addition; no reference counterpart).  A learned sink logit per query head ("head sink"; gpt-oss `self_attn.sinks`).
+ * "Sinks" keeps meaning sink TOKENS (above); the two features compose.  head_sink: device array of fp32, [head_num] for one layer
+ * ([num_layers, head_num] on an engine, llmie_decoder_set_head_sinks); a loader converts stored bf16 values to fp32.  Let l_j be the
+ * scaled logits of the keys the mask exposes to the query (causal; with a window, the window and its sink tokens) and s_h the value
+ * of query head h.  Its softmax runs over those keys and ONE extra column with logit s_h and no value row:
+ *        M   = max(max_j l_j, s_h)
+ *        out = sum_j exp(l_j - M) v_j / (sum_j exp(l_j - M) + exp(s_h - M) + 1e-6)
+ * The extra term enters exactly once per (query row, head), whatever the number of splits, waves, tiles or lanes that share the row.
+ * s_h = -INFINITY is "no sink for this head" and gives the bits of the call without a head sink.  The array is read on the device at
+ * every launch, so a captured step replays with new values.  NaN values: results unspecified; the call stays in bounds and ends.
+ *
+ * llmie_decoder_mha_sink: llmie_decoder_mha_window's operands and behaviour plus head_sink (nullable: NULL is that entry's call, bit
+ * for bit).  Supported with a head sink where the windowed form is: fp16 activations, head_size 64 / 128, head_num / kv_head_num in
+ * {1,2,4,8} (e4m3 cache: {1,2,4}), dense or paged, tickets or separate merge; anything else with head_sink != NULL is
+ * LLMIE_ERR_UNSUPPORTED and writes nothing.  llmie_decoder_mha_sink_plan: llmie_decoder_mha_window_plan plus the form bit
+ * LLMIE_ATTN_HEAD_SINK (the two older plan queries ignore the bit); the line gains " head_sink" when it is set -- same grid, slots and
+ * merge, the SINK instantiation of the kernels. */
+#define LLMIE_ATTN_HEAD_SINK 512u /* head_sink given */
+int llmie_decoder_mha_sink(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer,
+                           int batch, int head_num, int kv_head_num, int head_size, int max_seq_len,
+                           const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
+                           int rotary_dim, const int32_t *block_table, int max_pages, int num_pages, int window, int sinks,
+                           int32_t *tickets, int kv_e4m3, float k_scale, float v_scale, const float *head_sink /* device, [head_num] */,
+                           llmie_dtype dtype, llmie_stream stream);
+const char *llmie_decoder_mha_sink_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                        int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                        unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                        int *status);
+
+/* ABI 3 (an addition; host only, no device access).  RoPE frequency scaling: the one function that computes a (cos, sin) table.
+ * cos_sin_out: host, [max_pos][head_size/2] pairs (cos, sin), the layout of llmie_decoder_mha_rope's rope_table.  For pair
+ * j < rotary_dim/2 with f_j = rotary_base^(-2j/rotary_dim) the entry at position p is (cos(p f'_j), sin(p f'_j)) a, where
+ *   LLMIE_ROPE_LINEAR  f'_j = f_j / factor
+ *   LLMIE_ROPE_LLAMA3  wavelength w = 2 pi / f_j;  w > original/low_freq_factor: f_j / factor;  w < original/high_freq_factor: f_j;
+ *                      otherwise t = (original/w - low_freq_factor) / (high_freq_factor - low_freq_factor), f'_j = (1-t) f_j/factor + t f_j
+ *   LLMIE_ROPE_YARN    c(n) = rotary_dim ln(original / (2 pi n)) / (2 ln base); lo = c(beta_fast), hi = c(beta_slow); with `truncate`
+ *                      lo = floor(lo), hi = ceil(hi); then lo = max(lo, 0), hi = min(hi, rotary_dim - 1), hi += 0.001 if equal;
+ *                      ramp_j = clamp((j - lo)/(hi - lo), 0, 1); f'_j = f_j/factor ramp_j + f_j (1 - ramp_j); a = the attention factor
+ * (a = 1 for the other kinds).  factor >= 1 is used by every kind but NONE; original_max_pos by LLAMA3 and YARN; low_/high_freq_factor
+ * by LLAMA3; beta_fast, beta_slow, attn_factor and truncate by YARN: a beta of 0 means 32 / 1, an attn_factor <= 0 means
+ * 0.1 ln(factor) + 1.  Entries with j >= rotary_dim/2 stay (1, 0), unscaled.  Scaled kinds are evaluated in double and rounded once
+ * to fp32.  LLMIE_ROPE_NONE, or scaling = NULL, runs the fp32 formula llmie_decoder_create has always used (cosf / sinf of
+ * p / powf(base, 2j/rotary_dim)) and gives that table bit for bit; llmie_decoder_create calls this function with NULL.
+ * LLMIE_ERR_INVALID_ARG: NULL output, max_pos < 1, an odd or non-positive head_size, rotary_dim odd or outside [2, head_size],
+ * base <= 0, an unknown kind, factor < 1 (or not finite), original_max_pos < 1 where used, high_freq_factor <= low_freq_factor or
+ * low_freq_factor <= 0 (LLAMA3), a negative beta (YARN). */
+typedef enum { LLMIE_ROPE_NONE = 0, LLMIE_ROPE_LINEAR, LLMIE_ROPE_LLAMA3, LLMIE_ROPE_YARN } llmie_rope_kind;
+typedef struct {
+    llmie_rope_kind kind;
+    float factor;
+    int original_max_pos;
+    float low_freq_factor, high_freq_factor;
+    float beta_fast, beta_slow;
+    float attn_factor;
+    int truncate;
+} llmie_rope_scaling;
+int llmie_rope_table_fill(float *cos_sin_out, int max_pos, int head_size, int rotary_dim, float rotary_base,
+                          const llmie_rope_scaling *scaling);
+
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
  * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the
@@ -982,6 +1041,30 @@ int llmie_decoder_lora_detach(llmie_decoder *dec);
  * under LLMIE_PLAN_WINDOW (same sequences; NULL for an engine set_window refuses; the layer plan ends in " attn_window=1"). */
 #define LLMIE_PLAN_WINDOW 2048u /* a sliding window is set on some layer (llmie_decoder_set_window) */
 int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer_window /* host, [num_layers], 0 = full; NULL clears */, int sinks);
+
+/* ABI 3 (additions; llmie_decoder_config is not touched).  The two attention properties of gpt-oss / Llama-3 checkpoints on an engine.
+ *
+ * llmie_decoder_set_head_sinks: the learned per-head sink logits stated at llmie_decoder_mha_sink, head_sink_dev = DEVICE array
+ * [num_layers, head_num] of fp32 (row l = layer l; -INFINITY = no sink for that head); NULL clears.  The pointer is kept on the
+ * engine -- the array must stay alive while it is set -- and read when a call is planned, in the pattern of llmie_decoder_set_window;
+ * its VALUES are read on the device at every launch, so a captured step replays with new values.  From then on every decode entry
+ * and every prefill entry (and the spec, score, LoRA and MoE sequences built on them) runs the SINK instantiation of its attention
+ * launch with the layer's row; windows compose.  Only the attention launches change; llmie_decoder_set_head_sinks(dec, NULL) restores
+ * today's bits.  LLMIE_ERR_UNSUPPORTED: an engine whose decode attention has no such form (fp32; head sizes other than 64 / 128; head
+ * ratios other than 1 / 2 / 4 / 8; with an e4m3 cache also ratio 8).  A call whose operands send its attention to the generic kernel
+ * (unaligned buffers) fails with LLMIE_ERR_UNSUPPORTED while sinks are set.  llmie_decoder_plan_name and
+ * llmie_decoder_prefill_layer_plan answer for such a call under LLMIE_PLAN_HEAD_SINK (same sequences; NULL for an engine
+ * set_head_sinks refuses; the layer plan ends in " attn_head_sink=1", after " attn_window=1" when both are set).
+ *
+ * llmie_decoder_set_rope_scaling: refills the engine's (cos, sin) table with llmie_rope_table_fill(max_seq_len, head_size, rotary_dim,
+ * rotary_base, scaling) and uploads it with one SYNCHRONOUS copy: not inside a stream capture, and not while a call that reads the
+ * table is in flight.  NULL restores the create-time table bit for bit.  Every fused path reads the table, so decode, prefill and the
+ * entries built on them rotate by the new angles.  LLMIE_ERR_UNSUPPORTED: an engine whose decode attention does not take the table
+ * (head sizes outside {32,64,128,256} or head ratios outside {1,2,4,8}: those steps rotate with llmie_rope_decode by rotary_base);
+ * the refusals of llmie_rope_table_fill apply, and a refused call leaves the table as it was. */
+#define LLMIE_PLAN_HEAD_SINK 4096u /* head sinks are set (llmie_decoder_set_head_sinks) */
+int llmie_decoder_set_head_sinks(llmie_decoder *dec, const float *head_sink_dev /* device, [num_layers, head_num]; NULL clears */);
+int llmie_decoder_set_rope_scaling(llmie_decoder *dec, const llmie_rope_scaling *scaling /* host; NULL = the create-time table */);
 
 /* ABI 3 (an addition).  Mixture-of-experts FFN, Mixtral / Qwen-MoE semantics: every row is routed to top_k of `experts` expert FFNs.
  * fp16 activations and fp16 experts only.  Operands (device, 16-byte aligned): x [rows, hidden]; router Wr [experts, hidden];

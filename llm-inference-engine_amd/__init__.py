@@ -97,6 +97,12 @@ _SIGS = {
                                  _i, _f, _f, _i, _vp],
     "llmie_decoder_mha_window_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _i, _i, _vp],
     "llmie_kv_window_advance": [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "llmie_decoder_mha_sink": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _vp,
+                               _i, _f, _f, _vp, _i, _vp],
+    "llmie_decoder_mha_sink_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _i, _i, _vp],
+    "llmie_rope_table_fill": [_vp, _i, _i, _i, _f, _vp],
+    "llmie_decoder_set_head_sinks": [_vp, _vp],
+    "llmie_decoder_set_rope_scaling": [_vp, _vp],
     "llmie_decoder_prefill_workspace_bytes": [_vp, _i, _i],
     "llmie_decoder_prefill": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
     "llmie_lm_head_sample": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp,
@@ -190,6 +196,7 @@ _RESTYPES = {
     "llmie_gemm256_tiles": C.c_char_p,
     "llmie_decoder_mha_plan": C.c_char_p,
     "llmie_decoder_mha_window_plan": C.c_char_p,
+    "llmie_decoder_mha_sink_plan": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
     "llmie_decoder_prefill_layer_plan": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
@@ -304,7 +311,8 @@ def gemm256_tiles(form, operands, M, N, K):
     return r.decode() if r is not None else None
 
 
-ATTN_FORMS = {"step_dev": 1, "ragged": 2, "bias": 4, "rope": 8, "tickets": 16, "slabs": 32, "paged": 64, "x32": 128, "bad_scales": 256}
+ATTN_FORMS = {"step_dev": 1, "ragged": 2, "bias": 4, "rope": 8, "tickets": 16, "slabs": 32, "paged": 64, "x32": 128, "bad_scales": 256,
+              "head_sink": 512}
 ATTN_OPERANDS = ("qkv", "bias", "k", "v", "slab", "wf", "wh", "slab_stride")
 
 
@@ -338,6 +346,57 @@ def decoder_mha_window_plan(dtype, batch, head_num, kv_head_num, head_size, max_
                                             max_pages, num_pages, r, -1 if workspace_bytes is None else workspace_bytes, window, sinks,
                                             C.addressof(status))
     return (t.decode() if t is not None else None), status.value
+
+
+def decoder_mha_sink_plan(dtype, batch, head_num, kv_head_num, head_size, max_seq_len, window=0, sinks=0, step=-1, kv_e4m3=False,
+                          forms=(), max_pages=0, num_pages=0, residues=None, workspace_bytes="exact"):
+    """decoder_mha_window_plan plus the form "head_sink" (llmie_decoder_mha_sink_plan): with it the line ends in " head_sink" -- the
+    same grid, slots and merge on the SINK instantiation of the kernels -- or the call is refused where no such form exists.  No device
+    needed."""
+    f = sum(ATTN_FORMS[n] for n in forms)
+    r = sum((v & 15) << (4 * ATTN_OPERANDS.index(k)) for k, v in (residues or {}).items())
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_decoder_mha_sink_plan(dtype, int(kv_e4m3), batch, head_num, kv_head_num, head_size, max_seq_len, step, f,
+                                          max_pages, num_pages, r, -1 if workspace_bytes is None else workspace_bytes, window, sinks,
+                                          C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+ROPE_NONE, ROPE_LINEAR, ROPE_LLAMA3, ROPE_YARN = 0, 1, 2, 3
+ROPE_KINDS = {"none": ROPE_NONE, "linear": ROPE_LINEAR, "llama3": ROPE_LLAMA3, "yarn": ROPE_YARN}
+
+
+class RopeScaling(C.Structure):
+    """llmie_rope_scaling of include/llmie.h"""
+    _fields_ = [("kind", _i), ("factor", _f), ("original_max_pos", _i), ("low_freq_factor", _f), ("high_freq_factor", _f),
+                ("beta_fast", _f), ("beta_slow", _f), ("attn_factor", _f), ("truncate", _i)]
+
+
+def rope_scaling(scaling):
+    """None, a RopeScaling, or a dict of its fields (kind: a name of ROPE_KINDS or its number) -> RopeScaling or None"""
+    if scaling is None or isinstance(scaling, RopeScaling):
+        return scaling
+    d = dict(scaling)
+    kind = d.pop("kind")
+    s = RopeScaling(kind=ROPE_KINDS[kind] if isinstance(kind, str) else int(kind))
+    for k, v in d.items():
+        if k not in dict(RopeScaling._fields_):
+            raise LlmieError("rope_scaling: unknown field %r" % k)
+        setattr(s, k, v)
+    return s
+
+
+def rope_table(max_pos, head_size, rotary_dim, base, scaling=None):
+    """llmie_rope_table_fill: the (cos, sin) table as numpy float32 [max_pos, head_size // 2, 2]; scaling: see rope_scaling().  Host only."""
+    import numpy as np
+    shape = (max(int(max_pos), 0), max(int(head_size), 0) // 2, 2)
+    buf = np.empty(max(shape[0] * shape[1] * 2, 1), np.float32)   # (never NULL: the entry's own shape checks answer a bad shape)
+    sc = rope_scaling(scaling)
+    _check(lib().llmie_rope_table_fill(buf.ctypes.data, max_pos, head_size, rotary_dim, base, C.addressof(sc) if sc is not None else None),
+           "rope_table_fill")
+    return buf[:shape[0] * shape[1] * 2].reshape(shape)
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):
@@ -474,6 +533,25 @@ def decoder_mha_window(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv
                                           rotary_dim, _p(block_table), block_table.shape[1] if block_table is not None else 0,
                                           k_cache.shape[1] if block_table is not None else 0, window, sinks, _p(tickets),
                                           int(kv_scales is not None), ks, vs, _dt(qkv), _st()), "decoder_mha_window")
+    return out
+
+
+def decoder_mha_sink(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv_head_num, ctx_len, workspace, rope_table,
+                     rotary_dim, max_seq_len, head_sink, window=0, sinks=0, block_table=None, tickets=None, kv_scales=None):
+    """decoder_mha_window plus a learned sink logit per query head (llmie_decoder_mha_sink): head_sink = float32 device tensor
+    [head_num] (-inf = no sink for that head) or None = decoder_mha_window's call.  The softmax of head h runs over the visible keys and
+    one extra column with logit head_sink[h] and no value row."""
+    import torch
+    batch, hs = qkv.shape[0], qkv.shape[-1]
+    ks, vs = kv_scales if kv_scales is not None else (1.0, 1.0)
+    if head_sink is not None:
+        assert head_sink.dtype == torch.float32 and head_sink.numel() == head_num, "head_sink: float32 [head_num]"
+    _check(lib().llmie_decoder_mha_sink(_p(qkv), _p(qkv_bias), _p(k_cache), _p(v_cache), _p(out), layer, batch, head_num,
+                                        kv_head_num, hs, max_seq_len, _p(ctx_len), _p(workspace),
+                                        0 if workspace is None else workspace.numel() * workspace.element_size(), _p(rope_table),
+                                        rotary_dim, _p(block_table), block_table.shape[1] if block_table is not None else 0,
+                                        k_cache.shape[1] if block_table is not None else 0, window, sinks, _p(tickets),
+                                        int(kv_scales is not None), ks, vs, _p(head_sink), _dt(qkv), _st()), "decoder_mha_sink")
     return out
 
 
@@ -936,6 +1014,22 @@ class Decoder:
         arr = (C.c_int32 * L)(*w)
         _check(lib().llmie_decoder_set_window(self.handle, C.addressof(arr), sinks), "decoder_set_window")
 
+    def set_head_sinks(self, head_sink):
+        """learned per-head sink logits (llmie_decoder_set_head_sinks): a float32 device tensor [num_layers, head_num] (-inf = no
+        sink for that head), kept alive by this object and read on the device at every attention launch; None clears"""
+        import torch
+        if head_sink is not None:
+            if head_sink.dtype != torch.float32 or tuple(head_sink.shape) != (self.cfg.num_layers, self.cfg.head_num):
+                raise LlmieError("set_head_sinks: needs a float32 tensor [num_layers=%d, head_num=%d]" % (self.cfg.num_layers, self.cfg.head_num))
+        _check(lib().llmie_decoder_set_head_sinks(self.handle, _p(head_sink)), "decoder_set_head_sinks")
+        self._head_sinks_keep = head_sink
+
+    def set_rope_scaling(self, scaling):
+        """RoPE frequency scaling (llmie_decoder_set_rope_scaling): refills and uploads the engine's (cos, sin) table -- one synchronous
+        copy, not inside a graph capture.  scaling: see rope_scaling(); None restores the create-time table"""
+        sc = rope_scaling(scaling)
+        _check(lib().llmie_decoder_set_rope_scaling(self.handle, C.addressof(sc) if sc is not None else None), "decoder_set_rope_scaling")
+
     def moe_workspace_bytes(self, max_tokens, inter, experts, top_k):
         return lib().llmie_decoder_moe_workspace_bytes(C.byref(self.cfg), max_tokens, inter, experts, top_k)
 
@@ -1046,6 +1140,7 @@ LORA_MAX_SLOTS = 1024   # LLMIE_LORA_MAX_SLOTS
 LORA_MAX_KSPLIT = 8     # LLMIE_LORA_MAX_KSPLIT
 PLAN_LORA = 1024        # LLMIE_PLAN_LORA
 PLAN_WINDOW = 2048      # LLMIE_PLAN_WINDOW
+PLAN_HEAD_SINK = 4096   # LLMIE_PLAN_HEAD_SINK
 PLAN_PAGED, PLAN_RAGGED, PLAN_HIDDEN_MISALIGNED = 1, 2, 4   # LLMIE_PLAN_* call flags of decoder_plan_name
 
 

@@ -389,6 +389,26 @@ void launchDecoderWindowAttention(TensorWrapper<T> *qkv_buf, const T *qkv_bias, 
                                         llmie_api::st()));
 }
 
+// No reference launcher: launchDecoderWindowAttention with a learned sink logit per query head (include/llmie.h
+// llmie_decoder_mha_sink): head_sink [head_num] fp32 on the device (-INFINITY: no sink for that head), or null = that launcher's call.
+// The softmax of head h runs over the keys the mask exposes and one extra column with logit head_sink[h] and no value row.
+template <typename T>
+void launchDecoderSinkAttention(TensorWrapper<T> *qkv_buf, const T *qkv_bias, int layer, TensorWrapper<T> *k_cache, TensorWrapper<T> *v_cache,
+                                TensorWrapper<int> *ctx_len, const void *rope_table, int rotary_dim, TensorWrapper<int> *block_table,
+                                int max_seq_len, int window, int sinks, TensorWrapper<float> *head_sink, TensorWrapper<T> *mha_output) {
+    const int batch = qkv_buf->shape[0], qkv_head_num = qkv_buf->shape[1], head_size = qkv_buf->shape[2];
+    const int kv_head_num = k_cache->shape[2];
+    const int head_num = qkv_head_num - 2 * kv_head_num;
+    LLM_CHECK_WITH_INFO(!head_sink || head_sink->shape[0] == head_num, "head_sink should be [head_num]");
+    if (!block_table) max_seq_len = k_cache->shape[3];
+    const size_t ws = llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len);
+    LLMIE_CALL(llmie_decoder_mha_sink(qkv_buf->data, qkv_bias, k_cache->data, v_cache->data, mha_output->data, layer, batch, head_num,
+                                      kv_head_num, head_size, max_seq_len, ctx_len->data, llmie_api::scratch(ws), ws, rope_table, rotary_dim,
+                                      block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                      block_table ? k_cache->shape[1] : 0, window, sinks, nullptr, 0, 1.f, 1.f,
+                                      head_sink ? head_sink->data : nullptr, llmie_api::dtype_of<T>(), llmie_api::st()));
+}
+
 // No reference launcher: the page ring of windowed sequences (include/llmie.h llmie_kv_window_advance).  block_table [batch,
 // max_pages] (in / out, -1 = unmapped), cached_len [batch], new_tokens [batch] or null (one each), status [batch] (0 mapped, 1 no
 // dead page: the row is untouched, 2 past the table).  One launch, nothing read by the host.

@@ -99,7 +99,29 @@ public:
         window_dirty = true;
     }
 
+    // Learned per-head sink logits (include/llmie.h llmie_decoder_set_head_sinks): a DEVICE array [num_layers, head_num] of fp32 that
+    // the caller keeps alive (null: none), and RoPE frequency scaling (llmie_decoder_set_rope_scaling; kind LLMIE_ROPE_NONE: the
+    // create-time table); both set on every engine this holder creates
+    void set_head_sinks(const float *head_sink_dev) {
+        head_sinks = head_sink_dev;
+        sinks_dirty = true;
+    }
+    void set_rope_scaling(const llmie_rope_scaling &s) {
+        rope_scaling = s;
+        rope_dirty = true;
+    }
+
 private:
+    const float *head_sinks = nullptr;
+    bool sinks_dirty = false;
+    llmie_rope_scaling rope_scaling{};
+    bool rope_dirty = false;
+    void sync_attention() {
+        if (!engine) return;
+        if (sinks_dirty) LLMIE_CALL(llmie_decoder_set_head_sinks(engine, head_sinks));
+        if (rope_dirty) LLMIE_CALL(llmie_decoder_set_rope_scaling(engine, rope_scaling.kind == LLMIE_ROPE_NONE ? nullptr : &rope_scaling));
+        sinks_dirty = rope_dirty = false;
+    }
     std::vector<int> window;
     int window_sinks = 0;
     bool window_dirty = false;
@@ -183,6 +205,7 @@ public:
             sync_lora();
             sync_moe();
             sync_window();
+            sync_attention();
             return engine;
         }
         destroy();
@@ -226,6 +249,8 @@ public:
         sync_moe();
         window_dirty = !window.empty();
         sync_window();
+        sinks_dirty = head_sinks != nullptr, rope_dirty = rope_scaling.kind != LLMIE_ROPE_NONE;
+        sync_attention();
         return engine;
     }
     void *prefill_workspace(const llmie_decoder_config *cfg, int tokens, int batch, size_t *bytes) {
@@ -403,6 +428,8 @@ public:
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
+    void setHeadSinks(const float *head_sink_dev) { engine_holder.set_head_sinks(head_sink_dev); }
+    void setRopeScaling(const llmie_rope_scaling &s) { engine_holder.set_rope_scaling(s); }
     void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 
     // self_decoder.cpp:24-122
@@ -577,6 +604,8 @@ public:
     void setLora(const typename EngineHolder<T>::LoraBinding &b) { engine_holder.set_lora(b); }
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
+    void setHeadSinks(const float *head_sink_dev) { engine_holder.set_head_sinks(head_sink_dev); }
+    void setRopeScaling(const llmie_rope_scaling &s) { engine_holder.set_rope_scaling(s); }
     void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 
     LlamaContextDecoder(const int &head_num, const int &kv_head_num, const int &head_size, const int &intermediate_size,

@@ -302,6 +302,26 @@ public:
         context_decoder->setWindow(layer_window, layer_window.empty() ? 0 : sinks);
         self_decoder->setWindow(layer_window, layer_window.empty() ? 0 : sinks);
     }
+    // Learned per-head sink logits (gpt-oss `self_attn.sinks`; include/llmie.h llmie_decoder_set_head_sinks): head_sink_dev is a DEVICE
+    // array [num_layers, head_num] of fp32 (a loader converts the stored bf16 values) that must stay alive while it is set; nullptr
+    // clears.  Takes effect from the next prefill / decode call of both decoders; the per-kernel loops know no sink column.
+    void setAttentionSinks(const float *head_sink_dev) {
+        LLM_CHECK_WITH_INFO(!head_sink_dev || ((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs)),
+                            "setAttentionSinks: head sinks need the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        context_decoder->setHeadSinks(head_sink_dev);
+        self_decoder->setHeadSinks(head_sink_dev);
+    }
+    // RoPE frequency scaling (`rope_scaling` of a config.json; include/llmie.h llmie_rope_scaling): both decoders' engines refill their
+    // (cos, sin) table; kind LLMIE_ROPE_NONE goes back to the unscaled table.  One synchronous copy per engine, at its next call.
+    void setRopeScaling(const llmie_rope_scaling &scaling) {
+        LLM_CHECK_WITH_INFO(scaling.kind == LLMIE_ROPE_NONE || ((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs)),
+                            "setRopeScaling: a scaled table needs the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        std::vector<float> probe(static_cast<size_t>(head_size));   // the struct's own checks, before an engine meets it
+        LLM_CHECK_WITH_INFO(llmie_rope_table_fill(probe.data(), 1, head_size, head_size, 10000.f, scaling.kind == LLMIE_ROPE_NONE ? nullptr : &scaling) == LLMIE_OK,
+                            std::string(llmie_last_error()));
+        context_decoder->setRopeScaling(scaling);
+        self_decoder->setRopeScaling(scaling);
+    }
     // the last step of the SamplingConfig path: the top_logprobs most likely tokens of the raw row (id -1 / -INFINITY past the
     // row's valid tokens) and the picked token's raw log-probability
     const std::vector<int> &lastTopIds() const { return last_top_ids; }

@@ -191,12 +191,35 @@ __device__ __forceinline__ float merge_splits(const float *__restrict__ p, int n
     }
     return o / (L + 1e-6f);
 }
+// Learned per-head sink logit (include/llmie.h): one more partial (m = s, l = 1, o = 0) merged LAST into the merged state (M, L, o) of
+// a (sequence, head), at every place that normalises -- so it enters once per row whatever the number of splits or waves.  s = -inf:
+// the maximum stays M, exp(M - M) = 1 and fma(0, 1, L) = L, i.e. the bits of o / (L + 1e-6) without a sink.
+__device__ __forceinline__ float sink_finish(float M, float L, float o, float s) {
+    const float Mc = fmaxf(M, s);
+    const float rescale = (M == -INFINITY) ? 0.f : __expf(M - Mc);
+    L *= rescale;
+    o *= rescale;
+    const float f = (s == -INFINITY) ? 0.f : __expf(s - Mc);
+    L = fmaf(f, 1.f, L);
+    return o / (L + 1e-6f);
+}
+// merge_splits, then the sink: the same rounds in the same order, so the ticket merge and the combine kernel agree bit for bit
+__device__ __forceinline__ float merge_splits_sink(const float *__restrict__ p, int nsplits, size_t stride, int d, float s) {
+    float M = -INFINITY, L = 0.f, o = 0.f;
+    for (int s0 = 0; s0 < nsplits; s0 += 16) {
+        float ms[16], ls[16], os[16];
+        merge_load(p, s0, nsplits - 1, stride, d, ms, ls, os);
+        merge_round(ms, ls, os, s0, nsplits, M, L, o);
+    }
+    return sink_finish(M, L, o, s);
+}
 
 // WIN (compile time) selects the sliding-window form: the workgroup's chunk comes from the live-chunk mapping, a row is masked from
 // below as well as from above, and no load goes through the block-table entry of a page without a live row.  Its two launch
 // arguments (window, sinks) are the pack WinArgs = (int, int); WIN = false has an empty pack: the arguments and the code the kernel
-// had before there was a window.
-template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T, bool WIN = false, typename... WinArgs>
+// had before there was a window.  SINK (compile time) adds the per-head sink logit: one more argument at the end of the pack, the
+// device array head_sink[head_num] (fp32), read where an output row is normalised (sink_finish); the streaming loop does not know it.
+template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T, bool WIN = false, bool SINK = false, typename... WinArgs>
 __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const T *__restrict__ qkv, const T *__restrict__ qkv_bias, KT *k_cache, KT *v_cache,
     float *__restrict__ part, T *__restrict__ out, int head_num, int kv_head_num, int max_seq_len,
@@ -208,8 +231,9 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const PagedKv pg /* pg.table != null: k_cache / v_cache are this layer's page pools */,
     const int cpw /* chunks of CHUNK tokens one workgroup walks through (online softmax across them): large batches amortise
                      the per-workgroup prologue / merge (~550 of ~1000 VALU instructions per wave at one chunk) */,
-    const WinArgs... win /* WIN: window, sinks -- the query sees key j iff j >= step - window or j < sinks (and j < step) */) {
-    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
+    const WinArgs... win /* WIN: window, sinks -- the query sees key j iff j >= step - window or j < sinks (and j < step);
+                            SINK: then const float *head_sink */) {
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0), "window, sinks, head_sink");
     using G = AttnGeom<KT, HS, kAttnWaves, kAttnG>;
     using V = typename CacheVec<KT>::type;  // one 16-byte vector of cache elements
     constexpr int N = G::N, LPT = G::LPT, TPW = G::TPW, CHUNK = G::CHUNK;
@@ -223,8 +247,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     // WIN: blockIdx.x counts the sequence's LIVE spans; t_lo = first token of the window, s_eff = its sink tokens
     int t0w = split * span, nsw = 0, t_lo = 0, s_eff = 0;
     if constexpr (WIN) {
-        const int wa[2] = {win...};
-        const int window = wa[0], sinks = wa[1];
+        const int window = pack_arg<0>(win...), sinks = pack_arg<1>(win...);
         const AttnLive lv = attn_live_chunks(step, window, sinks, span);
         if (split >= lv.total) return;   // (also: invalid position, total = 0)
         t0w = attn_live_chunk(lv, split) * span;
@@ -244,6 +267,9 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     auto row_live = [&](int t) { return t < t_end && (!WIN || t >= t_lo || t < s_eff); };
     auto chunk_live = [&](int tc) { return tc < s_eff || tc + CHUNK > t_lo; };
     const int batch = gridDim.z;
+    const float *head_sink = nullptr;
+    if constexpr (SINK) head_sink = pack_arg<WIN ? 2 : 0>(win...);
+    (void)head_sink;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPT, dl = lane % LPT;
@@ -646,7 +672,8 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
         }
         const int h = g * REP + r;
         if (nsplits == 1) {
-            out[attn_out_index(pg.out_x32, b, h * HS + d, head_num * HS)] = from_f32<T>(o / (L + 1e-6f));
+            if constexpr (SINK) out[attn_out_index(pg.out_x32, b, h * HS + d, head_num * HS)] = from_f32<T>(sink_finish(M, L, o, head_sink[h]));
+            else out[attn_out_index(pg.out_x32, b, h * HS + d, head_num * HS)] = from_f32<T>(o / (L + 1e-6f));
         } else {
             float *p = part + ((static_cast<size_t>(b) * head_num + h) * max_splits + split) * (HS + 2);
             p[2 + d] = o;
@@ -684,7 +711,9 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
                 const int r = i / HS, d = i - r * HS;
                 const int h = g * REP + r;
                 const float *p = part + (static_cast<size_t>(b) * head_num + h) * max_splits * stride;
-                const float v = merge_splits(p, nsplits, stride, d);
+                float v;
+                if constexpr (SINK) v = merge_splits_sink(p, nsplits, stride, d, head_sink[h]);
+                else v = merge_splits(p, nsplits, stride, d);
                 out[attn_out_index(pg.out_x32, b, h * HS + d, head_num * HS)] = from_f32<T>(v);
             }
         }
@@ -694,16 +723,20 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
 // merge the per-split partials: grid (head_num, batch), one thread per output dim.  Every thread reads the
 // (m, l) pairs itself (broadcast loads) and its own o values, 16 splits per round with all loads issued before
 // the first use, so the kernel is about one L2 round trip per 16 splits -- no LDS, no barrier.
-// WIN: the partial slots are the live chunks of the window (attn_live_chunks), as the split kernel filled them.
-template <typename T, bool WIN = false, typename... WinArgs>
+// WIN: the partial slots are the live chunks of the window (attn_live_chunks), as the split kernel filled them.  SINK: the head-sink
+// array ends the pack; the sink of head h enters after the last round (sink_finish).
+template <typename T, bool WIN = false, bool SINK = false, typename... WinArgs>
 __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float *__restrict__ part,
                                                                   T *__restrict__ out, int head_num,
                                                                   int head_size, int chunk, int step_arg,
                                                                   const int32_t *__restrict__ step_dev,
                                                                   int max_splits, int step_stride, int max_seq_len, int out_x32,
-                                                                  const WinArgs... win /* WIN: window, sinks */) {
-    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
+                                                                  const WinArgs... win /* WIN: window, sinks; SINK: head_sink */) {
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0), "window, sinks, head_sink");
     const int h = blockIdx.x, b = blockIdx.y;
+    float sink = -INFINITY;
+    if constexpr (SINK) sink = pack_arg<WIN ? 2 : 0>(win...)[h];   // beside the first round's loads
+    (void)sink;
     const size_t stride = static_cast<size_t>(head_size) + 2;
     const float *p = part + (static_cast<size_t>(b) * head_num + h) * max_splits * stride;
     // The first round's loads do not wait for the device-resident position: they go out beside its load, clamped to the buffer
@@ -715,8 +748,7 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float *_
     const int step = seq_step(step_dev, step_arg, step_stride, b, max_seq_len);
     int nsplits = (step + chunk - 1) / chunk;
     if constexpr (WIN) {
-        const int wa[2] = {win...};
-        nsplits = attn_live_chunks(step, wa[0], wa[1], chunk).total;
+        nsplits = attn_live_chunks(step, pack_arg<0>(win...), pack_arg<1>(win...), chunk).total;
     }
     if (nsplits <= 1) return;  // the split kernel already wrote the final output (or: invalid position)
     if (d < head_size) {
@@ -726,10 +758,13 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float *_
             merge_load(p, s0, nsplits - 1, stride, d, ms, ls, os);
             merge_round(ms, ls, os, s0, nsplits, M, L, o);
         }
-        out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(o / (L + 1e-6f));
+        if constexpr (SINK) out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(sink_finish(M, L, o, sink));
+        else out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(o / (L + 1e-6f));
     }
-    for (d += blockDim.x; d < head_size; d += blockDim.x)   // head sizes above the block size
-        out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(merge_splits(p, nsplits, stride, d));
+    for (d += blockDim.x; d < head_size; d += blockDim.x) {   // head sizes above the block size
+        if constexpr (SINK) out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(merge_splits_sink(p, nsplits, stride, d, sink));
+        else out[attn_out_index(out_x32, b, h * head_size + d, head_num * head_size)] = from_f32<T>(merge_splits(p, nsplits, stride, d));
+    }
 }
 
 // Any head size / GQA ratio (e.g. the reference unit test's hs=4): one workgroup per (b, q-head),
@@ -832,6 +867,7 @@ static DecodeAttnPlan plan_attn_split(const DecodeAttnCall &c, size_t need) {
         p.window = c.window, p.sinks = c.sinks;
         p.grid[0] = c.step_dev ? attn_live_bound(c.max_seq_len, c.window, c.sinks, p.chunk) : attn_live_chunks(c.step, c.window, c.sinks, p.chunk).total;
     }
+    p.head_sink = c.head_sink;
     p.max_splits_ws = (c.max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
     p.merge = p.grid[0] > 1 && !c.tickets;
     p.merge_grid[0] = c.head_num, p.merge_grid[1] = c.batch;
@@ -852,6 +888,8 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
     const bool ws_ok = c.workspace && c.workspace_bytes >= need;
     // a window runs on the split kernel's windowed instantiations only: fp16 activations, head size 64 / 128 (ratios as below)
     if (c.window > 0 && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128))) return attn_refusal(DAREF_WINDOW);
+    // ... and so does a head sink: the SINK instantiations exist where the windowed ones do
+    if (c.head_sink && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128))) return attn_refusal(DAREF_HEAD_SINK);
     if (c.kv_e4m3) {
         // fp16 activations over e4m3 cache bytes: 16 cache elements per 16-byte load (8 lanes per token row at head size 128,
         // 256-token chunks); head ratio 8 does not fit registers (16 dims per lane x 8 heads); no generic form, and one refusal
@@ -868,6 +906,7 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
     if (aligned && c.batch <= 65535 && c.kv_head_num <= 65535 && geometry)
         return ws_ok ? plan_attn_split(c, need) : attn_refusal(DAREF_WORKSPACE, need);
     if (c.window > 0) return attn_refusal(DAREF_WINDOW);   // the generic kernel attends to everything
+    if (c.head_sink) return attn_refusal(DAREF_HEAD_SINK);   // ... and normalises over the real keys only
     if (c.paged) return attn_refusal(DAREF_PAGED_GEOMETRY);
     if (c.slabs) return attn_refusal(DAREF_SLABS_GEOMETRY);
     // (tickets on a supported geometry that fell through -- unaligned -- are ignored: the generic kernel has no partials)
@@ -903,6 +942,10 @@ int decode_attn_refuse(const DecodeAttnCall &c, const DecodeAttnPlan &p) {
             set_error("decoder_mha: a sliding window needs fp16 activations, head_size 64/128, head_num/kv_head_num in {1,2,4,8} (e4m3 cache: "
                       "{1,2,4}) and 16-byte aligned buffers (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
             break;
+        case DAREF_HEAD_SINK:
+            set_error("decoder_mha: a head sink needs fp16 activations, head_size 64/128, head_num/kv_head_num in {1,2,4,8} (e4m3 cache: "
+                      "{1,2,4}) and 16-byte aligned buffers (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
+            break;
         case DAREF_GENERIC_SPAN:
             set_error("decoder_mha: generic path supports at most 15360 tokens (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
             break;
@@ -924,18 +967,35 @@ struct DecodeAttnArgs {
     QkvSlabs qs;
     KvScale ks;
     PagedKv pg;
+    const float *head_sink;   // [head_num] fp32 of this layer, or null
 };
 
 template <typename T, int HS, int REP, typename KT> static void launch_split(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
     // the windowed instantiations: fp16 activations, head size 64 / 128 (what plan_decode_attn plans with a window)
     if constexpr (std::is_same<T, half_t>::value && (HS == 64 || HS == 128)) {
+        if (p.head_sink) {   // the SINK instantiations, windowed or not: the same launches with the head-sink array as last argument
+            auto run = [&](auto win_c, auto... ex) {
+                constexpr bool W = decltype(win_c)::value;
+                decode_attn_split_kernel<T, HS, REP, 4, 8, KT, W, true, decltype(ex)...><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+                    static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
+                    static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
+                    a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, ex...);
+                if (p.merge)
+                    decode_attn_combine_kernel<T, W, true, decltype(ex)...><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
+                        a.part, static_cast<T *>(a.out), a.head_num, HS, p.chunk, a.step, a.step_dev, p.max_splits_ws, a.pg.step_stride,
+                        a.max_seq_len, a.pg.out_x32, ex...);
+            };
+            if (p.window > 0) run(std::true_type{}, p.window, p.sinks, a.head_sink);
+            else run(std::false_type{}, a.head_sink);
+            return;
+        }
         if (p.window > 0) {
-            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, true, int, int><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, true, false, int, int><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
                 static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
                 static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
                 a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, p.window, p.sinks);
             if (p.merge)
-                decode_attn_combine_kernel<T, true, int, int><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
+                decode_attn_combine_kernel<T, true, false, int, int><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
                     a.part, static_cast<T *>(a.out), a.head_num, HS, p.chunk, a.step, a.step_dev, p.max_splits_ws, a.pg.step_stride,
                     a.max_seq_len, a.pg.out_x32, p.window, p.sinks);
             return;
@@ -1001,7 +1061,7 @@ static DecodeAttnArgs decode_attn_args(const DecodeAttnShape &g, const DecodeAtt
     return DecodeAttnArgs{io.qkv, io.qkv_bias, static_cast<char *>(kv.k) + layer_bytes, static_cast<char *>(kv.v) + layer_bytes, io.out,
                           static_cast<float *>(io.workspace), g.head_num, g.kv_head_num, g.head_size, g.max_seq_len, pos.step, pos.step_dev,
                           io.rope, io.rot_dim, io.tickets, qs, KvScale{kv.k_scale, kv.v_scale},
-                          PagedKv{kv.block_table, kv.max_pages, pos.ragged ? 1 : 0, io.out_x32 ? 1 : 0}};
+                          PagedKv{kv.block_table, kv.max_pages, pos.ragged ? 1 : 0, io.out_x32 ? 1 : 0}, io.head_sink};
 }
 static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos,
                                        const DecodeAttnArgs &a) {
@@ -1018,6 +1078,7 @@ static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAtt
     }
     c.workspace = io.workspace != nullptr, c.workspace_bytes = io.workspace_bytes;
     c.window = io.window > 0 ? io.window : 0, c.sinks = io.window > 0 ? io.sinks : 0;
+    c.head_sink = io.head_sink != nullptr;
     return c;
 }
 
@@ -1067,7 +1128,9 @@ static void decode_attn_plan_text(const DecodeAttnCall &c, const DecodeAttnPlan 
     else m = snprintf(text + k, n - k, "%s", p.grid[0] > 1 ? "in-launch" : "none");
     // a windowed call (no window: the line above, unchanged): the mask and what grid x counts -- the live spans of the host step, or
     // their bound for any position
-    if (p.window > 0) snprintf(text + k + m, n - k - m, " window %d sinks %d live %s%d", p.window, p.sinks, c.step_dev ? "<=" : "", p.grid[0]);
+    int w = 0;
+    if (p.window > 0) w = snprintf(text + k + m, n - k - m, " window %d sinks %d live %s%d", p.window, p.sinks, c.step_dev ? "<=" : "", p.grid[0]);
+    if (p.head_sink) snprintf(text + k + m + w, n - k - m - w, " head_sink");   // the SINK instantiation of the same launches
 }
 
 // The page ring of a windowed sequence (llmie_kv_window_advance): one thread per sequence.  The logical pages the positions
@@ -1176,6 +1239,7 @@ static const char *decode_attn_plan_query(const char *who, llmie_dtype dtype, in
         if (c.slabs) c.mis_slab = res(4), c.mis_wf = res(5), c.mis_wh8 = res(6) % 8, c.slab_stride_mod4 = res(7) % 4;
         c.workspace = workspace_bytes >= 0, c.workspace_bytes = c.workspace ? static_cast<size_t>(workspace_bytes) : 0;
         c.window = window, c.sinks = window > 0 ? sinks : 0;
+        c.head_sink = (forms & LLMIE_ATTN_HEAD_SINK) != 0;
         const DecodeAttnPlan p = plan_decode_attn(c);
         if (p.kind == DA_REFUSED) rc = decode_attn_refuse(c, p);
         else decode_attn_plan_text(c, p, text, sizeof(text));
@@ -1187,7 +1251,8 @@ static const char *decode_attn_plan_query(const char *who, llmie_dtype dtype, in
 extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
                                               int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
                                               unsigned long long residues, long long workspace_bytes, int *status) {
-    return decode_attn_plan_query("decoder_mha_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step, forms,
+    return decode_attn_plan_query("decoder_mha_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
+                                  forms & ~LLMIE_ATTN_HEAD_SINK,
                                   max_pages, num_pages, residues, workspace_bytes, 0, 0, status);
 }
 
@@ -1196,7 +1261,7 @@ extern "C" const char *llmie_decoder_mha_window_plan(llmie_dtype dtype, int kv_e
                                                      unsigned long long residues, long long workspace_bytes, int window, int sinks,
                                                      int *status) {
     return decode_attn_plan_query("decoder_mha_window_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                  forms, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
+                                  forms & ~LLMIE_ATTN_HEAD_SINK, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
 }
 
 // Sliding-window decode attention on the operands of llmie_decoder_mha_ragged (+ tickets and the e4m3 cache, which the engine's calls
@@ -1215,6 +1280,32 @@ extern "C" int llmie_decoder_mha_window(const void *qkv, const void *qkv_bias, v
                              KvView{k_cache, v_cache, block_table, max_pages, num_pages, kv_e4m3 ? 1 : 0, kv_e4m3 ? k_scale : 1.f,
                                     kv_e4m3 ? v_scale : 1.f},
                              DecodePos{-1, ctx_len_dev, 1}, layer, stream);
+}
+
+// llmie_decoder_mha_window plus the learned per-head sink logit (head_sink: device fp32 [head_num], nullable = that entry's call)
+extern "C" int llmie_decoder_mha_sink(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer, int batch,
+                                      int head_num, int kv_head_num, int head_size, int max_seq_len, const int32_t *ctx_len_dev,
+                                      void *workspace, size_t workspace_bytes, const void *rope_table, int rotary_dim,
+                                      const int32_t *block_table, int max_pages, int num_pages, int window, int sinks, int32_t *tickets,
+                                      int kv_e4m3, float k_scale, float v_scale, const float *head_sink, llmie_dtype dtype,
+                                      llmie_stream stream) {
+    const int rc = decode_attn_validate_window("decoder_mha_sink", window, sinks);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(head_sink) % sizeof(float) == 0, "decoder_mha_sink: head_sink must be 4-byte aligned");
+    return decode_attn_entry("decoder_mha_sink", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim,
+                                          tickets, nullptr, nullptr, 0, window, sinks, head_sink},
+                             KvView{k_cache, v_cache, block_table, max_pages, num_pages, kv_e4m3 ? 1 : 0, kv_e4m3 ? k_scale : 1.f,
+                                    kv_e4m3 ? v_scale : 1.f},
+                             DecodePos{-1, ctx_len_dev, 1}, layer, stream);
+}
+
+extern "C" const char *llmie_decoder_mha_sink_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                                   int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                                   unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                                   int *status) {
+    return decode_attn_plan_query("decoder_mha_sink_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
+                                  forms, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
 }
 
 extern "C" int llmie_kv_window_advance(int32_t *block_table, int max_pages, const int32_t *cached_len, const int32_t *new_tokens, int batch,

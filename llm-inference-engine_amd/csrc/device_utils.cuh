@@ -272,4 +272,10 @@ __device__ __forceinline__ half8_t mx4_expand(unsigned w) {
 // 2^(byte - 127) as fp32 (byte 0: the subnormal 2^-127; byte 0xFF, NaN in e8m0, comes out as +inf: unspecified results)
 __device__ __forceinline__ float mx4_scale(unsigned byte) { return __builtin_bit_cast(float, byte ? byte << 23 : 0x00400000u); }
 
+// argument I of a kernel's trailing parameter pack (the attention kernels -- WIN: window, sinks; SINK: the head-sink array, last)
+template <int I, typename A, typename... R> __host__ __device__ __forceinline__ auto pack_arg(A a, R... r) {
+    if constexpr (I == 0) return a;
+    else return pack_arg<I - 1>(r...);
+}
+
 }  // namespace llmie

@@ -76,6 +76,10 @@ struct llmie_decoder {
     std::vector<int> layer_window;
     int sinks = 0;
     int window_of(int layer) const { return layer_window.empty() ? 0 : layer_window[layer]; }
+    // learned per-head sink logits (llmie_decoder_set_head_sinks): the caller's device array [num_layers, head_num] of fp32, or null;
+    // read where a call's attention launches are planned, like the window
+    const float *head_sinks = nullptr;
+    const float *head_sink_of(int layer) const { return head_sinks ? head_sinks + static_cast<size_t>(layer) * cfg.head_num : nullptr; }
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -343,6 +347,92 @@ extern "C" size_t llmie_decoder_resident_weight_bytes(const llmie_decoder_config
     return per_layer * cfg->num_layers;
 }
 
+// The one function that computes a (cos, sin) table (include/llmie.h): host only.  NONE / NULL is the fp32 formula the engine has always
+// used, bit for bit; the scaled kinds are evaluated in double and rounded once.
+extern "C" int llmie_rope_table_fill(float *cos_sin_out, int max_pos, int head_size, int rotary_dim, float rotary_base,
+                                     const llmie_rope_scaling *sc) {
+    LLMIE_REQUIRE(cos_sin_out, "rope_table_fill: NULL output");
+    LLMIE_REQUIRE(max_pos >= 1 && head_size >= 2, "rope_table_fill: bad shape (max_pos %d, head_size %d)", max_pos, head_size);
+    LLMIE_REQUIRE(rotary_dim >= 2 && rotary_dim % 2 == 0, "rope_table_fill: rotary_dim %d must be even and positive", rotary_dim);
+    const int kind = sc ? static_cast<int>(sc->kind) : static_cast<int>(LLMIE_ROPE_NONE);
+    LLMIE_REQUIRE(kind >= LLMIE_ROPE_NONE && kind <= LLMIE_ROPE_YARN, "rope_table_fill: unknown scaling kind %d", kind);
+    // (NONE keeps what llmie_decoder_create has always accepted: a rotary_dim above the head size stops at head_size / 2 pairs)
+    LLMIE_REQUIRE(kind == LLMIE_ROPE_NONE || (rotary_dim <= head_size && head_size % 2 == 0),
+                  "rope_table_fill: a scaled table needs an even head_size and rotary_dim <= head_size (%d, %d)", head_size, rotary_dim);
+    LLMIE_REQUIRE(kind == LLMIE_ROPE_NONE || rotary_base > 0.f, "rope_table_fill: rotary_base must be positive");
+    const int half = head_size / 2, rot = rotary_dim / 2;
+    if (kind == LLMIE_ROPE_NONE) {
+        for (int pos = 0; pos < max_pos; ++pos)
+            for (int j = 0; j < half; ++j) {
+                float c = 1.f, s = 0.f;
+                if (j < rot) {
+                    const float ang = static_cast<float>(pos) / powf(rotary_base, static_cast<float>(2 * j) / static_cast<float>(rotary_dim));
+                    c = cosf(ang), s = sinf(ang);
+                }
+                cos_sin_out[2 * (static_cast<size_t>(pos) * half + j)] = c;
+                cos_sin_out[2 * (static_cast<size_t>(pos) * half + j) + 1] = s;
+            }
+        return LLMIE_OK;
+    }
+    const double factor = sc->factor, orig = sc->original_max_pos, base = rotary_base, two_pi = 6.283185307179586476925286766559;
+    LLMIE_REQUIRE(std::isfinite(sc->factor) && sc->factor >= 1.f, "rope_table_fill: factor %g must be >= 1", factor);
+    if (kind != LLMIE_ROPE_LINEAR) LLMIE_REQUIRE(sc->original_max_pos >= 1, "rope_table_fill: original_max_pos %d must be positive", sc->original_max_pos);
+    double attn = 1.0, lo = 0.0, hi = 0.0;
+    if (kind == LLMIE_ROPE_LLAMA3)
+        LLMIE_REQUIRE(sc->low_freq_factor > 0.f && sc->high_freq_factor > sc->low_freq_factor,
+                      "rope_table_fill: needs 0 < low_freq_factor < high_freq_factor (%g, %g)", (double)sc->low_freq_factor, (double)sc->high_freq_factor);
+    if (kind == LLMIE_ROPE_YARN) {
+        LLMIE_REQUIRE(sc->beta_fast >= 0.f && sc->beta_slow >= 0.f, "rope_table_fill: a beta must not be negative");
+        const double bf = sc->beta_fast > 0.f ? sc->beta_fast : 32.0, bs = sc->beta_slow > 0.f ? sc->beta_slow : 1.0;
+        auto corr = [&](double n) { return rotary_dim * std::log(orig / (two_pi * n)) / (2.0 * std::log(base)); };
+        lo = corr(bf), hi = corr(bs);
+        if (sc->truncate) lo = std::floor(lo), hi = std::ceil(hi);
+        lo = std::max(lo, 0.0), hi = std::min(hi, static_cast<double>(rotary_dim - 1));
+        if (lo == hi) hi += 0.001;
+        attn = sc->attn_factor > 0.f ? static_cast<double>(sc->attn_factor) : 0.1 * std::log(factor) + 1.0;
+    }
+    std::vector<double> freq(rot);
+    for (int j = 0; j < rot; ++j) {
+        const double f = std::pow(base, -2.0 * j / rotary_dim);
+        double g = f / factor;
+        if (kind == LLMIE_ROPE_LLAMA3) {
+            const double w = two_pi / f, lf = sc->low_freq_factor, hf = sc->high_freq_factor;
+            if (w < orig / hf) g = f;
+            else if (!(w > orig / lf)) {
+                const double t = (orig / w - lf) / (hf - lf);
+                g = (1.0 - t) * f / factor + t * f;
+            }
+        } else if (kind == LLMIE_ROPE_YARN) {
+            const double ramp = std::min(1.0, std::max(0.0, (j - lo) / (hi - lo)));
+            g = f / factor * ramp + f * (1.0 - ramp);
+        }
+        freq[j] = g;
+    }
+    for (int pos = 0; pos < max_pos; ++pos)
+        for (int j = 0; j < half; ++j) {
+            float c = 1.f, s = 0.f;
+            if (j < rot) {
+                const double ang = pos * freq[j];
+                c = static_cast<float>(std::cos(ang) * attn), s = static_cast<float>(std::sin(ang) * attn);
+            }
+            cos_sin_out[2 * (static_cast<size_t>(pos) * half + j)] = c;
+            cos_sin_out[2 * (static_cast<size_t>(pos) * half + j) + 1] = s;
+        }
+    return LLMIE_OK;
+}
+// fills the engine's table on the host and uploads it with one synchronous copy
+static int rope_table_upload(llmie_decoder *d, const llmie_rope_scaling *sc, const char *who) {
+    const llmie_decoder_config &c = d->cfg;
+    std::vector<float> tab(static_cast<size_t>(c.max_seq_len) * (c.head_size / 2) * 2);
+    const int rc = llmie_rope_table_fill(tab.data(), c.max_seq_len, c.head_size, c.rotary_dim, c.rotary_base, sc);
+    if (rc != LLMIE_OK) return rc;
+    if (hipMemcpy(d->rope_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: RoPE table upload failed", who);
+        return LLMIE_ERR_LAUNCH;
+    }
+    return LLMIE_OK;
+}
+
 extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, const llmie_layer_weights *layers,
                                                void *workspace, size_t workspace_bytes) {
     if (!config_ok(cfg)) {
@@ -443,25 +533,11 @@ extern "C" llmie_decoder *llmie_decoder_create(const llmie_decoder_config *cfg, 
             for (llmie_layer_weights &w : d->layers) w.qkv.data = w.o.data = w.gate_up.data = w.down.data = nullptr;
         }
     }
-    {
-        // cos/sin of angle = pos / base^(2j/rot_dim) (rope_utils.cuh:6-19), evaluated on the host in fp32 with libm --
-        // one synchronous upload at create time (the only host<->device copy the engine ever does)
-        const int half = cfg->head_size / 2;
-        std::vector<float2> tab(static_cast<size_t>(cfg->max_seq_len) * half);
-        for (int pos = 0; pos < cfg->max_seq_len; ++pos)
-            for (int j = 0; j < half; ++j) {
-                float2 v{1.f, 0.f};
-                if (j < cfg->rotary_dim / 2) {
-                    const float ang = static_cast<float>(pos) / powf(cfg->rotary_base, static_cast<float>(2 * j) / static_cast<float>(cfg->rotary_dim));
-                    v = float2{cosf(ang), sinf(ang)};
-                }
-                tab[static_cast<size_t>(pos) * half + j] = v;
-            }
-        if (hipMemcpy(d->rope_table, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("decoder_create: RoPE table upload failed");
-            delete d;
-            return nullptr;
-        }
+    // cos/sin of angle = pos / base^(2j/rot_dim) (rope_utils.cuh:6-19), evaluated on the host in fp32 with libm -- one synchronous
+    // upload at create time (llmie_decoder_set_rope_scaling is the only other host<->device copy the engine ever does)
+    if (rope_table_upload(d, nullptr, "decoder_create") != LLMIE_OK) {
+        delete d;
+        return nullptr;
     }
     return d;
 }
@@ -641,6 +717,8 @@ static const char *const kMoeRefusal =
 static const char *const kMoeLoraRefusal = "an adapter table and experts cannot be attached to one engine at the same time";
 static const char *const kWindowRefusal =
     "a sliding window needs an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
+static const char *const kHeadSinkRefusal =
+    "head sinks need an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
 static const char *const kLoraRefusal =
     "adapters need an fp16 engine with fp16 / int8 / int4 weights (an fp8-weight engine never materialises fp16 normalised rows, a "
     "LLMIE_DEC_PACKED_ONLY engine has no row-major route), hidden and inter sizes that are multiples of 32 and q / kv widths that are "
@@ -920,6 +998,10 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
         set_error("decoder_plan_name: %s", kWindowRefusal);
         return nullptr;
     }
+    if ((call_flags & LLMIE_PLAN_HEAD_SINK) && !window_engine_ok(*cfg)) {
+        set_error("decoder_plan_name: %s", kHeadSinkRefusal);
+        return nullptr;
+    }
     if (prefill) {
         if (rows < 1) {
             set_error("decoder_plan_name: %d tokens", rows);
@@ -969,7 +1051,8 @@ struct DecodeStep {
                   const SlabScale *qkv_scale = nullptr, int out_x32 = 0, bool rope = true) const {
         return decoder_mha_rope(DecodeAttnShape{batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, dt},
                                 DecodeAttnIo{qkv, qkv_bias, out, dec->attn_ws, dec->attn_ws_bytes, rope ? dec->rope_table : nullptr,
-                                             rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32, dec->window_of(layer), dec->sinks},
+                                             rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32, dec->window_of(layer), dec->sinks,
+                                             dec->head_sink_of(layer)},
                                 kv, pos, layer, st);
     }
 
@@ -1493,8 +1576,9 @@ struct PrefillPass {
     int attention(int l, const llmie_matrix &wqkv, const PrefillLayerPlan &lp) const {
         PrefillAttnPlan ap = lp.attn;   // (the layer plan is per pass; the window is per layer)
         ap.window = dec->window_of(l), ap.sinks = ap.window > 0 ? dec->sinks : 0;
+        ap.head_sink = dec->head_sinks != nullptr;
         return prefill_attention_f16(ap, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
-                                     c.max_seq_len, c.rotary_dim, st);
+                                     c.max_seq_len, c.rotary_dim, st, dec->head_sink_of(l));
     }
     // act = swiglu(x . Wgu^T) of the lean and general sequences (ffn.cpp:105-122)
     int gate_up(const half_t *x, const llmie_matrix &w, int form) const {
@@ -1900,6 +1984,24 @@ extern "C" int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer
     return LLMIE_OK;
 }
 
+// Learned per-head sink logits: the caller's device array, kept on the engine and read where a call's attention launches are planned
+extern "C" int llmie_decoder_set_head_sinks(llmie_decoder *dec, const float *head_sink_dev) {
+    LLMIE_REQUIRE(dec, "decoder_set_head_sinks: NULL decoder");
+    if (head_sink_dev && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kHeadSinkRefusal);
+    LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(head_sink_dev) % sizeof(float) == 0, "decoder_set_head_sinks: the array must be 4-byte aligned");
+    dec->head_sinks = head_sink_dev;
+    return LLMIE_OK;
+}
+
+// RoPE frequency scaling: refill the table on the host, one synchronous upload (not inside a capture)
+extern "C" int llmie_decoder_set_rope_scaling(llmie_decoder *dec, const llmie_rope_scaling *scaling) {
+    LLMIE_REQUIRE(dec, "decoder_set_rope_scaling: NULL decoder");
+    if (!fused_attention_geometry(dec->cfg))
+        LLMIE_UNSUPPORTED("decoder_set_rope_scaling: this engine's decode attention rotates by rotary_base, not by the table (needs head_size in "
+                          "{32,64,128,256} and head_num/kv_head_num in {1,2,4,8})");
+    return rope_table_upload(dec, scaling, "decoder_set_rope_scaling");
+}
+
 extern "C" int llmie_decoder_lora_detach(llmie_decoder *dec) {
     LLMIE_REQUIRE(dec, "decoder_lora_detach: NULL decoder");
     dec->lora = llmie_decoder::Lora{};
@@ -1917,6 +2019,7 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
             LLMIE_UNSUPPORTED("%s", packed_only_refusal(cfg));
         if (int bad = prefill_shape_ok(*cfg, batch, tokens, max_q_len)) return bad;
         if ((call_flags & LLMIE_PLAN_WINDOW) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kWindowRefusal);
+        if ((call_flags & LLMIE_PLAN_HEAD_SINK) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kHeadSinkRefusal);
         const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
         const PrefillPlan plan = plan_prefill(call);
         if (plan.path == PP_REFUSED) return prefill_refuse(plan);
@@ -1942,7 +2045,9 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         for (int op = 0; op <= LLMIE_OP_DOWN_GEMM; ++op)
             if (lp.launches[op]) n += snprintf(text + n, sizeof(text) - n, " %s=%d", ops[op], lp.launches[op]);
         // (a windowed layer runs the windowed instantiation of the same flash form on the same grid)
-        if (call_flags & LLMIE_PLAN_WINDOW) snprintf(text + n, sizeof(text) - n, " attn_window=1");
+        if (call_flags & LLMIE_PLAN_WINDOW) n += snprintf(text + n, sizeof(text) - n, " attn_window=1");
+        // (... and head sinks the SINK instantiation of that form)
+        if (call_flags & LLMIE_PLAN_HEAD_SINK) snprintf(text + n, sizeof(text) - n, " attn_head_sink=1");
         return LLMIE_OK;
     }();
     if (status) *status = rc;

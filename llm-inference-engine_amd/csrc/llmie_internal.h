@@ -254,7 +254,7 @@ struct DecodePos {
 enum DecodeAttnKind : int { DA_REFUSED = 0, DA_SPLIT, DA_GENERIC };
 enum DecodeAttnRefusal : int {
     DAREF_NONE = 0, DAREF_RAGGED_LENGTHS, DAREF_X32, DAREF_PAGES, DAREF_SLAB_ALIGNMENT, DAREF_E4M3_FORM, DAREF_E4M3, DAREF_WORKSPACE,
-    DAREF_PAGED_GEOMETRY, DAREF_SLABS_GEOMETRY, DAREF_ROPE_GEOMETRY, DAREF_RAGGED_GEOMETRY, DAREF_GENERIC_SPAN, DAREF_WINDOW,
+    DAREF_PAGED_GEOMETRY, DAREF_SLABS_GEOMETRY, DAREF_ROPE_GEOMETRY, DAREF_RAGGED_GEOMETRY, DAREF_GENERIC_SPAN, DAREF_WINDOW, DAREF_HEAD_SINK,
 };
 // One decode attention call as the planner sees it: geometry, position form, which optional operands are there, how far each
 // pointer is from 16-byte alignment (address % 16 AFTER the layer offset; 0 for a null pointer), and the caller's scratch.
@@ -271,6 +271,7 @@ struct DecodeAttnCall {
     bool workspace;
     size_t workspace_bytes;
     int window, sinks;                 // sliding window (0: full attention, sinks then 0) and sink tokens
+    bool head_sink;                    // a learned sink logit per query head (device fp32 [head_num]) joins every softmax
 };
 struct DecodeAttnPlan {
     int kind, refusal;                 // DecodeAttnKind, DecodeAttnRefusal of DA_REFUSED
@@ -281,6 +282,7 @@ struct DecodeAttnPlan {
     bool e4m3;
     int cpw, chunk, grid[3], max_splits_ws;
     int window, sinks;                 // window > 0: the windowed instantiation; grid x counts live spans (attn_live_chunks)
+    bool head_sink;                    // the SINK instantiation of the same launches (same grid, slots and merge)
     bool merge;
     int merge_grid[2], merge_block;
     // DA_GENERIC: grid (heads, batch), dynamic LDS
@@ -296,7 +298,8 @@ struct DecodeAttnShape {
 // operands of a call beside the cache and the position.  rope: [max_pos][head_size/2] (cos,sin) table fused in front, or null;
 // tickets: [batch, kvh] zeroed arrival counters = in-launch merge, null = merge kernel; qkv_slabs: q/k/v are read from the QKV
 // projection's split-K slabs (qkv unused) with qkv_scale; out_x32: out is the x32 activation image (batch <= 32), not [batch, H];
-// window > 0: sliding-window attention with `sinks` sink tokens (include/llmie.h), 0 = full attention
+// window > 0: sliding-window attention with `sinks` sink tokens (include/llmie.h), 0 = full attention; head_sink: this layer's
+// learned sink logits, device fp32 [head_num], or null
 struct DecodeAttnIo {
     const void *qkv, *qkv_bias;
     void *out, *workspace;
@@ -308,6 +311,7 @@ struct DecodeAttnIo {
     const SlabScale *qkv_scale;
     int out_x32;
     int window, sinks;
+    const float *head_sink;
 };
 // decode attention of one layer with bias, RoPE and the KV append fused in front: plan, refuse or launch
 int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st);
@@ -320,11 +324,13 @@ struct PrefillAttnPlan {
     int grid[3];                    // (query tiles of the longest sequence, head_num, batch)
     bool rope_append;               // prefill_rope_append_kernel runs first (else the QKV projection's epilogue did RoPE + the append)
     int window, sinks;              // window > 0: the windowed instantiation (sliding window + sink tokens), 0: full causal attention
+    bool head_sink;                 // the SINK instantiation of the same form: a learned sink logit per query head joins every row's softmax
 };
 PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window = 0, int sinks = 0);
 int prefill_attention_f16(const PrefillAttnPlan &plan, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
-                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st);
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st,
+                          const float *head_sink = nullptr /* plan.head_sink: this layer's device fp32 [head_num] */);
 // short prefills: slab consumer of the QKV projection with RoPE + KV-cache append folded in (q -> qkv, k / v -> the caches only)
 bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, const void *qkv, const void *bias);
 int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,

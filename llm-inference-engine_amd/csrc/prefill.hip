@@ -258,16 +258,18 @@ int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, 
 // and the tiles from floor(max(0, history + q0 - W + 1) / 64) on (a tile of both once); a wave skips a tile wholly in front of every
 // window of its rows like one wholly in their future; rows of a walked tile that no query of the workgroup sees re-read a visible
 // row of the same tile (0 x NaN would poison P.V), so neither a dead row nor the table entry of a dead page is ever read.
-template <int HS, bool KV8, int NW, int RT = 1, bool WIN = false, typename... WinArgs>
+// SINK (compile time): a learned sink logit per query head (include/llmie.h) -- one more pack argument at the end, the device array
+// head_sink[head_num] (fp32).  The key-tile loop does not know it: it enters once per row, at the final normalisation.
+template <int HS, bool KV8, int NW, int RT = 1, bool WIN = false, bool SINK = false, typename... WinArgs>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void prefill_flash_kernel(const half_t *__restrict__ qkv, const void *__restrict__ k_cache,
                                                             const void *__restrict__ v_cache, half_t *__restrict__ out,
                                                             const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
                                                             int head_num, int kv_head_num, int max_seq_len, size_t layer_off,
                                                             float k_scale, float v_scale,
                                                             const int32_t *__restrict__ table /* paged cache or null */, int max_pages,
-                                                            const WinArgs... win /* WIN: window, sinks */) {
+                                                            const WinArgs... win /* WIN: window, sinks; SINK: head_sink */) {
     static_assert(HS == 128, "tuned for head_size 128");
-    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0), "window, sinks");
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0), "window, sinks, head_sink");
     // V rows are 288 bytes (256 + 32): the PV operand is fetched with ds_read_b64_tr_b16 (gfx950 transposed LDS read: a 16-lane
     // group reads a block of 4 keys x 16 head dims and every lane receives one column of it = 4 consecutive keys of its head
     // dim), whose 16 lanes address 4 rows x 4 eight-byte pieces -- rows 32 bytes apart modulo 256 keep a 32-lane half
@@ -341,8 +343,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     // its rows (row q0's)
     int win_w = 0, win_s = 0, w_lo = 0, tl_sink = 0, tl_first = 0, n_tiles = 0;
     if constexpr (WIN) {
-        const int wa[2] = {win...};
-        win_w = wa[0], win_s = wa[1];
+        win_w = pack_arg<0>(win...), win_s = pack_arg<1>(win...);
         w_lo = max(0, history + q0 - win_w + 1);
         const int all = (t_hi + BT - 1) / BT, first = w_lo / BT, ns = (min(win_s, t_hi) + BT - 1) / BT;
         if (ns < first) tl_sink = ns, tl_first = first;
@@ -574,7 +575,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     for (int u = 0; u < RT; ++u) {
         const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run[u]));
         if (qrow[u] < len) {
-            const float inv = v_rem / (l + 1e-6f);  // the reference's denominator epsilon (scale_and_mask_and_softmax.cu:118)
+            float inv = v_rem / (l + 1e-6f);  // the reference's denominator epsilon (scale_and_mask_and_softmax.cu:118)
+            if constexpr (SINK) {
+                // the sink of head h, after the row's four lanes were reduced (so it enters once per row): in the log2 domain of
+                // m_run, M' = max(m_run, s2); the sum and -- folded into inv, so that the o tiles are not rescaled a second time --
+                // the output take 2^(m_run - M').  A row that saw no key (m_run = -inf) has l = 0 and o = 0 and stays 0.
+                const float s2 = pack_arg<WIN ? 2 : 0>(win...)[h] * 1.44269504088896341f;
+                const float m2 = fmaxf(m_run[u], s2);
+                const float a = (m_run[u] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run[u] - m2);
+                const float e = (s2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s2 - m2);
+                inv = v_rem * a / (__builtin_fmaf(l, a, e) + 1e-6f);
+            }
             half_t *optr = out + (static_cast<size_t>(cum[b] + qrow[u]) * head_num + h) * HS;
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) {
@@ -602,13 +613,13 @@ PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool k
     const int bq = bq64 ? 64 : 128;
     // (a window changes the key tiles a workgroup walks, not the grid: the forms are chosen as for full attention)
     return PrefillAttnPlan{bq, bq64 || rt2 ? 4 : 8, !bq64 && rt2 ? 2 : 1, kv_e4m3, {(max_q_len + bq - 1) / bq, head_num, batch}, !rope_done,
-                           window > 0 ? window : 0, window > 0 ? sinks : 0};
+                           window > 0 ? window : 0, window > 0 ? sinks : 0, false};
 }
 
 // g.grid[1] / g.grid[2] are head_num / batch
 int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
-                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st) {
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, const float *head_sink) {
     const int head_num = g.grid[1], batch = g.grid[2];
     const size_t layer_off = kv.block_table ? static_cast<size_t>(layer) * kv.num_pages * kv_head_num * 128 * 128
                                             : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * 128;
@@ -628,15 +639,47 @@ int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qk
         case 181: flash = prefill_flash_kernel<128, true, 8, 1>; break;
         default: set_error("prefill attention: no flash kernel of %d waves x %d row tiles", g.waves, g.row_tiles); return LLMIE_ERR_UNSUPPORTED;
     }
-    if (g.window > 0) {   // the windowed instantiations of the same forms
-        decltype(&prefill_flash_kernel<128, false, 4, 1, true, int, int>) wflash = nullptr;
+    if (g.head_sink) {   // the SINK instantiations of the same forms, windowed or not: the head-sink array is the last argument
+        if (!head_sink) {
+            set_error("prefill attention: a head-sink plan without the array");
+            return LLMIE_ERR_INVALID_ARG;
+        }
+        auto run = [&](auto kv8_c, auto nw_c, auto rt_c) {
+            constexpr bool K8 = decltype(kv8_c)::value;
+            constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
+            const dim3 grid(g.grid[0], g.grid[1], g.grid[2]);
+            if (g.window > 0)
+                prefill_flash_kernel<128, K8, NW, RT, true, true, int, int, const float *><<<grid, NW * 64, 0, st>>>(
+                    qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
+                    kv.max_pages, g.window, g.sinks, head_sink);
+            else
+                prefill_flash_kernel<128, K8, NW, RT, false, true, const float *><<<grid, NW * 64, 0, st>>>(
+                    qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
+                    kv.max_pages, head_sink);
+        };
+        using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
+        using I4 = std::integral_constant<int, 4>;
+        using I8 = std::integral_constant<int, 8>;
         switch ((g.kv_e4m3 ? 100 : 0) + g.waves * 10 + g.row_tiles) {
-            case 41: wflash = prefill_flash_kernel<128, false, 4, 1, true, int, int>; break;
-            case 42: wflash = prefill_flash_kernel<128, false, 4, 2, true, int, int>; break;
-            case 81: wflash = prefill_flash_kernel<128, false, 8, 1, true, int, int>; break;
-            case 141: wflash = prefill_flash_kernel<128, true, 4, 1, true, int, int>; break;
-            case 142: wflash = prefill_flash_kernel<128, true, 4, 2, true, int, int>; break;
-            case 181: wflash = prefill_flash_kernel<128, true, 8, 1, true, int, int>; break;
+            case 41: run(std::false_type{}, I4{}, I1{}); break;
+            case 42: run(std::false_type{}, I4{}, I2{}); break;
+            case 81: run(std::false_type{}, I8{}, I1{}); break;
+            case 141: run(std::true_type{}, I4{}, I1{}); break;
+            case 142: run(std::true_type{}, I4{}, I2{}); break;
+            case 181: run(std::true_type{}, I8{}, I1{}); break;
+        }
+        return launch_status("prefill_attention(head sink)");
+    }
+    if (g.window > 0) {   // the windowed instantiations of the same forms
+        decltype(&prefill_flash_kernel<128, false, 4, 1, true, false, int, int>) wflash = nullptr;
+        switch ((g.kv_e4m3 ? 100 : 0) + g.waves * 10 + g.row_tiles) {
+            case 41: wflash = prefill_flash_kernel<128, false, 4, 1, true, false, int, int>; break;
+            case 42: wflash = prefill_flash_kernel<128, false, 4, 2, true, false, int, int>; break;
+            case 81: wflash = prefill_flash_kernel<128, false, 8, 1, true, false, int, int>; break;
+            case 141: wflash = prefill_flash_kernel<128, true, 4, 1, true, false, int, int>; break;
+            case 142: wflash = prefill_flash_kernel<128, true, 4, 2, true, false, int, int>; break;
+            case 181: wflash = prefill_flash_kernel<128, true, 8, 1, true, false, int, int>; break;
         }
         wflash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), g.waves * 64, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num,
                                                                             kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
