@@ -1036,54 +1036,50 @@ class Decoder:
     def moe_attach(self, layers, top_k, flags=0, max_tokens=None, workspace=None):
         """While attached, every forward / prefill entry runs the moe sequence.  layers: one entry per layer, None (the layer keeps
         its dense FFN) or a dict / tuple (router [E, H], gate_up [E, 2 Ie, H], down [E, H, Ie]) of fp16 device tensors.  max_tokens:
-        the most rows a call will bring (default: max_batch); workspace: a uint8 tensor of moe_workspace_bytes, or None (one is made)."""
-        import torch
+        the most rows a call will bring (default: max_batch); workspace: a uint8 tensor of moe_workspace_bytes, or None (one is made).
+        With a MoeExperts descriptor among the layers the call is llmie_decoder_moe_attach_ex; tuples / dicts beside it count as fp16
+        experts."""
         if any(isinstance(lw, MoeExperts) for lw in layers):
-            return self._moe_attach_ex(layers, top_k, flags, max_tokens, workspace)
-        arr = (MoeLayer * len(layers))()
-        keep, shape = [], None
-        for i, lw in enumerate(layers):
-            if lw is None:
-                continue
-            r, gu, dn = (lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw
-            shape = shape or (gu.shape[1] // 2, gu.shape[0])
-            if (gu.shape[1] // 2, gu.shape[0]) != shape or r.shape[0] != shape[1] or tuple(dn.shape[:1]) != (shape[1],) or dn.shape[2] != shape[0]:
-                raise LlmieError("moe_attach: layer %d: expert shapes differ from the first sparse layer's" % i)
-            arr[i].router, arr[i].gate_up, arr[i].down = _p(r), _p(gu), _p(dn)
-            keep.append((r, gu, dn))
-        if shape is None:
-            raise LlmieError("moe_attach: no layer has experts")
-        inter, experts = shape
-        if workspace is None:
-            need = self.moe_workspace_bytes(max_tokens or self.cfg.max_batch, inter, experts, top_k)
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
-        _check(lib().llmie_decoder_moe_attach(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), "decoder_moe_attach")
-        self._moe_keep = (keep, workspace)
-        return workspace
+            return self._moe_attach(layers, MoeExpertsDesc, self._moe_layer_ex, lib().llmie_decoder_moe_attach_ex, "decoder_moe_attach_ex", top_k,
+                                    flags, max_tokens, workspace)
+        return self._moe_attach(layers, MoeLayer, self._moe_layer, lib().llmie_decoder_moe_attach, "decoder_moe_attach", top_k, flags, max_tokens,
+                                workspace)
 
-    def _moe_attach_ex(self, layers, top_k, flags, max_tokens, workspace):
-        """moe_attach with MoeExperts descriptors (llmie_decoder_moe_attach_ex); tuples / dicts among them count as fp16 experts"""
+    # one sparse layer -> ((inter, experts), or None where its tensors disagree with `shape`; the entry's struct; what keeps it alive)
+    @staticmethod
+    def _moe_layer(lw, shape):
+        r, gu, dn = (lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw
+        own = (gu.shape[1] // 2, gu.shape[0])
+        inter, experts = shape or own
+        agree = r.shape[0] == experts and tuple(dn.shape[:1]) == (experts,) and dn.shape[2] == inter
+        return own if agree else None, MoeLayer(_p(r), _p(gu), _p(dn)), (r, gu, dn)
+
+    @staticmethod
+    def _moe_layer_ex(lw, shape):
+        if not isinstance(lw, MoeExperts):
+            lw = MoeExperts(*((lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw))
+        return (lw.inter, lw.experts), lw.desc(), lw
+
+    def _moe_attach(self, layers, struct, layer, attach, who, top_k, flags, max_tokens, workspace):
+        """what the two attach entries share: the layer walk, the shape agreement, the workspace and what is kept alive"""
         import torch
-        arr = (MoeExpertsDesc * len(layers))()
+        arr = (struct * len(layers))()
         keep, shape = [], None
         for i, lw in enumerate(layers):
             if lw is None:
                 continue
-            if not isinstance(lw, MoeExperts):
-                r, gu, dn = (lw["router"], lw["gate_up"], lw["down"]) if isinstance(lw, dict) else lw
-                lw = MoeExperts(r, gu, dn)
-            shape = shape or (lw.inter, lw.experts)
-            if (lw.inter, lw.experts) != shape:
+            own, arr[i], alive = layer(lw, shape)
+            shape = shape or own
+            if own is None or own != shape:
                 raise LlmieError("moe_attach: layer %d: expert shapes differ from the first sparse layer's" % i)
-            arr[i] = lw.desc()
-            keep.append(lw)
+            keep.append(alive)
         if shape is None:
             raise LlmieError("moe_attach: no layer has experts")
         inter, experts = shape
         if workspace is None:
             need = self.moe_workspace_bytes(max_tokens or self.cfg.max_batch, inter, experts, top_k)
             workspace = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
-        _check(lib().llmie_decoder_moe_attach_ex(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), "decoder_moe_attach_ex")
+        _check(attach(self.handle, arr, inter, experts, top_k, flags, _p(workspace), workspace.numel()), who)
         self._moe_keep = (keep, workspace)
         return workspace
 

@@ -64,9 +64,9 @@ struct llmie_decoder {
     // dense FFN), the expert geometry and the attach call's scratch.  layers non-empty: every forward / prefill entry runs the moe sequence
     struct Moe {
         std::vector<llmie_moe_experts> layers;   // (llmie_decoder_moe_attach: fp16 descriptors without biases, plain SwiGLU)
-        int inter = 0, experts = 0, top_k = 0;
-        unsigned flags = 0;
-        llmie_weight_format format = LLMIE_W_F16;   // of the experts (the engine's own weight format is cfg.wfmt)
+        // every call's description but its rows: the expert geometry, the attach flags, the experts' format (the engine's own weight
+        // format is cfg.wfmt) and the first sparse layer's epilogue
+        MoeCall call{};
         void *ws = nullptr;
         size_t ws_bytes = 0;
         bool on() const { return !layers.empty(); }
@@ -1229,7 +1229,7 @@ struct DecodeStep {
     }
     int unfused() const;
     int lora() const;
-    int moe() const;
+    int moe(const MoePlan &moe_plan) const;
 };
 
 // ---- the reference's launch sequence (self_decoder.cpp:69-119), one kernel per step; RoPE inside the attention launch where its
@@ -1314,25 +1314,34 @@ int DecodeStep::lora() const {
     return LLMIE_OK;
 }
 
-// the attach call's scratch must cover this call's rows: checked before anything is enqueued
-static int moe_rows_fit(const llmie_decoder *d, int rows, const char *who) {
-    const size_t need = llmie_moe_workspace_bytes(rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k);
+// the attach call's scratch must cover this call's rows: checked before anything is enqueued.  The call's one plan is made here
+static int moe_rows_fit(const llmie_decoder *d, int rows, const char *who, MoePlan *plan) {
+    MoeCall c = d->moe.call;
+    c.rows = rows;
+    const size_t need = llmie_moe_workspace_bytes(rows, c.H, c.Ie, c.E, c.k);
     if (d->moe.ws_bytes < need) {
         set_error("%s: the workspace given to llmie_decoder_moe_attach does not cover %d rows (%zu < %zu)", who, rows, d->moe.ws_bytes, need);
         return LLMIE_ERR_WORKSPACE;
     }
     // and the attach flags must hold at this row count (LLMIE_MOE_FORCE_GEMV has a row limit)
-    return moe_call_check(who, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.format);
+    return moe_call_check(who, c, plan);
 }
-// one stage of the FFN of a layer with a router, y = moe_ffn(x) + resid (x and y may be one buffer): route, gate/up, down
-static int engine_moe(const llmie_decoder *d, int layer, const void *x, const void *resid, void *y, int rows, unsigned stage, llmie_stream stream) {
-    return moe_ffn_stages("moe_ffn", x, &d->moe.layers[layer], resid, y, rows, d->H, d->moe.inter, d->moe.experts, d->moe.top_k, d->moe.flags, d->moe.ws,
-                          d->moe.ws_bytes, LLMIE_F16, stage, stream);
+// the FFN of a layer with a router, h = moe_ffn(h) + resid, under the call's plan: prepared once, its stages under the op kinds of a
+// dense layer's FFN launches
+static int engine_moe_ffn(llmie_decoder *dec, const MoePlan &plan, int layer, void *h, const void *resid, llmie_stream stream) {
+    int rc;
+    MoePrepared m;
+    const MoeOperands o{h, resid, h, &dec->moe.layers[layer], dec->moe.ws, dec->moe.ws_bytes, LLMIE_F16};
+    if ((rc = moe_prepare("moe_ffn", plan.call, o, &plan, &m))) return rc;
+    TIMED(LLMIE_OP_FFN_NORM, moe_launch(m, MOE_STAGE_ROUTE, as_stream(stream)));
+    TIMED(LLMIE_OP_GATE_UP_SWIGLU, moe_launch(m, MOE_STAGE_GATE_UP, as_stream(stream)));
+    TIMED(LLMIE_OP_DOWN_GEMM, moe_launch(m, MOE_STAGE_DOWN, as_stream(stream)));
+    return LLMIE_OK;
 }
 
 // ---- experts attached: the unfused sequence; a layer with a router runs route + expert FFN (the down projection's residual through
 // `resid`) where a dense layer runs its gate/up and down launches ----
-int DecodeStep::moe() const {
+int DecodeStep::moe(const MoePlan &moe_plan) const {
     int rc;
     for (int l = 0; l < c.num_layers; ++l) {
         const llmie_layer_weights &w = dec->layers[l];
@@ -1348,9 +1357,7 @@ int DecodeStep::moe() const {
         TIMED(LLMIE_OP_O_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->mha, w.o, h, batch, H, H, EPI_NONE_, nullptr), stream));
         TIMED(LLMIE_OP_FFN_NORM, llmie_fused_add_bias_residual_rmsnorm(dec->resid, h, w.o.bias, w.ffn_norm_gamma, c.rms_eps, batch, H, dt, stream));
         if (dec->moe.layers[l].router) {
-            TIMED(LLMIE_OP_FFN_NORM, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_ROUTE, stream));
-            TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_GATE_UP, stream));
-            TIMED(LLMIE_OP_DOWN_GEMM, engine_moe(dec, l, h, dec->resid, h, batch, MOE_STAGE_DOWN, stream));
+            if ((rc = engine_moe_ffn(dec, moe_plan, l, h, dec->resid, stream))) return rc;
         } else {
             TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_linear(dec, c.wfmt, proj_operands(c, h, w.gate_up, dec->act, batch, H, 2 * I, EPI_SWIGLU_, nullptr), stream));
             TIMED(LLMIE_OP_DOWN_GEMM, engine_linear(dec, c.wfmt, proj_operands(c, dec->act, w.down, h, batch, I, H, EPI_NONE_, dec->resid), stream));
@@ -1369,8 +1376,9 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
                   c.max_seq_len);
     if (dec->lora.table)
         if (int rc = lora_rows_fit(dec, batch, "decoder_forward")) return rc;
+    MoePlan moe_plan{};
     if (dec->moe.on() && !dec->lora.table)
-        if (int rc = moe_rows_fit(dec, batch, "decoder_forward")) return rc;
+        if (int rc = moe_rows_fit(dec, batch, "decoder_forward", &moe_plan)) return rc;
     if (hidden_out != hidden_in) {
         hipError_t e = hipMemcpyAsync(hidden_out, hidden_in, static_cast<size_t>(batch) * dec->H * dec->esz,
                                       hipMemcpyDeviceToDevice, as_stream(stream));
@@ -1391,7 +1399,7 @@ static int decoder_forward(llmie_decoder *dec, const void *hidden_in, void *hidd
         case DP_SPLITK: return s.splitk();
         case DP_UNFUSED: return s.unfused();
         case DP_LORA: return s.lora();
-        case DP_MOE: return s.moe();
+        case DP_MOE: return s.moe(moe_plan);
         default: return decode_refuse(call, plan);
     }
 }
@@ -1731,7 +1739,7 @@ struct PrefillPass {
     }
     // experts attached: the general sequence in the forms plan_prefill_layer forces (normalised fp16 rows in place); a layer with a
     // router runs route + expert FFN where a dense layer runs its gate/up and down launches
-    int moe() const {
+    int moe(const MoePlan &moe_plan) const {
         int rc;
         for (int l = 0; l < c.num_layers; ++l) {
             const llmie_layer_weights &w = dec->layers[l];
@@ -1742,9 +1750,7 @@ struct PrefillPass {
             TIMED(LLMIE_OP_O_GEMM, proj(attn, w.o, h, H, H, nullptr));
             TIMED(LLMIE_OP_FFN_NORM, ffn_norm(lp.ffn_norm, w));
             if (dec->moe.layers[l].router) {
-                TIMED(LLMIE_OP_FFN_NORM, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_ROUTE, stream));
-                TIMED(LLMIE_OP_GATE_UP_SWIGLU, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_GATE_UP, stream));
-                TIMED(LLMIE_OP_DOWN_GEMM, engine_moe(dec, l, h, resid, h, T, MOE_STAGE_DOWN, stream));
+                if ((rc = engine_moe_ffn(dec, moe_plan, l, h, resid, stream))) return rc;
             } else {
                 if ((rc = gate_up(h, w.gate_up, lp.gate_up))) return rc;
                 TIMED(LLMIE_OP_DOWN_GEMM, proj(act, w.down, h, I, H, resid));
@@ -1799,8 +1805,9 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (plan.path == PP_REFUSED) return prefill_refuse(plan);
     if (plan.path == PP_LORA)
         if (int rc = lora_rows_fit(dec, T, "decoder_prefill")) return rc;
+    MoePlan moe_plan{};
     if (plan.path == PP_MOE)
-        if (int rc = moe_rows_fit(dec, T, "decoder_prefill")) return rc;
+        if (int rc = moe_rows_fit(dec, T, "decoder_prefill", &moe_plan)) return rc;
     const PrefillCarve o = prefill_carve(&c, T, batch);
     if (workspace_bytes < o.total || reinterpret_cast<uintptr_t>(workspace) % 256) {
         set_error("decoder_prefill: workspace too small or unaligned (%zu < %zu)", workspace_bytes, o.total);
@@ -1850,7 +1857,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
         return rc;
     switch (plan.path) {
         case PP_LORA: return p.lora();
-        case PP_MOE: return p.moe();
+        case PP_MOE: return p.moe(moe_plan);
         case PP_PACKED_ONLY: return p.packed_only();
         case PP_SHORT_SPLITK: return p.short_splitk();
         case PP_LEAN: return p.lean();
@@ -1902,15 +1909,15 @@ extern "C" size_t llmie_decoder_moe_workspace_bytes(const llmie_decoder_config *
 }
 
 // both attach entries: the descriptors of every layer are already checked pointer by pointer
-static int moe_attach_common(llmie_decoder *dec, const char *who, std::vector<llmie_moe_experts> &&layers, llmie_weight_format format, int inter,
-                             int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes) {
-    const size_t need = llmie_moe_workspace_bytes(dec->cfg.max_batch, dec->H, inter, experts, top_k);
+static int moe_attach_common(llmie_decoder *dec, const char *who, std::vector<llmie_moe_experts> &&layers, const MoeCall &call, void *workspace,
+                             size_t workspace_bytes) {
+    const size_t need = llmie_moe_workspace_bytes(dec->cfg.max_batch, call.H, call.Ie, call.E, call.k);
     if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 256) {
         set_error("%s: workspace too small or not 256-byte aligned (%zu < %zu)", who, workspace_bytes, need);
         return LLMIE_ERR_WORKSPACE;
     }
     dec->moe.layers = std::move(layers);
-    dec->moe.inter = inter, dec->moe.experts = experts, dec->moe.top_k = top_k, dec->moe.flags = flags, dec->moe.format = format;
+    dec->moe.call = call;
     dec->moe.ws = workspace, dec->moe.ws_bytes = workspace_bytes;
     return LLMIE_OK;
 }
@@ -1922,7 +1929,8 @@ extern "C" int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_laye
     if (!moe_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_moe_attach: %s", kMoeRefusal);
     if (dec->lora.table) LLMIE_UNSUPPORTED("decoder_moe_attach: %s", kMoeLoraRefusal);
     // the operator's own checks of the expert geometry and flags, at one row (a flag with a row limit is checked per call)
-    if (int rc = moe_call_check("decoder_moe_attach", 1, dec->H, inter, experts, top_k, flags)) return rc;
+    const MoeCall call{1, dec->H, inter, experts, top_k, flags, LLMIE_W_F16, false};
+    if (int rc = moe_call_check("decoder_moe_attach", call)) return rc;
     bool any = false;
     std::vector<llmie_moe_experts> ex(dec->cfg.num_layers, llmie_moe_experts{});
     for (int l = 0; l < dec->cfg.num_layers; ++l) {
@@ -1933,7 +1941,7 @@ extern "C" int llmie_decoder_moe_attach(llmie_decoder *dec, const llmie_moe_laye
         ex[l].format = LLMIE_W_F16, ex[l].router = m.router, ex[l].gate_up = m.gate_up, ex[l].down = m.down, ex[l].act = LLMIE_MOE_ACT_SWIGLU;
     }
     LLMIE_REQUIRE(any, "decoder_moe_attach: no layer has a router");
-    return moe_attach_common(dec, "decoder_moe_attach", std::move(ex), LLMIE_W_F16, inter, experts, top_k, flags, workspace, workspace_bytes);
+    return moe_attach_common(dec, "decoder_moe_attach", std::move(ex), call, workspace, workspace_bytes);
 }
 
 extern "C" int llmie_decoder_moe_attach_ex(llmie_decoder *dec, const llmie_moe_experts *layers, int inter, int experts, int top_k, unsigned flags,
@@ -1952,9 +1960,10 @@ extern "C" int llmie_decoder_moe_attach_ex(llmie_decoder *dec, const llmie_moe_e
             LLMIE_UNSUPPORTED("decoder_moe_attach_ex: layer %d differs from the first sparse layer in expert format or act", l);
     }
     LLMIE_REQUIRE(first, "decoder_moe_attach_ex: no layer has a router");
-    if (int rc = moe_call_check("decoder_moe_attach_ex", 1, dec->H, inter, experts, top_k, flags, first->format)) return rc;
-    return moe_attach_common(dec, "decoder_moe_attach_ex", std::vector<llmie_moe_experts>(layers, layers + dec->cfg.num_layers), first->format, inter,
-                             experts, top_k, flags, workspace, workspace_bytes);
+    const MoeCall call{1, dec->H, inter, experts, top_k, flags, first->format, moe_epilogue_live(*first)};
+    if (int rc = moe_call_check("decoder_moe_attach_ex", call)) return rc;
+    return moe_attach_common(dec, "decoder_moe_attach_ex", std::vector<llmie_moe_experts>(layers, layers + dec->cfg.num_layers), call, workspace,
+                             workspace_bytes);
 }
 
 extern "C" int llmie_decoder_moe_detach(llmie_decoder *dec) {

@@ -341,15 +341,56 @@ int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t 
 int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, int batch, int num_tokens, int32_t *tok_b, int32_t *tok_tpos,
                         QkvRopeArgs args, QkvRopeArgs *args_dev, hipStream_t st);
 
-// ---- mixture-of-experts FFN (moe.hip): llmie_moe_ffn by stages, for the engine's per-op accounting, and its host checks alone ----
-enum : unsigned { MOE_STAGE_ROUTE = 1, MOE_STAGE_GATE_UP = 2 /* grouped route: with the plan launch */, MOE_STAGE_DOWN = 4 /* with combine */ };
-// (who: the entry's name in messages; ex: the expert descriptor of llmie_moe_ffn_ex -- llmie_moe_ffn fills one with fp16 experts)
-int moe_ffn_stages(const char *who, const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter,
-                   int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
-                   llmie_stream stream);
-int moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags,
-                   llmie_weight_format format = LLMIE_W_F16);
+// ---- mixture-of-experts FFN (moe.hip): one pure host planner decides the launches, one launcher runs the plan by stages ----
+// A call is three structs, from the C entry to the kernel launch.  What the planner reads and nothing else:
+struct MoeCall {
+    int rows, H, Ie, E, k;
+    unsigned flags;                    // LLMIE_MOE_*
+    llmie_weight_format format;        // of the experts: LLMIE_W_F16 or LLMIE_W_MXFP4
+    bool ex;                           // the _ex epilogue is live: an expert bias, or the clamped act
+};
+inline bool moe_epilogue_live(const llmie_moe_experts &e) { return e.gate_up_bias || e.down_bias || e.act != LLMIE_MOE_ACT_SWIGLU; }
+enum MoeRoute : int { MOE_GEMV = 0, MOE_GROUPED = 1 };
+// the workspace carve: byte offsets behind the plan's 256-byte header; tile_* and d are 0-sized on the GEMV route
+struct MoeCarve {
+    size_t expert, weight, act, tile_expert, tile_pairs, d, bytes;
+};
+// What plan_moe answers for a MoeCall (which it keeps): the launcher, the plan text and the workspace rule read this and nothing else
+struct MoePlan {
+    MoeCall call;
+    int route, rt, tiles, pairs;       // MoeRoute; grouped: the tile height 16 * rt and the host bound of the tile count
+    int route_grid, gate_up_grid[2], down_grid[2], combine_grid[2];
+    // the instantiations.  GEMV route: XC of moe_gemv_*_kernel (fp16 experts) or the (XB, KW) index of moe_mx4_gemv_*_kernel, for
+    // the gate/up launch (K = H) and the down launch (K = Ie).  ex: the EX instantiations of the fp16 expert kernels
+    int gate_up_cfg, down_cfg;
+    bool ex;
+    MoeCarve ws;
+};
+// the operands of a call: x, resid (or null) and y are [rows, H]; x and y may be one buffer
+struct MoeOperands {
+    const void *x, *resid;
+    void *y;
+    const llmie_moe_experts *experts;
+    void *workspace;
+    size_t workspace_bytes;
+    llmie_dtype dtype;
+};
+// a call that passed every check, planned and carved: the plan and the kernel argument structs of moe.hip
+struct MoePrepared {
+    MoePlan plan;
+    alignas(16) unsigned char args[256];
+};
+enum : unsigned { MOE_STAGE_ROUTE = 1, MOE_STAGE_GATE_UP = 2 /* grouped route: with the plan launch */, MOE_STAGE_DOWN = 4 /* with combine */,
+                  MOE_STAGE_ALL = 7 };
+// would llmie_moe_ffn / _ex take this shape and these flags?  The code and the message under `who`, and the plan (null: not wanted);
+// nothing is launched
+int moe_call_check(const char *who, const MoeCall &c, MoePlan *plan = nullptr);
 int moe_experts_ok(const char *who, const llmie_moe_experts *ex);   // a descriptor's own checks: format, pointers, scales, act, alignment
+// every check of llmie_moe_ffn_ex under the name `who`, then plan, carve and fill the kernel arguments.  shape: rows .. flags of the
+// call (format and ex follow the descriptor).  planned: a plan made ahead for this very shape (the engine's, once per forward call),
+// taken where the descriptor's format and epilogue are the ones it was made for; null: none
+int moe_prepare(const char *who, const MoeCall &shape, const MoeOperands &o, const MoePlan *planned, MoePrepared *out);
+int moe_launch(const MoePrepared &m, unsigned stages, hipStream_t st);   // nothing but the launches of these stages
 
 // ---- the sampler family (sampling_params.hip, spec_decode.hip, topk_sampling.hip and the LM-head entries of engine.hip) ----
 // A call is a few structs that say what its operands are, from the C entry to the kernel launch: a new operand is added to ONE struct,

@@ -18,11 +18,23 @@
 //             epilogues of the kernels above (a template flag on the fp16 expert kernels, uniform branches elsewhere), and MXFP4
 //             experts on kernels of their own beside the fp16 ones: moe_mx4_gemv_* (waves own weight rows, a lane's 16-byte load is
 //             one block of 32 codes) and moe_mx4_grouped_kernel (operands swapped: a lane owns one weight row and one scale).
+//             llmie_moe_ffn is the _ex call of a descriptor with fp16 experts, no bias and the plain act; such a call (MoePlan::ex
+//             false) launches the EX = false instantiations.
 // Every output element is computed by one lane chain that depends on its row, the weights and the route only: no atomics, same bits
 // wherever the row stands.
+//
+// Host side: a call is MoeCall + MoeOperands (llmie_internal.h).  plan_moe -- pure, the only producer of a MoePlan --
+// decides the route, RT, the grids, the workspace carve and the kernel instantiations; the launcher (moe_launch), the plan text
+// (llmie_moe_ffn_plan / _plan_ex) and the workspace rule read that plan.  moe_prepare makes every check of an entry in one fixed
+// order, plans, carves and fills the kernel arguments once; moe_launch runs the stages asked for and does nothing else, each launch
+// written once behind a dispatch helper that turns the plan's fields into template arguments.  llmie_moe_ffn / _ex are prepare +
+// every stage; the engine plans once per forward / prefill call, prepares once per sparse layer and launches the three stages
+// under its three op kinds.
 #include "llmie_internal.h"
 
 #include <cstring>
+#include <new>
+#include <type_traits>
 
 namespace llmie {
 namespace {
@@ -41,16 +53,9 @@ constexpr unsigned kMoeFlags = LLMIE_MOE_SOFTMAX_ALL | LLMIE_MOE_FORCE_GEMV | LL
 
 __host__ __device__ inline size_t moe_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
-// ---- plan_moe: a pure host function of (rows, H, Ie, E, k, flags, expert format) ----
-enum MoeRoute : int { MOE_GEMV = 0, MOE_GROUPED = 1 };
-struct MoePlan {
-    int route, rt, tiles, pairs;
-    int route_grid, gate_up_grid[2], down_grid[2], combine_grid[2];
-    // the workspace carve: byte offsets; tile_* and d are 0-sized on the GEMV route
-    size_t expert, weight, act, tile_expert, tile_pairs, d, bytes;
-};
-
-int moe_shape_check(const char *who, int rows, int H, int Ie, int E, int k) {
+// ---- plan_moe: a pure host function of a MoeCall (llmie_internal.h), and the only producer of a MoePlan ----
+int moe_shape_check(const char *who, const MoeCall &c) {
+    const int rows = c.rows, H = c.H, Ie = c.Ie, E = c.E, k = c.k;
     LLMIE_REQUIRE(rows > 0 && H > 0 && Ie > 0 && E > 0 && k > 0, "%s: non-positive size rows=%d hidden=%d inter=%d experts=%d top_k=%d", who, rows, H,
                   Ie, E, k);
     if (E > kMoeMaxExperts) LLMIE_UNSUPPORTED("%s: %d experts above LLMIE_MOE_MAX_EXPERTS (%d)", who, E, kMoeMaxExperts);
@@ -64,22 +69,45 @@ int moe_shape_check(const char *who, int rows, int H, int Ie, int E, int k) {
 
 inline int moe_tiles(int pairs, int E, int rt) { return pairs / (16 * rt) + (E < pairs ? E : pairs); }
 
-void moe_carve(MoePlan *p, int H, int Ie, int tiles_max, size_t tile_pair_slots) {
+MoeCarve moe_carve(const MoeCall &c, bool grouped, int tiles_max, size_t tile_pair_slots) {
+    const size_t pairs = static_cast<size_t>(c.rows) * c.k;
+    MoeCarve w{};
     size_t off = 256;   // the plan's header: {tiles in use}
-    p->expert = off, off += moe_align(4 * static_cast<size_t>(p->pairs));
-    p->weight = off, off += moe_align(4 * static_cast<size_t>(p->pairs));
-    p->act = off, off += moe_align(2 * static_cast<size_t>(p->pairs) * Ie);
-    p->tile_expert = off, off += moe_align(4 * static_cast<size_t>(tiles_max));
-    p->tile_pairs = off, off += moe_align(4 * tile_pair_slots);
-    p->d = off, off += p->route == MOE_GROUPED ? moe_align(4 * static_cast<size_t>(p->pairs) * H) : 0;
-    p->bytes = off;
+    w.expert = off, off += moe_align(4 * pairs);
+    w.weight = off, off += moe_align(4 * pairs);
+    w.act = off, off += moe_align(2 * pairs * c.Ie);
+    w.tile_expert = off, off += moe_align(4 * static_cast<size_t>(tiles_max));
+    w.tile_pairs = off, off += moe_align(4 * tile_pair_slots);
+    w.d = off, off += grouped ? moe_align(4 * pairs * c.H) : 0;
+    w.bytes = off;
+    return w;
+}
+// every section at the larger of its sizes over the routes and RT: covers the plan of every row count up to c.rows
+MoeCarve moe_cover_carve(const MoeCall &c) {
+    const int pairs = c.rows * c.k, t1 = moe_tiles(pairs, c.E, 1), t4 = moe_tiles(pairs, c.E, 4);
+    const size_t s1 = static_cast<size_t>(t1) * 16, s4 = static_cast<size_t>(t4) * 64;
+    return moe_carve(c, true, t1 > t4 ? t1 : t4, s1 > s4 ? s1 : s4);
+}
+
+// XC of the fp16 GEMV kernels: 16-byte chunks of a K-long row per thread
+int moe_xc(int K) {
+    const int need = (K / 8 + 255) / 256;
+    return need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 8));
+}
+// the (XB, KW) of the MXFP4 GEMV kernels: 0 .. 3 = (1, 1), (2, 1), (2, 2), (2, 4)
+int moe_mx4_cfg(int K) {
+    const int nb = K / 32;
+    return nb <= 64 ? 0 : (nb <= 128 ? 1 : (nb <= 256 ? 2 : 3));
 }
 
 // the shape has been checked (moe_shape_check)
 // format: LLMIE_W_F16 or LLMIE_W_MXFP4 experts.  The GEMV row threshold is a per-format constant (tools/moebench.py --mxfp4 shows the
 // MXFP4 crossover at the 16 rows the GEMV kernels stop at); RT = 4 from 32 pairs per expert in both (rt4 is ahead from 128 tokens in both)
-int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned flags, llmie_weight_format format, MoePlan *p) {
-    const int gemv_rows = format == LLMIE_W_MXFP4 ? kMoeGemvRowsMx4 : kMoeGemvRows;
+int plan_moe(const char *who, const MoeCall &c, MoePlan *p) {
+    const int rows = c.rows, H = c.H, Ie = c.Ie, E = c.E;
+    const unsigned flags = c.flags;
+    const bool mx4 = c.format == LLMIE_W_MXFP4;
+    const int gemv_rows = mx4 ? kMoeGemvRowsMx4 : kMoeGemvRows;
     const bool fg = flags & LLMIE_MOE_FORCE_GEMV, fm = flags & LLMIE_MOE_FORCE_GROUPED;
     LLMIE_REQUIRE(!(fg && fm), "%s: LLMIE_MOE_FORCE_GEMV and LLMIE_MOE_FORCE_GROUPED together", who);
     LLMIE_REQUIRE(!(flags & ~kMoeFlags), "%s: unknown flags 0x%x", who, flags);
@@ -87,21 +115,24 @@ int plan_moe(const char *who, int rows, int H, int Ie, int E, int k, unsigned fl
     const bool gemv_fits = H <= kMoeGemvMaxK && Ie <= kMoeGemvMaxK;
     if (fg && rows > kMoeGemvForceRows) LLMIE_UNSUPPORTED("%s: LLMIE_MOE_FORCE_GEMV with %d rows, above %d", who, rows, kMoeGemvForceRows);
     if (fg && !gemv_fits) LLMIE_UNSUPPORTED("%s: LLMIE_MOE_FORCE_GEMV with hidden=%d / inter=%d above %d", who, H, Ie, kMoeGemvMaxK);
-    std::memset(p, 0, sizeof(*p));
-    p->pairs = rows * k;
+    *p = MoePlan{};
+    p->call = c, p->ex = c.ex;
+    p->pairs = rows * c.k;
     p->route = fg ? MOE_GEMV : (fm ? MOE_GROUPED : (rows <= gemv_rows && gemv_fits ? MOE_GEMV : MOE_GROUPED));
     p->route_grid = (rows + 3) / 4;
     if (p->route == MOE_GEMV) {
+        const auto cfg = [&](int K) { return mx4 ? moe_mx4_cfg(K) : moe_xc(K); };
+        p->gate_up_cfg = cfg(H), p->down_cfg = cfg(Ie);
         p->gate_up_grid[0] = Ie / kMoeGemvCols, p->gate_up_grid[1] = p->pairs;
         p->down_grid[0] = H / kMoeGemvCols, p->down_grid[1] = rows;
-        moe_carve(p, H, Ie, 0, 0);
+        p->ws = moe_carve(c, false, 0, 0);
     } else {
         p->rt = (flags & LLMIE_MOE_FORCE_RT1) ? 1 : ((flags & LLMIE_MOE_FORCE_RT4) || p->pairs / E >= kMoeRt4PairsPerExpert ? 4 : 1);
         p->tiles = moe_tiles(p->pairs, E, p->rt);
         p->gate_up_grid[0] = p->tiles, p->gate_up_grid[1] = Ie / kMoeGroupCols;
         p->down_grid[0] = p->tiles, p->down_grid[1] = H / kMoeGroupCols;
         p->combine_grid[0] = rows, p->combine_grid[1] = (H / 4 + kMoeCombineThreads - 1) / kMoeCombineThreads;   // rows on x: no 65535 limit
-        moe_carve(p, H, Ie, p->tiles, static_cast<size_t>(p->tiles) * 16 * p->rt);
+        p->ws = moe_carve(c, true, p->tiles, static_cast<size_t>(p->tiles) * 16 * p->rt);
     }
     return LLMIE_OK;
 }
@@ -768,70 +799,44 @@ __global__ __launch_bounds__(256) void moe_mx4_grouped_kernel(const MoeFfnArgs a
         }
 }
 
-int moe_xc(int K) {
-    const int need = (K / 8 + 255) / 256;
-    return need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 8));
-}
-// the (XB, KW) of the MXFP4 GEMV kernels: 0 .. 3 = (1, 1), (2, 1), (2, 2), (2, 4)
-int moe_mx4_cfg(int K) {
-    const int nb = K / 32;
-    return nb <= 64 ? 0 : (nb <= 128 ? 1 : (nb <= 256 ? 2 : 3));
-}
+// what MoePrepared::args holds: the argument structs of the kernels above, filled once per call
+struct MoeLaunchArgs {
+    MoeRouteArgs r;
+    MoeFfnArgs a;
+};
+static_assert(sizeof(MoeLaunchArgs) <= sizeof(MoePrepared::args) && alignof(MoeLaunchArgs) <= 16, "MoePrepared::args holds a MoeLaunchArgs");
 
 void moe_route_launch(const MoeRouteArgs &r, hipStream_t st) { moe_route_kernel<<<(r.rows + 3) / 4, 256, 0, st>>>(r); }
 
-thread_local char g_moe_plan_text[256];
-
-}  // namespace
-}  // namespace llmie
-
-using namespace llmie;
-
-extern "C" size_t llmie_moe_workspace_bytes(int max_rows, int hidden, int inter, int experts, int top_k) {
-    if (moe_shape_check("moe_workspace_bytes", max_rows, hidden, inter, experts, top_k)) return 0;
-    // every section at the larger of its sizes over the routes and RT: covers the plan of every row count up to max_rows
-    MoePlan p{};
-    p.pairs = max_rows * top_k;
-    p.route = MOE_GROUPED;
-    const int t1 = moe_tiles(p.pairs, experts, 1), t4 = moe_tiles(p.pairs, experts, 4);
-    const size_t s1 = static_cast<size_t>(t1) * 16, s4 = static_cast<size_t>(t4) * 64;
-    moe_carve(&p, hidden, inter, t1 > t4 ? t1 : t4, s1 > s4 ? s1 : s4);
-    return p.bytes;
+// ---- a plan's fields -> the instantiation: f gets the template arguments as integral constants, so a launch is written once ----
+template <int V> using MoeInt = std::integral_constant<int, V>;
+// (the instantiations go into the code object in the order in which these alternatives and the launcher name them; both keep the order
+// of the launch code they replaced, so the code object is that one's byte for byte -- where a kernel lies showed in the grouped
+// route's time)
+template <class F> void moe_ex_dispatch(bool ex, F f) { !ex ? f(std::false_type{}) : f(std::true_type{}); }   // (EX)
+template <class F> void moe_rt_dispatch(int rt, F f) { rt == 4 ? f(MoeInt<4>{}) : f(MoeInt<1>{}); }           // (RT)
+template <class F> void moe_gemv_dispatch(int xc, bool ex, F f) {   // fp16 GEMV pair: (XC, EX)
+    const auto g = [&](auto x) { moe_ex_dispatch(ex, [&](auto e) { f(x, e); }); };
+    xc == 1 ? g(MoeInt<1>{}) : (xc == 2 ? g(MoeInt<2>{}) : (xc == 4 ? g(MoeInt<4>{}) : g(MoeInt<8>{})));
+}
+template <class F> void moe_mx4_gemv_dispatch(int cfg, F f) {   // MXFP4 GEMV pair: (XB, KW) of moe_mx4_cfg's index
+    using One = MoeInt<1>; using Two = MoeInt<2>;
+    cfg == 0 ? f(One{}, One{}) : (cfg == 1 ? f(Two{}, One{}) : (cfg == 2 ? f(Two{}, Two{}) : f(Two{}, MoeInt<4>{})));
 }
 
-static int moe_plan_line(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format) {
+thread_local char g_moe_plan_text[256];
+
+int moe_plan_line(const char *who, const MoeCall &c) {
     MoePlan p;
-    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
-    if (int rc = plan_moe(who, rows, hidden, inter, experts, top_k, flags, format, &p)) return rc;
+    if (int rc = moe_call_check(who, c, &p)) return rc;
     snprintf(g_moe_plan_text, sizeof(g_moe_plan_text), "route=%s rt=%d tiles=%d route_grid=%d plan_grid=%d gate_up_grid=%dx%d down_grid=%dx%d combine_grid=%dx%d ws=%zu",
              p.route == MOE_GEMV ? "gemv" : "grouped", p.rt, p.tiles, p.route_grid, p.route == MOE_GROUPED ? 1 : 0, p.gate_up_grid[0], p.gate_up_grid[1],
-             p.down_grid[0], p.down_grid[1], p.combine_grid[0], p.combine_grid[1], p.bytes);
+             p.down_grid[0], p.down_grid[1], p.combine_grid[0], p.combine_grid[1], p.ws.bytes);
     return LLMIE_OK;
 }
 
-extern "C" const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
-    return moe_plan_line("moe_ffn_plan", rows, hidden, inter, experts, top_k, flags, LLMIE_W_F16) ? nullptr : g_moe_plan_text;
-}
-
-extern "C" const char *llmie_moe_ffn_plan_ex(int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format,
-                                             llmie_moe_act act) {
-    if (format != LLMIE_W_F16 && format != LLMIE_W_MXFP4) {
-        set_error("moe_ffn_plan_ex: expert format %d is neither LLMIE_W_F16 nor LLMIE_W_MXFP4", static_cast<int>(format));
-        return nullptr;
-    }
-    if (act != LLMIE_MOE_ACT_SWIGLU && act != LLMIE_MOE_ACT_SWIGLU_CLAMPED) {
-        set_error("moe_ffn_plan_ex: unknown act %d", static_cast<int>(act));
-        return nullptr;
-    }
-    if (moe_plan_line("moe_ffn_plan_ex", rows, hidden, inter, experts, top_k, flags, format)) return nullptr;
-    const size_t n = strlen(g_moe_plan_text);
-    snprintf(g_moe_plan_text + n, sizeof(g_moe_plan_text) - n, " format=%s act=%s", format == LLMIE_W_MXFP4 ? "mxfp4" : "f16",
-             act == LLMIE_MOE_ACT_SWIGLU_CLAMPED ? "swiglu_clamped" : "swiglu");
-    return g_moe_plan_text;
-}
-
 // an expert descriptor on its own: format, the pointers every call needs, scales against the format, the act's constants
-static int moe_experts_check(const char *who, const llmie_moe_experts *ex) {
+int moe_experts_check(const char *who, const llmie_moe_experts *ex) {
     LLMIE_REQUIRE(ex, "%s: NULL expert descriptor", who);
     if (ex->format != LLMIE_W_F16 && ex->format != LLMIE_W_MXFP4)
         LLMIE_UNSUPPORTED("%s: expert format %d is neither LLMIE_W_F16 nor LLMIE_W_MXFP4", who, static_cast<int>(ex->format));
@@ -845,46 +850,75 @@ static int moe_experts_check(const char *who, const llmie_moe_experts *ex) {
                       "%s: clamped SwiGLU needs a finite limit > 0 and a finite alpha (limit=%g alpha=%g)", who, ex->limit, ex->alpha);
     return LLMIE_OK;
 }
-static int moe_experts_aligned(const char *who, const llmie_moe_experts *ex) {
+int moe_experts_aligned(const char *who, const llmie_moe_experts *ex) {
     if (mis16(ex->router) || mis16(ex->gate_up) || mis16(ex->down)) LLMIE_UNSUPPORTED("%s: x / router / gate_up / down / resid / y not 16-byte aligned", who);
     if (reinterpret_cast<uintptr_t>(ex->router_bias) % 2 || reinterpret_cast<uintptr_t>(ex->gate_up_bias) % 2 || reinterpret_cast<uintptr_t>(ex->down_bias) % 2)
         LLMIE_UNSUPPORTED("%s: a bias is not 2-byte aligned", who);
     return LLMIE_OK;
 }
 
+// llmie_moe_route / _route_ex behind their NULL checks: the entry's name and the router bias (null: llmie_moe_route) are what they differ in
+int moe_route_entry(const char *who, const MoeRouteArgs &r, unsigned flags, llmie_dtype dtype, llmie_stream stream) {
+    if (int rc = moe_shape_check(who, MoeCall{r.rows, r.H, 64, r.E, r.k})) return rc;
+    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: fp16 activations only", who);
+    if (mis16(r.x) || mis16(r.router)) LLMIE_UNSUPPORTED("%s: x / router not 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(r.bias) % 2) LLMIE_UNSUPPORTED("%s: router_bias not 2-byte aligned", who);
+    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "%s: unknown flags 0x%x", who, flags);
+    moe_route_launch(r, as_stream(stream));
+    return launch_status(who);
+}
+
+}  // namespace
+}  // namespace llmie
+
+using namespace llmie;
+
+extern "C" size_t llmie_moe_workspace_bytes(int max_rows, int hidden, int inter, int experts, int top_k) {
+    const MoeCall c{max_rows, hidden, inter, experts, top_k, 0, LLMIE_W_F16, false};
+    return moe_shape_check("moe_workspace_bytes", c) ? 0 : moe_cover_carve(c).bytes;
+}
+
+extern "C" const char *llmie_moe_ffn_plan(int rows, int hidden, int inter, int experts, int top_k, unsigned flags) {
+    return moe_plan_line("moe_ffn_plan", MoeCall{rows, hidden, inter, experts, top_k, flags, LLMIE_W_F16, false}) ? nullptr : g_moe_plan_text;
+}
+
+extern "C" const char *llmie_moe_ffn_plan_ex(int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format,
+                                             llmie_moe_act act) {
+    if (format != LLMIE_W_F16 && format != LLMIE_W_MXFP4) {
+        set_error("moe_ffn_plan_ex: expert format %d is neither LLMIE_W_F16 nor LLMIE_W_MXFP4", static_cast<int>(format));
+        return nullptr;
+    }
+    if (act != LLMIE_MOE_ACT_SWIGLU && act != LLMIE_MOE_ACT_SWIGLU_CLAMPED) {
+        set_error("moe_ffn_plan_ex: unknown act %d", static_cast<int>(act));
+        return nullptr;
+    }
+    if (moe_plan_line("moe_ffn_plan_ex", MoeCall{rows, hidden, inter, experts, top_k, flags, format, act != LLMIE_MOE_ACT_SWIGLU})) return nullptr;
+    const size_t n = strlen(g_moe_plan_text);
+    snprintf(g_moe_plan_text + n, sizeof(g_moe_plan_text) - n, " format=%s act=%s", format == LLMIE_W_MXFP4 ? "mxfp4" : "f16",
+             act == LLMIE_MOE_ACT_SWIGLU_CLAMPED ? "swiglu_clamped" : "swiglu");
+    return g_moe_plan_text;
+}
+
 extern "C" int llmie_moe_route(const void *x, const void *router, int rows, int hidden, int experts, int top_k, unsigned flags, int32_t *expert_out,
                                float *weight_out, llmie_dtype dtype, llmie_stream stream) {
     LLMIE_REQUIRE(x && router && expert_out && weight_out, "moe_route: NULL pointer");
-    if (int rc = moe_shape_check("moe_route", rows, hidden, 64, experts, top_k)) return rc;
-    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_route: fp16 activations only");
-    if (mis16(x) || mis16(router)) LLMIE_UNSUPPORTED("moe_route: x / router not 16-byte aligned");
-    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "moe_route: unknown flags 0x%x", flags);
-    MoeRouteArgs r{static_cast<const half_t *>(x), static_cast<const half_t *>(router), rows, hidden, experts, top_k,
-                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out, nullptr};
-    moe_route_launch(r, as_stream(stream));
-    return launch_status("moe_route");
+    return moe_route_entry("moe_route", MoeRouteArgs{static_cast<const half_t *>(x), static_cast<const half_t *>(router), rows, hidden, experts, top_k,
+                                                     (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out, nullptr}, flags, dtype, stream);
 }
 
 // llmie_moe_route with the descriptor's router and router bias; the expert matrices are not looked at
 extern "C" int llmie_moe_route_ex(const void *x, const llmie_moe_experts *ex, int rows, int hidden, int experts, int top_k, unsigned flags,
                                   int32_t *expert_out, float *weight_out, llmie_dtype dtype, llmie_stream stream) {
     LLMIE_REQUIRE(x && ex && ex->router && expert_out && weight_out, "moe_route_ex: NULL pointer");
-    if (int rc = moe_shape_check("moe_route_ex", rows, hidden, 64, experts, top_k)) return rc;
-    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("moe_route_ex: fp16 activations only");
-    if (mis16(x) || mis16(ex->router)) LLMIE_UNSUPPORTED("moe_route_ex: x / router not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(ex->router_bias) % 2) LLMIE_UNSUPPORTED("moe_route_ex: router_bias not 2-byte aligned");
-    LLMIE_REQUIRE(!(flags & ~kMoeFlags), "moe_route_ex: unknown flags 0x%x", flags);
-    MoeRouteArgs r{static_cast<const half_t *>(x), static_cast<const half_t *>(ex->router), rows, hidden, experts, top_k,
-                   (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out, static_cast<const half_t *>(ex->router_bias)};
-    moe_route_launch(r, as_stream(stream));
-    return launch_status("moe_route_ex");
+    return moe_route_entry("moe_route_ex", MoeRouteArgs{static_cast<const half_t *>(x), static_cast<const half_t *>(ex->router), rows, hidden, experts, top_k,
+                                                        (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0, expert_out, weight_out,
+                                                        static_cast<const half_t *>(ex->router_bias)}, flags, dtype, stream);
 }
 
-// would llmie_moe_ffn / _ex take this shape and these flags?  The code and the message under `who`; nothing is launched
-int llmie::moe_call_check(const char *who, int rows, int hidden, int inter, int experts, int top_k, unsigned flags, llmie_weight_format format) {
-    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
-    MoePlan p;
-    return plan_moe(who, rows, hidden, inter, experts, top_k, flags, format, &p);
+int llmie::moe_call_check(const char *who, const MoeCall &c, MoePlan *plan) {
+    MoePlan own;
+    if (int rc = moe_shape_check(who, c)) return rc;
+    return plan_moe(who, c, plan ? plan : &own);
 }
 // would the entries take this descriptor (llmie_decoder_moe_attach_ex checks every sparse layer's)?
 int llmie::moe_experts_ok(const char *who, const llmie_moe_experts *ex) {
@@ -892,113 +926,99 @@ int llmie::moe_experts_ok(const char *who, const llmie_moe_experts *ex) {
     return moe_experts_aligned(who, ex);
 }
 
+// llmie_moe_ffn / _ex = prepare + every stage
+static int moe_ffn_entry(const char *who, const MoeCall &shape, const MoeOperands &o, llmie_stream stream) {
+    MoePrepared m;
+    if (int rc = moe_prepare(who, shape, o, nullptr, &m)) return rc;
+    return moe_launch(m, MOE_STAGE_ALL, as_stream(stream));
+}
+
 extern "C" int llmie_moe_ffn(const void *x, const void *router, const void *gate_up, const void *down, const void *resid, void *y, int rows,
                              int hidden, int inter, int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes,
                              llmie_dtype dtype, llmie_stream stream) {
     llmie_moe_experts ex{};   // fp16, no biases, plain SwiGLU
     ex.format = LLMIE_W_F16, ex.router = router, ex.gate_up = gate_up, ex.down = down, ex.act = LLMIE_MOE_ACT_SWIGLU;
-    return moe_ffn_stages("moe_ffn", x, &ex, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
-                          MOE_STAGE_ROUTE | MOE_STAGE_GATE_UP | MOE_STAGE_DOWN, stream);
+    return moe_ffn_entry("moe_ffn", MoeCall{rows, hidden, inter, experts, top_k, flags}, MoeOperands{x, resid, y, &ex, workspace, workspace_bytes, dtype},
+                         stream);
 }
 
 extern "C" int llmie_moe_ffn_ex(const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter, int experts,
                                 int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, llmie_stream stream) {
-    return moe_ffn_stages("moe_ffn_ex", x, ex, resid, y, rows, hidden, inter, experts, top_k, flags, workspace, workspace_bytes, dtype,
-                          MOE_STAGE_ROUTE | MOE_STAGE_GATE_UP | MOE_STAGE_DOWN, stream);
+    return moe_ffn_entry("moe_ffn_ex", MoeCall{rows, hidden, inter, experts, top_k, flags}, MoeOperands{x, resid, y, ex, workspace, workspace_bytes, dtype},
+                         stream);
 }
 
-// llmie_moe_ffn / _ex, or some of its stages (the engine accounts them under three op kinds): every check is made for every stage.
-// fp16 experts without a bias under plain SwiGLU launch the instantiations llmie_moe_ffn always launched
-int llmie::moe_ffn_stages(const char *who, const void *x, const llmie_moe_experts *ex, const void *resid, void *y, int rows, int hidden, int inter,
-                          int experts, int top_k, unsigned flags, void *workspace, size_t workspace_bytes, llmie_dtype dtype, unsigned stages,
-                          llmie_stream stream) {
-    LLMIE_REQUIRE(x && y, "%s: NULL pointer", who);
+int llmie::moe_prepare(const char *who, const MoeCall &shape, const MoeOperands &o, const MoePlan *planned, MoePrepared *out) {
+    const llmie_moe_experts *ex = o.experts;
+    LLMIE_REQUIRE(o.x && o.y, "%s: NULL pointer", who);
     if (int rc = moe_experts_check(who, ex)) return rc;
-    if (int rc = moe_shape_check(who, rows, hidden, inter, experts, top_k)) return rc;
-    if (dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: fp16 activations only", who);
-    if (mis16(x) || mis16(resid) || mis16(y)) LLMIE_UNSUPPORTED("%s: x / router / gate_up / down / resid / y not 16-byte aligned", who);
+    if (int rc = moe_shape_check(who, shape)) return rc;
+    if (o.dtype != LLMIE_F16) LLMIE_UNSUPPORTED("%s: fp16 activations only", who);
+    if (mis16(o.x) || mis16(o.resid) || mis16(o.y)) LLMIE_UNSUPPORTED("%s: x / router / gate_up / down / resid / y not 16-byte aligned", who);
     if (int rc = moe_experts_aligned(who, ex)) return rc;
-    const void *router = ex->router;
-    const bool mx4 = ex->format == LLMIE_W_MXFP4;
-    const bool plain = !mx4 && !ex->gate_up_bias && !ex->down_bias && ex->act == LLMIE_MOE_ACT_SWIGLU;
-    MoePlan p;
-    if (int rc = plan_moe(who, rows, hidden, inter, experts, top_k, flags, ex->format, &p)) return rc;
-    if (!workspace || workspace_bytes < p.bytes || reinterpret_cast<uintptr_t>(workspace) % 256) {
-        set_error("%s: workspace missing, too small or not 256-byte aligned (%zu < %zu)", who, workspace ? workspace_bytes : size_t(0), p.bytes);
+    MoeCall c = shape;
+    c.format = ex->format, c.ex = moe_epilogue_live(*ex);
+    MoePlan &p = out->plan;
+    if (planned && planned->call.format == c.format && planned->ex == c.ex) p = *planned;   // (a layer whose epilogue differs is planned here)
+    else if (int rc = plan_moe(who, c, &p)) return rc;
+    if (!o.workspace || o.workspace_bytes < p.ws.bytes || reinterpret_cast<uintptr_t>(o.workspace) % 256) {
+        set_error("%s: workspace missing, too small or not 256-byte aligned (%zu < %zu)", who, o.workspace ? o.workspace_bytes : size_t(0), p.ws.bytes);
         return LLMIE_ERR_WORKSPACE;
     }
-    char *base = static_cast<char *>(workspace);
-    hipStream_t st = as_stream(stream);
-    MoeFfnArgs a{};
-    a.x = static_cast<const half_t *>(x), a.gate_up = static_cast<const half_t *>(ex->gate_up), a.down = static_cast<const half_t *>(ex->down);
-    a.resid = static_cast<const half_t *>(resid), a.y = static_cast<half_t *>(y), a.act = reinterpret_cast<half_t *>(base + p.act);
-    a.expert = reinterpret_cast<const int32_t *>(base + p.expert), a.weight = reinterpret_cast<const float *>(base + p.weight);
-    a.rows = rows, a.H = hidden, a.Ie = inter, a.E = experts, a.k = top_k, a.pairs = p.pairs;
-    a.hdr = reinterpret_cast<const int32_t *>(base), a.tile_expert = reinterpret_cast<const int32_t *>(base + p.tile_expert);
-    a.tile_pairs = reinterpret_cast<const int32_t *>(base + p.tile_pairs), a.d = reinterpret_cast<float *>(base + p.d);
+    char *base = static_cast<char *>(o.workspace);
+    MoeLaunchArgs *la = new (out->args) MoeLaunchArgs{};
+    MoeFfnArgs &a = la->a;
+    a.x = static_cast<const half_t *>(o.x), a.gate_up = static_cast<const half_t *>(ex->gate_up), a.down = static_cast<const half_t *>(ex->down);
+    a.resid = static_cast<const half_t *>(o.resid), a.y = static_cast<half_t *>(o.y), a.act = reinterpret_cast<half_t *>(base + p.ws.act);
+    a.expert = reinterpret_cast<const int32_t *>(base + p.ws.expert), a.weight = reinterpret_cast<const float *>(base + p.ws.weight);
+    a.rows = c.rows, a.H = c.H, a.Ie = c.Ie, a.E = c.E, a.k = c.k, a.pairs = p.pairs;
+    a.hdr = reinterpret_cast<const int32_t *>(base), a.tile_expert = reinterpret_cast<const int32_t *>(base + p.ws.tile_expert);
+    a.tile_pairs = reinterpret_cast<const int32_t *>(base + p.ws.tile_pairs), a.d = reinterpret_cast<float *>(base + p.ws.d);
     a.gate_up_scale = static_cast<const uint8_t *>(ex->gate_up_scale), a.down_scale = static_cast<const uint8_t *>(ex->down_scale);
     a.gate_up_bias = static_cast<const half_t *>(ex->gate_up_bias), a.down_bias = static_cast<const half_t *>(ex->down_bias);
     a.act_kind = static_cast<int>(ex->act), a.alpha = ex->alpha, a.limit = ex->limit;
-    MoeRouteArgs r{a.x, static_cast<const half_t *>(router), rows, hidden, experts, top_k, (flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0,
-                   reinterpret_cast<int32_t *>(base + p.expert), reinterpret_cast<float *>(base + p.weight), static_cast<const half_t *>(ex->router_bias)};
+    la->r = MoeRouteArgs{a.x, static_cast<const half_t *>(ex->router), c.rows, c.H, c.E, c.k, (c.flags & LLMIE_MOE_SOFTMAX_ALL) ? 1 : 0,
+                         reinterpret_cast<int32_t *>(base + p.ws.expert), reinterpret_cast<float *>(base + p.ws.weight),
+                         static_cast<const half_t *>(ex->router_bias)};
+    return LLMIE_OK;
+}
+
+// the stages of a prepared call (the engine accounts them under three op kinds).  fp16 experts without a bias under plain SwiGLU
+// (plan.ex false) launch the instantiations llmie_moe_ffn always launched
+int llmie::moe_launch(const MoePrepared &m, unsigned stages, hipStream_t st) {
+    const MoePlan &p = m.plan;
+    const MoeLaunchArgs &la = *reinterpret_cast<const MoeLaunchArgs *>(m.args);
+    const MoeFfnArgs &a = la.a;
+    const bool mx4 = p.call.format == LLMIE_W_MXFP4, gemv = p.route == MOE_GEMV;
+    const dim3 g1(p.gate_up_grid[0], p.gate_up_grid[1]), g2(p.down_grid[0], p.down_grid[1]), g3(p.combine_grid[0], p.combine_grid[1]);
     if (stages & MOE_STAGE_ROUTE) {
-        moe_route_launch(r, st);
+        moe_route_launch(la.r, st);
         if (int rc = launch_status("moe_ffn(route)")) return rc;
     }
-    const dim3 g1(p.gate_up_grid[0], p.gate_up_grid[1]), g2(p.down_grid[0], p.down_grid[1]), g3(p.combine_grid[0], p.combine_grid[1]);
-// one launch of KERNEL<N, EX> for the XC the K needs; EX = !plain
-#define LLMIE_MOE_GEMV(KERNEL, K, GRID)                                                      \
-    switch (moe_xc(K)) {                                                                     \
-        case 1: if (plain) KERNEL<1, false><<<GRID, 256, 0, st>>>(a); else KERNEL<1, true><<<GRID, 256, 0, st>>>(a); break; \
-        case 2: if (plain) KERNEL<2, false><<<GRID, 256, 0, st>>>(a); else KERNEL<2, true><<<GRID, 256, 0, st>>>(a); break; \
-        case 4: if (plain) KERNEL<4, false><<<GRID, 256, 0, st>>>(a); else KERNEL<4, true><<<GRID, 256, 0, st>>>(a); break; \
-        default: if (plain) KERNEL<8, false><<<GRID, 256, 0, st>>>(a); else KERNEL<8, true><<<GRID, 256, 0, st>>>(a); break; \
-    }
-#define LLMIE_MOE_MX4_GEMV(KERNEL, K, GRID)                        \
-    switch (moe_mx4_cfg(K)) {                                      \
-        case 0: KERNEL<1, 1><<<GRID, 256, 0, st>>>(a); break;      \
-        case 1: KERNEL<2, 1><<<GRID, 256, 0, st>>>(a); break;      \
-        case 2: KERNEL<2, 2><<<GRID, 256, 0, st>>>(a); break;      \
-        default: KERNEL<2, 4><<<GRID, 256, 0, st>>>(a); break;     \
-    }
-    if (p.route == MOE_GEMV) {
+    if (gemv) {
         if (stages & MOE_STAGE_GATE_UP) {
-            if (mx4) LLMIE_MOE_MX4_GEMV(moe_mx4_gemv_gate_up_kernel, hidden, g1)
-            else LLMIE_MOE_GEMV(moe_gemv_gate_up_kernel, hidden, g1)
+            if (mx4) moe_mx4_gemv_dispatch(p.gate_up_cfg, [&](auto xb, auto kw) { moe_mx4_gemv_gate_up_kernel<xb(), kw()><<<g1, 256, 0, st>>>(a); });
+            else moe_gemv_dispatch(p.gate_up_cfg, p.ex, [&](auto xc, auto ex) { moe_gemv_gate_up_kernel<xc(), ex()><<<g1, 256, 0, st>>>(a); });
+            if (int rc = launch_status("moe_ffn(gate_up gemv)")) return rc;
         }
-        if (int rc = launch_status("moe_ffn(gate_up gemv)")) return rc;
         if (stages & MOE_STAGE_DOWN) {
-            if (mx4) LLMIE_MOE_MX4_GEMV(moe_mx4_gemv_down_kernel, inter, g2)
-            else LLMIE_MOE_GEMV(moe_gemv_down_kernel, inter, g2)
+            if (mx4) moe_mx4_gemv_dispatch(p.down_cfg, [&](auto xb, auto kw) { moe_mx4_gemv_down_kernel<xb(), kw()><<<g2, 256, 0, st>>>(a); });
+            else moe_gemv_dispatch(p.down_cfg, p.ex, [&](auto xc, auto ex) { moe_gemv_down_kernel<xc(), ex()><<<g2, 256, 0, st>>>(a); });
+            return launch_status("moe_ffn(down gemv)");
         }
-        return launch_status("moe_ffn(down gemv)");
+        return LLMIE_OK;
     }
-#undef LLMIE_MOE_GEMV
-#undef LLMIE_MOE_MX4_GEMV
     if (stages & MOE_STAGE_GATE_UP) {
-        moe_plan_kernel<<<1, 256, 0, st>>>(a.expert, p.pairs, experts, p.rt, reinterpret_cast<int32_t *>(base), reinterpret_cast<int32_t *>(base + p.tile_expert),
-                                           reinterpret_cast<int32_t *>(base + p.tile_pairs), p.tiles);
+        moe_plan_kernel<<<1, 256, 0, st>>>(a.expert, p.pairs, a.E, p.rt, const_cast<int32_t *>(a.hdr), const_cast<int32_t *>(a.tile_expert),
+                                           const_cast<int32_t *>(a.tile_pairs), p.tiles);
         if (int rc = launch_status("moe_ffn(plan)")) return rc;
-        if (mx4) {
-            if (p.rt == 4) moe_mx4_grouped_kernel<4, true><<<g1, 256, 0, st>>>(a);
-            else moe_mx4_grouped_kernel<1, true><<<g1, 256, 0, st>>>(a);
-        } else if (plain) {
-            if (p.rt == 4) moe_grouped_kernel<4, true, false><<<g1, 256, 0, st>>>(a);
-            else moe_grouped_kernel<1, true, false><<<g1, 256, 0, st>>>(a);
-        } else {
-            if (p.rt == 4) moe_grouped_kernel<4, true, true><<<g1, 256, 0, st>>>(a);
-            else moe_grouped_kernel<1, true, true><<<g1, 256, 0, st>>>(a);
-        }
+        if (mx4) moe_rt_dispatch(p.rt, [&](auto rt) { moe_mx4_grouped_kernel<rt(), true><<<g1, 256, 0, st>>>(a); });
+        else moe_ex_dispatch(p.ex, [&](auto ex) { moe_rt_dispatch(p.rt, [&](auto rt) { moe_grouped_kernel<rt(), true, ex()><<<g1, 256, 0, st>>>(a); }); });
         if (int rc = launch_status("moe_ffn(gate_up grouped)")) return rc;
     }
     if (stages & MOE_STAGE_DOWN) {
-        if (mx4) {
-            if (p.rt == 4) moe_mx4_grouped_kernel<4, false><<<g2, 256, 0, st>>>(a);
-            else moe_mx4_grouped_kernel<1, false><<<g2, 256, 0, st>>>(a);
-        } else {
-            if (p.rt == 4) moe_grouped_kernel<4, false, false><<<g2, 256, 0, st>>>(a);
-            else moe_grouped_kernel<1, false, false><<<g2, 256, 0, st>>>(a);
-        }
+        if (mx4) moe_rt_dispatch(p.rt, [&](auto rt) { moe_mx4_grouped_kernel<rt(), false><<<g2, 256, 0, st>>>(a); });
+        else moe_rt_dispatch(p.rt, [&](auto rt) { moe_grouped_kernel<rt(), false, false><<<g2, 256, 0, st>>>(a); });
         if (int rc = launch_status("moe_ffn(down grouped)")) return rc;
         moe_combine_kernel<<<g3, kMoeCombineThreads, 0, st>>>(a);
         return launch_status("moe_ffn(combine)");
