@@ -294,6 +294,51 @@ const char *llmie_decoder_mha_sink_plan(llmie_dtype dtype, int kv_e4m3, int batc
                                         unsigned long long residues, long long workspace_bytes, int window, int sinks,
                                         int *status);
 
+/* ABI 3 (an addition; no reference counterpart).  QK-norm: a learned RMSNorm over head_size on every q head and every k head,
+ * between the QKV projection and RoPE (Qwen3 `self_attn.q_norm` / `self_attn.k_norm`, shape [head_size]).  For a head row
+ * x[0..hs) of the projection's output (fp16), a gamma g[0..hs) (fp16) and eps >= 0:
+ *        ss  = sum_d float(x_d)^2                         fp32, in ONE fixed order (below)
+ *        inv = 1 / sqrt(ss / hs + eps)                    fp32
+ *        n_d = fp16( (float(x_d) * inv) * float(g_d) )    one rounding
+ * It is applied to every q head with q_gamma and to every k head with k_gamma, never to v, BEFORE RoPE: the rotation reads the fp16
+ * value n_d.  A Gemma-style (1 + w) gamma is the loader's business: it passes 1 + w.  QK-norm together with a QKV bias is refused
+ * with LLMIE_ERR_UNSUPPORTED (no checkpoint has both, and decode and prefill add the bias on different sides of RoPE).
+ * Summation order: within each aligned group of 8 consecutive elements ss_g = fmaf(x, x, ss_g) in ascending d, from 0; the hs / 8
+ * group sums are combined by a butterfly over the bits of the group index, lowest bit first, with plain fp32 adds.  The operator,
+ * the fused decode kernel (both cache formats) and the prefill kernel follow it, so they agree to the bit.
+ * The gammas are DEVICE arrays read at every launch: a captured step replays with new values.  NaN / Inf gammas: results
+ * unspecified; the call stays in bounds and ends.
+ *
+ * llmie_qk_norm: the operator on its own, in place on packed rows [rows, (head_num + 2 kv_head_num) * head_size]; the v columns are
+ * not touched.  fp16, head_size 64 / 128.  The per-kernel path runs it between llmie_linear and llmie_qkv_bias_transpose_rope.
+ * LLMIE_ERR_INVALID_ARG: NULL pointers; non-positive sizes; head_num % kv_head_num != 0; eps < 0 or NaN; qkv or a gamma not
+ * 16-byte aligned.  LLMIE_ERR_UNSUPPORTED: LLMIE_F32; other head sizes.  Nothing is written in either case.
+ *
+ * llmie_decoder_mha_qknorm: llmie_decoder_mha_sink's operands and behaviour plus the gammas (device, [head_size] each, nullable
+ * together: both NULL is that entry's call, bit for bit; exactly one NULL, a gamma not 16-byte aligned or qk_eps < 0 / NaN is
+ * LLMIE_ERR_INVALID_ARG).  With gammas the output, the caches and the pools are those of llmie_qk_norm on qkv followed by
+ * llmie_decoder_mha_sink(head_sink = NULL), bit for bit.  Supported with gammas: fp16 activations, head_size 64 / 128,
+ * head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4}), dense or paged, tickets or separate merge.  With gammas each of a QKV
+ * bias, window > 0, head_sink != NULL, fp32, head size 32 / 256, ratio 8 over e4m3 and operands that would fall to the generic
+ * kernel (unaligned buffers) is LLMIE_ERR_UNSUPPORTED and writes nothing.  llmie_decoder_mha_qknorm_plan:
+ * llmie_decoder_mha_sink_plan plus the form bit LLMIE_ATTN_QK_NORM (the three older plan queries ignore the bit); the line gains
+ * " qk_norm" when it is set -- same grid, slots and merge, the QKN instantiation of the split kernel. */
+#define LLMIE_ATTN_QK_NORM 1024u /* q_gamma / k_gamma given */
+int llmie_qk_norm(void *qkv /* [rows, (head_num + 2 kv_head_num) * head_size], in place */, int rows, int head_num, int kv_head_num,
+                  int head_size, const void *q_gamma, const void *k_gamma /* device, [head_size] each */, float eps,
+                  llmie_dtype dtype, llmie_stream stream);
+int llmie_decoder_mha_qknorm(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer,
+                             int batch, int head_num, int kv_head_num, int head_size, int max_seq_len,
+                             const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes, const void *rope_table,
+                             int rotary_dim, const int32_t *block_table, int max_pages, int num_pages, int window, int sinks,
+                             int32_t *tickets, int kv_e4m3, float k_scale, float v_scale, const float *head_sink /* device, [head_num] */,
+                             const void *q_gamma, const void *k_gamma /* device [head_size], nullable together */, float qk_eps,
+                             llmie_dtype dtype, llmie_stream stream);
+const char *llmie_decoder_mha_qknorm_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                          int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                          unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                          int *status);
+
 /* ABI 3 (an addition; host only, no device access).  RoPE frequency scaling: the one function that computes a (cos, sin) table.
  * cos_sin_out: host, [max_pos][head_size/2] pairs (cos, sin), the layout of llmie_decoder_mha_rope's rope_table.  For pair
  * j < rotary_dim/2 with f_j = rotary_base^(-2j/rotary_dim) the entry at position p is (cos(p f'_j), sin(p f'_j)) a, where
@@ -1065,6 +1110,24 @@ int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer_window /* 
 #define LLMIE_PLAN_HEAD_SINK 4096u /* head sinks are set (llmie_decoder_set_head_sinks) */
 int llmie_decoder_set_head_sinks(llmie_decoder *dec, const float *head_sink_dev /* device, [num_layers, head_num]; NULL clears */);
 int llmie_decoder_set_rope_scaling(llmie_decoder *dec, const llmie_rope_scaling *scaling /* host; NULL = the create-time table */);
+
+/* ABI 3 (an addition; llmie_decoder_config is not touched).  QK-norm (stated at llmie_qk_norm) on an engine: q_gamma_dev / k_gamma_dev =
+ * DEVICE arrays [num_layers, head_size] of fp16 (row l = layer l), 16-byte aligned; both NULL clears.  The pointers and eps are kept
+ * on the engine -- the arrays must stay alive while they are set -- and read when a call's attention launch is built, in the pattern
+ * of llmie_decoder_set_head_sinks; the VALUES are read on the device at every launch.  From then on every decode entry runs the QKN
+ * instantiation of its attention launch, and every prefill entry plans the QKV forms without the RoPE epilogue (plain, plain_e4m3,
+ * unpack_plain, splitk: what LLMIE_SW_NO_QKV_ROPE_FUSION plans) and normalises in the RoPE + append launch in front of the flash
+ * kernel; the spec, score, beam, LoRA and MoE sequences built on them follow.  llmie_decoder_set_qk_norm(dec, NULL, NULL, eps)
+ * restores today's bits.  LLMIE_ERR_INVALID_ARG: exactly one NULL; an array not 16-byte aligned; eps < 0 or NaN.
+ * LLMIE_ERR_UNSUPPORTED: an engine whose decode attention has no such form (fp32; head sizes other than 64 / 128; head ratios other
+ * than 1 / 2 / 4 / 8; with an e4m3 cache also ratio 8); a layer with a QKV bias; a window or head sinks set on the engine -- and
+ * llmie_decoder_set_window / llmie_decoder_set_head_sinks with a non-NULL argument refuse while QK-norm is set.  A call whose
+ * operands send its attention to the generic kernel (unaligned buffers) fails with LLMIE_ERR_UNSUPPORTED while QK-norm is set and
+ * writes nothing.  llmie_decoder_plan_name and llmie_decoder_prefill_layer_plan answer for such a call under LLMIE_PLAN_QK_NORM
+ * (decode: same sequences; NULL for an engine set_qk_norm refuses; the layer plan ends in " qk_norm=1"). */
+#define LLMIE_PLAN_QK_NORM 8192u /* QK-norm is set (llmie_decoder_set_qk_norm) */
+int llmie_decoder_set_qk_norm(llmie_decoder *dec, const void *q_gamma_dev, const void *k_gamma_dev /* device, [num_layers, head_size] fp16;
+                              both NULL clears */, float eps);
 
 /* ABI 3 (an addition).  Mixture-of-experts FFN, Mixtral / Qwen-MoE semantics: every row is routed to top_k of `experts` expert FFNs.
  * fp16 activations and fp16 experts only.  Operands (device, 16-byte aligned): x [rows, hidden]; router Wr [experts, hidden];

@@ -100,6 +100,11 @@ _SIGS = {
     "llmie_decoder_mha_sink": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _vp,
                                _i, _f, _f, _vp, _i, _vp],
     "llmie_decoder_mha_sink_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _i, _i, _vp],
+    "llmie_qk_norm": [_vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp],
+    "llmie_decoder_mha_qknorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _vp,
+                                 _i, _f, _f, _vp, _vp, _vp, _f, _i, _vp],
+    "llmie_decoder_mha_qknorm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_uint, _i, _i, C.c_ulonglong, C.c_longlong, _i, _i, _vp],
+    "llmie_decoder_set_qk_norm": [_vp, _vp, _vp, _f],
     "llmie_rope_table_fill": [_vp, _i, _i, _i, _f, _vp],
     "llmie_decoder_set_head_sinks": [_vp, _vp],
     "llmie_decoder_set_rope_scaling": [_vp, _vp],
@@ -197,6 +202,7 @@ _RESTYPES = {
     "llmie_decoder_mha_plan": C.c_char_p,
     "llmie_decoder_mha_window_plan": C.c_char_p,
     "llmie_decoder_mha_sink_plan": C.c_char_p,
+    "llmie_decoder_mha_qknorm_plan": C.c_char_p,
     "llmie_decoder_plan_name": C.c_char_p,
     "llmie_decoder_prefill_layer_plan": C.c_char_p,
     "llmie_target_arch": C.c_char_p,
@@ -312,7 +318,7 @@ def gemm256_tiles(form, operands, M, N, K):
 
 
 ATTN_FORMS = {"step_dev": 1, "ragged": 2, "bias": 4, "rope": 8, "tickets": 16, "slabs": 32, "paged": 64, "x32": 128, "bad_scales": 256,
-              "head_sink": 512}
+              "head_sink": 512, "qk_norm": 1024}
 ATTN_OPERANDS = ("qkv", "bias", "k", "v", "slab", "wf", "wh", "slab_stride")
 
 
@@ -361,6 +367,22 @@ def decoder_mha_sink_plan(dtype, batch, head_num, kv_head_num, head_size, max_se
     t = lib().llmie_decoder_mha_sink_plan(dtype, int(kv_e4m3), batch, head_num, kv_head_num, head_size, max_seq_len, step, f,
                                           max_pages, num_pages, r, -1 if workspace_bytes is None else workspace_bytes, window, sinks,
                                           C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def decoder_mha_qknorm_plan(dtype, batch, head_num, kv_head_num, head_size, max_seq_len, window=0, sinks=0, step=-1, kv_e4m3=False,
+                            forms=(), max_pages=0, num_pages=0, residues=None, workspace_bytes="exact"):
+    """decoder_mha_sink_plan plus the form "qk_norm" (llmie_decoder_mha_qknorm_plan): with it the line ends in " qk_norm" -- the same
+    grid, slots and merge on the QKN instantiation of the split kernel -- or the call is refused where no such form exists (a QKV bias,
+    a window, a head sink, fp32, head sizes other than 64 / 128, ratio 8 over e4m3, unaligned operands).  No device needed."""
+    f = sum(ATTN_FORMS[n] for n in forms)
+    r = sum((v & 15) << (4 * ATTN_OPERANDS.index(k)) for k, v in (residues or {}).items())
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_decoder_mha_qknorm_plan(dtype, int(kv_e4m3), batch, head_num, kv_head_num, head_size, max_seq_len, step, f,
+                                            max_pages, num_pages, r, -1 if workspace_bytes is None else workspace_bytes, window, sinks,
+                                            C.addressof(status))
     return (t.decode() if t is not None else None), status.value
 
 
@@ -552,6 +574,34 @@ def decoder_mha_sink(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv_h
                                         rotary_dim, _p(block_table), block_table.shape[1] if block_table is not None else 0,
                                         k_cache.shape[1] if block_table is not None else 0, window, sinks, _p(tickets),
                                         int(kv_scales is not None), ks, vs, _p(head_sink), _dt(qkv), _st()), "decoder_mha_sink")
+    return out
+
+
+def qk_norm(qkv, head_num, kv_head_num, q_gamma, k_gamma, eps=1e-6):
+    """per-head RMSNorm of the q and k heads of packed rows, in place (llmie_qk_norm; Qwen3 q_norm / k_norm): qkv = fp16 device tensor
+    [rows, head_num + 2 kv_head_num, head_size]; q_gamma / k_gamma = fp16 device tensors [head_size].  The v columns are not touched."""
+    rows, hs = qkv.shape[0], qkv.shape[-1]
+    _check(lib().llmie_qk_norm(_p(qkv), rows, head_num, kv_head_num, hs, _p(q_gamma), _p(k_gamma), eps, _dt(qkv), _st()), "qk_norm")
+    return qkv
+
+
+def decoder_mha_qknorm(qkv, qkv_bias, k_cache, v_cache, out, layer, head_num, kv_head_num, ctx_len, workspace, rope_table,
+                       rotary_dim, max_seq_len, q_gamma, k_gamma, qk_eps=1e-6, head_sink=None, window=0, sinks=0, block_table=None,
+                       tickets=None, kv_scales=None):
+    """decoder_mha_sink plus QK-norm (llmie_decoder_mha_qknorm): q_gamma / k_gamma = device tensors [head_size] in the activation
+    type, or both None = decoder_mha_sink's call.  With gammas the result is qk_norm on qkv followed by decoder_mha_sink, bit for bit."""
+    batch, hs = qkv.shape[0], qkv.shape[-1]
+    ks, vs = kv_scales if kv_scales is not None else (1.0, 1.0)
+    for g in (q_gamma, k_gamma):
+        if g is not None:
+            assert g.dtype == qkv.dtype and g.numel() == hs, "q_gamma / k_gamma: [head_size] in the activation type"
+    _check(lib().llmie_decoder_mha_qknorm(_p(qkv), _p(qkv_bias), _p(k_cache), _p(v_cache), _p(out), layer, batch, head_num,
+                                          kv_head_num, hs, max_seq_len, _p(ctx_len), _p(workspace),
+                                          0 if workspace is None else workspace.numel() * workspace.element_size(), _p(rope_table),
+                                          rotary_dim, _p(block_table), block_table.shape[1] if block_table is not None else 0,
+                                          k_cache.shape[1] if block_table is not None else 0, window, sinks, _p(tickets),
+                                          int(kv_scales is not None), ks, vs, _p(head_sink), _p(q_gamma), _p(k_gamma), qk_eps,
+                                          _dt(qkv), _st()), "decoder_mha_qknorm")
     return out
 
 
@@ -1024,6 +1074,17 @@ class Decoder:
         _check(lib().llmie_decoder_set_head_sinks(self.handle, _p(head_sink)), "decoder_set_head_sinks")
         self._head_sinks_keep = head_sink
 
+    def set_qk_norm(self, q_gamma, k_gamma, eps=1e-6):
+        """QK-norm (llmie_decoder_set_qk_norm; Qwen3 q_norm / k_norm): fp16 device tensors [num_layers, head_size] each, kept alive by
+        this object and read on the device at every attention launch; both None clears"""
+        import torch
+        for name, g in (("q_gamma", q_gamma), ("k_gamma", k_gamma)):
+            if g is not None and (g.dtype != torch.float16 or tuple(g.shape) != (self.cfg.num_layers, self.cfg.head_size)):
+                raise LlmieError("set_qk_norm: %s needs a float16 tensor [num_layers=%d, head_size=%d]"
+                                 % (name, self.cfg.num_layers, self.cfg.head_size))
+        _check(lib().llmie_decoder_set_qk_norm(self.handle, _p(q_gamma), _p(k_gamma), eps), "decoder_set_qk_norm")
+        self._qk_norm_keep = (q_gamma, k_gamma)
+
     def set_rope_scaling(self, scaling):
         """RoPE frequency scaling (llmie_decoder_set_rope_scaling): refills and uploads the engine's (cos, sin) table -- one synchronous
         copy, not inside a graph capture.  scaling: see rope_scaling(); None restores the create-time table"""
@@ -1137,6 +1198,7 @@ LORA_MAX_KSPLIT = 8     # LLMIE_LORA_MAX_KSPLIT
 PLAN_LORA = 1024        # LLMIE_PLAN_LORA
 PLAN_WINDOW = 2048      # LLMIE_PLAN_WINDOW
 PLAN_HEAD_SINK = 4096   # LLMIE_PLAN_HEAD_SINK
+PLAN_QK_NORM = 8192     # LLMIE_PLAN_QK_NORM
 PLAN_PAGED, PLAN_RAGGED, PLAN_HIDDEN_MISALIGNED = 1, 2, 4   # LLMIE_PLAN_* call flags of decoder_plan_name
 
 

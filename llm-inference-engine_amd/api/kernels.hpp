@@ -409,6 +409,41 @@ void launchDecoderSinkAttention(TensorWrapper<T> *qkv_buf, const T *qkv_bias, in
                                       head_sink ? head_sink->data : nullptr, llmie_api::dtype_of<T>(), llmie_api::st()));
 }
 
+// No reference launcher: per-head RMSNorm of the q and k heads of packed rows, in place (include/llmie.h llmie_qk_norm; Qwen3 q_norm /
+// k_norm): qkv_buf [rows, head_num + 2 kv_head_num, head_size], q_gamma / k_gamma [head_size] on the device.  The v heads are not
+// touched.  Runs between the QKV projection and launchFusedQKVAddBiasAndTransposeAndRope in a per-kernel loop.
+template <typename T>
+void launchQkNorm(TensorWrapper<T> *qkv_buf, int kv_head_num, TensorWrapper<T> *q_gamma, TensorWrapper<T> *k_gamma, float eps) {
+    const int rows = qkv_buf->shape[0], head_num = qkv_buf->shape[1] - 2 * kv_head_num, head_size = qkv_buf->shape[2];
+    LLM_CHECK_WITH_INFO(q_gamma->shape[0] == head_size && k_gamma->shape[0] == head_size, "q_gamma / k_gamma should be [head_size]");
+    LLMIE_CALL(llmie_qk_norm(qkv_buf->data, rows, head_num, kv_head_num, head_size, q_gamma->data, k_gamma->data, eps, llmie_api::dtype_of<T>(),
+                             llmie_api::st()));
+}
+
+// No reference launcher: launchDecoderSinkAttention with QK-norm fused in front of the rotation (include/llmie.h
+// llmie_decoder_mha_qknorm): q_gamma / k_gamma [head_size] on the device, or both null = that launcher's call.  Bit-identical to
+// launchQkNorm on qkv_buf followed by launchDecoderSinkAttention.
+template <typename T>
+void launchDecoderQkNormAttention(TensorWrapper<T> *qkv_buf, const T *qkv_bias, int layer, TensorWrapper<T> *k_cache, TensorWrapper<T> *v_cache,
+                                  TensorWrapper<int> *ctx_len, const void *rope_table, int rotary_dim, TensorWrapper<int> *block_table,
+                                  int max_seq_len, int window, int sinks, TensorWrapper<float> *head_sink, TensorWrapper<T> *q_gamma,
+                                  TensorWrapper<T> *k_gamma, float qk_eps, TensorWrapper<T> *mha_output) {
+    const int batch = qkv_buf->shape[0], qkv_head_num = qkv_buf->shape[1], head_size = qkv_buf->shape[2];
+    const int kv_head_num = k_cache->shape[2];
+    const int head_num = qkv_head_num - 2 * kv_head_num;
+    LLM_CHECK_WITH_INFO(!head_sink || head_sink->shape[0] == head_num, "head_sink should be [head_num]");
+    LLM_CHECK_WITH_INFO((!q_gamma || q_gamma->shape[0] == head_size) && (!k_gamma || k_gamma->shape[0] == head_size),
+                        "q_gamma / k_gamma should be [head_size]");
+    if (!block_table) max_seq_len = k_cache->shape[3];
+    const size_t ws = llmie_decoder_mha_workspace_bytes(batch, head_num, head_size, max_seq_len);
+    LLMIE_CALL(llmie_decoder_mha_qknorm(qkv_buf->data, qkv_bias, k_cache->data, v_cache->data, mha_output->data, layer, batch, head_num,
+                                        kv_head_num, head_size, max_seq_len, ctx_len->data, llmie_api::scratch(ws), ws, rope_table, rotary_dim,
+                                        block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                        block_table ? k_cache->shape[1] : 0, window, sinks, nullptr, 0, 1.f, 1.f,
+                                        head_sink ? head_sink->data : nullptr, q_gamma ? q_gamma->data : nullptr,
+                                        k_gamma ? k_gamma->data : nullptr, qk_eps, llmie_api::dtype_of<T>(), llmie_api::st()));
+}
+
 // No reference launcher: the page ring of windowed sequences (include/llmie.h llmie_kv_window_advance).  block_table [batch,
 // max_pages] (in / out, -1 = unmapped), cached_len [batch], new_tokens [batch] or null (one each), status [batch] (0 mapped, 1 no
 // dead page: the row is untouched, 2 past the table).  One launch, nothing read by the host.

@@ -110,8 +110,17 @@ public:
         rope_scaling = s;
         rope_dirty = true;
     }
+    // QK-norm (include/llmie.h llmie_decoder_set_qk_norm): DEVICE arrays [num_layers, head_size] of fp16 that the caller keeps alive
+    // (both null: none) and eps; set on every engine this holder creates
+    void set_qk_norm(const void *q_gamma_dev, const void *k_gamma_dev, float eps) {
+        q_gammas = q_gamma_dev, k_gammas = k_gamma_dev, qk_eps = eps;
+        qk_norm_dirty = true;
+    }
 
 private:
+    const void *q_gammas = nullptr, *k_gammas = nullptr;
+    float qk_eps = 0.f;
+    bool qk_norm_dirty = false;
     const float *head_sinks = nullptr;
     bool sinks_dirty = false;
     llmie_rope_scaling rope_scaling{};
@@ -120,7 +129,8 @@ private:
         if (!engine) return;
         if (sinks_dirty) LLMIE_CALL(llmie_decoder_set_head_sinks(engine, head_sinks));
         if (rope_dirty) LLMIE_CALL(llmie_decoder_set_rope_scaling(engine, rope_scaling.kind == LLMIE_ROPE_NONE ? nullptr : &rope_scaling));
-        sinks_dirty = rope_dirty = false;
+        if (qk_norm_dirty) LLMIE_CALL(llmie_decoder_set_qk_norm(engine, q_gammas, k_gammas, qk_eps));
+        sinks_dirty = rope_dirty = qk_norm_dirty = false;
     }
     std::vector<int> window;
     int window_sinks = 0;
@@ -249,7 +259,7 @@ public:
         sync_moe();
         window_dirty = !window.empty();
         sync_window();
-        sinks_dirty = head_sinks != nullptr, rope_dirty = rope_scaling.kind != LLMIE_ROPE_NONE;
+        sinks_dirty = head_sinks != nullptr, rope_dirty = rope_scaling.kind != LLMIE_ROPE_NONE, qk_norm_dirty = q_gammas != nullptr;
         sync_attention();
         return engine;
     }
@@ -429,6 +439,7 @@ public:
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
     void setHeadSinks(const float *head_sink_dev) { engine_holder.set_head_sinks(head_sink_dev); }
+    void setQkNorm(const void *q_gamma_dev, const void *k_gamma_dev, float eps) { engine_holder.set_qk_norm(q_gamma_dev, k_gamma_dev, eps); }
     void setRopeScaling(const llmie_rope_scaling &s) { engine_holder.set_rope_scaling(s); }
     void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 
@@ -605,6 +616,7 @@ public:
     // sliding-window attention on the fused engine (this class's other kernel sequence attends to everything)
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
     void setHeadSinks(const float *head_sink_dev) { engine_holder.set_head_sinks(head_sink_dev); }
+    void setQkNorm(const void *q_gamma_dev, const void *k_gamma_dev, float eps) { engine_holder.set_qk_norm(q_gamma_dev, k_gamma_dev, eps); }
     void setRopeScaling(const llmie_rope_scaling &s) { engine_holder.set_rope_scaling(s); }
     void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 

@@ -311,6 +311,16 @@ public:
         context_decoder->setHeadSinks(head_sink_dev);
         self_decoder->setHeadSinks(head_sink_dev);
     }
+    // QK-norm (Qwen3 `self_attn.q_norm` / `k_norm`; include/llmie.h llmie_decoder_set_qk_norm): q / k are DEVICE arrays [num_layers,
+    // head_size] of fp16, 16-byte aligned, that must stay alive while they are set; both nullptr clears.  eps: `rms_norm_eps`.  Takes
+    // effect from the next prefill / decode call of both decoders; the per-kernel loops do not normalise q and k.
+    void setQkNorm(const half *q, const half *k, float eps) {
+        LLM_CHECK_WITH_INFO((q != nullptr) == (k != nullptr), "setQkNorm: q and k gammas go together");
+        LLM_CHECK_WITH_INFO(!q || ((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs)),
+                            "setQkNorm: QK-norm needs the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        context_decoder->setQkNorm(q, k, eps);
+        self_decoder->setQkNorm(q, k, eps);
+    }
     // RoPE frequency scaling (`rope_scaling` of a config.json; include/llmie.h llmie_rope_scaling): both decoders' engines refill their
     // (cos, sin) table; kind LLMIE_ROPE_NONE goes back to the unscaled table.  One synchronous copy per engine, at its next call.
     void setRopeScaling(const llmie_rope_scaling &scaling) {

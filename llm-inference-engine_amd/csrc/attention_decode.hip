@@ -14,6 +14,7 @@
 // fill the 256 CUs even at batch 1 (7B, S=2048: 32*16 = 512 workgroups).
 // HBM-bound: algorithmic bytes = 2 * step * kvh * hs * sizeof(T) per sequence.
 #include "llmie_internal.h"
+#include "qk_norm.cuh"
 
 #include <climits>
 #include <cstdlib>
@@ -219,7 +220,10 @@ __device__ __forceinline__ float merge_splits_sink(const float *__restrict__ p, 
 // arguments (window, sinks) are the pack WinArgs = (int, int); WIN = false has an empty pack: the arguments and the code the kernel
 // had before there was a window.  SINK (compile time) adds the per-head sink logit: one more argument at the end of the pack, the
 // device array head_sink[head_num] (fp32), read where an output row is normalised (sink_finish); the streaming loop does not know it.
-template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T, bool WIN = false, bool SINK = false, typename... WinArgs>
+// QKN (compile time) adds the per-head q/k RMSNorm in front of the rotation (include/llmie.h, llmie_qk_norm; qk_norm.cuh): three more
+// arguments at the end of the pack, (const T *q_gamma, const T *k_gamma, float eps); every line of it sits behind if constexpr (QKN).
+template <typename T, int HS, int REP, int kAttnWaves = 4, int kAttnG = 8, typename KT = T, bool WIN = false, bool SINK = false, bool QKN = false,
+          typename... WinArgs>
 __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const T *__restrict__ qkv, const T *__restrict__ qkv_bias, KT *k_cache, KT *v_cache,
     float *__restrict__ part, T *__restrict__ out, int head_num, int kv_head_num, int max_seq_len,
@@ -232,8 +236,8 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const int cpw /* chunks of CHUNK tokens one workgroup walks through (online softmax across them): large batches amortise
                      the per-workgroup prologue / merge (~550 of ~1000 VALU instructions per wave at one chunk) */,
     const WinArgs... win /* WIN: window, sinks -- the query sees key j iff j >= step - window or j < sinks (and j < step);
-                            SINK: then const float *head_sink */) {
-    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0), "window, sinks, head_sink");
+                            SINK: then const float *head_sink; QKN: then const T *q_gamma, const T *k_gamma, float eps */) {
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0) + (QKN ? 3 : 0), "window, sinks, head_sink, q_gamma, k_gamma, eps");
     using G = AttnGeom<KT, HS, kAttnWaves, kAttnG>;
     using V = typename CacheVec<KT>::type;  // one 16-byte vector of cache elements
     constexpr int N = G::N, LPT = G::LPT, TPW = G::TPW, CHUNK = G::CHUNK;
@@ -371,6 +375,16 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
         load_elems<T, N>(qkv_bias ? qkv_bias + static_cast<size_t>(g * REP + r) * HS + dl * N : dummy, qbias[r]);
     load_elems<T, N>(qkv_bias ? qkv_bias + static_cast<size_t>(hk) * HS + dl * N : dummy, kbias);
     load_elems<T, N>(qkv_bias ? qkv_bias + static_cast<size_t>(hv) * HS + dl * N : dummy, vbias);
+    // QKN: this lane's slices of the two gammas (its head dims dl * N .. + N), with the other small operands
+    T qgam[QKN ? N : 1], kgam[QKN ? N : 1];
+    float qkn_eps = 0.f;
+    if constexpr (QKN) {
+        constexpr int Q0 = (WIN ? 2 : 0) + (SINK ? 1 : 0);
+        load_elems<T, N>(pack_arg<Q0>(win...) + dl * N, qgam);
+        load_elems<T, N>(pack_arg<Q0 + 1>(win...) + dl * N, kgam);
+        qkn_eps = pack_arg<Q0 + 2>(win...);
+    }
+    (void)qgam, (void)kgam, (void)qkn_eps;
     float2 csraw[N];
     if (rope) {
         const float2 *cs = rope + static_cast<size_t>(t_new) * (HS / 2) + (dl % (LPT / 2)) * N;
@@ -449,12 +463,24 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
     const float k_p2 = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, k_scale) & 0x7f800000u);
     const float k_q = FP8KV ? k_scale / k_p2 : k_scale;
     (void)k_p2;
+    // QKN: the head row this lane holds a slice of (fp16 values, as the projection stored them) -> normalised, rounded to T: the
+    // sum of squares in qk_norm.cuh's order (N = 16: the two groups of a lane differ in the group index's lowest bit, added first)
+    auto qk_normalise = [&](float (&x)[N], const T (&gam)[QKN ? N : 1]) {
+        if constexpr (QKN) {
+            float ss = qkn_group_ss(x);
+            if constexpr (N == 16) ss = ss + qkn_group_ss(x + 8);
+            const float inv = qkn_inv(qkn_lane_butterfly<LPT>(ss), HS, qkn_eps);
+#pragma unroll
+            for (int e = 0; e < N; ++e) x[e] = to_f32(qkn_apply<T>(x[e], inv, to_f32(gam[e])));
+        }
+    };
     float qf[REP][N];
 #pragma unroll
     for (int r = 0; r < REP; ++r) {
         float f[N];
 #pragma unroll
         for (int e = 0; e < N; ++e) f[e] = to_f32(qraw[r][e]);
+        qk_normalise(f, qgam);   // QKN: one sum per head
         if (rope) {
             rotate(f);
 #pragma unroll
@@ -491,6 +517,14 @@ __global__ __launch_bounds__(kAttnWaves * 64) void decode_attn_split_kernel(
         if (qs.slab) {
             load_elems<T, N>(&qkvlds[REP * HS + dl * N], kn);
             load_elems<T, N>(&qkvlds[(REP + 1) * HS + dl * N], vn);
+        }
+        if constexpr (QKN) {   // k (never v): normalised by every lane, like the rotation below
+            float f[N];
+#pragma unroll
+            for (int e = 0; e < N; ++e) f[e] = to_f32(kn[e]);
+            qk_normalise(f, kgam);
+#pragma unroll
+            for (int e = 0; e < N; ++e) kn[e] = from_f32<T>(f[e]);
         }
         if (rope) {
             float f[N];
@@ -868,6 +902,7 @@ static DecodeAttnPlan plan_attn_split(const DecodeAttnCall &c, size_t need) {
         p.grid[0] = c.step_dev ? attn_live_bound(c.max_seq_len, c.window, c.sinks, p.chunk) : attn_live_chunks(c.step, c.window, c.sinks, p.chunk).total;
     }
     p.head_sink = c.head_sink;
+    p.qk_norm = c.qk_norm;
     p.max_splits_ws = (c.max_seq_len + attn_min_chunk() - 1) / attn_min_chunk();
     p.merge = p.grid[0] > 1 && !c.tickets;
     p.merge_grid[0] = c.head_num, p.merge_grid[1] = c.batch;
@@ -890,6 +925,10 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
     if (c.window > 0 && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128))) return attn_refusal(DAREF_WINDOW);
     // ... and so does a head sink: the SINK instantiations exist where the windowed ones do
     if (c.head_sink && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128))) return attn_refusal(DAREF_HEAD_SINK);
+    // QK-norm: the QKN instantiations exist for the same activations and head sizes, without a window or a head sink; the norm runs in
+    // front of RoPE and a QKV bias is added behind it here (in front of it in the prefill kernel), so the two together are refused
+    if (c.qk_norm && (c.dtype != LLMIE_F16 || (c.head_size != 64 && c.head_size != 128) || c.bias || c.window > 0 || c.head_sink))
+        return attn_refusal(DAREF_QK_NORM);
     if (c.kv_e4m3) {
         // fp16 activations over e4m3 cache bytes: 16 cache elements per 16-byte load (8 lanes per token row at head size 128,
         // 256-token chunks); head ratio 8 does not fit registers (16 dims per lane x 8 heads); no generic form, and one refusal
@@ -907,6 +946,7 @@ DecodeAttnPlan plan_decode_attn(const DecodeAttnCall &c) {
         return ws_ok ? plan_attn_split(c, need) : attn_refusal(DAREF_WORKSPACE, need);
     if (c.window > 0) return attn_refusal(DAREF_WINDOW);   // the generic kernel attends to everything
     if (c.head_sink) return attn_refusal(DAREF_HEAD_SINK);   // ... and normalises over the real keys only
+    if (c.qk_norm) return attn_refusal(DAREF_QK_NORM);       // ... and reads q and k as the projection left them
     if (c.paged) return attn_refusal(DAREF_PAGED_GEOMETRY);
     if (c.slabs) return attn_refusal(DAREF_SLABS_GEOMETRY);
     // (tickets on a supported geometry that fell through -- unaligned -- are ignored: the generic kernel has no partials)
@@ -946,6 +986,10 @@ int decode_attn_refuse(const DecodeAttnCall &c, const DecodeAttnPlan &p) {
             set_error("decoder_mha: a head sink needs fp16 activations, head_size 64/128, head_num/kv_head_num in {1,2,4,8} (e4m3 cache: "
                       "{1,2,4}) and 16-byte aligned buffers (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
             break;
+        case DAREF_QK_NORM:
+            set_error("decoder_mha: QK-norm needs fp16 activations, head_size 64/128, head_num/kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4}), "
+                      "16-byte aligned buffers, and no QKV bias, window or head sink (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
+            break;
         case DAREF_GENERIC_SPAN:
             set_error("decoder_mha: generic path supports at most 15360 tokens (head_size=%d, rep=%d)", c.head_size, c.head_num / c.kv_head_num);
             break;
@@ -968,15 +1012,29 @@ struct DecodeAttnArgs {
     KvScale ks;
     PagedKv pg;
     const float *head_sink;   // [head_num] fp32 of this layer, or null
+    const void *q_gamma, *k_gamma;   // QK-norm: [head_size] each in the activation type, of this layer, or both null
+    float qk_eps;
 };
 
 template <typename T, int HS, int REP, typename KT> static void launch_split(const DecodeAttnPlan &p, const DecodeAttnArgs &a, hipStream_t st) {
     // the windowed instantiations: fp16 activations, head size 64 / 128 (what plan_decode_attn plans with a window)
     if constexpr (std::is_same<T, half_t>::value && (HS == 64 || HS == 128)) {
+        if (p.qk_norm) {   // the QKN instantiations (no window, no head sink: plan_decode_attn); the merge launch is the plain one
+            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, false, false, true, const T *, const T *, float>
+                <<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+                    static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
+                    static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
+                    a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, static_cast<const T *>(a.q_gamma), static_cast<const T *>(a.k_gamma), a.qk_eps);
+            if (p.merge)
+                decode_attn_combine_kernel<T><<<dim3(p.merge_grid[0], p.merge_grid[1]), p.merge_block, 0, st>>>(
+                    a.part, static_cast<T *>(a.out), a.head_num, HS, p.chunk, a.step, a.step_dev, p.max_splits_ws, a.pg.step_stride,
+                    a.max_seq_len, a.pg.out_x32);
+            return;
+        }
         if (p.head_sink) {   // the SINK instantiations, windowed or not: the same launches with the head-sink array as last argument
             auto run = [&](auto win_c, auto... ex) {
                 constexpr bool W = decltype(win_c)::value;
-                decode_attn_split_kernel<T, HS, REP, 4, 8, KT, W, true, decltype(ex)...><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+                decode_attn_split_kernel<T, HS, REP, 4, 8, KT, W, true, false, decltype(ex)...><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
                     static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
                     static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
                     a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, ex...);
@@ -990,7 +1048,7 @@ template <typename T, int HS, int REP, typename KT> static void launch_split(con
             return;
         }
         if (p.window > 0) {
-            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, true, false, int, int><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
+            decode_attn_split_kernel<T, HS, REP, 4, 8, KT, true, false, false, int, int><<<dim3(p.grid[0], p.grid[1], p.grid[2]), 4 * 64, 0, st>>>(
                 static_cast<const T *>(a.qkv), static_cast<const T *>(a.bias), static_cast<KT *>(a.kc), static_cast<KT *>(a.vc), a.part,
                 static_cast<T *>(a.out), a.head_num, a.kv_head_num, a.max_seq_len, a.step, a.step_dev, p.max_splits_ws, a.rope, a.rot_dim,
                 a.tickets, a.qs, a.ks.k, a.ks.v, a.pg, p.cpw, p.window, p.sinks);
@@ -1061,7 +1119,8 @@ static DecodeAttnArgs decode_attn_args(const DecodeAttnShape &g, const DecodeAtt
     return DecodeAttnArgs{io.qkv, io.qkv_bias, static_cast<char *>(kv.k) + layer_bytes, static_cast<char *>(kv.v) + layer_bytes, io.out,
                           static_cast<float *>(io.workspace), g.head_num, g.kv_head_num, g.head_size, g.max_seq_len, pos.step, pos.step_dev,
                           io.rope, io.rot_dim, io.tickets, qs, KvScale{kv.k_scale, kv.v_scale},
-                          PagedKv{kv.block_table, kv.max_pages, pos.ragged ? 1 : 0, io.out_x32 ? 1 : 0}, io.head_sink};
+                          PagedKv{kv.block_table, kv.max_pages, pos.ragged ? 1 : 0, io.out_x32 ? 1 : 0}, io.head_sink, io.q_gamma, io.k_gamma,
+                          io.qk_eps};
 }
 static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos,
                                        const DecodeAttnArgs &a) {
@@ -1079,6 +1138,7 @@ static DecodeAttnCall decode_attn_call(const DecodeAttnShape &g, const DecodeAtt
     c.workspace = io.workspace != nullptr, c.workspace_bytes = io.workspace_bytes;
     c.window = io.window > 0 ? io.window : 0, c.sinks = io.window > 0 ? io.sinks : 0;
     c.head_sink = io.head_sink != nullptr;
+    c.qk_norm = io.q_gamma != nullptr;
     return c;
 }
 
@@ -1130,7 +1190,9 @@ static void decode_attn_plan_text(const DecodeAttnCall &c, const DecodeAttnPlan 
     // their bound for any position
     int w = 0;
     if (p.window > 0) w = snprintf(text + k + m, n - k - m, " window %d sinks %d live %s%d", p.window, p.sinks, c.step_dev ? "<=" : "", p.grid[0]);
-    if (p.head_sink) snprintf(text + k + m + w, n - k - m - w, " head_sink");   // the SINK instantiation of the same launches
+    int s = 0;
+    if (p.head_sink) s = snprintf(text + k + m + w, n - k - m - w, " head_sink");   // the SINK instantiation of the same launches
+    if (p.qk_norm) snprintf(text + k + m + w + s, n - k - m - w - s, " qk_norm");   // the QKN instantiation of the split kernel
 }
 
 // The page ring of a windowed sequence (llmie_kv_window_advance): one thread per sequence.  The logical pages the positions
@@ -1240,6 +1302,7 @@ static const char *decode_attn_plan_query(const char *who, llmie_dtype dtype, in
         c.workspace = workspace_bytes >= 0, c.workspace_bytes = c.workspace ? static_cast<size_t>(workspace_bytes) : 0;
         c.window = window, c.sinks = window > 0 ? sinks : 0;
         c.head_sink = (forms & LLMIE_ATTN_HEAD_SINK) != 0;
+        c.qk_norm = (forms & LLMIE_ATTN_QK_NORM) != 0;
         const DecodeAttnPlan p = plan_decode_attn(c);
         if (p.kind == DA_REFUSED) rc = decode_attn_refuse(c, p);
         else decode_attn_plan_text(c, p, text, sizeof(text));
@@ -1252,7 +1315,7 @@ extern "C" const char *llmie_decoder_mha_plan(llmie_dtype dtype, int kv_e4m3, in
                                               int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
                                               unsigned long long residues, long long workspace_bytes, int *status) {
     return decode_attn_plan_query("decoder_mha_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                  forms & ~LLMIE_ATTN_HEAD_SINK,
+                                  forms & ~(LLMIE_ATTN_HEAD_SINK | LLMIE_ATTN_QK_NORM),
                                   max_pages, num_pages, residues, workspace_bytes, 0, 0, status);
 }
 
@@ -1261,7 +1324,8 @@ extern "C" const char *llmie_decoder_mha_window_plan(llmie_dtype dtype, int kv_e
                                                      unsigned long long residues, long long workspace_bytes, int window, int sinks,
                                                      int *status) {
     return decode_attn_plan_query("decoder_mha_window_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
-                                  forms & ~LLMIE_ATTN_HEAD_SINK, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
+                                  forms & ~(LLMIE_ATTN_HEAD_SINK | LLMIE_ATTN_QK_NORM), max_pages, num_pages, residues, workspace_bytes, window,
+                                  sinks, status);
 }
 
 // Sliding-window decode attention on the operands of llmie_decoder_mha_ragged (+ tickets and the e4m3 cache, which the engine's calls
@@ -1305,6 +1369,39 @@ extern "C" const char *llmie_decoder_mha_sink_plan(llmie_dtype dtype, int kv_e4m
                                                    unsigned long long residues, long long workspace_bytes, int window, int sinks,
                                                    int *status) {
     return decode_attn_plan_query("decoder_mha_sink_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
+                                  forms & ~LLMIE_ATTN_QK_NORM, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
+}
+
+// llmie_decoder_mha_sink plus the per-head q/k RMSNorm in front of RoPE (q_gamma / k_gamma: device [head_size] in the activation type,
+// both NULL = that entry's call)
+extern "C" int llmie_decoder_mha_qknorm(const void *qkv, const void *qkv_bias, void *k_cache, void *v_cache, void *out, int layer, int batch,
+                                        int head_num, int kv_head_num, int head_size, int max_seq_len, const int32_t *ctx_len_dev,
+                                        void *workspace, size_t workspace_bytes, const void *rope_table, int rotary_dim,
+                                        const int32_t *block_table, int max_pages, int num_pages, int window, int sinks, int32_t *tickets,
+                                        int kv_e4m3, float k_scale, float v_scale, const float *head_sink, const void *q_gamma,
+                                        const void *k_gamma, float qk_eps, llmie_dtype dtype, llmie_stream stream) {
+    const int rc = decode_attn_validate_window("decoder_mha_qknorm", window, sinks);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(head_sink) % sizeof(float) == 0, "decoder_mha_qknorm: head_sink must be 4-byte aligned");
+    LLMIE_REQUIRE((q_gamma != nullptr) == (k_gamma != nullptr), "decoder_mha_qknorm: q_gamma and k_gamma go together (one is NULL)");
+    if (q_gamma) {
+        LLMIE_REQUIRE((reinterpret_cast<uintptr_t>(q_gamma) | reinterpret_cast<uintptr_t>(k_gamma)) % 16 == 0,
+                      "decoder_mha_qknorm: the gammas must be 16-byte aligned");
+        LLMIE_REQUIRE(qk_eps >= 0.f, "decoder_mha_qknorm: qk_eps must be a number >= 0");
+    }
+    return decode_attn_entry("decoder_mha_qknorm", DecodeAttnShape{batch, head_num, kv_head_num, head_size, max_seq_len, dtype},
+                             DecodeAttnIo{qkv, qkv_bias, out, workspace, workspace_bytes, static_cast<const float2 *>(rope_table), rotary_dim,
+                                          tickets, nullptr, nullptr, 0, window, sinks, head_sink, q_gamma, k_gamma, q_gamma ? qk_eps : 0.f},
+                             KvView{k_cache, v_cache, block_table, max_pages, num_pages, kv_e4m3 ? 1 : 0, kv_e4m3 ? k_scale : 1.f,
+                                    kv_e4m3 ? v_scale : 1.f},
+                             DecodePos{-1, ctx_len_dev, 1}, layer, stream);
+}
+
+extern "C" const char *llmie_decoder_mha_qknorm_plan(llmie_dtype dtype, int kv_e4m3, int batch, int head_num, int kv_head_num, int head_size,
+                                                     int max_seq_len, int step, unsigned forms, int max_pages, int num_pages,
+                                                     unsigned long long residues, long long workspace_bytes, int window, int sinks,
+                                                     int *status) {
+    return decode_attn_plan_query("decoder_mha_qknorm_plan", dtype, kv_e4m3, batch, head_num, kv_head_num, head_size, max_seq_len, step,
                                   forms, max_pages, num_pages, residues, workspace_bytes, window, sinks, status);
 }
 

@@ -80,6 +80,12 @@ struct llmie_decoder {
     // read where a call's attention launches are planned, like the window
     const float *head_sinks = nullptr;
     const float *head_sink_of(int layer) const { return head_sinks ? head_sinks + static_cast<size_t>(layer) * cfg.head_num : nullptr; }
+    // QK-norm (llmie_decoder_set_qk_norm): the caller's device arrays [num_layers, head_size] of fp16, or both null, and eps; read
+    // where a call's attention launches are built, like the head sinks
+    const half_t *q_gammas = nullptr, *k_gammas = nullptr;
+    float qk_eps = 0.f;
+    const half_t *q_gamma_of(int layer) const { return q_gammas ? q_gammas + static_cast<size_t>(layer) * cfg.head_size : nullptr; }
+    const half_t *k_gamma_of(int layer) const { return k_gammas ? k_gammas + static_cast<size_t>(layer) * cfg.head_size : nullptr; }
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -719,6 +725,9 @@ static const char *const kWindowRefusal =
     "a sliding window needs an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
 static const char *const kHeadSinkRefusal =
     "head sinks need an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4})";
+static const char *const kQkNormRefusal =
+    "QK-norm needs an fp16 engine with head_size 64 / 128 and head_num / kv_head_num in {1,2,4,8} (e4m3 cache: {1,2,4}), no layer with a "
+    "QKV bias, and neither a sliding window nor head sinks set";
 static const char *const kLoraRefusal =
     "adapters need an fp16 engine with fp16 / int8 / int4 weights (an fp8-weight engine never materialises fp16 normalised rows, a "
     "LLMIE_DEC_PACKED_ONLY engine has no row-major route), hidden and inter sizes that are multiples of 32 and q / kv widths that are "
@@ -826,6 +835,7 @@ struct PrefillCall {
     EngineSwitches sw;
     bool lora;                // an adapter table is attached
     bool moe;                 // experts are attached
+    bool qk_norm;             // QK-norm is set: q and k are normalised in the RoPE + append launch, so no QKV form does RoPE itself
 };
 struct PrefillPlan {
     int path, refusal;
@@ -895,7 +905,7 @@ struct PrefillLayerPlan {
 // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
 // this holds writes the epilogue's token table once, whatever its layers end up choosing.)
 static bool prefill_rope_fusable(const PrefillCall &p) {
-    return !p.lora && !p.moe && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+    return !p.lora && !p.moe && !p.qk_norm && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
 }
 static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
     const llmie_decoder_config &c = p.cfg;
@@ -915,7 +925,7 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
     if (path == PP_SHORT_SPLITK) {
         // (the slab consumer of the QKV projection does RoPE + the cache append as well: one launch less per layer)
         const SplitKSlabs sk{slabs.p, 1, T, QKV};
-        o.qkv = !p.sw.no_qkv_rope_fusion && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
+        o.qkv = !p.sw.no_qkv_rope_fusion && !p.qk_norm && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
         o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
     } else if (path == PP_LORA || path == PP_MOE || c.wfmt == LLMIE_W_MXFP4) {
         // the general sequence with the forms the adapter updates need: normalised rows in place, the QKV buffer un-rotated (the update
@@ -978,8 +988,11 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
 static PrefillCall prefill_call_of_flags(const llmie_decoder_config &cfg, int tokens, unsigned call_flags, const EngineSwitches &sw) {
     return PrefillCall{cfg, tokens, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
                        !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw,
-                       (call_flags & LLMIE_PLAN_LORA) != 0};
+                       (call_flags & LLMIE_PLAN_LORA) != 0, false, (call_flags & LLMIE_PLAN_QK_NORM) != 0};
 }
+// what QK-norm needs of an engine's config (beside the geometry): nothing a config says rules it out but the geometry; the layers'
+// QKV biases and the window / head-sink state are the engine's (llmie_decoder_set_qk_norm)
+static bool qk_norm_engine_ok(const llmie_decoder_config &c) { return window_engine_ok(c); }
 
 // Host-only: the launch sequence llmie_decoder_forward (prefill = 0, rows = batch) or llmie_decoder_prefill (prefill = 1, rows =
 // tokens) plans for an engine of this config; NULL with llmie_last_error() set where the call -- or creating the engine -- is refused.
@@ -1000,6 +1013,10 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
     }
     if ((call_flags & LLMIE_PLAN_HEAD_SINK) && !window_engine_ok(*cfg)) {
         set_error("decoder_plan_name: %s", kHeadSinkRefusal);
+        return nullptr;
+    }
+    if ((call_flags & LLMIE_PLAN_QK_NORM) && (!qk_norm_engine_ok(*cfg) || (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK)))) {
+        set_error("decoder_plan_name: %s", kQkNormRefusal);
         return nullptr;
     }
     if (prefill) {
@@ -1052,7 +1069,7 @@ struct DecodeStep {
         return decoder_mha_rope(DecodeAttnShape{batch, c.head_num, c.kv_head_num, c.head_size, c.max_seq_len, dt},
                                 DecodeAttnIo{qkv, qkv_bias, out, dec->attn_ws, dec->attn_ws_bytes, rope ? dec->rope_table : nullptr,
                                              rope ? c.rotary_dim : 0, nullptr, qkv_slabs, qkv_scale, out_x32, dec->window_of(layer), dec->sinks,
-                                             dec->head_sink_of(layer)},
+                                             dec->head_sink_of(layer), dec->q_gamma_of(layer), dec->k_gamma_of(layer), dec->qk_eps},
                                 kv, pos, layer, st);
     }
 
@@ -1586,7 +1603,8 @@ struct PrefillPass {
         ap.window = dec->window_of(l), ap.sinks = ap.window > 0 ? dec->sinks : 0;
         ap.head_sink = dec->head_sinks != nullptr;
         return prefill_attention_f16(ap, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
-                                     c.max_seq_len, c.rotary_dim, st, dec->head_sink_of(l));
+                                     c.max_seq_len, c.rotary_dim, st, dec->head_sink_of(l),
+                                     PrefillQkNorm{dec->q_gamma_of(l), dec->k_gamma_of(l), dec->qk_eps});
     }
     // act = swiglu(x . Wgu^T) of the lean and general sequences (ffn.cpp:105-122)
     int gate_up(const half_t *x, const llmie_matrix &w, int form) const {
@@ -1793,7 +1811,7 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (int rc = prefill_shape_ok(c, batch, num_tokens, max_q_len)) return rc;
     const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
     const EngineSwitches &sw = engine_switches();
-    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr, dec->moe.on()};
+    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr, dec->moe.on(), dec->q_gammas != nullptr};
     for (const llmie_layer_weights &w : dec->layers) {
         call.weights_a16 = call.weights_a16 && (mis16(w.qkv.data) | mis16(w.o.data) | mis16(w.gate_up.data) | mis16(w.down.data)) == 0;
         call.int4_scales_a4 = call.int4_scales_a4 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
@@ -1988,6 +2006,7 @@ extern "C" int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer
     }
     LLMIE_REQUIRE(any || sinks == 0, "decoder_set_window: %d sink tokens without a window on any layer", sinks);
     if (any && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_window: %s", kWindowRefusal);
+    if (any && dec->q_gammas) LLMIE_UNSUPPORTED("decoder_set_window: %s", kQkNormRefusal);
     if (any) dec->layer_window.assign(layer_window, layer_window + dec->cfg.num_layers), dec->sinks = sinks;
     else dec->layer_window.clear(), dec->sinks = 0;
     return LLMIE_OK;
@@ -1997,8 +2016,27 @@ extern "C" int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer
 extern "C" int llmie_decoder_set_head_sinks(llmie_decoder *dec, const float *head_sink_dev) {
     LLMIE_REQUIRE(dec, "decoder_set_head_sinks: NULL decoder");
     if (head_sink_dev && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kHeadSinkRefusal);
+    if (head_sink_dev && dec->q_gammas) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kQkNormRefusal);
     LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(head_sink_dev) % sizeof(float) == 0, "decoder_set_head_sinks: the array must be 4-byte aligned");
     dec->head_sinks = head_sink_dev;
+    return LLMIE_OK;
+}
+
+// QK-norm: the caller's device arrays and eps, kept on the engine and read where a call's attention launches are built
+extern "C" int llmie_decoder_set_qk_norm(llmie_decoder *dec, const void *q_gamma_dev, const void *k_gamma_dev, float eps) {
+    LLMIE_REQUIRE(dec, "decoder_set_qk_norm: NULL decoder");
+    LLMIE_REQUIRE((q_gamma_dev != nullptr) == (k_gamma_dev != nullptr), "decoder_set_qk_norm: q_gamma and k_gamma go together (one is NULL)");
+    if (!q_gamma_dev) {   // back to un-normalised q and k
+        dec->q_gammas = dec->k_gammas = nullptr, dec->qk_eps = 0.f;
+        return LLMIE_OK;
+    }
+    LLMIE_REQUIRE((mis16(q_gamma_dev) | mis16(k_gamma_dev)) == 0, "decoder_set_qk_norm: the gamma arrays must be 16-byte aligned");
+    LLMIE_REQUIRE(eps >= 0.f, "decoder_set_qk_norm: eps must be a number >= 0");
+    bool bias = false;
+    for (const llmie_layer_weights &w : dec->layers) bias |= w.qkv.bias != nullptr;
+    if (!qk_norm_engine_ok(dec->cfg) || bias || !dec->layer_window.empty() || dec->head_sinks)
+        LLMIE_UNSUPPORTED("decoder_set_qk_norm: %s", kQkNormRefusal);
+    dec->q_gammas = static_cast<const half_t *>(q_gamma_dev), dec->k_gammas = static_cast<const half_t *>(k_gamma_dev), dec->qk_eps = eps;
     return LLMIE_OK;
 }
 
@@ -2029,6 +2067,8 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         if (int bad = prefill_shape_ok(*cfg, batch, tokens, max_q_len)) return bad;
         if ((call_flags & LLMIE_PLAN_WINDOW) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kWindowRefusal);
         if ((call_flags & LLMIE_PLAN_HEAD_SINK) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kHeadSinkRefusal);
+        if ((call_flags & LLMIE_PLAN_QK_NORM) && (!qk_norm_engine_ok(*cfg) || (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK))))
+            LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kQkNormRefusal);
         const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
         const PrefillPlan plan = plan_prefill(call);
         if (plan.path == PP_REFUSED) return prefill_refuse(plan);
@@ -2056,7 +2096,9 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         // (a windowed layer runs the windowed instantiation of the same flash form on the same grid)
         if (call_flags & LLMIE_PLAN_WINDOW) n += snprintf(text + n, sizeof(text) - n, " attn_window=1");
         // (... and head sinks the SINK instantiation of that form)
-        if (call_flags & LLMIE_PLAN_HEAD_SINK) snprintf(text + n, sizeof(text) - n, " attn_head_sink=1");
+        if (call_flags & LLMIE_PLAN_HEAD_SINK) n += snprintf(text + n, sizeof(text) - n, " attn_head_sink=1");
+        // (QK-norm: the QKN instantiation of the RoPE + append launch; the QKV forms above are already the ones without the epilogue)
+        if (call_flags & LLMIE_PLAN_QK_NORM) snprintf(text + n, sizeof(text) - n, " qk_norm=1");
         return LLMIE_OK;
     }();
     if (status) *status = rc;

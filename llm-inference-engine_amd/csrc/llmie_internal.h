@@ -254,7 +254,7 @@ struct DecodePos {
 enum DecodeAttnKind : int { DA_REFUSED = 0, DA_SPLIT, DA_GENERIC };
 enum DecodeAttnRefusal : int {
     DAREF_NONE = 0, DAREF_RAGGED_LENGTHS, DAREF_X32, DAREF_PAGES, DAREF_SLAB_ALIGNMENT, DAREF_E4M3_FORM, DAREF_E4M3, DAREF_WORKSPACE,
-    DAREF_PAGED_GEOMETRY, DAREF_SLABS_GEOMETRY, DAREF_ROPE_GEOMETRY, DAREF_RAGGED_GEOMETRY, DAREF_GENERIC_SPAN, DAREF_WINDOW, DAREF_HEAD_SINK,
+    DAREF_PAGED_GEOMETRY, DAREF_SLABS_GEOMETRY, DAREF_ROPE_GEOMETRY, DAREF_RAGGED_GEOMETRY, DAREF_GENERIC_SPAN, DAREF_WINDOW, DAREF_HEAD_SINK, DAREF_QK_NORM,
 };
 // One decode attention call as the planner sees it: geometry, position form, which optional operands are there, how far each
 // pointer is from 16-byte alignment (address % 16 AFTER the layer offset; 0 for a null pointer), and the caller's scratch.
@@ -272,6 +272,7 @@ struct DecodeAttnCall {
     size_t workspace_bytes;
     int window, sinks;                 // sliding window (0: full attention, sinks then 0) and sink tokens
     bool head_sink;                    // a learned sink logit per query head (device fp32 [head_num]) joins every softmax
+    bool qk_norm;                      // per-head RMSNorm of q and k in front of RoPE (device gammas [head_size] each)
 };
 struct DecodeAttnPlan {
     int kind, refusal;                 // DecodeAttnKind, DecodeAttnRefusal of DA_REFUSED
@@ -283,6 +284,7 @@ struct DecodeAttnPlan {
     int cpw, chunk, grid[3], max_splits_ws;
     int window, sinks;                 // window > 0: the windowed instantiation; grid x counts live spans (attn_live_chunks)
     bool head_sink;                    // the SINK instantiation of the same launches (same grid, slots and merge)
+    bool qk_norm;                      // the QKN instantiation of the split kernel (same grid, slots and merge)
     bool merge;
     int merge_grid[2], merge_block;
     // DA_GENERIC: grid (heads, batch), dynamic LDS
@@ -299,7 +301,8 @@ struct DecodeAttnShape {
 // tickets: [batch, kvh] zeroed arrival counters = in-launch merge, null = merge kernel; qkv_slabs: q/k/v are read from the QKV
 // projection's split-K slabs (qkv unused) with qkv_scale; out_x32: out is the x32 activation image (batch <= 32), not [batch, H];
 // window > 0: sliding-window attention with `sinks` sink tokens (include/llmie.h), 0 = full attention; head_sink: this layer's
-// learned sink logits, device fp32 [head_num], or null
+// learned sink logits, device fp32 [head_num], or null; q_gamma / k_gamma: this layer's QK-norm gammas, device [head_size] each in
+// the activation type, or both null, with qk_eps
 struct DecodeAttnIo {
     const void *qkv, *qkv_bias;
     void *out, *workspace;
@@ -312,6 +315,8 @@ struct DecodeAttnIo {
     int out_x32;
     int window, sinks;
     const float *head_sink;
+    const void *q_gamma, *k_gamma;
+    float qk_eps;
 };
 // decode attention of one layer with bias, RoPE and the KV append fused in front: plan, refuse or launch
 int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st);
@@ -326,11 +331,18 @@ struct PrefillAttnPlan {
     int window, sinks;              // window > 0: the windowed instantiation (sliding window + sink tokens), 0: full causal attention
     bool head_sink;                 // the SINK instantiation of the same form: a learned sink logit per query head joins every row's softmax
 };
+// QK-norm of a prefill attention call (include/llmie.h, llmie_qk_norm): this layer's gammas, device fp16 [128] each, or both null; the
+// RoPE + append launch normalises q and k in front of the rotation (so the plan must have rope_append, and the layer no QKV bias)
+struct PrefillQkNorm {
+    const half_t *q_gamma, *k_gamma;
+    float eps;
+};
 PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window = 0, int sinks = 0);
 int prefill_attention_f16(const PrefillAttnPlan &plan, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
                           int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st,
-                          const float *head_sink = nullptr /* plan.head_sink: this layer's device fp32 [head_num] */);
+                          const float *head_sink = nullptr /* plan.head_sink: this layer's device fp32 [head_num] */,
+                          const PrefillQkNorm &qkn = PrefillQkNorm{nullptr, nullptr, 0.f});
 // short prefills: slab consumer of the QKV projection with RoPE + KV-cache append folded in (q -> qkv, k / v -> the caches only)
 bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, const void *qkv, const void *bias);
 int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,

@@ -13,6 +13,7 @@
 //                                                     the S^T layout is exactly the B-operand layout, no data movement)
 //                                so every lane owns one query row's statistics (col = lane & 15) throughout.
 #include "llmie_internal.h"
+#include "qk_norm.cuh"
 
 #include <cstdlib>
 
@@ -39,7 +40,12 @@ __device__ __forceinline__ void locate_token(const int32_t *__restrict__ cum, in
 
 // KV8: the caches are e4m3 bytes, stored = e4m3(x / scale) (same [L, bs, kvh, max_seq, hs] indexing in elements)
 
-template <int HS, bool KV8>
+// QKN (compile time): the per-head q/k RMSNorm in front of the rotation (include/llmie.h, llmie_qk_norm).  Its three launch arguments
+// (const half_t *q_gamma, const half_t *k_gamma, float eps) are the pack QknArgs; QKN = false has an empty pack: the arguments and
+// the code the kernel had before.  The HS / 16 work items of a head are adjacent lanes (heads * GROUPS and 256 are multiples of
+// GROUPS, so a head's lanes are all in the loop or all out of it): each sums its two groups of 8, the lanes are reduced by
+// exchanges and the two halves -- the highest bit of the group index -- are added last (qk_norm.cuh's order).
+template <int HS, bool KV8, bool QKN = false, typename... QknArgs>
 __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__restrict__ qkv, const half_t *__restrict__ bias,
                                                                   void *__restrict__ k_cache, void *__restrict__ v_cache,
                                                                   const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
@@ -47,7 +53,8 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__rest
                                                                   int kv_head_num, int max_seq_len, int rotary_dim, size_t layer_off,
                                                                   float k_inv_scale, float v_inv_scale,
                                                                   const int32_t *__restrict__ table /* paged cache or null */,
-                                                                  int max_pages) {
+                                                                  int max_pages, const QknArgs... qkn /* QKN: q_gamma, k_gamma, eps */) {
+    static_assert(sizeof...(QknArgs) == (QKN ? 3 : 0), "q_gamma, k_gamma, eps");
     const int t = blockIdx.x;
     int b, pos;
     locate_token(cum, batch, t, b, pos);
@@ -63,7 +70,24 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__rest
     for (int i = threadIdx.x; i < heads * GROUPS; i += 256) {
         const int h = i / GROUPS, d = (i - h * GROUPS) * 8;
         half_t *src = row + static_cast<size_t>(h) * HS;
-        const half8_t lo = *reinterpret_cast<const half8_t *>(src + d), hi = *reinterpret_cast<const half8_t *>(src + d + HALF);
+        half8_t lo = *reinterpret_cast<const half8_t *>(src + d), hi = *reinterpret_cast<const half8_t *>(src + d + HALF);
+        if constexpr (QKN) {
+            // every lane of the head takes part in the sums (v heads too: no exchange under a divergent branch); q and k heads apply
+            const half_t *gam = h < head_num ? pack_arg<0>(qkn...) : pack_arg<1>(qkn...);
+            const half8_t glo = *reinterpret_cast<const half8_t *>(gam + d), ghi = *reinterpret_cast<const half8_t *>(gam + d + HALF);
+            half_t xl[8], xh[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xl[e] = lo[e], xh[e] = hi[e];
+            const float ss_lo = qkn_lane_butterfly<GROUPS>(qkn_group_ss(xl)), ss_hi = qkn_lane_butterfly<GROUPS>(qkn_group_ss(xh));
+            const float inv = qkn_inv(ss_lo + ss_hi, HS, pack_arg<2>(qkn...));
+            if (h < head_num + kv_head_num) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    lo[e] = qkn_apply<half_t>(to_f32(xl[e]), inv, to_f32(glo[e]));
+                    hi[e] = qkn_apply<half_t>(to_f32(xh[e]), inv, to_f32(ghi[e]));
+                }
+            }
+        }
         half8_t blo = {0, 0, 0, 0, 0, 0, 0, 0}, bhi = blo;
         if (bias) {
             blo = *reinterpret_cast<const half8_t *>(bias + static_cast<size_t>(h) * HS + d);
@@ -619,12 +643,22 @@ PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool k
 // g.grid[1] / g.grid[2] are head_num / batch
 int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
-                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, const float *head_sink) {
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, const float *head_sink, const PrefillQkNorm &qkn) {
     const int head_num = g.grid[1], batch = g.grid[2];
     const size_t layer_off = kv.block_table ? static_cast<size_t>(layer) * kv.num_pages * kv_head_num * 128 * 128
                                             : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * 128;
     const float ks = g.kv_e4m3 ? kv.k_scale : 1.f, vs = g.kv_e4m3 ? kv.v_scale : 1.f;
-    if (g.rope_append) {   // (else the QKV projection's epilogue rotated q in `qkv` and wrote k / v into the caches)
+    if (qkn.q_gamma && (!g.rope_append || qkv_bias)) {   // (the planner and the engine keep both away)
+        set_error("prefill attention: QK-norm needs the RoPE + append launch and no QKV bias");
+        return LLMIE_ERR_UNSUPPORTED;
+    }
+    if (g.rope_append && qkn.q_gamma) {   // the QKN instantiations: the norm runs in this launch, in front of the rotation
+        auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true, true, const half_t *, const half_t *, float>
+                                : prefill_rope_append_kernel<128, false, true, const half_t *, const half_t *, float>;
+        append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
+                                           rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages, qkn.q_gamma, qkn.k_gamma,
+                                           qkn.eps);
+    } else if (g.rope_append) {   // (else the QKV projection's epilogue rotated q in `qkv` and wrote k / v into the caches)
         auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true> : prefill_rope_append_kernel<128, false>;
         append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
                                            rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages);
