@@ -46,7 +46,8 @@ extern "C" {
  *      stop sets and top-N log-probabilities in the sampler: llmie_sampling_ext, llmie_sample_logits_ext,
  *      llmie_lm_head_sample_ext; several hypotheses per request: llmie_beam_step(_workspace_bytes),
  *      llmie_kv_pages_fork(_workspace_bytes); speculative decoding: llmie_spec_verify(_workspace_bytes), llmie_ngram_draft,
- *      llmie_spec_verify_sampled(_workspace_bytes)). */
+ *      llmie_spec_verify_sampled(_workspace_bytes); draft trees: llmie_spec_tree_prepare, llmie_spec_verify_tree(_workspace_bytes),
+ *      llmie_kv_tree_commit, llmie_ngram_draft_tree, llmie_decoder_set_tree). */
 #define LLMIE_ABI_VERSION 3
 
 typedef enum { LLMIE_F32 = 0, LLMIE_F16 = 1 } llmie_dtype;
@@ -983,6 +984,82 @@ int llmie_ngram_draft(const int32_t *tokens /* [batch, stride] */, int stride, c
                       int32_t *out_ids /* [batch, k+1]: the verify chunk's input ids */, int32_t *out_draft_ids /* [batch, k] */,
                       int32_t *out_draft_len /* [batch] */, llmie_stream stream);
 
+/* ABI 3 (an addition).  TREE speculative decoding: several alternatives per position verified in one forward.  No reference launcher.
+ * A sequence's chunk has n node slots, 1 <= n <= LLMIE_SPEC_TREE_MAX_NODES, the same stride for every sequence.  Node 0 is the last
+ * emitted token (input 0 of the linear chunk); nodes 1 .. n - 1 are drafts; parent[b, i] names node i's parent.
+ *
+ * llmie_spec_tree_prepare: parent [batch, n] -> depth_out [batch, n] (int32), anc_out [batch, n] (uint64).  count =
+ * node_count[b] clamped to [1, n] (node_count == NULL: n).  Node 0: depth 0, anc 1.  Node i >= 1 is LIVE iff i < count and
+ * 0 <= parent[b, i] < i and the parent is live; a live node has depth = depth[parent] + 1 and anc = anc[parent] | (1 << i) -- bit j
+ * of anc[i] says that node j lies on the path root -> i, i included; a dead node has depth 0 and anc = 1 << i.  So "live" is "bit 0
+ * of anc is set", the one liveness rule every consumer uses.  One launch; everything is read on the device; legal inside a graph
+ * capture.  LLMIE_ERR_INVALID_ARG: NULL parent / depth_out / anc_out, batch < 1, n < 1; LLMIE_ERR_UNSUPPORTED: n above the maximum.
+ *
+ * llmie_spec_verify_tree: EXACT-MATCH verification of a tree.  The operands are those of llmie_spec_verify with k -> n, draft_ids ->
+ * node_ids [batch, n] (the token of each node; slot 0 is not read), draft_len -> parent, depth, anc [batch, n] as
+ * llmie_spec_tree_prepare left them; out_tokens, out_logprob and out_path (may be NULL) are [batch, n]; logits are
+ * [batch * n, vocab], row r = b * n + i follows node i; mask_index and the top-N outputs of ext are indexed by r.
+ * pick_i is the token llmie_sample_logits_ext returns for row (b, i) alone at Philox step s_b + depth_i, on the history of b
+ * followed -- history_append != 0, as far as history_stride lets depth_i appends reach -- by node_ids of the nodes on the path
+ * root -> i, root excluded and i included, in depth order.  (A dead node samples at depth 0 on the stored history; nothing reads
+ * its pick.)  The walk: cur = 0; emit pick_cur, out_path[b, m] = cur; stop if pick_cur finishes the sequence; otherwise take the
+ * LOWEST live j with parent[b, j] == cur and node_ids[b, j] == pick_cur; none: stop; else cur = j and go on.  count is in [1, n];
+ * later slots of out_path are -1; out_tokens, out_count, out_logprob, seq_len, finished, the history append, last_token,
+ * cached_len += count, step_rows += count, a sequence finished on entry (left alone) and the top-N outputs (every row) are exactly
+ * llmie_spec_verify's.  With parent[i] = i - 1, n = k + 1, node_ids[b, i] = draft_ids[b, i - 1] and node_count = draft_len + 1 every
+ * output and every state array equals llmie_spec_verify's bit for bit.  Refused on the host before any launch: whatever
+ * llmie_spec_verify refuses, in its order and under this entry's name, with n < 1 (LLMIE_ERR_INVALID_ARG), NULL node_ids /
+ * out_tokens / out_count, NULL parent / depth / anc, n above the maximum (LLMIE_ERR_UNSUPPORTED) and the workspace rule on
+ * llmie_spec_verify_tree_workspace_bytes in the places of the k checks.  Two launches (one 1024-thread workgroup per node: the path
+ * tokens, at most 63, are gathered into LDS first; one pass per sequence walks the tree in LDS); no allocation, no
+ * synchronisation, legal inside a graph capture; same inputs, same bits; no dependence on slot or neighbours.
+ *
+ * llmie_kv_tree_commit: behind the verify, accepted node out_path[b, m] sits at cache slot base_len[b] + out_path[b, m] and belongs
+ * at base_len[b] + m (its K row already carries the right rotation: depth(out_path[m]) = m).  Moves the K and V rows of every
+ * layer and kv head for m < out_count[b] (clamped to [0, n]); rows with out_path[m] == m stay; count 0 does nothing.  Dense caches
+ * [layers, batch, kvh, max_seq_len, head_size] (block_table NULL) or pools [layers, num_pages, kvh, 128, head_size] through
+ * block_table [batch, max_pages]; elem_bytes 2 (fp16) or 1 (e4m3).  A byte copy with the semantics "all sources read, then all
+ * destinations written": a destination slot may be a later source, and source and destination may lie in different pages.  A row
+ * whose source or destination lies outside the cache (or the table) is skipped.  base_len is the history_lengths array THE FORWARD
+ * ran with: it must not be the array the verify advanced (cached_len) -- keep two arrays and copy cached -> base afterwards.
+ * LLMIE_ERR_INVALID_ARG: NULL caches / base_len / out_path / out_count, non-positive sizes, n < 1, elem_bytes not 1 or 2, a block
+ * table with max_pages < 1 or num_pages < 1, caches not 16-byte aligned; LLMIE_ERR_UNSUPPORTED: n above the maximum,
+ * head_size * elem_bytes not a multiple of 16 or above 512.  One launch (one workgroup per (layer x kv head, sequence, K or V) stages
+ * its rows in LDS, a barrier, then the stores); legal inside a graph capture.
+ *
+ * llmie_ngram_draft_tree: a tree drafter that needs no second model, on llmie_ngram_draft's operands.  L, "no drafts" (then
+ * out_node_count[b] = 1) and the matches are those of llmie_ngram_draft.  Candidates: for n' = min(max_n, L - 1) down to min_n, every
+ * n' that has a match contributes the continuation start llmie_ngram_draft would choose with max_n = n' (the largest start with k
+ * tokens behind it, else the largest at all); the first `branches` DISTINCT starts are kept, 1 <= branches <= 8, each with
+ * min(k, L - start) tokens, 1 <= k <= LLMIE_SPEC_MAX_DRAFT.  Trie merge, in that order: from the root, every token reuses the
+ * lowest existing child of the current node that carries it, else appends a new node while fewer than n exist; a candidate is cut
+ * where the budget ends.  Node order is creation order, so parent < child.  out_ids [batch, n]: node 0 the last token (pad_id when
+ * L == 0), unused slots pad_id; out_parent [batch, n]: -1 for node 0 and unused slots; out_node_count [batch].  With branches = 1
+ * the ids, the chain and node_count - 1 equal llmie_ngram_draft's outputs.  Bounds as llmie_ngram_draft's (LLMIE_ERR_INVALID_ARG
+ * below, LLMIE_ERR_UNSUPPORTED above), with n in [1, LLMIE_SPEC_TREE_MAX_NODES].  One launch, legal inside a graph capture. */
+#define LLMIE_SPEC_TREE_MAX_NODES 64
+int llmie_ngram_draft_tree(const int32_t *tokens /* [batch, stride] */, int stride, const int32_t *len /* [batch] */,
+                           const uint8_t *finished /* nullable */, int batch, int n, int k, int branches, int max_n, int min_n, int pad_id,
+                           int32_t *out_ids /* [batch, n] */, int32_t *out_parent /* [batch, n] */, int32_t *out_node_count /* [batch] */,
+                           llmie_stream stream);
+int llmie_spec_tree_prepare(const int32_t *parent /* [batch, n] */, const int32_t *node_count /* [batch], NULL = n; clamped to [1,n] */,
+                            int batch, int n, int32_t *depth_out /* [batch, n] */, uint64_t *anc_out /* [batch, n] */, llmie_stream stream);
+size_t llmie_spec_verify_tree_workspace_bytes(int batch, int n, int vocab);
+int llmie_spec_verify_tree(const void *logits /* [batch*n, vocab], row r = b*n+i */, int batch, int n, int vocab,
+                           const int32_t *node_ids /* [batch, n] */, const int32_t *parent /* [batch, n] */,
+                           const int32_t *depth /* [batch, n] */, const uint64_t *anc /* [batch, n] */,
+                           const llmie_sampling_params *params_dev /* [batch] */, int32_t *history, int history_stride,
+                           int32_t *history_len, int history_append, int32_t *seq_len, uint8_t *finished,
+                           int32_t *out_tokens /* [batch, n] */, int32_t *out_count /* [batch] */, int32_t *out_path /* [batch, n], nullable */,
+                           float *out_logprob /* [batch, n], nullable */, int32_t *last_token /* [batch], nullable */,
+                           int32_t *cached_len /* [batch], nullable, in/out */, int32_t *step_rows /* [batch], nullable, in/out */, int step,
+                           const int32_t *step_dev, int end_id, void *workspace, size_t workspace_bytes, llmie_dtype dtype,
+                           llmie_stream stream, const llmie_sampling_ext *ext /* nullable */);
+int llmie_kv_tree_commit(void *k_cache, void *v_cache, const int32_t *block_table /* [batch, max_pages] or NULL: dense */,
+                         const int32_t *base_len /* [batch]: the forward's history_lengths */, const int32_t *out_path /* [batch, n] */,
+                         const int32_t *out_count /* [batch] */, int batch, int n, int layers, int kv_head_num, int max_seq_len,
+                         int head_size, int max_pages, int num_pages, int elem_bytes, llmie_stream stream);
+
 /* ABI 3 (an addition).  Multi-LoRA: per-row adapters on top of a projection.  No reference launcher.
  *
  * For a projection y = x . W^T (W is [N, K]; x [rows, K], y [rows, N], fp16, row-major), row m carrying adapter slot s = slot[m] gets
@@ -1128,6 +1205,27 @@ int llmie_decoder_set_rope_scaling(llmie_decoder *dec, const llmie_rope_scaling 
 #define LLMIE_PLAN_QK_NORM 8192u /* QK-norm is set (llmie_decoder_set_qk_norm) */
 int llmie_decoder_set_qk_norm(llmie_decoder *dec, const void *q_gamma_dev, const void *k_gamma_dev /* device, [num_layers, head_size] fp16;
                               both NULL clears */, float eps);
+
+/* ABI 3 (an addition; llmie_decoder_config is not touched).  A draft tree on an engine: depth_dev / anc_dev = DEVICE arrays
+ * [batch, stride] as llmie_spec_tree_prepare leaves them (int32 / uint64), 1 <= stride <= LLMIE_SPEC_TREE_MAX_NODES; NULL, NULL, 0
+ * clears.  The pointers are kept on the engine, in the pattern of llmie_decoder_set_qk_norm; the VALUES are read on the device at
+ * every launch, so a captured step follows a new tree on replay.  While a tree is set, every prefill entry (llmie_decoder_prefill,
+ * _prefill_paged and the LoRA and MoE sequences built on them) treats position i < input_lengths[b] of sequence b as node i:
+ *   RoPE + append: q and k are rotated by the table row history[b] + clamp(depth[b, i], 0, i); k / v go to slot history[b] + i;
+ *   attention: query i sees key t iff t < history[b], or t = history[b] + j with bit j of
+ *     (anc[b, i] & ((2 << i) - 1)) | (1 << i) set (64-bit): bits above i are ignored and the self bit is forced, so no row is
+ *     fully masked.
+ * Such a call always plans the 64-row flash form (q64w4t1) behind the RoPE + append launch and the QKV forms without the RoPE
+ * epilogue, as QK-norm does; it composes with QK-norm and the e4m3 cache.  A chain -- depth[i] = i, anc[i] = (2 << i) - 1 -- gives
+ * the bits of the same call without a tree wherever that call plans q64w4t1.  The decode entries ignore the tree.
+ * LLMIE_ERR_INVALID_ARG: exactly one array NULL, stride outside [1, 64] (or not 0 when clearing), misaligned arrays; a prefill call
+ * with max_q_len > stride while a tree is set.  LLMIE_ERR_UNSUPPORTED, nothing written: an engine without a prefill path; a sliding
+ * window or head sinks set on the engine -- and llmie_decoder_set_window / llmie_decoder_set_head_sinks with a non-NULL argument
+ * refuse while a tree is set (both are follow-ups).  llmie_decoder_plan_name and llmie_decoder_prefill_layer_plan answer for such a
+ * call under LLMIE_PLAN_TREE (refused together with LLMIE_PLAN_WINDOW / LLMIE_PLAN_HEAD_SINK; the layer plan ends in " tree"). */
+#define LLMIE_PLAN_TREE 16384u /* a draft tree is set (llmie_decoder_set_tree) */
+int llmie_decoder_set_tree(llmie_decoder *dec, const int32_t *depth_dev, const uint64_t *anc_dev /* device, [batch, stride]; both NULL clears */,
+                           int stride);
 
 /* ABI 3 (an addition).  Mixture-of-experts FFN, Mixtral / Qwen-MoE semantics: every row is routed to top_k of `experts` expert FFNs.
  * fp16 activations and fp16 experts only.  Operands (device, 16-byte aligned): x [rows, hidden]; router Wr [experts, hidden];

@@ -138,6 +138,13 @@ _SIGS = {
     "llmie_spec_verify_sampled_workspace_bytes": [_i, _i, _i],
     "llmie_spec_verify_sampled": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
                                   _vp, _i, _vp, _sz, _i, _vp, _vp],
+    "llmie_spec_tree_prepare": [_vp, _vp, _i, _i, _vp, _vp, _vp],
+    "llmie_spec_verify_tree_workspace_bytes": [_i, _i, _i],
+    "llmie_spec_verify_tree": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                               _vp, _i, _vp, _sz, _i, _vp, _vp],
+    "llmie_kv_tree_commit": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "llmie_ngram_draft_tree": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "llmie_decoder_set_tree": [_vp, _vp, _vp, _i],
     "llmie_lora_table_bytes": [_i, _i],
     "llmie_lora_slot_load": [_vp, _i, _i, _i, _vp, _vp],
     "llmie_lora_workspace_bytes": [_i, _i, _i],
@@ -187,6 +194,7 @@ _RESTYPES = {
     "llmie_kv_pages_fork_workspace_bytes": _sz,
     "llmie_spec_verify_workspace_bytes": _sz,
     "llmie_spec_verify_sampled_workspace_bytes": _sz,
+    "llmie_spec_verify_tree_workspace_bytes": _sz,
     "llmie_lora_table_bytes": _sz,
     "llmie_lora_workspace_bytes": _sz,
     "llmie_decoder_lora_workspace_bytes": _sz,
@@ -1085,6 +1093,22 @@ class Decoder:
         _check(lib().llmie_decoder_set_qk_norm(self.handle, _p(q_gamma), _p(k_gamma), eps), "decoder_set_qk_norm")
         self._qk_norm_keep = (q_gamma, k_gamma)
 
+    def set_tree(self, depth, anc):
+        """a draft tree (llmie_decoder_set_tree): depth int32 / anc int64 device tensors [batch, stride] as spec_tree_prepare leaves
+        them, kept alive by this object and read on the device at every prefill launch; both None clears"""
+        import torch
+        if depth is None and anc is None:
+            _check(lib().llmie_decoder_set_tree(self.handle, None, None, 0), "decoder_set_tree")
+            self._tree_keep = None
+            return
+        if depth is not None and anc is not None:
+            if (depth.dtype != torch.int32 or anc.dtype != torch.int64 or depth.dim() != 2 or tuple(depth.shape) != tuple(anc.shape)
+                    or not depth.is_contiguous() or not anc.is_contiguous()):
+                raise LlmieError("set_tree: needs contiguous int32 depth and int64 anc tensors of one shape [batch, stride]")
+        stride = (depth if depth is not None else anc).shape[-1]
+        _check(lib().llmie_decoder_set_tree(self.handle, _p(depth), _p(anc), stride), "decoder_set_tree")
+        self._tree_keep = (depth, anc)
+
     def set_rope_scaling(self, scaling):
         """RoPE frequency scaling (llmie_decoder_set_rope_scaling): refills and uploads the engine's (cos, sin) table -- one synchronous
         copy, not inside a graph capture.  scaling: see rope_scaling(); None restores the create-time table"""
@@ -1199,6 +1223,7 @@ PLAN_LORA = 1024        # LLMIE_PLAN_LORA
 PLAN_WINDOW = 2048      # LLMIE_PLAN_WINDOW
 PLAN_HEAD_SINK = 4096   # LLMIE_PLAN_HEAD_SINK
 PLAN_QK_NORM = 8192     # LLMIE_PLAN_QK_NORM
+PLAN_TREE = 16384       # LLMIE_PLAN_TREE
 PLAN_PAGED, PLAN_RAGGED, PLAN_HIDDEN_MISALIGNED = 1, 2, 4   # LLMIE_PLAN_* call flags of decoder_plan_name
 
 
@@ -1667,6 +1692,106 @@ def ngram_draft(tokens, length, k, max_n=3, min_n=1, pad_id=0, finished=None, ou
     _check(lib().llmie_ngram_draft(_p(tokens), stride, _p(length), _p(finished), batch, k, max_n, min_n, pad_id, _p(ids), _p(draft_ids),
                                    _p(draft_len), _st()), "ngram_draft")
     return ids, draft_ids, draft_len
+
+
+# ---- draft trees: several alternatives per position, verified in one forward
+SPEC_TREE_MAX_NODES = 64  # LLMIE_SPEC_TREE_MAX_NODES
+NGRAM_TREE_MAX_BRANCHES = 8
+
+
+class SpecTreeState:
+    """What one tree step passes between its launches, all [batch, n] unless noted: ids (the token of each node; node 0 = the last
+    emitted token), parent, node_count [batch], depth, anc (int64: the bits of the uint64 ancestor masks), and the verify's outputs
+    tokens, count [batch], path.  The tensors are written in place, so a captured step follows a new tree on replay."""
+
+    def __init__(self, ids, parent, node_count, depth, anc, tokens, count, path):
+        self.ids, self.parent, self.node_count, self.depth, self.anc = ids, parent, node_count, depth, anc
+        self.tokens, self.count, self.path = tokens, count, path
+        self.n = ids.shape[1]
+
+
+def spec_tree_state(batch, n, device="cuda"):
+    """an empty SpecTreeState for `batch` sequences of n node slots (1 <= n <= SPEC_TREE_MAX_NODES)"""
+    import torch
+    if not 1 <= n <= SPEC_TREE_MAX_NODES:
+        raise LlmieError("spec_tree_state: n %d outside [1,%d]" % (n, SPEC_TREE_MAX_NODES))
+    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+    parent = torch.full((batch, n), -1, dtype=torch.int32, device=device)
+    return SpecTreeState(z(batch, n), parent, torch.ones(batch, dtype=torch.int32, device=device), z(batch, n),
+                         torch.zeros((batch, n), dtype=torch.int64, device=device), z(batch, n), z(batch), z(batch, n))
+
+
+def spec_tree_prepare(parent, node_count=None, out=None):
+    """llmie_spec_tree_prepare on parent int32 [batch, n] (node_count int32 [batch] or None = n): returns (depth int32 [batch, n],
+    anc int64 [batch, n] -- the bits of the uint64 ancestor masks; live = bit 0).  out: such a pair to write into."""
+    import torch
+    batch, n = parent.shape
+    depth, anc = out if out is not None else (torch.empty((batch, n), dtype=torch.int32, device=parent.device),
+                                              torch.empty((batch, n), dtype=torch.int64, device=parent.device))
+    _check(lib().llmie_spec_tree_prepare(_p(parent), _p(node_count), batch, n, _p(depth), _p(anc), _st()), "spec_tree_prepare")
+    return depth, anc
+
+
+def spec_verify_tree_workspace_bytes(batch, n, vocab):
+    return lib().llmie_spec_verify_tree_workspace_bytes(batch, n, vocab)
+
+
+def spec_verify_tree(logits, node_ids, parent, depth, anc, params, seq_len, finished, end_id, state=None, history=None, history_len=None,
+                     append=False, out_logprob=None, step=0, step_dev=None, workspace="auto", ext=None, out=None):
+    """llmie_spec_verify_tree on logits [batch * n, vocab] (row b * n + i follows node i of sequence b), node_ids / parent int32
+    [batch, n] and depth / anc as spec_tree_prepare left them: returns (tokens int32 [batch, n], count int32 [batch], path int32
+    [batch, n] -- the node of every emitted token, -1 behind count) and moves seq_len, finished, the history and `state` (a
+    SpecState) as spec_verify does.  ext: sampling_ext(...) with batch * n rows.  out: a (tokens, count, path) triple to write
+    into.  workspace: spec_verify_tree_workspace_bytes(batch, n, vocab) bytes, or the string auto (as in spec_verify)."""
+    import torch
+    batch, n = node_ids.shape
+    rows, vocab = logits.shape
+    if rows != batch * n:
+        raise LlmieError("spec_verify_tree: %d rows of logits for %d sequences of %d nodes" % (rows, batch, n))
+    if isinstance(workspace, str):
+        workspace = _grow(_spec_scratch, logits.device, spec_verify_tree_workspace_bytes(batch, n, vocab))
+    tokens, count, path = out if out is not None else (torch.empty((batch, n), dtype=torch.int32, device=logits.device),
+                                                       torch.empty(batch, dtype=torch.int32, device=logits.device),
+                                                       torch.empty((batch, n), dtype=torch.int32, device=logits.device))
+    stride = 0 if history is None else history.shape[1]
+    st = state if state is not None else SpecState(None, None, None)
+    _check(lib().llmie_spec_verify_tree(_p(logits), batch, n, vocab, _p(node_ids), _p(parent), _p(depth), _p(anc), _p(params), _p(history),
+                                        stride, _p(history_len), 1 if append else 0, _p(seq_len), _p(finished), _p(tokens), _p(count),
+                                        _p(path), _p(out_logprob), _p(st.last_token), _p(st.cached_len), _p(st.step_rows), step,
+                                        _p(step_dev), end_id, _p(workspace),
+                                        0 if workspace is None else workspace.numel() * workspace.element_size(), _dt(logits), _st(),
+                                        None if ext is None else _ext_ref(ext)), "spec_verify_tree")
+    return tokens, count, path
+
+
+def kv_tree_commit(k_cache, v_cache, base_len, path, count, block_table=None):
+    """llmie_kv_tree_commit: moves the K / V rows of the accepted path into place -- node path[b, m] from slot base_len[b] +
+    path[b, m] to base_len[b] + m, every layer and kv head.  Dense caches [L, batch, kvh, max_seq, hs] (block_table None) or pools
+    [L, num_pages, kvh, 128, hs] with block_table int32 [batch, max_pages]; fp16 or e4m3 bytes.  base_len: the history_lengths
+    the forward ran with -- NOT the array spec_verify_tree advanced."""
+    batch, n = path.shape
+    L, d1, kvh, d3, hs = k_cache.shape
+    if block_table is None:
+        max_seq, max_pages, num_pages = d3, 0, 0
+    else:
+        max_seq, max_pages, num_pages = 0, block_table.shape[1], d1
+    _check(lib().llmie_kv_tree_commit(_p(k_cache), _p(v_cache), _p(block_table), _p(base_len), _p(path), _p(count), batch, n, L, kvh,
+                                      max_seq, hs, max_pages, num_pages, k_cache.element_size(), _st()), "kv_tree_commit")
+
+
+def ngram_draft_tree(tokens, length, n, k, branches=4, max_n=3, min_n=1, pad_id=0, finished=None, out=None):
+    """llmie_ngram_draft_tree on tokens int32 [batch, stride] with length int32 [batch]: up to `branches` prompt-lookup
+    continuations of up to k tokens each (one per matching suffix length, longest first) merged into a trie of at most n nodes.
+    Returns (ids int32 [batch, n] -- node 0 the last token, unused slots pad_id --, parent int32 [batch, n] -- -1 for node 0 and
+    unused slots --, node_count int32 [batch]).  out: such a triple to write into."""
+    import torch
+    batch, stride = tokens.shape
+    ids, parent, node_count = out if out is not None else (torch.empty((batch, n), dtype=torch.int32, device=tokens.device),
+                                                           torch.empty((batch, n), dtype=torch.int32, device=tokens.device),
+                                                           torch.empty(batch, dtype=torch.int32, device=tokens.device))
+    _check(lib().llmie_ngram_draft_tree(_p(tokens), stride, _p(length), _p(finished), batch, n, k, branches, max_n, min_n, pad_id,
+                                        _p(ids), _p(parent), _p(node_count), _st()), "ngram_draft_tree")
+    return ids, parent, node_count
 
 
 def linear_fp8_workspace_bytes(M, K, N=0):

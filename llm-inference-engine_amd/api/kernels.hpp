@@ -368,6 +368,62 @@ inline void launchNgramDraft(TensorWrapper<int> *tokens, TensorWrapper<int> *len
                                  max_n, min_n, pad_id, out_ids->data, out_draft_ids->data, out_draft_len->data, llmie_api::st()));
 }
 
+// No reference launchers: draft TREES (include/llmie.h has the rules).  parent [batch, n] (node_count [batch] or null = n) ->
+// depth [batch, n], anc [batch, n] (64-bit ancestor masks; live = bit 0).
+inline void launchSpecTreePrepare(TensorWrapper<int> *parent, TensorWrapper<int> *node_count, TensorWrapper<int> *depth, uint64_t *anc) {
+    const int batch = parent->shape[0], n = parent->shape[1];
+    LLM_CHECK_WITH_INFO(depth->shape[0] == batch && depth->shape[1] == n, "depth should be [batch, n]");
+    LLMIE_CALL(llmie_spec_tree_prepare(parent->data, node_count ? node_count->data : nullptr, batch, n, depth->data, anc, llmie_api::st()));
+}
+
+// launchSpecVerify's operands with the draft chain replaced by a tree: node_ids / parent / depth [batch, n] and anc as
+// launchSpecTreePrepare left them; logits [batch * n, vocab]; out_tokens / out_path (may be null) / out_logprob (may be null) [batch, n].
+template <typename T>
+void launchSpecVerifyTree(TensorWrapper<T> *logits, TensorWrapper<int> *node_ids, TensorWrapper<int> *parent, TensorWrapper<int> *depth,
+                          const uint64_t *anc, const llmie_sampling_params *params_dev, TensorWrapper<int> *history,
+                          TensorWrapper<int> *history_len, bool history_append, TensorWrapper<int> *seq_len, TensorWrapper<bool> *finished,
+                          TensorWrapper<int> *out_tokens, TensorWrapper<int> *out_count, TensorWrapper<int> *out_path,
+                          TensorWrapper<float> *out_logprob, TensorWrapper<int> *last_token, TensorWrapper<int> *cached_len,
+                          TensorWrapper<int> *step_rows, int step, int end_id, const llmie_sampling_ext *ext = nullptr) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int batch = node_ids->shape[0], n = node_ids->shape[1], vocab = logits->shape[1];
+    LLM_CHECK_WITH_INFO(logits->shape[0] == batch * n, "logits rows should equal batch * n");
+    const size_t ws = llmie_spec_verify_tree_workspace_bytes(batch, n, vocab);
+    LLMIE_CALL(llmie_spec_verify_tree(logits->data, batch, n, vocab, node_ids->data, parent->data, depth->data, anc, params_dev,
+                                      history ? history->data : nullptr, history ? history->shape[1] : 0,
+                                      history_len ? history_len->data : nullptr, history_append ? 1 : 0, seq_len->data,
+                                      reinterpret_cast<uint8_t *>(finished->data), out_tokens->data, out_count->data,
+                                      out_path ? out_path->data : nullptr, out_logprob ? out_logprob->data : nullptr,
+                                      last_token ? last_token->data : nullptr, cached_len ? cached_len->data : nullptr,
+                                      step_rows ? step_rows->data : nullptr, step, nullptr, end_id, llmie_api::scratch(ws), ws,
+                                      llmie_api::dtype_of<T>(), llmie_api::st(), ext));
+}
+
+// Behind the verify: the K / V rows of the accepted path move from slot base_len + out_path[m] to base_len + m.  Caches
+// [L, batch, kvh, max_seq_len, hs], or pools [L, num_pages, kvh, 128, hs] with block_table [batch, max_pages].  base_len: the
+// history lengths THE FORWARD ran with (not the array the verify advanced).
+template <typename T>
+void launchKvTreeCommit(TensorWrapper<T> *k_cache, TensorWrapper<T> *v_cache, TensorWrapper<int> *block_table, TensorWrapper<int> *base_len,
+                        TensorWrapper<int> *out_path, TensorWrapper<int> *out_count) {
+    const int batch = out_path->shape[0], n = out_path->shape[1];
+    const int layers = k_cache->shape[0], kvh = k_cache->shape[2], hs = k_cache->shape[4];
+    LLMIE_CALL(llmie_kv_tree_commit(k_cache->data, v_cache->data, block_table ? block_table->data : nullptr, base_len->data, out_path->data,
+                                    out_count->data, batch, n, layers, kvh, block_table ? 0 : k_cache->shape[3], hs,
+                                    block_table ? block_table->shape[1] : 0, block_table ? k_cache->shape[1] : 0, static_cast<int>(sizeof(T)),
+                                    llmie_api::st()));
+}
+
+// launchNgramDraft's tree form: up to `branches` continuations of up to k tokens merged into a trie of out_ids->shape[1] nodes
+inline void launchNgramDraftTree(TensorWrapper<int> *tokens, TensorWrapper<int> *len, TensorWrapper<bool> *finished, int k, int branches,
+                                 int max_n, int min_n, int pad_id, TensorWrapper<int> *out_ids, TensorWrapper<int> *out_parent,
+                                 TensorWrapper<int> *out_node_count) {
+    static_assert(sizeof(bool) == 1, "finished flags are one byte each");
+    const int batch = tokens->shape[0], stride = tokens->shape[1], n = out_ids->shape[1];
+    LLM_CHECK_WITH_INFO(out_ids->shape[0] == batch && out_parent->shape[0] == batch && out_parent->shape[1] == n, "out_ids / out_parent should be [batch, n]");
+    LLMIE_CALL(llmie_ngram_draft_tree(tokens->data, stride, len->data, finished ? reinterpret_cast<uint8_t *>(finished->data) : nullptr, batch, n,
+                                      k, branches, max_n, min_n, pad_id, out_ids->data, out_parent->data, out_node_count->data, llmie_api::st()));
+}
+
 // No reference launcher: decode attention of a ragged batch under a sliding window with sink tokens (include/llmie.h has the mask):
 // qkv_buf [batch, head_num + 2 kv_head_num, head_size] (bias: the QKV bias or null), ctx_len [batch] = context length of every
 // sequence with this step's token, caches [L, batch, kvh, max_seq_len, hs] -- or, with block_table [batch, max_pages], page pools

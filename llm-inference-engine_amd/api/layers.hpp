@@ -117,7 +117,18 @@ public:
         qk_norm_dirty = true;
     }
 
+    // A draft tree (include/llmie.h llmie_decoder_set_tree): DEVICE arrays [batch, stride] as llmie_spec_tree_prepare leaves them, which
+    // the caller keeps alive (both null, stride 0: none); set on every engine this holder creates.  Prefill entries only.
+    void set_tree(const int32_t *depth_dev, const uint64_t *anc_dev, int stride) {
+        tree_depth = depth_dev, tree_anc = anc_dev, tree_stride = stride;
+        tree_dirty = true;
+    }
+
 private:
+    const int32_t *tree_depth = nullptr;
+    const uint64_t *tree_anc = nullptr;
+    int tree_stride = 0;
+    bool tree_dirty = false;
     const void *q_gammas = nullptr, *k_gammas = nullptr;
     float qk_eps = 0.f;
     bool qk_norm_dirty = false;
@@ -130,7 +141,8 @@ private:
         if (sinks_dirty) LLMIE_CALL(llmie_decoder_set_head_sinks(engine, head_sinks));
         if (rope_dirty) LLMIE_CALL(llmie_decoder_set_rope_scaling(engine, rope_scaling.kind == LLMIE_ROPE_NONE ? nullptr : &rope_scaling));
         if (qk_norm_dirty) LLMIE_CALL(llmie_decoder_set_qk_norm(engine, q_gammas, k_gammas, qk_eps));
-        sinks_dirty = rope_dirty = qk_norm_dirty = false;
+        if (tree_dirty) LLMIE_CALL(llmie_decoder_set_tree(engine, tree_depth, tree_anc, tree_stride));
+        sinks_dirty = rope_dirty = qk_norm_dirty = tree_dirty = false;
     }
     std::vector<int> window;
     int window_sinks = 0;
@@ -260,6 +272,7 @@ public:
         window_dirty = !window.empty();
         sync_window();
         sinks_dirty = head_sinks != nullptr, rope_dirty = rope_scaling.kind != LLMIE_ROPE_NONE, qk_norm_dirty = q_gammas != nullptr;
+        tree_dirty = tree_anc != nullptr;
         sync_attention();
         return engine;
     }
@@ -617,6 +630,8 @@ public:
     void setWindow(const std::vector<int> &layer_window, int sinks) { engine_holder.set_window(layer_window, sinks); }
     void setHeadSinks(const float *head_sink_dev) { engine_holder.set_head_sinks(head_sink_dev); }
     void setQkNorm(const void *q_gamma_dev, const void *k_gamma_dev, float eps) { engine_holder.set_qk_norm(q_gamma_dev, k_gamma_dev, eps); }
+    // a draft tree for the next prefill calls (EngineHolder::set_tree); nullptr, nullptr, 0 clears
+    void setTree(const int32_t *depth_dev, const uint64_t *anc_dev, int stride) { engine_holder.set_tree(depth_dev, anc_dev, stride); }
     void setRopeScaling(const llmie_rope_scaling &s) { engine_holder.set_rope_scaling(s); }
     void setExperts(const typename EngineHolder<T>::MoeBinding &b) { engine_holder.set_moe(b); }
 

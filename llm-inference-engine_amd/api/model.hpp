@@ -82,6 +82,7 @@ private:
     DevBuf<int> d_penalty_ids, d_penalty_len;
     DevBuf<unsigned char> d_sample_ws, d_score_ws;
     DevBuf<int> d_targets, d_spec;
+    DevBuf<uint64_t> d_tree_anc;
     DevBuf<float> d_logprob;
     DevBuf<unsigned char> d_lora_table;   // the adapter slot table (loadAdapter)
     DevBuf<int> d_lora_slot;              // the slot of the one sequence this model runs
@@ -461,8 +462,79 @@ public:
         h_step = cached + count;   // `last` and the accepted drafts are cached; the last pick is not
         return got;
     }
+    // speculativeStep with a draft TREE (include/llmie.h llmie_spec_verify_tree): node 0 is `last`, node i >= 1 carries draft_ids[i - 1]
+    // and hangs on parent[i] (parent[0] is not read; parent < child), n = draft_ids.size() + 1 <= LLMIE_SPEC_TREE_MAX_NODES.  One
+    // forward over the n nodes with the tree set on the context decoder (a node sees the history and its ancestors, and is rotated at
+    // cached + depth), the LM head on every row, the walk, then llmie_kv_tree_commit moves the accepted nodes' K / V rows to the slots
+    // cached + m.  Returns the emitted tokens (path: the node of each, if wanted); state moves as in speculativeStep.  Needs the
+    // fused engine (fp16, head_size 128): the per-kernel loops know no tree.  lastLogits() holds the [n, vocab_size] rows.
+    std::vector<int> speculativeTreeStep(int last, const std::vector<int> &draft_ids, const std::vector<int> &parent, std::vector<int> *path = nullptr) {
+        const int n = static_cast<int>(draft_ids.size()) + 1, cached = h_step;
+        LLM_CHECK_WITH_INFO(n >= 1 && n <= LLMIE_SPEC_TREE_MAX_NODES && static_cast<int>(parent.size()) == n, "1 .. LLMIE_SPEC_TREE_MAX_NODES nodes, one parent each");
+        LLM_CHECK_WITH_INFO((std::is_same<T, half>::value) && head_size == 128 && EngineHolder<T>::usable(&layer_ptrs),
+                            "speculativeTreeStep: tree attention needs the fused engine (fp16, head_size 128, every layer matrix in HF layout)");
+        std::vector<int> chunk{last};
+        chunk.insert(chunk.end(), draft_ids.begin(), draft_ids.end());
+        // tree [n]: parent | depth | ids | tokens | path | count, then the 64-bit masks
+        int *tree = d_spec.ensure(5 * n + 1);
+        uint64_t *anc = d_tree_anc.ensure(n);
+        int *d_parent = tree, *d_depth = tree + n, *d_node_ids = tree + 2 * n, *d_tokens = tree + 3 * n, *d_path = tree + 4 * n, *d_count = tree + 5 * n;
+        CHECK(hipMemcpyAsync(d_parent, parent.data(), sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(d_node_ids, chunk.data(), sizeof(int) * n, hipMemcpyHostToDevice, llmie_api::st()));
+        LLMIE_CALL(llmie_spec_tree_prepare(d_parent, nullptr, 1, n, d_depth, anc, llmie_api::st()));
+        const size_t fed = penalty_ids.size();
+        // the tree is set for this one prefill call only: the guard clears it on every way out, an exception of runContext (a chunk that
+        // does not fit) included, so that no later prefill reads this step's buffers (takes effect at the next prefill call)
+        struct TreeGuard {
+            LlamaContextDecoder<T> *dec;
+            ~TreeGuard() { dec->setTree(nullptr, nullptr, 0); }
+        };
+        T *ctx_out = nullptr;
+        {
+            TreeGuard guard{context_decoder.get()};
+            context_decoder->setTree(d_depth, anc, n);
+            ctx_out = runContext(chunk, cached);   // (checks the fit; resets finished / seq_len; leaves cached in d_hist_len)
+        }
+        penalty_ids.resize(fed);
+        penalty_ids.push_back(last);
+        const DataType ty = getTensorType<T>();
+        TensorWrapper<T> x(Device::GPU, ty, {n, hidden_units}, ctx_out);
+        TensorWrapper<T> unused(Device::GPU, ty, {n, hidden_units}, d_unused.ensure(static_cast<size_t>(n) * hidden_units));
+        launchRMSNorm(&x, &unused, &llama_weights->out_rmsnorm_weight, rmsnorm_eps, true);
+        TensorWrapper<T> probs(Device::GPU, ty, {n, vocab_size}, d_probs.ensure(static_cast<size_t>(n) * vocab_size));
+        launchLinearGemm(&x, &llama_weights->post_decoder_embedding_weight, &probs, cublas_wrapper, false, true);
+        const llmie_sampling_params p{sampling.temperature, sampling.top_k, sampling.top_p, sampling.min_p,
+                                      sampling.repetition_penalty, sampling.presence_penalty, sampling.frequency_penalty,
+                                      sampling.seed};
+        const int room = LLMIE_SAMPLE_MAX_HISTORY - n;
+        const int nh = static_cast<int>(std::min<size_t>(penalty_ids.size(), room)), stride = nh + n;
+        int *hist = d_penalty_ids.ensure(stride), *hlen = d_penalty_len.ensure(1);
+        CHECK(hipMemcpyAsync(d_sparams.ensure(1), &p, sizeof(p), hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(hist, penalty_ids.data() + (penalty_ids.size() - nh), sizeof(int) * nh, hipMemcpyHostToDevice, llmie_api::st()));
+        CHECK(hipMemcpyAsync(hlen, &nh, sizeof(int), hipMemcpyHostToDevice, llmie_api::st()));
+        const size_t ws = llmie_spec_verify_tree_workspace_bytes(1, n, vocab_size);
+        LLMIE_CALL(llmie_spec_verify_tree(probs.data, 1, n, vocab_size, d_node_ids, d_parent, d_depth, anc, d_sparams.p, hist, stride, hlen, 1,
+                                          d_seq_len.p, reinterpret_cast<uint8_t *>(d_finished.p), d_tokens, d_count, d_path, nullptr, nullptr,
+                                          nullptr, nullptr, cached + 1, nullptr, eos_token_id, d_sample_ws.ensure(ws), ws,
+                                          llmie_api::dtype_of<T>(), llmie_api::st(), nullptr));
+        // base_len = the history length the forward ran with (d_hist_len, which nothing advanced)
+        LLMIE_CALL(llmie_kv_tree_commit(d_kcache.p, d_vcache.p, nullptr, d_hist_len.p, d_path, d_count, 1, n, num_layers, kv_head_num, max_seq_len,
+                                        head_size, 0, 0, static_cast<int>(sizeof(T)), llmie_api::st()));
+        std::vector<int> got(2 * n + 1);
+        CHECK(hipMemcpyAsync(got.data(), d_tokens, sizeof(int) * (2 * n + 1), hipMemcpyDeviceToHost, llmie_api::st()));
+        CHECK(hipStreamSynchronize(llmie_api::st()));   // (also keeps p / nh / the tree alive until the copies are done)
+        const int count = got[2 * n];
+        if (path) path->assign(got.begin() + n, got.begin() + n + count);
+        got.resize(count);
+        penalty_ids.insert(penalty_ids.end(), got.begin(), got.end() - 1);   // the last pick joins when it is fed
+        h_step = cached + count;   // `last` and the accepted nodes are cached, in place; the last pick is not
+        return got;
+    }
     // the context decoder's output [n, hidden_units] of the last prefill (generateFirstToken normalises its last row in place)
     const T *contextOutput() const { return d_ctx_out.p; }
+    // the K cache [num_layers, 1, kv_head_num, max_seq_len, head_size] and the number of its rows that are valid (the cached tokens)
+    const T *keyCache() const { return d_kcache.p; }
+    int cachedLength() const { return h_step; }
     // the self decoder's output [1, hidden_units] of the last decode step, before the final norm
     const T *decodeOutput() const { return d_dec_out.p; }
     // the decode step response() runs after a prefill: token `id` joins the context, then generateNextToken

@@ -86,6 +86,11 @@ struct llmie_decoder {
     float qk_eps = 0.f;
     const half_t *q_gamma_of(int layer) const { return q_gammas ? q_gammas + static_cast<size_t>(layer) * cfg.head_size : nullptr; }
     const half_t *k_gamma_of(int layer) const { return k_gammas ? k_gammas + static_cast<size_t>(layer) * cfg.head_size : nullptr; }
+    // draft tree (llmie_decoder_set_tree): the caller's device arrays [batch, tree_stride] as llmie_spec_tree_prepare leaves them, or
+    // null / null / 0; read by every prefill launch that is built while they are set (the decode entries do not know them)
+    const int32_t *tree_depth = nullptr;
+    const uint64_t *tree_anc = nullptr;
+    int tree_stride = 0;
     // profiling (eager only)
     bool profiling = false;
     std::vector<hipEvent_t> ev;      // pairs: start, stop
@@ -836,6 +841,7 @@ struct PrefillCall {
     bool lora;                // an adapter table is attached
     bool moe;                 // experts are attached
     bool qk_norm;             // QK-norm is set: q and k are normalised in the RoPE + append launch, so no QKV form does RoPE itself
+    bool tree = false;        // a draft tree is set: the RoPE + append launch rotates by depth, so no QKV form does RoPE itself
 };
 struct PrefillPlan {
     int path, refusal;
@@ -905,7 +911,7 @@ struct PrefillLayerPlan {
 // accumulator).  Prefill-sized T on the eight-phase kernels only; everything else keeps the two launches.  (Pass level: a pass where
 // this holds writes the epilogue's token table once, whatever its layers end up choosing.)
 static bool prefill_rope_fusable(const PrefillCall &p) {
-    return !p.lora && !p.moe && !p.qk_norm && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
+    return !p.lora && !p.moe && !p.qk_norm && !p.tree && p.cfg.wfmt != LLMIE_W_MXFP4 && !p.sw.no_qkv_rope_fusion && p.T >= kWqPrefillRows && gemm256_fills(p.T, (p.cfg.head_num + 2 * p.cfg.kv_head_num) * p.cfg.head_size);
 }
 static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int batch, int max_q_len, const PrefillLayerCall &lc) {
     const llmie_decoder_config &c = p.cfg;
@@ -925,7 +931,7 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
     if (path == PP_SHORT_SPLITK) {
         // (the slab consumer of the QKV projection does RoPE + the cache append as well: one launch less per layer)
         const SplitKSlabs sk{slabs.p, 1, T, QKV};
-        o.qkv = !p.sw.no_qkv_rope_fusion && !p.qk_norm && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
+        o.qkv = !p.sw.no_qkv_rope_fusion && !p.qk_norm && !p.tree && splitk_finalize_qkv_rope_eligible(sk, c.head_size, ws, at(lc.mis_qkv_bias)) ? PQ_SPLITK_ROPE : PQ_SPLITK;
         o.attn_norm = PN_NONE, o.ffn_norm = PN_ROWNORM, o.gate_up = PG_SPLITK;
     } else if (path == PP_LORA || path == PP_MOE || c.wfmt == LLMIE_W_MXFP4) {
         // the general sequence with the forms the adapter updates need: normalised rows in place, the QKV buffer un-rotated (the update
@@ -974,7 +980,7 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
     }
     o.rope_done = o.qkv == PQ_ROPE_F16 || o.qkv == PQ_ROPE_W8 || o.qkv == PQ_ROPE_IMAGE || o.qkv == PQ_ROPE_E4M3 || o.qkv == PQ_ROPE_UNPACKED ||
                   o.qkv == PQ_SPLITK_ROPE;
-    o.attn = plan_prefill_attn(batch, max_q_len, c.head_num, c.kv_fmt == LLMIE_KV_FP8, o.rope_done);
+    o.attn = plan_prefill_attn(batch, max_q_len, c.head_num, c.kv_fmt == LLMIE_KV_FP8, o.rope_done, 0, 0, p.tree);
     // (the split-K sequence's ATTN_NORM launch is the row kernel behind the down projection)
     for (int op : {LLMIE_OP_ATTN_NORM, LLMIE_OP_QKV_GEMM, LLMIE_OP_MHA, LLMIE_OP_O_GEMM, LLMIE_OP_FFN_NORM, LLMIE_OP_GATE_UP_SWIGLU, LLMIE_OP_DOWN_GEMM})
         o.launches[op] = 1;
@@ -988,8 +994,11 @@ static PrefillLayerPlan plan_prefill_layer(const PrefillCall &p, int path, int b
 static PrefillCall prefill_call_of_flags(const llmie_decoder_config &cfg, int tokens, unsigned call_flags, const EngineSwitches &sw) {
     return PrefillCall{cfg, tokens, !(call_flags & LLMIE_PLAN_WEIGHTS_MISALIGNED), !(call_flags & LLMIE_PLAN_SCALES_MISALIGNED),
                        !(call_flags & (LLMIE_PLAN_HIDDEN_MISALIGNED | LLMIE_PLAN_GAMMAS_MISALIGNED)), (call_flags & LLMIE_PLAN_O_BIAS) != 0, sw,
-                       (call_flags & LLMIE_PLAN_LORA) != 0, false, (call_flags & LLMIE_PLAN_QK_NORM) != 0};
+                       (call_flags & LLMIE_PLAN_LORA) != 0, false, (call_flags & LLMIE_PLAN_QK_NORM) != 0, (call_flags & LLMIE_PLAN_TREE) != 0};
 }
+// a draft tree and a sliding window / head sinks exclude each other (named follow-ups)
+static const char *const kTreeRefusal =
+    "a draft tree needs an engine with a prefill path (fp16 activations, head_size 128) and neither a sliding window nor head sinks set";
 // what QK-norm needs of an engine's config (beside the geometry): nothing a config says rules it out but the geometry; the layers'
 // QKV biases and the window / head-sink state are the engine's (llmie_decoder_set_qk_norm)
 static bool qk_norm_engine_ok(const llmie_decoder_config &c) { return window_engine_ok(c); }
@@ -1017,6 +1026,10 @@ extern "C" const char *llmie_decoder_plan_name(const llmie_decoder_config *cfg, 
     }
     if ((call_flags & LLMIE_PLAN_QK_NORM) && (!qk_norm_engine_ok(*cfg) || (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK)))) {
         set_error("decoder_plan_name: %s", kQkNormRefusal);
+        return nullptr;
+    }
+    if ((call_flags & LLMIE_PLAN_TREE) && (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK))) {
+        set_error("decoder_plan_name: %s", kTreeRefusal);
         return nullptr;
     }
     if (prefill) {
@@ -1604,7 +1617,8 @@ struct PrefillPass {
         ap.head_sink = dec->head_sinks != nullptr;
         return prefill_attention_f16(ap, kv, qkv, (const half_t *)wqkv.bias, attn, cum, history_lengths, dec->rope_table, l, T, c.kv_head_num,
                                      c.max_seq_len, c.rotary_dim, st, dec->head_sink_of(l),
-                                     PrefillQkNorm{dec->q_gamma_of(l), dec->k_gamma_of(l), dec->qk_eps});
+                                     PrefillQkNorm{dec->q_gamma_of(l), dec->k_gamma_of(l), dec->qk_eps},
+                                     PrefillTree{dec->tree_depth, dec->tree_anc, dec->tree_stride});
     }
     // act = swiglu(x . Wgu^T) of the lean and general sequences (ffn.cpp:105-122)
     int gate_up(const half_t *x, const llmie_matrix &w, int form) const {
@@ -1811,7 +1825,9 @@ static int decoder_prefill(llmie_decoder *dec, const void *hidden_in, void *hidd
     if (int rc = prefill_shape_ok(c, batch, num_tokens, max_q_len)) return rc;
     const int H = dec->H, QKV = dec->QKV, I = dec->I, T = num_tokens;
     const EngineSwitches &sw = engine_switches();
-    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr, dec->moe.on(), dec->q_gammas != nullptr};
+    PrefillCall call{c, T, true, true, mis16(hidden_out) == 0, false, sw, dec->lora.table != nullptr, dec->moe.on(), dec->q_gammas != nullptr,
+                     dec->tree_anc != nullptr};
+    if (call.tree) LLMIE_REQUIRE(max_q_len <= dec->tree_stride, "decoder_prefill: max_q_len %d above the stride %d of the tree that is set", max_q_len, dec->tree_stride);
     for (const llmie_layer_weights &w : dec->layers) {
         call.weights_a16 = call.weights_a16 && (mis16(w.qkv.data) | mis16(w.o.data) | mis16(w.gate_up.data) | mis16(w.down.data)) == 0;
         call.int4_scales_a4 = call.int4_scales_a4 && (reinterpret_cast<uintptr_t>(w.qkv.scale) | reinterpret_cast<uintptr_t>(w.o.scale) |
@@ -2007,6 +2023,7 @@ extern "C" int llmie_decoder_set_window(llmie_decoder *dec, const int32_t *layer
     LLMIE_REQUIRE(any || sinks == 0, "decoder_set_window: %d sink tokens without a window on any layer", sinks);
     if (any && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_window: %s", kWindowRefusal);
     if (any && dec->q_gammas) LLMIE_UNSUPPORTED("decoder_set_window: %s", kQkNormRefusal);
+    if (any && dec->tree_anc) LLMIE_UNSUPPORTED("decoder_set_window: %s", kTreeRefusal);
     if (any) dec->layer_window.assign(layer_window, layer_window + dec->cfg.num_layers), dec->sinks = sinks;
     else dec->layer_window.clear(), dec->sinks = 0;
     return LLMIE_OK;
@@ -2017,6 +2034,7 @@ extern "C" int llmie_decoder_set_head_sinks(llmie_decoder *dec, const float *hea
     LLMIE_REQUIRE(dec, "decoder_set_head_sinks: NULL decoder");
     if (head_sink_dev && !window_engine_ok(dec->cfg)) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kHeadSinkRefusal);
     if (head_sink_dev && dec->q_gammas) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kQkNormRefusal);
+    if (head_sink_dev && dec->tree_anc) LLMIE_UNSUPPORTED("decoder_set_head_sinks: %s", kTreeRefusal);
     LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(head_sink_dev) % sizeof(float) == 0, "decoder_set_head_sinks: the array must be 4-byte aligned");
     dec->head_sinks = head_sink_dev;
     return LLMIE_OK;
@@ -2037,6 +2055,24 @@ extern "C" int llmie_decoder_set_qk_norm(llmie_decoder *dec, const void *q_gamma
     if (!qk_norm_engine_ok(dec->cfg) || bias || !dec->layer_window.empty() || dec->head_sinks)
         LLMIE_UNSUPPORTED("decoder_set_qk_norm: %s", kQkNormRefusal);
     dec->q_gammas = static_cast<const half_t *>(q_gamma_dev), dec->k_gammas = static_cast<const half_t *>(k_gamma_dev), dec->qk_eps = eps;
+    return LLMIE_OK;
+}
+
+// Draft tree: the caller's device arrays, kept on the engine and read by every prefill launch built while they are set
+extern "C" int llmie_decoder_set_tree(llmie_decoder *dec, const int32_t *depth_dev, const uint64_t *anc_dev, int stride) {
+    LLMIE_REQUIRE(dec, "decoder_set_tree: NULL decoder");
+    LLMIE_REQUIRE((depth_dev != nullptr) == (anc_dev != nullptr), "decoder_set_tree: depth and anc go together (one is NULL)");
+    if (!depth_dev) {   // back to a causal chunk
+        LLMIE_REQUIRE(stride == 0, "decoder_set_tree: stride %d without a tree", stride);
+        dec->tree_depth = nullptr, dec->tree_anc = nullptr, dec->tree_stride = 0;
+        return LLMIE_OK;
+    }
+    LLMIE_REQUIRE(stride >= 1 && stride <= LLMIE_SPEC_TREE_MAX_NODES, "decoder_set_tree: stride %d outside [1,%d]", stride, LLMIE_SPEC_TREE_MAX_NODES);
+    LLMIE_REQUIRE(reinterpret_cast<uintptr_t>(depth_dev) % 4 == 0 && reinterpret_cast<uintptr_t>(anc_dev) % 8 == 0,
+                  "decoder_set_tree: depth must be 4-byte and anc 8-byte aligned");
+    const PrefillCall probe{dec->cfg, 1, true, true, true, false, engine_switches(), false, false, false, true};
+    if (plan_prefill(probe).path == PP_REFUSED || !dec->layer_window.empty() || dec->head_sinks) LLMIE_UNSUPPORTED("decoder_set_tree: %s", kTreeRefusal);
+    dec->tree_depth = depth_dev, dec->tree_anc = anc_dev, dec->tree_stride = stride;
     return LLMIE_OK;
 }
 
@@ -2069,6 +2105,10 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         if ((call_flags & LLMIE_PLAN_HEAD_SINK) && !window_engine_ok(*cfg)) LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kHeadSinkRefusal);
         if ((call_flags & LLMIE_PLAN_QK_NORM) && (!qk_norm_engine_ok(*cfg) || (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK))))
             LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kQkNormRefusal);
+        if ((call_flags & LLMIE_PLAN_TREE) && (call_flags & (LLMIE_PLAN_WINDOW | LLMIE_PLAN_HEAD_SINK)))
+            LLMIE_UNSUPPORTED("decoder_prefill_layer_plan: %s", kTreeRefusal);
+        if (call_flags & LLMIE_PLAN_TREE)
+            LLMIE_REQUIRE(max_q_len <= LLMIE_SPEC_TREE_MAX_NODES, "decoder_prefill_layer_plan: max_q_len %d above the %d nodes of a tree", max_q_len, LLMIE_SPEC_TREE_MAX_NODES);
         const PrefillCall call = prefill_call_of_flags(*cfg, tokens, call_flags, switches_of_mask(switch_mask));
         const PrefillPlan plan = plan_prefill(call);
         if (plan.path == PP_REFUSED) return prefill_refuse(plan);
@@ -2098,7 +2138,9 @@ extern "C" const char *llmie_decoder_prefill_layer_plan(const llmie_decoder_conf
         // (... and head sinks the SINK instantiation of that form)
         if (call_flags & LLMIE_PLAN_HEAD_SINK) n += snprintf(text + n, sizeof(text) - n, " attn_head_sink=1");
         // (QK-norm: the QKN instantiation of the RoPE + append launch; the QKV forms above are already the ones without the epilogue)
-        if (call_flags & LLMIE_PLAN_QK_NORM) snprintf(text + n, sizeof(text) - n, " qk_norm=1");
+        if (call_flags & LLMIE_PLAN_QK_NORM) n += snprintf(text + n, sizeof(text) - n, " qk_norm=1");
+        // (a draft tree: the TREE instantiations of the RoPE + append launch and of the 64-row flash form)
+        if (lp.attn.tree) snprintf(text + n, sizeof(text) - n, " tree");
         return LLMIE_OK;
     }();
     if (status) *status = rc;

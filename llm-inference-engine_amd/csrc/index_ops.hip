@@ -299,3 +299,75 @@ extern "C" int llmie_kv_pages_copy(void *dense, void *pool, const int32_t *block
     return llmie::launch_status("kv_pages_copy");
 }
 
+// llmie_kv_tree_commit: behind a tree verify, accepted node out_path[b, m] sits at cache slot base_len[b] + out_path[b, m] and
+// belongs at base_len[b] + m.  One workgroup per (layer x kv head, sequence, K or V): every source row is staged in LDS, a barrier,
+// then every destination row is stored -- a destination may be a later source.  Byte copy; rows with out_path[m] == m stay.
+namespace llmie {
+constexpr int kCommitMaxRowBytes = 512, kCommitMaxNodes = 64;
+__global__ __launch_bounds__(256) void kv_tree_commit_kernel(unsigned char *k_cache, unsigned char *v_cache, const int32_t *__restrict__ table,
+                                                             const int32_t *__restrict__ base_len, const int32_t *__restrict__ out_path,
+                                                             const int32_t *__restrict__ out_count, int n, int batch, int kvh, int max_seq,
+                                                             int row_bytes, int max_pages, int num_pages) {
+    __shared__ uint4_t stage[kCommitMaxNodes * kCommitMaxRowBytes / 16];
+    __shared__ long long src_off[kCommitMaxNodes], dst_off[kCommitMaxNodes];   // byte offsets into the cache, -1: the row does not move
+    const int lg = blockIdx.x, b = blockIdx.y;   // lg = layer * kvh + g
+    const int layer = lg / kvh, g = lg - layer * kvh;
+    unsigned char *cache = blockIdx.z ? v_cache : k_cache;
+    const int count = min(max(out_count[b], 0), n), base = base_len[b];
+    const int tid = threadIdx.x;
+    // the byte offset of slot t of this (layer, kv head, sequence), or -1 for a slot outside the cache
+    auto slot_off = [&](int t) -> long long {
+        if (t < 0) return -1;
+        if (table) {
+            if (t / 128 >= max_pages) return -1;
+            const int page = table[static_cast<size_t>(b) * max_pages + t / 128];
+            if (page < 0 || page >= num_pages) return -1;
+            return static_cast<long long>((((static_cast<size_t>(layer) * num_pages + page) * kvh + g) * 128 + t % 128) * row_bytes);
+        }
+        if (t >= max_seq) return -1;
+        return static_cast<long long>((((static_cast<size_t>(layer) * batch + b) * kvh + g) * max_seq + t) * row_bytes);
+    };
+    if (tid < n) {
+        long long so = -1, dn = -1;
+        if (tid < count && base >= 0) {
+            const int node = out_path[static_cast<size_t>(b) * n + tid];
+            if (node >= 0 && node < n && node != tid) so = slot_off(base + node), dn = slot_off(base + tid);
+        }
+        if (so < 0 || dn < 0) so = dn = -1;
+        src_off[tid] = so, dst_off[tid] = dn;
+    }
+    __syncthreads();
+    const int cpr = row_bytes / 16;   // 16-byte chunks per row
+    for (int i = tid; i < count * cpr; i += 256) {
+        const int m = i / cpr, c = i - m * cpr;
+        if (src_off[m] >= 0) stage[i] = *reinterpret_cast<const uint4_t *>(cache + src_off[m] + 16 * c);
+    }
+    __syncthreads();
+    for (int i = tid; i < count * cpr; i += 256) {
+        const int m = i / cpr, c = i - m * cpr;
+        if (dst_off[m] >= 0) *reinterpret_cast<uint4_t *>(cache + dst_off[m] + 16 * c) = stage[i];
+    }
+}
+}  // namespace llmie
+
+extern "C" int llmie_kv_tree_commit(void *k_cache, void *v_cache, const int32_t *block_table, const int32_t *base_len, const int32_t *out_path,
+                                    const int32_t *out_count, int batch, int n, int layers, int kv_head_num, int max_seq_len, int head_size,
+                                    int max_pages, int num_pages, int elem_bytes, llmie_stream stream) {
+    LLMIE_REQUIRE(k_cache && v_cache && base_len && out_path && out_count, "kv_tree_commit: NULL pointer");
+    LLMIE_REQUIRE(layers > 0 && batch > 0 && kv_head_num > 0 && head_size > 0, "kv_tree_commit: bad shape");
+    LLMIE_REQUIRE(n >= 1, "kv_tree_commit: n %d < 1", n);
+    LLMIE_REQUIRE(elem_bytes == 1 || elem_bytes == 2, "kv_tree_commit: elem_bytes %d is neither 1 nor 2", elem_bytes);
+    if (block_table) LLMIE_REQUIRE(max_pages > 0 && num_pages > 0, "kv_tree_commit: a block table with max_pages %d / num_pages %d", max_pages, num_pages);
+    else LLMIE_REQUIRE(max_seq_len > 0, "kv_tree_commit: max_seq_len %d must be positive", max_seq_len);
+    if (n > llmie::kCommitMaxNodes) LLMIE_UNSUPPORTED("kv_tree_commit: n %d above LLMIE_SPEC_TREE_MAX_NODES (%d)", n, llmie::kCommitMaxNodes);
+    const int row_bytes = head_size * elem_bytes;
+    if (row_bytes % 16 != 0 || row_bytes > llmie::kCommitMaxRowBytes)
+        LLMIE_UNSUPPORTED("kv_tree_commit: rows of %d bytes (a multiple of 16 up to %d)", row_bytes, llmie::kCommitMaxRowBytes);
+    LLMIE_REQUIRE((reinterpret_cast<uintptr_t>(k_cache) | reinterpret_cast<uintptr_t>(v_cache)) % 16 == 0, "kv_tree_commit: the caches must be 16-byte aligned");
+    LLMIE_REQUIRE(static_cast<long long>(layers) * kv_head_num <= 0x7fffffffll && batch <= 65535, "kv_tree_commit: grid too large");
+    dim3 grid(layers * kv_head_num, batch, 2);
+    llmie::kv_tree_commit_kernel<<<grid, 256, 0, llmie::as_stream(stream)>>>(static_cast<unsigned char *>(k_cache), static_cast<unsigned char *>(v_cache),
+                                                                          block_table, base_len, out_path, out_count, n, batch, kv_head_num,
+                                                                          max_seq_len, row_bytes, max_pages, num_pages);
+    return llmie::launch_status("kv_tree_commit");
+}

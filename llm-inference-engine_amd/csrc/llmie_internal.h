@@ -330,6 +330,14 @@ struct PrefillAttnPlan {
     bool rope_append;               // prefill_rope_append_kernel runs first (else the QKV projection's epilogue did RoPE + the append)
     int window, sinks;              // window > 0: the windowed instantiation (sliding window + sink tokens), 0: full causal attention
     bool head_sink;                 // the SINK instantiation of the same form: a learned sink logit per query head joins every row's softmax
+    bool tree;                      // the TREE instantiations of both launches: the chunk of every sequence is a draft tree (q64w4t1 only)
+};
+// The draft tree of a prefill attention call (include/llmie.h, llmie_decoder_set_tree): device arrays [batch, stride] as
+// llmie_spec_tree_prepare leaves them, or all null / 0
+struct PrefillTree {
+    const int32_t *depth;
+    const uint64_t *anc;
+    int stride;
 };
 // QK-norm of a prefill attention call (include/llmie.h, llmie_qk_norm): this layer's gammas, device fp16 [128] each, or both null; the
 // RoPE + append launch normalises q and k in front of the rotation (so the plan must have rope_append, and the layer no QKV bias)
@@ -337,12 +345,14 @@ struct PrefillQkNorm {
     const half_t *q_gamma, *k_gamma;
     float eps;
 };
-PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window = 0, int sinks = 0);
+PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window = 0, int sinks = 0,
+                                  bool tree = false);
 int prefill_attention_f16(const PrefillAttnPlan &plan, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
                           int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st,
                           const float *head_sink = nullptr /* plan.head_sink: this layer's device fp32 [head_num] */,
-                          const PrefillQkNorm &qkn = PrefillQkNorm{nullptr, nullptr, 0.f});
+                          const PrefillQkNorm &qkn = PrefillQkNorm{nullptr, nullptr, 0.f},
+                          const PrefillTree &tree = PrefillTree{nullptr, nullptr, 0});
 // short prefills: slab consumer of the QKV projection with RoPE + KV-cache append folded in (q -> qkv, k / v -> the caches only)
 bool splitk_finalize_qkv_rope_eligible(const SplitKSlabs &sk, int head_size, const void *qkv, const void *bias);
 int splitk_finalize_qkv_rope(const SplitKSlabs &sk, const SlabScale &sc, half_t *qkv, const half_t *qkv_bias, const KvView &kv,

@@ -45,7 +45,10 @@ __device__ __forceinline__ void locate_token(const int32_t *__restrict__ cum, in
 // the code the kernel had before.  The HS / 16 work items of a head are adjacent lanes (heads * GROUPS and 256 are multiples of
 // GROUPS, so a head's lanes are all in the loop or all out of it): each sums its two groups of 8, the lanes are reduced by
 // exchanges and the two halves -- the highest bit of the group index -- are added last (qk_norm.cuh's order).
-template <int HS, bool KV8, bool QKN = false, typename... QknArgs>
+// TREE (compile time): the chunk of every sequence is a draft tree (include/llmie.h, llmie_decoder_set_tree).  Its two launch arguments
+// (const int32_t *depth, int stride) follow QKN's in the pack: position i of sequence b is node i, rotated by table row
+// history + clamp(depth[b, i], 0, i) -- a corrupt depth stays inside the rows a chain would use -- and stored at slot history + i.
+template <int HS, bool KV8, bool QKN = false, bool TREE = false, typename... QknArgs>
 __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__restrict__ qkv, const half_t *__restrict__ bias,
                                                                   void *__restrict__ k_cache, void *__restrict__ v_cache,
                                                                   const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
@@ -53,8 +56,8 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__rest
                                                                   int kv_head_num, int max_seq_len, int rotary_dim, size_t layer_off,
                                                                   float k_inv_scale, float v_inv_scale,
                                                                   const int32_t *__restrict__ table /* paged cache or null */,
-                                                                  int max_pages, const QknArgs... qkn /* QKN: q_gamma, k_gamma, eps */) {
-    static_assert(sizeof...(QknArgs) == (QKN ? 3 : 0), "q_gamma, k_gamma, eps");
+                                                                  int max_pages, const QknArgs... qkn /* QKN: q_gamma, k_gamma, eps; TREE: depth, stride */) {
+    static_assert(sizeof...(QknArgs) == (QKN ? 3 : 0) + (TREE ? 2 : 0), "q_gamma, k_gamma, eps, depth, stride");
     const int t = blockIdx.x;
     int b, pos;
     locate_token(cum, batch, t, b, pos);
@@ -63,7 +66,13 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(half_t *__rest
     constexpr int HALF = HS / 2;
     const int heads = head_num + 2 * kv_head_num;
     half_t *row = qkv + static_cast<size_t>(t) * heads * HS;
-    const float2 *cs = rope + static_cast<size_t>(tpos) * HALF;
+    int rpos = tpos;   // the table row q and k are rotated by
+    if constexpr (TREE) {
+        const int32_t *depth = pack_arg<QKN ? 3 : 0>(qkn...);
+        const int stride = pack_arg<QKN ? 4 : 1>(qkn...);
+        if (pos < stride) rpos = hist[b] + min(max(depth[static_cast<size_t>(b) * stride + pos], 0), pos);
+    }
+    const float2 *cs = rope + static_cast<size_t>(rpos) * HALF;
     // one work item = 8 consecutive dims d .. d+7 of the first half of a head and their rotate-half partners d+HS/2 ..:
     // two 16-byte loads, two 16-byte stores (the first version moved 2 bytes per access: 58 us per layer at 2048 tokens)
     constexpr int GROUPS = HALF / 8;
@@ -284,16 +293,22 @@ int prefill_token_table(const int32_t *cum_seqlens, const int32_t *history_len, 
 // row of the same tile (0 x NaN would poison P.V), so neither a dead row nor the table entry of a dead page is ever read.
 // SINK (compile time): a learned sink logit per query head (include/llmie.h) -- one more pack argument at the end, the device array
 // head_sink[head_num] (fp32).  The key-tile loop does not know it: it enters once per row, at the final normalisation.
-template <int HS, bool KV8, int NW, int RT = 1, bool WIN = false, bool SINK = false, typename... WinArgs>
+// TREE (compile time, NW = 4 and RT = 1 only): the chunk is a draft tree of at most 64 nodes (include/llmie.h, llmie_decoder_set_tree) --
+// two more pack arguments at the end (const uint64_t *anc, int stride).  Query i sees the whole history and key history + j iff bit j
+// of a = (anc[b, i] & ((2 << i) - 1)) | (1 << i) is set: bits above i are ignored (so the "tile wholly in the future" skip holds) and
+// the self bit is forced (so no row is fully masked).  Each lane keeps its row's mask as one 64-bit value; every tile that reaches the
+// history's end takes the masked branch (wave-uniform).
+template <int HS, bool KV8, int NW, int RT = 1, bool WIN = false, bool SINK = false, bool TREE = false, typename... WinArgs>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void prefill_flash_kernel(const half_t *__restrict__ qkv, const void *__restrict__ k_cache,
                                                             const void *__restrict__ v_cache, half_t *__restrict__ out,
                                                             const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
                                                             int head_num, int kv_head_num, int max_seq_len, size_t layer_off,
                                                             float k_scale, float v_scale,
                                                             const int32_t *__restrict__ table /* paged cache or null */, int max_pages,
-                                                            const WinArgs... win /* WIN: window, sinks; SINK: head_sink */) {
+                                                            const WinArgs... win /* WIN: window, sinks; SINK: head_sink; TREE: anc, stride */) {
     static_assert(HS == 128, "tuned for head_size 128");
-    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0), "window, sinks, head_sink");
+    static_assert(sizeof...(WinArgs) == (WIN ? 2 : 0) + (SINK ? 1 : 0) + (TREE ? 2 : 0), "window, sinks, head_sink, anc, stride");
+    static_assert(!TREE || (NW == 4 && RT == 1 && !WIN && !SINK), "the tree form: 64 query rows = one 64-bit mask per row, full attention");
     // V rows are 288 bytes (256 + 32): the PV operand is fetched with ds_read_b64_tr_b16 (gfx950 transposed LDS read: a 16-lane
     // group reads a block of 4 keys x 16 head dims and every lane receives one column of it = 4 consecutive keys of its head
     // dim), whose 16 lanes address 4 rows x 4 eight-byte pieces -- rows 32 bytes apart modulo 256 keep a 32-lane half
@@ -347,6 +362,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         for (int s = 0; s < 4; ++s) qf[u][s] = *reinterpret_cast<const half8_t *>(qptr + 32 * s + 8 * q);
         qpos[u] = history + qrow_c;  // keys t <= qpos are visible
     }
+    unsigned long long tree_mask = 0;   // TREE: bit j = this lane's query row sees chunk position j
+    if constexpr (TREE) {
+        const int i = min(qrow[0], len - 1) & 63, stride = pack_arg<1>(win...);
+        const unsigned long long self = 1ull << i;
+        tree_mask = self | (i < stride ? pack_arg<0>(win...)[static_cast<size_t>(b) * stride + i] & ((self << 1) - 1ull) : (self << 1) - 1ull);
+    }
+    (void)tree_mask;
 
     const half_t *kc = static_cast<const half_t *>(k_cache), *vc = static_cast<const half_t *>(v_cache);
     const uint8_t *kc8 = static_cast<const uint8_t *>(k_cache), *vc8 = static_cast<const uint8_t *>(v_cache);
@@ -497,8 +519,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         // (wave-uniform test), and 2^(-inf) = 0 needs no select.
         const float scale2 = scale * 1.44269504088896341f;
         // (WIN: or that begin at or in front of the window start of the wave's last row)
-        const bool need_mask = t0 + BT - 1 > history + q0 + wave * WROWS || t0 + BT > ctx ||
-                               (WIN && t0 <= history + q0 + wave * WROWS + WROWS - 1 - win_w);
+        const bool need_mask = TREE ? t0 + BT > history
+                                    : (t0 + BT - 1 > history + q0 + wave * WROWS || t0 + BT > ctx ||
+                                       (WIN && t0 <= history + q0 + wave * WROWS + WROWS - 1 - win_w));
         half8_t pf[RT][2];  // P^T fragments of row tile u = MFMA B operand of the two 32-key steps
         typedef float float2v_t __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -510,7 +533,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int t = t0 + tt * 16 + 4 * q + e;
-                        const float v = (t <= qpos[u] && t < ctx && (!WIN || t > qpos[u] - win_w || t < win_s)) ? sacc[u][tt][e] : -INFINITY;
+                        bool vis;
+                        if constexpr (TREE) {
+                            const int j = t - history;   // (j < len <= 64 where the shift counts)
+                            vis = j < 0 || (j < len && j < 64 && ((tree_mask >> (j & 63)) & 1ull));
+                        } else {
+                            vis = t <= qpos[u] && t < ctx && (!WIN || t > qpos[u] - win_w || t < win_s);
+                        }
+                        const float v = vis ? sacc[u][tt][e] : -INFINITY;
                         sacc[u][tt][e] = v;
                         mloc = fmaxf(mloc, v);
                     }
@@ -622,7 +652,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 }
 
 // Which flash instantiation a prefill attention launch runs, its grid, and whether the RoPE + append launch goes in front.  Pure host code.
-PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window, int sinks) {
+PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool kv_e4m3, bool rope_done, int window, int sinks, bool tree) {
+    // a draft tree: the one form that has the TREE instantiation -- 64 query rows per workgroup, one 64-bit mask per row -- behind the
+    // RoPE + append launch, which rotates by depth
+    if (tree) return PrefillAttnPlan{64, 4, 1, kv_e4m3, {(max_q_len + 63) / 64, head_num, batch}, true, 0, 0, false, true};
     // 128 query rows per workgroup either way: 8 waves x 16 rows (one workgroup per CU at a time, dynamic rounds, longest first), or
     // 4 waves x 2 x 16 rows (every fragment read from LDS feeds two MFMAs; two workgroups per CU, out of phase with each other).
     // Measured (bench, same box, us per layer): 8 x 512 tokens 54.5 -> 47.5 and 16 x 256 tokens 38 with the 4-wave form; 1 x 2048
@@ -637,13 +670,14 @@ PrefillAttnPlan plan_prefill_attn(int batch, int max_q_len, int head_num, bool k
     const int bq = bq64 ? 64 : 128;
     // (a window changes the key tiles a workgroup walks, not the grid: the forms are chosen as for full attention)
     return PrefillAttnPlan{bq, bq64 || rt2 ? 4 : 8, !bq64 && rt2 ? 2 : 1, kv_e4m3, {(max_q_len + bq - 1) / bq, head_num, batch}, !rope_done,
-                           window > 0 ? window : 0, window > 0 ? sinks : 0, false};
+                           window > 0 ? window : 0, window > 0 ? sinks : 0, false, false};
 }
 
 // g.grid[1] / g.grid[2] are head_num / batch
 int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qkv, const half_t *qkv_bias, half_t *out,
                           const int32_t *cum_seqlens, const int32_t *history_len, const float2 *rope, int layer, int num_tokens,
-                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, const float *head_sink, const PrefillQkNorm &qkn) {
+                          int kv_head_num, int max_seq_len, int rotary_dim, hipStream_t st, const float *head_sink, const PrefillQkNorm &qkn,
+                          const PrefillTree &tree) {
     const int head_num = g.grid[1], batch = g.grid[2];
     const size_t layer_off = kv.block_table ? static_cast<size_t>(layer) * kv.num_pages * kv_head_num * 128 * 128
                                             : static_cast<size_t>(layer) * batch * kv_head_num * max_seq_len * 128;
@@ -652,9 +686,34 @@ int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qk
         set_error("prefill attention: QK-norm needs the RoPE + append launch and no QKV bias");
         return LLMIE_ERR_UNSUPPORTED;
     }
+    if (g.tree) {   // the TREE instantiations of both launches (the planner and the engine keep a window and head sinks away)
+        if (!tree.depth || !tree.anc || tree.stride < 1 || tree.stride > 64 || !g.rope_append || g.window > 0 || g.head_sink || g.waves != 4 ||
+            g.row_tiles != 1 || g.q_rows != 64) {
+            set_error("prefill attention: a tree plan needs the arrays, the RoPE + append launch and the 64-row form without window or head sinks");
+            return LLMIE_ERR_INVALID_ARG;
+        }
+        if (qkn.q_gamma) {
+            auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true, true, true, const half_t *, const half_t *, float, const int32_t *, int>
+                                    : prefill_rope_append_kernel<128, false, true, true, const half_t *, const half_t *, float, const int32_t *, int>;
+            append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
+                                               rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages, qkn.q_gamma, qkn.k_gamma,
+                                               qkn.eps, tree.depth, tree.stride);
+        } else {
+            auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true, false, true, const int32_t *, int>
+                                    : prefill_rope_append_kernel<128, false, false, true, const int32_t *, int>;
+            append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
+                                               rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages, tree.depth, tree.stride);
+        }
+        auto tflash = g.kv_e4m3 ? prefill_flash_kernel<128, true, 4, 1, false, false, true, const unsigned long long *, int>
+                                : prefill_flash_kernel<128, false, 4, 1, false, false, true, const unsigned long long *, int>;
+        tflash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), 256, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num, max_seq_len,
+                                                                     layer_off, ks, vs, kv.block_table, kv.max_pages,
+                                                                     reinterpret_cast<const unsigned long long *>(tree.anc), tree.stride);
+        return launch_status("prefill_attention(tree)");
+    }
     if (g.rope_append && qkn.q_gamma) {   // the QKN instantiations: the norm runs in this launch, in front of the rotation
-        auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true, true, const half_t *, const half_t *, float>
-                                : prefill_rope_append_kernel<128, false, true, const half_t *, const half_t *, float>;
+        auto append = g.kv_e4m3 ? prefill_rope_append_kernel<128, true, true, false, const half_t *, const half_t *, float>
+                                : prefill_rope_append_kernel<128, false, true, false, const half_t *, const half_t *, float>;
         append<<<num_tokens, 256, 0, st>>>(qkv, qkv_bias, kv.k, kv.v, cum_seqlens, history_len, rope, batch, head_num, kv_head_num, max_seq_len,
                                            rotary_dim, layer_off, 1.0f / ks, 1.0f / vs, kv.block_table, kv.max_pages, qkn.q_gamma, qkn.k_gamma,
                                            qkn.eps);
@@ -683,11 +742,11 @@ int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qk
             constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
             const dim3 grid(g.grid[0], g.grid[1], g.grid[2]);
             if (g.window > 0)
-                prefill_flash_kernel<128, K8, NW, RT, true, true, int, int, const float *><<<grid, NW * 64, 0, st>>>(
+                prefill_flash_kernel<128, K8, NW, RT, true, true, false, int, int, const float *><<<grid, NW * 64, 0, st>>>(
                     qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
                     kv.max_pages, g.window, g.sinks, head_sink);
             else
-                prefill_flash_kernel<128, K8, NW, RT, false, true, const float *><<<grid, NW * 64, 0, st>>>(
+                prefill_flash_kernel<128, K8, NW, RT, false, true, false, const float *><<<grid, NW * 64, 0, st>>>(
                     qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num, kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,
                     kv.max_pages, head_sink);
         };
@@ -706,14 +765,14 @@ int prefill_attention_f16(const PrefillAttnPlan &g, const KvView &kv, half_t *qk
         return launch_status("prefill_attention(head sink)");
     }
     if (g.window > 0) {   // the windowed instantiations of the same forms
-        decltype(&prefill_flash_kernel<128, false, 4, 1, true, false, int, int>) wflash = nullptr;
+        decltype(&prefill_flash_kernel<128, false, 4, 1, true, false, false, int, int>) wflash = nullptr;
         switch ((g.kv_e4m3 ? 100 : 0) + g.waves * 10 + g.row_tiles) {
-            case 41: wflash = prefill_flash_kernel<128, false, 4, 1, true, false, int, int>; break;
-            case 42: wflash = prefill_flash_kernel<128, false, 4, 2, true, false, int, int>; break;
-            case 81: wflash = prefill_flash_kernel<128, false, 8, 1, true, false, int, int>; break;
-            case 141: wflash = prefill_flash_kernel<128, true, 4, 1, true, false, int, int>; break;
-            case 142: wflash = prefill_flash_kernel<128, true, 4, 2, true, false, int, int>; break;
-            case 181: wflash = prefill_flash_kernel<128, true, 8, 1, true, false, int, int>; break;
+            case 41: wflash = prefill_flash_kernel<128, false, 4, 1, true, false, false, int, int>; break;
+            case 42: wflash = prefill_flash_kernel<128, false, 4, 2, true, false, false, int, int>; break;
+            case 81: wflash = prefill_flash_kernel<128, false, 8, 1, true, false, false, int, int>; break;
+            case 141: wflash = prefill_flash_kernel<128, true, 4, 1, true, false, false, int, int>; break;
+            case 142: wflash = prefill_flash_kernel<128, true, 4, 2, true, false, false, int, int>; break;
+            case 181: wflash = prefill_flash_kernel<128, true, 8, 1, true, false, false, int, int>; break;
         }
         wflash<<<dim3(g.grid[0], g.grid[1], g.grid[2]), g.waves * 64, 0, st>>>(qkv, kv.k, kv.v, out, cum_seqlens, history_len, head_num,
                                                                             kv_head_num, max_seq_len, layer_off, ks, vs, kv.block_table,

@@ -14,6 +14,12 @@ fp16 logits (no model: the entries alone, between device events), the drafts dra
 are the target's plus noise -- so that acceptances and rejections (the residual pass) both occur; the two arms alternate inside
 every round.
 
+    python tools/specbench.py --tree 8 16 32 64 [--batch 1 8] [--k 7] [--rounds 7] [--reps 20]
+
+the tree arm: beside the plain step and the linear verify steps of --k, one TREE step per n -- spec_tree_prepare + input_embedding
++ prefill_paged of n nodes per sequence with the tree set (a binary tree in heap order) + rmsnorm + linear over the batch * n rows
++ spec_verify_tree + kv_tree_commit; the tree drafter's launch is timed on its own (ngram_tree_ms).
+
 Same build, same process, same weights; the arms alternate inside every round (plain, k = 2, 4, 7, plain, ...) and the median
 round of each arm is reported with its min and max.  A verify step emits 1 .. k + 1 tokens for its time, a plain step one: the
 break-even is verify_ms / plain_ms emitted tokens per verify step, i.e. that minus one accepted drafts.  Prints one JSON line
@@ -43,10 +49,10 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps   # ms
 
 
-def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
+def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps, trees=()):
     H, V, L, KVH, HS = cfg["head_num"] * cfg["head_size"], cfg["vocab_size"], cfg["num_layers"], cfg["kv_head_num"], cfg["head_size"]
     kmax = max(ks)
-    max_pages = (ctx + kmax + 1 + V_PAGE - 1) // V_PAGE
+    max_pages = (ctx + max([kmax + 1] + list(trees)) + V_PAGE - 1) // V_PAGE
     num_pages = B * max_pages
     i32 = lambda v: torch.tensor(v, dtype=torch.int32, device="cuda")
     ecfg = dict(cfg, max_seq_len=max_pages * V_PAGE, max_batch=B, rotary_dim=HS, rotary_base=10000.0, rms_eps=EPS, dtype=llmie.F16,
@@ -90,6 +96,31 @@ def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
             llmie.spec_verify(logits, drafts, params, seq, fin, -1, draft_len=None, step=7, workspace=ws, out=outs)
 
         arms[k] = verify
+    # tree steps: a binary tree in heap order per sequence (depth log2 n; every node live), the walk decided by random logits
+    tree_arms = {}
+    for n in trees:
+        T = B * n
+        t_ids = torch.randint(0, V, (B, n), generator=g, device="cuda").to(torch.int32)
+        t_parent = i32([[-1] + [(i - 1) // 2 for i in range(1, n)]] * B)
+        st = llmie.spec_tree_state(B, n)
+        xt, t_logits = torch.empty((T, H), dtype=torch.float16, device="cuda"), torch.empty((T, V), dtype=torch.float16, device="cuda")
+        yt = torch.empty_like(xt)
+        t_in_len = i32([n] * B)
+        t_ws = torch.empty(llmie.spec_verify_tree_workspace_bytes(B, n, V), dtype=torch.uint8, device="cuda")
+
+        def tree_step(n=n, t_ids=t_ids, t_parent=t_parent, st=st, xt=xt, yt=yt, t_logits=t_logits, t_in_len=t_in_len, t_ws=t_ws):
+            llmie.spec_tree_prepare(t_parent, None, out=(st.depth, st.anc))
+            dec.set_tree(st.depth, st.anc)
+            llmie.input_embedding(t_ids.view(-1), weights["embed"], xt)
+            dec.prefill_paged(xt, yt, kp, vp, table, t_in_len, cached, n)
+            dec.set_tree(None, None)
+            llmie.rmsnorm(yt, None, weights["final_norm"], EPS)
+            llmie.linear(yt, weights["lm_head"], t_logits)
+            llmie.spec_verify_tree(t_logits, t_ids, t_parent, st.depth, st.anc, params, seq, fin, -1, step=7, workspace=t_ws,
+                                   out=(st.tokens, st.count, st.path))
+            llmie.kv_tree_commit(kp, vp, cached, st.path, st.count, block_table=table)
+
+        tree_arms[n] = tree_step
     # the drafter alone, on rows of ctx tokens from an alphabet of 4 (matches of every n all over the row: the costly case)
     toks = torch.randint(0, 4, (B, ctx + 64), generator=g, device="cuda").to(torch.int32)
     tlen = i32([ctx] * B)
@@ -98,18 +129,32 @@ def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
     def draft():
         llmie.ngram_draft(toks, tlen, kmax, max_n=3, min_n=1, out=dout)
 
+    nmax = max(trees) if trees else 0
+    tout = (torch.empty((B, max(nmax, 1)), dtype=torch.int32, device="cuda"), torch.empty((B, max(nmax, 1)), dtype=torch.int32, device="cuda"), i32([0] * B))
+
+    def draft_tree():
+        llmie.ngram_draft_tree(toks, tlen, nmax, min(kmax, 15), branches=8, max_n=3, min_n=1, out=tout)
+
     for _ in range(3):   # every shape of the timed window, warm
         plain()
         draft()
         for k in ks:
             arms[k]()
+        for n in trees:
+            tree_arms[n]()
+        if trees:
+            draft_tree()
     torch.cuda.synchronize()
-    tp, tv, td = [], {k: [] for k in ks}, []
+    tp, tv, td, tt, tdt = [], {k: [] for k in ks}, [], {n: [] for n in trees}, []
     for _ in range(rounds):
         tp.append(timed(plain, reps))
         for k in ks:
             tv[k].append(timed(arms[k], reps))
+        for n in trees:
+            tt[n].append(timed(tree_arms[n], reps))
         td.append(timed(draft, reps))
+        if trees:
+            tdt.append(timed(draft_tree, reps))
     mp = statistics.median(tp)
     res = dict(batch=B, ctx=ctx, plain_ms=mp, plain_ms_min_max=[min(tp), max(tp)], ngram_ms=statistics.median(td), verify=[])
     for k in ks:
@@ -119,6 +164,18 @@ def run_batch(llmie, cfg, weights, B, ks, ctx, rounds, reps):
         res["verify"].append(dict(k=k, rows=B * (k + 1), verify_ms=mv, verify_ms_min_max=[min(tv[k]), max(tv[k])], verify_over_plain=mv / mp,
                                   verify_over_plain_min_max=[min(ratios), max(ratios)], break_even_tokens_per_step=mv / mp,
                                   break_even_accepted_drafts=mv / mp - 1, speedup_if_all_accepted=(k + 1) * mp / mv))
+    if trees:
+        res["ngram_tree_ms"] = statistics.median(tdt)
+        res["tree"] = []
+        kref = max(ks)
+        for n in trees:
+            mt = statistics.median(tt[n])
+            ratios = [a / b for a, b in zip(tt[n], tp)]
+            lin = [a / b for a, b in zip(tt[n], tv[kref])]
+            res["tree"].append(dict(n=n, rows=B * n, tree_ms=mt, tree_ms_min_max=[min(tt[n]), max(tt[n])], tree_over_plain=mt / mp,
+                                    tree_over_plain_min_max=[min(ratios), max(ratios)], break_even_tokens_per_step=mt / mp,
+                                    break_even_accepted_nodes=mt / mp - 1, linear_k=kref, tree_over_linear=statistics.median(lin),
+                                    tree_over_linear_min_max=[min(lin), max(lin)]))
     dec.close()
     del kp, vp
     torch.cuda.empty_cache()
@@ -178,6 +235,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--layers", type=int, default=0, help="fewer layers than the model's 32 (a rehearsal; not a measurement)")
     ap.add_argument("--sampled", action="store_true", help="the sampled-draft arm: spec_verify_sampled beside spec_verify, the entries alone")
+    ap.add_argument("--tree", type=int, nargs="*", default=[], help="the tree arm: node counts n (1 .. 64) of one tree step each")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -198,7 +256,7 @@ def main():
         cfg["num_layers"] = a.layers
     weights = bench.build_weights(torch, cfg, 0)
     res = dict(bench="spec_decode", device=torch.cuda.get_device_name(0), rounds=a.rounds, reps=a.reps, layers=cfg["num_layers"],
-               results=[run_batch(llmie, cfg, weights, B, a.k, a.ctx, a.rounds, a.reps) for B in a.batch])
+               results=[run_batch(llmie, cfg, weights, B, a.k, a.ctx, a.rounds, a.reps, a.tree) for B in a.batch])
     line = json.dumps(res)
     print(line)
     if a.out:
