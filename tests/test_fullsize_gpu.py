@@ -57,6 +57,9 @@ def test_graph_replay_equals_eager(llmie, full):
     vc.copy_(v0)
     out = torch.empty_like(x)
     s = torch.cuda.Stream()
+    # the eager step above is still in flight on the current stream and shares the decoder's workspace and the caches with the
+    # warm-up: the capture stream starts behind it (nothing on the host has waited for the device up to here)
+    s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         dec.forward(x, out, kc, vc, -1, step_dev=step_dev)  # warm-up on the capture stream
     s.synchronize()
