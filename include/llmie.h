@@ -370,6 +370,55 @@ typedef struct {
 int llmie_rope_table_fill(float *cos_sin_out, int max_pos, int head_size, int rotary_dim, float rotary_base,
                           const llmie_rope_scaling *scaling);
 
+/* ABI 3 (an addition; no reference counterpart).  Multi-head Latent Attention, one decode step in the absorbed form (DeepSeek-V2 /
+ * V2-Lite / V3 / R1, Kimi-K2).  fp16 activations, weights and cache; fp32 accumulation and softmax state.  The geometry is fixed --
+ * the constants below -- and head_num is a multiple of 16 in [16, 128]; anything else is LLMIE_ERR_UNSUPPORTED.
+ *   cache      ONE cache, no K / V pair and no KV-head axis: dense [layers, batch, max_seq_len, 576], or paged [layers, num_pages,
+ *              128, 576] through block_table[b * max_pages + p] (max_pages * 128 >= max_seq_len).  A row is c[512] || k_pe[64].
+ *   ctx_len_dev[b]  device int32: the context length of sequence b WITH this step's token, read by the kernels (a captured step
+ *              replays).  A value outside [1, max_seq_len] leaves everything of that sequence untouched: cache row, q_lat, o_lat.
+ *   rope_table [max_pos >= max_seq_len][32] (cos, sin) as llmie_rope_table_fill(head_size = 64, rotary_dim = 64, ...) makes it (YaRN
+ *              included); rotate-half pairs (j, j + 32): y_j = x_j cos - x_{j+32} sin, y_{j+32} = x_{j+32} cos + x_j sin, in fp32.
+ *   kv_b       [head_num, 256, 512]: HF kv_b_proj.weight as stored; per head rows 0..127 are W_UK, rows 128..255 are W_UV.  Both
+ *              are used as stored (W_UK as a [K, N] operand, W_UV as [N, K]); no transposed copy is made.
+ * llmie_mla_kv_append: kv_a [batch, 576] (raw kv_a_proj_with_mqa output), gamma [512].  Writes cache row ctx_len[b] - 1 =
+ *   fp16(c * (1 / sqrt(mean(c^2) + eps)) * gamma) || rope(k_pe, pos = ctx_len[b] - 1).  One launch, one wave per sequence.  Summation
+ *   order of sum(c^2), fp32: lane i of 64 takes c[8i .. 8i+7], ss = fma(c_j, c_j, ss) for j = 0..7 from ss = 0; then the xor butterfly
+ *   ss += ss[lane ^ d] over d = 32, 16, 8, 4, 2, 1.  mean = ss * (1/512).
+ * llmie_mla_q_absorb: q [batch, head_num, 192] (128 nope || 64 rope) -> q_lat [batch, head_num, 576] =
+ *   fp16(W_UK[h]^T q_nope) || rope(q_pe, pos = ctx_len[b] - 1).
+ * llmie_mla_decode: o_lat [batch, head_num, 512] = sum_t softmax_t(softmax_scale * q_lat . row_t[0:576]) row_t[0:512] over
+ *   t < ctx_len[b].  The softmax is PLAIN: the row maximum is subtracted and the denominator is the sum itself -- no + 1e-6 as in the
+ *   llmie_decoder_mha* entries.  softmax_scale > 0 is the caller's (DeepSeek folds YaRN's mscale^2 into it).  max_ctx: a host bound of
+ *   the context lengths that sizes the grid -- a sequence above it is left untouched --, or 0: the grid is sized from max_seq_len.
+ *   The tokens are cut into splits of a fixed length that depends on nothing but ctx_len[b]: row b of a batch has the bits of the
+ *   batch-1 call at the same context, whatever max_ctx was.  No atomics; results repeat bit for bit.  workspace: at least
+ *   llmie_mla_decode_workspace_bytes(batch, head_num, max_ctx ? max_ctx : max_seq_len) bytes, 16-byte aligned (0 bytes: one split,
+ *   NULL allowed); too small: LLMIE_ERR_WORKSPACE.
+ * llmie_mla_out_project: out [batch, head_num * 128], out[b, h] = W_UV[h] o_lat[b, h]: the input of llmie_linear with o_proj.
+ * llmie_mla_decode_plan: host only.  The launch llmie_mla_decode makes for such a call (the entry calls the same planner), as one
+ *   line: "mla f16 nh128 hb16 tile32 chunk256 grid 8x8x2 merge 128x2/128" -- heads per workgroup, keys per staged tile, tokens per
+ *   split, grid (splits, head blocks, batch), the merge launch grid/block or "none" with one split.  workspace_bytes < 0: no workspace.
+ *   NULL for a call the entry refuses (*status = its code, llmie_last_error() says why). */
+#define LLMIE_MLA_KV_LORA_RANK 512
+#define LLMIE_MLA_QK_ROPE_HEAD_DIM 64
+#define LLMIE_MLA_QK_NOPE_HEAD_DIM 128
+#define LLMIE_MLA_V_HEAD_DIM 128
+#define LLMIE_MLA_ROW 576          /* kv_lora_rank + qk_rope_head_dim: halves per cached token */
+#define LLMIE_MLA_PAGE_TOKENS 128
+size_t llmie_mla_decode_workspace_bytes(int batch, int head_num, int max_seq_len);
+int llmie_mla_kv_append(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, int layer, int batch,
+                        int max_seq_len, const int32_t *ctx_len_dev, const int32_t *block_table /* nullable: dense */, int max_pages,
+                        int num_pages, llmie_stream stream);
+int llmie_mla_q_absorb(const void *q, const void *kv_b, const void *rope_table, void *q_lat, int batch, int head_num, int max_seq_len,
+                       const int32_t *ctx_len_dev, llmie_stream stream);
+int llmie_mla_decode(const void *q_lat, const void *cache, void *o_lat, int layer, int batch, int head_num, int max_seq_len, int max_ctx,
+                     const int32_t *ctx_len_dev, float softmax_scale, void *workspace, size_t workspace_bytes,
+                     const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages, llmie_stream stream);
+int llmie_mla_out_project(const void *o_lat, const void *kv_b, void *out, int batch, int head_num, llmie_stream stream);
+const char *llmie_mla_decode_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
+                                  long long workspace_bytes, int *status);
+
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
  * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the

@@ -173,6 +173,12 @@ _SIGS = {
     "llmie_decoder_plan_name": [_vp, _i, _i, C.c_uint, C.c_uint],
     "llmie_decoder_prefill_layer_plan": [_vp, _i, _i, _i, C.c_uint, C.c_uint, _vp],
     "llmie_decoder_debug_stamps": [_vp, _vp],
+    "llmie_mla_decode_workspace_bytes": [_i, _i, _i],
+    "llmie_mla_kv_append": [_vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_q_absorb": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "llmie_mla_decode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp, _i, _i, _vp],
+    "llmie_mla_out_project": [_vp, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_decode_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
     "llmie_target_arch": [],
@@ -199,6 +205,8 @@ _RESTYPES = {
     "llmie_lora_workspace_bytes": _sz,
     "llmie_decoder_lora_workspace_bytes": _sz,
     "llmie_moe_workspace_bytes": _sz,
+    "llmie_mla_decode_workspace_bytes": _sz,
+    "llmie_mla_decode_plan": C.c_char_p,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_moe_ffn_plan_ex": C.c_char_p,
@@ -427,6 +435,68 @@ def rope_table(max_pos, head_size, rotary_dim, base, scaling=None):
     _check(lib().llmie_rope_table_fill(buf.ctypes.data, max_pos, head_size, rotary_dim, base, C.addressof(sc) if sc is not None else None),
            "rope_table_fill")
     return buf[:shape[0] * shape[1] * 2].reshape(shape)
+
+
+# ------------------------------------------------------------------ MLA decode attention (DeepSeek; include/llmie.h llmie_mla_*)
+MLA_LATENT, MLA_ROPE, MLA_NOPE, MLA_V, MLA_ROW, MLA_PAGE = 512, 64, 128, 128, 576, 128
+
+
+def _mla_cache(cache, block_table):
+    """(max_seq_len or None, max_pages, num_pages) of a dense [L, batch, S, 576] / paged [L, pages, 128, 576] latent cache"""
+    assert cache.dim() == 4 and cache.shape[3] == MLA_ROW, "latent cache: [layers, batch, max_seq_len, 576] or [layers, pages, 128, 576]"
+    if block_table is None:
+        return cache.shape[2], 0, 0
+    assert cache.shape[2] == MLA_PAGE, "paged latent cache: pages of 128 tokens"
+    return None, block_table.shape[1], cache.shape[1]
+
+
+def mla_decode_plan(batch, head_num, max_seq_len, max_ctx=0, paged=False, max_pages=0, num_pages=0, workspace_bytes="exact"):
+    """(plan text or None, status) of llmie_mla_decode's launch: e.g. "mla f16 nh128 hb16 tile32 chunk256 grid 8x8x2 merge 128x2/128"
+    (heads per workgroup, key tile, tokens per split, grid, merge launch or "none"); None where the entry refuses the call
+    (llmie_last_error() says why).  workspace_bytes: a size, None (no workspace) or "exact".  No device needed."""
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_mla_decode_workspace_bytes(batch, head_num, max_ctx if max_ctx > 0 else max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_mla_decode_plan(batch, head_num, max_seq_len, max_ctx, int(paged), max_pages, num_pages,
+                                    -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_workspace(batch, head_num, max_seq_len, device="cuda"):
+    """uint8 scratch for mla_decode's split partials (one element at least, so that it is a tensor)"""
+    import torch
+    return torch.empty(max(lib().llmie_mla_decode_workspace_bytes(batch, head_num, max_seq_len), 16), dtype=torch.uint8, device=device)
+
+
+def mla_kv_append(kv_a, gamma, eps, rope_tab, cache, layer, ctx_len, block_table=None, max_seq_len=None):
+    """cache row ctx_len[b] - 1 of `layer` <- rmsnorm(kv_a[b, :512]) * gamma || rope(kv_a[b, 512:]); paged: max_seq_len given"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_kv_append(_p(kv_a), _p(gamma), eps, _p(rope_tab), _p(cache), layer, kv_a.shape[0],
+                                     dense_len if block_table is None else max_seq_len, _p(ctx_len), _p(block_table), max_pages, num_pages,
+                                     _st()), "mla_kv_append")
+
+
+def mla_q_absorb(q, kv_b, rope_tab, q_lat, ctx_len, max_seq_len):
+    """q [batch, heads, 192], kv_b [heads, 256, 512] -> q_lat [batch, heads, 576] = W_UK^T q_nope || rope(q_pe)"""
+    _check(lib().llmie_mla_q_absorb(_p(q), _p(kv_b), _p(rope_tab), _p(q_lat), q.shape[0], q.shape[1], max_seq_len, _p(ctx_len), _st()),
+           "mla_q_absorb")
+    return q_lat
+
+
+def mla_decode(q_lat, cache, layer, ctx_len, softmax_scale, o_lat, workspace=None, block_table=None, max_seq_len=None, max_ctx=0):
+    """o_lat [batch, heads, 512] <- plain softmax attention of q_lat over the latent cache rows t < ctx_len[b]"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_decode(_p(q_lat), _p(cache), _p(o_lat), layer, q_lat.shape[0], q_lat.shape[1],
+                                  dense_len if block_table is None else max_seq_len, max_ctx, _p(ctx_len), softmax_scale, _p(workspace),
+                                  workspace.numel() * workspace.element_size() if workspace is not None else 0, _p(block_table), max_pages,
+                                  num_pages, _st()), "mla_decode")
+    return o_lat
+
+
+def mla_out_project(o_lat, kv_b, out):
+    """out [batch, heads * 128] <- W_UV[h] o_lat[b, h]"""
+    _check(lib().llmie_mla_out_project(_p(o_lat), _p(kv_b), _p(out), o_lat.shape[0], o_lat.shape[1], _st()), "mla_out_project")
+    return out
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):

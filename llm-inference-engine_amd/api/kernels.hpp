@@ -577,3 +577,34 @@ inline void launchLinearMxfp4(TensorWrapper<half> *x, const uint8_t *wq, const u
     LLMIE_CALL(llmie_linear_mxfp4(x->data, wq, scale, y->data, M, K, N, bias ? bias->data : nullptr, residual ? residual->data : nullptr,
                                   ws ? llmie_api::scratch(ws) : nullptr, ws, llmie_api::st()));
 }
+
+// No reference launchers: Multi-head Latent Attention, one decode step in the absorbed form (include/llmie.h llmie_mla_*; DeepSeek-V2 /
+// V3 / R1, Kimi-K2).  cache: ONE latent cache [L, batch, max_seq_len, 576] -- or, with block_table [batch, max_pages], the pool
+// [L, num_pages, 128, 576] and max_seq_len given --, ctx_len [batch] = context length of every sequence with this step's token,
+// rope_table [max_pos][32] (cos, sin), kv_b [head_num, 256, 512] = kv_b_proj.weight as stored.  Per layer: append, absorb, attention,
+// out project (whose output is the input of o_proj).
+inline void launchMlaKvAppend(TensorWrapper<half> *kv_a, TensorWrapper<half> *gamma, float eps, const void *rope_table, TensorWrapper<half> *cache,
+                              int layer, TensorWrapper<int> *ctx_len, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(kv_a->shape[1] == LLMIE_MLA_ROW && cache->shape[3] == LLMIE_MLA_ROW, "kv_a should be [batch, 576], the cache [.., 576]");
+    LLMIE_CALL(llmie_mla_kv_append(kv_a->data, gamma->data, eps, rope_table, cache->data, layer, kv_a->shape[0],
+                                   block_table ? max_seq_len : cache->shape[2], ctx_len->data, block_table ? block_table->data : nullptr,
+                                   block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaQAbsorb(TensorWrapper<half> *q, TensorWrapper<half> *kv_b, const void *rope_table, TensorWrapper<int> *ctx_len, int max_seq_len,
+                             TensorWrapper<half> *q_lat) {
+    LLM_CHECK_WITH_INFO(q->shape[2] == 192 && q_lat->shape[2] == LLMIE_MLA_ROW, "q should be [batch, head_num, 192], q_lat [batch, head_num, 576]");
+    LLMIE_CALL(llmie_mla_q_absorb(q->data, kv_b->data, rope_table, q_lat->data, q->shape[0], q->shape[1], max_seq_len, ctx_len->data, llmie_api::st()));
+}
+inline void launchMlaDecodeAttention(TensorWrapper<half> *q_lat, TensorWrapper<half> *cache, int layer, TensorWrapper<int> *ctx_len, float softmax_scale,
+                                     TensorWrapper<half> *o_lat, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0, int max_ctx = 0) {
+    const int batch = q_lat->shape[0], head_num = q_lat->shape[1];
+    if (!block_table) max_seq_len = cache->shape[2];
+    const size_t ws = llmie_mla_decode_workspace_bytes(batch, head_num, max_ctx > 0 ? max_ctx : max_seq_len);
+    LLMIE_CALL(llmie_mla_decode(q_lat->data, cache->data, o_lat->data, layer, batch, head_num, max_seq_len, max_ctx, ctx_len->data, softmax_scale,
+                                ws ? llmie_api::scratch(ws) : nullptr, ws, block_table ? block_table->data : nullptr,
+                                block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaOutProject(TensorWrapper<half> *o_lat, TensorWrapper<half> *kv_b, TensorWrapper<half> *out) {
+    LLM_CHECK_WITH_INFO(out->shape[0] == o_lat->shape[0] && out->shape[1] == o_lat->shape[1] * LLMIE_MLA_V_HEAD_DIM, "out should be [batch, head_num * 128]");
+    LLMIE_CALL(llmie_mla_out_project(o_lat->data, kv_b->data, out->data, o_lat->shape[0], o_lat->shape[1], llmie_api::st()));
+}

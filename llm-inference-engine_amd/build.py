@@ -19,6 +19,9 @@ LIB = os.path.join(LIBDIR, "libllmie.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
+# per-source additions: the MLA kernels are compiled without the packed fp32 VALU forms (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32)
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"mla.hip": NO_PK_F32}
 
 
 def _sources():
@@ -36,7 +39,7 @@ def _compile(src, force, hdr_m):
     o = os.path.join(OBJ, src + ".o")
     if (not force and os.path.exists(o) and os.path.getmtime(o) >= max(os.path.getmtime(s), hdr_m)):
         return o, False
-    cmd = [HIPCC] + FLAGS + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", s, "-o", o]
+    cmd = [HIPCC] + FLAGS + EXTRA_FLAGS.get(src, []) + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", s, "-o", o]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, r.stdout, r.stderr))

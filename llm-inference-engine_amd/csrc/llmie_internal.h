@@ -321,6 +321,25 @@ struct DecodeAttnIo {
 // decode attention of one layer with bias, RoPE and the KV append fused in front: plan, refuse or launch
 int decoder_mha_rope(const DecodeAttnShape &g, const DecodeAttnIo &io, const KvView &kv, const DecodePos &pos, int layer, hipStream_t st);
 
+// ---- MLA decode attention (mla.hip): one pure host planner checks the call and decides the launch, the entry runs the plan ----
+struct MlaDecodeCall {
+    int batch, head_num, max_seq_len;
+    int max_ctx;                       // host bound of the context lengths, 0: only the device knows them
+    bool paged;
+    int max_pages, num_pages;
+    bool workspace;
+    size_t workspace_bytes;
+};
+struct MlaDecodePlan {
+    int heads, tile, chunk;            // query heads per workgroup, keys per staged tile, tokens per split
+    int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
+    int grid[3];                       // (splits, head blocks, batch)
+    bool merge;                        // more than one split: mla_merge_kernel follows
+    int merge_grid[2], merge_block;
+    size_t workspace_bytes;            // the split partials (0 with one split)
+};
+int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
+
 // prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip: one pure host planner decides the
 // launch, one launcher runs the plan
 struct PrefillAttnPlan {

@@ -1,0 +1,487 @@
+// Multi-head Latent Attention, decode step (DeepSeek-V2 / V3 / R1, Kimi-K2), in the absorbed form: the cache holds ONE row of
+// 576 halves per token (512 latent dims c, 64 rotated k_pe dims), every query head attends over that row, and the per-head
+// projections W_UK / W_UV are folded into the query and the output (include/llmie.h, llmie_mla_*).  Four launches per layer:
+//   mla_kv_append_kernel    RMSNorm(c) * gamma  ||  rope(k_pe)  ->  cache row ctx - 1               (one wave per sequence)
+//   mla_q_absorb_kernel     q_lat = (W_UK[h]^T q_nope) || rope(q_pe)                                (MFMA, W_UK staged once)
+//   mla_decode_kernel       split-KV flash decode over the latent rows, 16 heads per workgroup      (MFMA, the hot path)
+//   mla_merge_kernel        fixed-order merge of the split partials (only with more than one split)
+//   mla_out_project_kernel  out[b, h] = W_UV[h] o_lat[b, h]                                         (MFMA, operands from registers)
+//
+// mla_decode_kernel.  Grid (splits, head_num / 16, batch), 4 waves.  A workgroup walks one chunk of kMlaChunk tokens of one
+// sequence in tiles of kMlaTile = 32 keys.  A tile (32 rows x 576 halves) goes global -> registers -> LDS once and serves BOTH
+// products from there: all 576 columns are the A operand of S^T = C . Q^T, the first 512 columns are -- read with the transposed
+// LDS read ds_read_b64_tr_b16 -- the A operand of O^T += C^T . P^T.  Rows are padded to 592 halves (1184 bytes = 160 mod 256):
+// the 4 rows x 32 bytes a 16-lane group of the transposed read addresses, and the 4 rows of the next group, fall into 8 different
+// 32-byte bank groups.  Two tile buffers: tile t+1 is published while tile t is multiplied and tile t+2 is in flight in
+// registers, one barrier per iteration for the staging (as prefill_flash_kernel) plus one for the logit exchange below.
+//   S^T: wave (kh, kk) multiplies keys 16 kh .. +15 by dims 288 kk .. +287 (9 MFMA steps; its q fragments, 36 VGPRs, come from
+//        global memory once) and leaves the partial logits in LDS (2 x 2 KB, fp32).
+//   softmax: after the barrier EVERY wave adds the two partials of all 32 keys x 16 heads (8 values per lane, in exactly the
+//        order the P^T operand wants them) and keeps the same running max / sum -- redundant, a few dozen VALU slots, and it
+//        saves a second exchange of m, l and the fp16 P tile.
+//   O^T: wave w accumulates output dims 128 w .. +127: 16 transposed reads, 8 MFMAs, 8 floatx4 accumulators.
+// Rows of a tile at or past ctx re-read row ctx - 1 (same tile, same page) and their logits are -inf before the max; no load
+// leaves the context and no block-table entry past (ctx - 1) / 128 is read.  The chunking depends on ctx alone, so a sequence's
+// bits do not depend on the batch, its slot or the grid.  Plain softmax: out = sum p v / sum p, no epsilon in the denominator.
+#include "llmie_internal.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace llmie {
+
+namespace {
+
+constexpr int kLat = LLMIE_MLA_KV_LORA_RANK, kRope = LLMIE_MLA_QK_ROPE_HEAD_DIM, kRow = LLMIE_MLA_ROW;
+constexpr int kNope = LLMIE_MLA_QK_NOPE_HEAD_DIM, kVd = LLMIE_MLA_V_HEAD_DIM, kQ = kNope + kRope, kPage = LLMIE_MLA_PAGE_TOKENS;
+constexpr int kMlaHeads = 16, kMlaTile = 32, kMlaChunk = 256, kMlaStride = kRow + 16, kMlaMergeBlock = 128;
+static_assert(kLat == 512 && kRope == 64 && kRow == 576 && kNope == 128 && kVd == 128, "the kernels are written for this geometry");
+static_assert(kPage % kMlaTile == 0 && kMlaChunk % kMlaTile == 0, "a tile never crosses a page or a chunk");
+static_assert((kMlaStride * 2) % 64 == 32, "row stride = an odd multiple of 32 bytes: conflict-free transposed reads");
+
+typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
+typedef __attribute__((address_space(3))) fp16x4_t *lds_fp16x4_ptr;
+struct Tr8 { fp16x4_t lo, hi; };   // two transposed reads side by side are the 8-half MFMA operand
+
+__device__ __forceinline__ bool mla_live(int ctx, int max_ctx) { return ctx >= 1 && ctx <= max_ctx; }
+
+// where the cache row of (sequence b, position t) begins, in halves
+__device__ __forceinline__ size_t mla_row_off(const int32_t *__restrict__ table, int max_pages, size_t layer_off, int b, int t, int max_seq_len) {
+    return table ? layer_off + (static_cast<size_t>(table[static_cast<size_t>(b) * max_pages + t / kPage]) * kPage + t % kPage) * kRow
+                 : layer_off + (static_cast<size_t>(b) * max_seq_len + t) * kRow;
+}
+
+// ---- append: one wave per sequence.  Lane i holds c[8 i .. 8 i + 7]; sum of squares: ss = fma(c_j, c_j, ss) over j = 0 .. 7 in
+// that order from ss = 0, then the xor butterfly over lane distances 32, 16, 8, 4, 2, 1 (the order include/llmie.h states) ----
+__global__ __launch_bounds__(64) void mla_kv_append_kernel(const half_t *__restrict__ kv_a, const half_t *__restrict__ gamma, float eps,
+                                                           const float2 *__restrict__ rope, half_t *__restrict__ cache, size_t layer_off,
+                                                           int max_seq_len, const int32_t *__restrict__ ctx_len,
+                                                           const int32_t *__restrict__ table, int max_pages) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int ctx = ctx_len[b];
+    if (!mla_live(ctx, max_seq_len)) return;
+    const int pos = ctx - 1;
+    half_t *row = cache + mla_row_off(table, max_pages, layer_off, b, pos, max_seq_len);
+    const half_t *src = kv_a + static_cast<size_t>(b) * kRow;
+    const half8_t x = *reinterpret_cast<const half8_t *>(src + 8 * lane);
+    const half8_t g = *reinterpret_cast<const half8_t *>(gamma + 8 * lane);
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(to_f32(x[j]), to_f32(x[j]), ss);
+    ss = lane_xor_sum<32>(ss);
+    ss = lane_xor_sum<16>(ss);
+    ss = lane_xor_sum<8>(ss);
+    ss = lane_xor_sum<4>(ss);
+    ss = lane_xor_sum<2>(ss);
+    ss = lane_xor_sum<1>(ss);
+    const float inv = 1.f / sqrtf(ss * (1.f / kLat) + eps);
+    half8_t y;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = from_f32<half_t>(to_f32(x[j]) * inv * to_f32(g[j]));
+    *reinterpret_cast<half8_t *>(row + 8 * lane) = y;
+    if (lane < kRope / 2) {
+        const float2 cs = rope[static_cast<size_t>(pos) * (kRope / 2) + lane];
+        const float x0 = to_f32(src[kLat + lane]), x1 = to_f32(src[kLat + kRope / 2 + lane]);
+        row[kLat + lane] = from_f32<half_t>(x0 * cs.x - x1 * cs.y);
+        row[kLat + kRope / 2 + lane] = from_f32<half_t>(x1 * cs.x + x0 * cs.y);
+    }
+}
+
+// ---- q absorb: grid (4 column blocks of 128, head_num), 4 waves.  W_UK[h] (rows h * 256 .. + 127 of kv_b, [n][c]) is the
+// [K, N] operand as stored: its 128 x 128 block goes to LDS once, each wave gathers the fragments of its 32 columns with the
+// transposed read (8 fragments, kept in registers) and then walks the batch 16 rows at a time: O^T[c][b] = sum_n W[n][c] q[b][n].
+// k index 8 q + j of a 32-step stands for n = 32 s + 16 (j >> 2) + 4 q + (j & 3) on both operands. ----
+__global__ __launch_bounds__(256) void mla_q_absorb_kernel(const half_t *__restrict__ qin, const half_t *__restrict__ kv_b,
+                                                           const float2 *__restrict__ rope, half_t *__restrict__ q_lat, int batch,
+                                                           int head_num, int max_seq_len, const int32_t *__restrict__ ctx_len) {
+    constexpr int WS = 128 + 16;   // 288-byte rows: 32 mod 256
+    __shared__ __attribute__((aligned(16))) half_t Ws[kNope * WS];
+    const int cb = blockIdx.x, h = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const half_t *w = kv_b + static_cast<size_t>(h) * (kNope + kVd) * kLat + cb * 128;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int id = tid + 256 * i, n = id >> 4, ch = id & 15;
+        *reinterpret_cast<half8_t *>(Ws + n * WS + ch * 8) = *reinterpret_cast<const half8_t *>(w + static_cast<size_t>(n) * kLat + ch * 8);
+    }
+    __syncthreads();
+    half8_t wf[4][2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            const half_t *blk = Ws + (32 * s + 4 * q + (r >> 2)) * WS + 32 * wave + 16 * dt + 4 * (r & 3);
+            const fp16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk));
+            const fp16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * WS));
+            wf[s][dt] = __builtin_bit_cast(half8_t, Tr8{lo, hi});
+        }
+    for (int bt = 0; bt < batch; bt += 16) {
+        const int brow = min(bt + r, batch - 1);
+        const half_t *qp = qin + (static_cast<size_t>(brow) * head_num + h) * kQ;
+        half8_t pf[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const half4_t lo = *reinterpret_cast<const half4_t *>(qp + 32 * s + 4 * q);
+            const half4_t hi = *reinterpret_cast<const half4_t *>(qp + 32 * s + 16 + 4 * q);
+            pf[s] = half8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        }
+        const bool live = bt + r < batch && mla_live(ctx_len[brow], max_seq_len);
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][dt], pf[s], acc, 0, 0, 0);
+            if (live) {
+                const half4_t v = {from_f32<half_t>(acc[0]), from_f32<half_t>(acc[1]), from_f32<half_t>(acc[2]), from_f32<half_t>(acc[3])};
+                *reinterpret_cast<half4_t *>(q_lat + (static_cast<size_t>(brow) * head_num + h) * kRow + cb * 128 + 32 * wave + 16 * dt + 4 * q) = v;
+            }
+        }
+    }
+    if (cb == 0) {   // the rotated q_pe of this head, pairs (j, j + 32) at position ctx - 1
+        for (int idx = tid; idx < batch * (kRope / 2); idx += 256) {
+            const int b = idx / (kRope / 2), j = idx % (kRope / 2);
+            const int ctx = ctx_len[b];
+            if (!mla_live(ctx, max_seq_len)) continue;
+            const float2 cs = rope[static_cast<size_t>(ctx - 1) * (kRope / 2) + j];
+            const half_t *qp = qin + (static_cast<size_t>(b) * head_num + h) * kQ + kNope;
+            half_t *dst = q_lat + (static_cast<size_t>(b) * head_num + h) * kRow + kLat;
+            const float x0 = to_f32(qp[j]), x1 = to_f32(qp[j + kRope / 2]);
+            dst[j] = from_f32<half_t>(x0 * cs.x - x1 * cs.y);
+            dst[j + kRope / 2] = from_f32<half_t>(x1 * cs.x + x0 * cs.y);
+        }
+    }
+}
+
+// ---- out project: grid (head_num, 2), 4 waves of 16 value rows each.  W_UV[h] (rows h * 256 + 128 .. of kv_b, [v][c]) is the
+// [N, K] operand as stored: a wave's 16 rows x 512 are 16 A fragments loaded straight into registers, once; the batch goes by
+// 16 rows at a time (B fragments straight from o_lat).  No LDS. ----
+__global__ __launch_bounds__(256) void mla_out_project_kernel(const half_t *__restrict__ o_lat, const half_t *__restrict__ kv_b,
+                                                              half_t *__restrict__ out, int batch, int head_num) {
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int vb = blockIdx.y * 64 + 16 * wave;
+    const half_t *w = kv_b + (static_cast<size_t>(h) * (kNope + kVd) + kNope + vb + r) * kLat + 8 * q;
+    half8_t af[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) af[s] = *reinterpret_cast<const half8_t *>(w + 32 * s);
+    for (int bt = 0; bt < batch; bt += 16) {
+        const int brow = min(bt + r, batch - 1);
+        const half_t *op = o_lat + (static_cast<size_t>(brow) * head_num + h) * kLat + 8 * q;
+        half8_t bf[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) bf[s] = *reinterpret_cast<const half8_t *>(op + 32 * s);
+        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[s], bf[s], acc, 0, 0, 0);
+        if (bt + r < batch) {
+            const half4_t v = {from_f32<half_t>(acc[0]), from_f32<half_t>(acc[1]), from_f32<half_t>(acc[2]), from_f32<half_t>(acc[3])};
+            *reinterpret_cast<half4_t *>(out + (static_cast<size_t>(brow) * head_num + h) * kVd + vb + 4 * q) = v;
+        }
+    }
+}
+
+// ---- the attention ----
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mla_decode_kernel(
+    const half_t *__restrict__ q_lat, const half_t *__restrict__ cache, half_t *__restrict__ o_lat, float *__restrict__ ws_o,
+    float2 *__restrict__ ws_ml, const int32_t *__restrict__ ctx_len, const int32_t *__restrict__ table, int max_pages, size_t layer_off,
+    int head_num, int max_seq_len, int max_ctx, float scale2 /* softmax_scale * log2(e) */) {
+    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes
+    __shared__ __attribute__((aligned(16))) float Sp[2 * 8 * 16 * 4];                // partial logits [kk][key / 4][head][key % 4]
+    const int split = blockIdx.x, hb = blockIdx.y, b = blockIdx.z, splits = gridDim.x;
+    const int ctx = ctx_len[b];
+    if (!mla_live(ctx, max_ctx)) return;
+    const int t_begin = split * kMlaChunk;
+    if (t_begin >= ctx) return;
+    const int n_tiles = (min(ctx, t_begin + kMlaChunk) - t_begin + kMlaTile - 1) / kMlaTile;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int kh = wave & 1, kk = wave >> 1;
+    const int head = hb * kMlaHeads + r;
+
+    half8_t qf[9];   // Q[head r][288 kk + 32 s + 8 q ..]: the B operand of this wave's 9 steps
+    {
+        const half_t *qp = q_lat + (static_cast<size_t>(b) * head_num + head) * kRow + 288 * kk + 8 * q;
+#pragma unroll
+        for (int s = 0; s < 9; ++s) qf[s] = *reinterpret_cast<const half8_t *>(qp + 32 * s);
+    }
+
+    constexpr int NCH = kMlaTile * kRow / 8 / 256;   // 9 sixteen-byte pieces of a tile per thread
+    half8_t treg[NCH];
+    auto fetch_tile = [&](int t0) {   // global -> registers; one page lookup per tile, wave-uniform
+        const size_t base = table ? layer_off + static_cast<size_t>(__builtin_amdgcn_readfirstlane(table[static_cast<size_t>(b) * max_pages + t0 / kPage])) * kPage * kRow
+                                  : layer_off + static_cast<size_t>(b) * max_seq_len * kRow;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
+            const int t = min(t0 + row, ctx - 1);   // (t0 <= ctx - 1 < t0 + 32 where the clamp acts: same tile, same page)
+            treg[i] = *reinterpret_cast<const half8_t *>(cache + base + static_cast<size_t>(table ? t % kPage : t) * kRow + ch * 8);
+        }
+    };
+    auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
+            *reinterpret_cast<half8_t *>(Ts[buf] + row * kMlaStride + ch * 8) = treg[i];
+        }
+    };
+
+    floatx4 o[8];   // O^T: dims 128 wave + 16 dt + 4 q + e, column = head r
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;   // log2 domain, scale applied; l_run: this lane's 8 of a tile's 32 keys
+
+    fetch_tile(t_begin);
+    publish_tile(0);
+    if (1 < n_tiles) fetch_tile(t_begin + kMlaTile);
+    for (int it = 0; it < n_tiles; ++it) {
+        const int t0 = t_begin + it * kMlaTile;
+        const half_t *Tt = Ts[it & 1];
+        __syncthreads();   // tile `it` published; every wave done with tile it - 1 (the other buffer) and with its logits
+        if (it + 1 < n_tiles) {
+            publish_tile((it + 1) & 1);
+            if (it + 2 < n_tiles) fetch_tile(t0 + 2 * kMlaTile);   // in flight under this iteration's MFMAs
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- S^T partial: keys 16 kh + r, dims 288 kk .. ----
+        {
+            half8_t kf[9];
+            const half_t *kp = Tt + (16 * kh + r) * kMlaStride + 288 * kk + 8 * q;
+#pragma unroll
+            for (int s = 0; s < 9; ++s) kf[s] = *reinterpret_cast<const half8_t *>(kp + 32 * s);
+            floatx4 sacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 9; ++s) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], qf[s], sacc, 0, 0, 0);
+            // sacc[e] = S[key 16 kh + 4 q + e][head r]
+            *reinterpret_cast<floatx4 *>(Sp + (((kk * 8 + 4 * kh + q) * 16 + r) << 2)) = sacc;
+        }
+        __syncthreads();   // both halves of every logit are there
+        float s8[8];       // keys t0 + 16 (j >> 2) + 4 q + (j & 3): the k index 8 q + j of the P^T operand
+        {
+            const floatx4 a0 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + q) * 16 + r) << 2));
+            const floatx4 b0 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + q) * 16 + r) << 2));
+            const floatx4 a1 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + 4 + q) * 16 + r) << 2));
+            const floatx4 b1 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + 4 + q) * 16 + r) << 2));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s8[e] = a0[e] + b0[e], s8[4 + e] = a1[e] + b1[e];
+        }
+        float mloc = -INFINITY;
+        if (t0 + kMlaTile > ctx) {   // wave-uniform: only the context's last tile masks
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int t = t0 + 16 * (j >> 2) + 4 * q + (j & 3);
+                s8[j] = t < ctx ? s8[j] : -INFINITY;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mloc = fmaxf(mloc, s8[j]);
+        mloc = lane_xor_max<16>(lane_xor_max<32>(mloc)) * scale2;   // over the 4 lanes of head r; scale2 > 0; key t0 < ctx: finite
+        const float m_new = fmaxf(m_run, mloc);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: 2^(-inf) = 0
+        float lsum = 0.f;
+        half8_t pf;
+        typedef float float2v_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j], scale2, -m_new));
+            const float p1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j + 1], scale2, -m_new));
+            lsum += p0 + p1;
+            const half2_t hh = __builtin_convertvector(float2v_t{p0, p1}, half2_t);
+            pf[j] = hh[0];
+            pf[j + 1] = hh[1];
+        }
+        l_run = l_run * alpha + lsum;
+        m_run = m_new;
+        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+        }
+        // ---- O^T += C^T . P^T: A fragment = C[key(q, j)][128 wave + 16 dt + r], gathered down a column by the transposed read ----
+        {
+            const half_t *blk = Tt + (4 * q + (r >> 2)) * kMlaStride + 128 * wave + 4 * (r & 3);
+            fp16x4_t lo[8], hi[8];
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) {
+                lo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + dt * 16));
+                hi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * kMlaStride + dt * 16));
+            }
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt)
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, Tr8{lo[dt], hi[dt]}), pf, o[dt], 0, 0, 0);
+        }
+    }
+    const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run));
+    const size_t bh = static_cast<size_t>(b) * head_num + head;
+    if (splits == 1) {   // the only split: the output itself
+        const float inv = 1.f / l;
+        half_t *op = o_lat + bh * kLat + 128 * wave + 4 * q;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {
+            const half4_t v = {from_f32<half_t>(o[dt][0] * inv), from_f32<half_t>(o[dt][1] * inv), from_f32<half_t>(o[dt][2] * inv),
+                               from_f32<half_t>(o[dt][3] * inv)};
+            *reinterpret_cast<half4_t *>(op + 16 * dt) = v;
+        }
+    } else {
+        float *op = ws_o + (bh * splits + split) * kLat + 128 * wave + 4 * q;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) *reinterpret_cast<floatx4 *>(op + 16 * dt) = o[dt];
+        if (wave == 0 && q == 0) ws_ml[bh * splits + split] = make_float2(m_run, l);
+    }
+}
+
+// merge: grid (head_num, batch), 128 threads x 4 dims.  Splits 0 .. ceil(ctx / chunk) - 1 in that order: M = max m_i,
+// w_i = 2^(m_i - M), L = sum w_i l_i, out = (sum w_i o_i) / L.  One partial gives the bits of the one-split launch (w = 1).
+__global__ __launch_bounds__(kMlaMergeBlock) void mla_merge_kernel(const float *__restrict__ ws_o, const float2 *__restrict__ ws_ml,
+                                                                   half_t *__restrict__ o_lat, const int32_t *__restrict__ ctx_len,
+                                                                   int head_num, int max_ctx, int splits) {
+    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int ctx = ctx_len[b];
+    if (!mla_live(ctx, max_ctx)) return;
+    const int n = (ctx + kMlaChunk - 1) / kMlaChunk;   // <= splits (ctx <= max_ctx)
+    const size_t bh = static_cast<size_t>(b) * head_num + h;
+    float M = -INFINITY;
+    for (int i = 0; i < n; ++i) M = fmaxf(M, ws_ml[bh * splits + i].x);
+    float L = 0.f;
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < n; ++i) {
+        const float2 ml = ws_ml[bh * splits + i];
+        const float w = __builtin_amdgcn_exp2f(ml.x - M);
+        L = __builtin_fmaf(w, ml.y, L);
+        const floatx4 v = *reinterpret_cast<const floatx4 *>(ws_o + (bh * splits + i) * kLat + 4 * tid);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(w, v[e], acc[e]);
+    }
+    const float inv = 1.f / L;
+    const half4_t v = {from_f32<half_t>(acc[0] * inv), from_f32<half_t>(acc[1] * inv), from_f32<half_t>(acc[2] * inv),
+                       from_f32<half_t>(acc[3] * inv)};
+    *reinterpret_cast<half4_t *>(o_lat + bh * kLat + 4 * tid) = v;
+}
+
+int mla_heads_check(const char *who, int batch, int head_num) {
+    LLMIE_REQUIRE(batch >= 1, "%s: batch=%d should be >= 1", who, batch);
+    if (head_num < 16 || head_num > 128 || head_num % 16 != 0)
+        LLMIE_UNSUPPORTED("%s: head_num=%d: the MLA kernels take a multiple of 16 in [16, 128] (kv_lora_rank 512, rope 64, nope 128, v 128)", who,
+                          head_num);
+    return LLMIE_OK;
+}
+
+int mla_cache_check(const char *who, int max_seq_len, bool paged, int max_pages, int num_pages) {
+    LLMIE_REQUIRE(max_seq_len >= 1, "%s: max_seq_len=%d should be >= 1", who, max_seq_len);
+    if (paged) {
+        LLMIE_REQUIRE(num_pages >= 1 && max_pages >= 1, "%s: paged cache: max_pages=%d and num_pages=%d should be >= 1", who, max_pages, num_pages);
+        LLMIE_REQUIRE(static_cast<long long>(max_pages) * kPage >= max_seq_len, "%s: paged cache: max_pages=%d pages of %d tokens do not hold max_seq_len=%d",
+                      who, max_pages, kPage, max_seq_len);
+    }
+    return LLMIE_OK;
+}
+
+size_t mla_layer_off(int layer, int batch, int max_seq_len, bool paged, int num_pages) {
+    return static_cast<size_t>(layer) * (paged ? static_cast<size_t>(num_pages) * kPage : static_cast<size_t>(batch) * max_seq_len) * kRow;
+}
+
+}  // namespace
+
+// The one planner of llmie_mla_decode: every check that needs no pointer, then the launch.  Pure host code.
+int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
+    int rc = mla_heads_check(who, c.batch, c.head_num);
+    if (rc == LLMIE_OK) rc = mla_cache_check(who, c.max_seq_len, c.paged, c.max_pages, c.num_pages);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
+                  who, c.max_ctx, c.max_seq_len);
+    p->heads = kMlaHeads, p->tile = kMlaTile, p->chunk = kMlaChunk;
+    p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
+    p->grid[0] = (p->span + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch;
+    p->merge = p->grid[0] > 1;
+    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch, p->merge_block = kMlaMergeBlock;
+    p->workspace_bytes = p->merge ? static_cast<size_t>(c.batch) * c.head_num * p->grid[0] * (kLat + 2) * sizeof(float) : 0;
+    if (p->workspace_bytes > 0 && (!c.workspace || c.workspace_bytes < p->workspace_bytes)) {
+        set_error("%s: workspace of %zu bytes, %d splits of %d tokens need %zu (llmie_mla_decode_workspace_bytes)", who,
+                  c.workspace ? c.workspace_bytes : static_cast<size_t>(0), p->grid[0], kMlaChunk, p->workspace_bytes);
+        return LLMIE_ERR_WORKSPACE;
+    }
+    return LLMIE_OK;
+}
+
+}  // namespace llmie
+
+using namespace llmie;
+
+extern "C" size_t llmie_mla_decode_workspace_bytes(int batch, int head_num, int max_seq_len) {
+    if (batch < 1 || head_num < 1 || max_seq_len <= kMlaChunk) return 0;
+    return static_cast<size_t>(batch) * head_num * ((max_seq_len + kMlaChunk - 1) / kMlaChunk) * (kLat + 2) * sizeof(float);
+}
+
+extern "C" const char *llmie_mla_decode_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
+                                             long long workspace_bytes, int *status) {
+    static thread_local char text[160];
+    MlaDecodePlan p{};
+    const MlaDecodeCall c{batch, head_num, max_seq_len, max_ctx, paged != 0, max_pages, num_pages, workspace_bytes >= 0,
+                          workspace_bytes >= 0 ? static_cast<size_t>(workspace_bytes) : 0};
+    const int rc = plan_mla_decode("mla_decode_plan", c, &p);
+    if (status) *status = rc;
+    if (rc != LLMIE_OK) return nullptr;
+    int n = snprintf(text, sizeof(text), "mla f16 nh%d hb%d tile%d chunk%d grid %dx%dx%d merge ", head_num, p.heads, p.tile, p.chunk, p.grid[0],
+                     p.grid[1], p.grid[2]);
+    if (p.merge) snprintf(text + n, sizeof(text) - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
+    else snprintf(text + n, sizeof(text) - n, "none");
+    return text;
+}
+
+extern "C" int llmie_mla_kv_append(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, int layer, int batch,
+                                   int max_seq_len, const int32_t *ctx_len_dev, const int32_t *block_table, int max_pages, int num_pages,
+                                   llmie_stream stream) {
+    LLMIE_REQUIRE(kv_a && gamma && rope_table && cache && ctx_len_dev, "mla_kv_append: NULL operand");
+    LLMIE_REQUIRE(batch >= 1 && layer >= 0, "mla_kv_append: batch=%d should be >= 1 and layer=%d >= 0", batch, layer);
+    LLMIE_REQUIRE(eps > 0.f, "mla_kv_append: eps should be > 0");
+    const int rc = mla_cache_check("mla_kv_append", max_seq_len, block_table != nullptr, max_pages, num_pages);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(mis16(kv_a) == 0 && mis16(gamma) == 0 && mis16(cache) == 0, "mla_kv_append: kv_a, gamma and the cache should be 16-byte aligned");
+    hipLaunchKernelGGL(mla_kv_append_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const half_t *>(kv_a),
+                       static_cast<const half_t *>(gamma), eps, static_cast<const float2 *>(rope_table), static_cast<half_t *>(cache),
+                       mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), max_seq_len, ctx_len_dev, block_table, max_pages);
+    return launch_status("mla_kv_append");
+}
+
+extern "C" int llmie_mla_q_absorb(const void *q, const void *kv_b, const void *rope_table, void *q_lat, int batch, int head_num, int max_seq_len,
+                                  const int32_t *ctx_len_dev, llmie_stream stream) {
+    LLMIE_REQUIRE(q && kv_b && rope_table && q_lat && ctx_len_dev, "mla_q_absorb: NULL operand");
+    const int rc = mla_heads_check("mla_q_absorb", batch, head_num);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(max_seq_len >= 1, "mla_q_absorb: max_seq_len=%d should be >= 1", max_seq_len);
+    LLMIE_REQUIRE(mis16(q) == 0 && mis16(kv_b) == 0 && mis16(q_lat) == 0, "mla_q_absorb: q, kv_b and q_lat should be 16-byte aligned");
+    hipLaunchKernelGGL(mla_q_absorb_kernel, dim3(kLat / 128, head_num), dim3(256), 0, as_stream(stream), static_cast<const half_t *>(q),
+                       static_cast<const half_t *>(kv_b), static_cast<const float2 *>(rope_table), static_cast<half_t *>(q_lat), batch, head_num,
+                       max_seq_len, ctx_len_dev);
+    return launch_status("mla_q_absorb");
+}
+
+extern "C" int llmie_mla_decode(const void *q_lat, const void *cache, void *o_lat, int layer, int batch, int head_num, int max_seq_len, int max_ctx,
+                                const int32_t *ctx_len_dev, float softmax_scale, void *workspace, size_t workspace_bytes,
+                                const int32_t *block_table, int max_pages, int num_pages, llmie_stream stream) {
+    LLMIE_REQUIRE(q_lat && cache && o_lat && ctx_len_dev, "mla_decode: NULL operand");
+    LLMIE_REQUIRE(layer >= 0, "mla_decode: layer=%d should be >= 0", layer);
+    LLMIE_REQUIRE(softmax_scale > 0.f && std::isfinite(softmax_scale), "mla_decode: softmax_scale should be positive and finite");
+    MlaDecodePlan p{};
+    const MlaDecodeCall c{batch, head_num, max_seq_len, max_ctx, block_table != nullptr, max_pages, num_pages, workspace != nullptr, workspace_bytes};
+    const int rc = plan_mla_decode("mla_decode", c, &p);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(mis16(q_lat) == 0 && mis16(cache) == 0 && mis16(o_lat) == 0 && (!p.merge || mis16(workspace) == 0),
+                  "mla_decode: q_lat, the cache, o_lat and the workspace should be 16-byte aligned");
+    float *ws_o = static_cast<float *>(workspace);
+    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(batch) * head_num * p.grid[0] * kLat) : nullptr;
+    hipLaunchKernelGGL(mla_decode_kernel, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, as_stream(stream),
+                       static_cast<const half_t *>(q_lat), static_cast<const half_t *>(cache), static_cast<half_t *>(o_lat), ws_o, ws_ml, ctx_len_dev,
+                       block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), head_num, max_seq_len,
+                       p.span, softmax_scale * 1.44269504088896341f);
+    if (p.merge)
+        hipLaunchKernelGGL(mla_merge_kernel, dim3(p.merge_grid[0], p.merge_grid[1]), dim3(p.merge_block), 0, as_stream(stream), ws_o, ws_ml,
+                           static_cast<half_t *>(o_lat), ctx_len_dev, head_num, p.span, p.grid[0]);
+    return launch_status("mla_decode");
+}
+
+extern "C" int llmie_mla_out_project(const void *o_lat, const void *kv_b, void *out, int batch, int head_num, llmie_stream stream) {
+    LLMIE_REQUIRE(o_lat && kv_b && out, "mla_out_project: NULL operand");
+    const int rc = mla_heads_check("mla_out_project", batch, head_num);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(mis16(o_lat) == 0 && mis16(kv_b) == 0 && mis16(out) == 0, "mla_out_project: o_lat, kv_b and out should be 16-byte aligned");
+    hipLaunchKernelGGL(mla_out_project_kernel, dim3(head_num, kVd / 64), dim3(256), 0, as_stream(stream), static_cast<const half_t *>(o_lat),
+                       static_cast<const half_t *>(kv_b), static_cast<half_t *>(out), batch, head_num);
+    return launch_status("mla_out_project");
+}

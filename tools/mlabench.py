@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""MLA decode attention per layer, at DeepSeek shapes (16 and 128 heads, fp16 latent cache of 576 halves per token), same process,
+interleaved rounds, medians:
+
+    python tools/mlabench.py [--heads 16 128] [--batches 1 8 32] [--ctx 2048 8192] [--rounds 7] [--reps 10] [--out FILE]
+
+  decode    llmie_mla_decode alone (device-resident context lengths, grid sized from max_seq_len = ctx), dense and paged
+  chain     the four launches of a layer: mla_kv_append, mla_q_absorb, mla_decode, mla_out_project (dense and paged)
+  torch     a torch fp16 composition of the same absorbed math on the same tensors: matmul -> softmax -> matmul (dense cache)
+  bound     the arithmetic bound max(ctx * 1152 B * batch / HBM rate, FLOPs / MFMA rate) of the attention, FLOPs = 2 * batch * heads *
+            ctx * (576 + 512); the rates are the datasheet peaks bench.py reports under `peaks` (--hbm-gbs, --mfma-tflops)
+
+Prints one JSON line (and writes it to --out): microseconds, and the ratios decode / bound and torch / decode.  Only time is measured."""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+spec = importlib.util.spec_from_file_location("llmie_amd", os.path.join(ROOT, "llm-inference-engine_amd", "__init__.py"))
+llmie = importlib.util.module_from_spec(spec)
+sys.modules["llmie_amd"] = llmie
+spec.loader.exec_module(llmie)
+F16 = torch.float16
+SCALE = 1.0 / 192 ** 0.5
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / reps
+
+
+def interleaved(arms, rounds, reps):
+    """{name: (median, min, max) seconds per call}; a round runs every arm once, in turn; every arm is warmed up first"""
+    for fn in arms.values():
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            times[k].append(timed(fn, reps))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
+
+
+def bench(heads, batch, ctx, rounds, reps, hbm_gbs, mfma_tflops):
+    dev = "cuda"
+    pages = ctx // 128
+    dense = torch.empty((1, batch, ctx, 576), dtype=F16, device=dev).normal_(0, 0.5)
+    pool = dense.view(1, batch * pages, 128, 576).clone()
+    table = torch.randperm(batch * pages, device=dev).int().view(batch, pages).contiguous()
+    q = torch.randn((batch, heads, 192), device=dev).to(F16)
+    kv_b = (torch.randn((heads, 256, 512), device=dev) / 128 ** 0.5).to(F16)
+    kv_a = (0.5 * torch.randn((batch, 576), device=dev)).to(F16)
+    gamma = torch.ones(512, dtype=F16, device=dev)
+    tab = torch.from_numpy(llmie.rope_table(ctx, 64, 64, 10000.0)).to(dev)
+    lengths = torch.full((batch,), ctx, dtype=torch.int32, device=dev)
+    q_lat = torch.empty((batch, heads, 576), dtype=F16, device=dev)
+    o_lat = torch.empty((batch, heads, 512), dtype=F16, device=dev)
+    out = torch.empty((batch, heads * 128), dtype=F16, device=dev)
+    ws = llmie.mla_workspace(batch, heads, ctx)
+    llmie.mla_q_absorb(q, kv_b, tab, q_lat, lengths, ctx)
+    paged = dict(block_table=table, max_seq_len=ctx)
+
+    def decode(cache, **kw):
+        llmie.mla_decode(q_lat, cache, 0, lengths, SCALE, o_lat, ws, **kw)
+
+    def chain(cache, **kw):
+        llmie.mla_kv_append(kv_a, gamma, 1e-6, tab, cache, 0, lengths, **kw)
+        llmie.mla_q_absorb(q, kv_b, tab, q_lat, lengths, ctx)
+        decode(cache, **kw)
+        llmie.mla_out_project(o_lat, kv_b, out)
+
+    def composed():
+        c = dense[0]
+        p = torch.softmax(torch.matmul(q_lat, c.transpose(1, 2)) * SCALE, dim=-1)
+        return torch.matmul(p, c[:, :, :512])
+
+    t = interleaved({"decode": lambda: decode(dense), "decode_paged": lambda: decode(pool, **paged), "chain": lambda: chain(dense),
+                     "chain_paged": lambda: chain(pool, **paged), "torch": composed}, rounds, reps)
+    flops = 2.0 * batch * heads * ctx * (576 + 512)
+    t_hbm, t_mfma = ctx * 1152.0 * batch / (hbm_gbs * 1e9), flops / (mfma_tflops * 1e12)
+    bound = max(t_hbm, t_mfma)
+    return dict(heads=heads, batch=batch, ctx=ctx, plan=llmie.mla_decode_plan(batch, heads, ctx)[0],
+                us={k: round(v[0] * 1e6, 1) for k, v in t.items()}, spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
+                bound_us=round(bound * 1e6, 2), bound_by="hbm" if t_hbm >= t_mfma else "mfma",
+                decode_over_bound=round(t["decode"][0] / bound, 2), torch_over_decode=round(t["torch"][0] / t["decode"][0], 2))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--heads", type=int, nargs="+", default=[16, 128])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
+    ap.add_argument("--ctx", type=int, nargs="+", default=[2048, 8192])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--hbm-gbs", type=float, default=8000.0)
+    ap.add_argument("--mfma-tflops", type=float, default=2500.0)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "mlabench measures on the GPU: there is no CPU path"
+    res = dict(tool="mlabench", device=torch.cuda.get_device_name(0), peaks=dict(hbm_GBs_datasheet=a.hbm_gbs, mfma_f16_TFLOPs_datasheet=a.mfma_tflops))
+    res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
