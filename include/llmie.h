@@ -419,6 +419,43 @@ int llmie_mla_out_project(const void *o_lat, const void *kv_b, void *out, int ba
 const char *llmie_mla_decode_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
                                   long long workspace_bytes, int *status);
 
+/* ABI 3 (an addition).  MLA prefill in the UN-absorbed form: a prompt (or a chunk of one) is written to the latent cache in bulk,
+ * its latent rows are projected up once to per-head k_nope || v rows, and a flash kernel with q / k width 192 and v width 128
+ * attends over them -- 2 x (192 + 128) FLOP per key and head against the absorbed form's 2 x (576 + 512).  Geometry, dtypes, cache
+ * (dense or paged), rope_table and kv_b as above.  Sequences are packed as for llmie_decoder_prefill:
+ *   cum_dev[batch + 1]  device int32, exclusive prefix of the new-token counts: len_b = cum[b + 1] - cum[b], may be 0
+ *   hist_dev[batch]     device int32, tokens sequence b already has in the cache; ctx_b = hist[b] + len_b
+ *   max_q_len, kv_span  host bounds that size the grids: max_q_len >= every len_b, kv_span >= every ctx_b, kv_span <= max_seq_len
+ * A sequence with len_b = 0, len_b > max_q_len or ctx_b > kv_span is left wholly untouched: its cache, its kv_up rows, its output.
+ * llmie_mla_kv_append_rows: kv_a [total_tokens, 576], gamma [512].  Writes cache rows hist[b] .. ctx_b - 1 of every sequence, one wave
+ *   per packed token, with the arithmetic and summation order stated for llmie_mla_kv_append at position hist[b] + i: a row has the
+ *   bits of the row that single-token appends would have written.
+ * llmie_mla_kv_up: reads cache rows 0 .. ctx_b - 1 (history included) and writes kv_up [batch, kv_span, head_num, 256], caller-owned:
+ *   kv_up[b, t, h] = fp16(kv_b[h] c_t) -- columns 0..127 k_nope, 128..255 v; kv_b as stored ([N, K]), fp32 accumulation over the 512
+ *   latent dims, one rounding.  Rows at or past ctx_b are not written.
+ * llmie_mla_prefill: q [total_tokens, head_num, 192] (128 nope || 64 rope, NOT rotated) -> out [total_tokens, head_num * 128], the
+ *   input of llmie_linear with o_proj.  Query i of sequence b sits at p = hist[b] + i and sees keys t <= p:
+ *   out = sum_t softmax_t(softmax_scale * (q_nope . k_nope[t, h] + rope(q_pe, p) . k_pe[t])) v[t, h], k_nope and v from kv_up, k_pe
+ *   from the cache row (columns 512..575, rotated by the append, shared by all heads).  rope(q_pe) is computed in fp32 and rounded
+ *   once to fp16.  PLAIN softmax as llmie_mla_decode; softmax_scale > 0 is the caller's.  A row's bits depend on its position and
+ *   the rows it sees alone -- not on the batch, its slot, the grid, or how the prompt was cut into calls.
+ * llmie_mla_prefill_plan: host only.  The launches the three entries make for such a call (they call the same planner), as one line:
+ *   "mla_prefill f16 nh32 q64 kt32 flash 4x32x2 up tt64 hb4 6x8x2 append 400" -- query rows per workgroup, keys per staged tile, the
+ *   flash grid (query tiles, heads, batch), the up-projection's latent rows per staged tile, heads per workgroup and grid (token
+ *   tiles, head blocks, batch), the append grid (one wave per packed token).  NULL for a call the entries refuse. */
+int llmie_mla_kv_append_rows(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, int layer, int batch,
+                             int total_tokens, int max_q_len, int kv_span, int max_seq_len, const int32_t *cum_dev, const int32_t *hist_dev,
+                             const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages, llmie_stream stream);
+int llmie_mla_kv_up(const void *cache, const void *kv_b, void *kv_up, int layer, int batch, int head_num, int max_q_len, int kv_span,
+                    int max_seq_len, const int32_t *cum_dev, const int32_t *hist_dev, const int32_t *block_table /* nullable: dense */,
+                    int max_pages, int num_pages, llmie_stream stream);
+int llmie_mla_prefill(const void *q, const void *kv_up, const void *cache, const void *rope_table, void *out, int layer, int batch,
+                      int head_num, int total_tokens, int max_q_len, int kv_span, int max_seq_len, const int32_t *cum_dev,
+                      const int32_t *hist_dev, float softmax_scale, const int32_t *block_table /* nullable: dense */, int max_pages,
+                      int num_pages, llmie_stream stream);
+const char *llmie_mla_prefill_plan(int batch, int head_num, int total_tokens, int max_q_len, int kv_span, int max_seq_len, int paged,
+                                   int max_pages, int num_pages, int *status);
+
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
  * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the

@@ -179,6 +179,10 @@ _SIGS = {
     "llmie_mla_decode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp, _i, _i, _vp],
     "llmie_mla_out_project": [_vp, _vp, _vp, _i, _i, _vp],
     "llmie_mla_decode_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
+    "llmie_mla_kv_append_rows": [_vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_kv_up": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_prefill": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _i, _vp],
+    "llmie_mla_prefill_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
     "llmie_target_arch": [],
@@ -207,6 +211,7 @@ _RESTYPES = {
     "llmie_moe_workspace_bytes": _sz,
     "llmie_mla_decode_workspace_bytes": _sz,
     "llmie_mla_decode_plan": C.c_char_p,
+    "llmie_mla_prefill_plan": C.c_char_p,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_moe_ffn_plan_ex": C.c_char_p,
@@ -496,6 +501,45 @@ def mla_decode(q_lat, cache, layer, ctx_len, softmax_scale, o_lat, workspace=Non
 def mla_out_project(o_lat, kv_b, out):
     """out [batch, heads * 128] <- W_UV[h] o_lat[b, h]"""
     _check(lib().llmie_mla_out_project(_p(o_lat), _p(kv_b), _p(out), o_lat.shape[0], o_lat.shape[1], _st()), "mla_out_project")
+    return out
+
+
+# MLA prefill, un-absorbed (include/llmie.h): cum [batch + 1] / hist [batch] device int32 as for the decoder's prefill; max_q_len and
+# kv_span are host bounds of the new-token counts and the contexts (hist + new); paged: block_table and max_seq_len given
+def mla_prefill_plan(batch, head_num, max_q_len, kv_span, max_seq_len, total_tokens=None, paged=False, max_pages=0, num_pages=0):
+    """(plan text or None, status) of the three prefill launches: e.g. "mla_prefill f16 nh32 q64 kt32 flash 4x32x2 up tt64 hb4 6x8x2
+    append 400" (query rows per workgroup, keys per tile, flash grid, up-projection tile / head block / grid, append grid); None where
+    the entries refuse the call (llmie_last_error() says why).  total_tokens: batch * max_q_len when not given.  No device needed."""
+    status = C.c_int(0)
+    t = lib().llmie_mla_prefill_plan(batch, head_num, batch * max_q_len if total_tokens is None else total_tokens, max_q_len, kv_span,
+                                     max_seq_len, int(paged), max_pages, num_pages, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_kv_append_rows(kv_a, gamma, eps, rope_tab, cache, layer, cum, hist, max_q_len, kv_span, block_table=None, max_seq_len=None):
+    """cache rows hist[b] .. hist[b] + len_b - 1 of `layer` <- rmsnorm(kv_a[t, :512]) * gamma || rope(kv_a[t, 512:]), kv_a [tokens, 576]"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_kv_append_rows(_p(kv_a), _p(gamma), eps, _p(rope_tab), _p(cache), layer, hist.numel(), kv_a.shape[0], max_q_len,
+                                          kv_span, dense_len if block_table is None else max_seq_len, _p(cum), _p(hist), _p(block_table),
+                                          max_pages, num_pages, _st()), "mla_kv_append_rows")
+
+
+def mla_kv_up(cache, kv_b, kv_up, layer, cum, hist, max_q_len, block_table=None, max_seq_len=None):
+    """kv_up [batch, kv_span, heads, 256] <- kv_b[h] c_t (k_nope || v) for the cache rows t < hist[b] + len_b of every live sequence"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_kv_up(_p(cache), _p(kv_b), _p(kv_up), layer, kv_up.shape[0], kv_up.shape[2], max_q_len, kv_up.shape[1],
+                                 dense_len if block_table is None else max_seq_len, _p(cum), _p(hist), _p(block_table), max_pages, num_pages,
+                                 _st()), "mla_kv_up")
+    return kv_up
+
+
+def mla_prefill(q, kv_up, cache, rope_tab, layer, cum, hist, softmax_scale, out, max_q_len, block_table=None, max_seq_len=None):
+    """out [tokens, heads * 128] <- causal plain-softmax attention of q [tokens, heads, 192] (raw: rotated in the kernel) over kv_up
+    and the cached k_pe"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_prefill(_p(q), _p(kv_up), _p(cache), _p(rope_tab), _p(out), layer, kv_up.shape[0], q.shape[1], q.shape[0], max_q_len,
+                                   kv_up.shape[1], dense_len if block_table is None else max_seq_len, _p(cum), _p(hist), softmax_scale,
+                                   _p(block_table), max_pages, num_pages, _st()), "mla_prefill")
     return out
 
 

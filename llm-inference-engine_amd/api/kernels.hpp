@@ -608,3 +608,31 @@ inline void launchMlaOutProject(TensorWrapper<half> *o_lat, TensorWrapper<half> 
     LLM_CHECK_WITH_INFO(out->shape[0] == o_lat->shape[0] && out->shape[1] == o_lat->shape[1] * LLMIE_MLA_V_HEAD_DIM, "out should be [batch, head_num * 128]");
     LLMIE_CALL(llmie_mla_out_project(o_lat->data, kv_b->data, out->data, o_lat->shape[0], o_lat->shape[1], llmie_api::st()));
 }
+// MLA prefill, un-absorbed (llmie_mla_kv_append_rows / _kv_up / _prefill): cum [batch + 1] = exclusive prefix of the new-token counts,
+// hist [batch] = tokens already cached, max_q_len / kv_span = host bounds of the counts / of the contexts (history + new tokens);
+// kv_up [batch, kv_span, head_num, 256] is the caller's.  Per layer: append rows, up-project, attention (whose output is o_proj's input).
+inline void launchMlaKvAppendRows(TensorWrapper<half> *kv_a, TensorWrapper<half> *gamma, float eps, const void *rope_table, TensorWrapper<half> *cache,
+                                  int layer, TensorWrapper<int> *cum, TensorWrapper<int> *hist, int max_q_len, int kv_span,
+                                  TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(kv_a->shape[1] == LLMIE_MLA_ROW && cache->shape[3] == LLMIE_MLA_ROW, "kv_a should be [tokens, 576], the cache [.., 576]");
+    LLMIE_CALL(llmie_mla_kv_append_rows(kv_a->data, gamma->data, eps, rope_table, cache->data, layer, hist->shape[0], kv_a->shape[0], max_q_len, kv_span,
+                                        block_table ? max_seq_len : cache->shape[2], cum->data, hist->data, block_table ? block_table->data : nullptr,
+                                        block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaKvUp(TensorWrapper<half> *cache, TensorWrapper<half> *kv_b, int layer, TensorWrapper<int> *cum, TensorWrapper<int> *hist,
+                          int max_q_len, TensorWrapper<half> *kv_up, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(kv_up->shape[3] == 256 && kv_up->shape[0] == hist->shape[0], "kv_up should be [batch, kv_span, head_num, 256]");
+    LLMIE_CALL(llmie_mla_kv_up(cache->data, kv_b->data, kv_up->data, layer, kv_up->shape[0], kv_up->shape[2], max_q_len, kv_up->shape[1],
+                               block_table ? max_seq_len : cache->shape[2], cum->data, hist->data, block_table ? block_table->data : nullptr,
+                               block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaPrefillAttention(TensorWrapper<half> *q, TensorWrapper<half> *kv_up, TensorWrapper<half> *cache, const void *rope_table, int layer,
+                                      TensorWrapper<int> *cum, TensorWrapper<int> *hist, int max_q_len, float softmax_scale, TensorWrapper<half> *out,
+                                      TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(q->shape[2] == 192 && out->shape[0] == q->shape[0] && out->shape[1] == q->shape[1] * LLMIE_MLA_V_HEAD_DIM,
+                        "q should be [tokens, head_num, 192], out [tokens, head_num * 128]");
+    LLMIE_CALL(llmie_mla_prefill(q->data, kv_up->data, cache->data, rope_table, out->data, layer, kv_up->shape[0], q->shape[1], q->shape[0], max_q_len,
+                                 kv_up->shape[1], block_table ? max_seq_len : cache->shape[2], cum->data, hist->data, softmax_scale,
+                                 block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                 block_table ? cache->shape[1] : 0, llmie_api::st()));
+}

@@ -339,6 +339,24 @@ struct MlaDecodePlan {
     size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
+// ---- MLA prefill (mla_prefill.hip): bulk append, K/V up-projection, 192/128 flash attention.  One planner for the three entries ----
+struct MlaPrefillCall {
+    int batch;
+    int head_num;                      // 0: the call has no head axis (the append)
+    int total_tokens;                  // packed new tokens; 0: the call has no packed-token axis (the up-projection)
+    int max_q_len, kv_span;            // host bounds: >= every new-token count, >= every context (history + new tokens)
+    int max_seq_len;
+    bool paged;
+    int max_pages, num_pages;
+};
+struct MlaPrefillPlan {
+    int q_rows, key_tile;              // flash: query rows per workgroup, keys per staged tile
+    int flash_grid[3];                 // (query tiles, heads, batch)
+    int up_tokens, up_heads;           // up-projection: latent rows per staged tile, heads a workgroup walks
+    int up_grid[3];                    // (token tiles, head blocks, batch)
+    int append_grid;                   // one wave per packed token
+};
+int plan_mla_prefill(const char *who, const MlaPrefillCall &c, MlaPrefillPlan *p);   // sets the refusal's error text, returns its error code
 
 // prefill attention (RoPE + KV append + flash attention) on the packed QKV buffer; prefill.hip: one pure host planner decides the
 // launch, one launcher runs the plan

@@ -10,6 +10,13 @@ interleaved rounds, medians:
   bound     the arithmetic bound max(ctx * 1152 B * batch / HBM rate, FLOPs / MFMA rate) of the attention, FLOPs = 2 * batch * heads *
             ctx * (576 + 512); the rates are the datasheet peaks bench.py reports under `peaks` (--hbm-gbs, --mfma-tflops)
 
+With --prefill (lengths of one sequence) and --prefill-ragged (the lengths of one ragged batch) the prompt rows follow, no history:
+  append, up, flash   llmie_mla_kv_append_rows, llmie_mla_kv_up, llmie_mla_prefill, each alone, and `sum`, the three in a row (dense)
+  torch     a torch fp16 composition on the same tensors, per sequence: matmul for the up-projection, then causal
+            scaled_dot_product_attention with k = cat(k_nope, k_pe) (q_pe rotated ahead of the clock); null where torch refuses it
+  bound     max(bytes / HBM rate, FLOPs / MFMA rate): bytes = the latent rows read, kv_up written and read once, q and out; FLOPs =
+            2 * 512 * 256 per token and head for the projection + 2 * (192 + 128) per visible (query, key) pair and head
+
 Prints one JSON line (and writes it to --out): microseconds, and the ratios decode / bound and torch / decode.  Only time is measured."""
 import argparse
 import importlib.util
@@ -96,6 +103,68 @@ def bench(heads, batch, ctx, rounds, reps, hbm_gbs, mfma_tflops):
                 decode_over_bound=round(t["decode"][0] / bound, 2), torch_over_decode=round(t["torch"][0] / t["decode"][0], 2))
 
 
+def bench_prefill(heads, lens, rounds, reps, hbm_gbs, mfma_tflops):
+    dev, batch, total, span = "cuda", len(lens), sum(lens), -(-max(lens) // 128) * 128
+    cache = torch.zeros((1, batch, span, 576), dtype=F16, device=dev)
+    kv_b = (torch.randn((heads, 256, 512), device=dev) / 128 ** 0.5).to(F16)
+    kv_a = (0.5 * torch.randn((total, 576), device=dev)).to(F16)
+    q = torch.randn((total, heads, 192), device=dev).to(F16)
+    gamma = torch.ones(512, dtype=F16, device=dev)
+    tab = torch.from_numpy(llmie.rope_table(span, 64, 64, 10000.0)).to(dev)
+    starts = [sum(lens[:b]) for b in range(batch + 1)]
+    cum = torch.tensor(starts, dtype=torch.int32, device=dev)
+    hist = torch.zeros(batch, dtype=torch.int32, device=dev)
+    kv_up = torch.empty((batch, span, heads, 256), dtype=F16, device=dev)
+    out = torch.empty((total, heads * 128), dtype=F16, device=dev)
+    mq = max(lens)
+
+    def append():
+        llmie.mla_kv_append_rows(kv_a, gamma, 1e-6, tab, cache, 0, cum, hist, mq, span)
+
+    def up():
+        llmie.mla_kv_up(cache, kv_b, kv_up, 0, cum, hist, mq)
+
+    def flash():
+        llmie.mla_prefill(q, kv_up, cache, tab, 0, cum, hist, SCALE, out, mq)
+
+    def three():
+        append(), up(), flash()
+
+    # the composition's query: q_pe rotated ahead of the clock
+    pos = torch.cat([torch.arange(n, device=dev) for n in lens])
+    c, s_, x0, x1 = tab[pos, :, 0][:, None], tab[pos, :, 1][:, None], q[..., 128:160].float(), q[..., 160:].float()
+    q_rot = torch.cat([q[..., :128], (x0 * c - x1 * s_).to(F16), (x1 * c + x0 * s_).to(F16)], -1)
+    w = kv_b.view(heads * 256, 512)
+
+    def composed():
+        for b, n in enumerate(lens):
+            rows = cache[0, b, :n]
+            u = torch.matmul(rows[:, :512], w.t()).view(n, heads, 256)
+            k = torch.cat([u[..., :128], rows[:, None, 512:].expand(n, heads, 64)], -1)
+            t0 = starts[b]
+            torch.nn.functional.scaled_dot_product_attention(q_rot[t0:t0 + n].transpose(0, 1)[None], k.transpose(0, 1)[None],
+                                                             u[..., 128:].transpose(0, 1)[None], is_causal=True, scale=SCALE)
+
+    three()
+    arms = {"append": append, "up": up, "flash": flash, "sum": three}
+    try:
+        composed()
+        torch.cuda.synchronize()
+        arms["torch"] = composed
+    except Exception as e:   # (a shape torch's attention refuses: the row says so)
+        print("torch composition refused: %s" % str(e).splitlines()[0], file=sys.stderr)
+    t = interleaved(arms, rounds, reps)
+    pairs = sum(n * (n + 1) / 2 for n in lens)
+    flops = 2.0 * 512 * 256 * total * heads + 2.0 * (192 + 128) * pairs * heads
+    nbytes = total * 1152.0 + 2 * total * heads * 512.0 + total * heads * (384 + 256.0)
+    t_hbm, t_mfma = nbytes / (hbm_gbs * 1e9), flops / (mfma_tflops * 1e12)
+    bound = max(t_hbm, t_mfma)
+    return dict(heads=heads, lens=lens, plan=llmie.mla_prefill_plan(batch, heads, mq, span, span, total_tokens=total)[0],
+                us={k: round(v[0] * 1e6, 1) for k, v in t.items()}, spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
+                bound_us=round(bound * 1e6, 2), bound_by="hbm" if t_hbm >= t_mfma else "mfma", sum_over_bound=round(t["sum"][0] / bound, 2),
+                torch_over_sum=round(t["torch"][0] / t["sum"][0], 2) if "torch" in t else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", type=int, nargs="+", default=[16, 128])
@@ -105,11 +174,16 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
     ap.add_argument("--mfma-tflops", type=float, default=2500.0)
+    ap.add_argument("--prefill", type=int, nargs="*", default=[], help="prompt lengths of the batch-1 prefill rows, e.g. 512 2048 8192")
+    ap.add_argument("--prefill-ragged", type=int, nargs="*", default=[], help="the prompt lengths of one ragged prefill batch")
     ap.add_argument("--out")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "mlabench measures on the GPU: there is no CPU path"
     res = dict(tool="mlabench", device=torch.cuda.get_device_name(0), peaks=dict(hbm_GBs_datasheet=a.hbm_gbs, mfma_f16_TFLOPs_datasheet=a.mfma_tflops))
     res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
+    if a.prefill or a.prefill_ragged:
+        res["prefill_rows"] = [bench_prefill(h, lens, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads
+                               for lens in [[n] for n in a.prefill] + ([a.prefill_ragged] if a.prefill_ragged else [])]
     line = json.dumps(res)
     print(line)
     if a.out:
