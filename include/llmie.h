@@ -456,6 +456,39 @@ int llmie_mla_prefill(const void *q, const void *kv_up, const void *cache, const
 const char *llmie_mla_prefill_plan(int batch, int head_num, int total_tokens, int max_q_len, int kv_span, int max_seq_len, int paged,
                                    int max_pages, int num_pages, int *status);
 
+/* ABI 3 (an addition).  MLA verify attention: SEVERAL query rows per sequence -- the draft chain of a multi-token-prediction head or
+ * an n-gram drafter, or a draft tree -- attend over the latent cache in the absorbed form in one pass over the history.  Geometry,
+ * dtypes, cache (dense or paged), head_num range and softmax (PLAIN) are those of llmie_mla_decode.
+ *   q_lat [batch, rows, head_num, 576], o_lat [batch, rows, head_num, 512], 1 <= rows <= LLMIE_SPEC_TREE_MAX_NODES (64).
+ *   hist_dev[b]   device int32: tokens in the cache in front of this step's nodes.
+ *   count_dev[b]  device int32 in [1, rows]: the nodes of sequence b; NULL: rows for every sequence.  ctx_b = hist[b] + count[b].
+ *   The nodes' rows are ALREADY in the cache at slots hist[b] + i -- the caller appended them; the attention only reads the cache.
+ *   A sequence with hist[b] < 0, count[b] outside [1, rows] or ctx_b > (max_ctx ? max_ctx : max_seq_len) is left wholly untouched;
+ *   rows i >= count[b] of o_lat are not written.
+ *   Mask: the convention of llmie_decoder_set_tree.  Row i sees key t iff t < hist[b], or t = hist[b] + j with bit j of
+ *   (anc[b * rows + i] & ((2 << i) - 1)) | (1 << i) set; anc_dev = NULL is the chain (2 << i) - 1.  The arrays llmie_spec_tree_prepare
+ *   leaves can be passed with rows = stride.
+ *   Arithmetic: per row that of llmie_mla_decode -- fp32 accumulation, one rounding at the end, splits of a fixed length that depend on
+ *   ctx_b alone, no atomics.  A row's bits do not depend on the batch slot, the grid, max_ctx or the rows beside it.  workspace: at
+ *   least llmie_mla_verify_workspace_bytes(batch, rows, head_num, max_ctx ? max_ctx : max_seq_len) bytes, 16-byte aligned (0 bytes: one
+ *   split, NULL allowed); too small: LLMIE_ERR_WORKSPACE.
+ * The entries around it need no new kernel: llmie_mla_q_absorb serves batch * rows query rows when it is given a per-ROW length array
+ * pos + 1 (pos = hist + i for a chain, hist + depth for a tree); llmie_mla_out_project takes batch * rows rows as it is;
+ * llmie_mla_kv_append_rows writes a chain's rows.  (A tree's append -- rotate at hist + depth, store at hist + index -- and the
+ * latent-cache counterpart of llmie_kv_tree_commit are not part of the library yet.)
+ * llmie_mla_verify_plan: host only.  The launch llmie_mla_verify makes (the entry calls the same planner), as one line:
+ *   "mla_verify f16 nh128 rows8 chain cols 16x4 tile32 chunk256 grid 8x8x4 merge 128x16/128" -- the mask kind, MFMA columns per
+ *   workgroup (heads x query rows), keys per staged tile, tokens per split, grid (splits, head blocks, batch x row blocks), the merge
+ *   launch grid/block or "none" with one split.  tree: the call passes anc_dev.  workspace_bytes < 0: no workspace.  NULL for a call
+ *   the entry refuses (*status = its code, llmie_last_error() says why). */
+size_t llmie_mla_verify_workspace_bytes(int batch, int rows, int head_num, int max_seq_len);
+int llmie_mla_verify(const void *q_lat, const void *cache, void *o_lat, int layer, int batch, int rows, int head_num, int max_seq_len,
+                     int max_ctx, const int32_t *hist_dev, const int32_t *count_dev /* nullable */, const uint64_t *anc_dev /* nullable: chain */,
+                     float softmax_scale, void *workspace, size_t workspace_bytes, const int32_t *block_table /* nullable: dense */,
+                     int max_pages, int num_pages, llmie_stream stream);
+const char *llmie_mla_verify_plan(int batch, int rows, int head_num, int max_seq_len, int max_ctx, int tree, int paged, int max_pages,
+                                  int num_pages, long long workspace_bytes, int *status);
+
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
  * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the

@@ -183,6 +183,9 @@ _SIGS = {
     "llmie_mla_kv_up": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "llmie_mla_prefill": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _i, _vp],
     "llmie_mla_prefill_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "llmie_mla_verify_workspace_bytes": [_i, _i, _i, _i],
+    "llmie_mla_verify": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _sz, _vp, _i, _i, _vp],
+    "llmie_mla_verify_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
     "llmie_target_arch": [],
@@ -212,6 +215,8 @@ _RESTYPES = {
     "llmie_mla_decode_workspace_bytes": _sz,
     "llmie_mla_decode_plan": C.c_char_p,
     "llmie_mla_prefill_plan": C.c_char_p,
+    "llmie_mla_verify_workspace_bytes": _sz,
+    "llmie_mla_verify_plan": C.c_char_p,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_moe_ffn_plan_ex": C.c_char_p,
@@ -541,6 +546,38 @@ def mla_prefill(q, kv_up, cache, rope_tab, layer, cum, hist, softmax_scale, out,
                                    kv_up.shape[1], dense_len if block_table is None else max_seq_len, _p(cum), _p(hist), softmax_scale,
                                    _p(block_table), max_pages, num_pages, _st()), "mla_prefill")
     return out
+
+
+# MLA verify (include/llmie.h llmie_mla_verify): `rows` query rows per sequence -- a draft chain or a draft tree -- on the latent cache
+def mla_verify_plan(batch, rows, head_num, max_seq_len, max_ctx=0, tree=False, paged=False, max_pages=0, num_pages=0, workspace_bytes="exact"):
+    """(plan text or None, status) of llmie_mla_verify's launch: e.g. "mla_verify f16 nh128 rows8 chain cols 16x4 tile32 chunk256 grid
+    8x8x4 merge 128x16/128" (mask kind, MFMA columns per workgroup = heads x query rows, key tile, tokens per split, grid, merge launch
+    or "none"); None where the entry refuses the call.  workspace_bytes: a size, None (no workspace) or "exact".  No device needed."""
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_mla_verify_workspace_bytes(batch, rows, head_num, max_ctx if max_ctx > 0 else max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_mla_verify_plan(batch, rows, head_num, max_seq_len, max_ctx, int(tree), int(paged), max_pages, num_pages,
+                                    -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_verify_workspace(batch, rows, head_num, max_seq_len, device="cuda"):
+    """uint8 scratch for mla_verify's split partials (one element at least, so that it is a tensor)"""
+    import torch
+    return torch.empty(max(lib().llmie_mla_verify_workspace_bytes(batch, rows, head_num, max_seq_len), 16), dtype=torch.uint8, device=device)
+
+
+def mla_verify(q_lat, cache, layer, hist, softmax_scale, o_lat, count=None, anc=None, workspace=None, block_table=None, max_seq_len=None,
+               max_ctx=0):
+    """o_lat [batch, rows, heads, 512] <- plain softmax attention of q_lat [batch, rows, heads, 576]: row i of sequence b sees the cache
+    rows t < hist[b] and the nodes hist[b] + j its mask names (anc [batch, rows] uint64 / int64 bits as llmie_spec_tree_prepare leaves
+    them; None: the chain j <= i); count [batch] int32 nodes per sequence (None: rows)"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_verify(_p(q_lat), _p(cache), _p(o_lat), layer, q_lat.shape[0], q_lat.shape[1], q_lat.shape[2],
+                                  dense_len if block_table is None else max_seq_len, max_ctx, _p(hist), _p(count), _p(anc), softmax_scale,
+                                  _p(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                  _p(block_table), max_pages, num_pages, _st()), "mla_verify")
+    return o_lat
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):

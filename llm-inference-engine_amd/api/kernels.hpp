@@ -608,6 +608,22 @@ inline void launchMlaOutProject(TensorWrapper<half> *o_lat, TensorWrapper<half> 
     LLM_CHECK_WITH_INFO(out->shape[0] == o_lat->shape[0] && out->shape[1] == o_lat->shape[1] * LLMIE_MLA_V_HEAD_DIM, "out should be [batch, head_num * 128]");
     LLMIE_CALL(llmie_mla_out_project(o_lat->data, kv_b->data, out->data, o_lat->shape[0], o_lat->shape[1], llmie_api::st()));
 }
+// MLA verify (llmie_mla_verify): q_lat [batch, rows, head_num, 576] -> o_lat [batch, rows, head_num, 512]; hist [batch] = tokens cached in
+// front of the nodes, count [batch] (nullable: rows each) = nodes per sequence, anc (nullable: the chain) = device uint64 [batch, rows]
+// ancestor masks as llmie_spec_tree_prepare leaves them.  The nodes' rows are in the cache already (launchMlaKvAppendRows for a chain);
+// launchMlaQAbsorb / launchMlaOutProject serve the batch * rows rows with a per-row length array.
+inline void launchMlaVerifyAttention(TensorWrapper<half> *q_lat, TensorWrapper<half> *cache, int layer, TensorWrapper<int> *hist,
+                                     TensorWrapper<int> *count, const uint64_t *anc, float softmax_scale, TensorWrapper<half> *o_lat,
+                                     TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0, int max_ctx = 0) {
+    LLM_CHECK_WITH_INFO(q_lat->shape.size() == 4 && q_lat->shape[3] == LLMIE_MLA_ROW, "q_lat should be [batch, rows, head_num, 576]");
+    const int batch = q_lat->shape[0], rows = q_lat->shape[1], head_num = q_lat->shape[2];
+    if (!block_table) max_seq_len = cache->shape[2];
+    const size_t ws = llmie_mla_verify_workspace_bytes(batch, rows, head_num, max_ctx > 0 ? max_ctx : max_seq_len);
+    LLMIE_CALL(llmie_mla_verify(q_lat->data, cache->data, o_lat->data, layer, batch, rows, head_num, max_seq_len, max_ctx, hist->data,
+                                count ? count->data : nullptr, anc, softmax_scale, ws ? llmie_api::scratch(ws) : nullptr, ws,
+                                block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
 // MLA prefill, un-absorbed (llmie_mla_kv_append_rows / _kv_up / _prefill): cum [batch + 1] = exclusive prefix of the new-token counts,
 // hist [batch] = tokens already cached, max_q_len / kv_span = host bounds of the counts / of the contexts (history + new tokens);
 // kv_up [batch, kv_span, head_num, 256] is the caller's.  Per layer: append rows, up-project, attention (whose output is o_proj's input).

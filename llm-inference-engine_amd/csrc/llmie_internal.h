@@ -339,6 +339,26 @@ struct MlaDecodePlan {
     size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
+// ---- MLA verify attention (mla_verify.hip): several query rows per sequence on the latent cache; the pattern of plan_mla_decode ----
+struct MlaVerifyCall {
+    int batch, rows, head_num, max_seq_len;   // rows: query-row slots per sequence (a chain's length, a tree's stride)
+    int max_ctx;                       // host bound of hist + count, 0: only the device knows them
+    bool tree;                         // an ancestor-mask array is given (the launch is the same: the plan text says it)
+    bool paged;
+    int max_pages, num_pages;
+    bool workspace;
+    size_t workspace_bytes;
+};
+struct MlaVerifyPlan {
+    int heads, rows, tile, chunk;      // MFMA columns per workgroup = heads x rows, keys per staged tile, tokens per split
+    int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
+    int row_blocks;                    // ceil(call rows / rows)
+    int grid[3];                       // (splits, head blocks, batch x row blocks)
+    bool merge;                        // more than one split: mla_verify_merge_kernel follows
+    int merge_grid[2], merge_block;
+    size_t workspace_bytes;            // the split partials (0 with one split)
+};
+int plan_mla_verify(const char *who, const MlaVerifyCall &c, MlaVerifyPlan *p);   // sets the refusal's error text, returns its error code
 // ---- MLA prefill (mla_prefill.hip): bulk append, K/V up-projection, 192/128 flash attention.  One planner for the three entries ----
 struct MlaPrefillCall {
     int batch;

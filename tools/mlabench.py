@@ -17,6 +17,12 @@ With --prefill (lengths of one sequence) and --prefill-ragged (the lengths of on
   bound     max(bytes / HBM rate, FLOPs / MFMA rate): bytes = the latent rows read, kv_up written and read once, q and out; FLOPs =
             2 * 512 * 256 per token and head for the projection + 2 * (192 + 128) per visible (query, key) pair and head
 
+With --verify ROWS... (e.g. 2 4 8 16) the speculative step follows, per heads x ctx x batch and row count, one interleaved run per cell:
+  verify    llmie_mla_verify: `rows` chain rows per sequence, the last of them at context ctx (hist = ctx - rows)
+  decode    ONE llmie_mla_decode call at context ctx; rows x decode is the only route to a chain without the verify kernel
+  prefill   (--verify-prefill, the first cell of every row count) llmie_mla_kv_up + llmie_mla_prefill with hist = ctx - rows: the
+            un-absorbed route, which projects the whole history up on every step
+
 Prints one JSON line (and writes it to --out): microseconds, and the ratios decode / bound and torch / decode.  Only time is measured."""
 import argparse
 import importlib.util
@@ -165,6 +171,37 @@ def bench_prefill(heads, lens, rounds, reps, hbm_gbs, mfma_tflops):
                 torch_over_sum=round(t["torch"][0] / t["sum"][0], 2) if "torch" in t else None)
 
 
+def bench_verify(heads, batch, ctx, rows, rounds, reps, with_prefill):
+    dev = "cuda"
+    cache = torch.empty((1, batch, ctx, 576), dtype=F16, device=dev).normal_(0, 0.5)
+    q_lat = torch.randn((batch, rows, heads, 576), device=dev).to(F16)
+    o_lat = torch.empty((batch, rows, heads, 512), dtype=F16, device=dev)
+    hist = torch.full((batch,), ctx - rows, dtype=torch.int32, device=dev)
+    lengths = torch.full((batch,), ctx, dtype=torch.int32, device=dev)
+    ws_v, ws_d = llmie.mla_verify_workspace(batch, rows, heads, ctx), llmie.mla_workspace(batch, heads, ctx)
+    q1, o1 = q_lat[:, 0].contiguous(), torch.empty((batch, heads, 512), dtype=F16, device=dev)
+    arms = {"verify": lambda: llmie.mla_verify(q_lat, cache, 0, hist, SCALE, o_lat, workspace=ws_v),
+            "decode": lambda: llmie.mla_decode(q1, cache, 0, lengths, SCALE, o1, ws_d)}
+    if with_prefill:
+        kv_b = (torch.randn((heads, 256, 512), device=dev) / 128 ** 0.5).to(F16)
+        tab = torch.from_numpy(llmie.rope_table(ctx, 64, 64, 10000.0)).to(dev)
+        q = torch.randn((batch * rows, heads, 192), device=dev).to(F16)
+        cum = torch.arange(0, (batch + 1) * rows, rows, dtype=torch.int32, device=dev)
+        kv_up = torch.empty((batch, ctx, heads, 256), dtype=F16, device=dev)
+        out = torch.empty((batch * rows, heads * 128), dtype=F16, device=dev)
+
+        def prefill():
+            llmie.mla_kv_up(cache, kv_b, kv_up, 0, cum, hist, rows)
+            llmie.mla_prefill(q, kv_up, cache, tab, 0, cum, hist, SCALE, out, rows)
+
+        arms["prefill"] = prefill
+    t = interleaved(arms, rounds, reps)
+    us = {k: round(v[0] * 1e6, 1) for k, v in t.items()}
+    return dict(heads=heads, batch=batch, ctx=ctx, rows=rows, plan=llmie.mla_verify_plan(batch, rows, heads, ctx)[0], us=us,
+                spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
+                rows_x_decode_us=round(rows * t["decode"][0] * 1e6, 1), rows_decode_over_verify=round(rows * t["decode"][0] / t["verify"][0], 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", type=int, nargs="+", default=[16, 128])
@@ -176,11 +213,19 @@ def main():
     ap.add_argument("--mfma-tflops", type=float, default=2500.0)
     ap.add_argument("--prefill", type=int, nargs="*", default=[], help="prompt lengths of the batch-1 prefill rows, e.g. 512 2048 8192")
     ap.add_argument("--prefill-ragged", type=int, nargs="*", default=[], help="the prompt lengths of one ragged prefill batch")
+    ap.add_argument("--verify", type=int, nargs="*", default=[], help="query rows per sequence of the speculative step, e.g. 2 4 8 16")
+    ap.add_argument("--verify-prefill", action="store_true", help="add the kv_up + mla_prefill route to the first cell of every row count")
+    ap.add_argument("--verify-only", action="store_true", help="skip the decode / chain / torch rows")
     ap.add_argument("--out")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "mlabench measures on the GPU: there is no CPU path"
     res = dict(tool="mlabench", device=torch.cuda.get_device_name(0), peaks=dict(hbm_GBs_datasheet=a.hbm_gbs, mfma_f16_TFLOPs_datasheet=a.mfma_tflops))
-    res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
+    if not a.verify_only:
+        res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
+    if a.verify:
+        cells = [(h, b, c) for h in a.heads for c in a.ctx for b in a.batches]
+        res["verify_rows"] = [bench_verify(h, b, c, r, a.rounds, a.reps, a.verify_prefill and (h, b, c) == cells[0]) for r in a.verify
+                              for h, b, c in cells]
     if a.prefill or a.prefill_ragged:
         res["prefill_rows"] = [bench_prefill(h, lens, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads
                                for lens in [[n] for n in a.prefill] + ([a.prefill_ragged] if a.prefill_ragged else [])]
