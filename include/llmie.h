@@ -405,6 +405,7 @@ int llmie_rope_table_fill(float *cos_sin_out, int max_pos, int head_size, int ro
 #define LLMIE_MLA_QK_NOPE_HEAD_DIM 128
 #define LLMIE_MLA_V_HEAD_DIM 128
 #define LLMIE_MLA_ROW 576          /* kv_lora_rank + qk_rope_head_dim: halves per cached token */
+#define LLMIE_MLA_ROW_E4M3_BYTES 640   /* the e4m3 cache (below): 512 e4m3 latent bytes + 64 fp16 k_pe halves per cached token */
 #define LLMIE_MLA_PAGE_TOKENS 128
 size_t llmie_mla_decode_workspace_bytes(int batch, int head_num, int max_seq_len);
 int llmie_mla_kv_append(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, int layer, int batch,
@@ -488,6 +489,47 @@ int llmie_mla_verify(const void *q_lat, const void *cache, void *o_lat, int laye
                      int max_pages, int num_pages, llmie_stream stream);
 const char *llmie_mla_verify_plan(int batch, int rows, int head_num, int max_seq_len, int max_ctx, int tree, int paged, int max_pages,
                                   int num_pages, long long workspace_bytes, int *status);
+
+/* ABI 3 (an addition).  The MLA latent cache in e4m3: a token costs LLMIE_MLA_ROW_E4M3_BYTES = 640 bytes instead of 1152.
+ *   row        bytes 0..511: latent dim j as OCP e4m3fn e4m3(c_j / c_scale), round-to-nearest-even, saturated to +-448 (the append
+ *              never writes the NaN codes 0x7f / 0xff; what a reader makes of them is undefined).  c_j is the fp16 value
+ *              llmie_mla_kv_append stores -- same RMSNorm arithmetic and summation order, rounded to fp16 first --, so quantising an
+ *              fp16 row gives the same byte.  Bytes 512..639: the 64 rotated k_pe halves in fp16, the bits the fp16 append writes.
+ *   c_scale    one positive finite fp32 per cache, the caller's (as k_scale / v_scale of the MHA path): value = code * c_scale.
+ *              Anything else: LLMIE_ERR_INVALID_ARG.
+ *   cache      bytes: dense [layers, batch, max_seq_len, 640], or paged [layers, num_pages, 128, 640] through block_table as for
+ *              the fp16 cache; 16-byte aligned.  Geometry, head_num range, ctx_len_dev, rope_table, cum_dev / hist_dev: as above.
+ * llmie_mla_kv_append_e4m3 / llmie_mla_kv_append_rows_e4m3: llmie_mla_kv_append / llmie_mla_kv_append_rows onto such a cache, with their
+ *   semantics and refusals; one wave per token, a bulk row has the bytes of the single-token append.
+ * llmie_mla_decode_e4m3: llmie_mla_decode over such a cache; q_lat, o_lat, the workspace (llmie_mla_decode_workspace_bytes), the
+ *   splits and the PLAIN softmax are its.  Arithmetic: every code becomes the fp16 of its exact value (no rounding, subnormal codes
+ *   included) and feeds the fp16 MFMAs; c_scale is applied in fp32 and never to an fp16 operand:
+ *     logit_t = softmax_scale * (c_scale * sum_{j < 512} q_j code_tj + sum_{j >= 512} q_j k_pe_tj)   (the 512 latent terms are summed
+ *               as dims 0..287 and 288..511, each partial times c_scale, the k_pe partial joins the second)
+ *     o_lat   = fp16((sum_t p_t code_t) * c_scale / sum_t p_t), the factor c_scale once per element, in front of the split partial
+ *               store (the merge is llmie_mla_decode's) or of the fp16 store.
+ *   The chunking depends on ctx_len[b] alone: a batch row has the bits of its batch-1 call, dense equals paged bit for bit, no atomics.
+ * llmie_mla_decode_e4m3_plan: host only, as llmie_mla_decode_plan: "mla e4m3 nh128 hb16 tile32 chunk256 row640 grid 8x8x2 merge
+ *   128x2/128" -- row: bytes per cached token.
+ * llmie_mla_cache_dequant_e4m3: the bridge of the prompt path.  Rows t < ctx_len[b] of `layer` of an e4m3 cache -> the same rows of an
+ *   fp16 latent cache of the same geometry (same dense shape, or same block_table and num_pages): latent = fp16(fp32(code) * c_scale)
+ *   (one fp32 product, one rounding), k_pe copied.  Rows at or past ctx_len[b], and sequences with ctx_len[b] outside
+ *   [1, max_ctx ? max_ctx : max_seq_len], are untouched.  llmie_mla_kv_up / _prefill / _verify then run over that cache. */
+int llmie_mla_kv_append_e4m3(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, float c_scale, int layer,
+                             int batch, int max_seq_len, const int32_t *ctx_len_dev, const int32_t *block_table /* nullable: dense */,
+                             int max_pages, int num_pages, llmie_stream stream);
+int llmie_mla_kv_append_rows_e4m3(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, float c_scale, int layer,
+                                  int batch, int total_tokens, int max_q_len, int kv_span, int max_seq_len, const int32_t *cum_dev,
+                                  const int32_t *hist_dev, const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages,
+                                  llmie_stream stream);
+int llmie_mla_decode_e4m3(const void *q_lat, const void *cache, void *o_lat, int layer, int batch, int head_num, int max_seq_len, int max_ctx,
+                          const int32_t *ctx_len_dev, float softmax_scale, void *workspace, size_t workspace_bytes,
+                          const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages, float c_scale, llmie_stream stream);
+const char *llmie_mla_decode_e4m3_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
+                                       long long workspace_bytes, int *status);
+int llmie_mla_cache_dequant_e4m3(const void *cache_e4m3, void *cache_f16, float c_scale, int layer, int batch, int max_seq_len, int max_ctx,
+                                 const int32_t *ctx_len_dev, const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages,
+                                 llmie_stream stream);
 
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need

@@ -186,6 +186,11 @@ _SIGS = {
     "llmie_mla_verify_workspace_bytes": [_i, _i, _i, _i],
     "llmie_mla_verify": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _sz, _vp, _i, _i, _vp],
     "llmie_mla_verify_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
+    "llmie_mla_kv_append_e4m3": [_vp, _vp, _f, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_kv_append_rows_e4m3": [_vp, _vp, _f, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_decode_e4m3": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp, _i, _i, _f, _vp],
+    "llmie_mla_decode_e4m3_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
+    "llmie_mla_cache_dequant_e4m3": [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
     "llmie_target_arch": [],
@@ -217,6 +222,7 @@ _RESTYPES = {
     "llmie_mla_prefill_plan": C.c_char_p,
     "llmie_mla_verify_workspace_bytes": _sz,
     "llmie_mla_verify_plan": C.c_char_p,
+    "llmie_mla_decode_e4m3_plan": C.c_char_p,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_moe_ffn_plan_ex": C.c_char_p,
@@ -578,6 +584,72 @@ def mla_verify(q_lat, cache, layer, hist, softmax_scale, o_lat, count=None, anc=
                                   _p(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0,
                                   _p(block_table), max_pages, num_pages, _st()), "mla_verify")
     return o_lat
+
+
+# MLA on the e4m3 latent cache (include/llmie.h llmie_mla_*_e4m3): uint8 caches of 640 bytes per token -- 512 e4m3 codes of c / c_scale,
+# then the 64 k_pe halves --, one positive finite c_scale per cache
+MLA_ROW_E4M3 = 640
+
+
+def _mla_cache_e4m3(cache, block_table):
+    """(max_seq_len or None, max_pages, num_pages) of a dense [L, batch, S, 640] / paged [L, pages, 128, 640] uint8 latent cache"""
+    import torch
+    assert cache.dtype == torch.uint8 and cache.dim() == 4 and cache.shape[3] == MLA_ROW_E4M3, \
+        "e4m3 latent cache: uint8 [layers, batch, max_seq_len, 640] or [layers, pages, 128, 640]"
+    if block_table is None:
+        return cache.shape[2], 0, 0
+    assert cache.shape[2] == MLA_PAGE, "paged latent cache: pages of 128 tokens"
+    return None, block_table.shape[1], cache.shape[1]
+
+
+def mla_decode_e4m3_plan(batch, head_num, max_seq_len, max_ctx=0, paged=False, max_pages=0, num_pages=0, workspace_bytes="exact"):
+    """mla_decode_plan for llmie_mla_decode_e4m3: e.g. "mla e4m3 nh128 hb16 tile32 chunk256 row640 grid 8x8x2 merge 128x2/128" (row:
+    bytes per cached token).  No device needed."""
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_mla_decode_workspace_bytes(batch, head_num, max_ctx if max_ctx > 0 else max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_mla_decode_e4m3_plan(batch, head_num, max_seq_len, max_ctx, int(paged), max_pages, num_pages,
+                                         -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_kv_append_e4m3(kv_a, gamma, eps, rope_tab, cache, c_scale, layer, ctx_len, block_table=None, max_seq_len=None):
+    """mla_kv_append onto an e4m3 cache: row ctx_len[b] - 1 <- e4m3(fp16 row / c_scale) || rope(kv_a[b, 512:]) in fp16"""
+    dense_len, max_pages, num_pages = _mla_cache_e4m3(cache, block_table)
+    _check(lib().llmie_mla_kv_append_e4m3(_p(kv_a), _p(gamma), eps, _p(rope_tab), _p(cache), c_scale, layer, kv_a.shape[0],
+                                          dense_len if block_table is None else max_seq_len, _p(ctx_len), _p(block_table), max_pages,
+                                          num_pages, _st()), "mla_kv_append_e4m3")
+
+
+def mla_kv_append_rows_e4m3(kv_a, gamma, eps, rope_tab, cache, c_scale, layer, cum, hist, max_q_len, kv_span, block_table=None,
+                            max_seq_len=None):
+    """mla_kv_append_rows onto an e4m3 cache: every row has the bytes of its single-token mla_kv_append_e4m3"""
+    dense_len, max_pages, num_pages = _mla_cache_e4m3(cache, block_table)
+    _check(lib().llmie_mla_kv_append_rows_e4m3(_p(kv_a), _p(gamma), eps, _p(rope_tab), _p(cache), c_scale, layer, hist.numel(), kv_a.shape[0],
+                                               max_q_len, kv_span, dense_len if block_table is None else max_seq_len, _p(cum), _p(hist),
+                                               _p(block_table), max_pages, num_pages, _st()), "mla_kv_append_rows_e4m3")
+
+
+def mla_decode_e4m3(q_lat, cache, c_scale, layer, ctx_len, softmax_scale, o_lat, workspace=None, block_table=None, max_seq_len=None,
+                    max_ctx=0):
+    """mla_decode over an e4m3 cache (workspace: mla_workspace): latent = code * c_scale, applied in fp32"""
+    dense_len, max_pages, num_pages = _mla_cache_e4m3(cache, block_table)
+    _check(lib().llmie_mla_decode_e4m3(_p(q_lat), _p(cache), _p(o_lat), layer, q_lat.shape[0], q_lat.shape[1],
+                                       dense_len if block_table is None else max_seq_len, max_ctx, _p(ctx_len), softmax_scale, _p(workspace),
+                                       workspace.numel() * workspace.element_size() if workspace is not None else 0, _p(block_table),
+                                       max_pages, num_pages, c_scale, _st()), "mla_decode_e4m3")
+    return o_lat
+
+
+def mla_cache_dequant_e4m3(cache_e4m3, cache_f16, c_scale, layer, ctx_len, block_table=None, max_seq_len=None, max_ctx=0):
+    """rows t < ctx_len[b] of `layer`: e4m3 cache -> the fp16 latent cache of the same geometry (mla_kv_up / mla_prefill / mla_verify
+    then run over it): latent = fp16(code * c_scale), k_pe copied"""
+    dense_len, max_pages, num_pages = _mla_cache_e4m3(cache_e4m3, block_table)
+    assert _mla_cache(cache_f16, block_table) == (dense_len, max_pages, num_pages) and cache_f16.shape[:2] == cache_e4m3.shape[:2]
+    _check(lib().llmie_mla_cache_dequant_e4m3(_p(cache_e4m3), _p(cache_f16), c_scale, layer, ctx_len.numel(),
+                                              dense_len if block_table is None else max_seq_len, max_ctx, _p(ctx_len), _p(block_table),
+                                              max_pages, num_pages, _st()), "mla_cache_dequant_e4m3")
+    return cache_f16
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):

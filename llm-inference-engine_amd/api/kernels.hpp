@@ -652,3 +652,43 @@ inline void launchMlaPrefillAttention(TensorWrapper<half> *q, TensorWrapper<half
                                  block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
                                  block_table ? cache->shape[1] : 0, llmie_api::st()));
 }
+// MLA on the e4m3 latent cache (llmie_mla_*_e4m3): the cache is bytes, [L, batch, max_seq_len, 640] or the pool [L, num_pages, 128, 640]
+// -- 512 e4m3 codes of c / c_scale, then the 64 k_pe halves --, c_scale one positive finite scale per cache.  Append and attention as
+// their fp16 launchers; launchMlaCacheDequantE4m3 fills an fp16 cache of the same geometry for launchMlaKvUp / Prefill / Verify.
+inline void launchMlaKvAppendE4m3(TensorWrapper<half> *kv_a, TensorWrapper<half> *gamma, float eps, const void *rope_table,
+                                  TensorWrapper<int8_t> *cache, float c_scale, int layer, TensorWrapper<int> *ctx_len,
+                                  TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(kv_a->shape[1] == LLMIE_MLA_ROW && cache->shape[3] == LLMIE_MLA_ROW_E4M3_BYTES, "kv_a should be [batch, 576], the cache [.., 640]");
+    LLMIE_CALL(llmie_mla_kv_append_e4m3(kv_a->data, gamma->data, eps, rope_table, cache->data, c_scale, layer, kv_a->shape[0],
+                                        block_table ? max_seq_len : cache->shape[2], ctx_len->data, block_table ? block_table->data : nullptr,
+                                        block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaKvAppendRowsE4m3(TensorWrapper<half> *kv_a, TensorWrapper<half> *gamma, float eps, const void *rope_table,
+                                      TensorWrapper<int8_t> *cache, float c_scale, int layer, TensorWrapper<int> *cum, TensorWrapper<int> *hist,
+                                      int max_q_len, int kv_span, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    LLM_CHECK_WITH_INFO(kv_a->shape[1] == LLMIE_MLA_ROW && cache->shape[3] == LLMIE_MLA_ROW_E4M3_BYTES, "kv_a should be [tokens, 576], the cache [.., 640]");
+    LLMIE_CALL(llmie_mla_kv_append_rows_e4m3(kv_a->data, gamma->data, eps, rope_table, cache->data, c_scale, layer, hist->shape[0], kv_a->shape[0],
+                                             max_q_len, kv_span, block_table ? max_seq_len : cache->shape[2], cum->data, hist->data,
+                                             block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                             block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
+inline void launchMlaDecodeAttentionE4m3(TensorWrapper<half> *q_lat, TensorWrapper<int8_t> *cache, float c_scale, int layer, TensorWrapper<int> *ctx_len,
+                                         float softmax_scale, TensorWrapper<half> *o_lat, TensorWrapper<int> *block_table = nullptr,
+                                         int max_seq_len = 0, int max_ctx = 0) {
+    const int batch = q_lat->shape[0], head_num = q_lat->shape[1];
+    if (!block_table) max_seq_len = cache->shape[2];
+    const size_t ws = llmie_mla_decode_workspace_bytes(batch, head_num, max_ctx > 0 ? max_ctx : max_seq_len);
+    LLMIE_CALL(llmie_mla_decode_e4m3(q_lat->data, cache->data, o_lat->data, layer, batch, head_num, max_seq_len, max_ctx, ctx_len->data, softmax_scale,
+                                     ws ? llmie_api::scratch(ws) : nullptr, ws, block_table ? block_table->data : nullptr,
+                                     block_table ? block_table->shape[1] : 0, block_table ? cache->shape[1] : 0, c_scale, llmie_api::st()));
+}
+inline void launchMlaCacheDequantE4m3(TensorWrapper<int8_t> *cache_e4m3, TensorWrapper<half> *cache_f16, float c_scale, int layer,
+                                      TensorWrapper<int> *ctx_len, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0, int max_ctx = 0) {
+    LLM_CHECK_WITH_INFO(cache_e4m3->shape[3] == LLMIE_MLA_ROW_E4M3_BYTES && cache_f16->shape[3] == LLMIE_MLA_ROW &&
+                            cache_e4m3->shape[1] == cache_f16->shape[1] && cache_e4m3->shape[2] == cache_f16->shape[2],
+                        "the caches should be [.., 640] bytes and [.., 576] halves of one geometry");
+    LLMIE_CALL(llmie_mla_cache_dequant_e4m3(cache_e4m3->data, cache_f16->data, c_scale, layer, ctx_len->shape[0],
+                                            block_table ? max_seq_len : cache_e4m3->shape[2], max_ctx, ctx_len->data,
+                                            block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                            block_table ? cache_e4m3->shape[1] : 0, llmie_api::st()));
+}

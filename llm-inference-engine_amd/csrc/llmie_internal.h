@@ -329,9 +329,11 @@ struct MlaDecodeCall {
     int max_pages, num_pages;
     bool workspace;
     size_t workspace_bytes;
+    bool e4m3;                         // the cache rows are LLMIE_MLA_ROW_E4M3_BYTES bytes (mla_e4m3.hip); the split is the same
 };
 struct MlaDecodePlan {
     int heads, tile, chunk;            // query heads per workgroup, keys per staged tile, tokens per split
+    int row_bytes;                     // of one cached token
     int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
     int grid[3];                       // (splits, head blocks, batch)
     bool merge;                        // more than one split: mla_merge_kernel follows
@@ -339,6 +341,9 @@ struct MlaDecodePlan {
     size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
+// the merge launch of a plan with p.merge: both decode kernels leave their (m, l, o[512]) fp32 partials in the one format it reads
+void mla_merge_launch(const MlaDecodePlan &p, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *ctx_len, int head_num,
+                      hipStream_t st);
 // ---- MLA verify attention (mla_verify.hip): several query rows per sequence on the latent cache; the pattern of plan_mla_decode ----
 struct MlaVerifyCall {
     int batch, rows, head_num, max_seq_len;   // rows: query-row slots per sequence (a chain's length, a tree's stride)

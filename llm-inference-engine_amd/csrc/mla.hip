@@ -32,7 +32,7 @@ namespace llmie {
 
 namespace {
 
-constexpr int kMlaHeads = 16, kMlaTile = 32, kMlaChunk = 256, kMlaStride = kRow + 16, kMlaMergeBlock = 128;
+constexpr int kMlaStride = kRow + 16;
 static_assert(kPage % kMlaTile == 0 && kMlaChunk % kMlaTile == 0, "a tile never crosses a page or a chunk");
 static_assert((kMlaStride * 2) % 64 == 32, "row stride = an odd multiple of 32 bytes: conflict-free transposed reads");
 
@@ -349,6 +349,7 @@ int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
     LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
                   who, c.max_ctx, c.max_seq_len);
     p->heads = kMlaHeads, p->tile = kMlaTile, p->chunk = kMlaChunk;
+    p->row_bytes = c.e4m3 ? kRowE4 : kRow * static_cast<int>(sizeof(half_t));
     p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
     p->grid[0] = (p->span + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch;
     p->merge = p->grid[0] > 1;
@@ -360,6 +361,12 @@ int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
         return LLMIE_ERR_WORKSPACE;
     }
     return LLMIE_OK;
+}
+
+void mla_merge_launch(const MlaDecodePlan &p, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *ctx_len, int head_num,
+                      hipStream_t st) {
+    hipLaunchKernelGGL(mla_merge_kernel, dim3(p.merge_grid[0], p.merge_grid[1]), dim3(p.merge_block), 0, st, ws_o, ws_ml, o_lat, ctx_len, head_num,
+                       p.span, p.grid[0]);
 }
 
 }  // namespace llmie
@@ -433,9 +440,7 @@ extern "C" int llmie_mla_decode(const void *q_lat, const void *cache, void *o_la
                        static_cast<const half_t *>(q_lat), static_cast<const half_t *>(cache), static_cast<half_t *>(o_lat), ws_o, ws_ml, ctx_len_dev,
                        block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), head_num, max_seq_len,
                        p.span, softmax_scale * 1.44269504088896341f);
-    if (p.merge)
-        hipLaunchKernelGGL(mla_merge_kernel, dim3(p.merge_grid[0], p.merge_grid[1]), dim3(p.merge_block), 0, as_stream(stream), ws_o, ws_ml,
-                           static_cast<half_t *>(o_lat), ctx_len_dev, head_num, p.span, p.grid[0]);
+    if (p.merge) mla_merge_launch(p, ws_o, ws_ml, static_cast<half_t *>(o_lat), ctx_len_dev, head_num, as_stream(stream));
     return launch_status("mla_decode");
 }
 

@@ -8,6 +8,11 @@ namespace llmie {
 constexpr int kLat = LLMIE_MLA_KV_LORA_RANK, kRope = LLMIE_MLA_QK_ROPE_HEAD_DIM, kRow = LLMIE_MLA_ROW;
 constexpr int kNope = LLMIE_MLA_QK_NOPE_HEAD_DIM, kVd = LLMIE_MLA_V_HEAD_DIM, kQ = kNope + kRope, kPage = LLMIE_MLA_PAGE_TOKENS;
 static_assert(kLat == 512 && kRope == 64 && kRow == 576 && kNope == 128 && kVd == 128, "the kernels are written for this geometry");
+// the e4m3 row (mla_e4m3.hip): 512 e4m3 latent bytes, then the 64 k_pe halves: 40 pieces of 16 bytes, 32 latent and 8 rope
+constexpr int kRowE4 = LLMIE_MLA_ROW_E4M3_BYTES, kLatPieces = kLat / 16, kPePieces = kRope * 2 / 16;
+static_assert(kRowE4 == kLat + 2 * kRope && kRowE4 == 16 * (kLatPieces + kPePieces), "the e4m3 row: 640 bytes");
+// the decode split both cache formats share (plan_mla_decode): heads per workgroup, keys per staged tile, tokens per split, merge block
+constexpr int kMlaHeads = 16, kMlaTile = 32, kMlaChunk = 256, kMlaMergeBlock = 128;
 
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) fp16x4_t *lds_fp16x4_ptr;
@@ -19,6 +24,12 @@ __device__ __forceinline__ bool mla_live(int ctx, int max_ctx) { return ctx >= 1
 __device__ __forceinline__ size_t mla_row_off(const int32_t *__restrict__ table, int max_pages, size_t layer_off, int b, int t, int max_seq_len) {
     return table ? layer_off + (static_cast<size_t>(table[static_cast<size_t>(b) * max_pages + t / kPage]) * kPage + t % kPage) * kRow
                  : layer_off + (static_cast<size_t>(b) * max_seq_len + t) * kRow;
+}
+
+// the same place in an e4m3 cache, in bytes (layer_off in bytes: mla_layer_off_bytes)
+__device__ __forceinline__ size_t mla_row_off_bytes(const int32_t *__restrict__ table, int max_pages, size_t layer_off, int b, int t, int max_seq_len) {
+    return table ? layer_off + (static_cast<size_t>(table[static_cast<size_t>(b) * max_pages + t / kPage]) * kPage + t % kPage) * kRowE4
+                 : layer_off + (static_cast<size_t>(b) * max_seq_len + t) * kRowE4;
 }
 
 inline int mla_heads_check(const char *who, int batch, int head_num) {
@@ -41,6 +52,10 @@ inline int mla_cache_check(const char *who, int max_seq_len, bool paged, int max
 
 inline size_t mla_layer_off(int layer, int batch, int max_seq_len, bool paged, int num_pages) {
     return static_cast<size_t>(layer) * (paged ? static_cast<size_t>(num_pages) * kPage : static_cast<size_t>(batch) * max_seq_len) * kRow;
+}
+
+inline size_t mla_layer_off_bytes(int layer, int batch, int max_seq_len, bool paged, int num_pages) {
+    return static_cast<size_t>(layer) * (paged ? static_cast<size_t>(num_pages) * kPage : static_cast<size_t>(batch) * max_seq_len) * kRowE4;
 }
 
 }  // namespace llmie

@@ -23,6 +23,10 @@ With --verify ROWS... (e.g. 2 4 8 16) the speculative step follows, per heads x 
   prefill   (--verify-prefill, the first cell of every row count) llmie_mla_kv_up + llmie_mla_prefill with hist = ctx - rows: the
             un-absorbed route, which projects the whole history up on every step
 
+With --e4m3 the e4m3 latent cache (640 bytes per token) follows instead of the rows above, one interleaved run per cell:
+  decode_e4m3   llmie_mla_decode_e4m3 on the quantised copy of the cache the fp16 `decode` of the same run reads (dense); their ratio,
+            and the HBM bound at ctx * 640 B * batch
+
 Prints one JSON line (and writes it to --out): microseconds, and the ratios decode / bound and torch / decode.  Only time is measured."""
 import argparse
 import importlib.util
@@ -107,6 +111,28 @@ def bench(heads, batch, ctx, rounds, reps, hbm_gbs, mfma_tflops):
                 us={k: round(v[0] * 1e6, 1) for k, v in t.items()}, spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
                 bound_us=round(bound * 1e6, 2), bound_by="hbm" if t_hbm >= t_mfma else "mfma",
                 decode_over_bound=round(t["decode"][0] / bound, 2), torch_over_decode=round(t["torch"][0] / t["decode"][0], 2))
+
+
+def bench_e4m3(heads, batch, ctx, rounds, reps, hbm_gbs, mfma_tflops):
+    """decode_e4m3 beside the fp16 decode of the same interleaved run (dense), on caches that hold the same latents"""
+    dev, c_scale = "cuda", 0.0123
+    dense = torch.empty((1, batch, ctx, 576), dtype=F16, device=dev).normal_(0, 0.5)
+    e4 = torch.empty((1, batch, ctx, 640), dtype=torch.uint8, device=dev)
+    e4[..., :512] = (dense[..., :512].float() / c_scale).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+    e4[..., 512:] = dense[..., 512:].contiguous().view(torch.uint8)
+    q_lat = (torch.randn((batch, heads, 576), device=dev) / 24).to(F16)
+    lengths = torch.full((batch,), ctx, dtype=torch.int32, device=dev)
+    o16, o8 = (torch.empty((batch, heads, 512), dtype=F16, device=dev) for _ in range(2))
+    ws = llmie.mla_workspace(batch, heads, ctx)
+    t = interleaved({"decode": lambda: llmie.mla_decode(q_lat, dense, 0, lengths, SCALE, o16, ws),
+                     "decode_e4m3": lambda: llmie.mla_decode_e4m3(q_lat, e4, c_scale, 0, lengths, SCALE, o8, ws)}, rounds, reps)
+    flops = 2.0 * batch * heads * ctx * (576 + 512)
+    t_hbm, t_mfma = ctx * 640.0 * batch / (hbm_gbs * 1e9), flops / (mfma_tflops * 1e12)
+    return dict(heads=heads, batch=batch, ctx=ctx, plan=llmie.mla_decode_e4m3_plan(batch, heads, ctx)[0],
+                us={k: round(v[0] * 1e6, 1) for k, v in t.items()}, spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
+                e4m3_over_f16=round(t["decode_e4m3"][0] / t["decode"][0], 3), hbm_bound_640_us=round(t_hbm * 1e6, 2),
+                bound_us=round(max(t_hbm, t_mfma) * 1e6, 2), bound_by="hbm" if t_hbm >= t_mfma else "mfma",
+                e4m3_over_hbm_bound=round(t["decode_e4m3"][0] / t_hbm, 2))
 
 
 def bench_prefill(heads, lens, rounds, reps, hbm_gbs, mfma_tflops):
@@ -216,11 +242,14 @@ def main():
     ap.add_argument("--verify", type=int, nargs="*", default=[], help="query rows per sequence of the speculative step, e.g. 2 4 8 16")
     ap.add_argument("--verify-prefill", action="store_true", help="add the kv_up + mla_prefill route to the first cell of every row count")
     ap.add_argument("--verify-only", action="store_true", help="skip the decode / chain / torch rows")
+    ap.add_argument("--e4m3", action="store_true", help="the e4m3 latent cache: decode_e4m3 beside the fp16 decode, per heads x ctx x batch (these rows only)")
     ap.add_argument("--out")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "mlabench measures on the GPU: there is no CPU path"
     res = dict(tool="mlabench", device=torch.cuda.get_device_name(0), peaks=dict(hbm_GBs_datasheet=a.hbm_gbs, mfma_f16_TFLOPs_datasheet=a.mfma_tflops))
-    if not a.verify_only:
+    if a.e4m3:
+        res["e4m3_rows"] = [bench_e4m3(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
+    elif not a.verify_only:
         res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
     if a.verify:
         cells = [(h, b, c) for h in a.heads for c in a.ctx for b in a.batches]
