@@ -341,9 +341,41 @@ struct MlaDecodePlan {
     size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
-// the merge launch of a plan with p.merge: both decode kernels leave their (m, l, o[512]) fp32 partials in the one format it reads
-void mla_merge_launch(const MlaDecodePlan &p, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *ctx_len, int head_num,
-                      hipStream_t st);
+// what llmie_mla_decode and llmie_mla_decode_e4m3 (c.e4m3) do with their operands: the checks under the entry's name `who`, the plan,
+// the launch of the format's mla_decode_kernel and the merge
+struct MlaDecodeIo {
+    const void *q_lat, *cache;
+    void *o_lat;
+    int layer;
+    const int32_t *ctx_len, *block_table;
+    float softmax_scale;
+    void *workspace;
+    float c_scale;                     // the e4m3 cache's scale; not read for the fp16 cache
+};
+int mla_decode_run(const char *who, const MlaDecodeCall &c, const MlaDecodeIo &io, hipStream_t st);
+// the text of llmie_mla_decode_plan / _e4m3_plan (c.e4m3: with the row size) into the entry's buffer, or null and the refusal
+const char *mla_decode_plan_text(const char *who, const MlaDecodeCall &c, char *text, size_t size, int *status);
+// the merge launch of decode (rows = 0: len_dev = ctx_len, one row per sequence) and verify (len_dev = hist, count_dev or null, rows
+// query-row slots per sequence): all three attention kernels leave their (m, l, o[512]) fp32 partials in the one format it reads
+void mla_merge_launch(const int merge_grid[2], int span, int splits, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *len_dev,
+                      const int32_t *count_dev, int rows, int head_num, hipStream_t st);
+// the one append launch of the four llmie_mla_kv_append* entries, one wave per token: the single-token form (cum null: token =
+// sequence b, row ctx_len[b] - 1) or the bulk form (packed tokens), into the fp16 cache or, e4m3, quantised by c_scale
+struct MlaAppendCall {
+    const void *kv_a, *gamma;
+    float eps;
+    const void *rope;
+    void *cache;
+    int layer, batch, max_seq_len;
+    const int32_t *ctx_len;            // single-token form
+    const int32_t *cum, *hist;         // bulk form
+    int max_q_len, kv_span;
+    const int32_t *block_table;
+    int max_pages, num_pages;
+    bool e4m3;
+    float c_scale;
+};
+void mla_append_launch(const MlaAppendCall &a, int tokens, hipStream_t st);
 // ---- MLA verify attention (mla_verify.hip): several query rows per sequence on the latent cache; the pattern of plan_mla_decode ----
 struct MlaVerifyCall {
     int batch, rows, head_num, max_seq_len;   // rows: query-row slots per sequence (a chain's length, a tree's stride)
@@ -359,7 +391,7 @@ struct MlaVerifyPlan {
     int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
     int row_blocks;                    // ceil(call rows / rows)
     int grid[3];                       // (splits, head blocks, batch x row blocks)
-    bool merge;                        // more than one split: mla_verify_merge_kernel follows
+    bool merge;                        // more than one split: mla_merge_kernel follows
     int merge_grid[2], merge_block;
     size_t workspace_bytes;            // the split partials (0 with one split)
 };

@@ -1,7 +1,7 @@
 // Multi-head Latent Attention, decode step (DeepSeek-V2 / V3 / R1, Kimi-K2), in the absorbed form: the cache holds ONE row of
 // 576 halves per token (512 latent dims c, 64 rotated k_pe dims), every query head attends over that row, and the per-head
 // projections W_UK / W_UV are folded into the query and the output (include/llmie.h, llmie_mla_*).  Four launches per layer:
-//   mla_kv_append_kernel    RMSNorm(c) * gamma  ||  rope(k_pe)  ->  cache row ctx - 1               (one wave per sequence)
+//   mla_kv_append_kernel    RMSNorm(c) * gamma  ||  rope(k_pe)  ->  cache row ctx - 1               (one wave per token)
 //   mla_q_absorb_kernel     q_lat = (W_UK[h]^T q_nope) || rope(q_pe)                                (MFMA, W_UK staged once)
 //   mla_decode_kernel       split-KV flash decode over the latent rows, 16 heads per workgroup      (MFMA, the hot path)
 //   mla_merge_kernel        fixed-order merge of the split partials (only with more than one split)
@@ -23,52 +23,58 @@
 // Rows of a tile at or past ctx re-read row ctx - 1 (same tile, same page) and their logits are -inf before the max; no load
 // leaves the context and no block-table entry past (ctx - 1) / 128 is read.  The chunking depends on ctx alone, so a sequence's
 // bits do not depend on the batch, its slot or the grid.  Plain softmax: out = sum p v / sum p, no epsilon in the denominator.
+// The append, the decode and the merge kernel are templates that also serve the bulk append (mla_prefill.hip), the e4m3 cache
+// (mla_e4m3.hip) and verify's merge (mla_verify.hip) through mla_append_launch, mla_decode_run and mla_merge_launch.
 #include "mla_common.cuh"
 
-#include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 namespace llmie {
 
 namespace {
 
-constexpr int kMlaStride = kRow + 16;
-static_assert(kPage % kMlaTile == 0 && kMlaChunk % kMlaTile == 0, "a tile never crosses a page or a chunk");
-static_assert((kMlaStride * 2) % 64 == 32, "row stride = an odd multiple of 32 bytes: conflict-free transposed reads");
+static_assert(kMlaTile == 32 && kLatPieces == 32 && kPePieces == 8, "the e4m3 fetch layout: 4 waves x 8 rows, 4 latent + 1 rope piece per lane");
 
-// ---- append: one wave per sequence.  Lane i holds c[8 i .. 8 i + 7]; sum of squares: ss = fma(c_j, c_j, ss) over j = 0 .. 7 in
-// that order from ss = 0, then the xor butterfly over lane distances 32, 16, 8, 4, 2, 1 (the order include/llmie.h states) ----
+template <bool E4> using cache_elem_t = std::conditional_t<E4, unsigned char, half_t>;   // the e4m3 cache is addressed in bytes
+
+// ---- append: one wave per token.  cum == null: token = sequence b, row ctx_len[b] - 1; else the packed token blockIdx.x of the bulk
+// form.  The row is mla_append_latent || mla_append_rope (mla_common.cuh) for both formats; E4: code = e4m3(fp16 / c_scale),
+// saturated, the 640 bytes are put together in LDS and leave as 40 stores of 16 bytes. ----
+template <bool E4, typename... Scale>
 __global__ __launch_bounds__(64) void mla_kv_append_kernel(const half_t *__restrict__ kv_a, const half_t *__restrict__ gamma, float eps,
-                                                           const float2 *__restrict__ rope, half_t *__restrict__ cache, size_t layer_off,
-                                                           int max_seq_len, const int32_t *__restrict__ ctx_len,
-                                                           const int32_t *__restrict__ table, int max_pages) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int ctx = ctx_len[b];
-    if (!mla_live(ctx, max_seq_len)) return;
-    const int pos = ctx - 1;
-    half_t *row = cache + mla_row_off(table, max_pages, layer_off, b, pos, max_seq_len);
-    const half_t *src = kv_a + static_cast<size_t>(b) * kRow;
-    const half8_t x = *reinterpret_cast<const half8_t *>(src + 8 * lane);
-    const half8_t g = *reinterpret_cast<const half8_t *>(gamma + 8 * lane);
-    float ss = 0.f;
+                                                           const float2 *__restrict__ rope, cache_elem_t<E4> *__restrict__ cache, size_t layer_off,
+                                                           int max_seq_len, const int32_t *__restrict__ ctx_len, const int32_t *__restrict__ cum,
+                                                           const int32_t *__restrict__ hist, int batch, int max_q_len, int kv_span,
+                                                           const int32_t *__restrict__ table, int max_pages, const Scale... c_scale /* E4 */) {
+    static_assert(sizeof...(Scale) == (E4 ? 1 : 0), "c_scale");
+    const int tok = blockIdx.x, lane = threadIdx.x;
+    int b = tok, pos;
+    if (cum) {
+        if (!mla_packed_locate(cum, hist, batch, tok, max_q_len, kv_span, &b, &pos)) return;
+    } else {
+        const int ctx = ctx_len[b];
+        if (!mla_live(ctx, max_seq_len)) return;
+        pos = ctx - 1;
+    }
+    const half_t *src = kv_a + static_cast<size_t>(tok) * kRow;
+    const half8_t y = mla_append_latent(src, gamma, eps, lane);
+    if constexpr (E4) {
+        __shared__ __attribute__((aligned(16))) unsigned char Rs[kRowE4];
+        float z[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(to_f32(x[j]), to_f32(x[j]), ss);
-    ss = lane_xor_sum<32>(ss);
-    ss = lane_xor_sum<16>(ss);
-    ss = lane_xor_sum<8>(ss);
-    ss = lane_xor_sum<4>(ss);
-    ss = lane_xor_sum<2>(ss);
-    ss = lane_xor_sum<1>(ss);
-    const float inv = 1.f / sqrtf(ss * (1.f / kLat) + eps);
-    half8_t y;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) y[j] = from_f32<half_t>(to_f32(x[j]) * inv * to_f32(g[j]));
-    *reinterpret_cast<half8_t *>(row + 8 * lane) = y;
-    if (lane < kRope / 2) {
-        const float2 cs = rope[static_cast<size_t>(pos) * (kRope / 2) + lane];
-        const float x0 = to_f32(src[kLat + lane]), x1 = to_f32(src[kLat + kRope / 2 + lane]);
-        row[kLat + lane] = from_f32<half_t>(x0 * cs.x - x1 * cs.y);
-        row[kLat + kRope / 2 + lane] = from_f32<half_t>(x1 * cs.x + x0 * cs.y);
+        for (int j = 0; j < 8; ++j) z[j] = to_f32(y[j]) / pack_arg<0>(c_scale...);
+        *reinterpret_cast<uint2 *>(Rs + 8 * lane) = make_uint2(pack4_e4m3(z[0], z[1], z[2], z[3]), pack4_e4m3(z[4], z[5], z[6], z[7]));
+        if (lane < kRope / 2) mla_append_rope(src, rope, pos, lane, reinterpret_cast<half_t *>(Rs + kLat));
+        __syncthreads();
+        if (lane < kRowE4 / 16)
+            *reinterpret_cast<uint4_t *>(cache + mla_row_off<kRowE4>(table, max_pages, layer_off, b, pos, max_seq_len) + 16 * lane) =
+                *reinterpret_cast<const uint4_t *>(Rs + 16 * lane);
+    } else {
+        half_t *row = cache + mla_row_off<kRow>(table, max_pages, layer_off, b, pos, max_seq_len);
+        *reinterpret_cast<half8_t *>(row + 8 * lane) = y;
+        if (lane < kRope / 2) mla_append_rope(src, rope, pos, lane, row + kLat);
     }
 }
 
@@ -164,12 +170,24 @@ __global__ __launch_bounds__(256) void mla_out_project_kernel(const half_t *__re
     }
 }
 
-// ---- the attention ----
+// ---- the attention, one template over the cache format.  E4 = false: the fp16 cache, the argument list without c_scale.  E4 = true
+// (cache in bytes, layer_off in bytes) differs in three places, each behind `if constexpr`:
+//   fetch    a tile is 32 rows x 640 bytes = 1280 pieces of 16 bytes, 5 per thread (9 in the fp16 form: 20 VGPRs in flight, not 36).
+//            A row is 32 latent pieces + 8 rope pieces, so wave w takes rows 8 w .. 8 w + 7: latent piece i = 0..3 of a lane is row
+//            8 w + 2 i + (lane >> 5), column lane & 31; its rope piece is row 8 w + (lane >> 3), column lane & 7: no division.
+//   publish  every latent piece becomes 16 halves with v_cvt_scalef32_pk_f16_fp8 at scale 1.0 (two codes per instruction): each half
+//            IS the code's value -- every finite e4m3 value, the subnormal codes included, is an fp16 normal --, so no power-of-two
+//            factor rides along and no MFMA operand is subnormal.  The rope piece is stored as it came.
+//   scale    c_scale never touches an fp16 operand.  Wave kk = 0 (dims 0..287) multiplies its logit partial by c_scale; wave
+//            kk = 1 keeps two accumulators -- steps 0..6 are latent dims 288..511, steps 7..8 are k_pe -- and leaves
+//            c_scale * s_lat + s_pe.  o is multiplied by c_scale once, in front of the store. ----
+template <bool E4, typename... Scale>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mla_decode_kernel(
-    const half_t *__restrict__ q_lat, const half_t *__restrict__ cache, half_t *__restrict__ o_lat, float *__restrict__ ws_o,
+    const half_t *__restrict__ q_lat, const cache_elem_t<E4> *__restrict__ cache, half_t *__restrict__ o_lat, float *__restrict__ ws_o,
     float2 *__restrict__ ws_ml, const int32_t *__restrict__ ctx_len, const int32_t *__restrict__ table, int max_pages, size_t layer_off,
-    int head_num, int max_seq_len, int max_ctx, float scale2 /* softmax_scale * log2(e) */) {
-    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes
+    int head_num, int max_seq_len, int max_ctx, float scale2 /* softmax_scale * log2(e) */, const Scale... c_scale /* E4 */) {
+    static_assert(sizeof...(Scale) == (E4 ? 1 : 0), "c_scale");
+    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes (E4: the codes' values || k_pe, in fp16)
     __shared__ __attribute__((aligned(16))) float Sp[2 * 8 * 16 * 4];                // partial logits [kk][key / 4][head][key % 4]
     const int split = blockIdx.x, hb = blockIdx.y, b = blockIdx.z, splits = gridDim.x;
     const int ctx = ctx_len[b];
@@ -188,27 +206,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
         for (int s = 0; s < 9; ++s) qf[s] = *reinterpret_cast<const half8_t *>(qp + 32 * s);
     }
 
-    constexpr int NCH = kMlaTile * kRow / 8 / 256;   // 9 sixteen-byte pieces of a tile per thread
+    constexpr int NCH = E4 ? 5 : kMlaTile * kRow / 8 / 256;   // sixteen-byte pieces of a tile per thread (fp16: 9)
     half8_t treg[NCH];
+    // E4 staging: wave w owns rows 8 w .. 8 w + 7 of a tile
+    const int lrow = 8 * wave + (lane >> 5), lcol = lane & 31;   // latent piece i: row lrow + 2 i, codes 16 lcol ..
+    const int prow = 8 * wave + (lane >> 3), pcol = lane & 7;    // rope piece: halves kLat + 8 pcol ..
     auto fetch_tile = [&](int t0) {   // global -> registers; one page lookup per tile, wave-uniform
-        const size_t base = table ? layer_off + static_cast<size_t>(__builtin_amdgcn_readfirstlane(table[static_cast<size_t>(b) * max_pages + t0 / kPage])) * kPage * kRow
-                                  : layer_off + static_cast<size_t>(b) * max_seq_len * kRow;
+        const cache_elem_t<E4> *base = cache + layer_off + mla_tile_row0(table, max_pages, b, t0, max_seq_len) * (E4 ? kRowE4 : kRow);
+        const int last = ctx - 1 - t0;   // >= 0; a row past it re-reads it (same tile, same page)
+        if constexpr (E4) {
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-            const int t = min(t0 + row, ctx - 1);   // (t0 <= ctx - 1 < t0 + 32 where the clamp acts: same tile, same page)
-            treg[i] = *reinterpret_cast<const half8_t *>(cache + base + static_cast<size_t>(table ? t % kPage : t) * kRow + ch * 8);
+            for (int i = 0; i < 4; ++i) treg[i] = *reinterpret_cast<const half8_t *>(base + min(lrow + 2 * i, last) * kRowE4 + 16 * lcol);
+            treg[4] = *reinterpret_cast<const half8_t *>(base + min(prow, last) * kRowE4 + kLat + 16 * pcol);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
+                treg[i] = *reinterpret_cast<const half8_t *>(base + min(row, last) * kRow + ch * 8);
+            }
         }
     };
-    auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows
+    auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows (E4: codes to halves)
+        if constexpr (E4) {
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-            *reinterpret_cast<half8_t *>(Ts[buf] + row * kMlaStride + ch * 8) = treg[i];
+            for (int i = 0; i < 4; ++i) {
+                const uint4_t w = __builtin_bit_cast(uint4_t, treg[i]);
+                half_t *dst = Ts[buf] + (lrow + 2 * i) * kMlaStride + 16 * lcol;
+                *reinterpret_cast<half8_t *>(dst) = e4m3x8_to_f16(w[0], w[1]);
+                *reinterpret_cast<half8_t *>(dst + 8) = e4m3x8_to_f16(w[2], w[3]);
+            }
+            *reinterpret_cast<half8_t *>(Ts[buf] + prow * kMlaStride + kLat + 8 * pcol) = treg[4];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
+                *reinterpret_cast<half8_t *>(Ts[buf] + row * kMlaStride + ch * 8) = treg[i];
+            }
         }
     };
 
-    floatx4 o[8];   // O^T: dims 128 wave + 16 dt + 4 q + e, column = head r
+    floatx4 o[8];   // O^T (E4: in units of c_scale): dims 128 wave + 16 dt + 4 q + e, column = head r
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;   // log2 domain, scale applied; l_run: this lane's 8 of a tile's 32 keys
@@ -225,16 +262,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
             if (it + 2 < n_tiles) fetch_tile(t0 + 2 * kMlaTile);   // in flight under this iteration's MFMAs
         }
         __builtin_amdgcn_sched_barrier(0);
-        // ---- S^T partial: keys 16 kh + r, dims 288 kk .. ----
+        // ---- S^T partial: keys 16 kh + r, dims 288 kk .. (E4: c_scale joins in fp32) ----
         {
             half8_t kf[9];
             const half_t *kp = Tt + (16 * kh + r) * kMlaStride + 288 * kk + 8 * q;
 #pragma unroll
             for (int s = 0; s < 9; ++s) kf[s] = *reinterpret_cast<const half8_t *>(kp + 32 * s);
-            floatx4 sacc = {0.f, 0.f, 0.f, 0.f};
+            floatx4 sacc = {0.f, 0.f, 0.f, 0.f};   // sacc[e] = S[key 16 kh + 4 q + e][head r]
 #pragma unroll
-            for (int s = 0; s < 9; ++s) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], qf[s], sacc, 0, 0, 0);
-            // sacc[e] = S[key 16 kh + 4 q + e][head r]
+            for (int s = 0; s < 7; ++s) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], qf[s], sacc, 0, 0, 0);
+            if constexpr (E4) {
+                const floatx4 s_lat = sacc;
+                floatx4 s_end = kk ? floatx4{0.f, 0.f, 0.f, 0.f} : s_lat;   // kk = 0: latent dims 224..287; kk = 1: k_pe, an accumulator of its own
+                s_end = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[7], qf[7], s_end, 0, 0, 0);
+                s_end = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[8], qf[8], s_end, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    sacc[e] = kk ? __builtin_fmaf(pack_arg<0>(c_scale...), s_lat[e], s_end[e]) : pack_arg<0>(c_scale...) * s_end[e];
+            } else {
+                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[7], qf[7], sacc, 0, 0, 0);
+                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[8], qf[8], sacc, 0, 0, 0);
+            }
             *reinterpret_cast<floatx4 *>(Sp + (((kk * 8 + 4 * kh + q) * 16 + r) << 2)) = sacc;
         }
         __syncthreads();   // both halves of every logit are there
@@ -293,34 +341,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
         }
     }
     const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run));
-    const size_t bh = static_cast<size_t>(b) * head_num + head;
-    if (splits == 1) {   // the only split: the output itself
-        const float inv = 1.f / l;
-        half_t *op = o_lat + bh * kLat + 128 * wave + 4 * q;
+    if constexpr (E4) {
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
-            const half4_t v = {from_f32<half_t>(o[dt][0] * inv), from_f32<half_t>(o[dt][1] * inv), from_f32<half_t>(o[dt][2] * inv),
-                               from_f32<half_t>(o[dt][3] * inv)};
-            *reinterpret_cast<half4_t *>(op + 16 * dt) = v;
-        }
-    } else {
-        float *op = ws_o + (bh * splits + split) * kLat + 128 * wave + 4 * q;
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) *reinterpret_cast<floatx4 *>(op + 16 * dt) = o[dt];
-        if (wave == 0 && q == 0) ws_ml[bh * splits + split] = make_float2(m_run, l);
+        for (int dt = 0; dt < 8; ++dt) o[dt] *= pack_arg<0>(c_scale...);   // the one place the output meets c_scale
     }
+    mla_store_split(o, m_run, l, static_cast<size_t>(b) * head_num + head, split, splits, wave, q, o_lat, ws_o, ws_ml);
 }
 
-// merge: grid (head_num, batch), 128 threads x 4 dims.  Splits 0 .. ceil(ctx / chunk) - 1 in that order: M = max m_i,
+// merge: 128 threads x 4 dims per (query row, head).  Splits 0 .. ceil(ctx / chunk) - 1 in that order: M = max m_i,
 // w_i = 2^(m_i - M), L = sum w_i l_i, out = (sum w_i o_i) / L.  One partial gives the bits of the one-split launch (w = 1).
+// Decode: grid (head_num, batch), len_dev = ctx_len.  VERIFY: grid (head_num, batch x rows), len_dev = hist, the pack = (count_dev,
+// rows); a partial that saw nothing (m = -inf, l = 0, o = 0) has weight 0, and the split that holds the row's own node is finite, so M is.
+template <bool VERIFY, typename... Rows>
 __global__ __launch_bounds__(kMlaMergeBlock) void mla_merge_kernel(const float *__restrict__ ws_o, const float2 *__restrict__ ws_ml,
-                                                                   half_t *__restrict__ o_lat, const int32_t *__restrict__ ctx_len,
-                                                                   int head_num, int max_ctx, int splits) {
-    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int ctx = ctx_len[b];
-    if (!mla_live(ctx, max_ctx)) return;
-    const int n = (ctx + kMlaChunk - 1) / kMlaChunk;   // <= splits (ctx <= max_ctx)
-    const size_t bh = static_cast<size_t>(b) * head_num + h;
+                                                                   half_t *__restrict__ o_lat, const int32_t *__restrict__ len_dev, int head_num,
+                                                                   int span, int splits, const Rows... vr /* VERIFY: count_dev, rows */) {
+    static_assert(sizeof...(Rows) == (VERIFY ? 2 : 0), "count_dev, rows");
+    const int h = blockIdx.x, tid = threadIdx.x;
+    int row = blockIdx.y, ctx;   // the (sequence, query row) slot, and the context its splits cover
+    if constexpr (VERIFY) {
+        const int rows = pack_arg<1>(vr...), b = row / rows;
+        int hist, count;
+        if (!verify_live(len_dev, pack_arg<0>(vr...), b, rows, span, &hist, &count) || row - b * rows >= count) return;
+        ctx = hist + count;
+    } else {
+        ctx = len_dev[row];
+        if (!mla_live(ctx, span)) return;
+    }
+    const int n = (ctx + kMlaChunk - 1) / kMlaChunk;   // <= splits (ctx <= span)
+    const size_t bh = static_cast<size_t>(row) * head_num + h;
     float M = -INFINITY;
     for (int i = 0; i < n; ++i) M = fmaxf(M, ws_ml[bh * splits + i].x);
     float L = 0.f;
@@ -363,10 +412,62 @@ int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
     return LLMIE_OK;
 }
 
-void mla_merge_launch(const MlaDecodePlan &p, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *ctx_len, int head_num,
-                      hipStream_t st) {
-    hipLaunchKernelGGL(mla_merge_kernel, dim3(p.merge_grid[0], p.merge_grid[1]), dim3(p.merge_block), 0, st, ws_o, ws_ml, o_lat, ctx_len, head_num,
-                       p.span, p.grid[0]);
+void mla_merge_launch(const int merge_grid[2], int span, int splits, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *len_dev,
+                      const int32_t *count_dev, int rows, int head_num, hipStream_t st) {
+    const dim3 grid(merge_grid[0], merge_grid[1]), block(kMlaMergeBlock);
+    if (rows) hipLaunchKernelGGL((mla_merge_kernel<true, const int32_t *, int>), grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits, count_dev, rows);
+    else hipLaunchKernelGGL(mla_merge_kernel<false>, grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits);
+}
+
+void mla_append_launch(const MlaAppendCall &a, int tokens, hipStream_t st) {
+    const size_t layer_off = mla_layer_off(a.layer, a.batch, a.max_seq_len, a.block_table != nullptr, a.num_pages, a.e4m3 ? kRowE4 : kRow);
+    const half_t *kv_a = static_cast<const half_t *>(a.kv_a), *gamma = static_cast<const half_t *>(a.gamma);
+    const float2 *rope = static_cast<const float2 *>(a.rope);
+    if (a.e4m3)
+        hipLaunchKernelGGL((mla_kv_append_kernel<true, float>), dim3(tokens), dim3(64), 0, st, kv_a, gamma, a.eps, rope, static_cast<unsigned char *>(a.cache),
+                           layer_off, a.max_seq_len, a.ctx_len, a.cum, a.hist, a.batch, a.max_q_len, a.kv_span, a.block_table, a.max_pages, a.c_scale);
+    else
+        hipLaunchKernelGGL(mla_kv_append_kernel<false>, dim3(tokens), dim3(64), 0, st, kv_a, gamma, a.eps, rope, static_cast<half_t *>(a.cache), layer_off,
+                           a.max_seq_len, a.ctx_len, a.cum, a.hist, a.batch, a.max_q_len, a.kv_span, a.block_table, a.max_pages);
+}
+
+int mla_decode_run(const char *who, const MlaDecodeCall &c, const MlaDecodeIo &io, hipStream_t st) {
+    LLMIE_REQUIRE(io.q_lat && io.cache && io.o_lat && io.ctx_len, "%s: NULL operand", who);
+    LLMIE_REQUIRE(io.layer >= 0, "%s: layer=%d should be >= 0", who, io.layer);
+    LLMIE_REQUIRE(mla_scale_ok(io.softmax_scale), "%s: softmax_scale should be positive and finite", who);
+    if (c.e4m3) LLMIE_REQUIRE(mla_scale_ok(io.c_scale), "%s: c_scale should be positive and finite", who);
+    MlaDecodePlan p{};
+    const int rc = plan_mla_decode(who, c, &p);
+    if (rc != LLMIE_OK) return rc;
+    LLMIE_REQUIRE(mis16(io.q_lat) == 0 && mis16(io.cache) == 0 && mis16(io.o_lat) == 0 && (!p.merge || mis16(io.workspace) == 0),
+                  "%s: q_lat, the cache, o_lat and the workspace should be 16-byte aligned", who);
+    const half_t *q_lat = static_cast<const half_t *>(io.q_lat);
+    half_t *o_lat = static_cast<half_t *>(io.o_lat);
+    float *ws_o = static_cast<float *>(io.workspace);
+    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(c.batch) * c.head_num * p.grid[0] * kLat) : nullptr;
+    const size_t layer_off = mla_layer_off(io.layer, c.batch, c.max_seq_len, c.paged, c.num_pages, c.e4m3 ? kRowE4 : kRow);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    if (c.e4m3)
+        hipLaunchKernelGGL((mla_decode_kernel<true, float>), grid, dim3(256), 0, st, q_lat, static_cast<const unsigned char *>(io.cache), o_lat, ws_o, ws_ml,
+                           io.ctx_len, io.block_table, c.max_pages, layer_off, c.head_num, c.max_seq_len, p.span, io.softmax_scale * kLog2e, io.c_scale);
+    else
+        hipLaunchKernelGGL(mla_decode_kernel<false>, grid, dim3(256), 0, st, q_lat, static_cast<const half_t *>(io.cache), o_lat, ws_o, ws_ml, io.ctx_len,
+                           io.block_table, c.max_pages, layer_off, c.head_num, c.max_seq_len, p.span, io.softmax_scale * kLog2e);
+    if (p.merge) mla_merge_launch(p.merge_grid, p.span, p.grid[0], ws_o, ws_ml, o_lat, io.ctx_len, nullptr, 0, c.head_num, st);
+    return launch_status(who);
+}
+
+const char *mla_decode_plan_text(const char *who, const MlaDecodeCall &c, char *text, size_t size, int *status) {
+    MlaDecodePlan p{};
+    const int rc = plan_mla_decode(who, c, &p);
+    if (status) *status = rc;
+    if (rc != LLMIE_OK) return nullptr;
+    int n = snprintf(text, size, "mla %s nh%d hb%d tile%d chunk%d ", c.e4m3 ? "e4m3" : "f16", c.head_num, p.heads, p.tile, p.chunk);
+    if (c.e4m3) n += snprintf(text + n, size - n, "row%d ", p.row_bytes);
+    n += snprintf(text + n, size - n, "grid %dx%dx%d merge ", p.grid[0], p.grid[1], p.grid[2]);
+    if (p.merge) snprintf(text + n, size - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
+    else snprintf(text + n, size - n, "none");
+    return text;
 }
 
 }  // namespace llmie
@@ -381,17 +482,9 @@ extern "C" size_t llmie_mla_decode_workspace_bytes(int batch, int head_num, int 
 extern "C" const char *llmie_mla_decode_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
                                              long long workspace_bytes, int *status) {
     static thread_local char text[160];
-    MlaDecodePlan p{};
     const MlaDecodeCall c{batch, head_num, max_seq_len, max_ctx, paged != 0, max_pages, num_pages, workspace_bytes >= 0,
                           workspace_bytes >= 0 ? static_cast<size_t>(workspace_bytes) : 0};
-    const int rc = plan_mla_decode("mla_decode_plan", c, &p);
-    if (status) *status = rc;
-    if (rc != LLMIE_OK) return nullptr;
-    int n = snprintf(text, sizeof(text), "mla f16 nh%d hb%d tile%d chunk%d grid %dx%dx%d merge ", head_num, p.heads, p.tile, p.chunk, p.grid[0],
-                     p.grid[1], p.grid[2]);
-    if (p.merge) snprintf(text + n, sizeof(text) - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
-    else snprintf(text + n, sizeof(text) - n, "none");
-    return text;
+    return mla_decode_plan_text("mla_decode_plan", c, text, sizeof(text), status);
 }
 
 extern "C" int llmie_mla_kv_append(const void *kv_a, const void *gamma, float eps, const void *rope_table, void *cache, int layer, int batch,
@@ -403,9 +496,9 @@ extern "C" int llmie_mla_kv_append(const void *kv_a, const void *gamma, float ep
     const int rc = mla_cache_check("mla_kv_append", max_seq_len, block_table != nullptr, max_pages, num_pages);
     if (rc != LLMIE_OK) return rc;
     LLMIE_REQUIRE(mis16(kv_a) == 0 && mis16(gamma) == 0 && mis16(cache) == 0, "mla_kv_append: kv_a, gamma and the cache should be 16-byte aligned");
-    hipLaunchKernelGGL(mla_kv_append_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const half_t *>(kv_a),
-                       static_cast<const half_t *>(gamma), eps, static_cast<const float2 *>(rope_table), static_cast<half_t *>(cache),
-                       mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), max_seq_len, ctx_len_dev, block_table, max_pages);
+    mla_append_launch(MlaAppendCall{kv_a, gamma, eps, rope_table, cache, layer, batch, max_seq_len, ctx_len_dev, nullptr, nullptr, 0, 0, block_table,
+                                    max_pages, num_pages},
+                      batch, as_stream(stream));
     return launch_status("mla_kv_append");
 }
 
@@ -425,23 +518,8 @@ extern "C" int llmie_mla_q_absorb(const void *q, const void *kv_b, const void *r
 extern "C" int llmie_mla_decode(const void *q_lat, const void *cache, void *o_lat, int layer, int batch, int head_num, int max_seq_len, int max_ctx,
                                 const int32_t *ctx_len_dev, float softmax_scale, void *workspace, size_t workspace_bytes,
                                 const int32_t *block_table, int max_pages, int num_pages, llmie_stream stream) {
-    LLMIE_REQUIRE(q_lat && cache && o_lat && ctx_len_dev, "mla_decode: NULL operand");
-    LLMIE_REQUIRE(layer >= 0, "mla_decode: layer=%d should be >= 0", layer);
-    LLMIE_REQUIRE(softmax_scale > 0.f && std::isfinite(softmax_scale), "mla_decode: softmax_scale should be positive and finite");
-    MlaDecodePlan p{};
     const MlaDecodeCall c{batch, head_num, max_seq_len, max_ctx, block_table != nullptr, max_pages, num_pages, workspace != nullptr, workspace_bytes};
-    const int rc = plan_mla_decode("mla_decode", c, &p);
-    if (rc != LLMIE_OK) return rc;
-    LLMIE_REQUIRE(mis16(q_lat) == 0 && mis16(cache) == 0 && mis16(o_lat) == 0 && (!p.merge || mis16(workspace) == 0),
-                  "mla_decode: q_lat, the cache, o_lat and the workspace should be 16-byte aligned");
-    float *ws_o = static_cast<float *>(workspace);
-    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(batch) * head_num * p.grid[0] * kLat) : nullptr;
-    hipLaunchKernelGGL(mla_decode_kernel, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, as_stream(stream),
-                       static_cast<const half_t *>(q_lat), static_cast<const half_t *>(cache), static_cast<half_t *>(o_lat), ws_o, ws_ml, ctx_len_dev,
-                       block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), head_num, max_seq_len,
-                       p.span, softmax_scale * 1.44269504088896341f);
-    if (p.merge) mla_merge_launch(p, ws_o, ws_ml, static_cast<half_t *>(o_lat), ctx_len_dev, head_num, as_stream(stream));
-    return launch_status("mla_decode");
+    return mla_decode_run("mla_decode", c, MlaDecodeIo{q_lat, cache, o_lat, layer, ctx_len_dev, block_table, softmax_scale, workspace}, as_stream(stream));
 }
 
 extern "C" int llmie_mla_out_project(const void *o_lat, const void *kv_b, void *out, int batch, int head_num, llmie_stream stream) {

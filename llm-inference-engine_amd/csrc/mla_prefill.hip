@@ -4,7 +4,7 @@
 // FLOP against the absorbed form's 2 x (576 + 512).  Sequences are packed as in prefill.hip: cum[batch + 1] = exclusive prefix of the
 // new-token counts, hist[b] = tokens already cached.  A sequence with no new token, more than max_q_len of them, or a context above
 // kv_span is left wholly untouched by all three launches.
-//   mla_kv_append_rows_kernel   the body of mla_kv_append_kernel at position hist[b] + i            (one wave per packed token)
+//   mla_kv_append_kernel        (mla.hip, mla_append_launch) the single-token row at position hist[b] + i  (one wave per packed token)
 //   mla_kv_up_kernel            kv_up[b, t, h, 0:256] = fp16(W[h] c_t), t < ctx                      (MFMA, latent tile staged once)
 //   mla_prefill_flash_kernel    causal online-softmax attention, plain softmax                       (MFMA, the hot path)
 //
@@ -32,7 +32,6 @@
 // position and the rows it sees alone: not on the batch, the slot, the grid, or how the prompt was cut into calls.
 #include "mla_common.cuh"
 
-#include <cmath>
 #include <cstdio>
 
 namespace llmie {
@@ -45,53 +44,6 @@ constexpr int kUpTok = 64, kUpHeads = 4, kUpStride = kLat + 16;
 static_assert(kPage % kPfTile == 0 && kPage % kUpTok == 0, "a tile never crosses a page");
 static_assert((kPfStride * 2) % 64 == 32 && (kUpStride * 2) % 64 == 32, "row stride = an odd multiple of 32 bytes");
 static_assert(kPfTile * kPfPieces % 256 == 0, "a tile is a whole number of pieces per thread");
-
-__device__ __forceinline__ bool mla_prefill_live(int len, int history, int max_q_len, int kv_span) {
-    return len >= 1 && len <= max_q_len && history >= 0 && history <= kv_span - len;
-}
-
-// ---- bulk append: one wave per packed token; the arithmetic and its order are mla_kv_append_kernel's (include/llmie.h) ----
-__global__ __launch_bounds__(64) void mla_kv_append_rows_kernel(const half_t *__restrict__ kv_a, const half_t *__restrict__ gamma, float eps,
-                                                                const float2 *__restrict__ rope, half_t *__restrict__ cache, size_t layer_off,
-                                                                int max_seq_len, const int32_t *__restrict__ cum, const int32_t *__restrict__ hist,
-                                                                int batch, int max_q_len, int kv_span, const int32_t *__restrict__ table,
-                                                                int max_pages) {
-    const int tok = blockIdx.x, lane = threadIdx.x;
-    if (tok >= cum[batch]) return;
-    int b = 0;   // the last sequence that begins at or in front of the token: an empty one shares its begin with its successor
-    for (int hi = batch; hi - b > 1;) {
-        const int mid = (b + hi) >> 1;
-        if (cum[mid] <= tok) b = mid;
-        else hi = mid;
-    }
-    const int history = hist[b];
-    if (!mla_prefill_live(cum[b + 1] - cum[b], history, max_q_len, kv_span)) return;
-    const int pos = history + tok - cum[b];
-    half_t *row = cache + mla_row_off(table, max_pages, layer_off, b, pos, max_seq_len);
-    const half_t *src = kv_a + static_cast<size_t>(tok) * kRow;
-    const half8_t x = *reinterpret_cast<const half8_t *>(src + 8 * lane);
-    const half8_t g = *reinterpret_cast<const half8_t *>(gamma + 8 * lane);
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(to_f32(x[j]), to_f32(x[j]), ss);
-    ss = lane_xor_sum<32>(ss);
-    ss = lane_xor_sum<16>(ss);
-    ss = lane_xor_sum<8>(ss);
-    ss = lane_xor_sum<4>(ss);
-    ss = lane_xor_sum<2>(ss);
-    ss = lane_xor_sum<1>(ss);
-    const float inv = 1.f / sqrtf(ss * (1.f / kLat) + eps);
-    half8_t y;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) y[j] = from_f32<half_t>(to_f32(x[j]) * inv * to_f32(g[j]));
-    *reinterpret_cast<half8_t *>(row + 8 * lane) = y;
-    if (lane < kRope / 2) {
-        const float2 cs = rope[static_cast<size_t>(pos) * (kRope / 2) + lane];
-        const float x0 = to_f32(src[kLat + lane]), x1 = to_f32(src[kLat + kRope / 2 + lane]);
-        row[kLat + lane] = from_f32<half_t>(x0 * cs.x - x1 * cs.y);
-        row[kLat + kRope / 2 + lane] = from_f32<half_t>(x1 * cs.x + x0 * cs.y);
-    }
-}
 
 // ---- up-projection ----
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mla_kv_up_kernel(const half_t *__restrict__ cache, const half_t *__restrict__ kv_b,
@@ -106,14 +58,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
     if (t0 >= ctx) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     {   // the latent tile, global -> LDS; one page lookup per tile; rows at or past ctx re-read row ctx - 1 (same tile, same page)
-        const size_t base = table ? layer_off + static_cast<size_t>(__builtin_amdgcn_readfirstlane(table[static_cast<size_t>(b) * max_pages + t0 / kPage])) * kPage * kRow
-                                  : layer_off + static_cast<size_t>(b) * max_seq_len * kRow;
+        const half_t *base = cache + layer_off + mla_tile_row0(table, max_pages, b, t0, max_seq_len) * kRow;
+        const int last = ctx - 1 - t0;   // >= 0
         half8_t lreg[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int id = tid + 256 * i, row = id >> 6, ch = id & 63;
-            const int t = min(t0 + row, ctx - 1);
-            lreg[i] = *reinterpret_cast<const half8_t *>(cache + base + static_cast<size_t>(table ? t % kPage : t) * kRow + ch * 8);
+            lreg[i] = *reinterpret_cast<const half8_t *>(base + min(row, last) * kRow + ch * 8);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -371,10 +322,9 @@ extern "C" int llmie_mla_kv_append_rows(const void *kv_a, const void *gamma, flo
     const int rc = plan_mla_prefill("mla_kv_append_rows", MlaPrefillCall{batch, 0, total_tokens, max_q_len, kv_span, max_seq_len, block_table != nullptr, max_pages, num_pages}, &p);
     if (rc != LLMIE_OK) return rc;
     LLMIE_REQUIRE(mis16(kv_a) == 0 && mis16(gamma) == 0 && mis16(cache) == 0, "mla_kv_append_rows: kv_a, gamma and the cache should be 16-byte aligned");
-    hipLaunchKernelGGL(mla_kv_append_rows_kernel, dim3(p.append_grid), dim3(64), 0, as_stream(stream), static_cast<const half_t *>(kv_a),
-                       static_cast<const half_t *>(gamma), eps, static_cast<const float2 *>(rope_table), static_cast<half_t *>(cache),
-                       mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), max_seq_len, cum_dev, hist_dev, batch, max_q_len,
-                       kv_span, block_table, max_pages);
+    mla_append_launch(MlaAppendCall{kv_a, gamma, eps, rope_table, cache, layer, batch, max_seq_len, nullptr, cum_dev, hist_dev, max_q_len, kv_span,
+                                    block_table, max_pages, num_pages},
+                      p.append_grid, as_stream(stream));
     return launch_status("mla_kv_append_rows");
 }
 
@@ -389,7 +339,7 @@ extern "C" int llmie_mla_kv_up(const void *cache, const void *kv_b, void *kv_up,
     LLMIE_REQUIRE(mis16(cache) == 0 && mis16(kv_b) == 0 && mis16(kv_up) == 0, "mla_kv_up: the cache, kv_b and kv_up should be 16-byte aligned");
     hipLaunchKernelGGL(mla_kv_up_kernel, dim3(p.up_grid[0], p.up_grid[1], p.up_grid[2]), dim3(256), 0, as_stream(stream),
                        static_cast<const half_t *>(cache), static_cast<const half_t *>(kv_b), static_cast<half_t *>(kv_up), cum_dev, hist_dev, block_table,
-                       max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), head_num, max_seq_len, max_q_len, kv_span);
+                       max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages, kRow), head_num, max_seq_len, max_q_len, kv_span);
     return launch_status("mla_kv_up");
 }
 
@@ -399,7 +349,7 @@ extern "C" int llmie_mla_prefill(const void *q, const void *kv_up, const void *c
                                  llmie_stream stream) {
     LLMIE_REQUIRE(q && kv_up && cache && rope_table && out && cum_dev && hist_dev, "mla_prefill: NULL operand");
     LLMIE_REQUIRE(layer >= 0 && total_tokens >= 1, "mla_prefill: layer=%d should be >= 0 and total_tokens=%d >= 1", layer, total_tokens);
-    LLMIE_REQUIRE(softmax_scale > 0.f && std::isfinite(softmax_scale), "mla_prefill: softmax_scale should be positive and finite");
+    LLMIE_REQUIRE(mla_scale_ok(softmax_scale), "mla_prefill: softmax_scale should be positive and finite");
     MlaPrefillPlan p{};
     const int rc = plan_mla_prefill("mla_prefill", MlaPrefillCall{batch, head_num, total_tokens, max_q_len, kv_span, max_seq_len, block_table != nullptr, max_pages, num_pages}, &p);
     if (rc != LLMIE_OK) return rc;
@@ -408,7 +358,7 @@ extern "C" int llmie_mla_prefill(const void *q, const void *kv_up, const void *c
     hipLaunchKernelGGL(mla_prefill_flash_kernel, dim3(p.flash_grid[0], p.flash_grid[1], p.flash_grid[2]), dim3(256), 0, as_stream(stream),
                        static_cast<const half_t *>(q), static_cast<const half_t *>(kv_up), static_cast<const half_t *>(cache),
                        static_cast<const float2 *>(rope_table), static_cast<half_t *>(out), cum_dev, hist_dev, block_table, max_pages,
-                       mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), head_num, max_seq_len, max_q_len, kv_span,
-                       softmax_scale * 1.44269504088896341f);
+                       mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages, kRow), head_num, max_seq_len, max_q_len, kv_span,
+                       softmax_scale * kLog2e);
     return launch_status("mla_prefill");
 }

@@ -3,10 +3,10 @@
 // already in the cache at slots hist + i; row i sees every key t < hist and the nodes hist + j whose bit j is set in its ancestor mask
 // (the convention of llmie_decoder_set_tree; no mask array = the chain).  Two launches:
 //   mla_verify_kernel        split-KV flash attention, 16 heads x kVerRows query rows = 64 MFMA columns per workgroup   (the hot path)
-//   mla_verify_merge_kernel  fixed-order merge of the split partials (only with more than one split)
+//   mla_merge_kernel         (mla.hip, mla_merge_launch) fixed-order merge of the split partials (only with more than one split)
 //
 // mla_verify_kernel.  Grid (splits, head_num / 16, batch x ceil(rows / kVerRows)), 4 waves, one workgroup per CU on the unified
-// 512-register file.  A workgroup walks one chunk of kVerChunk tokens of ONE sequence in tiles of 32 keys for a block of kVerRows query
+// 512-register file.  A workgroup walks one chunk of kMlaChunk tokens of ONE sequence in tiles of 32 keys for a block of kVerRows query
 // rows: a tile (32 rows x 576 halves, rows padded to 592) goes global -> registers -> LDS ONCE for all of them, two buffers, tile t + 1
 // published while tile t is multiplied and tile t + 2 in flight in registers -- the staging of mla_decode_kernel.  What differs is
 // what a staged fragment feeds.  Column block cb = query row kVerRows rb + cb, column r of it = head 16 hb + r:
@@ -26,44 +26,31 @@
 // on nothing but its own q row, mask and the tiles: a row's bits do not depend on the batch, its slot, the grid or its neighbours.
 #include "mla_common.cuh"
 
-#include <cmath>
-
 namespace llmie {
 
 namespace {
 
-constexpr int kVerHeads = 16, kVerRows = 4, kVerCols = kVerHeads * kVerRows, kVerTile = 32, kVerChunk = 256, kVerStride = kRow + 16;
-constexpr int kVerMergeBlock = 128;
-static_assert(kPage % kVerTile == 0 && kVerChunk % kVerTile == 0, "a tile never crosses a page or a chunk");
-static_assert((kVerStride * 2) % 64 == 32, "row stride = an odd multiple of 32 bytes: conflict-free transposed reads");
+constexpr int kVerRows = 4, kVerCols = kMlaHeads * kVerRows;   // heads, tile, chunk and the padded LDS row are the decode kernel's
 static_assert(kVerRows >= 2 && LLMIE_SPEC_TREE_MAX_NODES <= 64, "at least two column blocks per fragment; the mask is one uint64");
-
-// the sequence's extent, or false where the call leaves it untouched
-__device__ __forceinline__ bool verify_live(const int32_t *__restrict__ hist_dev, const int32_t *__restrict__ count_dev, int b, int rows, int span,
-                                            int *hist, int *count) {
-    *hist = hist_dev[b];
-    *count = count_dev ? count_dev[b] : rows;
-    return *hist >= 0 && *count >= 1 && *count <= rows && *hist <= span - *count;
-}
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void mla_verify_kernel(
     const half_t *__restrict__ q_lat, const half_t *__restrict__ cache, half_t *__restrict__ o_lat, float *__restrict__ ws_o,
     float2 *__restrict__ ws_ml, const int32_t *__restrict__ hist_dev, const int32_t *__restrict__ count_dev, const uint64_t *__restrict__ anc,
     const int32_t *__restrict__ table, int max_pages, size_t layer_off, int rows, int row_blocks, int head_num, int max_seq_len, int span,
     float scale2 /* softmax_scale * log2(e) */) {
-    __shared__ __attribute__((aligned(16))) half_t Ts[2][kVerTile * kVerStride];   // 2 x 37888 bytes
+    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes
     __shared__ __attribute__((aligned(16))) float Sp[2 * 8 * kVerCols * 4];          // partial logits [kk][key / 4][column][key % 4]
     const int split = blockIdx.x, hb = blockIdx.y, b = blockIdx.z / row_blocks, rb = blockIdx.z - b * row_blocks, splits = gridDim.x;
     int hist, count;
     if (!verify_live(hist_dev, count_dev, b, rows, span, &hist, &count)) return;
     const int row0 = rb * kVerRows, ctx = hist + count;
     if (row0 >= count) return;
-    const int t_begin = split * kVerChunk;
+    const int t_begin = split * kMlaChunk;
     if (t_begin >= ctx) return;
-    const int n_tiles = (min(ctx, t_begin + kVerChunk) - t_begin + kVerTile - 1) / kVerTile;
+    const int n_tiles = (min(ctx, t_begin + kMlaChunk) - t_begin + kMlaTile - 1) / kMlaTile;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int kh = wave & 1, kk = wave >> 1;
-    const int head = hb * kVerHeads + r;
+    const int head = hb * kMlaHeads + r;
 
     half8_t qf[kVerRows][9];      // Q[row cb][head r][288 kk + 32 s + 8 q ..]: the B operands of this wave's 9 steps
     uint64_t vis[kVerRows];       // bit j: row cb sees node j (wave-uniform)
@@ -83,19 +70,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     half8_t treg[NCH];
     const int srow = 8 * wave, xrow = srow + (lane >> 3), xch = 64 + (lane & 7);
     auto fetch_tile = [&](int t0) {   // global -> registers; one page lookup per tile, wave-uniform
-        const size_t base = table ? layer_off + static_cast<size_t>(__builtin_amdgcn_readfirstlane(table[static_cast<size_t>(b) * max_pages + t0 / kPage])) * kPage * kRow
-                                  : layer_off + static_cast<size_t>(b) * max_seq_len * kRow;
-        const half_t *src = cache + base;
-        const int p0 = table ? t0 % kPage : t0, last = ctx - 1 - t0;   // (0 <= last; last < 32 where the clamp acts: same tile, same page)
+        const half_t *src = cache + layer_off + mla_tile_row0(table, max_pages, b, t0, max_seq_len) * kRow;
+        const int last = ctx - 1 - t0;   // (0 <= last; last < 32 where the clamp acts: same tile, same page)
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            treg[i] = *reinterpret_cast<const half8_t *>(src + static_cast<size_t>(p0 + min(srow + i, last)) * kRow + lane * 8);
-        treg[8] = *reinterpret_cast<const half8_t *>(src + static_cast<size_t>(p0 + min(xrow, last)) * kRow + xch * 8);
+            treg[i] = *reinterpret_cast<const half8_t *>(src + static_cast<size_t>(min(srow + i, last)) * kRow + lane * 8);
+        treg[8] = *reinterpret_cast<const half8_t *>(src + static_cast<size_t>(min(xrow, last)) * kRow + xch * 8);
     };
     auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<half8_t *>(Ts[buf] + (srow + i) * kVerStride + lane * 8) = treg[i];
-        *reinterpret_cast<half8_t *>(Ts[buf] + xrow * kVerStride + xch * 8) = treg[8];
+        for (int i = 0; i < 8; ++i) *reinterpret_cast<half8_t *>(Ts[buf] + (srow + i) * kMlaStride + lane * 8) = treg[i];
+        *reinterpret_cast<half8_t *>(Ts[buf] + xrow * kMlaStride + xch * 8) = treg[8];
     };
 
     floatx4 o[kVerRows][8];   // O^T: dims 128 wave + 16 dt + 4 q + e, column = (row cb, head r)
@@ -109,20 +94,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     fetch_tile(t_begin);
     publish_tile(0);
-    if (1 < n_tiles) fetch_tile(t_begin + kVerTile);
+    if (1 < n_tiles) fetch_tile(t_begin + kMlaTile);
     for (int it = 0; it < n_tiles; ++it) {
-        const int t0 = t_begin + it * kVerTile;
+        const int t0 = t_begin + it * kMlaTile;
         const half_t *Tt = Ts[it & 1];
         __syncthreads();   // tile `it` published; every wave done with tile it - 1 (the other buffer) and with its logits
         if (it + 1 < n_tiles) {
             publish_tile((it + 1) & 1);
-            if (it + 2 < n_tiles) fetch_tile(t0 + 2 * kVerTile);   // in flight under this iteration's MFMAs
+            if (it + 2 < n_tiles) fetch_tile(t0 + 2 * kMlaTile);   // in flight under this iteration's MFMAs
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- S^T partial: keys 16 kh + r, dims 288 kk ..; one K fragment, kVerRows column blocks ----
         {
             half8_t kf[9];
-            const half_t *kp = Tt + (16 * kh + r) * kVerStride + 288 * kk + 8 * q;
+            const half_t *kp = Tt + (16 * kh + r) * kMlaStride + 288 * kk + 8 * q;
 #pragma unroll
             for (int s = 0; s < 9; ++s) kf[s] = *reinterpret_cast<const half8_t *>(kp + 32 * s);
             floatx4 sacc[kVerRows];
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         __syncthreads();   // both halves of every logit are there
         __builtin_amdgcn_sched_barrier(0);
-        const bool masked = t0 + kVerTile > hist;   // wave-uniform: the tile holds a node, or rows past ctx
+        const bool masked = t0 + kMlaTile > hist;   // wave-uniform: the tile holds a node, or rows past ctx
         half8_t pf[kVerRows];
 #pragma unroll
         for (int cb = 0; cb < kVerRows; ++cb) {
@@ -189,14 +174,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // ---- O^T += C^T . P^T: A fragment = C[key(q, j)][128 wave + 16 dt + r], gathered down a column by the transposed read; one
         // gather, kVerRows column blocks ----
         {
-            const half_t *blk = Tt + (4 * q + (r >> 2)) * kVerStride + 128 * wave + 4 * (r & 3);
+            const half_t *blk = Tt + (4 * q + (r >> 2)) * kMlaStride + 128 * wave + 4 * (r & 3);
 #pragma unroll
             for (int d0 = 0; d0 < 8; d0 += 4) {   // in two halves: 16 fragment registers in flight, not 32
                 fp16x4_t lo[4], hi[4];
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     lo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + (d0 + dt) * 16));
-                    hi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * kVerStride + (d0 + dt) * 16));
+                    hi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * kMlaStride + (d0 + dt) * 16));
                 }
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
@@ -213,6 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run[cb]));
         if (row0 + cb >= count) continue;   // (wave-uniform) a row past the count: nothing is written
         const size_t bh = (static_cast<size_t>(b) * rows + row0 + cb) * head_num + head;
+        // mla_store_split written out: called here, the helper costs this 512-register kernel three VGPRs spilled to scratch
         if (splits == 1) {   // the only split: the output itself (the self bit: l > 0)
             const float inv = 1.f / l;
             half_t *op = o_lat + bh * kLat + 128 * wave + 4 * q;
@@ -231,38 +217,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
-// merge: grid (head_num, batch x rows), 128 threads x 4 dims.  Splits 0 .. ceil(ctx / chunk) - 1 in that order: M = max m_i,
-// w_i = 2^(m_i - M), L = sum w_i l_i, out = (sum w_i o_i) / L.  A partial that saw nothing (m = -inf, l = 0, o = 0) has weight 0; the
-// split that holds the row's own node is finite, so M is.  One partial gives the bits of the one-split launch (w = 1).
-__global__ __launch_bounds__(kVerMergeBlock) void mla_verify_merge_kernel(const float *__restrict__ ws_o, const float2 *__restrict__ ws_ml,
-                                                                          half_t *__restrict__ o_lat, const int32_t *__restrict__ hist_dev,
-                                                                          const int32_t *__restrict__ count_dev, int rows, int head_num, int span,
-                                                                          int splits) {
-    const int h = blockIdx.x, b = blockIdx.y / rows, i = blockIdx.y - b * rows, tid = threadIdx.x;
-    int hist, count;
-    if (!verify_live(hist_dev, count_dev, b, rows, span, &hist, &count) || i >= count) return;
-    const int n = (hist + count + kVerChunk - 1) / kVerChunk;   // <= splits (ctx <= span)
-    const size_t bh = (static_cast<size_t>(b) * rows + i) * head_num + h;
-    float M = -INFINITY;
-    for (int s = 0; s < n; ++s) M = fmaxf(M, ws_ml[bh * splits + s].x);
-    float L = 0.f;
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < n; ++s) {
-        const float2 ml = ws_ml[bh * splits + s];
-        const float w = __builtin_amdgcn_exp2f(ml.x - M);
-        L = __builtin_fmaf(w, ml.y, L);
-        const floatx4 v = *reinterpret_cast<const floatx4 *>(ws_o + (bh * splits + s) * kLat + 4 * tid);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(w, v[e], acc[e]);
-    }
-    const float inv = 1.f / L;
-    const half4_t v = {from_f32<half_t>(acc[0] * inv), from_f32<half_t>(acc[1] * inv), from_f32<half_t>(acc[2] * inv),
-                       from_f32<half_t>(acc[3] * inv)};
-    *reinterpret_cast<half4_t *>(o_lat + bh * kLat + 4 * tid) = v;
-}
-
 size_t verify_workspace(int batch, int rows, int head_num, int span) {
-    const int splits = (span + kVerChunk - 1) / kVerChunk;
+    const int splits = (span + kMlaChunk - 1) / kMlaChunk;
     return splits > 1 ? static_cast<size_t>(batch) * rows * head_num * splits * (kLat + 2) * sizeof(float) : 0;
 }
 
@@ -279,18 +235,18 @@ int plan_mla_verify(const char *who, const MlaVerifyCall &c, MlaVerifyPlan *p) {
                           LLMIE_SPEC_TREE_MAX_NODES);
     LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
                   who, c.max_ctx, c.max_seq_len);
-    p->heads = kVerHeads, p->rows = kVerRows, p->tile = kVerTile, p->chunk = kVerChunk;
+    p->heads = kMlaHeads, p->rows = kVerRows, p->tile = kMlaTile, p->chunk = kMlaChunk;
     p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
     p->row_blocks = (c.rows + kVerRows - 1) / kVerRows;
     LLMIE_REQUIRE(static_cast<long long>(c.batch) * p->row_blocks <= 65535 && static_cast<long long>(c.batch) * c.rows <= 65535,
                   "%s: batch=%d x rows=%d does not fit one launch (batch x rows <= 65535)", who, c.batch, c.rows);
-    p->grid[0] = (p->span + kVerChunk - 1) / kVerChunk, p->grid[1] = c.head_num / kVerHeads, p->grid[2] = c.batch * p->row_blocks;
+    p->grid[0] = (p->span + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch * p->row_blocks;
     p->merge = p->grid[0] > 1;
-    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch * c.rows, p->merge_block = kVerMergeBlock;
+    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch * c.rows, p->merge_block = kMlaMergeBlock;
     p->workspace_bytes = verify_workspace(c.batch, c.rows, c.head_num, p->span);
     if (p->workspace_bytes > 0 && (!c.workspace || c.workspace_bytes < p->workspace_bytes)) {
         set_error("%s: workspace of %zu bytes, %d rows x %d splits of %d tokens need %zu (llmie_mla_verify_workspace_bytes)", who,
-                  c.workspace ? c.workspace_bytes : static_cast<size_t>(0), c.rows, p->grid[0], kVerChunk, p->workspace_bytes);
+                  c.workspace ? c.workspace_bytes : static_cast<size_t>(0), c.rows, p->grid[0], kMlaChunk, p->workspace_bytes);
         return LLMIE_ERR_WORKSPACE;
     }
     return LLMIE_OK;
@@ -327,7 +283,7 @@ extern "C" int llmie_mla_verify(const void *q_lat, const void *cache, void *o_la
                                 llmie_stream stream) {
     LLMIE_REQUIRE(q_lat && cache && o_lat && hist_dev, "mla_verify: NULL operand");
     LLMIE_REQUIRE(layer >= 0, "mla_verify: layer=%d should be >= 0", layer);
-    LLMIE_REQUIRE(softmax_scale > 0.f && std::isfinite(softmax_scale), "mla_verify: softmax_scale should be positive and finite");
+    LLMIE_REQUIRE(mla_scale_ok(softmax_scale), "mla_verify: softmax_scale should be positive and finite");
     MlaVerifyPlan p{};
     const MlaVerifyCall c{batch, rows, head_num, max_seq_len, max_ctx, anc_dev != nullptr, block_table != nullptr, max_pages, num_pages,
                           workspace != nullptr, workspace_bytes};
@@ -339,10 +295,9 @@ extern "C" int llmie_mla_verify(const void *q_lat, const void *cache, void *o_la
     float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(batch) * rows * head_num * p.grid[0] * kLat) : nullptr;
     hipLaunchKernelGGL(mla_verify_kernel, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, as_stream(stream),
                        static_cast<const half_t *>(q_lat), static_cast<const half_t *>(cache), static_cast<half_t *>(o_lat), ws_o, ws_ml, hist_dev,
-                       count_dev, anc_dev, block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages), rows,
-                       p.row_blocks, head_num, max_seq_len, p.span, softmax_scale * 1.44269504088896341f);
+                       count_dev, anc_dev, block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages, kRow), rows,
+                       p.row_blocks, head_num, max_seq_len, p.span, softmax_scale * kLog2e);
     if (p.merge)
-        hipLaunchKernelGGL(mla_verify_merge_kernel, dim3(p.merge_grid[0], p.merge_grid[1]), dim3(p.merge_block), 0, as_stream(stream), ws_o, ws_ml,
-                           static_cast<half_t *>(o_lat), hist_dev, count_dev, rows, head_num, p.span, p.grid[0]);
+        mla_merge_launch(p.merge_grid, p.span, p.grid[0], ws_o, ws_ml, static_cast<half_t *>(o_lat), hist_dev, count_dev, rows, head_num, as_stream(stream));
     return launch_status("mla_verify");
 }
