@@ -531,6 +531,54 @@ int llmie_mla_cache_dequant_e4m3(const void *cache_e4m3, void *cache_f16, float 
                                  const int32_t *ctx_len_dev, const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages,
                                  llmie_stream stream);
 
+/* ABI 3 (an addition).  MLA SPARSE decode (DeepSeek-V3.2, "DeepSeek Sparse Attention"): the latent cache stays as it is, a decode
+ * step attends over the top_k cached tokens that a small indexer scores best.  Two operations on top of llmie_mla_kv_append / _q_absorb /
+ * _out_project; the fp16 latent cache only.
+ *   index cache   fp16, LLMIE_MLA_INDEX_DIM = 128 halves per token with the geometry of the latent cache: dense [layers, batch,
+ *                 max_seq_len, 128], or paged [layers, num_pages * 128, 128] under the SAME block_table and the 128-token page.  The
+ *                 caller writes its rows (an append kernel is not part of the library yet).
+ *   q_idx [batch, 64, 128] fp16, already rotated; w_idx [batch, 64] fp32, the model's scale factors already folded in.
+ * llmie_mla_index_topk: the index logit of position t, I_t = sum_h w_h * max(q_idx_h . k_idx_t, 0) over the LLMIE_MLA_INDEX_HEADS = 64
+ *   heads, fp16 products accumulated in fp32, and the exact top_k of it.  sel[b, 0 .. count - 1] = the selected positions in STRICTLY
+ *   ASCENDING order, the other slots of the top_k hold -1; sel_count[b] = count = min(ctx_len[b], top_k).  ctx_len[b] <= top_k: sel is
+ *   0 .. ctx - 1 and no logit is computed.  Otherwise the top_k largest I_t; NaN ranks below every number, -0 = +0, and ties at the
+ *   threshold go to the LOWER positions.  The summation order of a logit is fixed and does not depend on where the key sits --
+ *   v = max(d_r, 0) w_r, then v = fma(max(d_{16 c + r}, 0), w_{16 c + r}, v) for c = 1, 2, 3 (d_h the MFMA dot of head h), then
+ *   v += v[r ^ d] over d = 8, 4, 2, 1 --, so EQUAL KEY ROWS GIVE EQUAL LOGIT BITS and a row of a batch has the selection of its batch-1
+ *   call.  A sequence with ctx_len[b] outside [1, max_ctx ? max_ctx : max_seq_len] keeps its sel row and gets sel_count[b] = 0.
+ *   logits_out (nullable, for tests and debugging): [batch, span], span = max_ctx ? max_ctx : max_seq_len; receives I_t of every
+ *   t < ctx_len[b] of the sequences with ctx_len[b] > top_k, nothing else.  workspace: at least llmie_mla_index_topk_workspace_bytes(
+ *   batch, span) bytes (fp32 logits, rows padded to 256), 16-byte aligned; none is needed where span <= top_k.  No global atomics;
+ *   results repeat bit for bit.  One workgroup selects a whole sequence: at batch 1 and very long contexts that launch dominates.
+ * llmie_mla_decode_sparse: llmie_mla_decode over the rows sel[b, j], j < count_b = min(sel_count[b], top_k), instead of t < ctx_len[b]:
+ *   o_lat[b, h] = sum_j softmax_j(softmax_scale * q_lat . row_{sel_j}[0:576]) row_{sel_j}[0:512], PLAIN softmax, the splits cut the
+ *   ENTRIES into chunks of 256 that depend on count_b alone.  With sel = 0 .. ctx - 1 the result has the bits of llmie_mla_decode; a row
+ *   of a batch has the bits of its batch-1 call.  A sequence is live when ctx_len[b] is in [1, max_seq_len] and count_b >= 1; otherwise
+ *   its o_lat row is untouched.  Every entry is clamped into [0, ctx_len[b] - 1] before it addresses the cache: an entry inside count_b
+ *   that is negative or >= ctx_len[b] is the caller's error, it attends the clamped row and nothing faults; so is sel_count[b] > top_k
+ *   (clamped for the reads, the row's result is then undefined).  workspace: llmie_mla_decode_workspace_bytes(batch, head_num, top_k),
+ *   16-byte aligned (0 bytes, NULL allowed, with top_k <= 256).  A layer of more than 2^31 - 1 cache rows is LLMIE_ERR_UNSUPPORTED.
+ * The _plan entries: host only, one line each (the entry calls the same planner), NULL for a call the entry refuses:
+ *   "mla_index f16 ih64 id128 keys64 topk2048 grid 512x2 select 2x1024" -- index heads, dims, keys per workgroup, the logits grid (key
+ *   blocks, batch) or "none" where span <= top_k, the select grid x block;
+ *   "mla_sparse f16 nh128 hb16 tile32 chunk256 topk2048 grid 8x8x2 merge 128x2/128" -- as llmie_mla_decode_plan, the splits from top_k. */
+#define LLMIE_MLA_INDEX_HEADS 64
+#define LLMIE_MLA_INDEX_DIM 128
+#define LLMIE_MLA_SPARSE_MAX_TOPK 4096
+size_t llmie_mla_index_topk_workspace_bytes(int batch, int max_seq_len);
+int llmie_mla_index_topk(const void *q_idx, const float *w_idx, const void *k_idx_cache, int32_t *sel /* [batch, top_k] */,
+                         int32_t *sel_count /* [batch] */, float *logits_out /* nullable: [batch, span] */, int layer, int batch, int top_k,
+                         int max_seq_len, int max_ctx, const int32_t *ctx_len_dev, void *workspace, size_t workspace_bytes,
+                         const int32_t *block_table /* nullable: dense */, int max_pages, int num_pages, llmie_stream stream);
+const char *llmie_mla_index_topk_plan(int batch, int top_k, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,
+                                      long long workspace_bytes, int *status);
+int llmie_mla_decode_sparse(const void *q_lat, const void *cache, void *o_lat, const int32_t *sel, const int32_t *sel_count, int layer,
+                            int batch, int head_num, int top_k, int max_seq_len, const int32_t *ctx_len_dev, float softmax_scale,
+                            void *workspace, size_t workspace_bytes, const int32_t *block_table /* nullable: dense */, int max_pages,
+                            int num_pages, llmie_stream stream);
+const char *llmie_mla_decode_sparse_plan(int batch, int head_num, int top_k, int max_seq_len, int paged, int max_pages, int num_pages,
+                                         long long workspace_bytes, int *status);
+
 /* ABI 3 (an addition).  The page ring of windowed sequences over a paged cache: one launch, nothing read by the host, so a captured
  * decode loop replays it.  For every sequence b and every logical page that the positions [cached_len[b], cached_len[b] + n) need
  * (n = new_tokens[b], or 1 with new_tokens = NULL) and whose block-table entry is unmapped (-1), it takes the pool page of the

@@ -191,6 +191,11 @@ _SIGS = {
     "llmie_mla_decode_e4m3": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp, _i, _i, _f, _vp],
     "llmie_mla_decode_e4m3_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
     "llmie_mla_cache_dequant_e4m3": [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp],
+    "llmie_mla_index_topk_workspace_bytes": [_i, _i],
+    "llmie_mla_index_topk": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _i, _vp],
+    "llmie_mla_index_topk_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
+    "llmie_mla_decode_sparse": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp, _i, _i, _vp],
+    "llmie_mla_decode_sparse_plan": [_i, _i, _i, _i, _i, _i, _i, C.c_longlong, _vp],
     "llmie_abi_version": [],
     "llmie_last_error": [],
     "llmie_target_arch": [],
@@ -223,6 +228,9 @@ _RESTYPES = {
     "llmie_mla_verify_workspace_bytes": _sz,
     "llmie_mla_verify_plan": C.c_char_p,
     "llmie_mla_decode_e4m3_plan": C.c_char_p,
+    "llmie_mla_index_topk_workspace_bytes": _sz,
+    "llmie_mla_index_topk_plan": C.c_char_p,
+    "llmie_mla_decode_sparse_plan": C.c_char_p,
     "llmie_decoder_moe_workspace_bytes": _sz,
     "llmie_moe_ffn_plan": C.c_char_p,
     "llmie_moe_ffn_plan_ex": C.c_char_p,
@@ -650,6 +658,73 @@ def mla_cache_dequant_e4m3(cache_e4m3, cache_f16, c_scale, layer, ctx_len, block
                                               dense_len if block_table is None else max_seq_len, max_ctx, _p(ctx_len), _p(block_table),
                                               max_pages, num_pages, _st()), "mla_cache_dequant_e4m3")
     return cache_f16
+
+
+# MLA sparse decode (include/llmie.h llmie_mla_index_topk / llmie_mla_decode_sparse; DeepSeek-V3.2): the indexer picks top_k cached
+# tokens per sequence, the attention runs over them.  Index cache: fp16 [L, batch, S, 128], or paged [L, pages * 128, 128] under the
+# latent cache's block_table (max_seq_len given)
+MLA_INDEX_HEADS, MLA_INDEX_DIM, MLA_SPARSE_MAX_TOPK = 64, 128, 4096
+
+
+def _mla_index_cache(cache, block_table):
+    """(max_seq_len or None, max_pages, num_pages) of a dense [L, batch, S, 128] / paged [L, pages * 128, 128] index key cache"""
+    assert cache.shape[-1] == MLA_INDEX_DIM, "index key cache: [layers, batch, max_seq_len, 128] or [layers, pages * 128, 128]"
+    if block_table is None:
+        assert cache.dim() == 4
+        return cache.shape[2], 0, 0
+    assert cache.dim() == 3 and cache.shape[1] % MLA_PAGE == 0, "paged index key cache: pages of 128 tokens"
+    return None, block_table.shape[1], cache.shape[1] // MLA_PAGE
+
+
+def mla_index_topk_plan(batch, top_k, max_seq_len, max_ctx=0, paged=False, max_pages=0, num_pages=0, workspace_bytes="exact"):
+    """(plan text or None, status) of llmie_mla_index_topk's launches: e.g. "mla_index f16 ih64 id128 keys64 topk2048 grid 512x2 select
+    2x1024" (logits grid or "none", select grid x block); workspace_bytes: a size, None (no workspace) or "exact".  No device needed."""
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_mla_index_topk_workspace_bytes(batch, max_ctx if max_ctx > 0 else max_seq_len)
+    status = C.c_int(0)
+    t = lib().llmie_mla_index_topk_plan(batch, top_k, max_seq_len, max_ctx, int(paged), max_pages, num_pages,
+                                        -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_index_workspace(batch, max_seq_len, device="cuda"):
+    """uint8 scratch for mla_index_topk's fp32 logits"""
+    import torch
+    return torch.empty(max(lib().llmie_mla_index_topk_workspace_bytes(batch, max_seq_len), 16), dtype=torch.uint8, device=device)
+
+
+def mla_index_topk(q_idx, w_idx, k_idx_cache, layer, ctx_len, sel, sel_count, workspace=None, logits_out=None, block_table=None,
+                   max_seq_len=None, max_ctx=0):
+    """sel [batch, top_k] int32 <- the top_k positions of largest sum_h w_idx[b, h] relu(q_idx[b, h] . k_idx[t]), ascending, -1 behind
+    them; sel_count [batch] <- min(ctx_len, top_k).  logits_out: fp32 [batch, max_ctx or max_seq_len], or None"""
+    dense_len, max_pages, num_pages = _mla_index_cache(k_idx_cache, block_table)
+    _check(lib().llmie_mla_index_topk(_p(q_idx), _p(w_idx), _p(k_idx_cache), _p(sel), _p(sel_count), _p(logits_out), layer, sel.shape[0],
+                                      sel.shape[1], dense_len if block_table is None else max_seq_len, max_ctx, _p(ctx_len), _p(workspace),
+                                      workspace.numel() * workspace.element_size() if workspace is not None else 0, _p(block_table),
+                                      max_pages, num_pages, _st()), "mla_index_topk")
+    return sel, sel_count
+
+
+def mla_decode_sparse_plan(batch, head_num, top_k, max_seq_len, paged=False, max_pages=0, num_pages=0, workspace_bytes="exact"):
+    """(plan text or None, status) of llmie_mla_decode_sparse's launch: e.g. "mla_sparse f16 nh128 hb16 tile32 chunk256 topk2048 grid
+    8x8x2 merge 128x2/128"; workspace_bytes as for mla_decode_plan (the size is mla_workspace(batch, head_num, top_k)'s)"""
+    if workspace_bytes == "exact":
+        workspace_bytes = lib().llmie_mla_decode_workspace_bytes(batch, head_num, top_k)
+    status = C.c_int(0)
+    t = lib().llmie_mla_decode_sparse_plan(batch, head_num, top_k, max_seq_len, int(paged), max_pages, num_pages,
+                                           -1 if workspace_bytes is None else workspace_bytes, C.addressof(status))
+    return (t.decode() if t is not None else None), status.value
+
+
+def mla_decode_sparse(q_lat, cache, layer, ctx_len, sel, sel_count, softmax_scale, o_lat, workspace=None, block_table=None, max_seq_len=None):
+    """o_lat [batch, heads, 512] <- plain softmax attention of q_lat over the latent cache rows sel[b, j], j < sel_count[b]
+    (workspace: mla_workspace(batch, heads, top_k))"""
+    dense_len, max_pages, num_pages = _mla_cache(cache, block_table)
+    _check(lib().llmie_mla_decode_sparse(_p(q_lat), _p(cache), _p(o_lat), _p(sel), _p(sel_count), layer, q_lat.shape[0], q_lat.shape[1],
+                                         sel.shape[1], dense_len if block_table is None else max_seq_len, _p(ctx_len), softmax_scale,
+                                         _p(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                         _p(block_table), max_pages, num_pages, _st()), "mla_decode_sparse")
+    return o_lat
 
 
 def decoder_plan_name(cfg, prefill, rows, call_flags=0, switch_mask=0):

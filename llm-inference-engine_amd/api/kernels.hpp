@@ -608,6 +608,32 @@ inline void launchMlaOutProject(TensorWrapper<half> *o_lat, TensorWrapper<half> 
     LLM_CHECK_WITH_INFO(out->shape[0] == o_lat->shape[0] && out->shape[1] == o_lat->shape[1] * LLMIE_MLA_V_HEAD_DIM, "out should be [batch, head_num * 128]");
     LLMIE_CALL(llmie_mla_out_project(o_lat->data, kv_b->data, out->data, o_lat->shape[0], o_lat->shape[1], llmie_api::st()));
 }
+// MLA sparse decode (llmie_mla_index_topk / llmie_mla_decode_sparse; DeepSeek-V3.2): q_idx [batch, 64, 128] (rotated), w_idx [batch, 64]
+// fp32, k_idx the index key cache [L, batch, max_seq_len, 128] -- or [L, num_pages * 128, 128] under the latent cache's block_table --,
+// sel [batch, top_k] / sel_count [batch] the selection: ascending positions, -1 behind them.  Then the attention over those rows.
+inline void launchMlaIndexTopk(TensorWrapper<half> *q_idx, TensorWrapper<float> *w_idx, TensorWrapper<half> *k_idx, int layer, TensorWrapper<int> *ctx_len,
+                               TensorWrapper<int> *sel, TensorWrapper<int> *sel_count, TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0,
+                               int max_ctx = 0) {
+    LLM_CHECK_WITH_INFO(q_idx->shape[1] == LLMIE_MLA_INDEX_HEADS && q_idx->shape[2] == LLMIE_MLA_INDEX_DIM && k_idx->shape.back() == LLMIE_MLA_INDEX_DIM,
+                        "q_idx should be [batch, 64, 128], the index key cache [.., 128]");
+    const int batch = sel->shape[0];
+    if (!block_table) max_seq_len = k_idx->shape[2];
+    const size_t ws = llmie_mla_index_topk_workspace_bytes(batch, max_ctx > 0 ? max_ctx : max_seq_len);
+    LLMIE_CALL(llmie_mla_index_topk(q_idx->data, w_idx->data, k_idx->data, sel->data, sel_count->data, nullptr, layer, batch, sel->shape[1], max_seq_len,
+                                    max_ctx, ctx_len->data, llmie_api::scratch(ws), ws, block_table ? block_table->data : nullptr,
+                                    block_table ? block_table->shape[1] : 0, block_table ? k_idx->shape[1] / LLMIE_MLA_PAGE_TOKENS : 0, llmie_api::st()));
+}
+inline void launchMlaDecodeSparse(TensorWrapper<half> *q_lat, TensorWrapper<half> *cache, int layer, TensorWrapper<int> *ctx_len, TensorWrapper<int> *sel,
+                                  TensorWrapper<int> *sel_count, float softmax_scale, TensorWrapper<half> *o_lat,
+                                  TensorWrapper<int> *block_table = nullptr, int max_seq_len = 0) {
+    const int batch = q_lat->shape[0], head_num = q_lat->shape[1], top_k = sel->shape[1];
+    if (!block_table) max_seq_len = cache->shape[2];
+    const size_t ws = llmie_mla_decode_workspace_bytes(batch, head_num, top_k);
+    LLMIE_CALL(llmie_mla_decode_sparse(q_lat->data, cache->data, o_lat->data, sel->data, sel_count->data, layer, batch, head_num, top_k, max_seq_len,
+                                       ctx_len->data, softmax_scale, ws ? llmie_api::scratch(ws) : nullptr, ws,
+                                       block_table ? block_table->data : nullptr, block_table ? block_table->shape[1] : 0,
+                                       block_table ? cache->shape[1] : 0, llmie_api::st()));
+}
 // MLA verify (llmie_mla_verify): q_lat [batch, rows, head_num, 576] -> o_lat [batch, rows, head_num, 512]; hist [batch] = tokens cached in
 // front of the nodes, count [batch] (nullable: rows each) = nodes per sequence, anc (nullable: the chain) = device uint64 [batch, rows]
 // ancestor masks as llmie_spec_tree_prepare leaves them.  The nodes' rows are in the cache already (launchMlaKvAppendRows for a chain);

@@ -21,7 +21,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 # per-source additions: the MLA kernels are compiled without the packed fp32 VALU forms (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32)
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"mla.hip": NO_PK_F32, "mla_prefill.hip": NO_PK_F32, "mla_verify.hip": NO_PK_F32, "mla_e4m3.hip": NO_PK_F32}
+EXTRA_FLAGS = {"mla.hip": NO_PK_F32, "mla_prefill.hip": NO_PK_F32, "mla_verify.hip": NO_PK_F32, "mla_e4m3.hip": NO_PK_F32,
+               "mla_sparse.hip": NO_PK_F32}
 
 
 def _sources():

@@ -376,6 +376,40 @@ struct MlaAppendCall {
     float c_scale;
 };
 void mla_append_launch(const MlaAppendCall &a, int tokens, hipStream_t st);
+// ---- MLA sparse decode (mla_sparse.hip): the indexer's top-k selection and the gathered split-KV attention; one planner per entry ----
+struct MlaIndexCall {
+    int batch, top_k, max_seq_len;
+    int max_ctx;                       // host bound of the context lengths, 0: only the device knows them
+    bool paged;
+    int max_pages, num_pages;
+    bool workspace;
+    size_t workspace_bytes;
+};
+struct MlaIndexPlan {
+    int keys;                          // keys per workgroup of mla_index_logits_kernel
+    int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
+    size_t pitch;                      // fp32 logits per workspace row: span padded to 256
+    bool logits;                       // span > top_k: some selection may need logits (else only the select kernel runs)
+    int grid[2];                       // (key blocks, batch)
+    int select_grid, select_block;     // one workgroup per sequence
+    size_t workspace_bytes;            // the logits (0 where none are needed)
+};
+int plan_mla_index_topk(const char *who, const MlaIndexCall &c, MlaIndexPlan *p);   // sets the refusal's error text, returns its error code
+struct MlaSparseCall {
+    int batch, head_num, top_k, max_seq_len;
+    bool paged;
+    int max_pages, num_pages;
+    bool workspace;
+    size_t workspace_bytes;
+};
+struct MlaSparsePlan {
+    int heads, tile, chunk;            // query heads per workgroup, rows per staged tile, selected entries per split
+    int grid[3];                       // (splits of top_k, head blocks, batch)
+    bool merge;                        // more than one split: mla_merge_kernel follows, sel_count is its length array
+    int merge_grid[2], merge_block;
+    size_t workspace_bytes;            // the split partials (0 with one split)
+};
+int plan_mla_decode_sparse(const char *who, const MlaSparseCall &c, MlaSparsePlan *p);   // sets the refusal's error text, returns its error code
 // ---- MLA verify attention (mla_verify.hip): several query rows per sequence on the latent cache; the pattern of plan_mla_decode ----
 struct MlaVerifyCall {
     int batch, rows, head_num, max_seq_len;   // rows: query-row slots per sequence (a chain's length, a tree's stride)

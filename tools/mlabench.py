@@ -27,6 +27,14 @@ With --e4m3 the e4m3 latent cache (640 bytes per token) follows instead of the r
   decode_e4m3   llmie_mla_decode_e4m3 on the quantised copy of the cache the fp16 `decode` of the same run reads (dense); their ratio,
             and the HBM bound at ctx * 640 B * batch
 
+With --sparse [--top-k 2048] [--sparse-ctx 8192 32768] [--index-ctx 8192 32768 131072] the sparse decode step follows instead, per
+heads x batch one interleaved run, then per index context x batch:
+  dense_sameK / sparse_sameK   llmie_mla_decode at ctx = top_k beside llmie_mla_decode_sparse over sel = 0 .. top_k - 1: the same rows,
+            so their ratio (gather_over_dense) is the price of the gather
+  dense_ctxC / sparse_ctxC     llmie_mla_decode over a full context C beside llmie_mla_decode_sparse over a random sorted selection of it
+  index_topk   llmie_mla_index_topk (both launches) by device events; kernel_us: each kernel's own time from a profiled pass of the
+            same call; the bound ctx * 256 B * batch / HBM rate of the logits
+
 Prints one JSON line (and writes it to --out): microseconds, and the ratios decode / bound and torch / decode.  Only time is measured."""
 import argparse
 import importlib.util
@@ -228,6 +236,64 @@ def bench_verify(heads, batch, ctx, rows, rounds, reps, with_prefill):
                 rows_x_decode_us=round(rows * t["decode"][0] * 1e6, 1), rows_decode_over_verify=round(rows * t["decode"][0] / t["verify"][0], 2))
 
 
+def bench_sparse(heads, batch, ctxs, top_k, rounds, reps):
+    """llmie_mla_decode_sparse at top_k entries beside llmie_mla_decode, one interleaved run: the identity selection 0 .. top_k - 1 against
+    the dense decode at ctx = top_k (the same rows: the price of the gather), and a random sorted selection out of every full context
+    against the dense decode over that context"""
+    dev, span = "cuda", max(ctxs)
+    cache = torch.empty((1, batch, span, 576), dtype=F16, device=dev).normal_(0, 0.5)
+    q_lat = (torch.randn((batch, heads, 576), device=dev) / 24).to(F16)
+    o_d, o_s = (torch.empty((batch, heads, 512), dtype=F16, device=dev) for _ in range(2))
+    ws_d, ws_s = llmie.mla_workspace(batch, heads, span), llmie.mla_workspace(batch, heads, top_k)
+    count = torch.full((batch,), top_k, dtype=torch.int32, device=dev)
+
+    def arms_at(ctx, sel, tag):
+        lengths = torch.full((batch,), ctx, dtype=torch.int32, device=dev)
+        return {"dense_%s" % tag: lambda: llmie.mla_decode(q_lat, cache, 0, lengths, SCALE, o_d, ws_d, max_ctx=ctx),
+                "sparse_%s" % tag: lambda: llmie.mla_decode_sparse(q_lat, cache, 0, lengths, sel, count, SCALE, o_s, ws_s)}
+
+    arms = arms_at(top_k, torch.arange(top_k, dtype=torch.int32, device=dev).repeat(batch, 1).contiguous(), "same%d" % top_k)
+    for ctx in ctxs:
+        sel = torch.rand((batch, ctx), device=dev).topk(top_k, dim=1).indices.sort(dim=1).values.int().contiguous()
+        arms.update(arms_at(ctx, sel, "ctx%d" % ctx))
+    t = interleaved(arms, rounds, reps)
+    return dict(heads=heads, batch=batch, top_k=top_k, plan=llmie.mla_decode_sparse_plan(batch, heads, top_k, span)[0],
+                us={k: round(v[0] * 1e6, 1) for k, v in t.items()}, spread_us={k: [round(v[1] * 1e6, 1), round(v[2] * 1e6, 1)] for k, v in t.items()},
+                gather_over_dense=round(t["sparse_same%d" % top_k][0] / t["dense_same%d" % top_k][0], 3),
+                dense_over_sparse={str(c): round(t["dense_ctx%d" % c][0] / t["sparse_ctx%d" % c][0], 2) for c in ctxs})
+
+
+def bench_index(batch, ctx, top_k, rounds, reps, hbm_gbs):
+    """llmie_mla_index_topk: the entry (both launches) by device events, then each kernel's own time from a profiled pass of the same call"""
+    from torch.profiler import ProfilerActivity, profile
+    dev = "cuda"
+    k_idx = torch.randn((1, batch, ctx, 128), device=dev, dtype=F16)
+    q_idx = torch.randn((batch, 64, 128), device=dev, dtype=F16)
+    w_idx = torch.randn((batch, 64), device=dev) / 8
+    lengths = torch.full((batch,), ctx, dtype=torch.int32, device=dev)
+    sel, cnt = torch.empty((batch, top_k), dtype=torch.int32, device=dev), torch.empty(batch, dtype=torch.int32, device=dev)
+    ws = llmie.mla_index_workspace(batch, ctx)
+
+    def call():
+        llmie.mla_index_topk(q_idx, w_idx, k_idx, 0, lengths, sel, cnt, ws)
+
+    t = interleaved({"index_topk": call}, rounds, reps)["index_topk"]
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(reps):
+            call()
+        torch.cuda.synchronize()
+    kernels = {}
+    for ev in prof.key_averages():
+        for name in ("mla_index_logits_kernel", "mla_index_select_kernel"):
+            if name in ev.key:
+                total = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0)
+                kernels[name] = round(total / max(ev.count, 1), 1)
+    bound = ctx * 256.0 * batch / (hbm_gbs * 1e9)
+    return dict(batch=batch, ctx=ctx, top_k=top_k, plan=llmie.mla_index_topk_plan(batch, top_k, ctx)[0], us=round(t[0] * 1e6, 1),
+                spread_us=[round(t[1] * 1e6, 1), round(t[2] * 1e6, 1)], kernel_us=kernels or None, hbm_bound_us=round(bound * 1e6, 2),
+                logits_over_bound=round(kernels["mla_index_logits_kernel"] / (bound * 1e6), 2) if "mla_index_logits_kernel" in kernels else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", type=int, nargs="+", default=[16, 128])
@@ -243,11 +309,18 @@ def main():
     ap.add_argument("--verify-prefill", action="store_true", help="add the kv_up + mla_prefill route to the first cell of every row count")
     ap.add_argument("--verify-only", action="store_true", help="skip the decode / chain / torch rows")
     ap.add_argument("--e4m3", action="store_true", help="the e4m3 latent cache: decode_e4m3 beside the fp16 decode, per heads x ctx x batch (these rows only)")
+    ap.add_argument("--sparse", action="store_true", help="the sparse decode step (these rows only): decode_sparse beside decode, and index_topk")
+    ap.add_argument("--top-k", type=int, default=2048)
+    ap.add_argument("--sparse-ctx", type=int, nargs="+", default=[8192, 32768], help="full contexts the sparse decode is compared with")
+    ap.add_argument("--index-ctx", type=int, nargs="*", default=[8192, 32768, 131072], help="contexts of the index_topk rows")
     ap.add_argument("--out")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "mlabench measures on the GPU: there is no CPU path"
     res = dict(tool="mlabench", device=torch.cuda.get_device_name(0), peaks=dict(hbm_GBs_datasheet=a.hbm_gbs, mfma_f16_TFLOPs_datasheet=a.mfma_tflops))
-    if a.e4m3:
+    if a.sparse:
+        res["sparse_rows"] = [bench_sparse(h, b, a.sparse_ctx, a.top_k, a.rounds, a.reps) for h in a.heads for b in a.batches]
+        res["index_rows"] = [bench_index(b, c, a.top_k, a.rounds, a.reps, a.hbm_gbs) for c in a.index_ctx for b in a.batches]
+    elif a.e4m3:
         res["e4m3_rows"] = [bench_e4m3(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
     elif not a.verify_only:
         res["rows"] = [bench(h, b, c, a.rounds, a.reps, a.hbm_gbs, a.mfma_tflops) for h in a.heads for c in a.ctx for b in a.batches]
