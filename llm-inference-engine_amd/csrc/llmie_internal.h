@@ -331,14 +331,17 @@ struct MlaDecodeCall {
     size_t workspace_bytes;
     bool e4m3;                         // the cache rows are LLMIE_MLA_ROW_E4M3_BYTES bytes (mla_e4m3.hip); the split is the same
 };
-struct MlaDecodePlan {
-    int heads, tile, chunk;            // query heads per workgroup, keys per staged tile, tokens per split
+// what the plans of the decode, the sparse decode and verify share (filled by mla_split_plan, mla_common.cuh)
+struct MlaSplitPlan {
+    int heads, tile, chunk;            // query heads per workgroup, rows per staged tile, tokens (sparse: selected entries) per split
+    int grid[3];                       // (splits, head blocks, batch; verify: batch x row blocks)
+    bool merge;                        // more than one split: mla_merge_kernel follows
+    int merge_grid[2], merge_block;    // (head_num, batch; verify: batch x rows)
+    size_t workspace_bytes;            // the split partials (0 with one split)
+};
+struct MlaDecodePlan : MlaSplitPlan {
     int row_bytes;                     // of one cached token
     int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
-    int grid[3];                       // (splits, head blocks, batch)
-    bool merge;                        // more than one split: mla_merge_kernel follows
-    int merge_grid[2], merge_block;
-    size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p);   // sets the refusal's error text, returns its error code
 // what llmie_mla_decode and llmie_mla_decode_e4m3 (c.e4m3) do with their operands: the checks under the entry's name `who`, the plan,
@@ -355,10 +358,12 @@ struct MlaDecodeIo {
 int mla_decode_run(const char *who, const MlaDecodeCall &c, const MlaDecodeIo &io, hipStream_t st);
 // the text of llmie_mla_decode_plan / _e4m3_plan (c.e4m3: with the row size) into the entry's buffer, or null and the refusal
 const char *mla_decode_plan_text(const char *who, const MlaDecodeCall &c, char *text, size_t size, int *status);
-// the merge launch of decode (rows = 0: len_dev = ctx_len, one row per sequence) and verify (len_dev = hist, count_dev or null, rows
-// query-row slots per sequence): all three attention kernels leave their (m, l, o[512]) fp32 partials in the one format it reads
-void mla_merge_launch(const int merge_grid[2], int span, int splits, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *len_dev,
-                      const int32_t *count_dev, int rows, int head_num, hipStream_t st);
+// the merge launch of decode (rows = 0: len_dev = ctx_len, one row per sequence), of the sparse decode (len_dev = sel_count, span =
+// top_k; live_dev = ctx_len and live_span = its bound: an instantiation of its own that leaves a dead context untouched; null
+// elsewhere) and of verify (len_dev = hist, count_dev or null, rows query-row slots per sequence): all attention kernels leave their
+// (m, l, o[512]) fp32 partials in the one format it reads
+void mla_merge_launch(const MlaSplitPlan &p, int span, float *ws_o, half_t *o_lat, const int32_t *len_dev, const int32_t *count_dev, int rows,
+                      const int32_t *live_dev, int live_span, hipStream_t st);
 // the one append launch of the four llmie_mla_kv_append* entries, one wave per token: the single-token form (cum null: token =
 // sequence b, row ctx_len[b] - 1) or the bulk form (packed tokens), into the fp16 cache or, e4m3, quantised by c_scale
 struct MlaAppendCall {
@@ -402,13 +407,7 @@ struct MlaSparseCall {
     bool workspace;
     size_t workspace_bytes;
 };
-struct MlaSparsePlan {
-    int heads, tile, chunk;            // query heads per workgroup, rows per staged tile, selected entries per split
-    int grid[3];                       // (splits of top_k, head blocks, batch)
-    bool merge;                        // more than one split: mla_merge_kernel follows, sel_count is its length array
-    int merge_grid[2], merge_block;
-    size_t workspace_bytes;            // the split partials (0 with one split)
-};
+using MlaSparsePlan = MlaSplitPlan;    // the splits are of top_k; sel_count is the merge's length array
 int plan_mla_decode_sparse(const char *who, const MlaSparseCall &c, MlaSparsePlan *p);   // sets the refusal's error text, returns its error code
 // ---- MLA verify attention (mla_verify.hip): several query rows per sequence on the latent cache; the pattern of plan_mla_decode ----
 struct MlaVerifyCall {
@@ -420,14 +419,10 @@ struct MlaVerifyCall {
     bool workspace;
     size_t workspace_bytes;
 };
-struct MlaVerifyPlan {
-    int heads, rows, tile, chunk;      // MFMA columns per workgroup = heads x rows, keys per staged tile, tokens per split
+struct MlaVerifyPlan : MlaSplitPlan {
+    int rows;                          // query rows per workgroup: MFMA columns = heads x rows
     int span;                          // the contexts the grid covers: max_ctx, or max_seq_len
     int row_blocks;                    // ceil(call rows / rows)
-    int grid[3];                       // (splits, head blocks, batch x row blocks)
-    bool merge;                        // more than one split: mla_merge_kernel follows
-    int merge_grid[2], merge_block;
-    size_t workspace_bytes;            // the split partials (0 with one split)
 };
 int plan_mla_verify(const char *who, const MlaVerifyCall &c, MlaVerifyPlan *p);   // sets the refusal's error text, returns its error code
 // ---- MLA prefill (mla_prefill.hip): bulk append, K/V up-projection, 192/128 flash attention.  One planner for the three entries ----

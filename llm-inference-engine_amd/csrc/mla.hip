@@ -7,7 +7,8 @@
 //   mla_merge_kernel        fixed-order merge of the split partials (only with more than one split)
 //   mla_out_project_kernel  out[b, h] = W_UV[h] o_lat[b, h]                                         (MFMA, operands from registers)
 //
-// mla_decode_kernel.  Grid (splits, head_num / 16, batch), 4 waves.  A workgroup walks one chunk of kMlaChunk tokens of one
+// mla_decode_kernel.  Its tile loop, described here, is mla_split_tiles in mla_tile_loop.cuh, which mla_sparse_attend_kernel
+// (mla_sparse.hip) runs too, over gathered rows.  Grid (splits, head_num / 16, batch), 4 waves.  A workgroup walks one chunk of kMlaChunk tokens of one
 // sequence in tiles of kMlaTile = 32 keys.  A tile (32 rows x 576 halves) goes global -> registers -> LDS once and serves BOTH
 // products from there: all 576 columns are the A operand of S^T = C . Q^T, the first 512 columns are -- read with the transposed
 // LDS read ds_read_b64_tr_b16 -- the A operand of O^T += C^T . P^T.  Rows are padded to 592 halves (1184 bytes = 160 mod 256):
@@ -25,19 +26,13 @@
 // bits do not depend on the batch, its slot or the grid.  Plain softmax: out = sum p v / sum p, no epsilon in the denominator.
 // The append, the decode and the merge kernel are templates that also serve the bulk append (mla_prefill.hip), the e4m3 cache
 // (mla_e4m3.hip) and verify's merge (mla_verify.hip) through mla_append_launch, mla_decode_run and mla_merge_launch.
-#include "mla_common.cuh"
+#include "mla_tile_loop.cuh"
 
-#include <cstdio>
 #include <cstring>
-#include <type_traits>
 
 namespace llmie {
 
 namespace {
-
-static_assert(kMlaTile == 32 && kLatPieces == 32 && kPePieces == 8, "the e4m3 fetch layout: 4 waves x 8 rows, 4 latent + 1 rope piece per lane");
-
-template <bool E4> using cache_elem_t = std::conditional_t<E4, unsigned char, half_t>;   // the e4m3 cache is addressed in bytes
 
 // ---- append: one wave per token.  cum == null: token = sequence b, row ctx_len[b] - 1; else the packed token blockIdx.x of the bulk
 // form.  The row is mla_append_latent || mla_append_rope (mla_common.cuh) for both formats; E4: code = e4m3(fp16 / c_scale),
@@ -170,193 +165,34 @@ __global__ __launch_bounds__(256) void mla_out_project_kernel(const half_t *__re
     }
 }
 
-// ---- the attention, one template over the cache format.  E4 = false: the fp16 cache, the argument list without c_scale.  E4 = true
-// (cache in bytes, layer_off in bytes) differs in three places, each behind `if constexpr`:
-//   fetch    a tile is 32 rows x 640 bytes = 1280 pieces of 16 bytes, 5 per thread (9 in the fp16 form: 20 VGPRs in flight, not 36).
-//            A row is 32 latent pieces + 8 rope pieces, so wave w takes rows 8 w .. 8 w + 7: latent piece i = 0..3 of a lane is row
-//            8 w + 2 i + (lane >> 5), column lane & 31; its rope piece is row 8 w + (lane >> 3), column lane & 7: no division.
-//   publish  every latent piece becomes 16 halves with v_cvt_scalef32_pk_f16_fp8 at scale 1.0 (two codes per instruction): each half
-//            IS the code's value -- every finite e4m3 value, the subnormal codes included, is an fp16 normal --, so no power-of-two
-//            factor rides along and no MFMA operand is subnormal.  The rope piece is stored as it came.
-//   scale    c_scale never touches an fp16 operand.  Wave kk = 0 (dims 0..287) multiplies its logit partial by c_scale; wave
-//            kk = 1 keeps two accumulators -- steps 0..6 are latent dims 288..511, steps 7..8 are k_pe -- and leaves
-//            c_scale * s_lat + s_pe.  o is multiplied by c_scale once, in front of the store. ----
+// ---- the attention: the tile loop is mla_split_tiles (mla_tile_loop.cuh, one template over the cache format and the row source) over
+// the contiguous rows of positions t < ctx.  E4 = false: the fp16 cache, the argument list without c_scale; E4 = true: cache in bytes,
+// layer_off in bytes.  The kernel decides what is its own: whether the sequence is live and which chunk this split walks. ----
 template <bool E4, typename... Scale>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mla_decode_kernel(
     const half_t *__restrict__ q_lat, const cache_elem_t<E4> *__restrict__ cache, half_t *__restrict__ o_lat, float *__restrict__ ws_o,
     float2 *__restrict__ ws_ml, const int32_t *__restrict__ ctx_len, const int32_t *__restrict__ table, int max_pages, size_t layer_off,
     int head_num, int max_seq_len, int max_ctx, float scale2 /* softmax_scale * log2(e) */, const Scale... c_scale /* E4 */) {
-    static_assert(sizeof...(Scale) == (E4 ? 1 : 0), "c_scale");
-    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes (E4: the codes' values || k_pe, in fp16)
-    __shared__ __attribute__((aligned(16))) float Sp[2 * 8 * 16 * 4];                // partial logits [kk][key / 4][head][key % 4]
-    const int split = blockIdx.x, hb = blockIdx.y, b = blockIdx.z, splits = gridDim.x;
-    const int ctx = ctx_len[b];
+    const int b = blockIdx.z, ctx = ctx_len[b];
     if (!mla_live(ctx, max_ctx)) return;
-    const int t_begin = split * kMlaChunk;
+    const int t_begin = blockIdx.x * kMlaChunk;
     if (t_begin >= ctx) return;
-    const int n_tiles = (min(ctx, t_begin + kMlaChunk) - t_begin + kMlaTile - 1) / kMlaTile;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int kh = wave & 1, kk = wave >> 1;
-    const int head = hb * kMlaHeads + r;
-
-    half8_t qf[9];   // Q[head r][288 kk + 32 s + 8 q ..]: the B operand of this wave's 9 steps
-    {
-        const half_t *qp = q_lat + (static_cast<size_t>(b) * head_num + head) * kRow + 288 * kk + 8 * q;
-#pragma unroll
-        for (int s = 0; s < 9; ++s) qf[s] = *reinterpret_cast<const half8_t *>(qp + 32 * s);
-    }
-
-    constexpr int NCH = E4 ? 5 : kMlaTile * kRow / 8 / 256;   // sixteen-byte pieces of a tile per thread (fp16: 9)
-    half8_t treg[NCH];
-    // E4 staging: wave w owns rows 8 w .. 8 w + 7 of a tile
-    const int lrow = 8 * wave + (lane >> 5), lcol = lane & 31;   // latent piece i: row lrow + 2 i, codes 16 lcol ..
-    const int prow = 8 * wave + (lane >> 3), pcol = lane & 7;    // rope piece: halves kLat + 8 pcol ..
-    auto fetch_tile = [&](int t0) {   // global -> registers; one page lookup per tile, wave-uniform
-        const cache_elem_t<E4> *base = cache + layer_off + mla_tile_row0(table, max_pages, b, t0, max_seq_len) * (E4 ? kRowE4 : kRow);
-        const int last = ctx - 1 - t0;   // >= 0; a row past it re-reads it (same tile, same page)
-        if constexpr (E4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) treg[i] = *reinterpret_cast<const half8_t *>(base + min(lrow + 2 * i, last) * kRowE4 + 16 * lcol);
-            treg[4] = *reinterpret_cast<const half8_t *>(base + min(prow, last) * kRowE4 + kLat + 16 * pcol);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-                treg[i] = *reinterpret_cast<const half8_t *>(base + min(row, last) * kRow + ch * 8);
-            }
-        }
-    };
-    auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows (E4: codes to halves)
-        if constexpr (E4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint4_t w = __builtin_bit_cast(uint4_t, treg[i]);
-                half_t *dst = Ts[buf] + (lrow + 2 * i) * kMlaStride + 16 * lcol;
-                *reinterpret_cast<half8_t *>(dst) = e4m3x8_to_f16(w[0], w[1]);
-                *reinterpret_cast<half8_t *>(dst + 8) = e4m3x8_to_f16(w[2], w[3]);
-            }
-            *reinterpret_cast<half8_t *>(Ts[buf] + prow * kMlaStride + kLat + 8 * pcol) = treg[4];
-        } else {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-                *reinterpret_cast<half8_t *>(Ts[buf] + row * kMlaStride + ch * 8) = treg[i];
-            }
-        }
-    };
-
-    floatx4 o[8];   // O^T (E4: in units of c_scale): dims 128 wave + 16 dt + 4 q + e, column = head r
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;   // log2 domain, scale applied; l_run: this lane's 8 of a tile's 32 keys
-
-    fetch_tile(t_begin);
-    publish_tile(0);
-    if (1 < n_tiles) fetch_tile(t_begin + kMlaTile);
-    for (int it = 0; it < n_tiles; ++it) {
-        const int t0 = t_begin + it * kMlaTile;
-        const half_t *Tt = Ts[it & 1];
-        __syncthreads();   // tile `it` published; every wave done with tile it - 1 (the other buffer) and with its logits
-        if (it + 1 < n_tiles) {
-            publish_tile((it + 1) & 1);
-            if (it + 2 < n_tiles) fetch_tile(t0 + 2 * kMlaTile);   // in flight under this iteration's MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- S^T partial: keys 16 kh + r, dims 288 kk .. (E4: c_scale joins in fp32) ----
-        {
-            half8_t kf[9];
-            const half_t *kp = Tt + (16 * kh + r) * kMlaStride + 288 * kk + 8 * q;
-#pragma unroll
-            for (int s = 0; s < 9; ++s) kf[s] = *reinterpret_cast<const half8_t *>(kp + 32 * s);
-            floatx4 sacc = {0.f, 0.f, 0.f, 0.f};   // sacc[e] = S[key 16 kh + 4 q + e][head r]
-#pragma unroll
-            for (int s = 0; s < 7; ++s) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], qf[s], sacc, 0, 0, 0);
-            if constexpr (E4) {
-                const floatx4 s_lat = sacc;
-                floatx4 s_end = kk ? floatx4{0.f, 0.f, 0.f, 0.f} : s_lat;   // kk = 0: latent dims 224..287; kk = 1: k_pe, an accumulator of its own
-                s_end = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[7], qf[7], s_end, 0, 0, 0);
-                s_end = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[8], qf[8], s_end, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    sacc[e] = kk ? __builtin_fmaf(pack_arg<0>(c_scale...), s_lat[e], s_end[e]) : pack_arg<0>(c_scale...) * s_end[e];
-            } else {
-                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[7], qf[7], sacc, 0, 0, 0);
-                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[8], qf[8], sacc, 0, 0, 0);
-            }
-            *reinterpret_cast<floatx4 *>(Sp + (((kk * 8 + 4 * kh + q) * 16 + r) << 2)) = sacc;
-        }
-        __syncthreads();   // both halves of every logit are there
-        float s8[8];       // keys t0 + 16 (j >> 2) + 4 q + (j & 3): the k index 8 q + j of the P^T operand
-        {
-            const floatx4 a0 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + q) * 16 + r) << 2));
-            const floatx4 b0 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + q) * 16 + r) << 2));
-            const floatx4 a1 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + 4 + q) * 16 + r) << 2));
-            const floatx4 b1 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + 4 + q) * 16 + r) << 2));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s8[e] = a0[e] + b0[e], s8[4 + e] = a1[e] + b1[e];
-        }
-        float mloc = -INFINITY;
-        if (t0 + kMlaTile > ctx) {   // wave-uniform: only the context's last tile masks
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int t = t0 + 16 * (j >> 2) + 4 * q + (j & 3);
-                s8[j] = t < ctx ? s8[j] : -INFINITY;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mloc = fmaxf(mloc, s8[j]);
-        mloc = lane_xor_max<16>(lane_xor_max<32>(mloc)) * scale2;   // over the 4 lanes of head r; scale2 > 0; key t0 < ctx: finite
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: 2^(-inf) = 0
-        float lsum = 0.f;
-        half8_t pf;
-        typedef float float2v_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j], scale2, -m_new));
-            const float p1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j + 1], scale2, -m_new));
-            lsum += p0 + p1;
-            const half2_t hh = __builtin_convertvector(float2v_t{p0, p1}, half2_t);
-            pf[j] = hh[0];
-            pf[j + 1] = hh[1];
-        }
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
-        }
-        // ---- O^T += C^T . P^T: A fragment = C[key(q, j)][128 wave + 16 dt + r], gathered down a column by the transposed read ----
-        {
-            const half_t *blk = Tt + (4 * q + (r >> 2)) * kMlaStride + 128 * wave + 4 * (r & 3);
-            fp16x4_t lo[8], hi[8];
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                lo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + dt * 16));
-                hi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * kMlaStride + dt * 16));
-            }
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, Tr8{lo[dt], hi[dt]}), pf, o[dt], 0, 0, 0);
-        }
-    }
-    const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run));
-    if constexpr (E4) {
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) o[dt] *= pack_arg<0>(c_scale...);   // the one place the output meets c_scale
-    }
-    mla_store_split(o, m_run, l, static_cast<size_t>(b) * head_num + head, split, splits, wave, q, o_lat, ws_o, ws_ml);
+    mla_split_tiles<E4>(q_lat, MlaContiguousRows<E4>{cache + layer_off, table, max_pages, b, max_seq_len, t_begin, ctx}, o_lat, ws_o, ws_ml, b,
+                        head_num, t_begin, ctx, scale2, c_scale...);
 }
 
 // merge: 128 threads x 4 dims per (query row, head).  Splits 0 .. ceil(ctx / chunk) - 1 in that order: M = max m_i,
 // w_i = 2^(m_i - M), L = sum w_i l_i, out = (sum w_i o_i) / L.  One partial gives the bits of the one-split launch (w = 1).
-// Decode: grid (head_num, batch), len_dev = ctx_len.  VERIFY: grid (head_num, batch x rows), len_dev = hist, the pack = (count_dev,
-// rows); a partial that saw nothing (m = -inf, l = 0, o = 0) has weight 0, and the split that holds the row's own node is finite, so M is.
+// Decode: grid (head_num, batch), len_dev = ctx_len, no pack.  The sparse decode: len_dev = sel_count, span = top_k, the pack =
+// (ctx_len, its bound max_seq_len), so that a sequence the attention kernel left alone for its dead context is left alone here.
+// VERIFY: grid (head_num, batch x rows), len_dev = hist, the pack = (count_dev, rows); a partial that saw nothing (m = -inf, l = 0,
+// o = 0) has weight 0, and the split that holds the row's own node is finite, so M is.
 template <bool VERIFY, typename... Rows>
 __global__ __launch_bounds__(kMlaMergeBlock) void mla_merge_kernel(const float *__restrict__ ws_o, const float2 *__restrict__ ws_ml,
                                                                    half_t *__restrict__ o_lat, const int32_t *__restrict__ len_dev, int head_num,
-                                                                   int span, int splits, const Rows... vr /* VERIFY: count_dev, rows */) {
-    static_assert(sizeof...(Rows) == (VERIFY ? 2 : 0), "count_dev, rows");
+                                                                   int span, int splits,
+                                                                   const Rows... vr /* VERIFY: count_dev, rows; sparse: live_dev, live_span */) {
+    static_assert(sizeof...(Rows) == 2 || (!VERIFY && sizeof...(Rows) == 0), "count_dev, rows; or live_dev, live_span; or nothing");
     const int h = blockIdx.x, tid = threadIdx.x;
     int row = blockIdx.y, ctx;   // the (sequence, query row) slot, and the context its splits cover
     if constexpr (VERIFY) {
@@ -367,6 +203,9 @@ __global__ __launch_bounds__(kMlaMergeBlock) void mla_merge_kernel(const float *
     } else {
         ctx = len_dev[row];
         if (!mla_live(ctx, span)) return;
+        if constexpr (sizeof...(Rows) == 2) {
+            if (!mla_live(pack_arg<0>(vr...)[row], pack_arg<1>(vr...))) return;
+        }
     }
     const int n = (ctx + kMlaChunk - 1) / kMlaChunk;   // <= splits (ctx <= span)
     const size_t bh = static_cast<size_t>(row) * head_num + h;
@@ -394,17 +233,11 @@ __global__ __launch_bounds__(kMlaMergeBlock) void mla_merge_kernel(const float *
 int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
     int rc = mla_heads_check(who, c.batch, c.head_num);
     if (rc == LLMIE_OK) rc = mla_cache_check(who, c.max_seq_len, c.paged, c.max_pages, c.num_pages);
+    if (rc == LLMIE_OK) rc = mla_max_ctx_check(who, c.max_ctx, c.max_seq_len);
     if (rc != LLMIE_OK) return rc;
-    LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
-                  who, c.max_ctx, c.max_seq_len);
-    p->heads = kMlaHeads, p->tile = kMlaTile, p->chunk = kMlaChunk;
     p->row_bytes = c.e4m3 ? kRowE4 : kRow * static_cast<int>(sizeof(half_t));
     p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
-    p->grid[0] = (p->span + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch;
-    p->merge = p->grid[0] > 1;
-    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch, p->merge_block = kMlaMergeBlock;
-    p->workspace_bytes = p->merge ? static_cast<size_t>(c.batch) * c.head_num * p->grid[0] * (kLat + 2) * sizeof(float) : 0;
-    if (p->workspace_bytes > 0 && (!c.workspace || c.workspace_bytes < p->workspace_bytes)) {
+    if (!mla_split_plan(p, p->span, c.head_num, c.batch, c.batch, c.workspace, c.workspace_bytes)) {
         set_error("%s: workspace of %zu bytes, %d splits of %d tokens need %zu (llmie_mla_decode_workspace_bytes)", who,
                   c.workspace ? c.workspace_bytes : static_cast<size_t>(0), p->grid[0], kMlaChunk, p->workspace_bytes);
         return LLMIE_ERR_WORKSPACE;
@@ -412,10 +245,17 @@ int plan_mla_decode(const char *who, const MlaDecodeCall &c, MlaDecodePlan *p) {
     return LLMIE_OK;
 }
 
-void mla_merge_launch(const int merge_grid[2], int span, int splits, const float *ws_o, const float2 *ws_ml, half_t *o_lat, const int32_t *len_dev,
-                      const int32_t *count_dev, int rows, int head_num, hipStream_t st) {
-    const dim3 grid(merge_grid[0], merge_grid[1]), block(kMlaMergeBlock);
-    if (rows) hipLaunchKernelGGL((mla_merge_kernel<true, const int32_t *, int>), grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits, count_dev, rows);
+void mla_merge_launch(const MlaSplitPlan &p, int span, float *ws_o, half_t *o_lat, const int32_t *len_dev, const int32_t *count_dev, int rows,
+                      const int32_t *live_dev, int live_span, hipStream_t st) {
+    const dim3 grid(p.merge_grid[0], p.merge_grid[1]), block(p.merge_block);
+    const int head_num = p.merge_grid[0], splits = p.grid[0];
+    const float2 *ws_ml = mla_ws_ml(ws_o, p);
+    if (rows)
+        hipLaunchKernelGGL((mla_merge_kernel<true, const int32_t *, int>), grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits, count_dev,
+                           rows);
+    else if (live_dev)
+        hipLaunchKernelGGL((mla_merge_kernel<false, const int32_t *, int>), grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits,
+                           live_dev, live_span);
     else hipLaunchKernelGGL(mla_merge_kernel<false>, grid, block, 0, st, ws_o, ws_ml, o_lat, len_dev, head_num, span, splits);
 }
 
@@ -444,7 +284,7 @@ int mla_decode_run(const char *who, const MlaDecodeCall &c, const MlaDecodeIo &i
     const half_t *q_lat = static_cast<const half_t *>(io.q_lat);
     half_t *o_lat = static_cast<half_t *>(io.o_lat);
     float *ws_o = static_cast<float *>(io.workspace);
-    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(c.batch) * c.head_num * p.grid[0] * kLat) : nullptr;
+    float2 *ws_ml = mla_ws_ml(ws_o, p);
     const size_t layer_off = mla_layer_off(io.layer, c.batch, c.max_seq_len, c.paged, c.num_pages, c.e4m3 ? kRowE4 : kRow);
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
     if (c.e4m3)
@@ -453,7 +293,7 @@ int mla_decode_run(const char *who, const MlaDecodeCall &c, const MlaDecodeIo &i
     else
         hipLaunchKernelGGL(mla_decode_kernel<false>, grid, dim3(256), 0, st, q_lat, static_cast<const half_t *>(io.cache), o_lat, ws_o, ws_ml, io.ctx_len,
                            io.block_table, c.max_pages, layer_off, c.head_num, c.max_seq_len, p.span, io.softmax_scale * kLog2e);
-    if (p.merge) mla_merge_launch(p.merge_grid, p.span, p.grid[0], ws_o, ws_ml, o_lat, io.ctx_len, nullptr, 0, c.head_num, st);
+    if (p.merge) mla_merge_launch(p, p.span, ws_o, o_lat, io.ctx_len, nullptr, 0, nullptr, 0, st);
     return launch_status(who);
 }
 
@@ -464,9 +304,8 @@ const char *mla_decode_plan_text(const char *who, const MlaDecodeCall &c, char *
     if (rc != LLMIE_OK) return nullptr;
     int n = snprintf(text, size, "mla %s nh%d hb%d tile%d chunk%d ", c.e4m3 ? "e4m3" : "f16", c.head_num, p.heads, p.tile, p.chunk);
     if (c.e4m3) n += snprintf(text + n, size - n, "row%d ", p.row_bytes);
-    n += snprintf(text + n, size - n, "grid %dx%dx%d merge ", p.grid[0], p.grid[1], p.grid[2]);
-    if (p.merge) snprintf(text + n, size - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
-    else snprintf(text + n, size - n, "none");
+    n += snprintf(text + n, size - n, "grid %dx%dx%d ", p.grid[0], p.grid[1], p.grid[2]);
+    mla_merge_text(text + n, size - n, p);
     return text;
 }
 
@@ -475,8 +314,8 @@ const char *mla_decode_plan_text(const char *who, const MlaDecodeCall &c, char *
 using namespace llmie;
 
 extern "C" size_t llmie_mla_decode_workspace_bytes(int batch, int head_num, int max_seq_len) {
-    if (batch < 1 || head_num < 1 || max_seq_len <= kMlaChunk) return 0;
-    return static_cast<size_t>(batch) * head_num * ((max_seq_len + kMlaChunk - 1) / kMlaChunk) * (kLat + 2) * sizeof(float);
+    if (batch < 1 || head_num < 1 || max_seq_len < 1) return 0;
+    return mla_partials_bytes(batch, head_num, mla_splits(max_seq_len));
 }
 
 extern "C" const char *llmie_mla_decode_plan(int batch, int head_num, int max_seq_len, int max_ctx, int paged, int max_pages, int num_pages,

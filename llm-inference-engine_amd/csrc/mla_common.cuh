@@ -1,10 +1,13 @@
-// What the four MLA translation units (mla.hip: the decode step, both cache formats, and the one append; mla_prefill.hip: the prompt;
-// mla_verify.hip: several query rows; mla_e4m3.hip: the e4m3 cache's entries and its dequant) share: the fixed geometry, where a latent
-// cache row lives, the append's row arithmetic, the split partial's store, and the host checks every entry makes.
+// What the five MLA translation units (mla.hip: the decode step, both cache formats, and the one append; mla_prefill.hip: the prompt;
+// mla_verify.hip: several query rows; mla_e4m3.hip: the e4m3 cache's entries and its dequant; mla_sparse.hip: the indexer and the
+// decode over a selection) share: the fixed geometry, where a latent cache row lives, the append's row arithmetic, the split partial's
+// store, the host checks every entry makes and the host split plan.  The split-KV tile loop itself, which mla.hip and mla_sparse.hip
+// alone run, is in mla_tile_loop.cuh.
 #pragma once
 #include "llmie_internal.h"
 
 #include <cmath>
+#include <cstdio>
 
 namespace llmie {
 
@@ -145,6 +148,47 @@ inline int mla_cache_check(const char *who, int max_seq_len, bool paged, int max
                       who, max_pages, kPage, max_seq_len);
     }
     return LLMIE_OK;
+}
+
+inline int mla_max_ctx_check(const char *who, int max_ctx, int max_seq_len) {
+    LLMIE_REQUIRE(max_ctx >= 0 && max_ctx <= max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]", who,
+                  max_ctx, max_seq_len);
+    return LLMIE_OK;
+}
+
+inline int mla_top_k_check(const char *who, int top_k) {
+    LLMIE_REQUIRE(top_k >= 1 && top_k <= LLMIE_MLA_SPARSE_MAX_TOPK, "%s: top_k=%d should be in [1, %d]", who, top_k, LLMIE_MLA_SPARSE_MAX_TOPK);
+    return LLMIE_OK;
+}
+
+// ---- the split plan the decode, the sparse decode and verify share (MlaSplitPlan, llmie_internal.h) ----
+inline int mla_splits(int units) { return (units + kMlaChunk - 1) / kMlaChunk; }   // units: a context span, or top_k
+
+// the partials of `slots` (sequence, query row) slots: per head and split o[512] in fp32, then (m, l); nothing with one split
+inline size_t mla_partials_bytes(size_t slots, int head_num, int splits) {
+    return splits > 1 ? slots * head_num * splits * (kLat + 2) * sizeof(float) : 0;
+}
+
+// fills the plan: `units` in chunks of kMlaChunk, one merge row per slot, grid z as given; false where the caller's workspace does
+// not hold the partials (the caller words the refusal)
+inline bool mla_split_plan(MlaSplitPlan *p, int units, int head_num, int slots, int grid_z, bool workspace, size_t workspace_bytes) {
+    p->heads = kMlaHeads, p->tile = kMlaTile, p->chunk = kMlaChunk;
+    p->grid[0] = mla_splits(units), p->grid[1] = head_num / kMlaHeads, p->grid[2] = grid_z;
+    p->merge = p->grid[0] > 1;
+    p->merge_grid[0] = head_num, p->merge_grid[1] = slots, p->merge_block = kMlaMergeBlock;
+    p->workspace_bytes = mla_partials_bytes(slots, head_num, p->grid[0]);
+    return p->workspace_bytes == 0 || (workspace && workspace_bytes >= p->workspace_bytes);
+}
+
+// the (m, l) pairs lie behind the slots x head_num x splits partial outputs; null with one split
+inline float2 *mla_ws_ml(float *ws_o, const MlaSplitPlan &p) {
+    return p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(p.merge_grid[1]) * p.merge_grid[0] * p.grid[0] * kLat) : nullptr;
+}
+
+// the tail of the three plan texts: "merge 16x2/128", or "merge none"
+inline void mla_merge_text(char *text, size_t size, const MlaSplitPlan &p) {
+    if (p.merge) snprintf(text, size, "merge %dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
+    else snprintf(text, size, "merge none");
 }
 
 // where a layer begins, in units of row's: row = kRow (halves) or kRowE4 (bytes)

@@ -4,7 +4,7 @@
 //   mla_index_logits_kernel   I_t of every position t < ctx into an fp32 workspace row                (MFMA, no LDS, HBM-bound)
 //   mla_index_select_kernel   exact top_k of a row: radix select, then one ordered compaction          (one workgroup per sequence)
 //   mla_sparse_attend_kernel  the split-KV flash decode of mla_decode_kernel over sel[b, 0 .. count)    (MFMA, the hot path)
-// and the merge is mla.hip's (mla_merge_launch, with sel_count as the length array).
+// and the merge is mla.hip's (mla_merge_launch, with sel_count as the length array and ctx_len for the liveness).
 //
 // mla_index_logits_kernel.  Grid (ceil(span / 64), batch), 4 waves of 16 keys.  The key rows are the A operand straight from global
 // memory -- lane (r, q) reads row r at halves 32 s + 8 q .. for the 4 steps --, q_idx[b] is the B operand: 16 fragments (4 head blocks
@@ -20,17 +20,15 @@
 // admit.  One more pass emits, in ascending position, every key > T and the first `need` keys = T: a workgroup prefix scan of the packed
 // pair (count of keys > T, count of keys = T) over 4096 positions at a time.  No global atomics, plain stores.
 //
-// mla_sparse_attend_kernel.  Grid (ceil(top_k / 256), head_num / 16, batch): the work split, the LDS tile layout, the staging (two
-// buffers, the next-but-one tile in flight in registers), the softmax and the partial format are mla_decode_kernel's (mla.hip says how
-// they work), over entries j < count = min(sel_count[b], top_k) instead of positions t < ctx.  What is new is the row locate: the 32
+// mla_sparse_attend_kernel.  Grid (ceil(top_k / 256), head_num / 16, batch): the kernel runs the tile loop of mla_decode_kernel, the
+// one text of it (mla_split_tiles in mla_tile_loop.cuh; mla.hip says how it works), with the gathered row source, over entries
+// j < count = min(sel_count[b], top_k) instead of positions t < ctx.  What is the kernel's own is the row locate: the 32
 // rows of a staged tile no longer share a base, so at its start a workgroup resolves its chunk's up to 256 row numbers inside the layer
 // ONCE, into 1 KB of LDS (one sel read and one block-table read per row), and the tile loop's fetch has one LDS read in front of each
 // 16-byte global load, no dependent sel -> table -> row chain.  Every position is clamped into [0, ctx - 1]: a negative entry or one
 // >= ctx inside count is the caller's error, it attends the clamped row and nothing faults.  Entries at or past count re-read entry
 // count - 1 and are masked to -inf in the last tile only.  With sel = 0 .. ctx - 1 the result has the bits of llmie_mla_decode.
-#include "mla_common.cuh"
-
-#include <cstdio>
+#include "mla_tile_loop.cuh"
 
 namespace llmie {
 
@@ -202,150 +200,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
     float2 *__restrict__ ws_ml, const int32_t *__restrict__ sel, const int32_t *__restrict__ sel_count, const int32_t *__restrict__ ctx_len,
     const int32_t *__restrict__ table, int max_pages, size_t layer_off, int head_num, int top_k, int max_seq_len,
     float scale2 /* softmax_scale * log2(e) */) {
-    __shared__ __attribute__((aligned(16))) half_t Ts[2][kMlaTile * kMlaStride];   // 2 x 37888 bytes
-    __shared__ __attribute__((aligned(16))) float Sp[2 * 8 * 16 * 4];                // partial logits [kk][key / 4][head][key % 4]
-    __shared__ int Rw[kMlaChunk];                                                    // the chunk's row numbers inside the layer
-    const int split = blockIdx.x, hb = blockIdx.y, b = blockIdx.z, splits = gridDim.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int kh = wave & 1, kk = wave >> 1;
-    const int head = hb * kMlaHeads + r;
-    const size_t bh = static_cast<size_t>(b) * head_num + head;
+    __shared__ int Rw[kMlaChunk];   // the chunk's row numbers inside the layer
+    const int b = blockIdx.z, tid = threadIdx.x;
     const int ctx = ctx_len[b], count = min(sel_count[b], top_k);
-    const int j_begin = split * kMlaChunk;
-    if (!mla_live(ctx, max_seq_len)) {
-        // a dead context leaves o_lat as it is, but the merge launch knows sel_count alone and merges the splits of such a sequence
-        // all the same: give it partials whose merge is the row's own bits -- split 0 holds (m, l, o) = (0, 1, o_lat), the others nothing
-        if (splits > 1 && j_begin < count) {
-            float *op = ws_o + (bh * splits + split) * kLat + 128 * wave + 4 * q;
-            const half_t *keep = o_lat + bh * kLat + 128 * wave + 4 * q;
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                const half4_t h = *reinterpret_cast<const half4_t *>(keep + 16 * dt);
-                *reinterpret_cast<floatx4 *>(op + 16 * dt) = split ? floatx4{0.f, 0.f, 0.f, 0.f} : floatx4{to_f32(h[0]), to_f32(h[1]), to_f32(h[2]), to_f32(h[3])};
-            }
-            if (wave == 0 && q == 0) ws_ml[bh * splits + split] = split ? make_float2(-INFINITY, 0.f) : make_float2(0.f, 1.f);
-        }
-        return;
-    }
-    if (j_begin >= count) return;   // count < 1 included
-    const int n_tiles = (min(count, j_begin + kMlaChunk) - j_begin + kMlaTile - 1) / kMlaTile;
-
+    const int j_begin = blockIdx.x * kMlaChunk;
+    // a dead context (the merge launch tests the same: nothing writes the row), or nothing to do (count < 1 included); one test
+    // (`|`): both lengths are loaded side by side
+    if (!mla_live(ctx, max_seq_len) | (j_begin >= count)) return;
     {   // locate: entry j_begin + tid, one past the last re-reads the last; the position is clamped into the sequence
         const int pos = min(max(sel[static_cast<size_t>(b) * top_k + min(j_begin + tid, count - 1)], 0), ctx - 1);
         Rw[tid] = table ? table[static_cast<size_t>(b) * max_pages + pos / kPage] * kPage + pos % kPage : b * max_seq_len + pos;
     }
-
-    half8_t qf[9];   // Q[head r][288 kk + 32 s + 8 q ..]: the B operand of this wave's 9 steps
-    {
-        const half_t *qp = q_lat + bh * kRow + 288 * kk + 8 * q;
-#pragma unroll
-        for (int s = 0; s < 9; ++s) qf[s] = *reinterpret_cast<const half8_t *>(qp + 32 * s);
-    }
-
-    constexpr int NCH = kMlaTile * kRow / 8 / 256;   // sixteen-byte pieces of a tile per thread: 9
-    half8_t treg[NCH];
-    const half_t *layer = cache + layer_off;
-    auto fetch_tile = [&](int it) {   // global -> registers: tile `it` of the chunk, every piece behind one LDS read of its row number
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-            treg[i] = *reinterpret_cast<const half8_t *>(layer + static_cast<size_t>(Rw[it * kMlaTile + row]) * kRow + ch * 8);
-        }
-    };
-    auto publish_tile = [&](int buf) {   // registers -> LDS, padded rows
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int id = tid + 256 * i, row = id / (kRow / 8), ch = id - row * (kRow / 8);
-            *reinterpret_cast<half8_t *>(Ts[buf] + row * kMlaStride + ch * 8) = treg[i];
-        }
-    };
-
-    floatx4 o[8];   // O^T: dims 128 wave + 16 dt + 4 q + e, column = head r
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;   // log2 domain, scale applied; l_run: this lane's 8 of a tile's 32 keys
-
-    __syncthreads();   // the row numbers are there
-    fetch_tile(0);
-    publish_tile(0);
-    if (1 < n_tiles) fetch_tile(1);
-    for (int it = 0; it < n_tiles; ++it) {
-        const int j0 = j_begin + it * kMlaTile;
-        const half_t *Tt = Ts[it & 1];
-        __syncthreads();   // tile `it` published; every wave done with tile it - 1 (the other buffer) and with its logits
-        if (it + 1 < n_tiles) {
-            publish_tile((it + 1) & 1);
-            if (it + 2 < n_tiles) fetch_tile(it + 2);   // in flight under this iteration's MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- S^T partial: keys 16 kh + r, dims 288 kk .. ----
-        {
-            half8_t kf[9];
-            const half_t *kp = Tt + (16 * kh + r) * kMlaStride + 288 * kk + 8 * q;
-#pragma unroll
-            for (int s = 0; s < 9; ++s) kf[s] = *reinterpret_cast<const half8_t *>(kp + 32 * s);
-            floatx4 sacc = {0.f, 0.f, 0.f, 0.f};   // sacc[e] = S[key 16 kh + 4 q + e][head r]
-#pragma unroll
-            for (int s = 0; s < 9; ++s) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], qf[s], sacc, 0, 0, 0);
-            *reinterpret_cast<floatx4 *>(Sp + (((kk * 8 + 4 * kh + q) * 16 + r) << 2)) = sacc;
-        }
-        __syncthreads();   // both halves of every logit are there
-        float s8[8];       // entries j0 + 16 (j >> 2) + 4 q + (j & 3): the k index 8 q + j of the P^T operand
-        {
-            const floatx4 a0 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + q) * 16 + r) << 2));
-            const floatx4 b0 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + q) * 16 + r) << 2));
-            const floatx4 a1 = *reinterpret_cast<const floatx4 *>(Sp + (((0 * 8 + 4 + q) * 16 + r) << 2));
-            const floatx4 b1 = *reinterpret_cast<const floatx4 *>(Sp + (((1 * 8 + 4 + q) * 16 + r) << 2));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s8[e] = a0[e] + b0[e], s8[4 + e] = a1[e] + b1[e];
-        }
-        float mloc = -INFINITY;
-        if (j0 + kMlaTile > count) {   // wave-uniform: only the selection's last tile masks
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int jj = j0 + 16 * (j >> 2) + 4 * q + (j & 3);
-                s8[j] = jj < count ? s8[j] : -INFINITY;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mloc = fmaxf(mloc, s8[j]);
-        mloc = lane_xor_max<16>(lane_xor_max<32>(mloc)) * scale2;   // over the 4 lanes of head r; scale2 > 0; entry j0 < count: finite
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: 2^(-inf) = 0
-        float lsum = 0.f;
-        half8_t pf;
-        typedef float float2v_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j], scale2, -m_new));
-            const float p1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8[j + 1], scale2, -m_new));
-            lsum += p0 + p1;
-            const half2_t hh = __builtin_convertvector(float2v_t{p0, p1}, half2_t);
-            pf[j] = hh[0];
-            pf[j + 1] = hh[1];
-        }
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
-        }
-        // ---- O^T += C^T . P^T: A fragment = C[key(q, j)][128 wave + 16 dt + r], gathered down a column by the transposed read ----
-        {
-            const half_t *blk = Tt + (4 * q + (r >> 2)) * kMlaStride + 128 * wave + 4 * (r & 3);
-            fp16x4_t lo[8], hi[8];
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                lo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + dt * 16));
-                hi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4_ptr)(blk + 16 * kMlaStride + dt * 16));
-            }
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, Tr8{lo[dt], hi[dt]}), pf, o[dt], 0, 0, 0);
-        }
-    }
-    const float l = lane_xor_sum<32>(lane_xor_sum<16>(l_run));
-    mla_store_split(o, m_run, l, bh, split, splits, wave, q, o_lat, ws_o, ws_ml);
+    // (the barrier behind these writes is MlaGatheredRows::ready(), behind the loop's q loads)
+    mla_split_tiles<false>(q_lat, MlaGatheredRows{cache + layer_off, Rw}, o_lat, ws_o, ws_ml, b, head_num, j_begin, count, scale2);
 }
 
 size_t index_pitch(int span) { return (static_cast<size_t>(span) + kIdxPad - 1) / kIdxPad * kIdxPad; }
@@ -355,11 +222,10 @@ size_t index_pitch(int span) { return (static_cast<size_t>(span) + kIdxPad - 1) 
 // The one planner of llmie_mla_index_topk: every check that needs no pointer, then the two launches.  Pure host code.
 int plan_mla_index_topk(const char *who, const MlaIndexCall &c, MlaIndexPlan *p) {
     LLMIE_REQUIRE(c.batch >= 1 && c.batch <= 65535, "%s: batch=%d should be in [1, 65535]", who, c.batch);
-    LLMIE_REQUIRE(c.top_k >= 1 && c.top_k <= LLMIE_MLA_SPARSE_MAX_TOPK, "%s: top_k=%d should be in [1, %d]", who, c.top_k, LLMIE_MLA_SPARSE_MAX_TOPK);
-    const int rc = mla_cache_check(who, c.max_seq_len, c.paged, c.max_pages, c.num_pages);
+    int rc = mla_top_k_check(who, c.top_k);
+    if (rc == LLMIE_OK) rc = mla_cache_check(who, c.max_seq_len, c.paged, c.max_pages, c.num_pages);
+    if (rc == LLMIE_OK) rc = mla_max_ctx_check(who, c.max_ctx, c.max_seq_len);
     if (rc != LLMIE_OK) return rc;
-    LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
-                  who, c.max_ctx, c.max_seq_len);
     p->keys = kIdxKeys;
     p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
     p->pitch = index_pitch(p->span);
@@ -381,15 +247,11 @@ int plan_mla_decode_sparse(const char *who, const MlaSparseCall &c, MlaSparsePla
     if (rc == LLMIE_OK) rc = mla_cache_check(who, c.max_seq_len, c.paged, c.max_pages, c.num_pages);
     if (rc != LLMIE_OK) return rc;
     LLMIE_REQUIRE(c.batch <= 65535, "%s: batch=%d should be <= 65535", who, c.batch);
-    LLMIE_REQUIRE(c.top_k >= 1 && c.top_k <= LLMIE_MLA_SPARSE_MAX_TOPK, "%s: top_k=%d should be in [1, %d]", who, c.top_k, LLMIE_MLA_SPARSE_MAX_TOPK);
+    rc = mla_top_k_check(who, c.top_k);
+    if (rc != LLMIE_OK) return rc;
     const long long rows = c.paged ? static_cast<long long>(c.num_pages) * kPage : static_cast<long long>(c.batch) * c.max_seq_len;
     if (rows > 2147483647LL) LLMIE_UNSUPPORTED("%s: a layer of %lld cache rows: the row numbers of a selection are 32 bits, at most 2^31 - 1 rows", who, rows);
-    p->heads = kMlaHeads, p->tile = kMlaTile, p->chunk = kMlaChunk;
-    p->grid[0] = (c.top_k + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch;
-    p->merge = p->grid[0] > 1;
-    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch, p->merge_block = kMlaMergeBlock;
-    p->workspace_bytes = p->merge ? static_cast<size_t>(c.batch) * c.head_num * p->grid[0] * (kLat + 2) * sizeof(float) : 0;
-    if (p->workspace_bytes > 0 && (!c.workspace || c.workspace_bytes < p->workspace_bytes)) {
+    if (!mla_split_plan(p, c.top_k, c.head_num, c.batch, c.batch, c.workspace, c.workspace_bytes)) {
         set_error("%s: workspace of %zu bytes, %d splits of %d entries need %zu (llmie_mla_decode_workspace_bytes with top_k)", who,
                   c.workspace ? c.workspace_bytes : static_cast<size_t>(0), p->grid[0], kMlaChunk, p->workspace_bytes);
         return LLMIE_ERR_WORKSPACE;
@@ -455,10 +317,9 @@ extern "C" const char *llmie_mla_decode_sparse_plan(int batch, int head_num, int
     const int rc = plan_mla_decode_sparse("mla_decode_sparse_plan", c, &p);
     if (status) *status = rc;
     if (rc != LLMIE_OK) return nullptr;
-    int n = snprintf(text, sizeof(text), "mla_sparse f16 nh%d hb%d tile%d chunk%d topk%d grid %dx%dx%d merge ", head_num, p.heads, p.tile, p.chunk,
-                     top_k, p.grid[0], p.grid[1], p.grid[2]);
-    if (p.merge) snprintf(text + n, sizeof(text) - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
-    else snprintf(text + n, sizeof(text) - n, "none");
+    const int n = snprintf(text, sizeof(text), "mla_sparse f16 nh%d hb%d tile%d chunk%d topk%d grid %dx%dx%d ", head_num, p.heads, p.tile, p.chunk,
+                           top_k, p.grid[0], p.grid[1], p.grid[2]);
+    mla_merge_text(text + n, sizeof(text) - n, p);
     return text;
 }
 
@@ -478,11 +339,11 @@ extern "C" int llmie_mla_decode_sparse(const void *q_lat, const void *cache, voi
                   "mla_decode_sparse: q_lat, the cache, o_lat and the workspace should be 16-byte aligned");
     half_t *out = static_cast<half_t *>(o_lat);
     float *ws_o = static_cast<float *>(workspace);
-    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(batch) * head_num * p.grid[0] * kLat) : nullptr;
+    float2 *ws_ml = mla_ws_ml(ws_o, p);
     const hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(mla_sparse_attend_kernel, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, st, static_cast<const half_t *>(q_lat),
                        static_cast<const half_t *>(cache), out, ws_o, ws_ml, sel, sel_count, ctx_len_dev, block_table, max_pages,
                        mla_layer_off(layer, batch, max_seq_len, paged, num_pages, kRow), head_num, top_k, max_seq_len, softmax_scale * kLog2e);
-    if (p.merge) mla_merge_launch(p.merge_grid, top_k, p.grid[0], ws_o, ws_ml, out, sel_count, nullptr, 0, head_num, st);
+    if (p.merge) mla_merge_launch(p, top_k, ws_o, out, sel_count, nullptr, 0, ctx_len_dev, max_seq_len, st);
     return launch_status("mla_decode_sparse");
 }

@@ -217,11 +217,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
-size_t verify_workspace(int batch, int rows, int head_num, int span) {
-    const int splits = (span + kMlaChunk - 1) / kMlaChunk;
-    return splits > 1 ? static_cast<size_t>(batch) * rows * head_num * splits * (kLat + 2) * sizeof(float) : 0;
-}
-
 }  // namespace
 
 // The one planner of llmie_mla_verify: every check that needs no pointer, then the launch.  Pure host code.
@@ -233,18 +228,14 @@ int plan_mla_verify(const char *who, const MlaVerifyCall &c, MlaVerifyPlan *p) {
     if (c.rows > LLMIE_SPEC_TREE_MAX_NODES)
         LLMIE_UNSUPPORTED("%s: rows=%d: at most LLMIE_SPEC_TREE_MAX_NODES=%d query rows per sequence (one 64-bit ancestor mask per row)", who, c.rows,
                           LLMIE_SPEC_TREE_MAX_NODES);
-    LLMIE_REQUIRE(c.max_ctx >= 0 && c.max_ctx <= c.max_seq_len, "%s: max_ctx=%d should be 0 (lengths known to the device only) or in [1, max_seq_len=%d]",
-                  who, c.max_ctx, c.max_seq_len);
-    p->heads = kMlaHeads, p->rows = kVerRows, p->tile = kMlaTile, p->chunk = kMlaChunk;
+    rc = mla_max_ctx_check(who, c.max_ctx, c.max_seq_len);
+    if (rc != LLMIE_OK) return rc;
+    p->rows = kVerRows;
     p->span = c.max_ctx > 0 ? c.max_ctx : c.max_seq_len;
     p->row_blocks = (c.rows + kVerRows - 1) / kVerRows;
     LLMIE_REQUIRE(static_cast<long long>(c.batch) * p->row_blocks <= 65535 && static_cast<long long>(c.batch) * c.rows <= 65535,
                   "%s: batch=%d x rows=%d does not fit one launch (batch x rows <= 65535)", who, c.batch, c.rows);
-    p->grid[0] = (p->span + kMlaChunk - 1) / kMlaChunk, p->grid[1] = c.head_num / kMlaHeads, p->grid[2] = c.batch * p->row_blocks;
-    p->merge = p->grid[0] > 1;
-    p->merge_grid[0] = c.head_num, p->merge_grid[1] = c.batch * c.rows, p->merge_block = kMlaMergeBlock;
-    p->workspace_bytes = verify_workspace(c.batch, c.rows, c.head_num, p->span);
-    if (p->workspace_bytes > 0 && (!c.workspace || c.workspace_bytes < p->workspace_bytes)) {
+    if (!mla_split_plan(p, p->span, c.head_num, c.batch * c.rows, c.batch * p->row_blocks, c.workspace, c.workspace_bytes)) {
         set_error("%s: workspace of %zu bytes, %d rows x %d splits of %d tokens need %zu (llmie_mla_verify_workspace_bytes)", who,
                   c.workspace ? c.workspace_bytes : static_cast<size_t>(0), c.rows, p->grid[0], kMlaChunk, p->workspace_bytes);
         return LLMIE_ERR_WORKSPACE;
@@ -258,7 +249,7 @@ using namespace llmie;
 
 extern "C" size_t llmie_mla_verify_workspace_bytes(int batch, int rows, int head_num, int max_seq_len) {
     if (batch < 1 || rows < 1 || head_num < 1 || max_seq_len < 1) return 0;
-    return verify_workspace(batch, rows, head_num, max_seq_len);
+    return mla_partials_bytes(static_cast<size_t>(batch) * rows, head_num, mla_splits(max_seq_len));
 }
 
 extern "C" const char *llmie_mla_verify_plan(int batch, int rows, int head_num, int max_seq_len, int max_ctx, int tree, int paged, int max_pages,
@@ -270,10 +261,9 @@ extern "C" const char *llmie_mla_verify_plan(int batch, int rows, int head_num, 
     const int rc = plan_mla_verify("mla_verify_plan", c, &p);
     if (status) *status = rc;
     if (rc != LLMIE_OK) return nullptr;
-    int n = snprintf(text, sizeof(text), "mla_verify f16 nh%d rows%d %s cols %dx%d tile%d chunk%d grid %dx%dx%d merge ", head_num, rows,
-                     c.tree ? "tree" : "chain", p.heads, p.rows, p.tile, p.chunk, p.grid[0], p.grid[1], p.grid[2]);
-    if (p.merge) snprintf(text + n, sizeof(text) - n, "%dx%d/%d", p.merge_grid[0], p.merge_grid[1], p.merge_block);
-    else snprintf(text + n, sizeof(text) - n, "none");
+    const int n = snprintf(text, sizeof(text), "mla_verify f16 nh%d rows%d %s cols %dx%d tile%d chunk%d grid %dx%dx%d ", head_num, rows,
+                           c.tree ? "tree" : "chain", p.heads, p.rows, p.tile, p.chunk, p.grid[0], p.grid[1], p.grid[2]);
+    mla_merge_text(text + n, sizeof(text) - n, p);
     return text;
 }
 
@@ -292,12 +282,11 @@ extern "C" int llmie_mla_verify(const void *q_lat, const void *cache, void *o_la
     LLMIE_REQUIRE(mis16(q_lat) == 0 && mis16(cache) == 0 && mis16(o_lat) == 0 && (!p.merge || mis16(workspace) == 0),
                   "mla_verify: q_lat, the cache, o_lat and the workspace should be 16-byte aligned");
     float *ws_o = static_cast<float *>(workspace);
-    float2 *ws_ml = p.merge ? reinterpret_cast<float2 *>(ws_o + static_cast<size_t>(batch) * rows * head_num * p.grid[0] * kLat) : nullptr;
+    float2 *ws_ml = mla_ws_ml(ws_o, p);
     hipLaunchKernelGGL(mla_verify_kernel, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, as_stream(stream),
                        static_cast<const half_t *>(q_lat), static_cast<const half_t *>(cache), static_cast<half_t *>(o_lat), ws_o, ws_ml, hist_dev,
                        count_dev, anc_dev, block_table, max_pages, mla_layer_off(layer, batch, max_seq_len, block_table != nullptr, num_pages, kRow), rows,
                        p.row_blocks, head_num, max_seq_len, p.span, softmax_scale * kLog2e);
-    if (p.merge)
-        mla_merge_launch(p.merge_grid, p.span, p.grid[0], ws_o, ws_ml, static_cast<half_t *>(o_lat), hist_dev, count_dev, rows, head_num, as_stream(stream));
+    if (p.merge) mla_merge_launch(p, p.span, ws_o, static_cast<half_t *>(o_lat), hist_dev, count_dev, rows, nullptr, 0, as_stream(stream));
     return launch_status("mla_verify");
 }

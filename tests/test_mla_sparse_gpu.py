@@ -166,14 +166,15 @@ def test_the_whole_context_gives_the_bits_of_mla_decode(lib, ctx, use_pages):
 
 
 def test_ragged_batch_dead_rows_and_bad_entries(lib):
-    """counts (300, 0, 33, 280, 40): row 1 (count 0) and row 3 (a dead context) stay untouched; row 4 holds -1 and ctx + 5 inside its
-    count and attends the clamped rows; the live rows have the bits of their batch-1 calls"""
-    q_lat, cache = attend_case(16, B=5)
-    ctxs, counts, sel = (700, 650, 40, 0, 500), (300, 0, 33, 280, 40), subsets(5, 5, 700, 300)
+    """counts (300, 0, 33, 280, 40, 290): row 1 (count 0), row 3 (a dead context: 0) and row 5 (a dead context: past max_seq_len = 768)
+    stay untouched, the dead ones under counts that reach the second split, so the merge runs for them; row 4 holds -1 and ctx + 5
+    inside its count and attends the clamped rows; the live rows have the bits of their batch-1 calls"""
+    q_lat, cache = attend_case(16, B=6)
+    ctxs, counts, sel = (700, 650, 40, 0, 500, 800), (300, 0, 33, 280, 40, 290), subsets(5, 6, 700, 300)
     sel[2, :33], sel[4, :40] = subsets(6, 1, 40, 33, 33)[0], subsets(7, 1, 500, 40, 40)[0]
     sel[4, 0], sel[4, 39] = -1, 505
-    o_lat = run_sparse(lib, q_lat, cache, ctxs, sel, counts, True, keep=(1, 3))[0]
-    assert (o_lat[1] == SENTINEL).all() and (o_lat[3] == SENTINEL).all()
+    o_lat = run_sparse(lib, q_lat, cache, ctxs, sel, counts, True, keep=(1, 3, 5))[0]
+    assert (o_lat[1] == SENTINEL).all() and (o_lat[3] == SENTINEL).all() and (o_lat[5] == SENTINEL).all()
     for b in (0, 2, 4):
         alone = run_sparse(lib, q_lat[b:b + 1], cache[:, b:b + 1], ctxs[b:b + 1], sel[b:b + 1], counts[b:b + 1], False)[0]
         assert torch.equal(alone[0], o_lat[b])
